@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the coarse-grained reverse-diffusion sampler on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch: draw z_T, 1000 posterior steps (1000 EGNN
 dynamics forwards + posterior updates), one more forward + the final decode, results copied to the
@@ -11,14 +11,19 @@ production model H=256, L=6 (endiffusion/conf/model/ddpmgblur.yaml).  Synthetic 
 point sets, counter-based Gaussian noise) and deterministic random-init weights: the reference ships no
 checkpoint and there is no network.
 
-The JSON line's headline (`value`, `dtype`, `roofline`) is the EXACT-fp32 path (v_mfma_f32_32x32x2_f32), the
-arithmetic the reference computes in.  The one opt-in mode is timed in the same invocation over the same K steps and
+The JSON line's headline (`value`, `dtype`, `ms_per_step`, `roofline`) is the EXACT-fp32 path (v_mfma_f32_32x32x2_f32), the
+arithmetic the reference computes in.  A plain run sets up, warms up, times the K steps of the headline and prints the line;
+everything else is measured only with `--full`: the one opt-in mode, timed in the same invocation over the same K steps and
 reported as a sibling block with its own roofline and its measured deviation from the fp32 path: `"fp16x3"`
 (per-edge and node contractions on a two-way FP16 split of operands ranged by exact powers of two, 3 fp16 MFMAs per product;
 fp32-ACCURATE: as far from a float64 evaluation as the exact-fp32 path and the float32 reference themselves,
-tests/test_gpu_parity.py).  (The bf16 splits of rounds 1-5 were retired in round 6.)  At N=1 the line also carries
-`cpu_baseline` (the oracle timed on this host) and `configs` (BASELINE.json configs 2, 3, 5 and the reference's
-default B=2 job, timed on short chains).
+tests/test_gpu_parity.py).  (The bf16 splits of rounds 1-5 were retired in round 6.)  At N=1 the full line also carries
+`cpu_baseline` (the oracle timed on this host), `configs` (BASELINE.json configs 2, 3, 5 and the reference's
+default B=2 job, timed on short chains), `next_rows` (training step, stage 2) and `roofline.sustained` (the MFMA probe).
+
+`--dump-outputs DIR` writes what the headline's last timed step returned, rank 0's molecules, as DIR/x.npy (positions,
+[B, N, 3]) and DIR/h.npy (features, [B, N, F]) in float32 (other ranks: x_rank<r>.npy, h_rank<r>.npy).  Weights, masks and
+noise are seeded, so the same arguments give the same inputs in every run.
 
 For N > 1 the driver launches this file under torch.distributed.run, one rank per GPU: rank 0's weights
 are broadcast once over RCCL (xGMI); batches are independent, so there is no per-step collective (weak
@@ -143,7 +148,8 @@ def build_model(H, L, T, dev, rank, world, context_nf=0, cls=None, seed=0, dist_
 
 
 def timed_headline(model, precision, args, dev, rank, world, dist):
-    """W untimed + exactly K timed steps of the headline workload in one precision; returns the result block."""
+    """W untimed + exactly K timed steps of the headline workload in one precision; returns the result block and the
+    (x, h) the last timed step returned."""
     from hierdiff_amd import _lib
     from hierdiff_amd.sharding import shard_sample_ids
     H, L, S, B, N, T = args.hidden, args.layers, 2, args.batch, args.nodes, args.timesteps
@@ -174,7 +180,7 @@ def timed_headline(model, precision, args, dev, rank, world, dist):
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for k in range(args.steps):
-        one_step(args.warmup + k)
+        last = one_step(args.warmup + k)
     torch.cuda.synchronize(dev)
     own = time.perf_counter() - t0            # this rank's K steps, before it waits for the others
     if dist is not None:
@@ -261,7 +267,7 @@ def timed_headline(model, precision, args, dev, rank, world, dist):
              "elapsed_max_s": round(elapsed, 4), "rank_elapsed_s": [round(v, 4) for v in rank_elapsed],
              "launch": "hipGraph replay" if model.use_graph else "plain launches"}
     if roofline:
-        sus = sustained_mfma(precision, dev)
+        sus = sustained_mfma(precision, dev) if args.full else {}
         if sus:
             # the chip's own rate for this mode's matrix instruction under its power budget, measured right here (hd_mfma_probe:
             # register operands, random data, two wavefronts per SIMD): what `frac` (against the guide's dense peak at 2.4 GHz)
@@ -271,7 +277,7 @@ def timed_headline(model, precision, args, dev, rank, world, dist):
             sus["matrix_time_us_per_launch"] = round(m * roofline["flops_per_launch"] / (sus["tflops"] * 1e12) * 1e6, 1)
             roofline["sustained"] = sus
         block["roofline"] = roofline
-    return block
+    return block, last
 
 
 def sustained_mfma(precision: str, dev) -> dict:
@@ -689,8 +695,13 @@ def main() -> None:
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--timesteps", type=int, default=1000)
     ap.add_argument("--precision", choices=["all", "fp32", "fp16x3"], default="all",
-                    help="'all' (default): headline = exact fp32, plus the fp16x3 sibling block; a single mode "
+                    help="'all' (default): headline = exact fp32, plus the fp16x3 sibling block with --full; a single mode "
                          "times only that mode (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the fp16x3 sibling block, the sustained-MFMA probe, "
+                         "the configs / next_rows blocks and the CPU baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the (x, h) of the headline's last timed step as DIR/x.npy, DIR/h.npy (float32)")
     ap.add_argument("--graph", action="store_true", help="replay each diffusion step from a captured hipGraph")
     ap.add_argument("--event-stride", type=int, default=8,
                     help="bracket the edge-kernel launches of every k-th forward with HIP events")
@@ -704,6 +715,8 @@ def main() -> None:
     ap.add_argument("--force-launcher", action="store_true",
                     help="start the ranks through torch.distributed.run even for --gpus 1 (the N > 1 code path on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -728,8 +741,15 @@ def main() -> None:
 
     H, L, B, N, T = args.hidden, args.layers, args.batch, args.nodes, args.timesteps
     model = build_model(H, L, T, dev, rank, world, dist_on=dist is not None)
-    modes = ["fp32", "fp16x3"] if args.precision == "all" else [args.precision]
-    blocks = {p: timed_headline(model, p, args, dev, rank, world, dist) for p in modes}
+    if args.precision != "all":
+        modes = [args.precision]
+    else:
+        modes = ["fp32", "fp16x3"] if args.full else ["fp32"]
+    blocks, outputs = {}, {}
+    for p in modes:
+        blocks[p], outputs[p] = timed_headline(model, p, args, dev, rank, world, dist)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs[modes[0]], rank)
 
     if rank != 0:
         if dist is not None:
@@ -769,14 +789,22 @@ def main() -> None:
             if world == 1 and "fp32" in blocks:
                 sib.update(precision_gap(model, args, dev, mode))
             out[mode] = sib
-    if world == 1 and not args.no_configs:
+    if world == 1 and args.full and not args.no_configs:
         out["configs"] = other_configs(args, dev)
         out["next_rows"] = next_rows(dev)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(H, L, B, N, T)
     print(json.dumps(driver_visible_order(out)), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dump_outputs(path: str, xh, rank: int) -> None:
+    """(x, h) as returned to the caller of the timed path, as float32 .npy files (B=256, N=30: under 0.3 MB each)."""
+    os.makedirs(path, exist_ok=True)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    for name, t in zip(("x", "h"), xh):
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), t.detach().cpu().to(torch.float32).numpy())
 
 
 def cpu_baseline(H: int, L: int, B: int, N: int, T: int) -> dict:

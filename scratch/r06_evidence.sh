@@ -12,8 +12,8 @@ python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smo
 bash scratch/round_profiles.sh r06 > $OUT/round_profiles.log 2>&1
 cp gpurun_out/prof_r06/r06_counters.json profiles/r06_counters.json
 cp gpurun_out/prof_r06/r06_counters.json gpurun_out/prof_r06/r06_*_T50_kernel_stats.csv gpurun_out/prof_r06/summary.txt $OUT/ 2>/dev/null
-( time python bench.py ) > $OUT/bench_default.json 2> $OUT/bench_default.err
-python bench.py --steps 20 --warmup 2 --no-configs --no-cpu-baseline > $OUT/bench_20steps.json 2> $OUT/bench_20steps.err
+( time python bench.py --full ) > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full --steps 20 --warmup 2 --no-configs --no-cpu-baseline > $OUT/bench_20steps.json 2> $OUT/bench_20steps.err
 python tests/fuzz_parity.py 120 11 > $OUT/fuzz_parity.log 2>&1
 python tests/fuzz_grads.py 24 13 big > $OUT/fuzz_grads_big.log 2>&1
 python scratch/digest_cost.py > $OUT/digest_cost.log 2>&1

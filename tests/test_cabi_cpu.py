@@ -233,13 +233,12 @@ def test_cli_reads_reference_yaml_configs(tmp_path):
     conf2 = write_reference_style_conf(tmp_path / "b", with_analyze=False)
     cfg2 = load_model_config(str(conf2 / "model" / "ddpmgblur.yaml"))
     assert cfg2.analyze is None and max(DiffusionQM9(cfg2).nodes_dist.sample(500)) > 8
-    # the reference's own files, where the build container has them (never on the GPU box)
-    ref_yaml = "/root/reference/endiffusion/conf/model/ddpmgblur.yaml"
-    if os.path.exists(ref_yaml):
-        c = load_model_config(ref_yaml)
-        assert c.dynamics.hidden_nf == 256 and c.dynamics.n_layers == 6 and c.timesteps == 1000
-        assert c.analyze.endswith("conf/analyze/GEOM.yaml") and os.path.isfile(c.analyze)
-        assert load_sample_config("/root/reference/endiffusion/conf/sample/default.yaml") == (2, 16)
+    # the reference's own files, stored verbatim as fixtures (tests/golden/reference_conf/conf: model, sample, analyze)
+    ref_conf = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_conf", "conf")
+    c = load_model_config(os.path.join(ref_conf, "model", "ddpmgblur.yaml"))
+    assert c.dynamics.hidden_nf == 256 and c.dynamics.n_layers == 6 and c.timesteps == 1000
+    assert c.analyze == os.path.join(ref_conf, "analyze", "GEOM.yaml") and os.path.isfile(c.analyze)
+    assert load_sample_config(os.path.join(ref_conf, "sample", "default.yaml")) == (2, 16)
     with pytest.raises(ValueError):
         bad = tmp_path / "bad.yaml"
         bad.write_text("_target_: something.Else\ncfg: {}\n")

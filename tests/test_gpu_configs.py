@@ -591,6 +591,28 @@ def test_bench_self_launches_its_ranks(tmp_path):
     assert len(line["rank_elapsed_s"]) == 1 and line["value"] > 0
 
 
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps of the exact-fp32 headline and nothing else (the fp16x3 block, the
+    configs / next_rows rows, the CPU baseline and the MFMA probe need --full); --dump-outputs writes the (x, h) of its last
+    timed step, and two runs with the same arguments write the same bits."""
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--timesteps", "20"]
+    lines, dumps = [], []
+    for tag in ("a", "b"):
+        d = tmp_path / f"out_{tag}"
+        lines.append(_run_bench(args + ["--dump-outputs", str(d)], False, tmp_path, f"plain {tag}"))
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("x", "h")})
+    for line in lines:
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["dtype"] == "f32" and line["unit"] == "molecules/s"
+        assert line["ms_per_step"] > 0 and abs(line["ms_per_step"] * 2 - line["elapsed_max_s"] * 1e3) < 0.1
+        for k in ("fp16x3", "configs", "next_rows", "cpu_baseline"):
+            assert k not in line, k
+        assert "sustained" not in line.get("roofline", {})
+    for n, width in (("x", 3), ("h", None)):
+        a, b = dumps[0][n], dumps[1][n]
+        assert a.dtype == np.float32 and a.shape[:2] == (256, 30) and (width is None or a.shape[2] == width)
+        assert np.isfinite(a).all() and np.array_equal(a, b), n
+
+
 # ----------------------------------------------------------------------------- (l) the reference's shipped job: many small batches
 
 @pytest.mark.parametrize("precision", ["fp32", "fp16x3"])
