@@ -75,6 +75,9 @@ SIGNATURES = {
     "hd_egcl_graph_create": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.POINTER(_VP)]),
     "hd_egcl_graph_destroy": (C.c_int, [_VP]),
     "hd_egcl_forward": (C.c_int, [_VP, _VP] + [_FP] * 8 + [_VP]),
+    "hd_egcl_saved_floats": (C.c_longlong, [_VP, C.c_int, C.c_int]),
+    "hd_egcl_forward_train": (C.c_int, [_VP, _VP] + [_FP] * 9 + [_VP]),
+    "hd_egcl_backward": (C.c_int, [_VP, _VP] + [_FP] * 13 + [_VP]),
     "hd_linear": (C.c_int, [C.c_int, _FP, C.c_int, C.c_int, C.c_int, _FP, _FP, C.c_int, C.c_int, _FP, C.c_int, _VP]),
     "hd_gemm_f32": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _FP, C.c_longlong, C.c_longlong, _FP, C.c_longlong, C.c_longlong,
                               _FP, C.c_int, _FP, C.c_int, _FP, _FP, _FP, C.c_int, _FP, _FP, _VP]),

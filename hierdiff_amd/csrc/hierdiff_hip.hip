@@ -1829,6 +1829,7 @@ struct hd_egcl {
     // float offsets into dw
     size_t ab_img, ab_bias, w_r, w_e, w_c, w1e_img, zero_bias, w2_img, b2, wa, ba, wc1_img, bc1, wc2, we1_img, be1, w_er,
         we2_img, be2, wn1_img, bn1, wn2_img, bn2, ones;
+    size_t raw;             // the blob itself, state_dict layout (the backward's dX = dY W products read the weights unpacked)
     // widths 128 / 256 (round 5): the three node-level contractions also as k_node_f32 fragment images, for k_node_split_f32
     size_t ab_nimg, wn1_nimg, wn2_nimg;
     bool node_split;
@@ -1839,6 +1840,9 @@ struct hd_egcl_graph {
     int device, M, E, Mp, Ep;
     int *row, *col, *cptr, *crows;
     float *hin, *hres, *x4, *AB, *agg, *xagg, *Tn, *ea, *T1, *P, *M1, *C1, *geo, *trans, *ones;
+    int *rptr, *rrows;      // CSR over the sending index `row` (the backward's dA and dx sums)
+    float* bw;              // backward workspace (hd_egcl_backward, allocated by its first call)
+    size_t bw_floats;
 };
 
 static long long egcl_weight_count(const hd_egcl_config& c) {
@@ -1911,7 +1915,9 @@ extern "C" int hd_egcl_set_weights(hd_egcl* g, const float* blob, long long n, i
     g->wn1_img = take((size_t)2 * H * H); g->bn1 = take(H); g->wn2_img = take((size_t)H * H); g->bn2 = take(H);
     g->node_split = (H == 128 || H == 256);
     if (g->node_split) { g->ab_nimg = take((size_t)H * 2 * H); g->wn1_nimg = take((size_t)2 * H * H); g->wn2_nimg = take((size_t)H * H); }
+    g->raw = take((size_t)n);
     std::vector<float> pk(off, 0.0f);
+    std::copy(src, src + n, pk.begin() + g->raw);
     const float* p = src;
     auto next = [&](size_t cnt) { const float* q = p; p += cnt; return q; };
     {   // mes_mlp.0 [H][2H + 1 + De + ctx]: columns [source(H) | target(H) | radial | edge_attr(De) | context(ctx)] (gcl.py:92-98)
@@ -1982,6 +1988,7 @@ extern "C" int hd_egcl_graph_destroy(hd_egcl_graph* t) {
     hipFree(t->row); hipFree(t->col); hipFree(t->cptr); hipFree(t->crows);
     hipFree(t->hin); hipFree(t->hres); hipFree(t->x4); hipFree(t->AB); hipFree(t->agg); hipFree(t->xagg); hipFree(t->Tn);
     hipFree(t->ea); hipFree(t->T1); hipFree(t->P); hipFree(t->M1); hipFree(t->C1); hipFree(t->geo); hipFree(t->trans); hipFree(t->ones);
+    hipFree(t->rptr); hipFree(t->rrows); hipFree(t->bw);
     delete t;
     return HD_OK;
 }
@@ -1997,6 +2004,10 @@ extern "C" int hd_egcl_graph_create(hd_egcl* g, const int* row, const int* col, 
     for (int e = 0; e < E; ++e) cptr[vc[e] + 1]++;
     for (int i = 0; i < M; ++i) cptr[i + 1] += cptr[i];
     { std::vector<int> cur(cptr.begin(), cptr.end() - 1); for (int e = 0; e < E; ++e) crows[cur[vc[e]]++] = e; }
+    std::vector<int> rptr(M + 1, 0), rrows((size_t)E);
+    for (int e = 0; e < E; ++e) rptr[vr[e] + 1]++;
+    for (int i = 0; i < M; ++i) rptr[i + 1] += rptr[i];
+    { std::vector<int> cur(rptr.begin(), rptr.end() - 1); for (int e = 0; e < E; ++e) rrows[cur[vr[e]]++] = e; }
     hd_egcl_graph* t = new hd_egcl_graph();
     std::memset(t, 0, sizeof(*t));
     t->g = g; t->device = g->device; t->M = M; t->E = E;
@@ -2004,6 +2015,7 @@ extern "C" int hd_egcl_graph_create(hd_egcl* g, const int* row, const int* col, 
     const int H = g->H;
     auto build = [&]() -> int {
         HD_TRY(dev_upload(&t->row, vr)); HD_TRY(dev_upload(&t->col, vc)); HD_TRY(dev_upload(&t->cptr, cptr)); HD_TRY(dev_upload(&t->crows, crows));
+        HD_TRY(dev_upload(&t->rptr, rptr)); HD_TRY(dev_upload(&t->rrows, rrows));
         auto zalloc = [&](float** p, size_t count) -> int {
             HD_TRY(dev_alloc(p, count));
             HIP_TRY(hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(float)));
@@ -2030,9 +2042,37 @@ static void egcl_gemm(hd_egcl* g, int epi, bool cat, const GemmArgs& a, hipStrea
     else launch_gemm<2, 2, 1>(epi, cat, a, s);
 }
 
-extern "C" int hd_egcl_forward(hd_egcl* g, hd_egcl_graph* t, const float* h, const float* x, const float* edge_attr,
-                               const float* node_mask, const float* edge_mask, float* h_out, float* x_out,
-                               float* edge_attr_out, void* stream) {
+// What hd_egcl_forward_train keeps for the backward, in the caller's buffer (float offsets; row counts padded like the graph's
+// workspaces, so that every kernel that reads them sees the same extents as in the inference call).  The edge rows' pre-activations
+// come out of the forward GEMMs' epilogues on the way (the SiLU' of the backward needs them and SiLU cannot be inverted); the node
+// model's are recomputed by the backward instead - M node rows against E = M * n edge rows, and the node path of widths 128 / 256
+// (k_node_split_f32) keeps no pre-activation.
+struct EgclSaved {
+    size_t pre1, P, pre2, ef, pc, C1, pe, E1, geo, agg, total;
+};
+
+static EgclSaved egcl_saved_layout(const hd_egcl* g, long long M, long long E) {
+    const size_t H = g->H;
+    const size_t Mp = (size_t)((M + 127) / 128 * 128), Ep = (size_t)std::max<long long>(128, (E + 127) / 128 * 128);
+    EgclSaved L;
+    size_t o = 0;
+    auto take = [&](size_t n) { size_t r = o; o += n; return r; };
+    L.pre1 = take(Ep * H); L.P = take(Ep * H); L.pre2 = take(Ep * H); L.ef = take(Ep * H);
+    L.pc = g->cfg.coord_update ? take(Ep * H) : 0; L.C1 = g->cfg.coord_update ? take(Ep * H) : 0;
+    L.pe = g->cfg.edge_update ? take(Ep * H) : 0; L.E1 = g->cfg.edge_update ? take(Ep * H) : 0;
+    L.geo = take(Ep * 4); L.agg = take(Mp * H);
+    L.total = o;
+    return L;
+}
+
+extern "C" long long hd_egcl_saved_floats(const hd_egcl* g, int M, int E) {
+    if (!g || M < 1 || E < 0) return 0;
+    return (long long)egcl_saved_layout(g, M, E).total;
+}
+
+static int egcl_forward_impl(hd_egcl* g, hd_egcl_graph* t, const float* h, const float* x, const float* edge_attr,
+                             const float* node_mask, const float* edge_mask, float* h_out, float* x_out,
+                             float* edge_attr_out, float* saved, void* stream) {
     if (!g || !t) return fail(HD_E_INVALID, "hd_egcl_forward: null handle/graph");
     if (t->g != g) return fail(HD_E_INVALID, "hd_egcl_forward: graph belongs to another handle");
     if (!g->weights_set) return fail(HD_E_STATE, "hd_egcl_forward: weights not set (hd_egcl_set_weights)");
@@ -2045,6 +2085,15 @@ extern "C" int hd_egcl_forward(hd_egcl* g, hd_egcl_graph* t, const float* h, con
     const int H = g->H, De = g->De, ctx = g->ctx, M = t->M, E = t->E;
     const float* W = g->dw;
     const bool wide = De == H;
+    // training (saved != NULL): the activations go to the caller's buffer instead of the graph's workspace - same kernels, same bits
+    const EgclSaved SL = egcl_saved_layout(g, M, E);
+    float* const Pb = saved ? saved + SL.P : t->P;
+    float* const M1b = saved ? saved + SL.ef : t->M1;
+    float* const C1b = saved ? saved + SL.C1 : t->C1;
+    float* const E1b = saved ? saved + SL.E1 : t->C1;
+    float* const geob = saved ? saved + SL.geo : t->geo;
+    float* const aggb = saved ? saved + SL.agg : t->agg;
+    auto sv = [&](size_t off) { return saved ? saved + off : nullptr; };
     auto blocks = [](long long total) { return dim3((unsigned)((total + 255) / 256)); };
     auto gemm_args = [&](const float* A, int lda, int K1, int K, const float* A2, size_t img, size_t bias, float* Cc, int ldc,
                          int rows, int Nc, const float* nmask) {
@@ -2086,8 +2135,9 @@ extern "C" int hd_egcl_forward(hd_egcl* g, hd_egcl_graph* t, const float* h, con
     }
     if (E > 0) {
         if (wide && direct) {
-            GemmArgs p = gemm_args(edge_attr, H, H, H, nullptr, g->w1e_img, g->zero_bias, t->P, H, E, H, nullptr);
-            p.erow = t->row; p.ecol = t->col; p.ABn = t->AB; p.xn = xsrc; p.xs = xs; p.geo = t->geo; p.geo_mode = c.geo; p.colv = W + g->w_r;
+            GemmArgs p = gemm_args(edge_attr, H, H, H, nullptr, g->w1e_img, g->zero_bias, Pb, H, E, H, nullptr);
+            p.erow = t->row; p.ecol = t->col; p.ABn = t->AB; p.xn = xsrc; p.xs = xs; p.geo = geob; p.geo_mode = c.geo; p.colv = W + g->w_r;
+            p.pre = sv(SL.pre1);
             egcl_gemm(g, EPI_EGCL_PRE, false, p, s);
         } else if (wide) {
             egcl_gemm(g, EPI_BIAS, false, gemm_args(edge_attr, H, H, H, nullptr, g->w1e_img, g->zero_bias, t->T1, H, E, H, nullptr), s);
@@ -2095,22 +2145,28 @@ extern "C" int hd_egcl_forward(hd_egcl* g, hd_egcl_graph* t, const float* h, con
         if (!(wide && direct)) {
             EgclPreArgs a;
             a.AB = t->AB; a.T1 = wide ? t->T1 : nullptr; a.ea = wide ? nullptr : edge_attr; a.w_e = W + g->w_e; a.w_r = W + g->w_r;
-            a.w_c = W + g->w_c; a.hin = hsrc; a.x = xsrc; a.xs = xs; a.row = t->row; a.col = t->col; a.P = t->P; a.geo = t->geo;
-            a.E = E; a.H = H; a.De = De; a.ctx = ctx; a.geo_mode = c.geo;
+            a.w_c = W + g->w_c; a.hin = hsrc; a.x = xsrc; a.xs = xs; a.row = t->row; a.col = t->col; a.P = Pb; a.geo = geob;
+            a.E = E; a.H = H; a.De = De; a.ctx = ctx; a.geo_mode = c.geo; a.pre = sv(SL.pre1);
             hipLaunchKernelGGL(k_egcl_pre, blocks((long long)E * (H / 4)), dim3(256), 0, s, a);
         }
-        egcl_gemm(g, EPI_BIAS_SILU, false, gemm_args(t->P, H, H, H, nullptr, g->w2_img, g->b2, t->M1, H, E, H, nullptr), s);
+        {
+            GemmArgs m2 = gemm_args(Pb, H, H, H, nullptr, g->w2_img, g->b2, M1b, H, E, H, nullptr);
+            m2.pre = sv(SL.pre2);
+            egcl_gemm(g, EPI_BIAS_SILU, false, m2, s);
+        }
         {   // edge_feat = M (* att) * edge_mask, in place
             EgclRowArgs a;
             std::memset(&a, 0, sizeof(a));
-            a.X = t->M1; a.w = W + g->wa; a.bias = W + g->ba; a.emask = edge_mask; a.E = E; a.H = H; a.attention = c.attention;
+            a.X = M1b; a.w = W + g->wa; a.bias = W + g->ba; a.emask = edge_mask; a.E = E; a.H = H; a.attention = c.attention;
             hipLaunchKernelGGL((k_egcl_row<0>), dim3((E + 3) / 4), dim3(256), 0, s, a);
         }
         if (c.coord_update) {
-            egcl_gemm(g, EPI_BIAS_SILU, false, gemm_args(t->M1, H, H, H, nullptr, g->wc1_img, g->bc1, t->C1, H, E, H, nullptr), s);
+            GemmArgs c1 = gemm_args(M1b, H, H, H, nullptr, g->wc1_img, g->bc1, C1b, H, E, H, nullptr);
+            c1.pre = sv(SL.pc);
+            egcl_gemm(g, EPI_BIAS_SILU, false, c1, s);
             EgclRowArgs a;
             std::memset(&a, 0, sizeof(a));
-            a.X = t->C1; a.w = W + g->wc2; a.emask = edge_mask; a.geo = t->geo; a.trans = t->trans; a.range = c.coords_range;
+            a.X = C1b; a.w = W + g->wc2; a.emask = edge_mask; a.geo = geob; a.trans = t->trans; a.range = c.coords_range;
             a.E = E; a.H = H; a.use_tanh = c.tanh;
             hipLaunchKernelGGL((k_egcl_row<1>), dim3((E + 3) / 4), dim3(256), 0, s, a);
         }
@@ -2119,7 +2175,7 @@ extern "C" int hd_egcl_forward(hd_egcl* g, hd_egcl_graph* t, const float* h, con
         CsrSumArgs cs;
         std::memset(&cs, 0, sizeof(cs));
         cs.ptr = t->cptr; cs.rows = t->crows; cs.M = M; cs.col0 = 0;
-        cs.G = t->M1; cs.out = t->agg; cs.H = H; cs.ldo = H;
+        cs.G = M1b; cs.out = aggb; cs.H = H; cs.ldo = H;
         cs.G2 = c.coord_update ? t->trans : nullptr; cs.out2 = t->xagg;      // the [E][4] translations in the same launch
         if (direct) { cs.x_in = x; cs.x_out = x_out; cs.xmask = node_mask; }   // ... and k_egcl_node_out's coordinate line with them
         hipLaunchKernelGGL(k_csr_sum, blocks((long long)M * (H / 4 + (c.coord_update ? 1 : 0))), dim3(256), 0, s, cs);
@@ -2128,12 +2184,12 @@ extern "C" int hd_egcl_forward(hd_egcl* g, hd_egcl_graph* t, const float* h, con
     const float* nm = node_mask ? node_mask : t->ones;
     if (nsplit) {
         NodeSplitArgs p1 = nsargs(), p2 = nsargs();
-        p1.Wimg[0] = W + g->wn1_nimg; p1.bias[0] = W + g->bn1; p1.agg_dense = t->agg;
+        p1.Wimg[0] = W + g->wn1_nimg; p1.bias[0] = W + g->bn1; p1.agg_dense = aggb;
         p2.Wimg[0] = W + g->wn2_nimg; p2.bias[0] = W + g->bn2; p2.resid_none = c.recurrent ? 0 : 1;
         if (H == 128) { launch_node_split_f32_h<128, 1>(p1, s); launch_node_split_f32_h<128, 2>(p2, s); }
         else { launch_node_split_f32_h<256, 1>(p1, s); launch_node_split_f32_h<256, 2>(p2, s); }
     } else {
-    egcl_gemm(g, EPI_BIAS_SILU, true, gemm_args(hsrc, H, H, 2 * H, t->agg, g->wn1_img, g->bn1, t->Tn, H, M, H, nullptr), s);
+    egcl_gemm(g, EPI_BIAS_SILU, true, gemm_args(hsrc, H, H, 2 * H, aggb, g->wn1_img, g->bn1, t->Tn, H, M, H, nullptr), s);
     if (direct) {
         GemmArgs n2 = gemm_args(t->Tn, H, H, H, nullptr, g->wn2_img, g->bn2, h_out, H, M, H, nm);
         n2.resid = h; n2.ldr = H; n2.resid_none = c.recurrent ? 0 : 1;
@@ -2147,11 +2203,11 @@ extern "C" int hd_egcl_forward(hd_egcl* g, hd_egcl_graph* t, const float* h, con
         // edge_mlp: E1 = SiLU([edge_feat | edge_attr] We1^T + radial w_er + be1);  edge_attr' = (E1 We2^T + be2) * edge_mask
         // (round 3: the radial column + SiLU and the final mask ride in the GEMM epilogues, and the second GEMM writes the caller's
         // tensor - rows >= E are never stored: four stream operations less per layer, same expressions element by element)
-        GemmArgs e1 = gemm_args(t->M1, H, H, 2 * H, edge_attr, g->we1_img, g->be1, t->C1, H, E, H, nullptr);
-        e1.rowv = t->geo + 3; e1.rowv_stride = 4; e1.colv = W + g->w_er;
+        GemmArgs e1 = gemm_args(M1b, H, H, 2 * H, edge_attr, g->we1_img, g->be1, E1b, H, E, H, nullptr);
+        e1.rowv = geob + 3; e1.rowv_stride = 4; e1.colv = W + g->w_er; e1.pre = sv(SL.pe);
         egcl_gemm(g, EPI_RANK1_SILU, true, e1, s);
         egcl_gemm(g, edge_mask ? EPI_BIAS_MASK : EPI_BIAS, false,
-                  gemm_args(t->C1, H, H, H, nullptr, g->we2_img, g->be2, edge_attr_out, H, E, H, edge_mask), s);
+                  gemm_args(E1b, H, H, H, nullptr, g->we2_img, g->be2, edge_attr_out, H, E, H, edge_mask), s);
     }
     if (!direct) {
         EgclNodeOutArgs a;
@@ -2161,6 +2217,19 @@ extern "C" int hd_egcl_forward(hd_egcl* g, hd_egcl_graph* t, const float* h, con
     }
     HIP_TRY(hipGetLastError());
     return HD_OK;
+}
+
+extern "C" int hd_egcl_forward(hd_egcl* g, hd_egcl_graph* t, const float* h, const float* x, const float* edge_attr,
+                               const float* node_mask, const float* edge_mask, float* h_out, float* x_out,
+                               float* edge_attr_out, void* stream) {
+    return egcl_forward_impl(g, t, h, x, edge_attr, node_mask, edge_mask, h_out, x_out, edge_attr_out, nullptr, stream);
+}
+
+extern "C" int hd_egcl_forward_train(hd_egcl* g, hd_egcl_graph* t, const float* h, const float* x, const float* edge_attr,
+                                     const float* node_mask, const float* edge_mask, float* h_out, float* x_out,
+                                     float* edge_attr_out, float* saved, void* stream) {
+    if (!saved) return fail(HD_E_INVALID, "hd_egcl_forward_train: null saved buffer (hd_egcl_saved_floats)");
+    return egcl_forward_impl(g, t, h, x, edge_attr, node_mask, edge_mask, h_out, x_out, edge_attr_out, saved, stream);
 }
 
 extern "C" int hd_linear(int device, const float* x, int M, int K, int ldx, const float* W, const float* b, int N, int act,
@@ -2629,6 +2698,178 @@ extern "C" int hd_mfma_probe(int device, int kind, const float* in1024, float* s
     if (se != hipSuccess) return fail(HD_E_HIP, std::string("hd_mfma_probe: ") + hipGetErrorString(se));
     HIP_TRY(hipGetLastError());
     *ns_per_mfma_per_simd = (double)ms * 1e6 / ((double)iters * 8 * 2);     // 8 MFMAs per iteration and wavefront, 2 wavefronts per SIMD
+    return HD_OK;
+}
+
+// ----------------------------------------------------------------------------- stage-2 layer E_GCL (backward)
+
+// Offsets of the parameters in the flat state_dict-order blob (hd_egcl_set_weights; the weight gradient has the same layout).
+struct EgclRaw {
+    size_t W1, b1, W2, b2, We1, be1, We2, be2, Wn1, bn1, Wn2, bn2, Wc1, bc1, wc2, wa, ba;
+};
+
+static EgclRaw egcl_raw_offsets(const hd_egcl_config& c) {
+    const size_t H = c.hidden_nf, De = c.edges_in_d, ctx = c.context_nf;
+    EgclRaw R;
+    std::memset(&R, 0, sizeof(R));
+    size_t o = 0;
+    auto take = [&](size_t n) { size_t r = o; o += n; return r; };
+    R.W1 = take(H * (2 * H + 1 + De + ctx)); R.b1 = take(H); R.W2 = take(H * H); R.b2 = take(H);
+    if (c.edge_update) { R.We1 = take(H * (H + 1 + De)); R.be1 = take(H); R.We2 = take(H * H); R.be2 = take(H); }
+    R.Wn1 = take(2 * H * H); R.bn1 = take(H); R.Wn2 = take(H * H); R.bn2 = take(H);
+    if (c.coord_update) { R.Wc1 = take(H * H); R.bc1 = take(H); R.wc2 = take(H); }
+    if (c.attention) { R.wa = take(H); R.ba = take(1); }
+    return R;
+}
+
+constexpr int EGCL_MAX_SPLIT = 32;
+
+extern "C" int hd_egcl_backward(hd_egcl* g, hd_egcl_graph* t, const float* h, const float* x, const float* edge_attr,
+                                const float* node_mask, const float* edge_mask, const float* saved, const float* dh_out,
+                                const float* dx_out, const float* dedge_attr_out, float* dh, float* dx, float* dedge_attr,
+                                float* dweights, void* stream) {
+    if (!g || !t) return fail(HD_E_INVALID, "hd_egcl_backward: null handle/graph");
+    if (t->g != g) return fail(HD_E_INVALID, "hd_egcl_backward: graph belongs to another handle");
+    if (!g->weights_set) return fail(HD_E_STATE, "hd_egcl_backward: weights not set (hd_egcl_set_weights)");
+    if (!h || !x || !saved || !dh || !dx || !dweights) return fail(HD_E_INVALID, "hd_egcl_backward: null tensor");
+    const hd_egcl_config& c = g->cfg;
+    if (g->De > 0 && !edge_attr) return fail(HD_E_INVALID, "hd_egcl_backward: edge_attr required");
+    HIP_TRY(hipSetDevice(g->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int H = g->H, De = g->De, ctx = g->ctx, M = t->M, E = t->E, W = H + ctx;
+    const int ld1 = 2 * H + 1 + De + ctx, lde = H + 1 + De;
+    const float* Wt = g->dw + g->raw;
+    const EgclRaw R = egcl_raw_offsets(c);
+    const EgclSaved SL = egcl_saved_layout(g, M, E);
+    auto S = [&](size_t off) { return saved + off; };
+    // workspace: 7 edge-row buffers [Ep][H], two per-edge quads [Ep][4], node buffers, the split-K slabs
+    const size_t Ep = t->Ep, Mp = t->Mp, EH = Ep * H, MH = Mp * H;
+    const size_t wsf = (size_t)EGCL_MAX_SPLIT * (2 * (size_t)H * H + 2 * H);
+    const size_t need = 7 * EH + 8 * Ep + 9 * MH + 4 * MH + 4 * Mp + wsf;
+    if (t->bw_floats < need) {
+        hipFree(t->bw); t->bw = nullptr; t->bw_floats = 0;
+        HD_TRY(dev_alloc(&t->bw, need));
+        t->bw_floats = need;
+    }
+    float* p = t->bw;
+    auto take = [&](size_t n) { float* r = p; p += n; return r; };
+    float* B[7];
+    for (int i = 0; i < 7; ++i) B[i] = take(EH);
+    float *escal = take(4 * Ep), *sc4 = take(4 * Ep);
+    float *X = take(2 * MH), *pn = take(MH), *Tn = take(MH), *dout = take(MH), *dpn = take(MH), *dX = take(2 * MH), *dAB = take(2 * MH);
+    float *T2 = take(MH), *Tc = take(MH), *dxs = take(4 * Mp), *ws = take(wsf);
+    auto blocks = [](long long total) { return dim3((unsigned)((total + 255) / 256)); };
+    const dim3 wave_grid((unsigned)((E + 3) / 4)), wave_block(256);
+    // C [rows][ldc] = epi(A B) with A(m,k) = A[m sam + k sak], B(k,n) = B[k sbk + n sbn] (hd_gemm_f32; one unit stride each)
+    auto mm = [&](int rows, int N, int K, const float* A, long long sam, long long sak, const float* Bm, long long sbk, long long sbn,
+                  float* C, int ldc, const float* bias, int epi, const float* aux, float* C2) {
+        return hd_gemm_f32(g->device, rows, N, K, A, sam, sak, Bm, sbk, sbn, C, ldc, bias, epi, aux, nullptr, C2, 1, nullptr, nullptr, s);
+    };
+    // dW [Mo][ldc] (first N columns) = dY^T X over K rows (dY [K][lda], X(k, n) = X[k ldb + n sxn]), db = column sums of dY:
+    // split-K in slab order for the long reductions over edge rows (deterministic)
+    auto dwg = [&](int Mo, int N, int K, const float* dY, long long lda, const float* Xm, long long ldb, float* C, int ldc,
+                   float* colsum) {
+        const int split = std::min(EGCL_MAX_SPLIT, std::max(1, K / 256));
+        return hd_gemm_f32(g->device, Mo, N, K, dY, 1, lda, Xm, ldb, 1, C, ldc, nullptr, TG_EPI_BIAS, nullptr, nullptr, nullptr,
+                           split, split > 1 ? ws : nullptr, colsum, s);
+    };
+    float* dW = dweights;
+    if (E == 0) HIP_TRY(hipMemsetAsync(dW, 0, (size_t)g->n_weights * sizeof(float), s));     // the edge models get no gradient
+
+    // ---- node model: h_new = (h +) node_mlp([h | agg]), output * node_mask (gcl.py:119-128, :186-190)
+    {
+        EgclBNodeInArgs a;
+        a.h = h; a.agg = S(SL.agg); a.dh_out = dh_out; a.dx_out = dx_out; a.nmask = node_mask; a.X = X; a.dout = dout; a.dxs = dxs;
+        a.M = M; a.H = H; a.ctx = ctx;
+        hipLaunchKernelGGL(k_egcl_bnode_in, blocks((long long)M * 2 * H), dim3(256), 0, s, a);
+    }
+    HD_TRY(mm(M, H, 2 * H, X, 2 * H, 1, Wt + R.Wn1, 1, 2 * H, pn, H, Wt + R.bn1, TG_EPI_BIAS_SILU2, nullptr, Tn));
+    HD_TRY(mm(M, H, H, dout, H, 1, Wt + R.Wn2, H, 1, dpn, H, nullptr, TG_EPI_MUL_DSILU, pn, nullptr));
+    HD_TRY(dwg(H, H, M, dout, H, Tn, H, dW + R.Wn2, H, dW + R.bn2));
+    HD_TRY(mm(M, 2 * H, H, dpn, H, 1, Wt + R.Wn1, 2 * H, 1, dX, 2 * H, nullptr, TG_EPI_BIAS, nullptr, nullptr));
+    HD_TRY(dwg(H, 2 * H, M, dpn, H, X, 2 * H, dW + R.Wn1, 2 * H, dW + R.bn1));
+    if (E > 0) {
+        float* dpe = nullptr;
+        float* defp = nullptr;
+        // ---- edge model: edge_attr' = (SiLU([ef | radial | ea] We1^T + be1) We2^T + be2) * edge_mask (gcl.py:110-116)
+        if (c.edge_update) {
+            const float* Dm = dedge_attr_out;
+            if (!dedge_attr_out || edge_mask) {
+                EgclBMaskArgs a;
+                a.in = dedge_attr_out; a.emask = edge_mask; a.out = B[0]; a.E = E; a.H = H;
+                hipLaunchKernelGGL(k_egcl_bmask, blocks((long long)E * (H / 4)), dim3(256), 0, s, a);
+                Dm = B[0];
+            }
+            dpe = B[1];
+            HD_TRY(mm(E, H, H, Dm, H, 1, Wt + R.We2, H, 1, dpe, H, nullptr, TG_EPI_MUL_DSILU, S(SL.pe), nullptr));
+            HD_TRY(dwg(H, H, E, Dm, H, S(SL.E1), H, dW + R.We2, H, dW + R.be2));
+            HD_TRY(dwg(H, H, E, dpe, H, S(SL.ef), H, dW + R.We1, lde, dW + R.be1));
+            HD_TRY(dwg(H, 1, E, dpe, H, S(SL.geo) + 3, 4, dW + R.We1 + H, lde, nullptr));
+            HD_TRY(dwg(H, De, E, dpe, H, edge_attr, De, dW + R.We1 + H + 1, lde, nullptr));
+            if (dedge_attr)
+                HD_TRY(mm(E, De, H, dpe, H, 1, Wt + R.We1 + H + 1, lde, 1, dedge_attr, De, nullptr, TG_EPI_BIAS, nullptr, nullptr));
+            defp = B[3];
+            HD_TRY(mm(E, H, H, dpe, H, 1, Wt + R.We1, lde, 1, defp, H, nullptr, TG_EPI_BIAS, nullptr, nullptr));
+        }
+        // ---- coordinate model (gcl.py:130-152)
+        if (c.coord_update) {
+            EgclBCoordArgs a;
+            a.C1 = S(SL.C1); a.pc = S(SL.pc); a.wc2 = Wt + R.wc2; a.geo = S(SL.geo); a.col = t->col; a.dxs = dxs; a.emask = edge_mask;
+            a.dpc = B[2]; a.escal = escal; a.sc4 = sc4; a.range = c.coords_range; a.E = E; a.H = H; a.use_tanh = c.tanh;
+            hipLaunchKernelGGL(k_egcl_bcoord, wave_grid, wave_block, 0, s, a);
+            HD_TRY(dwg(H, H, E, B[2], H, S(SL.ef), H, dW + R.Wc1, H, dW + R.bc1));
+            HD_TRY(dwg(1, H, E, sc4 + 1, 4, S(SL.C1), H, dW + R.wc2, H, nullptr));
+            HD_TRY(mm(E, H, H, B[2], H, 1, Wt + R.Wc1, H, 1, B[3], H, nullptr, defp ? TG_EPI_RESID_MASK : TG_EPI_BIAS, defp, nullptr));
+            defp = B[3];
+        }
+        // ---- message model: gate, mes_mlp.2, mes_mlp.0 (gcl.py:91-107)
+        {
+            EgclBGateArgs a;
+            a.defp = defp; a.dagg = dX + H; a.ld_dagg = 2 * H; a.col = t->col; a.pre2 = S(SL.pre2); a.wa = Wt + R.wa; a.ba = Wt + R.ba;
+            a.emask = edge_mask; a.dpre2 = B[4]; a.M1 = B[5]; a.sc4 = sc4; a.E = E; a.H = H; a.attention = c.attention;
+            hipLaunchKernelGGL(k_egcl_bgate, wave_grid, wave_block, 0, s, a);
+        }
+        if (c.attention) HD_TRY(dwg(1, H, E, sc4, 4, B[5], H, dW + R.wa, H, dW + R.ba));
+        HD_TRY(dwg(H, H, E, B[4], H, S(SL.P), H, dW + R.W2, H, dW + R.b2));
+        float* dpre1 = B[6];
+        HD_TRY(mm(E, H, H, B[4], H, 1, Wt + R.W2, H, 1, dpre1, H, nullptr, TG_EPI_MUL_DSILU, S(SL.pre1), nullptr));
+        if (De > 0) {
+            HD_TRY(dwg(H, De, E, dpre1, H, edge_attr, De, dW + R.W1 + 2 * H + 1, ld1, nullptr));
+            if (dedge_attr)
+                HD_TRY(mm(E, De, H, dpre1, H, 1, Wt + R.W1 + 2 * H + 1, ld1, 1, dedge_attr, De, nullptr,
+                          c.edge_update ? TG_EPI_RESID_MASK : TG_EPI_BIAS, c.edge_update ? dedge_attr : nullptr, nullptr));
+        }
+        {
+            EgclBGeoArgs a;
+            a.dpre1 = dpre1; a.w_r = Wt + R.W1 + 2 * H; a.ld_wr = ld1; a.dpe = dpe; a.w_er = Wt + R.We1 + H; a.ld_wer = lde;
+            a.x = x; a.row = t->row; a.col = t->col; a.escal = escal; a.sc4 = sc4; a.E = E; a.H = H; a.geo_mode = c.geo;
+            a.coord_in = c.coord_update;
+            hipLaunchKernelGGL(k_egcl_bgeo, wave_grid, wave_block, 0, s, a);
+        }
+        HD_TRY(dwg(H, 1, E, dpre1, H, sc4 + 2, 4, dW + R.W1 + 2 * H, ld1, nullptr));
+        {   // dA[i] = sum over edges sent by i, dB[i] = sum over edges received by i, of dpre1 (ascending edge order, one launch)
+            CsrSumArgs cs;
+            std::memset(&cs, 0, sizeof(cs));
+            cs.G = dpre1; cs.H = H; cs.M = M; cs.out = dAB; cs.ldo = 2 * H;
+            cs.ptr = t->rptr; cs.rows = t->rrows; cs.col0 = 0;
+            cs.ptr_b = t->cptr; cs.rows_b = t->crows; cs.col0_b = H;
+            hipLaunchKernelGGL(k_csr_sum, dim3((unsigned)(((long long)M * (H / 4) + 255) / 256), 2), dim3(256), 0, s, cs);
+        }
+        HD_TRY(dwg(H, H, M, dAB, 2 * H, h, W, dW + R.W1, ld1, dW + R.b1));
+        HD_TRY(dwg(H, H, M, dAB + H, 2 * H, h, W, dW + R.W1 + H, ld1, nullptr));
+        if (ctx > 0) HD_TRY(dwg(H, ctx, M, dAB, 2 * H, h + H - ctx, W, dW + R.W1 + 2 * H + 1 + De, ld1, nullptr));
+        HD_TRY(mm(M, H, H, dAB, 2 * H, 1, Wt + R.W1, ld1, 1, T2, H, nullptr, TG_EPI_BIAS, nullptr, nullptr));
+        HD_TRY(mm(M, H, H, dAB + H, 2 * H, 1, Wt + R.W1 + H, ld1, 1, T2, H, nullptr, TG_EPI_RESID_MASK, T2, nullptr));
+        if (ctx > 0) HD_TRY(mm(M, ctx, H, dAB, 2 * H, 1, Wt + R.W1 + 2 * H + 1 + De, ld1, 1, Tc, ctx, nullptr, TG_EPI_BIAS, nullptr, nullptr));
+    }
+    {
+        EgclBNodeOutArgs a;
+        a.dout = dout; a.dX = dX; a.T2 = E > 0 ? T2 : nullptr; a.Tc = (E > 0 && ctx > 0) ? Tc : nullptr; a.dh_out = dh_out;
+        a.nmask = node_mask; a.dxs = dxs; a.escal = escal; a.rptr = t->rptr; a.rrows = t->rrows; a.cptr = t->cptr; a.crows = t->crows;
+        a.dh = dh; a.dx = dx; a.M = M; a.H = H; a.ctx = ctx; a.recurrent = c.recurrent;
+        hipLaunchKernelGGL(k_egcl_bnode_out, blocks((long long)M * W), dim3(256), 0, s, a);
+    }
+    HIP_TRY(hipGetLastError());
     return HD_OK;
 }
 

@@ -27,6 +27,7 @@ struct EgclPreArgs {
     float* geo;             // [E][4] = {cdiff_x, cdiff_y, cdiff_z, radial}
     int E, H, De, ctx, geo_mode;      // geo_mode: the message model's distance input is 1 / radial^2 (gcl.py:170-175)
     int xs;                           // floats per coordinate row of `x` (4: the padded copy; 3: the caller's tensor, round 5)
+    float* pre;                       // [E][H] pre1 before the SiLU, or NULL (hd_egcl_forward_train keeps it for the backward)
 };
 
 __global__ void k_egcl_pre(EgclPreArgs a) {
@@ -62,6 +63,7 @@ __global__ void k_egcl_pre(EgclPreArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) pre[j] = __builtin_fmaf(v, w[j], pre[j]);
     }
+    if (a.pre) *reinterpret_cast<f32x4*>(a.pre + (size_t)e * a.H + k) = pre;
 #pragma unroll
     for (int j = 0; j < 4; ++j) pre[j] = silu_f(pre[j]);
     *reinterpret_cast<f32x4*>(a.P + (size_t)e * a.H + k) = pre;

@@ -84,6 +84,7 @@ struct GemmArgs {
     const float* xn;      // [M][xs] coordinates
     float* geo;           // [E][4] = {cdiff_x, cdiff_y, cdiff_z, radial}, written by the column tile 0 workgroups
     int xs, geo_mode;
+    float* pre;           // EPI_BIAS_SILU / EPI_EGCL_PRE / EPI_RANK1_SILU: the argument of the SiLU, [M][ldc], or NULL
 };
 
 
@@ -223,6 +224,7 @@ __global__ __launch_bounds__(WM * WN * 64) void k_gemm(GemmArgs g) {
             f32x4 v = *reinterpret_cast<const f32x4*>(Cs + r * LDC_S + 4 * c4) + *reinterpret_cast<const f32x4*>(g.bias + col);
             f32x4* dst = reinterpret_cast<f32x4*>(g.C + (size_t)row * g.ldc + col);
             if (EPI == EPI_BIAS_SILU) {
+                if (g.pre) *reinterpret_cast<f32x4*>(g.pre + (size_t)row * g.ldc + col) = v;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] = silu_f(v[j]);
             }
@@ -247,6 +249,7 @@ __global__ __launch_bounds__(WM * WN * 64) void k_gemm(GemmArgs g) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) pre[j] = __builtin_fmaf(g.geo_mode ? 1.0f / (radial * radial) : radial, wr[j], pre[j]);
                 pre += v;
+                if (g.pre) *reinterpret_cast<f32x4*>(g.pre + (size_t)row * g.ldc + col) = pre;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] = silu_f(pre[j]);
             }
@@ -255,7 +258,10 @@ __global__ __launch_bounds__(WM * WN * 64) void k_gemm(GemmArgs g) {
                 const float rv = g.rowv[(size_t)row * g.rowv_stride];
                 const f32x4 cw = *reinterpret_cast<const f32x4*>(g.colv + col);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = silu_f(__builtin_fmaf(rv, cw[j], v[j]));
+                for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf(rv, cw[j], v[j]);
+                if (g.pre) *reinterpret_cast<f32x4*>(g.pre + (size_t)row * g.ldc + col) = v;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = silu_f(v[j]);
             }
             *dst = v;
         }

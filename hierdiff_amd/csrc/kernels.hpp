@@ -25,6 +25,7 @@
 #include "k_sampling.hpp"
 #include "k_egcl.hpp"
 #include "k_tgemm.hpp"
+#include "k_egcl_bwd.hpp"
 #include "k_dw2.hpp"
 #include "k_loss.hpp"
 #include "k_digest.hpp"

@@ -8,7 +8,9 @@ Same constructor, same `state_dict` keys, same `forward(batch)` (loss / accuracy
 reference.  The arithmetic runs in libhierdiff_hip.so: every E_GCL layer through `hd_egcl_forward` (hierdiff_amd.stage2), every
 dense layer (embeddings, heads) through `hd_linear`; torch moves memory only (gathers, concatenations, the vocabulary lookup)
 and reduces the handful of scalars of the loss.  The tree bookkeeping between the chains (breadth-first edge layers, argmax
-over candidates, adjacency updates) is host Python in the reference and here.  Value only (no autograd); no CPU fallback.
+over candidates, adjacency updates) is host Python in the reference and here.  `forward` computes values only; the trainable
+objective is `training_forward(batch)` (same dict, differentiable `total_loss`: E_GCL chains through hd_egcl_forward_train /
+hd_egcl_backward, embeddings and heads through hd_gemm_f32 in all three directions).  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -121,6 +123,7 @@ class Edge_denoise(nn.Module):
         self.node_predict = nn.Sequential(nn.Linear(H + context_nf, H), nn.SiLU(), nn.Linear(H, out_node_nf))
         self.loss_lambda = {'focal_loss': focal_loss, 'edge_loss': edge_loss, 'node_loss': node_loss}
         self._edges_dict: Dict[Tuple[int, int, str], List[torch.Tensor]] = {}
+        self._grad_path = False                 # set for the length of a training_forward call
 
     # ------------------------------------------------------------------ HIP dense layers
     def _device(self) -> torch.device:
@@ -134,6 +137,11 @@ class Edge_denoise(nn.Module):
         """act(layer(x)) through hd_linear (act: 0 none, 1 SiLU, 2 sigmoid); x [..., K] -> [..., N]."""
         dev = self._device()
         lead = x.shape[:-1]
+        if self._grad_path:                     # differentiable: hd_gemm_f32 forward, dX and dW (training._Linear)
+            from .training import _Linear
+            y = _Linear.apply(x.to(dev, torch.float32).reshape(-1, x.shape[-1]), layer.weight, layer.bias)
+            y = torch.nn.functional.silu(y) if act == 1 else torch.sigmoid(y) if act == 2 else y
+            return y.reshape(*lead, y.shape[-1])
         x2 = x.detach().to(dev, torch.float32).reshape(-1, x.shape[-1]).contiguous()
         W = layer.weight.detach().to(torch.float32).contiguous()
         b = None if layer.bias is None else layer.bias.detach().to(torch.float32).contiguous()
@@ -164,7 +172,8 @@ class Edge_denoise(nn.Module):
         dev = self._device()
         h = h.to(dev, torch.float32)
         h_f = self._linear(h[:, :self.in_node_nf], self.feature_embedding)
-        h_v = self.vocab_embedding.weight.detach()[h[:, self.in_node_nf + self.context_nf].long()]
+        vocab = self.vocab_embedding.weight if self._grad_path else self.vocab_embedding.weight.detach()
+        h_v = vocab[h[:, self.in_node_nf + self.context_nf].long()]
         hh = self._linear(torch.cat([h_f, h_v], dim=1), self.node_embedding)
         if self.context_nf > 0:
             hh = torch.cat([hh, h[:, self.in_node_nf:self.in_node_nf + self.context_nf]], dim=1)
@@ -213,6 +222,18 @@ class Edge_denoise(nn.Module):
                                "(SURVEY.md section 8f row 4)")
         with torch.no_grad():
             return self._forward_values(batch)
+
+    def training_forward(self, batch):
+        """The reference's `forward(batch)` as a training objective: the same dict as `forward`, with `total_loss` (and the three
+        losses) differentiable with respect to every parameter.  Loss values agree with `forward`'s to fp32 round-off (the dense
+        layers sum in another order)."""
+        self._device()
+        self._grad_path = True
+        try:
+            with torch.enable_grad():
+                return self._forward_values(batch)
+        finally:
+            self._grad_path = False
 
     def _forward_values(self, batch):
         dev = self._device()

@@ -4,7 +4,9 @@ The layer of HierDiff's second stage (`models/edge_denoise.py:35-43`: gcl_full_i
 same constructor, same `state_dict` keys (mes_mlp.0.weight, edge_mlp.0.weight, node_mlp.0.weight, coord_mlp.0.weight,
 att_mlp.0.weight, ...), same `forward(h, edge_index, coord, edge_attr, node_attr, node_mask, edge_mask)` and return value.
 The arithmetic runs in libhierdiff_hip.so (`hd_egcl_forward`, exact fp32 MFMA GEMMs over edge / node rows + row kernels);
-the torch modules below only hold parameters.  Inference only (value); no CPU fallback.
+the torch modules below only hold parameters.  No CPU fallback.  Under autograd (a parameter or an input that requires grad)
+the layer is differentiable: `_EgclFunction` runs `hd_egcl_forward_train` (same kernels, same bits, plus the activations the
+backward needs in a tensor autograd owns) and `hd_egcl_backward` (exact fp32, deterministic); otherwise the inference call.
 Not supported (config-off in the reference's stage-2 models): agg='mean', node_attr, angle_net (dead code in the reference), act_fn != SiLU.
 """
 from __future__ import annotations
@@ -189,8 +191,36 @@ class E_GCL(nn.Module):
         return g
 
     # ------------------------------------------------------------------ reference API
-    @torch.no_grad()
     def forward(self, h, edge_index, coord, edge_attr=None, node_attr=None, node_mask=None, edge_mask=None):
+        if torch.is_grad_enabled():
+            if h.device.type != "cuda":
+                raise HierDiffHipError("E_GCL.forward needs cuda tensors (no CPU fallback)")
+            if self._plist is None:
+                self._plist = list(self.parameters())
+            if any(p.requires_grad for p in self._plist) or any(t is not None and t.requires_grad for t in (h, coord, edge_attr)):
+                return self._forward_train(h, edge_index, coord, edge_attr, node_attr, node_mask, edge_mask)
+        with torch.no_grad():
+            return self._forward_value(h, edge_index, coord, edge_attr, node_attr, node_mask, edge_mask)
+
+    def _forward_train(self, h, edge_index, coord, edge_attr, node_attr, node_mask, edge_mask):
+        if node_attr is not None:
+            raise NotImplementedError("node_attr is not used by the reference's stage-2 models")
+        row, col = edge_index
+        H, ctx, De = self._cfg.hidden_nf, self._cfg.context_nf, self._cfg.edges_in_d
+        if h.shape[1] != H + ctx:
+            raise ValueError(f"h has {h.shape[1]} columns, layer expects {H + ctx}")
+        if De > 0 and (edge_attr is None or edge_attr.shape != (row.shape[0], De)):
+            raise ValueError(f"edge_attr must be [E, {De}]")
+        self._sync_weights()
+        g = self._graph(row, col, h.shape[0])
+        dev = h.device
+        ea = None if De == 0 else edge_attr
+        nm = None if node_mask is None else node_mask.detach().to(dev, torch.float32).reshape(-1).contiguous()
+        em = None if edge_mask is None else edge_mask.detach().to(dev, torch.float32).reshape(-1).contiguous()
+        outs = _EgclFunction.apply(self, g, nm, em, h, coord, ea, *self._plist)
+        return outs if self.edge_update else outs[:2]
+
+    def _forward_value(self, h, edge_index, coord, edge_attr=None, node_attr=None, node_mask=None, edge_mask=None):
         if node_attr is not None:
             raise NotImplementedError("node_attr is not used by the reference's stage-2 models")
         if h.device.type != "cuda":
@@ -230,3 +260,57 @@ class E_GCL(nn.Module):
         diff = coord[row] - coord[col]
         radial = torch.sum(diff ** 2, 1).unsqueeze(1)
         return radial, diff / (torch.sqrt(radial + 1e-8) + 1)
+
+
+class _EgclFunction(torch.autograd.Function):
+    """One E_GCL application under autograd.  Inputs: the layer, its graph (kept alive by this node, so that the layer's LRU may
+    drop it), the masks (no gradient), h, x, edge_attr and the layer's parameter tensors in registration order - so autograd
+    accumulates their gradients over every application of the layer in a model's forward.  The activations of the forward live in
+    `saved`, a tensor this node owns (the graph's workspaces belong to whichever call ran last on it)."""
+
+    @staticmethod
+    def forward(ctx, layer, g, nm, em, h, x, ea, *params):
+        lib = _lib.load()
+        hd = layer._handle()
+        dev = h.device
+        f32 = lambda t: None if t is None else t.detach().to(dev, torch.float32).contiguous()
+        hc, xc, eac = f32(h), f32(x), f32(ea)
+        H = layer._cfg.hidden_nf
+        saved = torch.empty(int(lib.hd_egcl_saved_floats(hd, g.M, g.E)), device=dev, dtype=torch.float32)
+        h_out = torch.empty_like(hc)
+        x_out = torch.empty_like(xc)
+        ea_out = torch.empty((g.E, H), device=dev, dtype=torch.float32) if layer.edge_update else None
+        p = lambda t: None if t is None else t.data_ptr()
+        _lib.check(lib.hd_egcl_forward_train(hd, g._h, p(hc), p(xc), p(eac), p(nm), p(em), p(h_out), p(x_out), p(ea_out), p(saved),
+                                             torch.cuda.current_stream(dev).cuda_stream), "hd_egcl_forward_train")
+        ctx.layer, ctx.g, ctx.has_ea = layer, g, ea is not None
+        ctx.shapes = [tuple(q.shape) for q in params]
+        ctx.save_for_backward(hc, xc, eac, nm, em, saved)
+        if ea_out is None:
+            ea_out = torch.empty((0,), device=dev, dtype=torch.float32)
+            ctx.mark_non_differentiable(ea_out)
+        return h_out, x_out, ea_out
+
+    @staticmethod
+    def backward(ctx, dh_out, dx_out, dea_out):
+        hc, xc, eac, nm, em, saved = ctx.saved_tensors
+        layer, g = ctx.layer, ctx.g
+        lib = _lib.load()
+        hd = layer._handle()
+        dev = hc.device
+        c = lambda t: None if t is None or t.numel() == 0 else t.detach().to(torch.float32).contiguous()
+        dh_out, dx_out, dea_out = c(dh_out), c(dx_out), c(dea_out) if layer.edge_update else None
+        dh = torch.empty_like(hc)
+        dx = torch.empty_like(xc)
+        dea = torch.empty_like(eac) if (eac is not None and ctx.needs_input_grad[6]) else None
+        dw = torch.empty(int(lib.hd_egcl_weight_count(hd)), device=dev, dtype=torch.float32)
+        p = lambda t: None if t is None else t.data_ptr()
+        _lib.check(lib.hd_egcl_backward(hd, g._h, p(hc), p(xc), p(eac), p(nm), p(em), p(saved), p(dh_out), p(dx_out), p(dea_out),
+                                        p(dh), p(dx), p(dea), p(dw), torch.cuda.current_stream(dev).cuda_stream), "hd_egcl_backward")
+        grads = []
+        off = 0
+        for shp in ctx.shapes:
+            n = int(np.prod(shp))
+            grads.append(dw[off:off + n].view(shp))
+            off += n
+        return (None, None, None, None, dh, dx, dea) + tuple(grads)

@@ -157,6 +157,8 @@ def _linear_dw(g, x, want_db, rows=None):
     """dW = g^T x [N, K] (and db = column sums of g) over the first `rows` rows, split-K in slab order."""
     rows = g.shape[0] if rows is None else rows
     N, K = g.shape[1], x.shape[1]
+    if want_db and g.stride(0) == 1:        # one output column (the stage-2 heads' last Linear): the column sums need a row stride
+        g = torch.nn.functional.pad(g.reshape(g.shape[0], N), (0, 4 - N))          # other than 1 - rows of four, zeros beyond N
     dW = torch.empty((N, K), device=g.device, dtype=torch.float32)
     db = torch.empty((N,), device=g.device, dtype=torch.float32) if want_db else None
     _gemm(N, K, rows, g, 1, g.stride(0), x, x.stride(0), 1, dW, split=_split_for(N, K, rows), colsum=db)

@@ -280,6 +280,22 @@ int hd_egcl_graph_destroy(hd_egcl_graph* t);
 int hd_egcl_forward(hd_egcl* g, hd_egcl_graph* t, const float* h, const float* x, const float* edge_attr,
                     const float* node_mask, const float* edge_mask, float* h_out, float* x_out, float* edge_attr_out,
                     void* stream);
+/* Training (ABI 12, additive): the same forward, which also keeps what the backward needs in a CALLER-OWNED buffer `saved` of
+ * hd_egcl_saved_floats(g, M, E) device floats (the graph's workspaces are overwritten by the next call on the same graph, and a model
+ * applies one layer several times per forward).  h_out / x_out / edge_attr_out are the bits of hd_egcl_forward. */
+long long hd_egcl_saved_floats(const hd_egcl* g, int M, int E);
+int hd_egcl_forward_train(hd_egcl* g, hd_egcl_graph* t, const float* h, const float* x, const float* edge_attr,
+                          const float* node_mask, const float* edge_mask, float* h_out, float* x_out, float* edge_attr_out,
+                          float* saved, void* stream);
+/* Backward of hd_egcl_forward_train with the same inputs and its `saved` buffer, given dh_out [M][H+ctx], dx_out [M][3] and
+ * dedge_attr_out [E][H] (each may be NULL = zero).  Writes dh [M][H+ctx], dx [M][3], dedge_attr [E][De] (NULL: not wanted) and
+ * dweights, the gradient of every parameter in the layout of hd_egcl_set_weights (state_dict order).  Exact fp32: the dense
+ * products on the training GEMM (hd_gemm_f32), sums over edges in a fixed order (CSR over row / col, split-K in slab order) -
+ * deterministic.  The mask tensors get no gradient.  The backward reads the weights of the last hd_egcl_set_weights. */
+int hd_egcl_backward(hd_egcl* g, hd_egcl_graph* t, const float* h, const float* x, const float* edge_attr,
+                     const float* node_mask, const float* edge_mask, const float* saved, const float* dh_out,
+                     const float* dx_out, const float* dedge_attr_out, float* dh, float* dx, float* dedge_attr,
+                     float* dweights, void* stream);
 
 /* y [M][ldy] (first N columns) = act(x [M][ldx] (first K columns) . W [N][K]^T + b [N] or NULL); device fp32, any M, K, N.
  * act: 0 none, 1 SiLU, 2 sigmoid.  The small dense layers around the E_GCL chains of the stage-2 model - torch.nn.Linear in
