@@ -78,7 +78,14 @@ SIGNATURES = {
     "hd_egcl_saved_floats": (C.c_longlong, [_VP, C.c_int, C.c_int]),
     "hd_egcl_forward_train": (C.c_int, [_VP, _VP] + [_FP] * 9 + [_VP]),
     "hd_egcl_backward": (C.c_int, [_VP, _VP] + [_FP] * 13 + [_VP]),
-    "hd_linear": (C.c_int, [C.c_int, _FP, C.c_int, C.c_int, C.c_int, _FP, _FP, C.c_int, C.c_int, _FP, C.c_int, _VP]),
+    "hd_refine_embed_forward": (C.c_int, [C.c_int, _VP, _VP] + [C.c_int] * 4 + [_FP, _FP, _FP] + [C.c_int] * 3 + [_VP, _VP]),
+    "hd_refine_embed_backward": (C.c_int, [C.c_int, _VP, _VP] + [C.c_int] * 4 + [_FP] + [C.c_int] * 3 + [_FP, _FP, _VP]),
+    "hd_sqdist_forward": (C.c_int, [_VP, _FP, _FP, _VP]),
+    "hd_sqdist_backward": (C.c_int, [_VP, _FP, _FP, _FP, _VP]),
+    "hd_cand_xent_forward": (C.c_int, [C.c_int, C.c_int, _FP, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _FP, _VP, _VP,
+                                       _VP, _VP]),
+    "hd_cand_xent_backward": (C.c_int, [C.c_int, C.c_int, _FP, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _FP, _FP, _VP]),
+    "hd_linear":(C.c_int, [C.c_int, _FP, C.c_int, C.c_int, C.c_int, _FP, _FP, C.c_int, C.c_int, _FP, C.c_int, _VP]),
     "hd_gemm_f32": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _FP, C.c_longlong, C.c_longlong, _FP, C.c_longlong, C.c_longlong,
                               _FP, C.c_int, _FP, C.c_int, _FP, _FP, _FP, C.c_int, _FP, _FP, _VP]),
     "hd_colsum_f32": (C.c_int, [C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _FP, _VP]),

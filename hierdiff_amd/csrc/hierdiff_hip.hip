@@ -2892,3 +2892,96 @@ extern "C" float hd_philox_normal_host(uint64_t seed, uint64_t sample_id, uint32
     const float ang = 6.283185307179586f * u2;
     return (index & 1) ? rad * std::sin(ang) : rad * std::cos(ang);
 }
+
+// ----------------------------------------------------------------------------- refine model (k_refine.hpp)
+
+static int refine_device(int device, const char* what) {
+    if (hd_device_count() <= device || device < 0) return fail(HD_E_HIP, std::string(what) + ": no such HIP device (is a GPU visible?)");
+    HIP_TRY(hipSetDevice(device));
+    return HD_OK;
+}
+
+extern "C" int hd_refine_embed_forward(int device, const long long* v, const long long* size, int M, int H, int nv, int ns,
+                                       const float* Ev, const float* Es, float* out, int ldo, int off_v, int off_s, int* bad,
+                                       void* stream) {
+    if (!v || !size || !Ev || !Es || !out || !bad) return fail(HD_E_INVALID, "hd_refine_embed_forward: null argument");
+    if (M < 0 || H < 1 || nv < 1 || ns < 1 || off_v < 0 || off_s < 0 || ldo < std::max(off_v, off_s) + H)
+        return fail(HD_E_INVALID, "hd_refine_embed_forward: bad shape");
+    HD_TRY(refine_device(device, "hd_refine_embed_forward"));
+    if (M == 0) return HD_OK;
+    const long long total = (long long)M * H;
+    hipLaunchKernelGGL(k_refine_embed, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, v, size, M, H, nv, ns,
+                       Ev, Es, out, ldo, off_v, off_s, bad);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_refine_embed_backward(int device, const long long* v, const long long* size, int M, int H, int nv, int ns,
+                                        const float* dout, int ldo, int off_v, int off_s, float* dEv, float* dEs, void* stream) {
+    if (!v || !size || !dout || !dEv || !dEs) return fail(HD_E_INVALID, "hd_refine_embed_backward: null argument");
+    if (M < 0 || H < 1 || nv < 1 || ns < 1 || off_v < 0 || off_s < 0 || ldo < std::max(off_v, off_s) + H)
+        return fail(HD_E_INVALID, "hd_refine_embed_backward: bad shape");
+    HD_TRY(refine_device(device, "hd_refine_embed_backward"));
+    hipLaunchKernelGGL(k_refine_embed_bwd, dim3((unsigned)(nv + ns)), dim3(256), 0, (hipStream_t)stream, v, size, M, H, nv, dout, ldo,
+                       off_v, off_s, dEv, dEs);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_sqdist_forward(hd_egcl_graph* t, const float* x, float* ea, void* stream) {
+    if (!t || !x || !ea) return fail(HD_E_INVALID, "hd_sqdist_forward: null argument");
+    if (t->E == 0) return HD_OK;
+    HIP_TRY(hipSetDevice(t->device));
+    hipLaunchKernelGGL(k_sqdist, dim3((unsigned)((t->E + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t->row, t->col, t->E, x, ea);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_sqdist_backward(hd_egcl_graph* t, const float* x, const float* dea, float* dx, void* stream) {
+    if (!t || !x || !dx || (t->E > 0 && !dea)) return fail(HD_E_INVALID, "hd_sqdist_backward: null argument");
+    HIP_TRY(hipSetDevice(t->device));
+    hipLaunchKernelGGL(k_sqdist_bwd, dim3((unsigned)((t->M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t->row, t->col, t->rptr,
+                       t->rrows, t->cptr, t->crows, t->M, x, dea, dx);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+static int cand_xent_args(CandXentArgs& a, const char* what, int B, const float* logits, int ld, int ncols, const int* cand_ids,
+                          const int* cand_off, int nsets, const int* set_idx, const int* target) {
+    if (!logits || !cand_ids || !cand_off || !set_idx || !target) return fail(HD_E_INVALID, std::string(what) + ": null argument");
+    if (B < 0 || ncols < 1 || ld < ncols || nsets < 1) return fail(HD_E_INVALID, std::string(what) + ": bad shape");
+    a.logits = logits; a.ids = cand_ids; a.off = cand_off; a.set = set_idx; a.target = target;
+    a.B = B; a.ld = ld; a.ncols = ncols; a.nsets = nsets;
+    return HD_OK;
+}
+
+extern "C" int hd_cand_xent_forward(int device, int B, const float* logits, int ld, int ncols, const int* cand_ids, const int* cand_off,
+                                    int nsets, const int* set_idx, const int* target, int k, float* logp, int* hit, int* topk,
+                                    int* err, void* stream) {
+    CandXentArgs a;
+    std::memset(&a, 0, sizeof(a));
+    HD_TRY(cand_xent_args(a, "hd_cand_xent_forward", B, logits, ld, ncols, cand_ids, cand_off, nsets, set_idx, target));
+    if (!logp || !hit || !err || (k > 0 && !topk)) return fail(HD_E_INVALID, "hd_cand_xent_forward: null argument");
+    if (k < 0 || k > HD_XENT_MAX_K) return fail(HD_E_INVALID, "hd_cand_xent_forward: k must be 0..16");
+    HD_TRY(refine_device(device, "hd_cand_xent_forward"));
+    if (B == 0) return HD_OK;
+    a.logp = logp; a.hit = hit; a.topk = topk; a.err = err; a.k = k;
+    hipLaunchKernelGGL(k_cand_xent, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_cand_xent_backward(int device, int B, const float* logits, int ld, int ncols, const int* cand_ids, const int* cand_off,
+                                     int nsets, const int* set_idx, const int* target, const float* dloss, float* dlogits,
+                                     void* stream) {
+    CandXentArgs a;
+    std::memset(&a, 0, sizeof(a));
+    HD_TRY(cand_xent_args(a, "hd_cand_xent_backward", B, logits, ld, ncols, cand_ids, cand_off, nsets, set_idx, target));
+    if (!dloss || !dlogits) return fail(HD_E_INVALID, "hd_cand_xent_backward: null argument");
+    HD_TRY(refine_device(device, "hd_cand_xent_backward"));
+    if (B == 0) return HD_OK;
+    a.dloss = dloss; a.dlogits = dlogits;
+    hipLaunchKernelGGL(k_cand_xent_bwd, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}

@@ -297,6 +297,29 @@ int hd_egcl_backward(hd_egcl* g, hd_egcl_graph* t, const float* h, const float* 
                      const float* dx_out, const float* dedge_attr_out, float* dh, float* dx, float* dedge_attr,
                      float* dweights, void* stream);
 
+/* ---- Refine model (Node2Vec, models/model_refine.py of the reference; ABI 12, additive), exact fp32, deterministic.
+ * Input gather: out [M][ldo] columns off_v.. = Ev [nv][H] row v[m], columns off_s.. = Es [ns][H] row size[m] (v, size: device int64
+ * [M]).  An id outside its table writes zeros and sets *bad = 1 (a device int the caller zeroes and reads); it is never dereferenced.
+ * Backward: dEv [nv][H] and dEs [ns][H] = per-id sums of the same columns of dout, rows added in ascending order. */
+int hd_refine_embed_forward(int device, const long long* v, const long long* size, int M, int H, int nv, int ns, const float* Ev,
+                            const float* Es, float* out, int ldo, int off_v, int off_s, int* bad, void* stream);
+int hd_refine_embed_backward(int device, const long long* v, const long long* size, int M, int H, int nv, int ns, const float* dout,
+                             int ldo, int off_v, int off_s, float* dEv, float* dEs, void* stream);
+/* Edge attribute on an E_GCL edge graph: ea [E] = |x[row] - x[col]|^2 (x [M][3]); backward dx [M][3] from dea [E], summed per
+ * node over the graph's CSR lists (first the edges the node sends, then those it receives). */
+int hd_sqdist_forward(hd_egcl_graph* t, const float* x, float* ea, void* stream);
+int hd_sqdist_backward(hd_egcl_graph* t, const float* x, const float* dea, float* dx, void* stream);
+/* Size-restricted softmax head.  logits [B][ld] (first ncols columns); candidate sets cand_ids (device int32, set s at
+ * [cand_off[s], cand_off[s + 1]), ids unique within a set) with cand_off [nsets + 1]; set_idx [B], target [B] device int32.
+ * Forward: logp [B] = log-softmax over the row's set at the target, hit [B] = (argmax over the set == target), topk [B][k] the k
+ * best candidate ids (0 <= k <= 16; value descending, ties to the lower position in the set; -1 past the set's size).  *err
+ * (device int, zeroed by the caller): 1 a target outside its set, 2 a set index out of range, 3 a candidate id >= ncols.
+ * Backward: dlogits [B][ld] = dloss[b] (softmax over the set - onehot(target)) on the set's columns, 0 on the other ncols columns. */
+int hd_cand_xent_forward(int device, int B, const float* logits, int ld, int ncols, const int* cand_ids, const int* cand_off, int nsets,
+                         const int* set_idx, const int* target, int k, float* logp, int* hit, int* topk, int* err, void* stream);
+int hd_cand_xent_backward(int device, int B, const float* logits, int ld, int ncols, const int* cand_ids, const int* cand_off, int nsets,
+                          const int* set_idx, const int* target, const float* dloss, float* dlogits, void* stream);
+
 /* y [M][ldy] (first N columns) = act(x [M][ldx] (first K columns) . W [N][K]^T + b [N] or NULL); device fp32, any M, K, N.
  * act: 0 none, 1 SiLU, 2 sigmoid.  The small dense layers around the E_GCL chains of the stage-2 model - torch.nn.Linear in
  * /root/reference/models/edge_denoise.py:29-33 (feature / edge / node embeddings) and :55-57 (focal / edge / node prediction
