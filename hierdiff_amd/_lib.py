@@ -55,6 +55,10 @@ SIGNATURES = {
     "hd_set_schedule": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "hd_sample_loop": (C.c_int, [_VP, _VP, _FP, _FP, C.c_int, C.c_int, C.c_int, _FP, _FP, C.c_int,
                                  C.c_uint64, C.c_uint64, C.c_int, _VP]),
+    "hd_set_inpaint_schedule": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_float)]),
+    "hd_sample_loop_inpaint": (C.c_int, [_VP, _VP, _FP, _FP, C.c_int, C.c_int, C.c_int, _FP, _FP, C.c_int,
+                                         C.c_uint64, C.c_uint64, C.c_int, _U8P, _FP, C.c_int, _VP]),
+    "hd_inpaint_decode_fix": (C.c_int, [_VP, _VP, _U8P, _FP, _FP, _FP, _FP, _VP]),
     "hd_topology_nodes": (C.c_int, [_VP, _VP]),
     "hd_topology_nodes_device": (C.c_int, [_VP, _VP, _VP]),
     "hd_edge_layer_forward": (C.c_int, [_VP, _VP, C.c_int] + [_FP] * 9 + [_VP]),

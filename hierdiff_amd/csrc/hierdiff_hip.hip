@@ -96,6 +96,11 @@ struct hd_handle {
     hipEvent_t ev_last;         // recorded behind the handle's latest graph replay (any stream): the step / draw / time words
     bool ev_last_set;           // above are shared by every topology of the handle, so replays are serialised on it
     unsigned long long weights_gen, sched_gen;   // bumped when the packed weights / schedule tables are re-allocated
+    // inpainting loop (hd_set_inpaint_schedule / hd_sample_loop_inpaint)
+    float* d_coef_ip;           // [T][4] {alpha_s, sigma_s, alpha_t|s, sigma_t|s}
+    unsigned long long ip_sched_gen, ip_gen;     // sched_gen the table was set for (0: not set); bumped when d_coef_ip / d_ipdraw move
+    uint32_t* d_ipdraw;         // graph replay: the draw words of a step's 3 * resamplings noise streams
+    int ipdraw_cap;
     int split_max_tiles;        // HD_SPLIT_MAX_TILES (a measurement build may override it from the environment)
     int fuse_min_rows;          // HD_FUSE_MIN_ROWS
     int node_split_max_rows;    // HD_NODE_SPLIT_MAX_ROWS
@@ -131,6 +136,17 @@ struct GraphKey {
     }
 };
 
+// The same for a captured step of the inpainting loop.
+struct InpaintKey {
+    int has_ctx, T, resamplings;
+    uint64_t seed;
+    unsigned long long weights_gen, sched_gen, ip_gen;
+    bool operator==(const InpaintKey& o) const {
+        return has_ctx == o.has_ctx && T == o.T && resamplings == o.resamplings && seed == o.seed && weights_gen == o.weights_gen &&
+               sched_gen == o.sched_gen && ip_gen == o.ip_gen;
+    }
+};
+
 struct hd_topology {
     hd_handle* h;
     int device;
@@ -152,6 +168,12 @@ struct hd_topology {
     float *zbuf, *ctxbuf;
     hipGraphExec_t gexec;
     GraphKey gkey;
+    // hd_sample_loop_inpaint with use_graph: its own captured step, and library-owned copies of the fixed mask / known values
+    // (allocated by the first such call)
+    hipGraphExec_t gexec_ip;
+    InpaintKey ikey;
+    uint8_t* ip_fixed;
+    float* ip_known;
     // lifetime: the tables arrive in stream order of `stream0` (hd_topology_create_s); `ready` marks their arrival for
     // any other stream a caller launches on.  A topology used on one stream only hands its arena back to the pool
     // (arena_release) with an event instead of a device-wide synchronisation.
@@ -260,6 +282,7 @@ extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
     h->ev_in = h->ev_out = nullptr;
     h->ev_last = nullptr; h->ev_last_set = false;
     h->weights_gen = h->sched_gen = 0;
+    h->d_coef_ip = nullptr; h->ip_sched_gen = 0; h->ip_gen = 0; h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
     h->d_nanflag = nullptr; h->d_nan_events = nullptr; h->d_step = nullptr; h->d_draw = nullptr; h->d_tcur = nullptr;
     h->d_base = nullptr;
     h->split_max_tiles = HD_SPLIT_MAX_TILES;
@@ -308,6 +331,7 @@ extern "C" int hd_destroy(hd_handle* h) {
     (void)hipDeviceSynchronize();
     hipFree(h->dw); hipFree(h->d_nanflag); hipFree(h->d_nan_events);
     hipFree(h->d_tau); hipFree(h->d_coef); hipFree(h->d_step); hipFree(h->d_draw); hipFree(h->d_tcur); hipFree(h->d_base);
+    hipFree(h->d_coef_ip); hipFree(h->d_ipdraw);
 #ifdef HD_DEBUG_KERNELS
     hipFree(h->d_trace);
 #endif
@@ -681,7 +705,7 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     ArenaSlot sl{t->device, t->arena, t->arena_bytes, t->staging, t->staging_bytes, nullptr};
     // a captured graph, or launches on several streams: wait for the device (the rare case - a sampling topology lives as
     // long as its model); otherwise an event behind the topology's last work guards the arena's next owner
-    bool pooled = t->arena && !t->gexec && !t->multi_stream;
+    bool pooled = t->arena && !t->gexec && !t->gexec_ip && !t->multi_stream;
     if (pooled && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) == hipSuccess) {
         if (hipEventRecord(sl.done, t->last_stream) != hipSuccess) { (void)hipEventDestroy(sl.done); sl.done = nullptr; pooled = false; }
     } else {
@@ -689,6 +713,9 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     }
     if (!pooled) (void)hipDeviceSynchronize();
     if (t->gexec) hipGraphExecDestroy(t->gexec);
+    if (t->gexec_ip) hipGraphExecDestroy(t->gexec_ip);
+    if (t->ip_fixed) (void)hipFree(t->ip_fixed);
+    if (t->ip_known) (void)hipFree(t->ip_known);
     if (t->ready) (void)hipEventDestroy(t->ready);
     if (t->arena) arena_release(sl);                    // tables and workspace live in one allocation
     delete t->node_of_host;
@@ -2662,6 +2689,188 @@ extern "C" int hd_sample_loop(hd_handle* h, hd_topology* topo, float* z, const f
         HIP_TRY(hipEventRecord(h->ev_out, rs));
         HIP_TRY(hipStreamWaitEvent(s, h->ev_out, 0));
     }
+    return HD_OK;
+}
+
+// ----------------------------------------------------------------------------- fragment-constrained sampling (inpainting)
+
+extern "C" int hd_set_inpaint_schedule(hd_handle* h, int T, const float* coef4) {
+    if (!h || !coef4 || T < 1) return fail(HD_E_INVALID, "hd_set_inpaint_schedule: bad argument");
+    if (h->T < 1) return fail(HD_E_STATE, "hd_set_inpaint_schedule: schedule not set (hd_set_schedule)");
+    if (T != h->T) return fail(HD_E_INVALID, "hd_set_inpaint_schedule: T differs from the schedule's (hd_set_schedule)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());
+    hipFree(h->d_coef_ip);
+    h->d_coef_ip = nullptr;
+    h->ip_sched_gen = 0;
+    const std::vector<float> rows(coef4, coef4 + (size_t)4 * T);
+    HD_TRY(dev_upload(&h->d_coef_ip, rows));
+    h->ip_sched_gen = h->sched_gen;
+    h->ip_gen++;                               // captured graphs hold the old table address
+    return HD_OK;
+}
+
+static int inpaint_launch(hd_handle* h, hd_topology* t, bool jump, float* z, const uint8_t* fixed, const float* known, uint64_t seed,
+                          uint64_t base, uint32_t draw, int step, const uint32_t* draw_ptr, const int* step_ptr,
+                          const unsigned long long* base_ptr, hipStream_t s) {
+    ProfScope ps(h, s, 2);
+    InpaintArgs a;
+    a.z = z; a.nm = t->nm_bytes; a.fixed = fixed; a.known = known; a.coef = h->d_coef_ip; a.seed = seed; a.sample_base = base;
+    a.draw = draw; a.step = step; a.draw_ptr = draw_ptr; a.step_ptr = step_ptr; a.base_ptr = base_ptr;
+    a.B = t->B; a.N = t->N; a.D = h->D;
+    const size_t lds = (size_t)t->N * h->D * sizeof(float);
+    if (jump) hipLaunchKernelGGL(k_inpaint_jump, dim3(t->B), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL(k_inpaint_replace, dim3(t->B), dim3(256), lds, s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_sample_loop_inpaint(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
+                                      int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
+                                      uint64_t seed, uint64_t sample_id_base, int use_graph, const uint8_t* fixed_mask,
+                                      const float* xh_known, int resamplings, void* stream) {
+    HD_TRY(check_ready(h, topo, "hd_sample_loop_inpaint"));
+    if (h->T < 1) return fail(HD_E_STATE, "hd_sample_loop_inpaint: schedule not set (hd_set_schedule)");
+    if (!h->d_coef_ip || h->ip_sched_gen != h->sched_gen)
+        return fail(HD_E_STATE, "hd_sample_loop_inpaint: inpainting schedule not set for the current schedule (hd_set_inpaint_schedule)");
+    if (!z || !fixed_mask || !xh_known) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: null z / fixed_mask / xh_known");
+    if (s_hi > h->T || s_lo < 0 || s_lo > s_hi) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: need 0 <= s_lo <= s_hi <= T");
+    if (raw_x || raw_h) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: injected noise is not supported (counter-based generator only)");
+    if (noise_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: noise_rows must be B");
+    if (mol_shape >= 0 && mol_shape < topo->N) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: fixed tail rows (mol_shape < N) are not supported");
+    if (resamplings < 1) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: resamplings must be >= 1");
+    if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: context required");
+    if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: needs a time-conditioned model");
+    const int T = h->T, R = resamplings, nd = 3 * R;
+    const uint32_t stride = (uint32_t)T + 2u;                // draws of one noise stream: 0 .. T + 1
+    if ((unsigned long long)stride * (unsigned long long)nd > 0xffffffffULL)
+        return fail(HD_E_INVALID, "hd_sample_loop_inpaint: (T + 2) * 3 * resamplings exceeds the 32-bit draw index");
+    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: N * D floats exceed one workgroup's LDS");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int nsteps = s_hi - s_lo;
+    topo_use(topo, s);
+    if (nsteps == 0) return HD_OK;
+    const int N = topo->N;
+    const uint32_t draw0 = (uint32_t)(T - (s_hi - 1));
+    if (!use_graph) {
+        for (int k = 0; k < nsteps; ++k) {
+            const int sidx = s_hi - 1 - k;
+            const uint32_t d = draw0 + (uint32_t)k;
+            for (int j = 0; j < R; ++j) {
+                HD_TRY(forward_impl(h, topo, z, h->d_tau + sidx + 1, 1, context, -1, topo->eps, s));
+                NoiseSrc ns = make_noise(nullptr, nullptr, noise_rows, seed, sample_id_base, stride * (uint32_t)(3 * j) + d, 0);
+                HD_TRY(step_impl(h, topo, z, topo->eps, h->d_coef + (size_t)sidx * 4, 1, ns, N, z, N, nullptr, nullptr, 0, s));
+                HD_TRY(inpaint_launch(h, topo, false, z, fixed_mask, xh_known, seed, sample_id_base, stride * (uint32_t)(3 * j + 1) + d,
+                                      sidx, nullptr, nullptr, nullptr, s));
+                if (j < R - 1)
+                    HD_TRY(inpaint_launch(h, topo, true, z, nullptr, nullptr, seed, sample_id_base, stride * (uint32_t)(3 * j + 2) + d,
+                                          sidx, nullptr, nullptr, nullptr, s));
+            }
+        }
+        return HD_OK;
+    }
+    // One captured step - all rounds of it - replayed nsteps times, like hd_sample_loop: step index, time and first sample id in
+    // the handle's device words, the draws of the 3 * R noise streams in d_ipdraw; library-owned copies of every tensor.
+    const size_t BN = (size_t)topo->B * N;
+    const size_t zbytes = BN * h->D * sizeof(float);
+    const size_t cbytes = BN * h->cfg.context_node_nf * sizeof(float);
+    hipStream_t rs = s;
+    if (s == nullptr) {
+        if (!h->own_stream) HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+        rs = h->own_stream;
+        HIP_TRY(hipEventRecord(h->ev_in, s));
+        HIP_TRY(hipStreamWaitEvent(rs, h->ev_in, 0));
+    }
+    if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(rs, h->ev_last, 0));
+    if (nd > h->ipdraw_cap) {                                // grow the draw words: graphs that hold the old address go stale (ip_gen)
+        if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
+        HIP_TRY(hipStreamSynchronize(rs));
+        hipFree(h->d_ipdraw);
+        h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
+        HD_TRY(dev_alloc(&h->d_ipdraw, (size_t)nd));
+        h->ipdraw_cap = nd;
+        h->ip_gen++;
+    }
+    if (!topo->ip_fixed) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->ip_fixed), BN));
+    if (!topo->ip_known) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->ip_known), zbytes));
+    InpaintKey key;
+    key.has_ctx = context ? 1 : 0; key.T = T; key.resamplings = R; key.seed = seed; key.weights_gen = h->weights_gen;
+    key.sched_gen = h->sched_gen; key.ip_gen = h->ip_gen;
+    if (topo->gexec_ip && !(topo->ikey == key)) {
+        if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
+        HIP_TRY(hipStreamSynchronize(rs));
+        hipGraphExecDestroy(topo->gexec_ip);
+        topo->gexec_ip = nullptr;
+    }
+    if (!topo->gexec_ip) {
+        const int was_prof = h->prof;
+        h->prof = 0;
+        hipGraph_t graph = nullptr;
+        HIP_TRY(hipStreamBeginCapture(rs, hipStreamCaptureModeThreadLocal));
+        int rc = HD_OK;
+        for (int j = 0; j < R && rc == HD_OK; ++j) {
+            rc = forward_impl(h, topo, topo->zbuf, h->d_tcur, 1, context ? topo->ctxbuf : nullptr, -1, topo->eps, rs);
+            if (rc == HD_OK) {
+                NoiseSrc ns = make_noise(nullptr, nullptr, noise_rows, seed, 0, 0, 0);
+                rc = step_impl(h, topo, topo->zbuf, topo->eps, h->d_coef, 1, ns, N, topo->zbuf, N, h->d_step, h->d_ipdraw + 3 * j,
+                               0, rs, h->d_base);
+            }
+            if (rc == HD_OK)
+                rc = inpaint_launch(h, topo, false, topo->zbuf, topo->ip_fixed, topo->ip_known, seed, 0, 0, 0, h->d_ipdraw + 3 * j + 1,
+                                    h->d_step, h->d_base, rs);
+            if (rc == HD_OK && j < R - 1)
+                rc = inpaint_launch(h, topo, true, topo->zbuf, nullptr, nullptr, seed, 0, 0, 0, h->d_ipdraw + 3 * j + 2, h->d_step,
+                                    h->d_base, rs);
+        }
+        if (rc == HD_OK) {
+            hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, rs, h->d_step, h->d_draw, h->d_tcur, h->d_tau);
+            hipLaunchKernelGGL(k_inpaint_advance, dim3((nd + 255) / 256), dim3(256), 0, rs, h->d_ipdraw, nd);
+        }
+        const hipError_t ce = hipStreamEndCapture(rs, &graph);
+        h->prof = was_prof;
+        if (rc != HD_OK) { if (graph) hipGraphDestroy(graph); return rc; }
+        if (ce != hipSuccess) return fail(HD_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
+        const hipError_t ie = hipGraphInstantiate(&topo->gexec_ip, graph, nullptr, nullptr, 0);
+        hipGraphDestroy(graph);
+        if (ie != hipSuccess) { topo->gexec_ip = nullptr; return fail(HD_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+        topo->ikey = key;
+    }
+    HIP_TRY(hipMemcpyAsync(topo->zbuf, z, zbytes, hipMemcpyDeviceToDevice, rs));
+    if (context) HIP_TRY(hipMemcpyAsync(topo->ctxbuf, context, cbytes, hipMemcpyDeviceToDevice, rs));
+    HIP_TRY(hipMemcpyAsync(topo->ip_fixed, fixed_mask, BN, hipMemcpyDeviceToDevice, rs));
+    HIP_TRY(hipMemcpyAsync(topo->ip_known, xh_known, zbytes, hipMemcpyDeviceToDevice, rs));
+    hipLaunchKernelGGL(k_loop_state, dim3(1), dim3(1), 0, rs, h->d_step, h->d_draw, h->d_tcur, h->d_base, h->d_tau,
+                       s_hi - 1, draw0, (unsigned long long)sample_id_base);
+    hipLaunchKernelGGL(k_inpaint_state, dim3((nd + 255) / 256), dim3(256), 0, rs, h->d_ipdraw, nd, stride, draw0);
+    for (int k = 0; k < nsteps; ++k) {
+        const hipError_t le = hipGraphLaunch(topo->gexec_ip, rs);
+        if (le != hipSuccess) return fail(HD_E_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(le));
+    }
+    HIP_TRY(hipMemcpyAsync(z, topo->zbuf, zbytes, hipMemcpyDeviceToDevice, rs));
+    HIP_TRY(hipEventRecord(h->ev_last, rs));
+    h->ev_last_set = true;
+    if (rs != s) {
+        HIP_TRY(hipEventRecord(h->ev_out, rs));
+        HIP_TRY(hipStreamWaitEvent(s, h->ev_out, 0));
+    }
+    return HD_OK;
+}
+
+extern "C" int hd_inpaint_decode_fix(hd_handle* h, hd_topology* topo, const uint8_t* fixed_mask, const float* x_known,
+                                     const float* h_known, float* x, float* hfeat, void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_inpaint_decode_fix: null handle/topology");
+    if (topo->h != h) return fail(HD_E_INVALID, "hd_inpaint_decode_fix: topology belongs to another handle");
+    if (!fixed_mask || !x_known || !h_known || !x || !hfeat) return fail(HD_E_INVALID, "hd_inpaint_decode_fix: null tensor");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    ProfScope ps(h, s, 2);
+    InpaintFixArgs a;
+    a.nm = topo->nm_bytes; a.fixed = fixed_mask; a.x_known = x_known; a.h_known = h_known; a.x = x; a.hfeat = hfeat;
+    a.B = topo->B; a.N = topo->N; a.F = h->F;
+    hipLaunchKernelGGL(k_inpaint_decode_fix, dim3((topo->B + 3) / 4), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
     return HD_OK;
 }
 

@@ -1,0 +1,193 @@
+// Fragment-constrained sampling ("inpainting", hd_sample_loop_inpaint): the replacement step behind every posterior step, the
+// jump back of a resampling round and the fix-up behind the final decode.  No reference counterpart: the known fragments of a
+// molecule are re-noised to the level of the current step and put in place of the generated rows (the replacement method of
+// score-based models; with resamplings > 1 the RePaint form).  Included through kernels.hpp, after k_sampling.hpp.
+//
+// One workgroup (256 threads) per molecule, one thread per (node, component) as in k_post_step; every sum runs over the
+// workgroup in the fixed order of block_sum4 (no atomics), so a molecule's bits depend on its own rows alone.  Exact fp32.
+// Step index, draw and first sample id come from kernel arguments (plain launches) or from device words (graph replay).
+#pragma once
+#include "k_sampling.hpp"
+
+struct InpaintArgs {
+    float* z;                   // [B][N][D] in place: z_gen -> z_s (replace), z_s -> z_t (jump)
+    const uint8_t* nm;          // [B*N] node mask bytes
+    const uint8_t* fixed;       // [B*N] fixed mask bytes (replace only)
+    const float* known;         // [B][N][D] normalised known values (replace only)
+    const float* coef;          // [T][4] {alpha_s, sigma_s, alpha_t|s, sigma_t|s}, row s
+    uint64_t seed, sample_base;
+    uint32_t draw;
+    int step;
+    const uint32_t* draw_ptr;   // optional device-side draw (graph replay); overrides draw
+    const int* step_ptr;        // optional device-side step index; overrides step
+    const unsigned long long* base_ptr;   // optional device-side first global sample id; overrides sample_base
+    int B, N, D;
+};
+
+// steps 2-3 of the algorithm (include/hierdiff_hip.h): z_kn = alpha_s known + sigma_s e_kn on the fixed rows, shifted so that the
+// fixed block keeps the centre of gravity the generated rows had, then the masked mean removal of the plain step.
+// A molecule without fixed nodes is left untouched.  Dynamic LDS = N * D floats.
+__global__ __launch_bounds__(256) void k_inpaint_replace(InpaintArgs a) {
+    extern __shared__ float ip_s[];                // [N * D] blended z before the final re-centring
+    __shared__ float red[4];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x;
+    const int N = a.N, D = a.D, total = N * D;
+    float nf = 0.f;
+    for (int nn = tid; nn < N; nn += 256) nf += (a.fixed[b * N + nn] && a.nm[b * N + nn]) ? 1.f : 0.f;
+    nf = block_sum4(nf, red, tid);
+    if (nf == 0.f) return;                         // uniform over the workgroup
+    const uint64_t sid = (a.base_ptr ? (uint64_t)*a.base_ptr : a.sample_base) + (uint64_t)b;
+    const uint32_t draw = a.draw_ptr ? *a.draw_ptr : a.draw;
+    const float* cf = a.coef + (size_t)(a.step_ptr ? *a.step_ptr : a.step) * 4;
+    const float alpha_s = cf[0], sigma_s = cf[1];
+    float sg[3] = {0.f, 0.f, 0.f}, sk[3] = {0.f, 0.f, 0.f}, cnt = 0.f;
+    for (int e = tid; e < total; e += 256) {
+        const int nn = e / D, c = e - nn * D;
+        const bool valid = a.nm[b * N + nn] != 0;
+        const bool fx = valid && a.fixed[b * N + nn] != 0;
+        const size_t g = ((size_t)b * N + nn) * D + c;
+        const float zg = a.z[g];
+        float v = zg;
+        if (fx) v = alpha_s * a.known[g] + sigma_s * philox_normal(a.seed, sid, draw, (uint32_t)e);
+        ip_s[e] = v;
+        if (c < 3) {
+            if (fx) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { if (c == k) { sg[k] += zg; sk[k] += v; } }
+            }
+            if (c == 0 && valid) cnt += 1.f;
+        }
+    }
+    float shift[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) shift[k] = block_sum4(sg[k], red, tid) / nf - block_sum4(sk[k], red, tid) / nf;
+    cnt = block_sum4(cnt, red, tid);
+    float sv[3] = {0.f, 0.f, 0.f};
+    for (int e = tid; e < total; e += 256) {       // each thread revisits its own elements: no barrier needed on ip_s
+        const int nn = e / D, c = e - nn * D;
+        if (c < 3) {
+            float v = ip_s[e];
+            if (a.nm[b * N + nn] && a.fixed[b * N + nn]) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { if (c == k) v += shift[k]; }
+                ip_s[e] = v;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { if (c == k) sv[k] += v; }
+        }
+    }
+    float mean[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) mean[k] = block_sum4(sv[k], red, tid) / cnt;
+    for (int e = tid; e < total; e += 256) {
+        const int nn = e / D, c = e - nn * D;
+        float v = ip_s[e];
+        if (c < 3) {
+            const float m = a.nm[b * N + nn] ? 1.f : 0.f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { if (c == k) v -= mean[k] * m; }
+        }
+        a.z[((size_t)b * N + nn) * D + c] = v;
+    }
+}
+
+// step 4: z_t = alpha_t|s z_s + sigma_t|s e_jump, e_jump the combined noise of the plain step (masked, x part mean-free over the
+// molecule's valid nodes).  Dynamic LDS = N * D floats.
+__global__ __launch_bounds__(256) void k_inpaint_jump(InpaintArgs a) {
+    extern __shared__ float ip_s[];                // [N * D] masked raw normals
+    __shared__ float red[4];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x;
+    const int N = a.N, D = a.D, total = N * D;
+    const uint64_t sid = (a.base_ptr ? (uint64_t)*a.base_ptr : a.sample_base) + (uint64_t)b;
+    const uint32_t draw = a.draw_ptr ? *a.draw_ptr : a.draw;
+    const float* cf = a.coef + (size_t)(a.step_ptr ? *a.step_ptr : a.step) * 4;
+    const float alpha_ts = cf[2], sigma_ts = cf[3];
+    float sn[3] = {0.f, 0.f, 0.f}, cnt = 0.f;
+    for (int e = tid; e < total; e += 256) {
+        const int nn = e / D, c = e - nn * D;
+        const float m = a.nm[b * N + nn] ? 1.f : 0.f;
+        const float z = philox_normal(a.seed, sid, draw, (uint32_t)e) * m;
+        ip_s[e] = z;
+        if (c < 3) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { if (c == k) sn[k] += z; }
+            if (c == 0) cnt += m;
+        }
+    }
+    float nmn[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) nmn[k] = block_sum4(sn[k], red, tid);
+    cnt = block_sum4(cnt, red, tid);
+    if (cnt == 0.f) return;                        // a molecule without valid nodes stays all zero
+#pragma unroll
+    for (int k = 0; k < 3; ++k) nmn[k] /= cnt;
+    for (int e = tid; e < total; e += 256) {
+        const int nn = e / D, c = e - nn * D;
+        float z = ip_s[e];
+        if (c < 3) {
+            const float m = a.nm[b * N + nn] ? 1.f : 0.f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { if (c == k) z -= nmn[k] * m; }
+        }
+        const size_t g = ((size_t)b * N + nn) * D + c;
+        a.z[g] = alpha_ts * a.z[g] + sigma_ts * z;
+    }
+}
+
+// Behind the final decode, in data units: h = h_known and x = x_known + (mean_fixed(x) - mean_fixed(x_known)) on the fixed rows - the
+// returned fragments are a pure translation of the given ones.  One wavefront per molecule.
+struct InpaintFixArgs {
+    const uint8_t* nm;
+    const uint8_t* fixed;
+    const float* x_known;       // [B][N][3]
+    const float* h_known;       // [B][N][F]
+    float* x;                   // [B][N][3]
+    float* hfeat;               // [B][N][F]
+    int B, N, F;
+};
+
+__global__ void k_inpaint_decode_fix(InpaintFixArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (b >= a.B) return;
+    float sd[3] = {0.f, 0.f, 0.f}, sk[3] = {0.f, 0.f, 0.f}, nf = 0.f;
+    for (int nn = lane; nn < a.N; nn += 64) {
+        const size_t r = (size_t)b * a.N + nn;
+        if (a.nm[r] && a.fixed[r]) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { sd[k] += a.x[r * 3 + k]; sk[k] += a.x_known[r * 3 + k]; }
+            nf += 1.f;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        nf += __shfl_xor(nf, o);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { sd[k] += __shfl_xor(sd[k], o); sk[k] += __shfl_xor(sk[k], o); }
+    }
+    if (nf == 0.f) return;
+    float shift[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) shift[k] = sd[k] / nf - sk[k] / nf;
+    for (int nn = lane; nn < a.N; nn += 64) {
+        const size_t r = (size_t)b * a.N + nn;
+        if (!(a.nm[r] && a.fixed[r])) continue;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a.x[r * 3 + k] = a.x_known[r * 3 + k] + shift[k];
+        for (int f = 0; f < a.F; ++f) a.hfeat[r * a.F + f] = a.h_known[r * a.F + f];
+    }
+}
+
+// graph-replay helpers of the inpainting loop: draws[i] = (T + 2) * i + (T - s) for the 3 * resamplings streams of a step
+// (stream 3 j + k: round j, k = 0 posterior step, 1 known-part noise, 2 jump noise), moved on by one per step
+__global__ void k_inpaint_state(uint32_t* draws, int n, uint32_t stride, uint32_t d0) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) draws[i] = stride * (uint32_t)i + d0;
+}
+
+__global__ void k_inpaint_advance(uint32_t* draws, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) draws[i] += 1;
+}

@@ -800,6 +800,161 @@ class DiffusionQM9(_Base):
             x, hfeat = self._final_decode(z, eps, node_mask, edge_mask, coef3, fix_noise, final_raw)
         return x, hfeat
 
+    # ------------------------------------------------------------------ fragment-constrained sampling (no reference counterpart)
+    def _inpaint_schedule(self, handle, tabs):
+        """{alpha_s, sigma_s, alpha_t|s, sigma_t|s} per step from the gamma grid of `_schedule`, uploaded once per table."""
+        if self.__dict__.get("_inpaint_tabs") is not tabs:
+            g = tabs["gamma"].to(torch.float32).reshape(-1)[:-1]
+            coef = tabs["coef"]
+            rows = torch.stack([torch.sqrt(torch.sigmoid(-g)), torch.sqrt(torch.sigmoid(g)), coef[:, 0], torch.sqrt(coef[:, 1])], dim=1)
+            rows = np.ascontiguousarray(rows.numpy(), dtype=np.float32)
+            _lib.check(_lib.load().hd_set_inpaint_schedule(handle, self.T, rows.ctypes.data_as(C.POINTER(C.c_float))),
+                       "hd_set_inpaint_schedule")
+            self._inpaint_tabs = tabs
+        return tabs
+
+    def _inpaint_setup(self, node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask):
+        """Argument checks of the inpainting entry points (ValueError / NotImplementedError before anything is queued), then the
+        device-side inputs of hd_sample_loop_inpaint."""
+        if node_mask.dim() != 3 or node_mask.shape[2] != 1:
+            raise ValueError(f"node_mask must be [B, N, 1], got {tuple(node_mask.shape)}")
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        F_ = self.in_node_nf
+        if tuple(fixed_mask.shape) != (B, N, 1):
+            raise ValueError(f"fixed_mask must be [{B}, {N}, 1], got {tuple(fixed_mask.shape)}")
+        if tuple(x_known.shape) != (B, N, self.n_dims):
+            raise ValueError(f"x_known must be [{B}, {N}, {self.n_dims}], got {tuple(x_known.shape)}")
+        if tuple(h_known.shape) != (B, N, F_):
+            raise ValueError(f"h_known must be [{B}, {N}, {F_}], got {tuple(h_known.shape)}")
+        if isinstance(resamplings, bool) or int(resamplings) != resamplings or int(resamplings) < 1:
+            raise ValueError(f"resamplings must be an integer >= 1, got {resamplings!r}")
+        if (self.T + 2) * 3 * int(resamplings) >= 2 ** 32:
+            raise ValueError("(timesteps + 2) * 3 * resamplings exceeds the generator's 32-bit draw index")
+        dev = node_mask.device
+        nmb, fmb = node_mask.to(torch.bool), fixed_mask.to(dev).to(torch.bool)
+        if bool((fmb & ~nmb).any()):
+            raise ValueError("fixed_mask must be a subset of node_mask")
+        if edge_mask is not None and edge_mask.numel() != B * N * N:
+            raise ValueError(f"edge_mask must hold {B} x {N} x {N} entries")
+        if self.dynamics.context_node_nf > 0 and context is None:
+            raise ValueError("context required")
+        if self.pocket:
+            raise NotImplementedError("inpainting: pocket models are not supported")
+        if getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics":
+            raise NotImplementedError("inpainting: mode 'gnn_dynamics' is not supported")
+        if self.noise_mode == "torch":
+            raise NotImplementedError("inpainting: noise_mode 'torch' is not supported (counter-based noise only)")
+        if dev.type != "cuda":
+            raise _lib.HierDiffHipError("sampling runs only on an MI355X (no CPU fallback)")
+        h = self._lib_handle()
+        tabs = self._inpaint_schedule(h, self._schedule(rows=B))
+        topo = self.dynamics.topology(node_mask, edge_mask, B, N)
+        ctx = None
+        if self.dynamics.context_node_nf > 0:
+            ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
+        xk = x_known.to(dev, torch.float32).contiguous()
+        hk = h_known.to(dev, torch.float32).contiguous()
+        # the model's own `normalize`, masked by the fixed rows (the library ignores the others)
+        xh_known = torch.cat([xk / float(self.norm_values[0]),
+                              (hk - float(self.norm_biases[1] or 0.0)) / float(self.norm_values[1])], dim=2)
+        xh_known = torch.where(fmb, xh_known, torch.zeros_like(xh_known)).contiguous()
+        fm_u8 = fmb.reshape(B * N).to(torch.uint8).contiguous()
+        return AttrDict(h=h, tabs=tabs, topo=topo, ctx=ctx, xk=xk, hk=hk, xh_known=xh_known, fm_u8=fm_u8, B=B, N=N,
+                        R=int(resamplings), stream=_stream(dev), dev=dev)
+
+    def _inpaint_run(self, st, z, s_hi, s_lo, sample_id_base):
+        _lib.check(_lib.load().hd_sample_loop_inpaint(
+            st.h, st.topo.ptr, z.data_ptr(), _ptr(st.ctx), -1, s_hi, s_lo, None, None, st.B, self.seed, sample_id_base,
+            int(self.use_graph), st.fm_u8.data_ptr(), st.xh_known.data_ptr(), st.R, st.stream), "hd_sample_loop_inpaint")
+
+    @torch.no_grad()
+    def inpaint_steps(self, z, s_hi: int, s_lo: int, node_mask, fixed_mask, x_known, h_known, context=None, resamplings: int = 1,
+                      sample_id_base: int = 0, edge_mask=None):
+        """The steps s = s_hi-1 ... s_lo of `sample_inpaint`'s loop on a given z_{s_hi} [B,N,D] (normalised units); returns z_{s_lo}.
+        Draws are keyed by the step, so a chain cut into pieces gives the bits of the whole."""
+        st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask)
+        if tuple(z.shape) != (st.B, st.N, self.n_dims + self.in_node_nf) or not (0 <= s_lo <= s_hi <= self.T):
+            raise ValueError("z must be [B, N, 3 + F] and 0 <= s_lo <= s_hi <= timesteps")
+        z = z.detach().to(st.dev, torch.float32).clone().contiguous()
+        self._inpaint_run(st, z, int(s_hi), int(s_lo), sample_id_base)
+        return z
+
+    @torch.no_grad()
+    def sample_inpaint(self, node_mask: torch.Tensor, fixed_mask: torch.Tensor, x_known: torch.Tensor, h_known: torch.Tensor,
+                       context=None, resamplings: int = 1, sample_id_base: int = 0, edge_mask: Optional[torch.Tensor] = None):
+        """(x, h) on the device for molecules whose `fixed_mask` [B,N,1] nodes are known: `x_known` [B,N,3] / `h_known` [B,N,F] in
+        data units (what `sample` returns; rows outside `fixed_mask` are ignored, the frame of the positions is free).  The free
+        nodes are sampled around them by the replacement method, `resamplings` network calls per step (RePaint for > 1), inside
+        the library's loop (hd_sample_loop_inpaint; algorithm and draw layout in include/hierdiff_hip.h).  Returned fixed rows:
+        h = h_known exactly, x = x_known translated as one block.  Training-free conditioning: how well the free part fits the
+        known one depends on the model and on `resamplings`.  A sample depends on its global id (sample_id_base + row), its
+        masks, the weights and its known values only."""
+        st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask)
+        lib, T, B, N = _lib.load(), self.T, st.B, st.N
+        z = torch.empty((B, N, self.n_dims + self.in_node_nf), device=st.dev, dtype=torch.float32)
+        _lib.check(lib.hd_noise(st.h, st.topo.ptr, None, None, B, self.seed, sample_id_base, 0, 0, z.data_ptr(), st.stream),
+                   "hd_noise")
+        if self.debug_checks:              # the loop's invariant after every step (host-synchronising, like the reference's asserts)
+            for s in reversed(range(T)):
+                self._inpaint_run(st, z, s + 1, s, sample_id_base)
+                self._check_mean_zero(z[:, :, :self.n_dims], node_mask)
+        else:
+            self._inpaint_run(st, z, T, 0, sample_id_base)
+        zeros = torch.zeros((B, 1), device=st.dev)
+        eps = self.dynamics.forward_with_topology(st.topo, zeros, z, st.ctx, None)
+        x, hfeat = self._final_decode(z, eps, node_mask, edge_mask, st.tabs["decode"].numpy(), False, None,
+                                      philox=(sample_id_base, T + 1))
+        x, hfeat = x.contiguous(), hfeat.contiguous()
+        _lib.check(lib.hd_inpaint_decode_fix(st.h, st.topo.ptr, st.fm_u8.data_ptr(), st.xk.data_ptr(), st.hk.data_ptr(),
+                                             x.data_ptr(), hfeat.data_ptr(), st.stream), "hd_inpaint_decode_fix")
+        return x, hfeat
+
+    @torch.no_grad()
+    def sample_grow(self, known: Sequence[Dict[str, torch.Tensor]], sizes, device, context=None, resamplings: int = 1,
+                    sample_id_base: int = 0):
+        """List-level form of `sample_inpaint` in `sample`'s result format: `known[i]` = {'x': [k_i,3], 'h': [k_i,F]} are the fragments
+        molecule i keeps (its first k_i rows in the result; k_i = 0 allowed), `sizes[i]` >= k_i its total number of fragments (one
+        integer: that many for every molecule).  `context`: as in `sample`.  Returns [{'x': [n_i,3], 'h': [n_i,F] (, 'context')}] on
+        the CPU."""
+        device = torch.device(device)
+        num = len(known)
+        if isinstance(sizes, (int, np.integer)):
+            sizes = [int(sizes)] * num
+        sizes = [int(n) for n in sizes]
+        if len(sizes) != num or num == 0:
+            raise ValueError("sizes must hold one total size per known molecule (and there must be at least one)")
+        ks = []
+        for i, mol in enumerate(known):
+            kx, kh = torch.as_tensor(mol["x"]), torch.as_tensor(mol["h"])
+            if kx.dim() != 2 or kx.shape[1] != self.n_dims or kh.dim() != 2 or tuple(kh.shape) != (kx.shape[0], self.in_node_nf):
+                raise ValueError(f"known[{i}]: need 'x' [k, {self.n_dims}] and 'h' [k, {self.in_node_nf}]")
+            if sizes[i] < max(1, kx.shape[0]):
+                raise ValueError(f"known[{i}]: total size {sizes[i]} is smaller than its {kx.shape[0]} known fragments (or zero)")
+            ks.append(int(kx.shape[0]))
+        n_max = max(sizes)
+        ar = torch.arange(n_max)
+        node_mask = (ar[None, :] < torch.tensor(sizes)[:, None]).unsqueeze(-1)
+        fixed_mask = (ar[None, :] < torch.tensor(ks)[:, None]).unsqueeze(-1)
+        x_known = torch.zeros(num, n_max, self.n_dims)
+        h_known = torch.zeros(num, n_max, self.in_node_nf)
+        for i, mol in enumerate(known):
+            x_known[i, :ks[i]] = torch.as_tensor(mol["x"], dtype=torch.float32)
+            h_known[i, :ks[i]] = torch.as_tensor(mol["h"], dtype=torch.float32)
+        ctx = None
+        if context is not None:
+            ctx = torch.zeros([num, n_max, 1]) + torch.as_tensor(context, dtype=torch.float32).cpu()
+            if ctx.shape != (num, n_max, 1):
+                raise ValueError(f"context of shape {tuple(torch.as_tensor(context).shape)} does not broadcast to [{num}, {n_max}, 1]")
+        x, h = self.sample_inpaint(node_mask.to(device), fixed_mask.to(device), x_known.to(device), h_known.to(device),
+                                   context=None if ctx is None else ctx.to(device), resamplings=resamplings,
+                                   sample_id_base=sample_id_base)
+        x, h = x.cpu(), h.cpu()
+        out = [{'x': x[i, :sizes[i]].clone(), 'h': h[i, :sizes[i]].clone()} for i in range(num)]
+        if ctx is not None:
+            for i in range(num):
+                out[i]['context'] = ctx[i, :sizes[i]].clone()
+        return out
+
     @torch.no_grad()
     def sample(self, num_samples, device, context=None, pocket_cond=None, sample_id_base: int = 0):
         """diffusion_qm9.py:347-395: list of {'x': [n_i,3], 'h': [n_i,8], ('context': [n_i,1])} on the CPU."""

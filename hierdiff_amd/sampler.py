@@ -9,6 +9,11 @@ molecules and write `sample_results.pkl` = `pickle((results, test_names))` with
 
     python -m hierdiff_amd.sampler --checkpoint diffusion.ckpt --batch-size 256 --num-batches 4 --out sample_results.pkl
 
+Fragment growing (no reference counterpart): `--known FILE --grow N [--resamplings R]` keeps the fragments of every molecule in
+FILE (this sampler's own output: a list of {'x', 'h'}, pickled alone or as the (results, test_names) tuple, or saved with torch.save
+as `.pt`) and samples N more around each (`DiffusionQM9.sample_grow`); the output format is unchanged, the known fragments come
+first.  Single process only.
+
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N`; rank 0's weights are broadcast once,
 each rank samples a contiguous share of the global sample ids and writes `<out>.rank<r>`; rank 0 concatenates
 them in id order into `<out>`.
@@ -106,6 +111,21 @@ def read_results(path: str) -> Tuple[List[dict], list]:
     return res[0], res[1]
 
 
+def read_known(path: str) -> List[dict]:
+    """`--known`: a list of {'x': [k,3], 'h': [k,8]} - `.pt` files through torch.load(weights_only=True), anything else as a pickle
+    of the list or of the sampler's (results, test_names) tuple."""
+    if path.endswith(".pt"):
+        obj = torch.load(path, map_location="cpu", weights_only=True)
+    else:
+        with open(path, "rb") as f:
+            obj = pickle.load(f)
+    if isinstance(obj, tuple) and len(obj) == 2 and isinstance(obj[0], list):
+        obj = obj[0]
+    if not isinstance(obj, list) or not all(isinstance(m, dict) and "x" in m and "h" in m for m in obj):
+        raise ValueError(f"{path}: expected a list of {{'x', 'h'}} dicts (the sampler's output format)")
+    return obj
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--checkpoint", default=None, help="reference Lightning checkpoint (.ckpt); random init if omitted")
@@ -127,7 +147,16 @@ def main(argv=None) -> int:
                     help="the reference's model YAML (conf/model/ddpmgblur.yaml); overrides --hidden-nf / --n-layers / --timesteps")
     ap.add_argument("--sample-config", default=None,
                     help="the reference's sample YAML (conf/sample/default.yaml: batch_size, num_batches)")
+    ap.add_argument("--known", default=None,
+                    help="fragment growing: file with the fragments to keep (the sampler's output format); needs --grow")
+    ap.add_argument("--grow", type=int, default=None, help="fragments to add to each molecule of --known")
+    ap.add_argument("--resamplings", type=int, default=1,
+                    help="network calls per diffusion step of --known runs (1: plain replacement; more: RePaint-style resampling)")
     args = ap.parse_args(argv)
+    if (args.known is None) != (args.grow is None):
+        ap.error("--known and --grow go together")
+    if args.known is not None and (args.grow < 0 or args.resamplings < 1):
+        ap.error("--grow must be >= 0 and --resamplings >= 1")
     if args.sample_config:
         args.batch_size, args.num_batches = load_sample_config(args.sample_config)
 
@@ -157,6 +186,19 @@ def main(argv=None) -> int:
     model.seed = args.seed
     if world > 1:
         broadcast_model_weights(model, src=0)
+
+    if args.known is not None:
+        if world > 1:
+            raise SystemExit("--known runs in a single process")
+        known = read_known(args.known)
+        grown: List[dict] = []
+        for b, lo in enumerate(range(0, len(known), max(1, args.batch_size))):
+            part = known[lo:lo + max(1, args.batch_size)]
+            ctx = None if not args.context else args.context[b % len(args.context)]
+            grown.extend(model.sample_grow(part, [int(m["x"].shape[0]) + args.grow for m in part], dev, context=ctx,
+                                           resamplings=args.resamplings, sample_id_base=lo))
+        write_results(args.out, grown)
+        return 0
 
     torch.manual_seed(args.seed)           # the node-count draw uses torch's CPU generator (distributions.py)
     results: List[dict] = []

@@ -29,6 +29,7 @@
  *   hd_final_decode              <- sample_p_xh_given_z0 after the network call (:302-310)
  *   hd_noise                     <- sample_combined_position_feature_noise (:445-456)
  *   hd_sample_loop               <- the timestep loop of DiffusionQM9.sample (:375-384)
+ *   hd_sample_loop_inpaint       <- no counterpart: the same loop with known fragments kept in place
  */
 #ifndef HIERDIFF_HIP_H
 #define HIERDIFF_HIP_H
@@ -172,7 +173,14 @@ int hd_final_decode(hd_handle* h, hd_topology* topo, const float* z0, const floa
 /* z[rows,N,3+F] = masked, centre-of-gravity-free combined noise from raw normals (rows = B), or,
  * with raw_x == NULL, from the library's counter-based generator (Philox4x32-10 + Box-Muller):
  * normal(seed, sample_id_base + b, draw, n*D + c).  share_rows != 0 draws one row (sample id
- * sample_id_base) and broadcasts it over the batch before masking (fix_noise). */
+ * sample_id_base) and broadcasts it over the batch before masking (fix_noise).
+ *
+ * Draw layout of one sample (seed, sample id): every normal is normal(seed, sample id, draw, n*D + c).
+ *   plain sampling        draw 0 = z_T, draw T - s = the posterior step s (t = s + 1), draw T + 1 = the final decode;
+ *   inpainting loop       draw = (T + 2) * (3 j + k) + (T - s) for resampling round j = 0 .. r-1 of step s and stream
+ *                         k = 0 posterior step, 1 noise of the known part (e_kn), 2 noise of the jump back (e_jump).
+ *                         (j, k) = (0, 0) is the plain stream, so r = 1 without fixed nodes reproduces plain sampling bit for bit;
+ *                         (T + 2) * 3 r must fit 32 bits. */
 int hd_noise(hd_handle* h, hd_topology* topo, const float* raw_x, const float* raw_h, int noise_rows,
              uint64_t seed, uint64_t sample_id_base, uint32_t draw, int share_rows, float* z, void* stream);
 
@@ -190,6 +198,39 @@ int hd_set_schedule(hd_handle* h, int T, const float* tau, const float* coef4);
 int hd_sample_loop(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
                    int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
                    uint64_t seed, uint64_t sample_id_base, int use_graph, void* stream);
+
+/* ---- Fragment-constrained sampling ("inpainting"; ABI 12, additive; no reference counterpart): sample the free nodes of a
+ * molecule around fragments whose positions and features are known, by the replacement method of score-based models, optionally with
+ * RePaint-style resampling.  For s = s_hi-1 ... s_lo, t = s + 1, and round j = 0 .. resamplings-1:
+ *   1. z_gen = the posterior step of the plain loop (network call at tau[t], noise, masked mean removal), unchanged;
+ *   2. z_kn  = alpha_s xh_known + sigma_s e_kn on the fixed rows (e_kn standard normal per node and component);
+ *   3. per molecule c = mean_fixed(z_gen.x) - mean_fixed(z_kn.x); z_s = where(fixed, z_kn + [c, 0], z_gen), then the masked mean
+ *      removal of the x part the plain step ends with.  A molecule without fixed nodes keeps z_gen bit for bit;
+ *   4. if j < resamplings-1: z_t = alpha_t|s z_s + sigma_t|s e_jump (e_jump: combined noise, masked, x part mean-free over the valid
+ *      nodes) and back to 1 at the same (s, t).
+ * Noise comes from the counter-based generator only, in the draw layout documented at the noise entry point above: a sample's bits
+ * depend on its global id, its masks, the weights and its known values - not on the batch it runs in.  Sums over a molecule's nodes
+ * run in a fixed order (no atomics).
+ *
+ * Schedule rows for the loop: host array of T rows {alpha_s, sigma_s, alpha_t_given_s, sigma_t_given_s} for s = 0..T-1 (t = s+1), from the
+ * same gamma grid as the plain schedule; T must equal the T of the last schedule upload, and a new plain schedule needs a new upload here. */
+int hd_set_inpaint_schedule(hd_handle* h, int T, const float* coef4);
+/* The arguments of the plain loop plus
+ *   fixed_mask   device bytes [B*N] (0 = free), a subset of the node mask (rows outside it are ignored);
+ *   xh_known     device [B,N,D] NORMALISED known positions and features (rows outside fixed_mask are ignored);
+ *   resamplings  r >= 1.
+ * Restrictions (HD_E_INVALID): raw_x / raw_h must be NULL, noise_rows = B, mol_shape < 0 or = N (no pocket rows).
+ * use_graph: one captured step (all its rounds) per topology, cached like the plain loop's and rebuilt when resamplings, seed,
+ * weights or schedule change; use_graph = 0 gives the same bits.  Stream-ordered, no host synchronisation in steady state. */
+int hd_sample_loop_inpaint(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
+                           int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
+                           uint64_t seed, uint64_t sample_id_base, int use_graph, const uint8_t* fixed_mask,
+                           const float* xh_known, int resamplings, void* stream);
+/* Behind the final decode, in DATA units (after unnormalize): on the fixed rows hfeat = h_known exactly and
+ * x = x_known + (mean_fixed(x) - mean_fixed(x_known)), so the returned fragments are a pure translation of the given ones.
+ * x, x_known device [B,N,3]; hfeat, h_known device [B,N,F]; other rows and molecules without fixed nodes are untouched. */
+int hd_inpaint_decode_fix(hd_handle* h, hd_topology* topo, const uint8_t* fixed_mask, const float* x_known,
+                          const float* h_known, float* x, float* hfeat, void* stream);
 
 /* ---- Training primitives (the handle's hd_config.precision must be 0; the fp16x3 contractions are chosen per call below).
  * One "edge layer" is the part of a GCL / EquivariantUpdate that works on edges (egnn_new.py:35-56 / :91-104 with the
