@@ -2105,8 +2105,9 @@ static int egcl_forward_impl(hd_egcl* g, hd_egcl_graph* t, const float* h, const
     if (!g->weights_set) return fail(HD_E_STATE, "hd_egcl_forward: weights not set (hd_egcl_set_weights)");
     if (!h || !x || !h_out || !x_out) return fail(HD_E_INVALID, "hd_egcl_forward: null tensor");
     const hd_egcl_config& c = g->cfg;
-    if (g->De > 0 && !edge_attr) return fail(HD_E_INVALID, "hd_egcl_forward: edge_attr required");
-    if (c.edge_update && !edge_attr_out) return fail(HD_E_INVALID, "hd_egcl_forward: edge_attr_out required with edge_update");
+    // (a graph without edges has zero-length edge tensors: their pointers are not read and may be NULL)
+    if (g->De > 0 && t->E > 0 && !edge_attr) return fail(HD_E_INVALID, "hd_egcl_forward: edge_attr required");
+    if (c.edge_update && t->E > 0 && !edge_attr_out) return fail(HD_E_INVALID, "hd_egcl_forward: edge_attr_out required with edge_update");
     HIP_TRY(hipSetDevice(g->device));
     hipStream_t s = (hipStream_t)stream;
     const int H = g->H, De = g->De, ctx = g->ctx, M = t->M, E = t->E;
@@ -2942,7 +2943,7 @@ extern "C" int hd_egcl_backward(hd_egcl* g, hd_egcl_graph* t, const float* h, co
     if (!g->weights_set) return fail(HD_E_STATE, "hd_egcl_backward: weights not set (hd_egcl_set_weights)");
     if (!h || !x || !saved || !dh || !dx || !dweights) return fail(HD_E_INVALID, "hd_egcl_backward: null tensor");
     const hd_egcl_config& c = g->cfg;
-    if (g->De > 0 && !edge_attr) return fail(HD_E_INVALID, "hd_egcl_backward: edge_attr required");
+    if (g->De > 0 && t->E > 0 && !edge_attr) return fail(HD_E_INVALID, "hd_egcl_backward: edge_attr required");
     HIP_TRY(hipSetDevice(g->device));
     hipStream_t s = (hipStream_t)stream;
     const int H = g->H, De = g->De, ctx = g->ctx, M = t->M, E = t->E, W = H + ctx;
@@ -3113,7 +3114,7 @@ static int refine_device(int device, const char* what) {
 extern "C" int hd_refine_embed_forward(int device, const long long* v, const long long* size, int M, int H, int nv, int ns,
                                        const float* Ev, const float* Es, float* out, int ldo, int off_v, int off_s, int* bad,
                                        void* stream) {
-    if (!v || !size || !Ev || !Es || !out || !bad) return fail(HD_E_INVALID, "hd_refine_embed_forward: null argument");
+    if (!Ev || !Es || !bad || (M > 0 && (!v || !size || !out))) return fail(HD_E_INVALID, "hd_refine_embed_forward: null argument");
     if (M < 0 || H < 1 || nv < 1 || ns < 1 || off_v < 0 || off_s < 0 || ldo < std::max(off_v, off_s) + H)
         return fail(HD_E_INVALID, "hd_refine_embed_forward: bad shape");
     HD_TRY(refine_device(device, "hd_refine_embed_forward"));
@@ -3127,7 +3128,7 @@ extern "C" int hd_refine_embed_forward(int device, const long long* v, const lon
 
 extern "C" int hd_refine_embed_backward(int device, const long long* v, const long long* size, int M, int H, int nv, int ns,
                                         const float* dout, int ldo, int off_v, int off_s, float* dEv, float* dEs, void* stream) {
-    if (!v || !size || !dout || !dEv || !dEs) return fail(HD_E_INVALID, "hd_refine_embed_backward: null argument");
+    if (!dEv || !dEs || (M > 0 && (!v || !size || !dout))) return fail(HD_E_INVALID, "hd_refine_embed_backward: null argument");
     if (M < 0 || H < 1 || nv < 1 || ns < 1 || off_v < 0 || off_s < 0 || ldo < std::max(off_v, off_s) + H)
         return fail(HD_E_INVALID, "hd_refine_embed_backward: bad shape");
     HD_TRY(refine_device(device, "hd_refine_embed_backward"));
@@ -3138,7 +3139,7 @@ extern "C" int hd_refine_embed_backward(int device, const long long* v, const lo
 }
 
 extern "C" int hd_sqdist_forward(hd_egcl_graph* t, const float* x, float* ea, void* stream) {
-    if (!t || !x || !ea) return fail(HD_E_INVALID, "hd_sqdist_forward: null argument");
+    if (!t || !x || (t->E > 0 && !ea)) return fail(HD_E_INVALID, "hd_sqdist_forward: null argument");
     if (t->E == 0) return HD_OK;
     HIP_TRY(hipSetDevice(t->device));
     hipLaunchKernelGGL(k_sqdist, dim3((unsigned)((t->E + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t->row, t->col, t->E, x, ea);

@@ -317,7 +317,9 @@ int hd_egcl_set_weights(hd_egcl* g, const float* blob, long long n, int on_devic
 int hd_egcl_graph_create(hd_egcl* g, const int* row, const int* col, int M, int E, hd_egcl_graph** out);
 int hd_egcl_graph_destroy(hd_egcl_graph* t);
 /* (h_out [M][H+ctx], x_out [M][3], edge_attr_out [E][H]) = E_GCL.forward(h [M][H+ctx], edges, x [M][3], edge_attr [E][De],
- * node_mask [M] or NULL, edge_mask [E] or NULL); all device fp32; edge_attr_out only with edge_update. */
+ * node_mask [M] or NULL, edge_mask [E] or NULL); all device fp32; edge_attr_out only with edge_update.  A graph with E = 0 is
+ * valid (the node model on a zero aggregate): its zero-length edge tensors - edge_attr, edge_attr_out, and edge_mask,
+ * dedge_attr_out, dedge_attr of the calls below - are never read or written and may be NULL. */
 int hd_egcl_forward(hd_egcl* g, hd_egcl_graph* t, const float* h, const float* x, const float* edge_attr,
                     const float* node_mask, const float* edge_mask, float* h_out, float* x_out, float* edge_attr_out,
                     void* stream);
@@ -341,13 +343,14 @@ int hd_egcl_backward(hd_egcl* g, hd_egcl_graph* t, const float* h, const float* 
 /* ---- Refine model (Node2Vec, models/model_refine.py of the reference; ABI 12, additive), exact fp32, deterministic.
  * Input gather: out [M][ldo] columns off_v.. = Ev [nv][H] row v[m], columns off_s.. = Es [ns][H] row size[m] (v, size: device int64
  * [M]).  An id outside its table writes zeros and sets *bad = 1 (a device int the caller zeroes and reads); it is never dereferenced.
- * Backward: dEv [nv][H] and dEs [ns][H] = per-id sums of the same columns of dout, rows added in ascending order. */
+ * Backward: dEv [nv][H] and dEs [ns][H] = per-id sums of the same columns of dout, rows added in ascending order; the row of an
+ * id that never occurs is zero.  M = 0 is valid (the backward writes zero tables); v, size, out / dout may then be NULL. */
 int hd_refine_embed_forward(int device, const long long* v, const long long* size, int M, int H, int nv, int ns, const float* Ev,
                             const float* Es, float* out, int ldo, int off_v, int off_s, int* bad, void* stream);
 int hd_refine_embed_backward(int device, const long long* v, const long long* size, int M, int H, int nv, int ns, const float* dout,
                              int ldo, int off_v, int off_s, float* dEv, float* dEs, void* stream);
 /* Edge attribute on an E_GCL edge graph: ea [E] = |x[row] - x[col]|^2 (x [M][3]); backward dx [M][3] from dea [E], summed per
- * node over the graph's CSR lists (first the edges the node sends, then those it receives). */
+ * node over the graph's CSR lists (first the edges the node sends, then those it receives).  E = 0: ea / dea may be NULL, dx = 0. */
 int hd_sqdist_forward(hd_egcl_graph* t, const float* x, float* ea, void* stream);
 int hd_sqdist_backward(hd_egcl_graph* t, const float* x, const float* dea, float* dx, void* stream);
 /* Size-restricted softmax head.  logits [B][ld] (first ncols columns); candidate sets cand_ids (device int32, set s at

@@ -338,3 +338,107 @@ def test_training_step_launches_the_new_kernels_and_no_blas_library_kernel():
     assert not blas, blas
     for k in ("k_cand_xent", "k_cand_xent_bwd", "k_refine_embed", "k_refine_embed_bwd", "k_sqdist", "k_sqdist_bwd", "k_tgemm"):
         assert any(k in n for n in names), k
+
+
+# ----------------------------------------------------------------------------- the refine kernels at their edges
+def _sqdist_both(row, col, M, seed):
+    """(ea, dx) of hd_sqdist_forward / _backward on a graph and of float64 torch, for a random upstream gradient."""
+    from hierdiff_amd.refine import _SqDist
+    from hierdiff_amd.stage2 import E_GCL
+    rng = np.random.Generator(np.random.PCG64(seed))
+    E = int(row.numel())
+    layer = E_GCL(32, 32, 32, edges_in_d=1, attention=True, tanh=True, coords_range=30, edge_update=False).to(DEV)
+    g = layer._graph(row.to(torch.int32), col.to(torch.int32), M)
+    x0 = rng.standard_normal((M, 3)).astype(np.float32)
+    up = torch.from_numpy(rng.standard_normal((E, 1)).astype(np.float32))
+    x = torch.from_numpy(x0).to(DEV).requires_grad_(True)
+    ea = _SqDist.apply(g, x)
+    (ea * up.to(DEV)).sum().backward()
+    xr = torch.from_numpy(x0).double().requires_grad_(True)
+    ref = ((xr[row.long()] - xr[col.long()]) ** 2).sum(1, keepdim=True)
+    (ref * up.double()).sum().backward()
+    return ea.detach().cpu(), x.grad.cpu(), ref.detach(), xr.grad
+
+
+@pytest.mark.autograd
+@pytest.mark.parametrize("M,E", [(300, 3001), (257, 700), (1000, 517)])
+def test_sqdist_on_a_ragged_graph(M, E):
+    """Isolated, send-only and receive-only nodes (empty CSR lists), a hub on 40 % of the edges, self and repeated edges; M not a
+    multiple of the kernel's 256 nodes per workgroup."""
+    from tests.fuzz_egcl_grads import ragged_graph
+    rng = np.random.Generator(np.random.PCG64([9, M, E]))
+    row, col = ragged_graph(rng, M, E, self_edges=True)
+    row[:7], col[:7] = row[7:14], col[7:14]                                  # repeated edges for certain ...
+    col[14:20] = row[14:20]                                                  # ... and self edges
+    deg = torch.bincount(torch.cat([row, col]), minlength=M)
+    assert int((deg == 0).sum()) > 0 and int(deg.max()) > E // 3
+    ea, dx, ref, dref = _sqdist_both(row, col, M, 10)
+    assert _rel(ea, ref) < 1e-6
+    assert _rel(dx, dref) < 1e-5
+    assert bool((dx[deg == 0] == 0).all()), "an isolated node has no gradient"
+
+
+@pytest.mark.autograd
+def test_sqdist_on_a_graph_without_edges():
+    none = torch.zeros(0, dtype=torch.long)
+    ea, dx, ref, dref = _sqdist_both(none, none, 5, 11)
+    assert ea.shape == (0, 1) and bool((dx == 0).all()) and bool((dref == 0).all())
+
+
+def _embed_bwd(v, s, dout, ldo, H, nv, ns, off_v, off_s):
+    from hierdiff_amd import _lib
+    M = int(v.numel())
+    dEv, dEs = torch.full((nv, H), float("nan"), device=DEV), torch.full((ns, H), float("nan"), device=DEV)
+    p = lambda t: None if t.numel() == 0 else t.data_ptr()
+    _lib.check(_lib.load().hd_refine_embed_backward(0, p(v), p(s), M, H, nv, ns, p(dout), ldo, off_v, off_s, dEv.data_ptr(),
+                                                    dEs.data_ptr(), torch.cuda.current_stream().cuda_stream), "hd_refine_embed_backward")
+    torch.cuda.synchronize()
+    return dEv.cpu(), dEs.cpu()
+
+
+@pytest.mark.parametrize("M", [0, 1, 255, 257, 700])
+@pytest.mark.parametrize("H", [32, 256])
+def test_embed_backward_at_its_edges(M, H):
+    """hd_refine_embed_backward through the C ABI: ids that never occur give exactly zero rows, one id carries every row (the size
+    table), M = 0 and M = 1, and `ldo` wider than the three column blocks with the two blocks anywhere in the row."""
+    rng = np.random.Generator(np.random.PCG64([12, M, H]))
+    nv, ns = 41, 7
+    ldo, off_v, off_s = 3 * H + 9, 5, 2 * H + 9
+    v = torch.from_numpy(rng.integers(0, 20, M) * 2)                     # only even ids below 40 occur
+    s = torch.full((M,), 3, dtype=torch.long)                            # one id carries every row
+    dout = torch.from_numpy(rng.standard_normal((M, ldo)).astype(np.float32))
+    dEv, dEs = _embed_bwd(v.to(DEV), s.to(DEV), dout.to(DEV), ldo, H, nv, ns, off_v, off_s)
+    rv = torch.zeros(nv, H, dtype=torch.float64).index_add_(0, v, dout[:, off_v:off_v + H].double())
+    rs = torch.zeros(ns, H, dtype=torch.float64).index_add_(0, s, dout[:, off_s:off_s + H].double())
+    assert bool(torch.isfinite(dEv).all()) and bool(torch.isfinite(dEs).all())
+    assert _rel(dEv, rv) < 1e-5 and _rel(dEs, rs) < 1e-5
+    unused = torch.ones(nv, dtype=torch.bool)
+    unused[v] = False
+    assert int(unused.sum()) >= 21 and bool((dEv[unused] == 0).all())
+    assert bool((dEs[torch.arange(ns) != 3] == 0).all())
+    if M <= 1:
+        assert torch.equal(dEs[3], dout[:, off_s:off_s + H].sum(0))
+
+
+def test_embed_forward_with_a_wide_row_and_no_rows():
+    from hierdiff_amd import _lib
+    lib = _lib.load()
+    H, nv, ns, ldo, off_v, off_s = 32, 11, 5, 3 * 32 + 6, 3, 70
+    rng = np.random.Generator(np.random.PCG64(13))
+    Ev = torch.from_numpy(rng.standard_normal((nv, H)).astype(np.float32)).to(DEV)
+    Es = torch.from_numpy(rng.standard_normal((ns, H)).astype(np.float32)).to(DEV)
+    bad = torch.zeros(1, dtype=torch.int32, device=DEV)
+    s = torch.cuda.current_stream().cuda_stream
+    _lib.check(lib.hd_refine_embed_forward(0, None, None, 0, H, nv, ns, Ev.data_ptr(), Es.data_ptr(), None, ldo, off_v, off_s,
+                                           bad.data_ptr(), s), "hd_refine_embed_forward")
+    v = torch.tensor([10, 0, 3], device=DEV)
+    z = torch.tensor([4, 4, 0], device=DEV)
+    out = torch.full((3, ldo), -7.0, device=DEV)
+    _lib.check(lib.hd_refine_embed_forward(0, v.data_ptr(), z.data_ptr(), 3, H, nv, ns, Ev.data_ptr(), Es.data_ptr(), out.data_ptr(), ldo,
+                                           off_v, off_s, bad.data_ptr(), s), "hd_refine_embed_forward")
+    assert int(bad.cpu()) == 0
+    assert torch.equal(out[:, off_v:off_v + H], Ev[v]) and torch.equal(out[:, off_s:off_s + H], Es[z])
+    keep = torch.ones(ldo, dtype=torch.bool)
+    keep[off_v:off_v + H] = False
+    keep[off_s:off_s + H] = False
+    assert bool((out[:, keep.to(DEV)] == -7.0).all())

@@ -432,6 +432,100 @@ def test_gemm_f32_three_layouts_vs_float64(M, N, K):
     assert torch.equal(dW, dW_b) and torch.equal(db, db_b)
 
 
+def _gemm_bar(got, ref, K, amax, bmax, what, cpu_f32=None):
+    """The GEMM bar of this file (rel-L2 < 2e-6) and, for a result that is one row or one column (a short vector, whose rel-L2 one
+    bad element can hide in), every element within 2e-6 sqrt(K) max|a| max|b|.  cpu_f32: the same quantity from torch's float32
+    arithmetic on the CPU - where THAT misses 2e-6 against float64 the operands cancel, and the bar is 4 x its rel-L2 (two float32
+    summation orders differ by a factor of a few; a dropped chunk is caught by the element bound, which does not move)."""
+    got, ref = got.double().cpu().numpy(), ref.double().cpu().numpy()
+    r = rel_l2(got, ref)
+    bar = 2e-6 if cpu_f32 is None else max(2e-6, 4 * rel_l2(cpu_f32.double().cpu().numpy(), ref))
+    assert r < bar, f"{what}: rel-L2 {r:.2e} (bar {bar:.2e})"
+    if min(ref.shape) == 1:
+        worst = float(np.abs(got - ref).max())
+        assert worst <= 2e-6 * np.sqrt(K) * amax * bmax, f"{what}: element off by {worst:.2e}"
+
+
+@pytest.mark.parametrize("K", [31, 511, 512, 513, 4100, 8193])
+def test_gemm_f32_in_the_shapes_of_the_egcl_backward(K):
+    """hd_gemm_f32 as hd_egcl_backward calls it (hierdiff_hip.hip: the lambda `dwg`), against float64 products: dW = dY^T X over K
+    rows with split_k = min(32, max(1, K / 256)) (and 1 at K = 511), results of one row / one column / 2 and 4 columns, an operand
+    that is column 1..3 of a [K][4] buffer (stride 4, unaligned base: sc4 + 1, sc4 + 2, geo + 3), with and without the column sums,
+    written into a column block of a wider matrix (ldc > N) with the column sums in the same blob - everything outside the block
+    and the sums must keep its bits.
+    Every product is within 2e-6.  One column sum is not, and cannot be: at K = 513, Mo = 1 the 513 N(0, 1) terms (norm 22) add up
+    to 0.124, measured rel-L2 7.8e-6 on the MI355X and 1.55e-5 for torch's float32 sum on the CPU - for column sums the bar is
+    therefore max(2e-6, 4 x the CPU float32 sum's rel-L2), next to the element bound 2e-6 sqrt(K) max|a| (see _gemm_bar)."""
+    from hierdiff_amd import training as tr
+    g = torch.Generator().manual_seed(1000 + K)
+    SENT = -12345.5
+    splits = [min(32, max(1, K // 256))] + ([1] if K == 511 else [])
+    n_case = 0
+    for Mo, N in [(64, 1), (1, 64), (256, 2), (256, 4), (1, 256), (128, 128)]:
+        # operand sources: 0 whole buffers (the layer's [E][H] activations) / 1 A a column (Mo == 1) / 2 B a column (N == 1) / 3 both /
+        # 4 views into wider buffers with an odd row stride and, for B, an offset start
+        for variant in range(5):
+            a_col, b_col, odd = variant in (1, 3), variant in (2, 3), variant == 4
+            if (a_col and Mo != 1) or (b_col and N != 1):
+                continue
+            ca, cb = 1 + (K + Mo) % 3, 1 + (K + N + 1) % 3
+            dY = torch.randn(K, 4 if a_col else Mo + int(odd or Mo == 1), generator=g).to(DEV)    # (the column sums need lda > 1)
+            X = torch.randn(K, 4 if b_col else N + 3 * int(odd), generator=g).to(DEV)
+            A = dY[:, ca:ca + 1] if a_col else dY[:, :Mo]             # A(m, k) = A[m + k lda]
+            B = X[:, cb:cb + 1] if b_col else X[:, 2 * int(odd):2 * int(odd) + N]           # B(k, n) = B[k ldb + n]
+            ref = A.double().t() @ B.double()
+            ref_cs = A.double().sum(0)
+            amax, bmax = float(A.abs().max()), float(B.abs().max())
+            for split in splits:
+                for want_cs in (False, True):
+                    ld, o = N + 5, 3
+                    blob = torch.full((Mo * ld + Mo + 7,), SENT, device=DEV)
+                    Cfull = blob[:Mo * ld].view(Mo, ld)
+                    C = Cfull[:, o:o + N]
+                    cs = blob[Mo * ld + 2:Mo * ld + 2 + Mo] if want_cs else None
+                    tr._gemm(Mo, N, K, A, 1, A.stride(0), B, B.stride(0), 1, C, split=split, colsum=cs)
+                    what = f"K={K} Mo={Mo} N={N} a_col={a_col} b_col={b_col} split={split} colsum={want_cs}"
+                    _gemm_bar(C, ref, K, amax, bmax, what)
+                    keep = torch.ones_like(blob, dtype=torch.bool)
+                    keep[:Mo * ld].view(Mo, ld)[:, o:o + N] = False
+                    if want_cs:
+                        keep[Mo * ld + 2:Mo * ld + 2 + Mo] = False
+                        _gemm_bar(cs.view(-1, 1), ref_cs.view(-1, 1), K, amax, 1.0, what + " column sums", A.cpu().sum(0).view(-1, 1))
+                    assert bool((blob[keep] == SENT).all()), what + ": wrote outside its block"
+                    n_case += 1
+    assert n_case == 30 * len(splits)
+
+
+@pytest.mark.parametrize("R", [513, 4100])
+@pytest.mark.parametrize("N", [1, 2, 4])
+def test_gemm_f32_narrow_dx_and_in_place_epilogues(R, N):
+    """dedge_attr = dpre1 W[:, block] (dX layout, N = De in {1, 2, 4} columns of a wider weight matrix), plain and with the
+    epilogues 2 ((aux + acc) * row_mask) and 3 (acc * SiLU'(aux)) whose `aux` IS the result (hd_egcl_backward: T2, dedge_attr): the
+    in-place call gives the bits of the out-of-place one, and both the float64 product's values."""
+    from hierdiff_amd import training as tr
+    H = 64
+    g = torch.Generator().manual_seed(R * 8 + N)
+    dpre = torch.randn(R, H, generator=g).to(DEV)
+    ld = 2 * H + 1 + N
+    W = torch.randn(H, ld, generator=g).to(DEV)
+    Wb = W[:, 2 * H + 1:]                                             # the edge-attribute columns of mes_mlp.0.weight
+    aux0 = torch.randn(R, N, generator=g).to(DEV)
+    mask = (torch.rand(R, generator=g) > 0.3).float().to(DEV)
+    acc = dpre.double() @ Wb.double()
+    amax, bmax = float(dpre.abs().max()), float(Wb.abs().max())
+    run = lambda C, **kw: tr._gemm(R, N, H, dpre, H, 1, Wb, ld, 1, C, **kw)
+    _gemm_bar(run(torch.empty(R, N, device=DEV)), acc, H, amax, bmax, "plain")
+    sg = torch.sigmoid(aux0.double())
+    refs = {tr._EPI_RESID_MASK: (aux0.double() + acc) * mask.double()[:, None], tr._EPI_MUL_DSILU: acc * (sg * (1 + aux0.double() * (1 - sg)))}
+    for epi, ref in refs.items():
+        rm = mask if epi == tr._EPI_RESID_MASK else None
+        out = run(torch.full((R, N), float("nan"), device=DEV), epi=epi, aux=aux0, rmask=rm)
+        inplace = aux0.clone()
+        run(inplace, epi=epi, aux=inplace, rmask=rm)
+        assert torch.equal(out, inplace), f"epi {epi}: in place differs"
+        _gemm_bar(out, ref, H, amax, bmax, f"epi {epi}")
+
+
 def test_gemm_f32_rejects_bad_arguments():
     from hierdiff_amd import _lib
     lib = _lib.load()
