@@ -101,6 +101,12 @@ struct hd_handle {
     unsigned long long ip_sched_gen, ip_gen;     // sched_gen the table was set for (0: not set); bumped when d_coef_ip / d_ipdraw move
     uint32_t* d_ipdraw;         // graph replay: the draw words of a step's 3 * resamplings noise streams
     int ipdraw_cap;
+    // path loop (hd_set_path / hd_sample_path / hd_sample_path_inpaint): K transitions t_idx[k] -> s_idx[k] on the schedule's grid
+    int path_K, path_form;      // form 0: ancestral rows, 1: linear rows {a, b, c, 0}
+    std::vector<int> path_t_h, path_s_h;
+    int *d_path_t, *d_path_s;
+    float *d_path_coef, *d_path_coef_ip;         // [K][4] each; d_path_coef_ip null when no inpainting rows were given
+    unsigned long long path_sched_gen, path_gen; // sched_gen the path was set for (0: not set); bumped by every hd_set_path
     int split_max_tiles;        // HD_SPLIT_MAX_TILES (a measurement build may override it from the environment)
     int fuse_min_rows;          // HD_FUSE_MIN_ROWS
     int node_split_max_rows;    // HD_NODE_SPLIT_MAX_ROWS
@@ -147,6 +153,19 @@ struct InpaintKey {
     }
 };
 
+// The same for a captured transition of the path loop (plain: resamplings = 0).
+struct PathKey {
+    const float *raw_x, *raw_h;
+    int has_ctx, mol_shape, noise_rows, k_lo, resamplings;   // k_lo: injected-noise offsets are relative to the first transition
+    uint64_t seed;
+    unsigned long long weights_gen, sched_gen, path_gen, ip_gen;
+    bool operator==(const PathKey& o) const {
+        return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape && noise_rows == o.noise_rows &&
+               k_lo == o.k_lo && resamplings == o.resamplings && seed == o.seed && weights_gen == o.weights_gen &&
+               sched_gen == o.sched_gen && path_gen == o.path_gen && ip_gen == o.ip_gen;
+    }
+};
+
 struct hd_topology {
     hd_handle* h;
     int device;
@@ -174,6 +193,11 @@ struct hd_topology {
     InpaintKey ikey;
     uint8_t* ip_fixed;
     float* ip_known;
+    // hd_sample_path / hd_sample_path_inpaint with use_graph: ONE captured transition (whatever the path's length), replayed
+    // once per transition; `path_builds` counts its instantiations (hd_path_graph_builds)
+    hipGraphExec_t gexec_path;
+    PathKey pkey;
+    long long path_builds;
     // lifetime: the tables arrive in stream order of `stream0` (hd_topology_create_s); `ready` marks their arrival for
     // any other stream a caller launches on.  A topology used on one stream only hands its arena back to the pool
     // (arena_release) with an event instead of a device-wide synchronisation.
@@ -283,6 +307,8 @@ extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
     h->ev_last = nullptr; h->ev_last_set = false;
     h->weights_gen = h->sched_gen = 0;
     h->d_coef_ip = nullptr; h->ip_sched_gen = 0; h->ip_gen = 0; h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
+    h->path_K = 0; h->path_form = 0; h->d_path_t = h->d_path_s = nullptr; h->d_path_coef = h->d_path_coef_ip = nullptr;
+    h->path_sched_gen = 0; h->path_gen = 0;
     h->d_nanflag = nullptr; h->d_nan_events = nullptr; h->d_step = nullptr; h->d_draw = nullptr; h->d_tcur = nullptr;
     h->d_base = nullptr;
     h->split_max_tiles = HD_SPLIT_MAX_TILES;
@@ -332,6 +358,7 @@ extern "C" int hd_destroy(hd_handle* h) {
     hipFree(h->dw); hipFree(h->d_nanflag); hipFree(h->d_nan_events);
     hipFree(h->d_tau); hipFree(h->d_coef); hipFree(h->d_step); hipFree(h->d_draw); hipFree(h->d_tcur); hipFree(h->d_base);
     hipFree(h->d_coef_ip); hipFree(h->d_ipdraw);
+    hipFree(h->d_path_t); hipFree(h->d_path_s); hipFree(h->d_path_coef); hipFree(h->d_path_coef_ip);
 #ifdef HD_DEBUG_KERNELS
     hipFree(h->d_trace);
 #endif
@@ -705,7 +732,7 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     ArenaSlot sl{t->device, t->arena, t->arena_bytes, t->staging, t->staging_bytes, nullptr};
     // a captured graph, or launches on several streams: wait for the device (the rare case - a sampling topology lives as
     // long as its model); otherwise an event behind the topology's last work guards the arena's next owner
-    bool pooled = t->arena && !t->gexec && !t->gexec_ip && !t->multi_stream;
+    bool pooled = t->arena && !t->gexec && !t->gexec_ip && !t->gexec_path && !t->multi_stream;
     if (pooled && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) == hipSuccess) {
         if (hipEventRecord(sl.done, t->last_stream) != hipSuccess) { (void)hipEventDestroy(sl.done); sl.done = nullptr; pooled = false; }
     } else {
@@ -714,6 +741,7 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     if (!pooled) (void)hipDeviceSynchronize();
     if (t->gexec) hipGraphExecDestroy(t->gexec);
     if (t->gexec_ip) hipGraphExecDestroy(t->gexec_ip);
+    if (t->gexec_path) hipGraphExecDestroy(t->gexec_path);
     if (t->ip_fixed) (void)hipFree(t->ip_fixed);
     if (t->ip_known) (void)hipFree(t->ip_known);
     if (t->ready) (void)hipEventDestroy(t->ready);
@@ -2516,13 +2544,16 @@ static NoiseSrc make_noise(const float* raw_x, const float* raw_h, int rows, uin
 
 static int step_impl(hd_handle* h, hd_topology* t, const float* zt, const float* eps, const float* coef, int coef_rows,
                      const NoiseSrc& ns, int mol, float* zs, int out_stride, const int* step_ptr,
-                     const uint32_t* draw_ptr, uint32_t draw0, hipStream_t s, const unsigned long long* base_ptr = nullptr) {
+                     const uint32_t* draw_ptr, uint32_t draw0, hipStream_t s, const unsigned long long* base_ptr = nullptr,
+                     int form = 0, int raw_step0 = -1) {
     ProfScope ps(h, s, 2);
     StepArgs a;
+    a.raw_step0 = raw_step0;
     a.zt = zt; a.eps = eps; a.coef = coef; a.nm = t->nm_bytes; a.zs = zs; a.noise = ns; a.draw_ptr = draw_ptr;
     a.step_ptr = step_ptr; a.base_ptr = base_ptr; a.draw0 = draw0; a.coef_rows = coef_rows; a.B = t->B; a.N = t->N; a.D = h->D; a.F = h->F;
     a.mol = mol; a.out_stride = out_stride;
-    hipLaunchKernelGGL(k_post_step, dim3(t->B), dim3(256), (size_t)a.mol * a.D * sizeof(float), s, a);
+    if (form == 0) hipLaunchKernelGGL(k_post_step<0>, dim3(t->B), dim3(256), (size_t)a.mol * a.D * sizeof(float), s, a);
+    else hipLaunchKernelGGL(k_post_step<1>, dim3(t->B), dim3(256), (size_t)a.mol * a.D * sizeof(float), s, a);
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
@@ -2713,10 +2744,10 @@ extern "C" int hd_set_inpaint_schedule(hd_handle* h, int T, const float* coef4) 
 
 static int inpaint_launch(hd_handle* h, hd_topology* t, bool jump, float* z, const uint8_t* fixed, const float* known, uint64_t seed,
                           uint64_t base, uint32_t draw, int step, const uint32_t* draw_ptr, const int* step_ptr,
-                          const unsigned long long* base_ptr, hipStream_t s) {
+                          const unsigned long long* base_ptr, hipStream_t s, const float* coef = nullptr) {
     ProfScope ps(h, s, 2);
     InpaintArgs a;
-    a.z = z; a.nm = t->nm_bytes; a.fixed = fixed; a.known = known; a.coef = h->d_coef_ip; a.seed = seed; a.sample_base = base;
+    a.z = z; a.nm = t->nm_bytes; a.fixed = fixed; a.known = known; a.coef = coef ? coef : h->d_coef_ip; a.seed = seed; a.sample_base = base;
     a.draw = draw; a.step = step; a.draw_ptr = draw_ptr; a.step_ptr = step_ptr; a.base_ptr = base_ptr;
     a.B = t->B; a.N = t->N; a.D = h->D;
     const size_t lds = (size_t)t->N * h->D * sizeof(float);
@@ -2856,6 +2887,212 @@ extern "C" int hd_sample_loop_inpaint(hd_handle* h, hd_topology* topo, float* z,
         HIP_TRY(hipStreamWaitEvent(s, h->ev_out, 0));
     }
     return HD_OK;
+}
+
+// ----------------------------------------------------------------------------- few-step sampling: the loop on a path
+
+extern "C" int hd_set_path(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* coef4, int form,
+                           const float* coef4_inpaint) {
+    if (form != 0 && form != 1) return fail(HD_E_INVALID, "hd_set_path: form must be 0 (ancestral rows) or 1 (linear rows)");
+    if (form == 1 && coef4_inpaint) return fail(HD_E_INVALID, "hd_set_path: inpainting rows go with ancestral rows only (form 0)");
+    if (!h || !t_idx || !s_idx || !coef4 || K < 1) return fail(HD_E_INVALID, "hd_set_path: bad argument");
+    if (h->T < 1) return fail(HD_E_STATE, "hd_set_path: schedule not set (hd_set_schedule)");
+    if (K > h->T) return fail(HD_E_INVALID, "hd_set_path: more transitions than the schedule has steps");
+    for (int k = 0; k < K; ++k) {
+        if (t_idx[k] > h->T || s_idx[k] < 0 || s_idx[k] >= t_idx[k])
+            return fail(HD_E_INVALID, "hd_set_path: need 0 <= s_idx[k] < t_idx[k] <= T");
+        if (k > 0 && t_idx[k] != s_idx[k - 1]) return fail(HD_E_INVALID, "hd_set_path: transition k must start where k - 1 arrived");
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
+    hipFree(h->d_path_t); hipFree(h->d_path_s); hipFree(h->d_path_coef); hipFree(h->d_path_coef_ip);
+    h->d_path_t = h->d_path_s = nullptr; h->d_path_coef = h->d_path_coef_ip = nullptr;
+    h->path_sched_gen = 0; h->path_K = 0;
+    h->path_t_h.assign(t_idx, t_idx + K);
+    h->path_s_h.assign(s_idx, s_idx + K);
+    HD_TRY(dev_upload(&h->d_path_t, h->path_t_h));
+    HD_TRY(dev_upload(&h->d_path_s, h->path_s_h));
+    HD_TRY(dev_upload(&h->d_path_coef, std::vector<float>(coef4, coef4 + (size_t)4 * K)));
+    if (coef4_inpaint) HD_TRY(dev_upload(&h->d_path_coef_ip, std::vector<float>(coef4_inpaint, coef4_inpaint + (size_t)4 * K)));
+    h->path_K = K; h->path_form = form;
+    h->path_sched_gen = h->sched_gen;
+    h->path_gen++;                             // captured graphs hold the old table addresses
+    return HD_OK;
+}
+
+extern "C" long long hd_path_graph_builds(const hd_topology* topo) { return topo ? topo->path_builds : -1; }
+
+// Both path loops: R = 0 is the plain one, R >= 1 the inpainting one with R rounds per transition.
+static int path_loop(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
+                     const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
+                     const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s) {
+    const int T = h->T, K = h->path_K, N = topo->N, form = h->path_form;
+    const int mol = (mol_shape < 0 || mol_shape > N) ? N : mol_shape;
+    const int ms = mol_shape < 0 ? -1 : mol;
+    const int nd = 3 * R;
+    const uint32_t stride = (uint32_t)T + 2u;
+    const int share = (noise_rows == 1) ? 1 : 0;
+    const int ntr = k_hi - k_lo;
+    topo_use(topo, s);
+    if (ntr == 0) return HD_OK;
+    if (!use_graph) {
+        for (int k = k_lo; k < k_hi; ++k) {
+            const float* tcur = h->d_tau + h->path_t_h[k];
+            const uint32_t d = (uint32_t)(T - h->path_s_h[k]);
+            const size_t ro = (size_t)(k - k_lo) * noise_rows * mol;
+            for (int j = 0; j < (R ? R : 1); ++j) {
+                HD_TRY(forward_impl(h, topo, z, tcur, 1, context, ms, topo->eps, s));
+                NoiseSrc ns = make_noise(raw_x ? raw_x + ro * 3 : nullptr, raw_h ? raw_h + ro * h->F : nullptr, noise_rows, seed,
+                                         sample_id_base, stride * (uint32_t)(3 * j) + d, share);
+                HD_TRY(step_impl(h, topo, z, topo->eps, h->d_path_coef + (size_t)k * 4, 1, ns, mol, z, N, nullptr, nullptr, 0, s,
+                                 nullptr, form));
+                if (!R) continue;
+                HD_TRY(inpaint_launch(h, topo, false, z, fixed_mask, xh_known, seed, sample_id_base, stride * (uint32_t)(3 * j + 1) + d,
+                                      k, nullptr, nullptr, nullptr, s, h->d_path_coef_ip));
+                if (j < R - 1)
+                    HD_TRY(inpaint_launch(h, topo, true, z, nullptr, nullptr, seed, sample_id_base, stride * (uint32_t)(3 * j + 2) + d,
+                                          k, nullptr, nullptr, nullptr, s, h->d_path_coef_ip));
+            }
+        }
+        return HD_OK;
+    }
+    // ONE captured transition, replayed ntr times: the path position lives in d_step and k_path_advance derives the network time,
+    // the coefficient row and the draws from the uploaded tables.  Everything else as in hd_sample_loop.
+    const size_t BN = (size_t)topo->B * N;
+    const size_t zbytes = BN * h->D * sizeof(float);
+    const size_t cbytes = BN * h->cfg.context_node_nf * sizeof(float);
+    hipStream_t rs = s;
+    if (s == nullptr) {
+        if (!h->own_stream) HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+        rs = h->own_stream;
+        HIP_TRY(hipEventRecord(h->ev_in, s));
+        HIP_TRY(hipStreamWaitEvent(rs, h->ev_in, 0));
+    }
+    if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(rs, h->ev_last, 0));
+    if (nd > h->ipdraw_cap) {                                // grow the draw words: graphs that hold the old address go stale (ip_gen)
+        if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
+        HIP_TRY(hipStreamSynchronize(rs));
+        hipFree(h->d_ipdraw);
+        h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
+        HD_TRY(dev_alloc(&h->d_ipdraw, (size_t)nd));
+        h->ipdraw_cap = nd;
+        h->ip_gen++;
+    }
+    if (R) {
+        if (!topo->ip_fixed) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->ip_fixed), BN));
+        if (!topo->ip_known) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->ip_known), zbytes));
+    }
+    PathKey key;
+    key.raw_x = raw_x; key.raw_h = raw_h; key.has_ctx = context ? 1 : 0; key.mol_shape = ms; key.noise_rows = noise_rows;
+    key.k_lo = raw_x ? k_lo : 0; key.resamplings = R; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
+    key.path_gen = h->path_gen; key.ip_gen = R ? h->ip_gen : 0;
+    if (topo->gexec_path && !(topo->pkey == key)) {
+        if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
+        HIP_TRY(hipStreamSynchronize(rs));
+        hipGraphExecDestroy(topo->gexec_path);
+        topo->gexec_path = nullptr;
+    }
+    PathWords w;
+    w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = R ? h->d_ipdraw : nullptr;
+    w.tau = h->d_tau; w.t_idx = h->d_path_t; w.s_idx = h->d_path_s; w.K = K; w.T = T; w.nd = nd; w.stride = stride;
+    if (!topo->gexec_path) {
+        const int was_prof = h->prof;
+        h->prof = 0;
+        hipGraph_t graph = nullptr;
+        HIP_TRY(hipStreamBeginCapture(rs, hipStreamCaptureModeThreadLocal));
+        int rc = HD_OK;
+        for (int j = 0; j < (R ? R : 1) && rc == HD_OK; ++j) {
+            rc = forward_impl(h, topo, topo->zbuf, h->d_tcur, 1, context ? topo->ctxbuf : nullptr, ms, topo->eps, rs);
+            if (rc == HD_OK) {
+                NoiseSrc ns = make_noise(raw_x, raw_h, noise_rows, seed, 0, 0, share);
+                rc = step_impl(h, topo, topo->zbuf, topo->eps, h->d_path_coef, 1, ns, mol, topo->zbuf, N, h->d_step,
+                               R ? h->d_ipdraw + 3 * j : h->d_draw, 0, rs, h->d_base, form, k_lo);
+            }
+            if (rc == HD_OK && R)
+                rc = inpaint_launch(h, topo, false, topo->zbuf, topo->ip_fixed, topo->ip_known, seed, 0, 0, 0, h->d_ipdraw + 3 * j + 1,
+                                    h->d_step, h->d_base, rs, h->d_path_coef_ip);
+            if (rc == HD_OK && R && j < R - 1)
+                rc = inpaint_launch(h, topo, true, topo->zbuf, nullptr, nullptr, seed, 0, 0, 0, h->d_ipdraw + 3 * j + 2, h->d_step,
+                                    h->d_base, rs, h->d_path_coef_ip);
+        }
+        if (rc == HD_OK) hipLaunchKernelGGL(k_path_advance, dim3(1), dim3(64), 0, rs, w);
+        const hipError_t ce = hipStreamEndCapture(rs, &graph);
+        h->prof = was_prof;
+        if (rc != HD_OK) { if (graph) hipGraphDestroy(graph); return rc; }
+        if (ce != hipSuccess) return fail(HD_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
+        const hipError_t ie = hipGraphInstantiate(&topo->gexec_path, graph, nullptr, nullptr, 0);
+        hipGraphDestroy(graph);
+        if (ie != hipSuccess) { topo->gexec_path = nullptr; return fail(HD_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+        topo->pkey = key;
+        topo->path_builds++;
+    }
+    HIP_TRY(hipMemcpyAsync(topo->zbuf, z, zbytes, hipMemcpyDeviceToDevice, rs));
+    if (context) HIP_TRY(hipMemcpyAsync(topo->ctxbuf, context, cbytes, hipMemcpyDeviceToDevice, rs));
+    if (R) {
+        HIP_TRY(hipMemcpyAsync(topo->ip_fixed, fixed_mask, BN, hipMemcpyDeviceToDevice, rs));
+        HIP_TRY(hipMemcpyAsync(topo->ip_known, xh_known, zbytes, hipMemcpyDeviceToDevice, rs));
+    }
+    hipLaunchKernelGGL(k_path_state, dim3(1), dim3(64), 0, rs, w, k_lo, (unsigned long long)sample_id_base);
+    for (int k = 0; k < ntr; ++k) {
+        const hipError_t le = hipGraphLaunch(topo->gexec_path, rs);
+        if (le != hipSuccess) return fail(HD_E_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(le));
+    }
+    HIP_TRY(hipMemcpyAsync(z, topo->zbuf, zbytes, hipMemcpyDeviceToDevice, rs));
+    HIP_TRY(hipEventRecord(h->ev_last, rs));
+    h->ev_last_set = true;
+    if (rs != s) {
+        HIP_TRY(hipEventRecord(h->ev_out, rs));
+        HIP_TRY(hipStreamWaitEvent(s, h->ev_out, 0));
+    }
+    return HD_OK;
+}
+
+static int path_ready(hd_handle* h, const char* who, int k_lo, int k_hi) {
+    if (h->T < 1) return fail(HD_E_STATE, std::string(who) + ": schedule not set (hd_set_schedule)");
+    if (h->path_K < 1 || h->path_sched_gen != h->sched_gen)
+        return fail(HD_E_STATE, std::string(who) + ": path not set for the current schedule (hd_set_path)");
+    if (k_lo < 0 || k_lo > k_hi || k_hi > h->path_K) return fail(HD_E_INVALID, std::string(who) + ": need 0 <= k_lo <= k_hi <= K");
+    return HD_OK;
+}
+
+extern "C" int hd_sample_path(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
+                              const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base,
+                              int use_graph, void* stream) {
+    if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_sample_path: need 0 <= k_lo <= k_hi <= K");
+    HD_TRY(check_ready(h, topo, "hd_sample_path"));
+    HD_TRY(path_ready(h, "hd_sample_path", k_lo, k_hi));
+    if (!z) return fail(HD_E_INVALID, "hd_sample_path: null z");
+    if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, "hd_sample_path: raw_x and raw_h go together");
+    if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_path: noise_rows must be 1 or B");
+    if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, "hd_sample_path: context required");
+    if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_path: needs a time-conditioned model");
+    HIP_TRY(hipSetDevice(h->device));
+    return path_loop(h, topo, z, context, mol_shape, k_lo, k_hi, raw_x, raw_h, noise_rows, seed, sample_id_base, use_graph,
+                     nullptr, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo,
+                                      int k_hi, const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed,
+                                      uint64_t sample_id_base, int use_graph, const uint8_t* fixed_mask, const float* xh_known,
+                                      int resamplings, void* stream) {
+    if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_sample_path_inpaint: need 0 <= k_lo <= k_hi <= K");
+    HD_TRY(check_ready(h, topo, "hd_sample_path_inpaint"));
+    HD_TRY(path_ready(h, "hd_sample_path_inpaint", k_lo, k_hi));
+    if (h->path_form != 0) return fail(HD_E_INVALID, "hd_sample_path_inpaint: ancestral rows only (the path was set with form = 1)");
+    if (!h->d_path_coef_ip) return fail(HD_E_STATE, "hd_sample_path_inpaint: the path was set without inpainting rows (hd_set_path)");
+    if (!z || !fixed_mask || !xh_known) return fail(HD_E_INVALID, "hd_sample_path_inpaint: null z / fixed_mask / xh_known");
+    if (raw_x || raw_h) return fail(HD_E_INVALID, "hd_sample_path_inpaint: injected noise is not supported (counter-based generator only)");
+    if (noise_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_path_inpaint: noise_rows must be B");
+    if (mol_shape >= 0 && mol_shape < topo->N) return fail(HD_E_INVALID, "hd_sample_path_inpaint: fixed tail rows (mol_shape < N) are not supported");
+    if (resamplings < 1) return fail(HD_E_INVALID, "hd_sample_path_inpaint: resamplings must be >= 1");
+    if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, "hd_sample_path_inpaint: context required");
+    if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_path_inpaint: needs a time-conditioned model");
+    if (((unsigned long long)h->T + 2ULL) * 3ULL * (unsigned long long)resamplings > 0xffffffffULL)
+        return fail(HD_E_INVALID, "hd_sample_path_inpaint: (T + 2) * 3 * resamplings exceeds the 32-bit draw index");
+    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_sample_path_inpaint: N * D floats exceed one workgroup's LDS");
+    HIP_TRY(hipSetDevice(h->device));
+    return path_loop(h, topo, z, context, -1, k_lo, k_hi, nullptr, nullptr, noise_rows, seed, sample_id_base, use_graph,
+                     fixed_mask, xh_known, resamplings, (hipStream_t)stream);
 }
 
 extern "C" int hd_inpaint_decode_fix(hd_handle* h, hd_topology* topo, const uint8_t* fixed_mask, const float* x_known,

@@ -192,6 +192,7 @@ struct StepArgs {
     const int* step_ptr;        // optional device-side step index into coef (graph replay)
     const unsigned long long* base_ptr;   // optional device-side first global sample id (graph replay); overrides noise.sample_base
     uint32_t draw0;             // draw index of the first replayed step (raw-noise offset base)
+    int raw_step0;              // path loop: injected normals are indexed by *step_ptr - raw_step0 (path position); -1: by draw - draw0
     int coef_rows, B, N, D, F, mol, out_stride;
 };
 
@@ -208,6 +209,10 @@ HD_DEVINL float block_sum4(float v, float* red, int tid) {
 // sample_p_zs_given_zt after the network call (diffusion_qm9.py:326-345) + sample_normal.
 // One workgroup (256 threads) per molecule, one thread per (node, component): every raw normal (Philox + Box-Muller
 // is ~150 instructions) is produced once and kept in LDS for the second pass; dynamic LDS = mol * D floats.
+// FORM 0: the ancestral row {alpha_t|s, sigma2_t|s, sigma_t, sigma} above.  FORM 1 (path loop with eta < 1): the linear row
+// {a, b, c, 0} of z_s = (a z_t - b eps) + c noise, eps and noise with their x parts mean-removed as in form 0; with c == 0
+// (eta = 0) no normal is generated or read at all and the LDS pass that holds them goes away.
+template <int FORM>
 __global__ __launch_bounds__(256) void k_post_step(StepArgs a) {
     extern __shared__ float nz_s[];                // [mol * D] masked raw normals, later the un-centred z_s
     __shared__ float red[4];
@@ -218,22 +223,26 @@ __global__ __launch_bounds__(256) void k_post_step(StepArgs a) {
     if (a.draw_ptr) {
         ns.draw = *a.draw_ptr;
         if (ns.raw_x) {
-            const size_t k = (size_t)(ns.draw - a.draw0) * ns.rows * a.mol;
+            const size_t k = (size_t)(a.raw_step0 >= 0 ? (uint32_t)(*a.step_ptr - a.raw_step0) : ns.draw - a.draw0) * ns.rows * a.mol;
             ns.raw_x += k * 3;
             ns.raw_h += k * a.F;
         }
     }
     const float* cf = a.coef + (a.step_ptr ? (size_t)(*a.step_ptr) * 4 : (size_t)((a.coef_rows == 1) ? 0 : b) * 4);
     const float alpha_ts = cf[0], sigma2_ts = cf[1], sigma_t = cf[2], sigma = cf[3];
-    const float ceps = (sigma2_ts / alpha_ts) / sigma_t;
+    const float ceps = (FORM == 0) ? (sigma2_ts / alpha_ts) / sigma_t : 0.f;
+    const bool noisy = FORM == 0 || cf[2] != 0.f;  // uniform over the workgroup
     const int mol = a.mol, D = a.D, total = mol * D;
     // pass 1: raw normals (masked) into LDS; masked sums of eps_x and of the x-noise per component, node count
     float se[3] = {0.f, 0.f, 0.f}, sn[3] = {0.f, 0.f, 0.f}, cnt = 0.f;
     for (int e = tid; e < total; e += 256) {
         const int nn = e / D, c = e - nn * D;
         const float m = a.nm[b * a.N + nn] ? 1.f : 0.f;
-        const float z = raw_noise(ns, b, nn, c, mol, a.F) * m;
-        nz_s[e] = z;
+        float z = 0.f;
+        if (noisy) {
+            z = raw_noise(ns, b, nn, c, mol, a.F) * m;
+            nz_s[e] = z;
+        }
         if (c < 3) {
             const float ev = a.eps[((size_t)b * a.N + nn) * D + c];
 #pragma unroll
@@ -243,7 +252,7 @@ __global__ __launch_bounds__(256) void k_post_step(StepArgs a) {
     }
     float em[3], nmn[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { em[k] = block_sum4(se[k], red, tid); nmn[k] = block_sum4(sn[k], red, tid); }
+    for (int k = 0; k < 3; ++k) { em[k] = block_sum4(se[k], red, tid); nmn[k] = noisy ? block_sum4(sn[k], red, tid) : 0.f; }
     cnt = block_sum4(cnt, red, tid);
 #pragma unroll
     for (int k = 0; k < 3; ++k) { em[k] /= cnt; nmn[k] /= cnt; }
@@ -254,12 +263,14 @@ __global__ __launch_bounds__(256) void k_post_step(StepArgs a) {
         const float m = a.nm[b * a.N + nn] ? 1.f : 0.f;
         const float zt = a.zt[((size_t)b * a.N + nn) * D + c];
         float ev = a.eps[((size_t)b * a.N + nn) * D + c];
-        float z = nz_s[e];
+        float z = noisy ? nz_s[e] : 0.f;
         if (c < 3) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) { if (c == k) { ev -= em[k] * m; z -= nmn[k] * m; } }
         }
-        const float v = (zt / alpha_ts - ceps * ev) + sigma * z;
+        float v;
+        if constexpr (FORM == 0) v = (zt / alpha_ts - ceps * ev) + sigma * z;
+        else v = noisy ? (cf[0] * zt - cf[1] * ev) + cf[2] * z : cf[0] * zt - cf[1] * ev;
         nz_s[e] = v;
         if (c < 3) {
 #pragma unroll
@@ -373,6 +384,42 @@ __global__ void k_advance(int* step, uint32_t* draw, float* t_cur, const float* 
     *step = s;
     *draw = *draw + 1;
     *t_cur = tau[s + 1 >= 0 ? s + 1 : 0];
+}
+
+// The same for a path (hd_set_path / hd_sample_path): `step` holds the path POSITION k, which is also the row of the path's
+// coefficient tables; transition k goes from grid index t_idx[k] to s_idx[k], so the network time is tau[t_idx[k]] and the
+// noise counter the fine-grid index of the arrival step, draw = T - s_idx[k] (the plain loop's layout restricted to the
+// visited s).  The inpainting loop's 3 * resamplings streams are offset by `stride` each (nd = 0: plain path loop).
+// Behind the last transition (k == K) the words keep the values of k = K - 1; nothing reads them.  One workgroup.
+struct PathWords {
+    int* step;
+    uint32_t* draw;
+    float* t_cur;
+    unsigned long long* base;
+    uint32_t* ipdraw;     // [nd] or null
+    const float* tau;     // [T + 1]
+    const int* t_idx;     // [K]
+    const int* s_idx;     // [K]
+    int K, T, nd;
+    uint32_t stride;
+};
+
+HD_DEVINL void path_words_set(const PathWords& w, int k) {
+    const int kk = k < w.K ? k : w.K - 1;
+    const uint32_t d = (uint32_t)(w.T - w.s_idx[kk]);
+    if (threadIdx.x == 0) { *w.step = k; *w.draw = d; *w.t_cur = w.tau[w.t_idx[kk]]; }
+    for (int i = threadIdx.x; i < w.nd; i += blockDim.x) w.ipdraw[i] = w.stride * (uint32_t)i + d;
+}
+
+__global__ void k_path_state(PathWords w, int k0, unsigned long long b0) {
+    if (threadIdx.x == 0) *w.base = b0;
+    path_words_set(w, k0);
+}
+
+__global__ void k_path_advance(PathWords w) {
+    const int k = *w.step + 1;
+    __syncthreads();                               // every thread has read the position before thread 0 moves it
+    path_words_set(w, k);
 }
 
 

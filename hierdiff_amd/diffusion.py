@@ -172,6 +172,13 @@ class DiffusionQM9(_Base):
         self.schedule_eval = "fp64"
         self._sched_key = None
         self._sched = None
+        # few-step sampling (hierdiff_amd/paths.py): defaults of the `steps` / `eta` / `spacing` / `timesteps` keywords of the
+        # sampling entry points.  None / 1.0 = the full chain through the plain loop, i.e. nothing changes.
+        self.sample_steps = None
+        self.sample_eta = 1.0
+        self.sample_spacing = "uniform"
+        self.sample_timesteps = None
+        self._force_path_loop = False   # tests: run the identity path (K = T, eta = 1) through the path loop instead of the plain one
 
     def check_issues_norm_values(self, num_stdevs=8):
         """diffusion_qm9.py:117-131 (predefined schedules only)."""
@@ -581,6 +588,47 @@ class DiffusionQM9(_Base):
             self._sched_key = key
         return self._sched
 
+    def _resolve_path(self, steps=None, eta=None, spacing=None, timesteps=None, inpaint: bool = False):
+        """The keywords of the sampling entry points (None: the model's `sample_*` attributes) -> None for the plain loop, or
+        (path, eta).  Pure host arithmetic: every ValueError is raised before the GPU is touched."""
+        from . import paths
+        if steps is None and timesteps is None:
+            steps, timesteps = self.sample_steps, self.sample_timesteps
+        eta = paths.check_eta(self.sample_eta if eta is None else eta)
+        spacing = self.sample_spacing if spacing is None else spacing
+        if spacing not in paths.SPACINGS:
+            raise ValueError(f"spacing must be one of {paths.SPACINGS}, got {spacing!r}")
+        if steps is not None and timesteps is not None:
+            raise ValueError("give either steps or timesteps, not both")
+        if inpaint and eta < 1.0:
+            raise ValueError("inpainting takes ancestral steps only (eta = 1): the replacement method re-noises the known part "
+                             "with the posterior's own variance")
+        if steps is None and timesteps is None and eta == 1.0 and not self._force_path_loop:
+            return None
+        path = paths.build_path(self.T, steps, spacing, timesteps)
+        if len(path) == self.T + 1 and eta == 1.0 and not self._force_path_loop:
+            return None                  # the identity path with ancestral steps IS the plain loop
+        return path, eta
+
+    def _path_tables(self, handle, tabs, path, eta):
+        """Rows of `path` from the gamma grid of `_schedule`, uploaded to the handle (hd_set_path) once per (table, path, eta)."""
+        from . import paths
+        key = (tuple(path), float(eta))
+        hit = self.__dict__.get("_path_cache")
+        if hit is None or hit[0] is not tabs or hit[1] != key:
+            pt = paths.path_tables(tabs["gamma"], path, eta)
+            t_idx = np.ascontiguousarray(pt["t_idx"].numpy(), dtype=np.int32)
+            s_idx = np.ascontiguousarray(pt["s_idx"].numpy(), dtype=np.int32)
+            coef = np.ascontiguousarray(pt["coef"].numpy(), dtype=np.float32)
+            cip = None if pt["coef_inpaint"] is None else np.ascontiguousarray(pt["coef_inpaint"].numpy(), dtype=np.float32)
+            self._path_cache = None
+            _lib.check(_lib.load().hd_set_path(
+                handle, pt["K"], t_idx.ctypes.data_as(C.POINTER(C.c_int)), s_idx.ctypes.data_as(C.POINTER(C.c_int)),
+                coef.ctypes.data_as(C.POINTER(C.c_float)), pt["form"],
+                None if cip is None else cip.ctypes.data_as(C.POINTER(C.c_float))), "hd_set_path")
+            self._path_cache = (tabs, key, pt)
+        return self._path_cache[2]
+
     def _check_masked(self, x, node_mask, what):
         if self.debug_checks:
             bad = (x * (~node_mask.bool())).abs().max().item()
@@ -694,8 +742,18 @@ class DiffusionQM9(_Base):
     @torch.no_grad()
     def sample_from_masks(self, node_mask: torch.Tensor, edge_mask: Optional[torch.Tensor], context=None,
                           fix_noise: bool = False, raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None,
-                          sample_id_base: int = 0, z_init: Optional[torch.Tensor] = None, pocket=None):
+                          sample_id_base: int = 0, z_init: Optional[torch.Tensor] = None, pocket=None, *,
+                          steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
+                          timesteps: Optional[Sequence[int]] = None):
         """z_T -> (x, h) for given masks: draw z_T, T posterior steps, final decode.
+
+        steps / eta / spacing / timesteps (keyword-only; None: the model's `sample_steps` / `sample_eta` / `sample_spacing` /
+        `sample_timesteps`): few-step sampling - K = steps transitions on a sub-sequence of the trained grid ("uniform" or
+        "quadratic" spacing, or the explicit decreasing list `timesteps` from T to 0), ancestral (eta = 1) or with the DDIM-family
+        update (0 <= eta < 1; eta = 0 draws no noise on the path), inside the library's loop (hd_sample_path).  Noise counters are
+        those of the visited fine-grid steps, so a sample still depends only on its global id; `raw_noises` then holds K + 2
+        pairs (z_T, the K transitions, decode).  The defaults run today's full chain through the plain loop.  The mechanism is
+        exact; which K and eta keep sample quality is for the user to validate on a trained checkpoint.
 
         raw_noises: optional T+2 (randn_x[b,N,3], randn_h[b,N,F]) pairs in the reference's draw order
         (z_T, steps s=T-1..0, decode) for bit-for-bit comparable trajectories; otherwise noise comes
@@ -704,6 +762,11 @@ class DiffusionQM9(_Base):
         residue nodes: appended to z for every network call with a block-diagonal edge mask and never updated
         (diffusion_qm9.py:362-371,381-382); the final decode sees the molecule alone (:386-387)."""
         dev = node_mask.device
+        pe = self._resolve_path(steps, eta, spacing, timesteps)
+        if pe is not None and (getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics" or
+                               (self.noise_mode == "torch" and raw_noises is None)):
+            raise NotImplementedError("few-step sampling runs inside the library's loop: mode 'gnn_dynamics' and noise_mode 'torch' "
+                                      "(step-by-step Python loops) take the full chain only")
         if dev.type != "cuda":
             raise _lib.HierDiffHipError("sampling runs only on an MI355X (no CPU fallback)")
         B, N = node_mask.shape[0], node_mask.shape[1]
@@ -711,6 +774,7 @@ class DiffusionQM9(_Base):
         lib = _lib.load()
         h = self._lib_handle()
         tabs = self._schedule(rows=B)
+        K = self.T if pe is None else self._path_tables(h, tabs, *pe)["K"]
         topo = self.dynamics.topology(node_mask, edge_mask, B, N)
         ctx = None
         if self.dynamics.context_node_nf > 0:
@@ -737,6 +801,11 @@ class DiffusionQM9(_Base):
         def run_loop(z_mol, rx, rh, rows, seed, base):
             """T posterior steps on [B,N,D]; with a pocket the fixed rows ride along behind the molecule."""
             zz = z_mol if tail is None else torch.cat([z_mol, tail], dim=1).contiguous()
+            if pe is not None:           # the K transitions of the path
+                _lib.check(lib.hd_sample_path(h, topo_loop.ptr, zz.data_ptr(), _ptr(ctx), -1 if tail is None else N, 0, K,
+                                              _ptr(rx), _ptr(rh), rows, seed, base, int(self.use_graph), stream),
+                           "hd_sample_path")
+                return zz if tail is None else zz[:, :N].contiguous()
             _lib.check(lib.hd_sample_loop(h, topo_loop.ptr, zz.data_ptr(), _ptr(ctx), -1 if tail is None else N, T, 0,
                                           _ptr(rx), _ptr(rh), rows, seed, base, int(self.use_graph), stream),
                        "hd_sample_loop")
@@ -760,15 +829,15 @@ class DiffusionQM9(_Base):
                                               mol_shape=N, raw_noise=raw_noises[1 + i], gammas=gm)
             final_raw = tuple(r.to(dev, torch.float32).contiguous() for r in raw_noises[T + 1])
         elif raw_noises is not None:
-            assert len(raw_noises) == T + 2, "need T+2 raw noise pairs"
+            assert len(raw_noises) == K + 2, "need T+2 raw noise pairs (few-step sampling: steps + 2)"
             rx = [r[0].to(dev, torch.float32).contiguous() for r in raw_noises]
             rh = [r[1].to(dev, torch.float32).contiguous() for r in raw_noises]
             _lib.check(lib.hd_noise(h, topo.ptr, rx[0].data_ptr(), rh[0].data_ptr(), rx[0].shape[0], 0, 0, 0, 0,
                                     z.data_ptr(), stream), "hd_noise")
-            step_x = torch.stack(rx[1:T + 1]).contiguous()
-            step_h = torch.stack(rh[1:T + 1]).contiguous()
+            step_x = torch.stack(rx[1:K + 1]).contiguous()
+            step_h = torch.stack(rh[1:K + 1]).contiguous()
             z = run_loop(z, step_x, step_h, step_x.shape[1], 0, 0)
-            final_raw = (rx[T + 1], rh[T + 1])
+            final_raw = (rx[K + 1], rh[K + 1])
         elif self.noise_mode == "torch" or gnn:
             z = self.sample_combined_position_feature_noise(nb, N, node_mask)
             if nb == 1 and B > 1:
@@ -800,6 +869,42 @@ class DiffusionQM9(_Base):
             x, hfeat = self._final_decode(z, eps, node_mask, edge_mask, coef3, fix_noise, final_raw)
         return x, hfeat
 
+    @torch.no_grad()
+    def path_steps(self, z, node_mask, edge_mask=None, context=None, *, steps=None, eta=None, spacing=None, timesteps=None,
+                   k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False):
+        """Transitions k_lo .. k_hi-1 of `sample_from_masks`'s few-step loop on a given z [B,N,D] (normalised units, the state at
+        path position k_lo); returns the state at position k_hi (default: the end of the path, z_0 before the decode).  Draws are
+        keyed by the arrival step, so a chain cut into pieces gives the bits of the whole."""
+        force = self._force_path_loop
+        self._force_path_loop = True                 # also the identity path goes through hd_sample_path here
+        try:
+            path, e = self._resolve_path(steps, eta, spacing, timesteps)
+        finally:
+            self._force_path_loop = force
+        if getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics" or self.noise_mode == "torch":
+            raise NotImplementedError("few-step sampling: mode 'gnn_dynamics' and noise_mode 'torch' are not supported")
+        K = len(path) - 1
+        k_hi = K if k_hi is None else int(k_hi)
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        if tuple(z.shape) != (B, N, self.n_dims + self.in_node_nf) or not (0 <= int(k_lo) <= k_hi <= K):
+            raise ValueError("z must be [B, N, 3 + F] and 0 <= k_lo <= k_hi <= steps")
+        dev = node_mask.device
+        if dev.type != "cuda":
+            raise _lib.HierDiffHipError("sampling runs only on an MI355X (no CPU fallback)")
+        h = self._lib_handle()
+        self._path_tables(h, self._schedule(rows=B), path, e)
+        topo = self.dynamics.topology(node_mask, edge_mask, B, N)
+        ctx = None
+        if self.dynamics.context_node_nf > 0:
+            if context is None:
+                raise ValueError("context required")
+            ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
+        z = z.detach().to(dev, torch.float32).clone().contiguous()
+        _lib.check(_lib.load().hd_sample_path(h, topo.ptr, z.data_ptr(), _ptr(ctx), -1, int(k_lo), k_hi, None, None,
+                                              1 if fix_noise else B, self.seed, sample_id_base, int(self.use_graph), _stream(dev)),
+                   "hd_sample_path")
+        return z
+
     # ------------------------------------------------------------------ fragment-constrained sampling (no reference counterpart)
     def _inpaint_schedule(self, handle, tabs):
         """{alpha_s, sigma_s, alpha_t|s, sigma_t|s} per step from the gamma grid of `_schedule`, uploaded once per table."""
@@ -813,7 +918,7 @@ class DiffusionQM9(_Base):
             self._inpaint_tabs = tabs
         return tabs
 
-    def _inpaint_setup(self, node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask):
+    def _inpaint_setup(self, node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, path_args=(None,) * 4):
         """Argument checks of the inpainting entry points (ValueError / NotImplementedError before anything is queued), then the
         device-side inputs of hd_sample_loop_inpaint."""
         if node_mask.dim() != 3 or node_mask.shape[2] != 1:
@@ -844,10 +949,12 @@ class DiffusionQM9(_Base):
             raise NotImplementedError("inpainting: mode 'gnn_dynamics' is not supported")
         if self.noise_mode == "torch":
             raise NotImplementedError("inpainting: noise_mode 'torch' is not supported (counter-based noise only)")
+        pe = self._resolve_path(*path_args, inpaint=True)
         if dev.type != "cuda":
             raise _lib.HierDiffHipError("sampling runs only on an MI355X (no CPU fallback)")
         h = self._lib_handle()
         tabs = self._inpaint_schedule(h, self._schedule(rows=B))
+        K = None if pe is None else self._path_tables(h, tabs, *pe)["K"]
         topo = self.dynamics.topology(node_mask, edge_mask, B, N)
         ctx = None
         if self.dynamics.context_node_nf > 0:
@@ -860,9 +967,15 @@ class DiffusionQM9(_Base):
         xh_known = torch.where(fmb, xh_known, torch.zeros_like(xh_known)).contiguous()
         fm_u8 = fmb.reshape(B * N).to(torch.uint8).contiguous()
         return AttrDict(h=h, tabs=tabs, topo=topo, ctx=ctx, xk=xk, hk=hk, xh_known=xh_known, fm_u8=fm_u8, B=B, N=N,
-                        R=int(resamplings), stream=_stream(dev), dev=dev)
+                        R=int(resamplings), stream=_stream(dev), dev=dev, K=K)
 
     def _inpaint_run(self, st, z, s_hi, s_lo, sample_id_base):
+        if st.K is not None:             # few-step sampling: s_hi / s_lo count path positions from the t = 0 end
+            _lib.check(_lib.load().hd_sample_path_inpaint(
+                st.h, st.topo.ptr, z.data_ptr(), _ptr(st.ctx), -1, st.K - s_hi, st.K - s_lo, None, None, st.B, self.seed,
+                sample_id_base, int(self.use_graph), st.fm_u8.data_ptr(), st.xh_known.data_ptr(), st.R, st.stream),
+                "hd_sample_path_inpaint")
+            return
         _lib.check(_lib.load().hd_sample_loop_inpaint(
             st.h, st.topo.ptr, z.data_ptr(), _ptr(st.ctx), -1, s_hi, s_lo, None, None, st.B, self.seed, sample_id_base,
             int(self.use_graph), st.fm_u8.data_ptr(), st.xh_known.data_ptr(), st.R, st.stream), "hd_sample_loop_inpaint")
@@ -881,25 +994,30 @@ class DiffusionQM9(_Base):
 
     @torch.no_grad()
     def sample_inpaint(self, node_mask: torch.Tensor, fixed_mask: torch.Tensor, x_known: torch.Tensor, h_known: torch.Tensor,
-                       context=None, resamplings: int = 1, sample_id_base: int = 0, edge_mask: Optional[torch.Tensor] = None):
+                       context=None, resamplings: int = 1, sample_id_base: int = 0, edge_mask: Optional[torch.Tensor] = None, *,
+                       steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
+                       timesteps: Optional[Sequence[int]] = None):
         """(x, h) on the device for molecules whose `fixed_mask` [B,N,1] nodes are known: `x_known` [B,N,3] / `h_known` [B,N,F] in
         data units (what `sample` returns; rows outside `fixed_mask` are ignored, the frame of the positions is free).  The free
         nodes are sampled around them by the replacement method, `resamplings` network calls per step (RePaint for > 1), inside
         the library's loop (hd_sample_loop_inpaint; algorithm and draw layout in include/hierdiff_hip.h).  Returned fixed rows:
         h = h_known exactly, x = x_known translated as one block.  Training-free conditioning: how well the free part fits the
         known one depends on the model and on `resamplings`.  A sample depends on its global id (sample_id_base + row), its
-        masks, the weights and its known values only."""
-        st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask)
+        masks, the weights and its known values only.  steps / spacing / timesteps: few-step sampling as in `sample_from_masks`
+        (hd_sample_path_inpaint), ancestral steps only - eta < 1 raises ValueError."""
+        st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask,
+                                 (steps, eta, spacing, timesteps))
         lib, T, B, N = _lib.load(), self.T, st.B, st.N
+        n_loop = T if st.K is None else st.K
         z = torch.empty((B, N, self.n_dims + self.in_node_nf), device=st.dev, dtype=torch.float32)
         _lib.check(lib.hd_noise(st.h, st.topo.ptr, None, None, B, self.seed, sample_id_base, 0, 0, z.data_ptr(), st.stream),
                    "hd_noise")
         if self.debug_checks:              # the loop's invariant after every step (host-synchronising, like the reference's asserts)
-            for s in reversed(range(T)):
+            for s in reversed(range(n_loop)):
                 self._inpaint_run(st, z, s + 1, s, sample_id_base)
                 self._check_mean_zero(z[:, :, :self.n_dims], node_mask)
         else:
-            self._inpaint_run(st, z, T, 0, sample_id_base)
+            self._inpaint_run(st, z, n_loop, 0, sample_id_base)
         zeros = torch.zeros((B, 1), device=st.dev)
         eps = self.dynamics.forward_with_topology(st.topo, zeros, z, st.ctx, None)
         x, hfeat = self._final_decode(z, eps, node_mask, edge_mask, st.tabs["decode"].numpy(), False, None,
@@ -911,12 +1029,14 @@ class DiffusionQM9(_Base):
 
     @torch.no_grad()
     def sample_grow(self, known: Sequence[Dict[str, torch.Tensor]], sizes, device, context=None, resamplings: int = 1,
-                    sample_id_base: int = 0):
+                    sample_id_base: int = 0, *, steps: Optional[int] = None, eta: Optional[float] = None,
+                    spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None):
         """List-level form of `sample_inpaint` in `sample`'s result format: `known[i]` = {'x': [k_i,3], 'h': [k_i,F]} are the fragments
         molecule i keeps (its first k_i rows in the result; k_i = 0 allowed), `sizes[i]` >= k_i its total number of fragments (one
         integer: that many for every molecule).  `context`: as in `sample`.  Returns [{'x': [n_i,3], 'h': [n_i,F] (, 'context')}] on
-        the CPU."""
+        the CPU.  steps / eta / spacing / timesteps: as in `sample_inpaint`."""
         device = torch.device(device)
+        self._resolve_path(steps, eta, spacing, timesteps, inpaint=True)       # argument errors first
         num = len(known)
         if isinstance(sizes, (int, np.integer)):
             sizes = [int(sizes)] * num
@@ -947,7 +1067,7 @@ class DiffusionQM9(_Base):
                 raise ValueError(f"context of shape {tuple(torch.as_tensor(context).shape)} does not broadcast to [{num}, {n_max}, 1]")
         x, h = self.sample_inpaint(node_mask.to(device), fixed_mask.to(device), x_known.to(device), h_known.to(device),
                                    context=None if ctx is None else ctx.to(device), resamplings=resamplings,
-                                   sample_id_base=sample_id_base)
+                                   sample_id_base=sample_id_base, steps=steps, eta=eta, spacing=spacing, timesteps=timesteps)
         x, h = x.cpu(), h.cpu()
         out = [{'x': x[i, :sizes[i]].clone(), 'h': h[i, :sizes[i]].clone()} for i in range(num)]
         if ctx is not None:
@@ -956,9 +1076,14 @@ class DiffusionQM9(_Base):
         return out
 
     @torch.no_grad()
-    def sample(self, num_samples, device, context=None, pocket_cond=None, sample_id_base: int = 0):
-        """diffusion_qm9.py:347-395: list of {'x': [n_i,3], 'h': [n_i,8], ('context': [n_i,1])} on the CPU."""
+    def sample(self, num_samples, device, context=None, pocket_cond=None, sample_id_base: int = 0, *,
+               steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
+               timesteps: Optional[Sequence[int]] = None):
+        """diffusion_qm9.py:347-395: list of {'x': [n_i,3], 'h': [n_i,8], ('context': [n_i,1])} on the CPU.
+        steps / eta / spacing / timesteps: few-step sampling, see `sample_from_masks`."""
         device = torch.device(device)
+        self._resolve_path(steps, eta, spacing, timesteps)                     # argument errors before anything is drawn
+        few = {k: v for k, v in dict(steps=steps, eta=eta, spacing=spacing, timesteps=timesteps).items() if v is not None}
         sample_n = self.nodes_dist.sample(num_samples)
         pocket = None
         if pocket_cond is not None:
@@ -975,9 +1100,9 @@ class DiffusionQM9(_Base):
             if ctx.shape != (num_samples, max(sample_n), 1):
                 raise ValueError(f"context of shape {tuple(torch.as_tensor(context).shape)} does not broadcast to "
                                  f"[{num_samples}, {max(sample_n)}, 1]")
-        return self._sample_sizes(sample_n, device, None, sample_id_base, pocket, context_full=ctx)
+        return self._sample_sizes(sample_n, device, None, sample_id_base, pocket, context_full=ctx, **({"few": few} if few else {}))
 
-    def _sample_sizes(self, sample_n, device, contexts, sample_id_base, pocket=None, context_full=None):
+    def _sample_sizes(self, sample_n, device, contexts, sample_id_base, pocket=None, context_full=None, few=None):
         """One device batch for the molecule sizes `sample_n` (global sample ids sample_id_base + i); `contexts`: one scalar
         per molecule (merged batches: the value of the batch a molecule belongs to) or None; `context_full`: the
         [num_samples, n_max, 1] tensor of `sample()` instead.  Masks as diffusion_qm9.py:349-353, result slicing as :388-395."""
@@ -995,7 +1120,7 @@ class DiffusionQM9(_Base):
                 raise ValueError("merged batches take one global context value per batch (context_range entries)")
             context = (torch.zeros([num_samples, n_max, 1]) + torch.stack(cols).reshape(num_samples, 1, 1)).to(device)
         node_mask = node_mask.to(device)
-        x, h = self.sample_from_masks(node_mask, None, context, sample_id_base=sample_id_base, pocket=pocket)
+        x, h = self.sample_from_masks(node_mask, None, context, sample_id_base=sample_id_base, pocket=pocket, **(few or {}))
         x, h = x.cpu(), h.cpu()
         xs = [x[i, :sample_n[i]].clone() for i in range(num_samples)]
         hs = [h[i, :sample_n[i]].clone() for i in range(num_samples)]
@@ -1005,7 +1130,8 @@ class DiffusionQM9(_Base):
         return [{'x': xs[i], 'h': hs[i]} for i in range(num_samples)]
 
     def sample_batches(self, batch_size, num_batches, device, context_range=None, protein_data_all=None,
-                       sample_id_base: int = 0):
+                       sample_id_base: int = 0, *, steps: Optional[int] = None, eta: Optional[float] = None,
+                       spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None):
         """diffusion_qm9.py:397-436, incl. the protein branch (`protein_data_all`: list of dicts with
         'residue_type', 'coord', 'pocket_name', 'ligand_name').
 
@@ -1019,6 +1145,8 @@ class DiffusionQM9(_Base):
         configurations whose results depend on a batch's padded width (below).  One difference that
         is not a sample's own: the NaN guard (en_dynamics.py:109-111) zeroes the velocity of the whole DEVICE batch."""
         device = torch.device(device)
+        self._resolve_path(steps, eta, spacing, timesteps)                     # few-step sampling (`sample_from_masks`): argument errors first
+        few = {k: v for k, v in dict(steps=steps, eta=eta, spacing=spacing, timesteps=timesteps).items() if v is not None}
         # Not merged either: mode 'gnn_dynamics' (torch.randn draws whatever noise_mode says, messages over padded nodes) and
         # aggregation_method 'mean' (the divisor is the padded N of the call) - both depend on the padded width of the batch a
         # molecule sits in - and context_range entries that are not one scalar per batch.
@@ -1041,7 +1169,8 @@ class DiffusionQM9(_Base):
                     if hi + bs - lo > int(self.merge_batches) or (self.merge_edges and edges + more > int(self.merge_edges)):
                         break
                     hi, edges = hi + bs, edges + more
-                results.extend(self._sample_sizes(sizes[lo:hi], device, ctxs[lo:hi] if ctxs else None, sample_id_base + lo))
+                results.extend(self._sample_sizes(sizes[lo:hi], device, ctxs[lo:hi] if ctxs else None, sample_id_base + lo,
+                                                  **({"few": few} if few else {})))
                 lo = hi
             return results, []
         protein_cond_all = None
@@ -1057,13 +1186,13 @@ class DiffusionQM9(_Base):
                 # the reference indexes the names modulo len(protein_cond_all) == 4 (diffusion_qm9.py:428); kept as is
                 names = [protein_data_all[k]['pocket_name'] + '/' + protein_data_all[k]['ligand_name']
                          for k in range(lo % len(protein_cond_all), hi % len(protein_cond_all))]
-                results.extend(self.sample(batch_size, device, context=None, pocket_cond=cond, sample_id_base=base))
+                results.extend(self.sample(batch_size, device, context=None, pocket_cond=cond, sample_id_base=base, **few))
                 test_names.extend(names)
             elif context_range is not None:
                 results.extend(self.sample(batch_size, device, context=context_range[i % len(context_range)],
-                                           pocket_cond=None, sample_id_base=base))
+                                           pocket_cond=None, sample_id_base=base, **few))
             else:
-                results.extend(self.sample(batch_size, device, context=None, pocket_cond=None, sample_id_base=base))
+                results.extend(self.sample(batch_size, device, context=None, pocket_cond=None, sample_id_base=base, **few))
         return results, test_names
 
 
@@ -1071,9 +1200,11 @@ class EnVariationalDiffusion(DiffusionQM9):
     """EDM-style entry point (en_diffusion.py:634-667): masks supplied by the caller, fix_noise honoured."""
 
     @torch.no_grad()
-    def sample(self, n_samples, n_nodes, node_mask, edge_mask, context, fix_noise=False):  # type: ignore[override]
+    def sample(self, n_samples, n_nodes, node_mask, edge_mask, context, fix_noise=False, *,  # type: ignore[override]
+               steps=None, eta=None, spacing=None, timesteps=None):
         assert node_mask.shape[0] == n_samples and node_mask.shape[1] == n_nodes
-        x, h = self.sample_from_masks(node_mask, edge_mask, context, fix_noise=fix_noise)
+        x, h = self.sample_from_masks(node_mask, edge_mask, context, fix_noise=fix_noise, steps=steps, eta=eta, spacing=spacing,
+                                      timesteps=timesteps)
         if self.debug_checks:
             self._check_mean_zero(x, node_mask)
         max_cog = torch.sum(x, dim=1, keepdim=True).abs().max()

@@ -1,0 +1,142 @@
+"""Few-step sampling: paths through the trained time grid and their per-transition coefficient rows.
+
+A path is a strictly decreasing list of grid indices T = t_0 > t_1 > ... > t_K = 0; transition k goes from t = t_k to
+s = t_{k+1}.  The update of `sample_p_zs_given_zt` (diffusion_qm9.py:312-345) is written for any s < t, so a path needs no
+retraining and no new network code - only rows of coefficients from the SAME gamma grid the plain schedule uses
+(`noise_model.schedule_tables`), which `path_tables` computes on the host:
+
+  eta = 1      ancestral rows {alpha_t|s, sigma2_t|s, sigma_t, sigma} = `step_coefficients(g[s], g[t])`: the plain loop's own row
+               format, so the identity path T, T-1, .., 0 gives the plain table bit for bit;
+  0 <= eta < 1 linear rows {a, b, c, 0} of z_s = a z_t - b eps + c noise with sigma~ = eta sigma_t|s sigma_s / sigma_t,
+               a = alpha_s / alpha_t, b = alpha_s sigma_t / alpha_t - sqrt(sigma_s^2 - sigma~^2), c = sigma~ (the DDIM family;
+               eta = 0 is the noise-free update), evaluated in float64 and rounded once.  At eta = 1 this is the ancestral update
+               algebraically; the ancestral format is kept there so that stride 1 stays bit-identical.
+
+Which K and eta keep sample quality is a property of the trained checkpoint: nothing here can tell.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from .noise_model import step_coefficients
+
+SPACINGS = ("uniform", "quadratic")
+
+
+def _check_T_K(T, K) -> "tuple[int, int]":
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)):
+        raise ValueError(f"steps must be an integer, got {K!r}")
+    T, K = int(T), int(K)
+    if T < 1:
+        raise ValueError(f"timesteps must be >= 1, got {T}")
+    if K < 1 or K > T:
+        raise ValueError(f"steps must be in 1 .. {T} (the trained grid), got {K}")
+    return T, K
+
+
+def uniform_path(T: int, K: int) -> List[int]:
+    """t_k = T - round_half_up(k T / K) in integer arithmetic: strictly monotone for every 1 <= K <= T (consecutive values of
+    k T / K differ by T / K >= 1), the identity path for K = T."""
+    T, K = _check_T_K(T, K)
+    return [T - (2 * k * T + K) // (2 * K) for k in range(K + 1)]
+
+
+def quadratic_path(T: int, K: int) -> List[int]:
+    """t_k ~ T ((K - k) / K)^2: denser near t = 0 (the usual DDIM alternative).  Built from the t = 0 end upwards with
+    t_k = min(max(round(.), t_{k+1} + 1), T - k), which is strictly monotone and ends in T by construction."""
+    T, K = _check_T_K(T, K)
+    path = [0] * (K + 1)
+    for k in range(K - 1, -1, -1):
+        j = K - k
+        raw = (2 * T * j * j + K * K) // (2 * K * K)              # round_half_up(T j^2 / K^2)
+        path[k] = min(max(raw, path[k + 1] + 1), T - k)
+    return path
+
+
+def explicit_path(T: int, timesteps: Sequence[int]) -> List[int]:
+    """A caller's own list, validated: integers, first T, last 0, strictly decreasing."""
+    T = int(T)
+    try:
+        vals = list(timesteps)
+    except TypeError:
+        raise ValueError(f"timesteps must be a sequence of integers, got {timesteps!r}") from None
+    out = []
+    for v in vals:
+        if isinstance(v, torch.Tensor) and v.numel() == 1 and not v.is_floating_point():
+            v = int(v)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"timesteps must hold integers, got {v!r}")
+        out.append(int(v))
+    if len(out) < 2 or out[0] != T or out[-1] != 0:
+        raise ValueError(f"timesteps must start at {T} and end at 0, got {out[:1]} .. {out[-1:]}")
+    if any(b >= a for a, b in zip(out[:-1], out[1:])):
+        raise ValueError("timesteps must be strictly decreasing")
+    return out
+
+
+def build_path(T: int, steps: Optional[int] = None, spacing: str = "uniform", timesteps: Optional[Sequence[int]] = None) -> List[int]:
+    """The path for `steps` transitions with the given spacing, or the validated explicit `timesteps`."""
+    if steps is not None and timesteps is not None:
+        raise ValueError("give either steps or timesteps, not both")
+    if timesteps is not None:
+        return explicit_path(T, timesteps)
+    if steps is None:
+        steps = int(T)
+    if spacing == "uniform":
+        return uniform_path(T, steps)
+    if spacing == "quadratic":
+        return quadratic_path(T, steps)
+    raise ValueError(f"spacing must be one of {SPACINGS}, got {spacing!r}")
+
+
+def check_eta(eta) -> float:
+    try:
+        e = float(eta)
+    except (TypeError, ValueError):
+        raise ValueError(f"eta must be a number in [0, 1], got {eta!r}") from None
+    if not (0.0 <= e <= 1.0):
+        raise ValueError(f"eta must be in [0, 1], got {eta!r}")
+    return e
+
+
+def linear_coefficients(gamma_s: torch.Tensor, gamma_t: torch.Tensor, eta: float) -> torch.Tensor:
+    """[rows, 4] float64 {a, b, c, sigma_s^2 - sigma~^2} of z_s = a z_t - b eps + c noise (module docstring)."""
+    gs, gt = gamma_s.reshape(-1).to(torch.float64), gamma_t.reshape(-1).to(torch.float64)
+    alpha_s, alpha_t = torch.sqrt(torch.sigmoid(-gs)), torch.sqrt(torch.sigmoid(-gt))
+    sigma2_s, sigma_t = torch.sigmoid(gs), torch.sqrt(torch.sigmoid(gt))
+    sigma2_ts = -torch.expm1(F.softplus(gs) - F.softplus(gt))
+    sig = float(eta) * torch.sqrt(sigma2_ts) * torch.sqrt(sigma2_s) / sigma_t
+    rest = sigma2_s - sig * sig
+    a = alpha_s / alpha_t
+    b = a * sigma_t - torch.sqrt(torch.clamp(rest, min=0.0))
+    return torch.stack([a, b, sig, rest], dim=1)
+
+
+@torch.no_grad()
+def path_tables(gamma: torch.Tensor, path: Sequence[int], eta: float = 1.0) -> Dict[str, object]:
+    """Rows of a path from the gamma grid [T+1] (fp32, `schedule_tables(...)["gamma"]`): t_idx / s_idx int32 [K], coef fp32 [K,4],
+    form (0 ancestral rows, 1 linear rows) and, for eta = 1, the inpainting rows {alpha_s, sigma_s, alpha_t|s, sigma_t|s}."""
+    eta = check_eta(eta)
+    g = torch.as_tensor(gamma, dtype=torch.float32).reshape(-1, 1)
+    idx = torch.as_tensor(list(path), dtype=torch.int64)
+    t_idx, s_idx = idx[:-1], idx[1:]
+    if eta == 1.0:
+        # evaluated in ascending s like the plain table (torch's vectorised CPU kernels may round an element differently at
+        # another position of the array): for the identity path this IS the call `schedule_tables` makes, so the bits agree
+        s_up, t_up = s_idx.flip(0), t_idx.flip(0)
+        coef_up = step_coefficients(g[s_up], g[t_up])
+        gs = g[s_up].reshape(-1)
+        inpaint = torch.stack([torch.sqrt(torch.sigmoid(-gs)), torch.sqrt(torch.sigmoid(gs)), coef_up[:, 0], torch.sqrt(coef_up[:, 1])],
+                              dim=1).to(torch.float32).flip(0).contiguous()
+        coef = coef_up.flip(0).contiguous()
+        form = 0
+    else:
+        lin = linear_coefficients(g[s_idx], g[t_idx], eta)
+        coef = torch.cat([lin[:, :3], torch.zeros_like(lin[:, :1])], dim=1).to(torch.float32).contiguous()
+        inpaint, form = None, 1
+    return {"t_idx": t_idx.to(torch.int32).contiguous(), "s_idx": s_idx.to(torch.int32).contiguous(), "coef": coef, "form": form,
+            "coef_inpaint": inpaint, "K": int(t_idx.numel()), "eta": eta}

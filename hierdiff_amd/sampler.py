@@ -126,7 +126,8 @@ def read_known(path: str) -> List[dict]:
     return obj
 
 
-def main(argv=None) -> int:
+def parse_args(argv=None):
+    """The command line, checked: every argument error ends here (SystemExit), before a device is opened."""
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--checkpoint", default=None, help="reference Lightning checkpoint (.ckpt); random init if omitted")
     ap.add_argument("--batch-size", type=int, default=2)        # conf/sample/default.yaml:1
@@ -152,14 +153,30 @@ def main(argv=None) -> int:
     ap.add_argument("--grow", type=int, default=None, help="fragments to add to each molecule of --known")
     ap.add_argument("--resamplings", type=int, default=1,
                     help="network calls per diffusion step of --known runs (1: plain replacement; more: RePaint-style resampling)")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="few-step sampling: K <= timesteps transitions on a sub-sequence of the trained grid (default: all of "
+                         "them); combinable with --known/--grow.  Mechanism only: which K keeps sample quality is for you to validate")
+    ap.add_argument("--eta", type=float, default=1.0,
+                    help="1: ancestral steps (default); 0 <= eta < 1: DDIM-family update, 0 = noise-free (not with --known)")
+    ap.add_argument("--spacing", choices=["uniform", "quadratic"], default="uniform", help="how --steps spreads over the grid")
     args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not (0.0 <= args.eta <= 1.0):
+        ap.error("--eta must be in [0, 1]")
+    if args.known is not None and args.eta < 1.0:
+        ap.error("--eta < 1 does not combine with --known (inpainting takes ancestral steps)")
     if (args.known is None) != (args.grow is None):
         ap.error("--known and --grow go together")
     if args.known is not None and (args.grow < 0 or args.resamplings < 1):
         ap.error("--grow must be >= 0 and --resamplings >= 1")
     if args.sample_config:
         args.batch_size, args.num_batches = load_sample_config(args.sample_config)
+    return args
 
+
+def main(argv=None) -> int:
+    args = parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -184,6 +201,9 @@ def main(argv=None) -> int:
     model = model.to(dev)
     model.dynamics.precision = args.precision
     model.seed = args.seed
+    if args.steps is not None and args.steps > model.T:
+        raise SystemExit(f"--steps {args.steps} exceeds the model's {model.T} timesteps")
+    model.sample_steps, model.sample_eta, model.sample_spacing = args.steps, args.eta, args.spacing
     if world > 1:
         broadcast_model_weights(model, src=0)
 

@@ -180,7 +180,11 @@ int hd_final_decode(hd_handle* h, hd_topology* topo, const float* z0, const floa
  *   inpainting loop       draw = (T + 2) * (3 j + k) + (T - s) for resampling round j = 0 .. r-1 of step s and stream
  *                         k = 0 posterior step, 1 noise of the known part (e_kn), 2 noise of the jump back (e_jump).
  *                         (j, k) = (0, 0) is the plain stream, so r = 1 without fixed nodes reproduces plain sampling bit for bit;
- *                         (T + 2) * 3 r must fit 32 bits. */
+ *                         (T + 2) * 3 r must fit 32 bits.
+ *   path loops            (hd_sample_path, hd_sample_path_inpaint) the counter is the FINE-GRID index of the arrival step: the
+ *                         transition t -> s of a path draws at T - s (inpainting: (T + 2) * (3 j + k) + (T - s)), draw 0 = z_T and
+ *                         draw T + 1 = the final decode as above - the layouts above restricted to the visited s.  The identity path
+ *                         T, T-1, .., 0 therefore reproduces the plain loops bit for bit. */
 int hd_noise(hd_handle* h, hd_topology* topo, const float* raw_x, const float* raw_h, int noise_rows,
              uint64_t seed, uint64_t sample_id_base, uint32_t draw, int share_rows, float* z, void* stream);
 
@@ -191,13 +195,41 @@ int hd_set_schedule(hd_handle* h, int T, const float* tau, const float* coef4);
 /* Runs posterior steps s = s_hi-1 ... s_lo on z[B,N,D] in place (rows >= mol_shape untouched):
  * per step one hd_egnn_forward at tau[s+1] and one hd_posterior_step.
  *   raw_x/raw_h  device [(s_hi-s_lo), noise_rows, mol, 3|F] in step order (first = s_hi-1), or NULL
- *                to use the counter-based generator with draw = T - s (draw 0 is z_T).
+ *                to use the counter-based generator with draw = T - s (draw 0 is z_T).  (The loop on a sub-sequence of the
+ *                grid is hd_sample_path below; its draws are the same T - s of the steps it visits.)
  *   use_graph    replay each step from a captured hipGraph (0 = plain launches).  The instantiated graph is
  *                cached with the topology and reused by later calls with the same arguments (any z / context /
  *                sample_id_base); it is stream-ordered like every other call - no host synchronisation. */
 int hd_sample_loop(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
                    int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
                    uint64_t seed, uint64_t sample_id_base, int use_graph, void* stream);
+
+/* ---- Few-step sampling (ABI 12, additive): the reverse chain on a sub-sequence of the schedule's grid.  A path is K transitions
+ * t_idx[k] -> s_idx[k] (grid indices, 0 <= s_idx[k] < t_idx[k] <= T, t_idx[k + 1] = s_idx[k]); the update of sample_p_zs_given_zt
+ * (diffusion_qm9.py:312-345) holds for any s < t.  hd_set_path uploads the path next to the plain schedule, which must be set (it
+ * supplies T and tau) and whose replacement needs a new upload here (HD_E_STATE otherwise).  Host arrays:
+ *   coef4          K rows; form 0: {alpha_t_given_s, sigma2_t_given_s, sigma_t, sigma} of (s_idx[k], t_idx[k]), the plain step's row;
+ *                  form 1: {a, b, c, 0} of the linear update z_s = (a z_t - b eps) + c noise (DDIM family: sigma~ = eta sigma_t|s sigma_s /
+ *                  sigma_t, a = alpha_s / alpha_t, b = a sigma_t - sqrt(sigma_s^2 - sigma~^2), c = sigma~), eps and noise with their x parts
+ *                  mean-removed and the result re-centred as in the plain step.  A row with c == 0 generates and reads no normal.
+ *   coef4_inpaint  NULL, or K rows {alpha_s, sigma_s, alpha_t_given_s, sigma_t_given_s} for hd_sample_path_inpaint (form 0 only). */
+int hd_set_path(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* coef4, int form, const float* coef4_inpaint);
+/* Transitions k = k_lo ... k_hi-1 of the path on z[B,N,D] in place; arguments, stream ordering, pocket rows (mol_shape) and shared
+ * noise rows (noise_rows = 1) as in hd_sample_loop.  Network time tau[t_idx[k]]; noise counter T - s_idx[k] (layout at hd_noise).
+ *   raw_x/raw_h  device [(k_hi-k_lo), noise_rows, mol, 3|F] indexed by path position (first = k_lo), or NULL.
+ *   use_graph    ONE captured transition per topology, whatever K: the path position lives in device memory and the captured
+ *                kernels read time, coefficient row and draw through the uploaded tables.  Cached like the plain loop's graph and
+ *                rebuilt when the path, seed, weights, schedule or noise arguments change; use_graph = 0 gives the same bits. */
+int hd_sample_path(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
+                   const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base,
+                   int use_graph, void* stream);
+/* hd_sample_loop_inpaint on the path: the rounds 1 - 4 below per transition (s, t) = (s_idx[k], t_idx[k]).  Restrictions of
+ * hd_sample_loop_inpaint, and the path must hold ancestral rows (form 1: HD_E_INVALID) and inpainting rows (else HD_E_STATE). */
+int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
+                           const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base,
+                           int use_graph, const uint8_t* fixed_mask, const float* xh_known, int resamplings, void* stream);
+/* Number of times the topology's captured path transition was instantiated (-1: null topology): a cached replay leaves it unchanged. */
+long long hd_path_graph_builds(const hd_topology* topo);
 
 /* ---- Fragment-constrained sampling ("inpainting"; ABI 12, additive; no reference counterpart): sample the free nodes of a
  * molecule around fragments whose positions and features are known, by the replacement method of score-based models, optionally with
