@@ -64,6 +64,12 @@ SIGNATURES = {
     "hd_sample_path_inpaint": (C.c_int, [_VP, _VP, _FP, _FP, C.c_int, C.c_int, C.c_int, _FP, _FP, C.c_int,
                                          C.c_uint64, C.c_uint64, C.c_int, _U8P, _FP, C.c_int, _VP]),
     "hd_path_graph_builds": (C.c_longlong, [_VP]),
+    "hd_set_nll_terms": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "hd_nll_terms": (C.c_int, [_VP, _VP, _FP, _FP, C.c_int, C.c_int, C.c_int, _FP, _FP, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
+                               _VP, _FP, _VP]),
+    "hd_nll_graph_builds": (C.c_longlong, [_VP]),
+    "hd_nll_finish": (C.c_int, [_VP, _VP, _FP, _FP, C.c_int, _FP, _FP, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_float),
+                                C.c_int, C.c_int, _VP, _FP, _VP]),
     "hd_inpaint_decode_fix": (C.c_int, [_VP, _VP, _U8P, _FP, _FP, _FP, _FP, _VP]),
     "hd_topology_nodes": (C.c_int, [_VP, _VP]),
     "hd_topology_nodes_device": (C.c_int, [_VP, _VP, _VP]),

@@ -107,6 +107,12 @@ struct hd_handle {
     int *d_path_t, *d_path_s;
     float *d_path_coef, *d_path_coef_ip;         // [K][4] each; d_path_coef_ip null when no inpainting rows were given
     unsigned long long path_sched_gen, path_gen; // sched_gen the path was set for (0: not set); bumped by every hd_set_path
+    // scoring (hd_set_nll_terms / hd_nll_terms / hd_nll_finish): K terms t_idx[k] of the bound, rows {alpha_t, sigma_t, w_t, 0}
+    int nll_K;
+    std::vector<int> nll_t_h;
+    int* d_nll_t;
+    float* d_nll_coef;
+    unsigned long long nll_sched_gen, nll_gen;   // sched_gen the terms were set for (0: not set); bumped by every hd_set_nll_terms
     int split_max_tiles;        // HD_SPLIT_MAX_TILES (a measurement build may override it from the environment)
     int fuse_min_rows;          // HD_FUSE_MIN_ROWS
     int node_split_max_rows;    // HD_NODE_SPLIT_MAX_ROWS
@@ -166,6 +172,19 @@ struct PathKey {
     }
 };
 
+// The same for a captured term of the scoring loop (hd_nll_terms).
+struct NllKey {
+    const float *raw_x, *raw_h;
+    const float* err;                                  // the library-owned e_t table the captured kernel writes (null: not wanted)
+    int has_ctx, k_lo;                                 // k_lo: injected-noise offsets are relative to the first term
+    uint64_t seed;
+    unsigned long long weights_gen, sched_gen, nll_gen;
+    bool operator==(const NllKey& o) const {
+        return raw_x == o.raw_x && raw_h == o.raw_h && err == o.err && has_ctx == o.has_ctx && k_lo == o.k_lo && seed == o.seed &&
+               weights_gen == o.weights_gen && sched_gen == o.sched_gen && nll_gen == o.nll_gen;
+    }
+};
+
 struct hd_topology {
     hd_handle* h;
     int device;
@@ -198,6 +217,14 @@ struct hd_topology {
     hipGraphExec_t gexec_path;
     PathKey pkey;
     long long path_builds;
+    // hd_nll_terms / hd_nll_finish: eps_t and, for the captured term, library-owned copies of xh / the accumulator / the e_t table
+    // (allocated by the first such call; z_t lives in zbuf); `nll_builds` counts the instantiations (hd_nll_graph_builds)
+    hipGraphExec_t gexec_nll;
+    NllKey nkey;
+    long long nll_builds;
+    float *nll_eps, *nll_xh, *nll_err;
+    double* nll_acc;
+    int nll_err_rows;
     // lifetime: the tables arrive in stream order of `stream0` (hd_topology_create_s); `ready` marks their arrival for
     // any other stream a caller launches on.  A topology used on one stream only hands its arena back to the pool
     // (arena_release) with an event instead of a device-wide synchronisation.
@@ -309,6 +336,7 @@ extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
     h->d_coef_ip = nullptr; h->ip_sched_gen = 0; h->ip_gen = 0; h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
     h->path_K = 0; h->path_form = 0; h->d_path_t = h->d_path_s = nullptr; h->d_path_coef = h->d_path_coef_ip = nullptr;
     h->path_sched_gen = 0; h->path_gen = 0;
+    h->nll_K = 0; h->d_nll_t = nullptr; h->d_nll_coef = nullptr; h->nll_sched_gen = 0; h->nll_gen = 0;
     h->d_nanflag = nullptr; h->d_nan_events = nullptr; h->d_step = nullptr; h->d_draw = nullptr; h->d_tcur = nullptr;
     h->d_base = nullptr;
     h->split_max_tiles = HD_SPLIT_MAX_TILES;
@@ -359,6 +387,7 @@ extern "C" int hd_destroy(hd_handle* h) {
     hipFree(h->d_tau); hipFree(h->d_coef); hipFree(h->d_step); hipFree(h->d_draw); hipFree(h->d_tcur); hipFree(h->d_base);
     hipFree(h->d_coef_ip); hipFree(h->d_ipdraw);
     hipFree(h->d_path_t); hipFree(h->d_path_s); hipFree(h->d_path_coef); hipFree(h->d_path_coef_ip);
+    hipFree(h->d_nll_t); hipFree(h->d_nll_coef);
 #ifdef HD_DEBUG_KERNELS
     hipFree(h->d_trace);
 #endif
@@ -732,7 +761,7 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     ArenaSlot sl{t->device, t->arena, t->arena_bytes, t->staging, t->staging_bytes, nullptr};
     // a captured graph, or launches on several streams: wait for the device (the rare case - a sampling topology lives as
     // long as its model); otherwise an event behind the topology's last work guards the arena's next owner
-    bool pooled = t->arena && !t->gexec && !t->gexec_ip && !t->gexec_path && !t->multi_stream;
+    bool pooled = t->arena && !t->gexec && !t->gexec_ip && !t->gexec_path && !t->gexec_nll && !t->multi_stream;
     if (pooled && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) == hipSuccess) {
         if (hipEventRecord(sl.done, t->last_stream) != hipSuccess) { (void)hipEventDestroy(sl.done); sl.done = nullptr; pooled = false; }
     } else {
@@ -744,6 +773,11 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     if (t->gexec_path) hipGraphExecDestroy(t->gexec_path);
     if (t->ip_fixed) (void)hipFree(t->ip_fixed);
     if (t->ip_known) (void)hipFree(t->ip_known);
+    if (t->gexec_nll) hipGraphExecDestroy(t->gexec_nll);
+    if (t->nll_eps) (void)hipFree(t->nll_eps);
+    if (t->nll_xh) (void)hipFree(t->nll_xh);
+    if (t->nll_err) (void)hipFree(t->nll_err);
+    if (t->nll_acc) (void)hipFree(t->nll_acc);
     if (t->ready) (void)hipEventDestroy(t->ready);
     if (t->arena) arena_release(sl);                    // tables and workspace live in one allocation
     delete t->node_of_host;
@@ -3093,6 +3127,195 @@ extern "C" int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z,
     HIP_TRY(hipSetDevice(h->device));
     return path_loop(h, topo, z, context, -1, k_lo, k_hi, nullptr, nullptr, noise_rows, seed, sample_id_base, use_graph,
                      fixed_mask, xh_known, resamplings, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------- scoring: every term of the variational bound
+
+extern "C" int hd_set_nll_terms(hd_handle* h, int K, const int* t_idx, const float* coef4) {
+    if (!h || !t_idx || !coef4 || K < 1) return fail(HD_E_INVALID, "hd_set_nll_terms: bad argument");
+    if (h->T < 1) return fail(HD_E_STATE, "hd_set_nll_terms: schedule not set (hd_set_schedule)");
+    if (K > h->T) return fail(HD_E_INVALID, "hd_set_nll_terms: more terms than the schedule has steps");
+    for (int k = 0; k < K; ++k)
+        if (t_idx[k] < 1 || t_idx[k] > h->T) return fail(HD_E_INVALID, "hd_set_nll_terms: need 1 <= t_idx[k] <= T");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
+    hipFree(h->d_nll_t); hipFree(h->d_nll_coef);
+    h->d_nll_t = nullptr; h->d_nll_coef = nullptr;
+    h->nll_sched_gen = 0; h->nll_K = 0;
+    h->nll_t_h.assign(t_idx, t_idx + K);
+    HD_TRY(dev_upload(&h->d_nll_t, h->nll_t_h));
+    HD_TRY(dev_upload(&h->d_nll_coef, std::vector<float>(coef4, coef4 + (size_t)4 * K)));
+    h->nll_K = K;
+    h->nll_sched_gen = h->sched_gen;
+    h->nll_gen++;                              // captured graphs hold the old table addresses
+    return HD_OK;
+}
+
+extern "C" long long hd_nll_graph_builds(const hd_topology* topo) { return topo ? topo->nll_builds : -1; }
+
+// checks shared by hd_nll_terms and hd_nll_finish, in the order the header documents
+static int nll_ready(hd_handle* h, hd_topology* topo, const char* who, const float* raw_x, const float* raw_h, int noise_rows,
+                     int mol_shape, const float* context) {
+    const std::string w(who);
+    if (h->T < 1) return fail(HD_E_STATE, w + ": schedule not set (hd_set_schedule)");
+    if (h->nll_K < 1 || h->nll_sched_gen != h->sched_gen)
+        return fail(HD_E_STATE, w + ": terms not set for the current schedule (hd_set_nll_terms)");
+    if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, w + ": raw_x and raw_h go together");
+    if (noise_rows != topo->B) return fail(HD_E_INVALID, w + ": noise_rows must be B");
+    if (mol_shape >= 0 && mol_shape < topo->N) return fail(HD_E_INVALID, w + ": fixed tail rows (mol_shape < N) are not supported");
+    if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, w + ": context required");
+    if (!h->cfg.condition_time) return fail(HD_E_INVALID, w + ": needs a time-conditioned model");
+    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, w + ": N * D floats exceed one workgroup's LDS");
+    return HD_OK;
+}
+
+static int nll_launch_zt(hd_handle* h, hd_topology* t, const float* xh, const float* coef, float alpha, float sigma, const NoiseSrc& ns,
+                         int k, int raw_k0, const int* step_ptr, const uint32_t* draw_ptr, const unsigned long long* base_ptr,
+                         hipStream_t s) {
+    ProfScope ps(h, s, 2);
+    NllZtArgs a;
+    a.xh = xh; a.nm = t->nm_bytes; a.eps = t->nll_eps; a.zt = t->zbuf; a.coef = coef; a.noise = ns; a.step_ptr = step_ptr;
+    a.draw_ptr = draw_ptr; a.base_ptr = base_ptr; a.alpha = alpha; a.sigma = sigma; a.k = k; a.raw_k0 = raw_k0;
+    a.B = t->B; a.N = t->N; a.D = h->D; a.F = h->F;
+    hipLaunchKernelGGL(k_nll_zt, dim3(t->B), dim3(256), (size_t)t->N * h->D * sizeof(float), s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+static int nll_launch_err(hd_handle* h, hd_topology* t, double* acc, float* err, int k, const int* step_ptr, hipStream_t s) {
+    ProfScope ps(h, s, 2);
+    NllErrArgs a;
+    a.eps = t->nll_eps; a.net = t->eps; a.coef = h->d_nll_coef; a.acc = acc; a.err = err; a.step_ptr = step_ptr; a.k = k;
+    a.B = t->B; a.ND = t->N * h->D;
+    hipLaunchKernelGGL(k_nll_err, dim3(t->B), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_nll_terms(hd_handle* h, hd_topology* topo, const float* xh, const float* context, int mol_shape, int k_lo, int k_hi,
+                            const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base,
+                            int use_graph, double* acc, float* err_terms, void* stream) {
+    if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_nll_terms: need 0 <= k_lo <= k_hi <= K");
+    HD_TRY(check_ready(h, topo, "hd_nll_terms"));
+    HD_TRY(nll_ready(h, topo, "hd_nll_terms", raw_x, raw_h, noise_rows, mol_shape, context));
+    if (k_hi > h->nll_K) return fail(HD_E_INVALID, "hd_nll_terms: need 0 <= k_lo <= k_hi <= K");
+    if (!xh || !acc) return fail(HD_E_INVALID, "hd_nll_terms: null xh / acc");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int B = topo->B, N = topo->N, K = h->nll_K, nterms = k_hi - k_lo;
+    const size_t BN = (size_t)B * N;
+    const size_t zbytes = BN * h->D * sizeof(float);
+    const size_t cbytes = BN * h->cfg.context_node_nf * sizeof(float);
+    topo_use(topo, s);
+    if (nterms == 0) return HD_OK;
+    if (!topo->nll_eps) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_eps), zbytes));
+    if (!use_graph) {
+        for (int k = k_lo; k < k_hi; ++k) {
+            const int t = h->nll_t_h[k];
+            HD_TRY(nll_launch_zt(h, topo, xh, h->d_nll_coef, 0.f, 0.f, make_noise(raw_x, raw_h, B, seed, sample_id_base, (uint32_t)t, 0),
+                                 k, k_lo, nullptr, nullptr, nullptr, s));
+            HD_TRY(forward_impl(h, topo, topo->zbuf, h->d_tau + t, 1, context, -1, topo->eps, s));
+            HD_TRY(nll_launch_err(h, topo, acc, err_terms, k, nullptr, s));
+        }
+        return HD_OK;
+    }
+    // ONE captured term, replayed nterms times: the term position lives in d_step and k_nll_advance derives the network time and
+    // the draw from the uploaded list.  Everything else as in the path loop (library-owned copies, events instead of host waits).
+    hipStream_t rs = s;
+    if (s == nullptr) {
+        if (!h->own_stream) HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+        rs = h->own_stream;
+        HIP_TRY(hipEventRecord(h->ev_in, s));
+        HIP_TRY(hipStreamWaitEvent(rs, h->ev_in, 0));
+    }
+    if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(rs, h->ev_last, 0));
+    if (!topo->nll_xh) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_xh), zbytes));
+    if (!topo->nll_acc) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_acc), (size_t)B * sizeof(double)));
+    if (err_terms && topo->nll_err_rows < K) {               // grow the e_t table: a graph that holds the old address goes stale (key)
+        if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
+        HIP_TRY(hipStreamSynchronize(rs));
+        if (topo->nll_err) (void)hipFree(topo->nll_err);
+        topo->nll_err = nullptr; topo->nll_err_rows = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_err), (size_t)K * B * sizeof(float)));
+        topo->nll_err_rows = K;
+    }
+    NllKey key;
+    key.raw_x = raw_x; key.raw_h = raw_h; key.err = err_terms ? topo->nll_err : nullptr; key.has_ctx = context ? 1 : 0;
+    key.k_lo = raw_x ? k_lo : 0; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen; key.nll_gen = h->nll_gen;
+    if (topo->gexec_nll && !(topo->nkey == key)) {
+        if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
+        HIP_TRY(hipStreamSynchronize(rs));
+        hipGraphExecDestroy(topo->gexec_nll);
+        topo->gexec_nll = nullptr;
+    }
+    NllWords w;
+    w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.tau = h->d_tau; w.t_idx = h->d_nll_t; w.K = K;
+    if (!topo->gexec_nll) {
+        const int was_prof = h->prof;
+        h->prof = 0;
+        hipGraph_t graph = nullptr;
+        HIP_TRY(hipStreamBeginCapture(rs, hipStreamCaptureModeThreadLocal));
+        int rc = nll_launch_zt(h, topo, topo->nll_xh, h->d_nll_coef, 0.f, 0.f, make_noise(raw_x, raw_h, B, seed, 0, 0, 0), 0, k_lo,
+                               h->d_step, h->d_draw, h->d_base, rs);
+        if (rc == HD_OK) rc = forward_impl(h, topo, topo->zbuf, h->d_tcur, 1, context ? topo->ctxbuf : nullptr, -1, topo->eps, rs);
+        if (rc == HD_OK) rc = nll_launch_err(h, topo, topo->nll_acc, key.err ? topo->nll_err : nullptr, 0, h->d_step, rs);
+        if (rc == HD_OK) hipLaunchKernelGGL(k_nll_advance, dim3(1), dim3(1), 0, rs, w);
+        const hipError_t ce = hipStreamEndCapture(rs, &graph);
+        h->prof = was_prof;
+        if (rc != HD_OK) { if (graph) hipGraphDestroy(graph); return rc; }
+        if (ce != hipSuccess) return fail(HD_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
+        const hipError_t ie = hipGraphInstantiate(&topo->gexec_nll, graph, nullptr, nullptr, 0);
+        hipGraphDestroy(graph);
+        if (ie != hipSuccess) { topo->gexec_nll = nullptr; return fail(HD_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+        topo->nkey = key;
+        topo->nll_builds++;
+    }
+    HIP_TRY(hipMemcpyAsync(topo->nll_xh, xh, zbytes, hipMemcpyDeviceToDevice, rs));
+    if (context) HIP_TRY(hipMemcpyAsync(topo->ctxbuf, context, cbytes, hipMemcpyDeviceToDevice, rs));
+    HIP_TRY(hipMemcpyAsync(topo->nll_acc, acc, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, rs));
+    hipLaunchKernelGGL(k_nll_state, dim3(1), dim3(1), 0, rs, w, k_lo, (unsigned long long)sample_id_base);
+    for (int k = 0; k < nterms; ++k) {
+        const hipError_t le = hipGraphLaunch(topo->gexec_nll, rs);
+        if (le != hipSuccess) return fail(HD_E_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(le));
+    }
+    HIP_TRY(hipMemcpyAsync(acc, topo->nll_acc, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, rs));
+    if (err_terms)
+        HIP_TRY(hipMemcpyAsync(err_terms + (size_t)k_lo * B, topo->nll_err + (size_t)k_lo * B, (size_t)nterms * B * sizeof(float),
+                               hipMemcpyDeviceToDevice, rs));
+    HIP_TRY(hipEventRecord(h->ev_last, rs));
+    h->ev_last_set = true;
+    if (rs != s) {
+        HIP_TRY(hipEventRecord(h->ev_out, rs));
+        HIP_TRY(hipStreamWaitEvent(s, h->ev_out, 0));
+    }
+    return HD_OK;
+}
+
+extern "C" int hd_nll_finish(hd_handle* h, hd_topology* topo, const float* xh, const float* context, int mol_shape, const float* raw_x,
+                             const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int K, const float* consts7,
+                             int int_nf, int cont_nf, const double* acc, float* nll, void* stream) {
+    HD_TRY(check_ready(h, topo, "hd_nll_finish"));
+    HD_TRY(nll_ready(h, topo, "hd_nll_finish", raw_x, raw_h, noise_rows, mol_shape, context));
+    if (!xh || !acc || !nll || !consts7) return fail(HD_E_INVALID, "hd_nll_finish: null xh / acc / nll / consts7");
+    if (K < 1 || K > h->T) return fail(HD_E_INVALID, "hd_nll_finish: need 1 <= K <= T");
+    if (int_nf < 0 || cont_nf < 0 || int_nf + cont_nf > h->F)
+        return fail(HD_E_INVALID, "hd_nll_finish: int_nf + cont_nf exceed the feature columns");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(s, h->ev_last, 0));      // zbuf / eps are the replayed term's workspaces too
+    if (!topo->nll_eps) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_eps), (size_t)topo->B * topo->N * h->D * sizeof(float)));
+    HD_TRY(nll_launch_zt(h, topo, xh, nullptr, consts7[0], consts7[1], make_noise(raw_x, raw_h, topo->B, seed, sample_id_base, 0, 0), 0, 0,
+                         nullptr, nullptr, nullptr, s));
+    HD_TRY(forward_impl(h, topo, topo->zbuf, h->d_tau, 1, context, -1, topo->eps, s));
+    ProfScope ps(h, s, 2);
+    NllFinishArgs a;
+    a.net = topo->eps; a.z0 = topo->zbuf; a.xh = xh; a.eps = topo->nll_eps; a.nm = topo->nm_bytes; a.acc = acc; a.nll = nll;
+    a.g0 = consts7[2]; a.gT = consts7[3]; a.scale = (float)h->T / (float)K; a.nv2 = consts7[4]; a.nb2 = consts7[5]; a.log_nv0 = consts7[6];
+    a.B = topo->B; a.N = topo->N; a.D = h->D; a.int_nf = int_nf; a.cont_nf = cont_nf;
+    hipLaunchKernelGGL(k_nll_finish, dim3(topo->B), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
 }
 
 extern "C" int hd_inpaint_decode_fix(hd_handle* h, hd_topology* topo, const uint8_t* fixed_mask, const float* x_known,

@@ -905,6 +905,154 @@ class DiffusionQM9(_Base):
                    "hd_sample_path")
         return z
 
+    # ------------------------------------------------------------------ scoring: every term of the bound (no reference counterpart)
+    def _nll_tables(self, handle, tabs, t_list):
+        """Rows of the terms from the gamma grid of `_schedule`, uploaded to the handle (hd_set_nll_terms) once per (table, list)."""
+        from . import scoring
+        key = tuple(t_list)
+        hit = self.__dict__.get("_nll_cache")
+        if hit is None or hit[0] is not tabs or hit[1] != key:
+            tt = scoring.term_tables(tabs["gamma"], t_list)
+            t_idx = np.ascontiguousarray(tt["t_idx"].numpy(), dtype=np.int32)
+            coef = np.ascontiguousarray(tt["coef"].numpy(), dtype=np.float32)
+            self._nll_cache = None
+            _lib.check(_lib.load().hd_set_nll_terms(handle, tt["K"], t_idx.ctypes.data_as(C.POINTER(C.c_int)),
+                                                    coef.ctypes.data_as(C.POINTER(C.c_float))), "hd_set_nll_terms")
+            self._nll_cache = (tabs, key, tt)
+        return self._nll_cache[2]
+
+    def _nll_setup(self, x, h, node_mask, edge_mask, context, terms, timesteps, seed, sample_id_base, raw_noises, return_terms,
+                   use_graph):
+        """Argument checks of `nll_full` (ValueError / NotImplementedError before anything is queued), then the device-side inputs of
+        hd_nll_terms / hd_nll_finish."""
+        from . import scoring
+        t_list = scoring.resolve_terms(self.T, terms, timesteps)
+        K = len(t_list)
+        if self.pocket:
+            raise ValueError("nll_full: pocket models / mol_shape are not supported (the score covers whole molecules)")
+        if node_mask.dim() != 3 or node_mask.shape[2] != 1:
+            raise ValueError(f"node_mask must be [B, N, 1], got {tuple(node_mask.shape)}")
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        F_ = self.in_node_nf
+        if tuple(x.shape) != (B, N, self.n_dims):
+            raise ValueError(f"x must be [{B}, {N}, {self.n_dims}], got {tuple(x.shape)}")
+        if tuple(h.shape) != (B, N, F_):
+            raise ValueError(f"h must be [{B}, {N}, {F_}], got {tuple(h.shape)}")
+        if edge_mask is not None and edge_mask.numel() != B * N * N:
+            raise ValueError(f"edge_mask must hold {B} x {N} x {N} entries")
+        if self.dynamics.context_node_nf > 0 and context is None:
+            raise ValueError("context required")
+        if raw_noises is not None:
+            if len(raw_noises) != K + 1:
+                raise ValueError(f"raw_noises must hold {K} + 1 (randn_x, randn_h) pairs: one per term in list order, then eps_0")
+            for rx_, rh_ in raw_noises:
+                if tuple(rx_.shape) != (B, N, self.n_dims) or tuple(rh_.shape) != (B, N, F_):
+                    raise ValueError(f"raw_noises pairs must be ([{B}, {N}, {self.n_dims}], [{B}, {N}, {F_}])")
+        if isinstance(sample_id_base, bool) or int(sample_id_base) != sample_id_base or int(sample_id_base) < 0:
+            raise ValueError(f"sample_id_base must be an integer >= 0, got {sample_id_base!r}")
+        if getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics":
+            raise NotImplementedError("nll_full: mode 'gnn_dynamics' is not supported")
+        dev = x.device
+        if dev.type != "cuda":
+            raise _lib.HierDiffHipError("scoring runs only on an MI355X (no CPU fallback)")
+        handle = self._lib_handle()
+        tabs = self._schedule(rows=B)
+        self._nll_tables(handle, tabs, t_list)
+        node_mask = node_mask.to(dev)
+        topo = self.dynamics.topology(node_mask, edge_mask, B, N)
+        ctx = None
+        if self.dynamics.context_node_nf > 0:
+            ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
+        x_n, h_n, _ = self.normalize(x.to(torch.float32), h.to(dev, torch.float32), node_mask.to(torch.float32))
+        xh = torch.cat([x_n, h_n], dim=2).contiguous()
+        rx = rh = None
+        if raw_noises is not None:
+            rx = torch.stack([r[0].to(dev, torch.float32) for r in raw_noises]).contiguous()
+            rh = torch.stack([r[1].to(dev, torch.float32) for r in raw_noises]).contiguous()
+        g = tabs["gamma"].to(torch.float32).reshape(-1)
+        consts = np.array([float(torch.sqrt(torch.sigmoid(-g[0]))), float(torch.sqrt(torch.sigmoid(g[0]))), float(g[0]),
+                           float(g[self.T]), float(self.norm_values[2]), float(self.norm_biases[2] or 0.0),
+                           math.log(float(self.norm_values[0]))], dtype=np.float32)
+        return AttrDict(h=handle, topo=topo, ctx=ctx, xh=xh, rx=rx, rh=rh, B=B, N=N, K=K, t_list=t_list, consts=consts,
+                        seed=int(self.seed if seed is None else seed), base=int(sample_id_base), use_graph=int(bool(use_graph)),
+                        acc=torch.zeros(B, dtype=torch.float64, device=dev),
+                        err=torch.zeros((K, B), dtype=torch.float32, device=dev) if return_terms else None,
+                        stream=_stream(dev), dev=dev)
+
+    def _nll_terms(self, st, k_lo: int, k_hi: int):
+        """Terms k_lo .. k_hi-1 of the list into st.acc (and st.err)."""
+        nd, F_ = self.n_dims, self.in_node_nf
+        per = st.B * st.N
+        _lib.check(_lib.load().hd_nll_terms(
+            st.h, st.topo.ptr, st.xh.data_ptr(), _ptr(st.ctx), -1, int(k_lo), int(k_hi),
+            None if st.rx is None else st.rx.data_ptr() + 4 * per * nd * int(k_lo),
+            None if st.rh is None else st.rh.data_ptr() + 4 * per * F_ * int(k_lo), st.B, st.seed, st.base, st.use_graph,
+            st.acc.data_ptr(), _ptr(st.err), st.stream), "hd_nll_terms")
+
+    def _nll_finish(self, st):
+        int_nf, cont_nf = (5, 3) if self.node_coarse_type == 'prop' else (3, 0)
+        nd, F_ = self.n_dims, self.in_node_nf
+        per = st.B * st.N
+        nll = torch.empty(st.B, dtype=torch.float32, device=st.dev)
+        _lib.check(_lib.load().hd_nll_finish(
+            st.h, st.topo.ptr, st.xh.data_ptr(), _ptr(st.ctx), -1,
+            None if st.rx is None else st.rx.data_ptr() + 4 * per * nd * st.K,
+            None if st.rh is None else st.rh.data_ptr() + 4 * per * F_ * st.K, st.B, st.seed, st.base, st.K,
+            st.consts.ctypes.data_as(C.POINTER(C.c_float)), int_nf, cont_nf, st.acc.data_ptr(), nll.data_ptr(), st.stream),
+            "hd_nll_finish")
+        return nll
+
+    @torch.no_grad()
+    def nll_full(self, x, h, node_mask, edge_mask=None, context=None, *, terms: Optional[int] = None,
+                 timesteps: Optional[Sequence[int]] = None, seed: Optional[int] = None, sample_id_base: int = 0,
+                 raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, return_terms: bool = False,
+                 use_graph: bool = True):
+        """nll [B] of raw data (x, h) in the units of eval-mode `nll`, with EVERY term of the variational bound evaluated instead of
+        one random t:  kl_prior + (T / K) sum_{t in S} L_t + neg_log_constants + L_0 - delta_log_px,  L_t = 0.5 (SNR(g_s - g_t) - 1)
+        |eps_t - eps^_t|^2 - inside the library's loop (hd_nll_terms: one captured term per topology, replayed K times; algorithm and
+        draw layout in include/hierdiff_hip.h).  S = all of 1 .. T (default: exact in t, still one noise draw per term), the K
+        visited steps of a uniform K-step path (`terms=K`, stratified with the factor T / K) or an explicit subset (`timesteps`).
+        Noise: the counter-based generator at (seed or `self.seed`, sample_id_base + row, draw = t; eps_0: draw 0), so a molecule's
+        score depends on its global id, its mask, the weights, the schedule and its data only; `raw_noises` instead injects K + 1
+        (randn_x [B,N,3], randn_h [B,N,F]) pairs - the terms in list order (descending t), then eps_0.  With `return_terms` also
+        (t_idx [K], e_t [K, B]), the `error` of the reference's info dict per term.  Independent of `self.training`; no gradients
+        (training keeps the one-t estimator).  Pocket models raise ValueError.  Scores of untrained weights mean nothing
+        chemically."""
+        st = self._nll_setup(x, h, node_mask, edge_mask, context, terms, timesteps, seed, sample_id_base, raw_noises, return_terms,
+                             use_graph)
+        self._nll_terms(st, 0, st.K)
+        nll = self._nll_finish(st)
+        if return_terms:
+            return nll, (torch.tensor(st.t_list, dtype=torch.int64), st.err)
+        return nll
+
+    @torch.no_grad()
+    def score(self, samples: Sequence[Dict[str, torch.Tensor]], device, batch_size: int = 256, **kw):
+        """`nll_full` for a list in the sampler's result format [{'x': [n,3], 'h': [n,F] (, 'context')}] (what `sample` returns and
+        stage 2 consumes): padded to batches of `batch_size`, x re-centred per molecule, molecule i scored under the sample id
+        sample_id_base + i.  Returns a CPU tensor [len(samples)].  Keywords: terms / timesteps / seed / sample_id_base / use_graph
+        of `nll_full`."""
+        from . import scoring
+        device = torch.device(device)
+        extra = set(kw) - {"terms", "timesteps", "seed", "sample_id_base", "use_graph"}
+        if extra:
+            raise ValueError(f"score: unsupported keyword(s) {sorted(extra)} (terms, timesteps, seed, sample_id_base, use_graph)")
+        base = kw.pop("sample_id_base", 0)
+        scoring.resolve_terms(self.T, kw.get("terms"), kw.get("timesteps"))          # argument errors first
+        if isinstance(batch_size, bool) or int(batch_size) != batch_size or int(batch_size) < 1:
+            raise ValueError(f"batch_size must be an integer >= 1, got {batch_size!r}")
+        samples = list(samples)
+        if not samples:
+            raise ValueError("score: no samples")
+        with_ctx = self.dynamics.context_node_nf > 0
+        batches = [scoring.pad_samples(samples[lo:lo + int(batch_size)], self.n_dims, self.in_node_nf, with_ctx)
+                   for lo in range(0, len(samples), int(batch_size))]
+        out = []
+        for i, (x, h, nm, ctx) in enumerate(batches):
+            out.append(self.nll_full(x.to(device), h.to(device), nm.to(device), None, None if ctx is None else ctx.to(device),
+                                     sample_id_base=base + i * int(batch_size), **kw).cpu())
+        return torch.cat(out)
+
     # ------------------------------------------------------------------ fragment-constrained sampling (no reference counterpart)
     def _inpaint_schedule(self, handle, tabs):
         """{alpha_s, sigma_s, alpha_t|s, sigma_t|s} per step from the gamma grid of `_schedule`, uploaded once per table."""

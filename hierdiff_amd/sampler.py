@@ -132,7 +132,7 @@ def parse_args(argv=None):
     ap.add_argument("--checkpoint", default=None, help="reference Lightning checkpoint (.ckpt); random init if omitted")
     ap.add_argument("--batch-size", type=int, default=2)        # conf/sample/default.yaml:1
     ap.add_argument("--num-batches", type=int, default=16)      # conf/sample/default.yaml:2
-    ap.add_argument("--out", default="sample_results.pkl")
+    ap.add_argument("--out", default=None, help="output pickle (default: sample_results.pkl; with --score: scores.pkl)")
     ap.add_argument("--hidden-nf", type=int, default=256)
     ap.add_argument("--n-layers", type=int, default=6)
     ap.add_argument("--timesteps", type=int, default=1000)
@@ -159,7 +159,21 @@ def parse_args(argv=None):
     ap.add_argument("--eta", type=float, default=1.0,
                     help="1: ancestral steps (default); 0 <= eta < 1: DDIM-family update, 0 = noise-free (not with --known)")
     ap.add_argument("--spacing", choices=["uniform", "quadratic"], default="uniform", help="how --steps spreads over the grid")
+    ap.add_argument("--score", default=None, metavar="FILE",
+                    help="score the molecules of FILE (a sample_results.pkl or a bare list in the sampler's output format) instead of "
+                         "sampling: the variational bound with every timestep evaluated, one value per molecule, written to --out.  "
+                         "Mechanism only: scores of untrained weights mean nothing chemically")
+    ap.add_argument("--terms", type=int, default=None,
+                    help="with --score: evaluate K <= timesteps uniformly spaced terms of the bound (default: all of them)")
     args = ap.parse_args(argv)
+    if args.score is not None and (args.known is not None or args.grow is not None or args.steps is not None):
+        ap.error("--score does not combine with --known / --grow / --steps (it samples nothing)")
+    if args.terms is not None and args.score is None:
+        ap.error("--terms needs --score")
+    if args.terms is not None and args.terms < 1:
+        ap.error("--terms must be >= 1")
+    if args.out is None:
+        args.out = "scores.pkl" if args.score is not None else "sample_results.pkl"
     if args.steps is not None and args.steps < 1:
         ap.error("--steps must be >= 1")
     if not (0.0 <= args.eta <= 1.0):
@@ -206,6 +220,16 @@ def main(argv=None) -> int:
     model.sample_steps, model.sample_eta, model.sample_spacing = args.steps, args.eta, args.spacing
     if world > 1:
         broadcast_model_weights(model, src=0)
+
+    if args.score is not None:
+        if world > 1:
+            raise SystemExit("--score runs in a single process")
+        if args.terms is not None and args.terms > model.T:
+            raise SystemExit(f"--terms {args.terms} exceeds the model's {model.T} timesteps")
+        scores = model.score(read_known(args.score), dev, batch_size=max(1, args.batch_size), terms=args.terms)
+        with open(args.out, "wb") as f:
+            pickle.dump(scores, f)
+        return 0
 
     if args.known is not None:
         if world > 1:

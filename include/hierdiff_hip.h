@@ -30,6 +30,7 @@
  *   hd_noise                     <- sample_combined_position_feature_noise (:445-456)
  *   hd_sample_loop               <- the timestep loop of DiffusionQM9.sample (:375-384)
  *   hd_sample_loop_inpaint       <- no counterpart: the same loop with known fragments kept in place
+ *   hd_nll_terms / hd_nll_finish <- the one-timestep estimator of compute_loss / nll in eval mode (:530-699), every listed t
  */
 #ifndef HIERDIFF_HIP_H
 #define HIERDIFF_HIP_H
@@ -184,7 +185,11 @@ int hd_final_decode(hd_handle* h, hd_topology* topo, const float* z0, const floa
  *   path loops            (hd_sample_path, hd_sample_path_inpaint) the counter is the FINE-GRID index of the arrival step: the
  *                         transition t -> s of a path draws at T - s (inpainting: (T + 2) * (3 j + k) + (T - s)), draw 0 = z_T and
  *                         draw T + 1 = the final decode as above - the layouts above restricted to the visited s.  The identity path
- *                         T, T-1, .., 0 therefore reproduces the plain loops bit for bit. */
+ *                         T, T-1, .., 0 therefore reproduces the plain loops bit for bit.
+ *   scoring               (hd_nll_terms, hd_nll_finish) a stream of its own, used with the DATA of a sample instead of its chain: the
+ *                         noise eps_t of the bound's term t = 1 .. T is draw = t, the noise eps_0 of the t = 0 likelihood is draw 0.
+ *                         The counter is the term's grid index, never its position in the term list, so a molecule's score does not
+ *                         depend on the order of the terms or on how their range was split into calls. */
 int hd_noise(hd_handle* h, hd_topology* topo, const float* raw_x, const float* raw_h, int noise_rows,
              uint64_t seed, uint64_t sample_id_base, uint32_t draw, int share_rows, float* z, void* stream);
 
@@ -230,6 +235,43 @@ int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z, const floa
                            int use_graph, const uint8_t* fixed_mask, const float* xh_known, int resamplings, void* stream);
 /* Number of times the topology's captured path transition was instantiated (-1: null topology): a cached replay leaves it unchanged. */
 long long hd_path_graph_builds(const hd_topology* topo);
+
+/* ---- Scoring (ABI 12, additive; no reference counterpart beyond the one-timestep estimator, compute_loss with t0_always = True,
+ * diffusion_qm9.py:530-699): the variational bound of GIVEN molecules with every term of a list evaluated, in the device loop.
+ * For normalised data xh [B,N,D] and a term t in 1 .. T (s = t - 1):
+ *     eps_t = combined noise (masked, x part mean-free over the valid nodes; draw layout at hd_noise),
+ *     z_t = alpha_t xh + sigma_t eps_t,   eps^_t = hd_egnn_forward(z_t, tau[t]),   e_t = sum_{nodes, columns} (eps_t - eps^_t)^2,
+ *     acc[b] += w_t e_t,   w_t = 0.5 expm1(gamma_t - gamma_s)   (= 0.5 (SNR(gamma_s - gamma_t) - 1), the reference's weight)
+ * and nll = kl_prior + (T / K) fp32(acc) + neg_log_constants + L_0 - delta_log_px, L_0 = -log p(x, h | z_0) with its own draw eps_0 -
+ * the reference's estimator with its random t replaced by the K listed ones (K = T: the full bound, exact in t, one eps per term).
+ * acc is a DOUBLE per molecule in device memory: one thread adds the terms in list order, node sums run in a fixed order, no atomics; a
+ * molecule's score depends on its global id, its mask, the weights, the schedule and its data - not on the batch, the order of the
+ * terms or how their range was split into calls.
+ *
+ * hd_set_nll_terms uploads the list next to the plain schedule, which must be set (it supplies T and tau) and whose replacement needs
+ * a new upload here (HD_E_STATE otherwise).  Host arrays: t_idx [K] grid indices in 1 .. T, coef4 K rows {alpha_t, sigma_t, w_t, 0}. */
+int hd_set_nll_terms(hd_handle* h, int K, const int* t_idx, const float* coef4);
+/* Terms k = k_lo ... k_hi-1 of the list: acc[B] (device doubles, zeroed by the caller before the first term) += w_t e_t.
+ *   xh           device [B,N,D] normalised data; context as in hd_egnn_forward (passed through unchanged)
+ *   raw_x/raw_h  device [(k_hi-k_lo), B, N, 3|F] normals per term, indexed by list position (first = k_lo), or NULL = the generator
+ *   err_terms    NULL, or device [K][B]: row k receives e_t of term k (rows outside k_lo .. k_hi-1 are untouched)
+ *   use_graph    ONE captured term per topology, whatever K, replayed k_hi - k_lo times: the position lives in device memory and the
+ *                captured kernels read time, row and draw through the uploaded tables.  Cached with the topology and rebuilt when the
+ *                terms, seed, weights, schedule or noise arguments change (hd_nll_graph_builds counts the instantiations; -1: null
+ *                topology); use_graph = 0 gives the same bits.  Stream-ordered, no host synchronisation in steady state.
+ * Restrictions (HD_E_INVALID): noise_rows = B, mol_shape < 0 or = N (no pocket rows), N * D floats within one workgroup's LDS. */
+int hd_nll_terms(hd_handle* h, hd_topology* topo, const float* xh, const float* context, int mol_shape, int k_lo, int k_hi,
+                 const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
+                 double* acc, float* err_terms, void* stream);
+long long hd_nll_graph_builds(const hd_topology* topo);
+/* nll[B] from acc: draws eps_0 (raw_x/raw_h device [B,N,3|F], or NULL = the generator at draw 0), z_0 = alpha_0 xh + sigma_0 eps_0, the
+ * network at tau[0], then one kernel for kl_prior, the constants, L_0 and the sum.  K = number of terms acc holds (T / K scales them).
+ *   consts7      host {alpha_0, sigma_0, gamma_0, gamma_T, norm_values[2], norm_biases[2], log(norm_values[0])}
+ *   int_nf / cont_nf  integer / continuous feature columns of the t = 0 likelihood, as in hd_vlb_loss_forward (5 / 3 or 3 / 0).
+ * Restrictions of hd_nll_terms. */
+int hd_nll_finish(hd_handle* h, hd_topology* topo, const float* xh, const float* context, int mol_shape, const float* raw_x,
+                  const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int K, const float* consts7, int int_nf,
+                  int cont_nf, const double* acc, float* nll, void* stream);
 
 /* ---- Fragment-constrained sampling ("inpainting"; ABI 12, additive; no reference counterpart): sample the free nodes of a
  * molecule around fragments whose positions and features are known, by the replacement method of score-based models, optionally with
