@@ -107,6 +107,7 @@ struct hd_handle {
     int *d_path_t, *d_path_s;
     float *d_path_coef, *d_path_coef_ip;         // [K][4] each; d_path_coef_ip null when no inpainting rows were given
     unsigned long long path_sched_gen, path_gen; // sched_gen the path was set for (0: not set); bumped by every hd_set_path
+    bool path_up;               // the path ascends (hd_set_path_up: t_idx[k] < s_idx[k], linear rows with c == 0)
     // scoring (hd_set_nll_terms / hd_nll_terms / hd_nll_finish): K terms t_idx[k] of the bound, rows {alpha_t, sigma_t, w_t, 0}
     int nll_K;
     std::vector<int> nll_t_h;
@@ -335,7 +336,7 @@ extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
     h->weights_gen = h->sched_gen = 0;
     h->d_coef_ip = nullptr; h->ip_sched_gen = 0; h->ip_gen = 0; h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
     h->path_K = 0; h->path_form = 0; h->d_path_t = h->d_path_s = nullptr; h->d_path_coef = h->d_path_coef_ip = nullptr;
-    h->path_sched_gen = 0; h->path_gen = 0;
+    h->path_sched_gen = 0; h->path_gen = 0; h->path_up = false;
     h->nll_K = 0; h->d_nll_t = nullptr; h->d_nll_coef = nullptr; h->nll_sched_gen = 0; h->nll_gen = 0;
     h->d_nanflag = nullptr; h->d_nan_events = nullptr; h->d_step = nullptr; h->d_draw = nullptr; h->d_tcur = nullptr;
     h->d_base = nullptr;
@@ -2948,7 +2949,37 @@ extern "C" int hd_set_path(hd_handle* h, int K, const int* t_idx, const int* s_i
     HD_TRY(dev_upload(&h->d_path_s, h->path_s_h));
     HD_TRY(dev_upload(&h->d_path_coef, std::vector<float>(coef4, coef4 + (size_t)4 * K)));
     if (coef4_inpaint) HD_TRY(dev_upload(&h->d_path_coef_ip, std::vector<float>(coef4_inpaint, coef4_inpaint + (size_t)4 * K)));
-    h->path_K = K; h->path_form = form;
+    h->path_K = K; h->path_form = form; h->path_up = false;
+    h->path_sched_gen = h->sched_gen;
+    h->path_gen++;                             // captured graphs hold the old table addresses
+    return HD_OK;
+}
+
+// An ascending path into the same tables: transition k leaves from_idx[k] (path_t: network time, as for descending paths) and
+// arrives at to_idx[k] (path_s).  Linear rows with c == 0, so k_post_step<1> never looks at the draw word T - to_idx[k].
+extern "C" int hd_set_path_up(hd_handle* h, int K, const int* from_idx, const int* to_idx, const float* coef4) {
+    if (!from_idx || !to_idx || !coef4 || K < 1) return fail(HD_E_INVALID, "hd_set_path_up: bad argument");
+    for (int k = 0; k < K; ++k) {
+        if (coef4[(size_t)4 * k + 2] != 0.f || coef4[(size_t)4 * k + 3] != 0.f)
+            return fail(HD_E_INVALID, "hd_set_path_up: rows must be {a, b, 0, 0} (the inversion draws nothing)");
+        if (from_idx[k] < 0 || from_idx[k] >= to_idx[k]) return fail(HD_E_INVALID, "hd_set_path_up: need 0 <= from_idx[k] < to_idx[k] <= T");
+        if (k > 0 && from_idx[k] != to_idx[k - 1]) return fail(HD_E_INVALID, "hd_set_path_up: transition k must start where k - 1 arrived");
+    }
+    if (!h) return fail(HD_E_INVALID, "hd_set_path_up: null handle");
+    if (h->T < 1) return fail(HD_E_STATE, "hd_set_path_up: schedule not set (hd_set_schedule)");
+    if (K > h->T) return fail(HD_E_INVALID, "hd_set_path_up: more transitions than the schedule has steps");
+    if (to_idx[K - 1] > h->T) return fail(HD_E_INVALID, "hd_set_path_up: need 0 <= from_idx[k] < to_idx[k] <= T");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
+    hipFree(h->d_path_t); hipFree(h->d_path_s); hipFree(h->d_path_coef); hipFree(h->d_path_coef_ip);
+    h->d_path_t = h->d_path_s = nullptr; h->d_path_coef = h->d_path_coef_ip = nullptr;
+    h->path_sched_gen = 0; h->path_K = 0;
+    h->path_t_h.assign(from_idx, from_idx + K);
+    h->path_s_h.assign(to_idx, to_idx + K);
+    HD_TRY(dev_upload(&h->d_path_t, h->path_t_h));
+    HD_TRY(dev_upload(&h->d_path_s, h->path_s_h));
+    HD_TRY(dev_upload(&h->d_path_coef, std::vector<float>(coef4, coef4 + (size_t)4 * K)));
+    h->path_K = K; h->path_form = 1; h->path_up = true;
     h->path_sched_gen = h->sched_gen;
     h->path_gen++;                             // captured graphs hold the old table addresses
     return HD_OK;
@@ -3112,6 +3143,7 @@ extern "C" int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z,
     if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_sample_path_inpaint: need 0 <= k_lo <= k_hi <= K");
     HD_TRY(check_ready(h, topo, "hd_sample_path_inpaint"));
     HD_TRY(path_ready(h, "hd_sample_path_inpaint", k_lo, k_hi));
+    if (h->path_up) return fail(HD_E_INVALID, "hd_sample_path_inpaint: the path ascends (hd_set_path_up): inversion fixes no fragments");
     if (h->path_form != 0) return fail(HD_E_INVALID, "hd_sample_path_inpaint: ancestral rows only (the path was set with form = 1)");
     if (!h->d_path_coef_ip) return fail(HD_E_STATE, "hd_sample_path_inpaint: the path was set without inpainting rows (hd_set_path)");
     if (!z || !fixed_mask || !xh_known) return fail(HD_E_INVALID, "hd_sample_path_inpaint: null z / fixed_mask / xh_known");
@@ -3127,6 +3159,53 @@ extern "C" int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z,
     HIP_TRY(hipSetDevice(h->device));
     return path_loop(h, topo, z, context, -1, k_lo, k_hi, nullptr, nullptr, noise_rows, seed, sample_id_base, use_graph,
                      fixed_mask, xh_known, resamplings, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------- editing given molecules: start state, slerp
+
+extern "C" int hd_diffuse(hd_handle* h, hd_topology* topo, const float* xh, float alpha, float sigma, const float* raw_x,
+                          const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, uint32_t draw, int share_rows,
+                          float* z, void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_diffuse: null handle/topology");
+    if (!xh || !z) return fail(HD_E_INVALID, "hd_diffuse: null tensor");
+    if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, "hd_diffuse: raw_x and raw_h go together");
+    if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_diffuse: noise_rows must be 1 or B");
+    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_diffuse: N * D floats exceed one workgroup's LDS");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    ProfScope ps(h, s, 2);
+    DiffuseArgs a;
+    a.xh = xh; a.nm = topo->nm_bytes; a.z = z;
+    a.noise = make_noise(raw_x, raw_h, noise_rows, seed, sample_id_base, draw, share_rows);
+    a.draw_ptr = nullptr; a.base_ptr = nullptr; a.alpha = alpha; a.sigma = sigma;
+    a.B = topo->B; a.N = topo->N; a.D = h->D; a.F = h->F;
+    hipLaunchKernelGGL(k_diffuse, dim3(topo->B), dim3(256), (size_t)topo->N * h->D * sizeof(float), s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_slerp(hd_handle* h, hd_topology* topo, const float* za, const float* zb, const float* lam_host, int L, float* out,
+                        void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_slerp: null handle/topology");
+    if (!za || !zb || !lam_host || !out) return fail(HD_E_INVALID, "hd_slerp: null tensor");
+    if (L < 1) return fail(HD_E_INVALID, "hd_slerp: L must be >= 1");
+    const size_t per = (size_t)topo->B * topo->N * h->D;
+    for (const float* in : {za, zb})
+        if (out < in + per && in < out + per * (size_t)L) return fail(HD_E_INVALID, "hd_slerp: out may not alias za or zb");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    ProfScope ps(h, s, 2);
+    SlerpArgs a;
+    a.za = za; a.zb = zb; a.nm = topo->nm_bytes; a.out = out; a.B = topo->B; a.N = topo->N; a.D = h->D;
+    for (int l0 = 0; l0 < L; l0 += SLERP_CHUNK) {      // the weights ride in the kernel arguments: no host buffer outlives the call
+        a.l0 = l0; a.n = std::min(SLERP_CHUNK, L - l0);
+        for (int i = 0; i < SLERP_CHUNK; ++i) a.lam[i] = i < a.n ? lam_host[l0 + i] : 0.f;
+        hipLaunchKernelGGL(k_slerp, dim3(topo->B, a.n), dim3(256), 0, s, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return HD_OK;
 }
 
 // ----------------------------------------------------------------------------- scoring: every term of the variational bound

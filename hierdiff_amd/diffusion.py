@@ -1053,6 +1053,322 @@ class DiffusionQM9(_Base):
                                      sample_id_base=base + i * int(batch_size), **kw).cpu())
         return torch.cat(out)
 
+    # ------------------------------------------------------------------ editing given molecules (no reference counterpart)
+    def _up_tables(self, handle, tabs, path):
+        """Rows of the ascending `path` from the gamma grid of `_schedule`, uploaded to the handle (hd_set_path_up).  The tables are
+        the ones hd_set_path fills, so the two directions share `_path_cache`: whichever was set last is the one that is cached."""
+        from . import paths
+        key = (tuple(path), "up")
+        hit = self.__dict__.get("_path_cache")
+        if hit is None or hit[0] is not tabs or hit[1] != key:
+            ut = paths.up_tables(tabs["gamma"], path)
+            u = np.ascontiguousarray(ut["from_idx"].numpy(), dtype=np.int32)
+            v = np.ascontiguousarray(ut["to_idx"].numpy(), dtype=np.int32)
+            coef = np.ascontiguousarray(ut["coef"].numpy(), dtype=np.float32)
+            self._path_cache = None
+            _lib.check(_lib.load().hd_set_path_up(
+                handle, ut["K"], u.ctypes.data_as(C.POINTER(C.c_int)), v.ctypes.data_as(C.POINTER(C.c_int)),
+                coef.ctypes.data_as(C.POINTER(C.c_float))), "hd_set_path_up")
+            self._path_cache = (tabs, key, ut)
+        return self._path_cache[2]
+
+    def _grid_index(self, t, lo: int, what: str) -> int:
+        if isinstance(t, torch.Tensor) and t.numel() == 1 and not t.is_floating_point():
+            t = int(t)
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not (lo <= int(t) <= self.T):
+            raise ValueError(f"{what} must be a grid index in {lo} .. {self.T}, got {t!r}")
+        return int(t)
+
+    def _edit_check(self, what: str, node_mask, z_shapes=(), context=None, sample_id_base=0, needs_noise: bool = False,
+                    needs_context: bool = True):
+        """Argument and configuration errors of the editing entry points, all raised before the GPU is touched."""
+        if self.pocket:
+            raise ValueError(f"{what}: pocket models are not supported (whole molecules only)")
+        if not isinstance(node_mask, torch.Tensor) or node_mask.dim() != 3 or node_mask.shape[2] != 1:
+            raise ValueError(f"node_mask must be [B, N, 1], got {tuple(getattr(node_mask, 'shape', ()))}")
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        for name, t, width in z_shapes:
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (B, N, width):
+                raise ValueError(f"{name} must be [{B}, {N}, {width}], got {tuple(getattr(t, 'shape', ()))}")
+        if needs_context and self.dynamics.context_node_nf > 0 and context is None:
+            raise ValueError("context required")
+        if isinstance(sample_id_base, bool) or int(sample_id_base) != sample_id_base or int(sample_id_base) < 0:
+            raise ValueError(f"sample_id_base must be an integer >= 0, got {sample_id_base!r}")
+        if getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics":
+            raise NotImplementedError(f"{what}: mode 'gnn_dynamics' is not supported (the library's loop evaluates the egnn network)")
+        if needs_noise and self.noise_mode == "torch":
+            raise NotImplementedError(f"{what}: noise_mode 'torch' is not supported (counter-based or injected noise only)")
+        return B, N
+
+    def _edit_device(self, node_mask, edge_mask, context, B, N):
+        """Handle, schedule, topology and context rows on node_mask's device (the first lines that need a GPU)."""
+        dev = node_mask.device
+        if dev.type != "cuda":
+            raise _lib.HierDiffHipError("editing runs only on an MI355X (no CPU fallback)")
+        handle = self._lib_handle()
+        tabs = self._schedule(rows=B)
+        topo = self.dynamics.topology(node_mask, edge_mask, B, N)
+        ctx = None
+        if self.dynamics.context_node_nf > 0 and context is not None:        # (`diffuse` and `slerp` call no network: no context)
+            ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
+        return AttrDict(h=handle, tabs=tabs, topo=topo, ctx=ctx, dev=dev, stream=_stream(dev))
+
+    def _alpha_sigma(self, tabs, t: int):
+        """(alpha_t, sigma_t) as the loss and `scoring.term_tables` compute them: fp32 sqrt(sigmoid(-+gamma_t)) of the fp32 grid."""
+        g = tabs["gamma"].to(torch.float32).reshape(-1)[t]
+        return float(torch.sqrt(torch.sigmoid(-g))), float(torch.sqrt(torch.sigmoid(g)))
+
+    def _diffuse_xh(self, st, x, h, node_mask, alpha, sigma, raw, nb, seed, base, share):
+        """z = alpha xh + sigma eps through hd_diffuse: x re-centred per molecule, (x, h) normalised."""
+        nmf = node_mask.to(st.dev, torch.float32)
+        x = x.to(st.dev, torch.float32) * nmf
+        x = x - (x.sum(1, keepdim=True) / nmf.sum(1, keepdim=True).clamp(min=1.0)) * nmf
+        x_n, h_n, _ = self.normalize(x, h.to(st.dev, torch.float32), nmf)
+        xh = torch.cat([x_n, h_n], dim=2).contiguous()
+        z = torch.empty_like(xh)
+        rx = rh = None
+        if raw is not None:
+            rx, rh = (r.to(st.dev, torch.float32).contiguous() for r in raw)
+        _lib.check(_lib.load().hd_diffuse(st.h, st.topo.ptr, xh.data_ptr(), alpha, sigma, _ptr(rx), _ptr(rh), nb, seed, base, 0,
+                                          share, z.data_ptr(), st.stream), "hd_diffuse")
+        return z
+
+    @torch.no_grad()
+    def diffuse(self, x, h, node_mask, t, *, edge_mask=None, seed: Optional[int] = None, sample_id_base: int = 0,
+                raw_noise: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, fix_noise: bool = False):
+        """z_t [B,N,D] = alpha_t xh + sigma_t eps in normalised units for raw data (x [B,N,3], h [B,N,F]) at the grid index `t` in
+        0 .. T: the start state of `sample_from_latent(t_start=t)` (variations of given molecules; hd_diffuse).  x is re-centred per
+        molecule, as `score` does.  eps is the combined noise (masked, x part mean-free): the counter-based generator at (seed or
+        `self.seed`, sample_id_base + row, draw 0) - the slot plain sampling uses for z_T, layout in include/hierdiff_hip.h - or the
+        injected `raw_noise` = (randn_x [b,N,3], randn_h [b,N,F]), b = 1 with `fix_noise` (one row shared by the batch), else B."""
+        F_ = self.in_node_nf
+        t = self._grid_index(t, 0, "t")
+        B, N = self._edit_check("diffuse", node_mask, (("x", x, self.n_dims), ("h", h, F_)), sample_id_base=sample_id_base,
+                                needs_noise=raw_noise is None, needs_context=False)
+        nb = 1 if fix_noise else B
+        if raw_noise is not None and (tuple(raw_noise[0].shape) != (nb, N, self.n_dims) or tuple(raw_noise[1].shape) != (nb, N, F_)):
+            raise ValueError(f"raw_noise must be ([{nb}, {N}, {self.n_dims}], [{nb}, {N}, {F_}])")
+        st = self._edit_device(node_mask, edge_mask, None, B, N)
+        alpha, sigma = self._alpha_sigma(st.tabs, t)
+        return self._diffuse_xh(st, x, h, node_mask, alpha, sigma, raw_noise, nb, int(self.seed if seed is None else seed),
+                                int(sample_id_base), int(fix_noise))
+
+    @torch.no_grad()
+    def encode(self, x, h, node_mask, edge_mask=None, context=None, *, t_end: Optional[int] = None, steps: Optional[int] = None,
+               spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None):
+        """The latent z_{t_end} [B,N,D] (default t_end = T) of raw data (x, h): z_0 = alpha_0 xh without noise, then the deterministic
+        eta = 0 update of the DDIM family run UPWARDS in t ("DDIM inversion") on `paths.ascending_path(T, t_end, steps, spacing,
+        timesteps)` - default every grid point - inside the library's loop (hd_set_path_up / hd_sample_path: one captured transition
+        per topology).  Nothing is drawn: the result depends on the data, the masks, the weights and the path only.  Decoding with
+        `sample_from_latent(eta=0)` on the same points comes back near the molecule; how near is a property of the weights and K."""
+        from . import paths
+        t_end = self._grid_index(self.T if t_end is None else t_end, 1, "t_end")
+        spacing = self.sample_spacing if spacing is None else spacing
+        path = paths.ascending_path(self.T, t_end, steps, spacing, timesteps)
+        B, N = self._edit_check("encode", node_mask, (("x", x, self.n_dims), ("h", h, self.in_node_nf)), context)
+        st = self._edit_device(node_mask, edge_mask, context, B, N)
+        alpha0, _ = self._alpha_sigma(st.tabs, 0)
+        z = self._diffuse_xh(st, x, h, node_mask, alpha0, 0.0, None, B, 0, 0, 0)
+        K = self._up_tables(st.h, st.tabs, path)["K"]
+        _lib.check(_lib.load().hd_sample_path(st.h, st.topo.ptr, z.data_ptr(), _ptr(st.ctx), -1, 0, K, None, None, B, 0, 0,
+                                              int(self.use_graph), st.stream), "hd_sample_path")
+        return z
+
+    def _latent_path(self, t_start, steps, eta, spacing, timesteps):
+        """(t_start, partial path, eta) of the keywords; pure host arithmetic."""
+        from . import paths
+        t_start = self._grid_index(self.T if t_start is None else t_start, 1, "t_start")
+        eta = paths.check_eta(self.sample_eta if eta is None else eta)
+        spacing = self.sample_spacing if spacing is None else spacing
+        return t_start, paths.partial_path(self.T, t_start, steps, spacing, timesteps), eta
+
+    @torch.no_grad()
+    def latent_steps(self, z, node_mask, edge_mask=None, context=None, *, t_start: Optional[int] = None, steps: Optional[int] = None,
+                     eta: Optional[float] = None, spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None,
+                     k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False,
+                     raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None):
+        """Transitions k_lo .. k_hi-1 of `sample_from_latent`'s partial chain on a given z [B,N,D] (the state at path position k_lo);
+        returns the state at position k_hi (default: the end, z_0 before the decode), as `path_steps` does for a full path.  Draws are
+        keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.  `raw_noises`: k_hi - k_lo injected
+        (randn_x, randn_h) pairs, one per transition run."""
+        t_start, path, eta = self._latent_path(t_start, steps, eta, spacing, timesteps)
+        K = len(path) - 1
+        k_lo, k_hi = int(k_lo), K if k_hi is None else int(k_hi)
+        if not (0 <= k_lo <= k_hi <= K):
+            raise ValueError(f"need 0 <= k_lo <= k_hi <= {K} (the path's transitions)")
+        B, N = self._edit_check("sample_from_latent", node_mask, (("z", z, self.n_dims + self.in_node_nf),), context, sample_id_base,
+                                needs_noise=raw_noises is None)
+        nb = 1 if fix_noise else B
+        if raw_noises is not None:
+            if len(raw_noises) != k_hi - k_lo:
+                raise ValueError(f"raw_noises must hold one (randn_x, randn_h) pair per transition ({k_hi - k_lo})")
+            for rx_, rh_ in raw_noises:
+                if tuple(rx_.shape) != (nb, N, self.n_dims) or tuple(rh_.shape) != (nb, N, self.in_node_nf):
+                    raise ValueError(f"raw_noises pairs must be ([{nb}, {N}, {self.n_dims}], [{nb}, {N}, {self.in_node_nf}])")
+        st = self._edit_device(node_mask, edge_mask, context, B, N)
+        self._path_tables(st.h, st.tabs, path, eta)
+        z = z.detach().to(st.dev, torch.float32).clone().contiguous()
+        rx = rh = None
+        seed, base = self.seed, int(sample_id_base)
+        if raw_noises is not None and k_hi > k_lo:
+            rx = torch.stack([r[0].to(st.dev, torch.float32) for r in raw_noises]).contiguous()
+            rh = torch.stack([r[1].to(st.dev, torch.float32) for r in raw_noises]).contiguous()
+            seed, base = 0, 0
+        _lib.check(_lib.load().hd_sample_path(st.h, st.topo.ptr, z.data_ptr(), _ptr(st.ctx), -1, k_lo, k_hi, _ptr(rx), _ptr(rh), nb,
+                                              seed, base, int(self.use_graph), st.stream), "hd_sample_path")
+        return z
+
+    @torch.no_grad()
+    def sample_from_latent(self, z, node_mask, edge_mask=None, context=None, *, t_start: Optional[int] = None,
+                           steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
+                           timesteps: Optional[Sequence[int]] = None, sample_id_base: int = 0, fix_noise: bool = False,
+                           raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None):
+        """(x, h) from a state z [B,N,D] at the grid index `t_start` (default T; normalised units - what `diffuse` and `encode`
+        return): the partial reverse chain on `paths.partial_path(T, t_start, steps, spacing, timesteps)` (default: every grid point
+        below t_start) inside the library's loop (hd_sample_path), then the final decode of `sample_from_masks`.  `eta` defaults to
+        the model's `sample_eta`: 1 ancestral, 0 <= eta < 1 the DDIM family, 0 noise-free on the path.  Draws: T - s of the visited
+        steps and T + 1 for the decode at (self.seed, sample_id_base + row) - plain sampling's layout, so t_start = T on the identity
+        path is `sample_from_masks(z_init=z)` bit for bit; `raw_noises` instead injects K + 1 pairs (the K transitions, the decode).
+        `t_start` sets how far variations drift from the lead; which t_start, K and eta are chemically useful is for the user to
+        validate on a trained checkpoint."""
+        _, path, _ = self._latent_path(t_start, steps, eta, spacing, timesteps)
+        K = len(path) - 1
+        if raw_noises is not None and len(raw_noises) != K + 1:
+            raise ValueError(f"raw_noises must hold {K} + 1 (randn_x, randn_h) pairs: the transitions, then the decode")
+        z0 = self.latent_steps(z, node_mask, edge_mask, context, t_start=t_start, steps=steps, eta=eta, spacing=spacing,
+                               timesteps=timesteps, sample_id_base=sample_id_base, fix_noise=fix_noise,
+                               raw_noises=None if raw_noises is None else raw_noises[:K])
+        B, N = z0.shape[0], z0.shape[1]
+        dev = z0.device
+        node_mask = node_mask.to(dev)
+        topo = self.dynamics.topology(node_mask, edge_mask, B, N)
+        ctx = None
+        if self.dynamics.context_node_nf > 0:
+            ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
+        self._check_mean_zero(z0[:, :, :self.n_dims], node_mask)
+        eps = self.dynamics.forward_with_topology(topo, torch.zeros((B, 1), device=dev), z0, ctx, None)
+        coef3 = self._schedule(rows=B)["decode"].numpy()
+        if raw_noises is not None:
+            return self._final_decode(z0, eps, node_mask, edge_mask, coef3, fix_noise, raw_noises[K])
+        return self._final_decode(z0, eps, node_mask, edge_mask, coef3, fix_noise, None, philox=(int(sample_id_base), self.T + 1))
+
+    @torch.no_grad()
+    def slerp(self, z_a, z_b, lambdas, node_mask):
+        """[L,B,N,D]: spherical interpolation of two latents [B,N,D] per molecule at the weights `lambdas` (L floats; 0 returns z_a
+        and 1 returns z_b bit for bit), in one library call (hd_slerp: angle and weights in double over the valid entries, the linear
+        form where the latents are parallel; masked entries exactly 0, nothing re-centred)."""
+        try:
+            lam = [float(v) for v in (lambdas.reshape(-1).tolist() if isinstance(lambdas, (torch.Tensor, np.ndarray)) else lambdas)]
+        except (TypeError, ValueError):
+            raise ValueError(f"lambdas must be a sequence of numbers, got {lambdas!r}") from None
+        if not lam or not all(math.isfinite(v) for v in lam):
+            raise ValueError("lambdas must hold at least one finite weight")
+        D = self.n_dims + self.in_node_nf
+        if self.pocket:
+            raise ValueError("slerp: pocket models are not supported (whole molecules only)")
+        if not isinstance(node_mask, torch.Tensor) or node_mask.dim() != 3 or node_mask.shape[2] != 1:
+            raise ValueError(f"node_mask must be [B, N, 1], got {tuple(getattr(node_mask, 'shape', ()))}")
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        for name, t in (("z_a", z_a), ("z_b", z_b)):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (B, N, D):
+                raise ValueError(f"{name} must be [{B}, {N}, {D}], got {tuple(getattr(t, 'shape', ()))}")
+        dev = node_mask.device
+        if dev.type != "cuda":
+            raise _lib.HierDiffHipError("editing runs only on an MI355X (no CPU fallback)")
+        handle = self._lib_handle()
+        topo = self.dynamics.topology(node_mask, None, B, N)
+        za, zb = (t.detach().to(dev, torch.float32).contiguous() for t in (z_a, z_b))
+        out = torch.empty((len(lam), B, N, D), device=dev, dtype=torch.float32)
+        lam_c = (C.c_float * len(lam))(*lam)
+        _lib.check(_lib.load().hd_slerp(handle, topo.ptr, za.data_ptr(), zb.data_ptr(), lam_c, len(lam), out.data_ptr(), _stream(dev)),
+                   "hd_slerp")
+        return out
+
+    @torch.no_grad()
+    def vary(self, samples: Sequence[Dict[str, torch.Tensor]], device, t_start, n_variants: int = 1, batch_size: int = 256,
+             sample_id_base: int = 0, **few):
+        """Variations of given molecules (the SDEdit idea): every molecule of `samples` (the sampler's result format, as `score`
+        takes it) is noised to the grid index `t_start` (`diffuse`) and the reverse chain runs from there (`sample_from_latent`;
+        keywords steps / eta / spacing / timesteps).  Returns `n_variants` results per input in the same format, input-major; variant
+        v of input i runs under the sample id sample_id_base + i * n_variants + v, so it does not depend on the batch it ran in.
+        Mechanism only: how far which t_start drifts, and whether the analogues are chemically useful, is for the user to validate."""
+        from . import scoring
+        device = torch.device(device)
+        extra = set(few) - {"steps", "eta", "spacing", "timesteps"}
+        if extra:
+            raise ValueError(f"vary: unsupported keyword(s) {sorted(extra)} (steps, eta, spacing, timesteps)")
+        self._latent_path(t_start, few.get("steps"), few.get("eta"), few.get("spacing"), few.get("timesteps"))    # argument errors first
+        for name, v in (("n_variants", n_variants), ("batch_size", batch_size)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        if isinstance(sample_id_base, bool) or int(sample_id_base) != sample_id_base or int(sample_id_base) < 0:
+            raise ValueError(f"sample_id_base must be an integer >= 0, got {sample_id_base!r}")
+        samples = list(samples)
+        if not samples:
+            raise ValueError("vary: no samples")
+        with_ctx = self.dynamics.context_node_nf > 0
+        jobs = [mol for mol in samples for _ in range(int(n_variants))]
+        batches = [(lo, scoring.pad_samples(jobs[lo:lo + int(batch_size)], self.n_dims, self.in_node_nf, with_ctx))
+                   for lo in range(0, len(jobs), int(batch_size))]
+        self._edit_check("vary", batches[0][1][2], (), batches[0][1][3], needs_noise=True)
+        out = []
+        for lo, (x, h, nm, ctx) in batches:
+            nmd, ctxd = nm.to(device), None if ctx is None else ctx.to(device)
+            base = int(sample_id_base) + lo
+            z = self.diffuse(x.to(device), h.to(device), nmd, t_start, sample_id_base=base)
+            xv, hv = self.sample_from_latent(z, nmd, None, ctxd, t_start=t_start, sample_id_base=base, **few)
+            xv, hv = xv.cpu(), hv.cpu()
+            for i in range(nm.shape[0]):
+                n = int(nm[i].sum())
+                res = {'x': xv[i, :n].clone(), 'h': hv[i, :n].clone()}
+                if ctx is not None:
+                    res['context'] = ctx[i, :n].clone()
+                out.append(res)
+        return out
+
+    @torch.no_grad()
+    def interpolate(self, sample_a: Dict[str, torch.Tensor], sample_b: Dict[str, torch.Tensor], frames: int, device, *,
+                    t_end: Optional[int] = None, steps: Optional[int] = None, spacing: Optional[str] = None):
+        """`frames` molecules between two of equal node count (the sampler's result format; ValueError otherwise): both are encoded
+        to z_{t_end} (`encode`), the latents interpolated on the sphere at lambda = i / (frames - 1) (`slerp`), and every frame decoded
+        with eta = 0 on the reversed path (`sample_from_latent`), all frames as one batch that shares the decode's noise row - so
+        frames 0 and frames - 1 are the eta = 0 reconstructions of the two inputs, bit for bit.  A context is interpolated linearly.
+        Returns a list of `frames` results.  Mechanism only: what lies between two molecules is a property of the weights."""
+        from . import scoring
+        device = torch.device(device)
+        if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or int(frames) < 2:
+            raise ValueError(f"frames must be an integer >= 2, got {frames!r}")
+        L = int(frames)
+        from . import paths
+        t_end_i = self._grid_index(self.T if t_end is None else t_end, 1, "t_end")
+        paths.partial_path(self.T, t_end_i, steps, self.sample_spacing if spacing is None else spacing)        # argument errors first
+        with_ctx = self.dynamics.context_node_nf > 0
+        x, h, nm, ctx = scoring.pad_samples([sample_a, sample_b], self.n_dims, self.in_node_nf, with_ctx)
+        if int(nm[0].sum()) != int(nm[1].sum()):
+            raise ValueError(f"interpolate: the molecules must have equal node counts, got {int(nm[0].sum())} and {int(nm[1].sum())}")
+        self._edit_check("interpolate", nm, (), ctx, needs_noise=True)
+        nmd = nm.to(device)
+        z = self.encode(x.to(device), h.to(device), nmd, None, None if ctx is None else ctx.to(device), t_end=t_end_i, steps=steps,
+                        spacing=spacing)
+        lam = [i / (L - 1) for i in range(L)]
+        zf = self.slerp(z[0:1], z[1:2], lam, nmd[0:1]).reshape(L, z.shape[1], z.shape[2])
+        nm_f = nmd[0:1].expand(L, -1, -1).contiguous()
+        ctx_f = None
+        if ctx is not None:
+            w = torch.tensor(lam, dtype=torch.float32).view(L, 1, 1)
+            ctx_f = ((1.0 - w) * ctx[0:1] + w * ctx[1:2]).contiguous()
+        xf, hf = self.sample_from_latent(zf, nm_f, None, None if ctx_f is None else ctx_f.to(device), t_start=t_end_i, steps=steps,
+                                         eta=0.0, spacing=spacing, fix_noise=True)
+        xf, hf = xf.cpu(), hf.cpu()
+        n = int(nm[0].sum())
+        out = []
+        for i in range(L):
+            res = {'x': xf[i, :n].clone(), 'h': hf[i, :n].clone()}
+            if ctx_f is not None:
+                res['context'] = ctx_f[i, :n].clone()
+            out.append(res)
+        return out
+
     # ------------------------------------------------------------------ fragment-constrained sampling (no reference counterpart)
     def _inpaint_schedule(self, handle, tabs):
         """{alpha_s, sigma_s, alpha_t|s, sigma_t|s} per step from the gamma grid of `_schedule`, uploaded once per table."""

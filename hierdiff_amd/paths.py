@@ -140,3 +140,65 @@ def path_tables(gamma: torch.Tensor, path: Sequence[int], eta: float = 1.0) -> D
         inpaint, form = None, 1
     return {"t_idx": t_idx.to(torch.int32).contiguous(), "s_idx": s_idx.to(torch.int32).contiguous(), "coef": coef, "form": form,
             "coef_inpaint": inpaint, "K": int(t_idx.numel()), "eta": eta}
+
+
+# ----------------------------------------------------------------------------- editing given molecules: partial and ascending paths
+# A partial path starts at a grid index `start` <= T instead of T (the reverse chain below a noised molecule); an ascending path is
+# one reversed (the eta = 0 update run upwards in t, "DDIM inversion").  Which start, K and eta are chemically useful is, again, a
+# property of the trained checkpoint.
+
+def _check_start(T, start, what: str = "start") -> "tuple[int, int]":
+    if isinstance(start, bool) or not isinstance(start, (int, np.integer)):
+        raise ValueError(f"{what} must be an integer, got {start!r}")
+    T, start = int(T), int(start)
+    if T < 1:
+        raise ValueError(f"timesteps must be >= 1, got {T}")
+    if not (1 <= start <= T):
+        raise ValueError(f"{what} must be in 1 .. {T} (the trained grid), got {start}")
+    return T, start
+
+
+def partial_path(T: int, start: int, steps: Optional[int] = None, spacing: str = "uniform",
+                 timesteps: Optional[Sequence[int]] = None) -> List[int]:
+    """Strictly decreasing from `start` (1 <= start <= T) to 0 in K <= start transitions: the builders' formulas with T replaced by
+    `start` (default K = start: every grid point below it), or the validated explicit `timesteps`, which must begin at `start`.
+    start = T is `build_path`."""
+    T, start = _check_start(T, start)
+    if steps is not None and timesteps is not None:
+        raise ValueError("give either steps or timesteps, not both")
+    return build_path(start, steps, spacing, timesteps)
+
+
+def ascending_path(T: int, end: int, steps: Optional[int] = None, spacing: str = "uniform",
+                   timesteps: Optional[Sequence[int]] = None) -> List[int]:
+    """`partial_path(T, end, ...)` reversed: strictly increasing from 0 to `end`.  An explicit `timesteps` is given in the
+    descending order of `partial_path`."""
+    _check_start(T, end, "end")
+    return partial_path(T, end, steps, spacing, timesteps)[::-1]
+
+
+def inversion_coefficients(gamma_u: torch.Tensor, gamma_v: torch.Tensor) -> torch.Tensor:
+    """[rows, 2] float64 {a, b} of the upward noise-free update z_v = a z_u - b eps for u < v: a = alpha_v / alpha_u,
+    b = a sigma_u - sigma_v - the eta = 0 row of `linear_coefficients` with the roles of s and t exchanged, so that with the same
+    eps the down row (v -> u) undoes it.  Round to fp32 once, where the rows are uploaded."""
+    gu, gv = gamma_u.reshape(-1).to(torch.float64), gamma_v.reshape(-1).to(torch.float64)
+    a = torch.sqrt(torch.sigmoid(-gv)) / torch.sqrt(torch.sigmoid(-gu))
+    b = a * torch.sqrt(torch.sigmoid(gu)) - torch.sqrt(torch.sigmoid(gv))
+    return torch.stack([a, b], dim=1)
+
+
+@torch.no_grad()
+def up_tables(gamma: torch.Tensor, path: Sequence[int]) -> Dict[str, object]:
+    """Arrays of hd_set_path_up for an ascending `path` (0 = path[0] < .. < path[K] <= T) from the gamma grid [T+1] (fp32):
+    from_idx / to_idx int32 [K], coef fp32 [K,4] = {a, b, 0, 0}."""
+    idx = [int(v) for v in path]
+    if len(idx) < 2 or any(b <= a for a, b in zip(idx[:-1], idx[1:])):
+        raise ValueError("an ascending path must be strictly increasing and hold at least one transition")
+    g = torch.as_tensor(gamma, dtype=torch.float32).reshape(-1)
+    if idx[0] < 0 or idx[-1] >= g.numel():
+        raise ValueError(f"an ascending path must stay within 0 .. {g.numel() - 1}")
+    idx_t = torch.as_tensor(idx, dtype=torch.int64)
+    u, v = idx_t[:-1], idx_t[1:]
+    ab = inversion_coefficients(g[u], g[v])
+    coef = torch.cat([ab, torch.zeros_like(ab)], dim=1).to(torch.float32).contiguous()
+    return {"from_idx": u.to(torch.int32).contiguous(), "to_idx": v.to(torch.int32).contiguous(), "coef": coef, "K": int(u.numel())}

@@ -14,6 +14,13 @@ FILE (this sampler's own output: a list of {'x', 'h'}, pickled alone or as the (
 as `.pt`) and samples N more around each (`DiffusionQM9.sample_grow`); the output format is unchanged, the known fragments come
 first.  Single process only.
 
+Editing given molecules (no reference counterpart; mechanism only - which settings are chemically useful is for you to validate):
+`--vary FILE --t-start S [--variants V]` noises every molecule of FILE to the grid index S and runs the reverse chain from there
+(`DiffusionQM9.vary`; combines with --steps / --eta / --spacing, which then spread over the S steps below the start);
+`--interpolate FILE --frames L` encodes consecutive molecules of FILE to their latents, interpolates on the sphere and decodes L
+frames per pair (`DiffusionQM9.interpolate`; --steps / --spacing apply to both directions; pairs of unequal size are skipped with a
+note).  Output: the same pickle format.  Single process only.
+
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N`; rank 0's weights are broadcast once,
 each rank samples a contiguous share of the global sample ids and writes `<out>.rank<r>`; rank 0 concatenates
 them in id order into `<out>`.
@@ -165,7 +172,32 @@ def parse_args(argv=None):
                          "Mechanism only: scores of untrained weights mean nothing chemically")
     ap.add_argument("--terms", type=int, default=None,
                     help="with --score: evaluate K <= timesteps uniformly spaced terms of the bound (default: all of them)")
+    ap.add_argument("--vary", default=None, metavar="FILE",
+                    help="variations of the molecules of FILE (the sampler's output format): noise each to --t-start and run the "
+                         "reverse chain from there; combines with --steps / --eta / --spacing.  Mechanism only")
+    ap.add_argument("--t-start", type=int, default=None,
+                    help="with --vary: the grid index in 1 .. timesteps the molecules are noised to (how far variations drift)")
+    ap.add_argument("--variants", type=int, default=1, help="with --vary: results per input molecule")
+    ap.add_argument("--interpolate", default=None, metavar="FILE",
+                    help="interpolate between consecutive molecules of FILE: encode (eta = 0 upwards), slerp, decode --frames "
+                         "molecules per pair; pairs of unequal size are skipped.  Mechanism only")
+    ap.add_argument("--frames", type=int, default=None, help="with --interpolate: molecules per pair, both ends included (>= 2)")
     args = ap.parse_args(argv)
+    modes = [n for n in ("score", "known", "vary", "interpolate") if getattr(args, n) is not None]
+    if len(modes) > 1:
+        ap.error("--" + " and --".join(modes) + " do not combine")
+    if (args.vary is None) != (args.t_start is None):
+        ap.error("--vary and --t-start go together")
+    if args.vary is not None and (args.t_start < 1 or args.variants < 1):
+        ap.error("--t-start and --variants must be >= 1")
+    if args.variants != 1 and args.vary is None:
+        ap.error("--variants needs --vary")
+    if (args.interpolate is None) != (args.frames is None):
+        ap.error("--interpolate and --frames go together")
+    if args.interpolate is not None and args.frames < 2:
+        ap.error("--frames must be >= 2")
+    if args.interpolate is not None and args.eta != 1.0:
+        ap.error("--eta does not combine with --interpolate (frames are decoded with eta = 0)")
     if args.score is not None and (args.known is not None or args.grow is not None or args.steps is not None):
         ap.error("--score does not combine with --known / --grow / --steps (it samples nothing)")
     if args.terms is not None and args.score is None:
@@ -229,6 +261,32 @@ def main(argv=None) -> int:
         scores = model.score(read_known(args.score), dev, batch_size=max(1, args.batch_size), terms=args.terms)
         with open(args.out, "wb") as f:
             pickle.dump(scores, f)
+        return 0
+
+    if args.vary is not None:
+        if world > 1:
+            raise SystemExit("--vary runs in a single process")
+        if args.t_start > model.T:
+            raise SystemExit(f"--t-start {args.t_start} exceeds the model's {model.T} timesteps")
+        if args.steps is not None and args.steps > args.t_start:
+            raise SystemExit(f"--steps {args.steps} exceeds the {args.t_start} steps below --t-start")
+        model.sample_steps = None               # --steps spreads over the t_start steps below the start, not over the whole grid
+        write_results(args.out, model.vary(read_known(args.vary), dev, args.t_start, n_variants=args.variants,
+                                           batch_size=max(1, args.batch_size), steps=args.steps))
+        return 0
+
+    if args.interpolate is not None:
+        if world > 1:
+            raise SystemExit("--interpolate runs in a single process")
+        model.sample_steps = None
+        mols = read_known(args.interpolate)
+        frames: List[dict] = []
+        for i, (a, b) in enumerate(zip(mols[:-1], mols[1:])):
+            if int(a["x"].shape[0]) != int(b["x"].shape[0]):
+                print(f"--interpolate: skipping pair {i}, {i + 1}: {int(a['x'].shape[0])} and {int(b['x'].shape[0])} nodes")
+                continue
+            frames.extend(model.interpolate(a, b, args.frames, dev, steps=args.steps))
+        write_results(args.out, frames)
         return 0
 
     if args.known is not None:

@@ -189,7 +189,11 @@ int hd_final_decode(hd_handle* h, hd_topology* topo, const float* z0, const floa
  *   scoring               (hd_nll_terms, hd_nll_finish) a stream of its own, used with the DATA of a sample instead of its chain: the
  *                         noise eps_t of the bound's term t = 1 .. T is draw = t, the noise eps_0 of the t = 0 likelihood is draw 0.
  *                         The counter is the term's grid index, never its position in the term list, so a molecule's score does not
- *                         depend on the order of the terms or on how their range was split into calls. */
+ *                         depend on the order of the terms or on how their range was split into calls.
+ *   editing               (hd_diffuse, then hd_sample_path on a partial path) the start state z_{t_start} = alpha xh + sigma eps draws at
+ *                         draw 0, the slot plain sampling uses for z_T; the partial chain below it draws at T - s of the steps it visits
+ *                         and the decode at T + 1 - the plain layout with draw 0 re-purposed and draws 1 .. T - t_start unused.
+ *                         Inversion (hd_set_path_up) and hd_slerp draw nothing. */
 int hd_noise(hd_handle* h, hd_topology* topo, const float* raw_x, const float* raw_h, int noise_rows,
              uint64_t seed, uint64_t sample_id_base, uint32_t draw, int share_rows, float* z, void* stream);
 
@@ -235,6 +239,37 @@ int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z, const floa
                            int use_graph, const uint8_t* fixed_mask, const float* xh_known, int resamplings, void* stream);
 /* Number of times the topology's captured path transition was instantiated (-1: null topology): a cached replay leaves it unchanged. */
 long long hd_path_graph_builds(const hd_topology* topo);
+
+/* ---- Editing given molecules (ABI 12, additive; no reference counterpart): start a reverse chain from a noised molecule instead of
+ * z_T (variations of a lead; the SDEdit idea), run the deterministic eta = 0 update UPWARDS in t to encode a molecule to its latent
+ * ("DDIM inversion"), and interpolate latents on the sphere.  Mechanism only: which t_start, K and eta are chemically useful is for
+ * the user to validate on a trained checkpoint.
+ *
+ * hd_diffuse: z[B,N,D] = alpha xh + sigma eps for normalised data xh [B,N,D], eps = the combined noise of hd_noise (masked, x part
+ * mean-free over the valid nodes; raw_x / raw_h device [noise_rows,N,3|F] with noise_rows = B or 1 = one shared row, or NULL = the
+ * generator at (seed, sample_id_base + b, draw), share_rows as in hd_noise; eps equals hd_noise's tensor for the same arguments bit
+ * for bit).  alpha / sigma: sqrt(sigmoid(-+gamma_t)) of the grid point the caller starts from.  sigma == 0 generates and reads no
+ * normal (z_0 = alpha_0 xh, the start of an inversion).  Writes z only; a molecule without valid nodes gets alpha xh.  Stream-ordered,
+ * no host synchronisation.  HD_E_INVALID: raw_x and raw_h not both given or both NULL, noise_rows not 1 or B, N * D floats beyond one
+ * workgroup's LDS (64 KiB). */
+int hd_diffuse(hd_handle* h, hd_topology* topo, const float* xh, float alpha, float sigma, const float* raw_x, const float* raw_h,
+               int noise_rows, uint64_t seed, uint64_t sample_id_base, uint32_t draw, int share_rows, float* z, void* stream);
+/* An ASCENDING path into the tables hd_set_path fills: K transitions from_idx[k] -> to_idx[k] with 0 <= from_idx[k] < to_idx[k] <= T,
+ * from_idx[k + 1] = to_idx[k], K <= T (HD_E_INVALID otherwise; hd_set_path itself keeps refusing ascending pairs).  Host rows coef4
+ * {a, b, 0, 0} of z_v = (a z_u - b eps) for u = from_idx[k], v = to_idx[k]: a = alpha_v / alpha_u, b = a sigma_u - sigma_v, the eta = 0
+ * row of hd_set_path with the roles of s and t exchanged; a non-zero third or fourth entry is HD_E_INVALID - inversion draws nothing.
+ * Form 1, no inpainting rows.  The network time of transition k is tau[from_idx[k]], the departure, as for descending paths.
+ * hd_sample_path then runs either direction unchanged (one captured transition per topology, the cached graph rebuilt when the path
+ * changes); hd_sample_path_inpaint on an ascending path is HD_E_INVALID.  Schedule requirements as hd_set_path. */
+int hd_set_path_up(hd_handle* h, int K, const int* from_idx, const int* to_idx, const float* coef4);
+/* out[L,B,N,D]: per molecule and weight lam_l (HOST array of L >= 1 floats) the spherical interpolation
+ *     out_l = (sin((1 - lam_l) theta) za + sin(lam_l theta) zb) / sin theta,   theta = acos(clamp(<za, zb> / (|za| |zb|), -1, 1)),
+ * of two latents za, zb [B,N,D] on the topology's masks; dot product and norms run over the valid entries, accumulated in double in a
+ * fixed order, theta and the two weights in double, the combination in fp32.  Where sin theta < 1e-6 (parallel or antiparallel
+ * latents) or a latent is zero: the linear form (1 - lam) za + lam zb.  lam = 0 returns za and lam = 1 returns zb bit for bit; masked
+ * entries are exactly 0; nothing is re-centred (a linear combination of mean-free x parts is mean-free).  One launch per 64 frames,
+ * stream-ordered, no host synchronisation; lam_host is read before the call returns.  HD_E_INVALID: L < 1, out overlapping za or zb. */
+int hd_slerp(hd_handle* h, hd_topology* topo, const float* za, const float* zb, const float* lam_host, int L, float* out, void* stream);
 
 /* ---- Scoring (ABI 12, additive; no reference counterpart beyond the one-timestep estimator, compute_loss with t0_always = True,
  * diffusion_qm9.py:530-699): the variational bound of GIVEN molecules with every term of a list evaluated, in the device loop.
