@@ -164,12 +164,14 @@ struct InpaintKey {
 struct PathKey {
     const float *raw_x, *raw_h;
     int has_ctx, mol_shape, noise_rows, k_lo, resamplings;   // k_lo: injected-noise offsets are relative to the first transition
+    int w_rows;                                              // guided transition: rows of the scale array, and phi (0 / 0: unguided)
+    float phi;
     uint64_t seed;
     unsigned long long weights_gen, sched_gen, path_gen, ip_gen;
     bool operator==(const PathKey& o) const {
         return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape && noise_rows == o.noise_rows &&
-               k_lo == o.k_lo && resamplings == o.resamplings && seed == o.seed && weights_gen == o.weights_gen &&
-               sched_gen == o.sched_gen && path_gen == o.path_gen && ip_gen == o.ip_gen;
+               k_lo == o.k_lo && resamplings == o.resamplings && w_rows == o.w_rows && phi == o.phi && seed == o.seed &&
+               weights_gen == o.weights_gen && sched_gen == o.sched_gen && path_gen == o.path_gen && ip_gen == o.ip_gen;
     }
 };
 
@@ -218,6 +220,13 @@ struct hd_topology {
     hipGraphExec_t gexec_path;
     PathKey pkey;
     long long path_builds;
+    // hd_sample_path_guided: the second network output, and for the captured guided transition - a graph of its own next to the
+    // unguided one - library-owned copies of the null context and the scales (one allocation, made by the first guided call);
+    // `guided_builds` counts the instantiations (hd_guided_graph_builds)
+    hipGraphExec_t gexec_guided;
+    PathKey gdkey;
+    long long guided_builds;
+    float *guide_mem, *eps_u, *ctxu_buf, *wbuf;
     // hd_nll_terms / hd_nll_finish: eps_t and, for the captured term, library-owned copies of xh / the accumulator / the e_t table
     // (allocated by the first such call; z_t lives in zbuf); `nll_builds` counts the instantiations (hd_nll_graph_builds)
     hipGraphExec_t gexec_nll;
@@ -762,7 +771,7 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     ArenaSlot sl{t->device, t->arena, t->arena_bytes, t->staging, t->staging_bytes, nullptr};
     // a captured graph, or launches on several streams: wait for the device (the rare case - a sampling topology lives as
     // long as its model); otherwise an event behind the topology's last work guards the arena's next owner
-    bool pooled = t->arena && !t->gexec && !t->gexec_ip && !t->gexec_path && !t->gexec_nll && !t->multi_stream;
+    bool pooled = t->arena && !t->gexec && !t->gexec_ip && !t->gexec_path && !t->gexec_guided && !t->gexec_nll && !t->multi_stream;
     if (pooled && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) == hipSuccess) {
         if (hipEventRecord(sl.done, t->last_stream) != hipSuccess) { (void)hipEventDestroy(sl.done); sl.done = nullptr; pooled = false; }
     } else {
@@ -772,6 +781,8 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     if (t->gexec) hipGraphExecDestroy(t->gexec);
     if (t->gexec_ip) hipGraphExecDestroy(t->gexec_ip);
     if (t->gexec_path) hipGraphExecDestroy(t->gexec_path);
+    if (t->gexec_guided) hipGraphExecDestroy(t->gexec_guided);
+    if (t->guide_mem) (void)hipFree(t->guide_mem);
     if (t->ip_fixed) (void)hipFree(t->ip_fixed);
     if (t->ip_known) (void)hipFree(t->ip_known);
     if (t->gexec_nll) hipGraphExecDestroy(t->gexec_nll);
@@ -2987,10 +2998,40 @@ extern "C" int hd_set_path_up(hd_handle* h, int K, const int* from_idx, const in
 
 extern "C" long long hd_path_graph_builds(const hd_topology* topo) { return topo ? topo->path_builds : -1; }
 
-// Both path loops: R = 0 is the plain one, R >= 1 the inpainting one with R rounds per transition.
+// Classifier-free guidance of a path loop: every network call becomes two (context, then ctx_u) and k_guide_combine in place.
+struct GuideSrc {
+    const float* ctx_u;   // [B,N,C] the null (or any second) context
+    const float* w;       // device [w_rows]
+    int w_rows;
+    float phi;
+};
+
+static int guide_launch(hd_handle* h, hd_topology* t, const float* eps_c, const float* eps_u, const float* w, int w_rows, float phi,
+                        float* out, hipStream_t s) {
+    ProfScope ps(h, s, 2);
+    GuideArgs a;
+    a.eps_c = eps_c; a.eps_u = eps_u; a.w = w; a.nm = t->nm_bytes; a.out = out; a.rescale = phi; a.w_rows = w_rows;
+    a.B = t->B; a.N = t->N; a.D = h->D;
+    hipLaunchKernelGGL(k_guide_combine, dim3(t->B), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+// the topology's second network output and the library-owned copies of the null context / the scales: one allocation
+static int guide_buffers(hd_handle* h, hd_topology* t) {
+    if (t->guide_mem) return HD_OK;
+    auto pad = [](size_t n) { return (std::max<size_t>(n, 1) + 63) & ~size_t(63); };
+    const size_t BN = (size_t)t->B * t->N;
+    const size_t n_eps = pad(BN * h->D), n_ctx = pad(BN * (size_t)std::max(1, h->cfg.context_node_nf)), n_w = pad((size_t)t->B);
+    HD_TRY(dev_alloc(&t->guide_mem, n_eps + n_ctx + n_w));
+    t->eps_u = t->guide_mem; t->ctxu_buf = t->eps_u + n_eps; t->wbuf = t->ctxu_buf + n_ctx;
+    return HD_OK;
+}
+
+// The path loops: R = 0 is the plain one, R >= 1 the inpainting one with R rounds per transition; gd != NULL guides either.
 static int path_loop(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
                      const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
-                     const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s) {
+                     const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const GuideSrc* gd = nullptr) {
     const int T = h->T, K = h->path_K, N = topo->N, form = h->path_form;
     const int mol = (mol_shape < 0 || mol_shape > N) ? N : mol_shape;
     const int ms = mol_shape < 0 ? -1 : mol;
@@ -3000,6 +3041,7 @@ static int path_loop(hd_handle* h, hd_topology* topo, float* z, const float* con
     const int ntr = k_hi - k_lo;
     topo_use(topo, s);
     if (ntr == 0) return HD_OK;
+    if (gd) HD_TRY(guide_buffers(h, topo));
     if (!use_graph) {
         for (int k = k_lo; k < k_hi; ++k) {
             const float* tcur = h->d_tau + h->path_t_h[k];
@@ -3007,6 +3049,10 @@ static int path_loop(hd_handle* h, hd_topology* topo, float* z, const float* con
             const size_t ro = (size_t)(k - k_lo) * noise_rows * mol;
             for (int j = 0; j < (R ? R : 1); ++j) {
                 HD_TRY(forward_impl(h, topo, z, tcur, 1, context, ms, topo->eps, s));
+                if (gd) {
+                    HD_TRY(forward_impl(h, topo, z, tcur, 1, gd->ctx_u, ms, topo->eps_u, s));
+                    HD_TRY(guide_launch(h, topo, topo->eps, topo->eps_u, gd->w, gd->w_rows, gd->phi, topo->eps, s));
+                }
                 NoiseSrc ns = make_noise(raw_x ? raw_x + ro * 3 : nullptr, raw_h ? raw_h + ro * h->F : nullptr, noise_rows, seed,
                                          sample_id_base, stride * (uint32_t)(3 * j) + d, share);
                 HD_TRY(step_impl(h, topo, z, topo->eps, h->d_path_coef + (size_t)k * 4, 1, ns, mol, z, N, nullptr, nullptr, 0, s,
@@ -3051,16 +3097,20 @@ static int path_loop(hd_handle* h, hd_topology* topo, float* z, const float* con
     key.raw_x = raw_x; key.raw_h = raw_h; key.has_ctx = context ? 1 : 0; key.mol_shape = ms; key.noise_rows = noise_rows;
     key.k_lo = raw_x ? k_lo : 0; key.resamplings = R; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
     key.path_gen = h->path_gen; key.ip_gen = R ? h->ip_gen : 0;
-    if (topo->gexec_path && !(topo->pkey == key)) {
+    key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
+    // the guided transition is a graph of its own: guided and unguided calls on one topology do not evict each other
+    hipGraphExec_t& gx = gd ? topo->gexec_guided : topo->gexec_path;
+    PathKey& kx = gd ? topo->gdkey : topo->pkey;
+    if (gx && !(kx == key)) {
         if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
         HIP_TRY(hipStreamSynchronize(rs));
-        hipGraphExecDestroy(topo->gexec_path);
-        topo->gexec_path = nullptr;
+        hipGraphExecDestroy(gx);
+        gx = nullptr;
     }
     PathWords w;
     w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = R ? h->d_ipdraw : nullptr;
     w.tau = h->d_tau; w.t_idx = h->d_path_t; w.s_idx = h->d_path_s; w.K = K; w.T = T; w.nd = nd; w.stride = stride;
-    if (!topo->gexec_path) {
+    if (!gx) {
         const int was_prof = h->prof;
         h->prof = 0;
         hipGraph_t graph = nullptr;
@@ -3068,6 +3118,8 @@ static int path_loop(hd_handle* h, hd_topology* topo, float* z, const float* con
         int rc = HD_OK;
         for (int j = 0; j < (R ? R : 1) && rc == HD_OK; ++j) {
             rc = forward_impl(h, topo, topo->zbuf, h->d_tcur, 1, context ? topo->ctxbuf : nullptr, ms, topo->eps, rs);
+            if (rc == HD_OK && gd) rc = forward_impl(h, topo, topo->zbuf, h->d_tcur, 1, topo->ctxu_buf, ms, topo->eps_u, rs);
+            if (rc == HD_OK && gd) rc = guide_launch(h, topo, topo->eps, topo->eps_u, topo->wbuf, gd->w_rows, gd->phi, topo->eps, rs);
             if (rc == HD_OK) {
                 NoiseSrc ns = make_noise(raw_x, raw_h, noise_rows, seed, 0, 0, share);
                 rc = step_impl(h, topo, topo->zbuf, topo->eps, h->d_path_coef, 1, ns, mol, topo->zbuf, N, h->d_step,
@@ -3085,21 +3137,25 @@ static int path_loop(hd_handle* h, hd_topology* topo, float* z, const float* con
         h->prof = was_prof;
         if (rc != HD_OK) { if (graph) hipGraphDestroy(graph); return rc; }
         if (ce != hipSuccess) return fail(HD_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-        const hipError_t ie = hipGraphInstantiate(&topo->gexec_path, graph, nullptr, nullptr, 0);
+        const hipError_t ie = hipGraphInstantiate(&gx, graph, nullptr, nullptr, 0);
         hipGraphDestroy(graph);
-        if (ie != hipSuccess) { topo->gexec_path = nullptr; return fail(HD_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
-        topo->pkey = key;
-        topo->path_builds++;
+        if (ie != hipSuccess) { gx = nullptr; return fail(HD_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+        kx = key;
+        if (gd) topo->guided_builds++; else topo->path_builds++;
     }
     HIP_TRY(hipMemcpyAsync(topo->zbuf, z, zbytes, hipMemcpyDeviceToDevice, rs));
     if (context) HIP_TRY(hipMemcpyAsync(topo->ctxbuf, context, cbytes, hipMemcpyDeviceToDevice, rs));
+    if (gd) {
+        HIP_TRY(hipMemcpyAsync(topo->ctxu_buf, gd->ctx_u, cbytes, hipMemcpyDeviceToDevice, rs));
+        HIP_TRY(hipMemcpyAsync(topo->wbuf, gd->w, (size_t)gd->w_rows * sizeof(float), hipMemcpyDeviceToDevice, rs));
+    }
     if (R) {
         HIP_TRY(hipMemcpyAsync(topo->ip_fixed, fixed_mask, BN, hipMemcpyDeviceToDevice, rs));
         HIP_TRY(hipMemcpyAsync(topo->ip_known, xh_known, zbytes, hipMemcpyDeviceToDevice, rs));
     }
     hipLaunchKernelGGL(k_path_state, dim3(1), dim3(64), 0, rs, w, k_lo, (unsigned long long)sample_id_base);
     for (int k = 0; k < ntr; ++k) {
-        const hipError_t le = hipGraphLaunch(topo->gexec_path, rs);
+        const hipError_t le = hipGraphLaunch(gx, rs);
         if (le != hipSuccess) return fail(HD_E_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(le));
     }
     HIP_TRY(hipMemcpyAsync(z, topo->zbuf, zbytes, hipMemcpyDeviceToDevice, rs));
@@ -3159,6 +3215,63 @@ extern "C" int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z,
     HIP_TRY(hipSetDevice(h->device));
     return path_loop(h, topo, z, context, -1, k_lo, k_hi, nullptr, nullptr, noise_rows, seed, sample_id_base, use_graph,
                      fixed_mask, xh_known, resamplings, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------- classifier-free guidance
+
+extern "C" int hd_guide_combine(hd_handle* h, hd_topology* topo, const float* eps_c, const float* eps_u, const float* w_dev, int w_rows,
+                                float rescale, float* out, void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_guide_combine: null handle/topology");
+    if (!eps_c || !eps_u || !w_dev || !out) return fail(HD_E_INVALID, "hd_guide_combine: null tensor");
+    if (w_rows != 1 && w_rows != topo->B) return fail(HD_E_INVALID, "hd_guide_combine: w_rows must be 1 or B");
+    if (!(rescale >= 0.f && rescale <= 1.f)) return fail(HD_E_INVALID, "hd_guide_combine: rescale must lie in [0, 1]");
+    const size_t per = (size_t)topo->B * topo->N * h->D;
+    if (out < eps_u + per && eps_u < out + per) return fail(HD_E_INVALID, "hd_guide_combine: out may not overlap eps_u");
+    if (out != eps_c && out < eps_c + per && eps_c < out + per)
+        return fail(HD_E_INVALID, "hd_guide_combine: out may be eps_c itself, not a shifted overlap of it");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    return guide_launch(h, topo, eps_c, eps_u, w_dev, w_rows, rescale, out, s);
+}
+
+extern "C" long long hd_guided_graph_builds(const hd_topology* topo) { return topo ? topo->guided_builds : -1; }
+
+extern "C" int hd_sample_path_guided(hd_handle* h, hd_topology* topo, float* z, const float* context, const float* context_u,
+                                     const float* w_dev, int w_rows, float rescale, int k_lo, int k_hi, const float* raw_x,
+                                     const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
+                                     const uint8_t* fixed_mask, const float* xh_known, int resamplings, void* stream) {
+    const char* who = "hd_sample_path_guided";
+    if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_sample_path_guided: need 0 <= k_lo <= k_hi <= K");
+    HD_TRY(check_ready(h, topo, who));
+    HD_TRY(path_ready(h, who, k_lo, k_hi));
+    if (h->cfg.context_node_nf < 1) return fail(HD_E_INVALID, "hd_sample_path_guided: needs a context-conditioned model");
+    if (!z || !context || !context_u || !w_dev) return fail(HD_E_INVALID, "hd_sample_path_guided: null z / context / context_u / w");
+    if (w_rows != 1 && w_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_path_guided: w_rows must be 1 or B");
+    if (!(rescale >= 0.f && rescale <= 1.f)) return fail(HD_E_INVALID, "hd_sample_path_guided: rescale must lie in [0, 1]");
+    if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_path_guided: needs a time-conditioned model");
+    int R = 0;
+    if (fixed_mask) {                                        // the restrictions of hd_sample_path_inpaint
+        if (h->path_up) return fail(HD_E_INVALID, "hd_sample_path_guided: the path ascends (hd_set_path_up): inversion fixes no fragments");
+        if (h->path_form != 0) return fail(HD_E_INVALID, "hd_sample_path_guided: inpainting takes ancestral rows only (the path was set with form = 1)");
+        if (!h->d_path_coef_ip) return fail(HD_E_STATE, "hd_sample_path_guided: the path was set without inpainting rows (hd_set_path)");
+        if (!xh_known) return fail(HD_E_INVALID, "hd_sample_path_guided: fixed_mask without xh_known");
+        if (raw_x || raw_h) return fail(HD_E_INVALID, "hd_sample_path_guided: inpainting takes no injected noise (counter-based generator only)");
+        if (noise_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_path_guided: inpainting needs noise_rows = B");
+        if (resamplings < 1) return fail(HD_E_INVALID, "hd_sample_path_guided: resamplings must be >= 1");
+        if (((unsigned long long)h->T + 2ULL) * 3ULL * (unsigned long long)resamplings > 0xffffffffULL)
+            return fail(HD_E_INVALID, "hd_sample_path_guided: (T + 2) * 3 * resamplings exceeds the 32-bit draw index");
+        if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_sample_path_guided: N * D floats exceed one workgroup's LDS");
+        R = resamplings;
+    } else {
+        if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, "hd_sample_path_guided: raw_x and raw_h go together");
+        if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_path_guided: noise_rows must be 1 or B");
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    GuideSrc gd;
+    gd.ctx_u = context_u; gd.w = w_dev; gd.w_rows = w_rows; gd.phi = rescale;
+    return path_loop(h, topo, z, context, -1, k_lo, k_hi, R ? nullptr : raw_x, R ? nullptr : raw_h, noise_rows, seed, sample_id_base,
+                     use_graph, R ? fixed_mask : nullptr, R ? xh_known : nullptr, R, (hipStream_t)stream, &gd);
 }
 
 // ----------------------------------------------------------------------------- editing given molecules: start state, slerp

@@ -179,6 +179,16 @@ class DiffusionQM9(_Base):
         self.sample_spacing = "uniform"
         self.sample_timesteps = None
         self._force_path_loop = False   # tests: run the identity path (K = T, eta = 1) through the path loop instead of the plain one
+        # classifier-free guidance (hierdiff_amd/guidance.py): defaults of the `guidance_scale` / `guidance_context` /
+        # `guidance_rescale` keywords of the sampling entry points.  None = unguided, i.e. nothing changes.  `null_context`: a float
+        # or a [C] vector, the context a molecule is given in place of its own - by guided sampling (the second network call) and by
+        # context dropout in training (`context_drop_prob`, one draw per molecule; `context_drop_generator`: optional CPU generator)
+        self.guidance_scale = None
+        self.guidance_context = None
+        self.guidance_rescale = 0.0
+        self.null_context = _get(cfg, "null_context", 0.0) or 0.0
+        self.context_drop_prob = float(_get(cfg, "context_drop_prob", 0.0) or 0.0)
+        self.context_drop_generator = None
 
     def check_issues_norm_values(self, num_stdevs=8):
         """diffusion_qm9.py:117-131 (predefined schedules only)."""
@@ -418,6 +428,9 @@ class DiffusionQM9(_Base):
         # every valid node, pocket residues included (models/utils.py:51-56)
         x = x - (x[:, :fix].sum(1, keepdim=True) / nm[:, :fix].sum(1, keepdim=True)) * nm
         context = batch['context'] if self.dynamics.context_node_nf > 0 else None
+        if context is not None and self.training and self.context_drop_prob > 0:
+            from . import guidance
+            context = guidance.drop_context(context, self.context_drop_prob, self.null_context, node_mask, self.context_drop_generator)
         bs, n_nodes, _ = x.size()
         edge_mask = edge_mask.reshape(bs, n_nodes * n_nodes)
         self._check_masked(x, node_mask, "assert_correctly_masked")
@@ -738,14 +751,54 @@ class DiffusionQM9(_Base):
         bs = 1 if fix_noise else mu.size(0)
         return mu + sigma * self.sample_combined_position_feature_noise(bs, mu.size(1), node_mask)
 
+    # ------------------------------------------------------------------ classifier-free guidance (no reference counterpart)
+    def _guide_device(self, gd, node_mask, dev):
+        """Device-side inputs of a guided call: (null / second context rows [B*N,C], scales [rows], rows, phi)."""
+        from . import guidance
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        C_ = int(self.dynamics.context_node_nf)
+        if gd.context is None:
+            ctx_u = guidance.masked_null_context(self.null_context, node_mask.to(dev), C_)
+        else:
+            ctx_u = gd.context.to(dev, torch.float32)
+        return AttrDict(ctx_u=ctx_u.reshape(B * N, C_).contiguous(), w=gd.w.to(dev).contiguous(), rows=gd.rows, phi=gd.rescale)
+
+    def _guided_path(self, h, topo, z, ctx, g, k_lo, k_hi, rx, rh, rows, seed, base, stream, fixed=None, known=None, R=0):
+        """hd_sample_path_guided on z in place (g: `_guide_device`); fixed / known / R: the inpainting form."""
+        _lib.check(_lib.load().hd_sample_path_guided(
+            h, topo.ptr, z.data_ptr(), ctx.data_ptr(), g.ctx_u.data_ptr(), g.w.data_ptr(), g.rows, g.phi, int(k_lo), int(k_hi),
+            _ptr(rx), _ptr(rh), rows, seed, base, int(self.use_graph), _ptr(fixed), _ptr(known), int(R), stream),
+            "hd_sample_path_guided")
+
+    def _decode_eps(self, topo, z, ctx, g=None):
+        """The network call of the final decode (t = 0); guided the way the loop's calls are: two forwards, hd_guide_combine."""
+        dev = z.device
+        zeros = torch.zeros((z.shape[0], 1), device=dev)
+        eps = self.dynamics.forward_with_topology(topo, zeros, z, ctx, None)
+        if g is None:
+            return eps
+        eps_u = self.dynamics.forward_with_topology(topo, zeros, z, g.ctx_u, None)
+        _lib.check(_lib.load().hd_guide_combine(self._lib_handle(synced=True), topo.ptr, eps.data_ptr(), eps_u.data_ptr(),
+                                                g.w.data_ptr(), g.rows, g.phi, eps.data_ptr(), _stream(dev)), "hd_guide_combine")
+        return eps
+
     # ------------------------------------------------------------------ full reverse process
     @torch.no_grad()
     def sample_from_masks(self, node_mask: torch.Tensor, edge_mask: Optional[torch.Tensor], context=None,
                           fix_noise: bool = False, raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None,
                           sample_id_base: int = 0, z_init: Optional[torch.Tensor] = None, pocket=None, *,
                           steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
-                          timesteps: Optional[Sequence[int]] = None):
+                          timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
         """z_T -> (x, h) for given masks: draw z_T, T posterior steps, final decode.
+
+        guidance_scale / guidance_context / guidance_rescale (keyword-only; None: the model's attributes of the same names):
+        classifier-free guidance of a context-conditioned model - every network call of the chain (the decode's included) runs
+        under `context` and under `guidance_context` ([B,N,C]; None: the model's `null_context`) and eps_u + w (eps_c - eps_u) goes
+        into the unchanged update, inside the library's loop (hd_sample_path_guided; the identity path when no few-step path is
+        asked for).  `guidance_scale`: a float or a [B] tensor (per molecule); `guidance_rescale` phi in [0, 1] rescales the
+        combination towards the spread of eps_c.  None, or a scalar 1.0 without a guidance_context, is the unguided code path,
+        untouched.  Draws are those of the unguided chain.  Mechanism only: the model must have been trained with context dropout
+        (`context_drop_prob`), and which scale helps is for the user to validate on a trained checkpoint.
 
         steps / eta / spacing / timesteps (keyword-only; None: the model's `sample_steps` / `sample_eta` / `sample_spacing` /
         `sample_timesteps`): few-step sampling - K = steps transitions on a sub-sequence of the trained grid ("uniform" or
@@ -763,6 +816,13 @@ class DiffusionQM9(_Base):
         (diffusion_qm9.py:362-371,381-382); the final decode sees the molecule alone (:386-387)."""
         dev = node_mask.device
         pe = self._resolve_path(steps, eta, spacing, timesteps)
+        from . import guidance, paths
+        gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, int(node_mask.shape[0]), int(node_mask.shape[1]),
+                              "sample_from_masks", pocket, needs_noise=raw_noises is None)
+        if gd is not None and context is None:
+            raise ValueError("context required")
+        if gd is not None and pe is None:            # a guided chain always runs in the path loop: the identity path, ancestral steps
+            pe = (paths.build_path(self.T), 1.0)
         if pe is not None and (getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics" or
                                (self.noise_mode == "torch" and raw_noises is None)):
             raise NotImplementedError("few-step sampling runs inside the library's loop: mode 'gnn_dynamics' and noise_mode 'torch' "
@@ -797,10 +857,14 @@ class DiffusionQM9(_Base):
             self._em_cat[:, N:, N:] = p_em.to(dev).bool()
             topo_loop = self.dynamics.topology(self._nm_cat, self._em_cat, B, N + P)
         stream = _stream(dev)
+        g = None if gd is None else self._guide_device(gd, node_mask, dev)
 
         def run_loop(z_mol, rx, rh, rows, seed, base):
             """T posterior steps on [B,N,D]; with a pocket the fixed rows ride along behind the molecule."""
             zz = z_mol if tail is None else torch.cat([z_mol, tail], dim=1).contiguous()
+            if g is not None:            # guided: the K transitions of the path, two network calls each
+                self._guided_path(h, topo_loop, zz, ctx, g, 0, K, rx, rh, rows, seed, base, stream)
+                return zz
             if pe is not None:           # the K transitions of the path
                 _lib.check(lib.hd_sample_path(h, topo_loop.ptr, zz.data_ptr(), _ptr(ctx), -1 if tail is None else N, 0, K,
                                               _ptr(rx), _ptr(rh), rows, seed, base, int(self.use_graph), stream),
@@ -860,7 +924,7 @@ class DiffusionQM9(_Base):
             final_raw = "philox"
         self._check_mean_zero(z[:, :, :self.n_dims], node_mask)
         zeros = torch.zeros((B, 1), device=dev)
-        eps = self.phi(z, zeros, node_mask, edge_mask, context) if gnn else self.dynamics.forward_with_topology(topo, zeros, z, ctx, None)
+        eps = self.phi(z, zeros, node_mask, edge_mask, context) if gnn else self._decode_eps(topo, z, ctx, g)
         coef3 = tabs["decode"].numpy()
         if final_raw == "philox":
             x, hfeat = self._final_decode(z, eps, node_mask, edge_mask, coef3, fix_noise, None,
@@ -871,7 +935,8 @@ class DiffusionQM9(_Base):
 
     @torch.no_grad()
     def path_steps(self, z, node_mask, edge_mask=None, context=None, *, steps=None, eta=None, spacing=None, timesteps=None,
-                   k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False):
+                   k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False,
+                   guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
         """Transitions k_lo .. k_hi-1 of `sample_from_masks`'s few-step loop on a given z [B,N,D] (normalised units, the state at
         path position k_lo); returns the state at position k_hi (default: the end of the path, z_0 before the decode).  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole."""
@@ -888,6 +953,10 @@ class DiffusionQM9(_Base):
         B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
         if tuple(z.shape) != (B, N, self.n_dims + self.in_node_nf) or not (0 <= int(k_lo) <= k_hi <= K):
             raise ValueError("z must be [B, N, 3 + F] and 0 <= k_lo <= k_hi <= steps")
+        from . import guidance
+        gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, B, N, "path_steps")
+        if gd is not None and context is None:
+            raise ValueError("context required")
         dev = node_mask.device
         if dev.type != "cuda":
             raise _lib.HierDiffHipError("sampling runs only on an MI355X (no CPU fallback)")
@@ -900,6 +969,10 @@ class DiffusionQM9(_Base):
                 raise ValueError("context required")
             ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
         z = z.detach().to(dev, torch.float32).clone().contiguous()
+        if gd is not None:
+            self._guided_path(h, topo, z, ctx, self._guide_device(gd, node_mask, dev), k_lo, k_hi, None, None,
+                              1 if fix_noise else B, self.seed, sample_id_base, _stream(dev))
+            return z
         _lib.check(_lib.load().hd_sample_path(h, topo.ptr, z.data_ptr(), _ptr(ctx), -1, int(k_lo), k_hi, None, None,
                                               1 if fix_noise else B, self.seed, sample_id_base, int(self.use_graph), _stream(dev)),
                    "hd_sample_path")
@@ -1186,7 +1259,7 @@ class DiffusionQM9(_Base):
     def latent_steps(self, z, node_mask, edge_mask=None, context=None, *, t_start: Optional[int] = None, steps: Optional[int] = None,
                      eta: Optional[float] = None, spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None,
                      k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False,
-                     raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None):
+                     raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
         """Transitions k_lo .. k_hi-1 of `sample_from_latent`'s partial chain on a given z [B,N,D] (the state at path position k_lo);
         returns the state at position k_hi (default: the end, z_0 before the decode), as `path_steps` does for a full path.  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.  `raw_noises`: k_hi - k_lo injected
@@ -1198,6 +1271,9 @@ class DiffusionQM9(_Base):
             raise ValueError(f"need 0 <= k_lo <= k_hi <= {K} (the path's transitions)")
         B, N = self._edit_check("sample_from_latent", node_mask, (("z", z, self.n_dims + self.in_node_nf),), context, sample_id_base,
                                 needs_noise=raw_noises is None)
+        from . import guidance
+        gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, B, N, "sample_from_latent",
+                              needs_noise=raw_noises is None)
         nb = 1 if fix_noise else B
         if raw_noises is not None:
             if len(raw_noises) != k_hi - k_lo:
@@ -1214,6 +1290,10 @@ class DiffusionQM9(_Base):
             rx = torch.stack([r[0].to(st.dev, torch.float32) for r in raw_noises]).contiguous()
             rh = torch.stack([r[1].to(st.dev, torch.float32) for r in raw_noises]).contiguous()
             seed, base = 0, 0
+        if gd is not None:
+            self._guided_path(st.h, st.topo, z, st.ctx, self._guide_device(gd, node_mask, st.dev), k_lo, k_hi, rx, rh, nb, seed, base,
+                              st.stream)
+            return z
         _lib.check(_lib.load().hd_sample_path(st.h, st.topo.ptr, z.data_ptr(), _ptr(st.ctx), -1, k_lo, k_hi, _ptr(rx), _ptr(rh), nb,
                                               seed, base, int(self.use_graph), st.stream), "hd_sample_path")
         return z
@@ -1222,7 +1302,7 @@ class DiffusionQM9(_Base):
     def sample_from_latent(self, z, node_mask, edge_mask=None, context=None, *, t_start: Optional[int] = None,
                            steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
                            timesteps: Optional[Sequence[int]] = None, sample_id_base: int = 0, fix_noise: bool = False,
-                           raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None):
+                           raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
         """(x, h) from a state z [B,N,D] at the grid index `t_start` (default T; normalised units - what `diffuse` and `encode`
         return): the partial reverse chain on `paths.partial_path(T, t_start, steps, spacing, timesteps)` (default: every grid point
         below t_start) inside the library's loop (hd_sample_path), then the final decode of `sample_from_masks`.  `eta` defaults to
@@ -1235,9 +1315,12 @@ class DiffusionQM9(_Base):
         K = len(path) - 1
         if raw_noises is not None and len(raw_noises) != K + 1:
             raise ValueError(f"raw_noises must hold {K} + 1 (randn_x, randn_h) pairs: the transitions, then the decode")
+        from . import guidance
+        gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, int(node_mask.shape[0]) if node_mask.dim() == 3 else None,
+                              int(node_mask.shape[1]) if node_mask.dim() == 3 else None, "sample_from_latent", needs_noise=raw_noises is None)
         z0 = self.latent_steps(z, node_mask, edge_mask, context, t_start=t_start, steps=steps, eta=eta, spacing=spacing,
                                timesteps=timesteps, sample_id_base=sample_id_base, fix_noise=fix_noise,
-                               raw_noises=None if raw_noises is None else raw_noises[:K])
+                               raw_noises=None if raw_noises is None else raw_noises[:K], guidance_scale=guidance_scale, guidance_context=guidance_context, guidance_rescale=guidance_rescale)
         B, N = z0.shape[0], z0.shape[1]
         dev = z0.device
         node_mask = node_mask.to(dev)
@@ -1246,7 +1329,7 @@ class DiffusionQM9(_Base):
         if self.dynamics.context_node_nf > 0:
             ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
         self._check_mean_zero(z0[:, :, :self.n_dims], node_mask)
-        eps = self.dynamics.forward_with_topology(topo, torch.zeros((B, 1), device=dev), z0, ctx, None)
+        eps = self._decode_eps(topo, z0, ctx, None if gd is None else self._guide_device(gd, node_mask, dev))
         coef3 = self._schedule(rows=B)["decode"].numpy()
         if raw_noises is not None:
             return self._final_decode(z0, eps, node_mask, edge_mask, coef3, fix_noise, raw_noises[K])
@@ -1291,12 +1374,21 @@ class DiffusionQM9(_Base):
         takes it) is noised to the grid index `t_start` (`diffuse`) and the reverse chain runs from there (`sample_from_latent`;
         keywords steps / eta / spacing / timesteps).  Returns `n_variants` results per input in the same format, input-major; variant
         v of input i runs under the sample id sample_id_base + i * n_variants + v, so it does not depend on the batch it ran in.
+        guidance_scale (a float, or one scale per result, input-major) / guidance_rescale: classifier-free guidance of the reverse
+        chain as in `sample_from_masks`, under the model's `null_context`.
         Mechanism only: how far which t_start drifts, and whether the analogues are chemically useful, is for the user to validate."""
         from . import scoring
         device = torch.device(device)
-        extra = set(few) - {"steps", "eta", "spacing", "timesteps"}
+        extra = set(few) - {"steps", "eta", "spacing", "timesteps", "guidance_scale", "guidance_context", "guidance_rescale"}
         if extra:
-            raise ValueError(f"vary: unsupported keyword(s) {sorted(extra)} (steps, eta, spacing, timesteps)")
+            raise ValueError(f"vary: unsupported keyword(s) {sorted(extra)} (steps, eta, spacing, timesteps, guidance_scale, "
+                             "guidance_context, guidance_rescale)")
+        from . import guidance
+        gscale, gctx = few.pop("guidance_scale", None), few.pop("guidance_context", None)
+        few["guidance_rescale"] = few.get("guidance_rescale", None)
+        if gctx is not None:
+            raise ValueError("vary: guidance_context is not supported (the list form pads its own batches): set the model's null_context")
+        gd_all = guidance.resolve(self, gscale, None, few["guidance_rescale"], None, None, "vary")
         self._latent_path(t_start, few.get("steps"), few.get("eta"), few.get("spacing"), few.get("timesteps"))    # argument errors first
         for name, v in (("n_variants", n_variants), ("batch_size", batch_size)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
@@ -1308,6 +1400,8 @@ class DiffusionQM9(_Base):
             raise ValueError("vary: no samples")
         with_ctx = self.dynamics.context_node_nf > 0
         jobs = [mol for mol in samples for _ in range(int(n_variants))]
+        if gd_all is not None and gd_all.rows != 1 and gd_all.rows != len(jobs):
+            raise ValueError(f"vary: guidance_scale must hold one scale per result ([{len(jobs)}], input-major), got {gd_all.rows}")
         batches = [(lo, scoring.pad_samples(jobs[lo:lo + int(batch_size)], self.n_dims, self.in_node_nf, with_ctx))
                    for lo in range(0, len(jobs), int(batch_size))]
         self._edit_check("vary", batches[0][1][2], (), batches[0][1][3], needs_noise=True)
@@ -1316,7 +1410,8 @@ class DiffusionQM9(_Base):
             nmd, ctxd = nm.to(device), None if ctx is None else ctx.to(device)
             base = int(sample_id_base) + lo
             z = self.diffuse(x.to(device), h.to(device), nmd, t_start, sample_id_base=base)
-            xv, hv = self.sample_from_latent(z, nmd, None, ctxd, t_start=t_start, sample_id_base=base, **few)
+            gs = None if gd_all is None else (float(gd_all.w[0]) if gd_all.rows == 1 else gd_all.w[lo:lo + nm.shape[0]])
+            xv, hv = self.sample_from_latent(z, nmd, None, ctxd, t_start=t_start, sample_id_base=base, guidance_scale=gs, **few)
             xv, hv = xv.cpu(), hv.cpu()
             for i in range(nm.shape[0]):
                 n = int(nm[i].sum())
@@ -1382,7 +1477,8 @@ class DiffusionQM9(_Base):
             self._inpaint_tabs = tabs
         return tabs
 
-    def _inpaint_setup(self, node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, path_args=(None,) * 4):
+    def _inpaint_setup(self, node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, path_args=(None,) * 4,
+                       guide_args=None):
         """Argument checks of the inpainting entry points (ValueError / NotImplementedError before anything is queued), then the
         device-side inputs of hd_sample_loop_inpaint."""
         if node_mask.dim() != 3 or node_mask.shape[2] != 1:
@@ -1414,6 +1510,12 @@ class DiffusionQM9(_Base):
         if self.noise_mode == "torch":
             raise NotImplementedError("inpainting: noise_mode 'torch' is not supported (counter-based noise only)")
         pe = self._resolve_path(*path_args, inpaint=True)
+        gd = None
+        if guide_args is not None:
+            from . import guidance, paths
+            gd = guidance.resolve(self, *guide_args, B, N, "inpainting")
+            if gd is not None and pe is None:        # a guided chain always runs in the path loop: the identity path
+                pe = (paths.build_path(self.T), 1.0)
         if dev.type != "cuda":
             raise _lib.HierDiffHipError("sampling runs only on an MI355X (no CPU fallback)")
         h = self._lib_handle()
@@ -1431,9 +1533,14 @@ class DiffusionQM9(_Base):
         xh_known = torch.where(fmb, xh_known, torch.zeros_like(xh_known)).contiguous()
         fm_u8 = fmb.reshape(B * N).to(torch.uint8).contiguous()
         return AttrDict(h=h, tabs=tabs, topo=topo, ctx=ctx, xk=xk, hk=hk, xh_known=xh_known, fm_u8=fm_u8, B=B, N=N,
-                        R=int(resamplings), stream=_stream(dev), dev=dev, K=K)
+                        R=int(resamplings), stream=_stream(dev), dev=dev, K=K,
+                        g=None if gd is None else self._guide_device(gd, node_mask, dev))
 
     def _inpaint_run(self, st, z, s_hi, s_lo, sample_id_base):
+        if st.g is not None:             # guided (always on a path): two network calls per round
+            self._guided_path(st.h, st.topo, z, st.ctx, st.g, st.K - s_hi, st.K - s_lo, None, None, st.B, self.seed, sample_id_base,
+                              st.stream, st.fm_u8, st.xh_known, st.R)
+            return
         if st.K is not None:             # few-step sampling: s_hi / s_lo count path positions from the t = 0 end
             _lib.check(_lib.load().hd_sample_path_inpaint(
                 st.h, st.topo.ptr, z.data_ptr(), _ptr(st.ctx), -1, st.K - s_hi, st.K - s_lo, None, None, st.B, self.seed,
@@ -1460,7 +1567,7 @@ class DiffusionQM9(_Base):
     def sample_inpaint(self, node_mask: torch.Tensor, fixed_mask: torch.Tensor, x_known: torch.Tensor, h_known: torch.Tensor,
                        context=None, resamplings: int = 1, sample_id_base: int = 0, edge_mask: Optional[torch.Tensor] = None, *,
                        steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
-                       timesteps: Optional[Sequence[int]] = None):
+                       timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
         """(x, h) on the device for molecules whose `fixed_mask` [B,N,1] nodes are known: `x_known` [B,N,3] / `h_known` [B,N,F] in
         data units (what `sample` returns; rows outside `fixed_mask` are ignored, the frame of the positions is free).  The free
         nodes are sampled around them by the replacement method, `resamplings` network calls per step (RePaint for > 1), inside
@@ -1468,9 +1575,10 @@ class DiffusionQM9(_Base):
         h = h_known exactly, x = x_known translated as one block.  Training-free conditioning: how well the free part fits the
         known one depends on the model and on `resamplings`.  A sample depends on its global id (sample_id_base + row), its
         masks, the weights and its known values only.  steps / spacing / timesteps: few-step sampling as in `sample_from_masks`
-        (hd_sample_path_inpaint), ancestral steps only - eta < 1 raises ValueError."""
+        (hd_sample_path_inpaint), ancestral steps only - eta < 1 raises ValueError.  guidance_scale / guidance_context /
+        guidance_rescale: classifier-free guidance as in `sample_from_masks` (every round's network call is guided)."""
         st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask,
-                                 (steps, eta, spacing, timesteps))
+                                 (steps, eta, spacing, timesteps), (guidance_scale, guidance_context, guidance_rescale))
         lib, T, B, N = _lib.load(), self.T, st.B, st.N
         n_loop = T if st.K is None else st.K
         z = torch.empty((B, N, self.n_dims + self.in_node_nf), device=st.dev, dtype=torch.float32)
@@ -1482,8 +1590,7 @@ class DiffusionQM9(_Base):
                 self._check_mean_zero(z[:, :, :self.n_dims], node_mask)
         else:
             self._inpaint_run(st, z, n_loop, 0, sample_id_base)
-        zeros = torch.zeros((B, 1), device=st.dev)
-        eps = self.dynamics.forward_with_topology(st.topo, zeros, z, st.ctx, None)
+        eps = self._decode_eps(st.topo, z, st.ctx, st.g)
         x, hfeat = self._final_decode(z, eps, node_mask, edge_mask, st.tabs["decode"].numpy(), False, None,
                                       philox=(sample_id_base, T + 1))
         x, hfeat = x.contiguous(), hfeat.contiguous()
@@ -1494,13 +1601,15 @@ class DiffusionQM9(_Base):
     @torch.no_grad()
     def sample_grow(self, known: Sequence[Dict[str, torch.Tensor]], sizes, device, context=None, resamplings: int = 1,
                     sample_id_base: int = 0, *, steps: Optional[int] = None, eta: Optional[float] = None,
-                    spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None):
+                    spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
         """List-level form of `sample_inpaint` in `sample`'s result format: `known[i]` = {'x': [k_i,3], 'h': [k_i,F]} are the fragments
         molecule i keeps (its first k_i rows in the result; k_i = 0 allowed), `sizes[i]` >= k_i its total number of fragments (one
         integer: that many for every molecule).  `context`: as in `sample`.  Returns [{'x': [n_i,3], 'h': [n_i,F] (, 'context')}] on
         the CPU.  steps / eta / spacing / timesteps: as in `sample_inpaint`."""
         device = torch.device(device)
         self._resolve_path(steps, eta, spacing, timesteps, inpaint=True)       # argument errors first
+        from . import guidance
+        guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, None, None, "sample_grow")
         num = len(known)
         if isinstance(sizes, (int, np.integer)):
             sizes = [int(sizes)] * num
@@ -1531,7 +1640,10 @@ class DiffusionQM9(_Base):
                 raise ValueError(f"context of shape {tuple(torch.as_tensor(context).shape)} does not broadcast to [{num}, {n_max}, 1]")
         x, h = self.sample_inpaint(node_mask.to(device), fixed_mask.to(device), x_known.to(device), h_known.to(device),
                                    context=None if ctx is None else ctx.to(device), resamplings=resamplings,
-                                   sample_id_base=sample_id_base, steps=steps, eta=eta, spacing=spacing, timesteps=timesteps)
+                                   sample_id_base=sample_id_base, steps=steps, eta=eta, spacing=spacing, timesteps=timesteps,
+                                   guidance_scale=guidance_scale,
+                                   guidance_context=None if guidance_context is None else guidance_context.to(device),
+                                   guidance_rescale=guidance_rescale)
         x, h = x.cpu(), h.cpu()
         out = [{'x': x[i, :sizes[i]].clone(), 'h': h[i, :sizes[i]].clone()} for i in range(num)]
         if ctx is not None:
@@ -1542,12 +1654,18 @@ class DiffusionQM9(_Base):
     @torch.no_grad()
     def sample(self, num_samples, device, context=None, pocket_cond=None, sample_id_base: int = 0, *,
                steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
-               timesteps: Optional[Sequence[int]] = None):
+               timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
         """diffusion_qm9.py:347-395: list of {'x': [n_i,3], 'h': [n_i,8], ('context': [n_i,1])} on the CPU.
-        steps / eta / spacing / timesteps: few-step sampling, see `sample_from_masks`."""
+        steps / eta / spacing / timesteps: few-step sampling, see `sample_from_masks`; guidance_scale (a float or a
+        [num_samples] tensor) / guidance_context ([num_samples, n_max, C]) / guidance_rescale: classifier-free guidance, ibid."""
         device = torch.device(device)
         self._resolve_path(steps, eta, spacing, timesteps)                     # argument errors before anything is drawn
-        few = {k: v for k, v in dict(steps=steps, eta=eta, spacing=spacing, timesteps=timesteps).items() if v is not None}
+        from . import guidance
+        gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, int(num_samples), None, "sample", pocket_cond)
+        if gd is not None and context is None:
+            raise ValueError("context required")
+        few = {k: v for k, v in dict(steps=steps, eta=eta, spacing=spacing, timesteps=timesteps, guidance_scale=guidance_scale,
+                                     guidance_context=guidance_context, guidance_rescale=guidance_rescale).items() if v is not None}
         sample_n = self.nodes_dist.sample(num_samples)
         pocket = None
         if pocket_cond is not None:
@@ -1595,7 +1713,7 @@ class DiffusionQM9(_Base):
 
     def sample_batches(self, batch_size, num_batches, device, context_range=None, protein_data_all=None,
                        sample_id_base: int = 0, *, steps: Optional[int] = None, eta: Optional[float] = None,
-                       spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None):
+                       spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
         """diffusion_qm9.py:397-436, incl. the protein branch (`protein_data_all`: list of dicts with
         'residue_type', 'coord', 'pocket_name', 'ligand_name').
 
@@ -1610,7 +1728,22 @@ class DiffusionQM9(_Base):
         is not a sample's own: the NaN guard (en_dynamics.py:109-111) zeroes the velocity of the whole DEVICE batch."""
         device = torch.device(device)
         self._resolve_path(steps, eta, spacing, timesteps)                     # few-step sampling (`sample_from_masks`): argument errors first
-        few = {k: v for k, v in dict(steps=steps, eta=eta, spacing=spacing, timesteps=timesteps).items() if v is not None}
+        # classifier-free guidance (`sample_from_masks`): guidance_scale may also be a list / tuple of scales cycled per batch the way
+        # context_range is; inside a merged device batch it becomes one scale per molecule
+        from . import guidance
+        gscale = self.guidance_scale if guidance_scale is None else guidance_scale
+        if guidance_context is not None:
+            raise ValueError("sample_batches: guidance_context is not supported (the batches' padded widths differ): set the "
+                             "model's null_context")
+        if isinstance(gscale, (torch.Tensor, np.ndarray)) and gscale.ndim > 0:
+            raise ValueError("sample_batches: guidance_scale must be a float or a list / tuple of floats cycled per batch")
+        g_seq = guidance.batch_scales(gscale, int(num_batches), int(batch_size)) if guidance.is_sequence_scale(gscale) else None
+        guidance.resolve(self, gscale if g_seq is None else torch.tensor(g_seq), None, guidance_rescale, None, None, "sample_batches",
+                         protein_data_all)
+        few = {k: v for k, v in dict(steps=steps, eta=eta, spacing=spacing, timesteps=timesteps,
+                                     guidance_rescale=guidance_rescale).items() if v is not None}
+        if g_seq is None and gscale is not None:
+            few["guidance_scale"] = gscale
         # Not merged either: mode 'gnn_dynamics' (torch.randn draws whatever noise_mode says, messages over padded nodes) and
         # aggregation_method 'mean' (the divisor is the padded N of the call) - both depend on the padded width of the batch a
         # molecule sits in - and context_range entries that are not one scalar per batch.
@@ -1633,8 +1766,11 @@ class DiffusionQM9(_Base):
                     if hi + bs - lo > int(self.merge_batches) or (self.merge_edges and edges + more > int(self.merge_edges)):
                         break
                     hi, edges = hi + bs, edges + more
+                few_m = dict(few)
+                if g_seq is not None:                          # one scale per molecule: that of the batch it belongs to
+                    few_m["guidance_scale"] = torch.tensor([g_seq[j // bs] for j in range(lo, hi)], dtype=torch.float32)
                 results.extend(self._sample_sizes(sizes[lo:hi], device, ctxs[lo:hi] if ctxs else None, sample_id_base + lo,
-                                                  **({"few": few} if few else {})))
+                                                  **({"few": few_m} if few_m else {})))
                 lo = hi
             return results, []
         protein_cond_all = None
@@ -1644,6 +1780,8 @@ class DiffusionQM9(_Base):
         for i in range(num_batches):
             lo, hi = i * batch_size, (i + 1) * batch_size
             base = sample_id_base + lo
+            if g_seq is not None:                              # per molecule, as in the merged run (a scalar 1.0 would be unguided)
+                few = dict(few, guidance_scale=torch.full((int(batch_size),), g_seq[i], dtype=torch.float32))
             if protein_cond_all is not None:
                 n_prot = len(protein_cond_all[0])
                 cond = [x[lo % n_prot: (hi - 1) % n_prot + 1] for x in protein_cond_all]
@@ -1665,10 +1803,10 @@ class EnVariationalDiffusion(DiffusionQM9):
 
     @torch.no_grad()
     def sample(self, n_samples, n_nodes, node_mask, edge_mask, context, fix_noise=False, *,  # type: ignore[override]
-               steps=None, eta=None, spacing=None, timesteps=None):
+               steps=None, eta=None, spacing=None, timesteps=None, guidance_scale=None, guidance_context=None, guidance_rescale=None):
         assert node_mask.shape[0] == n_samples and node_mask.shape[1] == n_nodes
         x, h = self.sample_from_masks(node_mask, edge_mask, context, fix_noise=fix_noise, steps=steps, eta=eta, spacing=spacing,
-                                      timesteps=timesteps)
+                                      timesteps=timesteps, guidance_scale=guidance_scale, guidance_context=guidance_context, guidance_rescale=guidance_rescale)
         if self.debug_checks:
             self._check_mean_zero(x, node_mask)
         max_cog = torch.sum(x, dim=1, keepdim=True).abs().max()

@@ -182,7 +182,24 @@ def parse_args(argv=None):
                     help="interpolate between consecutive molecules of FILE: encode (eta = 0 upwards), slerp, decode --frames "
                          "molecules per pair; pairs of unequal size are skipped.  Mechanism only")
     ap.add_argument("--frames", type=int, default=None, help="with --interpolate: molecules per pair, both ends included (>= 2)")
+    ap.add_argument("--guidance", type=float, default=None, metavar="W",
+                    help="classifier-free guidance scale (needs --context): every network call runs under the context and under "
+                         "the null context, eps_u + W (eps_c - eps_u) goes into the update; combines with --steps / --eta / "
+                         "--spacing, --known / --grow and --vary.  Mechanism only: the checkpoint must have been trained with "
+                         "context dropout, and which W helps is for you to validate")
+    ap.add_argument("--guidance-rescale", type=float, default=0.0, metavar="PHI",
+                    help="with --guidance: rescale the combination towards the spread of the conditional prediction (0 .. 1)")
+    ap.add_argument("--null-context", type=float, nargs="+", default=None, metavar="V",
+                    help="with --guidance: the null context (one value, or one per context column; default 0)")
     args = ap.parse_args(argv)
+    if args.guidance is not None and not args.context:
+        ap.error("--guidance needs --context")
+    if args.guidance is None and (args.guidance_rescale != 0.0 or args.null_context is not None):
+        ap.error("--guidance-rescale and --null-context need --guidance")
+    if not (0.0 <= args.guidance_rescale <= 1.0):
+        ap.error("--guidance-rescale must be in [0, 1]")
+    if args.guidance is not None and (args.score is not None or args.interpolate is not None):
+        ap.error("--guidance does not combine with --score / --interpolate")
     modes = [n for n in ("score", "known", "vary", "interpolate") if getattr(args, n) is not None]
     if len(modes) > 1:
         ap.error("--" + " and --".join(modes) + " do not combine")
@@ -250,6 +267,10 @@ def main(argv=None) -> int:
     if args.steps is not None and args.steps > model.T:
         raise SystemExit(f"--steps {args.steps} exceeds the model's {model.T} timesteps")
     model.sample_steps, model.sample_eta, model.sample_spacing = args.steps, args.eta, args.spacing
+    if args.guidance is not None:
+        model.guidance_scale, model.guidance_rescale = args.guidance, args.guidance_rescale
+        if args.null_context is not None:
+            model.null_context = args.null_context[0] if len(args.null_context) == 1 else list(args.null_context)
     if world > 1:
         broadcast_model_weights(model, src=0)
 

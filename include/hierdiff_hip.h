@@ -30,6 +30,7 @@
  *   hd_noise                     <- sample_combined_position_feature_noise (:445-456)
  *   hd_sample_loop               <- the timestep loop of DiffusionQM9.sample (:375-384)
  *   hd_sample_loop_inpaint       <- no counterpart: the same loop with known fragments kept in place
+ *   hd_sample_path_guided        <- no counterpart: the path loop with classifier-free guidance (two network calls per transition)
  *   hd_nll_terms / hd_nll_finish <- the one-timestep estimator of compute_loss / nll in eval mode (:530-699), every listed t
  */
 #ifndef HIERDIFF_HIP_H
@@ -193,7 +194,8 @@ int hd_final_decode(hd_handle* h, hd_topology* topo, const float* z0, const floa
  *   editing               (hd_diffuse, then hd_sample_path on a partial path) the start state z_{t_start} = alpha xh + sigma eps draws at
  *                         draw 0, the slot plain sampling uses for z_T; the partial chain below it draws at T - s of the steps it visits
  *                         and the decode at T + 1 - the plain layout with draw 0 re-purposed and draws 1 .. T - t_start unused.
- *                         Inversion (hd_set_path_up) and hd_slerp draw nothing. */
+ *                         Inversion (hd_set_path_up) and hd_slerp draw nothing.
+ *   guidance              (hd_sample_path_guided, hd_guide_combine) guided loops draw what their unguided loop draws. */
 int hd_noise(hd_handle* h, hd_topology* topo, const float* raw_x, const float* raw_h, int noise_rows,
              uint64_t seed, uint64_t sample_id_base, uint32_t draw, int share_rows, float* z, void* stream);
 
@@ -270,6 +272,39 @@ int hd_set_path_up(hd_handle* h, int K, const int* from_idx, const int* to_idx, 
  * entries are exactly 0; nothing is re-centred (a linear combination of mean-free x parts is mean-free).  One launch per 64 frames,
  * stream-ordered, no host synchronisation; lam_host is read before the call returns.  HD_E_INVALID: L < 1, out overlapping za or zb. */
 int hd_slerp(hd_handle* h, hd_topology* topo, const float* za, const float* zb, const float* lam_host, int L, float* out, void* stream);
+
+/* ---- Classifier-free guidance (ABI 12, additive; no reference counterpart): every transition of a path loop evaluates the network
+ * twice - under the context and under a second ("null") context - and the combination
+ *     eps^ = eps_u + w (eps_c - eps_u)
+ * goes into the unchanged update.  w sets how strongly a sample follows its context (w = 1: the conditional model, w = 0: the
+ * unconditional one, w > 1: extrapolation).  Mechanism only: the model must have seen the null context in training (context dropout,
+ * hierdiff_amd/guidance.py), and which w helps on a trained checkpoint is for the user to validate.  Nothing is drawn.
+ *
+ * hd_guide_combine: out[B,N,D] from eps_c, eps_u [B,N,D] and the DEVICE array w_dev of w_rows = 1 (shared) or B (per molecule) scales.
+ * Per molecule: w_b == 1 copies eps_c and w_b == 0 copies eps_u bit for bit (rescale is ignored for these two values); otherwise
+ * g = fmaf(w_b, eps_c - eps_u, eps_u) per entry and, with rescale = phi > 0, the noise-prediction form of "CFG rescale":
+ *     out = f g,   f = fp32(phi sqrt(S_c / S_g) + (1 - phi)),
+ * S_c / S_g the sums of squared deviations of eps_c / g from their means over the molecule's valid entries (node mask, all D columns),
+ * accumulated in double in a fixed order (no atomics); S_g == 0 or a non-finite quotient gives f = 1.  phi == 0 runs no reduction.
+ * Masked entries are exactly 0.  out may be eps_c itself.  Stream-ordered, no host synchronisation.  HD_E_INVALID: w_rows not 1 or B,
+ * rescale outside [0, 1], out overlapping eps_u (or eps_c other than exactly).  The kernel stages nothing in LDS: any N * D. */
+int hd_guide_combine(hd_handle* h, hd_topology* topo, const float* eps_c, const float* eps_u, const float* w_dev, int w_rows,
+                     float rescale, float* out, void* stream);
+/* hd_sample_path (fixed_mask == NULL) or hd_sample_path_inpaint (fixed_mask != NULL, its restrictions apply) with guidance: per
+ * network call of the unguided loop two forwards at the same time value - context into the topology's eps, context_u into a second
+ * topology-owned buffer, each with its own NaN guard - then hd_guide_combine in place, then the unchanged update.  Needs a path
+ * (hd_set_path / hd_set_path_up), a context-conditioned model and both contexts [B,N,C]; whole molecules only (no pocket rows: there
+ * is no mol_shape).  Draw layout: that of the unguided loop (hd_noise).  w_dev / w_rows / rescale as in hd_guide_combine.
+ *   use_graph    ONE captured transition per topology in a graph of its own next to the unguided one (calls of either kind on one
+ *                topology do not evict each other); context_u and w are replayed from library-owned copies like the context, so new
+ *                values of w or of the contexts replay the cached graph.  Rebuilt when anything the unguided graph is keyed on
+ *                changes, or w_rows, rescale or whether inpainting runs.  use_graph = 0 gives the same bits. */
+int hd_sample_path_guided(hd_handle* h, hd_topology* topo, float* z, const float* context, const float* context_u, const float* w_dev,
+                          int w_rows, float rescale, int k_lo, int k_hi, const float* raw_x, const float* raw_h, int noise_rows,
+                          uint64_t seed, uint64_t sample_id_base, int use_graph, const uint8_t* fixed_mask, const float* xh_known,
+                          int resamplings, void* stream);
+/* Number of times the topology's captured guided transition was instantiated (-1: null topology). */
+long long hd_guided_graph_builds(const hd_topology* topo);
 
 /* ---- Scoring (ABI 12, additive; no reference counterpart beyond the one-timestep estimator, compute_loss with t0_always = True,
  * diffusion_qm9.py:530-699): the variational bound of GIVEN molecules with every term of a list evaluated, in the device loop.
