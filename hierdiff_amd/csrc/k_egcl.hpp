@@ -203,7 +203,11 @@ __global__ void k_linear(LinArgs a) {
     const float* wr = a.W + (size_t)n * a.K;
     float acc = 0.f;
     int k = 0;
-    if ((a.K & 3) == 0 && (a.ldx & 3) == 0) {
+    // float4 loads need 16-byte aligned rows: K and ldx multiples of 4 AND aligned bases (a view at an odd float offset of a
+    // larger buffer takes the scalar loop below - the same fmaf chain in the same order, so the same bits)
+    const bool vec = (a.K & 3) == 0 && (a.ldx & 3) == 0 &&
+                     ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.W)) & 15) == 0;
+    if (vec) {
         for (; k < a.K; k += 4) {
             const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + k), wv = *reinterpret_cast<const f32x4*>(wr + k);
 #pragma unroll

@@ -511,7 +511,9 @@ int hd_cand_xent_backward(int device, int B, const float* logits, int ld, int nc
 /* y [M][ldy] (first N columns) = act(x [M][ldx] (first K columns) . W [N][K]^T + b [N] or NULL); device fp32, any M, K, N.
  * act: 0 none, 1 SiLU, 2 sigmoid.  The small dense layers around the E_GCL chains of the stage-2 model - torch.nn.Linear in
  * /root/reference/models/edge_denoise.py:29-33 (feature / edge / node embeddings) and :55-57 (focal / edge / node prediction
- * heads, Linear + SiLU + Linear [+ Sigmoid]).  One fmaf chain over k per output element. */
+ * heads, Linear + SiLU + Linear [+ Sigmoid]).  One fmaf chain over k per output element, k ascending: the kernel reads four
+ * floats at a time when K and ldx are multiples of 4 and both x and W are 16-byte aligned, one at a time otherwise (a view at an
+ * odd float offset, a padded ldx) - same chain, same bits either way.  M = 0 is accepted and writes nothing. */
 int hd_linear(int device, const float* x, int M, int K, int ldx, const float* W, const float* b, int N, int act,
               float* y, int ldy, void* stream);
 
@@ -539,6 +541,7 @@ int hd_gemm_f32(int device, int M, int N, int K, const float* A, long long a_m_s
  * output, noised input, normalised data [x | h], noise), nm [B][N], gam [4][B] = gamma at (s, t, 0, 1), t_int [B].  int_nf / cont_nf:
  * integer / continuous feature columns of the t = 0 likelihood (5 / 3 for node_coarse_type 'prop', 3 / 0 otherwise); l2_train: the
  * `l2` training loss; T timesteps; nv2 / nb2 = norm_values[2] / norm_biases[2]; log_nv0 = log(norm_values[0]).
+ * All tensors are dense and contiguous, and masked-out nodes of net / eps / xh must be zero (the sums run over every node).
  * forward: loss [B] (= nll per molecule), err [B] (= the `error` of the reference's info dict).
  * backward: given gout = dL/d(loss) [B]: dnet, dzt [B][N][D] and dgam [4][B] (the schedule network is trained).
  * hd_vlb_zt: z_t = sqrt(sigmoid(-g_t)) xh + sqrt(sigmoid(g_t)) eps (dzt = NULL), or dgt[b] = d/dg_t of that against dzt. */
