@@ -102,8 +102,9 @@ struct hd_handle {
     uint32_t* d_ipdraw;         // graph replay: the draw words of a step's 3 * resamplings noise streams
     int ipdraw_cap;
     // path loop (hd_set_path / hd_sample_path / hd_sample_path_inpaint): K transitions t_idx[k] -> s_idx[k] on the schedule's grid
-    int path_K, path_form;      // form 0: ancestral rows, 1: linear rows {a, b, c, 0}
+    int path_K, path_form;      // form 0: ancestral rows, 1: linear rows {a, b, c, 0}, 2: multistep rows {a, b, c2, p, q} (5 floats)
     std::vector<int> path_t_h, path_s_h;
+    std::vector<float> path_c2_h;   // form 2: c2 of every row (which transitions read the history)
     int *d_path_t, *d_path_s;
     float *d_path_coef, *d_path_coef_ip;         // [K][4] each; d_path_coef_ip null when no inpainting rows were given
     unsigned long long path_sched_gen, path_gen; // sched_gen the path was set for (0: not set); bumped by every hd_set_path
@@ -227,6 +228,11 @@ struct hd_topology {
     PathKey gdkey;
     long long guided_builds;
     float *guide_mem, *eps_u, *ctxu_buf, *wbuf;
+    // multistep paths (hd_set_path_multistep): the previous transition's data prediction x^ [B][N][D], allocated by the first
+    // form-2 call at an address the captured transitions keep; host-side, which path generation and position it belongs to
+    float* ms_hist;
+    unsigned long long ms_gen;                 // 0: no history
+    int ms_k;
     // hd_nll_terms / hd_nll_finish: eps_t and, for the captured term, library-owned copies of xh / the accumulator / the e_t table
     // (allocated by the first such call; z_t lives in zbuf); `nll_builds` counts the instantiations (hd_nll_graph_builds)
     hipGraphExec_t gexec_nll;
@@ -783,6 +789,7 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     if (t->gexec_path) hipGraphExecDestroy(t->gexec_path);
     if (t->gexec_guided) hipGraphExecDestroy(t->gexec_guided);
     if (t->guide_mem) (void)hipFree(t->guide_mem);
+    if (t->ms_hist) (void)hipFree(t->ms_hist);
     if (t->ip_fixed) (void)hipFree(t->ip_fixed);
     if (t->ip_known) (void)hipFree(t->ip_known);
     if (t->gexec_nll) hipGraphExecDestroy(t->gexec_nll);
@@ -2619,6 +2626,32 @@ extern "C" int hd_posterior_step(hd_handle* h, hd_topology* topo, const float* z
                      nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
+// the multistep form of the step: `coef` device rows [K][5] read at *step_ptr (k_solver.hpp), or the host row by value
+static int solver_launch(hd_handle* h, hd_topology* t, const float* zt, const float* eps, const float* coef, const float* row5,
+                         const float* x_prev, float* x_out, int mol, float* zs, const int* step_ptr, hipStream_t s) {
+    ProfScope ps(h, s, 2);
+    SolverArgs a;
+    a.zt = zt; a.eps = eps; a.coef = coef; a.nm = t->nm_bytes; a.x_prev = x_prev; a.x_out = x_out; a.zs = zs; a.step_ptr = step_ptr;
+    for (int k = 0; k < 5; ++k) a.row[k] = row5 ? row5[k] : 0.f;
+    a.B = t->B; a.N = t->N; a.D = h->D; a.mol = mol;
+    hipLaunchKernelGGL(k_multistep_step, dim3(t->B), dim3(256), (size_t)mol * a.D * sizeof(float), s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_multistep_step(hd_handle* h, hd_topology* topo, const float* zt, const float* eps, const float* row5,
+                                 const float* x_prev, float* x_out, float* zs, void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_multistep_step: null handle/topology");
+    if (!zt || !eps || !row5 || !x_out || !zs) return fail(HD_E_INVALID, "hd_multistep_step: null tensor");
+    if (row5[2] != 0.f && !x_prev) return fail(HD_E_INVALID, "hd_multistep_step: a row with c2 != 0 needs x_prev");
+    if (x_out == zt || x_out == eps || x_out == zs || zs == eps || (x_prev && (zs == x_prev || x_prev == zt || x_prev == eps)))
+        return fail(HD_E_INVALID, "hd_multistep_step: only zs == zt and x_out == x_prev may alias");
+    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_multistep_step: N * D floats exceed one workgroup's LDS");
+    HIP_TRY(hipSetDevice(h->device));
+    topo_use(topo, (hipStream_t)stream);
+    return solver_launch(h, topo, zt, eps, nullptr, row5, x_prev, x_out, topo->N, zs, nullptr, (hipStream_t)stream);
+}
+
 extern "C" int hd_final_decode(hd_handle* h, hd_topology* topo, const float* z0, const float* eps, const float* coef3,
                                const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed,
                                uint64_t sample_id_base, uint32_t draw, int share_rows, float* x, float* hfeat,
@@ -2996,6 +3029,36 @@ extern "C" int hd_set_path_up(hd_handle* h, int K, const int* from_idx, const in
     return HD_OK;
 }
 
+// A descending path with multistep rows {a, b, c2, p, q} (form 2, k_solver.hpp) into the same tables.
+extern "C" int hd_set_path_multistep(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* rows5) {
+    if (!h || !t_idx || !s_idx || !rows5 || K < 1) return fail(HD_E_INVALID, "hd_set_path_multistep: bad argument");
+    if (h->T < 1) return fail(HD_E_STATE, "hd_set_path_multistep: schedule not set (hd_set_schedule)");
+    if (K > h->T) return fail(HD_E_INVALID, "hd_set_path_multistep: more transitions than the schedule has steps");
+    for (int k = 0; k < K; ++k) {
+        if (t_idx[k] > h->T || s_idx[k] < 0 || s_idx[k] >= t_idx[k])
+            return fail(HD_E_INVALID, "hd_set_path_multistep: need 0 <= s_idx[k] < t_idx[k] <= T (a multistep path descends)");
+        if (k > 0 && t_idx[k] != s_idx[k - 1])
+            return fail(HD_E_INVALID, "hd_set_path_multistep: transition k must start where k - 1 arrived");
+    }
+    if (rows5[2] != 0.f) return fail(HD_E_INVALID, "hd_set_path_multistep: c2 of row 0 must be 0 (the first transition has no history)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
+    hipFree(h->d_path_t); hipFree(h->d_path_s); hipFree(h->d_path_coef); hipFree(h->d_path_coef_ip);
+    h->d_path_t = h->d_path_s = nullptr; h->d_path_coef = h->d_path_coef_ip = nullptr;
+    h->path_sched_gen = 0; h->path_K = 0;
+    h->path_t_h.assign(t_idx, t_idx + K);
+    h->path_s_h.assign(s_idx, s_idx + K);
+    h->path_c2_h.resize((size_t)K);
+    for (int k = 0; k < K; ++k) h->path_c2_h[(size_t)k] = rows5[(size_t)5 * k + 2];
+    HD_TRY(dev_upload(&h->d_path_t, h->path_t_h));
+    HD_TRY(dev_upload(&h->d_path_s, h->path_s_h));
+    HD_TRY(dev_upload(&h->d_path_coef, std::vector<float>(rows5, rows5 + (size_t)5 * K)));
+    h->path_K = K; h->path_form = 2; h->path_up = false;
+    h->path_sched_gen = h->sched_gen;
+    h->path_gen++;                             // captured graphs hold the old table addresses
+    return HD_OK;
+}
+
 extern "C" long long hd_path_graph_builds(const hd_topology* topo) { return topo ? topo->path_builds : -1; }
 
 // Classifier-free guidance of a path loop: every network call becomes two (context, then ctx_u) and k_guide_combine in place.
@@ -3029,9 +3092,36 @@ static int guide_buffers(hd_handle* h, hd_topology* t) {
 }
 
 // The path loops: R = 0 is the plain one, R >= 1 the inpainting one with R rounds per transition; gd != NULL guides either.
+static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
+                         const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
+                         const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const GuideSrc* gd);
+
 static int path_loop(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
                      const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
                      const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const GuideSrc* gd = nullptr) {
+    if (h->path_form != 2 || k_hi == k_lo)
+        return path_loop_run(h, topo, z, context, mol_shape, k_lo, k_hi, raw_x, raw_h, noise_rows, seed, sample_id_base, use_graph,
+                             fixed_mask, xh_known, R, s, gd);
+    // multistep rows: the history x^_{k_lo - 1} is the topology's - a call that starts on a row with c2 != 0 continues the call
+    // that left it, on the same path (generation) and at the position where that call ended
+    const int mol = (mol_shape < 0 || mol_shape > topo->N) ? topo->N : mol_shape;
+    if (R) return fail(HD_E_INVALID, "multistep path: inpainting takes ancestral rows only");
+    if (h->path_c2_h[(size_t)k_lo] != 0.f && !(topo->ms_hist && topo->ms_gen == h->path_gen && topo->ms_k == k_lo))
+        return fail(HD_E_STATE, "multistep path: transition k_lo = " + std::to_string(k_lo) + " needs the data prediction of transition "
+                    "k_lo - 1, which the last call on this topology did not leave (start at a row with c2 = 0, such as k_lo = 0, or "
+                    "continue where the last call on the same path ended)");
+    if ((size_t)mol * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "multistep path: N * D floats exceed one workgroup's LDS");
+    if (!topo->ms_hist) HD_TRY(dev_alloc(&topo->ms_hist, (size_t)topo->B * topo->N * h->D));
+    topo->ms_gen = 0;                                        // no history unless the whole range ran
+    HD_TRY(path_loop_run(h, topo, z, context, mol_shape, k_lo, k_hi, raw_x, raw_h, noise_rows, seed, sample_id_base, use_graph,
+                         fixed_mask, xh_known, R, s, gd));
+    topo->ms_gen = h->path_gen; topo->ms_k = k_hi;           // stream-ordered behind this call, like z
+    return HD_OK;
+}
+
+static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
+                         const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
+                         const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const GuideSrc* gd) {
     const int T = h->T, K = h->path_K, N = topo->N, form = h->path_form;
     const int mol = (mol_shape < 0 || mol_shape > N) ? N : mol_shape;
     const int ms = mol_shape < 0 ? -1 : mol;
@@ -3055,6 +3145,11 @@ static int path_loop(hd_handle* h, hd_topology* topo, float* z, const float* con
                 }
                 NoiseSrc ns = make_noise(raw_x ? raw_x + ro * 3 : nullptr, raw_h ? raw_h + ro * h->F : nullptr, noise_rows, seed,
                                          sample_id_base, stride * (uint32_t)(3 * j) + d, share);
+                if (form == 2) {
+                    HD_TRY(solver_launch(h, topo, z, topo->eps, h->d_path_coef + (size_t)k * 5, nullptr, topo->ms_hist, topo->ms_hist,
+                                         mol, z, nullptr, s));
+                    continue;
+                }
                 HD_TRY(step_impl(h, topo, z, topo->eps, h->d_path_coef + (size_t)k * 4, 1, ns, mol, z, N, nullptr, nullptr, 0, s,
                                  nullptr, form));
                 if (!R) continue;
@@ -3120,7 +3215,10 @@ static int path_loop(hd_handle* h, hd_topology* topo, float* z, const float* con
             rc = forward_impl(h, topo, topo->zbuf, h->d_tcur, 1, context ? topo->ctxbuf : nullptr, ms, topo->eps, rs);
             if (rc == HD_OK && gd) rc = forward_impl(h, topo, topo->zbuf, h->d_tcur, 1, topo->ctxu_buf, ms, topo->eps_u, rs);
             if (rc == HD_OK && gd) rc = guide_launch(h, topo, topo->eps, topo->eps_u, topo->wbuf, gd->w_rows, gd->phi, topo->eps, rs);
-            if (rc == HD_OK) {
+            if (rc == HD_OK && form == 2) {
+                rc = solver_launch(h, topo, topo->zbuf, topo->eps, h->d_path_coef, nullptr, topo->ms_hist, topo->ms_hist, mol,
+                                   topo->zbuf, h->d_step, rs);
+            } else if (rc == HD_OK) {
                 NoiseSrc ns = make_noise(raw_x, raw_h, noise_rows, seed, 0, 0, share);
                 rc = step_impl(h, topo, topo->zbuf, topo->eps, h->d_path_coef, 1, ns, mol, topo->zbuf, N, h->d_step,
                                R ? h->d_ipdraw + 3 * j : h->d_draw, 0, rs, h->d_base, form, k_lo);

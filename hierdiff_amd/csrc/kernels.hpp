@@ -32,5 +32,6 @@
 #include "k_nll.hpp"
 #include "k_edit.hpp"
 #include "k_guide.hpp"
+#include "k_solver.hpp"
 #include "k_digest.hpp"
 #include "k_refine.hpp"

@@ -178,6 +178,9 @@ class DiffusionQM9(_Base):
         self.sample_eta = 1.0
         self.sample_spacing = "uniform"
         self.sample_timesteps = None
+        # default of the `solver` keyword: None / "ddim" = the first-order updates above; "dpm2m" = DPM-Solver++(2M), eta = 0
+        self.sample_solver = None
+        self.sample_lower_order_final = True
         self._force_path_loop = False   # tests: run the identity path (K = T, eta = 1) through the path loop instead of the plain one
         # classifier-free guidance (hierdiff_amd/guidance.py): defaults of the `guidance_scale` / `guidance_context` /
         # `guidance_rescale` keywords of the sampling entry points.  None = unguided, i.e. nothing changes.  `null_context`: a float
@@ -601,12 +604,24 @@ class DiffusionQM9(_Base):
             self._sched_key = key
         return self._sched
 
-    def _resolve_path(self, steps=None, eta=None, spacing=None, timesteps=None, inpaint: bool = False):
+    def _resolve_path(self, steps=None, eta=None, spacing=None, timesteps=None, inpaint: bool = False, solver=None,
+                      lower_order_final=None):
         """The keywords of the sampling entry points (None: the model's `sample_*` attributes) -> None for the plain loop, or
-        (path, eta).  Pure host arithmetic: every ValueError is raised before the GPU is touched."""
+        (path, eta); with solver "dpm2m" (path, `paths.Multistep`) - always the path loop, eta = 0 whatever `sample_eta` says.
+        Pure host arithmetic: every ValueError is raised before the GPU is touched."""
         from . import paths
         if steps is None and timesteps is None:
             steps, timesteps = self.sample_steps, self.sample_timesteps
+        ms = paths.check_solver(self.sample_solver if solver is None else solver, eta,
+                                self.sample_lower_order_final if lower_order_final is None else lower_order_final)
+        if ms is not None:
+            if inpaint:
+                raise ValueError("inpainting takes ancestral steps only (eta = 1), not solver 'dpm2m': the replacement method "
+                                 "re-noises the known part with the posterior's own variance")
+            spacing = self.sample_spacing if spacing is None else spacing
+            if spacing not in paths.SPACINGS:
+                raise ValueError(f"spacing must be one of {paths.SPACINGS}, got {spacing!r}")
+            return paths.build_path(self.T, steps, spacing, timesteps), ms
         eta = paths.check_eta(self.sample_eta if eta is None else eta)
         spacing = self.sample_spacing if spacing is None else spacing
         if spacing not in paths.SPACINGS:
@@ -624,9 +639,11 @@ class DiffusionQM9(_Base):
         return path, eta
 
     def _path_tables(self, handle, tabs, path, eta):
-        """Rows of `path` from the gamma grid of `_schedule`, uploaded to the handle (hd_set_path) once per (table, path, eta)."""
+        """Rows of `path` from the gamma grid of `_schedule`, uploaded to the handle (hd_set_path; hd_set_path_multistep when `eta`
+        is a `paths.Multistep`) once per (table, path, eta or solver with its lower_order_final)."""
         from . import paths
-        key = (tuple(path), float(eta))
+        ms = isinstance(eta, paths.Multistep)
+        key = (tuple(path), ("dpm2m", bool(eta.lower_order_final)) if ms else float(eta))
         hit = self.__dict__.get("_path_cache")
         if hit is None or hit[0] is not tabs or hit[1] != key:
             pt = paths.path_tables(tabs["gamma"], path, eta)
@@ -635,10 +652,15 @@ class DiffusionQM9(_Base):
             coef = np.ascontiguousarray(pt["coef"].numpy(), dtype=np.float32)
             cip = None if pt["coef_inpaint"] is None else np.ascontiguousarray(pt["coef_inpaint"].numpy(), dtype=np.float32)
             self._path_cache = None
-            _lib.check(_lib.load().hd_set_path(
-                handle, pt["K"], t_idx.ctypes.data_as(C.POINTER(C.c_int)), s_idx.ctypes.data_as(C.POINTER(C.c_int)),
-                coef.ctypes.data_as(C.POINTER(C.c_float)), pt["form"],
-                None if cip is None else cip.ctypes.data_as(C.POINTER(C.c_float))), "hd_set_path")
+            if ms:
+                _lib.check(_lib.load().hd_set_path_multistep(
+                    handle, pt["K"], t_idx.ctypes.data_as(C.POINTER(C.c_int)), s_idx.ctypes.data_as(C.POINTER(C.c_int)),
+                    coef.ctypes.data_as(C.POINTER(C.c_float))), "hd_set_path_multistep")
+            else:
+                _lib.check(_lib.load().hd_set_path(
+                    handle, pt["K"], t_idx.ctypes.data_as(C.POINTER(C.c_int)), s_idx.ctypes.data_as(C.POINTER(C.c_int)),
+                    coef.ctypes.data_as(C.POINTER(C.c_float)), pt["form"],
+                    None if cip is None else cip.ctypes.data_as(C.POINTER(C.c_float))), "hd_set_path")
             self._path_cache = (tabs, key, pt)
         return self._path_cache[2]
 
@@ -788,8 +810,16 @@ class DiffusionQM9(_Base):
                           fix_noise: bool = False, raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None,
                           sample_id_base: int = 0, z_init: Optional[torch.Tensor] = None, pocket=None, *,
                           steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
-                          timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
+                          timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
+                          solver: Optional[str] = None, lower_order_final: Optional[bool] = None):
         """z_T -> (x, h) for given masks: draw z_T, T posterior steps, final decode.
+
+        solver / lower_order_final (keyword-only; None: the model's `sample_solver` / `sample_lower_order_final`): None and "ddim" are the first-order
+        updates below; "dpm2m" runs the path with DPM-Solver++(2M) (hd_set_path_multistep: the eta = 0 update plus a correction
+        from the previous transition's data prediction, kept in a topology-owned buffer; second order, no extra network call,
+        first order on the first and - with lower_order_final - the last transition).  It is deterministic on the path: `eta`
+        defaults to 0 whatever `sample_eta` says, another explicit eta raises ValueError; steps / spacing / timesteps / guidance_*
+        combine as usual, and the draws are z_T (draw 0) and the decode (T + 1) alone.  Mechanism only, as `steps` / `eta`.
 
         guidance_scale / guidance_context / guidance_rescale (keyword-only; None: the model's attributes of the same names):
         classifier-free guidance of a context-conditioned model - every network call of the chain (the decode's included) runs
@@ -815,7 +845,7 @@ class DiffusionQM9(_Base):
         residue nodes: appended to z for every network call with a block-diagonal edge mask and never updated
         (diffusion_qm9.py:362-371,381-382); the final decode sees the molecule alone (:386-387)."""
         dev = node_mask.device
-        pe = self._resolve_path(steps, eta, spacing, timesteps)
+        pe = self._resolve_path(steps, eta, spacing, timesteps, solver=solver, lower_order_final=lower_order_final)
         from . import guidance, paths
         gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, int(node_mask.shape[0]), int(node_mask.shape[1]),
                               "sample_from_masks", pocket, needs_noise=raw_noises is None)
@@ -936,14 +966,19 @@ class DiffusionQM9(_Base):
     @torch.no_grad()
     def path_steps(self, z, node_mask, edge_mask=None, context=None, *, steps=None, eta=None, spacing=None, timesteps=None,
                    k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False,
-                   guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
+                   guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
+                   solver: Optional[str] = None, lower_order_final: Optional[bool] = None):
         """Transitions k_lo .. k_hi-1 of `sample_from_masks`'s few-step loop on a given z [B,N,D] (normalised units, the state at
         path position k_lo); returns the state at position k_hi (default: the end of the path, z_0 before the decode).  Draws are
-        keyed by the arrival step, so a chain cut into pieces gives the bits of the whole."""
+        keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.
+        solver="dpm2m": transition k > 0 also needs the data prediction of transition k - 1, which the library keeps with the
+        topology (the masks).  A call with k_lo > 0 must therefore continue the previous call on the same masks and the same path
+        exactly where that call ended (its k_hi); a piece-wise chain then gives the bits of the whole.  Anything else - fresh masks,
+        another path or solver in between, a gap - raises HierDiffHipError (HD_E_STATE) instead of using a stale prediction."""
         force = self._force_path_loop
         self._force_path_loop = True                 # also the identity path goes through hd_sample_path here
         try:
-            path, e = self._resolve_path(steps, eta, spacing, timesteps)
+            path, e = self._resolve_path(steps, eta, spacing, timesteps, solver=solver, lower_order_final=lower_order_final)
         finally:
             self._force_path_loop = force
         if getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics" or self.noise_mode == "torch":
@@ -1228,13 +1263,16 @@ class DiffusionQM9(_Base):
 
     @torch.no_grad()
     def encode(self, x, h, node_mask, edge_mask=None, context=None, *, t_end: Optional[int] = None, steps: Optional[int] = None,
-               spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None):
+               spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None, solver: Optional[str] = None):
         """The latent z_{t_end} [B,N,D] (default t_end = T) of raw data (x, h): z_0 = alpha_0 xh without noise, then the deterministic
         eta = 0 update of the DDIM family run UPWARDS in t ("DDIM inversion") on `paths.ascending_path(T, t_end, steps, spacing,
         timesteps)` - default every grid point - inside the library's loop (hd_set_path_up / hd_sample_path: one captured transition
         per topology).  Nothing is drawn: the result depends on the data, the masks, the weights and the path only.  Decoding with
-        `sample_from_latent(eta=0)` on the same points comes back near the molecule; how near is a property of the weights and K."""
+        `sample_from_latent(eta=0)` on the same points comes back near the molecule; how near is a property of the weights and K.
+        The inversion stays first order: solver="dpm2m" raises ValueError (the model's `sample_solver` is not consulted)."""
         from . import paths
+        if paths.check_solver(solver) is not None:
+            raise ValueError("encode: the inversion is first order (eta = 0 upwards); solver 'dpm2m' is not supported")
         t_end = self._grid_index(self.T if t_end is None else t_end, 1, "t_end")
         spacing = self.sample_spacing if spacing is None else spacing
         path = paths.ascending_path(self.T, t_end, steps, spacing, timesteps)
@@ -1247,11 +1285,13 @@ class DiffusionQM9(_Base):
                                               int(self.use_graph), st.stream), "hd_sample_path")
         return z
 
-    def _latent_path(self, t_start, steps, eta, spacing, timesteps):
-        """(t_start, partial path, eta) of the keywords; pure host arithmetic."""
+    def _latent_path(self, t_start, steps, eta, spacing, timesteps, solver=None, lower_order_final=None):
+        """(t_start, partial path, eta - or the `paths.Multistep` of solver "dpm2m") of the keywords; pure host arithmetic."""
         from . import paths
         t_start = self._grid_index(self.T if t_start is None else t_start, 1, "t_start")
-        eta = paths.check_eta(self.sample_eta if eta is None else eta)
+        ms = paths.check_solver(self.sample_solver if solver is None else solver, eta,
+                                self.sample_lower_order_final if lower_order_final is None else lower_order_final)
+        eta = ms if ms is not None else paths.check_eta(self.sample_eta if eta is None else eta)
         spacing = self.sample_spacing if spacing is None else spacing
         return t_start, paths.partial_path(self.T, t_start, steps, spacing, timesteps), eta
 
@@ -1259,12 +1299,13 @@ class DiffusionQM9(_Base):
     def latent_steps(self, z, node_mask, edge_mask=None, context=None, *, t_start: Optional[int] = None, steps: Optional[int] = None,
                      eta: Optional[float] = None, spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None,
                      k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False,
-                     raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
+                     raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
+                     solver: Optional[str] = None, lower_order_final: Optional[bool] = None):
         """Transitions k_lo .. k_hi-1 of `sample_from_latent`'s partial chain on a given z [B,N,D] (the state at path position k_lo);
         returns the state at position k_hi (default: the end, z_0 before the decode), as `path_steps` does for a full path.  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.  `raw_noises`: k_hi - k_lo injected
-        (randn_x, randn_h) pairs, one per transition run."""
-        t_start, path, eta = self._latent_path(t_start, steps, eta, spacing, timesteps)
+        (randn_x, randn_h) pairs, one per transition run.  solver="dpm2m" over a sub-range: the continuity rule of `path_steps`."""
+        t_start, path, eta = self._latent_path(t_start, steps, eta, spacing, timesteps, solver, lower_order_final)
         K = len(path) - 1
         k_lo, k_hi = int(k_lo), K if k_hi is None else int(k_hi)
         if not (0 <= k_lo <= k_hi <= K):
@@ -1302,7 +1343,8 @@ class DiffusionQM9(_Base):
     def sample_from_latent(self, z, node_mask, edge_mask=None, context=None, *, t_start: Optional[int] = None,
                            steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
                            timesteps: Optional[Sequence[int]] = None, sample_id_base: int = 0, fix_noise: bool = False,
-                           raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
+                           raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
+                           solver: Optional[str] = None, lower_order_final: Optional[bool] = None):
         """(x, h) from a state z [B,N,D] at the grid index `t_start` (default T; normalised units - what `diffuse` and `encode`
         return): the partial reverse chain on `paths.partial_path(T, t_start, steps, spacing, timesteps)` (default: every grid point
         below t_start) inside the library's loop (hd_sample_path), then the final decode of `sample_from_masks`.  `eta` defaults to
@@ -1310,8 +1352,8 @@ class DiffusionQM9(_Base):
         steps and T + 1 for the decode at (self.seed, sample_id_base + row) - plain sampling's layout, so t_start = T on the identity
         path is `sample_from_masks(z_init=z)` bit for bit; `raw_noises` instead injects K + 1 pairs (the K transitions, the decode).
         `t_start` sets how far variations drift from the lead; which t_start, K and eta are chemically useful is for the user to
-        validate on a trained checkpoint."""
-        _, path, _ = self._latent_path(t_start, steps, eta, spacing, timesteps)
+        validate on a trained checkpoint.  solver / lower_order_final: as in `sample_from_masks` ("dpm2m": second order, eta = 0)."""
+        _, path, _ = self._latent_path(t_start, steps, eta, spacing, timesteps, solver, lower_order_final)
         K = len(path) - 1
         if raw_noises is not None and len(raw_noises) != K + 1:
             raise ValueError(f"raw_noises must hold {K} + 1 (randn_x, randn_h) pairs: the transitions, then the decode")
@@ -1320,7 +1362,8 @@ class DiffusionQM9(_Base):
                               int(node_mask.shape[1]) if node_mask.dim() == 3 else None, "sample_from_latent", needs_noise=raw_noises is None)
         z0 = self.latent_steps(z, node_mask, edge_mask, context, t_start=t_start, steps=steps, eta=eta, spacing=spacing,
                                timesteps=timesteps, sample_id_base=sample_id_base, fix_noise=fix_noise,
-                               raw_noises=None if raw_noises is None else raw_noises[:K], guidance_scale=guidance_scale, guidance_context=guidance_context, guidance_rescale=guidance_rescale)
+                               raw_noises=None if raw_noises is None else raw_noises[:K], guidance_scale=guidance_scale, guidance_context=guidance_context, guidance_rescale=guidance_rescale,
+                               solver=solver, lower_order_final=lower_order_final)
         B, N = z0.shape[0], z0.shape[1]
         dev = z0.device
         node_mask = node_mask.to(dev)
@@ -1372,24 +1415,26 @@ class DiffusionQM9(_Base):
              sample_id_base: int = 0, **few):
         """Variations of given molecules (the SDEdit idea): every molecule of `samples` (the sampler's result format, as `score`
         takes it) is noised to the grid index `t_start` (`diffuse`) and the reverse chain runs from there (`sample_from_latent`;
-        keywords steps / eta / spacing / timesteps).  Returns `n_variants` results per input in the same format, input-major; variant
+        keywords steps / eta / spacing / timesteps / solver / lower_order_final).  Returns `n_variants` results per input in the same format, input-major; variant
         v of input i runs under the sample id sample_id_base + i * n_variants + v, so it does not depend on the batch it ran in.
         guidance_scale (a float, or one scale per result, input-major) / guidance_rescale: classifier-free guidance of the reverse
         chain as in `sample_from_masks`, under the model's `null_context`.
         Mechanism only: how far which t_start drifts, and whether the analogues are chemically useful, is for the user to validate."""
         from . import scoring
         device = torch.device(device)
-        extra = set(few) - {"steps", "eta", "spacing", "timesteps", "guidance_scale", "guidance_context", "guidance_rescale"}
+        extra = set(few) - {"steps", "eta", "spacing", "timesteps", "guidance_scale", "guidance_context", "guidance_rescale", "solver",
+                            "lower_order_final"}
         if extra:
             raise ValueError(f"vary: unsupported keyword(s) {sorted(extra)} (steps, eta, spacing, timesteps, guidance_scale, "
-                             "guidance_context, guidance_rescale)")
+                             "guidance_context, guidance_rescale, solver, lower_order_final)")
         from . import guidance
         gscale, gctx = few.pop("guidance_scale", None), few.pop("guidance_context", None)
         few["guidance_rescale"] = few.get("guidance_rescale", None)
         if gctx is not None:
             raise ValueError("vary: guidance_context is not supported (the list form pads its own batches): set the model's null_context")
         gd_all = guidance.resolve(self, gscale, None, few["guidance_rescale"], None, None, "vary")
-        self._latent_path(t_start, few.get("steps"), few.get("eta"), few.get("spacing"), few.get("timesteps"))    # argument errors first
+        self._latent_path(t_start, few.get("steps"), few.get("eta"), few.get("spacing"), few.get("timesteps"), few.get("solver"),
+                          few.get("lower_order_final"))                                                            # argument errors first
         for name, v in (("n_variants", n_variants), ("batch_size", batch_size)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
                 raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
@@ -1453,7 +1498,7 @@ class DiffusionQM9(_Base):
             w = torch.tensor(lam, dtype=torch.float32).view(L, 1, 1)
             ctx_f = ((1.0 - w) * ctx[0:1] + w * ctx[1:2]).contiguous()
         xf, hf = self.sample_from_latent(zf, nm_f, None, None if ctx_f is None else ctx_f.to(device), t_start=t_end_i, steps=steps,
-                                         eta=0.0, spacing=spacing, fix_noise=True)
+                                         eta=0.0, spacing=spacing, fix_noise=True, solver="ddim")
         xf, hf = xf.cpu(), hf.cpu()
         n = int(nm[0].sum())
         out = []
@@ -1509,7 +1554,7 @@ class DiffusionQM9(_Base):
             raise NotImplementedError("inpainting: mode 'gnn_dynamics' is not supported")
         if self.noise_mode == "torch":
             raise NotImplementedError("inpainting: noise_mode 'torch' is not supported (counter-based noise only)")
-        pe = self._resolve_path(*path_args, inpaint=True)
+        pe = self._resolve_path(*path_args[:4], inpaint=True, solver=path_args[4] if len(path_args) > 4 else None)
         gd = None
         if guide_args is not None:
             from . import guidance, paths
@@ -1567,7 +1612,8 @@ class DiffusionQM9(_Base):
     def sample_inpaint(self, node_mask: torch.Tensor, fixed_mask: torch.Tensor, x_known: torch.Tensor, h_known: torch.Tensor,
                        context=None, resamplings: int = 1, sample_id_base: int = 0, edge_mask: Optional[torch.Tensor] = None, *,
                        steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
-                       timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
+                       timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
+                       solver: Optional[str] = None):
         """(x, h) on the device for molecules whose `fixed_mask` [B,N,1] nodes are known: `x_known` [B,N,3] / `h_known` [B,N,F] in
         data units (what `sample` returns; rows outside `fixed_mask` are ignored, the frame of the positions is free).  The free
         nodes are sampled around them by the replacement method, `resamplings` network calls per step (RePaint for > 1), inside
@@ -1576,9 +1622,11 @@ class DiffusionQM9(_Base):
         known one depends on the model and on `resamplings`.  A sample depends on its global id (sample_id_base + row), its
         masks, the weights and its known values only.  steps / spacing / timesteps: few-step sampling as in `sample_from_masks`
         (hd_sample_path_inpaint), ancestral steps only - eta < 1 raises ValueError.  guidance_scale / guidance_context /
-        guidance_rescale: classifier-free guidance as in `sample_from_masks` (every round's network call is guided)."""
+        guidance_rescale: classifier-free guidance as in `sample_from_masks` (every round's network call is guided).
+        solver="dpm2m" (or the model's `sample_solver`) raises ValueError like eta < 1."""
+        self._resolve_path(steps, eta, spacing, timesteps, inpaint=True, solver=solver)      # the solver's ValueError before any shape check
         st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask,
-                                 (steps, eta, spacing, timesteps), (guidance_scale, guidance_context, guidance_rescale))
+                                 (steps, eta, spacing, timesteps, solver), (guidance_scale, guidance_context, guidance_rescale))
         lib, T, B, N = _lib.load(), self.T, st.B, st.N
         n_loop = T if st.K is None else st.K
         z = torch.empty((B, N, self.n_dims + self.in_node_nf), device=st.dev, dtype=torch.float32)
@@ -1601,13 +1649,14 @@ class DiffusionQM9(_Base):
     @torch.no_grad()
     def sample_grow(self, known: Sequence[Dict[str, torch.Tensor]], sizes, device, context=None, resamplings: int = 1,
                     sample_id_base: int = 0, *, steps: Optional[int] = None, eta: Optional[float] = None,
-                    spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
+                    spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
+                    solver: Optional[str] = None):
         """List-level form of `sample_inpaint` in `sample`'s result format: `known[i]` = {'x': [k_i,3], 'h': [k_i,F]} are the fragments
         molecule i keeps (its first k_i rows in the result; k_i = 0 allowed), `sizes[i]` >= k_i its total number of fragments (one
         integer: that many for every molecule).  `context`: as in `sample`.  Returns [{'x': [n_i,3], 'h': [n_i,F] (, 'context')}] on
         the CPU.  steps / eta / spacing / timesteps: as in `sample_inpaint`."""
         device = torch.device(device)
-        self._resolve_path(steps, eta, spacing, timesteps, inpaint=True)       # argument errors first
+        self._resolve_path(steps, eta, spacing, timesteps, inpaint=True, solver=solver)       # argument errors first
         from . import guidance
         guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, None, None, "sample_grow")
         num = len(known)
@@ -1643,7 +1692,7 @@ class DiffusionQM9(_Base):
                                    sample_id_base=sample_id_base, steps=steps, eta=eta, spacing=spacing, timesteps=timesteps,
                                    guidance_scale=guidance_scale,
                                    guidance_context=None if guidance_context is None else guidance_context.to(device),
-                                   guidance_rescale=guidance_rescale)
+                                   guidance_rescale=guidance_rescale, solver=solver)
         x, h = x.cpu(), h.cpu()
         out = [{'x': x[i, :sizes[i]].clone(), 'h': h[i, :sizes[i]].clone()} for i in range(num)]
         if ctx is not None:
@@ -1654,18 +1703,21 @@ class DiffusionQM9(_Base):
     @torch.no_grad()
     def sample(self, num_samples, device, context=None, pocket_cond=None, sample_id_base: int = 0, *,
                steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
-               timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
+               timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
+               solver: Optional[str] = None, lower_order_final: Optional[bool] = None):
         """diffusion_qm9.py:347-395: list of {'x': [n_i,3], 'h': [n_i,8], ('context': [n_i,1])} on the CPU.
         steps / eta / spacing / timesteps: few-step sampling, see `sample_from_masks`; guidance_scale (a float or a
-        [num_samples] tensor) / guidance_context ([num_samples, n_max, C]) / guidance_rescale: classifier-free guidance, ibid."""
+        [num_samples] tensor) / guidance_context ([num_samples, n_max, C]) / guidance_rescale: classifier-free guidance, ibid.;
+        solver / lower_order_final: "dpm2m" = second-order multistep sampling, ibid."""
         device = torch.device(device)
-        self._resolve_path(steps, eta, spacing, timesteps)                     # argument errors before anything is drawn
+        self._resolve_path(steps, eta, spacing, timesteps, solver=solver, lower_order_final=lower_order_final)     # argument errors before anything is drawn
         from . import guidance
         gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, int(num_samples), None, "sample", pocket_cond)
         if gd is not None and context is None:
             raise ValueError("context required")
         few = {k: v for k, v in dict(steps=steps, eta=eta, spacing=spacing, timesteps=timesteps, guidance_scale=guidance_scale,
-                                     guidance_context=guidance_context, guidance_rescale=guidance_rescale).items() if v is not None}
+                                     guidance_context=guidance_context, guidance_rescale=guidance_rescale, solver=solver,
+                                     lower_order_final=lower_order_final).items() if v is not None}
         sample_n = self.nodes_dist.sample(num_samples)
         pocket = None
         if pocket_cond is not None:
@@ -1713,7 +1765,8 @@ class DiffusionQM9(_Base):
 
     def sample_batches(self, batch_size, num_batches, device, context_range=None, protein_data_all=None,
                        sample_id_base: int = 0, *, steps: Optional[int] = None, eta: Optional[float] = None,
-                       spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None):
+                       spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
+                       solver: Optional[str] = None, lower_order_final: Optional[bool] = None):
         """diffusion_qm9.py:397-436, incl. the protein branch (`protein_data_all`: list of dicts with
         'residue_type', 'coord', 'pocket_name', 'ligand_name').
 
@@ -1727,7 +1780,7 @@ class DiffusionQM9(_Base):
         configurations whose results depend on a batch's padded width (below).  One difference that
         is not a sample's own: the NaN guard (en_dynamics.py:109-111) zeroes the velocity of the whole DEVICE batch."""
         device = torch.device(device)
-        self._resolve_path(steps, eta, spacing, timesteps)                     # few-step sampling (`sample_from_masks`): argument errors first
+        self._resolve_path(steps, eta, spacing, timesteps, solver=solver, lower_order_final=lower_order_final)   # few-step sampling (`sample_from_masks`): argument errors first
         # classifier-free guidance (`sample_from_masks`): guidance_scale may also be a list / tuple of scales cycled per batch the way
         # context_range is; inside a merged device batch it becomes one scale per molecule
         from . import guidance
@@ -1740,8 +1793,8 @@ class DiffusionQM9(_Base):
         g_seq = guidance.batch_scales(gscale, int(num_batches), int(batch_size)) if guidance.is_sequence_scale(gscale) else None
         guidance.resolve(self, gscale if g_seq is None else torch.tensor(g_seq), None, guidance_rescale, None, None, "sample_batches",
                          protein_data_all)
-        few = {k: v for k, v in dict(steps=steps, eta=eta, spacing=spacing, timesteps=timesteps,
-                                     guidance_rescale=guidance_rescale).items() if v is not None}
+        few = {k: v for k, v in dict(steps=steps, eta=eta, spacing=spacing, timesteps=timesteps, guidance_rescale=guidance_rescale,
+                                     solver=solver, lower_order_final=lower_order_final).items() if v is not None}
         if g_seq is None and gscale is not None:
             few["guidance_scale"] = gscale
         # Not merged either: mode 'gnn_dynamics' (torch.randn draws whatever noise_mode says, messages over padded nodes) and
@@ -1803,10 +1856,12 @@ class EnVariationalDiffusion(DiffusionQM9):
 
     @torch.no_grad()
     def sample(self, n_samples, n_nodes, node_mask, edge_mask, context, fix_noise=False, *,  # type: ignore[override]
-               steps=None, eta=None, spacing=None, timesteps=None, guidance_scale=None, guidance_context=None, guidance_rescale=None):
+               steps=None, eta=None, spacing=None, timesteps=None, guidance_scale=None, guidance_context=None, guidance_rescale=None,
+               solver=None, lower_order_final=None):
         assert node_mask.shape[0] == n_samples and node_mask.shape[1] == n_nodes
         x, h = self.sample_from_masks(node_mask, edge_mask, context, fix_noise=fix_noise, steps=steps, eta=eta, spacing=spacing,
-                                      timesteps=timesteps, guidance_scale=guidance_scale, guidance_context=guidance_context, guidance_rescale=guidance_rescale)
+                                      timesteps=timesteps, guidance_scale=guidance_scale, guidance_context=guidance_context, guidance_rescale=guidance_rescale,
+                                      solver=solver, lower_order_final=lower_order_final)
         if self.debug_checks:
             self._check_mean_zero(x, node_mask)
         max_cog = torch.sum(x, dim=1, keepdim=True).abs().max()

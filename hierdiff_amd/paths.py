@@ -12,11 +12,15 @@ retraining and no new network code - only rows of coefficients from the SAME gam
                eta = 0 is the noise-free update), evaluated in float64 and rounded once.  At eta = 1 this is the ancestral update
                algebraically; the ancestral format is kept there so that stride 1 stays bit-identical.
 
-Which K and eta keep sample quality is a property of the trained checkpoint: nothing here can tell.
+  solver="dpm2m"  multistep rows {a, b, c2, p, q} (`multistep_coefficients`): the eta = 0 row plus one correction from the previous
+               transition's data prediction, z_s = (a z_t - b eps) + c2 (x^_k - x^_{k-1}) with x^_k = p z_t - q eps - DPM-Solver++(2M)
+               in data-prediction form, second order in the step of lambda = log(alpha / sigma) at no extra network call.
+
+Which K, eta and solver keep sample quality is a property of the trained checkpoint: nothing here can tell.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -25,6 +29,24 @@ import torch.nn.functional as F
 from .noise_model import step_coefficients
 
 SPACINGS = ("uniform", "quadratic")
+SOLVERS = (None, "ddim", "dpm2m")
+
+
+class Multistep(NamedTuple):
+    """What travels in the place of `eta` when the second-order multistep solver is asked for (`check_solver`)."""
+    lower_order_final: bool = True
+
+
+def check_solver(solver, eta=None, lower_order_final=True) -> Optional[Multistep]:
+    """None for the first-order code path (solver None or "ddim"), else the `Multistep` of "dpm2m", which takes no noise on the
+    path: an explicit eta other than 0 is a ValueError."""
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    if solver != "dpm2m":
+        return None
+    if eta is not None and check_eta(eta) != 0.0:
+        raise ValueError(f"solver 'dpm2m' is deterministic (eta = 0), got eta = {eta!r}")
+    return Multistep(bool(lower_order_final))
 
 
 def _check_T_K(T, K) -> "tuple[int, int]":
@@ -116,14 +138,48 @@ def linear_coefficients(gamma_s: torch.Tensor, gamma_t: torch.Tensor, eta: float
     return torch.stack([a, b, sig, rest], dim=1)
 
 
+def multistep_coefficients(gamma: torch.Tensor, path: Sequence[int], lower_order_final: bool = True) -> torch.Tensor:
+    """[K, 5] float64 rows {a, b, c2, p, q} of the DPM-Solver++(2M) update along a descending `path` through the gamma grid:
+        x^_k = p z_t - q eps,   z_s = (a z_t - b eps) + c2 (x^_k - x^_{k-1}),
+    a, b the eta = 0 row of `linear_coefficients`, p = 1 / alpha_t, q = sigma_t / alpha_t and, with lambda = -gamma / 2 and
+    h_k = lambda_s - lambda_t, r_k = h_{k-1} / h_k, c2 = alpha_s (-expm1(-h_k)) / (2 r_k); c2 = 0 on the first transition (no history)
+    and, with `lower_order_final`, on the last.  ValueError unless every h_k > 0 (gamma strictly increasing along the path upwards).
+    Round to fp32 once, where the rows are uploaded."""
+    idx = torch.as_tensor([int(v) for v in path], dtype=torch.int64)
+    if idx.numel() < 2:
+        raise ValueError("a path holds at least one transition")
+    g = torch.as_tensor(gamma).reshape(-1).to(torch.float64)
+    gt, gs = g[idx[:-1]], g[idx[1:]]
+    hk = (gt - gs) / 2
+    if not bool((hk > 0).all()):
+        raise ValueError("solver 'dpm2m' needs a gamma grid that increases strictly along the path (some step of "
+                         "lambda = log(alpha / sigma) is <= 0)")
+    lin = linear_coefficients(gs, gt, 0.0)
+    alpha_s, alpha_t = torch.sqrt(torch.sigmoid(-gs)), torch.sqrt(torch.sigmoid(-gt))
+    c2 = torch.zeros_like(hk)
+    c2[1:] = alpha_s[1:] * (-torch.expm1(-hk[1:])) / (2 * (hk[:-1] / hk[1:]))
+    if lower_order_final:
+        c2[-1] = 0.0
+    return torch.stack([lin[:, 0], lin[:, 1], c2, 1.0 / alpha_t, torch.sqrt(torch.sigmoid(gt)) / alpha_t], dim=1)
+
+
 @torch.no_grad()
-def path_tables(gamma: torch.Tensor, path: Sequence[int], eta: float = 1.0) -> Dict[str, object]:
+def path_tables(gamma: torch.Tensor, path: Sequence[int], eta: Optional[float] = None, solver: Optional[str] = None,
+                lower_order_final: bool = True) -> Dict[str, object]:
     """Rows of a path from the gamma grid [T+1] (fp32, `schedule_tables(...)["gamma"]`): t_idx / s_idx int32 [K], coef fp32 [K,4],
-    form (0 ancestral rows, 1 linear rows) and, for eta = 1, the inpainting rows {alpha_s, sigma_s, alpha_t|s, sigma_t|s}."""
-    eta = check_eta(eta)
+    form (0 ancestral rows, 1 linear rows) and, for eta = 1, the inpainting rows {alpha_s, sigma_s, alpha_t|s, sigma_t|s}.
+    solver="dpm2m" (`eta` may also be a `Multistep`): form 2, coef fp32 [K,5] = `multistep_coefficients`, whose a and b are the
+    fp32 values of the eta = 0 rows.  eta None: 1 (ancestral), or 0 with "dpm2m"."""
+    ms = eta if isinstance(eta, Multistep) else check_solver(solver, eta, lower_order_final)
     g = torch.as_tensor(gamma, dtype=torch.float32).reshape(-1, 1)
     idx = torch.as_tensor(list(path), dtype=torch.int64)
     t_idx, s_idx = idx[:-1], idx[1:]
+    if ms is not None:
+        coef = multistep_coefficients(g, path, ms.lower_order_final).to(torch.float32).contiguous()
+        return {"t_idx": t_idx.to(torch.int32).contiguous(), "s_idx": s_idx.to(torch.int32).contiguous(), "coef": coef, "form": 2,
+                "coef_inpaint": None, "K": int(t_idx.numel()), "eta": 0.0, "solver": "dpm2m",
+                "lower_order_final": ms.lower_order_final}
+    eta = check_eta(1.0 if eta is None else eta)
     if eta == 1.0:
         # evaluated in ascending s like the plain table (torch's vectorised CPU kernels may round an element differently at
         # another position of the array): for the identity path this IS the call `schedule_tables` makes, so the bits agree

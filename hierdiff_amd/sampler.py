@@ -16,7 +16,7 @@ first.  Single process only.
 
 Editing given molecules (no reference counterpart; mechanism only - which settings are chemically useful is for you to validate):
 `--vary FILE --t-start S [--variants V]` noises every molecule of FILE to the grid index S and runs the reverse chain from there
-(`DiffusionQM9.vary`; combines with --steps / --eta / --spacing, which then spread over the S steps below the start);
+(`DiffusionQM9.vary`; combines with --steps / --eta / --spacing / --solver, which then spread over the S steps below the start);
 `--interpolate FILE --frames L` encodes consecutive molecules of FILE to their latents, interpolates on the sphere and decodes L
 frames per pair (`DiffusionQM9.interpolate`; --steps / --spacing apply to both directions; pairs of unequal size are skipped with a
 note).  Output: the same pickle format.  Single process only.
@@ -133,6 +133,13 @@ def read_known(path: str) -> List[dict]:
     return obj
 
 
+class _DefaultEta(float):
+    """The default of --eta, told apart from an explicit `--eta 1` by identity (--solver dpm2m defaults to eta = 0)."""
+
+
+_ETA_DEFAULT = _DefaultEta(1.0)
+
+
 def parse_args(argv=None):
     """The command line, checked: every argument error ends here (SystemExit), before a device is opened."""
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
@@ -163,9 +170,15 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=None,
                     help="few-step sampling: K <= timesteps transitions on a sub-sequence of the trained grid (default: all of "
                          "them); combinable with --known/--grow.  Mechanism only: which K keeps sample quality is for you to validate")
-    ap.add_argument("--eta", type=float, default=1.0,
+    ap.add_argument("--eta", type=float, default=_ETA_DEFAULT,
                     help="1: ancestral steps (default); 0 <= eta < 1: DDIM-family update, 0 = noise-free (not with --known)")
     ap.add_argument("--spacing", choices=["uniform", "quadratic"], default="uniform", help="how --steps spreads over the grid")
+    ap.add_argument("--solver", choices=["ddim", "dpm2m"], default=None,
+                    help="dpm2m: second-order multistep sampling (DPM-Solver++ 2M) on the --steps path, deterministic (eta = 0) at no "
+                         "extra network call; combines with --steps / --spacing, --guidance and --vary, not with --known / --grow or "
+                         "--eta other than 0.  Mechanism only: which K keeps sample quality is for you to validate")
+    ap.add_argument("--no-lower-order-final", dest="lower_order_final", action="store_false",
+                    help="with --solver dpm2m: keep the second-order correction on the last transition too")
     ap.add_argument("--score", default=None, metavar="FILE",
                     help="score the molecules of FILE (a sample_results.pkl or a bare list in the sampler's output format) instead of "
                          "sampling: the variational bound with every timestep evaluated, one value per molecule, written to --out.  "
@@ -225,6 +238,17 @@ def parse_args(argv=None):
         args.out = "scores.pkl" if args.score is not None else "sample_results.pkl"
     if args.steps is not None and args.steps < 1:
         ap.error("--steps must be >= 1")
+    if not args.lower_order_final and args.solver != "dpm2m":
+        ap.error("--no-lower-order-final needs --solver dpm2m")
+    if args.solver == "dpm2m":
+        if args.known is not None or args.grow is not None:
+            ap.error("--solver dpm2m does not combine with --known / --grow (inpainting takes ancestral steps)")
+        if args.score is not None or args.interpolate is not None:
+            ap.error("--solver dpm2m does not combine with --score / --interpolate")
+        if args.eta is not _ETA_DEFAULT and args.eta != 0.0:
+            ap.error("--solver dpm2m is deterministic: --eta must be 0 (or left out)")
+        args.eta = 0.0
+    args.eta = float(args.eta)
     if not (0.0 <= args.eta <= 1.0):
         ap.error("--eta must be in [0, 1]")
     if args.known is not None and args.eta < 1.0:
@@ -267,6 +291,8 @@ def main(argv=None) -> int:
     if args.steps is not None and args.steps > model.T:
         raise SystemExit(f"--steps {args.steps} exceeds the model's {model.T} timesteps")
     model.sample_steps, model.sample_eta, model.sample_spacing = args.steps, args.eta, args.spacing
+    if args.solver == "dpm2m":
+        model.sample_solver, model.sample_lower_order_final = "dpm2m", args.lower_order_final
     if args.guidance is not None:
         model.guidance_scale, model.guidance_rescale = args.guidance, args.guidance_rescale
         if args.null_context is not None:

@@ -306,6 +306,28 @@ int hd_sample_path_guided(hd_handle* h, hd_topology* topo, float* z, const float
 /* Number of times the topology's captured guided transition was instantiated (-1: null topology). */
 long long hd_guided_graph_builds(const hd_topology* topo);
 
+/* ---- Second-order multistep sampling (ABI 12, additive; no reference counterpart): DPM-Solver++(2M) in data-prediction form on a
+ * descending path.  With lambda = log(alpha / sigma) = -gamma / 2, h_k = lambda_s - lambda_t of transition k and r_k = h_{k-1} / h_k:
+ *     x^_k = p z_t - q eps,        z_s = (a z_t - b eps) + c2 (x^_k - x^_{k-1}),
+ *     a = alpha_s / alpha_t,  b = a sigma_t - sigma_s  (the eta = 0 row of hd_set_path),  p = 1 / alpha_t,  q = sigma_t / alpha_t,
+ *     c2 = alpha_s (-expm1(-h_k)) / (2 r_k),
+ * eps with its x part mean-removed and z_s re-centred as in the plain step.  A row with c2 == 0 reads no history and gives the bits
+ * of the eta = 0 row {a, b, 0, 0}; nothing is drawn on the path.
+ * hd_set_path_multistep: hd_set_path with host rows5 = K rows {a, b, c2, p, q} (form 2).  Validated like hd_set_path (descending,
+ * chained, K <= T, schedule set); c2 of row 0 must be 0 (HD_E_INVALID).  hd_sample_path and hd_sample_path_guided (fixed_mask == NULL)
+ * then run the path, with and without use_graph (one captured transition per topology, the row read through the device-side path
+ * position); hd_sample_path_inpaint and guided calls with a fixed_mask are HD_E_INVALID.  Injected normals are not read.
+ *   history   x^_{k-1} lives in a topology-owned buffer [B,N,D] (allocated by the first such call).  The topology remembers which
+ *             path (every hd_set_path* call starts a new one) and which position k_hi its history belongs to: a call whose first row
+ *             has c2 != 0 must have k_lo equal to that position on the same path, HD_E_STATE otherwise.  A call starting on a row
+ *             with c2 == 0 (k_lo = 0) needs none. */
+int hd_set_path_multistep(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* rows5);
+/* The single update: x_out[B,N,D] = x^_k (masked entries 0) and zs[B,N,D] = z_s from zt, eps [B,N,D] (device) and the HOST row
+ * row5 = {a, b, c2, p, q}.  x_prev [B,N,D] is x^_{k-1}; it may be NULL when c2 == 0 and is not read then.  zs may be zt and x_out may
+ * be x_prev; any other overlap is HD_E_INVALID, as is N * D floats beyond one workgroup's LDS (64 KiB).  Stream-ordered. */
+int hd_multistep_step(hd_handle* h, hd_topology* topo, const float* zt, const float* eps, const float* row5, const float* x_prev,
+                      float* x_out, float* zs, void* stream);
+
 /* ---- Scoring (ABI 12, additive; no reference counterpart beyond the one-timestep estimator, compute_loss with t0_always = True,
  * diffusion_qm9.py:530-699): the variational bound of GIVEN molecules with every term of a list evaluated, in the device loop.
  * For normalised data xh [B,N,D] and a term t in 1 .. T (s = t - 1):
