@@ -4,6 +4,7 @@
 #include "kernels.hpp"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -205,25 +206,25 @@ struct hd_topology {
     float *hbuf, *AB, *AB2, *Tb, *agg, *x0, *xcur, *part, *xpart, *eps;
     float *abmax, *abmax2;                     // fp16x3: [M_pad][2] row maxima of the AB / AB2 buffers
     float *rowinfo;                            // fp16x3, split node chain: [M_pad][2] {max |h_r|, max |[h | agg]_r|} (k_node_split.hpp)
-    // hd_sample_loop with use_graph: the captured step works on library-owned copies of z / context so that the
-    // instantiated graph survives across calls (the caller's tensors move); one graph per topology
+    // use_graph: every device loop keeps ONE captured step / transition / term here - a slot, the key it was built for and,
+    // where the ABI reports it, a count of instantiations - and replays it once per step through the replay scaffold ("sampling
+    // maths" below; graph_slots lists the slots).  The captured body works on library-owned copies of the caller's tensors so
+    // that the instantiated graph survives across calls (the caller's tensors move); each loop allocates its copies on first use.
+    // hd_sample_loop: z / context
     float *zbuf, *ctxbuf;
     hipGraphExec_t gexec;
     GraphKey gkey;
-    // hd_sample_loop_inpaint with use_graph: its own captured step, and library-owned copies of the fixed mask / known values
-    // (allocated by the first such call)
+    // hd_sample_loop_inpaint: the fixed mask / known values
     hipGraphExec_t gexec_ip;
     InpaintKey ikey;
     uint8_t* ip_fixed;
     float* ip_known;
-    // hd_sample_path / hd_sample_path_inpaint with use_graph: ONE captured transition (whatever the path's length), replayed
-    // once per transition; `path_builds` counts its instantiations (hd_path_graph_builds)
+    // hd_sample_path / hd_sample_path_inpaint (hd_path_graph_builds)
     hipGraphExec_t gexec_path;
     PathKey pkey;
     long long path_builds;
     // hd_sample_path_guided: the second network output, and for the captured guided transition - a graph of its own next to the
-    // unguided one - library-owned copies of the null context and the scales (one allocation, made by the first guided call);
-    // `guided_builds` counts the instantiations (hd_guided_graph_builds)
+    // unguided one - the null context and the scales (one allocation, made by the first guided call; hd_guided_graph_builds)
     hipGraphExec_t gexec_guided;
     PathKey gdkey;
     long long guided_builds;
@@ -233,8 +234,8 @@ struct hd_topology {
     float* ms_hist;
     unsigned long long ms_gen;                 // 0: no history
     int ms_k;
-    // hd_nll_terms / hd_nll_finish: eps_t and, for the captured term, library-owned copies of xh / the accumulator / the e_t table
-    // (allocated by the first such call; z_t lives in zbuf); `nll_builds` counts the instantiations (hd_nll_graph_builds)
+    // hd_nll_terms / hd_nll_finish: eps_t and, for the captured term, xh / the accumulator / the e_t table (z_t lives in zbuf;
+    // hd_nll_graph_builds)
     hipGraphExec_t gexec_nll;
     NllKey nkey;
     long long nll_builds;
@@ -771,28 +772,34 @@ extern "C" int hd_arena_pool_trim(void) {
     return HD_OK;
 }
 
+// the graph slots of a topology, one per captured loop, and the one way a slot's graph goes (replay scaffold, "sampling maths")
+static std::array<hipGraphExec_t*, 5> graph_slots(hd_topology* t) {
+    return {&t->gexec, &t->gexec_ip, &t->gexec_path, &t->gexec_guided, &t->gexec_nll};
+}
+static void graph_drop(hipGraphExec_t* gx) {
+    if (*gx) hipGraphExecDestroy(*gx);
+    *gx = nullptr;
+}
+
 extern "C" int hd_topology_destroy(hd_topology* t) {
     if (!t) return HD_OK;
     (void)hipSetDevice(t->device);
     ArenaSlot sl{t->device, t->arena, t->arena_bytes, t->staging, t->staging_bytes, nullptr};
     // a captured graph, or launches on several streams: wait for the device (the rare case - a sampling topology lives as
     // long as its model); otherwise an event behind the topology's last work guards the arena's next owner
-    bool pooled = t->arena && !t->gexec && !t->gexec_ip && !t->gexec_path && !t->gexec_guided && !t->gexec_nll && !t->multi_stream;
+    bool pooled = t->arena && !t->multi_stream;
+    for (hipGraphExec_t* gx : graph_slots(t)) pooled = pooled && !*gx;
     if (pooled && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) == hipSuccess) {
         if (hipEventRecord(sl.done, t->last_stream) != hipSuccess) { (void)hipEventDestroy(sl.done); sl.done = nullptr; pooled = false; }
     } else {
         pooled = false;
     }
     if (!pooled) (void)hipDeviceSynchronize();
-    if (t->gexec) hipGraphExecDestroy(t->gexec);
-    if (t->gexec_ip) hipGraphExecDestroy(t->gexec_ip);
-    if (t->gexec_path) hipGraphExecDestroy(t->gexec_path);
-    if (t->gexec_guided) hipGraphExecDestroy(t->gexec_guided);
+    for (hipGraphExec_t* gx : graph_slots(t)) graph_drop(gx);
     if (t->guide_mem) (void)hipFree(t->guide_mem);
     if (t->ms_hist) (void)hipFree(t->ms_hist);
     if (t->ip_fixed) (void)hipFree(t->ip_fixed);
     if (t->ip_known) (void)hipFree(t->ip_known);
-    if (t->gexec_nll) hipGraphExecDestroy(t->gexec_nll);
     if (t->nll_eps) (void)hipFree(t->nll_eps);
     if (t->nll_xh) (void)hipFree(t->nll_xh);
     if (t->nll_err) (void)hipFree(t->nll_err);
@@ -2706,6 +2713,117 @@ extern "C" int hd_set_schedule(hd_handle* h, int T, const float* tau, const floa
     return HD_OK;
 }
 
+// ----------------------------------------------------------------------------- the replay scaffold of the captured loops
+//
+// Every device loop (hd_sample_loop, hd_sample_loop_inpaint, the path loops, hd_nll_terms) has the same two halves.  Plain
+// launches: the host walks the steps and passes position, draw and sample base by value.  use_graph: ONE step is captured into a
+// hipGraph that reads them from the handle's device words, works on library-owned copies of every tensor (the caller's move
+// between calls) and is kept in a slot of the topology until something in its key changes.  A loop's own part is its key, its slot
+// and build counter, its staging copies, its state kernel and the emitter of its body; the order of a replaying call is
+//     replay_enter -> (grow / allocate owned buffers) -> replay_evict -> replay_capture -> staging copies, state kernel
+//                  -> replay_run -> copy back -> replay_leave
+// No host synchronisation on the way unless a stale graph or buffer has to go: the caller's stream is ordered against the replay
+// stream with events.  Everything a body emits is a kernel node.
+
+// What an emitted step / transition / term works on.  Plain launches: the caller's tensors, and host values for the position
+// (`row`, `ro`), the draw and the first sample id.  The captured body: the library-owned copies, the handle's device words, and 0
+// for the host values (loop_io_captured).  Fields a loop does not use stay null.
+struct LoopIO {
+    float* z;
+    const float *ctx, *tcur;                   // context; network time: a row of d_tau, or the d_tcur word
+    const float *ctx_u, *w;                    // guidance: second context, scales
+    const uint8_t* fixed;                      // inpainting: mask, known values
+    const float* known;
+    const float* xh;                           // scoring: data, accumulator, e_t table
+    double* acc;
+    float* err;
+    int row;                                   // row of the loop's coefficient table
+    size_t ro;                                 // injected noise: molecule rows before this position's
+    uint32_t draw;
+    uint64_t base;
+    const int* step;                           // device words (null: plain launches)
+    const uint32_t* draw_w;
+    const unsigned long long* base_w;
+    hipStream_t s;
+};
+
+static LoopIO loop_io_captured(const hd_handle* h, const uint32_t* draw_w, hipStream_t rs) {
+    LoopIO io{};
+    io.tcur = h->d_tcur; io.step = h->d_step; io.draw_w = draw_w; io.base_w = h->d_base; io.s = rs;
+    return io;
+}
+
+// The replay stream (the legacy NULL stream cannot be captured: the handle's own stream stands in, ordered behind it), made to
+// wait for the handle's latest replay.  The replay state (d_step, d_draw, d_tcur, d_base, d_ipdraw) belongs to the handle: a replay
+// issued on another stream - another topology of this handle, or the same one from another caller stream - must have finished
+// before this one touches it.
+static int replay_enter(hd_handle* h, hipStream_t s, hipStream_t* rs) {
+    *rs = s;
+    if (s == nullptr) {
+        if (!h->own_stream) HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+        *rs = h->own_stream;
+        HIP_TRY(hipEventRecord(h->ev_in, s));
+        HIP_TRY(hipStreamWaitEvent(*rs, h->ev_in, 0));
+    }
+    if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(*rs, h->ev_last, 0));
+    return HD_OK;
+}
+
+// host wait before something a captured graph holds is freed: a replay may still be running, on any stream
+static int replay_quiesce(hd_handle* h, hipStream_t rs) {
+    if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
+    HIP_TRY(hipStreamSynchronize(rs));
+    return HD_OK;
+}
+
+// drop the slot's graph when it was built for another key
+template <typename Key>
+static int replay_evict(hd_handle* h, hipStream_t rs, hipGraphExec_t* gx, const Key& have, const Key& want) {
+    if (!*gx || have == want) return HD_OK;
+    HD_TRY(replay_quiesce(h, rs));
+    graph_drop(gx);
+    return HD_OK;
+}
+
+// Capture what `body` emits on rs (an int() callable: kernel launches only, profiling brackets off) and instantiate it into the slot.
+template <typename Body>
+static int replay_capture(hd_handle* h, hipStream_t rs, hipGraphExec_t* gx, Body body) {
+    hipGraph_t graph = nullptr;
+    HIP_TRY(hipStreamBeginCapture(rs, hipStreamCaptureModeThreadLocal));
+    const int was_prof = h->prof;
+    h->prof = 0;
+    const int rc = body();
+    const hipError_t ce = hipStreamEndCapture(rs, &graph);
+    h->prof = was_prof;
+    if (rc != HD_OK) { if (graph) hipGraphDestroy(graph); return rc; }
+    if (ce != hipSuccess) return fail(HD_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
+    const hipError_t ie = hipGraphInstantiate(gx, graph, nullptr, nullptr, 0);
+    hipGraphDestroy(graph);
+    if (ie != hipSuccess) { *gx = nullptr; return fail(HD_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+    return HD_OK;
+}
+
+static int replay_run(hipGraphExec_t gx, int n, hipStream_t rs) {
+    for (int k = 0; k < n; ++k) {
+        const hipError_t le = hipGraphLaunch(gx, rs);
+        if (le != hipSuccess) return fail(HD_E_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(le));
+    }
+    return HD_OK;
+}
+
+// mark the end of this replay for the handle's next one, and hand back to the caller's stream
+static int replay_leave(hd_handle* h, hipStream_t s, hipStream_t rs) {
+    HIP_TRY(hipEventRecord(h->ev_last, rs));
+    h->ev_last_set = true;
+    if (rs != s) {
+        HIP_TRY(hipEventRecord(h->ev_out, rs));
+        HIP_TRY(hipStreamWaitEvent(s, h->ev_out, 0));
+    }
+    return HD_OK;
+}
+
+// ----------------------------------------------------------------------------- the every-step loop
+
 extern "C" int hd_sample_loop(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
                               int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
                               uint64_t seed, uint64_t sample_id_base, int use_graph, void* stream) {
@@ -2726,81 +2844,49 @@ extern "C" int hd_sample_loop(hd_handle* h, hd_topology* topo, float* z, const f
     const int T = h->T;
     const uint32_t draw0 = (uint32_t)(T - (s_hi - 1));       // draw index of the first step (draw 0 = z_T)
     const int share = (noise_rows == 1) ? 1 : 0;
+    auto step = [&](const LoopIO& io) -> int {
+        HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx, mol_shape < 0 ? -1 : mol, topo->eps, io.s));
+        NoiseSrc ns = make_noise(raw_x ? raw_x + io.ro * 3 : nullptr, raw_h ? raw_h + io.ro * h->F : nullptr, noise_rows, seed,
+                                 io.base, io.draw, share);
+        return step_impl(h, topo, io.z, topo->eps, h->d_coef + (size_t)io.row * 4, 1, ns, mol, io.z, topo->N, io.step, io.draw_w,
+                         io.step ? draw0 : 0, io.s, io.base_w);
+    };
     if (!use_graph) {
+        LoopIO io{};
+        io.z = z; io.ctx = context; io.base = sample_id_base; io.s = s;
         for (int k = 0; k < nsteps; ++k) {
-            const int sidx = s_hi - 1 - k;
-            HD_TRY(forward_impl(h, topo, z, h->d_tau + sidx + 1, 1, context, mol_shape < 0 ? -1 : mol, topo->eps, s));
-            NoiseSrc ns = make_noise(raw_x ? raw_x + (size_t)k * noise_rows * mol * 3 : nullptr,
-                                     raw_h ? raw_h + (size_t)k * noise_rows * mol * h->F : nullptr, noise_rows, seed,
-                                     sample_id_base, draw0 + (uint32_t)k, share);
-            HD_TRY(step_impl(h, topo, z, topo->eps, h->d_coef + (size_t)sidx * 4, 1, ns, mol, z, topo->N, nullptr, nullptr, 0, s));
+            io.row = s_hi - 1 - k; io.tcur = h->d_tau + io.row + 1;
+            io.ro = (size_t)k * noise_rows * mol; io.draw = draw0 + (uint32_t)k;
+            HD_TRY(step(io));
         }
         return HD_OK;
     }
-    // hipGraph: one captured step whose step index / draw / time / sample base live in device memory, replayed
-    // nsteps times.  The instantiated graph is kept with the topology and reused by later calls (it works on
-    // library-owned copies of z and context, so nothing it has baked in moves between calls); it is rebuilt only when
-    // something in GraphKey changes.  No host synchronisation anywhere: the caller's stream is ordered against the
-    // replay stream with events.
+    // Rebuilt only when something in GraphKey changes.
     const size_t zbytes = (size_t)topo->B * topo->N * h->D * sizeof(float);
     const size_t cbytes = (size_t)topo->B * topo->N * h->cfg.context_node_nf * sizeof(float);
-    hipStream_t rs = s;
-    if (s == nullptr) {                                  // the legacy NULL stream cannot be captured
-        if (!h->own_stream) HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-        rs = h->own_stream;
-        HIP_TRY(hipEventRecord(h->ev_in, s));
-        HIP_TRY(hipStreamWaitEvent(rs, h->ev_in, 0));
-    }
+    hipStream_t rs;
+    HD_TRY(replay_enter(h, s, &rs));
     GraphKey key;
     key.raw_x = raw_x; key.raw_h = raw_h; key.has_ctx = context ? 1 : 0; key.mol_shape = mol_shape < 0 ? -1 : mol;
     key.noise_rows = noise_rows; key.T = T; key.s_hi = raw_x ? s_hi : 0; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
-    // The replay state (d_step, d_draw, d_tcur, d_base) belongs to the handle: a replay issued on another stream - another
-    // topology of this handle, or the same one from another caller stream - must have finished before this one touches it.
-    if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(rs, h->ev_last, 0));
-    if (topo->gexec && !(topo->gkey == key)) {
-        if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));   // a replay of the stale graph may still be running, on any stream
-        HIP_TRY(hipStreamSynchronize(rs));
-        hipGraphExecDestroy(topo->gexec);
-        topo->gexec = nullptr;
-    }
+    HD_TRY(replay_evict(h, rs, &topo->gexec, topo->gkey, key));
     if (!topo->gexec) {
-        const int was_prof = h->prof;
-        h->prof = 0;
-        hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(rs, hipStreamCaptureModeThreadLocal));
-        int rc = forward_impl(h, topo, topo->zbuf, h->d_tcur, 1, context ? topo->ctxbuf : nullptr, mol_shape < 0 ? -1 : mol,
-                              topo->eps, rs);
-        if (rc == HD_OK) {
-            NoiseSrc ns = make_noise(raw_x, raw_h, noise_rows, seed, 0, draw0, share);
-            rc = step_impl(h, topo, topo->zbuf, topo->eps, h->d_coef, 1, ns, mol, topo->zbuf, topo->N, h->d_step, h->d_draw,
-                           draw0, rs, h->d_base);
-        }
-        if (rc == HD_OK) hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, rs, h->d_step, h->d_draw, h->d_tcur, h->d_tau);
-        const hipError_t ce = hipStreamEndCapture(rs, &graph);
-        h->prof = was_prof;
-        if (rc != HD_OK) { if (graph) hipGraphDestroy(graph); return rc; }
-        if (ce != hipSuccess) return fail(HD_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-        const hipError_t ie = hipGraphInstantiate(&topo->gexec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (ie != hipSuccess) { topo->gexec = nullptr; return fail(HD_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+        LoopIO io = loop_io_captured(h, h->d_draw, rs);
+        io.z = topo->zbuf; io.ctx = context ? topo->ctxbuf : nullptr; io.draw = draw0;
+        HD_TRY(replay_capture(h, rs, &topo->gexec, [&]() -> int {
+            HD_TRY(step(io));
+            hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, rs, h->d_step, h->d_draw, h->d_tcur, h->d_tau);
+            return HD_OK;
+        }));
         topo->gkey = key;
     }
     HIP_TRY(hipMemcpyAsync(topo->zbuf, z, zbytes, hipMemcpyDeviceToDevice, rs));
     if (context) HIP_TRY(hipMemcpyAsync(topo->ctxbuf, context, cbytes, hipMemcpyDeviceToDevice, rs));
     hipLaunchKernelGGL(k_loop_state, dim3(1), dim3(1), 0, rs, h->d_step, h->d_draw, h->d_tcur, h->d_base, h->d_tau,
                        s_hi - 1, draw0, (unsigned long long)sample_id_base);
-    for (int k = 0; k < nsteps; ++k) {
-        const hipError_t le = hipGraphLaunch(topo->gexec, rs);
-        if (le != hipSuccess) return fail(HD_E_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(le));
-    }
+    HD_TRY(replay_run(topo->gexec, nsteps, rs));
     HIP_TRY(hipMemcpyAsync(z, topo->zbuf, zbytes, hipMemcpyDeviceToDevice, rs));
-    HIP_TRY(hipEventRecord(h->ev_last, rs));
-    h->ev_last_set = true;
-    if (rs != s) {
-        HIP_TRY(hipEventRecord(h->ev_out, rs));
-        HIP_TRY(hipStreamWaitEvent(s, h->ev_out, 0));
-    }
-    return HD_OK;
+    return replay_leave(h, s, rs);
 }
 
 // ----------------------------------------------------------------------------- fragment-constrained sampling (inpainting)
@@ -2836,27 +2922,79 @@ static int inpaint_launch(hd_handle* h, hd_topology* t, bool jump, float* z, con
     return HD_OK;
 }
 
+// The checks every inpainting loop makes on its arguments, in the order the header documents.  hd_sample_path_guided words two
+// of them its own way, so those texts come from the caller.
+static int inpaint_args_check(const char* who, const hd_handle* h, const hd_topology* topo, const float* raw_x, const float* raw_h,
+                              int noise_rows, int mol_shape, int resamplings, const float* context, const char* raw_msg,
+                              const char* rows_msg) {
+    const std::string w(who);
+    if (raw_x || raw_h) return fail(HD_E_INVALID, w + raw_msg);
+    if (noise_rows != topo->B) return fail(HD_E_INVALID, w + rows_msg);
+    if (mol_shape >= 0 && mol_shape < topo->N) return fail(HD_E_INVALID, w + ": fixed tail rows (mol_shape < N) are not supported");
+    if (resamplings < 1) return fail(HD_E_INVALID, w + ": resamplings must be >= 1");
+    if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, w + ": context required");
+    if (!h->cfg.condition_time) return fail(HD_E_INVALID, w + ": needs a time-conditioned model");
+    if (((unsigned long long)h->T + 2ULL) * 3ULL * (unsigned long long)resamplings > 0xffffffffULL)
+        return fail(HD_E_INVALID, w + ": (T + 2) * 3 * resamplings exceeds the 32-bit draw index");
+    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, w + ": N * D floats exceed one workgroup's LDS");
+    return HD_OK;
+}
+static const char* const kIpRawMsg = ": injected noise is not supported (counter-based generator only)";
+static const char* const kIpRowsMsg = ": noise_rows must be B";
+
+// ... and on the path, before them
+static int inpaint_path_check(const char* who, const hd_handle* h, const char* form_msg) {
+    const std::string w(who);
+    if (h->path_up) return fail(HD_E_INVALID, w + ": the path ascends (hd_set_path_up): inversion fixes no fragments");
+    if (h->path_form != 0) return fail(HD_E_INVALID, w + form_msg);
+    if (!h->d_path_coef_ip) return fail(HD_E_STATE, w + ": the path was set without inpainting rows (hd_set_path)");
+    return HD_OK;
+}
+
+// graph replay: room for the draw words of a step's nd = 3 * resamplings noise streams, and the library-owned mask / known values
+static int grow_ipdraw(hd_handle* h, hipStream_t rs, int nd) {
+    if (nd <= h->ipdraw_cap) return HD_OK;
+    HD_TRY(replay_quiesce(h, rs));                           // graphs that hold the old address go stale (ip_gen)
+    hipFree(h->d_ipdraw);
+    h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
+    HD_TRY(dev_alloc(&h->d_ipdraw, (size_t)nd));
+    h->ipdraw_cap = nd;
+    h->ip_gen++;
+    return HD_OK;
+}
+
+static int inpaint_buffers(const hd_handle* h, hd_topology* t) {
+    const size_t BN = (size_t)t->B * t->N;
+    if (!t->ip_fixed) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->ip_fixed), BN));
+    if (!t->ip_known) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->ip_known), BN * h->D * sizeof(float)));
+    return HD_OK;
+}
+
+// Round j of R behind its posterior step: put the known rows back at the arrival level and - except in the last round - jump back
+// to the departure level.  Noise stream 3 * j + m of `stride` draws: a host draw, or the word io.draw_w[3 * j + m].
+static int inpaint_round(hd_handle* h, hd_topology* t, const LoopIO& io, int j, int R, uint32_t stride, uint64_t seed,
+                         const float* coef_ip = nullptr) {
+    for (int m = 1; m <= (j < R - 1 ? 2 : 1); ++m)
+        HD_TRY(inpaint_launch(h, t, m == 2, io.z, m == 1 ? io.fixed : nullptr, m == 1 ? io.known : nullptr, seed, io.base,
+                              io.step ? 0u : stride * (uint32_t)(3 * j + m) + io.draw, io.row, io.step ? io.draw_w + 3 * j + m : nullptr,
+                              io.step, io.base_w, io.s, coef_ip));
+    return HD_OK;
+}
+
 extern "C" int hd_sample_loop_inpaint(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
                                       int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
                                       uint64_t seed, uint64_t sample_id_base, int use_graph, const uint8_t* fixed_mask,
                                       const float* xh_known, int resamplings, void* stream) {
-    HD_TRY(check_ready(h, topo, "hd_sample_loop_inpaint"));
+    const char* who = "hd_sample_loop_inpaint";
+    HD_TRY(check_ready(h, topo, who));
     if (h->T < 1) return fail(HD_E_STATE, "hd_sample_loop_inpaint: schedule not set (hd_set_schedule)");
     if (!h->d_coef_ip || h->ip_sched_gen != h->sched_gen)
         return fail(HD_E_STATE, "hd_sample_loop_inpaint: inpainting schedule not set for the current schedule (hd_set_inpaint_schedule)");
     if (!z || !fixed_mask || !xh_known) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: null z / fixed_mask / xh_known");
     if (s_hi > h->T || s_lo < 0 || s_lo > s_hi) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: need 0 <= s_lo <= s_hi <= T");
-    if (raw_x || raw_h) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: injected noise is not supported (counter-based generator only)");
-    if (noise_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: noise_rows must be B");
-    if (mol_shape >= 0 && mol_shape < topo->N) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: fixed tail rows (mol_shape < N) are not supported");
-    if (resamplings < 1) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: resamplings must be >= 1");
-    if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: context required");
-    if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: needs a time-conditioned model");
+    HD_TRY(inpaint_args_check(who, h, topo, raw_x, raw_h, noise_rows, mol_shape, resamplings, context, kIpRawMsg, kIpRowsMsg));
     const int T = h->T, R = resamplings, nd = 3 * R;
     const uint32_t stride = (uint32_t)T + 2u;                // draws of one noise stream: 0 .. T + 1
-    if ((unsigned long long)stride * (unsigned long long)nd > 0xffffffffULL)
-        return fail(HD_E_INVALID, "hd_sample_loop_inpaint: (T + 2) * 3 * resamplings exceeds the 32-bit draw index");
-    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: N * D floats exceed one workgroup's LDS");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     const int nsteps = s_hi - s_lo;
@@ -2864,87 +3002,46 @@ extern "C" int hd_sample_loop_inpaint(hd_handle* h, hd_topology* topo, float* z,
     if (nsteps == 0) return HD_OK;
     const int N = topo->N;
     const uint32_t draw0 = (uint32_t)(T - (s_hi - 1));
+    auto step = [&](const LoopIO& io) -> int {               // all R rounds of one step
+        for (int j = 0; j < R; ++j) {
+            HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx, -1, topo->eps, io.s));
+            NoiseSrc ns = make_noise(nullptr, nullptr, noise_rows, seed, io.base, io.step ? 0u : stride * (uint32_t)(3 * j) + io.draw, 0);
+            HD_TRY(step_impl(h, topo, io.z, topo->eps, h->d_coef + (size_t)io.row * 4, 1, ns, N, io.z, N, io.step,
+                             io.step ? io.draw_w + 3 * j : nullptr, 0, io.s, io.base_w));
+            HD_TRY(inpaint_round(h, topo, io, j, R, stride, seed));
+        }
+        return HD_OK;
+    };
     if (!use_graph) {
+        LoopIO io{};
+        io.z = z; io.ctx = context; io.fixed = fixed_mask; io.known = xh_known; io.base = sample_id_base; io.s = s;
         for (int k = 0; k < nsteps; ++k) {
-            const int sidx = s_hi - 1 - k;
-            const uint32_t d = draw0 + (uint32_t)k;
-            for (int j = 0; j < R; ++j) {
-                HD_TRY(forward_impl(h, topo, z, h->d_tau + sidx + 1, 1, context, -1, topo->eps, s));
-                NoiseSrc ns = make_noise(nullptr, nullptr, noise_rows, seed, sample_id_base, stride * (uint32_t)(3 * j) + d, 0);
-                HD_TRY(step_impl(h, topo, z, topo->eps, h->d_coef + (size_t)sidx * 4, 1, ns, N, z, N, nullptr, nullptr, 0, s));
-                HD_TRY(inpaint_launch(h, topo, false, z, fixed_mask, xh_known, seed, sample_id_base, stride * (uint32_t)(3 * j + 1) + d,
-                                      sidx, nullptr, nullptr, nullptr, s));
-                if (j < R - 1)
-                    HD_TRY(inpaint_launch(h, topo, true, z, nullptr, nullptr, seed, sample_id_base, stride * (uint32_t)(3 * j + 2) + d,
-                                          sidx, nullptr, nullptr, nullptr, s));
-            }
+            io.row = s_hi - 1 - k; io.tcur = h->d_tau + io.row + 1; io.draw = draw0 + (uint32_t)k;
+            HD_TRY(step(io));
         }
         return HD_OK;
     }
-    // One captured step - all rounds of it - replayed nsteps times, like hd_sample_loop: step index, time and first sample id in
-    // the handle's device words, the draws of the 3 * R noise streams in d_ipdraw; library-owned copies of every tensor.
+    // The draws of the 3 * R noise streams live in d_ipdraw; the fixed mask and the known values are library-owned copies too.
     const size_t BN = (size_t)topo->B * N;
     const size_t zbytes = BN * h->D * sizeof(float);
     const size_t cbytes = BN * h->cfg.context_node_nf * sizeof(float);
-    hipStream_t rs = s;
-    if (s == nullptr) {
-        if (!h->own_stream) HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-        rs = h->own_stream;
-        HIP_TRY(hipEventRecord(h->ev_in, s));
-        HIP_TRY(hipStreamWaitEvent(rs, h->ev_in, 0));
-    }
-    if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(rs, h->ev_last, 0));
-    if (nd > h->ipdraw_cap) {                                // grow the draw words: graphs that hold the old address go stale (ip_gen)
-        if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
-        HIP_TRY(hipStreamSynchronize(rs));
-        hipFree(h->d_ipdraw);
-        h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
-        HD_TRY(dev_alloc(&h->d_ipdraw, (size_t)nd));
-        h->ipdraw_cap = nd;
-        h->ip_gen++;
-    }
-    if (!topo->ip_fixed) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->ip_fixed), BN));
-    if (!topo->ip_known) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->ip_known), zbytes));
+    hipStream_t rs;
+    HD_TRY(replay_enter(h, s, &rs));
+    HD_TRY(grow_ipdraw(h, rs, nd));
+    HD_TRY(inpaint_buffers(h, topo));
     InpaintKey key;
     key.has_ctx = context ? 1 : 0; key.T = T; key.resamplings = R; key.seed = seed; key.weights_gen = h->weights_gen;
     key.sched_gen = h->sched_gen; key.ip_gen = h->ip_gen;
-    if (topo->gexec_ip && !(topo->ikey == key)) {
-        if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
-        HIP_TRY(hipStreamSynchronize(rs));
-        hipGraphExecDestroy(topo->gexec_ip);
-        topo->gexec_ip = nullptr;
-    }
+    HD_TRY(replay_evict(h, rs, &topo->gexec_ip, topo->ikey, key));
     if (!topo->gexec_ip) {
-        const int was_prof = h->prof;
-        h->prof = 0;
-        hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(rs, hipStreamCaptureModeThreadLocal));
-        int rc = HD_OK;
-        for (int j = 0; j < R && rc == HD_OK; ++j) {
-            rc = forward_impl(h, topo, topo->zbuf, h->d_tcur, 1, context ? topo->ctxbuf : nullptr, -1, topo->eps, rs);
-            if (rc == HD_OK) {
-                NoiseSrc ns = make_noise(nullptr, nullptr, noise_rows, seed, 0, 0, 0);
-                rc = step_impl(h, topo, topo->zbuf, topo->eps, h->d_coef, 1, ns, N, topo->zbuf, N, h->d_step, h->d_ipdraw + 3 * j,
-                               0, rs, h->d_base);
-            }
-            if (rc == HD_OK)
-                rc = inpaint_launch(h, topo, false, topo->zbuf, topo->ip_fixed, topo->ip_known, seed, 0, 0, 0, h->d_ipdraw + 3 * j + 1,
-                                    h->d_step, h->d_base, rs);
-            if (rc == HD_OK && j < R - 1)
-                rc = inpaint_launch(h, topo, true, topo->zbuf, nullptr, nullptr, seed, 0, 0, 0, h->d_ipdraw + 3 * j + 2, h->d_step,
-                                    h->d_base, rs);
-        }
-        if (rc == HD_OK) {
+        LoopIO io = loop_io_captured(h, h->d_ipdraw, rs);
+        io.z = topo->zbuf; io.ctx = context ? topo->ctxbuf : nullptr; io.fixed = topo->ip_fixed; io.known = topo->ip_known;
+        HD_TRY(replay_capture(h, rs, &topo->gexec_ip, [&]() -> int {
+            HD_TRY(step(io));
             hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, rs, h->d_step, h->d_draw, h->d_tcur, h->d_tau);
             hipLaunchKernelGGL(k_inpaint_advance, dim3((nd + 255) / 256), dim3(256), 0, rs, h->d_ipdraw, nd);
-        }
-        const hipError_t ce = hipStreamEndCapture(rs, &graph);
-        h->prof = was_prof;
-        if (rc != HD_OK) { if (graph) hipGraphDestroy(graph); return rc; }
-        if (ce != hipSuccess) return fail(HD_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-        const hipError_t ie = hipGraphInstantiate(&topo->gexec_ip, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (ie != hipSuccess) { topo->gexec_ip = nullptr; return fail(HD_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+            return HD_OK;
+        }));
         topo->ikey = key;
     }
     HIP_TRY(hipMemcpyAsync(topo->zbuf, z, zbytes, hipMemcpyDeviceToDevice, rs));
@@ -2954,21 +3051,37 @@ extern "C" int hd_sample_loop_inpaint(hd_handle* h, hd_topology* topo, float* z,
     hipLaunchKernelGGL(k_loop_state, dim3(1), dim3(1), 0, rs, h->d_step, h->d_draw, h->d_tcur, h->d_base, h->d_tau,
                        s_hi - 1, draw0, (unsigned long long)sample_id_base);
     hipLaunchKernelGGL(k_inpaint_state, dim3((nd + 255) / 256), dim3(256), 0, rs, h->d_ipdraw, nd, stride, draw0);
-    for (int k = 0; k < nsteps; ++k) {
-        const hipError_t le = hipGraphLaunch(topo->gexec_ip, rs);
-        if (le != hipSuccess) return fail(HD_E_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(le));
-    }
+    HD_TRY(replay_run(topo->gexec_ip, nsteps, rs));
     HIP_TRY(hipMemcpyAsync(z, topo->zbuf, zbytes, hipMemcpyDeviceToDevice, rs));
-    HIP_TRY(hipEventRecord(h->ev_last, rs));
-    h->ev_last_set = true;
-    if (rs != s) {
-        HIP_TRY(hipEventRecord(h->ev_out, rs));
-        HIP_TRY(hipStreamWaitEvent(s, h->ev_out, 0));
-    }
-    return HD_OK;
+    return replay_leave(h, s, rs);
 }
 
 // ----------------------------------------------------------------------------- few-step sampling: the loop on a path
+
+// The one writer of the path tables: K validated transitions t_idx[k] -> s_idx[k], their rows of `row_width` floats and, for
+// ancestral paths that inpaint, the inpainting rows.
+static int set_path_tables(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* rows, int row_width,
+                           const float* rows_ip, int form, bool up) {
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
+    hipFree(h->d_path_t); hipFree(h->d_path_s); hipFree(h->d_path_coef); hipFree(h->d_path_coef_ip);
+    h->d_path_t = h->d_path_s = nullptr; h->d_path_coef = h->d_path_coef_ip = nullptr;
+    h->path_sched_gen = 0; h->path_K = 0;
+    h->path_t_h.assign(t_idx, t_idx + K);
+    h->path_s_h.assign(s_idx, s_idx + K);
+    if (form == 2) {
+        h->path_c2_h.resize((size_t)K);
+        for (int k = 0; k < K; ++k) h->path_c2_h[(size_t)k] = rows[(size_t)row_width * k + 2];
+    }
+    HD_TRY(dev_upload(&h->d_path_t, h->path_t_h));
+    HD_TRY(dev_upload(&h->d_path_s, h->path_s_h));
+    HD_TRY(dev_upload(&h->d_path_coef, std::vector<float>(rows, rows + (size_t)row_width * K)));
+    if (rows_ip) HD_TRY(dev_upload(&h->d_path_coef_ip, std::vector<float>(rows_ip, rows_ip + (size_t)4 * K)));
+    h->path_K = K; h->path_form = form; h->path_up = up;
+    h->path_sched_gen = h->sched_gen;
+    h->path_gen++;                             // captured graphs hold the old table addresses
+    return HD_OK;
+}
 
 extern "C" int hd_set_path(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* coef4, int form,
                            const float* coef4_inpaint) {
@@ -2982,21 +3095,7 @@ extern "C" int hd_set_path(hd_handle* h, int K, const int* t_idx, const int* s_i
             return fail(HD_E_INVALID, "hd_set_path: need 0 <= s_idx[k] < t_idx[k] <= T");
         if (k > 0 && t_idx[k] != s_idx[k - 1]) return fail(HD_E_INVALID, "hd_set_path: transition k must start where k - 1 arrived");
     }
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
-    hipFree(h->d_path_t); hipFree(h->d_path_s); hipFree(h->d_path_coef); hipFree(h->d_path_coef_ip);
-    h->d_path_t = h->d_path_s = nullptr; h->d_path_coef = h->d_path_coef_ip = nullptr;
-    h->path_sched_gen = 0; h->path_K = 0;
-    h->path_t_h.assign(t_idx, t_idx + K);
-    h->path_s_h.assign(s_idx, s_idx + K);
-    HD_TRY(dev_upload(&h->d_path_t, h->path_t_h));
-    HD_TRY(dev_upload(&h->d_path_s, h->path_s_h));
-    HD_TRY(dev_upload(&h->d_path_coef, std::vector<float>(coef4, coef4 + (size_t)4 * K)));
-    if (coef4_inpaint) HD_TRY(dev_upload(&h->d_path_coef_ip, std::vector<float>(coef4_inpaint, coef4_inpaint + (size_t)4 * K)));
-    h->path_K = K; h->path_form = form; h->path_up = false;
-    h->path_sched_gen = h->sched_gen;
-    h->path_gen++;                             // captured graphs hold the old table addresses
-    return HD_OK;
+    return set_path_tables(h, K, t_idx, s_idx, coef4, 4, coef4_inpaint, form, false);
 }
 
 // An ascending path into the same tables: transition k leaves from_idx[k] (path_t: network time, as for descending paths) and
@@ -3013,20 +3112,7 @@ extern "C" int hd_set_path_up(hd_handle* h, int K, const int* from_idx, const in
     if (h->T < 1) return fail(HD_E_STATE, "hd_set_path_up: schedule not set (hd_set_schedule)");
     if (K > h->T) return fail(HD_E_INVALID, "hd_set_path_up: more transitions than the schedule has steps");
     if (to_idx[K - 1] > h->T) return fail(HD_E_INVALID, "hd_set_path_up: need 0 <= from_idx[k] < to_idx[k] <= T");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
-    hipFree(h->d_path_t); hipFree(h->d_path_s); hipFree(h->d_path_coef); hipFree(h->d_path_coef_ip);
-    h->d_path_t = h->d_path_s = nullptr; h->d_path_coef = h->d_path_coef_ip = nullptr;
-    h->path_sched_gen = 0; h->path_K = 0;
-    h->path_t_h.assign(from_idx, from_idx + K);
-    h->path_s_h.assign(to_idx, to_idx + K);
-    HD_TRY(dev_upload(&h->d_path_t, h->path_t_h));
-    HD_TRY(dev_upload(&h->d_path_s, h->path_s_h));
-    HD_TRY(dev_upload(&h->d_path_coef, std::vector<float>(coef4, coef4 + (size_t)4 * K)));
-    h->path_K = K; h->path_form = 1; h->path_up = true;
-    h->path_sched_gen = h->sched_gen;
-    h->path_gen++;                             // captured graphs hold the old table addresses
-    return HD_OK;
+    return set_path_tables(h, K, from_idx, to_idx, coef4, 4, nullptr, 1, true);
 }
 
 // A descending path with multistep rows {a, b, c2, p, q} (form 2, k_solver.hpp) into the same tables.
@@ -3041,22 +3127,7 @@ extern "C" int hd_set_path_multistep(hd_handle* h, int K, const int* t_idx, cons
             return fail(HD_E_INVALID, "hd_set_path_multistep: transition k must start where k - 1 arrived");
     }
     if (rows5[2] != 0.f) return fail(HD_E_INVALID, "hd_set_path_multistep: c2 of row 0 must be 0 (the first transition has no history)");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
-    hipFree(h->d_path_t); hipFree(h->d_path_s); hipFree(h->d_path_coef); hipFree(h->d_path_coef_ip);
-    h->d_path_t = h->d_path_s = nullptr; h->d_path_coef = h->d_path_coef_ip = nullptr;
-    h->path_sched_gen = 0; h->path_K = 0;
-    h->path_t_h.assign(t_idx, t_idx + K);
-    h->path_s_h.assign(s_idx, s_idx + K);
-    h->path_c2_h.resize((size_t)K);
-    for (int k = 0; k < K; ++k) h->path_c2_h[(size_t)k] = rows5[(size_t)5 * k + 2];
-    HD_TRY(dev_upload(&h->d_path_t, h->path_t_h));
-    HD_TRY(dev_upload(&h->d_path_s, h->path_s_h));
-    HD_TRY(dev_upload(&h->d_path_coef, std::vector<float>(rows5, rows5 + (size_t)5 * K)));
-    h->path_K = K; h->path_form = 2; h->path_up = false;
-    h->path_sched_gen = h->sched_gen;
-    h->path_gen++;                             // captured graphs hold the old table addresses
-    return HD_OK;
+    return set_path_tables(h, K, t_idx, s_idx, rows5, 5, nullptr, 2, false);
 }
 
 extern "C" long long hd_path_graph_builds(const hd_topology* topo) { return topo ? topo->path_builds : -1; }
@@ -3132,112 +3203,67 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
     topo_use(topo, s);
     if (ntr == 0) return HD_OK;
     if (gd) HD_TRY(guide_buffers(h, topo));
-    if (!use_graph) {
-        for (int k = k_lo; k < k_hi; ++k) {
-            const float* tcur = h->d_tau + h->path_t_h[k];
-            const uint32_t d = (uint32_t)(T - h->path_s_h[k]);
-            const size_t ro = (size_t)(k - k_lo) * noise_rows * mol;
-            for (int j = 0; j < (R ? R : 1); ++j) {
-                HD_TRY(forward_impl(h, topo, z, tcur, 1, context, ms, topo->eps, s));
-                if (gd) {
-                    HD_TRY(forward_impl(h, topo, z, tcur, 1, gd->ctx_u, ms, topo->eps_u, s));
-                    HD_TRY(guide_launch(h, topo, topo->eps, topo->eps_u, gd->w, gd->w_rows, gd->phi, topo->eps, s));
-                }
-                NoiseSrc ns = make_noise(raw_x ? raw_x + ro * 3 : nullptr, raw_h ? raw_h + ro * h->F : nullptr, noise_rows, seed,
-                                         sample_id_base, stride * (uint32_t)(3 * j) + d, share);
-                if (form == 2) {
-                    HD_TRY(solver_launch(h, topo, z, topo->eps, h->d_path_coef + (size_t)k * 5, nullptr, topo->ms_hist, topo->ms_hist,
-                                         mol, z, nullptr, s));
-                    continue;
-                }
-                HD_TRY(step_impl(h, topo, z, topo->eps, h->d_path_coef + (size_t)k * 4, 1, ns, mol, z, N, nullptr, nullptr, 0, s,
-                                 nullptr, form));
-                if (!R) continue;
-                HD_TRY(inpaint_launch(h, topo, false, z, fixed_mask, xh_known, seed, sample_id_base, stride * (uint32_t)(3 * j + 1) + d,
-                                      k, nullptr, nullptr, nullptr, s, h->d_path_coef_ip));
-                if (j < R - 1)
-                    HD_TRY(inpaint_launch(h, topo, true, z, nullptr, nullptr, seed, sample_id_base, stride * (uint32_t)(3 * j + 2) + d,
-                                          k, nullptr, nullptr, nullptr, s, h->d_path_coef_ip));
+    auto transition = [&](const LoopIO& io) -> int {         // all rounds of one transition; io.row is the path position
+        for (int j = 0; j < (R ? R : 1); ++j) {
+            HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx, ms, topo->eps, io.s));
+            if (gd) {
+                HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx_u, ms, topo->eps_u, io.s));
+                HD_TRY(guide_launch(h, topo, topo->eps, topo->eps_u, io.w, gd->w_rows, gd->phi, topo->eps, io.s));
             }
+            if (form == 2) {
+                HD_TRY(solver_launch(h, topo, io.z, topo->eps, h->d_path_coef + (size_t)io.row * 5, nullptr, topo->ms_hist,
+                                     topo->ms_hist, mol, io.z, io.step, io.s));
+                continue;
+            }
+            NoiseSrc ns = make_noise(raw_x ? raw_x + io.ro * 3 : nullptr, raw_h ? raw_h + io.ro * h->F : nullptr, noise_rows, seed,
+                                     io.base, io.step ? 0u : stride * (uint32_t)(3 * j) + io.draw, share);
+            HD_TRY(step_impl(h, topo, io.z, topo->eps, h->d_path_coef + (size_t)io.row * 4, 1, ns, mol, io.z, N, io.step,
+                             io.step ? io.draw_w + 3 * j : nullptr, 0, io.s, io.base_w, form, io.step ? k_lo : -1));
+            if (R) HD_TRY(inpaint_round(h, topo, io, j, R, stride, seed, h->d_path_coef_ip));
+        }
+        return HD_OK;
+    };
+    if (!use_graph) {
+        LoopIO io{};
+        io.z = z; io.ctx = context; io.fixed = fixed_mask; io.known = xh_known; io.base = sample_id_base; io.s = s;
+        if (gd) { io.ctx_u = gd->ctx_u; io.w = gd->w; }
+        for (int k = k_lo; k < k_hi; ++k) {
+            io.row = k; io.tcur = h->d_tau + h->path_t_h[k];
+            io.ro = (size_t)(k - k_lo) * noise_rows * mol; io.draw = (uint32_t)(T - h->path_s_h[k]);
+            HD_TRY(transition(io));
         }
         return HD_OK;
     }
-    // ONE captured transition, replayed ntr times: the path position lives in d_step and k_path_advance derives the network time,
-    // the coefficient row and the draws from the uploaded tables.  Everything else as in hd_sample_loop.
+    // The path position lives in d_step; k_path_advance derives the network time, the coefficient row and the draws from the
+    // uploaded tables.
     const size_t BN = (size_t)topo->B * N;
     const size_t zbytes = BN * h->D * sizeof(float);
     const size_t cbytes = BN * h->cfg.context_node_nf * sizeof(float);
-    hipStream_t rs = s;
-    if (s == nullptr) {
-        if (!h->own_stream) HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-        rs = h->own_stream;
-        HIP_TRY(hipEventRecord(h->ev_in, s));
-        HIP_TRY(hipStreamWaitEvent(rs, h->ev_in, 0));
-    }
-    if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(rs, h->ev_last, 0));
-    if (nd > h->ipdraw_cap) {                                // grow the draw words: graphs that hold the old address go stale (ip_gen)
-        if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
-        HIP_TRY(hipStreamSynchronize(rs));
-        hipFree(h->d_ipdraw);
-        h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
-        HD_TRY(dev_alloc(&h->d_ipdraw, (size_t)nd));
-        h->ipdraw_cap = nd;
-        h->ip_gen++;
-    }
-    if (R) {
-        if (!topo->ip_fixed) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->ip_fixed), BN));
-        if (!topo->ip_known) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->ip_known), zbytes));
-    }
+    hipStream_t rs;
+    HD_TRY(replay_enter(h, s, &rs));
+    HD_TRY(grow_ipdraw(h, rs, nd));
+    if (R) HD_TRY(inpaint_buffers(h, topo));
     PathKey key;
     key.raw_x = raw_x; key.raw_h = raw_h; key.has_ctx = context ? 1 : 0; key.mol_shape = ms; key.noise_rows = noise_rows;
     key.k_lo = raw_x ? k_lo : 0; key.resamplings = R; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
     key.path_gen = h->path_gen; key.ip_gen = R ? h->ip_gen : 0;
     key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
     // the guided transition is a graph of its own: guided and unguided calls on one topology do not evict each other
-    hipGraphExec_t& gx = gd ? topo->gexec_guided : topo->gexec_path;
+    hipGraphExec_t* gx = gd ? &topo->gexec_guided : &topo->gexec_path;
     PathKey& kx = gd ? topo->gdkey : topo->pkey;
-    if (gx && !(kx == key)) {
-        if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
-        HIP_TRY(hipStreamSynchronize(rs));
-        hipGraphExecDestroy(gx);
-        gx = nullptr;
-    }
+    HD_TRY(replay_evict(h, rs, gx, kx, key));
     PathWords w;
     w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = R ? h->d_ipdraw : nullptr;
     w.tau = h->d_tau; w.t_idx = h->d_path_t; w.s_idx = h->d_path_s; w.K = K; w.T = T; w.nd = nd; w.stride = stride;
-    if (!gx) {
-        const int was_prof = h->prof;
-        h->prof = 0;
-        hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(rs, hipStreamCaptureModeThreadLocal));
-        int rc = HD_OK;
-        for (int j = 0; j < (R ? R : 1) && rc == HD_OK; ++j) {
-            rc = forward_impl(h, topo, topo->zbuf, h->d_tcur, 1, context ? topo->ctxbuf : nullptr, ms, topo->eps, rs);
-            if (rc == HD_OK && gd) rc = forward_impl(h, topo, topo->zbuf, h->d_tcur, 1, topo->ctxu_buf, ms, topo->eps_u, rs);
-            if (rc == HD_OK && gd) rc = guide_launch(h, topo, topo->eps, topo->eps_u, topo->wbuf, gd->w_rows, gd->phi, topo->eps, rs);
-            if (rc == HD_OK && form == 2) {
-                rc = solver_launch(h, topo, topo->zbuf, topo->eps, h->d_path_coef, nullptr, topo->ms_hist, topo->ms_hist, mol,
-                                   topo->zbuf, h->d_step, rs);
-            } else if (rc == HD_OK) {
-                NoiseSrc ns = make_noise(raw_x, raw_h, noise_rows, seed, 0, 0, share);
-                rc = step_impl(h, topo, topo->zbuf, topo->eps, h->d_path_coef, 1, ns, mol, topo->zbuf, N, h->d_step,
-                               R ? h->d_ipdraw + 3 * j : h->d_draw, 0, rs, h->d_base, form, k_lo);
-            }
-            if (rc == HD_OK && R)
-                rc = inpaint_launch(h, topo, false, topo->zbuf, topo->ip_fixed, topo->ip_known, seed, 0, 0, 0, h->d_ipdraw + 3 * j + 1,
-                                    h->d_step, h->d_base, rs, h->d_path_coef_ip);
-            if (rc == HD_OK && R && j < R - 1)
-                rc = inpaint_launch(h, topo, true, topo->zbuf, nullptr, nullptr, seed, 0, 0, 0, h->d_ipdraw + 3 * j + 2, h->d_step,
-                                    h->d_base, rs, h->d_path_coef_ip);
-        }
-        if (rc == HD_OK) hipLaunchKernelGGL(k_path_advance, dim3(1), dim3(64), 0, rs, w);
-        const hipError_t ce = hipStreamEndCapture(rs, &graph);
-        h->prof = was_prof;
-        if (rc != HD_OK) { if (graph) hipGraphDestroy(graph); return rc; }
-        if (ce != hipSuccess) return fail(HD_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-        const hipError_t ie = hipGraphInstantiate(&gx, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (ie != hipSuccess) { gx = nullptr; return fail(HD_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+    if (!*gx) {
+        LoopIO io = loop_io_captured(h, R ? h->d_ipdraw : h->d_draw, rs);
+        io.z = topo->zbuf; io.ctx = context ? topo->ctxbuf : nullptr; io.fixed = topo->ip_fixed; io.known = topo->ip_known;
+        if (gd) { io.ctx_u = topo->ctxu_buf; io.w = topo->wbuf; }
+        HD_TRY(replay_capture(h, rs, gx, [&]() -> int {
+            HD_TRY(transition(io));
+            hipLaunchKernelGGL(k_path_advance, dim3(1), dim3(64), 0, rs, w);
+            return HD_OK;
+        }));
         kx = key;
         if (gd) topo->guided_builds++; else topo->path_builds++;
     }
@@ -3252,18 +3278,9 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
         HIP_TRY(hipMemcpyAsync(topo->ip_known, xh_known, zbytes, hipMemcpyDeviceToDevice, rs));
     }
     hipLaunchKernelGGL(k_path_state, dim3(1), dim3(64), 0, rs, w, k_lo, (unsigned long long)sample_id_base);
-    for (int k = 0; k < ntr; ++k) {
-        const hipError_t le = hipGraphLaunch(gx, rs);
-        if (le != hipSuccess) return fail(HD_E_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(le));
-    }
+    HD_TRY(replay_run(*gx, ntr, rs));
     HIP_TRY(hipMemcpyAsync(z, topo->zbuf, zbytes, hipMemcpyDeviceToDevice, rs));
-    HIP_TRY(hipEventRecord(h->ev_last, rs));
-    h->ev_last_set = true;
-    if (rs != s) {
-        HIP_TRY(hipEventRecord(h->ev_out, rs));
-        HIP_TRY(hipStreamWaitEvent(s, h->ev_out, 0));
-    }
-    return HD_OK;
+    return replay_leave(h, s, rs);
 }
 
 static int path_ready(hd_handle* h, const char* who, int k_lo, int k_hi) {
@@ -3294,22 +3311,13 @@ extern "C" int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z,
                                       int k_hi, const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed,
                                       uint64_t sample_id_base, int use_graph, const uint8_t* fixed_mask, const float* xh_known,
                                       int resamplings, void* stream) {
+    const char* who = "hd_sample_path_inpaint";
     if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_sample_path_inpaint: need 0 <= k_lo <= k_hi <= K");
-    HD_TRY(check_ready(h, topo, "hd_sample_path_inpaint"));
-    HD_TRY(path_ready(h, "hd_sample_path_inpaint", k_lo, k_hi));
-    if (h->path_up) return fail(HD_E_INVALID, "hd_sample_path_inpaint: the path ascends (hd_set_path_up): inversion fixes no fragments");
-    if (h->path_form != 0) return fail(HD_E_INVALID, "hd_sample_path_inpaint: ancestral rows only (the path was set with form = 1)");
-    if (!h->d_path_coef_ip) return fail(HD_E_STATE, "hd_sample_path_inpaint: the path was set without inpainting rows (hd_set_path)");
+    HD_TRY(check_ready(h, topo, who));
+    HD_TRY(path_ready(h, who, k_lo, k_hi));
+    HD_TRY(inpaint_path_check(who, h, ": ancestral rows only (the path was set with form = 1)"));
     if (!z || !fixed_mask || !xh_known) return fail(HD_E_INVALID, "hd_sample_path_inpaint: null z / fixed_mask / xh_known");
-    if (raw_x || raw_h) return fail(HD_E_INVALID, "hd_sample_path_inpaint: injected noise is not supported (counter-based generator only)");
-    if (noise_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_path_inpaint: noise_rows must be B");
-    if (mol_shape >= 0 && mol_shape < topo->N) return fail(HD_E_INVALID, "hd_sample_path_inpaint: fixed tail rows (mol_shape < N) are not supported");
-    if (resamplings < 1) return fail(HD_E_INVALID, "hd_sample_path_inpaint: resamplings must be >= 1");
-    if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, "hd_sample_path_inpaint: context required");
-    if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_path_inpaint: needs a time-conditioned model");
-    if (((unsigned long long)h->T + 2ULL) * 3ULL * (unsigned long long)resamplings > 0xffffffffULL)
-        return fail(HD_E_INVALID, "hd_sample_path_inpaint: (T + 2) * 3 * resamplings exceeds the 32-bit draw index");
-    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_sample_path_inpaint: N * D floats exceed one workgroup's LDS");
+    HD_TRY(inpaint_args_check(who, h, topo, raw_x, raw_h, noise_rows, mol_shape, resamplings, context, kIpRawMsg, kIpRowsMsg));
     HIP_TRY(hipSetDevice(h->device));
     return path_loop(h, topo, z, context, -1, k_lo, k_hi, nullptr, nullptr, noise_rows, seed, sample_id_base, use_graph,
                      fixed_mask, xh_known, resamplings, (hipStream_t)stream);
@@ -3350,16 +3358,11 @@ extern "C" int hd_sample_path_guided(hd_handle* h, hd_topology* topo, float* z, 
     if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_path_guided: needs a time-conditioned model");
     int R = 0;
     if (fixed_mask) {                                        // the restrictions of hd_sample_path_inpaint
-        if (h->path_up) return fail(HD_E_INVALID, "hd_sample_path_guided: the path ascends (hd_set_path_up): inversion fixes no fragments");
-        if (h->path_form != 0) return fail(HD_E_INVALID, "hd_sample_path_guided: inpainting takes ancestral rows only (the path was set with form = 1)");
-        if (!h->d_path_coef_ip) return fail(HD_E_STATE, "hd_sample_path_guided: the path was set without inpainting rows (hd_set_path)");
+        HD_TRY(inpaint_path_check(who, h, ": inpainting takes ancestral rows only (the path was set with form = 1)"));
         if (!xh_known) return fail(HD_E_INVALID, "hd_sample_path_guided: fixed_mask without xh_known");
-        if (raw_x || raw_h) return fail(HD_E_INVALID, "hd_sample_path_guided: inpainting takes no injected noise (counter-based generator only)");
-        if (noise_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_path_guided: inpainting needs noise_rows = B");
-        if (resamplings < 1) return fail(HD_E_INVALID, "hd_sample_path_guided: resamplings must be >= 1");
-        if (((unsigned long long)h->T + 2ULL) * 3ULL * (unsigned long long)resamplings > 0xffffffffULL)
-            return fail(HD_E_INVALID, "hd_sample_path_guided: (T + 2) * 3 * resamplings exceeds the 32-bit draw index");
-        if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_sample_path_guided: N * D floats exceed one workgroup's LDS");
+        // no mol_shape here; context and the time-conditioned model were checked above
+        HD_TRY(inpaint_args_check(who, h, topo, raw_x, raw_h, noise_rows, -1, resamplings, context,
+                                  ": inpainting takes no injected noise (counter-based generator only)", ": inpainting needs noise_rows = B"));
         R = resamplings;
     } else {
         if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, "hd_sample_path_guided: raw_x and raw_h go together");
@@ -3499,31 +3502,28 @@ extern "C" int hd_nll_terms(hd_handle* h, hd_topology* topo, const float* xh, co
     topo_use(topo, s);
     if (nterms == 0) return HD_OK;
     if (!topo->nll_eps) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_eps), zbytes));
+    auto term = [&](const LoopIO& io) -> int {               // io.row is the term's position in the list, io.draw its timestep
+        HD_TRY(nll_launch_zt(h, topo, io.xh, h->d_nll_coef, 0.f, 0.f, make_noise(raw_x, raw_h, B, seed, io.base, io.draw, 0), io.row, k_lo,
+                             io.step, io.draw_w, io.base_w, io.s));
+        HD_TRY(forward_impl(h, topo, topo->zbuf, io.tcur, 1, io.ctx, -1, topo->eps, io.s));
+        return nll_launch_err(h, topo, io.acc, io.err, io.row, io.step, io.s);
+    };
     if (!use_graph) {
+        LoopIO io{};
+        io.xh = xh; io.ctx = context; io.acc = acc; io.err = err_terms; io.base = sample_id_base; io.s = s;
         for (int k = k_lo; k < k_hi; ++k) {
-            const int t = h->nll_t_h[k];
-            HD_TRY(nll_launch_zt(h, topo, xh, h->d_nll_coef, 0.f, 0.f, make_noise(raw_x, raw_h, B, seed, sample_id_base, (uint32_t)t, 0),
-                                 k, k_lo, nullptr, nullptr, nullptr, s));
-            HD_TRY(forward_impl(h, topo, topo->zbuf, h->d_tau + t, 1, context, -1, topo->eps, s));
-            HD_TRY(nll_launch_err(h, topo, acc, err_terms, k, nullptr, s));
+            io.row = k; io.draw = (uint32_t)h->nll_t_h[k]; io.tcur = h->d_tau + h->nll_t_h[k];
+            HD_TRY(term(io));
         }
         return HD_OK;
     }
-    // ONE captured term, replayed nterms times: the term position lives in d_step and k_nll_advance derives the network time and
-    // the draw from the uploaded list.  Everything else as in the path loop (library-owned copies, events instead of host waits).
-    hipStream_t rs = s;
-    if (s == nullptr) {
-        if (!h->own_stream) HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-        rs = h->own_stream;
-        HIP_TRY(hipEventRecord(h->ev_in, s));
-        HIP_TRY(hipStreamWaitEvent(rs, h->ev_in, 0));
-    }
-    if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(rs, h->ev_last, 0));
+    // The term position lives in d_step; k_nll_advance derives the network time and the draw from the uploaded list.
+    hipStream_t rs;
+    HD_TRY(replay_enter(h, s, &rs));
     if (!topo->nll_xh) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_xh), zbytes));
     if (!topo->nll_acc) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_acc), (size_t)B * sizeof(double)));
     if (err_terms && topo->nll_err_rows < K) {               // grow the e_t table: a graph that holds the old address goes stale (key)
-        if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
-        HIP_TRY(hipStreamSynchronize(rs));
+        HD_TRY(replay_quiesce(h, rs));
         if (topo->nll_err) (void)hipFree(topo->nll_err);
         topo->nll_err = nullptr; topo->nll_err_rows = 0;
         HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_err), (size_t)K * B * sizeof(float)));
@@ -3532,31 +3532,17 @@ extern "C" int hd_nll_terms(hd_handle* h, hd_topology* topo, const float* xh, co
     NllKey key;
     key.raw_x = raw_x; key.raw_h = raw_h; key.err = err_terms ? topo->nll_err : nullptr; key.has_ctx = context ? 1 : 0;
     key.k_lo = raw_x ? k_lo : 0; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen; key.nll_gen = h->nll_gen;
-    if (topo->gexec_nll && !(topo->nkey == key)) {
-        if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
-        HIP_TRY(hipStreamSynchronize(rs));
-        hipGraphExecDestroy(topo->gexec_nll);
-        topo->gexec_nll = nullptr;
-    }
+    HD_TRY(replay_evict(h, rs, &topo->gexec_nll, topo->nkey, key));
     NllWords w;
     w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.tau = h->d_tau; w.t_idx = h->d_nll_t; w.K = K;
     if (!topo->gexec_nll) {
-        const int was_prof = h->prof;
-        h->prof = 0;
-        hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(rs, hipStreamCaptureModeThreadLocal));
-        int rc = nll_launch_zt(h, topo, topo->nll_xh, h->d_nll_coef, 0.f, 0.f, make_noise(raw_x, raw_h, B, seed, 0, 0, 0), 0, k_lo,
-                               h->d_step, h->d_draw, h->d_base, rs);
-        if (rc == HD_OK) rc = forward_impl(h, topo, topo->zbuf, h->d_tcur, 1, context ? topo->ctxbuf : nullptr, -1, topo->eps, rs);
-        if (rc == HD_OK) rc = nll_launch_err(h, topo, topo->nll_acc, key.err ? topo->nll_err : nullptr, 0, h->d_step, rs);
-        if (rc == HD_OK) hipLaunchKernelGGL(k_nll_advance, dim3(1), dim3(1), 0, rs, w);
-        const hipError_t ce = hipStreamEndCapture(rs, &graph);
-        h->prof = was_prof;
-        if (rc != HD_OK) { if (graph) hipGraphDestroy(graph); return rc; }
-        if (ce != hipSuccess) return fail(HD_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-        const hipError_t ie = hipGraphInstantiate(&topo->gexec_nll, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (ie != hipSuccess) { topo->gexec_nll = nullptr; return fail(HD_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+        LoopIO io = loop_io_captured(h, h->d_draw, rs);
+        io.xh = topo->nll_xh; io.ctx = context ? topo->ctxbuf : nullptr; io.acc = topo->nll_acc; io.err = err_terms ? topo->nll_err : nullptr;
+        HD_TRY(replay_capture(h, rs, &topo->gexec_nll, [&]() -> int {
+            HD_TRY(term(io));
+            hipLaunchKernelGGL(k_nll_advance, dim3(1), dim3(1), 0, rs, w);
+            return HD_OK;
+        }));
         topo->nkey = key;
         topo->nll_builds++;
     }
@@ -3564,21 +3550,12 @@ extern "C" int hd_nll_terms(hd_handle* h, hd_topology* topo, const float* xh, co
     if (context) HIP_TRY(hipMemcpyAsync(topo->ctxbuf, context, cbytes, hipMemcpyDeviceToDevice, rs));
     HIP_TRY(hipMemcpyAsync(topo->nll_acc, acc, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, rs));
     hipLaunchKernelGGL(k_nll_state, dim3(1), dim3(1), 0, rs, w, k_lo, (unsigned long long)sample_id_base);
-    for (int k = 0; k < nterms; ++k) {
-        const hipError_t le = hipGraphLaunch(topo->gexec_nll, rs);
-        if (le != hipSuccess) return fail(HD_E_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(le));
-    }
+    HD_TRY(replay_run(topo->gexec_nll, nterms, rs));
     HIP_TRY(hipMemcpyAsync(acc, topo->nll_acc, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, rs));
     if (err_terms)
         HIP_TRY(hipMemcpyAsync(err_terms + (size_t)k_lo * B, topo->nll_err + (size_t)k_lo * B, (size_t)nterms * B * sizeof(float),
                                hipMemcpyDeviceToDevice, rs));
-    HIP_TRY(hipEventRecord(h->ev_last, rs));
-    h->ev_last_set = true;
-    if (rs != s) {
-        HIP_TRY(hipEventRecord(h->ev_out, rs));
-        HIP_TRY(hipStreamWaitEvent(s, h->ev_out, 0));
-    }
-    return HD_OK;
+    return replay_leave(h, s, rs);
 }
 
 extern "C" int hd_nll_finish(hd_handle* h, hd_topology* topo, const float* xh, const float* context, int mol_shape, const float* raw_x,

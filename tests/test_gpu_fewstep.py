@@ -418,3 +418,43 @@ def test_list_level_entry_points_take_the_keywords():
     known = [{"x": a[0]["x"][:2], "h": a[0]["h"][:2]}]
     grown = model.sample_grow(known, [5], DEV, steps=6)
     assert grown[0]["x"].shape == (5, 3) and torch.equal(grown[0]["h"][:2], known[0]["h"])
+
+
+# ----------------------------------------------------------------------------- 14. every captured loop on one topology
+
+def test_the_loops_share_a_topology_without_evicting_each_other():
+    """The every-step loop, a strided path, the same path guided, the every-step inpainting loop (r = 2) and the scoring terms, twice
+    over on one handle and one topology: each keeps its own graph slot (one instantiation each) while all of them move the handle's
+    one set of replay words, and every output is the bits of plain launches on a fresh topology."""
+    from hierdiff_amd import _lib
+    lib = _lib.load()
+    T = 8
+    nm, _, fm, xk, hk, ctx = make_case(n_list=[5, 3, 5], n_fixed=[2, 0, 3], C_=1)       # B = 3, N = 5, one molecule shorter than N
+    B, N = nm.shape[:2]
+    xh, _, _ = orc.random_inputs([5, 3, 5], 8, seed=3)
+    nmd, ctxd = dev(nm), dev(ctx)
+    x_in, h_in = dev(xh[:, :, :3].contiguous()), dev(xh[:, :, 3:].contiguous())
+    path = dict(steps=3, eta=0.5, sample_id_base=7)
+
+    def one_round(model, graph):
+        model.use_graph = graph
+        out = list(model.sample_from_masks(nmd, None, ctxd, sample_id_base=5))
+        out += model.sample_from_masks(nmd, None, ctxd, **path)
+        out += model.sample_from_masks(nmd, None, ctxd, guidance_scale=2.5, guidance_rescale=0.7, **path)
+        out += model.sample_inpaint(nmd, dev(fm), dev(xk), dev(hk), context=ctxd, resamplings=2, sample_id_base=9)
+        nll, (_, e) = model.nll_full(x_in, h_in, nmd, None, ctxd, sample_id_base=11, return_terms=True, use_graph=graph)
+        return out + [nll, e]
+
+    model, _, _ = make_model(32, 1, T, C_=1)
+    first, second = one_round(model, True), one_round(model, True)
+    assert len(first) == 10 and all(torch.isfinite(a).all() for a in first)
+    for i, (a, b) in enumerate(zip(first, second)):
+        assert torch.equal(a, b), f"output {i}: the second round differs from the first"
+    topo = model.dynamics.topology(nmd, None, B, N).ptr
+    builds = (int(lib.hd_path_graph_builds(topo)), int(lib.hd_guided_graph_builds(topo)), int(lib.hd_nll_graph_builds(topo)))
+    assert builds == (1, 1, 1), builds
+    other, _, _ = make_model(32, 1, T, C_=1)                  # a fresh handle and topology, plain launches
+    for i, (a, b) in enumerate(zip(first, one_round(other, False))):
+        assert torch.equal(a, b), f"output {i}: graph replay differs from plain launches"
+    topo = other.dynamics.topology(nmd, None, B, N).ptr
+    assert (lib.hd_path_graph_builds(topo), lib.hd_guided_graph_builds(topo), lib.hd_nll_graph_builds(topo)) == (0, 0, 0)
