@@ -9,10 +9,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #define HD_DEVINL __device__ __forceinline__
 
@@ -55,14 +51,14 @@ HD_DEVINL float sigmoid_f(float x) {
     return __builtin_amdgcn_rcpf(1.0f + e);
 }
 
-// plain SiLU of the bf16x3 node kernel (contraction error ~1e-6 anyway): exp2(-x*log2e), 5 instructions; the
+// plain SiLU of the fp32 edge kernel and the fp16x3 node kernel (contraction error ~1e-6 anyway): exp2(-x*log2e), 5 instructions; the
 // exponent argument is off by <= |x|*1.7e-7, i.e. a relative error of that size on an already saturated value.
 HD_DEVINL float silu_fast(float x) {
     float e = __builtin_amdgcn_exp2f(x * -1.44269502162933349609375f);
     return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
-// ---- scaled-domain activations of the bf16x3 edge kernel.  The host multiplies everything that feeds a SiLU /
+// ---- scaled-domain activations of the fp16x3 edge kernel.  The host multiplies everything that feeds a SiLU /
 // sigmoid of the edge model by c = -log2(e) (first edge Linear incl. bias and the two distance columns, b2, the
 // attention bias), so with x' = c x
 //     silu'(x') := x' * rcp(1 + exp2(x')) = c * silu(x)          sigmoid(z) = rcp(1 + exp2(z'))
@@ -72,14 +68,6 @@ HD_DEVINL float silu_fast(float x) {
 // an MFMA of either co-resident wavefront is in flight (scratch/mb/coissue.hip: 4 v_pk_fma per MFMA cost
 // 52 ns/slot vs 30 ns for 4 v_fma_f32, which hide completely), so the file is built with -fno-slp-vectorize.
 HD_DEVINL float silu_scaled(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x)); }
-// bf16 head / tail of a pair, each packed into one dword (element 0 in the low half)
-HD_DEVINL void bf16_split2(float y0, float y1, uint32_t& hi, uint32_t& lo) {
-    const uint32_t hp = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){y0, y1}, bf16x2_t));
-    const float l0 = y0 - __builtin_bit_cast(float, hp << 16);
-    const float l1 = y1 - __builtin_bit_cast(float, hp & 0xffff0000u);
-    hi = hp;
-    lo = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){l0, l1}, bf16x2_t));
-}
 
 // fp16 head / tail of a pair ("fp16x3", PREC 3): 11 + 11 significant bits, |y - h - l| <= 2^-22 |y| as long as the tail stays a
 // normal fp16 number (|y| >= 2^-2 after the operand scaling described in k_edge.hpp); below that the tail is a SUBNORMAL fp16
@@ -93,33 +81,9 @@ HD_DEVINL void f16_split2(float y0, float y1, uint32_t& hi, uint32_t& lo) {
     hi = __builtin_bit_cast(uint32_t, hp);
     lo = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){l0, l1}, f16x2_t));
 }
-// the two-way modes share every line but these two: PREC 1 = bf16 pieces, PREC 3 = fp16 pieces
-template <bool F16>
-HD_DEVINL void split2(float y0, float y1, uint32_t& hi, uint32_t& lo) {
-    if constexpr (F16) f16_split2(y0, y1, hi, lo);
-    else bf16_split2(y0, y1, hi, lo);
-}
-template <bool F16>
-HD_DEVINL f32x16 mma16(bf16x8 a, bf16x8 b, f32x16 c) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
+HD_DEVINL f32x16 mma_f16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 // fp16 mode: floor of the per-edge bound on the first-layer activation (keeps the scale's exponent arithmetic in range)
 #define HD_F16_FLOOR 9.5367431640625e-07f      // 2^-20
-#define HD_TWOWAY(p) ((p) == 1 || (p) == 3)
-
-// three-way split (head, middle, tail: 24 significant bits, |y - h - m - l| <= 2^-27 |y|) for the bf16x6 contraction
-HD_DEVINL void bf16_split3(float y0, float y1, uint32_t& hi, uint32_t& mid, uint32_t& lo) {
-    const uint32_t hp = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){y0, y1}, bf16x2_t));
-    const float r0 = y0 - __builtin_bit_cast(float, hp << 16);
-    const float r1 = y1 - __builtin_bit_cast(float, hp & 0xffff0000u);
-    const uint32_t mp = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){r0, r1}, bf16x2_t));
-    const float s0 = r0 - __builtin_bit_cast(float, mp << 16);
-    const float s1 = r1 - __builtin_bit_cast(float, mp & 0xffff0000u);
-    hi = hp;
-    mid = mp;
-    lo = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){s0, s1}, bf16x2_t));
-}
 
 // compile-time loop: f(std::integral_constant<int, I>) for I = 0..N-1
 template <int I, int N, typename F>

@@ -42,7 +42,7 @@ static int fail(int code, const std::string& msg) {
 // fused: B = 128 3.10 vs 3.27, B = 160 3.73 vs 3.78, B = 192 4.28 vs 4.25, B = 224 4.88 vs 4.74)
 #define HD_FUSE_MIN_ROWS 5400
 // fp16x3 mode: batches with fewer active rows than this run the node update as the three launches of k_node_split.hpp (32 x 32
-// output tiles, four K quarters per workgroup) instead of the fused k_node<..., F16> (one workgroup per 32 rows); bit-identical
+// output tiles, four K quarters per workgroup) instead of the fused k_node (one workgroup per 32 rows); bit-identical
 #define HD_NODE_SPLIT_MAX_ROWS 2048
 // topologies with at most this many edge tiles (a third more in fp32) run k_edge_split (one tile per workgroup, columns
 // over its four wavefronts) instead of k_edge (one tile per wavefront); bit-identical, see k_edge_split.hpp
@@ -68,7 +68,7 @@ struct hd_handle {
     int H, fin, F, D, NS;       // NS: 32-column sub-tiles per k_gemm workgroup tile
     // arithmetic of the two kernel families, derived from cfg.precision and the width (hd_create):
     //   edge_mode 0 fp32 | 3 fp16x3      node_mode 0 fp32 (k_node_f32 / k_node_split_f32 / k_gemm_r16) | 3 fp16 two-piece
-    //   precision 0: 0 / 0;  3: 3 / 3 (H >= 128), else 3 / 0        (1 = bf16x3 and 2 = bf16x6 were retired in ABI 12)
+    //   precision 0: 0 / 0;  3: 3 / 3 (H >= 128), else 3 / 0        (codes 1 and 2 were retired in ABI 12)
     // `scaled`: the edge model runs in the domain scaled by -log2(e) (fp16x3, silu_scaled in common.hpp)
     int edge_mode, node_mode;
     bool scaled;
@@ -465,7 +465,7 @@ static void pack_edge_w2(std::vector<float>& dst, size_t off, int H, const float
                     }
 }
 
-// FP16 node kernel (k_node<..., F16>): [k-step s][column tile ct][hi|lo][64 lanes][8] halves, k = 16s + 8*(lane>>5) + i,
+// FP16 node kernel (k_node): [k-step s][column tile ct][hi|lo][64 lanes][8] halves, k = 16s + 8*(lane>>5) + i,
 // col = 32ct + (lane&31) - the same byte size as an fp32 image - holding the two FP16 pieces of W x 2^k (largest |element| in
 // [2^14, 2^15)).  Returns 2^k;
 // *l1 = max over output columns of sum_k |W[col][k]| (the constant of the kernel's row bounds).
@@ -1162,11 +1162,11 @@ static void gemm_r16(hd_handle* h, int epi, bool agg, const R16Args& g, hipStrea
     launch_r16<1>(epi, agg, g, s);      // 32-row workgroups (RT = 2) were measured: slower up to B = 64, equal above (profiles/r03_r16_sweep2.log)
 }
 
-// Fused node update in two-piece FP16 arithmetic (k_node<..., F16>), 32-row workgroups.
+// Fused node update in two-piece FP16 arithmetic (k_node), 32-row workgroups.
 template <int H>
-static int node_lds_bytes(bool upd, int np = 2) {        // region 0: the two fp16 pieces of X; region 1: those of T / the fp32 staging tile
-    const int r1 = std::max(32 * (H + 8) * 2 * np, 32 * (H + 4) * 4);
-    return 32 * ((upd ? 2 * H : H) + 8) * 2 * np + r1;
+static int node_lds_bytes(bool upd) {                    // region 0: the two fp16 pieces of X; region 1: those of T / the fp32 staging tile
+    const int r1 = std::max(32 * (H + 8) * 2 * 2, 32 * (H + 4) * 4);
+    return 32 * ((upd ? 2 * H : H) + 8) * 2 * 2 + r1;
 }
 
 template <int H>
@@ -1185,9 +1185,9 @@ static void launch_node_hw(bool upd, int nab, int mode, const NodeArgs& a, hipSt
     }
     if constexpr (H >= 128) {                              // two-piece FP16 (fp16x3 mode; narrower widths run the fp32 node kernels)
         const int lds = node_lds_bytes<H>(upd);
-        if (!upd) hipLaunchKernelGGL((k_node<H, NW, false, 1, 2, true>), grid, block, lds, s, a);
-        else if (nab == 1) hipLaunchKernelGGL((k_node<H, NW, true, 1, 2, true>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((k_node<H, NW, true, 2, 2, true>), grid, block, lds, s, a);
+        if (!upd) hipLaunchKernelGGL((k_node<H, NW, false, 1>), grid, block, lds, s, a);
+        else if (nab == 1) hipLaunchKernelGGL((k_node<H, NW, true, 1>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((k_node<H, NW, true, 2>), grid, block, lds, s, a);
     }
 }
 
@@ -1197,9 +1197,9 @@ static int prepare_node_hw() {
     HIP_TRY(hipFuncSetAttribute((const void*)k_node_f32<H, NW, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, node_f32_lds_bytes<H>(true)));
     HIP_TRY(hipFuncSetAttribute((const void*)k_node_f32<H, NW, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, node_f32_lds_bytes<H>(true)));
     if constexpr (H >= 128) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_node<H, NW, false, 1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, node_lds_bytes<H>(false)));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_node<H, NW, true, 1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, node_lds_bytes<H>(true)));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_node<H, NW, true, 2, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, node_lds_bytes<H>(true)));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_node<H, NW, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, node_lds_bytes<H>(false)));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_node<H, NW, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, node_lds_bytes<H>(true)));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_node<H, NW, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, node_lds_bytes<H>(true)));
     }
     return HD_OK;
 }
@@ -1388,7 +1388,7 @@ static int launch_edge_h(hd_handle* h, bool coord, const EdgeArgs& a, hipStream_
 #endif
     if constexpr (H >= 128) {
         // at most 512 tiles: one tile per workgroup, columns split over its four wavefronts (k_edge_split.hpp; bit-identical
-        // to k_edge in every precision mode, a quarter of the serial MFMA chain per wavefront)
+        // to k_edge in both precision modes, a quarter of the serial MFMA chain per wavefront)
         const int mode = prec;
         // measured break-even (profiles/history/r02_split_sweep.log): between 490 and 654 tiles in the 16-bit split modes, between 654 and 870
         // in fp32 (the longer MFMA chain has more to gain from the split)
@@ -1420,7 +1420,7 @@ static int launch_edge_h(hd_handle* h, bool coord, const EdgeArgs& a, hipStream_
             EdgeArgs m = a;
             m.n_wg = R * h->n_cu;
             const dim3 mgrid(m.n_wg + (a.n_tiles - 4 * m.n_wg));
-            const int ldsm = std::max(edge_lds_bytes<H>(), edge_split_lds_bytes<H, 0>());
+            const int ldsm = std::max(edge_lds_bytes<H>(), edge_split_lds_bytes<H>());
             if (mode == 0) {
                 if (coord) hipLaunchKernelGGL((k_edge_mixed<H, true, 0>), mgrid, block, ldsm, s, m);
                 else hipLaunchKernelGGL((k_edge_mixed<H, false, 0>), mgrid, block, ldsm, s, m);
@@ -1457,7 +1457,7 @@ static int prepare_edge_h() {
         HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, false, 3, HD_EDGE_SAVE | HD_EDGE_UNSCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, true, 3, HD_EDGE_UNSCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, false, 3, HD_EDGE_UNSCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        const int m0 = std::max(edge_lds_bytes<H>(), edge_split_lds_bytes<H, 0>());
+        const int m0 = std::max(edge_lds_bytes<H>(), edge_split_lds_bytes<H>());
         HIP_TRY(hipFuncSetAttribute((const void*)k_edge_mixed<H, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, m0));
         HIP_TRY(hipFuncSetAttribute((const void*)k_edge_mixed<H, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, m0));
         HIP_TRY(hipFuncSetAttribute((const void*)k_edge_mixed<H, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, m0));

@@ -15,13 +15,10 @@
 // sums below are invariant under 4-row shifts of a piece inside a tile, so a sample's bits do not depend on its
 // batch neighbours (hd_topology_create).
 
-// SiLU of the fp32 and bf16x6 edge kernels: the 5-instruction silu_fast (round 3; -2 % / -2.4 % on the edge kernels against the
+// SiLU of the fp32 edge kernel: the 5-instruction silu_fast (round 3; -2 % on the edge kernel against the
 // compensated silu_f of round 2, at unchanged distance to the float64 oracle and with every golden vector still inside the
 // bar: the exponent argument is off by <= |x| 1.7e-7 where the value is saturated anyway).  -DHD_F32_SILU=silu_f
-// -DHD_X6_SILU=silu_f builds the round-2 form.
-#ifndef HD_X6_SILU
-#define HD_X6_SILU silu_fast
-#endif
+// builds the round-2 form.
 #ifndef HD_F32_SILU
 #define HD_F32_SILU silu_fast
 #endif
@@ -59,7 +56,7 @@ struct EdgeArgs {
 // contraction to get them back (k_edge_bwd<., ., 0, ., true>).  Layout = the accumulator's: one 16-byte store per lane and
 // (column tile, row quad), 1 KiB per wavefront instruction; 32 H floats per tile like a row-major [32][H] block.
 constexpr int HD_EDGE_SAVE = 256;
-// Second such flag (PREC 3 only): the fp16x3 kernel on UNSCALED inputs.  The sampler's two-way modes run the edge model in a domain
+// Second such flag (PREC 3 only): the fp16x3 kernel on UNSCALED inputs.  The sampler's fp16x3 mode runs the edge model in a domain
 // scaled by c = -log2(e) (the factor sits in the packed weights, so exp(-x) is a bare v_exp_f32); the training forward works on the
 // parameters themselves - AB rows from a plain GEMM, w_r / w_d / b2 / wa as they are - and pays the multiplication by c in front of
 // every exponential instead (one VALU instruction per activation).  The image scalars come from device memory (EdgeArgs.dscal).
@@ -85,10 +82,7 @@ __global__ void __launch_bounds__(256) k_ab_rowmax(AbMaxArgs a) {
     if (lane == 0) { a.out[2 * (size_t)row] = ma; a.out[2 * (size_t)row + 1] = mb; }
 }
 
-// INSTANTIATED since round 6 (ABI 12): PREC 0 and PREC 3.  The branches for PREC 1 ("bf16x3": the same two-way loop on bf16 pieces,
-// v_mfma_f32_32x32x16_bf16) and PREC 2 ("bf16x6": three-way bf16 split, six MFMAs, 16-wide K chunks) are the retired arithmetics of
-// rounds 1-5; they remain in the templates as the form the fp16x3 path specialises (split2<F16>, mma16<F16>) and are compiled by no
-// launch site (EXPERIMENTS.md sections Q, R describe them).
+// Two arithmetics (the retired bf16x3 / bf16x6 codes 1 and 2: EXPERIMENTS.md sections Q, R).
 // PREC 0: exact fp32 (v_mfma_f32_32x32x2_f32) - the instruction runs on the SIMD's packed-fp32 datapath and nothing overlaps with it
 // (DESIGN.md section 4): unscaled domain, fp32 node GEMMs.
 // PREC 3: "fp16x3" - both operands split into an fp16 head and tail (a = ah + al), the product formed as ah*bh + al*bh + ah*bl with
@@ -123,13 +117,6 @@ HD_DEVINL void lds_wait4(V (&f)[4]) {
     asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]) : "i"(N));
 }
 
-template <typename V, unsigned O0, unsigned O1>
-HD_DEVINL void lds_read2f(V (&f)[2], unsigned addr) {
-    asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4" : "=&v"(f[0]), "=&v"(f[1]) : "v"(addr), "i"(O0), "i"(O1));
-}
-template <int N, typename V>
-HD_DEVINL void lds_wait2f(V (&f)[2]) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(f[0]), "+v"(f[1]) : "i"(N)); }
-
 // x[lane] + x[lane ^ 32] in every lane, on the VALU (gfx950 v_permlane32_swap: upper half of the first operand
 // <-> lower half of the second) instead of a ds_bpermute round trip.  The s_nops cover the VALU-write ->
 // permlane-read and permlane-write -> VALU-read hazards, which hipcc does not track through inline asm.
@@ -152,7 +139,7 @@ HD_DEVINL void xhalf_sum4(float (&x)[4]) {
     for (int k = 0; k < 4; ++k) x[k] = lo[k] + hi[k];
 }
 
-// AB row gathers of the bf16x3 edge kernel: two 16-byte loads (A_i quad, B_j quad) as inline asm, released by a
+// AB row gathers of the edge kernel: two 16-byte loads (A_i quad, B_j quad) as inline asm, released by a
 // hand-counted s_waitcnt vmcnt that names their registers.  Compiler-visible loads cannot be used next to the
 // W2 stream: hipcc treats global_load_lds as a second vmcnt event type, assumes mixed events complete out of
 // order and waits vmcnt(0) - i.e. for the stream it has just started - before the first use of a gathered row.
@@ -199,15 +186,12 @@ HD_DEVINL void vm_wait2(f32x4& va, f32x4& vb) {
 }
 
 // byte offset (from the lane's base) of a B fragment inside a chunk image
-//   bf16x3: unit u = (k-step, column tile), hl = head (0) / tail (1);   fp32: fragment u = (q, column tile)
+//   fp16x3: unit u = (k-step, column tile), hl = head (0) / tail (1);   fp32: fragment u = (q, column tile)
 template <int NCT>
-constexpr unsigned frag_off_bf(int u, int hl) { return (unsigned)((((hl * 2 + u / NCT) * NCT + u % NCT) * 64) * 16); }
+constexpr unsigned frag_off_f16(int u, int hl) { return (unsigned)((((hl * 2 + u / NCT) * NCT + u % NCT) * 64) * 16); }
 constexpr unsigned frag_off_f32(int u) { return (unsigned)(u * 64 * 16); }
-//   bf16x6: one k-step per chunk, part p = head / middle / tail, column tile ct
-template <int NCT>
-constexpr unsigned frag_off_x6(int p, int ct) { return (unsigned)((p * NCT + ct) * 64 * 16); }
 
-// ABL: ablation switches for bottleneck hunting (never set in production launches; env HD_ABLATE, H=256 bf16x3 GCL):
+// ABL: ablation switches for bottleneck hunting (never set in production launches; env HD_ABLATE, H=256 fp16x3 GCL):
 //   1 = skip the epilogue, 2 = skip operand generation (SiLU etc.), 4 = no per-chunk barrier / W2 streaming,
 //   8 = no AB row gathers, 16 = record per-wave cycle stamps + HW placement (hd_debug_edge_trace, scratch/edge_trace.py),
 //   32 = barrier kept, W2 stream dropped; 64 = W2 stream kept, barrier dropped (round 5: which half of "4" costs what);
@@ -215,19 +199,19 @@ constexpr unsigned frag_off_x6(int p, int ct) { return (unsigned)((p * NCT + ct)
 //
 // One workgroup = one 128-edge workgroup-tile (4 wavefronts x 32 edges), two workgroups per CU.  Forms that were built and
 // measured slower: a persistent one that walks several tiles per workgroup (spilled); the pipelined one-wave-per-SIMD form of
-// round 1 for bf16x3 (scratch/experiments/k_edge_pipelined.hpp); its round-2 successor for fp32 with the epilogue of tile t
-// riding under the MFMAs of tile t+1 (scratch/experiments/k_edge_f32p.hpp: bit-identical, 15 % slower - nothing overlaps with
-// the fp32 MFMA inside a wavefront); the same for bf16x6 (k_edge_x6p.hpp: no faster - the W2 stream and
-// the barrier have no second wavefront to hide behind).
+// round 1 for the two-way loop (scratch/experiments/k_edge_pipelined.hpp); its round-2 successor for fp32 with the epilogue of
+// tile t riding under the MFMAs of tile t+1 (scratch/experiments/k_edge_f32p.hpp: bit-identical, 15 % slower - nothing overlaps
+// with the fp32 MFMA inside a wavefront).
 // The body of k_edge as a device function: `bid` / `nwt` = this workgroup's index among / the number of the launch's
 // whole-tile workgroups (k_edge: blockIdx.x / n_wg; k_edge_mixed: the first n_wg blocks of the grid), `smem` the dynamic LDS
 // (W2 double buffer + wave scratch), `wrd_s` the separate 4H-float LDS object described below.
 template <int H, bool COORD, int PREC, int ABL>
 HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, const int bid, const int nwt) {
+    static_assert(PREC == 0 || PREC == 3, "exact fp32 or fp16x3");
     constexpr int NCT = H / 32;          // 32-column tiles
-    constexpr int KC = PREC == 2 ? 16 : 32;          // K chunk width (bf16x6: one MFMA k-step, its image is 1.5x as dense)
+    constexpr int KC = 32;               // K chunk width
     constexpr int NCH = H / KC;          // K chunks
-    constexpr int CHF = PREC == 2 ? 24 * H : 32 * H;   // floats per W2 chunk image
+    constexpr int CHF = 32 * H;          // floats per W2 chunk image
     static_assert(CHF % 1024 == 0, "a chunk image is streamed in 1 KiB pieces, four waves");
     // (ABL bit 128, measurement only: a quarter of the stream - what keeping the W2 heads resident and sharing the tails between
     // eight wavefronts would leave; results are garbage, the time is what the DMA volume is worth)
@@ -337,7 +321,7 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
             }
         }
     };
-    // four values at a time, stage by stage (pre-activation, exp, +1, rcp, product, bf16 split): written per
+    // four values at a time, stage by stage (pre-activation, exp, +1, rcp, product, fp16 split): written per
     // value hipcc schedules each exp -> add -> rcp -> mul chain back to back, which costs an s_nop after every
     // transcendental (forwarding hazard) and a dependent-issue stall per step
     auto make_quad = [&](f32x4 av, f32x4 bv, f32x4 wr4, f32x4 wd4, uint32_t (&hi)[2], uint32_t (&lo)[2]) {
@@ -349,22 +333,22 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
 #pragma unroll
         for (int j = 0; j < 4; ++j) pre[j] = __builtin_fmaf(d0, wd4[j], pre[j]);
         if constexpr (ABL & 2) {
-            bf16_split2(av[0], av[1], hi[0], lo[0]);
-            bf16_split2(av[2], av[3], hi[1], lo[1]);
+            f16_split2(av[0], av[1], hi[0], lo[0]);
+            f16_split2(av[2], av[3], hi[1], lo[1]);
             return;
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) e[j] = __builtin_amdgcn_exp2f((ABL & HD_EDGE_UNSCALED) ? pre[j] * HD_NEG_LOG2E : pre[j]);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] = PREC == 3 ? __builtin_fmaf(e[j], f16_inv, f16_inv) : 1.0f + e[j];
+        for (int j = 0; j < 4; ++j) e[j] = __builtin_fmaf(e[j], f16_inv, f16_inv);
 #pragma unroll
         for (int j = 0; j < 4; ++j) e[j] = __builtin_amdgcn_rcpf(e[j]);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) pre[j] *= e[j];             // PREC 3: row scale x the activation
-        split2<PREC == 3>(pre[0], pre[1], hi[0], lo[0]);
-        split2<PREC == 3>(pre[2], pre[3], hi[1], lo[1]);
+        for (int j = 0; j < 4; ++j) pre[j] *= e[j];             // row scale x the activation
+        f16_split2(pre[0], pre[1], hi[0], lo[0]);
+        f16_split2(pre[2], pre[3], hi[1], lo[1]);
     };
-    auto make_P_bf = [&](int c, u32x4 (&ph)[2], u32x4 (&pl)[2]) {
+    auto make_P_f16 = [&](int c, u32x4 (&ph)[2], u32x4 (&pl)[2]) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const f32x4 wr4 = *reinterpret_cast<const f32x4*>(wrd_s + 32 * c + 16 * hh + 4 * u);
@@ -376,49 +360,20 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
         }
     };
 
-    // bf16x6: four first-layer activations (unscaled domain, compensated SiLU as in fp32 mode) -> head / middle / tail dwords
-    auto make_quad_x6 = [&](f32x4 av, f32x4 bv, f32x4 wr4, f32x4 wd4, uint32_t (&hi)[2], uint32_t (&mi)[2], uint32_t (&lo)[2]) {
-        float y[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float pre = av[j] + bv[j];
-            pre = __builtin_fmaf(radial, wr4[j], pre);
-            pre = __builtin_fmaf(d0, wd4[j], pre);
-            y[j] = (ABL & 2) ? pre : HD_X6_SILU(pre);
-        }
-        if constexpr (ABL & 2) {
-            hi[0] = mi[0] = lo[0] = __builtin_bit_cast(uint32_t, y[0] + y[1]); hi[1] = mi[1] = lo[1] = __builtin_bit_cast(uint32_t, y[2] + y[3]);
-            return;
-        }
-        bf16_split3(y[0], y[1], hi[0], mi[0], lo[0]);
-        bf16_split3(y[2], y[3], hi[1], mi[1], lo[1]);
-    };
     // Software pipeline: the operands of chunk c+1 are produced (VALU) while the matrix pipe works on
     // chunk c; the AB rows are fetched two chunks ahead.
     float Pc[16];
-    u32x4 phc[2], plc[2];                  // bf16x3: head / tail of the 16 operand values, 8 bf16 per k-step
+    u32x4 phc[2], plc[2];                  // fp16x3: head / tail of the 16 operand values, 8 fp16 per k-step
     // Both precision modes fetch the AB rows with the hand-counted inline-asm loads (see vm_load2): a compiler-visible
     // load next to the W2 stream makes hipcc wait vmcnt(0) - i.e. for the stream it has just started - every chunk.
     constexpr int NQ = KC / 8;             // row quads per lane per chunk
-    u32x4 xh, xm, xl;                      // bf16x6: head / middle / tail of the 8 operand values of the chunk
 #pragma unroll
     for (int u = 0; u < NQ; ++u) rows_issue(u, 0);
-    if constexpr (NQ == 4) asm volatile("s_waitcnt vmcnt(0)" : "+v"(pa[0]), "+v"(pa[1]), "+v"(pa[2]), "+v"(pa[3]),
-                                                              "+v"(pb[0]), "+v"(pb[1]), "+v"(pb[2]), "+v"(pb[3]));
-    else asm volatile("s_waitcnt vmcnt(0)" : "+v"(pa[0]), "+v"(pa[1]), "+v"(pb[0]), "+v"(pb[1]));
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(pa[0]), "+v"(pa[1]), "+v"(pa[2]), "+v"(pa[3]),
+                                        "+v"(pb[0]), "+v"(pb[1]), "+v"(pb[2]), "+v"(pb[3]));
     __syncthreads();               // chunk 0 landed in every wave's share (w_r / w_d staged on the first pass)
     if constexpr (PREC == 0) make_P(0, Pc);
-    else if constexpr (HD_TWOWAY(PREC)) make_P_bf(0, phc, plc);
-    else {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const f32x4 wr4 = *reinterpret_cast<const f32x4*>(wrd_s + 8 * hh + 4 * u);
-            const f32x4 wd4 = *reinterpret_cast<const f32x4*>(wrd_s + H + 8 * hh + 4 * u);
-            uint32_t hi[2], mi[2], lo[2];
-            make_quad_x6(pa[u], pb[u], wr4, wd4, hi, mi, lo);
-            xh[2 * u] = hi[0]; xh[2 * u + 1] = hi[1]; xm[2 * u] = mi[0]; xm[2 * u + 1] = mi[1]; xl[2 * u] = lo[0]; xl[2 * u + 1] = lo[1];
-        }
-    }
+    else make_P_f16(0, phc, plc);
 #pragma unroll
     for (int u = 0; u < NQ; ++u) rows_issue(u, NCH > 1 ? 1 : 0);
 
@@ -449,8 +404,7 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
         if constexpr (!(ABL & 4) && !(ABL & 64)) {
             // chunk c landed in LDS and every wave is done with the other buffer.  The only VMEM operations younger
             // than chunk c's stream are the 8 row gathers of the previous iteration.
-            if constexpr (PREC == 2) { if (c > 0) asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory"); }
-            else if (c > 0) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
+            if (c > 0) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
             // The stream of the next chunk is issued unconditionally further down (the last chunk re-requests chunk 0,
             // unused unless a further tile follows): with the stream inside a branch hipcc has to assume "no stream in
             // flight" at the join and waits vmcnt(0) - i.e. for the stream itself - before the first use of the
@@ -510,8 +464,8 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
                     else vm_load2o<16 * q>(pa[q], pb[q], Arow_n2, Brow_n2);
                 }
             });
-        } else if constexpr (HD_TWOWAY(PREC)) {
-            // chunk image: [hi|lo][2 k-steps][NCT][64 lanes][8 bf16]; lane (h, n), element i of step s is
+        } else {
+            // chunk image: [hi|lo][2 k-steps][NCT][64 lanes][8 fp16]; lane (h, n), element i of step s is
             // W2[32ct + n][32c + 16h + 8s + i] - the same k order as P[8s + i].  Units u = (k-step, ct) of
             // three MFMAs (head*head, tail*head, head*tail) on one accumulator, two units per group.
             constexpr int NG = NCT;                     // 2*NCT units / 2
@@ -524,20 +478,20 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
             f32x4 wrq[2], wdq[2];
             wrq[0] = *reinterpret_cast<const f32x4*>(wr_n);
             wdq[0] = *reinterpret_cast<const f32x4*>(wd_n);
-            bf16x8 f0[4], f1[4];
-            lds_read4<bf16x8, frag_off_bf<NCT>(0, 0), frag_off_bf<NCT>(0, 1), frag_off_bf<NCT>(1, 0), frag_off_bf<NCT>(1, 1)>(f0, wb_lds);
+            f16x8 f0[4], f1[4];
+            lds_read4<f16x8, frag_off_f16<NCT>(0, 0), frag_off_f16<NCT>(0, 1), frag_off_f16<NCT>(1, 0), frag_off_f16<NCT>(1, 1)>(f0, wb_lds);
             // the stream for the next chunk goes out behind the first fragment reads: its eight LDS-DMA issues cover
             // the LDS latency the first MFMA group would otherwise wait out
             if constexpr (!(ABL & 4) && !(ABL & 32)) issue_chunk(c + 1 < NCH ? c + 1 : 0, buf ^ 1);
             static_for<0, NG>([&](auto Gc) {
                 constexpr int g = decltype(Gc)::value;
-                bf16x8(&cur)[4] = (g & 1) ? f1 : f0;
-                bf16x8(&nxt)[4] = (g & 1) ? f0 : f1;
+                f16x8(&cur)[4] = (g & 1) ? f1 : f0;
+                f16x8(&nxt)[4] = (g & 1) ? f0 : f1;
                 lds_wait4<0>(cur);
                 if constexpr (g + 1 < NG) {
                     constexpr int u = 2 * (g + 1);
-                    lds_read4<bf16x8, frag_off_bf<NCT>(u, 0), frag_off_bf<NCT>(u, 1), frag_off_bf<NCT>(u + 1, 0),
-                              frag_off_bf<NCT>(u + 1, 1)>(nxt, wb_lds);
+                    lds_read4<f16x8, frag_off_f16<NCT>(u, 0), frag_off_f16<NCT>(u, 1), frag_off_f16<NCT>(u + 1, 0),
+                              frag_off_f16<NCT>(u + 1, 1)>(nxt, wb_lds);
                 }
                 // The next chunk's 8 operand pairs are produced in the FIRST half of the groups and the AB
                 // rows of chunk c+2 are requested as soon as a quad of chunk c+1 has been consumed: the
@@ -566,22 +520,22 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
                 }
                 constexpr int u0 = 2 * g, u1 = 2 * g + 1;
                 constexpr int s0 = u0 / NCT, c0 = u0 % NCT, s1 = u1 / NCT, c1 = u1 % NCT;
-                const bf16x8 A_h0 = __builtin_bit_cast(bf16x8, phc[s0]), A_l0 = __builtin_bit_cast(bf16x8, plc[s0]);
-                const bf16x8 A_h1 = __builtin_bit_cast(bf16x8, phc[s1]), A_l1 = __builtin_bit_cast(bf16x8, plc[s1]);
+                const f16x8 A_h0 = __builtin_bit_cast(f16x8, phc[s0]), A_l0 = __builtin_bit_cast(f16x8, plc[s0]);
+                const f16x8 A_h1 = __builtin_bit_cast(f16x8, phc[s1]), A_l1 = __builtin_bit_cast(f16x8, plc[s1]);
                 if constexpr (ABL & 1024) {
                     // measurement only (round 6): NO matrix instruction - operands and fragments are consumed by an empty asm, so
                     // every vector / LDS / memory instruction of the kernel stays: the time of the VECTOR side alone, which is what a
                     // wave-specialised form (one matrix wavefront + one vector wavefront per SIMD) cannot go below
                     asm volatile("" :: "v"(A_h0), "v"(A_l0), "v"(A_h1), "v"(A_l1), "v"(cur[0]), "v"(cur[1]), "v"(cur[2]), "v"(cur[3]));
                 } else {
-                if constexpr (FIRST && s0 == 0) acc[c0] = mma16<PREC == 3>(A_h0, cur[0], f32x16{});
-                else acc[c0] = mma16<PREC == 3>(A_h0, cur[0], acc[c0]);
-                if constexpr (FIRST && s1 == 0) acc[c1] = mma16<PREC == 3>(A_h1, cur[2], f32x16{});
-                else acc[c1] = mma16<PREC == 3>(A_h1, cur[2], acc[c1]);
-                acc[c0] = mma16<PREC == 3>(A_l0, cur[0], acc[c0]);
-                acc[c1] = mma16<PREC == 3>(A_l1, cur[2], acc[c1]);
-                acc[c0] = mma16<PREC == 3>(A_h0, cur[1], acc[c0]);
-                acc[c1] = mma16<PREC == 3>(A_h1, cur[3], acc[c1]);
+                if constexpr (FIRST && s0 == 0) acc[c0] = mma_f16(A_h0, cur[0], f32x16{});
+                else acc[c0] = mma_f16(A_h0, cur[0], acc[c0]);
+                if constexpr (FIRST && s1 == 0) acc[c1] = mma_f16(A_h1, cur[2], f32x16{});
+                else acc[c1] = mma_f16(A_h1, cur[2], acc[c1]);
+                acc[c0] = mma_f16(A_l0, cur[0], acc[c0]);
+                acc[c1] = mma_f16(A_l1, cur[2], acc[c1]);
+                acc[c0] = mma_f16(A_h0, cur[1], acc[c0]);
+                acc[c1] = mma_f16(A_h1, cur[3], acc[c1]);
                 }
 #pragma unroll
                 for (int k = 0; k < 6; ++k) {            // interleave: 1 MFMA, then up to 4 VALU
@@ -591,86 +545,15 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
             });
 #pragma unroll
             for (int st = 0; st < 2; ++st) { phc[st] = phn[st]; plc[st] = pln[st]; }
-        } else {
-            // bf16x6.  Chunk image: [head|middle|tail][NCT][64 lanes][8 bf16]; lane (h, n), element i is W2[32ct + n][16c + 8h + i],
-            // the k order of the operand dwords.  Per pair of column tiles two stages of six MFMAs, the two accumulators
-            // alternating: stage A on the tail and middle fragments (h*L, h*M, m*M - the small terms first), stage B on the
-            // head fragments (h*H, m*H, l*H).  A stage's fragments are requested while the previous stage's MFMAs run.
-            const float* wr_n = wrd_s + 16 * cn1 + 8 * hh;
-            const float* wd_n = wrd_s + H + 16 * cn1 + 8 * hh;
-            u32x4 nh, nm, nl;
-            // fragments are requested TWO stages ahead (pair g+1's while pair g runs): with one stage (192 matrix-pipe
-            // cycles) of lead the LDS latency under eight streaming waves per CU was regularly exposed
-            bf16x8 fA[2][4], fB[2][2];
-            auto req_A = [&](auto G, bf16x8 (&f)[4]) {
-                constexpr int g = decltype(G)::value;
-                lds_read4<bf16x8, frag_off_x6<NCT>(2, 2 * g), frag_off_x6<NCT>(2, 2 * g + 1), frag_off_x6<NCT>(1, 2 * g),
-                          frag_off_x6<NCT>(1, 2 * g + 1)>(f, wb_lds);
-            };
-            auto req_B = [&](auto G, bf16x8 (&f)[2]) {
-                constexpr int g = decltype(G)::value;
-                lds_read2f<bf16x8, frag_off_x6<NCT>(0, 2 * g), frag_off_x6<NCT>(0, 2 * g + 1)>(f, wb_lds);
-            };
-            req_A(std::integral_constant<int, 0>{}, fA[0]);
-            req_B(std::integral_constant<int, 0>{}, fB[0]);
-            if constexpr (!(ABL & 4) && !(ABL & 32)) issue_chunk(c + 1 < NCH ? c + 1 : 0, buf ^ 1);
-            const bf16x8 A_h = __builtin_bit_cast(bf16x8, xh), A_m = __builtin_bit_cast(bf16x8, xm), A_l = __builtin_bit_cast(bf16x8, xl);
-            static_for<0, NCT / 2>([&](auto Gc) {
-                constexpr int g = decltype(Gc)::value, c0 = 2 * g, c1 = 2 * g + 1, NP = NCT / 2;
-                bf16x8(&a4)[4] = fA[g & 1];
-                bf16x8(&b2f)[2] = fB[g & 1];
-                lds_wait4<2>(a4);                       // outstanding behind this pair's A request: its B request (2 reads)
-                if constexpr (g + 1 < NP) req_A(std::integral_constant<int, g + 1>{}, fA[(g + 1) & 1]);
-                // operands of the next chunk: quad g in the first two pairs, then its registers take the rows of chunk c+2
-                // (outstanding, oldest first: quads g..1 of chunk c+1, the stream pieces, quads 0..g-1 of chunk c+2)
-                if constexpr (g < 2) {
-                    vm_wait2<2 + GL_PER_WAVE>(pa[g], pb[g]);
-                    const f32x4 wr4 = *reinterpret_cast<const f32x4*>(wr_n + 4 * g);
-                    const f32x4 wd4 = *reinterpret_cast<const f32x4*>(wd_n + 4 * g);
-                    uint32_t hi[2], mi[2], lo[2];
-                    make_quad_x6(pa[g], pb[g], wr4, wd4, hi, mi, lo);
-                    nh[2 * g] = hi[0]; nh[2 * g + 1] = hi[1]; nm[2 * g] = mi[0]; nm[2 * g + 1] = mi[1]; nl[2 * g] = lo[0]; nl[2 * g + 1] = lo[1];
-                    if constexpr (ABL & 8) { pa[g] = f32x4{radial, d0, radial, d0}; pb[g] = pa[g]; }
-                    else vm_load2o<16 * g>(pa[g], pb[g], Arow_n2, Brow_n2);
-                }
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, a4[0], acc[c0], 0, 0, 0);
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, a4[1], acc[c1], 0, 0, 0);
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, a4[2], acc[c0], 0, 0, 0);
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, a4[3], acc[c1], 0, 0, 0);
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_m, a4[2], acc[c0], 0, 0, 0);
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_m, a4[3], acc[c1], 0, 0, 0);
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                }
-                // outstanding behind this pair's B request: the next pair's A request (4 reads), if there is one
-                if constexpr (g + 1 < NP) { lds_wait2f<4>(b2f); req_B(std::integral_constant<int, g + 1>{}, fB[(g + 1) & 1]); }
-                else lds_wait2f<0>(b2f);
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, b2f[0], acc[c0], 0, 0, 0);
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, b2f[1], acc[c1], 0, 0, 0);
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_m, b2f[0], acc[c0], 0, 0, 0);
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_m, b2f[1], acc[c1], 0, 0, 0);
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_l, b2f[0], acc[c0], 0, 0, 0);
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_l, b2f[1], acc[c1], 0, 0, 0);
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                }
-            });
-            xh = nh; xm = nm; xl = nl;
         }
     };
     if constexpr (PEEL) { chunk(std::true_type{}, 0); ++gc; }
 #pragma unroll 1
     for (int c = PEEL ? 1 : 0; c < NCH; ++c, ++gc) chunk(std::false_type{}, c);
 
-    {                                      // drain the (unused) last gathers before their registers are reused
-        if constexpr (NQ == 4) asm volatile("s_waitcnt vmcnt(0)" : "+v"(pa[0]), "+v"(pa[1]), "+v"(pa[2]), "+v"(pa[3]),
-                                                                  "+v"(pb[0]), "+v"(pb[1]), "+v"(pb[2]), "+v"(pb[3]));
-        else asm volatile("s_waitcnt vmcnt(0)" : "+v"(pa[0]), "+v"(pa[1]), "+v"(pb[0]), "+v"(pb[1]));
-    }
+    // drain the (unused) last gathers before their registers are reused
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(pa[0]), "+v"(pa[1]), "+v"(pa[2]), "+v"(pa[3]),
+                                        "+v"(pb[0]), "+v"(pb[1]), "+v"(pb[2]), "+v"(pb[3]));
     if constexpr (ABL & 16) ts2 = __builtin_readcyclecounter();
     if constexpr (ABL & 1024) {             // the untouched accumulators are opaque to the epilogue (no constant folding of its SiLUs)
 #pragma unroll
@@ -679,7 +562,7 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
             for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(acc[ct][r]));
     }
     if constexpr (ABL & HD_EDGE_SAVE) {
-        static_assert(!HD_TWOWAY(PREC) || (PREC == 3 && (ABL & HD_EDGE_UNSCALED)), "the saved pre-activations are those of the unscaled modes");
+        static_assert(PREC == 0 || (ABL & HD_EDGE_UNSCALED), "the saved pre-activations are those of the unscaled modes");
         if constexpr (PREC == 3) {         // the un-scaling fma of the epilogue (row scale x image scale out, bias in), done here for all tiles
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) {
@@ -726,10 +609,10 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
         const float wav = wrd_s[3 * H + 32 * ct + n];
-        if constexpr (!HD_TWOWAY(PREC)) {
+        if constexpr (PREC == 0) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float mv = PREC == 2 ? HD_X6_SILU(acc[ct][r]) : HD_F32_SILU(acc[ct][r]);
+                const float mv = HD_F32_SILU(acc[ct][r]);
                 acc[ct][r] = mv;
                 dot[r] = __builtin_fmaf(mv, wav, dot[r]);
             }
@@ -738,7 +621,7 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
             // runs each value's exp -> add -> rcp -> mul chain back to back through one or two registers and
             // the epilogue sits out the transcendental latency ~500 times.
             float e[16];
-            if constexpr (PREC == 3 && !(ABL & HD_EDGE_SAVE)) {
+            if constexpr (!(ABL & HD_EDGE_SAVE)) {
                 const float b2v = wrd_s[2 * H + 32 * ct + n];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[ct][r] = __builtin_fmaf(acc[ct][r], rsc[r >> 2][r & 3], b2v);
@@ -806,7 +689,7 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
         float att_mine = 1.0f;
         if (a.attention) {
             const float ba = a.ba_ptr ? *a.ba_ptr : a.ba;
-            if constexpr (!HD_TWOWAY(PREC)) att_mine = sigmoid_f(rowdot + ba);
+            if constexpr (PREC == 0) att_mine = sigmoid_f(rowdot + ba);
             else att_mine = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f((ABL & HD_EDGE_UNSCALED) ? (rowdot + ba) * HD_NEG_LOG2E : rowdot + ba));   // scaled domain
         }
         float w[16];

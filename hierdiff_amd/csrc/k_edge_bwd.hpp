@@ -58,10 +58,9 @@ struct EdgeBwdArgs {
 HD_DEVINL float dsilu_from_sigmoid(float x, float s) { return s * __builtin_fmaf(x, 1.0f - s, 1.0f); }
 
 // STAGE 0 = A, 1 = B.  One workgroup = four 32-row tiles (one per wavefront), grid = tiles / 4.
-// PREC 0: the two H x H contractions (stage A: pre2 = W2 P, stage B: dP = G2 W2) in exact fp32.  (The PREC 2 branches - the retired
-// `training_precision = "bf16x6"` of rounds 4-5: three-way bf16 split, six MFMAs per product - are compiled by no launch site since
-// ABI 12; everything around a contraction - first-layer recomputation, SiLU and its derivative, gate / head, the materialised
-// G2 / P / G1 tiles, per-tile partial sums - is the fp32 code of PREC 0 in every arithmetic.)
+// PREC 0: the two H x H contractions (stage A: pre2 = W2 P, stage B: dP = G2 W2) in exact fp32.  Everything around a contraction -
+// first-layer recomputation, SiLU and its derivative, gate / head, the materialised G2 / P / G1 tiles, per-tile partial sums - is
+// the fp32 code of PREC 0 in both arithmetics.
 // SAVED (stage A only, round 5): the forward pass kept pre2 (k_edge with HD_EDGE_SAVE, 32 H floats per tile in accumulator order); the
 // accumulators are loaded instead of recomputed - no weight stream, no MFMA, 32 16-byte loads per lane up front - and the stage is
 // the HBM-bound element-wise kernel it is at heart (reads pre2 + the gathered gradient rows, writes G2: 2 x 4 H bytes per edge row).
@@ -72,9 +71,10 @@ HD_DEVINL float dsilu_from_sigmoid(float x, float s) { return s * __builtin_fmaf
 template <int H, bool COORD, int STAGE, int PREC = 0, bool SAVED = false>
 __global__ __launch_bounds__(256, 2) void k_edge_bwd(EdgeBwdArgs a) {
     static_assert(!SAVED || STAGE == 0, "only stage A has something to load");
+    static_assert(PREC == 0 || PREC == 3, "exact fp32 or fp16x3");
     static_assert(PREC != 3 || (STAGE == 1 && H >= 128), "the fp16x3 contraction exists for stage B at widths 128 / 256");
-    constexpr int KC = (PREC == 2 || PREC == 3) ? 16 : 32;         // K chunk width
-    constexpr int NCT = H / 32, NCH = H / KC, CHF = PREC == 2 ? 24 * H : PREC == 3 ? 16 * H : 32 * H;   // CHF: floats per weight chunk image
+    constexpr int KC = PREC == 3 ? 16 : 32;                        // K chunk width
+    constexpr int NCT = H / 32, NCH = H / KC, CHF = PREC == 3 ? 16 * H : 32 * H;   // CHF: floats per weight chunk image
     extern __shared__ __attribute__((aligned(16))) float smem_b[];
     float* wbuf0 = smem_b;                       // [2][CHF] two K chunks of the weight image (double buffer)
     float* scr = smem_b + (SAVED ? 0 : 2 * CHF); // per wave: 32 phi + 96 unit dir + 32 ni + 32 nj + 32 radial + 32 d0 + 32 valid
@@ -208,47 +208,7 @@ __global__ __launch_bounds__(256, 2) void k_edge_bwd(EdgeBwdArgs a) {
         __syncthreads();                                         // chunk c is complete; nobody reads the other buffer any more
         if (c + 1 < NCH) { issue_chunk(c + 1); load_raw(c + 1, raw); }
         const float* wbuf = wbuf0 + (c & 1) * CHF;
-        if constexpr (PREC == 2) {
-            // one k-step of 16 per chunk: the lane's 8 operand values -> head / middle / tail dwords (k order = element order of the
-            // image: lane (hh, n) element i is W[32 ct + n][16 c + 8 hh + i]); per pair of column tiles two groups of six MFMAs on
-            // alternating accumulators, the small terms first (h*L, h*M, m*M | h*H, m*H, l*H), fragments requested a pair ahead
-            u32x4 xh, xm, xl;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                uint32_t hi[2], mi[2], lo[2];
-                bf16_split3(P[4 * u], P[4 * u + 1], hi[0], mi[0], lo[0]);
-                bf16_split3(P[4 * u + 2], P[4 * u + 3], hi[1], mi[1], lo[1]);
-                xh[2 * u] = hi[0]; xh[2 * u + 1] = hi[1]; xm[2 * u] = mi[0]; xm[2 * u + 1] = mi[1]; xl[2 * u] = lo[0]; xl[2 * u + 1] = lo[1];
-            }
-            const bf16x8 A_h = __builtin_bit_cast(bf16x8, xh), A_m = __builtin_bit_cast(bf16x8, xm), A_l = __builtin_bit_cast(bf16x8, xl);
-            const bf16x8* wf = reinterpret_cast<const bf16x8*>(wbuf) + lane;          // [piece][ct][64 lanes] x 16 B
-            bf16x8 fcur[6], fnxt[6];
-            auto load_f = [&](int g, bf16x8 (&f)[6]) {
-#pragma unroll
-                for (int p = 0; p < 3; ++p) { f[2 * p] = wf[(p * NCT + 2 * g) * 64]; f[2 * p + 1] = wf[(p * NCT + 2 * g + 1) * 64]; }
-            };
-            load_f(0, fcur);
-#pragma unroll
-            for (int g = 0; g < NCT / 2; ++g) {
-                if (g + 1 < NCT / 2) load_f(g + 1, fnxt);
-                const int c0 = 2 * g, c1 = 2 * g + 1;
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, fcur[4], acc[c0], 0, 0, 0);       // h * L
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, fcur[5], acc[c1], 0, 0, 0);
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, fcur[2], acc[c0], 0, 0, 0);       // h * M
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, fcur[3], acc[c1], 0, 0, 0);
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_m, fcur[2], acc[c0], 0, 0, 0);       // m * M
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_m, fcur[3], acc[c1], 0, 0, 0);
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, fcur[0], acc[c0], 0, 0, 0);       // h * H
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, fcur[1], acc[c1], 0, 0, 0);
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_m, fcur[0], acc[c0], 0, 0, 0);       // m * H
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_m, fcur[1], acc[c1], 0, 0, 0);
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_l, fcur[0], acc[c0], 0, 0, 0);       // l * H
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_l, fcur[1], acc[c1], 0, 0, 0);
-#pragma unroll
-                for (int k = 0; k < 6; ++k) fcur[k] = fnxt[k];
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else if constexpr (PREC == 3) {
+        if constexpr (PREC == 3) {
             // one k-step of 16 per chunk; image [hi | lo][column tile][64 lanes] x 16 B (k_pack_w2_f16c).  Per pair of column tiles six
             // MFMAs on alternating accumulators (h*H, l*H, h*L), fragments requested a pair ahead.
             u32x4 xh, xl;
@@ -265,12 +225,12 @@ __global__ __launch_bounds__(256, 2) void k_edge_bwd(EdgeBwdArgs a) {
             for (int g = 0; g < NCT / 2; ++g) {
                 if (g + 1 < NCT / 2) load_f(g + 1, fnxt);
                 const int c0 = 2 * g, c1 = 2 * g + 1;
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_h, fcur[0], acc[c0], 0, 0, 0);       // h * H
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_h, fcur[2], acc[c1], 0, 0, 0);
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_l, fcur[0], acc[c0], 0, 0, 0);       // l * H
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_l, fcur[2], acc[c1], 0, 0, 0);
-                acc[c0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_h, fcur[1], acc[c0], 0, 0, 0);       // h * L
-                acc[c1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_h, fcur[3], acc[c1], 0, 0, 0);
+                acc[c0] = mma_f16(A_h, fcur[0], acc[c0]);       // h * H
+                acc[c1] = mma_f16(A_h, fcur[2], acc[c1]);
+                acc[c0] = mma_f16(A_l, fcur[0], acc[c0]);       // l * H
+                acc[c1] = mma_f16(A_l, fcur[2], acc[c1]);
+                acc[c0] = mma_f16(A_h, fcur[1], acc[c0]);       // h * L
+                acc[c1] = mma_f16(A_h, fcur[3], acc[c1]);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) fcur[k] = fnxt[k];
                 __builtin_amdgcn_sched_barrier(0);

@@ -1,9 +1,8 @@
-// Edge kernel for very small batches (every precision mode): ONE 32-edge tile per workgroup, its H output columns split over
+// Edge kernel for very small batches (both precision modes): ONE 32-edge tile per workgroup, its H output columns split over
 // the four wavefronts.  Included through kernels.hpp after k_edge.hpp (same EdgeArgs, same tile tables, same weight image).
 //
 // Why: in k_edge a wavefront owns a whole 32-edge x H tile, i.e. a serial chain of H*H/64 fp32 MFMAs (1,024 at H = 256:
-// 65.5 k matrix-pipe cycles = 29 us) plus prologue and epilogue - 43 us per launch however few tiles there are (18 - 25 us
-// in the bf16 modes).  The
+// 65.5 k matrix-pipe cycles = 29 us) plus prologue and epilogue - 43 us per launch however few tiles there are.  The
 // reference's shipped sampling job is batch_size 2 (conf/sample/default.yaml:1-2): 56 tiles, 14 workgroups on a 256-CU
 // chip.  Here every tile is spread over the four SIMDs of a CU: wavefront w computes columns [w*H/4, (w+1)*H/4) - a quarter
 // of the MFMAs - with its W2 fragments going L2 -> registers directly (no LDS staging, no barrier in the loop: nothing is
@@ -12,31 +11,32 @@
 //
 // Bit-identical to k_edge<H, COORD, PREC> by construction, so a molecule's bits still do not depend on the size of its batch:
 //   * every output element sees the same MFMA chain (accumulator from b2, K chunks ascending; fp32: k-quad q, j;
-//     bf16x3: k-step s, then head*head, tail*head, head*tail; bf16x6: h*L, h*M, m*M, h*H, m*H, l*H per 16-wide chunk)
-//     on operands produced by the same expressions (k_edge's make_P / make_quad / make_quad_x6);
+//     fp16x3: k-step s, then head*head, tail*head, head*tail)
+//     on operands produced by the same expressions (k_edge's make_P / make_quad);
 //   * the row dot with w_a / w_7 is one FMA chain per lane over the column tiles in ascending order - here it is handed
 //     from wavefront to wavefront through LDS (three hand-offs) and finished by the same transposed reduction;
 //   * gate / tanh head, masked per-node sums and the cross-half add are the same expressions on the same operands.
 // tests/test_gpu_parity.py::test_small_batch_edge_kernel_is_bit_identical compares 1-, 2- and 6-molecule batches (this kernel)
-// with the same molecules inside a 40-molecule batch (k_edge), in every precision mode.
+// with the same molecules inside a 40-molecule batch (k_edge), in both precision modes.
 #pragma once
 #include "k_edge.hpp"
 
 // LDS of the split form besides wrd_s: operand tile + hand-off scratch, carved from one byte buffer so that k_edge_mixed can
 // place it in the dynamic LDS the whole-tile form uses for its W2 double buffer
-template <int H, int PREC>
+template <int H>
 constexpr int edge_split_lds_bytes() {
-    return (H / (PREC == 2 ? 16 : 32)) * (PREC == 2 ? 3 : 4) * 64 * 16 + (16 * 64 + 64 + 8 + 32 + 96 + 4 + 32) * 4;
+    return (H / 32) * 4 * 64 * 16 + (16 * 64 + 64 + 8 + 32 + 96 + 4 + 32) * 4;
 }
 
 // DEEP: the standalone launch (at most ~680 workgroups on 256 CUs: registers are free) keeps more K chunks of W2 fragments in
 // flight than the body inside k_edge_mixed, which shares a 256-register budget with the whole-tile form
 template <int H, bool COORD, int PREC, bool DEEP>
 HD_DEVINL void edge_split_body(const EdgeArgs& a, char* lds, float* wrd_s, const int tile) {
-    constexpr int KC = PREC == 2 ? 16 : 32;                          // K chunk width, as in k_edge
-    constexpr int NCT = H / 32, NCW = NCT / 4, NCH = H / KC, CHF = PREC == 2 ? 24 * H : 32 * H, NQ = KC / 8;
+    static_assert(PREC == 0 || PREC == 3, "exact fp32 or fp16x3");
+    constexpr int KC = 32;                                           // K chunk width, as in k_edge
+    constexpr int NCT = H / 32, NCW = NCT / 4, NCH = H / KC, CHF = 32 * H, NQ = KC / 8;
     static_assert(NCT % 4 == 0, "column tiles are dealt to four wavefronts");
-    constexpr int SL = PREC == 2 ? 3 : 4;                            // 16-byte slots per lane and chunk
+    constexpr int SL = 4;                                            // 16-byte slots per lane and chunk
     u32x4* opnd_s = reinterpret_cast<u32x4*>(lds);                   // [NCH * SL * 64] operand tile
     float* dot_x = reinterpret_cast<float*>(lds + NCH * SL * 64 * 16);   // [16 * 64] running row dots, handed from wavefront to wavefront
     float* att_s = dot_x + 16 * 64;                                  // [64] gate per (half, row slot) as wavefront 3 holds it
@@ -95,8 +95,10 @@ HD_DEVINL void edge_split_body(const EdgeArgs& a, char* lds, float* wrd_s, const
             w.b[u] = *reinterpret_cast<const f32x4*>(Brow + KC * c + 4 * u);
         }
     };
-    // operand registers: fp32 16 floats; bf16x3 head / tail of the two k-steps; bf16x6 head / middle / tail of the one k-step
-    struct Opnd { float P[PREC == 0 ? 16 : 1]; u32x4 ph[2], pl[2], xh, xm, xl; };
+    // operand registers: fp32 16 floats; fp16x3 head / tail of the two k-steps.  `keep` is never touched: it holds the struct at the
+    // size it had with the retired three-piece slots, because hipcc's code for <128, COORD, fp32> (register numbering, the place of
+    // one ds_read) differs once the struct fits 128 bytes; drop it with the next change to this kernel's arithmetic.
+    struct Opnd { float P[PREC == 0 ? 16 : 1]; u32x4 ph[2], pl[2], keep[3]; };
     auto finish_P = [&](int c, const Raw& w, Opnd& o) {
 #pragma unroll
         for (int u = 0; u < NQ; ++u) {
@@ -110,7 +112,7 @@ HD_DEVINL void edge_split_body(const EdgeArgs& a, char* lds, float* wrd_s, const
                     pre = __builtin_fmaf(d0, wd4[j], pre);
                     o.P[4 * u + j] = HD_F32_SILU(pre);
                 }
-            } else if constexpr (HD_TWOWAY(PREC)) {                  // k_edge's make_quad (scaled domain) + make_P_bf
+            } else {                                                 // k_edge's make_quad (scaled domain) + make_P_f16
                 float pre[4], ev[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) pre[j] = w.a[u][j] + w.b[u][j];
@@ -121,39 +123,24 @@ HD_DEVINL void edge_split_body(const EdgeArgs& a, char* lds, float* wrd_s, const
 #pragma unroll
                 for (int j = 0; j < 4; ++j) ev[j] = __builtin_amdgcn_exp2f(pre[j]);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) ev[j] = PREC == 3 ? __builtin_fmaf(ev[j], f16_inv, f16_inv) : 1.0f + ev[j];
+                for (int j = 0; j < 4; ++j) ev[j] = __builtin_fmaf(ev[j], f16_inv, f16_inv);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) ev[j] = __builtin_amdgcn_rcpf(ev[j]);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) pre[j] *= ev[j];
                 uint32_t hi[2], lo[2];
-                split2<PREC == 3>(pre[0], pre[1], hi[0], lo[0]);
-                split2<PREC == 3>(pre[2], pre[3], hi[1], lo[1]);
+                f16_split2(pre[0], pre[1], hi[0], lo[0]);
+                f16_split2(pre[2], pre[3], hi[1], lo[1]);
                 o.ph[u >> 1][2 * (u & 1)] = hi[0]; o.ph[u >> 1][2 * (u & 1) + 1] = hi[1];
                 o.pl[u >> 1][2 * (u & 1)] = lo[0]; o.pl[u >> 1][2 * (u & 1) + 1] = lo[1];
-            } else {                                                 // k_edge's make_quad_x6
-                float y[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float pre = w.a[u][j] + w.b[u][j];
-                    pre = __builtin_fmaf(radial, wr4[j], pre);
-                    pre = __builtin_fmaf(d0, wd4[j], pre);
-                    y[j] = HD_X6_SILU(pre);
-                }
-                uint32_t hi[2], mi[2], lo[2];
-                bf16_split3(y[0], y[1], hi[0], mi[0], lo[0]);
-                bf16_split3(y[2], y[3], hi[1], mi[1], lo[1]);
-                o.xh[2 * u] = hi[0]; o.xh[2 * u + 1] = hi[1]; o.xm[2 * u] = mi[0]; o.xm[2 * u + 1] = mi[1];
-                o.xl[2 * u] = lo[0]; o.xl[2 * u + 1] = lo[1];
             }
         }
     };
     // W2 fragments of this wavefront's column tiles, L2 -> registers, in k_edge's chunk-image layouts:
     //   fp32   [4 q][NCT][64 lanes][4 floats]                       NF = 4 NCW fragments per chunk: (q, k)
-    //   bf16x3 [head|tail][2 k-steps][NCT][64 lanes][8 bf16]        NF = 4 NCW: (head / tail, s, k)
-    //   bf16x6 [head|middle|tail][NCT][64 lanes][8 bf16]            NF = 3 NCW: (part, k)
+    //   fp16x3 [head|tail][2 k-steps][NCT][64 lanes][8 fp16]        NF = 4 NCW: (head / tail, s, k)
     const int ct0 = wave * NCW;
-    constexpr int NF = (PREC == 2 ? 3 : 4) * NCW;
+    constexpr int NF = 4 * NCW;
     const char* wimg = reinterpret_cast<const char*>(a.W2img) + lane * 16;
     auto load_frags = [&](int c, u32x4 (&f)[NF]) {
         const char* base = wimg + (size_t)c * CHF * 4;
@@ -162,13 +149,12 @@ HD_DEVINL void edge_split_body(const EdgeArgs& a, char* lds, float* wrd_s, const
             const int x = i / NCW, k = i % NCW;
             unsigned off;
             if constexpr (PREC == 0) off = frag_off_f32(x * NCT + ct0 + k);                       // x = q
-            else if constexpr (HD_TWOWAY(PREC)) off = (unsigned)(((((x >> 1) * 2 + (x & 1)) * NCT + ct0 + k) * 64) * 16);   // x = 2 hl + s
-            else off = (unsigned)((x * NCT + ct0 + k) * 64 * 16);                                 // x = part
+            else off = (unsigned)(((((x >> 1) * 2 + (x & 1)) * NCT + ct0 + k) * 64) * 16);           // x = 2 hl + s
             f[i] = *reinterpret_cast<const u32x4*>(base + off);
         }
     };
-    constexpr int RING0 = PREC == 0 ? 3 : (HD_TWOWAY(PREC) ? 4 : 6);       // chunks of fragments in flight ahead of the MFMAs
-    constexpr int RING = DEEP ? (PREC == 0 ? 6 : (HD_TWOWAY(PREC) ? 6 : 8)) : RING0;
+    constexpr int RING0 = PREC == 0 ? 3 : 4;                         // chunks of fragments in flight ahead of the MFMAs
+    constexpr int RING = DEEP ? 6 : RING0;
     u32x4 fr[RING][NF];
     static_for<0, (RING - 1 < NCH ? RING - 1 : NCH)>([&](auto Cc) { load_frags(decltype(Cc)::value, fr[decltype(Cc)::value]); });
     // The operand tile (32 edge rows x H) is the same for the four wavefronts: each builds a quarter of the K chunks
@@ -189,10 +175,8 @@ HD_DEVINL void edge_split_body(const EdgeArgs& a, char* lds, float* wrd_s, const
             if constexpr (PREC == 0) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) dst[q * 64] = __builtin_bit_cast(u32x4, f32x4{o.P[4 * q], o.P[4 * q + 1], o.P[4 * q + 2], o.P[4 * q + 3]});
-            } else if constexpr (HD_TWOWAY(PREC)) {
-                dst[0] = o.ph[0]; dst[64] = o.ph[1]; dst[128] = o.pl[0]; dst[192] = o.pl[1];
             } else {
-                dst[0] = o.xh; dst[64] = o.xm; dst[128] = o.xl;
+                dst[0] = o.ph[0]; dst[64] = o.ph[1]; dst[128] = o.pl[0]; dst[192] = o.pl[1];
             }
         }
     }
@@ -224,30 +208,17 @@ HD_DEVINL void edge_split_body(const EdgeArgs& a, char* lds, float* wrd_s, const
 #pragma unroll
                     for (int k = 0; k < NCW; ++k)
                         acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(__builtin_bit_cast(f32x4, ov[q])[j], __builtin_bit_cast(f32x4, f[q * NCW + k])[j], acc[k], 0, 0, 0);
-        } else if constexpr (HD_TWOWAY(PREC)) {
+        } else {
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
-                const bf16x8 A_h = __builtin_bit_cast(bf16x8, ov[st]), A_l = __builtin_bit_cast(bf16x8, ov[2 + st]);
+                const f16x8 A_h = __builtin_bit_cast(f16x8, ov[st]), A_l = __builtin_bit_cast(f16x8, ov[2 + st]);
 #pragma unroll
                 for (int k = 0; k < NCW; ++k) {
-                    const bf16x8 Wh = __builtin_bit_cast(bf16x8, f[(0 + st) * NCW + k]), Wl = __builtin_bit_cast(bf16x8, f[(2 + st) * NCW + k]);
-                    acc[k] = mma16<PREC == 3>(A_h, Wh, acc[k]);
-                    acc[k] = mma16<PREC == 3>(A_l, Wh, acc[k]);
-                    acc[k] = mma16<PREC == 3>(A_h, Wl, acc[k]);
+                    const f16x8 Wh = __builtin_bit_cast(f16x8, f[(0 + st) * NCW + k]), Wl = __builtin_bit_cast(f16x8, f[(2 + st) * NCW + k]);
+                    acc[k] = mma_f16(A_h, Wh, acc[k]);
+                    acc[k] = mma_f16(A_l, Wh, acc[k]);
+                    acc[k] = mma_f16(A_h, Wl, acc[k]);
                 }
-            }
-        } else {
-            const bf16x8 A_h = __builtin_bit_cast(bf16x8, ov[0]), A_m = __builtin_bit_cast(bf16x8, ov[1]), A_l = __builtin_bit_cast(bf16x8, ov[2]);
-#pragma unroll
-            for (int k = 0; k < NCW; ++k) {
-                const bf16x8 Wh = __builtin_bit_cast(bf16x8, f[0 * NCW + k]), Wm = __builtin_bit_cast(bf16x8, f[1 * NCW + k]),
-                             Wt = __builtin_bit_cast(bf16x8, f[2 * NCW + k]);
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, Wt, acc[k], 0, 0, 0);
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, Wm, acc[k], 0, 0, 0);
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_m, Wm, acc[k], 0, 0, 0);
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_h, Wh, acc[k], 0, 0, 0);
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_m, Wh, acc[k], 0, 0, 0);
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_l, Wh, acc[k], 0, 0, 0);
             }
         }
     });
@@ -269,7 +240,6 @@ HD_DEVINL void edge_split_body(const EdgeArgs& a, char* lds, float* wrd_s, const
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             if constexpr (PREC == 0) acc[k][r] = HD_F32_SILU(acc[k][r]);
-            else if constexpr (PREC == 2) acc[k][r] = HD_X6_SILU(acc[k][r]);
             else acc[k][r] = acc[k][r] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(acc[k][r]));   // scaled domain
         }
     // the row dot is one FMA chain per lane over ct = 0 .. NCT-1: wavefront w continues where w-1 stopped
@@ -331,7 +301,7 @@ HD_DEVINL void edge_split_body(const EdgeArgs& a, char* lds, float* wrd_s, const
             float att_mine = 1.0f;
             if (a.attention) {
                 const float ba = a.ba_ptr ? *a.ba_ptr : a.ba;
-                if constexpr (!HD_TWOWAY(PREC)) att_mine = sigmoid_f(rowdot + ba);
+                if constexpr (PREC == 0) att_mine = sigmoid_f(rowdot + ba);
                 else att_mine = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(rowdot + ba));   // scaled domain
             }
             att_s[lane] = att_mine;
@@ -413,7 +383,7 @@ HD_DEVINL void edge_split_body(const EdgeArgs& a, char* lds, float* wrd_s, const
 template <int H, bool COORD, int PREC>
 __global__ __launch_bounds__(256) void k_edge_split(EdgeArgs a) {
     __shared__ __attribute__((aligned(16))) float wrd_s[4 * H];     // [w_r | w_d | b2 | wa]
-    __shared__ __attribute__((aligned(16))) char lds[edge_split_lds_bytes<H, PREC>()];
+    __shared__ __attribute__((aligned(16))) char lds[edge_split_lds_bytes<H>()];
     edge_split_body<H, COORD, PREC, true>(a, lds, wrd_s, blockIdx.x);      // grid = n_tiles
 }
 

@@ -1,6 +1,6 @@
 // Node-side kernels: input embedding (k_node_init), the fp32 tile GEMM k_gemm (stage-2 layer E_GCL; the sampler's fp32 node
 // chain of small batches is k_gemm_r16.hpp), and the fused node update
-// of the sampler in its three arithmetics (k_node: bf16x3 / bf16x6; k_node_f32: exact fp32).  Included through kernels.hpp.
+// of the sampler in its two arithmetics (k_node: fp16x3; k_node_f32: exact fp32).  Included through kernels.hpp.
 #pragma once
 #include "common.hpp"
 
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(WM * WN * 64) void k_gemm(GemmArgs g) {
     }
 }
 
-// ----------------------------------------------------------------------------- fused node update (bf16x3)
+// ----------------------------------------------------------------------------- fused node update (fp16x3)
 // One workgroup owns 32 node rows and runs the whole row-local chain of a GCL's node model plus the first
 // edge Linear of the layer(s) that follow, so the intermediate activations never leave the CU:
 //   X   = [h | (sum of the node's partial neighbour sums) / normalization_factor]      (egnn_new.py:52-56,280-282)
@@ -278,15 +278,13 @@ __global__ __launch_bounds__(WM * WN * 64) void k_gemm(GemmArgs g) {
 // (UPD = false: only the last line, on h as it is - used once after the embedding.)  It replaces
 // k_gemm(AB) + k_agg + k_gemm(n1) + k_gemm(n2): at M = 7,680 rows those four launches were bound by fixed costs
 // (launch, tile prologue, C stores), not by math.
-//   * A operands: the 32-row activation tile lives in LDS as bf16 head + tail, row stride K+8 elements
+//   * A operands: the 32-row activation tile lives in LDS as fp16 head + tail, row stride K+8 elements
 //     (16 B pad => conflict-free ds_read_b128), shared by all wavefronts.
 //   * B operands: every wavefront owns its own 32-column tiles, so weights have no reuse inside a workgroup
 //     and go L2 -> registers directly (fragment-ordered image, 1 KiB coalesced per load), PF k-steps ahead.
 //   * C tiles leave through an LDS transpose as whole float4 rows.
-// Weight image (pack_node_b): [k-step s][column tile ct][head|tail][64 lanes][8 bf16],
+// Weight image (pack_node_b): [k-step s][column tile ct][head|tail][64 lanes][8 fp16], scaled by a power of two per matrix,
 //   k = 16 s + 8 (lane>>5) + i,  col = 32 ct + (lane&31).
-// NP = 3 is the same kernel in the bf16x6 arithmetic (k_edge.hpp): activations and weights in three bf16 pieces
-// ([head|middle|tail] planes / image slots), six MFMAs per product, the fp32 mode's SiLU.
 
 struct NodeArgs {
     const float* h_in;      // [M_pad][H]
@@ -302,7 +300,7 @@ struct NodeArgs {
     const float* ABbias[2]; // [2H]
     float* ABout[2];        // [M_pad][2H]
     float* ABmax[2];        // optional [M_pad][2]: max_k |A_i[k]|, max_k |B_i[k]| of the AB rows written (fp16x3 edge kernels)
-    // F16 variant (two-piece FP16 operands, k_node<..., 2, true>): 1 / (power-of-two scale) of the three weight images, and the
+    // 1 / (power-of-two scale) of the three weight images, and the
     // constants of the a-priori row bounds: max_c sum_k |W[c][k]| of W3 / W4 and max |b3| / |b4|
     float w3inv, w4inv, abinv[2], w3l1, w4l1, b3max, b4max;
     float norm;
@@ -314,16 +312,16 @@ struct NodeArgs {
 // the barrier / epilogue that precedes the contraction, weights do not depend on data) and `run` consumes
 // it.  sched_barrier(0) at every k-step keeps hipcc from sinking the loads next to their MFMAs (it otherwise
 // shrinks the ring to 2-3 loads in flight to save registers and exposes the L2 latency every k-step).
-template <int KS, int CTn, int CTW, int PF, int NCT, int NP = 2, bool F16 = false>
+template <int KS, int CTn, int CTW, int PF, int NCT>
 struct NodeMma {
-    typedef u32x4 Ring[PF][CTn][NP];
+    typedef u32x4 Ring[PF][CTn][2];
     template <int s, int slot>
     static HD_DEVINL void load(Ring& br, const u32x4* Bl, int ct0, int CTG) {
 #pragma unroll
         for (int c = 0; c < CTn; ++c) {
             const int ct = (c / CTW) * CTG + ct0 + c % CTW;
 #pragma unroll
-            for (int p = 0; p < NP; ++p) br[slot][c][p] = Bl[((size_t)(s * NCT + ct) * NP + p) * 64];
+            for (int p = 0; p < 2; ++p) br[slot][c][p] = Bl[((size_t)(s * NCT + ct) * 2 + p) * 64];
         }
     }
     static HD_DEVINL void prefetch(Ring& br, const u32x4* Bl, int ct0, int CTG) {
@@ -331,84 +329,63 @@ struct NodeMma {
         asm volatile("" ::: "memory");                // keeps the loads above whatever follows (barriers included)
         __builtin_amdgcn_sched_barrier(0);
     }
-    // Ap[p]: this lane's row of piece p of the A tile (head, [middle,] tail).  Two pieces: a_h b_h + a_l b_h + a_h b_l (bf16x3);
-    // three pieces: a_h b_l + a_l b_h + a_m b_m + a_h b_m + a_m b_h + a_h b_h, small terms first (bf16x6, k_edge.hpp).
-    // F16: the K range is summed in four QUARTERS with their own accumulators, result = ((q0 + q1) + q2) + q3 - the order of
+    // Ap[p]: this lane's row of piece p of the A tile (head, tail); a product is a_h b_h + a_l b_h + a_h b_l.
+    // The K range is summed in four QUARTERS with their own accumulators, result = ((q0 + q1) + q2) + q3 - the order of
     // k_node_split.hpp, whose four wavefronts per output tile own one quarter each (the two paths are bit-identical).  `acc`
-    // arrives zeroed in that mode (the bias joins in the un-scaling fma) and serves as q0.
-    static constexpr int NQ = F16 ? 4 : 1;
-    static HD_DEVINL void run(f32x16 (&acc)[CTn], Ring& br, const __bf16* const (&Ap)[NP], const u32x4* Bl, int ct0, int CTG) {
-        static_assert(KS % NQ == 0, "whole k-steps per quarter");
-        f32x16 accq[NQ > 1 ? NQ - 1 : 1][CTn];
-        if constexpr (NQ > 1) {
+    // arrives zeroed (the bias joins in the un-scaling fma) and serves as q0.
+    static HD_DEVINL void run(f32x16 (&acc)[CTn], Ring& br, const _Float16* const (&Ap)[2], const u32x4* Bl, int ct0, int CTG) {
+        static_assert(KS % 4 == 0, "whole k-steps per quarter");
+        f32x16 accq[3][CTn];
 #pragma unroll
-            for (int q = 0; q < NQ - 1; ++q)
+        for (int q = 0; q < 3; ++q)
 #pragma unroll
-                for (int c = 0; c < CTn; ++c)
+            for (int c = 0; c < CTn; ++c)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) accq[q][c][r] = 0.f;
-        }
-        bf16x8_t a[NP];
+                for (int r = 0; r < 16; ++r) accq[q][c][r] = 0.f;
+        f16x8 a[2];
 #pragma unroll
-        for (int p = 0; p < NP; ++p) a[p] = *reinterpret_cast<const bf16x8_t*>(Ap[p]);
+        for (int p = 0; p < 2; ++p) a[p] = *reinterpret_cast<const f16x8*>(Ap[p]);
         static_for<0, KS>([&](auto S) {
             constexpr int s = decltype(S)::value, slot = s % PF;
-            constexpr int qi = s / (KS / NQ);
+            constexpr int qi = s / (KS / 4);
             f32x16(&dst)[CTn] = *(qi == 0 ? &acc : &accq[qi > 0 ? qi - 1 : 0]);
             __builtin_amdgcn_sched_barrier(0);
-            bf16x8_t an[NP];
+            f16x8 an[2];
 #pragma unroll
-            for (int p = 0; p < NP; ++p) an[p] = a[p];
+            for (int p = 0; p < 2; ++p) an[p] = a[p];
             if constexpr (s + 1 < KS) {
 #pragma unroll
-                for (int p = 0; p < NP; ++p) an[p] = *reinterpret_cast<const bf16x8_t*>(Ap[p] + 16 * (s + 1));
+                for (int p = 0; p < 2; ++p) an[p] = *reinterpret_cast<const f16x8*>(Ap[p] + 16 * (s + 1));
             }
             __builtin_amdgcn_sched_barrier(0);         // next A fragments are in flight under this step's MFMAs
-            bf16x8_t b[CTn][NP];
+            f16x8 b[CTn][2];
 #pragma unroll
             for (int c = 0; c < CTn; ++c)
 #pragma unroll
-                for (int p = 0; p < NP; ++p) b[c][p] = __builtin_bit_cast(bf16x8_t, br[slot][c][p]);
+                for (int p = 0; p < 2; ++p) b[c][p] = __builtin_bit_cast(f16x8, br[slot][c][p]);
             auto term = [&](int pa, int pb) {
 #pragma unroll
-                for (int c = 0; c < CTn; ++c) {
-                    if constexpr (F16) dst[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[pa]), __builtin_bit_cast(f16x8, b[c][pb]), dst[c], 0, 0, 0);
-                    else dst[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[pa], b[c][pb], dst[c], 0, 0, 0);
-                }
+                for (int c = 0; c < CTn; ++c) dst[c] = mma_f16(a[pa], b[c][pb], dst[c]);
             };
-            if constexpr (NP == 2) { term(0, 0); term(1, 0); term(0, 1); }
-            else { term(0, 2); term(2, 0); term(1, 1); term(0, 1); term(1, 0); term(0, 0); }
+            term(0, 0); term(1, 0); term(0, 1);
             if constexpr (s + PF < KS) load<s + PF, slot>(br, Bl, ct0, CTG);
 #pragma unroll
-            for (int p = 0; p < NP; ++p) a[p] = an[p];
+            for (int p = 0; p < 2; ++p) a[p] = an[p];
         });
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (NQ > 1) {
 #pragma unroll
-            for (int c = 0; c < CTn; ++c)
+        for (int c = 0; c < CTn; ++c)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[c][r] = ((acc[c][r] + accq[0][c][r]) + accq[1][c][r]) + accq[2][c][r];
-        }
+            for (int r = 0; r < 16; ++r) acc[c][r] = ((acc[c][r] + accq[0][c][r]) + accq[1][c][r]) + accq[2][c][r];
     }
 };
 
-// v -> NP bf16 pieces at the same element offset of NP consecutive LDS planes of `plane` elements
-template <int NP>
-HD_DEVINL void bf16_split_store(__bf16* d, int plane, float v) {
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const __bf16 piece = (__bf16)v;
-        d[p * plane] = piece;
-        v -= (float)piece;
-    }
-}
-
-// the same with FP16 pieces (two planes; the value arrives scaled into range, see k_node<..., F16>)
-HD_DEVINL void f16_split_store(__bf16* d, int plane, float v) {
-    _Float16* p = reinterpret_cast<_Float16*>(d);
+// v -> fp16 head and tail at the same element offset of two consecutive LDS planes of `plane` elements (the value arrives scaled
+// into range, see k_node)
+HD_DEVINL void f16_split_store(_Float16* d, int plane, float v) {
     const _Float16 hi = (_Float16)v;
-    p[0] = hi;
-    p[plane] = (_Float16)(v - (float)hi);
+    d[0] = hi;
+    d[plane] = (_Float16)(v - (float)hi);
 }
 // power-of-two scale s with bound * s in [2^13, 2^14) and its inverse (k_edge.hpp, fp16x3)
 HD_DEVINL void f16_row_scale(float bound, float& s, float& inv) {
@@ -417,7 +394,7 @@ HD_DEVINL void f16_row_scale(float bound, float& s, float& inv) {
     s = __builtin_bit_cast(float, (267u - eb) << 23);
 }
 
-// F16 (NPC = 2 only): the fp16x3 arithmetic of the edge kernels for the three node GEMMs - two-way FP16 split, three fp16 MFMAs per
+// The fp16x3 arithmetic of the edge kernels for the three node GEMMs - two-way FP16 split, three fp16 MFMAs per
 // product, operands ranged by exact powers of two.  Weights: per matrix, by the packer.  Activations: per ROW, from bounds that are
 // known before the first contraction starts (so no reduction across wavefronts is needed between the phases):
 //     X = [h | agg]:  max_k |X_r[k]|                                   (16 threads hold a row in phase 0: four shuffles)
@@ -427,9 +404,8 @@ HD_DEVINL void f16_row_scale(float bound, float& s, float& inv) {
 // keeps 22 significant bits down to 2^-2, i.e. over 15 binades below its bound, and smaller elements keep an absolute error of
 // 2^-25 / scale.  Each phase's accumulators hold (row scale x weight scale) x the result; the epilogue undoes it in the fma that
 // adds the bias.
-template <int H, int NW, bool UPD, int NAB, int NPC = 2, bool F16 = false>
+template <int H, int NW, bool UPD, int NAB>
 __global__ __launch_bounds__(64 * NW, 1) void k_node(NodeArgs a) {
-    static_assert(!F16 || NPC == 2, "the FP16 variant is a two-piece split");
     constexpr int NT = 64 * NW;
     constexpr int NCT = H / 32;            // column tiles of an H-wide output
     constexpr int CT = NCT / NW;           // ... per wavefront
@@ -437,13 +413,13 @@ __global__ __launch_bounds__(64 * NW, 1) void k_node(NodeArgs a) {
     constexpr int KX = UPD ? 2 * H : H;
     constexpr int LDX = KX + 8, LDH = H + 8;
     constexpr int PF12 = 4, PF3 = 3;       // k-steps of weights in flight per wavefront (deeper rings measured no faster)
-    constexpr int R0_BYTES = 32 * LDX * 2 * NPC;        // the NP bf16 pieces of X (NPC = 2: head + tail; 3: bf16x6 mode)
+    constexpr int R0_BYTES = 32 * LDX * 2 * 2;         // the two fp16 pieces of X (head + tail)
     constexpr int PX = 32 * LDX, PH = 32 * LDH;        // elements per piece plane
     extern __shared__ __attribute__((aligned(16))) char smem_n[];
-    __bf16* Xh = reinterpret_cast<__bf16*>(smem_n);                 // planes Xh + p * PX
-    __bf16* Th = reinterpret_cast<__bf16*>(smem_n + R0_BYTES);      // region 1: T (planes + p * PH), later the AB staging tile
-    __bf16* Nh = reinterpret_cast<__bf16*>(smem_n);                 // h' pieces re-use region 0 (planes + p * PH) ...
-    float* stage0 = reinterpret_cast<float*>(smem_n + PH * 2 * NPC); // ... followed by its fp32 staging tile [32][H]
+    _Float16* Xh = reinterpret_cast<_Float16*>(smem_n);                 // planes Xh + p * PX
+    _Float16* Th = reinterpret_cast<_Float16*>(smem_n + R0_BYTES);      // region 1: T (planes + p * PH), later the AB staging tile
+    _Float16* Nh = reinterpret_cast<_Float16*>(smem_n);                 // h' pieces re-use region 0 (planes + p * PH) ...
+    float* stage0 = reinterpret_cast<float*>(smem_n + PH * 2 * 2);  // ... followed by its fp32 staging tile [32][H]
     constexpr int LDS1 = H + 4;
     float* stage1 = reinterpret_cast<float*>(smem_n + R0_BYTES);    // [32][H+4]
 
@@ -464,15 +440,15 @@ __global__ __launch_bounds__(64 * NW, 1) void k_node(NodeArgs a) {
     }
     const int row0 = rt * 32;
 
-    typedef NodeMma<KX / 16, CT, CT, PF12, NCT, NPC, F16> M1;        // X W3^T      (UPD only)
-    typedef NodeMma<H / 16, CT, CT, PF12, NCT, NPC, F16> M2;         // T W4^T      (UPD only)
-    typedef NodeMma<H / 16, 2 * CT, CT, PF3, 2 * NCT, NPC, F16> M3;  // h' [W1a|W1b]^T
-    // F16: per row of the tile {scale of T, scale of h', 1 / scale of X, 1 / scale of T, 1 / scale of h'}
+    typedef NodeMma<KX / 16, CT, CT, PF12, NCT> M1;       // X W3^T      (UPD only)
+    typedef NodeMma<H / 16, CT, CT, PF12, NCT> M2;        // T W4^T      (UPD only)
+    typedef NodeMma<H / 16, 2 * CT, CT, PF3, 2 * NCT> M3; // h' [W1a|W1b]^T
+    // per row of the tile {scale of T, scale of h', 1 / scale of X, 1 / scale of T, 1 / scale of h'}
     __shared__ __attribute__((aligned(16))) float rsc[5][32];
     auto row4 = [&](int k, int q) { return *reinterpret_cast<const f32x4*>(&rsc[k][8 * q + 4 * hh]); };
-    auto rows_of = [&](const __bf16* base, int ld, int plane, const __bf16* (&out)[NPC]) {
+    auto rows_of = [&](const _Float16* base, int ld, int plane, const _Float16* (&out)[2]) {
 #pragma unroll
-        for (int p = 0; p < NPC; ++p) out[p] = base + p * plane + n * ld + 8 * hh;
+        for (int p = 0; p < 2; ++p) out[p] = base + p * plane + n * ld + 8 * hh;
     };
     typename M1::Ring br1;
     typename M2::Ring br2;
@@ -494,7 +470,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_node(NodeArgs a) {
 #pragma unroll
         for (int c = 0; c < 2 * CT; ++c) abv[q][c] = a.ABbias[q][(c / CT) * H + 32 * (ct0 + c % CT) + n];
 
-    // ---- phase 0: X -> LDS (bf16 head/tail).  NT/32 threads per row, each moving every (NT/32)-th float4 of
+    // ---- phase 0: X -> LDS (fp16 head/tail).  NT/32 threads per row, each moving every (NT/32)-th float4 of
     // the row, so a thread needs one pstart pair and all its loads are independent of each other.
     {
         constexpr int Q = H / 4;                     // float4 per H-wide row
@@ -503,24 +479,15 @@ __global__ __launch_bounds__(64 * NW, 1) void k_node(NodeArgs a) {
         static_assert(Q % TPR == 0, "row pieces must divide evenly");
         const int r = tid / TPR, cq = tid % TPR;
         const int row = row0 + r;
-        float sX = 1.0f;                                  // F16: this row's scale of X
+        float sX = 1.0f;                                  // this row's scale of X
         auto put = [&](int col, f32x4 v) {
-            if constexpr (F16) {
-                typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-                v = f32x4{v[0] * sX, v[1] * sX, v[2] * sX, v[3] * sX};
-                const f16x4_t hi = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-                const f16x4_t lo = {(_Float16)(v[0] - (float)hi[0]), (_Float16)(v[1] - (float)hi[1]), (_Float16)(v[2] - (float)hi[2]),
-                                    (_Float16)(v[3] - (float)hi[3])};
-                *reinterpret_cast<f16x4_t*>(Xh + r * LDX + col) = hi;
-                *reinterpret_cast<f16x4_t*>(Xh + PX + r * LDX + col) = lo;
-                return;
-            }
-#pragma unroll
-            for (int p = 0; p < NPC; ++p) {
-                const __bf16 h0 = (__bf16)v[0], h1 = (__bf16)v[1], h2 = (__bf16)v[2], h3 = (__bf16)v[3];
-                *reinterpret_cast<bf16x4_t*>(Xh + p * PX + r * LDX + col) = bf16x4_t{h0, h1, h2, h3};
-                v = f32x4{v[0] - (float)h0, v[1] - (float)h1, v[2] - (float)h2, v[3] - (float)h3};
-            }
+            typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
+            v = f32x4{v[0] * sX, v[1] * sX, v[2] * sX, v[3] * sX};
+            const f16x4_t hi = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+            const f16x4_t lo = {(_Float16)(v[0] - (float)hi[0]), (_Float16)(v[1] - (float)hi[1]), (_Float16)(v[2] - (float)hi[2]),
+                                (_Float16)(v[3] - (float)hi[3])};
+            *reinterpret_cast<f16x4_t*>(Xh + r * LDX + col) = hi;
+            *reinterpret_cast<f16x4_t*>(Xh + PX + r * LDX + col) = lo;
         };
         int p0 = 0, p1 = 0;
         if constexpr (UPD) {
@@ -542,55 +509,40 @@ __global__ __launch_bounds__(64 * NW, 1) void k_node(NodeArgs a) {
                 g0[u] = *reinterpret_cast<const f32x4*>(s0 + 4 * (cq + u * TPR));
                 g1[u] = *reinterpret_cast<const f32x4*>(s1 + 4 * (cq + u * TPR));
             }
-            if constexpr (F16) {
-                f32x4 gv[NP];
-                float mh = 0.f, mg = 0.f;
-#pragma unroll
-                for (int u = 0; u < NP; ++u) {
-                    f32x4 v = z4;
-                    if (has0) v += g0[u];
-                    if (has1) v += g1[u];
-                    for (int p = p0 + 2; p < p1; ++p) v += *reinterpret_cast<const f32x4*>(a.part + (size_t)p * H + 4 * (cq + u * TPR));
-                    gv[u] = v / a.norm;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { mh = fmaxf(mh, fabsf(hv[u][j])); mg = fmaxf(mg, fabsf(gv[u][j])); }
-                }
-#pragma unroll
-                for (int o = TPR / 2; o > 0; o >>= 1) { mh = fmaxf(mh, __shfl_xor(mh, o)); mg = fmaxf(mg, __shfl_xor(mg, o)); }
-                const float mx = fmaxf(mh, mg);
-                const float tb = __builtin_fmaf(mx, a.w3l1, a.b3max), hb = mh + __builtin_fmaf(tb, a.w4l1, a.b4max);
-                float iX, sT, iT, sH, iH;
-                f16_row_scale(mx, sX, iX); f16_row_scale(tb, sT, iT); f16_row_scale(hb, sH, iH);
-                if (cq == 0) { rsc[0][r] = sT; rsc[1][r] = sH; rsc[2][r] = iX * a.w3inv; rsc[3][r] = iT * a.w4inv; rsc[4][r] = iH; }
-#pragma unroll
-                for (int u = 0; u < NP; ++u) put(4 * (cq + u * TPR), hv[u]);
-#pragma unroll
-                for (int u = 0; u < NP; ++u) put(H + 4 * (cq + u * TPR), gv[u]);
-            } else {
-#pragma unroll
-            for (int u = 0; u < NP; ++u) put(4 * (cq + u * TPR), hv[u]);
+            f32x4 gv[NP];
+            float mh = 0.f, mg = 0.f;
 #pragma unroll
             for (int u = 0; u < NP; ++u) {
                 f32x4 v = z4;
                 if (has0) v += g0[u];
                 if (has1) v += g1[u];
                 for (int p = p0 + 2; p < p1; ++p) v += *reinterpret_cast<const f32x4*>(a.part + (size_t)p * H + 4 * (cq + u * TPR));
-                put(H + 4 * (cq + u * TPR), v / a.norm);
-            }
-            }
-        } else {
-            if constexpr (F16) {                                     // AB only: X = h, the operand of phase 3
-                float mh = 0.f;
+                gv[u] = v / a.norm;
 #pragma unroll
-                for (int u = 0; u < NP; ++u)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) mh = fmaxf(mh, fabsf(hv[u][j]));
-#pragma unroll
-                for (int o = TPR / 2; o > 0; o >>= 1) mh = fmaxf(mh, __shfl_xor(mh, o));
-                float iX;
-                f16_row_scale(mh, sX, iX);
-                if (cq == 0) rsc[4][r] = iX;
+                for (int j = 0; j < 4; ++j) { mh = fmaxf(mh, fabsf(hv[u][j])); mg = fmaxf(mg, fabsf(gv[u][j])); }
             }
+#pragma unroll
+            for (int o = TPR / 2; o > 0; o >>= 1) { mh = fmaxf(mh, __shfl_xor(mh, o)); mg = fmaxf(mg, __shfl_xor(mg, o)); }
+            const float mx = fmaxf(mh, mg);
+            const float tb = __builtin_fmaf(mx, a.w3l1, a.b3max), hb = mh + __builtin_fmaf(tb, a.w4l1, a.b4max);
+            float iX, sT, iT, sH, iH;
+            f16_row_scale(mx, sX, iX); f16_row_scale(tb, sT, iT); f16_row_scale(hb, sH, iH);
+            if (cq == 0) { rsc[0][r] = sT; rsc[1][r] = sH; rsc[2][r] = iX * a.w3inv; rsc[3][r] = iT * a.w4inv; rsc[4][r] = iH; }
+#pragma unroll
+            for (int u = 0; u < NP; ++u) put(4 * (cq + u * TPR), hv[u]);
+#pragma unroll
+            for (int u = 0; u < NP; ++u) put(H + 4 * (cq + u * TPR), gv[u]);
+        } else {                                                     // AB only: X = h, the operand of phase 3
+            float mh = 0.f;
+#pragma unroll
+            for (int u = 0; u < NP; ++u)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) mh = fmaxf(mh, fabsf(hv[u][j]));
+#pragma unroll
+            for (int o = TPR / 2; o > 0; o >>= 1) mh = fmaxf(mh, __shfl_xor(mh, o));
+            float iX;
+            f16_row_scale(mh, sX, iX);
+            if (cq == 0) rsc[4][r] = iX;
 #pragma unroll
             for (int u = 0; u < NP; ++u) put(4 * (cq + u * TPR), hv[u]);
         }
@@ -601,38 +553,25 @@ __global__ __launch_bounds__(64 * NW, 1) void k_node(NodeArgs a) {
         {
             f32x16 acc[CT];
 #pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                const float b = F16 ? 0.f : b3v[c];                  // F16: the bias joins in the un-scaling fma
+            for (int c = 0; c < CT; ++c)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[c][r] = b;
-            }
+                for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;            // the bias joins in the un-scaling fma
             __syncthreads();                                         // X complete
             M2::prefetch(br2, W4l, ct0, 0);
-            const __bf16* xr[NPC];
+            const _Float16* xr[2];
             rows_of(Xh, LDX, PX, xr);
             M1::run(acc, br1, xr, W3l, ct0, 0);
-            if constexpr (F16) {
-                f32x4 un[4], sc[4];
+            f32x4 un[4], sc[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) { un[q] = row4(2, q); sc[q] = row4(0, q); }
-#pragma unroll
-                for (int c = 0; c < CT; ++c)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int R = (r & 3) + 8 * (r >> 2) + 4 * hh;
-                        const float t = silu_f(__builtin_fmaf(acc[c][r], un[r >> 2][r & 3], b3v[c]));
-                        f16_split_store(Th + R * LDH + 32 * (ct0 + c) + n, PH, t * sc[r >> 2][r & 3]);
-                    }
-            } else {
+            for (int q = 0; q < 4; ++q) { un[q] = row4(2, q); sc[q] = row4(0, q); }
 #pragma unroll
             for (int c = 0; c < CT; ++c)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int R = (r & 3) + 8 * (r >> 2) + 4 * hh;
-                    // bf16x3: plain SiLU (the contraction error is ~1e-6 anyway); bf16x6: the fp32 mode's compensated one
-                    bf16_split_store<NPC>(Th + R * LDH + 32 * (ct0 + c) + n, PH, NPC == 3 ? silu_f(acc[c][r]) : silu_fast(acc[c][r]));
+                    const float t = silu_f(__builtin_fmaf(acc[c][r], un[r >> 2][r & 3], b3v[c]));
+                    f16_split_store(Th + R * LDH + 32 * (ct0 + c) + n, PH, t * sc[r >> 2][r & 3]);
                 }
-            }
         }
         __syncthreads();
         // ---- phase 2: h' = (h + T W4^T + b4) * mask
@@ -643,15 +582,14 @@ __global__ __launch_bounds__(64 * NW, 1) void k_node(NodeArgs a) {
             for (int r = 0; r < 16; ++r) mk[r] = a.nmask[row0 + (r & 3) + 8 * (r >> 2) + 4 * hh];
 #pragma unroll
             for (int c = 0; c < CT; ++c) {
-                const float b = F16 ? 0.f : b4v[c];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    acc[c][r] = b;
+                    acc[c][r] = 0.f;
                     hres[c][r] = a.h_in[(size_t)(row0 + (r & 3) + 8 * (r >> 2) + 4 * hh) * H + 32 * (ct0 + c) + n];
                 }
             }
             M3::prefetch(br3, AB0l, ct0, NCT);
-            const __bf16* tr[NPC];
+            const _Float16* tr[2];
             rows_of(Th, LDH, PH, tr);
             M2::run(acc, br2, tr, W4l, ct0, 0);
 #pragma unroll
@@ -659,15 +597,9 @@ __global__ __launch_bounds__(64 * NW, 1) void k_node(NodeArgs a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int R = (r & 3) + 8 * (r >> 2) + 4 * hh;
-                    if constexpr (F16) {
-                        const float v = (hres[c][r] + __builtin_fmaf(acc[c][r], row4(3, r >> 2)[r & 3], b4v[c])) * mk[r];
-                        f16_split_store(Nh + R * LDH + 32 * (ct0 + c) + n, PH, v * row4(1, r >> 2)[r & 3]);
-                        stage0[R * H + 32 * (ct0 + c) + n] = v;
-                    } else {
-                    const float v = (hres[c][r] + acc[c][r]) * mk[r];
-                    bf16_split_store<NPC>(Nh + R * LDH + 32 * (ct0 + c) + n, PH, v);
+                    const float v = (hres[c][r] + __builtin_fmaf(acc[c][r], row4(3, r >> 2)[r & 3], b4v[c])) * mk[r];
+                    f16_split_store(Nh + R * LDH + 32 * (ct0 + c) + n, PH, v * row4(1, r >> 2)[r & 3]);
                     stage0[R * H + 32 * (ct0 + c) + n] = v;
-                    }
                 }
         }
         __syncthreads();
@@ -687,29 +619,25 @@ __global__ __launch_bounds__(64 * NW, 1) void k_node(NodeArgs a) {
     for (int q = 0; q < NAB; ++q) {
         f32x16 acc[2 * CT];
 #pragma unroll
-        for (int c = 0; c < 2 * CT; ++c) {
-            const float b = F16 ? 0.f : abv[q][c];
+        for (int c = 0; c < 2 * CT; ++c)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[c][r] = b;
-        }
+            for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
         const u32x4* ABl = reinterpret_cast<const u32x4*>(a.ABimg[q]) + lane;
         if (q > 0 || !UPD) {
             M3::prefetch(br3, ABl, ct0, NCT);
             if (!UPD) __syncthreads();                               // h tile complete
         }
-        const __bf16* nr[NPC];
+        const _Float16* nr[2];
         rows_of(Nh, LDH, PH, nr);                            // (!UPD: h' is X itself, LDX == LDH)
         M3::run(acc, br3, nr, ABl, ct0, NCT);
-        if constexpr (F16) {
-            f32x4 un[4];
+        f32x4 un[4];
 #pragma unroll
-            for (int qq = 0; qq < 4; ++qq) un[qq] = row4(4, qq);
-            const float wi = a.abinv[q];
+        for (int qq = 0; qq < 4; ++qq) un[qq] = row4(4, qq);
+        const float wi = a.abinv[q];
 #pragma unroll
-            for (int c = 0; c < 2 * CT; ++c)
+        for (int c = 0; c < 2 * CT; ++c)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[c][r] = __builtin_fmaf(acc[c][r], un[r >> 2][r & 3] * wi, abv[q][c]);
-        }
+            for (int r = 0; r < 16; ++r) acc[c][r] = __builtin_fmaf(acc[c][r], un[r >> 2][r & 3] * wi, abv[q][c]);
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             if (half || q) __syncthreads();                 // previous staging tile fully stored

@@ -1,4 +1,4 @@
-// The node update of the fp16x3 mode for FEW rows (round 5): k_node<..., F16>'s arithmetic, bit for bit, as three launches whose
+// The node update of the fp16x3 mode for FEW rows (round 5): k_node's arithmetic, bit for bit, as three launches whose
 // workgroups own a 32-row x 32-column output tile each.  Included through kernels.hpp.
 //
 // Why.  The fused kernel (k_node.hpp) gives a 32-row tile to ONE workgroup, which then streams 1.3 - 1.8 MB of weight images
@@ -11,7 +11,7 @@
 //     phase 3   AB_q = h' [W1a | W1b]_q^T + [b1 | 0]     grid: row tiles x 2 H / 32 x images
 // A workgroup = four wavefronts = the four QUARTERS of the contraction's K range: wavefront w runs k-steps [w KS/4, (w+1) KS/4)
 // into its own accumulator (its weight fragments - 8 or 16 KiB - are all requested at kernel entry), the four partial tiles meet in
-// LDS and are added as ((q0 + q1) + q2) + q3.  k_node<..., F16> sums its contractions in exactly these quarters (NodeMma KQ = 4),
+// LDS and are added as ((q0 + q1) + q2) + q3.  k_node sums its contractions in exactly these quarters (NodeMma),
 // ranges its operands by the same row bounds (which are functions of the row's max |h| and max |[h | agg]| only: phase 1 leaves
 // the two numbers in `rowinfo` for the later phases) and splits the same fp32 values, so the two paths agree bit for bit and a
 // sample's bits do not depend on which one its batch size selects (tests/test_gpu_parity.py::test_fp16x3_node_paths_agree_bitwise).

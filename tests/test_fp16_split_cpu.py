@@ -65,7 +65,7 @@ def test_fp16x3_ranging_cannot_overflow():
 
 
 def test_node_update_row_bounds_hold_and_are_usable():
-    """k_node<..., F16> ranges T and h' per row from bounds known before the first contraction (k_node.hpp):
+    """k_node ranges T and h' per row from bounds known before the first contraction (k_node.hpp):
     |T_r| <= max|X_r| max_c sum_k|W3[c][k]| + max|b3|,  |h'_r| <= max|h_r| + bound(T_r) max_c sum_k|W4[c][k]| + max|b4|.
     They must hold for every element (no FP16 overflow possible) and must not be so loose that typical elements fall out of the
     22-bit range of a scaled operand (15 binades below the bound)."""

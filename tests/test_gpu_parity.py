@@ -286,7 +286,7 @@ def test_fp16x3_operand_ranging(w2_gain, first_gain):
 
 @pytest.mark.parametrize("node_gain,emb_gain", [(2.0 ** -8, 1.0), (60.0, 1.0), (1.0, 2.0 ** -10), (1.0, 3000.0)])
 def test_fp16x3_node_operand_ranging(node_gain, emb_gain):
-    """The node update of the mode (k_node<..., F16>, width 256) ranges its three activation operands per row from a-priori bounds
+    """The node update of the mode (k_node, width 256) ranges its three activation operands per row from a-priori bounds
     (row maximum of [h | agg], L1 norms of W3 / W4) and its weights per matrix: node-MLP weights 256 x smaller / 60 x larger,
     node features 1000 x smaller / 3000 x larger (|h| up to ~1e5, beyond FP16's 65504) stay at the exact-fp32 mode's distance
     to the float64 oracle."""
@@ -389,7 +389,7 @@ def test_pocket_sized_graph_vs_oracle(precision, H):
 def test_fp16x3_node_path_by_width(H):
     """Which node kernels the fp16x3 mode runs, stated as behaviour: below width 128 the FP16 node kernel does not exist
     and the mode runs the exact-fp32 node kernels (k_node_f32 / k_gemm_r16; the edge kernels are FP16 at every width), from
-    128 up it runs k_node<..., F16>.  With the second edge Linear, its bias and the coordinate head zeroed every message
+    128 up it runs k_node.  With the second edge Linear, its bias and the coordinate head zeroed every message
     and every coordinate update is exactly 0 in every arithmetic (SiLU(0) = 0), so the output features are a function of
     the NODE path alone: bit-equal to the fp32 mode's at widths 32 and 64, fp32-accurate but not bit-equal at 128."""
     from hierdiff_amd.weights import synthetic_state_dict
@@ -440,7 +440,7 @@ def test_fp32_node_paths_agree_bitwise(H, L, B):
 
 @pytest.mark.parametrize("H,L,B", [(256, 2, 100), (128, 2, 100), (256, 1, 90)])
 def test_fp16x3_node_paths_agree_bitwise(H, L, B):
-    """fp16x3 runs the node update fused (k_node<..., F16>: one launch, one workgroup per 32 rows) from 2,048 active rows on and
+    """fp16x3 runs the node update fused (k_node: one launch, one workgroup per 32 rows) from 2,048 active rows on and
     as the three launches of k_node_split below (32 x 32 output tiles over many workgroups, the four K quarters of a contraction
     on four wavefronts: a batch of 2 - 64 molecules does not fill 256 CUs with a serial 20 - 27 us chain per row tile).  Both sum
     every contraction as ((q0 + q1) + q2) + q3 over the same K quarters, range their FP16 operands by the same row bounds and
