@@ -2627,6 +2627,7 @@ extern "C" int hd_posterior_step(hd_handle* h, hd_topology* topo, const float* z
     if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_posterior_step: noise_rows must be 1 or B");
     const int mol = (mol_shape < 0 || mol_shape > topo->N) ? topo->N : mol_shape;
     if (zs == zt && mol != topo->N) return fail(HD_E_INVALID, "hd_posterior_step: in-place needs mol_shape == N");
+    if ((size_t)mol * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_posterior_step: N * D floats exceed one workgroup's LDS");
     HIP_TRY(hipSetDevice(h->device));
     topo_use(topo, (hipStream_t)stream);
     return step_impl(h, topo, zt, eps, coef, coef_rows, make_noise(raw_x, raw_h, noise_rows, 0, 0, 0, 0), mol, zs, mol,
@@ -2836,6 +2837,7 @@ extern "C" int hd_sample_loop(hd_handle* h, hd_topology* topo, float* z, const f
     if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, "hd_sample_loop: context required");
     if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_loop: needs a time-conditioned model");
     const int mol = (mol_shape < 0 || mol_shape > topo->N) ? topo->N : mol_shape;
+    if ((size_t)mol * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_sample_loop: N * D floats exceed one workgroup's LDS");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     const int nsteps = s_hi - s_lo;
@@ -3302,6 +3304,8 @@ extern "C" int hd_sample_path(hd_handle* h, hd_topology* topo, float* z, const f
     if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_path: noise_rows must be 1 or B");
     if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, "hd_sample_path: context required");
     if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_path: needs a time-conditioned model");
+    if ((size_t)((mol_shape < 0 || mol_shape > topo->N) ? topo->N : mol_shape) * h->D * sizeof(float) > 64 * 1024)
+        return fail(HD_E_INVALID, "hd_sample_path: N * D floats exceed one workgroup's LDS");
     HIP_TRY(hipSetDevice(h->device));
     return path_loop(h, topo, z, context, mol_shape, k_lo, k_hi, raw_x, raw_h, noise_rows, seed, sample_id_base, use_graph,
                      nullptr, nullptr, 0, (hipStream_t)stream);
@@ -3368,6 +3372,7 @@ extern "C" int hd_sample_path_guided(hd_handle* h, hd_topology* topo, float* z, 
         if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, "hd_sample_path_guided: raw_x and raw_h go together");
         if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_path_guided: noise_rows must be 1 or B");
     }
+    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_sample_path_guided: N * D floats exceed one workgroup's LDS");
     HIP_TRY(hipSetDevice(h->device));
     GuideSrc gd;
     gd.ctx_u = context_u; gd.w = w_dev; gd.w_rows = w_rows; gd.phi = rescale;

@@ -159,7 +159,10 @@ int hd_nan_events(hd_handle* h, void* stream, long long* count);
  *          sigma_t, sigma = sigma_t_given_s * sigma_s / sigma_t}
  *   raw_x  device [noise_rows, mol, 3], raw_h device [noise_rows, mol, F]: the two randn draws;
  *          noise_rows = 1 reproduces fix_noise=True.  mol = mol_shape (< 0: N).
- *   zs may alias zt only when mol == N. */
+ *   zs may alias zt only when mol == N.
+ * One workgroup per molecule keeps the mol * D values of its molecule in LDS: mol * D * sizeof(float) > 64 KiB is refused on the host,
+ * before any launch, with HD_E_INVALID ("hd_posterior_step: N * D floats exceed one workgroup's LDS"), like hd_multistep_step and
+ * hd_diffuse.  hd_sample_loop, hd_sample_path and hd_sample_path_guided, which launch the same kernel, refuse it under their own names. */
 int hd_posterior_step(hd_handle* h, hd_topology* topo, const float* zt, const float* eps, const float* coef,
                       int coef_rows, const float* raw_x, const float* raw_h, int noise_rows, int mol_shape,
                       float* zs, void* stream);
@@ -210,7 +213,8 @@ int hd_set_schedule(hd_handle* h, int T, const float* tau, const float* coef4);
  *                grid is hd_sample_path below; its draws are the same T - s of the steps it visits.)
  *   use_graph    replay each step from a captured hipGraph (0 = plain launches).  The instantiated graph is
  *                cached with the topology and reused by later calls with the same arguments (any z / context /
- *                sample_id_base); it is stream-ordered like every other call - no host synchronisation. */
+ *                sample_id_base); it is stream-ordered like every other call - no host synchronisation.
+ * HD_E_INVALID, before any launch: mol * D floats beyond one workgroup's LDS (64 KiB), as hd_posterior_step. */
 int hd_sample_loop(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
                    int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
                    uint64_t seed, uint64_t sample_id_base, int use_graph, void* stream);
@@ -230,7 +234,8 @@ int hd_set_path(hd_handle* h, int K, const int* t_idx, const int* s_idx, const f
  *   raw_x/raw_h  device [(k_hi-k_lo), noise_rows, mol, 3|F] indexed by path position (first = k_lo), or NULL.
  *   use_graph    ONE captured transition per topology, whatever K: the path position lives in device memory and the captured
  *                kernels read time, coefficient row and draw through the uploaded tables.  Cached like the plain loop's graph and
- *                rebuilt when the path, seed, weights, schedule or noise arguments change; use_graph = 0 gives the same bits. */
+ *                rebuilt when the path, seed, weights, schedule or noise arguments change; use_graph = 0 gives the same bits.
+ * HD_E_INVALID, before any launch: mol * D floats beyond one workgroup's LDS (64 KiB), as hd_posterior_step. */
 int hd_sample_path(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
                    const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base,
                    int use_graph, void* stream);
