@@ -205,6 +205,25 @@ constexpr unsigned frag_off_f32(int u) { return (unsigned)(u * 64 * 16); }
 // The body of k_edge as a device function: `bid` / `nwt` = this workgroup's index among / the number of the launch's
 // whole-tile workgroups (k_edge: blockIdx.x / n_wg; k_edge_mixed: the first n_wg blocks of the grid), `smem` the dynamic LDS
 // (W2 double buffer + wave scratch), `wrd_s` the separate 4H-float LDS object described below.
+// How far the K loop of edge_tile_body is peeled at its end (the forms of the chunk body: see `chunk` there).  2: the last two
+// chunks have bodies of their own; 1: only the last chunk has, the second-to-last runs the loop's full body (and fetches 8 rows
+// nobody reads); 0: every chunk runs the full body, as before the peel.  The level of an instantiation is the highest at which
+// hipcc compiles it without a register spill - a spill next to the hand-counted loads is not an option (hierdiff_amd/build.py:
+// audit).  It is a measured table, not a rule derived from the register count: with more straight-line code behind the loop hipcc
+// schedules some fp16x3 forms up to the 256-register limit of two waves per SIMD and then spills, also where the same form needs
+// only 212 registers one level lower (the unscaled GCL form at H = 128).  Every (instantiation, level) pair: EXPERIMENTS.md
+// section AA; taken with -DHD_EDGE_PEEL_LEVEL=n, which forces one level everywhere (measurement builds only: the audit of the
+// product build rejects the spilling kernels that level 2 gives).
+constexpr int edge_peel_level(int H, int PREC, int ABL) {
+#ifdef HD_EDGE_PEEL_LEVEL
+    return HD_EDGE_PEEL_LEVEL;
+#else
+    if (PREC == 0) return 2;                                  // exact fp32: 237-242 registers at H = 256, no spill at any level
+    if (ABL & HD_EDGE_UNSCALED) return H >= 256 ? 0 : 1;      // training forward: H = 256 spills at 1 and 2; H = 128 (GCL, not saving) at 2
+    return H >= 256 ? 1 : 2;                                  // sampler's fp16x3: H = 256 (coordinate form) spills at 2
+#endif
+}
+
 template <int H, bool COORD, int PREC, int ABL>
 HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, const int bid, const int nwt) {
     static_assert(PREC == 0 || PREC == 3, "exact fp32 or fp16x3");
@@ -216,6 +235,9 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
     // (ABL bit 128, measurement only: a quarter of the stream - what keeping the W2 heads resident and sharing the tails between
     // eight wavefronts would leave; results are garbage, the time is what the DMA volume is worth)
     constexpr int GL_PER_WAVE = (ABL & 128) ? CHF / (4 * 256) / 4 : CHF / (4 * 256);   // 1 KiB pieces per wave per chunk
+    constexpr int LEVEL = edge_peel_level(H, PREC, ABL);
+    static_assert(LEVEL >= 0 && LEVEL <= 2, "peel level");
+    constexpr bool HAS_PEN = LEVEL >= 2, HAS_LAST = LEVEL >= 1;
     float* wbuf = smem;                   // [2][CHF]
     // w_r / w_d live in their own LDS object (wrd_s: [w_r | w_d | b2 | wa], staged once per workgroup): hipcc makes every
     // compiler-visible LDS read that may alias the destination of an in-flight global_load_lds wait for vmcnt(0) - with
@@ -374,8 +396,10 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
     __syncthreads();               // chunk 0 landed in every wave's share (w_r / w_d staged on the first pass)
     if constexpr (PREC == 0) make_P(0, Pc);
     else make_P_f16(0, phc, plc);
+    if constexpr (NCH > 1 || !HAS_LAST) {   // (one chunk, peeled as the last: nothing follows it, no rows to fetch ahead)
 #pragma unroll
-    for (int u = 0; u < NQ; ++u) rows_issue(u, NCH > 1 ? 1 : 0);
+        for (int u = 0; u < NQ; ++u) rows_issue(u, NCH > 1 ? 1 : 0);
+    }
 
     // accumulators start at the second layer's bias (saves the H/32 * 16 bias adds of the epilogue).  fp16x3: the bias joins
     // in the epilogue's un-scaling fma, so the accumulators start at zero - and are not initialised at all: the first chunk
@@ -398,22 +422,59 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
     if constexpr (ABL & 16) ts1 = __builtin_readcyclecounter();
     // (Unrolling this loop by two with swapped operand sets, to drop the 16 register copies per chunk, was
     // measured twice: 9-17 spilled registers, 125 vs 109 us and later 110-116 vs 103-106 us; fp32 285 vs 278.)
-    auto chunk = [&](auto First, const int c) {
+    //
+    // Three forms of the chunk body, chosen at compile time (`Kind`), each one branch-free scheduling region:
+    //   CH_MID  (chunks 0 .. NCH-3): MFMAs of chunk c, stream of chunk c+1, operands of chunk c+1, row gathers of chunk c+2;
+    //   CH_PEN  (chunk NCH-2):       MFMAs of chunk c, stream of chunk c+1, operands of chunk c+1 - there is no chunk c+2;
+    //   CH_LAST (chunk NCH-1):       MFMAs only - no stream, no operands, no gathers, no w_r / w_d reads.
+    // The runtime loop covers the CH_MID chunks; CH_PEN and CH_LAST follow it as straight-line code.  A workgroup computes one
+    // tile per wavefront and ends (k_edge and the whole-tile part of k_edge_mixed alike), so nothing ever follows the last chunk
+    // and no peeled form requests chunk 0 again.  That is peel level 2 (edge_peel_level).  At level 1 there is no CH_PEN: chunk
+    // NCH-2 runs CH_MID with the rows of "chunk c+2" clamped to the last chunk (8 gathers nobody reads, as before the peel).  At
+    // level 0 every chunk runs CH_MID with all three clamps of the loop as it was: operands and rows of the last chunk again, the
+    // stream of chunk 0 again.
+    constexpr int CH_MID = 0, CH_PEN = 1, CH_LAST = 2;
+    auto chunk = [&](auto First, auto Kind, const int c) {
         constexpr bool FIRST = decltype(First)::value;
+        constexpr int KIND = decltype(Kind)::value;
         const int buf = (ABL & 4) ? 0 : (gc & 1);
         if constexpr (!(ABL & 4) && !(ABL & 64)) {
-            // chunk c landed in LDS and every wave is done with the other buffer.  The only VMEM operations younger
-            // than chunk c's stream are the 8 row gathers of the previous iteration.
-            if (c > 0) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-            // The stream of the next chunk is issued unconditionally further down (the last chunk re-requests chunk 0,
-            // unused unless a further tile follows): with the stream inside a branch hipcc has to assume "no stream in
-            // flight" at the join and waits vmcnt(0) - i.e. for the stream itself - before the first use of the
-            // gathered AB rows, every chunk.
+            // chunk c landed in LDS and every wave is done with the other buffer.  VMEM operations younger than chunk c's
+            // stream, which the body before this one issued:
+            //   CH_MID, CH_PEN (c > 0): that body was a CH_MID - the 8 row gathers of chunk c+1                 -> vmcnt(8)
+            //   CH_LAST (c > 0), level 2: that body was the CH_PEN, which issues nothing behind its stream      -> vmcnt(0)
+            //   CH_LAST (c > 0), level 1: that body was a CH_MID with cn2 clamped - 8 row gathers nobody reads,
+            //                             drained behind the loop                                               -> vmcnt(8)
+            //   c == 0:                 the prologue's __syncthreads has done it
+            if constexpr (KIND == CH_LAST) {
+                if constexpr (NCH > 1 && HAS_PEN) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+                else if constexpr (NCH > 1) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
+            } else if constexpr (KIND == CH_PEN) {
+                if constexpr (NCH > 2) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
+            } else {
+                if (c > 0) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
+            }
+            static_assert(HAS_LAST || KIND == CH_MID, "without a peeled last chunk every chunk runs the full body");
+            // The stream of the next chunk is issued unconditionally further down in the forms that have a next chunk:
+            // with the stream inside a branch hipcc has to assume "no stream in flight" at the join and waits vmcnt(0) -
+            // i.e. for the stream itself - before the first use of the gathered AB rows, every chunk.
         }
-        // Branch-free from here to the end of the body (one scheduling region): the last iteration
-        // recomputes the final chunk's operands and refetches its rows, results unused.
+        // Branch-free from here to the end of the body (one scheduling region).
         u32x4 phn[2], pln[2];
-        const int cn1 = c + 1 < NCH ? c + 1 : NCH - 1, cn2 = c + 2 < NCH ? c + 2 : NCH - 1;
+        // (the clamps exist at the lower peel levels only, where a CH_MID body runs for a chunk that has no chunk c+1 / c+2)
+        const int cn1 = HAS_LAST ? c + 1 : (c + 1 < NCH ? c + 1 : NCH - 1);
+        const int cn2 = HAS_PEN ? c + 2 : (c + 2 < NCH ? c + 2 : NCH - 1);
+        const int cstream = HAS_LAST ? c + 1 : (c + 1 < NCH ? c + 1 : 0);
+        // Row quad q of chunk c+1 must have landed.  Outstanding VMEM at that point, oldest first:
+        //   CH_MID: quads q..3 of chunk c+1 (8 - 2q loads), the GL_PER_WAVE stream pieces, quads 0..q-1 of chunk c+2 (2q loads)
+        //           = 8 + GL_PER_WAVE, of which all but the oldest two may stay                      -> vmcnt(6 + GL_PER_WAVE)
+        //   CH_PEN: quads q..3 of chunk c+1 (8 - 2q loads), the GL_PER_WAVE stream pieces - no gathers of a chunk c+2 behind them
+        //           = 8 - 2q + GL_PER_WAVE, of which all but the oldest two may stay                 -> vmcnt(6 - 2q + GL_PER_WAVE)
+        auto rows_wait = [&](auto Q) {
+            constexpr int q = decltype(Q)::value;
+            static_assert(KIND != CH_LAST, "the last chunk waits for no rows");
+            vm_wait2<(KIND == CH_MID ? 6 : 6 - 2 * q) + GL_PER_WAVE>(pa[q], pb[q]);
+        };
         const float* Arow_n2 = Arow + KC * cn2;        // rows of chunk c+2: one address pair per chunk,
         const float* Brow_n2 = Brow + KC * cn2;        // the quad offset rides in the load's immediate
         const float* wb = wbuf + buf * CHF;
@@ -433,11 +494,10 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
                           frag_off_f32(q * NCT + c0 + (HC > 2 ? 2 : 0)), frag_off_f32(q * NCT + c0 + (HC > 3 ? 3 : 0))>(f, wb_lds);
             };
             read_unit(std::integral_constant<int, 0>{}, f0);
-            if constexpr (!(ABL & 4) && !(ABL & 32)) issue_chunk(c + 1 < NCH ? c + 1 : 0, buf ^ 1);
+            if constexpr (KIND != CH_LAST && !(ABL & 4) && !(ABL & 32)) issue_chunk(cstream, buf ^ 1);
             // Operands of chunk c+1 are produced IN PLACE: once the MFMAs of k-quad q have been issued their four operand
             // registers are dead, so quad q of the next chunk is built there (from rows requested one iteration ago) and
-            // the rows of chunk c+2 go into the freed row registers.  Outstanding VMEM at that point, oldest first:
-            // quads q..3 of chunk c+1, the GL_PER_WAVE stream pieces, quads 0..q-1 of chunk c+2.
+            // the rows of chunk c+2 go into the freed row registers (outstanding VMEM at that point: see rows_wait).
             static_for<0, NU>([&](auto Uc) {
                 constexpr int u = decltype(Uc)::value, q = u / UPQ, c0 = (u % UPQ) * HC;
                 f32x4(&cur)[4] = (u & 1) ? f1 : f0;
@@ -449,8 +509,8 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
 #pragma unroll
                     for (int ct = 0; ct < HC; ++ct)
                         acc[c0 + ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(Pc[4 * q + j], cur[ct][j], acc[c0 + ct], 0, 0, 0);
-                if constexpr (u % UPQ == UPQ - 1) {
-                    vm_wait2<6 + GL_PER_WAVE>(pa[q], pb[q]);
+                if constexpr (KIND != CH_LAST && u % UPQ == UPQ - 1) {
+                    rows_wait(std::integral_constant<int, q>{});
                     const f32x4 wr4 = *reinterpret_cast<const f32x4*>(wrd_s + 32 * cn1 + 16 * hh + 4 * q);
                     const f32x4 wd4 = *reinterpret_cast<const f32x4*>(wrd_s + H + 32 * cn1 + 16 * hh + 4 * q);
 #pragma unroll
@@ -460,8 +520,10 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
                         pre = __builtin_fmaf(d0, wd4[j], pre);
                         Pc[4 * q + j] = HD_F32_SILU(pre);
                     }
-                    if constexpr (ABL & 8) { pa[q] = f32x4{radial, d0, radial, d0}; pb[q] = pa[q]; }
-                    else vm_load2o<16 * q>(pa[q], pb[q], Arow_n2, Brow_n2);
+                    if constexpr (KIND == CH_MID) {
+                        if constexpr (ABL & 8) { pa[q] = f32x4{radial, d0, radial, d0}; pb[q] = pa[q]; }
+                        else vm_load2o<16 * q>(pa[q], pb[q], Arow_n2, Brow_n2);
+                    }
                 }
             });
         } else {
@@ -476,13 +538,15 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
             const float* wr_n = wrd_s + 32 * cn1 + 16 * hh;
             const float* wd_n = wrd_s + H + 32 * cn1 + 16 * hh;
             f32x4 wrq[2], wdq[2];
-            wrq[0] = *reinterpret_cast<const f32x4*>(wr_n);
-            wdq[0] = *reinterpret_cast<const f32x4*>(wd_n);
+            if constexpr (KIND != CH_LAST) {
+                wrq[0] = *reinterpret_cast<const f32x4*>(wr_n);
+                wdq[0] = *reinterpret_cast<const f32x4*>(wd_n);
+            }
             f16x8 f0[4], f1[4];
             lds_read4<f16x8, frag_off_f16<NCT>(0, 0), frag_off_f16<NCT>(0, 1), frag_off_f16<NCT>(1, 0), frag_off_f16<NCT>(1, 1)>(f0, wb_lds);
             // the stream for the next chunk goes out behind the first fragment reads: its eight LDS-DMA issues cover
             // the LDS latency the first MFMA group would otherwise wait out
-            if constexpr (!(ABL & 4) && !(ABL & 32)) issue_chunk(c + 1 < NCH ? c + 1 : 0, buf ^ 1);
+            if constexpr (KIND != CH_LAST && !(ABL & 4) && !(ABL & 32)) issue_chunk(cstream, buf ^ 1);
             static_for<0, NG>([&](auto Gc) {
                 constexpr int g = decltype(Gc)::value;
                 f16x8(&cur)[4] = (g & 1) ? f1 : f0;
@@ -499,12 +563,10 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
                 // whole L2 latency there.
                 constexpr int NGP = NG >= 2 ? NG / 2 : 1;          // groups that produce operands
                 constexpr int PPG = 8 / NGP;                       // pairs per producing group
-                if constexpr (g < NGP) {
+                if constexpr (KIND != CH_LAST && g < NGP) {
                     static_for<0, PPG / 2>([&](auto V) {
                         constexpr int u = g * (PPG / 2) + decltype(V)::value;   // quad u = values 4u .. 4u+3 (pairs 2u, 2u+1)
-                        // outstanding, oldest first: quads u..3 of chunk c+1, this chunk's GL_PER_WAVE stream
-                        // pieces, quads 0..u-1 of chunk c+2  =  8 + GL_PER_WAVE loads
-                        vm_wait2<6 + GL_PER_WAVE>(pa[u], pb[u]);
+                        rows_wait(std::integral_constant<int, u>{});             // (the counts: see rows_wait)
                         if constexpr (u + 1 < 4) {                       // w_r / w_d for the following four values
                             wrq[(u + 1) & 1] = *reinterpret_cast<const f32x4*>(wr_n + 4 * (u + 1));
                             wdq[(u + 1) & 1] = *reinterpret_cast<const f32x4*>(wd_n + 4 * (u + 1));
@@ -514,8 +576,10 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
                         phn[u >> 1][2 * (u & 1)] = hi[0]; phn[u >> 1][2 * (u & 1) + 1] = hi[1];
                         pln[u >> 1][2 * (u & 1)] = lo[0]; pln[u >> 1][2 * (u & 1) + 1] = lo[1];
                         // rows of chunk c+2 into the freed registers (quad offset as an immediate)
-                        if constexpr (ABL & 8) { pa[u] = f32x4{radial, d0, radial, d0}; pb[u] = pa[u]; }
-                        else vm_load2o<16 * u>(pa[u], pb[u], Arow_n2, Brow_n2);
+                        if constexpr (KIND == CH_MID) {
+                            if constexpr (ABL & 8) { pa[u] = f32x4{radial, d0, radial, d0}; pb[u] = pa[u]; }
+                            else vm_load2o<16 * u>(pa[u], pb[u], Arow_n2, Brow_n2);
+                        }
                     });
                 }
                 constexpr int u0 = 2 * g, u1 = 2 * g + 1;
@@ -537,21 +601,45 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
                 acc[c0] = mma_f16(A_h0, cur[1], acc[c0]);
                 acc[c1] = mma_f16(A_h1, cur[3], acc[c1]);
                 }
+                if constexpr (KIND != CH_LAST) {         // (the last chunk has no vector work to interleave)
 #pragma unroll
-                for (int k = 0; k < 6; ++k) {            // interleave: 1 MFMA, then up to 4 VALU
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+                    for (int k = 0; k < 6; ++k) {        // interleave: 1 MFMA, then up to 4 VALU
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+                    }
                 }
             });
+            if constexpr (KIND != CH_LAST) {
 #pragma unroll
-            for (int st = 0; st < 2; ++st) { phc[st] = phn[st]; plc[st] = pln[st]; }
+                for (int st = 0; st < 2; ++st) { phc[st] = phn[st]; plc[st] = pln[st]; }
+            }
         }
     };
-    if constexpr (PEEL) { chunk(std::true_type{}, 0); ++gc; }
+    using KMid = std::integral_constant<int, CH_MID>;
+    using KPen = std::integral_constant<int, CH_PEN>;
+    using KLast = std::integral_constant<int, CH_LAST>;
+    if constexpr (!HAS_LAST) {
+        if constexpr (PEEL) { chunk(std::true_type{}, KMid{}, 0); ++gc; }
 #pragma unroll 1
-    for (int c = PEEL ? 1 : 0; c < NCH; ++c, ++gc) chunk(std::false_type{}, c);
+        for (int c = PEEL ? 1 : 0; c < NCH; ++c, ++gc) chunk(std::false_type{}, KMid{}, c);
+    } else if constexpr (NCH == 1) {       // the first chunk is the last
+        chunk(std::bool_constant<PEEL>{}, KLast{}, 0);
+    } else if constexpr (NCH == 2) {       // the first chunk is the second-to-last
+        chunk(std::bool_constant<PEEL>{}, std::conditional_t<HAS_PEN, KPen, KMid>{}, 0); ++gc;
+        chunk(std::false_type{}, KLast{}, 1);
+    } else {
+        if constexpr (PEEL) { chunk(std::true_type{}, KMid{}, 0); ++gc; }
+#pragma unroll 1
+        for (int c = PEEL ? 1 : 0; c < NCH - (HAS_PEN ? 2 : 1); ++c, ++gc) chunk(std::false_type{}, KMid{}, c);
+        if constexpr (HAS_PEN) { chunk(std::false_type{}, KPen{}, NCH - 2); ++gc; }
+        chunk(std::false_type{}, KLast{}, NCH - 1);
+    }
 
-    // drain the (unused) last gathers before their registers are reused
+    // Drain before the row registers are reused.  At peel levels 0 and 1 this wait is NEEDED: the last full body (chunk NCH-1 at
+    // level 0, chunk NCH-2 at level 1) has issued 8 row gathers nobody reads (cn2 clamped), and the barrier of the last chunk at
+    // level 1 waits vmcnt(8) only, which leaves them in flight.  At level 2 nothing is in flight here (the last chunk's barrier
+    // waited vmcnt(0), or the prologue did at NCH == 1) and the wait costs nothing; the ablated forms without that barrier drain
+    // their stream here.
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(pa[0]), "+v"(pa[1]), "+v"(pa[2]), "+v"(pa[3]),
                                         "+v"(pb[0]), "+v"(pb[1]), "+v"(pb[2]), "+v"(pb[3]));
     if constexpr (ABL & 16) ts2 = __builtin_readcyclecounter();

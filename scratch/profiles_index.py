@@ -10,6 +10,7 @@ RULES = [
     (r"r05_bench_default_slow_box\.json", "default bench line mid-round on a box whose 16-bit MFMA clock was ~6 % lower (fp16 22.2 ns per MFMA)", "DESIGN 6 (box-to-box spread)"),
     (r"r\d+_bench_default.*\.json|r\d+_bench_\d+steps.*\.json|r\d+_bench_(fp32|bf16x3|first_path)\.json|r\d+_bench_3steps\.json",
      "complete JSON line of a `python bench.py` run on a gpurun box", "DESIGN 6 (bench numbers of that round); the `configs` / `next_rows` blocks the driver's tail truncates"),
+    (r"r07_(parent|peel)_fp32_T50_kernel_stats\.csv", "rocprofv3 --kernel-trace --stats of `bench.py --gpus 1 --timesteps 50 --steps 1 --warmup 1 --no-kernel-events` (exact fp32), same box, minutes apart: `parent` = the library before the peeled K loop of k_edge, `peel` = with it", "EXPERIMENTS AA (k_edge -6.8 us per launch, every other kernel unchanged)"),
     (r"r\d+_(fp32|bf16x3|bf16x6|fp16x3|first_path)_T\d+_kernel_stats.*\.csv", "rocprofv3 --kernel-trace --stats of a 50-timestep bench run in that arithmetic", "roofline.achieved / avg_launch_us of the bench line must agree with this average"),
     (r"r01_fp32_firstpath_pmc_.*\.csv", "raw FETCH_SIZE / WRITE_SIZE counter pass of the first round-1 path", "history only"),
     (r"r\d+_counters\.json", "SQ / FETCH_SIZE / WRITE_SIZE counters per kernel family, reduced by scratch/summarize_profiles.py, with the library and source hashes", "bench line `roofline.pmc`, `traffic`; DESIGN 4 tables"),
