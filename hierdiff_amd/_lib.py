@@ -68,6 +68,10 @@ SIGNATURES = {
     "hd_sample_path_guided": (C.c_int, [_VP, _VP, _FP, _FP, _FP, _FP, C.c_int, C.c_float, C.c_int, C.c_int, _FP, _FP, C.c_int,
                                         C.c_uint64, C.c_uint64, C.c_int, _U8P, _FP, C.c_int, _VP]),
     "hd_guided_graph_builds": (C.c_longlong, [_VP]),
+    "hd_set_chain": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int]),
+    "hd_chain_attach": (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]),
+    "hd_chain_detach": (C.c_int, [_VP]),
+    "hd_chain_graph_builds": (C.c_longlong, [_VP]),
     "hd_diffuse": (C.c_int, [_VP, _VP, _FP, C.c_float, C.c_float, _FP, _FP, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int,
                              _FP, _VP]),
     "hd_set_path_up": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]),

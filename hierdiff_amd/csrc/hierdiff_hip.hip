@@ -110,6 +110,13 @@ struct hd_handle {
     float *d_path_coef, *d_path_coef_ip;         // [K][4] each; d_path_coef_ip null when no inpainting rows were given
     unsigned long long path_sched_gen, path_gen; // sched_gen the path was set for (0: not set); bumped by every hd_set_path
     bool path_up;               // the path ascends (hd_set_path_up: t_idx[k] < s_idx[k], linear rows with c == 0)
+    // recording (hd_set_chain): which frame of an attached sink every transition of the current path writes, and for the data
+    // prediction {alpha_t, sigma_t} of its departure level
+    int chain_frames;
+    int* d_chain_frame;         // [K], -1: none
+    float* d_chain_as;          // [K][2]; null when hd_set_chain got none
+    unsigned long long chain_path_gen, chain_gen;   // path_gen the tables were set for (0: not set); bumped by every hd_set_chain
+    float** d_chain_dst;        // graph replay: the sink a recording transition writes (set by k_path_state)
     // scoring (hd_set_nll_terms / hd_nll_terms / hd_nll_finish): K terms t_idx[k] of the bound, rows {alpha_t, sigma_t, w_t, 0}
     int nll_K;
     std::vector<int> nll_t_h;
@@ -177,6 +184,17 @@ struct PathKey {
     }
 };
 
+// The same for a captured recording transition (hd_chain_attach): the sink's address is NOT part of it (it lives in d_chain_dst).
+struct ChainKey {
+    PathKey path;
+    int what;
+    float nv0, nv1, nb1;
+    unsigned long long chain_gen;
+    bool operator==(const ChainKey& o) const {
+        return path == o.path && what == o.what && nv0 == o.nv0 && nv1 == o.nv1 && nb1 == o.nb1 && chain_gen == o.chain_gen;
+    }
+};
+
 // The same for a captured term of the scoring loop (hd_nll_terms).
 struct NllKey {
     const float *raw_x, *raw_h;
@@ -229,6 +247,14 @@ struct hd_topology {
     PathKey gdkey;
     long long guided_builds;
     float *guide_mem, *eps_u, *ctxu_buf, *wbuf;
+    // hd_chain_attach: the sink every path loop on this topology records into (null: none), and the recording transition - guided
+    // or not - in a graph of its own next to the two above (hd_chain_graph_builds)
+    float* chain_dst;
+    int chain_frames, chain_what;              // what 0: the state behind the transition, 1: its data prediction
+    float chain_nv0, chain_nv1, chain_nb1;
+    hipGraphExec_t gexec_chain;
+    ChainKey ckey;
+    long long chain_builds;
     // multistep paths (hd_set_path_multistep): the previous transition's data prediction x^ [B][N][D], allocated by the first
     // form-2 call at an address the captured transitions keep; host-side, which path generation and position it belongs to
     float* ms_hist;
@@ -353,6 +379,8 @@ extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
     h->d_coef_ip = nullptr; h->ip_sched_gen = 0; h->ip_gen = 0; h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
     h->path_K = 0; h->path_form = 0; h->d_path_t = h->d_path_s = nullptr; h->d_path_coef = h->d_path_coef_ip = nullptr;
     h->path_sched_gen = 0; h->path_gen = 0; h->path_up = false;
+    h->chain_frames = 0; h->d_chain_frame = nullptr; h->d_chain_as = nullptr; h->chain_path_gen = 0; h->chain_gen = 0;
+    h->d_chain_dst = nullptr;
     h->nll_K = 0; h->d_nll_t = nullptr; h->d_nll_coef = nullptr; h->nll_sched_gen = 0; h->nll_gen = 0;
     h->d_nanflag = nullptr; h->d_nan_events = nullptr; h->d_step = nullptr; h->d_draw = nullptr; h->d_tcur = nullptr;
     h->d_base = nullptr;
@@ -383,6 +411,7 @@ extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
         HD_TRY(dev_alloc(&h->d_draw, 1));
         HD_TRY(dev_alloc(&h->d_tcur, 1));
         HD_TRY(dev_alloc(&h->d_base, 1));
+        HD_TRY(dev_alloc(&h->d_chain_dst, 1));
         HIP_TRY(hipMemset(h->d_nanflag, 0, sizeof(int)));
         HIP_TRY(hipMemset(h->d_nan_events, 0, sizeof(long long)));
         HIP_TRY(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
@@ -404,6 +433,7 @@ extern "C" int hd_destroy(hd_handle* h) {
     hipFree(h->d_tau); hipFree(h->d_coef); hipFree(h->d_step); hipFree(h->d_draw); hipFree(h->d_tcur); hipFree(h->d_base);
     hipFree(h->d_coef_ip); hipFree(h->d_ipdraw);
     hipFree(h->d_path_t); hipFree(h->d_path_s); hipFree(h->d_path_coef); hipFree(h->d_path_coef_ip);
+    hipFree(h->d_chain_frame); hipFree(h->d_chain_as); hipFree(h->d_chain_dst);
     hipFree(h->d_nll_t); hipFree(h->d_nll_coef);
 #ifdef HD_DEBUG_KERNELS
     hipFree(h->d_trace);
@@ -773,8 +803,8 @@ extern "C" int hd_arena_pool_trim(void) {
 }
 
 // the graph slots of a topology, one per captured loop, and the one way a slot's graph goes (replay scaffold, "sampling maths")
-static std::array<hipGraphExec_t*, 5> graph_slots(hd_topology* t) {
-    return {&t->gexec, &t->gexec_ip, &t->gexec_path, &t->gexec_guided, &t->gexec_nll};
+static std::array<hipGraphExec_t*, 6> graph_slots(hd_topology* t) {
+    return {&t->gexec, &t->gexec_ip, &t->gexec_path, &t->gexec_guided, &t->gexec_chain, &t->gexec_nll};
 }
 static void graph_drop(hipGraphExec_t* gx) {
     if (*gx) hipGraphExecDestroy(*gx);
@@ -3134,6 +3164,42 @@ extern "C" int hd_set_path_multistep(hd_handle* h, int K, const int* t_idx, cons
 
 extern "C" long long hd_path_graph_builds(const hd_topology* topo) { return topo ? topo->path_builds : -1; }
 
+// ----------------------------------------------------------------------------- recording the trajectory of a path loop
+
+extern "C" int hd_set_chain(hd_handle* h, int K, const int* frame_of, const float* alpha_sigma, int frames) {
+    if (!h || !frame_of || K < 1 || frames < 1) return fail(HD_E_INVALID, "hd_set_chain: bad argument");
+    if (h->path_K < 1 || h->path_sched_gen != h->sched_gen) return fail(HD_E_STATE, "hd_set_chain: path not set for the current schedule (hd_set_path)");
+    if (K != h->path_K) return fail(HD_E_INVALID, "hd_set_chain: K differs from the path's (hd_set_path)");
+    for (int k = 0; k < K; ++k)
+        if (frame_of[k] < -1 || frame_of[k] >= frames) return fail(HD_E_INVALID, "hd_set_chain: need -1 <= frame_of[k] < frames");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
+    hipFree(h->d_chain_frame); hipFree(h->d_chain_as);
+    h->d_chain_frame = nullptr; h->d_chain_as = nullptr;
+    h->chain_path_gen = 0;
+    HD_TRY(dev_upload(&h->d_chain_frame, std::vector<int>(frame_of, frame_of + K)));
+    if (alpha_sigma) HD_TRY(dev_upload(&h->d_chain_as, std::vector<float>(alpha_sigma, alpha_sigma + (size_t)2 * K)));
+    h->chain_frames = frames;
+    h->chain_path_gen = h->path_gen;
+    h->chain_gen++;                            // captured graphs hold the old table addresses
+    return HD_OK;
+}
+
+extern "C" int hd_chain_attach(hd_topology* topo, float* chain, int frames, int what, float nv0, float nv1, float nb1) {
+    if (!topo || !chain || frames < 1) return fail(HD_E_INVALID, "hd_chain_attach: null topology / sink, or frames < 1");
+    if (what != 0 && what != 1) return fail(HD_E_INVALID, "hd_chain_attach: what must be 0 (the state) or 1 (the data prediction)");
+    topo->chain_dst = chain; topo->chain_frames = frames; topo->chain_what = what;
+    topo->chain_nv0 = nv0; topo->chain_nv1 = nv1; topo->chain_nb1 = nb1;
+    return HD_OK;
+}
+
+extern "C" int hd_chain_detach(hd_topology* topo) {
+    if (topo) topo->chain_dst = nullptr;
+    return HD_OK;
+}
+
+extern "C" long long hd_chain_graph_builds(const hd_topology* topo) { return topo ? topo->chain_builds : -1; }
+
 // Classifier-free guidance of a path loop: every network call becomes two (context, then ctx_u) and k_guide_combine in place.
 struct GuideSrc {
     const float* ctx_u;   // [B,N,C] the null (or any second) context
@@ -3164,7 +3230,22 @@ static int guide_buffers(hd_handle* h, hd_topology* t) {
     return HD_OK;
 }
 
+// One frame of the topology's sink (hd_chain_attach) from transition io.row: the state z, or with `eps` the data prediction.
+static int chain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* eps) {
+    ProfScope ps(h, io.s, 2);
+    ChainArgs a;
+    a.z = io.z; a.eps = eps; a.nm = t->nm_bytes; a.frame_of = h->d_chain_frame; a.alsig = h->d_chain_as;
+    a.dst_w = io.step ? h->d_chain_dst : nullptr; a.dst = io.step ? nullptr : t->chain_dst; a.step_ptr = io.step; a.k = io.row;
+    a.nv0 = t->chain_nv0; a.nv1 = t->chain_nv1; a.nb1 = t->chain_nb1; a.B = t->B; a.N = t->N; a.D = h->D;
+    if (eps) hipLaunchKernelGGL(k_chain_frame<1>, dim3(t->B), dim3(256), 0, io.s, a);
+    else hipLaunchKernelGGL(k_chain_frame<0>, dim3(t->B), dim3(256), 0, io.s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
 // The path loops: R = 0 is the plain one, R >= 1 the inpainting one with R rounds per transition; gd != NULL guides either.
+// A topology with a sink attached (hd_chain_attach) records: one more launch per transition, behind the update of its last round
+// (the state) or between that round's network call and its update (the data prediction).
 static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
                          const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
                          const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const GuideSrc* gd);
@@ -3205,16 +3286,31 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
     topo_use(topo, s);
     if (ntr == 0) return HD_OK;
     if (gd) HD_TRY(guide_buffers(h, topo));
+    const bool rec = topo->chain_dst != nullptr;
+    if (rec) {
+        if (!h->d_chain_frame || h->chain_path_gen != h->path_gen)
+            return fail(HD_E_STATE, "path loop: a chain sink is attached but the chain tables are not set for the current path (hd_set_chain)");
+        if (h->chain_frames != topo->chain_frames)
+            return fail(HD_E_INVALID, "path loop: the attached sink holds " + std::to_string(topo->chain_frames) + " frames, the chain "
+                        "tables were set for " + std::to_string(h->chain_frames));
+        if (topo->chain_what == 1 && !h->d_chain_as)
+            return fail(HD_E_STATE, "path loop: recording the data prediction needs the {alpha_t, sigma_t} rows (hd_set_chain)");
+        if (mol != N) return fail(HD_E_INVALID, "path loop: a chain sink records whole molecules only (mol_shape < N)");
+    }
+    const int rounds = R ? R : 1;
     auto transition = [&](const LoopIO& io) -> int {         // all rounds of one transition; io.row is the path position
-        for (int j = 0; j < (R ? R : 1); ++j) {
+        for (int j = 0; j < rounds; ++j) {
             HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx, ms, topo->eps, io.s));
             if (gd) {
                 HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx_u, ms, topo->eps_u, io.s));
                 HD_TRY(guide_launch(h, topo, topo->eps, topo->eps_u, io.w, gd->w_rows, gd->phi, topo->eps, io.s));
             }
+            const bool rec_z = rec && j == rounds - 1 && topo->chain_what == 0;
+            if (rec && j == rounds - 1 && topo->chain_what == 1) HD_TRY(chain_launch(h, topo, io, topo->eps));
             if (form == 2) {
                 HD_TRY(solver_launch(h, topo, io.z, topo->eps, h->d_path_coef + (size_t)io.row * 5, nullptr, topo->ms_hist,
                                      topo->ms_hist, mol, io.z, io.step, io.s));
+                if (rec_z) HD_TRY(chain_launch(h, topo, io, nullptr));
                 continue;
             }
             NoiseSrc ns = make_noise(raw_x ? raw_x + io.ro * 3 : nullptr, raw_h ? raw_h + io.ro * h->F : nullptr, noise_rows, seed,
@@ -3222,6 +3318,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
             HD_TRY(step_impl(h, topo, io.z, topo->eps, h->d_path_coef + (size_t)io.row * 4, 1, ns, mol, io.z, N, io.step,
                              io.step ? io.draw_w + 3 * j : nullptr, 0, io.s, io.base_w, form, io.step ? k_lo : -1));
             if (R) HD_TRY(inpaint_round(h, topo, io, j, R, stride, seed, h->d_path_coef_ip));
+            if (rec_z) HD_TRY(chain_launch(h, topo, io, nullptr));
         }
         return HD_OK;
     };
@@ -3250,13 +3347,22 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
     key.k_lo = raw_x ? k_lo : 0; key.resamplings = R; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
     key.path_gen = h->path_gen; key.ip_gen = R ? h->ip_gen : 0;
     key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
-    // the guided transition is a graph of its own: guided and unguided calls on one topology do not evict each other
-    hipGraphExec_t* gx = gd ? &topo->gexec_guided : &topo->gexec_path;
+    // the guided transition is a graph of its own: guided and unguided calls on one topology do not evict each other; so is the
+    // recording one (either kind), keyed on everything it bakes in but the sink's address
+    hipGraphExec_t* gx = rec ? &topo->gexec_chain : gd ? &topo->gexec_guided : &topo->gexec_path;
     PathKey& kx = gd ? topo->gdkey : topo->pkey;
-    HD_TRY(replay_evict(h, rs, gx, kx, key));
+    ChainKey ckey;
+    if (rec) {
+        ckey.path = key; ckey.what = topo->chain_what; ckey.nv0 = topo->chain_nv0; ckey.nv1 = topo->chain_nv1; ckey.nb1 = topo->chain_nb1;
+        ckey.chain_gen = h->chain_gen;
+        HD_TRY(replay_evict(h, rs, gx, topo->ckey, ckey));
+    } else {
+        HD_TRY(replay_evict(h, rs, gx, kx, key));
+    }
     PathWords w;
     w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = R ? h->d_ipdraw : nullptr;
     w.tau = h->d_tau; w.t_idx = h->d_path_t; w.s_idx = h->d_path_s; w.K = K; w.T = T; w.nd = nd; w.stride = stride;
+    w.chain = rec ? h->d_chain_dst : nullptr;
     if (!*gx) {
         LoopIO io = loop_io_captured(h, R ? h->d_ipdraw : h->d_draw, rs);
         io.z = topo->zbuf; io.ctx = context ? topo->ctxbuf : nullptr; io.fixed = topo->ip_fixed; io.known = topo->ip_known;
@@ -3266,8 +3372,8 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
             hipLaunchKernelGGL(k_path_advance, dim3(1), dim3(64), 0, rs, w);
             return HD_OK;
         }));
-        kx = key;
-        if (gd) topo->guided_builds++; else topo->path_builds++;
+        if (rec) { topo->ckey = ckey; topo->chain_builds++; }
+        else { kx = key; if (gd) topo->guided_builds++; else topo->path_builds++; }
     }
     HIP_TRY(hipMemcpyAsync(topo->zbuf, z, zbytes, hipMemcpyDeviceToDevice, rs));
     if (context) HIP_TRY(hipMemcpyAsync(topo->ctxbuf, context, cbytes, hipMemcpyDeviceToDevice, rs));
@@ -3279,7 +3385,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
         HIP_TRY(hipMemcpyAsync(topo->ip_fixed, fixed_mask, BN, hipMemcpyDeviceToDevice, rs));
         HIP_TRY(hipMemcpyAsync(topo->ip_known, xh_known, zbytes, hipMemcpyDeviceToDevice, rs));
     }
-    hipLaunchKernelGGL(k_path_state, dim3(1), dim3(64), 0, rs, w, k_lo, (unsigned long long)sample_id_base);
+    hipLaunchKernelGGL(k_path_state, dim3(1), dim3(64), 0, rs, w, k_lo, (unsigned long long)sample_id_base, topo->chain_dst);
     HD_TRY(replay_run(*gx, ntr, rs));
     HIP_TRY(hipMemcpyAsync(z, topo->zbuf, zbytes, hipMemcpyDeviceToDevice, rs));
     return replay_leave(h, s, rs);

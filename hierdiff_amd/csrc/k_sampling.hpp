@@ -391,6 +391,7 @@ __global__ void k_advance(int* step, uint32_t* draw, float* t_cur, const float* 
 // noise counter the fine-grid index of the arrival step, draw = T - s_idx[k] (the plain loop's layout restricted to the
 // visited s).  The inpainting loop's 3 * resamplings streams are offset by `stride` each (nd = 0: plain path loop).
 // Behind the last transition (k == K) the words keep the values of k = K - 1; nothing reads them.  One workgroup.
+// `chain`: the word a recording transition reads its sink from (k_chain.hpp; null: nothing records) - set by k_path_state alone.
 struct PathWords {
     int* step;
     uint32_t* draw;
@@ -402,6 +403,7 @@ struct PathWords {
     const int* s_idx;     // [K]
     int K, T, nd;
     uint32_t stride;
+    float** chain;
 };
 
 HD_DEVINL void path_words_set(const PathWords& w, int k) {
@@ -411,8 +413,8 @@ HD_DEVINL void path_words_set(const PathWords& w, int k) {
     for (int i = threadIdx.x; i < w.nd; i += blockDim.x) w.ipdraw[i] = w.stride * (uint32_t)i + d;
 }
 
-__global__ void k_path_state(PathWords w, int k0, unsigned long long b0) {
-    if (threadIdx.x == 0) *w.base = b0;
+__global__ void k_path_state(PathWords w, int k0, unsigned long long b0, float* chain) {
+    if (threadIdx.x == 0) { *w.base = b0; if (w.chain) *w.chain = chain; }
     path_words_set(w, k0);
 }
 

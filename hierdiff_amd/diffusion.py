@@ -664,6 +664,70 @@ class DiffusionQM9(_Base):
             self._path_cache = (tabs, key, pt)
         return self._path_cache[2]
 
+    # ------------------------------------------------------------------ recording a trajectory (the reference's sample_chain)
+    def _chain_check(self, keep_frames, record, what: str, pocket=None, needs_noise: bool = True):
+        """None when nothing is recorded (keep_frames None), else the library's code of `record`: 0 for "z" (the default: the state
+        behind every kept transition), 1 for "x0" (its data prediction).  Pure host checks, raised before the GPU is touched."""
+        if keep_frames is None:
+            if record is not None:
+                raise ValueError(f"{what}: record={record!r} records nothing without keep_frames")
+            return None
+        if record not in (None, "z", "x0"):
+            raise ValueError(f"{what}: record must be 'z' or 'x0', got {record!r}")
+        if isinstance(keep_frames, bool) or not isinstance(keep_frames, (int, np.integer)):
+            raise ValueError(f"{what}: keep_frames must be an integer, got {keep_frames!r}")
+        if self.pocket or pocket is not None:
+            raise NotImplementedError(f"{what}: recording a chain is not supported for pocket models (whole molecules only)")
+        if getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics":
+            raise NotImplementedError(f"{what}: recording a chain runs inside the library's loop: mode 'gnn_dynamics' is not supported")
+        if needs_noise and self.noise_mode == "torch":
+            raise NotImplementedError(f"{what}: recording a chain runs inside the library's loop: noise_mode 'torch' is not supported")
+        return 1 if record == "x0" else 0
+
+    def _chain_open(self, handle, topo, tabs, cf, what: int, B: int, N: int, dev):
+        """The sink [keep, B, N, D] of a recording call, attached to `topo` (hd_chain_attach) behind the tables of the path that
+        `_path_tables` has just set (hd_set_chain, once per (path tables, frame table)).  The caller detaches (`_chain_close`)."""
+        pt = self._path_cache[2]
+        keep = len(cf.frame_t)
+        key = (tuple(cf.frame_of), keep)
+        hit = self.__dict__.get("_chain_cache")
+        if hit is None or hit[0] is not pt or hit[1] != key:
+            als = np.ascontiguousarray([self._alpha_sigma(tabs, int(t)) for t in pt["t_idx"]], dtype=np.float32)
+            fo = np.ascontiguousarray(cf.frame_of, dtype=np.int32)
+            self._chain_cache = None
+            _lib.check(_lib.load().hd_set_chain(handle, int(fo.shape[0]), fo.ctypes.data_as(C.POINTER(C.c_int)),
+                                                als.ctypes.data_as(C.POINTER(C.c_float)), keep), "hd_set_chain")
+            self._chain_cache = (pt, key)
+        chain = torch.zeros((keep, B, N, self.n_dims + self.in_node_nf), device=dev, dtype=torch.float32)
+        _lib.check(_lib.load().hd_chain_attach(topo.ptr, chain.data_ptr(), keep, int(what), float(self.norm_values[0]),
+                                               float(self.norm_values[1]), float(self.norm_biases[1] or 0.0)), "hd_chain_attach")
+        return chain
+
+    @staticmethod
+    def _chain_close(topo):
+        _lib.check(_lib.load().hd_chain_detach(topo.ptr), "hd_chain_detach")
+
+    def _chain_times(self, keep_frames, t_start=None, inpaint: bool = False, steps=None, eta=None, spacing=None, timesteps=None,
+                     solver=None, lower_order_final=None, **_):
+        """[keep] the grid index every frame of a recording call has arrived at (`paths.chain_frames`): host arithmetic only."""
+        from . import paths
+        if t_start is not None:
+            path = self._latent_path(t_start, steps, eta, spacing, timesteps, solver, lower_order_final)[1]
+        else:
+            pe = self._resolve_path(steps, eta, spacing, timesteps, inpaint=inpaint, solver=solver, lower_order_final=lower_order_final)
+            path = paths.build_path(self.T) if pe is None else pe[0]
+        return torch.tensor(paths.chain_frames(len(path) - 1, keep_frames, path).frame_t, dtype=torch.int64)
+
+    def _chain_into(self, results, chain, sizes, chain_t):
+        """'chain_x' [keep, n_i, 3], 'chain_h' [keep, n_i, F], 'chain_t' [keep] into every molecule's dict (CPU, trimmed)."""
+        c = chain.cpu()
+        for i, res in enumerate(results):
+            n = int(sizes[i])
+            res['chain_x'] = c[:, i, :n, :self.n_dims].clone()
+            res['chain_h'] = c[:, i, :n, self.n_dims:].clone()
+            res['chain_t'] = chain_t.clone()
+        return results
+
     def _check_masked(self, x, node_mask, what):
         if self.debug_checks:
             bad = (x * (~node_mask.bool())).abs().max().item()
@@ -811,8 +875,17 @@ class DiffusionQM9(_Base):
                           sample_id_base: int = 0, z_init: Optional[torch.Tensor] = None, pocket=None, *,
                           steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
                           timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
-                          solver: Optional[str] = None, lower_order_final: Optional[bool] = None):
+                          solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
+                          keep_frames: Optional[int] = None, record: Optional[str] = None):
         """z_T -> (x, h) for given masks: draw z_T, T posterior steps, final decode.
+
+        keep_frames / record (keyword-only; None: nothing is recorded and the call is today's): the reference's `sample_chain`
+        (en_diffusion.py:669-710) - the chain runs in the path loop (the identity path when no few-step path is asked for) with a
+        sink attached, and a third tensor comes back: chain [keep_frames, B, N, D] on the device, in data units (`unnormalize`).
+        Frame (p * keep_frames) // K holds the state at path position p counted from the t = 0 end (`paths.chain_frames`: the last
+        state that falls into a frame stays, as in the reference), frame 0 is cat(x, h) of the decode.  record="x0" keeps the data
+        prediction of the same transitions instead of their states.  1 <= keep_frames <= K.  (x, h) are the bits of the same call
+        without recording.  Not with pocket models, mode 'gnn_dynamics' or noise_mode 'torch'.
 
         solver / lower_order_final (keyword-only; None: the model's `sample_solver` / `sample_lower_order_final`): None and "ddim" are the first-order
         updates below; "dpm2m" runs the path with DPM-Solver++(2M) (hd_set_path_multistep: the eta = 0 update plus a correction
@@ -853,6 +926,11 @@ class DiffusionQM9(_Base):
             raise ValueError("context required")
         if gd is not None and pe is None:            # a guided chain always runs in the path loop: the identity path, ancestral steps
             pe = (paths.build_path(self.T), 1.0)
+        what = self._chain_check(keep_frames, record, "sample_from_masks", pocket, needs_noise=raw_noises is None)
+        cf = None
+        if what is not None:                         # so does a recorded one
+            pe = (paths.build_path(self.T), 1.0) if pe is None else pe
+            cf = paths.chain_frames(len(pe[0]) - 1, keep_frames, pe[0])
         if pe is not None and (getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics" or
                                (self.noise_mode == "torch" and raw_noises is None)):
             raise NotImplementedError("few-step sampling runs inside the library's loop: mode 'gnn_dynamics' and noise_mode 'torch' "
@@ -889,7 +967,19 @@ class DiffusionQM9(_Base):
         stream = _stream(dev)
         g = None if gd is None else self._guide_device(gd, node_mask, dev)
 
+        chain = []
+
         def run_loop(z_mol, rx, rh, rows, seed, base):
+            """`run_steps`; a recording call attaches its sink to the topology for the time of the loop."""
+            if cf is None:
+                return run_steps(z_mol, rx, rh, rows, seed, base)
+            chain.append(self._chain_open(h, topo_loop, tabs, cf, what, B, N, dev))
+            try:
+                return run_steps(z_mol, rx, rh, rows, seed, base)
+            finally:
+                self._chain_close(topo_loop)
+
+        def run_steps(z_mol, rx, rh, rows, seed, base):
             """T posterior steps on [B,N,D]; with a pocket the fixed rows ride along behind the molecule."""
             zz = z_mol if tail is None else torch.cat([z_mol, tail], dim=1).contiguous()
             if g is not None:            # guided: the K transitions of the path, two network calls each
@@ -961,6 +1051,9 @@ class DiffusionQM9(_Base):
                                           philox=(sample_id_base, T + 1))
         else:
             x, hfeat = self._final_decode(z, eps, node_mask, edge_mask, coef3, fix_noise, final_raw)
+        if cf is not None:
+            chain[0][0] = torch.cat([x, hfeat], dim=2)
+            return x, hfeat, chain[0]
         return x, hfeat
 
     @torch.no_grad()
@@ -1300,7 +1393,7 @@ class DiffusionQM9(_Base):
                      eta: Optional[float] = None, spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None,
                      k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False,
                      raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
-                     solver: Optional[str] = None, lower_order_final: Optional[bool] = None):
+                     solver: Optional[str] = None, lower_order_final: Optional[bool] = None, _chain=None):
         """Transitions k_lo .. k_hi-1 of `sample_from_latent`'s partial chain on a given z [B,N,D] (the state at path position k_lo);
         returns the state at position k_hi (default: the end, z_0 before the decode), as `path_steps` does for a full path.  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.  `raw_noises`: k_hi - k_lo injected
@@ -1331,20 +1424,27 @@ class DiffusionQM9(_Base):
             rx = torch.stack([r[0].to(st.dev, torch.float32) for r in raw_noises]).contiguous()
             rh = torch.stack([r[1].to(st.dev, torch.float32) for r in raw_noises]).contiguous()
             seed, base = 0, 0
-        if gd is not None:
-            self._guided_path(st.h, st.topo, z, st.ctx, self._guide_device(gd, node_mask, st.dev), k_lo, k_hi, rx, rh, nb, seed, base,
-                              st.stream)
-            return z
-        _lib.check(_lib.load().hd_sample_path(st.h, st.topo.ptr, z.data_ptr(), _ptr(st.ctx), -1, k_lo, k_hi, _ptr(rx), _ptr(rh), nb,
-                                              seed, base, int(self.use_graph), st.stream), "hd_sample_path")
-        return z
+        if _chain is not None:           # `sample_from_latent` records: (frame table, code of `record`) -> (z, chain)
+            chain = self._chain_open(st.h, st.topo, st.tabs, _chain[0], _chain[1], B, N, st.dev)
+        try:
+            if gd is not None:
+                self._guided_path(st.h, st.topo, z, st.ctx, self._guide_device(gd, node_mask, st.dev), k_lo, k_hi, rx, rh, nb, seed,
+                                  base, st.stream)
+            else:
+                _lib.check(_lib.load().hd_sample_path(st.h, st.topo.ptr, z.data_ptr(), _ptr(st.ctx), -1, k_lo, k_hi, _ptr(rx),
+                                                      _ptr(rh), nb, seed, base, int(self.use_graph), st.stream), "hd_sample_path")
+        finally:
+            if _chain is not None:
+                self._chain_close(st.topo)
+        return z if _chain is None else (z, chain)
 
     @torch.no_grad()
     def sample_from_latent(self, z, node_mask, edge_mask=None, context=None, *, t_start: Optional[int] = None,
                            steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
                            timesteps: Optional[Sequence[int]] = None, sample_id_base: int = 0, fix_noise: bool = False,
                            raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
-                           solver: Optional[str] = None, lower_order_final: Optional[bool] = None):
+                           solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
+                           keep_frames: Optional[int] = None, record: Optional[str] = None):
         """(x, h) from a state z [B,N,D] at the grid index `t_start` (default T; normalised units - what `diffuse` and `encode`
         return): the partial reverse chain on `paths.partial_path(T, t_start, steps, spacing, timesteps)` (default: every grid point
         below t_start) inside the library's loop (hd_sample_path), then the final decode of `sample_from_masks`.  `eta` defaults to
@@ -1352,9 +1452,15 @@ class DiffusionQM9(_Base):
         steps and T + 1 for the decode at (self.seed, sample_id_base + row) - plain sampling's layout, so t_start = T on the identity
         path is `sample_from_masks(z_init=z)` bit for bit; `raw_noises` instead injects K + 1 pairs (the K transitions, the decode).
         `t_start` sets how far variations drift from the lead; which t_start, K and eta are chemically useful is for the user to
-        validate on a trained checkpoint.  solver / lower_order_final: as in `sample_from_masks` ("dpm2m": second order, eta = 0)."""
+        validate on a trained checkpoint.  solver / lower_order_final: as in `sample_from_masks` ("dpm2m": second order, eta = 0).
+        keep_frames / record: as in `sample_from_masks` - a third tensor chain [keep_frames, B, N, D] of the partial chain."""
         _, path, _ = self._latent_path(t_start, steps, eta, spacing, timesteps, solver, lower_order_final)
         K = len(path) - 1
+        what = self._chain_check(keep_frames, record, "sample_from_latent", needs_noise=raw_noises is None)
+        cf = None
+        if what is not None:
+            from . import paths
+            cf = paths.chain_frames(K, keep_frames, path)
         if raw_noises is not None and len(raw_noises) != K + 1:
             raise ValueError(f"raw_noises must hold {K} + 1 (randn_x, randn_h) pairs: the transitions, then the decode")
         from . import guidance
@@ -1363,7 +1469,10 @@ class DiffusionQM9(_Base):
         z0 = self.latent_steps(z, node_mask, edge_mask, context, t_start=t_start, steps=steps, eta=eta, spacing=spacing,
                                timesteps=timesteps, sample_id_base=sample_id_base, fix_noise=fix_noise,
                                raw_noises=None if raw_noises is None else raw_noises[:K], guidance_scale=guidance_scale, guidance_context=guidance_context, guidance_rescale=guidance_rescale,
-                               solver=solver, lower_order_final=lower_order_final)
+                               solver=solver, lower_order_final=lower_order_final, _chain=None if cf is None else (cf, what))
+        chain = None
+        if cf is not None:
+            z0, chain = z0
         B, N = z0.shape[0], z0.shape[1]
         dev = z0.device
         node_mask = node_mask.to(dev)
@@ -1375,8 +1484,14 @@ class DiffusionQM9(_Base):
         eps = self._decode_eps(topo, z0, ctx, None if gd is None else self._guide_device(gd, node_mask, dev))
         coef3 = self._schedule(rows=B)["decode"].numpy()
         if raw_noises is not None:
-            return self._final_decode(z0, eps, node_mask, edge_mask, coef3, fix_noise, raw_noises[K])
-        return self._final_decode(z0, eps, node_mask, edge_mask, coef3, fix_noise, None, philox=(int(sample_id_base), self.T + 1))
+            x, hfeat = self._final_decode(z0, eps, node_mask, edge_mask, coef3, fix_noise, raw_noises[K])
+        else:
+            x, hfeat = self._final_decode(z0, eps, node_mask, edge_mask, coef3, fix_noise, None,
+                                          philox=(int(sample_id_base), self.T + 1))
+        if chain is not None:
+            chain[0] = torch.cat([x, hfeat], dim=2)
+            return x, hfeat, chain
+        return x, hfeat
 
     @torch.no_grad()
     def slerp(self, z_a, z_b, lambdas, node_mask):
@@ -1419,14 +1534,15 @@ class DiffusionQM9(_Base):
         v of input i runs under the sample id sample_id_base + i * n_variants + v, so it does not depend on the batch it ran in.
         guidance_scale (a float, or one scale per result, input-major) / guidance_rescale: classifier-free guidance of the reverse
         chain as in `sample_from_masks`, under the model's `null_context`.
+        keep_frames / record: every result also holds 'chain_x' / 'chain_h' / 'chain_t' of its partial chain, as in `sample`.
         Mechanism only: how far which t_start drifts, and whether the analogues are chemically useful, is for the user to validate."""
         from . import scoring
         device = torch.device(device)
         extra = set(few) - {"steps", "eta", "spacing", "timesteps", "guidance_scale", "guidance_context", "guidance_rescale", "solver",
-                            "lower_order_final"}
+                            "lower_order_final", "keep_frames", "record"}
         if extra:
             raise ValueError(f"vary: unsupported keyword(s) {sorted(extra)} (steps, eta, spacing, timesteps, guidance_scale, "
-                             "guidance_context, guidance_rescale, solver, lower_order_final)")
+                             "guidance_context, guidance_rescale, solver, lower_order_final, keep_frames, record)")
         from . import guidance
         gscale, gctx = few.pop("guidance_scale", None), few.pop("guidance_context", None)
         few["guidance_rescale"] = few.get("guidance_rescale", None)
@@ -1435,6 +1551,9 @@ class DiffusionQM9(_Base):
         gd_all = guidance.resolve(self, gscale, None, few["guidance_rescale"], None, None, "vary")
         self._latent_path(t_start, few.get("steps"), few.get("eta"), few.get("spacing"), few.get("timesteps"), few.get("solver"),
                           few.get("lower_order_final"))                                                            # argument errors first
+        chain_t = None
+        if self._chain_check(few.get("keep_frames"), few.get("record"), "vary") is not None:
+            chain_t = self._chain_times(t_start=t_start, **few)
         for name, v in (("n_variants", n_variants), ("batch_size", batch_size)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
                 raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
@@ -1456,14 +1575,18 @@ class DiffusionQM9(_Base):
             base = int(sample_id_base) + lo
             z = self.diffuse(x.to(device), h.to(device), nmd, t_start, sample_id_base=base)
             gs = None if gd_all is None else (float(gd_all.w[0]) if gd_all.rows == 1 else gd_all.w[lo:lo + nm.shape[0]])
-            xv, hv = self.sample_from_latent(z, nmd, None, ctxd, t_start=t_start, sample_id_base=base, guidance_scale=gs, **few)
-            xv, hv = xv.cpu(), hv.cpu()
+            got = self.sample_from_latent(z, nmd, None, ctxd, t_start=t_start, sample_id_base=base, guidance_scale=gs, **few)
+            xv, hv = got[0].cpu(), got[1].cpu()
+            part = []
             for i in range(nm.shape[0]):
                 n = int(nm[i].sum())
                 res = {'x': xv[i, :n].clone(), 'h': hv[i, :n].clone()}
                 if ctx is not None:
                     res['context'] = ctx[i, :n].clone()
-                out.append(res)
+                part.append(res)
+            if chain_t is not None:
+                self._chain_into(part, got[2], [int(nm[i].sum()) for i in range(nm.shape[0])], chain_t)
+            out.extend(part)
         return out
 
     @torch.no_grad()
@@ -1523,7 +1646,7 @@ class DiffusionQM9(_Base):
         return tabs
 
     def _inpaint_setup(self, node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, path_args=(None,) * 4,
-                       guide_args=None):
+                       guide_args=None, force_path: bool = False):
         """Argument checks of the inpainting entry points (ValueError / NotImplementedError before anything is queued), then the
         device-side inputs of hd_sample_loop_inpaint."""
         if node_mask.dim() != 3 or node_mask.shape[2] != 1:
@@ -1561,6 +1684,9 @@ class DiffusionQM9(_Base):
             gd = guidance.resolve(self, *guide_args, B, N, "inpainting")
             if gd is not None and pe is None:        # a guided chain always runs in the path loop: the identity path
                 pe = (paths.build_path(self.T), 1.0)
+        if force_path and pe is None:                # so does a recorded one
+            from . import paths
+            pe = (paths.build_path(self.T), 1.0)
         if dev.type != "cuda":
             raise _lib.HierDiffHipError("sampling runs only on an MI355X (no CPU fallback)")
         h = self._lib_handle()
@@ -1613,7 +1739,7 @@ class DiffusionQM9(_Base):
                        context=None, resamplings: int = 1, sample_id_base: int = 0, edge_mask: Optional[torch.Tensor] = None, *,
                        steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
                        timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
-                       solver: Optional[str] = None):
+                       solver: Optional[str] = None, keep_frames: Optional[int] = None, record: Optional[str] = None):
         """(x, h) on the device for molecules whose `fixed_mask` [B,N,1] nodes are known: `x_known` [B,N,3] / `h_known` [B,N,F] in
         data units (what `sample` returns; rows outside `fixed_mask` are ignored, the frame of the positions is free).  The free
         nodes are sampled around them by the replacement method, `resamplings` network calls per step (RePaint for > 1), inside
@@ -1623,40 +1749,62 @@ class DiffusionQM9(_Base):
         masks, the weights and its known values only.  steps / spacing / timesteps: few-step sampling as in `sample_from_masks`
         (hd_sample_path_inpaint), ancestral steps only - eta < 1 raises ValueError.  guidance_scale / guidance_context /
         guidance_rescale: classifier-free guidance as in `sample_from_masks` (every round's network call is guided).
-        solver="dpm2m" (or the model's `sample_solver`) raises ValueError like eta < 1."""
-        self._resolve_path(steps, eta, spacing, timesteps, inpaint=True, solver=solver)      # the solver's ValueError before any shape check
+        solver="dpm2m" (or the model's `sample_solver`) raises ValueError like eta < 1.  keep_frames / record: as in
+        `sample_from_masks` - a third tensor chain [keep_frames, B, N, D]; a frame is the state behind its transition's last round
+        (known rows replaced), or that round's data prediction, and frame 0 the returned (x, h)."""
+        pe0 = self._resolve_path(steps, eta, spacing, timesteps, inpaint=True, solver=solver)   # the solver's ValueError before any shape check
+        what = self._chain_check(keep_frames, record, "sample_inpaint")
+        cf = None
+        if what is not None:
+            from . import paths
+            path0 = paths.build_path(self.T) if pe0 is None else pe0[0]
+            cf = paths.chain_frames(len(path0) - 1, keep_frames, path0)
         st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask,
-                                 (steps, eta, spacing, timesteps, solver), (guidance_scale, guidance_context, guidance_rescale))
+                                 (steps, eta, spacing, timesteps, solver), (guidance_scale, guidance_context, guidance_rescale),
+                                 force_path=cf is not None)
         lib, T, B, N = _lib.load(), self.T, st.B, st.N
         n_loop = T if st.K is None else st.K
         z = torch.empty((B, N, self.n_dims + self.in_node_nf), device=st.dev, dtype=torch.float32)
         _lib.check(lib.hd_noise(st.h, st.topo.ptr, None, None, B, self.seed, sample_id_base, 0, 0, z.data_ptr(), st.stream),
                    "hd_noise")
-        if self.debug_checks:              # the loop's invariant after every step (host-synchronising, like the reference's asserts)
-            for s in reversed(range(n_loop)):
-                self._inpaint_run(st, z, s + 1, s, sample_id_base)
-                self._check_mean_zero(z[:, :, :self.n_dims], node_mask)
-        else:
-            self._inpaint_run(st, z, n_loop, 0, sample_id_base)
+        chain = None if cf is None else self._chain_open(st.h, st.topo, st.tabs, cf, what, B, N, st.dev)
+        try:
+            if self.debug_checks:          # the loop's invariant after every step (host-synchronising, like the reference's asserts)
+                for s in reversed(range(n_loop)):
+                    self._inpaint_run(st, z, s + 1, s, sample_id_base)
+                    self._check_mean_zero(z[:, :, :self.n_dims], node_mask)
+            else:
+                self._inpaint_run(st, z, n_loop, 0, sample_id_base)
+        finally:
+            if cf is not None:
+                self._chain_close(st.topo)
         eps = self._decode_eps(st.topo, z, st.ctx, st.g)
         x, hfeat = self._final_decode(z, eps, node_mask, edge_mask, st.tabs["decode"].numpy(), False, None,
                                       philox=(sample_id_base, T + 1))
         x, hfeat = x.contiguous(), hfeat.contiguous()
         _lib.check(lib.hd_inpaint_decode_fix(st.h, st.topo.ptr, st.fm_u8.data_ptr(), st.xk.data_ptr(), st.hk.data_ptr(),
                                              x.data_ptr(), hfeat.data_ptr(), st.stream), "hd_inpaint_decode_fix")
+        if chain is not None:
+            chain[0] = torch.cat([x, hfeat], dim=2)
+            return x, hfeat, chain
         return x, hfeat
 
     @torch.no_grad()
     def sample_grow(self, known: Sequence[Dict[str, torch.Tensor]], sizes, device, context=None, resamplings: int = 1,
                     sample_id_base: int = 0, *, steps: Optional[int] = None, eta: Optional[float] = None,
                     spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
-                    solver: Optional[str] = None):
+                    solver: Optional[str] = None, keep_frames: Optional[int] = None, record: Optional[str] = None):
         """List-level form of `sample_inpaint` in `sample`'s result format: `known[i]` = {'x': [k_i,3], 'h': [k_i,F]} are the fragments
         molecule i keeps (its first k_i rows in the result; k_i = 0 allowed), `sizes[i]` >= k_i its total number of fragments (one
         integer: that many for every molecule).  `context`: as in `sample`.  Returns [{'x': [n_i,3], 'h': [n_i,F] (, 'context')}] on
-        the CPU.  steps / eta / spacing / timesteps: as in `sample_inpaint`."""
+        the CPU.  steps / eta / spacing / timesteps: as in `sample_inpaint`.  keep_frames / record: every dict also holds 'chain_x'
+        [keep, n_i, 3], 'chain_h' [keep, n_i, F] and 'chain_t' [keep], as in `sample`."""
         device = torch.device(device)
         self._resolve_path(steps, eta, spacing, timesteps, inpaint=True, solver=solver)       # argument errors first
+        chain_t = None
+        if self._chain_check(keep_frames, record, "sample_grow") is not None:
+            chain_t = self._chain_times(keep_frames, inpaint=True, steps=steps, eta=eta, spacing=spacing, timesteps=timesteps,
+                                        solver=solver)
         from . import guidance
         guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, None, None, "sample_grow")
         num = len(known)
@@ -1687,37 +1835,48 @@ class DiffusionQM9(_Base):
             ctx = torch.zeros([num, n_max, 1]) + torch.as_tensor(context, dtype=torch.float32).cpu()
             if ctx.shape != (num, n_max, 1):
                 raise ValueError(f"context of shape {tuple(torch.as_tensor(context).shape)} does not broadcast to [{num}, {n_max}, 1]")
-        x, h = self.sample_inpaint(node_mask.to(device), fixed_mask.to(device), x_known.to(device), h_known.to(device),
-                                   context=None if ctx is None else ctx.to(device), resamplings=resamplings,
-                                   sample_id_base=sample_id_base, steps=steps, eta=eta, spacing=spacing, timesteps=timesteps,
-                                   guidance_scale=guidance_scale,
-                                   guidance_context=None if guidance_context is None else guidance_context.to(device),
-                                   guidance_rescale=guidance_rescale, solver=solver)
-        x, h = x.cpu(), h.cpu()
+        got = self.sample_inpaint(node_mask.to(device), fixed_mask.to(device), x_known.to(device), h_known.to(device),
+                                  context=None if ctx is None else ctx.to(device), resamplings=resamplings,
+                                  sample_id_base=sample_id_base, steps=steps, eta=eta, spacing=spacing, timesteps=timesteps,
+                                  guidance_scale=guidance_scale,
+                                  guidance_context=None if guidance_context is None else guidance_context.to(device),
+                                  guidance_rescale=guidance_rescale, solver=solver,
+                                  **({} if chain_t is None else {"keep_frames": keep_frames, "record": record}))
+        x, h = got[0].cpu(), got[1].cpu()
         out = [{'x': x[i, :sizes[i]].clone(), 'h': h[i, :sizes[i]].clone()} for i in range(num)]
         if ctx is not None:
             for i in range(num):
                 out[i]['context'] = ctx[i, :sizes[i]].clone()
+        if chain_t is not None:
+            self._chain_into(out, got[2], sizes, chain_t)
         return out
 
     @torch.no_grad()
     def sample(self, num_samples, device, context=None, pocket_cond=None, sample_id_base: int = 0, *,
                steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
                timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
-               solver: Optional[str] = None, lower_order_final: Optional[bool] = None):
+               solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
+               keep_frames: Optional[int] = None, record: Optional[str] = None):
         """diffusion_qm9.py:347-395: list of {'x': [n_i,3], 'h': [n_i,8], ('context': [n_i,1])} on the CPU.
         steps / eta / spacing / timesteps: few-step sampling, see `sample_from_masks`; guidance_scale (a float or a
         [num_samples] tensor) / guidance_context ([num_samples, n_max, C]) / guidance_rescale: classifier-free guidance, ibid.;
-        solver / lower_order_final: "dpm2m" = second-order multistep sampling, ibid."""
+        solver / lower_order_final: "dpm2m" = second-order multistep sampling, ibid.
+        keep_frames / record ("z", the default, or "x0"): the trajectory, ibid. - every dict also holds 'chain_x' [keep, n_i, 3],
+        'chain_h' [keep, n_i, F] (CPU, data units, the reference's frame order: frame 0 is the result itself) and 'chain_t' [keep],
+        the grid index every frame's state had arrived at."""
         device = torch.device(device)
         self._resolve_path(steps, eta, spacing, timesteps, solver=solver, lower_order_final=lower_order_final)     # argument errors before anything is drawn
+        if self._chain_check(keep_frames, record, "sample", pocket_cond) is not None:
+            self._chain_times(keep_frames, steps=steps, eta=eta, spacing=spacing, timesteps=timesteps, solver=solver,
+                              lower_order_final=lower_order_final)
         from . import guidance
         gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, int(num_samples), None, "sample", pocket_cond)
         if gd is not None and context is None:
             raise ValueError("context required")
         few = {k: v for k, v in dict(steps=steps, eta=eta, spacing=spacing, timesteps=timesteps, guidance_scale=guidance_scale,
                                      guidance_context=guidance_context, guidance_rescale=guidance_rescale, solver=solver,
-                                     lower_order_final=lower_order_final).items() if v is not None}
+                                     lower_order_final=lower_order_final, keep_frames=keep_frames, record=record).items()
+               if v is not None}
         sample_n = self.nodes_dist.sample(num_samples)
         pocket = None
         if pocket_cond is not None:
@@ -1754,14 +1913,18 @@ class DiffusionQM9(_Base):
                 raise ValueError("merged batches take one global context value per batch (context_range entries)")
             context = (torch.zeros([num_samples, n_max, 1]) + torch.stack(cols).reshape(num_samples, 1, 1)).to(device)
         node_mask = node_mask.to(device)
-        x, h = self.sample_from_masks(node_mask, None, context, sample_id_base=sample_id_base, pocket=pocket, **(few or {}))
-        x, h = x.cpu(), h.cpu()
+        got = self.sample_from_masks(node_mask, None, context, sample_id_base=sample_id_base, pocket=pocket, **(few or {}))
+        x, h = got[0].cpu(), got[1].cpu()
         xs = [x[i, :sample_n[i]].clone() for i in range(num_samples)]
         hs = [h[i, :sample_n[i]].clone() for i in range(num_samples)]
         if context is not None:
             ctx = context.cpu()
-            return [{'x': xs[i], 'h': hs[i], 'context': ctx[i, :sample_n[i]].clone()} for i in range(num_samples)]
-        return [{'x': xs[i], 'h': hs[i]} for i in range(num_samples)]
+            out = [{'x': xs[i], 'h': hs[i], 'context': ctx[i, :sample_n[i]].clone()} for i in range(num_samples)]
+        else:
+            out = [{'x': xs[i], 'h': hs[i]} for i in range(num_samples)]
+        if len(got) == 3:                            # a recording call (`sample`: keep_frames)
+            self._chain_into(out, got[2], sample_n, self._chain_times(**few))
+        return out
 
     def sample_batches(self, batch_size, num_batches, device, context_range=None, protein_data_all=None,
                        sample_id_base: int = 0, *, steps: Optional[int] = None, eta: Optional[float] = None,
@@ -1870,3 +2033,22 @@ class EnVariationalDiffusion(DiffusionQM9):
             nm = node_mask.to(torch.float32)
             x = x - (x.sum(1, keepdim=True) / nm.sum(1, keepdim=True)) * nm
         return x, h
+
+    @torch.no_grad()
+    def sample_chain(self, n_samples, n_nodes, node_mask, edge_mask, context, keep_frames=None, *,
+                     steps=None, eta=None, spacing=None, timesteps=None, guidance_scale=None, guidance_context=None,
+                     guidance_rescale=None, solver=None, lower_order_final=None, record=None):
+        """en_diffusion.py:669-710: the reverse chain of `sample` with `keep_frames` of its states kept (None: all of them - T on
+        the full chain, the number of transitions of a few-step one).  Returns [n_samples * keep_frames, N, D], frame-major, in data
+        units: frame (s * keep_frames) // T holds z_s (the last state that falls into a frame stays) and frame 0 cat(x, h) of the
+        decode.  The keyword-only extras are those of `sample`, plus record="x0": the data prediction instead of the state.
+        Recorded inside the library's loop (`sample_from_masks`)."""
+        assert node_mask.shape[0] == n_samples and node_mask.shape[1] == n_nodes
+        if keep_frames is None:
+            pe = self._resolve_path(steps, eta, spacing, timesteps, solver=solver, lower_order_final=lower_order_final)
+            keep_frames = self.T if pe is None else len(pe[0]) - 1
+        _, _, chain = self.sample_from_masks(node_mask, edge_mask, context, steps=steps, eta=eta, spacing=spacing, timesteps=timesteps,
+                                             guidance_scale=guidance_scale, guidance_context=guidance_context,
+                                             guidance_rescale=guidance_rescale, solver=solver, lower_order_final=lower_order_final,
+                                             keep_frames=keep_frames, record=record)
+        return chain.reshape(n_samples * chain.shape[0], n_nodes, chain.shape[3])

@@ -258,3 +258,38 @@ def up_tables(gamma: torch.Tensor, path: Sequence[int]) -> Dict[str, object]:
     ab = inversion_coefficients(g[u], g[v])
     coef = torch.cat([ab, torch.zeros_like(ab)], dim=1).to(torch.float32).contiguous()
     return {"from_idx": u.to(torch.int32).contiguous(), "to_idx": v.to(torch.int32).contiguous(), "coef": coef, "K": int(u.numel())}
+
+
+# ----------------------------------------------------------------------------- recording a trajectory (the reference's sample_chain)
+# en_diffusion.py:669-710 keeps `keep` frames of a T-step chain: after the step that arrives at s it writes z_s into
+# chain[(s * keep) // T], later writes overwriting earlier ones, and frame 0 ends up holding the decoded (x, h).
+
+class ChainFrames(NamedTuple):
+    frame_of: List[int]     # [K] frame transition k writes, -1: none
+    frame_t: List[int]      # [keep] fine-grid timestep every frame's state has arrived at
+
+
+def chain_frames(K, keep, path: Optional[Sequence[int]] = None) -> ChainFrames:
+    """Which frame each of the K transitions of a path records.  Transition k arrives at path position p = K - 1 - k (counted from
+    the t = 0 end, as the reference counts s), whose frame is (p * keep) // K; only the LAST transition of a frame keeps its entry,
+    the others get -1 - the reference's last-write-wins with one write per frame.  1 <= keep <= K, so every frame is claimed
+    exactly once; on the identity path (K = T, p = s) this is the reference's formula.  `frame_t[f]` is the grid index the claiming
+    transition arrives at: `path[k + 1]` of the descending `path` (K + 1 entries; None: the identity path K, K - 1, .., 0)."""
+    for name, v in (("steps", K), ("keep_frames", keep)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    K, keep = int(K), int(keep)
+    if K < 1:
+        raise ValueError(f"a path holds at least one transition, got {K}")
+    if not (1 <= keep <= K):
+        raise ValueError(f"keep_frames must be in 1 .. {K} (the chain's transitions), got {keep}")
+    path = list(range(K, -1, -1)) if path is None else [int(v) for v in path]
+    if len(path) != K + 1:
+        raise ValueError(f"path must hold {K} + 1 grid indices, got {len(path)}")
+    last = [-1] * keep
+    for k in range(K):                                   # ascending k: the last writer of a frame stays
+        last[((K - 1 - k) * keep) // K] = k
+    frame_of = [-1] * K
+    for f, k in enumerate(last):
+        frame_of[k] = f
+    return ChainFrames(frame_of, [path[k + 1] for k in last])

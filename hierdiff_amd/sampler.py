@@ -204,7 +204,20 @@ def parse_args(argv=None):
                     help="with --guidance: rescale the combination towards the spread of the conditional prediction (0 .. 1)")
     ap.add_argument("--null-context", type=float, nargs="+", default=None, metavar="V",
                     help="with --guidance: the null context (one value, or one per context column; default 0)")
+    ap.add_argument("--chain", type=int, default=None, metavar="FRAMES",
+                    help="record the trajectory (the reference's sample_chain): every molecule also gets 'chain_x' / 'chain_h' "
+                         "[FRAMES, n, .] and 'chain_t' [FRAMES] - FRAMES <= the number of transitions, frame 0 the result itself; "
+                         "combines with everything --steps combines with (--eta / --spacing / --solver, --guidance, --known / "
+                         "--grow, --vary), not with --score / --interpolate")
+    ap.add_argument("--record", choices=["z", "x0"], default=None,
+                    help="with --chain: keep the states (z, default) or the network's data prediction of the same transitions (x0)")
     args = ap.parse_args(argv)
+    if args.record is not None and args.chain is None:
+        ap.error("--record needs --chain")
+    if args.chain is not None and args.chain < 1:
+        ap.error("--chain must be >= 1")
+    if args.chain is not None and (args.score is not None or args.interpolate is not None):
+        ap.error("--chain does not combine with --score / --interpolate")
     if args.guidance is not None and not args.context:
         ap.error("--guidance needs --context")
     if args.guidance is None and (args.guidance_rescale != 0.0 or args.null_context is not None):
@@ -299,6 +312,7 @@ def main(argv=None) -> int:
             model.null_context = args.null_context[0] if len(args.null_context) == 1 else list(args.null_context)
     if world > 1:
         broadcast_model_weights(model, src=0)
+    chain = {} if args.chain is None else {"keep_frames": args.chain, "record": args.record}
 
     if args.score is not None:
         if world > 1:
@@ -319,7 +333,7 @@ def main(argv=None) -> int:
             raise SystemExit(f"--steps {args.steps} exceeds the {args.t_start} steps below --t-start")
         model.sample_steps = None               # --steps spreads over the t_start steps below the start, not over the whole grid
         write_results(args.out, model.vary(read_known(args.vary), dev, args.t_start, n_variants=args.variants,
-                                           batch_size=max(1, args.batch_size), steps=args.steps))
+                                           batch_size=max(1, args.batch_size), steps=args.steps, **chain))
         return 0
 
     if args.interpolate is not None:
@@ -345,7 +359,7 @@ def main(argv=None) -> int:
             part = known[lo:lo + max(1, args.batch_size)]
             ctx = None if not args.context else args.context[b % len(args.context)]
             grown.extend(model.sample_grow(part, [int(m["x"].shape[0]) + args.grow for m in part], dev, context=ctx,
-                                           resamplings=args.resamplings, sample_id_base=lo))
+                                           resamplings=args.resamplings, sample_id_base=lo, **chain))
         write_results(args.out, grown)
         return 0
 
@@ -359,7 +373,7 @@ def main(argv=None) -> int:
             model.nodes_dist.sample(args.batch_size)
             continue
         ctx = None if not args.context else args.context[b % len(args.context)]
-        results.extend(model.sample(args.batch_size, dev, context=ctx, sample_id_base=b * args.batch_size))
+        results.extend(model.sample(args.batch_size, dev, context=ctx, sample_id_base=b * args.batch_size, **chain))
     if world == 1:
         write_results(args.out, results)
         return 0

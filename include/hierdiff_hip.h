@@ -333,6 +333,33 @@ int hd_set_path_multistep(hd_handle* h, int K, const int* t_idx, const int* s_id
 int hd_multistep_step(hd_handle* h, hd_topology* topo, const float* zt, const float* eps, const float* row5, const float* x_prev,
                       float* x_out, float* zs, void* stream);
 
+/* ---- Recording a trajectory (ABI 12, additive; the reference's sample_chain, en_diffusion.py:669-710): the path loops write
+ * intermediate states into a caller-owned sink chain[frames][B][N][D] (device, fp32) while they run - one more element-wise launch
+ * per transition (k_chain_frame), inside the captured transition when use_graph is set.  Frames are in data units, `unnormalize`
+ * applied as a multiply and then an add (never fused):  x = v nv0,  h = (v nv1 + nb1) mask,  padded rows exactly 0.
+ * hd_set_chain: the tables of the CURRENT path (hd_set_path*; every new path needs its own call, HD_E_STATE from the loops
+ * otherwise): frame_of[K], the frame transition k writes or -1 for none, and - needed for what = 1 only, else NULL -
+ * alpha_sigma[K][2] = {alpha_t, sigma_t} of every transition's departure level.  HD_E_INVALID: K != the path's K, an entry outside
+ * [-1, frames).  HD_E_STATE: no path set for the current schedule.
+ * hd_chain_attach: from now on every path-loop entry point on this topology (hd_sample_path, hd_sample_path_inpaint,
+ * hd_sample_path_guided; every row form, ascending paths included; with and without use_graph) records into `chain`, whose
+ * `frames` must equal hd_set_chain's:
+ *   what = 0   the state behind transition k (behind the last round's replacement when inpainting),
+ *   what = 1   the data prediction x^ = 1 / alpha_t (z_t - sigma_t eps^) of transition k (of its last round), eps^ the - guided -
+ *              network output, taken between the network call and the update.
+ * Whole molecules only (mol_shape < N is HD_E_INVALID while a sink is attached).  Recording changes no sample: z is only read.
+ * hd_chain_detach: stop recording; the unrecorded launches, graphs, keys and build counters are exactly those of a topology
+ * that never recorded.  hd_sample_loop and hd_sample_loop_inpaint never record (run the identity path instead).
+ *   use_graph    the recording transition is ONE more graph per topology next to the plain and the guided one (none evicts another).
+ *                The sink's address is not baked in: it lives in a device word the loop's state kernel sets, so a new sink
+ *                replays the cached graph.  Rebuilt when anything the unrecorded graph is keyed on changes, or what, nv0, nv1, nb1,
+ *                or the tables (every hd_set_chain). */
+int hd_set_chain(hd_handle* h, int K, const int* frame_of, const float* alpha_sigma, int frames);
+int hd_chain_attach(hd_topology* topo, float* chain, int frames, int what, float nv0, float nv1, float nb1);
+int hd_chain_detach(hd_topology* topo);
+/* Number of times the topology's captured recording transition was instantiated (-1: null topology). */
+long long hd_chain_graph_builds(const hd_topology* topo);
+
 /* ---- Scoring (ABI 12, additive; no reference counterpart beyond the one-timestep estimator, compute_loss with t0_always = True,
  * diffusion_qm9.py:530-699): the variational bound of GIVEN molecules with every term of a list evaluated, in the device loop.
  * For normalised data xh [B,N,D] and a term t in 1 .. T (s = t - 1):
