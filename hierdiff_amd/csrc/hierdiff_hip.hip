@@ -62,6 +62,18 @@ struct LayerW {                 // float offsets into hd_handle::dw
 
 struct ProfRec { int fam; hipEvent_t a, b; };
 
+// A path on the schedule's grid: K transitions t_idx[k] -> s_idx[k], the rows they read, and the generations that tie captured
+// graphs to the tables.  set_path_tables is the one writer (the every-step inpainting rows come from hd_set_inpaint_schedule).
+struct PathTables {
+    int path_K = 0, path_form = 0;   // form 0: ancestral rows, 1: linear rows {a, b, c, 0}, 2: multistep rows {a, b, c2, p, q} (5 floats)
+    bool path_up = false;            // the path ascends (hd_set_path_up: t_idx[k] < s_idx[k], linear rows with c == 0)
+    std::vector<int> path_t_h, path_s_h;
+    std::vector<float> path_c2_h;    // form 2: c2 of every row (which transitions read the history)
+    int *d_path_t = nullptr, *d_path_s = nullptr;
+    float *d_path_coef = nullptr, *d_path_coef_ip = nullptr;   // [K][4] each; d_path_coef_ip null when no inpainting rows were given
+    unsigned long long path_sched_gen = 0, path_gen = 0;       // sched_gen the tables were set for (0: not set); bumped by every rewrite
+};
+
 struct hd_handle {
     hd_config cfg;
     int device;
@@ -84,10 +96,9 @@ struct hd_handle {
     long long* d_nan_events;
     // schedule
     int T;
-    std::vector<float> tau_h, coef_h;
+    std::vector<float> tau_h;
     float* d_tau;
-    float* d_coef;
-    // graph-replay state (device words the captured step reads and k_advance moves on)
+    // graph-replay state (device words the captured transition reads and k_path_advance moves on)
     int* d_step;
     uint32_t* d_draw;
     float* d_tcur;
@@ -97,19 +108,14 @@ struct hd_handle {
     hipEvent_t ev_last;         // recorded behind the handle's latest graph replay (any stream): the step / draw / time words
     bool ev_last_set;           // above are shared by every topology of the handle, so replays are serialised on it
     unsigned long long weights_gen, sched_gen;   // bumped when the packed weights / schedule tables are re-allocated
-    // inpainting loop (hd_set_inpaint_schedule / hd_sample_loop_inpaint)
-    float* d_coef_ip;           // [T][4] {alpha_s, sigma_s, alpha_t|s, sigma_t|s}
-    unsigned long long ip_sched_gen, ip_gen;     // sched_gen the table was set for (0: not set); bumped when d_coef_ip / d_ipdraw move
-    uint32_t* d_ipdraw;         // graph replay: the draw words of a step's 3 * resamplings noise streams
+    // The path loop's tables.  `path`: the caller's (hd_set_path / hd_set_path_up / hd_set_path_multistep; hd_sample_path*).
+    // `every`: the identity path of the current schedule, T transitions s + 1 -> s from s = T - 1 down to 0, built by hd_set_schedule
+    // from its rows in reverse order (form 0; path_gen moves with sched_gen); hd_set_inpaint_schedule adds the inpainting rows
+    // {alpha_s, sigma_s, alpha_t|s, sigma_t|s}, reversed too.  hd_sample_loop / hd_sample_loop_inpaint run on it.
+    PathTables path, every;
+    unsigned long long ip_sched_gen, ip_gen;     // sched_gen every's inpainting rows were set for (0: not set); bumped when they / d_ipdraw move
+    uint32_t* d_ipdraw;         // graph replay: the draw words of a transition's 3 * resamplings noise streams
     int ipdraw_cap;
-    // path loop (hd_set_path / hd_sample_path / hd_sample_path_inpaint): K transitions t_idx[k] -> s_idx[k] on the schedule's grid
-    int path_K, path_form;      // form 0: ancestral rows, 1: linear rows {a, b, c, 0}, 2: multistep rows {a, b, c2, p, q} (5 floats)
-    std::vector<int> path_t_h, path_s_h;
-    std::vector<float> path_c2_h;   // form 2: c2 of every row (which transitions read the history)
-    int *d_path_t, *d_path_s;
-    float *d_path_coef, *d_path_coef_ip;         // [K][4] each; d_path_coef_ip null when no inpainting rows were given
-    unsigned long long path_sched_gen, path_gen; // sched_gen the path was set for (0: not set); bumped by every hd_set_path
-    bool path_up;               // the path ascends (hd_set_path_up: t_idx[k] < s_idx[k], linear rows with c == 0)
     // recording (hd_set_chain): which frame of an attached sink every transition of the current path writes, and for the data
     // prediction {alpha_t, sigma_t} of its departure level
     int chain_frames;
@@ -145,31 +151,8 @@ struct hd_handle {
     size_t pool_used;
 };
 
-// Everything a captured diffusion step has baked in: a cached graph is replayed only when all of it is unchanged.
-struct GraphKey {
-    const float *raw_x, *raw_h;
-    int has_ctx, mol_shape, noise_rows, T, s_hi;       // s_hi: injected-noise offsets are relative to the first step
-    uint64_t seed;
-    unsigned long long weights_gen, sched_gen;
-    bool operator==(const GraphKey& o) const {
-        return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape &&
-               noise_rows == o.noise_rows && T == o.T && s_hi == o.s_hi && seed == o.seed && weights_gen == o.weights_gen &&
-               sched_gen == o.sched_gen;
-    }
-};
-
-// The same for a captured step of the inpainting loop.
-struct InpaintKey {
-    int has_ctx, T, resamplings;
-    uint64_t seed;
-    unsigned long long weights_gen, sched_gen, ip_gen;
-    bool operator==(const InpaintKey& o) const {
-        return has_ctx == o.has_ctx && T == o.T && resamplings == o.resamplings && seed == o.seed && weights_gen == o.weights_gen &&
-               sched_gen == o.sched_gen && ip_gen == o.ip_gen;
-    }
-};
-
-// The same for a captured transition of the path loop (plain: resamplings = 0).
+// Everything a captured transition of the path loop has baked in (plain: resamplings = 0): a cached graph is replayed only when
+// all of it is unchanged.  path_gen is the generation of the tables it runs on (the caller's path, or the every-step tables).
 struct PathKey {
     const float *raw_x, *raw_h;
     int has_ctx, mol_shape, noise_rows, k_lo, resamplings;   // k_lo: injected-noise offsets are relative to the first transition
@@ -224,17 +207,19 @@ struct hd_topology {
     float *hbuf, *AB, *AB2, *Tb, *agg, *x0, *xcur, *part, *xpart, *eps;
     float *abmax, *abmax2;                     // fp16x3: [M_pad][2] row maxima of the AB / AB2 buffers
     float *rowinfo;                            // fp16x3, split node chain: [M_pad][2] {max |h_r|, max |[h | agg]_r|} (k_node_split.hpp)
-    // use_graph: every device loop keeps ONE captured step / transition / term here - a slot, the key it was built for and,
+    // use_graph: every device loop keeps ONE captured transition / term here - a slot, the key it was built for and,
     // where the ABI reports it, a count of instantiations - and replays it once per step through the replay scaffold ("sampling
     // maths" below; graph_slots lists the slots).  The captured body works on library-owned copies of the caller's tensors so
     // that the instantiated graph survives across calls (the caller's tensors move); each loop allocates its copies on first use.
-    // hd_sample_loop: z / context
+    // all loops: z / context
     float *zbuf, *ctxbuf;
+    // hd_sample_loop, hd_sample_loop_inpaint: the path loop on the handle's every-step tables, in slots of its own so that it and
+    // the loops on the caller's path do not evict each other (no build counters)
     hipGraphExec_t gexec;
-    GraphKey gkey;
-    // hd_sample_loop_inpaint: the fixed mask / known values
+    PathKey gkey;
     hipGraphExec_t gexec_ip;
-    InpaintKey ikey;
+    PathKey ikey;
+    // the inpainting loops: the fixed mask / known values
     uint8_t* ip_fixed;
     float* ip_known;
     // hd_sample_path / hd_sample_path_inpaint (hd_path_graph_builds)
@@ -366,7 +351,7 @@ extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
     h->dw = nullptr;
     h->dw_floats = 0;
     h->T = 0;
-    h->d_tau = h->d_coef = nullptr;
+    h->d_tau = nullptr;
     h->prof = 0;
     h->prof_stride = 1;
     h->prof_fwd = 0;
@@ -376,9 +361,7 @@ extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
     h->ev_in = h->ev_out = nullptr;
     h->ev_last = nullptr; h->ev_last_set = false;
     h->weights_gen = h->sched_gen = 0;
-    h->d_coef_ip = nullptr; h->ip_sched_gen = 0; h->ip_gen = 0; h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
-    h->path_K = 0; h->path_form = 0; h->d_path_t = h->d_path_s = nullptr; h->d_path_coef = h->d_path_coef_ip = nullptr;
-    h->path_sched_gen = 0; h->path_gen = 0; h->path_up = false;
+    h->ip_sched_gen = 0; h->ip_gen = 0; h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
     h->chain_frames = 0; h->d_chain_frame = nullptr; h->d_chain_as = nullptr; h->chain_path_gen = 0; h->chain_gen = 0;
     h->d_chain_dst = nullptr;
     h->nll_K = 0; h->d_nll_t = nullptr; h->d_nll_coef = nullptr; h->nll_sched_gen = 0; h->nll_gen = 0;
@@ -430,9 +413,11 @@ extern "C" int hd_destroy(hd_handle* h) {
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     hipFree(h->dw); hipFree(h->d_nanflag); hipFree(h->d_nan_events);
-    hipFree(h->d_tau); hipFree(h->d_coef); hipFree(h->d_step); hipFree(h->d_draw); hipFree(h->d_tcur); hipFree(h->d_base);
-    hipFree(h->d_coef_ip); hipFree(h->d_ipdraw);
-    hipFree(h->d_path_t); hipFree(h->d_path_s); hipFree(h->d_path_coef); hipFree(h->d_path_coef_ip);
+    hipFree(h->d_tau); hipFree(h->d_step); hipFree(h->d_draw); hipFree(h->d_tcur); hipFree(h->d_base);
+    hipFree(h->d_ipdraw);
+    for (PathTables* pt : {&h->path, &h->every}) {
+        hipFree(pt->d_path_t); hipFree(pt->d_path_s); hipFree(pt->d_path_coef); hipFree(pt->d_path_coef_ip);
+    }
     hipFree(h->d_chain_frame); hipFree(h->d_chain_as); hipFree(h->d_chain_dst);
     hipFree(h->d_nll_t); hipFree(h->d_nll_coef);
 #ifdef HD_DEBUG_KERNELS
@@ -2634,13 +2619,13 @@ static NoiseSrc make_noise(const float* raw_x, const float* raw_h, int rows, uin
 
 static int step_impl(hd_handle* h, hd_topology* t, const float* zt, const float* eps, const float* coef, int coef_rows,
                      const NoiseSrc& ns, int mol, float* zs, int out_stride, const int* step_ptr,
-                     const uint32_t* draw_ptr, uint32_t draw0, hipStream_t s, const unsigned long long* base_ptr = nullptr,
-                     int form = 0, int raw_step0 = -1) {
+                     const uint32_t* draw_ptr, hipStream_t s, const unsigned long long* base_ptr = nullptr,
+                     int form = 0, int raw_step0 = 0) {
     ProfScope ps(h, s, 2);
     StepArgs a;
     a.raw_step0 = raw_step0;
     a.zt = zt; a.eps = eps; a.coef = coef; a.nm = t->nm_bytes; a.zs = zs; a.noise = ns; a.draw_ptr = draw_ptr;
-    a.step_ptr = step_ptr; a.base_ptr = base_ptr; a.draw0 = draw0; a.coef_rows = coef_rows; a.B = t->B; a.N = t->N; a.D = h->D; a.F = h->F;
+    a.step_ptr = step_ptr; a.base_ptr = base_ptr; a.coef_rows = coef_rows; a.B = t->B; a.N = t->N; a.D = h->D; a.F = h->F;
     a.mol = mol; a.out_stride = out_stride;
     if (form == 0) hipLaunchKernelGGL(k_post_step<0>, dim3(t->B), dim3(256), (size_t)a.mol * a.D * sizeof(float), s, a);
     else hipLaunchKernelGGL(k_post_step<1>, dim3(t->B), dim3(256), (size_t)a.mol * a.D * sizeof(float), s, a);
@@ -2661,7 +2646,7 @@ extern "C" int hd_posterior_step(hd_handle* h, hd_topology* topo, const float* z
     HIP_TRY(hipSetDevice(h->device));
     topo_use(topo, (hipStream_t)stream);
     return step_impl(h, topo, zt, eps, coef, coef_rows, make_noise(raw_x, raw_h, noise_rows, 0, 0, 0, 0), mol, zs, mol,
-                     nullptr, nullptr, 0, (hipStream_t)stream);
+                     nullptr, nullptr, (hipStream_t)stream);
 }
 
 // the multistep form of the step: `coef` device rows [K][5] read at *step_ptr (k_solver.hpp), or the host row by value
@@ -2729,28 +2714,62 @@ extern "C" int hd_noise(hd_handle* h, hd_topology* topo, const float* raw_x, con
     return HD_OK;
 }
 
+// The one writer of path tables - the caller's or the handle's every-step ones: K validated transitions t_idx[k] -> s_idx[k],
+// their rows of `row_width` floats and, for ancestral paths that inpaint, the inpainting rows.
+static int set_path_tables(hd_handle* h, PathTables& pt, int K, const int* t_idx, const int* s_idx, const float* rows, int row_width,
+                           const float* rows_ip, int form, bool up) {
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
+    hipFree(pt.d_path_t); hipFree(pt.d_path_s); hipFree(pt.d_path_coef); hipFree(pt.d_path_coef_ip);
+    pt.d_path_t = pt.d_path_s = nullptr; pt.d_path_coef = pt.d_path_coef_ip = nullptr;
+    pt.path_sched_gen = 0; pt.path_K = 0;
+    pt.path_t_h.assign(t_idx, t_idx + K);
+    pt.path_s_h.assign(s_idx, s_idx + K);
+    if (form == 2) {
+        pt.path_c2_h.resize((size_t)K);
+        for (int k = 0; k < K; ++k) pt.path_c2_h[(size_t)k] = rows[(size_t)row_width * k + 2];
+    }
+    HD_TRY(dev_upload(&pt.d_path_t, pt.path_t_h));
+    HD_TRY(dev_upload(&pt.d_path_s, pt.path_s_h));
+    HD_TRY(dev_upload(&pt.d_path_coef, std::vector<float>(rows, rows + (size_t)row_width * K)));
+    if (rows_ip) HD_TRY(dev_upload(&pt.d_path_coef_ip, std::vector<float>(rows_ip, rows_ip + (size_t)4 * K)));
+    pt.path_K = K; pt.path_form = form; pt.path_up = up;
+    pt.path_sched_gen = h->sched_gen;
+    pt.path_gen++;                             // captured graphs hold the old table addresses
+    return HD_OK;
+}
+
+// rows [T][4] of the schedule in the order of the every-step tables: position k is step s = T - 1 - k
+static std::vector<float> rows_reversed(const float* coef4, int T) {
+    std::vector<float> r((size_t)4 * T);
+    for (int k = 0; k < T; ++k) std::copy(coef4 + (size_t)4 * (T - 1 - k), coef4 + (size_t)4 * (T - k), r.begin() + (size_t)4 * k);
+    return r;
+}
+
 extern "C" int hd_set_schedule(hd_handle* h, int T, const float* tau, const float* coef4) {
     if (!h || !tau || !coef4 || T < 1) return fail(HD_E_INVALID, "hd_set_schedule: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    hipFree(h->d_tau); hipFree(h->d_coef);
-    h->d_tau = h->d_coef = nullptr;
-    h->tau_h.assign(tau, tau + T + 1);
-    h->coef_h.assign(coef4, coef4 + (size_t)4 * T);
-    HD_TRY(dev_upload(&h->d_tau, h->tau_h));
-    HD_TRY(dev_upload(&h->d_coef, h->coef_h));
-    h->T = T;
+    h->T = 0;                                  // not set until everything below is in place
     h->sched_gen++;                            // captured graphs hold the old table addresses
+    // the every-step tables: the identity path T -> T - 1 -> ... -> 0 with the caller's rows (row s of coef4 is the step to s)
+    std::vector<int> t_idx((size_t)T), s_idx((size_t)T);
+    for (int k = 0; k < T; ++k) { t_idx[(size_t)k] = T - k; s_idx[(size_t)k] = T - 1 - k; }
+    HD_TRY(set_path_tables(h, h->every, T, t_idx.data(), s_idx.data(), rows_reversed(coef4, T).data(), 4, nullptr, 0, false));
+    hipFree(h->d_tau);                         // behind set_path_tables' device synchronisation
+    h->d_tau = nullptr;
+    h->tau_h.assign(tau, tau + T + 1);
+    HD_TRY(dev_upload(&h->d_tau, h->tau_h));
+    h->T = T;
     return HD_OK;
 }
 
 // ----------------------------------------------------------------------------- the replay scaffold of the captured loops
 //
-// Every device loop (hd_sample_loop, hd_sample_loop_inpaint, the path loops, hd_nll_terms) has the same two halves.  Plain
-// launches: the host walks the steps and passes position, draw and sample base by value.  use_graph: ONE step is captured into a
-// hipGraph that reads them from the handle's device words, works on library-owned copies of every tensor (the caller's move
-// between calls) and is kept in a slot of the topology until something in its key changes.  A loop's own part is its key, its slot
-// and build counter, its staging copies, its state kernel and the emitter of its body; the order of a replaying call is
+// The two device loops - the path loop (hd_sample_path*, and hd_sample_loop / hd_sample_loop_inpaint, which run it on the handle's
+// every-step tables) and hd_nll_terms - have the same two halves.  Plain launches: the host walks the steps and passes position,
+// draw and sample base by value.  use_graph: ONE transition / term is captured into a hipGraph that reads them from the handle's
+// device words, works on library-owned copies of every tensor (the caller's move between calls) and is kept in a slot of the
+// topology until something in its key changes.  A loop's own part is its key, its slot and build counter, its staging copies,
+// its state kernel and the emitter of its body; the order of a replaying call is
 //     replay_enter -> (grow / allocate owned buffers) -> replay_evict -> replay_capture -> staging copies, state kernel
 //                  -> replay_run -> copy back -> replay_leave
 // No host synchronisation on the way unless a stale graph or buffer has to go: the caller's stream is ordered against the replay
@@ -2853,74 +2872,6 @@ static int replay_leave(hd_handle* h, hipStream_t s, hipStream_t rs) {
     return HD_OK;
 }
 
-// ----------------------------------------------------------------------------- the every-step loop
-
-extern "C" int hd_sample_loop(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
-                              int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
-                              uint64_t seed, uint64_t sample_id_base, int use_graph, void* stream) {
-    HD_TRY(check_ready(h, topo, "hd_sample_loop"));
-    if (h->T < 1) return fail(HD_E_STATE, "hd_sample_loop: schedule not set (hd_set_schedule)");
-    if (!z) return fail(HD_E_INVALID, "hd_sample_loop: null z");
-    if (s_hi > h->T || s_lo < 0 || s_lo > s_hi) return fail(HD_E_INVALID, "hd_sample_loop: need 0 <= s_lo <= s_hi <= T");
-    if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, "hd_sample_loop: raw_x and raw_h go together");
-    if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_loop: noise_rows must be 1 or B");
-    if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, "hd_sample_loop: context required");
-    if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_loop: needs a time-conditioned model");
-    const int mol = (mol_shape < 0 || mol_shape > topo->N) ? topo->N : mol_shape;
-    if ((size_t)mol * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_sample_loop: N * D floats exceed one workgroup's LDS");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int nsteps = s_hi - s_lo;
-    topo_use(topo, s);
-    if (nsteps == 0) return HD_OK;
-    const int T = h->T;
-    const uint32_t draw0 = (uint32_t)(T - (s_hi - 1));       // draw index of the first step (draw 0 = z_T)
-    const int share = (noise_rows == 1) ? 1 : 0;
-    auto step = [&](const LoopIO& io) -> int {
-        HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx, mol_shape < 0 ? -1 : mol, topo->eps, io.s));
-        NoiseSrc ns = make_noise(raw_x ? raw_x + io.ro * 3 : nullptr, raw_h ? raw_h + io.ro * h->F : nullptr, noise_rows, seed,
-                                 io.base, io.draw, share);
-        return step_impl(h, topo, io.z, topo->eps, h->d_coef + (size_t)io.row * 4, 1, ns, mol, io.z, topo->N, io.step, io.draw_w,
-                         io.step ? draw0 : 0, io.s, io.base_w);
-    };
-    if (!use_graph) {
-        LoopIO io{};
-        io.z = z; io.ctx = context; io.base = sample_id_base; io.s = s;
-        for (int k = 0; k < nsteps; ++k) {
-            io.row = s_hi - 1 - k; io.tcur = h->d_tau + io.row + 1;
-            io.ro = (size_t)k * noise_rows * mol; io.draw = draw0 + (uint32_t)k;
-            HD_TRY(step(io));
-        }
-        return HD_OK;
-    }
-    // Rebuilt only when something in GraphKey changes.
-    const size_t zbytes = (size_t)topo->B * topo->N * h->D * sizeof(float);
-    const size_t cbytes = (size_t)topo->B * topo->N * h->cfg.context_node_nf * sizeof(float);
-    hipStream_t rs;
-    HD_TRY(replay_enter(h, s, &rs));
-    GraphKey key;
-    key.raw_x = raw_x; key.raw_h = raw_h; key.has_ctx = context ? 1 : 0; key.mol_shape = mol_shape < 0 ? -1 : mol;
-    key.noise_rows = noise_rows; key.T = T; key.s_hi = raw_x ? s_hi : 0; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
-    HD_TRY(replay_evict(h, rs, &topo->gexec, topo->gkey, key));
-    if (!topo->gexec) {
-        LoopIO io = loop_io_captured(h, h->d_draw, rs);
-        io.z = topo->zbuf; io.ctx = context ? topo->ctxbuf : nullptr; io.draw = draw0;
-        HD_TRY(replay_capture(h, rs, &topo->gexec, [&]() -> int {
-            HD_TRY(step(io));
-            hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, rs, h->d_step, h->d_draw, h->d_tcur, h->d_tau);
-            return HD_OK;
-        }));
-        topo->gkey = key;
-    }
-    HIP_TRY(hipMemcpyAsync(topo->zbuf, z, zbytes, hipMemcpyDeviceToDevice, rs));
-    if (context) HIP_TRY(hipMemcpyAsync(topo->ctxbuf, context, cbytes, hipMemcpyDeviceToDevice, rs));
-    hipLaunchKernelGGL(k_loop_state, dim3(1), dim3(1), 0, rs, h->d_step, h->d_draw, h->d_tcur, h->d_base, h->d_tau,
-                       s_hi - 1, draw0, (unsigned long long)sample_id_base);
-    HD_TRY(replay_run(topo->gexec, nsteps, rs));
-    HIP_TRY(hipMemcpyAsync(z, topo->zbuf, zbytes, hipMemcpyDeviceToDevice, rs));
-    return replay_leave(h, s, rs);
-}
-
 // ----------------------------------------------------------------------------- fragment-constrained sampling (inpainting)
 
 extern "C" int hd_set_inpaint_schedule(hd_handle* h, int T, const float* coef4) {
@@ -2929,11 +2880,10 @@ extern "C" int hd_set_inpaint_schedule(hd_handle* h, int T, const float* coef4) 
     if (T != h->T) return fail(HD_E_INVALID, "hd_set_inpaint_schedule: T differs from the schedule's (hd_set_schedule)");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());
-    hipFree(h->d_coef_ip);
-    h->d_coef_ip = nullptr;
+    hipFree(h->every.d_path_coef_ip);
+    h->every.d_path_coef_ip = nullptr;
     h->ip_sched_gen = 0;
-    const std::vector<float> rows(coef4, coef4 + (size_t)4 * T);
-    HD_TRY(dev_upload(&h->d_coef_ip, rows));
+    HD_TRY(dev_upload(&h->every.d_path_coef_ip, rows_reversed(coef4, T)));
     h->ip_sched_gen = h->sched_gen;
     h->ip_gen++;                               // captured graphs hold the old table address
     return HD_OK;
@@ -2941,10 +2891,10 @@ extern "C" int hd_set_inpaint_schedule(hd_handle* h, int T, const float* coef4) 
 
 static int inpaint_launch(hd_handle* h, hd_topology* t, bool jump, float* z, const uint8_t* fixed, const float* known, uint64_t seed,
                           uint64_t base, uint32_t draw, int step, const uint32_t* draw_ptr, const int* step_ptr,
-                          const unsigned long long* base_ptr, hipStream_t s, const float* coef = nullptr) {
+                          const unsigned long long* base_ptr, hipStream_t s, const float* coef) {
     ProfScope ps(h, s, 2);
     InpaintArgs a;
-    a.z = z; a.nm = t->nm_bytes; a.fixed = fixed; a.known = known; a.coef = coef ? coef : h->d_coef_ip; a.seed = seed; a.sample_base = base;
+    a.z = z; a.nm = t->nm_bytes; a.fixed = fixed; a.known = known; a.coef = coef; a.seed = seed; a.sample_base = base;
     a.draw = draw; a.step = step; a.draw_ptr = draw_ptr; a.step_ptr = step_ptr; a.base_ptr = base_ptr;
     a.B = t->B; a.N = t->N; a.D = h->D;
     const size_t lds = (size_t)t->N * h->D * sizeof(float);
@@ -2977,9 +2927,9 @@ static const char* const kIpRowsMsg = ": noise_rows must be B";
 // ... and on the path, before them
 static int inpaint_path_check(const char* who, const hd_handle* h, const char* form_msg) {
     const std::string w(who);
-    if (h->path_up) return fail(HD_E_INVALID, w + ": the path ascends (hd_set_path_up): inversion fixes no fragments");
-    if (h->path_form != 0) return fail(HD_E_INVALID, w + form_msg);
-    if (!h->d_path_coef_ip) return fail(HD_E_STATE, w + ": the path was set without inpainting rows (hd_set_path)");
+    if (h->path.path_up) return fail(HD_E_INVALID, w + ": the path ascends (hd_set_path_up): inversion fixes no fragments");
+    if (h->path.path_form != 0) return fail(HD_E_INVALID, w + form_msg);
+    if (!h->path.d_path_coef_ip) return fail(HD_E_STATE, w + ": the path was set without inpainting rows (hd_set_path)");
     return HD_OK;
 }
 
@@ -3005,7 +2955,7 @@ static int inpaint_buffers(const hd_handle* h, hd_topology* t) {
 // Round j of R behind its posterior step: put the known rows back at the arrival level and - except in the last round - jump back
 // to the departure level.  Noise stream 3 * j + m of `stride` draws: a host draw, or the word io.draw_w[3 * j + m].
 static int inpaint_round(hd_handle* h, hd_topology* t, const LoopIO& io, int j, int R, uint32_t stride, uint64_t seed,
-                         const float* coef_ip = nullptr) {
+                         const float* coef_ip) {
     for (int m = 1; m <= (j < R - 1 ? 2 : 1); ++m)
         HD_TRY(inpaint_launch(h, t, m == 2, io.z, m == 1 ? io.fixed : nullptr, m == 1 ? io.known : nullptr, seed, io.base,
                               io.step ? 0u : stride * (uint32_t)(3 * j + m) + io.draw, io.row, io.step ? io.draw_w + 3 * j + m : nullptr,
@@ -3013,107 +2963,7 @@ static int inpaint_round(hd_handle* h, hd_topology* t, const LoopIO& io, int j, 
     return HD_OK;
 }
 
-extern "C" int hd_sample_loop_inpaint(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
-                                      int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
-                                      uint64_t seed, uint64_t sample_id_base, int use_graph, const uint8_t* fixed_mask,
-                                      const float* xh_known, int resamplings, void* stream) {
-    const char* who = "hd_sample_loop_inpaint";
-    HD_TRY(check_ready(h, topo, who));
-    if (h->T < 1) return fail(HD_E_STATE, "hd_sample_loop_inpaint: schedule not set (hd_set_schedule)");
-    if (!h->d_coef_ip || h->ip_sched_gen != h->sched_gen)
-        return fail(HD_E_STATE, "hd_sample_loop_inpaint: inpainting schedule not set for the current schedule (hd_set_inpaint_schedule)");
-    if (!z || !fixed_mask || !xh_known) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: null z / fixed_mask / xh_known");
-    if (s_hi > h->T || s_lo < 0 || s_lo > s_hi) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: need 0 <= s_lo <= s_hi <= T");
-    HD_TRY(inpaint_args_check(who, h, topo, raw_x, raw_h, noise_rows, mol_shape, resamplings, context, kIpRawMsg, kIpRowsMsg));
-    const int T = h->T, R = resamplings, nd = 3 * R;
-    const uint32_t stride = (uint32_t)T + 2u;                // draws of one noise stream: 0 .. T + 1
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int nsteps = s_hi - s_lo;
-    topo_use(topo, s);
-    if (nsteps == 0) return HD_OK;
-    const int N = topo->N;
-    const uint32_t draw0 = (uint32_t)(T - (s_hi - 1));
-    auto step = [&](const LoopIO& io) -> int {               // all R rounds of one step
-        for (int j = 0; j < R; ++j) {
-            HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx, -1, topo->eps, io.s));
-            NoiseSrc ns = make_noise(nullptr, nullptr, noise_rows, seed, io.base, io.step ? 0u : stride * (uint32_t)(3 * j) + io.draw, 0);
-            HD_TRY(step_impl(h, topo, io.z, topo->eps, h->d_coef + (size_t)io.row * 4, 1, ns, N, io.z, N, io.step,
-                             io.step ? io.draw_w + 3 * j : nullptr, 0, io.s, io.base_w));
-            HD_TRY(inpaint_round(h, topo, io, j, R, stride, seed));
-        }
-        return HD_OK;
-    };
-    if (!use_graph) {
-        LoopIO io{};
-        io.z = z; io.ctx = context; io.fixed = fixed_mask; io.known = xh_known; io.base = sample_id_base; io.s = s;
-        for (int k = 0; k < nsteps; ++k) {
-            io.row = s_hi - 1 - k; io.tcur = h->d_tau + io.row + 1; io.draw = draw0 + (uint32_t)k;
-            HD_TRY(step(io));
-        }
-        return HD_OK;
-    }
-    // The draws of the 3 * R noise streams live in d_ipdraw; the fixed mask and the known values are library-owned copies too.
-    const size_t BN = (size_t)topo->B * N;
-    const size_t zbytes = BN * h->D * sizeof(float);
-    const size_t cbytes = BN * h->cfg.context_node_nf * sizeof(float);
-    hipStream_t rs;
-    HD_TRY(replay_enter(h, s, &rs));
-    HD_TRY(grow_ipdraw(h, rs, nd));
-    HD_TRY(inpaint_buffers(h, topo));
-    InpaintKey key;
-    key.has_ctx = context ? 1 : 0; key.T = T; key.resamplings = R; key.seed = seed; key.weights_gen = h->weights_gen;
-    key.sched_gen = h->sched_gen; key.ip_gen = h->ip_gen;
-    HD_TRY(replay_evict(h, rs, &topo->gexec_ip, topo->ikey, key));
-    if (!topo->gexec_ip) {
-        LoopIO io = loop_io_captured(h, h->d_ipdraw, rs);
-        io.z = topo->zbuf; io.ctx = context ? topo->ctxbuf : nullptr; io.fixed = topo->ip_fixed; io.known = topo->ip_known;
-        HD_TRY(replay_capture(h, rs, &topo->gexec_ip, [&]() -> int {
-            HD_TRY(step(io));
-            hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, rs, h->d_step, h->d_draw, h->d_tcur, h->d_tau);
-            hipLaunchKernelGGL(k_inpaint_advance, dim3((nd + 255) / 256), dim3(256), 0, rs, h->d_ipdraw, nd);
-            return HD_OK;
-        }));
-        topo->ikey = key;
-    }
-    HIP_TRY(hipMemcpyAsync(topo->zbuf, z, zbytes, hipMemcpyDeviceToDevice, rs));
-    if (context) HIP_TRY(hipMemcpyAsync(topo->ctxbuf, context, cbytes, hipMemcpyDeviceToDevice, rs));
-    HIP_TRY(hipMemcpyAsync(topo->ip_fixed, fixed_mask, BN, hipMemcpyDeviceToDevice, rs));
-    HIP_TRY(hipMemcpyAsync(topo->ip_known, xh_known, zbytes, hipMemcpyDeviceToDevice, rs));
-    hipLaunchKernelGGL(k_loop_state, dim3(1), dim3(1), 0, rs, h->d_step, h->d_draw, h->d_tcur, h->d_base, h->d_tau,
-                       s_hi - 1, draw0, (unsigned long long)sample_id_base);
-    hipLaunchKernelGGL(k_inpaint_state, dim3((nd + 255) / 256), dim3(256), 0, rs, h->d_ipdraw, nd, stride, draw0);
-    HD_TRY(replay_run(topo->gexec_ip, nsteps, rs));
-    HIP_TRY(hipMemcpyAsync(z, topo->zbuf, zbytes, hipMemcpyDeviceToDevice, rs));
-    return replay_leave(h, s, rs);
-}
-
 // ----------------------------------------------------------------------------- few-step sampling: the loop on a path
-
-// The one writer of the path tables: K validated transitions t_idx[k] -> s_idx[k], their rows of `row_width` floats and, for
-// ancestral paths that inpaint, the inpainting rows.
-static int set_path_tables(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* rows, int row_width,
-                           const float* rows_ip, int form, bool up) {
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
-    hipFree(h->d_path_t); hipFree(h->d_path_s); hipFree(h->d_path_coef); hipFree(h->d_path_coef_ip);
-    h->d_path_t = h->d_path_s = nullptr; h->d_path_coef = h->d_path_coef_ip = nullptr;
-    h->path_sched_gen = 0; h->path_K = 0;
-    h->path_t_h.assign(t_idx, t_idx + K);
-    h->path_s_h.assign(s_idx, s_idx + K);
-    if (form == 2) {
-        h->path_c2_h.resize((size_t)K);
-        for (int k = 0; k < K; ++k) h->path_c2_h[(size_t)k] = rows[(size_t)row_width * k + 2];
-    }
-    HD_TRY(dev_upload(&h->d_path_t, h->path_t_h));
-    HD_TRY(dev_upload(&h->d_path_s, h->path_s_h));
-    HD_TRY(dev_upload(&h->d_path_coef, std::vector<float>(rows, rows + (size_t)row_width * K)));
-    if (rows_ip) HD_TRY(dev_upload(&h->d_path_coef_ip, std::vector<float>(rows_ip, rows_ip + (size_t)4 * K)));
-    h->path_K = K; h->path_form = form; h->path_up = up;
-    h->path_sched_gen = h->sched_gen;
-    h->path_gen++;                             // captured graphs hold the old table addresses
-    return HD_OK;
-}
 
 extern "C" int hd_set_path(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* coef4, int form,
                            const float* coef4_inpaint) {
@@ -3127,7 +2977,7 @@ extern "C" int hd_set_path(hd_handle* h, int K, const int* t_idx, const int* s_i
             return fail(HD_E_INVALID, "hd_set_path: need 0 <= s_idx[k] < t_idx[k] <= T");
         if (k > 0 && t_idx[k] != s_idx[k - 1]) return fail(HD_E_INVALID, "hd_set_path: transition k must start where k - 1 arrived");
     }
-    return set_path_tables(h, K, t_idx, s_idx, coef4, 4, coef4_inpaint, form, false);
+    return set_path_tables(h, h->path, K, t_idx, s_idx, coef4, 4, coef4_inpaint, form, false);
 }
 
 // An ascending path into the same tables: transition k leaves from_idx[k] (path_t: network time, as for descending paths) and
@@ -3144,7 +2994,7 @@ extern "C" int hd_set_path_up(hd_handle* h, int K, const int* from_idx, const in
     if (h->T < 1) return fail(HD_E_STATE, "hd_set_path_up: schedule not set (hd_set_schedule)");
     if (K > h->T) return fail(HD_E_INVALID, "hd_set_path_up: more transitions than the schedule has steps");
     if (to_idx[K - 1] > h->T) return fail(HD_E_INVALID, "hd_set_path_up: need 0 <= from_idx[k] < to_idx[k] <= T");
-    return set_path_tables(h, K, from_idx, to_idx, coef4, 4, nullptr, 1, true);
+    return set_path_tables(h, h->path, K, from_idx, to_idx, coef4, 4, nullptr, 1, true);
 }
 
 // A descending path with multistep rows {a, b, c2, p, q} (form 2, k_solver.hpp) into the same tables.
@@ -3159,7 +3009,7 @@ extern "C" int hd_set_path_multistep(hd_handle* h, int K, const int* t_idx, cons
             return fail(HD_E_INVALID, "hd_set_path_multistep: transition k must start where k - 1 arrived");
     }
     if (rows5[2] != 0.f) return fail(HD_E_INVALID, "hd_set_path_multistep: c2 of row 0 must be 0 (the first transition has no history)");
-    return set_path_tables(h, K, t_idx, s_idx, rows5, 5, nullptr, 2, false);
+    return set_path_tables(h, h->path, K, t_idx, s_idx, rows5, 5, nullptr, 2, false);
 }
 
 extern "C" long long hd_path_graph_builds(const hd_topology* topo) { return topo ? topo->path_builds : -1; }
@@ -3168,8 +3018,8 @@ extern "C" long long hd_path_graph_builds(const hd_topology* topo) { return topo
 
 extern "C" int hd_set_chain(hd_handle* h, int K, const int* frame_of, const float* alpha_sigma, int frames) {
     if (!h || !frame_of || K < 1 || frames < 1) return fail(HD_E_INVALID, "hd_set_chain: bad argument");
-    if (h->path_K < 1 || h->path_sched_gen != h->sched_gen) return fail(HD_E_STATE, "hd_set_chain: path not set for the current schedule (hd_set_path)");
-    if (K != h->path_K) return fail(HD_E_INVALID, "hd_set_chain: K differs from the path's (hd_set_path)");
+    if (h->path.path_K < 1 || h->path.path_sched_gen != h->sched_gen) return fail(HD_E_STATE, "hd_set_chain: path not set for the current schedule (hd_set_path)");
+    if (K != h->path.path_K) return fail(HD_E_INVALID, "hd_set_chain: K differs from the path's (hd_set_path)");
     for (int k = 0; k < K; ++k)
         if (frame_of[k] < -1 || frame_of[k] >= frames) return fail(HD_E_INVALID, "hd_set_chain: need -1 <= frame_of[k] < frames");
     HIP_TRY(hipSetDevice(h->device));
@@ -3180,7 +3030,7 @@ extern "C" int hd_set_chain(hd_handle* h, int K, const int* frame_of, const floa
     HD_TRY(dev_upload(&h->d_chain_frame, std::vector<int>(frame_of, frame_of + K)));
     if (alpha_sigma) HD_TRY(dev_upload(&h->d_chain_as, std::vector<float>(alpha_sigma, alpha_sigma + (size_t)2 * K)));
     h->chain_frames = frames;
-    h->chain_path_gen = h->path_gen;
+    h->chain_path_gen = h->path.path_gen;
     h->chain_gen++;                            // captured graphs hold the old table addresses
     return HD_OK;
 }
@@ -3243,24 +3093,37 @@ static int chain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const fl
     return HD_OK;
 }
 
+// What a path loop runs on: the tables, the slot of its captured transition with the key that was built for (a recording transition
+// goes to gexec_chain instead), the count of instantiations to bump (null: not reported), and whether a sink attached to the
+// topology records.
+struct PathRun {
+    const PathTables* pt;
+    hipGraphExec_t* gx;
+    PathKey* key;
+    long long* builds;
+    bool record;
+};
+
 // The path loops: R = 0 is the plain one, R >= 1 the inpainting one with R rounds per transition; gd != NULL guides either.
-// A topology with a sink attached (hd_chain_attach) records: one more launch per transition, behind the update of its last round
-// (the state) or between that round's network call and its update (the data prediction).
+// A topology with a sink attached (hd_chain_attach) records when run.record: one more launch per transition, behind the update of
+// its last round (the state) or between that round's network call and its update (the data prediction).
 static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
                          const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
-                         const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const GuideSrc* gd);
+                         const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const PathRun& run, const GuideSrc* gd);
 
 static int path_loop(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
                      const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
-                     const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const GuideSrc* gd = nullptr) {
-    if (h->path_form != 2 || k_hi == k_lo)
+                     const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const PathRun& run,
+                     const GuideSrc* gd = nullptr) {
+    const PathTables& pt = *run.pt;
+    if (pt.path_form != 2 || k_hi == k_lo)
         return path_loop_run(h, topo, z, context, mol_shape, k_lo, k_hi, raw_x, raw_h, noise_rows, seed, sample_id_base, use_graph,
-                             fixed_mask, xh_known, R, s, gd);
+                             fixed_mask, xh_known, R, s, run, gd);
     // multistep rows: the history x^_{k_lo - 1} is the topology's - a call that starts on a row with c2 != 0 continues the call
     // that left it, on the same path (generation) and at the position where that call ended
     const int mol = (mol_shape < 0 || mol_shape > topo->N) ? topo->N : mol_shape;
     if (R) return fail(HD_E_INVALID, "multistep path: inpainting takes ancestral rows only");
-    if (h->path_c2_h[(size_t)k_lo] != 0.f && !(topo->ms_hist && topo->ms_gen == h->path_gen && topo->ms_k == k_lo))
+    if (pt.path_c2_h[(size_t)k_lo] != 0.f && !(topo->ms_hist && topo->ms_gen == pt.path_gen && topo->ms_k == k_lo))
         return fail(HD_E_STATE, "multistep path: transition k_lo = " + std::to_string(k_lo) + " needs the data prediction of transition "
                     "k_lo - 1, which the last call on this topology did not leave (start at a row with c2 = 0, such as k_lo = 0, or "
                     "continue where the last call on the same path ended)");
@@ -3268,15 +3131,16 @@ static int path_loop(hd_handle* h, hd_topology* topo, float* z, const float* con
     if (!topo->ms_hist) HD_TRY(dev_alloc(&topo->ms_hist, (size_t)topo->B * topo->N * h->D));
     topo->ms_gen = 0;                                        // no history unless the whole range ran
     HD_TRY(path_loop_run(h, topo, z, context, mol_shape, k_lo, k_hi, raw_x, raw_h, noise_rows, seed, sample_id_base, use_graph,
-                         fixed_mask, xh_known, R, s, gd));
-    topo->ms_gen = h->path_gen; topo->ms_k = k_hi;           // stream-ordered behind this call, like z
+                         fixed_mask, xh_known, R, s, run, gd));
+    topo->ms_gen = pt.path_gen; topo->ms_k = k_hi;           // stream-ordered behind this call, like z
     return HD_OK;
 }
 
 static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
                          const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
-                         const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const GuideSrc* gd) {
-    const int T = h->T, K = h->path_K, N = topo->N, form = h->path_form;
+                         const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const PathRun& run, const GuideSrc* gd) {
+    const PathTables& pt = *run.pt;
+    const int T = h->T, K = pt.path_K, N = topo->N, form = pt.path_form;
     const int mol = (mol_shape < 0 || mol_shape > N) ? N : mol_shape;
     const int ms = mol_shape < 0 ? -1 : mol;
     const int nd = 3 * R;
@@ -3286,9 +3150,9 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
     topo_use(topo, s);
     if (ntr == 0) return HD_OK;
     if (gd) HD_TRY(guide_buffers(h, topo));
-    const bool rec = topo->chain_dst != nullptr;
+    const bool rec = run.record && topo->chain_dst != nullptr;
     if (rec) {
-        if (!h->d_chain_frame || h->chain_path_gen != h->path_gen)
+        if (!h->d_chain_frame || h->chain_path_gen != pt.path_gen)
             return fail(HD_E_STATE, "path loop: a chain sink is attached but the chain tables are not set for the current path (hd_set_chain)");
         if (h->chain_frames != topo->chain_frames)
             return fail(HD_E_INVALID, "path loop: the attached sink holds " + std::to_string(topo->chain_frames) + " frames, the chain "
@@ -3308,16 +3172,16 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
             const bool rec_z = rec && j == rounds - 1 && topo->chain_what == 0;
             if (rec && j == rounds - 1 && topo->chain_what == 1) HD_TRY(chain_launch(h, topo, io, topo->eps));
             if (form == 2) {
-                HD_TRY(solver_launch(h, topo, io.z, topo->eps, h->d_path_coef + (size_t)io.row * 5, nullptr, topo->ms_hist,
+                HD_TRY(solver_launch(h, topo, io.z, topo->eps, pt.d_path_coef + (size_t)io.row * 5, nullptr, topo->ms_hist,
                                      topo->ms_hist, mol, io.z, io.step, io.s));
                 if (rec_z) HD_TRY(chain_launch(h, topo, io, nullptr));
                 continue;
             }
             NoiseSrc ns = make_noise(raw_x ? raw_x + io.ro * 3 : nullptr, raw_h ? raw_h + io.ro * h->F : nullptr, noise_rows, seed,
                                      io.base, io.step ? 0u : stride * (uint32_t)(3 * j) + io.draw, share);
-            HD_TRY(step_impl(h, topo, io.z, topo->eps, h->d_path_coef + (size_t)io.row * 4, 1, ns, mol, io.z, N, io.step,
-                             io.step ? io.draw_w + 3 * j : nullptr, 0, io.s, io.base_w, form, io.step ? k_lo : -1));
-            if (R) HD_TRY(inpaint_round(h, topo, io, j, R, stride, seed, h->d_path_coef_ip));
+            HD_TRY(step_impl(h, topo, io.z, topo->eps, pt.d_path_coef + (size_t)io.row * 4, 1, ns, mol, io.z, N, io.step,
+                             io.step ? io.draw_w + 3 * j : nullptr, io.s, io.base_w, form, k_lo));
+            if (R) HD_TRY(inpaint_round(h, topo, io, j, R, stride, seed, pt.d_path_coef_ip));
             if (rec_z) HD_TRY(chain_launch(h, topo, io, nullptr));
         }
         return HD_OK;
@@ -3327,8 +3191,8 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
         io.z = z; io.ctx = context; io.fixed = fixed_mask; io.known = xh_known; io.base = sample_id_base; io.s = s;
         if (gd) { io.ctx_u = gd->ctx_u; io.w = gd->w; }
         for (int k = k_lo; k < k_hi; ++k) {
-            io.row = k; io.tcur = h->d_tau + h->path_t_h[k];
-            io.ro = (size_t)(k - k_lo) * noise_rows * mol; io.draw = (uint32_t)(T - h->path_s_h[k]);
+            io.row = k; io.tcur = h->d_tau + pt.path_t_h[k];
+            io.ro = (size_t)(k - k_lo) * noise_rows * mol; io.draw = (uint32_t)(T - pt.path_s_h[k]);
             HD_TRY(transition(io));
         }
         return HD_OK;
@@ -3345,23 +3209,22 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
     PathKey key;
     key.raw_x = raw_x; key.raw_h = raw_h; key.has_ctx = context ? 1 : 0; key.mol_shape = ms; key.noise_rows = noise_rows;
     key.k_lo = raw_x ? k_lo : 0; key.resamplings = R; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
-    key.path_gen = h->path_gen; key.ip_gen = R ? h->ip_gen : 0;
+    key.path_gen = pt.path_gen; key.ip_gen = R ? h->ip_gen : 0;
     key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
-    // the guided transition is a graph of its own: guided and unguided calls on one topology do not evict each other; so is the
-    // recording one (either kind), keyed on everything it bakes in but the sink's address
-    hipGraphExec_t* gx = rec ? &topo->gexec_chain : gd ? &topo->gexec_guided : &topo->gexec_path;
-    PathKey& kx = gd ? topo->gdkey : topo->pkey;
+    // the caller's slot (the every-step, the guided and the unguided transition are graphs of their own: such calls on one topology
+    // do not evict each other); so is the recording one (either kind), keyed on everything it bakes in but the sink's address
+    hipGraphExec_t* gx = rec ? &topo->gexec_chain : run.gx;
     ChainKey ckey;
     if (rec) {
         ckey.path = key; ckey.what = topo->chain_what; ckey.nv0 = topo->chain_nv0; ckey.nv1 = topo->chain_nv1; ckey.nb1 = topo->chain_nb1;
         ckey.chain_gen = h->chain_gen;
         HD_TRY(replay_evict(h, rs, gx, topo->ckey, ckey));
     } else {
-        HD_TRY(replay_evict(h, rs, gx, kx, key));
+        HD_TRY(replay_evict(h, rs, gx, *run.key, key));
     }
     PathWords w;
     w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = R ? h->d_ipdraw : nullptr;
-    w.tau = h->d_tau; w.t_idx = h->d_path_t; w.s_idx = h->d_path_s; w.K = K; w.T = T; w.nd = nd; w.stride = stride;
+    w.tau = h->d_tau; w.t_idx = pt.d_path_t; w.s_idx = pt.d_path_s; w.K = K; w.T = T; w.nd = nd; w.stride = stride;
     w.chain = rec ? h->d_chain_dst : nullptr;
     if (!*gx) {
         LoopIO io = loop_io_captured(h, R ? h->d_ipdraw : h->d_draw, rs);
@@ -3373,7 +3236,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
             return HD_OK;
         }));
         if (rec) { topo->ckey = ckey; topo->chain_builds++; }
-        else { kx = key; if (gd) topo->guided_builds++; else topo->path_builds++; }
+        else { *run.key = key; if (run.builds) ++*run.builds; }
     }
     HIP_TRY(hipMemcpyAsync(topo->zbuf, z, zbytes, hipMemcpyDeviceToDevice, rs));
     if (context) HIP_TRY(hipMemcpyAsync(topo->ctxbuf, context, cbytes, hipMemcpyDeviceToDevice, rs));
@@ -3393,10 +3256,55 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
 
 static int path_ready(hd_handle* h, const char* who, int k_lo, int k_hi) {
     if (h->T < 1) return fail(HD_E_STATE, std::string(who) + ": schedule not set (hd_set_schedule)");
-    if (h->path_K < 1 || h->path_sched_gen != h->sched_gen)
+    if (h->path.path_K < 1 || h->path.path_sched_gen != h->sched_gen)
         return fail(HD_E_STATE, std::string(who) + ": path not set for the current schedule (hd_set_path)");
-    if (k_lo < 0 || k_lo > k_hi || k_hi > h->path_K) return fail(HD_E_INVALID, std::string(who) + ": need 0 <= k_lo <= k_hi <= K");
+    if (k_lo < 0 || k_lo > k_hi || k_hi > h->path.path_K) return fail(HD_E_INVALID, std::string(who) + ": need 0 <= k_lo <= k_hi <= K");
     return HD_OK;
+}
+
+// The checks a loop without fixed fragments makes on its noise, context and model arguments (inpaint_args_check is the other kind).
+static int plain_args_check(const char* who, const hd_handle* h, const hd_topology* topo, const float* raw_x, const float* raw_h,
+                            int noise_rows, int mol_shape, const float* context) {
+    const std::string w(who);
+    if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, w + ": raw_x and raw_h go together");
+    if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, w + ": noise_rows must be 1 or B");
+    if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, w + ": context required");
+    if (!h->cfg.condition_time) return fail(HD_E_INVALID, w + ": needs a time-conditioned model");
+    if ((size_t)((mol_shape < 0 || mol_shape > topo->N) ? topo->N : mol_shape) * h->D * sizeof(float) > 64 * 1024)
+        return fail(HD_E_INVALID, w + ": N * D floats exceed one workgroup's LDS");
+    return HD_OK;
+}
+
+// The every-step loops: the path loop on the handle's every-step tables, where step s is position T - 1 - s.  Slots of their own,
+// no build counter, and no recording - a sink attached to the topology belongs to the caller's path (hd_set_chain).
+extern "C" int hd_sample_loop(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
+                              int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
+                              uint64_t seed, uint64_t sample_id_base, int use_graph, void* stream) {
+    HD_TRY(check_ready(h, topo, "hd_sample_loop"));
+    if (h->T < 1) return fail(HD_E_STATE, "hd_sample_loop: schedule not set (hd_set_schedule)");
+    if (!z) return fail(HD_E_INVALID, "hd_sample_loop: null z");
+    if (s_hi > h->T || s_lo < 0 || s_lo > s_hi) return fail(HD_E_INVALID, "hd_sample_loop: need 0 <= s_lo <= s_hi <= T");
+    HD_TRY(plain_args_check("hd_sample_loop", h, topo, raw_x, raw_h, noise_rows, mol_shape, context));
+    HIP_TRY(hipSetDevice(h->device));
+    return path_loop(h, topo, z, context, mol_shape, h->T - s_hi, h->T - s_lo, raw_x, raw_h, noise_rows, seed, sample_id_base, use_graph,
+                     nullptr, nullptr, 0, (hipStream_t)stream, {&h->every, &topo->gexec, &topo->gkey, nullptr, false});
+}
+
+extern "C" int hd_sample_loop_inpaint(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
+                                      int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
+                                      uint64_t seed, uint64_t sample_id_base, int use_graph, const uint8_t* fixed_mask,
+                                      const float* xh_known, int resamplings, void* stream) {
+    const char* who = "hd_sample_loop_inpaint";
+    HD_TRY(check_ready(h, topo, who));
+    if (h->T < 1) return fail(HD_E_STATE, "hd_sample_loop_inpaint: schedule not set (hd_set_schedule)");
+    if (!h->every.d_path_coef_ip || h->ip_sched_gen != h->sched_gen)
+        return fail(HD_E_STATE, "hd_sample_loop_inpaint: inpainting schedule not set for the current schedule (hd_set_inpaint_schedule)");
+    if (!z || !fixed_mask || !xh_known) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: null z / fixed_mask / xh_known");
+    if (s_hi > h->T || s_lo < 0 || s_lo > s_hi) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: need 0 <= s_lo <= s_hi <= T");
+    HD_TRY(inpaint_args_check(who, h, topo, raw_x, raw_h, noise_rows, mol_shape, resamplings, context, kIpRawMsg, kIpRowsMsg));
+    HIP_TRY(hipSetDevice(h->device));
+    return path_loop(h, topo, z, context, -1, h->T - s_hi, h->T - s_lo, nullptr, nullptr, noise_rows, seed, sample_id_base, use_graph,
+                     fixed_mask, xh_known, resamplings, (hipStream_t)stream, {&h->every, &topo->gexec_ip, &topo->ikey, nullptr, false});
 }
 
 extern "C" int hd_sample_path(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
@@ -3406,15 +3314,10 @@ extern "C" int hd_sample_path(hd_handle* h, hd_topology* topo, float* z, const f
     HD_TRY(check_ready(h, topo, "hd_sample_path"));
     HD_TRY(path_ready(h, "hd_sample_path", k_lo, k_hi));
     if (!z) return fail(HD_E_INVALID, "hd_sample_path: null z");
-    if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, "hd_sample_path: raw_x and raw_h go together");
-    if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_path: noise_rows must be 1 or B");
-    if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, "hd_sample_path: context required");
-    if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_path: needs a time-conditioned model");
-    if ((size_t)((mol_shape < 0 || mol_shape > topo->N) ? topo->N : mol_shape) * h->D * sizeof(float) > 64 * 1024)
-        return fail(HD_E_INVALID, "hd_sample_path: N * D floats exceed one workgroup's LDS");
+    HD_TRY(plain_args_check("hd_sample_path", h, topo, raw_x, raw_h, noise_rows, mol_shape, context));
     HIP_TRY(hipSetDevice(h->device));
     return path_loop(h, topo, z, context, mol_shape, k_lo, k_hi, raw_x, raw_h, noise_rows, seed, sample_id_base, use_graph,
-                     nullptr, nullptr, 0, (hipStream_t)stream);
+                     nullptr, nullptr, 0, (hipStream_t)stream, {&h->path, &topo->gexec_path, &topo->pkey, &topo->path_builds, true});
 }
 
 extern "C" int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo,
@@ -3430,7 +3333,8 @@ extern "C" int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z,
     HD_TRY(inpaint_args_check(who, h, topo, raw_x, raw_h, noise_rows, mol_shape, resamplings, context, kIpRawMsg, kIpRowsMsg));
     HIP_TRY(hipSetDevice(h->device));
     return path_loop(h, topo, z, context, -1, k_lo, k_hi, nullptr, nullptr, noise_rows, seed, sample_id_base, use_graph,
-                     fixed_mask, xh_known, resamplings, (hipStream_t)stream);
+                     fixed_mask, xh_known, resamplings, (hipStream_t)stream,
+                     {&h->path, &topo->gexec_path, &topo->pkey, &topo->path_builds, true});
 }
 
 // ----------------------------------------------------------------------------- classifier-free guidance
@@ -3475,15 +3379,14 @@ extern "C" int hd_sample_path_guided(hd_handle* h, hd_topology* topo, float* z, 
                                   ": inpainting takes no injected noise (counter-based generator only)", ": inpainting needs noise_rows = B"));
         R = resamplings;
     } else {
-        if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, "hd_sample_path_guided: raw_x and raw_h go together");
-        if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_path_guided: noise_rows must be 1 or B");
+        HD_TRY(plain_args_check(who, h, topo, raw_x, raw_h, noise_rows, -1, context));
     }
-    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_sample_path_guided: N * D floats exceed one workgroup's LDS");
     HIP_TRY(hipSetDevice(h->device));
     GuideSrc gd;
     gd.ctx_u = context_u; gd.w = w_dev; gd.w_rows = w_rows; gd.phi = rescale;
     return path_loop(h, topo, z, context, -1, k_lo, k_hi, R ? nullptr : raw_x, R ? nullptr : raw_h, noise_rows, seed, sample_id_base,
-                     use_graph, R ? fixed_mask : nullptr, R ? xh_known : nullptr, R, (hipStream_t)stream, &gd);
+                     use_graph, R ? fixed_mask : nullptr, R ? xh_known : nullptr, R, (hipStream_t)stream,
+                     {&h->path, &topo->gexec_guided, &topo->gdkey, &topo->guided_builds, true}, &gd);
 }
 
 // ----------------------------------------------------------------------------- editing given molecules: start state, slerp

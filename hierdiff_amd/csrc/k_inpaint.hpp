@@ -1,11 +1,12 @@
-// Fragment-constrained sampling ("inpainting", hd_sample_loop_inpaint): the replacement step behind every posterior step, the
+// Fragment-constrained sampling ("inpainting", hd_sample_loop_inpaint / hd_sample_path_inpaint): the replacement step behind every posterior step, the
 // jump back of a resampling round and the fix-up behind the final decode.  No reference counterpart: the known fragments of a
 // molecule are re-noised to the level of the current step and put in place of the generated rows (the replacement method of
 // score-based models; with resamplings > 1 the RePaint form).  Included through kernels.hpp, after k_sampling.hpp.
 //
 // One workgroup (256 threads) per molecule, one thread per (node, component) as in k_post_step; every sum runs over the
 // workgroup in the fixed order of block_sum4 (no atomics), so a molecule's bits depend on its own rows alone.  Exact fp32.
-// Step index, draw and first sample id come from kernel arguments (plain launches) or from device words (graph replay).
+// Path position (the row of `coef`), draw and first sample id come from kernel arguments (plain launches) or from the path
+// loop's device words (graph replay; k_path_state / k_path_advance in k_sampling.hpp keep the draws of all streams).
 #pragma once
 #include "k_sampling.hpp"
 
@@ -14,7 +15,7 @@ struct InpaintArgs {
     const uint8_t* nm;          // [B*N] node mask bytes
     const uint8_t* fixed;       // [B*N] fixed mask bytes (replace only)
     const float* known;         // [B][N][D] normalised known values (replace only)
-    const float* coef;          // [T][4] {alpha_s, sigma_s, alpha_t|s, sigma_t|s}, row s
+    const float* coef;          // [K][4] {alpha_s, sigma_s, alpha_t|s, sigma_t|s}, one row per path position (arrival level s)
     uint64_t seed, sample_base;
     uint32_t draw;
     int step;
@@ -178,16 +179,4 @@ __global__ void k_inpaint_decode_fix(InpaintFixArgs a) {
         for (int k = 0; k < 3; ++k) a.x[r * 3 + k] = a.x_known[r * 3 + k] + shift[k];
         for (int f = 0; f < a.F; ++f) a.hfeat[r * a.F + f] = a.h_known[r * a.F + f];
     }
-}
-
-// graph-replay helpers of the inpainting loop: draws[i] = (T + 2) * i + (T - s) for the 3 * resamplings streams of a step
-// (stream 3 j + k: round j, k = 0 posterior step, 1 known-part noise, 2 jump noise), moved on by one per step
-__global__ void k_inpaint_state(uint32_t* draws, int n, uint32_t stride, uint32_t d0) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) draws[i] = stride * (uint32_t)i + d0;
-}
-
-__global__ void k_inpaint_advance(uint32_t* draws, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) draws[i] += 1;
 }

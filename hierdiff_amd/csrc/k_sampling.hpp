@@ -1,5 +1,5 @@
 // Small kernels around the EGNN body: coordinate update, fp32-mode neighbour-sum reduction, output stage, posterior
-// step, final decode, noise, graph-replay step counter.  Included through kernels.hpp.
+// step, final decode, noise, the path loop's graph-replay words.  Included through kernels.hpp.
 #pragma once
 #include "common.hpp"
 
@@ -191,8 +191,7 @@ struct StepArgs {
     const uint32_t* draw_ptr;   // optional device-side draw counter (graph replay); overrides noise.draw
     const int* step_ptr;        // optional device-side step index into coef (graph replay)
     const unsigned long long* base_ptr;   // optional device-side first global sample id (graph replay); overrides noise.sample_base
-    uint32_t draw0;             // draw index of the first replayed step (raw-noise offset base)
-    int raw_step0;              // path loop: injected normals are indexed by *step_ptr - raw_step0 (path position); -1: by draw - draw0
+    int raw_step0;              // graph replay: injected normals are indexed by *step_ptr - raw_step0 (the position the call started at)
     int coef_rows, B, N, D, F, mol, out_stride;
 };
 
@@ -223,7 +222,7 @@ __global__ __launch_bounds__(256) void k_post_step(StepArgs a) {
     if (a.draw_ptr) {
         ns.draw = *a.draw_ptr;
         if (ns.raw_x) {
-            const size_t k = (size_t)(a.raw_step0 >= 0 ? (uint32_t)(*a.step_ptr - a.raw_step0) : ns.draw - a.draw0) * ns.rows * a.mol;
+            const size_t k = (size_t)(uint32_t)(*a.step_ptr - a.raw_step0) * ns.rows * a.mol;
             ns.raw_x += k * 3;
             ns.raw_h += k * a.F;
         }
@@ -372,24 +371,13 @@ __global__ void k_noise(NoiseArgs a) {
     }
 }
 
-// graph-replay helpers: k_loop_state initialises the device-side step / draw / time / sample-base words (values ride
-// in the kernel arguments, so no host buffer has to outlive the call), k_advance moves them on after each captured step
-__global__ void k_loop_state(int* step, uint32_t* draw, float* t_cur, unsigned long long* base, const float* tau,
-                             int s0, uint32_t d0, unsigned long long b0) {
-    *step = s0; *draw = d0; *t_cur = tau[s0 + 1]; *base = b0;
-}
-
-__global__ void k_advance(int* step, uint32_t* draw, float* t_cur, const float* tau) {
-    int s = *step - 1;
-    *step = s;
-    *draw = *draw + 1;
-    *t_cur = tau[s + 1 >= 0 ? s + 1 : 0];
-}
-
-// The same for a path (hd_set_path / hd_sample_path): `step` holds the path POSITION k, which is also the row of the path's
-// coefficient tables; transition k goes from grid index t_idx[k] to s_idx[k], so the network time is tau[t_idx[k]] and the
-// noise counter the fine-grid index of the arrival step, draw = T - s_idx[k] (the plain loop's layout restricted to the
-// visited s).  The inpainting loop's 3 * resamplings streams are offset by `stride` each (nd = 0: plain path loop).
+// graph-replay helpers of the path loop: k_path_state initialises the device-side step / draw / time / sample-base words (values
+// ride in the kernel arguments, so no host buffer has to outlive the call), k_path_advance moves them on after each captured
+// transition.  `step` holds the path POSITION k, which is also the row of the path's coefficient tables; transition k goes from
+// grid index t_idx[k] to s_idx[k], so the network time is tau[t_idx[k]] and the noise counter the fine-grid index of the arrival
+// step, draw = T - s_idx[k] (draw 0 is z_T; the every-step tables visit every s, a few-step path some of them).  The inpainting
+// loop's 3 * resamplings streams are offset by `stride` each: ipdraw[i] = stride * i + draw, stream 3 j + m of round j being
+// m = 0 the posterior step, 1 the known-part noise, 2 the jump noise (nd = 0: plain path loop).
 // Behind the last transition (k == K) the words keep the values of k = K - 1; nothing reads them.  One workgroup.
 // `chain`: the word a recording transition reads its sink from (k_chain.hpp; null: nothing records) - set by k_path_state alone.
 struct PathWords {

@@ -189,7 +189,8 @@ int hd_final_decode(hd_handle* h, hd_topology* topo, const float* z0, const floa
  *   path loops            (hd_sample_path, hd_sample_path_inpaint) the counter is the FINE-GRID index of the arrival step: the
  *                         transition t -> s of a path draws at T - s (inpainting: (T + 2) * (3 j + k) + (T - s)), draw 0 = z_T and
  *                         draw T + 1 = the final decode as above - the layouts above restricted to the visited s.  The identity path
- *                         T, T-1, .., 0 therefore reproduces the plain loops bit for bit.
+ *                         T, T-1, .., 0 is what hd_sample_loop / hd_sample_loop_inpaint run on; uploaded through hd_set_path it
+ *                         gives their bits.
  *   scoring               (hd_nll_terms, hd_nll_finish) a stream of its own, used with the DATA of a sample instead of its chain: the
  *                         noise eps_t of the bound's term t = 1 .. T is draw = t, the noise eps_0 of the t = 0 likelihood is draw 0.
  *                         The counter is the term's grid index, never its position in the term list, so a molecule's score does not
@@ -203,11 +204,15 @@ int hd_noise(hd_handle* h, hd_topology* topo, const float* raw_x, const float* r
              uint64_t seed, uint64_t sample_id_base, uint32_t draw, int share_rows, float* z, void* stream);
 
 /* Schedule for hd_sample_loop: host arrays of T+1 time values tau[k] = fp32(k)/T and T rows of
- * {alpha_t_given_s, sigma2_t_given_s, sigma_t, sigma} for s = 0..T-1 (t = s+1). */
+ * {alpha_t_given_s, sigma2_t_given_s, sigma_t, sigma} for s = 0..T-1 (t = s+1).  The library keeps them as the handle's built-in
+ * every-step tables: the identity path T -> T-1 -> .. -> 0 with these rows, next to and independent of the caller's path
+ * (hd_set_path below). */
 int hd_set_schedule(hd_handle* h, int T, const float* tau, const float* coef4);
 
 /* Runs posterior steps s = s_hi-1 ... s_lo on z[B,N,D] in place (rows >= mol_shape untouched):
- * per step one hd_egnn_forward at tau[s+1] and one hd_posterior_step.
+ * per step one hd_egnn_forward at tau[s+1] and one hd_posterior_step.  This is the path loop (hd_sample_path below) on the handle's
+ * every-step tables, transitions T - s_hi ... T - s_lo - 1, with a graph slot of its own: it and hd_sample_path do not evict each
+ * other, and hd_path_graph_builds does not count it.
  *   raw_x/raw_h  device [(s_hi-s_lo), noise_rows, mol, 3|F] in step order (first = s_hi-1), or NULL
  *                to use the counter-based generator with draw = T - s (draw 0 is z_T).  (The loop on a sub-sequence of the
  *                grid is hd_sample_path below; its draws are the same T - s of the steps it visits.)
@@ -349,7 +354,8 @@ int hd_multistep_step(hd_handle* h, hd_topology* topo, const float* zt, const fl
  *              network output, taken between the network call and the update.
  * Whole molecules only (mol_shape < N is HD_E_INVALID while a sink is attached).  Recording changes no sample: z is only read.
  * hd_chain_detach: stop recording; the unrecorded launches, graphs, keys and build counters are exactly those of a topology
- * that never recorded.  hd_sample_loop and hd_sample_loop_inpaint never record (run the identity path instead).
+ * that never recorded.  hd_sample_loop and hd_sample_loop_inpaint never record: they run the path loop on the handle's every-step
+ * tables, and the chain tables and the sink belong to the caller's path (to record a full chain, upload the identity path).
  *   use_graph    the recording transition is ONE more graph per topology next to the plain and the guided one (none evicts another).
  *                The sink's address is not baked in: it lives in a device word the loop's state kernel sets, so a new sink
  *                replays the cached graph.  Rebuilt when anything the unrecorded graph is keyed on changes, or what, nv0, nv1, nb1,
@@ -411,15 +417,17 @@ int hd_nll_finish(hd_handle* h, hd_topology* topo, const float* xh, const float*
  * run in a fixed order (no atomics).
  *
  * Schedule rows for the loop: host array of T rows {alpha_s, sigma_s, alpha_t_given_s, sigma_t_given_s} for s = 0..T-1 (t = s+1), from the
- * same gamma grid as the plain schedule; T must equal the T of the last schedule upload, and a new plain schedule needs a new upload here. */
+ * same gamma grid as the plain schedule; T must equal the T of the last schedule upload, and a new plain schedule needs a new upload here.
+ * They become the inpainting rows of the handle's every-step tables (hd_set_schedule). */
 int hd_set_inpaint_schedule(hd_handle* h, int T, const float* coef4);
 /* The arguments of the plain loop plus
  *   fixed_mask   device bytes [B*N] (0 = free), a subset of the node mask (rows outside it are ignored);
  *   xh_known     device [B,N,D] NORMALISED known positions and features (rows outside fixed_mask are ignored);
  *   resamplings  r >= 1.
  * Restrictions (HD_E_INVALID): raw_x / raw_h must be NULL, noise_rows = B, mol_shape < 0 or = N (no pocket rows).
- * use_graph: one captured step (all its rounds) per topology, cached like the plain loop's and rebuilt when resamplings, seed,
- * weights or schedule change; use_graph = 0 gives the same bits.  Stream-ordered, no host synchronisation in steady state. */
+ * This is hd_sample_path_inpaint's loop on the handle's every-step tables (transitions T - s_hi ... T - s_lo - 1), with a graph slot
+ * of its own.  use_graph: one captured step (all its rounds) per topology, cached like the plain loop's and rebuilt when resamplings,
+ * seed, weights or schedule change; use_graph = 0 gives the same bits.  Stream-ordered, no host synchronisation in steady state. */
 int hd_sample_loop_inpaint(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
                            int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
                            uint64_t seed, uint64_t sample_id_base, int use_graph, const uint8_t* fixed_mask,
