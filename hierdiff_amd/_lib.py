@@ -72,6 +72,12 @@ SIGNATURES = {
     "hd_chain_attach": (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]),
     "hd_chain_detach": (C.c_int, [_VP]),
     "hd_chain_graph_builds": (C.c_longlong, [_VP]),
+    "hd_set_restraint": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_float)]),
+    "hd_restraint_attach": (C.c_int, [_VP, _FP, C.c_int, C.c_int, _VP, _FP, C.c_int, C.c_int, _VP, _FP, C.c_int, C.c_int, _FP, C.c_int,
+                                      C.c_float, _VP]),
+    "hd_restraint_detach": (C.c_int, [_VP]),
+    "hd_restrain_eps": (C.c_int, [_VP, _VP, _FP, _FP, C.POINTER(C.c_float), _FP, _VP]),
+    "hd_restraint_energy": (C.c_int, [_VP, _VP, _FP, _VP, _VP]),
     "hd_diffuse": (C.c_int, [_VP, _VP, _FP, C.c_float, C.c_float, _FP, _FP, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int,
                              _FP, _VP]),
     "hd_set_path_up": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]),

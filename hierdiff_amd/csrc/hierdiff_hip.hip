@@ -123,6 +123,10 @@ struct hd_handle {
     float* d_chain_as;          // [K][2]; null when hd_set_chain got none
     unsigned long long chain_path_gen, chain_gen;   // path_gen the tables were set for (0: not set); bumped by every hd_set_chain
     float** d_chain_dst;        // graph replay: the sink a recording transition writes (set by k_path_state)
+    // restraints (hd_set_restraint): the rows {alpha_t, sigma_t, lambda_k, clip_k} of every transition of the current path
+    float* d_rs_rows;           // [K][4]
+    int rs_K;
+    unsigned long long rs_path_gen, rs_gen;         // path_gen the rows were set for (0: not set); bumped when the table moves
     // scoring (hd_set_nll_terms / hd_nll_terms / hd_nll_finish): K terms t_idx[k] of the bound, rows {alpha_t, sigma_t, w_t, 0}
     int nll_K;
     std::vector<int> nll_t_h;
@@ -160,10 +164,12 @@ struct PathKey {
     float phi;
     uint64_t seed;
     unsigned long long weights_gen, sched_gen, path_gen, ip_gen;
+    unsigned long long rs_gen, rs_rows_gen;                  // restrained transition: the topology's tables, the handle's rows (0 / 0: plain)
     bool operator==(const PathKey& o) const {
         return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape && noise_rows == o.noise_rows &&
                k_lo == o.k_lo && resamplings == o.resamplings && w_rows == o.w_rows && phi == o.phi && seed == o.seed &&
-               weights_gen == o.weights_gen && sched_gen == o.sched_gen && path_gen == o.path_gen && ip_gen == o.ip_gen;
+               weights_gen == o.weights_gen && sched_gen == o.sched_gen && path_gen == o.path_gen && ip_gen == o.ip_gen &&
+               rs_gen == o.rs_gen && rs_rows_gen == o.rs_rows_gen;
     }
 };
 
@@ -240,6 +246,17 @@ struct hd_topology {
     hipGraphExec_t gexec_chain;
     ChainKey ckey;
     long long chain_builds;
+    // hd_restraint_attach: library-owned copies of the restraint tables (addresses a captured transition keeps; they grow, never
+    // shrink), the per-molecule scales and the scratch of k_restrain_eps.  rs_gen moves when anything a captured launch bakes in does
+    // (an address, a size, a row count, nv0); re-attaching tables of the same sizes is a copy.
+    bool rs_on;
+    float *rs_obs, *rs_pair_f, *rs_anc_f, *rs_scale;
+    int *rs_pair_idx, *rs_anc_idx;
+    double* rs_step;
+    size_t rs_cap[6];
+    int rs_obs_rows, rs_P, rs_pair_rows, rs_Q, rs_anc_rows, rs_A, rs_scale_rows;
+    float rs_nv0;
+    unsigned long long rs_gen;
     // multistep paths (hd_set_path_multistep): the previous transition's data prediction x^ [B][N][D], allocated by the first
     // form-2 call at an address the captured transitions keep; host-side, which path generation and position it belongs to
     float* ms_hist;
@@ -364,6 +381,7 @@ extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
     h->ip_sched_gen = 0; h->ip_gen = 0; h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
     h->chain_frames = 0; h->d_chain_frame = nullptr; h->d_chain_as = nullptr; h->chain_path_gen = 0; h->chain_gen = 0;
     h->d_chain_dst = nullptr;
+    h->d_rs_rows = nullptr; h->rs_K = 0; h->rs_path_gen = 0; h->rs_gen = 0;
     h->nll_K = 0; h->d_nll_t = nullptr; h->d_nll_coef = nullptr; h->nll_sched_gen = 0; h->nll_gen = 0;
     h->d_nanflag = nullptr; h->d_nan_events = nullptr; h->d_step = nullptr; h->d_draw = nullptr; h->d_tcur = nullptr;
     h->d_base = nullptr;
@@ -419,6 +437,7 @@ extern "C" int hd_destroy(hd_handle* h) {
         hipFree(pt->d_path_t); hipFree(pt->d_path_s); hipFree(pt->d_path_coef); hipFree(pt->d_path_coef_ip);
     }
     hipFree(h->d_chain_frame); hipFree(h->d_chain_as); hipFree(h->d_chain_dst);
+    hipFree(h->d_rs_rows);
     hipFree(h->d_nll_t); hipFree(h->d_nll_coef);
 #ifdef HD_DEBUG_KERNELS
     hipFree(h->d_trace);
@@ -813,6 +832,9 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     for (hipGraphExec_t* gx : graph_slots(t)) graph_drop(gx);
     if (t->guide_mem) (void)hipFree(t->guide_mem);
     if (t->ms_hist) (void)hipFree(t->ms_hist);
+    for (void* p : {(void*)t->rs_obs, (void*)t->rs_pair_idx, (void*)t->rs_pair_f, (void*)t->rs_anc_idx, (void*)t->rs_anc_f,
+                    (void*)t->rs_scale, (void*)t->rs_step})
+        if (p) (void)hipFree(p);
     if (t->ip_fixed) (void)hipFree(t->ip_fixed);
     if (t->ip_known) (void)hipFree(t->ip_known);
     if (t->nll_eps) (void)hipFree(t->nll_eps);
@@ -3050,6 +3072,139 @@ extern "C" int hd_chain_detach(hd_topology* topo) {
 
 extern "C" long long hd_chain_graph_builds(const hd_topology* topo) { return topo ? topo->chain_builds : -1; }
 
+// ----------------------------------------------------------------------------- restraints on the data prediction of a path loop
+
+extern "C" int hd_set_restraint(hd_handle* h, int K, const float* rows4) {
+    if (!h || !rows4 || K < 1) return fail(HD_E_INVALID, "hd_set_restraint: bad argument");
+    if (h->path.path_K < 1 || h->path.path_sched_gen != h->sched_gen)
+        return fail(HD_E_STATE, "hd_set_restraint: path not set for the current schedule (hd_set_path)");
+    if (K != h->path.path_K) return fail(HD_E_INVALID, "hd_set_restraint: K differs from the path's (hd_set_path)");
+    for (int k = 0; k < K; ++k) {
+        const float *r = rows4 + (size_t)4 * k;
+        if (!(r[0] > 0.f) || !(r[1] >= 0.f) || !(r[2] - r[2] == 0.f) || !(r[3] > 0.f))
+            return fail(HD_E_INVALID, "hd_set_restraint: need alpha_t > 0, sigma_t >= 0, a finite lambda_k and clip_k > 0 (inf: no clip)");
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old rows
+    if (!h->d_rs_rows || h->rs_K != K) {                // same K: the table stays where captured transitions expect it
+        hipFree(h->d_rs_rows);
+        h->d_rs_rows = nullptr; h->rs_path_gen = 0; h->rs_K = 0;
+        HD_TRY(dev_alloc(&h->d_rs_rows, (size_t)4 * K));
+        h->rs_K = K;
+        h->rs_gen++;
+    }
+    HIP_TRY(hipMemcpy(h->d_rs_rows, rows4, (size_t)4 * K * sizeof(float), hipMemcpyHostToDevice));
+    h->rs_path_gen = h->path.path_gen;
+    return HD_OK;
+}
+
+// one library-owned table of the topology: grown when `count` exceeds its capacity (then *moved is set), filled from `src`
+template <typename T>
+static int rs_table(T** buf, size_t* cap, const T* src, size_t count, bool* moved, hipStream_t s) {
+    if (count > *cap || !*buf) {
+        HIP_TRY(hipDeviceSynchronize());                // a replay may still read the old table
+        if (*buf) (void)hipFree(*buf);
+        *buf = nullptr; *cap = 0;
+        HD_TRY(dev_alloc(buf, count));
+        *cap = std::max<size_t>(count, 1);
+        *moved = true;
+    }
+    if (count) HIP_TRY(hipMemcpyAsync(*buf, src, count * sizeof(T), hipMemcpyDefault, s));
+    return HD_OK;
+}
+
+extern "C" int hd_restraint_attach(hd_topology* topo, const float* obs, int obs_rows, int P, const int* pair_idx, const float* pair_f,
+                                   int pair_rows, int Q, const int* anc_idx, const float* anc_f, int anc_rows, int A,
+                                   const float* scale, int scale_rows, float nv0, void* stream) {
+    if (!topo) return fail(HD_E_INVALID, "hd_restraint_attach: null topology");
+    if (P < 0 || Q < 0 || A < 0) return fail(HD_E_INVALID, "hd_restraint_attach: P, Q, A must be >= 0");
+    if ((P > 0 && !obs) || (Q > 0 && (!pair_idx || !pair_f)) || (A > 0 && (!anc_idx || !anc_f)) || !scale)
+        return fail(HD_E_INVALID, "hd_restraint_attach: null table / scale");
+    const int B = topo->B;
+    for (int r : {obs_rows, pair_rows, anc_rows, scale_rows})
+        if (r != 1 && r != B) return fail(HD_E_INVALID, "hd_restraint_attach: every table has 1 row (shared) or B rows");
+    if (!(nv0 > 0.f) || !(nv0 - nv0 == 0.f)) return fail(HD_E_INVALID, "hd_restraint_attach: nv0 must be positive and finite");
+    if ((size_t)topo->N * 3 * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_restraint_attach: N * 3 floats exceed one workgroup's LDS");
+    HIP_TRY(hipSetDevice(topo->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    topo->rs_on = false;
+    bool moved = false;
+    HD_TRY(rs_table(&topo->rs_obs, &topo->rs_cap[0], obs, (size_t)obs_rows * P * 5, &moved, s));
+    HD_TRY(rs_table(&topo->rs_pair_idx, &topo->rs_cap[1], pair_idx, (size_t)pair_rows * Q * 2, &moved, s));
+    HD_TRY(rs_table(&topo->rs_pair_f, &topo->rs_cap[2], pair_f, (size_t)pair_rows * Q * 3, &moved, s));
+    HD_TRY(rs_table(&topo->rs_anc_idx, &topo->rs_cap[3], anc_idx, (size_t)anc_rows * A, &moved, s));
+    HD_TRY(rs_table(&topo->rs_anc_f, &topo->rs_cap[4], anc_f, (size_t)anc_rows * A * 5, &moved, s));
+    HD_TRY(rs_table(&topo->rs_scale, &topo->rs_cap[5], scale, (size_t)scale_rows, &moved, s));
+    if (!topo->rs_step) { HD_TRY(dev_alloc(&topo->rs_step, (size_t)B * topo->N * 3)); moved = true; }
+    if (moved || obs_rows != topo->rs_obs_rows || P != topo->rs_P || pair_rows != topo->rs_pair_rows || Q != topo->rs_Q ||
+        anc_rows != topo->rs_anc_rows || A != topo->rs_A || scale_rows != topo->rs_scale_rows || nv0 != topo->rs_nv0)
+        topo->rs_gen++;
+    topo->rs_obs_rows = obs_rows; topo->rs_P = P; topo->rs_pair_rows = pair_rows; topo->rs_Q = Q; topo->rs_anc_rows = anc_rows;
+    topo->rs_A = A; topo->rs_scale_rows = scale_rows; topo->rs_nv0 = nv0;
+    topo->rs_on = true;
+    return HD_OK;
+}
+
+extern "C" int hd_restraint_detach(hd_topology* topo) {
+    if (topo) topo->rs_on = false;
+    return HD_OK;
+}
+
+static RestraintTables restraint_tables(const hd_topology* t) {
+    RestraintTables r;
+    r.obs = t->rs_obs; r.pair_idx = t->rs_pair_idx; r.pair_f = t->rs_pair_f; r.anc_idx = t->rs_anc_idx; r.anc_f = t->rs_anc_f;
+    r.obs_rows = t->rs_obs_rows; r.P = t->rs_P; r.pair_rows = t->rs_pair_rows; r.Q = t->rs_Q; r.anc_rows = t->rs_anc_rows; r.A = t->rs_A;
+    return r;
+}
+
+// The update of one transition on eps (in place when out == eps): `rows` the device table read at position *step / k, or the host row.
+static int restrain_launch(hd_handle* h, hd_topology* t, const float* z, const float* eps, float* out, const float* rows,
+                           const float* row4, const int* step, int k, hipStream_t s) {
+    ProfScope ps(h, s, 2);
+    RestrainArgs a;
+    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.t = restraint_tables(t); a.scale = t->rs_scale;
+    a.rows = rows;
+    for (int i = 0; i < 4; ++i) a.row[i] = row4 ? row4[i] : 0.f;
+    a.step_ptr = step; a.k = k; a.step = t->rs_step; a.nv0 = t->rs_nv0; a.scale_rows = t->rs_scale_rows;
+    a.B = t->B; a.N = t->N; a.D = h->D;
+    hipLaunchKernelGGL(k_restrain_eps, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_restrain_eps(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4, float* out,
+                               void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_restrain_eps: null handle/topology");
+    if (!z || !eps || !row4 || !out) return fail(HD_E_INVALID, "hd_restrain_eps: null tensor / row");
+    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restrain_eps: no restraints attached to the topology (hd_restraint_attach)");
+    if (!(row4[0] > 0.f) || !(row4[1] >= 0.f) || !(row4[2] - row4[2] == 0.f) || !(row4[3] > 0.f))
+        return fail(HD_E_INVALID, "hd_restrain_eps: need alpha_t > 0, sigma_t >= 0, a finite lambda and clip > 0 (inf: no clip)");
+    const size_t per = (size_t)topo->B * topo->N * h->D;
+    if (out < z + per && z < out + per) return fail(HD_E_INVALID, "hd_restrain_eps: out may not overlap z");
+    if (out != eps && out < eps + per && eps < out + per)
+        return fail(HD_E_INVALID, "hd_restrain_eps: out may be eps itself, not a shifted overlap of it");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    return restrain_launch(h, topo, z, eps, out, nullptr, row4, nullptr, 0, s);
+}
+
+extern "C" int hd_restraint_energy(hd_handle* h, hd_topology* topo, const float* x, double* out3, void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_restraint_energy: null handle/topology");
+    if (!x || !out3) return fail(HD_E_INVALID, "hd_restraint_energy: null tensor");
+    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restraint_energy: no restraints attached to the topology (hd_restraint_attach)");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    ProfScope ps(h, s, 2);
+    RestraintEnergyArgs a;
+    a.x = x; a.nm = topo->nm_bytes; a.t = restraint_tables(topo); a.out = out3; a.B = topo->B; a.N = topo->N;
+    hipLaunchKernelGGL(k_restraint_energy, dim3(topo->B), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
 // Classifier-free guidance of a path loop: every network call becomes two (context, then ctx_u) and k_guide_combine in place.
 struct GuideSrc {
     const float* ctx_u;   // [B,N,C] the null (or any second) context
@@ -3161,6 +3316,14 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
             return fail(HD_E_STATE, "path loop: recording the data prediction needs the {alpha_t, sigma_t} rows (hd_set_chain)");
         if (mol != N) return fail(HD_E_INVALID, "path loop: a chain sink records whole molecules only (mol_shape < N)");
     }
+    const bool rsn = run.record && topo->rs_on;
+    if (rsn) {
+        if (R) return fail(HD_E_INVALID, "path loop: restraints are attached to the topology, and inpainting takes none (it re-centres "
+                                         "on the known fragments: hd_restraint_detach)");
+        if (!h->d_rs_rows || h->rs_path_gen != pt.path_gen)
+            return fail(HD_E_STATE, "path loop: restraints are attached but their rows are not set for the current path (hd_set_restraint)");
+        if (mol != N) return fail(HD_E_INVALID, "path loop: restraints act on whole molecules only (mol_shape < N)");
+    }
     const int rounds = R ? R : 1;
     auto transition = [&](const LoopIO& io) -> int {         // all rounds of one transition; io.row is the path position
         for (int j = 0; j < rounds; ++j) {
@@ -3169,6 +3332,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
                 HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx_u, ms, topo->eps_u, io.s));
                 HD_TRY(guide_launch(h, topo, topo->eps, topo->eps_u, io.w, gd->w_rows, gd->phi, topo->eps, io.s));
             }
+            if (rsn) HD_TRY(restrain_launch(h, topo, io.z, topo->eps, topo->eps, h->d_rs_rows, nullptr, io.step, io.row, io.s));
             const bool rec_z = rec && j == rounds - 1 && topo->chain_what == 0;
             if (rec && j == rounds - 1 && topo->chain_what == 1) HD_TRY(chain_launch(h, topo, io, topo->eps));
             if (form == 2) {
@@ -3211,6 +3375,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float*
     key.k_lo = raw_x ? k_lo : 0; key.resamplings = R; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
     key.path_gen = pt.path_gen; key.ip_gen = R ? h->ip_gen : 0;
     key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
+    key.rs_gen = rsn ? topo->rs_gen : 0; key.rs_rows_gen = rsn ? h->rs_gen : 0;
     // the caller's slot (the every-step, the guided and the unguided transition are graphs of their own: such calls on one topology
     // do not evict each other); so is the recording one (either kind), keyed on everything it bakes in but the sink's address
     hipGraphExec_t* gx = rec ? &topo->gexec_chain : run.gx;
@@ -3327,6 +3492,8 @@ extern "C" int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z,
     const char* who = "hd_sample_path_inpaint";
     if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_sample_path_inpaint: need 0 <= k_lo <= k_hi <= K");
     HD_TRY(check_ready(h, topo, who));
+    if (topo->rs_on) return fail(HD_E_INVALID, "hd_sample_path_inpaint: restraints are attached to the topology, and inpainting takes "
+                                               "none (it re-centres on the known fragments: hd_restraint_detach)");
     HD_TRY(path_ready(h, who, k_lo, k_hi));
     HD_TRY(inpaint_path_check(who, h, ": ancestral rows only (the path was set with form = 1)"));
     if (!z || !fixed_mask || !xh_known) return fail(HD_E_INVALID, "hd_sample_path_inpaint: null z / fixed_mask / xh_known");
@@ -3372,6 +3539,8 @@ extern "C" int hd_sample_path_guided(hd_handle* h, hd_topology* topo, float* z, 
     if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_path_guided: needs a time-conditioned model");
     int R = 0;
     if (fixed_mask) {                                        // the restrictions of hd_sample_path_inpaint
+        if (topo->rs_on) return fail(HD_E_INVALID, "hd_sample_path_guided: restraints are attached to the topology, and inpainting "
+                                                   "takes none (it re-centres on the known fragments: hd_restraint_detach)");
         HD_TRY(inpaint_path_check(who, h, ": inpainting takes ancestral rows only (the path was set with form = 1)"));
         if (!xh_known) return fail(HD_E_INVALID, "hd_sample_path_guided: fixed_mask without xh_known");
         // no mol_shape here; context and the time-conditioned model were checked above

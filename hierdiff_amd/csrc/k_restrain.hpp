@@ -1,0 +1,217 @@
+// Restraint-guided sampling (hd_restraint_attach / hd_set_restraint / hd_restrain_eps / hd_restraint_energy; no reference
+// counterpart).  Included through kernels.hpp.
+//   k_restrain_eps       eps_x += project(clip(s_b lambda_k dU/dx)) with U evaluated on the transition's data prediction x^0
+//   k_restraint_energy   (U_obs, U_pair, U_anc) per molecule, in double, for given data-unit positions
+// U, in data units (x = nv0 z_x, the model's frame: the centre of mass of the valid nodes at the origin), per molecule:
+//   U_obs  = 1/2 sum_{i valid} sum_p k_p max(0, r_p - |x_i - y_p|)^2                    obs  [rows][P][5] = (y, r, k); r <= 0 or k <= 0: padding
+//   U_pair = 1/2 sum_q k_q (max(0, d - hi)^2 + max(0, lo - d)^2),  d = |x_i - x_j|      pair_idx [rows][Q][2], pair_f [rows][Q][3] = (lo, hi, k)
+//   U_anc  = 1/2 sum_a k_a max(0, |x_i - a| - r)^2                                       anc_idx [rows][A], anc_f [rows][A][5] = (a, r, k)
+// rows = 1 (shared) or B.  A pair / anchor row is inactive when an index is < 0, >= N or masked in that molecule (or i == j, or
+// k <= 0).  A term at distance exactly 0 has energy but no gradient.
+// One workgroup (256 threads) per molecule as k_guide_combine.  The gradient of node i is gathered by ONE aligned group of
+// RS_GROUP lanes: its lanes stride over the P obstacles, then the Q pairs (those that name i), then the A anchors (those that name
+// i), each lane summing in double in that order; an xor butterfly inside the group, no atomics.  Node i belongs to group
+// (i mod 256 / RS_GROUP) whatever B is, so the partition and the order of every sum depend on (N, P, Q, A) alone.  The mean of the
+// clipped steps is a strided double sum per thread, the butterfly of a wave, then the four wave partials in a fixed tree
+// (guide_block_sum).  Draws nothing.
+#pragma once
+#include "common.hpp"
+#include "k_guide.hpp"
+
+#define RS_GROUP 16
+
+struct RestraintTables {
+    const float* obs;       // [obs_rows][P][5]
+    const int* pair_idx;    // [pair_rows][Q][2]
+    const float* pair_f;    // [pair_rows][Q][3]
+    const int* anc_idx;     // [anc_rows][A]
+    const float* anc_f;     // [anc_rows][A][5]
+    int obs_rows, P, pair_rows, Q, anc_rows, A;
+};
+
+struct RestrainArgs {
+    const float* z;         // [B][N][D] z_t
+    const float* eps;       // [B][N][D] network output
+    float* out;             // [B][N][D]; may be eps itself (then only the x columns of valid nodes are written)
+    const uint8_t* nm;      // [B*N] node mask bytes
+    RestraintTables t;
+    const float* scale;     // [scale_rows] s_b, scale_rows = 1 (shared) or B
+    const float* rows;      // device [K][4] {alpha_t, sigma_t, lambda_k, clip_k} (path loop); null: `row`
+    float row[4];
+    const int* step_ptr;    // device-side path position (graph replay); null: `k`
+    int k;
+    double* step;           // [B][N][3] scratch: the clipped steps before the projection
+    float nv0;
+    int scale_rows, B, N, D;
+};
+
+struct RestraintEnergyArgs {
+    const float* x;         // [B][N][3] positions in data units
+    const uint8_t* nm;
+    RestraintTables t;
+    double* out;            // [B][3] (U_obs, U_pair, U_anc)
+    int B, N;
+};
+
+// One obstacle on the offset u = x_i - y at distance d: the energy, and in `c` the factor with dU/dx_i = c u.
+HD_DEVINL double rs_obs_term(double d, double r, double k, double& c) {
+    c = 0.0;
+    if (!(d < r)) return 0.0;
+    const double v = r - d;
+    if (d > 0.0) c = -k * v / d;
+    return 0.5 * k * v * v;
+}
+
+// A flat-bottomed distance term (pairs: [lo, hi]; anchors: lo = -1, hi = r) at distance d; dU/du = c u for the offset u.
+HD_DEVINL double rs_band_term(double d, double lo, double hi, double k, double& c) {
+    c = 0.0;
+    double v;
+    if (d > hi) v = d - hi;
+    else if (d < lo) v = d - lo;
+    else return 0.0;
+    if (d > 0.0) c = k * v / d;
+    return 0.5 * k * v * v;
+}
+
+HD_DEVINL double rs_dist(const float* x, int i, double yx, double yy, double yz, double (&u)[3]) {
+    u[0] = (double)x[3 * i] - yx; u[1] = (double)x[3 * i + 1] - yy; u[2] = (double)x[3 * i + 2] - yz;
+    return sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+}
+
+HD_DEVINL bool rs_pair_active(const int* pi, const float* pf, const uint8_t* nm, int N, int& i, int& j) {
+    i = pi[0]; j = pi[1];
+    return i >= 0 && j >= 0 && i < N && j < N && i != j && nm[i] && nm[j] && pf[2] > 0.f;
+}
+
+// lane `l` of the `G` lanes that gather node i: its share of dU/dx_i into g (x: the molecule's positions, data units)
+HD_DEVINL void rs_node_grad(const RestraintTables& t, int b, const float* x, const uint8_t* nm, int N, int i, int l, int G,
+                            double (&g)[3]) {
+    double u[3], c;
+    const float* obs = t.obs + (size_t)(t.obs_rows == 1 ? 0 : b) * t.P * 5;
+    for (int p = l; p < t.P; p += G) {
+        const float* o = obs + (size_t)p * 5;
+        if (!(o[3] > 0.f) || !(o[4] > 0.f)) continue;
+        const double d = rs_dist(x, i, (double)o[0], (double)o[1], (double)o[2], u);
+        rs_obs_term(d, (double)o[3], (double)o[4], c);
+        g[0] += c * u[0]; g[1] += c * u[1]; g[2] += c * u[2];
+    }
+    const size_t prow = (size_t)(t.pair_rows == 1 ? 0 : b) * t.Q;
+    for (int q = l; q < t.Q; q += G) {
+        const float* pf = t.pair_f + (prow + q) * 3;
+        int a, c2;
+        if (!rs_pair_active(t.pair_idx + (prow + q) * 2, pf, nm, N, a, c2)) continue;
+        if (a != i && c2 != i) continue;
+        const int o = a == i ? c2 : a;
+        const double d = rs_dist(x, i, (double)x[3 * o], (double)x[3 * o + 1], (double)x[3 * o + 2], u);
+        rs_band_term(d, (double)pf[0], (double)pf[1], (double)pf[2], c);
+        g[0] += c * u[0]; g[1] += c * u[1]; g[2] += c * u[2];
+    }
+    const size_t arow = (size_t)(t.anc_rows == 1 ? 0 : b) * t.A;
+    for (int a = l; a < t.A; a += G) {
+        const float* af = t.anc_f + (arow + a) * 5;
+        if (t.anc_idx[arow + a] != i || !(af[4] > 0.f) || !(af[3] >= 0.f)) continue;
+        const double d = rs_dist(x, i, (double)af[0], (double)af[1], (double)af[2], u);
+        rs_band_term(d, -1.0, (double)af[3], (double)af[4], c);
+        g[0] += c * u[0]; g[1] += c * u[1]; g[2] += c * u[2];
+    }
+}
+
+// Dynamic LDS: N * 3 floats (x^0 of the molecule).
+__global__ __launch_bounds__(256) void k_restrain_eps(RestrainArgs a) {
+    extern __shared__ float rs_x[];
+    __shared__ double red[4 * 4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int N = a.N, D = a.D, total = N * D;
+    const size_t base = (size_t)b * total;
+    const float* z = a.z + base;
+    const float* eps = a.eps + base;
+    float* out = a.out + base;
+    const uint8_t* nm = a.nm + (size_t)b * N;
+    if (out != eps)
+        for (int e = tid; e < total; e += 256) out[e] = eps[e];
+    const int k = a.step_ptr ? *a.step_ptr : a.k;
+    const float* row = a.rows ? a.rows + (size_t)k * 4 : a.row;
+    const float al = row[0], sg = row[1], lam = row[2], clip = row[3];
+    const double sl = (double)a.scale[a.scale_rows == 1 ? 0 : b] * (double)lam;
+    if (sl == 0.0) return;                             // uniform over the workgroup: nothing (more) is written
+    // x^0 with the operations and the order of k_chain_frame<1>: the bits record="x0" shows
+    const float ra = __fdiv_rn(1.f, al);
+    for (int e = tid; e < 3 * N; e += 256) {
+        const int i = e / 3, c = e - 3 * i;
+        const size_t o = (size_t)i * D + c;
+        rs_x[e] = __fmul_rn(__fmul_rn(ra, __fsub_rn(z[o], __fmul_rn(sg, eps[o]))), a.nv0);
+    }
+    __syncthreads();
+    double* step = a.step + (size_t)b * N * 3;
+    const bool clips = clip - clip == 0.f;             // finite
+    const int l = tid & (RS_GROUP - 1), grp = tid / RS_GROUP;
+    for (int i0 = 0; i0 < N; i0 += 256 / RS_GROUP) {   // uniform trip count: the shuffles below see whole groups
+        const int i = i0 + grp;
+        const bool on = i < N && nm[i];
+        double g[3] = {0.0, 0.0, 0.0};
+        if (on) rs_node_grad(a.t, b, rs_x, nm, N, i, l, RS_GROUP, g);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int o = RS_GROUP / 2; o > 0; o >>= 1) g[c] += __shfl_xor(g[c], o);
+        if (on && l == 0) {
+            double d0 = sl * g[0], d1 = sl * g[1], d2 = sl * g[2];
+            if (clips) {
+                const double len = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+                if (len > (double)clip) { const double f = (double)clip / len; d0 *= f; d1 *= f; d2 *= f; }
+            }
+            step[3 * i] = d0; step[3 * i + 1] = d1; step[3 * i + 2] = d2;
+        }
+    }
+    __syncthreads();                                   // the steps of this molecule are in memory for every thread of the workgroup
+    double s[4] = {0.0, 0.0, 0.0, 0.0};                // sum of the steps, valid nodes
+    for (int i = tid; i < N; i += 256) {
+        if (!nm[i]) continue;
+        s[0] += step[3 * i]; s[1] += step[3 * i + 1]; s[2] += step[3 * i + 2]; s[3] += 1.0;
+    }
+    guide_block_sum<4>(s, red, tid);
+    if (!(s[3] > 0.0)) return;
+    const double m[3] = {s[0] / s[3], s[1] / s[3], s[2] / s[3]};
+    for (int e = tid; e < 3 * N; e += 256) {
+        const int i = e / 3, c = e - 3 * i;
+        if (!nm[i]) continue;
+        const double dl = step[e] - m[c];
+        if (dl == 0.0) continue;                       // an unmoved entry keeps its bits (-0 included)
+        const size_t o = (size_t)i * D + c;
+        out[o] = (float)((double)eps[o] + dl);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_restraint_energy(RestraintEnergyArgs a) {
+    __shared__ double red[4 * 3];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int N = a.N;
+    const RestraintTables& t = a.t;
+    const float* x = a.x + (size_t)b * N * 3;
+    const uint8_t* nm = a.nm + (size_t)b * N;
+    double U[3] = {0.0, 0.0, 0.0}, u[3], c;
+    const float* obs = t.obs + (size_t)(t.obs_rows == 1 ? 0 : b) * t.P * 5;
+    for (long long e = tid; e < (long long)N * t.P; e += 256) {
+        const int i = (int)(e / t.P), p = (int)(e - (long long)i * t.P);
+        const float* o = obs + (size_t)p * 5;
+        if (!nm[i] || !(o[3] > 0.f) || !(o[4] > 0.f)) continue;
+        U[0] += rs_obs_term(rs_dist(x, i, (double)o[0], (double)o[1], (double)o[2], u), (double)o[3], (double)o[4], c);
+    }
+    const size_t prow = (size_t)(t.pair_rows == 1 ? 0 : b) * t.Q;
+    for (int q = tid; q < t.Q; q += 256) {
+        const float* pf = t.pair_f + (prow + q) * 3;
+        int i, j;
+        if (!rs_pair_active(t.pair_idx + (prow + q) * 2, pf, nm, N, i, j)) continue;
+        const double d = rs_dist(x, i, (double)x[3 * j], (double)x[3 * j + 1], (double)x[3 * j + 2], u);
+        U[1] += rs_band_term(d, (double)pf[0], (double)pf[1], (double)pf[2], c);
+    }
+    const size_t arow = (size_t)(t.anc_rows == 1 ? 0 : b) * t.A;
+    for (int q = tid; q < t.A; q += 256) {
+        const float* af = t.anc_f + (arow + q) * 5;
+        const int i = t.anc_idx[arow + q];
+        if (i < 0 || i >= N || !nm[i] || !(af[4] > 0.f) || !(af[3] >= 0.f)) continue;
+        U[2] += rs_band_term(rs_dist(x, i, (double)af[0], (double)af[1], (double)af[2], u), -1.0, (double)af[3], (double)af[4], c);
+    }
+    guide_block_sum<3>(U, red, tid);
+    if (tid < 3) a.out[(size_t)b * 3 + tid] = U[tid];
+}

@@ -192,6 +192,12 @@ class DiffusionQM9(_Base):
         self.null_context = _get(cfg, "null_context", 0.0) or 0.0
         self.context_drop_prob = float(_get(cfg, "context_drop_prob", 0.0) or 0.0)
         self.context_drop_generator = None
+        # restraint-guided sampling (hierdiff_amd/restraints.py): defaults of the `restraints` / `restraint_scale` / `restraint_schedule`
+        # / `restraint_clip` keywords of the sampling entry points.  No restraints, or a scale of None / 0 = nothing changes.
+        self.restraints = None
+        self.restraint_scale = None
+        self.restraint_schedule = "score"
+        self.restraint_clip = None
 
     def check_issues_norm_values(self, num_stdevs=8):
         """diffusion_qm9.py:117-131 (predefined schedules only)."""
@@ -707,6 +713,29 @@ class DiffusionQM9(_Base):
     def _chain_close(topo):
         _lib.check(_lib.load().hd_chain_detach(topo.ptr), "hd_chain_detach")
 
+    def _restrain_open(self, handle, topo, tabs, rr, B: int, dev):
+        """Attach the restraints of a resolved call (`restraints.Resolved`) to `topo` behind the rows of the path that `_path_tables`
+        has just set (hd_set_restraint, once per (path tables, schedule, clip)).  The caller detaches (`_restrain_close`)."""
+        from . import restraints
+        pt = self._path_cache[2]
+        key = rr.key()
+        hit = self.__dict__.get("_restraint_cache")
+        if hit is None or hit[0] is not pt or hit[1] != key:
+            path = [int(t) for t in pt["t_idx"]] + [int(pt["s_idx"][-1])]
+            rows = np.ascontiguousarray(restraints.lambda_rows(tabs["gamma"], path, rr.schedule, rr.clip, float(self.norm_values[0])))
+            self._restraint_cache = None
+            _lib.check(_lib.load().hd_set_restraint(handle, int(rows.shape[0]), rows.ctypes.data_as(C.POINTER(C.c_float))),
+                       "hd_set_restraint")
+            self._restraint_cache = (pt, key)
+        rr.rs.check_batch(B)
+        import weakref
+        rr.rs._model = weakref.ref(self)
+        rr.rs.attach(topo, rr.scale, float(self.norm_values[0]), dev, _stream(dev))
+
+    @staticmethod
+    def _restrain_close(topo):
+        _lib.check(_lib.load().hd_restraint_detach(topo.ptr), "hd_restraint_detach")
+
     def _chain_times(self, keep_frames, t_start=None, inpaint: bool = False, steps=None, eta=None, spacing=None, timesteps=None,
                      solver=None, lower_order_final=None, **_):
         """[keep] the grid index every frame of a recording call has arrived at (`paths.chain_frames`): host arithmetic only."""
@@ -876,8 +905,21 @@ class DiffusionQM9(_Base):
                           steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
                           timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                           solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
-                          keep_frames: Optional[int] = None, record: Optional[str] = None):
+                          keep_frames: Optional[int] = None, record: Optional[str] = None,
+                          restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None):
         """z_T -> (x, h) for given masks: draw z_T, T posterior steps, final decode.
+
+        restraints / restraint_scale / restraint_schedule / restraint_clip (keyword-only; None: the model's attributes of the same
+        names): restraint-guided sampling (hierdiff_amd/restraints.py) - at every transition of the chain the gradient of an energy
+        U (obstacles, pair distances, anchors; a `restraints.Restraints`) on the network's data prediction goes into eps^, scaled by
+        `restraint_scale` (a float or a [B] tensor) times the schedule's lambda_k ("score": nv0 sigma_t / alpha_t, "sigma": sigma_t,
+        or K explicit weights), clipped per node to `restraint_clip` and freed of its mean, inside the library's loop (the identity
+        path when no few-step path is asked for).  Coordinates are in data units in the MODEL'S frame: the centre of mass of the
+        molecule's valid nodes is the origin, so obstacles and anchors are placed relative to where the molecule's centre sits.  The
+        final decode at t = 0 is the network's own.  No restraints, or a scale of None or 0, is the unrestrained code path,
+        untouched.  Combines with steps / eta / spacing / timesteps, solver "dpm2m", guidance and keep_frames.  Not with pocket
+        models, mode 'gnn_dynamics' or noise_mode 'torch'.  Mechanism only: which scale, schedule and clip help is for the user to
+        validate on a trained checkpoint.
 
         keep_frames / record (keyword-only; None: nothing is recorded and the call is today's): the reference's `sample_chain`
         (en_diffusion.py:669-710) - the chain runs in the path loop (the identity path when no few-step path is asked for) with a
@@ -926,6 +968,11 @@ class DiffusionQM9(_Base):
             raise ValueError("context required")
         if gd is not None and pe is None:            # a guided chain always runs in the path loop: the identity path, ancestral steps
             pe = (paths.build_path(self.T), 1.0)
+        from . import restraints as _rs
+        rr = _rs.resolve(self, restraints, restraint_scale, restraint_schedule, restraint_clip, int(node_mask.shape[0]),
+                         "sample_from_masks", pocket, needs_noise=raw_noises is None)
+        if rr is not None and pe is None:            # so does a restrained one
+            pe = (paths.build_path(self.T), 1.0)
         what = self._chain_check(keep_frames, record, "sample_from_masks", pocket, needs_noise=raw_noises is None)
         cf = None
         if what is not None:                         # so does a recorded one
@@ -971,13 +1018,19 @@ class DiffusionQM9(_Base):
 
         def run_loop(z_mol, rx, rh, rows, seed, base):
             """`run_steps`; a recording call attaches its sink to the topology for the time of the loop."""
-            if cf is None:
+            if cf is None and rr is None:
                 return run_steps(z_mol, rx, rh, rows, seed, base)
-            chain.append(self._chain_open(h, topo_loop, tabs, cf, what, B, N, dev))
             try:
+                if rr is not None:
+                    self._restrain_open(h, topo_loop, tabs, rr, B, dev)
+                if cf is not None:
+                    chain.append(self._chain_open(h, topo_loop, tabs, cf, what, B, N, dev))
                 return run_steps(z_mol, rx, rh, rows, seed, base)
             finally:
-                self._chain_close(topo_loop)
+                if cf is not None:
+                    self._chain_close(topo_loop)
+                if rr is not None:
+                    self._restrain_close(topo_loop)
 
         def run_steps(z_mol, rx, rh, rows, seed, base):
             """T posterior steps on [B,N,D]; with a pocket the fixed rows ride along behind the molecule."""
@@ -1060,7 +1113,8 @@ class DiffusionQM9(_Base):
     def path_steps(self, z, node_mask, edge_mask=None, context=None, *, steps=None, eta=None, spacing=None, timesteps=None,
                    k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False,
                    guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
-                   solver: Optional[str] = None, lower_order_final: Optional[bool] = None):
+                   solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
+                   restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None):
         """Transitions k_lo .. k_hi-1 of `sample_from_masks`'s few-step loop on a given z [B,N,D] (normalised units, the state at
         path position k_lo); returns the state at position k_hi (default: the end of the path, z_0 before the decode).  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.
@@ -1085,11 +1139,14 @@ class DiffusionQM9(_Base):
         gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, B, N, "path_steps")
         if gd is not None and context is None:
             raise ValueError("context required")
+        from . import restraints as _rs
+        rr = _rs.resolve(self, restraints, restraint_scale, restraint_schedule, restraint_clip, B, "path_steps")
         dev = node_mask.device
         if dev.type != "cuda":
             raise _lib.HierDiffHipError("sampling runs only on an MI355X (no CPU fallback)")
         h = self._lib_handle()
-        self._path_tables(h, self._schedule(rows=B), path, e)
+        tabs = self._schedule(rows=B)
+        self._path_tables(h, tabs, path, e)
         topo = self.dynamics.topology(node_mask, edge_mask, B, N)
         ctx = None
         if self.dynamics.context_node_nf > 0:
@@ -1097,14 +1154,20 @@ class DiffusionQM9(_Base):
                 raise ValueError("context required")
             ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
         z = z.detach().to(dev, torch.float32).clone().contiguous()
-        if gd is not None:
-            self._guided_path(h, topo, z, ctx, self._guide_device(gd, node_mask, dev), k_lo, k_hi, None, None,
-                              1 if fix_noise else B, self.seed, sample_id_base, _stream(dev))
+        if rr is not None:
+            self._restrain_open(h, topo, tabs, rr, B, dev)
+        try:
+            if gd is not None:
+                self._guided_path(h, topo, z, ctx, self._guide_device(gd, node_mask, dev), k_lo, k_hi, None, None,
+                                  1 if fix_noise else B, self.seed, sample_id_base, _stream(dev))
+                return z
+            _lib.check(_lib.load().hd_sample_path(h, topo.ptr, z.data_ptr(), _ptr(ctx), -1, int(k_lo), k_hi, None, None,
+                                                  1 if fix_noise else B, self.seed, sample_id_base, int(self.use_graph), _stream(dev)),
+                       "hd_sample_path")
             return z
-        _lib.check(_lib.load().hd_sample_path(h, topo.ptr, z.data_ptr(), _ptr(ctx), -1, int(k_lo), k_hi, None, None,
-                                              1 if fix_noise else B, self.seed, sample_id_base, int(self.use_graph), _stream(dev)),
-                   "hd_sample_path")
-        return z
+        finally:
+            if rr is not None:
+                self._restrain_close(topo)
 
     # ------------------------------------------------------------------ scoring: every term of the bound (no reference counterpart)
     def _nll_tables(self, handle, tabs, t_list):
@@ -1356,14 +1419,16 @@ class DiffusionQM9(_Base):
 
     @torch.no_grad()
     def encode(self, x, h, node_mask, edge_mask=None, context=None, *, t_end: Optional[int] = None, steps: Optional[int] = None,
-               spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None, solver: Optional[str] = None):
+               spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None, solver: Optional[str] = None,
+               restraints=None):
         """The latent z_{t_end} [B,N,D] (default t_end = T) of raw data (x, h): z_0 = alpha_0 xh without noise, then the deterministic
         eta = 0 update of the DDIM family run UPWARDS in t ("DDIM inversion") on `paths.ascending_path(T, t_end, steps, spacing,
         timesteps)` - default every grid point - inside the library's loop (hd_set_path_up / hd_sample_path: one captured transition
         per topology).  Nothing is drawn: the result depends on the data, the masks, the weights and the path only.  Decoding with
         `sample_from_latent(eta=0)` on the same points comes back near the molecule; how near is a property of the weights and K.
         The inversion stays first order: solver="dpm2m" raises ValueError (the model's `sample_solver` is not consulted)."""
-        from . import paths
+        from . import paths, restraints as _rs
+        _rs.refuse(self, "encode", restraints, ": the inversion follows the network's own flow")
         if paths.check_solver(solver) is not None:
             raise ValueError("encode: the inversion is first order (eta = 0 upwards); solver 'dpm2m' is not supported")
         t_end = self._grid_index(self.T if t_end is None else t_end, 1, "t_end")
@@ -1393,7 +1458,8 @@ class DiffusionQM9(_Base):
                      eta: Optional[float] = None, spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None,
                      k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False,
                      raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
-                     solver: Optional[str] = None, lower_order_final: Optional[bool] = None, _chain=None):
+                     solver: Optional[str] = None, lower_order_final: Optional[bool] = None, _chain=None,
+                     restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None):
         """Transitions k_lo .. k_hi-1 of `sample_from_latent`'s partial chain on a given z [B,N,D] (the state at path position k_lo);
         returns the state at position k_hi (default: the end, z_0 before the decode), as `path_steps` does for a full path.  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.  `raw_noises`: k_hi - k_lo injected
@@ -1408,6 +1474,9 @@ class DiffusionQM9(_Base):
         from . import guidance
         gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, B, N, "sample_from_latent",
                               needs_noise=raw_noises is None)
+        from . import restraints as _rs
+        rr = _rs.resolve(self, restraints, restraint_scale, restraint_schedule, restraint_clip, B, "sample_from_latent",
+                         needs_noise=raw_noises is None)
         nb = 1 if fix_noise else B
         if raw_noises is not None:
             if len(raw_noises) != k_hi - k_lo:
@@ -1424,9 +1493,11 @@ class DiffusionQM9(_Base):
             rx = torch.stack([r[0].to(st.dev, torch.float32) for r in raw_noises]).contiguous()
             rh = torch.stack([r[1].to(st.dev, torch.float32) for r in raw_noises]).contiguous()
             seed, base = 0, 0
-        if _chain is not None:           # `sample_from_latent` records: (frame table, code of `record`) -> (z, chain)
-            chain = self._chain_open(st.h, st.topo, st.tabs, _chain[0], _chain[1], B, N, st.dev)
         try:
+            if rr is not None:
+                self._restrain_open(st.h, st.topo, st.tabs, rr, B, st.dev)
+            if _chain is not None:       # `sample_from_latent` records: (frame table, code of `record`) -> (z, chain)
+                chain = self._chain_open(st.h, st.topo, st.tabs, _chain[0], _chain[1], B, N, st.dev)
             if gd is not None:
                 self._guided_path(st.h, st.topo, z, st.ctx, self._guide_device(gd, node_mask, st.dev), k_lo, k_hi, rx, rh, nb, seed,
                                   base, st.stream)
@@ -1436,6 +1507,8 @@ class DiffusionQM9(_Base):
         finally:
             if _chain is not None:
                 self._chain_close(st.topo)
+            if rr is not None:
+                self._restrain_close(st.topo)
         return z if _chain is None else (z, chain)
 
     @torch.no_grad()
@@ -1444,7 +1517,8 @@ class DiffusionQM9(_Base):
                            timesteps: Optional[Sequence[int]] = None, sample_id_base: int = 0, fix_noise: bool = False,
                            raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                            solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
-                           keep_frames: Optional[int] = None, record: Optional[str] = None):
+                           keep_frames: Optional[int] = None, record: Optional[str] = None,
+                           restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None):
         """(x, h) from a state z [B,N,D] at the grid index `t_start` (default T; normalised units - what `diffuse` and `encode`
         return): the partial reverse chain on `paths.partial_path(T, t_start, steps, spacing, timesteps)` (default: every grid point
         below t_start) inside the library's loop (hd_sample_path), then the final decode of `sample_from_masks`.  `eta` defaults to
@@ -1453,7 +1527,8 @@ class DiffusionQM9(_Base):
         path is `sample_from_masks(z_init=z)` bit for bit; `raw_noises` instead injects K + 1 pairs (the K transitions, the decode).
         `t_start` sets how far variations drift from the lead; which t_start, K and eta are chemically useful is for the user to
         validate on a trained checkpoint.  solver / lower_order_final: as in `sample_from_masks` ("dpm2m": second order, eta = 0).
-        keep_frames / record: as in `sample_from_masks` - a third tensor chain [keep_frames, B, N, D] of the partial chain."""
+        keep_frames / record: as in `sample_from_masks` - a third tensor chain [keep_frames, B, N, D] of the partial chain.
+        restraints / restraint_scale / restraint_schedule / restraint_clip: as in `sample_from_masks`, on the partial chain."""
         _, path, _ = self._latent_path(t_start, steps, eta, spacing, timesteps, solver, lower_order_final)
         K = len(path) - 1
         what = self._chain_check(keep_frames, record, "sample_from_latent", needs_noise=raw_noises is None)
@@ -1469,7 +1544,8 @@ class DiffusionQM9(_Base):
         z0 = self.latent_steps(z, node_mask, edge_mask, context, t_start=t_start, steps=steps, eta=eta, spacing=spacing,
                                timesteps=timesteps, sample_id_base=sample_id_base, fix_noise=fix_noise,
                                raw_noises=None if raw_noises is None else raw_noises[:K], guidance_scale=guidance_scale, guidance_context=guidance_context, guidance_rescale=guidance_rescale,
-                               solver=solver, lower_order_final=lower_order_final, _chain=None if cf is None else (cf, what))
+                               solver=solver, lower_order_final=lower_order_final, _chain=None if cf is None else (cf, what),
+                               restraints=restraints, restraint_scale=restraint_scale, restraint_schedule=restraint_schedule, restraint_clip=restraint_clip)
         chain = None
         if cf is not None:
             z0, chain = z0
@@ -1539,10 +1615,15 @@ class DiffusionQM9(_Base):
         from . import scoring
         device = torch.device(device)
         extra = set(few) - {"steps", "eta", "spacing", "timesteps", "guidance_scale", "guidance_context", "guidance_rescale", "solver",
-                            "lower_order_final", "keep_frames", "record"}
+                            "lower_order_final", "keep_frames", "record", "restraints", "restraint_scale", "restraint_schedule",
+                            "restraint_clip"}
         if extra:
             raise ValueError(f"vary: unsupported keyword(s) {sorted(extra)} (steps, eta, spacing, timesteps, guidance_scale, "
-                             "guidance_context, guidance_rescale, solver, lower_order_final, keep_frames, record)")
+                             "guidance_context, guidance_rescale, solver, lower_order_final, keep_frames, record, restraints, "
+                             "restraint_scale, restraint_schedule, restraint_clip)")
+        from . import restraints as _rs
+        rr_all = _rs.resolve(self, few.pop("restraints", None), few.pop("restraint_scale", None), few.get("restraint_schedule"),
+                             few.get("restraint_clip"), None, "vary")
         from . import guidance
         gscale, gctx = few.pop("guidance_scale", None), few.pop("guidance_context", None)
         few["guidance_rescale"] = few.get("guidance_rescale", None)
@@ -1553,7 +1634,7 @@ class DiffusionQM9(_Base):
                           few.get("lower_order_final"))                                                            # argument errors first
         chain_t = None
         if self._chain_check(few.get("keep_frames"), few.get("record"), "vary") is not None:
-            chain_t = self._chain_times(t_start=t_start, **few)
+            chain_t = self._chain_times(t_start=t_start, **{k: v for k, v in few.items() if not k.startswith("restraint")})
         for name, v in (("n_variants", n_variants), ("batch_size", batch_size)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
                 raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
@@ -1566,6 +1647,11 @@ class DiffusionQM9(_Base):
         jobs = [mol for mol in samples for _ in range(int(n_variants))]
         if gd_all is not None and gd_all.rows != 1 and gd_all.rows != len(jobs):
             raise ValueError(f"vary: guidance_scale must hold one scale per result ([{len(jobs)}], input-major), got {gd_all.rows}")
+        if rr_all is not None:
+            rr_all.rs.check_batch(len(jobs), "vary (one set of rows per result, input-major)")
+            if rr_all.scale.numel() not in (1, len(jobs)):
+                raise ValueError(f"vary: restraint_scale must hold one scale per result ([{len(jobs)}], input-major), got "
+                                 f"{rr_all.scale.numel()}")
         batches = [(lo, scoring.pad_samples(jobs[lo:lo + int(batch_size)], self.n_dims, self.in_node_nf, with_ctx))
                    for lo in range(0, len(jobs), int(batch_size))]
         self._edit_check("vary", batches[0][1][2], (), batches[0][1][3], needs_noise=True)
@@ -1575,7 +1661,13 @@ class DiffusionQM9(_Base):
             base = int(sample_id_base) + lo
             z = self.diffuse(x.to(device), h.to(device), nmd, t_start, sample_id_base=base)
             gs = None if gd_all is None else (float(gd_all.w[0]) if gd_all.rows == 1 else gd_all.w[lo:lo + nm.shape[0]])
-            got = self.sample_from_latent(z, nmd, None, ctxd, t_start=t_start, sample_id_base=base, guidance_scale=gs, **few)
+            rk = {}
+            if rr_all is not None:
+                rk = dict(restraints=rr_all.rs.slice(lo, lo + nm.shape[0]),
+                          restraint_scale=rr_all.scale if rr_all.scale.numel() == 1 else rr_all.scale[lo:lo + nm.shape[0]])
+            got = self.sample_from_latent(z, nmd, None, ctxd, t_start=t_start, sample_id_base=base, guidance_scale=gs, **few, **rk)
+            en = None if rr_all is None else rk["restraints"].energy(
+                got[0], nmd, model=self, _attach=(torch.as_tensor(rk["restraint_scale"]), float(self.norm_values[0]))).cpu()
             xv, hv = got[0].cpu(), got[1].cpu()
             part = []
             for i in range(nm.shape[0]):
@@ -1583,6 +1675,8 @@ class DiffusionQM9(_Base):
                 res = {'x': xv[i, :n].clone(), 'h': hv[i, :n].clone()}
                 if ctx is not None:
                     res['context'] = ctx[i, :n].clone()
+                if en is not None:
+                    res['restraint_energy'] = en[i].clone()
                 part.append(res)
             if chain_t is not None:
                 self._chain_into(part, got[2], [int(nm[i].sum()) for i in range(nm.shape[0])], chain_t)
@@ -1591,13 +1685,14 @@ class DiffusionQM9(_Base):
 
     @torch.no_grad()
     def interpolate(self, sample_a: Dict[str, torch.Tensor], sample_b: Dict[str, torch.Tensor], frames: int, device, *,
-                    t_end: Optional[int] = None, steps: Optional[int] = None, spacing: Optional[str] = None):
+                    t_end: Optional[int] = None, steps: Optional[int] = None, spacing: Optional[str] = None, restraints=None):
         """`frames` molecules between two of equal node count (the sampler's result format; ValueError otherwise): both are encoded
         to z_{t_end} (`encode`), the latents interpolated on the sphere at lambda = i / (frames - 1) (`slerp`), and every frame decoded
         with eta = 0 on the reversed path (`sample_from_latent`), all frames as one batch that shares the decode's noise row - so
         frames 0 and frames - 1 are the eta = 0 reconstructions of the two inputs, bit for bit.  A context is interpolated linearly.
         Returns a list of `frames` results.  Mechanism only: what lies between two molecules is a property of the weights."""
-        from . import scoring
+        from . import scoring, restraints as _rs
+        _rs.refuse(self, "interpolate", restraints, ": its frames are reconstructions of the interpolated latents")
         device = torch.device(device)
         if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or int(frames) < 2:
             raise ValueError(f"frames must be an integer >= 2, got {frames!r}")
@@ -1739,7 +1834,8 @@ class DiffusionQM9(_Base):
                        context=None, resamplings: int = 1, sample_id_base: int = 0, edge_mask: Optional[torch.Tensor] = None, *,
                        steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
                        timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
-                       solver: Optional[str] = None, keep_frames: Optional[int] = None, record: Optional[str] = None):
+                       solver: Optional[str] = None, keep_frames: Optional[int] = None, record: Optional[str] = None,
+                       restraints=None):
         """(x, h) on the device for molecules whose `fixed_mask` [B,N,1] nodes are known: `x_known` [B,N,3] / `h_known` [B,N,F] in
         data units (what `sample` returns; rows outside `fixed_mask` are ignored, the frame of the positions is free).  The free
         nodes are sampled around them by the replacement method, `resamplings` network calls per step (RePaint for > 1), inside
@@ -1752,6 +1848,8 @@ class DiffusionQM9(_Base):
         solver="dpm2m" (or the model's `sample_solver`) raises ValueError like eta < 1.  keep_frames / record: as in
         `sample_from_masks` - a third tensor chain [keep_frames, B, N, D]; a frame is the state behind its transition's last round
         (known rows replaced), or that round's data prediction, and frame 0 the returned (x, h)."""
+        from . import restraints as _rs
+        _rs.refuse(self, "sample_inpaint", restraints, ": inpainting re-centres on the known fragments, so its frame moves")
         pe0 = self._resolve_path(steps, eta, spacing, timesteps, inpaint=True, solver=solver)   # the solver's ValueError before any shape check
         what = self._chain_check(keep_frames, record, "sample_inpaint")
         cf = None
@@ -1793,13 +1891,16 @@ class DiffusionQM9(_Base):
     def sample_grow(self, known: Sequence[Dict[str, torch.Tensor]], sizes, device, context=None, resamplings: int = 1,
                     sample_id_base: int = 0, *, steps: Optional[int] = None, eta: Optional[float] = None,
                     spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
-                    solver: Optional[str] = None, keep_frames: Optional[int] = None, record: Optional[str] = None):
+                    solver: Optional[str] = None, keep_frames: Optional[int] = None, record: Optional[str] = None,
+                    restraints=None):
         """List-level form of `sample_inpaint` in `sample`'s result format: `known[i]` = {'x': [k_i,3], 'h': [k_i,F]} are the fragments
         molecule i keeps (its first k_i rows in the result; k_i = 0 allowed), `sizes[i]` >= k_i its total number of fragments (one
         integer: that many for every molecule).  `context`: as in `sample`.  Returns [{'x': [n_i,3], 'h': [n_i,F] (, 'context')}] on
         the CPU.  steps / eta / spacing / timesteps: as in `sample_inpaint`.  keep_frames / record: every dict also holds 'chain_x'
         [keep, n_i, 3], 'chain_h' [keep, n_i, F] and 'chain_t' [keep], as in `sample`."""
         device = torch.device(device)
+        from . import restraints as _rs
+        _rs.refuse(self, "sample_grow", restraints, ": inpainting re-centres on the known fragments, so its frame moves")
         self._resolve_path(steps, eta, spacing, timesteps, inpaint=True, solver=solver)       # argument errors first
         chain_t = None
         if self._chain_check(keep_frames, record, "sample_grow") is not None:
@@ -1856,14 +1957,19 @@ class DiffusionQM9(_Base):
                steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
                timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
-               keep_frames: Optional[int] = None, record: Optional[str] = None):
+               keep_frames: Optional[int] = None, record: Optional[str] = None,
+               restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None):
         """diffusion_qm9.py:347-395: list of {'x': [n_i,3], 'h': [n_i,8], ('context': [n_i,1])} on the CPU.
         steps / eta / spacing / timesteps: few-step sampling, see `sample_from_masks`; guidance_scale (a float or a
         [num_samples] tensor) / guidance_context ([num_samples, n_max, C]) / guidance_rescale: classifier-free guidance, ibid.;
         solver / lower_order_final: "dpm2m" = second-order multistep sampling, ibid.
         keep_frames / record ("z", the default, or "x0"): the trajectory, ibid. - every dict also holds 'chain_x' [keep, n_i, 3],
         'chain_h' [keep, n_i, F] (CPU, data units, the reference's frame order: frame 0 is the result itself) and 'chain_t' [keep],
-        the grid index every frame's state had arrived at."""
+        the grid index every frame's state had arrived at.
+        restraints / restraint_scale (a float or a [num_samples] tensor) / restraint_schedule / restraint_clip: restraint-guided
+        sampling, ibid. (tables with a batch axis hold num_samples sets of rows; coordinates in the model's frame, the molecule's
+        centre of mass at the origin) - every dict also holds 'restraint_energy', float64 [3] = (U_obs, U_pair, U_anc) of the
+        returned 'x'.  The sizes are drawn: a row that names a node the molecule does not have is inactive."""
         device = torch.device(device)
         self._resolve_path(steps, eta, spacing, timesteps, solver=solver, lower_order_final=lower_order_final)     # argument errors before anything is drawn
         if self._chain_check(keep_frames, record, "sample", pocket_cond) is not None:
@@ -1873,9 +1979,13 @@ class DiffusionQM9(_Base):
         gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, int(num_samples), None, "sample", pocket_cond)
         if gd is not None and context is None:
             raise ValueError("context required")
+        from . import restraints as _rs
+        _rs.resolve(self, restraints, restraint_scale, restraint_schedule, restraint_clip, int(num_samples), "sample", pocket_cond)
         few = {k: v for k, v in dict(steps=steps, eta=eta, spacing=spacing, timesteps=timesteps, guidance_scale=guidance_scale,
                                      guidance_context=guidance_context, guidance_rescale=guidance_rescale, solver=solver,
-                                     lower_order_final=lower_order_final, keep_frames=keep_frames, record=record).items()
+                                     lower_order_final=lower_order_final, keep_frames=keep_frames, record=record,
+                                     restraints=restraints, restraint_scale=restraint_scale, restraint_schedule=restraint_schedule,
+                                     restraint_clip=restraint_clip).items()
                if v is not None}
         sample_n = self.nodes_dist.sample(num_samples)
         pocket = None
@@ -1924,12 +2034,20 @@ class DiffusionQM9(_Base):
             out = [{'x': xs[i], 'h': hs[i]} for i in range(num_samples)]
         if len(got) == 3:                            # a recording call (`sample`: keep_frames)
             self._chain_into(out, got[2], sample_n, self._chain_times(**few))
+        from . import restraints as _rs
+        fw = few or {}
+        rr = _rs.resolve(self, fw.get("restraints"), fw.get("restraint_scale"), fw.get("restraint_schedule"), fw.get("restraint_clip"),
+                         num_samples, "sample", pocket)
+        if rr is not None:
+            en = rr.rs.energy(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0]))).cpu()
+            for i in range(num_samples):
+                out[i]['restraint_energy'] = en[i].clone()
         return out
 
     def sample_batches(self, batch_size, num_batches, device, context_range=None, protein_data_all=None,
                        sample_id_base: int = 0, *, steps: Optional[int] = None, eta: Optional[float] = None,
                        spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
-                       solver: Optional[str] = None, lower_order_final: Optional[bool] = None):
+                       solver: Optional[str] = None, lower_order_final: Optional[bool] = None, restraints=None):
         """diffusion_qm9.py:397-436, incl. the protein branch (`protein_data_all`: list of dicts with
         'residue_type', 'coord', 'pocket_name', 'ligand_name').
 
@@ -1943,6 +2061,8 @@ class DiffusionQM9(_Base):
         configurations whose results depend on a batch's padded width (below).  One difference that
         is not a sample's own: the NaN guard (en_dynamics.py:109-111) zeroes the velocity of the whole DEVICE batch."""
         device = torch.device(device)
+        from . import restraints as _rs
+        _rs.refuse(self, "sample_batches", restraints, ": the batches' padded widths and molecule counts differ (use sample)")
         self._resolve_path(steps, eta, spacing, timesteps, solver=solver, lower_order_final=lower_order_final)   # few-step sampling (`sample_from_masks`): argument errors first
         # classifier-free guidance (`sample_from_masks`): guidance_scale may also be a list / tuple of scales cycled per batch the way
         # context_range is; inside a merged device batch it becomes one scale per molecule

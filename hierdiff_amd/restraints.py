@@ -1,0 +1,325 @@
+"""Restraint-guided sampling: host side (the tables, argument resolution, the per-transition rows).
+
+At every transition of a path loop an energy U is evaluated on the network's data prediction x^0 and its gradient goes into the noise
+prediction (hd_restraint_attach / hd_set_restraint / k_restrain_eps, include/hierdiff_hip.h); the update that follows is unchanged.
+
+    U_obs  = 1/2 sum_{i valid} sum_p k_p max(0, r_p - |x_i - y_p|)^2                  stay out of these spheres
+    U_pair = 1/2 sum_q k_q (max(0, d - hi)^2 + max(0, lo - d)^2),  d = |x_i - x_j|     keep two nodes lo .. hi apart
+    U_anc  = 1/2 sum_a k_a max(0, |x_i - a| - r)^2                                     put a node within r of a point
+
+THE FRAME.  Coordinates are x = norm_values[0] * z_x in the MODEL'S frame, which has the centre of mass of the molecule's valid nodes
+at the origin - during the whole chain and in the result.  Obstacles and anchors are given in that frame: place the pocket relative
+to where the ligand's centre should sit.  Nothing here translates them.
+
+A pair or anchor row whose node index is -1 (padding), >= the molecule's size or masked is inactive - documented behaviour, not an
+error, because `sample` draws the sizes.  A term at distance exactly 0 contributes no gradient.
+
+Everything in this module is host arithmetic except `Restraints.energy` on a device tensor.  Mechanism only: which scale, schedule
+and clip steer a trained checkpoint usefully is for the user to validate; synthetic weights say nothing chemical."""
+from __future__ import annotations
+
+import math
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+SCHEDULES = ("score", "sigma")
+
+
+def _table(v, width: int, name: str) -> Optional[torch.Tensor]:
+    """None, [n, width] (shared) or [B, n, width] (per molecule) -> a contiguous CPU tensor [rows, n, width]."""
+    if v is None:
+        return None
+    try:
+        t = torch.as_tensor(v).detach().cpu()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{name} must be a tensor or nested list [n, {width}] or [B, n, {width}]") from None
+    if t.numel() == 0:
+        return None
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() != 3 or t.shape[2] != width:
+        raise ValueError(f"{name} must be [n, {width}] (shared) or [B, n, {width}] (per molecule), got {tuple(t.shape)}")
+    if t.is_floating_point() and not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{name} must be finite")
+    return t.to(torch.float64)
+
+
+class Restraints:
+    """The three tables of one call, validated and kept on the CPU.
+
+    obstacles  [P, 5] or [B, P, 5]   rows (y_x, y_y, y_z, r, k); a row with r <= 0 or k <= 0 is padding
+    pairs      [Q, 5] or [B, Q, 5]   rows (i, j, lo, hi, k); i = j = -1 is padding
+    anchors    [A, 6] or [B, A, 6]   rows (i, a_x, a_y, a_z, r, k); i = -1 is padding
+    Tensors or nested lists; a table with a leading batch axis holds one set of rows per molecule.  ValueError: lo > hi, a negative
+    r, k, lo or hi, non-finite values, i == j, fractional indices, negative indices other than -1."""
+
+    def __init__(self, obstacles=None, pairs=None, anchors=None):
+        obs, pr, an = _table(obstacles, 5, "obstacles"), _table(pairs, 5, "pairs"), _table(anchors, 6, "anchors")
+        if obs is not None and bool((obs[..., 3:] < 0).any()):
+            raise ValueError("obstacles: r and k must be >= 0 (a row with r = 0 or k = 0 is padding)")
+        self.obs = torch.zeros(1, 0, 5) if obs is None else obs.to(torch.float32).contiguous()
+        self.pair_idx, self.pair_f = self._split(pr, 2, "pairs")
+        self.anc_idx, self.anc_f = self._split(an, 1, "anchors")
+        if pr is not None:
+            live = self.pair_idx[..., 0] >= 0
+            if bool(((self.pair_idx[..., 0] == self.pair_idx[..., 1]) & live).any()):
+                raise ValueError("pairs: i == j")
+            if bool(((self.pair_idx < 0).any(-1) & ~(self.pair_idx == -1).all(-1)).any()):
+                raise ValueError("pairs: a padding row has i = j = -1")
+            if bool((self.pair_f < 0).any()):
+                raise ValueError("pairs: lo, hi and k must be >= 0")
+            if bool((self.pair_f[..., 0] > self.pair_f[..., 1]).any()):
+                raise ValueError("pairs: lo > hi")
+        if an is not None and bool((self.anc_f[..., 3:] < 0).any()):
+            raise ValueError("anchors: r and k must be >= 0")
+        self.anc_idx = self.anc_idx[..., 0].contiguous()
+        self._model = None                       # weak reference to the last model these restraints ran in (`energy` on a device)
+
+    @staticmethod
+    def _split(t, n_idx: int, name: str):
+        if t is None:
+            return torch.full((1, 0, n_idx), -1, dtype=torch.int32), torch.zeros(1, 0, 3 if n_idx == 2 else 5)
+        idx = t[..., :n_idx]
+        if bool((idx != idx.round()).any()) or bool((idx < -1).any()):
+            raise ValueError(f"{name}: node indices must be integers >= 0, or -1 for padding")
+        return idx.to(torch.int32).contiguous(), t[..., n_idx:].to(torch.float32).contiguous()
+
+    @property
+    def sizes(self):
+        return int(self.obs.shape[1]), int(self.pair_idx.shape[1]), int(self.anc_idx.shape[1])
+
+    def rows(self):
+        return int(self.obs.shape[0]), int(self.pair_idx.shape[0]), int(self.anc_idx.shape[0])
+
+    def check_batch(self, B: int, what: str = "restraints") -> None:
+        for name, r in zip(("obstacles", "pairs", "anchors"), self.rows()):
+            if r != 1 and r != int(B):
+                raise ValueError(f"{what}: {name} hold rows for {r} molecules, the call has {B} (give [n, w] to share one set)")
+
+    def slice(self, lo: int, hi: int) -> "Restraints":
+        """The rows of molecules lo .. hi - 1 (shared tables stay shared)."""
+        out = object.__new__(Restraints)
+        for k in ("obs", "pair_idx", "pair_f", "anc_idx", "anc_f"):
+            t = getattr(self, k)
+            setattr(out, k, t if t.shape[0] == 1 else t[lo:hi].contiguous())
+        out._model = getattr(self, "_model", None)
+        return out
+
+    @classmethod
+    def from_json(cls, path: str) -> "Restraints":
+        """A JSON file with the keys `obstacles`, `pairs`, `anchors` (each optional; the row formats above)."""
+        import json
+        with open(path) as f:
+            d = json.load(f)
+        if not isinstance(d, dict) or set(d) - {"obstacles", "pairs", "anchors"}:
+            raise ValueError(f"{path}: expected an object with the keys obstacles / pairs / anchors")
+        return cls(d.get("obstacles"), d.get("pairs"), d.get("anchors"))
+
+    # ------------------------------------------------------------------ device side
+    def attach(self, topo, scale: torch.Tensor, nv0: float, dev, stream) -> None:
+        """hd_restraint_attach: the tables and the scales [1] or [B] into the topology's buffers (stream-ordered copies)."""
+        from . import _lib
+        P, Q, A = self.sizes
+        t = [x.to(dev).contiguous() for x in (self.obs, self.pair_idx, self.pair_f, self.anc_idx, self.anc_f, scale.to(torch.float32))]
+        ro, rp, ra = self.rows()
+        _lib.check(_lib.load().hd_restraint_attach(
+            topo.ptr, t[0].data_ptr() if P else None, ro, P, t[1].data_ptr() if Q else None, t[2].data_ptr() if Q else None, rp, Q,
+            t[3].data_ptr() if A else None, t[4].data_ptr() if A else None, ra, A, t[5].data_ptr(), int(t[5].numel()), float(nv0),
+            stream), "hd_restraint_attach")
+
+    @staticmethod
+    def detach(topo) -> None:
+        from . import _lib
+        _lib.check(_lib.load().hd_restraint_detach(topo.ptr), "hd_restraint_detach")
+
+    def energy(self, x: torch.Tensor, node_mask: torch.Tensor, model=None, _attach=None) -> torch.Tensor:
+        """[B, 3] float64 (U_obs, U_pair, U_anc) of positions x [B, N, 3] in data units under node_mask [B, N, 1].  On a device the HIP
+        kernel evaluates it (k_restraint_energy; `model`: the DiffusionQM9 whose handle and topology cache are used); on the CPU the
+        same formulas in torch float64."""
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        if tuple(x.shape) != (B, N, 3):
+            raise ValueError(f"x must be [{B}, {N}, 3], got {tuple(x.shape)}")
+        self.check_batch(B, "energy")
+        if x.device.type != "cuda":
+            return energy_terms(self, x.detach().double(), node_mask)
+        model = model if model is not None else (self._model() if getattr(self, "_model", None) is not None else None)
+        if model is None:
+            raise ValueError("energy on a device needs model= (the DiffusionQM9 that owns the library handle) unless these "
+                             "restraints have already run in one of its sampling calls")
+        from . import _lib
+        from .dynamics import _stream
+        dev = x.device
+        nm = node_mask.to(dev)
+        h = model._lib_handle()
+        topo = model.dynamics.topology(nm, None, B, N)
+        out = torch.empty((B, 3), device=dev, dtype=torch.float64)
+        xs = x.detach().to(torch.float32).contiguous()
+        # (`_attach`: the scales and nv0 of the sampling call whose result this is - the energy reads neither, and attaching what
+        # the call attached keeps its cached graph)
+        scale, nv0 = (torch.ones(1), 1.0) if _attach is None else _attach
+        self.attach(topo, scale, nv0, dev, _stream(dev))
+        try:
+            _lib.check(_lib.load().hd_restraint_energy(h, topo.ptr, xs.data_ptr(), out.data_ptr(), _stream(dev)), "hd_restraint_energy")
+        finally:
+            self.detach(topo)
+        return out
+
+
+def energy_terms(rs: Restraints, x: torch.Tensor, node_mask: torch.Tensor) -> torch.Tensor:
+    """[B, 3] (U_obs, U_pair, U_anc) in x's dtype, differentiable in x: the formulas of the module docstring in torch."""
+    B, N = int(x.shape[0]), int(x.shape[1])
+    nm = node_mask.reshape(B, N).bool().to(x.device)
+    out = []
+    for b in range(B):
+        xb, m = x[b], nm[b]
+        zero = xb.sum() * 0
+        o = rs.obs[0 if rs.obs.shape[0] == 1 else b].to(x)
+        o = o[(o[:, 3] > 0) & (o[:, 4] > 0)]
+        u_obs = zero
+        if o.shape[0] and bool(m.any()):
+            d = _norm(xb[m][:, None, :] - o[None, :, :3])
+            u_obs = 0.5 * (o[None, :, 4] * torch.clamp(o[None, :, 3] - d, min=0) ** 2).sum()
+        pi = rs.pair_idx[0 if rs.pair_idx.shape[0] == 1 else b].long()
+        pf = rs.pair_f[0 if rs.pair_f.shape[0] == 1 else b].to(x)
+        u_pair = zero
+        ok = (pi >= 0).all(1) & (pi < N).all(1) & (pi[:, 0] != pi[:, 1]) & (pf[:, 2] > 0)
+        ok = ok & m[pi[:, 0].clamp(0, N - 1)] & m[pi[:, 1].clamp(0, N - 1)]
+        if bool(ok.any()):
+            pi, pf = pi[ok], pf[ok]
+            d = _norm(xb[pi[:, 0]] - xb[pi[:, 1]])
+            u_pair = 0.5 * (pf[:, 2] * (torch.clamp(d - pf[:, 1], min=0) ** 2 + torch.clamp(pf[:, 0] - d, min=0) ** 2)).sum()
+        ai = rs.anc_idx[0 if rs.anc_idx.shape[0] == 1 else b].long()
+        af = rs.anc_f[0 if rs.anc_f.shape[0] == 1 else b].to(x)
+        u_anc = zero
+        ok = (ai >= 0) & (ai < N) & (af[:, 4] > 0)
+        ok = ok & m[ai.clamp(0, N - 1)]
+        if bool(ok.any()):
+            ai, af = ai[ok], af[ok]
+            d = _norm(xb[ai] - af[:, :3])
+            u_anc = 0.5 * (af[:, 4] * torch.clamp(d - af[:, 3], min=0) ** 2).sum()
+        out.append(torch.stack([u_obs, u_pair, u_anc]))
+    return torch.stack(out)
+
+
+def _norm(v):
+    """|v| along the last axis with a zero (sub)gradient at v = 0."""
+    s = (v * v).sum(-1)
+    safe = torch.where(s > 0, s, torch.ones_like(s))
+    return torch.where(s > 0, torch.sqrt(safe), torch.zeros_like(s))
+
+
+# ----------------------------------------------------------------------------- the per-transition rows
+
+def check_clip(clip) -> float:
+    if clip is None:
+        return math.inf
+    if isinstance(clip, bool) or not isinstance(clip, (int, float, np.integer, np.floating)) or not float(clip) > 0.0:
+        raise ValueError(f"restraint_clip must be a positive number (None or inf: no clip), got {clip!r}")
+    return float(clip)
+
+
+def lambda_rows(gamma, path: Sequence[int], schedule="score", clip=None, nv0: float = 1.0) -> np.ndarray:
+    """[K, 4] float32 rows {alpha_t, sigma_t, lambda_k, clip_k} of the transitions of `path` (grid indices, path[k] -> path[k + 1];
+    the departure level t = path[k] counts), from the gamma grid.  alpha_t / sigma_t are the fp32 sqrt(sigmoid(-+gamma_t)) of the fp32
+    grid - the values `record="x0"` uses; lambda_k is evaluated in float64 and rounded once:
+        "score" (default)   lambda_k = nv0 sigma_t / alpha_t   the score-guidance weight with d eps^ / d z ignored:
+                            d x^0 / d z_x = nv0 / alpha_t, and a score s enters eps^ as -sigma_t s
+        "sigma"             lambda_k = sigma_t
+        a length-K sequence explicit weights
+    clip: the largest |Delta_i| per node in eps units (None: no clip)."""
+    g32 = torch.as_tensor(gamma).detach().to(torch.float32).reshape(-1)
+    g64 = torch.as_tensor(gamma).detach().to(torch.float64).reshape(-1)
+    K = len(path) - 1
+    if K < 1:
+        raise ValueError("lambda_rows: the path has no transition")
+    c = check_clip(clip)
+    t = torch.as_tensor(list(path[:-1]), dtype=torch.int64)
+    al32, sg32 = torch.sqrt(torch.sigmoid(-g32[t])), torch.sqrt(torch.sigmoid(g32[t]))
+    if isinstance(schedule, str):
+        if schedule not in SCHEDULES:
+            raise ValueError(f"restraint_schedule must be one of {SCHEDULES} or a length-K sequence, got {schedule!r}")
+        al, sg = torch.sqrt(torch.sigmoid(-g64[t])), torch.sqrt(torch.sigmoid(g64[t]))
+        lam = float(nv0) * sg / al if schedule == "score" else sg
+    else:
+        try:
+            lam = torch.as_tensor(schedule, dtype=torch.float64).reshape(-1)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"restraint_schedule must be one of {SCHEDULES} or a length-K sequence, got {schedule!r}") from None
+        if lam.numel() != K or not bool(torch.isfinite(lam).all()):
+            raise ValueError(f"restraint_schedule: an explicit sequence holds one finite weight per transition ({K})")
+    rows = np.empty((K, 4), dtype=np.float32)
+    rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3] = al32.numpy(), sg32.numpy(), lam.numpy().astype(np.float32), np.float32(c)
+    return rows
+
+
+class Resolved:
+    """A restrained call: the tables, the scales float32 [1] or [B] (CPU), the schedule and the clip."""
+
+    def __init__(self, rs: Restraints, scale: torch.Tensor, schedule, clip: float):
+        self.rs, self.scale, self.schedule, self.clip = rs, scale, schedule, clip
+
+    def key(self):
+        s = self.schedule
+        return (s if isinstance(s, str) else tuple(float(v) for v in torch.as_tensor(s).reshape(-1).tolist()), self.clip)
+
+
+def check_model(model, what: str, pocket=None, needs_noise: bool = True) -> None:
+    if model.pocket or pocket is not None:
+        raise NotImplementedError(f"{what}: restraints on pocket models are not supported (the model's frame is the ligand's alone)")
+    if getattr(model.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics":
+        raise NotImplementedError(f"{what}: restraints with mode 'gnn_dynamics' are not supported (the library's loop evaluates the egnn network)")
+    if needs_noise and model.noise_mode == "torch":
+        raise NotImplementedError(f"{what}: restraints with noise_mode 'torch' are not supported (counter-based or injected noise only)")
+
+
+def resolve(model, restraints, scale, schedule, clip, B: Optional[int] = None, what: str = "restraints", pocket=None,
+            needs_noise: bool = True) -> Optional[Resolved]:
+    """Keywords (None: the model's `restraints` / `restraint_scale` / `restraint_schedule` / `restraint_clip`) -> None for the
+    unrestrained code path, untouched, or a `Resolved`.  No restraints, or a scale of None or 0, is the unrestrained path.  Pure host
+    checks: every error is raised before a device is looked at."""
+    restraints = model.restraints if restraints is None else restraints
+    scale = model.restraint_scale if scale is None else scale
+    schedule = model.restraint_schedule if schedule is None else schedule
+    clip = model.restraint_clip if clip is None else clip
+    if restraints is None:
+        return None
+    if not isinstance(restraints, Restraints):
+        raise ValueError(f"restraints must be a hierdiff_amd.restraints.Restraints, got {type(restraints).__name__}")
+    if scale is None:
+        return None
+    if isinstance(scale, bool):
+        raise ValueError(f"restraint_scale must be a number or a [B] tensor, got {scale!r}")
+    try:
+        s = torch.as_tensor(scale, dtype=torch.float32).detach().cpu()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"restraint_scale must be a number or a [B] tensor, got {scale!r}") from None
+    s = s.reshape(1) if s.dim() == 0 else s
+    if s.dim() != 1 or s.numel() < 1 or not bool(torch.isfinite(s).all()):
+        raise ValueError("restraint_scale must be a finite number or a [B] tensor")
+    if B is not None and s.numel() not in (1, int(B)):
+        raise ValueError(f"restraint_scale must hold one scale per molecule ([{B}]), got {s.numel()}")
+    if not isinstance(schedule, str):
+        try:
+            torch.as_tensor(schedule, dtype=torch.float64)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"restraint_schedule must be one of {SCHEDULES} or a length-K sequence, got {schedule!r}") from None
+    elif schedule not in SCHEDULES:
+        raise ValueError(f"restraint_schedule must be one of {SCHEDULES} or a length-K sequence, got {schedule!r}")
+    c = check_clip(clip)
+    if not bool((s != 0).any()):
+        return None
+    check_model(model, what, pocket, needs_noise)
+    if B is not None:
+        restraints.check_batch(B, what)
+    return Resolved(restraints, s.contiguous(), schedule, c)
+
+
+def refuse(model, what: str, restraints=None, why: str = "") -> None:
+    """Entry points that take no restraints: an error when the keyword or the model's attributes ask for them, instead of ignoring
+    them."""
+    if restraints is not None or resolve(model, None, None, None, None, None, what) is not None:
+        raise NotImplementedError(f"{what}: restraints are not supported here{why} (the `restraints` keyword, or model.restraints "
+                                  "with a non-zero model.restraint_scale); they act in sample / sample_from_masks / path_steps / "
+                                  "sample_from_latent / vary")

@@ -28,6 +28,7 @@ them in id order into `<out>`.
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import pickle
 from typing import Dict, List, Optional, Tuple
@@ -211,7 +212,33 @@ def parse_args(argv=None):
                          "--grow, --vary), not with --score / --interpolate")
     ap.add_argument("--record", choices=["z", "x0"], default=None,
                     help="with --chain: keep the states (z, default) or the network's data prediction of the same transitions (x0)")
+    ap.add_argument("--restraints", default=None, metavar="FILE.json",
+                    help="restraint-guided sampling: a JSON object with the keys obstacles [[y_x, y_y, y_z, r, k]], pairs [[i, j, lo, "
+                         "hi, k]], anchors [[i, a_x, a_y, a_z, r, k]] shared by all molecules, in data units in the MODEL'S frame (the "
+                         "molecule's centre of mass is the origin); the gradient of the energy on the network's data prediction goes "
+                         "into every transition.  Combines with everything --steps combines with (--eta / --spacing / --solver, "
+                         "--guidance, --chain, --vary) except --known / --grow.  Mechanism only: which scale, schedule and clip help "
+                         "is for you to validate")
+    ap.add_argument("--restraint-scale", type=float, default=None, metavar="S", help="with --restraints: the scale (default 1)")
+    ap.add_argument("--restraint-schedule", choices=["score", "sigma"], default=None,
+                    help="with --restraints: the weight of transition k, nv0 sigma_t / alpha_t (score, default) or sigma_t")
+    ap.add_argument("--restraint-clip", type=float, default=None, metavar="C",
+                    help="with --restraints: the largest step per node in noise-prediction units (default: none)")
     args = ap.parse_args(argv)
+    if args.restraints is None and (args.restraint_scale is not None or args.restraint_schedule is not None
+                                    or args.restraint_clip is not None):
+        ap.error("--restraint-scale / --restraint-schedule / --restraint-clip need --restraints")
+    if args.restraints is not None:
+        if args.known is not None or args.grow is not None:
+            ap.error("--restraints does not combine with --known / --grow (inpainting re-centres on the known fragments)")
+        if args.score is not None or args.interpolate is not None:
+            ap.error("--restraints does not combine with --score / --interpolate")
+        if args.restraint_clip is not None and not args.restraint_clip > 0.0:
+            ap.error("--restraint-clip must be > 0")
+        if args.restraint_scale is not None and not math.isfinite(args.restraint_scale):
+            ap.error("--restraint-scale must be finite")
+        if args.restraint_scale is None:
+            args.restraint_scale = 1.0
     if args.record is not None and args.chain is None:
         ap.error("--record needs --chain")
     if args.chain is not None and args.chain < 1:
@@ -313,6 +340,10 @@ def main(argv=None) -> int:
     if world > 1:
         broadcast_model_weights(model, src=0)
     chain = {} if args.chain is None else {"keep_frames": args.chain, "record": args.record}
+    if args.restraints is not None:
+        from .restraints import Restraints
+        chain.update(restraints=Restraints.from_json(args.restraints), restraint_scale=args.restraint_scale,
+                     restraint_schedule=args.restraint_schedule, restraint_clip=args.restraint_clip)
 
     if args.score is not None:
         if world > 1:

@@ -366,6 +366,52 @@ int hd_chain_detach(hd_topology* topo);
 /* Number of times the topology's captured recording transition was instantiated (-1: null topology). */
 long long hd_chain_graph_builds(const hd_topology* topo);
 
+/* ---- Restraint-guided sampling (ABI 12, additive; no reference counterpart): at every transition of a path loop an energy U is
+ * evaluated on the network's data prediction and its gradient is added into the noise prediction; the update that follows -
+ * ancestral, eta < 1, multistep - and a record = "x0" frame read the changed eps^.  One more launch per transition (k_restrain_eps),
+ * between the (guided) network call and everything that reads eps^, inside the captured transition when use_graph is set.
+ * FRAME: coordinates are x = nv0 z_x in the model's frame, which has the centre of mass of the molecule's valid nodes at the
+ * origin.  Obstacles and anchors are given in that frame: the caller places them relative to where the molecule's centre sits.
+ * Tables, per molecule (every table has 1 row, shared by all molecules, or B rows; device or host pointers, fp32 / int32):
+ *   obs      [rows][P][5] = (y_x, y_y, y_z, r, k)     U_obs  = 1/2 sum_{i valid} sum_p k_p max(0, r_p - |x_i - y_p|)^2
+ *                                                     a row with r <= 0 or k <= 0 is padding
+ *   pair_idx [rows][Q][2], pair_f [rows][Q][3] = (lo, hi, k)
+ *                                                     U_pair = 1/2 sum_q k_q (max(0, d - hi)^2 + max(0, lo - d)^2), d = |x_i - x_j|
+ *   anc_idx  [rows][A],    anc_f [rows][A][5] = (a_x, a_y, a_z, r, k)
+ *                                                     U_anc  = 1/2 sum_a k_a max(0, |x_i - a| - r)^2
+ * A pair / anchor row whose node index is negative (-1: padding), >= N or masked in that molecule is inactive - not an error, sizes
+ * are drawn.  A term at distance exactly 0 contributes no gradient.
+ * The update of transition k with the row {alpha_t, sigma_t, lambda_k, clip_k} and the scale s_b of molecule b:
+ *   x^0_i   = nv0 (1 / alpha_t) (z_x,i - sigma_t eps_x,i)        fp32, the operations and the order of a record = "x0" frame
+ *   Delta_i = s_b lambda_k dU/dx_i (x^0), valid nodes            double; |Delta_i| > clip_k: scaled to length clip_k (inf: no clip)
+ *   Delta_i -= mean over the valid nodes of Delta                eps_x stays free of centre of mass
+ *   eps_x,i += Delta_i                                           one rounding to fp32; feature columns and masked rows untouched
+ * s_b lambda_k == 0: the molecule's workgroup writes nothing, and an entry whose Delta is exactly 0 keeps its bits.  Every sum has a
+ * fixed order that depends on (N, P, Q, A) alone: a sample depends on its id, mask, weights, schedule, path and its own rows only.
+ * hd_set_restraint: the rows4[K][4] (host) of the CURRENT path (hd_set_path*; every new path needs its own call, HD_E_STATE from
+ *   the loops otherwise).  HD_E_INVALID: K != the path's K, alpha_t <= 0, sigma_t < 0, a non-finite lambda_k, clip_k <= 0.
+ * hd_restraint_attach: copies the tables and scale[scale_rows] (stream-ordered) into buffers the topology owns; from now on
+ *   hd_sample_path and hd_sample_path_guided (fixed_mask == NULL) on this topology are restrained; hd_sample_path_inpaint and
+ *   guided calls with a fixed_mask are HD_E_INVALID while attached (inpainting re-centres on the known fragments: its frame
+ *   moves), as is mol_shape < N.  hd_sample_loop* ignore attached restraints, as they ignore chain sinks.
+ *   HD_E_INVALID: a row count other than 1 or B, negative P / Q / A, nv0 not positive, N * 3 floats beyond one workgroup's LDS.
+ * hd_restraint_detach: the launches, graphs and keys are again exactly those of a topology that never had restraints.
+ *   use_graph    the restrained transition lives in the slot of its unrestrained kind (plain, guided, recording) under a key that
+ *                tells the two apart: a restrained call followed by an unrestrained one rebuilds and gives the unrestrained bits.
+ *                Re-attaching tables of the same sizes, new scales, and hd_set_restraint with the same K are copies: the cached
+ *                graph replays (hd_path_graph_builds / hd_guided_graph_builds / hd_chain_graph_builds do not move).  A table that
+ *                outgrows its buffer, another row count or nv0 rebuild it once.
+ * hd_restrain_eps: the single update above on given tensors with a host row4; out may be eps itself, nothing else may overlap.
+ * hd_restraint_energy: out3[B][3] = (U_obs, U_pair, U_anc) in double for positions x[B][N][3] (fp32, data units) under the
+ *   attached tables and the topology's mask.  Both are stream-ordered and need attached restraints (HD_E_STATE otherwise). */
+int hd_set_restraint(hd_handle* h, int K, const float* rows4);
+int hd_restraint_attach(hd_topology* topo, const float* obs, int obs_rows, int P, const int* pair_idx, const float* pair_f,
+                        int pair_rows, int Q, const int* anc_idx, const float* anc_f, int anc_rows, int A, const float* scale,
+                        int scale_rows, float nv0, void* stream);
+int hd_restraint_detach(hd_topology* topo);
+int hd_restrain_eps(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4, float* out, void* stream);
+int hd_restraint_energy(hd_handle* h, hd_topology* topo, const float* x, double* out3, void* stream);
+
 /* ---- Scoring (ABI 12, additive; no reference counterpart beyond the one-timestep estimator, compute_loss with t0_always = True,
  * diffusion_qm9.py:530-699): the variational bound of GIVEN molecules with every term of a list evaluated, in the device loop.
  * For normalised data xh [B,N,D] and a term t in 1 .. T (s = t - 1):
