@@ -8,9 +8,13 @@ plus the EDM-style signature named by the north star,
   EnVariationalDiffusion.sample(n_samples, n_nodes, node_mask, edge_mask, context, fix_noise=False)
   (endiffusion/equivariant_diffusion/en_diffusion.py:634-667; dead code in the reference).
 
-The 1000-step loop runs inside libhierdiff_hip.so (hd_sample_loop): about 45 kernels per step at the headline batch
-(DESIGN.md section 5), no host sync, by default replayed from one captured hipGraph that is cached per
-topology.  The loss / NLL value of the training half is available too (compute_loss, nll, forward).
+Every reverse chain runs inside libhierdiff_hip.so: the plain 1000-step loop (hd_sample_loop; inpainting: hd_sample_loop_inpaint)
+or, for few-step, multistep, guided, restrained and recorded calls, the loop over a path of grid points (hd_sample_path,
+hd_sample_path_inpaint, hd_sample_path_guided) - about 45 kernels per step at the headline batch, no host sync,
+by default replayed from one captured hipGraph that is cached per topology.  Every sampling entry point is the same four steps:
+the keywords resolved on the host (`plan.plan`), the device state (`_device_state`), the transitions (`_run`, the one place that
+picks among the five loops) and the decode (`_decode`).  The loss / NLL value of the training half is available too (compute_loss,
+nll, forward).
 """
 from __future__ import annotations
 
@@ -28,6 +32,7 @@ from .dynamics import EGNN_dynamics_QM9, Topology, _ptr, _stream
 from .geom_stats import GEOM_FRAGMENT_HISTOGRAM
 from .noise_model import (GammaNetwork, PredefinedNoiseSchedule, decode_coefficients, evaluate_gamma,
                           schedule_tables, sigma_and_alpha_t_given_s, step_coefficients)
+from .plan import KEYWORDS, full_path, given, latent_path, plan as make_plan, unsupported
 
 try:  # the reference class is a LightningModule; use it when the package exists so the module nests
     import pytorch_lightning as _pl  # type: ignore
@@ -610,89 +615,52 @@ class DiffusionQM9(_Base):
             self._sched_key = key
         return self._sched
 
+    def _plan(self, what: str, kind: str = "full", **kw):
+        """The host side of the sampling call `what` (`plan.plan`): its keywords resolved once, before the GPU is touched."""
+        return make_plan(self, what, kind, **kw)
+
     def _resolve_path(self, steps=None, eta=None, spacing=None, timesteps=None, inpaint: bool = False, solver=None,
                       lower_order_final=None):
-        """The keywords of the sampling entry points (None: the model's `sample_*` attributes) -> None for the plain loop, or
-        (path, eta); with solver "dpm2m" (path, `paths.Multistep`) - always the path loop, eta = 0 whatever `sample_eta` says.
-        Pure host arithmetic: every ValueError is raised before the GPU is touched."""
-        from . import paths
-        if steps is None and timesteps is None:
-            steps, timesteps = self.sample_steps, self.sample_timesteps
-        ms = paths.check_solver(self.sample_solver if solver is None else solver, eta,
-                                self.sample_lower_order_final if lower_order_final is None else lower_order_final)
-        if ms is not None:
-            if inpaint:
-                raise ValueError("inpainting takes ancestral steps only (eta = 1), not solver 'dpm2m': the replacement method "
-                                 "re-noises the known part with the posterior's own variance")
-            spacing = self.sample_spacing if spacing is None else spacing
-            if spacing not in paths.SPACINGS:
-                raise ValueError(f"spacing must be one of {paths.SPACINGS}, got {spacing!r}")
-            return paths.build_path(self.T, steps, spacing, timesteps), ms
-        eta = paths.check_eta(self.sample_eta if eta is None else eta)
-        spacing = self.sample_spacing if spacing is None else spacing
-        if spacing not in paths.SPACINGS:
-            raise ValueError(f"spacing must be one of {paths.SPACINGS}, got {spacing!r}")
-        if steps is not None and timesteps is not None:
-            raise ValueError("give either steps or timesteps, not both")
-        if inpaint and eta < 1.0:
-            raise ValueError("inpainting takes ancestral steps only (eta = 1): the replacement method re-noises the known part "
-                             "with the posterior's own variance")
-        if steps is None and timesteps is None and eta == 1.0 and not self._force_path_loop:
-            return None
-        path = paths.build_path(self.T, steps, spacing, timesteps)
-        if len(path) == self.T + 1 and eta == 1.0 and not self._force_path_loop:
-            return None                  # the identity path with ancestral steps IS the plain loop
-        return path, eta
+        """The path keywords alone (None: the model's `sample_*` attributes) -> None for the plain loop, or (path, eta); with solver
+        "dpm2m" (path, `paths.Multistep`).  A view of `plan.full_path`."""
+        return full_path(self, steps, eta, spacing, timesteps, inpaint, solver, lower_order_final)
+
+    def _upload_path(self, tabs, key, build, upload):
+        """The path tables on the handle, cached per (schedule table, key): `build()` computes them, `upload(tables)` sets them.  One
+        cache for both directions (hd_set_path / hd_set_path_multistep and hd_set_path_up fill the same tables): whichever was set
+        last is the one that is cached.  `_chain_open` and `_restrain_open` key their uploads on the identity of the cached tables."""
+        hit = self.__dict__.get("_path_cache")
+        if hit is None or hit[0] is not tabs or hit[1] != key:
+            pt = build()
+            self._path_cache = None
+            upload(pt)
+            self._path_cache = (tabs, key, pt)
+        return self._path_cache[2]
 
     def _path_tables(self, handle, tabs, path, eta):
         """Rows of `path` from the gamma grid of `_schedule`, uploaded to the handle (hd_set_path; hd_set_path_multistep when `eta`
         is a `paths.Multistep`) once per (table, path, eta or solver with its lower_order_final)."""
         from . import paths
         ms = isinstance(eta, paths.Multistep)
-        key = (tuple(path), ("dpm2m", bool(eta.lower_order_final)) if ms else float(eta))
-        hit = self.__dict__.get("_path_cache")
-        if hit is None or hit[0] is not tabs or hit[1] != key:
-            pt = paths.path_tables(tabs["gamma"], path, eta)
-            t_idx = np.ascontiguousarray(pt["t_idx"].numpy(), dtype=np.int32)
-            s_idx = np.ascontiguousarray(pt["s_idx"].numpy(), dtype=np.int32)
-            coef = np.ascontiguousarray(pt["coef"].numpy(), dtype=np.float32)
-            cip = None if pt["coef_inpaint"] is None else np.ascontiguousarray(pt["coef_inpaint"].numpy(), dtype=np.float32)
-            self._path_cache = None
+        ip, fp = (lambda a: np.ascontiguousarray(a.numpy(), dtype=np.int32).ctypes.data_as(C.POINTER(C.c_int)),
+                  lambda a: None if a is None else np.ascontiguousarray(a.numpy(), dtype=np.float32).ctypes.data_as(C.POINTER(C.c_float)))
+
+        def upload(pt):
             if ms:
-                _lib.check(_lib.load().hd_set_path_multistep(
-                    handle, pt["K"], t_idx.ctypes.data_as(C.POINTER(C.c_int)), s_idx.ctypes.data_as(C.POINTER(C.c_int)),
-                    coef.ctypes.data_as(C.POINTER(C.c_float))), "hd_set_path_multistep")
+                _lib.check(_lib.load().hd_set_path_multistep(handle, pt["K"], ip(pt["t_idx"]), ip(pt["s_idx"]), fp(pt["coef"])),
+                           "hd_set_path_multistep")
             else:
-                _lib.check(_lib.load().hd_set_path(
-                    handle, pt["K"], t_idx.ctypes.data_as(C.POINTER(C.c_int)), s_idx.ctypes.data_as(C.POINTER(C.c_int)),
-                    coef.ctypes.data_as(C.POINTER(C.c_float)), pt["form"],
-                    None if cip is None else cip.ctypes.data_as(C.POINTER(C.c_float))), "hd_set_path")
-            self._path_cache = (tabs, key, pt)
-        return self._path_cache[2]
+                _lib.check(_lib.load().hd_set_path(handle, pt["K"], ip(pt["t_idx"]), ip(pt["s_idx"]), fp(pt["coef"]), pt["form"],
+                                                   fp(pt["coef_inpaint"])), "hd_set_path")
+
+        return self._upload_path(tabs, (tuple(path), ("dpm2m", bool(eta.lower_order_final)) if ms else float(eta)),
+                                 lambda: paths.path_tables(tabs["gamma"], path, eta), upload)
 
     # ------------------------------------------------------------------ recording a trajectory (the reference's sample_chain)
-    def _chain_check(self, keep_frames, record, what: str, pocket=None, needs_noise: bool = True):
-        """None when nothing is recorded (keep_frames None), else the library's code of `record`: 0 for "z" (the default: the state
-        behind every kept transition), 1 for "x0" (its data prediction).  Pure host checks, raised before the GPU is touched."""
-        if keep_frames is None:
-            if record is not None:
-                raise ValueError(f"{what}: record={record!r} records nothing without keep_frames")
-            return None
-        if record not in (None, "z", "x0"):
-            raise ValueError(f"{what}: record must be 'z' or 'x0', got {record!r}")
-        if isinstance(keep_frames, bool) or not isinstance(keep_frames, (int, np.integer)):
-            raise ValueError(f"{what}: keep_frames must be an integer, got {keep_frames!r}")
-        if self.pocket or pocket is not None:
-            raise NotImplementedError(f"{what}: recording a chain is not supported for pocket models (whole molecules only)")
-        if getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics":
-            raise NotImplementedError(f"{what}: recording a chain runs inside the library's loop: mode 'gnn_dynamics' is not supported")
-        if needs_noise and self.noise_mode == "torch":
-            raise NotImplementedError(f"{what}: recording a chain runs inside the library's loop: noise_mode 'torch' is not supported")
-        return 1 if record == "x0" else 0
-
-    def _chain_open(self, handle, topo, tabs, cf, what: int, B: int, N: int, dev):
-        """The sink [keep, B, N, D] of a recording call, attached to `topo` (hd_chain_attach) behind the tables of the path that
-        `_path_tables` has just set (hd_set_chain, once per (path tables, frame table)).  The caller detaches (`_chain_close`)."""
+    def _chain_open(self, handle, topo, tabs, cf, what: int, B: int, N: int, dev, chain=None):
+        """The sink [keep, B, N, D] of a recording call (`chain`: the one an earlier piece of the same chain wrote to), attached to
+        `topo` (hd_chain_attach) behind the tables of the path that `_path_tables` has just set (hd_set_chain, once per (path
+        tables, frame table)).  The caller detaches (hd_chain_detach)."""
         pt = self._path_cache[2]
         keep = len(cf.frame_t)
         key = (tuple(cf.frame_of), keep)
@@ -704,18 +672,15 @@ class DiffusionQM9(_Base):
             _lib.check(_lib.load().hd_set_chain(handle, int(fo.shape[0]), fo.ctypes.data_as(C.POINTER(C.c_int)),
                                                 als.ctypes.data_as(C.POINTER(C.c_float)), keep), "hd_set_chain")
             self._chain_cache = (pt, key)
-        chain = torch.zeros((keep, B, N, self.n_dims + self.in_node_nf), device=dev, dtype=torch.float32)
+        if chain is None:
+            chain = torch.zeros((keep, B, N, self.n_dims + self.in_node_nf), device=dev, dtype=torch.float32)
         _lib.check(_lib.load().hd_chain_attach(topo.ptr, chain.data_ptr(), keep, int(what), float(self.norm_values[0]),
                                                float(self.norm_values[1]), float(self.norm_biases[1] or 0.0)), "hd_chain_attach")
         return chain
 
-    @staticmethod
-    def _chain_close(topo):
-        _lib.check(_lib.load().hd_chain_detach(topo.ptr), "hd_chain_detach")
-
     def _restrain_open(self, handle, topo, tabs, rr, B: int, dev):
         """Attach the restraints of a resolved call (`restraints.Resolved`) to `topo` behind the rows of the path that `_path_tables`
-        has just set (hd_set_restraint, once per (path tables, schedule, clip)).  The caller detaches (`_restrain_close`)."""
+        has just set (hd_set_restraint, once per (path tables, schedule, clip)).  The caller detaches (hd_restraint_detach)."""
         from . import restraints
         pt = self._path_cache[2]
         key = rr.key()
@@ -732,20 +697,10 @@ class DiffusionQM9(_Base):
         rr.rs._model = weakref.ref(self)
         rr.rs.attach(topo, rr.scale, float(self.norm_values[0]), dev, _stream(dev))
 
-    @staticmethod
-    def _restrain_close(topo):
-        _lib.check(_lib.load().hd_restraint_detach(topo.ptr), "hd_restraint_detach")
-
-    def _chain_times(self, keep_frames, t_start=None, inpaint: bool = False, steps=None, eta=None, spacing=None, timesteps=None,
-                     solver=None, lower_order_final=None, **_):
-        """[keep] the grid index every frame of a recording call has arrived at (`paths.chain_frames`): host arithmetic only."""
-        from . import paths
-        if t_start is not None:
-            path = self._latent_path(t_start, steps, eta, spacing, timesteps, solver, lower_order_final)[1]
-        else:
-            pe = self._resolve_path(steps, eta, spacing, timesteps, inpaint=inpaint, solver=solver, lower_order_final=lower_order_final)
-            path = paths.build_path(self.T) if pe is None else pe[0]
-        return torch.tensor(paths.chain_frames(len(path) - 1, keep_frames, path).frame_t, dtype=torch.int64)
+    def _chain_times(self, keep_frames, t_start=None, inpaint: bool = False, **few):
+        """[keep] the grid index every frame of a recording call has arrived at (`Plan.chain_t`): host arithmetic only."""
+        kind = "latent" if t_start is not None else "inpaint" if inpaint else "full"
+        return self._plan("chain", kind, t_start=t_start, keep_frames=keep_frames, **few).chain_t
 
     def _chain_into(self, results, chain, sizes, chain_t):
         """'chain_x' [keep, n_i, 3], 'chain_h' [keep, n_i, F], 'chain_t' [keep] into every molecule's dict (CPU, trimmed)."""
@@ -878,13 +833,6 @@ class DiffusionQM9(_Base):
             ctx_u = gd.context.to(dev, torch.float32)
         return AttrDict(ctx_u=ctx_u.reshape(B * N, C_).contiguous(), w=gd.w.to(dev).contiguous(), rows=gd.rows, phi=gd.rescale)
 
-    def _guided_path(self, h, topo, z, ctx, g, k_lo, k_hi, rx, rh, rows, seed, base, stream, fixed=None, known=None, R=0):
-        """hd_sample_path_guided on z in place (g: `_guide_device`); fixed / known / R: the inpainting form."""
-        _lib.check(_lib.load().hd_sample_path_guided(
-            h, topo.ptr, z.data_ptr(), ctx.data_ptr(), g.ctx_u.data_ptr(), g.w.data_ptr(), g.rows, g.phi, int(k_lo), int(k_hi),
-            _ptr(rx), _ptr(rh), rows, seed, base, int(self.use_graph), _ptr(fixed), _ptr(known), int(R), stream),
-            "hd_sample_path_guided")
-
     def _decode_eps(self, topo, z, ctx, g=None):
         """The network call of the final decode (t = 0); guided the way the loop's calls are: two forwards, hd_guide_combine."""
         dev = z.device
@@ -896,6 +844,88 @@ class DiffusionQM9(_Base):
         _lib.check(_lib.load().hd_guide_combine(self._lib_handle(synced=True), topo.ptr, eps.data_ptr(), eps_u.data_ptr(),
                                                 g.w.data_ptr(), g.rows, g.phi, eps.data_ptr(), _stream(dev)), "hd_guide_combine")
         return eps
+
+    # ------------------------------------------------------------------ the three device steps of every sampling call
+    def _device_state(self, node_mask, edge_mask, context, B, N, pl=None, what: str = "sampling", needs_context: bool = True,
+                      inpaint: bool = False):
+        """The first lines of a call that need the GPU: handle, schedule (`inpaint`: with the inpainting rows), the tables of the
+        plan's path, topology, context rows [B*N, C] and the guided call's second context.  Entry points add their extras (pocket:
+        `tail`, `topo_loop`; inpainting: `_inpaint_setup`) on top of it."""
+        dev = node_mask.device
+        if dev.type != "cuda":
+            raise _lib.HierDiffHipError(f"{what} runs only on an MI355X (no CPU fallback)")
+        h = self._lib_handle()
+        tabs = self._schedule(rows=B)
+        if inpaint:
+            self._inpaint_schedule(h, tabs)
+        if pl is not None and pl.path is not None:
+            self._path_tables(h, tabs, pl.path, pl.eta)
+        topo = self.dynamics.topology(node_mask, edge_mask, B, N)
+        ctx = None
+        if self.dynamics.context_node_nf > 0 and (needs_context or context is not None):
+            if context is None:
+                raise ValueError("context required")
+            ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
+        g = None if pl is None or pl.guidance is None else self._guide_device(pl.guidance, node_mask, dev)
+        return AttrDict(h=h, tabs=tabs, topo=topo, topo_loop=topo, tail=None, ctx=ctx, g=g, chain=None, B=B, N=N, dev=dev,
+                        stream=_stream(dev))
+
+    def _run(self, st, pl, z, k_lo, k_hi, noise, inpaint=None):
+        """Transitions k_lo .. k_hi-1 of the plan `pl` (positions counted from the start of the chain) on z [B,N,D] in place; returns
+        (z, chain - the sink of a recording plan, kept in `st` for the next piece - or None).  `noise` = (randn_x, randn_h, rows,
+        seed, sample id base): injected rows, or None, None and the generator's key.  `inpaint` = (fixed u8 [B*N], known xh, R).
+        Restraints, then the sink, are attached to the topology for the time of the loop.  The one place that picks the loop:
+        guided -> hd_sample_path_guided; a path -> hd_sample_path(_inpaint); else the every-step hd_sample_loop(_inpaint), whose
+        steps count down from T."""
+        lib, topo = _lib.load(), st.topo_loop
+        rx, rh, rows, seed, base = noise
+        fixed, known, R = inpaint if inpaint is not None else (None, None, 0)
+        zz = z if st.tail is None else torch.cat([z, st.tail], dim=1).contiguous()      # a pocket's fixed rows ride along
+        mol = -1 if st.tail is None else st.N
+        common = (_ptr(rx), _ptr(rh), rows, seed, base, int(self.use_graph))
+        try:
+            if pl.restraints is not None:
+                self._restrain_open(st.h, topo, st.tabs, pl.restraints, st.B, st.dev)
+            if pl.frames is not None:
+                st.chain = self._chain_open(st.h, topo, st.tabs, pl.frames, pl.record, st.B, st.N, st.dev, st.chain)
+            if st.g is not None:
+                _lib.check(lib.hd_sample_path_guided(st.h, topo.ptr, zz.data_ptr(), st.ctx.data_ptr(), st.g.ctx_u.data_ptr(),
+                                                     st.g.w.data_ptr(), st.g.rows, st.g.phi, int(k_lo), int(k_hi), *common,
+                                                     _ptr(fixed), _ptr(known), int(R), st.stream), "hd_sample_path_guided")
+            elif inpaint is not None:
+                fn, name, lo, hi = (lib.hd_sample_path_inpaint, "hd_sample_path_inpaint", k_lo, k_hi) if pl.path is not None else \
+                    (lib.hd_sample_loop_inpaint, "hd_sample_loop_inpaint", pl.K - k_lo, pl.K - k_hi)
+                _lib.check(fn(st.h, topo.ptr, zz.data_ptr(), _ptr(st.ctx), -1, int(lo), int(hi), *common, fixed.data_ptr(),
+                              known.data_ptr(), int(R), st.stream), name)
+            else:
+                fn, name, lo, hi = (lib.hd_sample_path, "hd_sample_path", k_lo, k_hi) if pl.path is not None else \
+                    (lib.hd_sample_loop, "hd_sample_loop", pl.K - k_lo, pl.K - k_hi)
+                _lib.check(fn(st.h, topo.ptr, zz.data_ptr(), _ptr(st.ctx), mol, int(lo), int(hi), *common, st.stream), name)
+        finally:
+            if pl.frames is not None:
+                _lib.check(lib.hd_chain_detach(topo.ptr), "hd_chain_detach")
+            if pl.restraints is not None:
+                pl.restraints.rs.detach(topo)
+        return (zz if st.tail is None else zz[:, :st.N].contiguous()), st.chain
+
+    def _decode(self, st, z, node_mask, edge_mask, fix_noise, noise, chain=None, inpaint=None, eps=None):
+        """(x, h) of z_0 - and `chain` with cat(x, h) as its frame 0 - : the network call at t = 0 (guided as the loop's are; `eps`:
+        the caller has made it) and the final decode.  `noise`: the sample id base (the generator's draw T + 1) or an injected
+        (randn_x, randn_h) pair, None = torch.randn.  `inpaint` = (fixed u8, x_known, h_known): the known rows are put back."""
+        if eps is None:
+            eps = self._decode_eps(st.topo, z, st.ctx, st.g)
+        philox = (int(noise), self.T + 1) if isinstance(noise, (int, np.integer)) else None
+        x, h = self._final_decode(z, eps, node_mask, edge_mask, st.tabs["decode"].numpy(), fix_noise, None if philox else noise,
+                                  philox=philox)
+        if inpaint is not None:
+            x, h = x.contiguous(), h.contiguous()
+            _lib.check(_lib.load().hd_inpaint_decode_fix(st.h, st.topo.ptr, inpaint[0].data_ptr(), inpaint[1].data_ptr(),
+                                                         inpaint[2].data_ptr(), x.data_ptr(), h.data_ptr(), st.stream),
+                       "hd_inpaint_decode_fix")
+        if chain is None:
+            return x, h
+        chain[0] = torch.cat([x, h], dim=2)
+        return x, h, chain
 
     # ------------------------------------------------------------------ full reverse process
     @torch.no_grad()
@@ -960,49 +990,22 @@ class DiffusionQM9(_Base):
         residue nodes: appended to z for every network call with a block-diagonal edge mask and never updated
         (diffusion_qm9.py:362-371,381-382); the final decode sees the molecule alone (:386-387)."""
         dev = node_mask.device
-        pe = self._resolve_path(steps, eta, spacing, timesteps, solver=solver, lower_order_final=lower_order_final)
-        from . import guidance, paths
-        gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, int(node_mask.shape[0]), int(node_mask.shape[1]),
-                              "sample_from_masks", pocket, needs_noise=raw_noises is None)
-        if gd is not None and context is None:
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        pl = self._plan("sample_from_masks", pocket=pocket, injected=raw_noises is not None, B=B, N=N, **given(locals()))
+        if pl.guidance is not None and context is None:
             raise ValueError("context required")
-        if gd is not None and pe is None:            # a guided chain always runs in the path loop: the identity path, ancestral steps
-            pe = (paths.build_path(self.T), 1.0)
-        from . import restraints as _rs
-        rr = _rs.resolve(self, restraints, restraint_scale, restraint_schedule, restraint_clip, int(node_mask.shape[0]),
-                         "sample_from_masks", pocket, needs_noise=raw_noises is None)
-        if rr is not None and pe is None:            # so does a restrained one
-            pe = (paths.build_path(self.T), 1.0)
-        what = self._chain_check(keep_frames, record, "sample_from_masks", pocket, needs_noise=raw_noises is None)
-        cf = None
-        if what is not None:                         # so does a recorded one
-            pe = (paths.build_path(self.T), 1.0) if pe is None else pe
-            cf = paths.chain_frames(len(pe[0]) - 1, keep_frames, pe[0])
-        if pe is not None and (getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics" or
-                               (self.noise_mode == "torch" and raw_noises is None)):
+        gnn = getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics"
+        if pl.path is not None and (gnn or (self.noise_mode == "torch" and raw_noises is None)):
             raise NotImplementedError("few-step sampling runs inside the library's loop: mode 'gnn_dynamics' and noise_mode 'torch' "
                                       "(step-by-step Python loops) take the full chain only")
-        if dev.type != "cuda":
-            raise _lib.HierDiffHipError("sampling runs only on an MI355X (no CPU fallback)")
-        B, N = node_mask.shape[0], node_mask.shape[1]
-        D = self.n_dims + self.in_node_nf
-        lib = _lib.load()
-        h = self._lib_handle()
-        tabs = self._schedule(rows=B)
-        K = self.T if pe is None else self._path_tables(h, tabs, *pe)["K"]
-        topo = self.dynamics.topology(node_mask, edge_mask, B, N)
-        ctx = None
-        if self.dynamics.context_node_nf > 0:
-            if context is None:
-                raise ValueError("context required")
-            ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
-        topo_loop, tail = topo, None
+        st = self._device_state(node_mask, edge_mask, context, B, N, pl)
+        lib, h, topo, stream, K, T = _lib.load(), st.h, st.topo, st.stream, pl.K, self.T
         if pocket is not None:
-            if ctx is not None or self.noise_mode == "torch":
+            if st.ctx is not None or self.noise_mode == "torch":
                 raise NotImplementedError("pocket conditioning: context=None and library/injected noise only")
             p_pos, p_feat, p_nm, p_em = pocket
             P = p_pos.shape[1]
-            tail = torch.cat([p_pos.to(dev, torch.float32), p_feat.to(dev, torch.float32)], dim=-1)
+            st.tail = torch.cat([p_pos.to(dev, torch.float32), p_feat.to(dev, torch.float32)], dim=-1)
             nmb = node_mask.to(torch.bool)
             em_mol = edge_mask.to(torch.bool).reshape(B, N, N) if edge_mask is not None else \
                 (nmb & nmb.transpose(1, 2) & ~torch.eye(N, dtype=torch.bool, device=dev)[None])
@@ -1010,48 +1013,10 @@ class DiffusionQM9(_Base):
             self._em_cat = torch.zeros(B, N + P, N + P, dtype=torch.bool, device=dev)
             self._em_cat[:, :N, :N] = em_mol
             self._em_cat[:, N:, N:] = p_em.to(dev).bool()
-            topo_loop = self.dynamics.topology(self._nm_cat, self._em_cat, B, N + P)
-        stream = _stream(dev)
-        g = None if gd is None else self._guide_device(gd, node_mask, dev)
-
-        chain = []
-
-        def run_loop(z_mol, rx, rh, rows, seed, base):
-            """`run_steps`; a recording call attaches its sink to the topology for the time of the loop."""
-            if cf is None and rr is None:
-                return run_steps(z_mol, rx, rh, rows, seed, base)
-            try:
-                if rr is not None:
-                    self._restrain_open(h, topo_loop, tabs, rr, B, dev)
-                if cf is not None:
-                    chain.append(self._chain_open(h, topo_loop, tabs, cf, what, B, N, dev))
-                return run_steps(z_mol, rx, rh, rows, seed, base)
-            finally:
-                if cf is not None:
-                    self._chain_close(topo_loop)
-                if rr is not None:
-                    self._restrain_close(topo_loop)
-
-        def run_steps(z_mol, rx, rh, rows, seed, base):
-            """T posterior steps on [B,N,D]; with a pocket the fixed rows ride along behind the molecule."""
-            zz = z_mol if tail is None else torch.cat([z_mol, tail], dim=1).contiguous()
-            if g is not None:            # guided: the K transitions of the path, two network calls each
-                self._guided_path(h, topo_loop, zz, ctx, g, 0, K, rx, rh, rows, seed, base, stream)
-                return zz
-            if pe is not None:           # the K transitions of the path
-                _lib.check(lib.hd_sample_path(h, topo_loop.ptr, zz.data_ptr(), _ptr(ctx), -1 if tail is None else N, 0, K,
-                                              _ptr(rx), _ptr(rh), rows, seed, base, int(self.use_graph), stream),
-                           "hd_sample_path")
-                return zz if tail is None else zz[:, :N].contiguous()
-            _lib.check(lib.hd_sample_loop(h, topo_loop.ptr, zz.data_ptr(), _ptr(ctx), -1 if tail is None else N, T, 0,
-                                          _ptr(rx), _ptr(rh), rows, seed, base, int(self.use_graph), stream),
-                       "hd_sample_loop")
-            return zz if tail is None else zz[:, :N].contiguous()
-
+            st.topo_loop = self.dynamics.topology(self._nm_cat, self._em_cat, B, N + P)
         nb = 1 if fix_noise else B
-        T = self.T
-        z = torch.empty((B, N, D), device=dev, dtype=torch.float32)
-        gnn = getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics"
+        z = torch.empty((B, N, self.n_dims + self.in_node_nf), device=dev, dtype=torch.float32)
+        chain = None
         if gnn and (pocket is not None or z_init is not None):
             raise NotImplementedError("mode 'gnn_dynamics': plain sampling only (no pocket, no z_init)")
         if gnn and raw_noises is not None:
@@ -1064,7 +1029,7 @@ class DiffusionQM9(_Base):
                 gm = None if gg is None else (gg[s_].expand(B, 1), gg[s_ + 1].expand(B, 1))
                 z = self.sample_p_zs_given_zt(s_array / T, (s_array + 1) / T, z, node_mask, edge_mask, context, fix_noise=fix_noise,
                                               mol_shape=N, raw_noise=raw_noises[1 + i], gammas=gm)
-            final_raw = tuple(r.to(dev, torch.float32).contiguous() for r in raw_noises[T + 1])
+            final = tuple(r.to(dev, torch.float32).contiguous() for r in raw_noises[T + 1])
         elif raw_noises is not None:
             assert len(raw_noises) == K + 2, "need T+2 raw noise pairs (few-step sampling: steps + 2)"
             rx = [r[0].to(dev, torch.float32).contiguous() for r in raw_noises]
@@ -1073,41 +1038,28 @@ class DiffusionQM9(_Base):
                                     z.data_ptr(), stream), "hd_noise")
             step_x = torch.stack(rx[1:K + 1]).contiguous()
             step_h = torch.stack(rh[1:K + 1]).contiguous()
-            z = run_loop(z, step_x, step_h, step_x.shape[1], 0, 0)
-            final_raw = (rx[K + 1], rh[K + 1])
+            z, chain = self._run(st, pl, z, 0, K, (step_x, step_h, step_x.shape[1], 0, 0))
+            final = (rx[K + 1], rh[K + 1])
         elif self.noise_mode == "torch" or gnn:
             z = self.sample_combined_position_feature_noise(nb, N, node_mask)
             if nb == 1 and B > 1:
                 z = z.expand(B, -1, -1).contiguous()
-            em = edge_mask
             for s in reversed(range(0, T)):
                 s_array = torch.full((B, 1), fill_value=s, device=dev)
-                t_array = s_array + 1
-                z = self.sample_p_zs_given_zt(s_array / T, t_array / T, z, node_mask, em, context,
+                z = self.sample_p_zs_given_zt(s_array / T, (s_array + 1) / T, z, node_mask, edge_mask, context,
                                               fix_noise=fix_noise, mol_shape=N)
-            final_raw = None
+            final = None                                 # torch.randn draws
         else:
             if z_init is not None:
                 z.copy_(z_init)
             else:
                 _lib.check(lib.hd_noise(h, topo.ptr, None, None, nb, self.seed, sample_id_base, 0, int(fix_noise),
                                         z.data_ptr(), stream), "hd_noise")
-            z = run_loop(z, None, None, nb, self.seed, sample_id_base)
-            # decode noise: draw T+1 of the same counter stream, materialised through hd_noise's raw form
-            final_raw = "philox"
+            z, chain = self._run(st, pl, z, 0, K, (None, None, nb, self.seed, sample_id_base))
+            final = int(sample_id_base)                  # decode noise: draw T+1 of the same counter stream
         self._check_mean_zero(z[:, :, :self.n_dims], node_mask)
-        zeros = torch.zeros((B, 1), device=dev)
-        eps = self.phi(z, zeros, node_mask, edge_mask, context) if gnn else self._decode_eps(topo, z, ctx, g)
-        coef3 = tabs["decode"].numpy()
-        if final_raw == "philox":
-            x, hfeat = self._final_decode(z, eps, node_mask, edge_mask, coef3, fix_noise, None,
-                                          philox=(sample_id_base, T + 1))
-        else:
-            x, hfeat = self._final_decode(z, eps, node_mask, edge_mask, coef3, fix_noise, final_raw)
-        if cf is not None:
-            chain[0][0] = torch.cat([x, hfeat], dim=2)
-            return x, hfeat, chain[0]
-        return x, hfeat
+        eps = self.phi(z, torch.zeros((B, 1), device=dev), node_mask, edge_mask, context) if gnn else None
+        return self._decode(st, z, node_mask, edge_mask, fix_noise, final, chain, eps=eps)
 
     @torch.no_grad()
     def path_steps(self, z, node_mask, edge_mask=None, context=None, *, steps=None, eta=None, spacing=None, timesteps=None,
@@ -1122,52 +1074,18 @@ class DiffusionQM9(_Base):
         topology (the masks).  A call with k_lo > 0 must therefore continue the previous call on the same masks and the same path
         exactly where that call ended (its k_hi); a piece-wise chain then gives the bits of the whole.  Anything else - fresh masks,
         another path or solver in between, a gap - raises HierDiffHipError (HD_E_STATE) instead of using a stale prediction."""
-        force = self._force_path_loop
-        self._force_path_loop = True                 # also the identity path goes through hd_sample_path here
-        try:
-            path, e = self._resolve_path(steps, eta, spacing, timesteps, solver=solver, lower_order_final=lower_order_final)
-        finally:
-            self._force_path_loop = force
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        pl = self._plan("path_steps", force_path=True, B=B, N=N, **given(locals()))       # also the identity path goes through hd_sample_path here
         if getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics" or self.noise_mode == "torch":
             raise NotImplementedError("few-step sampling: mode 'gnn_dynamics' and noise_mode 'torch' are not supported")
-        K = len(path) - 1
-        k_hi = K if k_hi is None else int(k_hi)
-        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
-        if tuple(z.shape) != (B, N, self.n_dims + self.in_node_nf) or not (0 <= int(k_lo) <= k_hi <= K):
+        k_hi = pl.K if k_hi is None else int(k_hi)
+        if tuple(z.shape) != (B, N, self.n_dims + self.in_node_nf) or not (0 <= int(k_lo) <= k_hi <= pl.K):
             raise ValueError("z must be [B, N, 3 + F] and 0 <= k_lo <= k_hi <= steps")
-        from . import guidance
-        gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, B, N, "path_steps")
-        if gd is not None and context is None:
+        if pl.guidance is not None and context is None:
             raise ValueError("context required")
-        from . import restraints as _rs
-        rr = _rs.resolve(self, restraints, restraint_scale, restraint_schedule, restraint_clip, B, "path_steps")
-        dev = node_mask.device
-        if dev.type != "cuda":
-            raise _lib.HierDiffHipError("sampling runs only on an MI355X (no CPU fallback)")
-        h = self._lib_handle()
-        tabs = self._schedule(rows=B)
-        self._path_tables(h, tabs, path, e)
-        topo = self.dynamics.topology(node_mask, edge_mask, B, N)
-        ctx = None
-        if self.dynamics.context_node_nf > 0:
-            if context is None:
-                raise ValueError("context required")
-            ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
-        z = z.detach().to(dev, torch.float32).clone().contiguous()
-        if rr is not None:
-            self._restrain_open(h, topo, tabs, rr, B, dev)
-        try:
-            if gd is not None:
-                self._guided_path(h, topo, z, ctx, self._guide_device(gd, node_mask, dev), k_lo, k_hi, None, None,
-                                  1 if fix_noise else B, self.seed, sample_id_base, _stream(dev))
-                return z
-            _lib.check(_lib.load().hd_sample_path(h, topo.ptr, z.data_ptr(), _ptr(ctx), -1, int(k_lo), k_hi, None, None,
-                                                  1 if fix_noise else B, self.seed, sample_id_base, int(self.use_graph), _stream(dev)),
-                       "hd_sample_path")
-            return z
-        finally:
-            if rr is not None:
-                self._restrain_close(topo)
+        st = self._device_state(node_mask, edge_mask, context, B, N, pl)
+        z = z.detach().to(st.dev, torch.float32).clone().contiguous()
+        return self._run(st, pl, z, k_lo, k_hi, (None, None, 1 if fix_noise else B, self.seed, sample_id_base))[0]
 
     # ------------------------------------------------------------------ scoring: every term of the bound (no reference counterpart)
     def _nll_tables(self, handle, tabs, t_list):
@@ -1319,22 +1237,17 @@ class DiffusionQM9(_Base):
 
     # ------------------------------------------------------------------ editing given molecules (no reference counterpart)
     def _up_tables(self, handle, tabs, path):
-        """Rows of the ascending `path` from the gamma grid of `_schedule`, uploaded to the handle (hd_set_path_up).  The tables are
-        the ones hd_set_path fills, so the two directions share `_path_cache`: whichever was set last is the one that is cached."""
+        """Rows of the ascending `path` from the gamma grid of `_schedule`, uploaded to the handle (hd_set_path_up): the tables that
+        hd_set_path fills, so the two directions share one cache (`_upload_path`)."""
         from . import paths
-        key = (tuple(path), "up")
-        hit = self.__dict__.get("_path_cache")
-        if hit is None or hit[0] is not tabs or hit[1] != key:
-            ut = paths.up_tables(tabs["gamma"], path)
-            u = np.ascontiguousarray(ut["from_idx"].numpy(), dtype=np.int32)
-            v = np.ascontiguousarray(ut["to_idx"].numpy(), dtype=np.int32)
+        ip = lambda a: np.ascontiguousarray(a.numpy(), dtype=np.int32).ctypes.data_as(C.POINTER(C.c_int))
+
+        def upload(ut):
             coef = np.ascontiguousarray(ut["coef"].numpy(), dtype=np.float32)
-            self._path_cache = None
-            _lib.check(_lib.load().hd_set_path_up(
-                handle, ut["K"], u.ctypes.data_as(C.POINTER(C.c_int)), v.ctypes.data_as(C.POINTER(C.c_int)),
-                coef.ctypes.data_as(C.POINTER(C.c_float))), "hd_set_path_up")
-            self._path_cache = (tabs, key, ut)
-        return self._path_cache[2]
+            _lib.check(_lib.load().hd_set_path_up(handle, ut["K"], ip(ut["from_idx"]), ip(ut["to_idx"]),
+                                                  coef.ctypes.data_as(C.POINTER(C.c_float))), "hd_set_path_up")
+
+        return self._upload_path(tabs, (tuple(path), "up"), lambda: paths.up_tables(tabs["gamma"], path), upload)
 
     def _grid_index(self, t, lo: int, what: str) -> int:
         if isinstance(t, torch.Tensor) and t.numel() == 1 and not t.is_floating_point():
@@ -1346,8 +1259,6 @@ class DiffusionQM9(_Base):
     def _edit_check(self, what: str, node_mask, z_shapes=(), context=None, sample_id_base=0, needs_noise: bool = False,
                     needs_context: bool = True):
         """Argument and configuration errors of the editing entry points, all raised before the GPU is touched."""
-        if self.pocket:
-            raise ValueError(f"{what}: pocket models are not supported (whole molecules only)")
         if not isinstance(node_mask, torch.Tensor) or node_mask.dim() != 3 or node_mask.shape[2] != 1:
             raise ValueError(f"node_mask must be [B, N, 1], got {tuple(getattr(node_mask, 'shape', ()))}")
         B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
@@ -1358,24 +1269,12 @@ class DiffusionQM9(_Base):
             raise ValueError("context required")
         if isinstance(sample_id_base, bool) or int(sample_id_base) != sample_id_base or int(sample_id_base) < 0:
             raise ValueError(f"sample_id_base must be an integer >= 0, got {sample_id_base!r}")
-        if getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics":
-            raise NotImplementedError(f"{what}: mode 'gnn_dynamics' is not supported (the library's loop evaluates the egnn network)")
-        if needs_noise and self.noise_mode == "torch":
-            raise NotImplementedError(f"{what}: noise_mode 'torch' is not supported (counter-based or injected noise only)")
+        unsupported(self, what, None, needs_noise, pocket_error=ValueError)
         return B, N
 
-    def _edit_device(self, node_mask, edge_mask, context, B, N):
-        """Handle, schedule, topology and context rows on node_mask's device (the first lines that need a GPU)."""
-        dev = node_mask.device
-        if dev.type != "cuda":
-            raise _lib.HierDiffHipError("editing runs only on an MI355X (no CPU fallback)")
-        handle = self._lib_handle()
-        tabs = self._schedule(rows=B)
-        topo = self.dynamics.topology(node_mask, edge_mask, B, N)
-        ctx = None
-        if self.dynamics.context_node_nf > 0 and context is not None:        # (`diffuse` and `slerp` call no network: no context)
-            ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
-        return AttrDict(h=handle, tabs=tabs, topo=topo, ctx=ctx, dev=dev, stream=_stream(dev))
+    def _edit_device(self, node_mask, edge_mask, context, B, N, pl=None):
+        """`_device_state` of the editing entry points (`diffuse` and `slerp` call no network: no context)."""
+        return self._device_state(node_mask, edge_mask, context, B, N, pl, what="editing", needs_context=False)
 
     def _alpha_sigma(self, tabs, t: int):
         """(alpha_t, sigma_t) as the loss and `scoring.term_tables` compute them: fp32 sqrt(sigmoid(-+gamma_t)) of the fp32 grid."""
@@ -1444,39 +1343,19 @@ class DiffusionQM9(_Base):
         return z
 
     def _latent_path(self, t_start, steps, eta, spacing, timesteps, solver=None, lower_order_final=None):
-        """(t_start, partial path, eta - or the `paths.Multistep` of solver "dpm2m") of the keywords; pure host arithmetic."""
-        from . import paths
-        t_start = self._grid_index(self.T if t_start is None else t_start, 1, "t_start")
-        ms = paths.check_solver(self.sample_solver if solver is None else solver, eta,
-                                self.sample_lower_order_final if lower_order_final is None else lower_order_final)
-        eta = ms if ms is not None else paths.check_eta(self.sample_eta if eta is None else eta)
-        spacing = self.sample_spacing if spacing is None else spacing
-        return t_start, paths.partial_path(self.T, t_start, steps, spacing, timesteps), eta
+        """(t_start, partial path, eta - or the `paths.Multistep` of solver "dpm2m") of the keywords: a view of `plan.latent_path`."""
+        return latent_path(self, t_start, steps, eta, spacing, timesteps, solver, lower_order_final)
 
-    @torch.no_grad()
-    def latent_steps(self, z, node_mask, edge_mask=None, context=None, *, t_start: Optional[int] = None, steps: Optional[int] = None,
-                     eta: Optional[float] = None, spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None,
-                     k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False,
-                     raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
-                     solver: Optional[str] = None, lower_order_final: Optional[bool] = None, _chain=None,
-                     restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None):
-        """Transitions k_lo .. k_hi-1 of `sample_from_latent`'s partial chain on a given z [B,N,D] (the state at path position k_lo);
-        returns the state at position k_hi (default: the end, z_0 before the decode), as `path_steps` does for a full path.  Draws are
-        keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.  `raw_noises`: k_hi - k_lo injected
-        (randn_x, randn_h) pairs, one per transition run.  solver="dpm2m" over a sub-range: the continuity rule of `path_steps`."""
-        t_start, path, eta = self._latent_path(t_start, steps, eta, spacing, timesteps, solver, lower_order_final)
-        K = len(path) - 1
-        k_lo, k_hi = int(k_lo), K if k_hi is None else int(k_hi)
-        if not (0 <= k_lo <= k_hi <= K):
-            raise ValueError(f"need 0 <= k_lo <= k_hi <= {K} (the path's transitions)")
+    @staticmethod
+    def _batch_of(node_mask):
+        """(B, N) for the plan, where the mask already looks like one (its shape errors come after the plan's)."""
+        ok = isinstance(node_mask, torch.Tensor) and node_mask.dim() == 3
+        return (int(node_mask.shape[0]), int(node_mask.shape[1])) if ok else (None, None)
+
+    def _latent_run(self, pl, z, node_mask, edge_mask, context, k_lo, k_hi, sample_id_base, fix_noise, raw_noises):
+        """Shape checks, device state and the transitions k_lo .. k_hi-1 of a partial chain: (state, z at k_hi, chain or None)."""
         B, N = self._edit_check("sample_from_latent", node_mask, (("z", z, self.n_dims + self.in_node_nf),), context, sample_id_base,
                                 needs_noise=raw_noises is None)
-        from . import guidance
-        gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, B, N, "sample_from_latent",
-                              needs_noise=raw_noises is None)
-        from . import restraints as _rs
-        rr = _rs.resolve(self, restraints, restraint_scale, restraint_schedule, restraint_clip, B, "sample_from_latent",
-                         needs_noise=raw_noises is None)
         nb = 1 if fix_noise else B
         if raw_noises is not None:
             if len(raw_noises) != k_hi - k_lo:
@@ -1484,32 +1363,31 @@ class DiffusionQM9(_Base):
             for rx_, rh_ in raw_noises:
                 if tuple(rx_.shape) != (nb, N, self.n_dims) or tuple(rh_.shape) != (nb, N, self.in_node_nf):
                     raise ValueError(f"raw_noises pairs must be ([{nb}, {N}, {self.n_dims}], [{nb}, {N}, {self.in_node_nf}])")
-        st = self._edit_device(node_mask, edge_mask, context, B, N)
-        self._path_tables(st.h, st.tabs, path, eta)
+        st = self._edit_device(node_mask, edge_mask, context, B, N, pl)
         z = z.detach().to(st.dev, torch.float32).clone().contiguous()
-        rx = rh = None
-        seed, base = self.seed, int(sample_id_base)
+        noise = (None, None, nb, self.seed, int(sample_id_base))
         if raw_noises is not None and k_hi > k_lo:
-            rx = torch.stack([r[0].to(st.dev, torch.float32) for r in raw_noises]).contiguous()
-            rh = torch.stack([r[1].to(st.dev, torch.float32) for r in raw_noises]).contiguous()
-            seed, base = 0, 0
-        try:
-            if rr is not None:
-                self._restrain_open(st.h, st.topo, st.tabs, rr, B, st.dev)
-            if _chain is not None:       # `sample_from_latent` records: (frame table, code of `record`) -> (z, chain)
-                chain = self._chain_open(st.h, st.topo, st.tabs, _chain[0], _chain[1], B, N, st.dev)
-            if gd is not None:
-                self._guided_path(st.h, st.topo, z, st.ctx, self._guide_device(gd, node_mask, st.dev), k_lo, k_hi, rx, rh, nb, seed,
-                                  base, st.stream)
-            else:
-                _lib.check(_lib.load().hd_sample_path(st.h, st.topo.ptr, z.data_ptr(), _ptr(st.ctx), -1, k_lo, k_hi, _ptr(rx),
-                                                      _ptr(rh), nb, seed, base, int(self.use_graph), st.stream), "hd_sample_path")
-        finally:
-            if _chain is not None:
-                self._chain_close(st.topo)
-            if rr is not None:
-                self._restrain_close(st.topo)
-        return z if _chain is None else (z, chain)
+            noise = (torch.stack([r[0].to(st.dev, torch.float32) for r in raw_noises]).contiguous(),
+                     torch.stack([r[1].to(st.dev, torch.float32) for r in raw_noises]).contiguous(), nb, 0, 0)
+        return (st,) + self._run(st, pl, z, k_lo, k_hi, noise)
+
+    @torch.no_grad()
+    def latent_steps(self, z, node_mask, edge_mask=None, context=None, *, t_start: Optional[int] = None, steps: Optional[int] = None,
+                     eta: Optional[float] = None, spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None,
+                     k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False,
+                     raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
+                     solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
+                     restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None):
+        """Transitions k_lo .. k_hi-1 of `sample_from_latent`'s partial chain on a given z [B,N,D] (the state at path position k_lo);
+        returns the state at position k_hi (default: the end, z_0 before the decode), as `path_steps` does for a full path.  Draws are
+        keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.  `raw_noises`: k_hi - k_lo injected
+        (randn_x, randn_h) pairs, one per transition run.  solver="dpm2m" over a sub-range: the continuity rule of `path_steps`."""
+        B, N = self._batch_of(node_mask)
+        pl = self._plan("sample_from_latent", "latent", t_start=t_start, injected=raw_noises is not None, B=B, N=N, **given(locals()))
+        k_lo, k_hi = int(k_lo), pl.K if k_hi is None else int(k_hi)
+        if not (0 <= k_lo <= k_hi <= pl.K):
+            raise ValueError(f"need 0 <= k_lo <= k_hi <= {pl.K} (the path's transitions)")
+        return self._latent_run(pl, z, node_mask, edge_mask, context, k_lo, k_hi, sample_id_base, fix_noise, raw_noises)[1]
 
     @torch.no_grad()
     def sample_from_latent(self, z, node_mask, edge_mask=None, context=None, *, t_start: Optional[int] = None,
@@ -1529,45 +1407,16 @@ class DiffusionQM9(_Base):
         validate on a trained checkpoint.  solver / lower_order_final: as in `sample_from_masks` ("dpm2m": second order, eta = 0).
         keep_frames / record: as in `sample_from_masks` - a third tensor chain [keep_frames, B, N, D] of the partial chain.
         restraints / restraint_scale / restraint_schedule / restraint_clip: as in `sample_from_masks`, on the partial chain."""
-        _, path, _ = self._latent_path(t_start, steps, eta, spacing, timesteps, solver, lower_order_final)
-        K = len(path) - 1
-        what = self._chain_check(keep_frames, record, "sample_from_latent", needs_noise=raw_noises is None)
-        cf = None
-        if what is not None:
-            from . import paths
-            cf = paths.chain_frames(K, keep_frames, path)
+        B, N = self._batch_of(node_mask)
+        pl = self._plan("sample_from_latent", "latent", t_start=t_start, injected=raw_noises is not None, B=B, N=N, **given(locals()))
+        K = pl.K
         if raw_noises is not None and len(raw_noises) != K + 1:
             raise ValueError(f"raw_noises must hold {K} + 1 (randn_x, randn_h) pairs: the transitions, then the decode")
-        from . import guidance
-        gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, int(node_mask.shape[0]) if node_mask.dim() == 3 else None,
-                              int(node_mask.shape[1]) if node_mask.dim() == 3 else None, "sample_from_latent", needs_noise=raw_noises is None)
-        z0 = self.latent_steps(z, node_mask, edge_mask, context, t_start=t_start, steps=steps, eta=eta, spacing=spacing,
-                               timesteps=timesteps, sample_id_base=sample_id_base, fix_noise=fix_noise,
-                               raw_noises=None if raw_noises is None else raw_noises[:K], guidance_scale=guidance_scale, guidance_context=guidance_context, guidance_rescale=guidance_rescale,
-                               solver=solver, lower_order_final=lower_order_final, _chain=None if cf is None else (cf, what),
-                               restraints=restraints, restraint_scale=restraint_scale, restraint_schedule=restraint_schedule, restraint_clip=restraint_clip)
-        chain = None
-        if cf is not None:
-            z0, chain = z0
-        B, N = z0.shape[0], z0.shape[1]
-        dev = z0.device
-        node_mask = node_mask.to(dev)
-        topo = self.dynamics.topology(node_mask, edge_mask, B, N)
-        ctx = None
-        if self.dynamics.context_node_nf > 0:
-            ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
+        st, z0, chain = self._latent_run(pl, z, node_mask, edge_mask, context, 0, K, sample_id_base, fix_noise,
+                                         None if raw_noises is None else raw_noises[:K])
+        node_mask = node_mask.to(st.dev)
         self._check_mean_zero(z0[:, :, :self.n_dims], node_mask)
-        eps = self._decode_eps(topo, z0, ctx, None if gd is None else self._guide_device(gd, node_mask, dev))
-        coef3 = self._schedule(rows=B)["decode"].numpy()
-        if raw_noises is not None:
-            x, hfeat = self._final_decode(z0, eps, node_mask, edge_mask, coef3, fix_noise, raw_noises[K])
-        else:
-            x, hfeat = self._final_decode(z0, eps, node_mask, edge_mask, coef3, fix_noise, None,
-                                          philox=(int(sample_id_base), self.T + 1))
-        if chain is not None:
-            chain[0] = torch.cat([x, hfeat], dim=2)
-            return x, hfeat, chain
-        return x, hfeat
+        return self._decode(st, z0, node_mask, edge_mask, fix_noise, int(sample_id_base) if raw_noises is None else raw_noises[K], chain)
 
     @torch.no_grad()
     def slerp(self, z_a, z_b, lambdas, node_mask):
@@ -1614,27 +1463,15 @@ class DiffusionQM9(_Base):
         Mechanism only: how far which t_start drifts, and whether the analogues are chemically useful, is for the user to validate."""
         from . import scoring
         device = torch.device(device)
-        extra = set(few) - {"steps", "eta", "spacing", "timesteps", "guidance_scale", "guidance_context", "guidance_rescale", "solver",
-                            "lower_order_final", "keep_frames", "record", "restraints", "restraint_scale", "restraint_schedule",
-                            "restraint_clip"}
+        extra = set(few) - set(KEYWORDS)
         if extra:
-            raise ValueError(f"vary: unsupported keyword(s) {sorted(extra)} (steps, eta, spacing, timesteps, guidance_scale, "
-                             "guidance_context, guidance_rescale, solver, lower_order_final, keep_frames, record, restraints, "
-                             "restraint_scale, restraint_schedule, restraint_clip)")
-        from . import restraints as _rs
-        rr_all = _rs.resolve(self, few.pop("restraints", None), few.pop("restraint_scale", None), few.get("restraint_schedule"),
-                             few.get("restraint_clip"), None, "vary")
-        from . import guidance
-        gscale, gctx = few.pop("guidance_scale", None), few.pop("guidance_context", None)
-        few["guidance_rescale"] = few.get("guidance_rescale", None)
-        if gctx is not None:
+            raise ValueError(f"vary: unsupported keyword(s) {sorted(extra)} ({', '.join(KEYWORDS)})")
+        if few.get("guidance_context") is not None:
             raise ValueError("vary: guidance_context is not supported (the list form pads its own batches): set the model's null_context")
-        gd_all = guidance.resolve(self, gscale, None, few["guidance_rescale"], None, None, "vary")
-        self._latent_path(t_start, few.get("steps"), few.get("eta"), few.get("spacing"), few.get("timesteps"), few.get("solver"),
-                          few.get("lower_order_final"))                                                            # argument errors first
-        chain_t = None
-        if self._chain_check(few.get("keep_frames"), few.get("record"), "vary") is not None:
-            chain_t = self._chain_times(t_start=t_start, **{k: v for k, v in few.items() if not k.startswith("restraint")})
+        pl = self._plan("vary", "latent", t_start=t_start, **few)                       # argument errors first
+        rr_all, gd_all, chain_t = pl.restraints, pl.guidance, pl.chain_t
+        for k in ("restraints", "restraint_scale", "guidance_scale", "guidance_context"):  # per batch below: a slice of the resolved ones
+            few.pop(k, None)
         for name, v in (("n_variants", n_variants), ("batch_size", batch_size)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
                 raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
@@ -1740,10 +1577,10 @@ class DiffusionQM9(_Base):
             self._inpaint_tabs = tabs
         return tabs
 
-    def _inpaint_setup(self, node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, path_args=(None,) * 4,
-                       guide_args=None, force_path: bool = False):
+    def _inpaint_setup(self, node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, pl=None):
         """Argument checks of the inpainting entry points (ValueError / NotImplementedError before anything is queued), then the
-        device-side inputs of hd_sample_loop_inpaint."""
+        device state with the inpainting extras on top: the fixed rows' mask bytes, their known values (normalised) and R.  `pl`: the
+        call's plan (None: the model's path defaults, unguided - `inpaint_steps`)."""
         if node_mask.dim() != 3 or node_mask.shape[2] != 1:
             raise ValueError(f"node_mask must be [B, N, 1], got {tuple(node_mask.shape)}")
         B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
@@ -1766,31 +1603,10 @@ class DiffusionQM9(_Base):
             raise ValueError(f"edge_mask must hold {B} x {N} x {N} entries")
         if self.dynamics.context_node_nf > 0 and context is None:
             raise ValueError("context required")
-        if self.pocket:
-            raise NotImplementedError("inpainting: pocket models are not supported")
-        if getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics":
-            raise NotImplementedError("inpainting: mode 'gnn_dynamics' is not supported")
-        if self.noise_mode == "torch":
-            raise NotImplementedError("inpainting: noise_mode 'torch' is not supported (counter-based noise only)")
-        pe = self._resolve_path(*path_args[:4], inpaint=True, solver=path_args[4] if len(path_args) > 4 else None)
-        gd = None
-        if guide_args is not None:
-            from . import guidance, paths
-            gd = guidance.resolve(self, *guide_args, B, N, "inpainting")
-            if gd is not None and pe is None:        # a guided chain always runs in the path loop: the identity path
-                pe = (paths.build_path(self.T), 1.0)
-        if force_path and pe is None:                # so does a recorded one
-            from . import paths
-            pe = (paths.build_path(self.T), 1.0)
-        if dev.type != "cuda":
-            raise _lib.HierDiffHipError("sampling runs only on an MI355X (no CPU fallback)")
-        h = self._lib_handle()
-        tabs = self._inpaint_schedule(h, self._schedule(rows=B))
-        K = None if pe is None else self._path_tables(h, tabs, *pe)["K"]
-        topo = self.dynamics.topology(node_mask, edge_mask, B, N)
-        ctx = None
-        if self.dynamics.context_node_nf > 0:
-            ctx = context.to(dev, torch.float32).reshape(B * N, -1).contiguous()
+        unsupported(self, "inpainting", None, True)
+        if pl is None:
+            pl = self._plan("inpainting", "inpaint", guided=False)
+        st = self._device_state(node_mask, edge_mask, context, B, N, pl, inpaint=True)
         xk = x_known.to(dev, torch.float32).contiguous()
         hk = h_known.to(dev, torch.float32).contiguous()
         # the model's own `normalize`, masked by the fixed rows (the library ignores the others)
@@ -1798,24 +1614,8 @@ class DiffusionQM9(_Base):
                               (hk - float(self.norm_biases[1] or 0.0)) / float(self.norm_values[1])], dim=2)
         xh_known = torch.where(fmb, xh_known, torch.zeros_like(xh_known)).contiguous()
         fm_u8 = fmb.reshape(B * N).to(torch.uint8).contiguous()
-        return AttrDict(h=h, tabs=tabs, topo=topo, ctx=ctx, xk=xk, hk=hk, xh_known=xh_known, fm_u8=fm_u8, B=B, N=N,
-                        R=int(resamplings), stream=_stream(dev), dev=dev, K=K,
-                        g=None if gd is None else self._guide_device(gd, node_mask, dev))
-
-    def _inpaint_run(self, st, z, s_hi, s_lo, sample_id_base):
-        if st.g is not None:             # guided (always on a path): two network calls per round
-            self._guided_path(st.h, st.topo, z, st.ctx, st.g, st.K - s_hi, st.K - s_lo, None, None, st.B, self.seed, sample_id_base,
-                              st.stream, st.fm_u8, st.xh_known, st.R)
-            return
-        if st.K is not None:             # few-step sampling: s_hi / s_lo count path positions from the t = 0 end
-            _lib.check(_lib.load().hd_sample_path_inpaint(
-                st.h, st.topo.ptr, z.data_ptr(), _ptr(st.ctx), -1, st.K - s_hi, st.K - s_lo, None, None, st.B, self.seed,
-                sample_id_base, int(self.use_graph), st.fm_u8.data_ptr(), st.xh_known.data_ptr(), st.R, st.stream),
-                "hd_sample_path_inpaint")
-            return
-        _lib.check(_lib.load().hd_sample_loop_inpaint(
-            st.h, st.topo.ptr, z.data_ptr(), _ptr(st.ctx), -1, s_hi, s_lo, None, None, st.B, self.seed, sample_id_base,
-            int(self.use_graph), st.fm_u8.data_ptr(), st.xh_known.data_ptr(), st.R, st.stream), "hd_sample_loop_inpaint")
+        st.update(pl=pl, xk=xk, hk=hk, xh_known=xh_known, fm_u8=fm_u8, R=int(resamplings), K=None if pl.path is None else pl.K)
+        return st
 
     @torch.no_grad()
     def inpaint_steps(self, z, s_hi: int, s_lo: int, node_mask, fixed_mask, x_known, h_known, context=None, resamplings: int = 1,
@@ -1826,8 +1626,9 @@ class DiffusionQM9(_Base):
         if tuple(z.shape) != (st.B, st.N, self.n_dims + self.in_node_nf) or not (0 <= s_lo <= s_hi <= self.T):
             raise ValueError("z must be [B, N, 3 + F] and 0 <= s_lo <= s_hi <= timesteps")
         z = z.detach().to(st.dev, torch.float32).clone().contiguous()
-        self._inpaint_run(st, z, int(s_hi), int(s_lo), sample_id_base)
-        return z
+        n_loop = st.pl.K                                 # s counts path positions from the t = 0 end (the grid itself by default)
+        return self._run(st, st.pl, z, n_loop - int(s_hi), n_loop - int(s_lo), (None, None, st.B, self.seed, sample_id_base),
+                         (st.fm_u8, st.xh_known, st.R))[0]
 
     @torch.no_grad()
     def sample_inpaint(self, node_mask: torch.Tensor, fixed_mask: torch.Tensor, x_known: torch.Tensor, h_known: torch.Tensor,
@@ -1850,42 +1651,20 @@ class DiffusionQM9(_Base):
         (known rows replaced), or that round's data prediction, and frame 0 the returned (x, h)."""
         from . import restraints as _rs
         _rs.refuse(self, "sample_inpaint", restraints, ": inpainting re-centres on the known fragments, so its frame moves")
-        pe0 = self._resolve_path(steps, eta, spacing, timesteps, inpaint=True, solver=solver)   # the solver's ValueError before any shape check
-        what = self._chain_check(keep_frames, record, "sample_inpaint")
-        cf = None
-        if what is not None:
-            from . import paths
-            path0 = paths.build_path(self.T) if pe0 is None else pe0[0]
-            cf = paths.chain_frames(len(path0) - 1, keep_frames, path0)
-        st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask,
-                                 (steps, eta, spacing, timesteps, solver), (guidance_scale, guidance_context, guidance_rescale),
-                                 force_path=cf is not None)
-        lib, T, B, N = _lib.load(), self.T, st.B, st.N
-        n_loop = T if st.K is None else st.K
-        z = torch.empty((B, N, self.n_dims + self.in_node_nf), device=st.dev, dtype=torch.float32)
-        _lib.check(lib.hd_noise(st.h, st.topo.ptr, None, None, B, self.seed, sample_id_base, 0, 0, z.data_ptr(), st.stream),
+        B, N = self._batch_of(node_mask)
+        pl = self._plan("sample_inpaint", "inpaint", B=B, N=N, **given(locals()))            # every keyword error before any shape check
+        st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, pl)
+        z = torch.empty((st.B, st.N, self.n_dims + self.in_node_nf), device=st.dev, dtype=torch.float32)
+        _lib.check(_lib.load().hd_noise(st.h, st.topo.ptr, None, None, st.B, self.seed, sample_id_base, 0, 0, z.data_ptr(), st.stream),
                    "hd_noise")
-        chain = None if cf is None else self._chain_open(st.h, st.topo, st.tabs, cf, what, B, N, st.dev)
-        try:
-            if self.debug_checks:          # the loop's invariant after every step (host-synchronising, like the reference's asserts)
-                for s in reversed(range(n_loop)):
-                    self._inpaint_run(st, z, s + 1, s, sample_id_base)
-                    self._check_mean_zero(z[:, :, :self.n_dims], node_mask)
-            else:
-                self._inpaint_run(st, z, n_loop, 0, sample_id_base)
-        finally:
-            if cf is not None:
-                self._chain_close(st.topo)
-        eps = self._decode_eps(st.topo, z, st.ctx, st.g)
-        x, hfeat = self._final_decode(z, eps, node_mask, edge_mask, st.tabs["decode"].numpy(), False, None,
-                                      philox=(sample_id_base, T + 1))
-        x, hfeat = x.contiguous(), hfeat.contiguous()
-        _lib.check(lib.hd_inpaint_decode_fix(st.h, st.topo.ptr, st.fm_u8.data_ptr(), st.xk.data_ptr(), st.hk.data_ptr(),
-                                             x.data_ptr(), hfeat.data_ptr(), st.stream), "hd_inpaint_decode_fix")
-        if chain is not None:
-            chain[0] = torch.cat([x, hfeat], dim=2)
-            return x, hfeat, chain
-        return x, hfeat
+        noise, inp = (None, None, st.B, self.seed, sample_id_base), (st.fm_u8, st.xh_known, st.R)
+        if self.debug_checks:              # the loop's invariant after every step (host-synchronising, like the reference's asserts)
+            for k in range(pl.K):
+                z, chain = self._run(st, pl, z, k, k + 1, noise, inp)
+                self._check_mean_zero(z[:, :, :self.n_dims], node_mask)
+        else:
+            z, chain = self._run(st, pl, z, 0, pl.K, noise, inp)
+        return self._decode(st, z, node_mask, edge_mask, False, int(sample_id_base), chain, (st.fm_u8, st.xk, st.hk))
 
     @torch.no_grad()
     def sample_grow(self, known: Sequence[Dict[str, torch.Tensor]], sizes, device, context=None, resamplings: int = 1,
@@ -1901,13 +1680,8 @@ class DiffusionQM9(_Base):
         device = torch.device(device)
         from . import restraints as _rs
         _rs.refuse(self, "sample_grow", restraints, ": inpainting re-centres on the known fragments, so its frame moves")
-        self._resolve_path(steps, eta, spacing, timesteps, inpaint=True, solver=solver)       # argument errors first
-        chain_t = None
-        if self._chain_check(keep_frames, record, "sample_grow") is not None:
-            chain_t = self._chain_times(keep_frames, inpaint=True, steps=steps, eta=eta, spacing=spacing, timesteps=timesteps,
-                                        solver=solver)
-        from . import guidance
-        guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, None, None, "sample_grow")
+        few = given(locals())
+        chain_t = self._plan("sample_grow", "inpaint", **few).chain_t                    # argument errors first
         num = len(known)
         if isinstance(sizes, (int, np.integer)):
             sizes = [int(sizes)] * num
@@ -1938,11 +1712,7 @@ class DiffusionQM9(_Base):
                 raise ValueError(f"context of shape {tuple(torch.as_tensor(context).shape)} does not broadcast to [{num}, {n_max}, 1]")
         got = self.sample_inpaint(node_mask.to(device), fixed_mask.to(device), x_known.to(device), h_known.to(device),
                                   context=None if ctx is None else ctx.to(device), resamplings=resamplings,
-                                  sample_id_base=sample_id_base, steps=steps, eta=eta, spacing=spacing, timesteps=timesteps,
-                                  guidance_scale=guidance_scale,
-                                  guidance_context=None if guidance_context is None else guidance_context.to(device),
-                                  guidance_rescale=guidance_rescale, solver=solver,
-                                  **({} if chain_t is None else {"keep_frames": keep_frames, "record": record}))
+                                  sample_id_base=sample_id_base, **few)
         x, h = got[0].cpu(), got[1].cpu()
         out = [{'x': x[i, :sizes[i]].clone(), 'h': h[i, :sizes[i]].clone()} for i in range(num)]
         if ctx is not None:
@@ -1971,22 +1741,10 @@ class DiffusionQM9(_Base):
         centre of mass at the origin) - every dict also holds 'restraint_energy', float64 [3] = (U_obs, U_pair, U_anc) of the
         returned 'x'.  The sizes are drawn: a row that names a node the molecule does not have is inactive."""
         device = torch.device(device)
-        self._resolve_path(steps, eta, spacing, timesteps, solver=solver, lower_order_final=lower_order_final)     # argument errors before anything is drawn
-        if self._chain_check(keep_frames, record, "sample", pocket_cond) is not None:
-            self._chain_times(keep_frames, steps=steps, eta=eta, spacing=spacing, timesteps=timesteps, solver=solver,
-                              lower_order_final=lower_order_final)
-        from . import guidance
-        gd = guidance.resolve(self, guidance_scale, guidance_context, guidance_rescale, int(num_samples), None, "sample", pocket_cond)
-        if gd is not None and context is None:
+        few = given(locals())
+        pl = self._plan("sample", pocket=pocket_cond, B=int(num_samples), **few)         # argument errors before anything is drawn
+        if pl.guidance is not None and context is None:
             raise ValueError("context required")
-        from . import restraints as _rs
-        _rs.resolve(self, restraints, restraint_scale, restraint_schedule, restraint_clip, int(num_samples), "sample", pocket_cond)
-        few = {k: v for k, v in dict(steps=steps, eta=eta, spacing=spacing, timesteps=timesteps, guidance_scale=guidance_scale,
-                                     guidance_context=guidance_context, guidance_rescale=guidance_rescale, solver=solver,
-                                     lower_order_final=lower_order_final, keep_frames=keep_frames, record=record,
-                                     restraints=restraints, restraint_scale=restraint_scale, restraint_schedule=restraint_schedule,
-                                     restraint_clip=restraint_clip).items()
-               if v is not None}
         sample_n = self.nodes_dist.sample(num_samples)
         pocket = None
         if pocket_cond is not None:
@@ -2003,9 +1761,9 @@ class DiffusionQM9(_Base):
             if ctx.shape != (num_samples, max(sample_n), 1):
                 raise ValueError(f"context of shape {tuple(torch.as_tensor(context).shape)} does not broadcast to "
                                  f"[{num_samples}, {max(sample_n)}, 1]")
-        return self._sample_sizes(sample_n, device, None, sample_id_base, pocket, context_full=ctx, **({"few": few} if few else {}))
+        return self._sample_sizes(sample_n, device, None, sample_id_base, pocket, context_full=ctx, few=few, pl=pl)
 
-    def _sample_sizes(self, sample_n, device, contexts, sample_id_base, pocket=None, context_full=None, few=None):
+    def _sample_sizes(self, sample_n, device, contexts, sample_id_base, pocket=None, context_full=None, few=None, pl=None):
         """One device batch for the molecule sizes `sample_n` (global sample ids sample_id_base + i); `contexts`: one scalar
         per molecule (merged batches: the value of the batch a molecule belongs to) or None; `context_full`: the
         [num_samples, n_max, 1] tensor of `sample()` instead.  Masks as diffusion_qm9.py:349-353, result slicing as :388-395."""
@@ -2023,7 +1781,10 @@ class DiffusionQM9(_Base):
                 raise ValueError("merged batches take one global context value per batch (context_range entries)")
             context = (torch.zeros([num_samples, n_max, 1]) + torch.stack(cols).reshape(num_samples, 1, 1)).to(device)
         node_mask = node_mask.to(device)
-        got = self.sample_from_masks(node_mask, None, context, sample_id_base=sample_id_base, pocket=pocket, **(few or {}))
+        few = few or {}
+        if pl is None:                               # (`sample` passes its plan; merged `sample_batches` batches come without one)
+            pl = self._plan("sample", pocket=pocket, B=num_samples, **few)
+        got = self.sample_from_masks(node_mask, None, context, sample_id_base=sample_id_base, pocket=pocket, **few)
         x, h = got[0].cpu(), got[1].cpu()
         xs = [x[i, :sample_n[i]].clone() for i in range(num_samples)]
         hs = [h[i, :sample_n[i]].clone() for i in range(num_samples)]
@@ -2033,11 +1794,8 @@ class DiffusionQM9(_Base):
         else:
             out = [{'x': xs[i], 'h': hs[i]} for i in range(num_samples)]
         if len(got) == 3:                            # a recording call (`sample`: keep_frames)
-            self._chain_into(out, got[2], sample_n, self._chain_times(**few))
-        from . import restraints as _rs
-        fw = few or {}
-        rr = _rs.resolve(self, fw.get("restraints"), fw.get("restraint_scale"), fw.get("restraint_schedule"), fw.get("restraint_clip"),
-                         num_samples, "sample", pocket)
+            self._chain_into(out, got[2], sample_n, pl.chain_t)
+        rr = pl.restraints
         if rr is not None:
             en = rr.rs.energy(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0]))).cpu()
             for i in range(num_samples):
@@ -2063,7 +1821,6 @@ class DiffusionQM9(_Base):
         device = torch.device(device)
         from . import restraints as _rs
         _rs.refuse(self, "sample_batches", restraints, ": the batches' padded widths and molecule counts differ (use sample)")
-        self._resolve_path(steps, eta, spacing, timesteps, solver=solver, lower_order_final=lower_order_final)   # few-step sampling (`sample_from_masks`): argument errors first
         # classifier-free guidance (`sample_from_masks`): guidance_scale may also be a list / tuple of scales cycled per batch the way
         # context_range is; inside a merged device batch it becomes one scale per molecule
         from . import guidance
@@ -2074,12 +1831,9 @@ class DiffusionQM9(_Base):
         if isinstance(gscale, (torch.Tensor, np.ndarray)) and gscale.ndim > 0:
             raise ValueError("sample_batches: guidance_scale must be a float or a list / tuple of floats cycled per batch")
         g_seq = guidance.batch_scales(gscale, int(num_batches), int(batch_size)) if guidance.is_sequence_scale(gscale) else None
-        guidance.resolve(self, gscale if g_seq is None else torch.tensor(g_seq), None, guidance_rescale, None, None, "sample_batches",
-                         protein_data_all)
-        few = {k: v for k, v in dict(steps=steps, eta=eta, spacing=spacing, timesteps=timesteps, guidance_rescale=guidance_rescale,
-                                     solver=solver, lower_order_final=lower_order_final).items() if v is not None}
-        if g_seq is None and gscale is not None:
-            few["guidance_scale"] = gscale
+        few = given(dict(locals(), guidance_scale=gscale if g_seq is None else None))
+        self._plan("sample_batches", pocket=protein_data_all,                            # few-step sampling, guidance: argument errors first
+                   **dict(few, **({} if g_seq is None else {"guidance_scale": torch.tensor(g_seq)})))
         # Not merged either: mode 'gnn_dynamics' (torch.randn draws whatever noise_mode says, messages over padded nodes) and
         # aggregation_method 'mean' (the divisor is the padded N of the call) - both depend on the padded width of the batch a
         # molecule sits in - and context_range entries that are not one scalar per batch.
@@ -2142,9 +1896,7 @@ class EnVariationalDiffusion(DiffusionQM9):
                steps=None, eta=None, spacing=None, timesteps=None, guidance_scale=None, guidance_context=None, guidance_rescale=None,
                solver=None, lower_order_final=None):
         assert node_mask.shape[0] == n_samples and node_mask.shape[1] == n_nodes
-        x, h = self.sample_from_masks(node_mask, edge_mask, context, fix_noise=fix_noise, steps=steps, eta=eta, spacing=spacing,
-                                      timesteps=timesteps, guidance_scale=guidance_scale, guidance_context=guidance_context, guidance_rescale=guidance_rescale,
-                                      solver=solver, lower_order_final=lower_order_final)
+        x, h = self.sample_from_masks(node_mask, edge_mask, context, fix_noise=fix_noise, **given(locals()))
         if self.debug_checks:
             self._check_mean_zero(x, node_mask)
         max_cog = torch.sum(x, dim=1, keepdim=True).abs().max()
@@ -2164,11 +1916,9 @@ class EnVariationalDiffusion(DiffusionQM9):
         decode.  The keyword-only extras are those of `sample`, plus record="x0": the data prediction instead of the state.
         Recorded inside the library's loop (`sample_from_masks`)."""
         assert node_mask.shape[0] == n_samples and node_mask.shape[1] == n_nodes
-        if keep_frames is None:
+        few = given(locals())
+        if keep_frames is None:                          # all of them: K of the path keywords alone (`record` needs keep_frames)
             pe = self._resolve_path(steps, eta, spacing, timesteps, solver=solver, lower_order_final=lower_order_final)
-            keep_frames = self.T if pe is None else len(pe[0]) - 1
-        _, _, chain = self.sample_from_masks(node_mask, edge_mask, context, steps=steps, eta=eta, spacing=spacing, timesteps=timesteps,
-                                             guidance_scale=guidance_scale, guidance_context=guidance_context,
-                                             guidance_rescale=guidance_rescale, solver=solver, lower_order_final=lower_order_final,
-                                             keep_frames=keep_frames, record=record)
+            few["keep_frames"] = self.T if pe is None else len(pe[0]) - 1
+        _, _, chain = self.sample_from_masks(node_mask, edge_mask, context, **few)
         return chain.reshape(n_samples * chain.shape[0], n_nodes, chain.shape[3])

@@ -62,12 +62,8 @@ def check_model(model, what: str = "guidance", pocket=None, needs_noise: bool = 
     C = int(getattr(model.dynamics, "context_node_nf", 0) or 0)
     if C < 1:
         raise ValueError(f"{what}: guidance needs a context-conditioned model (context_node_nf > 0)")
-    if getattr(model.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics":
-        raise NotImplementedError(f"{what}: guidance with mode 'gnn_dynamics' is not supported (the library's loop evaluates the egnn network)")
-    if needs_noise and model.noise_mode == "torch":
-        raise NotImplementedError(f"{what}: guidance with noise_mode 'torch' is not supported (counter-based or injected noise only)")
-    if model.pocket or pocket is not None:
-        raise NotImplementedError(f"{what}: guidance on pocket models is not supported")
+    from .plan import unsupported
+    unsupported(model, f"{what}: guidance", pocket, needs_noise)
 
 
 def resolve(model, scale, context, rescale, B: Optional[int] = None, N: Optional[int] = None, what: str = "guidance",

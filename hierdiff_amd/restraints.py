@@ -265,15 +265,6 @@ class Resolved:
         return (s if isinstance(s, str) else tuple(float(v) for v in torch.as_tensor(s).reshape(-1).tolist()), self.clip)
 
 
-def check_model(model, what: str, pocket=None, needs_noise: bool = True) -> None:
-    if model.pocket or pocket is not None:
-        raise NotImplementedError(f"{what}: restraints on pocket models are not supported (the model's frame is the ligand's alone)")
-    if getattr(model.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics":
-        raise NotImplementedError(f"{what}: restraints with mode 'gnn_dynamics' are not supported (the library's loop evaluates the egnn network)")
-    if needs_noise and model.noise_mode == "torch":
-        raise NotImplementedError(f"{what}: restraints with noise_mode 'torch' are not supported (counter-based or injected noise only)")
-
-
 def resolve(model, restraints, scale, schedule, clip, B: Optional[int] = None, what: str = "restraints", pocket=None,
             needs_noise: bool = True) -> Optional[Resolved]:
     """Keywords (None: the model's `restraints` / `restraint_scale` / `restraint_schedule` / `restraint_clip`) -> None for the
@@ -310,7 +301,8 @@ def resolve(model, restraints, scale, schedule, clip, B: Optional[int] = None, w
     c = check_clip(clip)
     if not bool((s != 0).any()):
         return None
-    check_model(model, what, pocket, needs_noise)
+    from .plan import unsupported
+    unsupported(model, f"{what}: restraints", pocket, needs_noise)         # (the model's frame is the ligand's alone)
     if B is not None:
         restraints.check_batch(B, what)
     return Resolved(restraints, s.contiguous(), schedule, c)

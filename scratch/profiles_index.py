@@ -76,6 +76,7 @@ RULES = [
     (r"r06_ablate_fp16x3_no_mfma\.log", "fp16x3 edge kernel of the measurement build: shipped / no MFMA (vector side alone, bit 1024) / matrix side alone / no epilogue, same box", "DESIGN 12 item 2, EXPERIMENTS W: wave specialisation cannot clear 6 %"),
     (r"r06_ab_gemm_rows\.log", "same-box A/B of the node-level training GEMMs: k_tgemm vs the row-resident k_tgemm_rows (slower; removed)", "EXPERIMENTS V"),
     (r"r06_ab_dw2_two_chunks\.log", "same-box A/B of k_dw2_f16 with one vs two chunks in flight (slower; reverted)", "EXPERIMENTS V"),
+    (r"sampling_bits_(parent|result)\.json", "`scratch/sampling_bits.py`: SHA-256 of what every Python sampling entry point returns over the option matrix of tests/make_golden_dispatch.py, before / after the plan / state / run / decode split; the two files are identical", "DESIGN 5a, EXPERIMENTS AE"),
     (r"r06_.*", "round-6 measurement", "DESIGN 0a"),
 ]
 def commit(path):

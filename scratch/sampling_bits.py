@@ -1,0 +1,100 @@
+"""Bits of every Python sampling entry point, to compare two versions of hierdiff_amd/diffusion.py on the same library.
+
+    python scratch/sampling_bits.py --out profiles/sampling_bits_<name>.json [--root DIR] [--detail FILE]
+
+The matrix of tests/make_golden_dispatch.py (every entry point crossed with steps / eta / solver / guidance / keep_frames + record /
+restraints / injected noise / fix_noise / k_lo > 0) run to completion at B = 3, sizes [7, 4, 1], T = 8, hidden 32, 2 layers, synthetic
+weights, the model's fixed seed, with `use_graph` on and off.  Per row: SHA-256 of every returned tensor (x, h, chain; of the list
+forms x, h, context, chain_x, chain_h, chain_t, restraint_energy over all molecules), or the type of the argument error, and what a second,
+warm call of the same row adds to the graph build counters (hd_path_graph_builds, hd_guided_graph_builds, hd_chain_graph_builds).
+A row the library refuses before it launches anything (solver "dpm2m" from k_lo > 0 without the transition before it) holds
+"HD_E_STATE"; any other library error ends the run.
+`--out` holds, per `use_graph` value and entry point, the number of rows, how they ended, the warm builds summed, and one SHA-256 over
+the rows' records in matrix order - small enough to commit; `--detail FILE` also writes every row's record (862 KB), which is what to
+compare when two `--out` files differ.  `--root DIR` runs another checkout (the parent commit).  Two runs agree when their files are
+identical."""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+import torch
+
+DEV = "cuda:0"
+HD_E_STATE = -4                   # include/hierdiff_hip.h
+COUNTERS = ("hd_path_graph_builds", "hd_guided_graph_builds", "hd_chain_graph_builds")
+
+
+def digest(t):
+    t = t.detach().cpu().contiguous()
+    return hashlib.sha256(str((tuple(t.shape), str(t.dtype))).encode() + t.numpy().tobytes()).hexdigest()
+
+
+def digests(got):
+    if torch.is_tensor(got):
+        return {"z": digest(got)}
+    if isinstance(got, tuple):
+        return {name: digest(t) for name, t in zip(("x", "h", "chain"), got)}
+    return {k: digest(torch.cat([res[k].reshape(-1).double() for res in got])) for k in sorted(got[0])}       # a list: per key
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--detail", default=None)
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.root))
+    from hierdiff_amd import _lib
+    from tests import make_golden_dispatch as gd
+
+    case = gd.Case(T=8, device=DEV)
+    lib = _lib.load()
+    # (the counters belong to the topology; every row runs on the masks of sizes [7, 4, 1], which the dynamics caches by content)
+    counters = lambda m: [int(getattr(lib, c)(m.dynamics.topology(case.nm, None, case.B, case.N).ptr)) for c in COUNTERS]
+    res = {"config": dict(B=3, sizes=gd.N_LIST, T=8, H=gd.H, L=gd.L, seed=case.model.seed), "rows": {}}
+    for graph in (True, False):
+        case.model.use_graph = case.edm.use_graph = graph
+        for key, entry, opt in gd.matrix():
+            m = case.edm if entry.startswith("edm_") else case.model
+            name = f"graph={int(graph)}|{key}"
+            try:
+                first = digests(case.call(entry, opt))
+                before = counters(m)
+                second = digests(case.call(entry, opt))
+                row = {"sha256": first, "warm_builds": [a - b for a, b in zip(counters(m), before)]}
+                if second != first:
+                    row["second_call_differs"] = second
+            except (ValueError, NotImplementedError) as e:
+                row = {"error": type(e).__name__}
+            except _lib.HierDiffHipError as e:        # only the state refusal, raised before anything is launched; all else ends the run
+                if f"({HD_E_STATE})" not in str(e) or "multistep path" not in str(e):
+                    raise
+                row = {"error": "HD_E_STATE"}
+            res["rows"][name] = row
+        torch.cuda.synchronize()
+        print(f"use_graph={graph}: {len(res['rows'])} rows", flush=True)
+    groups = {}
+    for name, row in res["rows"].items():
+        g = groups.setdefault("|".join(name.split("|")[:2]), {"rows": 0, "ended": {}, "warm_builds": [0, 0, 0], "sha256": hashlib.sha256()})
+        g["rows"] += 1
+        end = row.get("error", "completed")
+        g["ended"][end] = g["ended"].get(end, 0) + 1
+        g["warm_builds"] = [a + b for a, b in zip(g["warm_builds"], row.get("warm_builds", [0, 0, 0]))]
+        g["sha256"].update((name + json.dumps(row, sort_keys=True)).encode())
+    for g in groups.values():
+        g["sha256"] = g["sha256"].hexdigest()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write('{"config": ' + json.dumps(res["config"]) + ',\n"entry_points": {\n' + ",\n".join(
+            f"{json.dumps(k)}: {json.dumps(g)}" for k, g in groups.items()) + "\n}}\n")
+    if args.detail:
+        with open(args.detail, "w") as fh:
+            fh.write("{\n" + json.dumps("config") + ": " + json.dumps(res["config"]) + ",\n\"rows\": {\n" + ",\n".join(
+                f"{json.dumps(k)}: {json.dumps(v, separators=(',', ':'))}" for k, v in res["rows"].items()) + "\n}}\n")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
