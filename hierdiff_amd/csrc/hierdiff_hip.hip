@@ -65,13 +65,13 @@ struct ProfRec { int fam; hipEvent_t a, b; };
 // A path on the schedule's grid: K transitions t_idx[k] -> s_idx[k], the rows they read, and the generations that tie captured
 // graphs to the tables.  set_path_tables is the one writer (the every-step inpainting rows come from hd_set_inpaint_schedule).
 struct PathTables {
-    int path_K = 0, path_form = 0;   // form 0: ancestral rows, 1: linear rows {a, b, c, 0}, 2: multistep rows {a, b, c2, p, q} (5 floats)
-    bool path_up = false;            // the path ascends (hd_set_path_up: t_idx[k] < s_idx[k], linear rows with c == 0)
-    std::vector<int> path_t_h, path_s_h;
-    std::vector<float> path_c2_h;    // form 2: c2 of every row (which transitions read the history)
-    int *d_path_t = nullptr, *d_path_s = nullptr;
-    float *d_path_coef = nullptr, *d_path_coef_ip = nullptr;   // [K][4] each; d_path_coef_ip null when no inpainting rows were given
-    unsigned long long path_sched_gen = 0, path_gen = 0;       // sched_gen the tables were set for (0: not set); bumped by every rewrite
+    int K = 0, form = 0;             // form 0: ancestral rows, 1: linear rows {a, b, c, 0}, 2: multistep rows {a, b, c2, p, q} (5 floats)
+    bool up = false;                 // the path ascends (hd_set_path_up: t_idx[k] < s_idx[k], linear rows with c == 0)
+    std::vector<int> t_h, s_h;
+    std::vector<float> c2_h;         // form 2: c2 of every row (which transitions read the history)
+    int *d_t = nullptr, *d_s = nullptr;
+    float *d_coef = nullptr, *d_coef_ip = nullptr;   // [K][4] each; d_coef_ip null when no inpainting rows were given
+    unsigned long long sched_gen = 0, gen = 0;       // sched_gen the tables were set for (0: not set); bumped by every rewrite
 };
 
 struct hd_handle {
@@ -110,7 +110,7 @@ struct hd_handle {
     unsigned long long weights_gen, sched_gen;   // bumped when the packed weights / schedule tables are re-allocated
     // The path loop's tables.  `path`: the caller's (hd_set_path / hd_set_path_up / hd_set_path_multistep; hd_sample_path*).
     // `every`: the identity path of the current schedule, T transitions s + 1 -> s from s = T - 1 down to 0, built by hd_set_schedule
-    // from its rows in reverse order (form 0; path_gen moves with sched_gen); hd_set_inpaint_schedule adds the inpainting rows
+    // from its rows in reverse order (form 0; its gen moves with sched_gen); hd_set_inpaint_schedule adds the inpainting rows
     // {alpha_s, sigma_s, alpha_t|s, sigma_t|s}, reversed too.  hd_sample_loop / hd_sample_loop_inpaint run on it.
     PathTables path, every;
     unsigned long long ip_sched_gen, ip_gen;     // sched_gen every's inpainting rows were set for (0: not set); bumped when they / d_ipdraw move
@@ -121,12 +121,12 @@ struct hd_handle {
     int chain_frames;
     int* d_chain_frame;         // [K], -1: none
     float* d_chain_as;          // [K][2]; null when hd_set_chain got none
-    unsigned long long chain_path_gen, chain_gen;   // path_gen the tables were set for (0: not set); bumped by every hd_set_chain
+    unsigned long long chain_path_gen, chain_gen;   // path.gen the tables were set for (0: not set); bumped by every hd_set_chain
     float** d_chain_dst;        // graph replay: the sink a recording transition writes (set by k_path_state)
     // restraints (hd_set_restraint): the rows {alpha_t, sigma_t, lambda_k, clip_k} of every transition of the current path
     float* d_rs_rows;           // [K][4]
     int rs_K;
-    unsigned long long rs_path_gen, rs_gen;         // path_gen the rows were set for (0: not set); bumped when the table moves
+    unsigned long long rs_path_gen, rs_gen;         // path.gen the rows were set for (0: not set); bumped when the table moves
     // scoring (hd_set_nll_terms / hd_nll_terms / hd_nll_finish): K terms t_idx[k] of the bound, rows {alpha_t, sigma_t, w_t, 0}
     int nll_K;
     std::vector<int> nll_t_h;
@@ -156,7 +156,7 @@ struct hd_handle {
 };
 
 // Everything a captured transition of the path loop has baked in (plain: resamplings = 0): a cached graph is replayed only when
-// all of it is unchanged.  path_gen is the generation of the tables it runs on (the caller's path, or the every-step tables).
+// all of it is unchanged.  path_gen is the generation (PathTables::gen) of the tables it runs on (the caller's path, or the every-step tables).
 struct PathKey {
     const float *raw_x, *raw_h;
     int has_ctx, mol_shape, noise_rows, k_lo, resamplings;   // k_lo: injected-noise offsets are relative to the first transition
@@ -197,6 +197,15 @@ struct NllKey {
     }
 };
 
+// One captured transition / term of a device loop: the instantiated graph, the key it was built for, and how often the slot was
+// built (replay_slot is the one writer; the hd_*_graph_builds getters report the count where the ABI has one).
+template <typename Key>
+struct GraphSlot {
+    hipGraphExec_t exec;
+    Key key;
+    long long builds;
+};
+
 struct hd_topology {
     hd_handle* h;
     int device;
@@ -213,39 +222,30 @@ struct hd_topology {
     float *hbuf, *AB, *AB2, *Tb, *agg, *x0, *xcur, *part, *xpart, *eps;
     float *abmax, *abmax2;                     // fp16x3: [M_pad][2] row maxima of the AB / AB2 buffers
     float *rowinfo;                            // fp16x3, split node chain: [M_pad][2] {max |h_r|, max |[h | agg]_r|} (k_node_split.hpp)
-    // use_graph: every device loop keeps ONE captured transition / term here - a slot, the key it was built for and,
-    // where the ABI reports it, a count of instantiations - and replays it once per step through the replay scaffold ("sampling
-    // maths" below; graph_slots lists the slots).  The captured body works on library-owned copies of the caller's tensors so
-    // that the instantiated graph survives across calls (the caller's tensors move); each loop allocates its copies on first use.
+    // use_graph: every device loop keeps ONE captured transition / term here in a GraphSlot and replays it once per step through
+    // the replay scaffold (host_loops.hpp; graph_execs lists the slots).  The captured body works on library-owned copies of the
+    // caller's tensors so that the instantiated graph survives across calls (the caller's tensors move); each loop allocates its
+    // copies on first use.
     // all loops: z / context
     float *zbuf, *ctxbuf;
     // hd_sample_loop, hd_sample_loop_inpaint: the path loop on the handle's every-step tables, in slots of its own so that it and
-    // the loops on the caller's path do not evict each other (no build counters)
-    hipGraphExec_t gexec;
-    PathKey gkey;
-    hipGraphExec_t gexec_ip;
-    PathKey ikey;
+    // the loops on the caller's path do not evict each other (their build counts are not reported)
+    GraphSlot<PathKey> g_every, g_every_ip;
     // the inpainting loops: the fixed mask / known values
     uint8_t* ip_fixed;
     float* ip_known;
     // hd_sample_path / hd_sample_path_inpaint (hd_path_graph_builds)
-    hipGraphExec_t gexec_path;
-    PathKey pkey;
-    long long path_builds;
+    GraphSlot<PathKey> g_path;
     // hd_sample_path_guided: the second network output, and for the captured guided transition - a graph of its own next to the
     // unguided one - the null context and the scales (one allocation, made by the first guided call; hd_guided_graph_builds)
-    hipGraphExec_t gexec_guided;
-    PathKey gdkey;
-    long long guided_builds;
+    GraphSlot<PathKey> g_guided;
     float *guide_mem, *eps_u, *ctxu_buf, *wbuf;
     // hd_chain_attach: the sink every path loop on this topology records into (null: none), and the recording transition - guided
     // or not - in a graph of its own next to the two above (hd_chain_graph_builds)
     float* chain_dst;
     int chain_frames, chain_what;              // what 0: the state behind the transition, 1: its data prediction
     float chain_nv0, chain_nv1, chain_nb1;
-    hipGraphExec_t gexec_chain;
-    ChainKey ckey;
-    long long chain_builds;
+    GraphSlot<ChainKey> g_chain;
     // hd_restraint_attach: library-owned copies of the restraint tables (addresses a captured transition keeps; they grow, never
     // shrink), the per-molecule scales and the scratch of k_restrain_eps.  rs_gen moves when anything a captured launch bakes in does
     // (an address, a size, a row count, nv0); re-attaching tables of the same sizes is a copy.
@@ -264,9 +264,7 @@ struct hd_topology {
     int ms_k;
     // hd_nll_terms / hd_nll_finish: eps_t and, for the captured term, xh / the accumulator / the e_t table (z_t lives in zbuf;
     // hd_nll_graph_builds)
-    hipGraphExec_t gexec_nll;
-    NllKey nkey;
-    long long nll_builds;
+    GraphSlot<NllKey> g_nll;
     float *nll_eps, *nll_xh, *nll_err;
     double* nll_acc;
     int nll_err_rows;
@@ -434,7 +432,7 @@ extern "C" int hd_destroy(hd_handle* h) {
     hipFree(h->d_tau); hipFree(h->d_step); hipFree(h->d_draw); hipFree(h->d_tcur); hipFree(h->d_base);
     hipFree(h->d_ipdraw);
     for (PathTables* pt : {&h->path, &h->every}) {
-        hipFree(pt->d_path_t); hipFree(pt->d_path_s); hipFree(pt->d_path_coef); hipFree(pt->d_path_coef_ip);
+        hipFree(pt->d_t); hipFree(pt->d_s); hipFree(pt->d_coef); hipFree(pt->d_coef_ip);
     }
     hipFree(h->d_chain_frame); hipFree(h->d_chain_as); hipFree(h->d_chain_dst);
     hipFree(h->d_rs_rows);
@@ -806,9 +804,9 @@ extern "C" int hd_arena_pool_trim(void) {
     return HD_OK;
 }
 
-// the graph slots of a topology, one per captured loop, and the one way a slot's graph goes (replay scaffold, "sampling maths")
-static std::array<hipGraphExec_t*, 6> graph_slots(hd_topology* t) {
-    return {&t->gexec, &t->gexec_ip, &t->gexec_path, &t->gexec_guided, &t->gexec_chain, &t->gexec_nll};
+// the graphs of a topology's slots, one per captured loop, and the one way a slot's graph goes (replay scaffold, host_loops.hpp)
+static std::array<hipGraphExec_t*, 6> graph_execs(hd_topology* t) {
+    return {&t->g_every.exec, &t->g_every_ip.exec, &t->g_path.exec, &t->g_guided.exec, &t->g_chain.exec, &t->g_nll.exec};
 }
 static void graph_drop(hipGraphExec_t* gx) {
     if (*gx) hipGraphExecDestroy(*gx);
@@ -822,14 +820,14 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     // a captured graph, or launches on several streams: wait for the device (the rare case - a sampling topology lives as
     // long as its model); otherwise an event behind the topology's last work guards the arena's next owner
     bool pooled = t->arena && !t->multi_stream;
-    for (hipGraphExec_t* gx : graph_slots(t)) pooled = pooled && !*gx;
+    for (hipGraphExec_t* gx : graph_execs(t)) pooled = pooled && !*gx;
     if (pooled && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) == hipSuccess) {
         if (hipEventRecord(sl.done, t->last_stream) != hipSuccess) { (void)hipEventDestroy(sl.done); sl.done = nullptr; pooled = false; }
     } else {
         pooled = false;
     }
     if (!pooled) (void)hipDeviceSynchronize();
-    for (hipGraphExec_t* gx : graph_slots(t)) graph_drop(gx);
+    for (hipGraphExec_t* gx : graph_execs(t)) graph_drop(gx);
     if (t->guide_mem) (void)hipFree(t->guide_mem);
     if (t->ms_hist) (void)hipFree(t->ms_hist);
     for (void* p : {(void*)t->rs_obs, (void*)t->rs_pair_idx, (void*)t->rs_pair_f, (void*)t->rs_anc_idx, (void*)t->rs_anc_f,
@@ -2630,1160 +2628,7 @@ extern "C" int hd_params_digest(int device, const void* const* ptrs_dev, const l
     return HD_OK;
 }
 
-// ----------------------------------------------------------------------------- sampling maths
-
-static NoiseSrc make_noise(const float* raw_x, const float* raw_h, int rows, uint64_t seed, uint64_t base,
-                           uint32_t draw, int share) {
-    NoiseSrc n;
-    n.raw_x = raw_x; n.raw_h = raw_h; n.rows = rows; n.seed = seed; n.sample_base = base; n.draw = draw; n.share = share;
-    return n;
-}
-
-static int step_impl(hd_handle* h, hd_topology* t, const float* zt, const float* eps, const float* coef, int coef_rows,
-                     const NoiseSrc& ns, int mol, float* zs, int out_stride, const int* step_ptr,
-                     const uint32_t* draw_ptr, hipStream_t s, const unsigned long long* base_ptr = nullptr,
-                     int form = 0, int raw_step0 = 0) {
-    ProfScope ps(h, s, 2);
-    StepArgs a;
-    a.raw_step0 = raw_step0;
-    a.zt = zt; a.eps = eps; a.coef = coef; a.nm = t->nm_bytes; a.zs = zs; a.noise = ns; a.draw_ptr = draw_ptr;
-    a.step_ptr = step_ptr; a.base_ptr = base_ptr; a.coef_rows = coef_rows; a.B = t->B; a.N = t->N; a.D = h->D; a.F = h->F;
-    a.mol = mol; a.out_stride = out_stride;
-    if (form == 0) hipLaunchKernelGGL(k_post_step<0>, dim3(t->B), dim3(256), (size_t)a.mol * a.D * sizeof(float), s, a);
-    else hipLaunchKernelGGL(k_post_step<1>, dim3(t->B), dim3(256), (size_t)a.mol * a.D * sizeof(float), s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
-
-extern "C" int hd_posterior_step(hd_handle* h, hd_topology* topo, const float* zt, const float* eps, const float* coef,
-                                 int coef_rows, const float* raw_x, const float* raw_h, int noise_rows, int mol_shape,
-                                 float* zs, void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_posterior_step: null handle/topology");
-    if (!zt || !eps || !coef || !raw_x || !raw_h || !zs) return fail(HD_E_INVALID, "hd_posterior_step: null tensor");
-    if (coef_rows != 1 && coef_rows != topo->B) return fail(HD_E_INVALID, "hd_posterior_step: coef_rows must be 1 or B");
-    if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_posterior_step: noise_rows must be 1 or B");
-    const int mol = (mol_shape < 0 || mol_shape > topo->N) ? topo->N : mol_shape;
-    if (zs == zt && mol != topo->N) return fail(HD_E_INVALID, "hd_posterior_step: in-place needs mol_shape == N");
-    if ((size_t)mol * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_posterior_step: N * D floats exceed one workgroup's LDS");
-    HIP_TRY(hipSetDevice(h->device));
-    topo_use(topo, (hipStream_t)stream);
-    return step_impl(h, topo, zt, eps, coef, coef_rows, make_noise(raw_x, raw_h, noise_rows, 0, 0, 0, 0), mol, zs, mol,
-                     nullptr, nullptr, (hipStream_t)stream);
-}
-
-// the multistep form of the step: `coef` device rows [K][5] read at *step_ptr (k_solver.hpp), or the host row by value
-static int solver_launch(hd_handle* h, hd_topology* t, const float* zt, const float* eps, const float* coef, const float* row5,
-                         const float* x_prev, float* x_out, int mol, float* zs, const int* step_ptr, hipStream_t s) {
-    ProfScope ps(h, s, 2);
-    SolverArgs a;
-    a.zt = zt; a.eps = eps; a.coef = coef; a.nm = t->nm_bytes; a.x_prev = x_prev; a.x_out = x_out; a.zs = zs; a.step_ptr = step_ptr;
-    for (int k = 0; k < 5; ++k) a.row[k] = row5 ? row5[k] : 0.f;
-    a.B = t->B; a.N = t->N; a.D = h->D; a.mol = mol;
-    hipLaunchKernelGGL(k_multistep_step, dim3(t->B), dim3(256), (size_t)mol * a.D * sizeof(float), s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
-
-extern "C" int hd_multistep_step(hd_handle* h, hd_topology* topo, const float* zt, const float* eps, const float* row5,
-                                 const float* x_prev, float* x_out, float* zs, void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_multistep_step: null handle/topology");
-    if (!zt || !eps || !row5 || !x_out || !zs) return fail(HD_E_INVALID, "hd_multistep_step: null tensor");
-    if (row5[2] != 0.f && !x_prev) return fail(HD_E_INVALID, "hd_multistep_step: a row with c2 != 0 needs x_prev");
-    if (x_out == zt || x_out == eps || x_out == zs || zs == eps || (x_prev && (zs == x_prev || x_prev == zt || x_prev == eps)))
-        return fail(HD_E_INVALID, "hd_multistep_step: only zs == zt and x_out == x_prev may alias");
-    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_multistep_step: N * D floats exceed one workgroup's LDS");
-    HIP_TRY(hipSetDevice(h->device));
-    topo_use(topo, (hipStream_t)stream);
-    return solver_launch(h, topo, zt, eps, nullptr, row5, x_prev, x_out, topo->N, zs, nullptr, (hipStream_t)stream);
-}
-
-extern "C" int hd_final_decode(hd_handle* h, hd_topology* topo, const float* z0, const float* eps, const float* coef3,
-                               const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed,
-                               uint64_t sample_id_base, uint32_t draw, int share_rows, float* x, float* hfeat,
-                               void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_final_decode: null handle/topology");
-    if (!z0 || !eps || !coef3 || !x || !hfeat) return fail(HD_E_INVALID, "hd_final_decode: null tensor");
-    if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, "hd_final_decode: raw_x and raw_h go together");
-    if (raw_x && noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_final_decode: noise_rows must be 1 or B");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
-    ProfScope ps(h, s, 2);
-    DecodeArgs a;
-    a.z0 = z0; a.eps = eps; a.nm = topo->nm_bytes; a.x = x; a.hfeat = hfeat;
-    a.noise = make_noise(raw_x, raw_h, noise_rows, seed, sample_id_base, draw, share_rows);
-    a.sigma_0 = coef3[0]; a.alpha_0 = coef3[1]; a.sigma_x = coef3[2];
-    a.B = topo->B; a.N = topo->N; a.D = h->D; a.F = h->F;
-    hipLaunchKernelGGL(k_final_decode, dim3((topo->B + 3) / 4), dim3(256), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
-
-extern "C" int hd_noise(hd_handle* h, hd_topology* topo, const float* raw_x, const float* raw_h, int noise_rows,
-                        uint64_t seed, uint64_t sample_id_base, uint32_t draw, int share_rows, float* z, void* stream) {
-    if (!h || !topo || !z) return fail(HD_E_INVALID, "hd_noise: null argument");
-    if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, "hd_noise: raw_x and raw_h go together");
-    if (raw_x && noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_noise: noise_rows must be 1 or B");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
-    ProfScope ps(h, s, 2);
-    NoiseArgs a;
-    a.nm = topo->nm_bytes; a.z = z; a.noise = make_noise(raw_x, raw_h, noise_rows, seed, sample_id_base, draw, share_rows);
-    a.B = topo->B; a.N = topo->N; a.D = h->D; a.F = h->F;
-    hipLaunchKernelGGL(k_noise, dim3((topo->B + 3) / 4), dim3(256), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
-
-// The one writer of path tables - the caller's or the handle's every-step ones: K validated transitions t_idx[k] -> s_idx[k],
-// their rows of `row_width` floats and, for ancestral paths that inpaint, the inpainting rows.
-static int set_path_tables(hd_handle* h, PathTables& pt, int K, const int* t_idx, const int* s_idx, const float* rows, int row_width,
-                           const float* rows_ip, int form, bool up) {
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
-    hipFree(pt.d_path_t); hipFree(pt.d_path_s); hipFree(pt.d_path_coef); hipFree(pt.d_path_coef_ip);
-    pt.d_path_t = pt.d_path_s = nullptr; pt.d_path_coef = pt.d_path_coef_ip = nullptr;
-    pt.path_sched_gen = 0; pt.path_K = 0;
-    pt.path_t_h.assign(t_idx, t_idx + K);
-    pt.path_s_h.assign(s_idx, s_idx + K);
-    if (form == 2) {
-        pt.path_c2_h.resize((size_t)K);
-        for (int k = 0; k < K; ++k) pt.path_c2_h[(size_t)k] = rows[(size_t)row_width * k + 2];
-    }
-    HD_TRY(dev_upload(&pt.d_path_t, pt.path_t_h));
-    HD_TRY(dev_upload(&pt.d_path_s, pt.path_s_h));
-    HD_TRY(dev_upload(&pt.d_path_coef, std::vector<float>(rows, rows + (size_t)row_width * K)));
-    if (rows_ip) HD_TRY(dev_upload(&pt.d_path_coef_ip, std::vector<float>(rows_ip, rows_ip + (size_t)4 * K)));
-    pt.path_K = K; pt.path_form = form; pt.path_up = up;
-    pt.path_sched_gen = h->sched_gen;
-    pt.path_gen++;                             // captured graphs hold the old table addresses
-    return HD_OK;
-}
-
-// rows [T][4] of the schedule in the order of the every-step tables: position k is step s = T - 1 - k
-static std::vector<float> rows_reversed(const float* coef4, int T) {
-    std::vector<float> r((size_t)4 * T);
-    for (int k = 0; k < T; ++k) std::copy(coef4 + (size_t)4 * (T - 1 - k), coef4 + (size_t)4 * (T - k), r.begin() + (size_t)4 * k);
-    return r;
-}
-
-extern "C" int hd_set_schedule(hd_handle* h, int T, const float* tau, const float* coef4) {
-    if (!h || !tau || !coef4 || T < 1) return fail(HD_E_INVALID, "hd_set_schedule: bad argument");
-    h->T = 0;                                  // not set until everything below is in place
-    h->sched_gen++;                            // captured graphs hold the old table addresses
-    // the every-step tables: the identity path T -> T - 1 -> ... -> 0 with the caller's rows (row s of coef4 is the step to s)
-    std::vector<int> t_idx((size_t)T), s_idx((size_t)T);
-    for (int k = 0; k < T; ++k) { t_idx[(size_t)k] = T - k; s_idx[(size_t)k] = T - 1 - k; }
-    HD_TRY(set_path_tables(h, h->every, T, t_idx.data(), s_idx.data(), rows_reversed(coef4, T).data(), 4, nullptr, 0, false));
-    hipFree(h->d_tau);                         // behind set_path_tables' device synchronisation
-    h->d_tau = nullptr;
-    h->tau_h.assign(tau, tau + T + 1);
-    HD_TRY(dev_upload(&h->d_tau, h->tau_h));
-    h->T = T;
-    return HD_OK;
-}
-
-// ----------------------------------------------------------------------------- the replay scaffold of the captured loops
-//
-// The two device loops - the path loop (hd_sample_path*, and hd_sample_loop / hd_sample_loop_inpaint, which run it on the handle's
-// every-step tables) and hd_nll_terms - have the same two halves.  Plain launches: the host walks the steps and passes position,
-// draw and sample base by value.  use_graph: ONE transition / term is captured into a hipGraph that reads them from the handle's
-// device words, works on library-owned copies of every tensor (the caller's move between calls) and is kept in a slot of the
-// topology until something in its key changes.  A loop's own part is its key, its slot and build counter, its staging copies,
-// its state kernel and the emitter of its body; the order of a replaying call is
-//     replay_enter -> (grow / allocate owned buffers) -> replay_evict -> replay_capture -> staging copies, state kernel
-//                  -> replay_run -> copy back -> replay_leave
-// No host synchronisation on the way unless a stale graph or buffer has to go: the caller's stream is ordered against the replay
-// stream with events.  Everything a body emits is a kernel node.
-
-// What an emitted step / transition / term works on.  Plain launches: the caller's tensors, and host values for the position
-// (`row`, `ro`), the draw and the first sample id.  The captured body: the library-owned copies, the handle's device words, and 0
-// for the host values (loop_io_captured).  Fields a loop does not use stay null.
-struct LoopIO {
-    float* z;
-    const float *ctx, *tcur;                   // context; network time: a row of d_tau, or the d_tcur word
-    const float *ctx_u, *w;                    // guidance: second context, scales
-    const uint8_t* fixed;                      // inpainting: mask, known values
-    const float* known;
-    const float* xh;                           // scoring: data, accumulator, e_t table
-    double* acc;
-    float* err;
-    int row;                                   // row of the loop's coefficient table
-    size_t ro;                                 // injected noise: molecule rows before this position's
-    uint32_t draw;
-    uint64_t base;
-    const int* step;                           // device words (null: plain launches)
-    const uint32_t* draw_w;
-    const unsigned long long* base_w;
-    hipStream_t s;
-};
-
-static LoopIO loop_io_captured(const hd_handle* h, const uint32_t* draw_w, hipStream_t rs) {
-    LoopIO io{};
-    io.tcur = h->d_tcur; io.step = h->d_step; io.draw_w = draw_w; io.base_w = h->d_base; io.s = rs;
-    return io;
-}
-
-// The replay stream (the legacy NULL stream cannot be captured: the handle's own stream stands in, ordered behind it), made to
-// wait for the handle's latest replay.  The replay state (d_step, d_draw, d_tcur, d_base, d_ipdraw) belongs to the handle: a replay
-// issued on another stream - another topology of this handle, or the same one from another caller stream - must have finished
-// before this one touches it.
-static int replay_enter(hd_handle* h, hipStream_t s, hipStream_t* rs) {
-    *rs = s;
-    if (s == nullptr) {
-        if (!h->own_stream) HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-        *rs = h->own_stream;
-        HIP_TRY(hipEventRecord(h->ev_in, s));
-        HIP_TRY(hipStreamWaitEvent(*rs, h->ev_in, 0));
-    }
-    if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(*rs, h->ev_last, 0));
-    return HD_OK;
-}
-
-// host wait before something a captured graph holds is freed: a replay may still be running, on any stream
-static int replay_quiesce(hd_handle* h, hipStream_t rs) {
-    if (h->ev_last_set) HIP_TRY(hipEventSynchronize(h->ev_last));
-    HIP_TRY(hipStreamSynchronize(rs));
-    return HD_OK;
-}
-
-// drop the slot's graph when it was built for another key
-template <typename Key>
-static int replay_evict(hd_handle* h, hipStream_t rs, hipGraphExec_t* gx, const Key& have, const Key& want) {
-    if (!*gx || have == want) return HD_OK;
-    HD_TRY(replay_quiesce(h, rs));
-    graph_drop(gx);
-    return HD_OK;
-}
-
-// Capture what `body` emits on rs (an int() callable: kernel launches only, profiling brackets off) and instantiate it into the slot.
-template <typename Body>
-static int replay_capture(hd_handle* h, hipStream_t rs, hipGraphExec_t* gx, Body body) {
-    hipGraph_t graph = nullptr;
-    HIP_TRY(hipStreamBeginCapture(rs, hipStreamCaptureModeThreadLocal));
-    const int was_prof = h->prof;
-    h->prof = 0;
-    const int rc = body();
-    const hipError_t ce = hipStreamEndCapture(rs, &graph);
-    h->prof = was_prof;
-    if (rc != HD_OK) { if (graph) hipGraphDestroy(graph); return rc; }
-    if (ce != hipSuccess) return fail(HD_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-    const hipError_t ie = hipGraphInstantiate(gx, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    if (ie != hipSuccess) { *gx = nullptr; return fail(HD_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
-    return HD_OK;
-}
-
-static int replay_run(hipGraphExec_t gx, int n, hipStream_t rs) {
-    for (int k = 0; k < n; ++k) {
-        const hipError_t le = hipGraphLaunch(gx, rs);
-        if (le != hipSuccess) return fail(HD_E_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(le));
-    }
-    return HD_OK;
-}
-
-// mark the end of this replay for the handle's next one, and hand back to the caller's stream
-static int replay_leave(hd_handle* h, hipStream_t s, hipStream_t rs) {
-    HIP_TRY(hipEventRecord(h->ev_last, rs));
-    h->ev_last_set = true;
-    if (rs != s) {
-        HIP_TRY(hipEventRecord(h->ev_out, rs));
-        HIP_TRY(hipStreamWaitEvent(s, h->ev_out, 0));
-    }
-    return HD_OK;
-}
-
-// ----------------------------------------------------------------------------- fragment-constrained sampling (inpainting)
-
-extern "C" int hd_set_inpaint_schedule(hd_handle* h, int T, const float* coef4) {
-    if (!h || !coef4 || T < 1) return fail(HD_E_INVALID, "hd_set_inpaint_schedule: bad argument");
-    if (h->T < 1) return fail(HD_E_STATE, "hd_set_inpaint_schedule: schedule not set (hd_set_schedule)");
-    if (T != h->T) return fail(HD_E_INVALID, "hd_set_inpaint_schedule: T differs from the schedule's (hd_set_schedule)");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    hipFree(h->every.d_path_coef_ip);
-    h->every.d_path_coef_ip = nullptr;
-    h->ip_sched_gen = 0;
-    HD_TRY(dev_upload(&h->every.d_path_coef_ip, rows_reversed(coef4, T)));
-    h->ip_sched_gen = h->sched_gen;
-    h->ip_gen++;                               // captured graphs hold the old table address
-    return HD_OK;
-}
-
-static int inpaint_launch(hd_handle* h, hd_topology* t, bool jump, float* z, const uint8_t* fixed, const float* known, uint64_t seed,
-                          uint64_t base, uint32_t draw, int step, const uint32_t* draw_ptr, const int* step_ptr,
-                          const unsigned long long* base_ptr, hipStream_t s, const float* coef) {
-    ProfScope ps(h, s, 2);
-    InpaintArgs a;
-    a.z = z; a.nm = t->nm_bytes; a.fixed = fixed; a.known = known; a.coef = coef; a.seed = seed; a.sample_base = base;
-    a.draw = draw; a.step = step; a.draw_ptr = draw_ptr; a.step_ptr = step_ptr; a.base_ptr = base_ptr;
-    a.B = t->B; a.N = t->N; a.D = h->D;
-    const size_t lds = (size_t)t->N * h->D * sizeof(float);
-    if (jump) hipLaunchKernelGGL(k_inpaint_jump, dim3(t->B), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL(k_inpaint_replace, dim3(t->B), dim3(256), lds, s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
-
-// The checks every inpainting loop makes on its arguments, in the order the header documents.  hd_sample_path_guided words two
-// of them its own way, so those texts come from the caller.
-static int inpaint_args_check(const char* who, const hd_handle* h, const hd_topology* topo, const float* raw_x, const float* raw_h,
-                              int noise_rows, int mol_shape, int resamplings, const float* context, const char* raw_msg,
-                              const char* rows_msg) {
-    const std::string w(who);
-    if (raw_x || raw_h) return fail(HD_E_INVALID, w + raw_msg);
-    if (noise_rows != topo->B) return fail(HD_E_INVALID, w + rows_msg);
-    if (mol_shape >= 0 && mol_shape < topo->N) return fail(HD_E_INVALID, w + ": fixed tail rows (mol_shape < N) are not supported");
-    if (resamplings < 1) return fail(HD_E_INVALID, w + ": resamplings must be >= 1");
-    if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, w + ": context required");
-    if (!h->cfg.condition_time) return fail(HD_E_INVALID, w + ": needs a time-conditioned model");
-    if (((unsigned long long)h->T + 2ULL) * 3ULL * (unsigned long long)resamplings > 0xffffffffULL)
-        return fail(HD_E_INVALID, w + ": (T + 2) * 3 * resamplings exceeds the 32-bit draw index");
-    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, w + ": N * D floats exceed one workgroup's LDS");
-    return HD_OK;
-}
-static const char* const kIpRawMsg = ": injected noise is not supported (counter-based generator only)";
-static const char* const kIpRowsMsg = ": noise_rows must be B";
-
-// ... and on the path, before them
-static int inpaint_path_check(const char* who, const hd_handle* h, const char* form_msg) {
-    const std::string w(who);
-    if (h->path.path_up) return fail(HD_E_INVALID, w + ": the path ascends (hd_set_path_up): inversion fixes no fragments");
-    if (h->path.path_form != 0) return fail(HD_E_INVALID, w + form_msg);
-    if (!h->path.d_path_coef_ip) return fail(HD_E_STATE, w + ": the path was set without inpainting rows (hd_set_path)");
-    return HD_OK;
-}
-
-// graph replay: room for the draw words of a step's nd = 3 * resamplings noise streams, and the library-owned mask / known values
-static int grow_ipdraw(hd_handle* h, hipStream_t rs, int nd) {
-    if (nd <= h->ipdraw_cap) return HD_OK;
-    HD_TRY(replay_quiesce(h, rs));                           // graphs that hold the old address go stale (ip_gen)
-    hipFree(h->d_ipdraw);
-    h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
-    HD_TRY(dev_alloc(&h->d_ipdraw, (size_t)nd));
-    h->ipdraw_cap = nd;
-    h->ip_gen++;
-    return HD_OK;
-}
-
-static int inpaint_buffers(const hd_handle* h, hd_topology* t) {
-    const size_t BN = (size_t)t->B * t->N;
-    if (!t->ip_fixed) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->ip_fixed), BN));
-    if (!t->ip_known) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->ip_known), BN * h->D * sizeof(float)));
-    return HD_OK;
-}
-
-// Round j of R behind its posterior step: put the known rows back at the arrival level and - except in the last round - jump back
-// to the departure level.  Noise stream 3 * j + m of `stride` draws: a host draw, or the word io.draw_w[3 * j + m].
-static int inpaint_round(hd_handle* h, hd_topology* t, const LoopIO& io, int j, int R, uint32_t stride, uint64_t seed,
-                         const float* coef_ip) {
-    for (int m = 1; m <= (j < R - 1 ? 2 : 1); ++m)
-        HD_TRY(inpaint_launch(h, t, m == 2, io.z, m == 1 ? io.fixed : nullptr, m == 1 ? io.known : nullptr, seed, io.base,
-                              io.step ? 0u : stride * (uint32_t)(3 * j + m) + io.draw, io.row, io.step ? io.draw_w + 3 * j + m : nullptr,
-                              io.step, io.base_w, io.s, coef_ip));
-    return HD_OK;
-}
-
-// ----------------------------------------------------------------------------- few-step sampling: the loop on a path
-
-extern "C" int hd_set_path(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* coef4, int form,
-                           const float* coef4_inpaint) {
-    if (form != 0 && form != 1) return fail(HD_E_INVALID, "hd_set_path: form must be 0 (ancestral rows) or 1 (linear rows)");
-    if (form == 1 && coef4_inpaint) return fail(HD_E_INVALID, "hd_set_path: inpainting rows go with ancestral rows only (form 0)");
-    if (!h || !t_idx || !s_idx || !coef4 || K < 1) return fail(HD_E_INVALID, "hd_set_path: bad argument");
-    if (h->T < 1) return fail(HD_E_STATE, "hd_set_path: schedule not set (hd_set_schedule)");
-    if (K > h->T) return fail(HD_E_INVALID, "hd_set_path: more transitions than the schedule has steps");
-    for (int k = 0; k < K; ++k) {
-        if (t_idx[k] > h->T || s_idx[k] < 0 || s_idx[k] >= t_idx[k])
-            return fail(HD_E_INVALID, "hd_set_path: need 0 <= s_idx[k] < t_idx[k] <= T");
-        if (k > 0 && t_idx[k] != s_idx[k - 1]) return fail(HD_E_INVALID, "hd_set_path: transition k must start where k - 1 arrived");
-    }
-    return set_path_tables(h, h->path, K, t_idx, s_idx, coef4, 4, coef4_inpaint, form, false);
-}
-
-// An ascending path into the same tables: transition k leaves from_idx[k] (path_t: network time, as for descending paths) and
-// arrives at to_idx[k] (path_s).  Linear rows with c == 0, so k_post_step<1> never looks at the draw word T - to_idx[k].
-extern "C" int hd_set_path_up(hd_handle* h, int K, const int* from_idx, const int* to_idx, const float* coef4) {
-    if (!from_idx || !to_idx || !coef4 || K < 1) return fail(HD_E_INVALID, "hd_set_path_up: bad argument");
-    for (int k = 0; k < K; ++k) {
-        if (coef4[(size_t)4 * k + 2] != 0.f || coef4[(size_t)4 * k + 3] != 0.f)
-            return fail(HD_E_INVALID, "hd_set_path_up: rows must be {a, b, 0, 0} (the inversion draws nothing)");
-        if (from_idx[k] < 0 || from_idx[k] >= to_idx[k]) return fail(HD_E_INVALID, "hd_set_path_up: need 0 <= from_idx[k] < to_idx[k] <= T");
-        if (k > 0 && from_idx[k] != to_idx[k - 1]) return fail(HD_E_INVALID, "hd_set_path_up: transition k must start where k - 1 arrived");
-    }
-    if (!h) return fail(HD_E_INVALID, "hd_set_path_up: null handle");
-    if (h->T < 1) return fail(HD_E_STATE, "hd_set_path_up: schedule not set (hd_set_schedule)");
-    if (K > h->T) return fail(HD_E_INVALID, "hd_set_path_up: more transitions than the schedule has steps");
-    if (to_idx[K - 1] > h->T) return fail(HD_E_INVALID, "hd_set_path_up: need 0 <= from_idx[k] < to_idx[k] <= T");
-    return set_path_tables(h, h->path, K, from_idx, to_idx, coef4, 4, nullptr, 1, true);
-}
-
-// A descending path with multistep rows {a, b, c2, p, q} (form 2, k_solver.hpp) into the same tables.
-extern "C" int hd_set_path_multistep(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* rows5) {
-    if (!h || !t_idx || !s_idx || !rows5 || K < 1) return fail(HD_E_INVALID, "hd_set_path_multistep: bad argument");
-    if (h->T < 1) return fail(HD_E_STATE, "hd_set_path_multistep: schedule not set (hd_set_schedule)");
-    if (K > h->T) return fail(HD_E_INVALID, "hd_set_path_multistep: more transitions than the schedule has steps");
-    for (int k = 0; k < K; ++k) {
-        if (t_idx[k] > h->T || s_idx[k] < 0 || s_idx[k] >= t_idx[k])
-            return fail(HD_E_INVALID, "hd_set_path_multistep: need 0 <= s_idx[k] < t_idx[k] <= T (a multistep path descends)");
-        if (k > 0 && t_idx[k] != s_idx[k - 1])
-            return fail(HD_E_INVALID, "hd_set_path_multistep: transition k must start where k - 1 arrived");
-    }
-    if (rows5[2] != 0.f) return fail(HD_E_INVALID, "hd_set_path_multistep: c2 of row 0 must be 0 (the first transition has no history)");
-    return set_path_tables(h, h->path, K, t_idx, s_idx, rows5, 5, nullptr, 2, false);
-}
-
-extern "C" long long hd_path_graph_builds(const hd_topology* topo) { return topo ? topo->path_builds : -1; }
-
-// ----------------------------------------------------------------------------- recording the trajectory of a path loop
-
-extern "C" int hd_set_chain(hd_handle* h, int K, const int* frame_of, const float* alpha_sigma, int frames) {
-    if (!h || !frame_of || K < 1 || frames < 1) return fail(HD_E_INVALID, "hd_set_chain: bad argument");
-    if (h->path.path_K < 1 || h->path.path_sched_gen != h->sched_gen) return fail(HD_E_STATE, "hd_set_chain: path not set for the current schedule (hd_set_path)");
-    if (K != h->path.path_K) return fail(HD_E_INVALID, "hd_set_chain: K differs from the path's (hd_set_path)");
-    for (int k = 0; k < K; ++k)
-        if (frame_of[k] < -1 || frame_of[k] >= frames) return fail(HD_E_INVALID, "hd_set_chain: need -1 <= frame_of[k] < frames");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
-    hipFree(h->d_chain_frame); hipFree(h->d_chain_as);
-    h->d_chain_frame = nullptr; h->d_chain_as = nullptr;
-    h->chain_path_gen = 0;
-    HD_TRY(dev_upload(&h->d_chain_frame, std::vector<int>(frame_of, frame_of + K)));
-    if (alpha_sigma) HD_TRY(dev_upload(&h->d_chain_as, std::vector<float>(alpha_sigma, alpha_sigma + (size_t)2 * K)));
-    h->chain_frames = frames;
-    h->chain_path_gen = h->path.path_gen;
-    h->chain_gen++;                            // captured graphs hold the old table addresses
-    return HD_OK;
-}
-
-extern "C" int hd_chain_attach(hd_topology* topo, float* chain, int frames, int what, float nv0, float nv1, float nb1) {
-    if (!topo || !chain || frames < 1) return fail(HD_E_INVALID, "hd_chain_attach: null topology / sink, or frames < 1");
-    if (what != 0 && what != 1) return fail(HD_E_INVALID, "hd_chain_attach: what must be 0 (the state) or 1 (the data prediction)");
-    topo->chain_dst = chain; topo->chain_frames = frames; topo->chain_what = what;
-    topo->chain_nv0 = nv0; topo->chain_nv1 = nv1; topo->chain_nb1 = nb1;
-    return HD_OK;
-}
-
-extern "C" int hd_chain_detach(hd_topology* topo) {
-    if (topo) topo->chain_dst = nullptr;
-    return HD_OK;
-}
-
-extern "C" long long hd_chain_graph_builds(const hd_topology* topo) { return topo ? topo->chain_builds : -1; }
-
-// ----------------------------------------------------------------------------- restraints on the data prediction of a path loop
-
-extern "C" int hd_set_restraint(hd_handle* h, int K, const float* rows4) {
-    if (!h || !rows4 || K < 1) return fail(HD_E_INVALID, "hd_set_restraint: bad argument");
-    if (h->path.path_K < 1 || h->path.path_sched_gen != h->sched_gen)
-        return fail(HD_E_STATE, "hd_set_restraint: path not set for the current schedule (hd_set_path)");
-    if (K != h->path.path_K) return fail(HD_E_INVALID, "hd_set_restraint: K differs from the path's (hd_set_path)");
-    for (int k = 0; k < K; ++k) {
-        const float *r = rows4 + (size_t)4 * k;
-        if (!(r[0] > 0.f) || !(r[1] >= 0.f) || !(r[2] - r[2] == 0.f) || !(r[3] > 0.f))
-            return fail(HD_E_INVALID, "hd_set_restraint: need alpha_t > 0, sigma_t >= 0, a finite lambda_k and clip_k > 0 (inf: no clip)");
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old rows
-    if (!h->d_rs_rows || h->rs_K != K) {                // same K: the table stays where captured transitions expect it
-        hipFree(h->d_rs_rows);
-        h->d_rs_rows = nullptr; h->rs_path_gen = 0; h->rs_K = 0;
-        HD_TRY(dev_alloc(&h->d_rs_rows, (size_t)4 * K));
-        h->rs_K = K;
-        h->rs_gen++;
-    }
-    HIP_TRY(hipMemcpy(h->d_rs_rows, rows4, (size_t)4 * K * sizeof(float), hipMemcpyHostToDevice));
-    h->rs_path_gen = h->path.path_gen;
-    return HD_OK;
-}
-
-// one library-owned table of the topology: grown when `count` exceeds its capacity (then *moved is set), filled from `src`
-template <typename T>
-static int rs_table(T** buf, size_t* cap, const T* src, size_t count, bool* moved, hipStream_t s) {
-    if (count > *cap || !*buf) {
-        HIP_TRY(hipDeviceSynchronize());                // a replay may still read the old table
-        if (*buf) (void)hipFree(*buf);
-        *buf = nullptr; *cap = 0;
-        HD_TRY(dev_alloc(buf, count));
-        *cap = std::max<size_t>(count, 1);
-        *moved = true;
-    }
-    if (count) HIP_TRY(hipMemcpyAsync(*buf, src, count * sizeof(T), hipMemcpyDefault, s));
-    return HD_OK;
-}
-
-extern "C" int hd_restraint_attach(hd_topology* topo, const float* obs, int obs_rows, int P, const int* pair_idx, const float* pair_f,
-                                   int pair_rows, int Q, const int* anc_idx, const float* anc_f, int anc_rows, int A,
-                                   const float* scale, int scale_rows, float nv0, void* stream) {
-    if (!topo) return fail(HD_E_INVALID, "hd_restraint_attach: null topology");
-    if (P < 0 || Q < 0 || A < 0) return fail(HD_E_INVALID, "hd_restraint_attach: P, Q, A must be >= 0");
-    if ((P > 0 && !obs) || (Q > 0 && (!pair_idx || !pair_f)) || (A > 0 && (!anc_idx || !anc_f)) || !scale)
-        return fail(HD_E_INVALID, "hd_restraint_attach: null table / scale");
-    const int B = topo->B;
-    for (int r : {obs_rows, pair_rows, anc_rows, scale_rows})
-        if (r != 1 && r != B) return fail(HD_E_INVALID, "hd_restraint_attach: every table has 1 row (shared) or B rows");
-    if (!(nv0 > 0.f) || !(nv0 - nv0 == 0.f)) return fail(HD_E_INVALID, "hd_restraint_attach: nv0 must be positive and finite");
-    if ((size_t)topo->N * 3 * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_restraint_attach: N * 3 floats exceed one workgroup's LDS");
-    HIP_TRY(hipSetDevice(topo->device));
-    hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
-    topo->rs_on = false;
-    bool moved = false;
-    HD_TRY(rs_table(&topo->rs_obs, &topo->rs_cap[0], obs, (size_t)obs_rows * P * 5, &moved, s));
-    HD_TRY(rs_table(&topo->rs_pair_idx, &topo->rs_cap[1], pair_idx, (size_t)pair_rows * Q * 2, &moved, s));
-    HD_TRY(rs_table(&topo->rs_pair_f, &topo->rs_cap[2], pair_f, (size_t)pair_rows * Q * 3, &moved, s));
-    HD_TRY(rs_table(&topo->rs_anc_idx, &topo->rs_cap[3], anc_idx, (size_t)anc_rows * A, &moved, s));
-    HD_TRY(rs_table(&topo->rs_anc_f, &topo->rs_cap[4], anc_f, (size_t)anc_rows * A * 5, &moved, s));
-    HD_TRY(rs_table(&topo->rs_scale, &topo->rs_cap[5], scale, (size_t)scale_rows, &moved, s));
-    if (!topo->rs_step) { HD_TRY(dev_alloc(&topo->rs_step, (size_t)B * topo->N * 3)); moved = true; }
-    if (moved || obs_rows != topo->rs_obs_rows || P != topo->rs_P || pair_rows != topo->rs_pair_rows || Q != topo->rs_Q ||
-        anc_rows != topo->rs_anc_rows || A != topo->rs_A || scale_rows != topo->rs_scale_rows || nv0 != topo->rs_nv0)
-        topo->rs_gen++;
-    topo->rs_obs_rows = obs_rows; topo->rs_P = P; topo->rs_pair_rows = pair_rows; topo->rs_Q = Q; topo->rs_anc_rows = anc_rows;
-    topo->rs_A = A; topo->rs_scale_rows = scale_rows; topo->rs_nv0 = nv0;
-    topo->rs_on = true;
-    return HD_OK;
-}
-
-extern "C" int hd_restraint_detach(hd_topology* topo) {
-    if (topo) topo->rs_on = false;
-    return HD_OK;
-}
-
-static RestraintTables restraint_tables(const hd_topology* t) {
-    RestraintTables r;
-    r.obs = t->rs_obs; r.pair_idx = t->rs_pair_idx; r.pair_f = t->rs_pair_f; r.anc_idx = t->rs_anc_idx; r.anc_f = t->rs_anc_f;
-    r.obs_rows = t->rs_obs_rows; r.P = t->rs_P; r.pair_rows = t->rs_pair_rows; r.Q = t->rs_Q; r.anc_rows = t->rs_anc_rows; r.A = t->rs_A;
-    return r;
-}
-
-// The update of one transition on eps (in place when out == eps): `rows` the device table read at position *step / k, or the host row.
-static int restrain_launch(hd_handle* h, hd_topology* t, const float* z, const float* eps, float* out, const float* rows,
-                           const float* row4, const int* step, int k, hipStream_t s) {
-    ProfScope ps(h, s, 2);
-    RestrainArgs a;
-    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.t = restraint_tables(t); a.scale = t->rs_scale;
-    a.rows = rows;
-    for (int i = 0; i < 4; ++i) a.row[i] = row4 ? row4[i] : 0.f;
-    a.step_ptr = step; a.k = k; a.step = t->rs_step; a.nv0 = t->rs_nv0; a.scale_rows = t->rs_scale_rows;
-    a.B = t->B; a.N = t->N; a.D = h->D;
-    hipLaunchKernelGGL(k_restrain_eps, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
-
-extern "C" int hd_restrain_eps(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4, float* out,
-                               void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_restrain_eps: null handle/topology");
-    if (!z || !eps || !row4 || !out) return fail(HD_E_INVALID, "hd_restrain_eps: null tensor / row");
-    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restrain_eps: no restraints attached to the topology (hd_restraint_attach)");
-    if (!(row4[0] > 0.f) || !(row4[1] >= 0.f) || !(row4[2] - row4[2] == 0.f) || !(row4[3] > 0.f))
-        return fail(HD_E_INVALID, "hd_restrain_eps: need alpha_t > 0, sigma_t >= 0, a finite lambda and clip > 0 (inf: no clip)");
-    const size_t per = (size_t)topo->B * topo->N * h->D;
-    if (out < z + per && z < out + per) return fail(HD_E_INVALID, "hd_restrain_eps: out may not overlap z");
-    if (out != eps && out < eps + per && eps < out + per)
-        return fail(HD_E_INVALID, "hd_restrain_eps: out may be eps itself, not a shifted overlap of it");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
-    return restrain_launch(h, topo, z, eps, out, nullptr, row4, nullptr, 0, s);
-}
-
-extern "C" int hd_restraint_energy(hd_handle* h, hd_topology* topo, const float* x, double* out3, void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_restraint_energy: null handle/topology");
-    if (!x || !out3) return fail(HD_E_INVALID, "hd_restraint_energy: null tensor");
-    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restraint_energy: no restraints attached to the topology (hd_restraint_attach)");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
-    ProfScope ps(h, s, 2);
-    RestraintEnergyArgs a;
-    a.x = x; a.nm = topo->nm_bytes; a.t = restraint_tables(topo); a.out = out3; a.B = topo->B; a.N = topo->N;
-    hipLaunchKernelGGL(k_restraint_energy, dim3(topo->B), dim3(256), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
-
-// Classifier-free guidance of a path loop: every network call becomes two (context, then ctx_u) and k_guide_combine in place.
-struct GuideSrc {
-    const float* ctx_u;   // [B,N,C] the null (or any second) context
-    const float* w;       // device [w_rows]
-    int w_rows;
-    float phi;
-};
-
-static int guide_launch(hd_handle* h, hd_topology* t, const float* eps_c, const float* eps_u, const float* w, int w_rows, float phi,
-                        float* out, hipStream_t s) {
-    ProfScope ps(h, s, 2);
-    GuideArgs a;
-    a.eps_c = eps_c; a.eps_u = eps_u; a.w = w; a.nm = t->nm_bytes; a.out = out; a.rescale = phi; a.w_rows = w_rows;
-    a.B = t->B; a.N = t->N; a.D = h->D;
-    hipLaunchKernelGGL(k_guide_combine, dim3(t->B), dim3(256), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
-
-// the topology's second network output and the library-owned copies of the null context / the scales: one allocation
-static int guide_buffers(hd_handle* h, hd_topology* t) {
-    if (t->guide_mem) return HD_OK;
-    auto pad = [](size_t n) { return (std::max<size_t>(n, 1) + 63) & ~size_t(63); };
-    const size_t BN = (size_t)t->B * t->N;
-    const size_t n_eps = pad(BN * h->D), n_ctx = pad(BN * (size_t)std::max(1, h->cfg.context_node_nf)), n_w = pad((size_t)t->B);
-    HD_TRY(dev_alloc(&t->guide_mem, n_eps + n_ctx + n_w));
-    t->eps_u = t->guide_mem; t->ctxu_buf = t->eps_u + n_eps; t->wbuf = t->ctxu_buf + n_ctx;
-    return HD_OK;
-}
-
-// One frame of the topology's sink (hd_chain_attach) from transition io.row: the state z, or with `eps` the data prediction.
-static int chain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* eps) {
-    ProfScope ps(h, io.s, 2);
-    ChainArgs a;
-    a.z = io.z; a.eps = eps; a.nm = t->nm_bytes; a.frame_of = h->d_chain_frame; a.alsig = h->d_chain_as;
-    a.dst_w = io.step ? h->d_chain_dst : nullptr; a.dst = io.step ? nullptr : t->chain_dst; a.step_ptr = io.step; a.k = io.row;
-    a.nv0 = t->chain_nv0; a.nv1 = t->chain_nv1; a.nb1 = t->chain_nb1; a.B = t->B; a.N = t->N; a.D = h->D;
-    if (eps) hipLaunchKernelGGL(k_chain_frame<1>, dim3(t->B), dim3(256), 0, io.s, a);
-    else hipLaunchKernelGGL(k_chain_frame<0>, dim3(t->B), dim3(256), 0, io.s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
-
-// What a path loop runs on: the tables, the slot of its captured transition with the key that was built for (a recording transition
-// goes to gexec_chain instead), the count of instantiations to bump (null: not reported), and whether a sink attached to the
-// topology records.
-struct PathRun {
-    const PathTables* pt;
-    hipGraphExec_t* gx;
-    PathKey* key;
-    long long* builds;
-    bool record;
-};
-
-// The path loops: R = 0 is the plain one, R >= 1 the inpainting one with R rounds per transition; gd != NULL guides either.
-// A topology with a sink attached (hd_chain_attach) records when run.record: one more launch per transition, behind the update of
-// its last round (the state) or between that round's network call and its update (the data prediction).
-static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
-                         const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
-                         const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const PathRun& run, const GuideSrc* gd);
-
-static int path_loop(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
-                     const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
-                     const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const PathRun& run,
-                     const GuideSrc* gd = nullptr) {
-    const PathTables& pt = *run.pt;
-    if (pt.path_form != 2 || k_hi == k_lo)
-        return path_loop_run(h, topo, z, context, mol_shape, k_lo, k_hi, raw_x, raw_h, noise_rows, seed, sample_id_base, use_graph,
-                             fixed_mask, xh_known, R, s, run, gd);
-    // multistep rows: the history x^_{k_lo - 1} is the topology's - a call that starts on a row with c2 != 0 continues the call
-    // that left it, on the same path (generation) and at the position where that call ended
-    const int mol = (mol_shape < 0 || mol_shape > topo->N) ? topo->N : mol_shape;
-    if (R) return fail(HD_E_INVALID, "multistep path: inpainting takes ancestral rows only");
-    if (pt.path_c2_h[(size_t)k_lo] != 0.f && !(topo->ms_hist && topo->ms_gen == pt.path_gen && topo->ms_k == k_lo))
-        return fail(HD_E_STATE, "multistep path: transition k_lo = " + std::to_string(k_lo) + " needs the data prediction of transition "
-                    "k_lo - 1, which the last call on this topology did not leave (start at a row with c2 = 0, such as k_lo = 0, or "
-                    "continue where the last call on the same path ended)");
-    if ((size_t)mol * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "multistep path: N * D floats exceed one workgroup's LDS");
-    if (!topo->ms_hist) HD_TRY(dev_alloc(&topo->ms_hist, (size_t)topo->B * topo->N * h->D));
-    topo->ms_gen = 0;                                        // no history unless the whole range ran
-    HD_TRY(path_loop_run(h, topo, z, context, mol_shape, k_lo, k_hi, raw_x, raw_h, noise_rows, seed, sample_id_base, use_graph,
-                         fixed_mask, xh_known, R, s, run, gd));
-    topo->ms_gen = pt.path_gen; topo->ms_k = k_hi;           // stream-ordered behind this call, like z
-    return HD_OK;
-}
-
-static int path_loop_run(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
-                         const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
-                         const uint8_t* fixed_mask, const float* xh_known, int R, hipStream_t s, const PathRun& run, const GuideSrc* gd) {
-    const PathTables& pt = *run.pt;
-    const int T = h->T, K = pt.path_K, N = topo->N, form = pt.path_form;
-    const int mol = (mol_shape < 0 || mol_shape > N) ? N : mol_shape;
-    const int ms = mol_shape < 0 ? -1 : mol;
-    const int nd = 3 * R;
-    const uint32_t stride = (uint32_t)T + 2u;
-    const int share = (noise_rows == 1) ? 1 : 0;
-    const int ntr = k_hi - k_lo;
-    topo_use(topo, s);
-    if (ntr == 0) return HD_OK;
-    if (gd) HD_TRY(guide_buffers(h, topo));
-    const bool rec = run.record && topo->chain_dst != nullptr;
-    if (rec) {
-        if (!h->d_chain_frame || h->chain_path_gen != pt.path_gen)
-            return fail(HD_E_STATE, "path loop: a chain sink is attached but the chain tables are not set for the current path (hd_set_chain)");
-        if (h->chain_frames != topo->chain_frames)
-            return fail(HD_E_INVALID, "path loop: the attached sink holds " + std::to_string(topo->chain_frames) + " frames, the chain "
-                        "tables were set for " + std::to_string(h->chain_frames));
-        if (topo->chain_what == 1 && !h->d_chain_as)
-            return fail(HD_E_STATE, "path loop: recording the data prediction needs the {alpha_t, sigma_t} rows (hd_set_chain)");
-        if (mol != N) return fail(HD_E_INVALID, "path loop: a chain sink records whole molecules only (mol_shape < N)");
-    }
-    const bool rsn = run.record && topo->rs_on;
-    if (rsn) {
-        if (R) return fail(HD_E_INVALID, "path loop: restraints are attached to the topology, and inpainting takes none (it re-centres "
-                                         "on the known fragments: hd_restraint_detach)");
-        if (!h->d_rs_rows || h->rs_path_gen != pt.path_gen)
-            return fail(HD_E_STATE, "path loop: restraints are attached but their rows are not set for the current path (hd_set_restraint)");
-        if (mol != N) return fail(HD_E_INVALID, "path loop: restraints act on whole molecules only (mol_shape < N)");
-    }
-    const int rounds = R ? R : 1;
-    auto transition = [&](const LoopIO& io) -> int {         // all rounds of one transition; io.row is the path position
-        for (int j = 0; j < rounds; ++j) {
-            HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx, ms, topo->eps, io.s));
-            if (gd) {
-                HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx_u, ms, topo->eps_u, io.s));
-                HD_TRY(guide_launch(h, topo, topo->eps, topo->eps_u, io.w, gd->w_rows, gd->phi, topo->eps, io.s));
-            }
-            if (rsn) HD_TRY(restrain_launch(h, topo, io.z, topo->eps, topo->eps, h->d_rs_rows, nullptr, io.step, io.row, io.s));
-            const bool rec_z = rec && j == rounds - 1 && topo->chain_what == 0;
-            if (rec && j == rounds - 1 && topo->chain_what == 1) HD_TRY(chain_launch(h, topo, io, topo->eps));
-            if (form == 2) {
-                HD_TRY(solver_launch(h, topo, io.z, topo->eps, pt.d_path_coef + (size_t)io.row * 5, nullptr, topo->ms_hist,
-                                     topo->ms_hist, mol, io.z, io.step, io.s));
-                if (rec_z) HD_TRY(chain_launch(h, topo, io, nullptr));
-                continue;
-            }
-            NoiseSrc ns = make_noise(raw_x ? raw_x + io.ro * 3 : nullptr, raw_h ? raw_h + io.ro * h->F : nullptr, noise_rows, seed,
-                                     io.base, io.step ? 0u : stride * (uint32_t)(3 * j) + io.draw, share);
-            HD_TRY(step_impl(h, topo, io.z, topo->eps, pt.d_path_coef + (size_t)io.row * 4, 1, ns, mol, io.z, N, io.step,
-                             io.step ? io.draw_w + 3 * j : nullptr, io.s, io.base_w, form, k_lo));
-            if (R) HD_TRY(inpaint_round(h, topo, io, j, R, stride, seed, pt.d_path_coef_ip));
-            if (rec_z) HD_TRY(chain_launch(h, topo, io, nullptr));
-        }
-        return HD_OK;
-    };
-    if (!use_graph) {
-        LoopIO io{};
-        io.z = z; io.ctx = context; io.fixed = fixed_mask; io.known = xh_known; io.base = sample_id_base; io.s = s;
-        if (gd) { io.ctx_u = gd->ctx_u; io.w = gd->w; }
-        for (int k = k_lo; k < k_hi; ++k) {
-            io.row = k; io.tcur = h->d_tau + pt.path_t_h[k];
-            io.ro = (size_t)(k - k_lo) * noise_rows * mol; io.draw = (uint32_t)(T - pt.path_s_h[k]);
-            HD_TRY(transition(io));
-        }
-        return HD_OK;
-    }
-    // The path position lives in d_step; k_path_advance derives the network time, the coefficient row and the draws from the
-    // uploaded tables.
-    const size_t BN = (size_t)topo->B * N;
-    const size_t zbytes = BN * h->D * sizeof(float);
-    const size_t cbytes = BN * h->cfg.context_node_nf * sizeof(float);
-    hipStream_t rs;
-    HD_TRY(replay_enter(h, s, &rs));
-    HD_TRY(grow_ipdraw(h, rs, nd));
-    if (R) HD_TRY(inpaint_buffers(h, topo));
-    PathKey key;
-    key.raw_x = raw_x; key.raw_h = raw_h; key.has_ctx = context ? 1 : 0; key.mol_shape = ms; key.noise_rows = noise_rows;
-    key.k_lo = raw_x ? k_lo : 0; key.resamplings = R; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
-    key.path_gen = pt.path_gen; key.ip_gen = R ? h->ip_gen : 0;
-    key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
-    key.rs_gen = rsn ? topo->rs_gen : 0; key.rs_rows_gen = rsn ? h->rs_gen : 0;
-    // the caller's slot (the every-step, the guided and the unguided transition are graphs of their own: such calls on one topology
-    // do not evict each other); so is the recording one (either kind), keyed on everything it bakes in but the sink's address
-    hipGraphExec_t* gx = rec ? &topo->gexec_chain : run.gx;
-    ChainKey ckey;
-    if (rec) {
-        ckey.path = key; ckey.what = topo->chain_what; ckey.nv0 = topo->chain_nv0; ckey.nv1 = topo->chain_nv1; ckey.nb1 = topo->chain_nb1;
-        ckey.chain_gen = h->chain_gen;
-        HD_TRY(replay_evict(h, rs, gx, topo->ckey, ckey));
-    } else {
-        HD_TRY(replay_evict(h, rs, gx, *run.key, key));
-    }
-    PathWords w;
-    w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = R ? h->d_ipdraw : nullptr;
-    w.tau = h->d_tau; w.t_idx = pt.d_path_t; w.s_idx = pt.d_path_s; w.K = K; w.T = T; w.nd = nd; w.stride = stride;
-    w.chain = rec ? h->d_chain_dst : nullptr;
-    if (!*gx) {
-        LoopIO io = loop_io_captured(h, R ? h->d_ipdraw : h->d_draw, rs);
-        io.z = topo->zbuf; io.ctx = context ? topo->ctxbuf : nullptr; io.fixed = topo->ip_fixed; io.known = topo->ip_known;
-        if (gd) { io.ctx_u = topo->ctxu_buf; io.w = topo->wbuf; }
-        HD_TRY(replay_capture(h, rs, gx, [&]() -> int {
-            HD_TRY(transition(io));
-            hipLaunchKernelGGL(k_path_advance, dim3(1), dim3(64), 0, rs, w);
-            return HD_OK;
-        }));
-        if (rec) { topo->ckey = ckey; topo->chain_builds++; }
-        else { *run.key = key; if (run.builds) ++*run.builds; }
-    }
-    HIP_TRY(hipMemcpyAsync(topo->zbuf, z, zbytes, hipMemcpyDeviceToDevice, rs));
-    if (context) HIP_TRY(hipMemcpyAsync(topo->ctxbuf, context, cbytes, hipMemcpyDeviceToDevice, rs));
-    if (gd) {
-        HIP_TRY(hipMemcpyAsync(topo->ctxu_buf, gd->ctx_u, cbytes, hipMemcpyDeviceToDevice, rs));
-        HIP_TRY(hipMemcpyAsync(topo->wbuf, gd->w, (size_t)gd->w_rows * sizeof(float), hipMemcpyDeviceToDevice, rs));
-    }
-    if (R) {
-        HIP_TRY(hipMemcpyAsync(topo->ip_fixed, fixed_mask, BN, hipMemcpyDeviceToDevice, rs));
-        HIP_TRY(hipMemcpyAsync(topo->ip_known, xh_known, zbytes, hipMemcpyDeviceToDevice, rs));
-    }
-    hipLaunchKernelGGL(k_path_state, dim3(1), dim3(64), 0, rs, w, k_lo, (unsigned long long)sample_id_base, topo->chain_dst);
-    HD_TRY(replay_run(*gx, ntr, rs));
-    HIP_TRY(hipMemcpyAsync(z, topo->zbuf, zbytes, hipMemcpyDeviceToDevice, rs));
-    return replay_leave(h, s, rs);
-}
-
-static int path_ready(hd_handle* h, const char* who, int k_lo, int k_hi) {
-    if (h->T < 1) return fail(HD_E_STATE, std::string(who) + ": schedule not set (hd_set_schedule)");
-    if (h->path.path_K < 1 || h->path.path_sched_gen != h->sched_gen)
-        return fail(HD_E_STATE, std::string(who) + ": path not set for the current schedule (hd_set_path)");
-    if (k_lo < 0 || k_lo > k_hi || k_hi > h->path.path_K) return fail(HD_E_INVALID, std::string(who) + ": need 0 <= k_lo <= k_hi <= K");
-    return HD_OK;
-}
-
-// The checks a loop without fixed fragments makes on its noise, context and model arguments (inpaint_args_check is the other kind).
-static int plain_args_check(const char* who, const hd_handle* h, const hd_topology* topo, const float* raw_x, const float* raw_h,
-                            int noise_rows, int mol_shape, const float* context) {
-    const std::string w(who);
-    if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, w + ": raw_x and raw_h go together");
-    if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, w + ": noise_rows must be 1 or B");
-    if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, w + ": context required");
-    if (!h->cfg.condition_time) return fail(HD_E_INVALID, w + ": needs a time-conditioned model");
-    if ((size_t)((mol_shape < 0 || mol_shape > topo->N) ? topo->N : mol_shape) * h->D * sizeof(float) > 64 * 1024)
-        return fail(HD_E_INVALID, w + ": N * D floats exceed one workgroup's LDS");
-    return HD_OK;
-}
-
-// The every-step loops: the path loop on the handle's every-step tables, where step s is position T - 1 - s.  Slots of their own,
-// no build counter, and no recording - a sink attached to the topology belongs to the caller's path (hd_set_chain).
-extern "C" int hd_sample_loop(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
-                              int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
-                              uint64_t seed, uint64_t sample_id_base, int use_graph, void* stream) {
-    HD_TRY(check_ready(h, topo, "hd_sample_loop"));
-    if (h->T < 1) return fail(HD_E_STATE, "hd_sample_loop: schedule not set (hd_set_schedule)");
-    if (!z) return fail(HD_E_INVALID, "hd_sample_loop: null z");
-    if (s_hi > h->T || s_lo < 0 || s_lo > s_hi) return fail(HD_E_INVALID, "hd_sample_loop: need 0 <= s_lo <= s_hi <= T");
-    HD_TRY(plain_args_check("hd_sample_loop", h, topo, raw_x, raw_h, noise_rows, mol_shape, context));
-    HIP_TRY(hipSetDevice(h->device));
-    return path_loop(h, topo, z, context, mol_shape, h->T - s_hi, h->T - s_lo, raw_x, raw_h, noise_rows, seed, sample_id_base, use_graph,
-                     nullptr, nullptr, 0, (hipStream_t)stream, {&h->every, &topo->gexec, &topo->gkey, nullptr, false});
-}
-
-extern "C" int hd_sample_loop_inpaint(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape,
-                                      int s_hi, int s_lo, const float* raw_x, const float* raw_h, int noise_rows,
-                                      uint64_t seed, uint64_t sample_id_base, int use_graph, const uint8_t* fixed_mask,
-                                      const float* xh_known, int resamplings, void* stream) {
-    const char* who = "hd_sample_loop_inpaint";
-    HD_TRY(check_ready(h, topo, who));
-    if (h->T < 1) return fail(HD_E_STATE, "hd_sample_loop_inpaint: schedule not set (hd_set_schedule)");
-    if (!h->every.d_path_coef_ip || h->ip_sched_gen != h->sched_gen)
-        return fail(HD_E_STATE, "hd_sample_loop_inpaint: inpainting schedule not set for the current schedule (hd_set_inpaint_schedule)");
-    if (!z || !fixed_mask || !xh_known) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: null z / fixed_mask / xh_known");
-    if (s_hi > h->T || s_lo < 0 || s_lo > s_hi) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: need 0 <= s_lo <= s_hi <= T");
-    HD_TRY(inpaint_args_check(who, h, topo, raw_x, raw_h, noise_rows, mol_shape, resamplings, context, kIpRawMsg, kIpRowsMsg));
-    HIP_TRY(hipSetDevice(h->device));
-    return path_loop(h, topo, z, context, -1, h->T - s_hi, h->T - s_lo, nullptr, nullptr, noise_rows, seed, sample_id_base, use_graph,
-                     fixed_mask, xh_known, resamplings, (hipStream_t)stream, {&h->every, &topo->gexec_ip, &topo->ikey, nullptr, false});
-}
-
-extern "C" int hd_sample_path(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo, int k_hi,
-                              const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base,
-                              int use_graph, void* stream) {
-    if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_sample_path: need 0 <= k_lo <= k_hi <= K");
-    HD_TRY(check_ready(h, topo, "hd_sample_path"));
-    HD_TRY(path_ready(h, "hd_sample_path", k_lo, k_hi));
-    if (!z) return fail(HD_E_INVALID, "hd_sample_path: null z");
-    HD_TRY(plain_args_check("hd_sample_path", h, topo, raw_x, raw_h, noise_rows, mol_shape, context));
-    HIP_TRY(hipSetDevice(h->device));
-    return path_loop(h, topo, z, context, mol_shape, k_lo, k_hi, raw_x, raw_h, noise_rows, seed, sample_id_base, use_graph,
-                     nullptr, nullptr, 0, (hipStream_t)stream, {&h->path, &topo->gexec_path, &topo->pkey, &topo->path_builds, true});
-}
-
-extern "C" int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z, const float* context, int mol_shape, int k_lo,
-                                      int k_hi, const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed,
-                                      uint64_t sample_id_base, int use_graph, const uint8_t* fixed_mask, const float* xh_known,
-                                      int resamplings, void* stream) {
-    const char* who = "hd_sample_path_inpaint";
-    if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_sample_path_inpaint: need 0 <= k_lo <= k_hi <= K");
-    HD_TRY(check_ready(h, topo, who));
-    if (topo->rs_on) return fail(HD_E_INVALID, "hd_sample_path_inpaint: restraints are attached to the topology, and inpainting takes "
-                                               "none (it re-centres on the known fragments: hd_restraint_detach)");
-    HD_TRY(path_ready(h, who, k_lo, k_hi));
-    HD_TRY(inpaint_path_check(who, h, ": ancestral rows only (the path was set with form = 1)"));
-    if (!z || !fixed_mask || !xh_known) return fail(HD_E_INVALID, "hd_sample_path_inpaint: null z / fixed_mask / xh_known");
-    HD_TRY(inpaint_args_check(who, h, topo, raw_x, raw_h, noise_rows, mol_shape, resamplings, context, kIpRawMsg, kIpRowsMsg));
-    HIP_TRY(hipSetDevice(h->device));
-    return path_loop(h, topo, z, context, -1, k_lo, k_hi, nullptr, nullptr, noise_rows, seed, sample_id_base, use_graph,
-                     fixed_mask, xh_known, resamplings, (hipStream_t)stream,
-                     {&h->path, &topo->gexec_path, &topo->pkey, &topo->path_builds, true});
-}
-
-// ----------------------------------------------------------------------------- classifier-free guidance
-
-extern "C" int hd_guide_combine(hd_handle* h, hd_topology* topo, const float* eps_c, const float* eps_u, const float* w_dev, int w_rows,
-                                float rescale, float* out, void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_guide_combine: null handle/topology");
-    if (!eps_c || !eps_u || !w_dev || !out) return fail(HD_E_INVALID, "hd_guide_combine: null tensor");
-    if (w_rows != 1 && w_rows != topo->B) return fail(HD_E_INVALID, "hd_guide_combine: w_rows must be 1 or B");
-    if (!(rescale >= 0.f && rescale <= 1.f)) return fail(HD_E_INVALID, "hd_guide_combine: rescale must lie in [0, 1]");
-    const size_t per = (size_t)topo->B * topo->N * h->D;
-    if (out < eps_u + per && eps_u < out + per) return fail(HD_E_INVALID, "hd_guide_combine: out may not overlap eps_u");
-    if (out != eps_c && out < eps_c + per && eps_c < out + per)
-        return fail(HD_E_INVALID, "hd_guide_combine: out may be eps_c itself, not a shifted overlap of it");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
-    return guide_launch(h, topo, eps_c, eps_u, w_dev, w_rows, rescale, out, s);
-}
-
-extern "C" long long hd_guided_graph_builds(const hd_topology* topo) { return topo ? topo->guided_builds : -1; }
-
-extern "C" int hd_sample_path_guided(hd_handle* h, hd_topology* topo, float* z, const float* context, const float* context_u,
-                                     const float* w_dev, int w_rows, float rescale, int k_lo, int k_hi, const float* raw_x,
-                                     const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int use_graph,
-                                     const uint8_t* fixed_mask, const float* xh_known, int resamplings, void* stream) {
-    const char* who = "hd_sample_path_guided";
-    if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_sample_path_guided: need 0 <= k_lo <= k_hi <= K");
-    HD_TRY(check_ready(h, topo, who));
-    HD_TRY(path_ready(h, who, k_lo, k_hi));
-    if (h->cfg.context_node_nf < 1) return fail(HD_E_INVALID, "hd_sample_path_guided: needs a context-conditioned model");
-    if (!z || !context || !context_u || !w_dev) return fail(HD_E_INVALID, "hd_sample_path_guided: null z / context / context_u / w");
-    if (w_rows != 1 && w_rows != topo->B) return fail(HD_E_INVALID, "hd_sample_path_guided: w_rows must be 1 or B");
-    if (!(rescale >= 0.f && rescale <= 1.f)) return fail(HD_E_INVALID, "hd_sample_path_guided: rescale must lie in [0, 1]");
-    if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_path_guided: needs a time-conditioned model");
-    int R = 0;
-    if (fixed_mask) {                                        // the restrictions of hd_sample_path_inpaint
-        if (topo->rs_on) return fail(HD_E_INVALID, "hd_sample_path_guided: restraints are attached to the topology, and inpainting "
-                                                   "takes none (it re-centres on the known fragments: hd_restraint_detach)");
-        HD_TRY(inpaint_path_check(who, h, ": inpainting takes ancestral rows only (the path was set with form = 1)"));
-        if (!xh_known) return fail(HD_E_INVALID, "hd_sample_path_guided: fixed_mask without xh_known");
-        // no mol_shape here; context and the time-conditioned model were checked above
-        HD_TRY(inpaint_args_check(who, h, topo, raw_x, raw_h, noise_rows, -1, resamplings, context,
-                                  ": inpainting takes no injected noise (counter-based generator only)", ": inpainting needs noise_rows = B"));
-        R = resamplings;
-    } else {
-        HD_TRY(plain_args_check(who, h, topo, raw_x, raw_h, noise_rows, -1, context));
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    GuideSrc gd;
-    gd.ctx_u = context_u; gd.w = w_dev; gd.w_rows = w_rows; gd.phi = rescale;
-    return path_loop(h, topo, z, context, -1, k_lo, k_hi, R ? nullptr : raw_x, R ? nullptr : raw_h, noise_rows, seed, sample_id_base,
-                     use_graph, R ? fixed_mask : nullptr, R ? xh_known : nullptr, R, (hipStream_t)stream,
-                     {&h->path, &topo->gexec_guided, &topo->gdkey, &topo->guided_builds, true}, &gd);
-}
-
-// ----------------------------------------------------------------------------- editing given molecules: start state, slerp
-
-extern "C" int hd_diffuse(hd_handle* h, hd_topology* topo, const float* xh, float alpha, float sigma, const float* raw_x,
-                          const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, uint32_t draw, int share_rows,
-                          float* z, void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_diffuse: null handle/topology");
-    if (!xh || !z) return fail(HD_E_INVALID, "hd_diffuse: null tensor");
-    if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, "hd_diffuse: raw_x and raw_h go together");
-    if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_diffuse: noise_rows must be 1 or B");
-    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_diffuse: N * D floats exceed one workgroup's LDS");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
-    ProfScope ps(h, s, 2);
-    DiffuseArgs a;
-    a.xh = xh; a.nm = topo->nm_bytes; a.z = z;
-    a.noise = make_noise(raw_x, raw_h, noise_rows, seed, sample_id_base, draw, share_rows);
-    a.draw_ptr = nullptr; a.base_ptr = nullptr; a.alpha = alpha; a.sigma = sigma;
-    a.B = topo->B; a.N = topo->N; a.D = h->D; a.F = h->F;
-    hipLaunchKernelGGL(k_diffuse, dim3(topo->B), dim3(256), (size_t)topo->N * h->D * sizeof(float), s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
-
-extern "C" int hd_slerp(hd_handle* h, hd_topology* topo, const float* za, const float* zb, const float* lam_host, int L, float* out,
-                        void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_slerp: null handle/topology");
-    if (!za || !zb || !lam_host || !out) return fail(HD_E_INVALID, "hd_slerp: null tensor");
-    if (L < 1) return fail(HD_E_INVALID, "hd_slerp: L must be >= 1");
-    const size_t per = (size_t)topo->B * topo->N * h->D;
-    for (const float* in : {za, zb})
-        if (out < in + per && in < out + per * (size_t)L) return fail(HD_E_INVALID, "hd_slerp: out may not alias za or zb");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
-    ProfScope ps(h, s, 2);
-    SlerpArgs a;
-    a.za = za; a.zb = zb; a.nm = topo->nm_bytes; a.out = out; a.B = topo->B; a.N = topo->N; a.D = h->D;
-    for (int l0 = 0; l0 < L; l0 += SLERP_CHUNK) {      // the weights ride in the kernel arguments: no host buffer outlives the call
-        a.l0 = l0; a.n = std::min(SLERP_CHUNK, L - l0);
-        for (int i = 0; i < SLERP_CHUNK; ++i) a.lam[i] = i < a.n ? lam_host[l0 + i] : 0.f;
-        hipLaunchKernelGGL(k_slerp, dim3(topo->B, a.n), dim3(256), 0, s, a);
-        HIP_TRY(hipGetLastError());
-    }
-    return HD_OK;
-}
-
-// ----------------------------------------------------------------------------- scoring: every term of the variational bound
-
-extern "C" int hd_set_nll_terms(hd_handle* h, int K, const int* t_idx, const float* coef4) {
-    if (!h || !t_idx || !coef4 || K < 1) return fail(HD_E_INVALID, "hd_set_nll_terms: bad argument");
-    if (h->T < 1) return fail(HD_E_STATE, "hd_set_nll_terms: schedule not set (hd_set_schedule)");
-    if (K > h->T) return fail(HD_E_INVALID, "hd_set_nll_terms: more terms than the schedule has steps");
-    for (int k = 0; k < K; ++k)
-        if (t_idx[k] < 1 || t_idx[k] > h->T) return fail(HD_E_INVALID, "hd_set_nll_terms: need 1 <= t_idx[k] <= T");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
-    hipFree(h->d_nll_t); hipFree(h->d_nll_coef);
-    h->d_nll_t = nullptr; h->d_nll_coef = nullptr;
-    h->nll_sched_gen = 0; h->nll_K = 0;
-    h->nll_t_h.assign(t_idx, t_idx + K);
-    HD_TRY(dev_upload(&h->d_nll_t, h->nll_t_h));
-    HD_TRY(dev_upload(&h->d_nll_coef, std::vector<float>(coef4, coef4 + (size_t)4 * K)));
-    h->nll_K = K;
-    h->nll_sched_gen = h->sched_gen;
-    h->nll_gen++;                              // captured graphs hold the old table addresses
-    return HD_OK;
-}
-
-extern "C" long long hd_nll_graph_builds(const hd_topology* topo) { return topo ? topo->nll_builds : -1; }
-
-// checks shared by hd_nll_terms and hd_nll_finish, in the order the header documents
-static int nll_ready(hd_handle* h, hd_topology* topo, const char* who, const float* raw_x, const float* raw_h, int noise_rows,
-                     int mol_shape, const float* context) {
-    const std::string w(who);
-    if (h->T < 1) return fail(HD_E_STATE, w + ": schedule not set (hd_set_schedule)");
-    if (h->nll_K < 1 || h->nll_sched_gen != h->sched_gen)
-        return fail(HD_E_STATE, w + ": terms not set for the current schedule (hd_set_nll_terms)");
-    if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, w + ": raw_x and raw_h go together");
-    if (noise_rows != topo->B) return fail(HD_E_INVALID, w + ": noise_rows must be B");
-    if (mol_shape >= 0 && mol_shape < topo->N) return fail(HD_E_INVALID, w + ": fixed tail rows (mol_shape < N) are not supported");
-    if (h->cfg.context_node_nf > 0 && !context) return fail(HD_E_INVALID, w + ": context required");
-    if (!h->cfg.condition_time) return fail(HD_E_INVALID, w + ": needs a time-conditioned model");
-    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, w + ": N * D floats exceed one workgroup's LDS");
-    return HD_OK;
-}
-
-static int nll_launch_zt(hd_handle* h, hd_topology* t, const float* xh, const float* coef, float alpha, float sigma, const NoiseSrc& ns,
-                         int k, int raw_k0, const int* step_ptr, const uint32_t* draw_ptr, const unsigned long long* base_ptr,
-                         hipStream_t s) {
-    ProfScope ps(h, s, 2);
-    NllZtArgs a;
-    a.xh = xh; a.nm = t->nm_bytes; a.eps = t->nll_eps; a.zt = t->zbuf; a.coef = coef; a.noise = ns; a.step_ptr = step_ptr;
-    a.draw_ptr = draw_ptr; a.base_ptr = base_ptr; a.alpha = alpha; a.sigma = sigma; a.k = k; a.raw_k0 = raw_k0;
-    a.B = t->B; a.N = t->N; a.D = h->D; a.F = h->F;
-    hipLaunchKernelGGL(k_nll_zt, dim3(t->B), dim3(256), (size_t)t->N * h->D * sizeof(float), s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
-
-static int nll_launch_err(hd_handle* h, hd_topology* t, double* acc, float* err, int k, const int* step_ptr, hipStream_t s) {
-    ProfScope ps(h, s, 2);
-    NllErrArgs a;
-    a.eps = t->nll_eps; a.net = t->eps; a.coef = h->d_nll_coef; a.acc = acc; a.err = err; a.step_ptr = step_ptr; a.k = k;
-    a.B = t->B; a.ND = t->N * h->D;
-    hipLaunchKernelGGL(k_nll_err, dim3(t->B), dim3(256), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
-
-extern "C" int hd_nll_terms(hd_handle* h, hd_topology* topo, const float* xh, const float* context, int mol_shape, int k_lo, int k_hi,
-                            const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base,
-                            int use_graph, double* acc, float* err_terms, void* stream) {
-    if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_nll_terms: need 0 <= k_lo <= k_hi <= K");
-    HD_TRY(check_ready(h, topo, "hd_nll_terms"));
-    HD_TRY(nll_ready(h, topo, "hd_nll_terms", raw_x, raw_h, noise_rows, mol_shape, context));
-    if (k_hi > h->nll_K) return fail(HD_E_INVALID, "hd_nll_terms: need 0 <= k_lo <= k_hi <= K");
-    if (!xh || !acc) return fail(HD_E_INVALID, "hd_nll_terms: null xh / acc");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int B = topo->B, N = topo->N, K = h->nll_K, nterms = k_hi - k_lo;
-    const size_t BN = (size_t)B * N;
-    const size_t zbytes = BN * h->D * sizeof(float);
-    const size_t cbytes = BN * h->cfg.context_node_nf * sizeof(float);
-    topo_use(topo, s);
-    if (nterms == 0) return HD_OK;
-    if (!topo->nll_eps) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_eps), zbytes));
-    auto term = [&](const LoopIO& io) -> int {               // io.row is the term's position in the list, io.draw its timestep
-        HD_TRY(nll_launch_zt(h, topo, io.xh, h->d_nll_coef, 0.f, 0.f, make_noise(raw_x, raw_h, B, seed, io.base, io.draw, 0), io.row, k_lo,
-                             io.step, io.draw_w, io.base_w, io.s));
-        HD_TRY(forward_impl(h, topo, topo->zbuf, io.tcur, 1, io.ctx, -1, topo->eps, io.s));
-        return nll_launch_err(h, topo, io.acc, io.err, io.row, io.step, io.s);
-    };
-    if (!use_graph) {
-        LoopIO io{};
-        io.xh = xh; io.ctx = context; io.acc = acc; io.err = err_terms; io.base = sample_id_base; io.s = s;
-        for (int k = k_lo; k < k_hi; ++k) {
-            io.row = k; io.draw = (uint32_t)h->nll_t_h[k]; io.tcur = h->d_tau + h->nll_t_h[k];
-            HD_TRY(term(io));
-        }
-        return HD_OK;
-    }
-    // The term position lives in d_step; k_nll_advance derives the network time and the draw from the uploaded list.
-    hipStream_t rs;
-    HD_TRY(replay_enter(h, s, &rs));
-    if (!topo->nll_xh) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_xh), zbytes));
-    if (!topo->nll_acc) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_acc), (size_t)B * sizeof(double)));
-    if (err_terms && topo->nll_err_rows < K) {               // grow the e_t table: a graph that holds the old address goes stale (key)
-        HD_TRY(replay_quiesce(h, rs));
-        if (topo->nll_err) (void)hipFree(topo->nll_err);
-        topo->nll_err = nullptr; topo->nll_err_rows = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_err), (size_t)K * B * sizeof(float)));
-        topo->nll_err_rows = K;
-    }
-    NllKey key;
-    key.raw_x = raw_x; key.raw_h = raw_h; key.err = err_terms ? topo->nll_err : nullptr; key.has_ctx = context ? 1 : 0;
-    key.k_lo = raw_x ? k_lo : 0; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen; key.nll_gen = h->nll_gen;
-    HD_TRY(replay_evict(h, rs, &topo->gexec_nll, topo->nkey, key));
-    NllWords w;
-    w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.tau = h->d_tau; w.t_idx = h->d_nll_t; w.K = K;
-    if (!topo->gexec_nll) {
-        LoopIO io = loop_io_captured(h, h->d_draw, rs);
-        io.xh = topo->nll_xh; io.ctx = context ? topo->ctxbuf : nullptr; io.acc = topo->nll_acc; io.err = err_terms ? topo->nll_err : nullptr;
-        HD_TRY(replay_capture(h, rs, &topo->gexec_nll, [&]() -> int {
-            HD_TRY(term(io));
-            hipLaunchKernelGGL(k_nll_advance, dim3(1), dim3(1), 0, rs, w);
-            return HD_OK;
-        }));
-        topo->nkey = key;
-        topo->nll_builds++;
-    }
-    HIP_TRY(hipMemcpyAsync(topo->nll_xh, xh, zbytes, hipMemcpyDeviceToDevice, rs));
-    if (context) HIP_TRY(hipMemcpyAsync(topo->ctxbuf, context, cbytes, hipMemcpyDeviceToDevice, rs));
-    HIP_TRY(hipMemcpyAsync(topo->nll_acc, acc, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, rs));
-    hipLaunchKernelGGL(k_nll_state, dim3(1), dim3(1), 0, rs, w, k_lo, (unsigned long long)sample_id_base);
-    HD_TRY(replay_run(topo->gexec_nll, nterms, rs));
-    HIP_TRY(hipMemcpyAsync(acc, topo->nll_acc, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, rs));
-    if (err_terms)
-        HIP_TRY(hipMemcpyAsync(err_terms + (size_t)k_lo * B, topo->nll_err + (size_t)k_lo * B, (size_t)nterms * B * sizeof(float),
-                               hipMemcpyDeviceToDevice, rs));
-    return replay_leave(h, s, rs);
-}
-
-extern "C" int hd_nll_finish(hd_handle* h, hd_topology* topo, const float* xh, const float* context, int mol_shape, const float* raw_x,
-                             const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, int K, const float* consts7,
-                             int int_nf, int cont_nf, const double* acc, float* nll, void* stream) {
-    HD_TRY(check_ready(h, topo, "hd_nll_finish"));
-    HD_TRY(nll_ready(h, topo, "hd_nll_finish", raw_x, raw_h, noise_rows, mol_shape, context));
-    if (!xh || !acc || !nll || !consts7) return fail(HD_E_INVALID, "hd_nll_finish: null xh / acc / nll / consts7");
-    if (K < 1 || K > h->T) return fail(HD_E_INVALID, "hd_nll_finish: need 1 <= K <= T");
-    if (int_nf < 0 || cont_nf < 0 || int_nf + cont_nf > h->F)
-        return fail(HD_E_INVALID, "hd_nll_finish: int_nf + cont_nf exceed the feature columns");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
-    if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(s, h->ev_last, 0));      // zbuf / eps are the replayed term's workspaces too
-    if (!topo->nll_eps) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_eps), (size_t)topo->B * topo->N * h->D * sizeof(float)));
-    HD_TRY(nll_launch_zt(h, topo, xh, nullptr, consts7[0], consts7[1], make_noise(raw_x, raw_h, topo->B, seed, sample_id_base, 0, 0), 0, 0,
-                         nullptr, nullptr, nullptr, s));
-    HD_TRY(forward_impl(h, topo, topo->zbuf, h->d_tau, 1, context, -1, topo->eps, s));
-    ProfScope ps(h, s, 2);
-    NllFinishArgs a;
-    a.net = topo->eps; a.z0 = topo->zbuf; a.xh = xh; a.eps = topo->nll_eps; a.nm = topo->nm_bytes; a.acc = acc; a.nll = nll;
-    a.g0 = consts7[2]; a.gT = consts7[3]; a.scale = (float)h->T / (float)K; a.nv2 = consts7[4]; a.nb2 = consts7[5]; a.log_nv0 = consts7[6];
-    a.B = topo->B; a.N = topo->N; a.D = h->D; a.int_nf = int_nf; a.cont_nf = cont_nf;
-    hipLaunchKernelGGL(k_nll_finish, dim3(topo->B), dim3(256), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
-
-extern "C" int hd_inpaint_decode_fix(hd_handle* h, hd_topology* topo, const uint8_t* fixed_mask, const float* x_known,
-                                     const float* h_known, float* x, float* hfeat, void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_inpaint_decode_fix: null handle/topology");
-    if (topo->h != h) return fail(HD_E_INVALID, "hd_inpaint_decode_fix: topology belongs to another handle");
-    if (!fixed_mask || !x_known || !h_known || !x || !hfeat) return fail(HD_E_INVALID, "hd_inpaint_decode_fix: null tensor");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
-    ProfScope ps(h, s, 2);
-    InpaintFixArgs a;
-    a.nm = topo->nm_bytes; a.fixed = fixed_mask; a.x_known = x_known; a.h_known = h_known; a.x = x; a.hfeat = hfeat;
-    a.B = topo->B; a.N = topo->N; a.F = h->F;
-    hipLaunchKernelGGL(k_inpaint_decode_fix, dim3((topo->B + 3) / 4), dim3(256), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
-}
+#include "host_loops.hpp"
 
 // ----------------------------------------------------------------------------- measurement aid: sustained MFMA rate
 extern "C" int hd_mfma_probe(int device, int kind, const float* in1024, float* scratch, int iters, double* ns_per_mfma_per_simd,

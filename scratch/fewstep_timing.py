@@ -1,7 +1,7 @@
 """Cost of few-step sampling (hd_sample_path) next to the plain loop, at the headline shape.
 
     python scratch/fewstep_timing.py [--out profiles/fewstep_timing.json] [--reps 3] [--precisions fp32 fp16x3]
-                                     [--root DIR] [--plain-only] [--merge OTHER.json]
+                                     [--root DIR] [--plain-only] [--merge OTHER.json] [--rows K:ETA ...] [--plain-launches]
 
 B = 256, N = 30, H = 256, L = 6, T = 1000, graph replay.  Per precision, wall time of one whole `sample_from_masks` call (z_T,
 the loop, the decode; stream synchronised before and after; one untimed warm-up call each, which also captures the graph):
@@ -10,6 +10,8 @@ the loop, the decode; stream synchronised before and after; one untimed warm-up 
                        path loop
 Every entry keeps all repetitions; the summary holds median, min and max.  `--root DIR --plain-only` times the plain loop of
 another checkout (the parent commit) in the same session; `--merge` copies that file's result in as "parent_plain".
+`--rows 20:1 20:0 50:1 1000:1` times only those path rows (no plain loop, nothing derived); `--plain-launches` turns graph replay
+off (`use_graph = False`: the host walks the library's launch code every transition).
 """
 import argparse
 import json
@@ -49,6 +51,8 @@ def main():
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--plain-only", action="store_true")
     ap.add_argument("--merge", default=None)
+    ap.add_argument("--rows", nargs="*", default=None)
+    ap.add_argument("--plain-launches", action="store_true")
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.root))
     from hierdiff_amd import DiffusionQM9, default_config
@@ -58,12 +62,23 @@ def main():
     model = DiffusionQM9(default_config(hidden_nf=H, n_layers=L, timesteps=T))
     model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in synthetic_state_dict(9, 0, H, L, 2, True, 1, 1.0).items()})
     model = model.to(DEV)
+    model.use_graph = not args.plain_launches
     nm = torch.ones(B, N, 1, dtype=torch.bool, device=DEV)
     res = {"config": dict(B=B, N=N, H=H, L=L, T=T, reps=args.reps, device=torch.cuda.get_device_name(0), root=os.path.basename(
-        os.path.abspath(args.root))), "seconds": {}}
+        os.path.abspath(args.root)), use_graph=not args.plain_launches), "seconds": {}}
     with torch.no_grad():
         for prec in args.precisions:
             model.dynamics.precision = prec
+            if args.rows is not None:
+                row = {}
+                for K, eta in (r.split(":") for r in args.rows):
+                    model._force_path_loop = True
+                    name = f"path_K{K}_eta{eta}"
+                    row[name] = summary(timed(lambda: model.sample_from_masks(nm, None, steps=int(K), eta=float(eta)), args.reps))
+                    model._force_path_loop = False
+                    print(prec, name, json.dumps(row[name]), flush=True)
+                res["seconds"][prec] = row
+                continue
             row = {"plain": summary(timed(lambda: model.sample_from_masks(nm, None), args.reps))}
             print(prec, "plain", json.dumps(row["plain"]), flush=True)
             if not args.plain_only:

@@ -1,4 +1,5 @@
-"""Bits of every Python sampling entry point, to compare two versions of hierdiff_amd/diffusion.py on the same library.
+"""Bits of every Python sampling and scoring entry point, to compare two versions of hierdiff_amd/diffusion.py on the same library,
+or two versions of the library.
 
     python scratch/sampling_bits.py --out profiles/sampling_bits_<name>.json [--root DIR] [--detail FILE]
 
@@ -6,7 +7,10 @@ The matrix of tests/make_golden_dispatch.py (every entry point crossed with step
 restraints / injected noise / fix_noise / k_lo > 0) run to completion at B = 3, sizes [7, 4, 1], T = 8, hidden 32, 2 layers, synthetic
 weights, the model's fixed seed, with `use_graph` on and off.  Per row: SHA-256 of every returned tensor (x, h, chain; of the list
 forms x, h, context, chain_x, chain_h, chain_t, restraint_energy over all molecules), or the type of the argument error, and what a second,
-warm call of the same row adds to the graph build counters (hd_path_graph_builds, hd_guided_graph_builds, hd_chain_graph_builds).
+warm call of the same row adds to the graph build counters (hd_path_graph_builds, hd_guided_graph_builds, hd_chain_graph_builds,
+hd_nll_graph_builds).  Behind the matrix, the scoring loop at the same shape (`scoring_matrix`): DiffusionQM9.nll_full over all terms,
+a 4-term uniform list and an explicit subset, with and without the per-term errors and injected noise; the same in two calls of the
+term loop, the second from k_lo = 2 (`nll_split`); and `score` on the list form.
 A row the library refuses before it launches anything (solver "dpm2m" from k_lo > 0 without the transition before it) holds
 "HD_E_STATE"; any other library error ends the run.
 `--out` holds, per `use_graph` value and entry point, the number of rows, how they ended, the warm builds summed, and one SHA-256 over
@@ -23,7 +27,7 @@ import torch
 
 DEV = "cuda:0"
 HD_E_STATE = -4                   # include/hierdiff_hip.h
-COUNTERS = ("hd_path_graph_builds", "hd_guided_graph_builds", "hd_chain_graph_builds")
+COUNTERS = ("hd_path_graph_builds", "hd_guided_graph_builds", "hd_chain_graph_builds", "hd_nll_graph_builds")
 
 
 def digest(t):
@@ -37,6 +41,38 @@ def digests(got):
     if isinstance(got, tuple):
         return {name: digest(t) for name, t in zip(("x", "h", "chain"), got)}
     return {k: digest(torch.cat([res[k].reshape(-1).double() for res in got])) for k in sorted(got[0])}       # a list: per key
+
+
+def scoring_matrix():
+    """(key, entry, opt) of the scoring rows, in the form of make_golden_dispatch.matrix()."""
+    rows = []
+    for entry in ("nll_full", "nll_split"):
+        for terms in ({}, {"terms": 4}, {"timesteps": [7, 2, 5]}):
+            for errors in (False, True):
+                for injected in (False, True):
+                    opt = dict(terms, return_terms=errors, injected=injected)
+                    rows.append((entry + "|" + ",".join(f"{k}={v}" for k, v in opt.items()), entry, opt))
+    return rows + [(f"score|{kw}", "score", kw) for kw in ({}, {"terms": 4})]
+
+
+def score_call(case, entry, opt, graph):
+    from tests import edit_reference as er
+    m = case.model
+    if entry == "score":
+        return {"nll": digest(m.score(case.samples, case.device, sample_id_base=3, use_graph=graph, **opt))}
+    kw = {k: v for k, v in opt.items() if k in ("terms", "timesteps")}
+    K = len(kw.get("timesteps", ())) or kw.get("terms", case.T)
+    raws = [(a.to(case.device), b.to(case.device)) for a, b in er.raw_draws(K + 1, case.B, case.N, 5)] if opt["injected"] else None
+    args = (case.x, case.h, case.nm, None, case.ctx)
+    if entry == "nll_full":
+        got = m.nll_full(*args, sample_id_base=3, raw_noises=raws, return_terms=opt["return_terms"], use_graph=graph, **kw)
+        nll, err = (got[0], got[1][1]) if opt["return_terms"] else (got, None)
+    else:                                                 # the term loop in two calls, the second from k_lo = 2
+        st = m._nll_setup(*args, kw.get("terms"), kw.get("timesteps"), None, 3, raws, opt["return_terms"], graph)
+        m._nll_terms(st, 0, 2)
+        m._nll_terms(st, 2, st.K)
+        nll, err = m._nll_finish(st), st.err
+    return {"nll": digest(nll)} if err is None else {"nll": digest(nll), "err": digest(err)}
 
 
 def main():
@@ -56,13 +92,15 @@ def main():
     res = {"config": dict(B=3, sizes=gd.N_LIST, T=8, H=gd.H, L=gd.L, seed=case.model.seed), "rows": {}}
     for graph in (True, False):
         case.model.use_graph = case.edm.use_graph = graph
-        for key, entry, opt in gd.matrix():
+        for key, entry, opt in gd.matrix() + scoring_matrix():
             m = case.edm if entry.startswith("edm_") else case.model
             name = f"graph={int(graph)}|{key}"
+            run = (lambda: score_call(case, entry, opt, graph)) if entry in ("nll_full", "nll_split", "score") else \
+                (lambda: digests(case.call(entry, opt)))
             try:
-                first = digests(case.call(entry, opt))
+                first = run()
                 before = counters(m)
-                second = digests(case.call(entry, opt))
+                second = run()
                 row = {"sha256": first, "warm_builds": [a - b for a, b in zip(counters(m), before)]}
                 if second != first:
                     row["second_call_differs"] = second
@@ -77,11 +115,11 @@ def main():
         print(f"use_graph={graph}: {len(res['rows'])} rows", flush=True)
     groups = {}
     for name, row in res["rows"].items():
-        g = groups.setdefault("|".join(name.split("|")[:2]), {"rows": 0, "ended": {}, "warm_builds": [0, 0, 0], "sha256": hashlib.sha256()})
+        g = groups.setdefault("|".join(name.split("|")[:2]), {"rows": 0, "ended": {}, "warm_builds": [0] * len(COUNTERS), "sha256": hashlib.sha256()})
         g["rows"] += 1
         end = row.get("error", "completed")
         g["ended"][end] = g["ended"].get(end, 0) + 1
-        g["warm_builds"] = [a + b for a, b in zip(g["warm_builds"], row.get("warm_builds", [0, 0, 0]))]
+        g["warm_builds"] = [a + b for a, b in zip(g["warm_builds"], row.get("warm_builds", [0] * len(COUNTERS)))]
         g["sha256"].update((name + json.dumps(row, sort_keys=True)).encode())
     for g in groups.values():
         g["sha256"] = g["sha256"].hexdigest()
