@@ -127,6 +127,10 @@ struct hd_handle {
     float* d_rs_rows;           // [K][4]
     int rs_K;
     unsigned long long rs_path_gen, rs_gen;         // path.gen the rows were set for (0: not set); bumped when the table moves
+    // steering (hd_set_steer): the rows {alpha_t, sigma_t, beta_k} of every transition of the current path
+    float* d_st_rows;           // [K][3]
+    int st_K;
+    unsigned long long st_path_gen, st_gen;         // as rs_path_gen / rs_gen
     // scoring (hd_set_nll_terms / hd_nll_terms / hd_nll_finish): K terms t_idx[k] of the bound, rows {alpha_t, sigma_t, w_t, 0}
     int nll_K;
     std::vector<int> nll_t_h;
@@ -165,11 +169,15 @@ struct PathKey {
     uint64_t seed;
     unsigned long long weights_gen, sched_gen, path_gen, ip_gen;
     unsigned long long rs_gen, rs_rows_gen;                  // restrained transition: the topology's tables, the handle's rows (0 / 0: plain)
+    int st_P;                                                // steered transition: particles per group, rho, the topology's steering
+    double st_ess;                                           // buffers, the handle's rows (all 0: not steered)
+    unsigned long long st_gen, st_rows_gen;
     bool operator==(const PathKey& o) const {
         return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape && noise_rows == o.noise_rows &&
                k_lo == o.k_lo && resamplings == o.resamplings && w_rows == o.w_rows && phi == o.phi && seed == o.seed &&
                weights_gen == o.weights_gen && sched_gen == o.sched_gen && path_gen == o.path_gen && ip_gen == o.ip_gen &&
-               rs_gen == o.rs_gen && rs_rows_gen == o.rs_rows_gen;
+               rs_gen == o.rs_gen && rs_rows_gen == o.rs_rows_gen && st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen &&
+               st_rows_gen == o.st_rows_gen;
     }
 };
 
@@ -257,6 +265,16 @@ struct hd_topology {
     int rs_obs_rows, rs_P, rs_pair_rows, rs_Q, rs_anc_rows, rs_A, rs_scale_rows;
     float rs_nv0;
     unsigned long long rs_gen;
+    // hd_steer_attach: the steering state of the chain that runs on this topology (log-weights, last energies, lineage roots, the
+    // ancestors of the latest transition, per-group statistics) and the scratch of k_steer_gather - one allocation each, made by the
+    // first attach at addresses captured transitions keep.  It survives between the pieces of a chain; `reset` starts a new one.
+    bool st_on;
+    int st_P;
+    double st_ess;
+    double *st_f64;                            // logw [B], U_prev [B], its scratch [B], stats [B / P][3] (room for [B][3])
+    int* st_i32;                               // root [B], anc [B]
+    float* st_scratch;                         // [2][B][N][D]
+    unsigned long long st_gen;
     // multistep paths (hd_set_path_multistep): the previous transition's data prediction x^ [B][N][D], allocated by the first
     // form-2 call at an address the captured transitions keep; host-side, which path generation and position it belongs to
     float* ms_hist;
@@ -380,6 +398,7 @@ extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
     h->chain_frames = 0; h->d_chain_frame = nullptr; h->d_chain_as = nullptr; h->chain_path_gen = 0; h->chain_gen = 0;
     h->d_chain_dst = nullptr;
     h->d_rs_rows = nullptr; h->rs_K = 0; h->rs_path_gen = 0; h->rs_gen = 0;
+    h->d_st_rows = nullptr; h->st_K = 0; h->st_path_gen = 0; h->st_gen = 0;
     h->nll_K = 0; h->d_nll_t = nullptr; h->d_nll_coef = nullptr; h->nll_sched_gen = 0; h->nll_gen = 0;
     h->d_nanflag = nullptr; h->d_nan_events = nullptr; h->d_step = nullptr; h->d_draw = nullptr; h->d_tcur = nullptr;
     h->d_base = nullptr;
@@ -436,6 +455,7 @@ extern "C" int hd_destroy(hd_handle* h) {
     }
     hipFree(h->d_chain_frame); hipFree(h->d_chain_as); hipFree(h->d_chain_dst);
     hipFree(h->d_rs_rows);
+    hipFree(h->d_st_rows);
     hipFree(h->d_nll_t); hipFree(h->d_nll_coef);
 #ifdef HD_DEBUG_KERNELS
     hipFree(h->d_trace);
@@ -831,7 +851,7 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     if (t->guide_mem) (void)hipFree(t->guide_mem);
     if (t->ms_hist) (void)hipFree(t->ms_hist);
     for (void* p : {(void*)t->rs_obs, (void*)t->rs_pair_idx, (void*)t->rs_pair_f, (void*)t->rs_anc_idx, (void*)t->rs_anc_f,
-                    (void*)t->rs_scale, (void*)t->rs_step})
+                    (void*)t->rs_scale, (void*)t->rs_step, (void*)t->st_f64, (void*)t->st_i32, (void*)t->st_scratch})
         if (p) (void)hipFree(p);
     if (t->ip_fixed) (void)hipFree(t->ip_fixed);
     if (t->ip_known) (void)hipFree(t->ip_known);
@@ -2856,6 +2876,15 @@ extern "C" float hd_philox_normal_host(uint64_t seed, uint64_t sample_id, uint32
     const float rad = std::sqrt(-2.0f * std::log(u1));
     const float ang = 6.283185307179586f * u2;
     return (index & 1) ? rad * std::sin(ang) : rad * std::cos(ang);
+}
+
+// the host twin of philox_uniform (k_steer.hpp): words 2 and 3 of the same counter block, 26 bits each, in double
+extern "C" double hd_philox_uniform_host(uint64_t seed, uint64_t sample_id, uint32_t draw, uint32_t index) {
+    uint32_t c[4] = {index >> 1, draw, (uint32_t)sample_id, (uint32_t)(sample_id >> 32)};
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int r = 0; r < 10; ++r) { philox_round_h(c, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+    const uint64_t v = ((uint64_t)(c[2] >> 6) << 26) | (uint64_t)(c[3] >> 6);
+    return ((double)v + 0.5) * (1.0 / 4503599627370496.0);
 }
 
 // ----------------------------------------------------------------------------- refine model (k_refine.hpp)

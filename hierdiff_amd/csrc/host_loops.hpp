@@ -580,6 +580,128 @@ extern "C" int hd_restraint_energy(hd_handle* h, hd_topology* topo, const float*
     return HD_OK;
 }
 
+// ----------------------------------------------------------------------------- steering: particle resampling on the restraint energy
+
+static bool steer_row_ok(const float* r) { return r[0] > 0.f && r[1] >= 0.f && r[2] >= 0.f && r[2] - r[2] == 0.f; }
+
+extern "C" int hd_set_steer(hd_handle* h, int K, const float* rows3) {
+    if (!h || !rows3 || K < 1) return fail(HD_E_INVALID, "hd_set_steer: bad argument");
+    if (h->path.K < 1 || h->path.sched_gen != h->sched_gen)
+        return fail(HD_E_STATE, "hd_set_steer: path not set for the current schedule (hd_set_path)");
+    if (K != h->path.K) return fail(HD_E_INVALID, "hd_set_steer: K differs from the path's (hd_set_path)");
+    for (int k = 0; k < K; ++k)
+        if (!steer_row_ok(rows3 + (size_t)3 * k))
+            return fail(HD_E_INVALID, "hd_set_steer: need alpha_t > 0, sigma_t >= 0 and a finite beta_k >= 0");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old rows
+    if (!h->d_st_rows || h->st_K != K) {                // same K: the table stays where captured transitions expect it
+        hipFree(h->d_st_rows);
+        h->d_st_rows = nullptr; h->st_path_gen = 0; h->st_K = 0;
+        HD_TRY(dev_alloc(&h->d_st_rows, (size_t)3 * K));
+        h->st_K = K;
+        h->st_gen++;
+    }
+    HIP_TRY(hipMemcpy(h->d_st_rows, rows3, (size_t)3 * K * sizeof(float), hipMemcpyHostToDevice));
+    h->st_path_gen = h->path.gen;
+    return HD_OK;
+}
+
+static SteerState steer_state(const hd_topology* t) {
+    SteerState s;
+    const size_t B = (size_t)t->B;
+    s.logw = t->st_f64; s.uprev = t->st_f64 + B; s.stats = t->st_f64 + 3 * B; s.root = t->st_i32; s.anc = t->st_i32 + B;
+    return s;
+}
+
+extern "C" int hd_steer_attach(hd_topology* topo, int P, double ess, int reset, void* stream) {
+    if (!topo) return fail(HD_E_INVALID, "hd_steer_attach: null topology");
+    if (P < 2 || P > ST_MAX_P) return fail(HD_E_INVALID, "hd_steer_attach: need 2 <= P <= 256 particles per group");
+    if (topo->B % P != 0) return fail(HD_E_INVALID, "hd_steer_attach: the topology's B is not a multiple of P");
+    if (!(ess > 0.0) || !(ess <= 1.0)) return fail(HD_E_INVALID, "hd_steer_attach: need 0 < ess <= 1");
+    HIP_TRY(hipSetDevice(topo->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    topo->st_on = false;
+    const size_t B = (size_t)topo->B;
+    const bool fresh = !topo->st_f64;
+    if (!reset && (fresh || P != topo->st_P))
+        return fail(HD_E_STATE, "hd_steer_attach: reset = 0 continues a chain, and this topology holds no steering state for this P");
+    if (fresh) {
+        if (!topo->st_i32) HD_TRY(dev_alloc(&topo->st_i32, 2 * B));
+        if (!topo->st_scratch) HD_TRY(dev_alloc(&topo->st_scratch, 2 * B * topo->N * topo->h->D));
+        HD_TRY(dev_alloc(&topo->st_f64, 6 * B));            // last: its presence says all three are there
+    }
+    if (fresh || P != topo->st_P || ess != topo->st_ess) topo->st_gen++;
+    topo->st_P = P; topo->st_ess = ess;
+    if (reset) {
+        hipLaunchKernelGGL(k_steer_init, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, steer_state(topo), topo->B, P);
+        HIP_TRY(hipGetLastError());
+    }
+    topo->st_on = true;
+    return HD_OK;
+}
+
+extern "C" int hd_steer_detach(hd_topology* topo) {
+    if (topo) topo->st_on = false;
+    return HD_OK;
+}
+
+// The three stages of one transition on z / eps (both may be rewritten): `rows` the device table read at *io.step / io.row, or the
+// host row; the draw and the first sample id by value or from the loop's device words.
+static int steer_launch(hd_handle* h, hd_topology* t, const LoopIO& io, float* z, float* eps, const float* rows, const float* row3,
+                        LoopIO::Draw d, uint64_t seed) {
+    ProfScope ps(h, io.s, 2);
+    const SteerState st = steer_state(t);
+    SteerWeighArgs w;
+    w.z = z; w.eps = eps; w.nm = t->nm_bytes; w.t = restraint_tables(t); w.rows = rows;
+    for (int i = 0; i < 3; ++i) w.row[i] = row3 ? row3[i] : 0.f;
+    w.step_ptr = io.step; w.k = io.row; w.nv0 = t->rs_nv0; w.logw = st.logw; w.uprev = st.uprev; w.B = t->B; w.N = t->N; w.D = h->D;
+    hipLaunchKernelGGL(k_steer_weigh, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, w);
+    SteerResampleArgs r;
+    r.st = st; r.ess = t->st_ess; r.seed = seed; r.base = io.base; r.draw = d.value; r.draw_ptr = d.word; r.base_ptr = io.base_w;
+    r.P = t->st_P;
+    hipLaunchKernelGGL(k_steer_resample, dim3(t->B / t->st_P), dim3(256), 0, io.s, r);
+    SteerGatherArgs g;
+    g.z = z; g.eps = eps; g.scratch = t->st_scratch; g.uprev = st.uprev; g.us = t->st_f64 + 2 * (size_t)t->B; g.anc = st.anc;
+    g.B = t->B; g.total = t->N * h->D;
+    hipLaunchKernelGGL(k_steer_gather<0>, dim3(t->B), dim3(256), 0, io.s, g);
+    hipLaunchKernelGGL(k_steer_gather<1>, dim3(t->B), dim3(256), 0, io.s, g);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_steer_step(hd_handle* h, hd_topology* topo, float* z, float* eps, const float* row3, uint32_t draw, uint64_t seed,
+                             uint64_t sample_id_base, void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_steer_step: null handle/topology");
+    if (!z || !eps || !row3) return fail(HD_E_INVALID, "hd_steer_step: null tensor / row");
+    if (!topo->st_on) return fail(HD_E_STATE, "hd_steer_step: no steering attached to the topology (hd_steer_attach)");
+    if (!topo->rs_on) return fail(HD_E_STATE, "hd_steer_step: no restraints attached to the topology (hd_restraint_attach)");
+    if (!steer_row_ok(row3)) return fail(HD_E_INVALID, "hd_steer_step: need alpha_t > 0, sigma_t >= 0 and a finite beta >= 0");
+    const size_t per = (size_t)topo->B * topo->N * h->D;
+    if (z < eps + per && eps < z + per) return fail(HD_E_INVALID, "hd_steer_step: z and eps may not overlap");
+    HIP_TRY(hipSetDevice(h->device));
+    LoopIO io{};
+    io.base = sample_id_base; io.s = (hipStream_t)stream;
+    topo_use(topo, io.s);
+    return steer_launch(h, topo, io, z, eps, nullptr, row3, LoopIO::Draw{draw, nullptr}, seed);
+}
+
+extern "C" int hd_steer_read(hd_topology* topo, double* logw, double* uprev, int* root, int* anc, double* stats, void* stream) {
+    if (!topo) return fail(HD_E_INVALID, "hd_steer_read: null topology");
+    if (!topo->st_f64) return fail(HD_E_STATE, "hd_steer_read: the topology holds no steering state (hd_steer_attach)");
+    HIP_TRY(hipSetDevice(topo->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    const SteerState st = steer_state(topo);
+    const size_t B = (size_t)topo->B;
+    if (logw) HIP_TRY(hipMemcpyAsync(logw, st.logw, B * sizeof(double), hipMemcpyDefault, s));
+    if (uprev) HIP_TRY(hipMemcpyAsync(uprev, st.uprev, B * sizeof(double), hipMemcpyDefault, s));
+    if (root) HIP_TRY(hipMemcpyAsync(root, st.root, B * sizeof(int), hipMemcpyDefault, s));
+    if (anc) HIP_TRY(hipMemcpyAsync(anc, st.anc, B * sizeof(int), hipMemcpyDefault, s));
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, st.stats, B / topo->st_P * 3 * sizeof(double), hipMemcpyDefault, s));
+    return HD_OK;
+}
+
 // Classifier-free guidance of a path loop: every network call becomes two (context, then ctx_u) and k_guide_combine in place.
 struct GuideSrc {
     const float* ctx_u;   // [B,N,C] the null (or any second) context
@@ -676,6 +798,16 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
             return fail(HD_E_STATE, "path loop: restraints are attached but their rows are not set for the current path (hd_set_restraint)");
         if (mol != N) return fail(HD_E_INVALID, "path loop: restraints act on whole molecules only (mol_shape < N)");
     }
+    const bool stn = c.record && topo->st_on;
+    if (stn) {
+        if (!rsn) return fail(HD_E_STATE, "path loop: steering is attached to the topology but no restraints are (hd_restraint_attach): "
+                                          "it weighs the particles by their restraint energy");
+        if (!h->d_st_rows || h->st_path_gen != pt.gen)
+            return fail(HD_E_STATE, "path loop: steering is attached but its rows are not set for the current path (hd_set_steer)");
+        if (form == 2) return fail(HD_E_INVALID, "path loop: steering needs a stochastic update, and multistep rows draw nothing "
+                                                 "(duplicated particles would never diverge: hd_steer_detach)");
+        if (c.noise_rows != topo->B) return fail(HD_E_INVALID, "path loop: steering needs every row's own noise (noise_rows must be B)");
+    }
     const int rounds = R ? R : 1;
     auto transition = [&](const LoopIO& io) -> int {         // all rounds of one transition; io.row is the path position
         for (int j = 0; j < rounds; ++j) {
@@ -685,6 +817,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
                 HD_TRY(guide_launch(h, topo, topo->eps, topo->eps_u, io.w, gd->w_rows, gd->phi, topo->eps, io.s));
             }
             if (rsn) HD_TRY(restrain_launch(h, topo, io, io.z, topo->eps, topo->eps, h->d_rs_rows, nullptr));
+            if (stn) HD_TRY(steer_launch(h, topo, io, io.z, topo->eps, h->d_st_rows, nullptr, io.draw_of(0, stride), c.seed));
             const bool rec_z = rec && j == rounds - 1 && topo->chain_what == 0;
             if (rec && j == rounds - 1 && topo->chain_what == 1) HD_TRY(chain_launch(h, topo, io, topo->eps));
             if (form == 2) {
@@ -726,6 +859,8 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     key.k_lo = c.raw_x ? k_lo : 0; key.resamplings = R; key.seed = c.seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
     key.path_gen = pt.gen; key.ip_gen = R ? h->ip_gen : 0; key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
     key.rs_gen = rsn ? topo->rs_gen : 0; key.rs_rows_gen = rsn ? h->rs_gen : 0;
+    key.st_P = stn ? topo->st_P : 0; key.st_ess = stn ? topo->st_ess : 0.0; key.st_gen = stn ? topo->st_gen : 0;
+    key.st_rows_gen = stn ? h->st_gen : 0;
     PathWords w;
     w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = R ? h->d_ipdraw : nullptr;
     w.tau = h->d_tau; w.t_idx = pt.d_t; w.s_idx = pt.d_s; w.K = K; w.T = T; w.nd = nd; w.stride = stride; w.chain = rec ? h->d_chain_dst : nullptr;

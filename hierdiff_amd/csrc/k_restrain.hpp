@@ -182,14 +182,12 @@ __global__ __launch_bounds__(256) void k_restrain_eps(RestrainArgs a) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_restraint_energy(RestraintEnergyArgs a) {
-    __shared__ double red[4 * 3];
-    const int tid = threadIdx.x, b = blockIdx.x;
-    const int N = a.N;
-    const RestraintTables& t = a.t;
-    const float* x = a.x + (size_t)b * N * 3;
-    const uint8_t* nm = a.nm + (size_t)b * N;
-    double U[3] = {0.0, 0.0, 0.0}, u[3], c;
+// (U_obs, U_pair, U_anc) of the molecule b at positions x [N][3] (data units; global memory or LDS) into U, in every thread: a strided
+// double sum per thread, then guide_block_sum.  `red`: 4 * 3 doubles of LDS.  The one energy code of k_restraint_energy and k_steer_weigh.
+HD_DEVINL void rs_energy_block(const RestraintTables& t, int b, const float* x, const uint8_t* nm, int N, double* red, int tid,
+                               double (&U)[3]) {
+    double u[3], c;
+    U[0] = 0.0; U[1] = 0.0; U[2] = 0.0;
     const float* obs = t.obs + (size_t)(t.obs_rows == 1 ? 0 : b) * t.P * 5;
     for (long long e = tid; e < (long long)N * t.P; e += 256) {
         const int i = (int)(e / t.P), p = (int)(e - (long long)i * t.P);
@@ -213,5 +211,12 @@ __global__ __launch_bounds__(256) void k_restraint_energy(RestraintEnergyArgs a)
         U[2] += rs_band_term(rs_dist(x, i, (double)af[0], (double)af[1], (double)af[2], u), -1.0, (double)af[3], (double)af[4], c);
     }
     guide_block_sum<3>(U, red, tid);
+}
+
+__global__ __launch_bounds__(256) void k_restraint_energy(RestraintEnergyArgs a) {
+    __shared__ double red[4 * 3];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    double U[3];
+    rs_energy_block(a.t, b, a.x + (size_t)b * a.N * 3, a.nm + (size_t)b * a.N, a.N, red, tid, U);
     if (tid < 3) a.out[(size_t)b * 3 + tid] = U[tid];
 }

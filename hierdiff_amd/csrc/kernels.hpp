@@ -36,5 +36,6 @@
 #include "k_solver.hpp"
 #include "k_chain.hpp"
 #include "k_restrain.hpp"
+#include "k_steer.hpp"
 #include "k_digest.hpp"
 #include "k_refine.hpp"

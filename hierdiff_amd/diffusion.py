@@ -203,6 +203,12 @@ class DiffusionQM9(_Base):
         self.restraint_scale = None
         self.restraint_schedule = "score"
         self.restraint_clip = None
+        # steered sampling (hierdiff_amd/steering.py): defaults of the `particles` / `steer_scale` / `steer_ess` keywords.  particles of
+        # None or 1, or a steer_scale of None or 0 = nothing changes.  `steer_last`: the `steering.Result` of the last steered call.
+        self.particles = None
+        self.steer_scale = None
+        self.steer_ess = None
+        self.steer_last = None
 
     def check_issues_norm_values(self, num_stdevs=8):
         """diffusion_qm9.py:117-131 (predefined schedules only)."""
@@ -615,9 +621,14 @@ class DiffusionQM9(_Base):
             self._sched_key = key
         return self._sched
 
-    def _plan(self, what: str, kind: str = "full", **kw):
-        """The host side of the sampling call `what` (`plan.plan`): its keywords resolved once, before the GPU is touched."""
-        return make_plan(self, what, kind, **kw)
+    def _plan(self, what: str, kind: str = "full", fix_noise: bool = False, **kw):
+        """The host side of the sampling call `what` (`plan.plan`): its keywords resolved once, before the GPU is touched.
+        `fix_noise`: the call shares one row of noise, which a steered plan refuses."""
+        pl = make_plan(self, what, kind, **kw)
+        if pl.steer is not None and fix_noise:
+            raise ValueError(f"{what}: steering needs every row's own noise (fix_noise shares one row: duplicated particles would "
+                             "never diverge)")
+        return pl
 
     def _resolve_path(self, steps=None, eta=None, spacing=None, timesteps=None, inpaint: bool = False, solver=None,
                       lower_order_final=None):
@@ -696,6 +707,39 @@ class DiffusionQM9(_Base):
         import weakref
         rr.rs._model = weakref.ref(self)
         rr.rs.attach(topo, rr.scale, float(self.norm_values[0]), dev, _stream(dev))
+
+    def _steer_open(self, handle, topo, tabs, st, reset: bool, dev):
+        """Attach the steering of a resolved call (`steering.Steer`) to `topo` behind the rows of the path that `_path_tables` has
+        just set (hd_set_steer, once per (path tables, beta, schedule)).  `reset`: the call starts a chain (k_lo = 0); a later
+        piece continues on the state the topology holds.  The caller closes (`_steer_close`)."""
+        from . import steering
+        pt = self._path_cache[2]
+        key = st.key()
+        hit = self.__dict__.get("_steer_cache")
+        if hit is None or hit[0] is not pt or hit[1] != key:
+            path = [int(t) for t in pt["t_idx"]] + [int(pt["s_idx"][-1])]
+            rows = np.ascontiguousarray(steering.beta_rows(tabs["gamma"], path, st))
+            self._steer_cache = None
+            _lib.check(_lib.load().hd_set_steer(handle, int(rows.shape[0]), rows.ctypes.data_as(C.POINTER(C.c_float))), "hd_set_steer")
+            self._steer_cache = (pt, key)
+        _lib.check(_lib.load().hd_steer_attach(topo.ptr, st.P, st.ess, int(bool(reset)), _stream(dev)), "hd_steer_attach")
+
+    def _steer_close(self, topo, st, B: int, dev, ok: bool):
+        """Detach (hd_steer_detach) and, behind a call that ran, keep the state it left as `steer_last` (hd_steer_read)."""
+        from . import steering
+        lib = _lib.load()
+        _lib.check(lib.hd_steer_detach(topo.ptr), "hd_steer_detach")
+        if not ok:
+            return
+        G = B // st.P
+        logw = torch.empty(B, device=dev, dtype=torch.float64)
+        root = torch.empty(B, device=dev, dtype=torch.int32)
+        stats = torch.empty((G, 3), device=dev, dtype=torch.float64)
+        _lib.check(lib.hd_steer_read(topo.ptr, logw.data_ptr(), None, root.data_ptr(), None, stats.data_ptr(), _stream(dev)),
+                   "hd_steer_read")
+        stats = stats.cpu()
+        self.steer_last = steering.Result(steering.normalise(logw.cpu(), st.P), root.cpu().long(), torch.arange(B) // st.P,
+                                          stats[:, 0].long(), stats[:, 1].clone(), stats[:, 2].long())
 
     def _chain_times(self, keep_frames, t_start=None, inpaint: bool = False, **few):
         """[keep] the grid index every frame of a recording call has arrived at (`Plan.chain_t`): host arithmetic only."""
@@ -852,6 +896,9 @@ class DiffusionQM9(_Base):
         plan's path, topology, context rows [B*N, C] and the guided call's second context.  Entry points add their extras (pocket:
         `tail`, `topo_loop`; inpainting: `_inpaint_setup`) on top of it."""
         dev = node_mask.device
+        if pl is not None and pl.steer is not None:   # rows of a group interact: equal masks, contexts and tables, checked on the host
+            from . import steering
+            steering.check_groups(pl.steer, node_mask, context, pl.restraints.rs, pl.restraints.scale, what)
         if dev.type != "cuda":
             raise _lib.HierDiffHipError(f"{what} runs only on an MI355X (no CPU fallback)")
         h = self._lib_handle()
@@ -883,9 +930,12 @@ class DiffusionQM9(_Base):
         zz = z if st.tail is None else torch.cat([z, st.tail], dim=1).contiguous()      # a pocket's fixed rows ride along
         mol = -1 if st.tail is None else st.N
         common = (_ptr(rx), _ptr(rh), rows, seed, base, int(self.use_graph))
+        steer, ran = getattr(pl, "steer", None), False
         try:
             if pl.restraints is not None:
                 self._restrain_open(st.h, topo, st.tabs, pl.restraints, st.B, st.dev)
+            if steer is not None:
+                self._steer_open(st.h, topo, st.tabs, steer, int(k_lo) == 0, st.dev)
             if pl.frames is not None:
                 st.chain = self._chain_open(st.h, topo, st.tabs, pl.frames, pl.record, st.B, st.N, st.dev, st.chain)
             if st.g is not None:
@@ -901,7 +951,10 @@ class DiffusionQM9(_Base):
                 fn, name, lo, hi = (lib.hd_sample_path, "hd_sample_path", k_lo, k_hi) if pl.path is not None else \
                     (lib.hd_sample_loop, "hd_sample_loop", pl.K - k_lo, pl.K - k_hi)
                 _lib.check(fn(st.h, topo.ptr, zz.data_ptr(), _ptr(st.ctx), mol, int(lo), int(hi), *common, st.stream), name)
+            ran = True
         finally:
+            if steer is not None:
+                self._steer_close(topo, steer, st.B, st.dev, ran)
             if pl.frames is not None:
                 _lib.check(lib.hd_chain_detach(topo.ptr), "hd_chain_detach")
             if pl.restraints is not None:
@@ -936,7 +989,8 @@ class DiffusionQM9(_Base):
                           timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                           solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                           keep_frames: Optional[int] = None, record: Optional[str] = None,
-                          restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None):
+                          restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
+                          particles=None, steer_scale=None, steer_ess=None, steer_schedule=None):
         """z_T -> (x, h) for given masks: draw z_T, T posterior steps, final decode.
 
         restraints / restraint_scale / restraint_schedule / restraint_clip (keyword-only; None: the model's attributes of the same
@@ -950,6 +1004,17 @@ class DiffusionQM9(_Base):
         untouched.  Combines with steps / eta / spacing / timesteps, solver "dpm2m", guidance and keep_frames.  Not with pocket
         models, mode 'gnn_dynamics' or noise_mode 'torch'.  Mechanism only: which scale, schedule and clip help is for the user to
         validate on a trained checkpoint.
+
+        particles / steer_scale / steer_ess / steer_schedule (keyword-only; None: the model's `particles` / `steer_scale` /
+        `steer_ess`): steered sampling (hierdiff_amd/steering.py) - the batch is G groups of `particles` rows (group g owns rows
+        g P .. g P + P - 1, which must have equal masks, contexts and restraint rows); at every transition the rows of a group are
+        weighted by the change of the restraint energy of their data prediction, logw += -steer_scale (U_k - U_prev) (times the k-th
+        value of `steer_schedule`), and resampled systematically inside the library's loop when their effective sample size falls below
+        steer_ess * P (default 0.5).  Needs `restraints`; `restraint_scale` may be None or 0 (selection without the gradient
+        update).  The state of the call is left as `self.steer_last` (`steering.Result`).  A group's result depends on the seed, the
+        ids of its rows, P and its own masks and tables only.  particles of None or 1, or a steer_scale of None or 0, is the unsteered
+        code path, untouched.  Not with eta = 0, solver "dpm2m", fix_noise, raw_noises, pocket models, mode 'gnn_dynamics' or
+        noise_mode 'torch'.  Mechanism only.
 
         keep_frames / record (keyword-only; None: nothing is recorded and the call is today's): the reference's `sample_chain`
         (en_diffusion.py:669-710) - the chain runs in the path loop (the identity path when no few-step path is asked for) with a
@@ -991,7 +1056,7 @@ class DiffusionQM9(_Base):
         (diffusion_qm9.py:362-371,381-382); the final decode sees the molecule alone (:386-387)."""
         dev = node_mask.device
         B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
-        pl = self._plan("sample_from_masks", pocket=pocket, injected=raw_noises is not None, B=B, N=N, **given(locals()))
+        pl = self._plan("sample_from_masks", pocket=pocket, injected=raw_noises is not None, B=B, N=N, fix_noise=fix_noise, **given(locals()))
         if pl.guidance is not None and context is None:
             raise ValueError("context required")
         gnn = getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics"
@@ -1066,7 +1131,8 @@ class DiffusionQM9(_Base):
                    k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False,
                    guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                    solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
-                   restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None):
+                   restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
+                   particles=None, steer_scale=None, steer_ess=None, steer_schedule=None):
         """Transitions k_lo .. k_hi-1 of `sample_from_masks`'s few-step loop on a given z [B,N,D] (normalised units, the state at
         path position k_lo); returns the state at position k_hi (default: the end of the path, z_0 before the decode).  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.
@@ -1075,7 +1141,7 @@ class DiffusionQM9(_Base):
         exactly where that call ended (its k_hi); a piece-wise chain then gives the bits of the whole.  Anything else - fresh masks,
         another path or solver in between, a gap - raises HierDiffHipError (HD_E_STATE) instead of using a stale prediction."""
         B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
-        pl = self._plan("path_steps", force_path=True, B=B, N=N, **given(locals()))       # also the identity path goes through hd_sample_path here
+        pl = self._plan("path_steps", force_path=True, B=B, N=N, fix_noise=fix_noise, **given(locals()))       # also the identity path goes through hd_sample_path here
         if getattr(self.dynamics, "mode", "egnn_dynamics") == "gnn_dynamics" or self.noise_mode == "torch":
             raise NotImplementedError("few-step sampling: mode 'gnn_dynamics' and noise_mode 'torch' are not supported")
         k_hi = pl.K if k_hi is None else int(k_hi)
@@ -1328,6 +1394,8 @@ class DiffusionQM9(_Base):
         The inversion stays first order: solver="dpm2m" raises ValueError (the model's `sample_solver` is not consulted)."""
         from . import paths, restraints as _rs
         _rs.refuse(self, "encode", restraints, ": the inversion follows the network's own flow")
+        from . import steering as _st
+        _st.refuse(self, "encode")
         if paths.check_solver(solver) is not None:
             raise ValueError("encode: the inversion is first order (eta = 0 upwards); solver 'dpm2m' is not supported")
         t_end = self._grid_index(self.T if t_end is None else t_end, 1, "t_end")
@@ -1377,13 +1445,15 @@ class DiffusionQM9(_Base):
                      k_lo: int = 0, k_hi: Optional[int] = None, sample_id_base: int = 0, fix_noise: bool = False,
                      raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                      solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
-                     restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None):
+                     restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
+                     particles=None, steer_scale=None, steer_ess=None, steer_schedule=None):
         """Transitions k_lo .. k_hi-1 of `sample_from_latent`'s partial chain on a given z [B,N,D] (the state at path position k_lo);
         returns the state at position k_hi (default: the end, z_0 before the decode), as `path_steps` does for a full path.  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.  `raw_noises`: k_hi - k_lo injected
         (randn_x, randn_h) pairs, one per transition run.  solver="dpm2m" over a sub-range: the continuity rule of `path_steps`."""
         B, N = self._batch_of(node_mask)
-        pl = self._plan("sample_from_latent", "latent", t_start=t_start, injected=raw_noises is not None, B=B, N=N, **given(locals()))
+        pl = self._plan("sample_from_latent", "latent", t_start=t_start, injected=raw_noises is not None, B=B, N=N, fix_noise=fix_noise,
+                        **given(locals()))
         k_lo, k_hi = int(k_lo), pl.K if k_hi is None else int(k_hi)
         if not (0 <= k_lo <= k_hi <= pl.K):
             raise ValueError(f"need 0 <= k_lo <= k_hi <= {pl.K} (the path's transitions)")
@@ -1396,7 +1466,8 @@ class DiffusionQM9(_Base):
                            raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                            solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                            keep_frames: Optional[int] = None, record: Optional[str] = None,
-                           restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None):
+                           restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
+                           particles=None, steer_scale=None, steer_ess=None, steer_schedule=None):
         """(x, h) from a state z [B,N,D] at the grid index `t_start` (default T; normalised units - what `diffuse` and `encode`
         return): the partial reverse chain on `paths.partial_path(T, t_start, steps, spacing, timesteps)` (default: every grid point
         below t_start) inside the library's loop (hd_sample_path), then the final decode of `sample_from_masks`.  `eta` defaults to
@@ -1408,7 +1479,8 @@ class DiffusionQM9(_Base):
         keep_frames / record: as in `sample_from_masks` - a third tensor chain [keep_frames, B, N, D] of the partial chain.
         restraints / restraint_scale / restraint_schedule / restraint_clip: as in `sample_from_masks`, on the partial chain."""
         B, N = self._batch_of(node_mask)
-        pl = self._plan("sample_from_latent", "latent", t_start=t_start, injected=raw_noises is not None, B=B, N=N, **given(locals()))
+        pl = self._plan("sample_from_latent", "latent", t_start=t_start, injected=raw_noises is not None, B=B, N=N, fix_noise=fix_noise,
+                        **given(locals()))
         K = pl.K
         if raw_noises is not None and len(raw_noises) != K + 1:
             raise ValueError(f"raw_noises must hold {K} + 1 (randn_x, randn_h) pairs: the transitions, then the decode")
@@ -1482,6 +1554,9 @@ class DiffusionQM9(_Base):
             raise ValueError("vary: no samples")
         with_ctx = self.dynamics.context_node_nf > 0
         jobs = [mol for mol in samples for _ in range(int(n_variants))]
+        if pl.steer is not None and (int(n_variants) % pl.steer.P or int(batch_size) % pl.steer.P):
+            raise ValueError(f"vary: n_variants ({n_variants}) and batch_size ({batch_size}) must be multiples of particles "
+                             f"({pl.steer.P}): the variants of one input form its groups")
         if gd_all is not None and gd_all.rows != 1 and gd_all.rows != len(jobs):
             raise ValueError(f"vary: guidance_scale must hold one scale per result ([{len(jobs)}], input-major), got {gd_all.rows}")
         if rr_all is not None:
@@ -1517,6 +1592,9 @@ class DiffusionQM9(_Base):
                 part.append(res)
             if chain_t is not None:
                 self._chain_into(part, got[2], [int(nm[i].sum()) for i in range(nm.shape[0])], chain_t)
+            if pl.steer is not None:
+                from . import steering
+                steering.into(part, self.steer_last, group0=lo // pl.steer.P)
             out.extend(part)
         return out
 
@@ -1530,6 +1608,8 @@ class DiffusionQM9(_Base):
         Returns a list of `frames` results.  Mechanism only: what lies between two molecules is a property of the weights."""
         from . import scoring, restraints as _rs
         _rs.refuse(self, "interpolate", restraints, ": its frames are reconstructions of the interpolated latents")
+        from . import steering as _st
+        _st.refuse(self, "interpolate")
         device = torch.device(device)
         if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or int(frames) < 2:
             raise ValueError(f"frames must be an integer >= 2, got {frames!r}")
@@ -1651,6 +1731,8 @@ class DiffusionQM9(_Base):
         (known rows replaced), or that round's data prediction, and frame 0 the returned (x, h)."""
         from . import restraints as _rs
         _rs.refuse(self, "sample_inpaint", restraints, ": inpainting re-centres on the known fragments, so its frame moves")
+        from . import steering as _st
+        _st.refuse(self, "sample_inpaint")
         B, N = self._batch_of(node_mask)
         pl = self._plan("sample_inpaint", "inpaint", B=B, N=N, **given(locals()))            # every keyword error before any shape check
         st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, pl)
@@ -1680,6 +1762,8 @@ class DiffusionQM9(_Base):
         device = torch.device(device)
         from . import restraints as _rs
         _rs.refuse(self, "sample_grow", restraints, ": inpainting re-centres on the known fragments, so its frame moves")
+        from . import steering as _st
+        _st.refuse(self, "sample_grow")
         few = given(locals())
         chain_t = self._plan("sample_grow", "inpaint", **few).chain_t                    # argument errors first
         num = len(known)
@@ -1728,7 +1812,8 @@ class DiffusionQM9(_Base):
                timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                keep_frames: Optional[int] = None, record: Optional[str] = None,
-               restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None):
+               restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
+               particles=None, steer_scale=None, steer_ess=None, steer_schedule=None):
         """diffusion_qm9.py:347-395: list of {'x': [n_i,3], 'h': [n_i,8], ('context': [n_i,1])} on the CPU.
         steps / eta / spacing / timesteps: few-step sampling, see `sample_from_masks`; guidance_scale (a float or a
         [num_samples] tensor) / guidance_context ([num_samples, n_max, C]) / guidance_rescale: classifier-free guidance, ibid.;
@@ -1745,7 +1830,10 @@ class DiffusionQM9(_Base):
         pl = self._plan("sample", pocket=pocket_cond, B=int(num_samples), **few)         # argument errors before anything is drawn
         if pl.guidance is not None and context is None:
             raise ValueError("context required")
-        sample_n = self.nodes_dist.sample(num_samples)
+        if pl.steer is not None:                         # one size per group, P times: the particles of a group share their mask
+            sample_n = [n for n in self.nodes_dist.sample(int(num_samples) // pl.steer.P) for _ in range(pl.steer.P)]
+        else:
+            sample_n = self.nodes_dist.sample(num_samples)
         pocket = None
         if pocket_cond is not None:
             if not self.pocket:
@@ -1800,6 +1888,9 @@ class DiffusionQM9(_Base):
             en = rr.rs.energy(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0]))).cpu()
             for i in range(num_samples):
                 out[i]['restraint_energy'] = en[i].clone()
+        if pl.steer is not None:
+            from . import steering
+            steering.into(out, self.steer_last)
         return out
 
     def sample_batches(self, batch_size, num_batches, device, context_range=None, protein_data_all=None,
@@ -1821,6 +1912,8 @@ class DiffusionQM9(_Base):
         device = torch.device(device)
         from . import restraints as _rs
         _rs.refuse(self, "sample_batches", restraints, ": the batches' padded widths and molecule counts differ (use sample)")
+        from . import steering as _st
+        _st.refuse(self, "sample_batches")
         # classifier-free guidance (`sample_from_masks`): guidance_scale may also be a list / tuple of scales cycled per batch the way
         # context_range is; inside a merged device batch it becomes one scale per molecule
         from . import guidance

@@ -11,11 +11,12 @@ from typing import List, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import guidance as _guidance, paths, restraints as _rs
+from . import guidance as _guidance, paths, restraints as _rs, steering as _steering
 
 #: the sampling keywords of the entry points; the list forms (`sample`, `sample_batches`, `vary`, the EDM signature) forward those given
 KEYWORDS = ("steps", "eta", "spacing", "timesteps", "guidance_scale", "guidance_context", "guidance_rescale", "solver",
-            "lower_order_final", "keep_frames", "record", "restraints", "restraint_scale", "restraint_schedule", "restraint_clip")
+            "lower_order_final", "keep_frames", "record", "restraints", "restraint_scale", "restraint_schedule", "restraint_clip",
+            "particles", "steer_scale", "steer_ess", "steer_schedule")
 
 
 def given(values: dict) -> dict:
@@ -32,6 +33,7 @@ class Plan(NamedTuple):
     frames: Optional[paths.ChainFrames]           # a recording call: frame of every transition; None: nothing is recorded
     record: Optional[int]                         # the library's code of `record`: 0 "z", 1 "x0"
     chain_t: Optional[torch.Tensor]               # [keep] int64, the grid index every frame has arrived at
+    steer: Optional[_steering.Steer] = None       # a steered call: particles per group, beta, rho; None: the unsteered code path
 
 
 def unsupported(model, what: str, pocket=None, needs_noise: bool = True, pocket_error=NotImplementedError) -> None:
@@ -98,13 +100,18 @@ def latent_path(model, t_start, steps, eta, spacing, timesteps, solver=None, low
 def plan(model, what: str, kind: str = "full", *, t_start=None, pocket=None, injected: bool = False, B: Optional[int] = None,
          N: Optional[int] = None, force_path: bool = False, guided: bool = True, steps=None, eta=None, spacing=None, timesteps=None, guidance_scale=None,
          guidance_context=None, guidance_rescale=None, solver=None, lower_order_final=None, keep_frames=None, record=None,
-         restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None) -> Plan:
+         restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
+         particles=None, steer_scale=None, steer_ess=None, steer_schedule=None) -> Plan:
     """The `Plan` of the call `what`.  `kind`: "full" (the chain from T), "latent" (from `t_start`) or "inpaint" (from T, ancestral
     steps only; it takes no restraints - its callers refuse them).  `pocket`: the fixed residues of the call, if any; `injected`: the
     caller brings its own noise; `B` / `N`: the batch, where the caller knows it (shapes of per-molecule scales are checked);
     `force_path`: never the plain loop; `guided=False`: the call takes no guidance (`inpaint_steps`).
 
-    Errors are raised in this order: path and solver, guidance, restraints, chain (keep_frames / record); the shapes of a call's
+    particles / steer_scale / steer_ess / steer_schedule: steered sampling (hierdiff_amd/steering.py) -> `Plan.steer`; particles of
+    None or 1, or a steer_scale of None or 0, is the unsteered plan, field for field.  Its errors come last, behind the chain's, so
+    no earlier refusal moves; an inpainting plan refuses it.
+
+    Errors are raised in this order: path and solver, guidance, restraints, chain (keep_frames / record), steering; the shapes of a call's
     tensors are its entry point's business and come after the plan.  A guided, restrained or recorded call always runs on a path:
     where the keywords ask for the plain loop it gets the identity path with ancestral steps - here, and nowhere else."""
     if kind == "latent":
@@ -115,8 +122,10 @@ def plan(model, what: str, kind: str = "full", *, t_start=None, pocket=None, inj
     needs_noise = not injected
     gd = _guidance.resolve(model, guidance_scale, guidance_context, guidance_rescale, B, N, what, pocket, needs_noise) if guided else None
     rr = None
+    steered = _steering.wanted(model, particles, steer_scale)
     if kind != "inpaint":
-        rr = _rs.resolve(model, restraints, restraint_scale, restraint_schedule, restraint_clip, B, what, pocket, needs_noise)
+        rr = _rs.resolve(model, restraints, restraint_scale, restraint_schedule, restraint_clip, B, what, pocket, needs_noise,
+                         steered=steered)
     code = None
     if keep_frames is None:
         if record is not None:
@@ -134,4 +143,13 @@ def plan(model, what: str, kind: str = "full", *, t_start=None, pocket=None, inj
     if code is not None:
         frames = paths.chain_frames(len(path) - 1, keep_frames, path)
         chain_t = torch.tensor(frames.frame_t, dtype=torch.int64)
-    return Plan(path, eta, model.T if path is None else len(path) - 1, gd, rr, frames, code, chain_t)
+    K = model.T if path is None else len(path) - 1
+    st = None
+    if steered:
+        if kind == "inpaint":
+            raise NotImplementedError(f"{what}: steered sampling is not supported here: inpainting takes no restraints (it acts in "
+                                      f"{_steering.WHERE})")
+        unsupported(model, f"{what}: steering", pocket, needs_noise)
+        st = _steering.resolve(model, particles, steer_scale, steer_ess, steer_schedule, eta, K, rr is not None, B, what,
+                               injected=injected)
+    return Plan(path, eta, K, gd, rr, frames, code, chain_t, st)

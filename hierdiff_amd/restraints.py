@@ -266,10 +266,12 @@ class Resolved:
 
 
 def resolve(model, restraints, scale, schedule, clip, B: Optional[int] = None, what: str = "restraints", pocket=None,
-            needs_noise: bool = True) -> Optional[Resolved]:
+            needs_noise: bool = True, steered: bool = False) -> Optional[Resolved]:
     """Keywords (None: the model's `restraints` / `restraint_scale` / `restraint_schedule` / `restraint_clip`) -> None for the
     unrestrained code path, untouched, or a `Resolved`.  No restraints, or a scale of None or 0, is the unrestrained path.  Pure host
-    checks: every error is raised before a device is looked at."""
+    checks: every error is raised before a device is looked at.  `steered`: the call steers particles by the restraint energy
+    (hierdiff_amd/steering.py), which needs the tables but not the gradient update - a scale of None or 0 then resolves to a
+    `Resolved` with the scale 0 (k_restrain_eps writes nothing)."""
     restraints = model.restraints if restraints is None else restraints
     scale = model.restraint_scale if scale is None else scale
     schedule = model.restraint_schedule if schedule is None else schedule
@@ -279,7 +281,9 @@ def resolve(model, restraints, scale, schedule, clip, B: Optional[int] = None, w
     if not isinstance(restraints, Restraints):
         raise ValueError(f"restraints must be a hierdiff_amd.restraints.Restraints, got {type(restraints).__name__}")
     if scale is None:
-        return None
+        if not steered:
+            return None
+        scale = 0.0
     if isinstance(scale, bool):
         raise ValueError(f"restraint_scale must be a number or a [B] tensor, got {scale!r}")
     try:
@@ -299,7 +303,7 @@ def resolve(model, restraints, scale, schedule, clip, B: Optional[int] = None, w
     elif schedule not in SCHEDULES:
         raise ValueError(f"restraint_schedule must be one of {SCHEDULES} or a length-K sequence, got {schedule!r}")
     c = check_clip(clip)
-    if not bool((s != 0).any()):
+    if not bool((s != 0).any()) and not steered:
         return None
     from .plan import unsupported
     unsupported(model, f"{what}: restraints", pocket, needs_noise)         # (the model's frame is the ligand's alone)

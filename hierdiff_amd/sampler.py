@@ -224,7 +224,32 @@ def parse_args(argv=None):
                     help="with --restraints: the weight of transition k, nv0 sigma_t / alpha_t (score, default) or sigma_t")
     ap.add_argument("--restraint-clip", type=float, default=None, metavar="C",
                     help="with --restraints: the largest step per node in noise-prediction units (default: none)")
+    ap.add_argument("--particles", type=int, default=None, metavar="P",
+                    help="with --restraints and --steer-scale: steered sampling - every P consecutive molecules of a batch are the "
+                         "particles of one group (one drawn size, equal context), weighted at every transition by the change of "
+                         "their restraint energy and resampled inside the device loop when their effective sample size falls below "
+                         "--steer-ess * P; --batch-size (and --variants) must be multiples of P.  Without --restraint-scale the "
+                         "gradient update is off (selection only).  Results also hold steer_logw / steer_root / steer_group.  "
+                         "Mechanism only: which P, scale and threshold help is for you to validate")
+    ap.add_argument("--steer-scale", type=float, default=None, metavar="S", help="with --particles: beta, the weight of the energy "
+                    "change in the log-weights")
+    ap.add_argument("--steer-ess", type=float, default=None, metavar="R", help="with --particles: resample below R * P (default 0.5)")
     args = ap.parse_args(argv)
+    if (args.particles is None) != (args.steer_scale is None):
+        ap.error("--particles and --steer-scale go together")
+    if args.steer_ess is not None and args.particles is None:
+        ap.error("--steer-ess needs --particles and --steer-scale")
+    if args.particles is not None:
+        if args.restraints is None:
+            ap.error("--particles needs --restraints (the particles are weighted by their restraint energy)")
+        if not 1 <= args.particles <= 256:
+            ap.error("--particles must lie in 1 .. 256")
+        if not (math.isfinite(args.steer_scale) and args.steer_scale >= 0.0):
+            ap.error("--steer-scale must be finite and >= 0")
+        if args.steer_ess is not None and not 0.0 < args.steer_ess <= 1.0:
+            ap.error("--steer-ess must lie in (0, 1]")
+        if args.batch_size % args.particles or (args.vary is not None and args.variants % args.particles):
+            ap.error("--batch-size (and with --vary, --variants) must be a multiple of --particles")
     if args.restraints is None and (args.restraint_scale is not None or args.restraint_schedule is not None
                                     or args.restraint_clip is not None):
         ap.error("--restraint-scale / --restraint-schedule / --restraint-clip need --restraints")
@@ -237,7 +262,7 @@ def parse_args(argv=None):
             ap.error("--restraint-clip must be > 0")
         if args.restraint_scale is not None and not math.isfinite(args.restraint_scale):
             ap.error("--restraint-scale must be finite")
-        if args.restraint_scale is None:
+        if args.restraint_scale is None and args.particles is None:
             args.restraint_scale = 1.0
     if args.record is not None and args.chain is None:
         ap.error("--record needs --chain")
@@ -344,6 +369,8 @@ def main(argv=None) -> int:
         from .restraints import Restraints
         chain.update(restraints=Restraints.from_json(args.restraints), restraint_scale=args.restraint_scale,
                      restraint_schedule=args.restraint_schedule, restraint_clip=args.restraint_clip)
+    if args.particles is not None:
+        chain.update(particles=args.particles, steer_scale=args.steer_scale, steer_ess=args.steer_ess)
 
     if args.score is not None:
         if world > 1:
@@ -394,6 +421,7 @@ def main(argv=None) -> int:
         write_results(args.out, grown)
         return 0
 
+    steered = args.particles is not None and args.particles > 1 and args.steer_scale != 0.0
     torch.manual_seed(args.seed)           # the node-count draw uses torch's CPU generator (distributions.py)
     results: List[dict] = []
     first, count = shard_sample_ids(0, args.num_batches, rank, world)      # whole batches per rank
@@ -401,7 +429,7 @@ def main(argv=None) -> int:
         if not (first <= b < first + count):
             # advance the node-count generator over batches owned by other ranks, so the global sequence of
             # molecule sizes (and, with the counter-based noise, every sample) is independent of the world size
-            model.nodes_dist.sample(args.batch_size)
+            model.nodes_dist.sample(args.batch_size // (args.particles if steered else 1))    # (a steered batch draws one size per group)
             continue
         ctx = None if not args.context else args.context[b % len(args.context)]
         results.extend(model.sample(args.batch_size, dev, context=ctx, sample_id_base=b * args.batch_size, **chain))

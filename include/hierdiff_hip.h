@@ -412,6 +412,40 @@ int hd_restraint_detach(hd_topology* topo);
 int hd_restrain_eps(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4, float* out, void* stream);
 int hd_restraint_energy(hd_handle* h, hd_topology* topo, const float* x, double* out3, void* stream);
 
+/* ---- Steered sampling (ABI 12, additive; no reference counterpart): sequential Monte-Carlo steering of a restrained path loop.
+ * The batch is G groups of P rows (particles); group g owns rows g P .. g P + P - 1, which the CALLER guarantees to have equal
+ * masks, contexts and restraint rows.  At every transition k, behind the network call, guidance and the restraint update of eps^:
+ *   U(b)     = U_obs + U_pair + U_anc of row b's data prediction x^0 (the fp32 x^0 of the restraint update; the energy in double)
+ *   logw[b] += -beta_k (U(b) - U_prev[b]);  U_prev[b] = U(b)       a non-finite U or update: logw[b] = -inf (weight 0)
+ *   per group: w_i = exp(logw_i - max), S = sum w, ESS = S^2 / sum w^2 (sums in index order).  ESS < ess P: systematic resampling
+ *     with one uniform u - anc[j] = the smallest i whose inclusive prefix sum of w exceeds (u + j) / P * S - and rows with
+ *     anc[j] != j receive z_t, eps^, U_prev and the lineage root of row anc[j]; the group's logw is reset to 0.  Otherwise, and in a
+ *     group whose weights are all 0 (counted), nothing moves.
+ * The posterior step follows with every row's own noise, so duplicates diverge: steering needs noise_rows == B and a stochastic
+ * update (multistep rows are HD_E_INVALID).  u = hd_philox_uniform_host(seed, sample_id_base + g P, the transition's draw T - s,
+ * 0xfffffffe).  Four more launches per transition (k_steer_weigh, k_steer_resample, two of k_steer_gather), plain kernel nodes of
+ * a captured transition.  A group's result depends on the seed, the ids of its rows, P, its masks and tables, the weights, the
+ * schedule and the path only - not on other groups, graph replay or how the chain is cut into calls.
+ * hd_set_steer: the rows3[K][3] = {alpha_t, sigma_t, beta_k} (host) of the CURRENT path, as hd_set_restraint.  HD_E_INVALID: K != the
+ *   path's K, alpha_t <= 0, sigma_t < 0, beta_k negative or non-finite.
+ * hd_steer_attach: from now on hd_sample_path / hd_sample_path_guided on this topology are steered; they need attached restraints
+ *   (hd_restraint_attach; a scale of 0 steers without the gradient update) and the rows of hd_set_steer.  The steering state
+ *   (logw, U_prev, roots, statistics) belongs to the topology and survives between calls: reset != 0 starts a chain (logw = U_prev =
+ *   0, root[b] = b mod P), reset == 0 continues the one the last call left (HD_E_STATE when there is none for this P).
+ *   HD_E_INVALID: P outside 2 .. 256, B not a multiple of P, ess outside (0, 1].  Re-attaching with the same P and ess replays
+ *   the cached graph.
+ * hd_steer_detach: the launches, graphs and keys are again those of a topology that never was steered.
+ * hd_steer_step: the stage above once, on given tensors z, eps [B][N][D] (both rewritten in the moved rows) with a host row3.
+ * hd_steer_read: stream-ordered copies of the state into host or device buffers, any of which may be NULL: logw [B], uprev [B]
+ *   (double), root [B], anc [B] (int32; anc: the source ROW of the latest transition), stats [B / P][3] (double: resampling events,
+ *   the smallest ESS, transitions in which every weight was 0) since the last reset. */
+int hd_set_steer(hd_handle* h, int K, const float* rows3);
+int hd_steer_attach(hd_topology* topo, int P, double ess, int reset, void* stream);
+int hd_steer_detach(hd_topology* topo);
+int hd_steer_step(hd_handle* h, hd_topology* topo, float* z, float* eps, const float* row3, uint32_t draw, uint64_t seed,
+                  uint64_t sample_id_base, void* stream);
+int hd_steer_read(hd_topology* topo, double* logw, double* uprev, int* root, int* anc, double* stats, void* stream);
+
 /* ---- Scoring (ABI 12, additive; no reference counterpart beyond the one-timestep estimator, compute_loss with t0_always = True,
  * diffusion_qm9.py:530-699): the variational bound of GIVEN molecules with every term of a list evaluated, in the device loop.
  * For normalised data xh [B,N,D] and a term t in 1 .. T (s = t - 1):
@@ -686,6 +720,9 @@ int hd_params_digest(int device, const void* const* ptrs_dev, const long long* p
 /* Host implementation of the library's normal generator (same bits as the device one up to libm
  * round-off); used by tests and by callers that want to reproduce a draw on the CPU. */
 float hd_philox_normal_host(uint64_t seed, uint64_t sample_id, uint32_t draw, uint32_t index);
+/* Host twin of the uniform the steering stage draws (exactly the device's bits: integer arithmetic and one exact conversion): words
+ * 2 and 3 of the counter block (index / 2, draw, sample_id) - the normals take words 0 and 1 - 26 bits each, in double, in (0, 1). */
+double hd_philox_uniform_host(uint64_t seed, uint64_t sample_id, uint32_t draw, uint32_t index);
 
 /* Kernel timing of the most recent hd_egnn_forward when profiling is enabled: per-kernel-family
  * accumulated milliseconds measured with HIP events on the caller's stream.
