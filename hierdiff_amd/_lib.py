@@ -89,6 +89,9 @@ SIGNATURES = {
     "hd_set_path_up": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "hd_set_path_multistep": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "hd_multistep_step": (C.c_int, [_VP, _VP, _FP, _FP, C.POINTER(C.c_float), _FP, _FP, _FP, _VP]),
+    "hd_set_path_multistep_sde": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "hd_multistep_sde_step": (C.c_int, [_VP, _VP, _FP, _FP, C.POINTER(C.c_float), _FP, _FP, _FP, _FP, C.c_int, C.c_uint64, C.c_uint64,
+                                        C.c_uint32, C.c_int, C.c_int, _FP, _VP]),
     "hd_slerp": (C.c_int, [_VP, _VP, _FP, _FP, C.POINTER(C.c_float), C.c_int, _FP, _VP]),
     "hd_set_nll_terms": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "hd_nll_terms": (C.c_int, [_VP, _VP, _FP, _FP, C.c_int, C.c_int, C.c_int, _FP, _FP, C.c_int, C.c_uint64, C.c_uint64, C.c_int,

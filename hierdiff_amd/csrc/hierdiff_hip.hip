@@ -68,7 +68,7 @@ struct PathTables {
     int K = 0, form = 0;             // form 0: ancestral rows, 1: linear rows {a, b, c, 0}, 2: multistep rows {a, b, c2, p, q} (5 floats)
     bool up = false;                 // the path ascends (hd_set_path_up: t_idx[k] < s_idx[k], linear rows with c == 0)
     std::vector<int> t_h, s_h;
-    std::vector<float> c2_h;         // form 2: c2 of every row (which transitions read the history)
+    std::vector<float> c2_h;         // forms 2 and 3: c2 of every row (which transitions read the history)
     int *d_t = nullptr, *d_s = nullptr;
     float *d_coef = nullptr, *d_coef_ip = nullptr;   // [K][4] each; d_coef_ip null when no inpainting rows were given
     unsigned long long sched_gen = 0, gen = 0;       // sched_gen the tables were set for (0: not set); bumped by every rewrite
@@ -273,7 +273,7 @@ struct hd_topology {
     double st_ess;
     double *st_f64;                            // logw [B], U_prev [B], its scratch [B], stats [B / P][3] (room for [B][3])
     int* st_i32;                               // root [B], anc [B]
-    float* st_scratch;                         // [2][B][N][D]
+    float* st_scratch;                         // [3][B][N][D]
     unsigned long long st_gen;
     // multistep paths (hd_set_path_multistep): the previous transition's data prediction x^ [B][N][D], allocated by the first
     // form-2 call at an address the captured transitions keep; host-side, which path generation and position it belongs to

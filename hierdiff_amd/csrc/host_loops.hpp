@@ -98,6 +98,43 @@ extern "C" int hd_multistep_step(hd_handle* h, hd_topology* topo, const float* z
     return solver_launch(h, topo, io, zt, eps, nullptr, row5, x_prev, x_out, topo->N);
 }
 
+// the stochastic multistep form (k_multistep_sde_step): `coef` device rows [K][6] read at *io.step, or the host row by value; the
+// noise as in step_impl
+static int sde_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* zt, const float* eps, const float* coef,
+                      const float* row6, const float* x_prev, float* x_out, const NoiseSrc& ns, const uint32_t* draw_w, int mol,
+                      int raw_step0) {
+    ProfScope ps(h, io.s, 2);
+    SdeSolverArgs a;
+    a.zt = zt; a.eps = eps; a.coef = coef; a.nm = t->nm_bytes; a.x_prev = x_prev; a.x_out = x_out; a.zs = io.z; a.noise = ns;
+    a.draw_ptr = draw_w; a.step_ptr = io.step; a.base_ptr = io.base_w; a.raw_step0 = raw_step0;
+    for (int k = 0; k < 6; ++k) a.row[k] = row6 ? row6[k] : 0.f;
+    a.B = t->B; a.N = t->N; a.D = h->D; a.F = h->F; a.mol = mol;
+    hipLaunchKernelGGL(k_multistep_sde_step, dim3(t->B), dim3(256), (size_t)mol * a.D * sizeof(float), io.s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_multistep_sde_step(hd_handle* h, hd_topology* topo, const float* zt, const float* eps, const float* row6,
+                                     const float* x_prev, float* x_out, const float* raw_x, const float* raw_h, int noise_rows,
+                                     uint64_t seed, uint64_t sample_id_base, uint32_t draw, int share_rows, int mol_shape, float* zs,
+                                     void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_multistep_sde_step: null handle/topology");
+    if (!zt || !eps || !row6 || !x_out || !zs) return fail(HD_E_INVALID, "hd_multistep_sde_step: null tensor");
+    if (row6[3] != 0.f && !x_prev) return fail(HD_E_INVALID, "hd_multistep_sde_step: a row with c2 != 0 needs x_prev");
+    if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, "hd_multistep_sde_step: raw_x and raw_h go together");
+    if (noise_rows != 1 && noise_rows != topo->B) return fail(HD_E_INVALID, "hd_multistep_sde_step: noise_rows must be 1 or B");
+    if (x_out == zt || x_out == eps || x_out == zs || zs == eps || (x_prev && (zs == x_prev || x_prev == zt || x_prev == eps)))
+        return fail(HD_E_INVALID, "hd_multistep_sde_step: only zs == zt and x_out == x_prev may alias");
+    const int mol = (mol_shape < 0 || mol_shape > topo->N) ? topo->N : mol_shape;
+    if ((size_t)mol * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_multistep_sde_step: N * D floats exceed one workgroup's LDS");
+    HIP_TRY(hipSetDevice(h->device));
+    topo_use(topo, (hipStream_t)stream);
+    LoopIO io{};
+    io.z = zs; io.s = (hipStream_t)stream;
+    return sde_launch(h, topo, io, zt, eps, nullptr, row6, x_prev, x_out,
+                      make_noise(raw_x, raw_h, noise_rows, seed, sample_id_base, draw, (noise_rows == 1 || share_rows) ? 1 : 0), nullptr, mol, 0);
+}
+
 extern "C" int hd_final_decode(hd_handle* h, hd_topology* topo, const float* z0, const float* eps, const float* coef3,
                                const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed,
                                uint64_t sample_id_base, uint32_t draw, int share_rows, float* x, float* hfeat,
@@ -148,9 +185,9 @@ static int set_path_tables(hd_handle* h, PathTables& pt, int K, const int* t_idx
     pt.sched_gen = 0; pt.K = 0;
     pt.t_h.assign(t_idx, t_idx + K);
     pt.s_h.assign(s_idx, s_idx + K);
-    if (form == 2) {
+    if (form == 2 || form == 3) {
         pt.c2_h.resize((size_t)K);
-        for (int k = 0; k < K; ++k) pt.c2_h[(size_t)k] = rows[(size_t)row_width * k + 2];
+        for (int k = 0; k < K; ++k) pt.c2_h[(size_t)k] = rows[(size_t)row_width * k + (form == 3 ? 3 : 2)];
     }
     HD_TRY(dev_upload(&pt.d_t, pt.t_h));
     HD_TRY(dev_upload(&pt.d_s, pt.s_h));
@@ -407,6 +444,21 @@ extern "C" int hd_set_path_multistep(hd_handle* h, int K, const int* t_idx, cons
     return set_path_tables(h, h->path, K, t_idx, s_idx, rows5, 5, nullptr, 2, false);
 }
 
+// A descending path with stochastic multistep rows {a, b, c, c2, p, q} (form 3, k_solver.hpp) into the same tables.
+extern "C" int hd_set_path_multistep_sde(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* rows6) {
+    if (!h || !t_idx || !s_idx || !rows6 || K < 1) return fail(HD_E_INVALID, "hd_set_path_multistep_sde: bad argument");
+    if (h->T < 1) return fail(HD_E_STATE, "hd_set_path_multistep_sde: schedule not set (hd_set_schedule)");
+    if (K > h->T) return fail(HD_E_INVALID, "hd_set_path_multistep_sde: more transitions than the schedule has steps");
+    for (int k = 0; k < K; ++k) {
+        if (t_idx[k] > h->T || s_idx[k] < 0 || s_idx[k] >= t_idx[k])
+            return fail(HD_E_INVALID, "hd_set_path_multistep_sde: need 0 <= s_idx[k] < t_idx[k] <= T (a multistep path descends)");
+        if (k > 0 && t_idx[k] != s_idx[k - 1])
+            return fail(HD_E_INVALID, "hd_set_path_multistep_sde: transition k must start where k - 1 arrived");
+    }
+    if (rows6[3] != 0.f) return fail(HD_E_INVALID, "hd_set_path_multistep_sde: c2 of row 0 must be 0 (the first transition has no history)");
+    return set_path_tables(h, h->path, K, t_idx, s_idx, rows6, 6, nullptr, 3, false);
+}
+
 extern "C" long long hd_path_graph_builds(const hd_topology* topo) { return topo ? topo->g_path.builds : -1; }
 
 // ----------------------------------------------------------------------------- recording the trajectory of a path loop
@@ -628,7 +680,7 @@ extern "C" int hd_steer_attach(hd_topology* topo, int P, double ess, int reset, 
         return fail(HD_E_STATE, "hd_steer_attach: reset = 0 continues a chain, and this topology holds no steering state for this P");
     if (fresh) {
         if (!topo->st_i32) HD_TRY(dev_alloc(&topo->st_i32, 2 * B));
-        if (!topo->st_scratch) HD_TRY(dev_alloc(&topo->st_scratch, 2 * B * topo->N * topo->h->D));
+        if (!topo->st_scratch) HD_TRY(dev_alloc(&topo->st_scratch, 3 * B * topo->N * topo->h->D));
         HD_TRY(dev_alloc(&topo->st_f64, 6 * B));            // last: its presence says all three are there
     }
     if (fresh || P != topo->st_P || ess != topo->st_ess) topo->st_gen++;
@@ -648,8 +700,9 @@ extern "C" int hd_steer_detach(hd_topology* topo) {
 
 // The three stages of one transition on z / eps (both may be rewritten): `rows` the device table read at *io.step / io.row, or the
 // host row; the draw and the first sample id by value or from the loop's device words.
+// `hist`: the data prediction the stochastic multistep rows keep, which follows its lineage with z and eps (null: none).
 static int steer_launch(hd_handle* h, hd_topology* t, const LoopIO& io, float* z, float* eps, const float* rows, const float* row3,
-                        LoopIO::Draw d, uint64_t seed) {
+                        LoopIO::Draw d, uint64_t seed, float* hist = nullptr) {
     ProfScope ps(h, io.s, 2);
     const SteerState st = steer_state(t);
     SteerWeighArgs w;
@@ -662,7 +715,7 @@ static int steer_launch(hd_handle* h, hd_topology* t, const LoopIO& io, float* z
     r.P = t->st_P;
     hipLaunchKernelGGL(k_steer_resample, dim3(t->B / t->st_P), dim3(256), 0, io.s, r);
     SteerGatherArgs g;
-    g.z = z; g.eps = eps; g.scratch = t->st_scratch; g.uprev = st.uprev; g.us = t->st_f64 + 2 * (size_t)t->B; g.anc = st.anc;
+    g.z = z; g.eps = eps; g.hist = hist; g.scratch = t->st_scratch; g.uprev = st.uprev; g.us = t->st_f64 + 2 * (size_t)t->B; g.anc = st.anc;
     g.B = t->B; g.total = t->N * h->D;
     hipLaunchKernelGGL(k_steer_gather<0>, dim3(t->B), dim3(256), 0, io.s, g);
     hipLaunchKernelGGL(k_steer_gather<1>, dim3(t->B), dim3(256), 0, io.s, g);
@@ -817,7 +870,8 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
                 HD_TRY(guide_launch(h, topo, topo->eps, topo->eps_u, io.w, gd->w_rows, gd->phi, topo->eps, io.s));
             }
             if (rsn) HD_TRY(restrain_launch(h, topo, io, io.z, topo->eps, topo->eps, h->d_rs_rows, nullptr));
-            if (stn) HD_TRY(steer_launch(h, topo, io, io.z, topo->eps, h->d_st_rows, nullptr, io.draw_of(0, stride), c.seed));
+            if (stn) HD_TRY(steer_launch(h, topo, io, io.z, topo->eps, h->d_st_rows, nullptr, io.draw_of(0, stride), c.seed,
+                                         form == 3 ? topo->ms_hist : nullptr));
             const bool rec_z = rec && j == rounds - 1 && topo->chain_what == 0;
             if (rec && j == rounds - 1 && topo->chain_what == 1) HD_TRY(chain_launch(h, topo, io, topo->eps));
             if (form == 2) {
@@ -828,6 +882,12 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
             const LoopIO::Draw d = io.draw_of(3 * j, stride);
             NoiseSrc ns = make_noise(c.raw_x ? c.raw_x + io.ro * 3 : nullptr, c.raw_h ? c.raw_h + io.ro * h->F : nullptr, c.noise_rows,
                                      c.seed, io.base, d.value, share);
+            if (form == 3) {
+                HD_TRY(sde_launch(h, topo, io, io.z, topo->eps, pt.d_coef + (size_t)io.row * 6, nullptr, topo->ms_hist, topo->ms_hist, ns,
+                                  d.word, mol, k_lo));
+                if (rec_z) HD_TRY(chain_launch(h, topo, io, nullptr));
+                continue;
+            }
             HD_TRY(step_impl(h, topo, io, io.z, topo->eps, pt.d_coef + (size_t)io.row * 4, 1, ns, d.word, mol, N, form, k_lo));
             if (R) HD_TRY(inpaint_round(h, topo, io, j, R, stride, c.seed, pt.d_coef_ip));
             if (rec_z) HD_TRY(chain_launch(h, topo, io, nullptr));
@@ -902,7 +962,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
 static int path_loop(hd_handle* h, hd_topology* topo, const PathCall& c) {
     const PathTables& pt = *c.pt;
     HIP_TRY(hipSetDevice(h->device));
-    if (pt.form != 2 || c.k_hi == c.k_lo) return path_loop_run(h, topo, c);
+    if ((pt.form != 2 && pt.form != 3) || c.k_hi == c.k_lo) return path_loop_run(h, topo, c);
     // multistep rows: the history x^_{k_lo - 1} is the topology's - a call that starts on a row with c2 != 0 continues the call
     // that left it, on the same path (generation) and at the position where that call ended
     const int mol = (c.mol_shape < 0 || c.mol_shape > topo->N) ? topo->N : c.mol_shape;

@@ -11,7 +11,8 @@
 //                      row of positive weight); lineage roots follow, logw = 0.  Otherwise anc[j] = j.  m = -inf (every weight 0):
 //                      the group is left alone and counted.
 //   k_steer_gather<0>  rows with anc[b] != b: z, eps^ and U_prev of row anc[b] into the topology's scratch
-//   k_steer_gather<1>  ... and from the scratch into row b.  Rows with anc[b] == b are not written.
+//   k_steer_gather<1>  ... and from the scratch into row b.  Rows with anc[b] == b are not written.  With `hist` (the stochastic
+//                      multistep rows, k_solver.hpp) the data prediction x^_{k-1} of the lineage travels the same way.
 // u = philox_uniform(seed, id of the group's first row, the transition's draw T - s, ST_UNIFORM_INDEX): words 2 and 3 of the block
 // whose words 0 and 1 no normal uses (index / 2 = 2^31 - 1; a molecule has at most 16384 entries), 26 bits each, in double.
 // No atomics; every sum has a fixed order.  stats [G][3] = (resampling events, smallest ESS, transitions with every weight 0).
@@ -155,7 +156,8 @@ __global__ __launch_bounds__(256) void k_steer_resample(SteerResampleArgs a) {
 
 struct SteerGatherArgs {
     float *z, *eps;         // [B][N][D]
-    float* scratch;         // [2][B][N][D]
+    float* scratch;         // [3][B][N][D]
+    float* hist;            // [B][N][D] x^_{k-1} of the stochastic multistep rows, or null
     double *uprev, *us;     // [B], and its scratch
     const int* anc;
     int B, total;           // total = N * D
@@ -170,9 +172,11 @@ __global__ __launch_bounds__(256) void k_steer_gather(SteerGatherArgs a) {
     if constexpr (BACK == 0) {
         const size_t os = (size_t)src * a.total;
         for (int e = tid; e < a.total; e += 256) { a.scratch[ob + e] = a.z[os + e]; a.scratch[all + ob + e] = a.eps[os + e]; }
+        if (a.hist) for (int e = tid; e < a.total; e += 256) a.scratch[2 * all + ob + e] = a.hist[os + e];
         if (tid == 0) a.us[b] = a.uprev[src];
     } else {
         for (int e = tid; e < a.total; e += 256) { a.z[ob + e] = a.scratch[ob + e]; a.eps[ob + e] = a.scratch[all + ob + e]; }
+        if (a.hist) for (int e = tid; e < a.total; e += 256) a.hist[ob + e] = a.scratch[2 * all + ob + e];
         if (tid == 0) a.uprev[b] = a.us[b];
     }
 }

@@ -183,7 +183,8 @@ class DiffusionQM9(_Base):
         self.sample_eta = 1.0
         self.sample_spacing = "uniform"
         self.sample_timesteps = None
-        # default of the `solver` keyword: None / "ddim" = the first-order updates above; "dpm2m" = DPM-Solver++(2M), eta = 0
+        # default of the `solver` keyword: None / "ddim" = the first-order updates above; "dpm2m" = DPM-Solver++(2M), eta = 0;
+        # "sde2m" = SDE-DPM-Solver++(2M), second order with the ancestral noise (eta = 1)
         self.sample_solver = None
         self.sample_lower_order_final = True
         self._force_path_loop = False   # tests: run the identity path (K = T, eta = 1) through the path loop instead of the plain one
@@ -657,14 +658,17 @@ class DiffusionQM9(_Base):
                   lambda a: None if a is None else np.ascontiguousarray(a.numpy(), dtype=np.float32).ctypes.data_as(C.POINTER(C.c_float)))
 
         def upload(pt):
-            if ms:
+            if ms and eta.stochastic:
+                _lib.check(_lib.load().hd_set_path_multistep_sde(handle, pt["K"], ip(pt["t_idx"]), ip(pt["s_idx"]), fp(pt["coef"])),
+                           "hd_set_path_multistep_sde")
+            elif ms:
                 _lib.check(_lib.load().hd_set_path_multistep(handle, pt["K"], ip(pt["t_idx"]), ip(pt["s_idx"]), fp(pt["coef"])),
                            "hd_set_path_multistep")
             else:
                 _lib.check(_lib.load().hd_set_path(handle, pt["K"], ip(pt["t_idx"]), ip(pt["s_idx"]), fp(pt["coef"]), pt["form"],
                                                    fp(pt["coef_inpaint"])), "hd_set_path")
 
-        return self._upload_path(tabs, (tuple(path), ("dpm2m", bool(eta.lower_order_final)) if ms else float(eta)),
+        return self._upload_path(tabs, (tuple(path), ("sde2m" if eta.stochastic else "dpm2m", bool(eta.lower_order_final)) if ms else float(eta)),
                                  lambda: paths.path_tables(tabs["gamma"], path, eta), upload)
 
     # ------------------------------------------------------------------ recording a trajectory (the reference's sample_chain)
@@ -1013,7 +1017,7 @@ class DiffusionQM9(_Base):
         steer_ess * P (default 0.5).  Needs `restraints`; `restraint_scale` may be None or 0 (selection without the gradient
         update).  The state of the call is left as `self.steer_last` (`steering.Result`).  A group's result depends on the seed, the
         ids of its rows, P and its own masks and tables only.  particles of None or 1, or a steer_scale of None or 0, is the unsteered
-        code path, untouched.  Not with eta = 0, solver "dpm2m", fix_noise, raw_noises, pocket models, mode 'gnn_dynamics' or
+        code path, untouched.  Not with eta = 0, solver "dpm2m" (solver "sde2m" is the second-order update that steers), fix_noise, raw_noises, pocket models, mode 'gnn_dynamics' or
         noise_mode 'torch'.  Mechanism only.
 
         keep_frames / record (keyword-only; None: nothing is recorded and the call is today's): the reference's `sample_chain`
@@ -1029,7 +1033,11 @@ class DiffusionQM9(_Base):
         from the previous transition's data prediction, kept in a topology-owned buffer; second order, no extra network call,
         first order on the first and - with lower_order_final - the last transition).  It is deterministic on the path: `eta`
         defaults to 0 whatever `sample_eta` says, another explicit eta raises ValueError; steps / spacing / timesteps / guidance_*
-        combine as usual, and the draws are z_T (draw 0) and the decode (T + 1) alone.  Mechanism only, as `steps` / `eta`.
+        combine as usual, and the draws are z_T (draw 0) and the decode (T + 1) alone.  "sde2m" runs SDE-DPM-Solver++(2M)
+        (hd_set_path_multistep_sde): the same correction, with c2 = alpha_s (-expm1(-2 h)) / (2 r), on the ancestral update - second
+        order with the ancestral noise on the path, so it combines with steering (particles=); `eta` defaults to 1 whatever
+        `sample_eta` says, another explicit eta raises ValueError; draws and `raw_noises` (K + 2 pairs) are those of eta = 1 on
+        the same path, and fix_noise works.  Mechanism only, as `steps` / `eta`.
 
         guidance_scale / guidance_context / guidance_rescale (keyword-only; None: the model's attributes of the same names):
         classifier-free guidance of a context-conditioned model - every network call of the chain (the decode's included) runs
@@ -1136,7 +1144,7 @@ class DiffusionQM9(_Base):
         """Transitions k_lo .. k_hi-1 of `sample_from_masks`'s few-step loop on a given z [B,N,D] (normalised units, the state at
         path position k_lo); returns the state at position k_hi (default: the end of the path, z_0 before the decode).  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.
-        solver="dpm2m": transition k > 0 also needs the data prediction of transition k - 1, which the library keeps with the
+        solver="dpm2m" / "sde2m": transition k > 0 also needs the data prediction of transition k - 1, which the library keeps with the
         topology (the masks).  A call with k_lo > 0 must therefore continue the previous call on the same masks and the same path
         exactly where that call ended (its k_hi); a piece-wise chain then gives the bits of the whole.  Anything else - fresh masks,
         another path or solver in between, a gap - raises HierDiffHipError (HD_E_STATE) instead of using a stale prediction."""
@@ -1391,13 +1399,13 @@ class DiffusionQM9(_Base):
         timesteps)` - default every grid point - inside the library's loop (hd_set_path_up / hd_sample_path: one captured transition
         per topology).  Nothing is drawn: the result depends on the data, the masks, the weights and the path only.  Decoding with
         `sample_from_latent(eta=0)` on the same points comes back near the molecule; how near is a property of the weights and K.
-        The inversion stays first order: solver="dpm2m" raises ValueError (the model's `sample_solver` is not consulted)."""
+        The inversion stays first order: solver="dpm2m" or "sde2m" raises ValueError (the model's `sample_solver` is not consulted)."""
         from . import paths, restraints as _rs
         _rs.refuse(self, "encode", restraints, ": the inversion follows the network's own flow")
         from . import steering as _st
         _st.refuse(self, "encode")
         if paths.check_solver(solver) is not None:
-            raise ValueError("encode: the inversion is first order (eta = 0 upwards); solver 'dpm2m' is not supported")
+            raise ValueError(f"encode: the inversion is first order (eta = 0 upwards); solver {solver!r} is not supported")
         t_end = self._grid_index(self.T if t_end is None else t_end, 1, "t_end")
         spacing = self.sample_spacing if spacing is None else spacing
         path = paths.ascending_path(self.T, t_end, steps, spacing, timesteps)
@@ -1726,7 +1734,7 @@ class DiffusionQM9(_Base):
         masks, the weights and its known values only.  steps / spacing / timesteps: few-step sampling as in `sample_from_masks`
         (hd_sample_path_inpaint), ancestral steps only - eta < 1 raises ValueError.  guidance_scale / guidance_context /
         guidance_rescale: classifier-free guidance as in `sample_from_masks` (every round's network call is guided).
-        solver="dpm2m" (or the model's `sample_solver`) raises ValueError like eta < 1.  keep_frames / record: as in
+        solver="dpm2m" or "sde2m" (or the model's `sample_solver`) raises ValueError like eta < 1.  keep_frames / record: as in
         `sample_from_masks` - a third tensor chain [keep_frames, B, N, D]; a frame is the state behind its transition's last round
         (known rows replaced), or that round's data prediction, and frame 0 the returned (x, h)."""
         from . import restraints as _rs
@@ -1817,7 +1825,7 @@ class DiffusionQM9(_Base):
         """diffusion_qm9.py:347-395: list of {'x': [n_i,3], 'h': [n_i,8], ('context': [n_i,1])} on the CPU.
         steps / eta / spacing / timesteps: few-step sampling, see `sample_from_masks`; guidance_scale (a float or a
         [num_samples] tensor) / guidance_context ([num_samples, n_max, C]) / guidance_rescale: classifier-free guidance, ibid.;
-        solver / lower_order_final: "dpm2m" = second-order multistep sampling, ibid.
+        solver / lower_order_final: "dpm2m" / "sde2m" = second-order multistep sampling, ibid.
         keep_frames / record ("z", the default, or "x0"): the trajectory, ibid. - every dict also holds 'chain_x' [keep, n_i, 3],
         'chain_h' [keep, n_i, F] (CPU, data units, the reference's frame order: frame 0 is the result itself) and 'chain_t' [keep],
         the grid index every frame's state had arrived at.

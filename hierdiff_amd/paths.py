@@ -16,6 +16,10 @@ retraining and no new network code - only rows of coefficients from the SAME gam
                transition's data prediction, z_s = (a z_t - b eps) + c2 (x^_k - x^_{k-1}) with x^_k = p z_t - q eps - DPM-Solver++(2M)
                in data-prediction form, second order in the step of lambda = log(alpha / sigma) at no extra network call.
 
+  solver="sde2m"  stochastic multistep rows {a, b, c, c2, p, q} (`multistep_sde_coefficients`): the eta = 1 linear row plus the same
+               kind of correction, z_s = ((a z_t - b eps) + c noise) + c2 (x^_k - x^_{k-1}) with c2 = alpha_s (-expm1(-2 h_k)) / (2 r_k)
+               - SDE-DPM-Solver++(2M): second order AND noise on the path (what steering needs), at no extra network call.
+
 Which K, eta and solver keep sample quality is a property of the trained checkpoint: nothing here can tell.
 """
 from __future__ import annotations
@@ -29,19 +33,26 @@ import torch.nn.functional as F
 from .noise_model import step_coefficients
 
 SPACINGS = ("uniform", "quadratic")
-SOLVERS = (None, "ddim", "dpm2m")
+SOLVERS = (None, "ddim", "dpm2m", "sde2m")
 
 
 class Multistep(NamedTuple):
-    """What travels in the place of `eta` when the second-order multistep solver is asked for (`check_solver`)."""
+    """What travels in the place of `eta` when a second-order multistep solver is asked for (`check_solver`): "dpm2m", or with
+    `stochastic` "sde2m"."""
     lower_order_final: bool = True
+    stochastic: bool = False
 
 
 def check_solver(solver, eta=None, lower_order_final=True) -> Optional[Multistep]:
     """None for the first-order code path (solver None or "ddim"), else the `Multistep` of "dpm2m", which takes no noise on the
-    path: an explicit eta other than 0 is a ValueError."""
+    path: an explicit eta other than 0 is a ValueError - or of "sde2m", whose noise is the ancestral one: an explicit eta other
+    than 1 is a ValueError."""
     if solver not in SOLVERS:
         raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    if solver == "sde2m":
+        if eta is not None and check_eta(eta) != 1.0:
+            raise ValueError(f"solver 'sde2m' draws the ancestral noise (eta = 1), got eta = {eta!r}")
+        return Multistep(bool(lower_order_final), True)
     if solver != "dpm2m":
         return None
     if eta is not None and check_eta(eta) != 0.0:
@@ -163,17 +174,49 @@ def multistep_coefficients(gamma: torch.Tensor, path: Sequence[int], lower_order
     return torch.stack([lin[:, 0], lin[:, 1], c2, 1.0 / alpha_t, torch.sqrt(torch.sigmoid(gt)) / alpha_t], dim=1)
 
 
+def multistep_sde_coefficients(gamma: torch.Tensor, path: Sequence[int], lower_order_final: bool = True) -> torch.Tensor:
+    """[K, 6] float64 rows {a, b, c, c2, p, q} of the SDE-DPM-Solver++(2M) update along a descending `path`:
+        x^_k = p z_t - q eps,   z_s = ((a z_t - b eps) + c noise) + c2 (x^_k - x^_{k-1}),
+    a, b, c the eta = 1 row of `linear_coefficients` (c = sigma_s sqrt(1 - exp(-2 h_k)) is the ancestral sigma~), p and q as in
+    `multistep_coefficients` and c2 = alpha_s (-expm1(-2 h_k)) / (2 r_k): twice the step in the exponent, because the noise
+    takes the other half of the contraction.  c2 = 0 on the first transition and, with `lower_order_final`, on the last.
+    ValueError unless every h_k > 0.  Round to fp32 once, where the rows are uploaded."""
+    idx = torch.as_tensor([int(v) for v in path], dtype=torch.int64)
+    if idx.numel() < 2:
+        raise ValueError("a path holds at least one transition")
+    g = torch.as_tensor(gamma).reshape(-1).to(torch.float64)
+    gt, gs = g[idx[:-1]], g[idx[1:]]
+    hk = (gt - gs) / 2
+    if not bool((hk > 0).all()):
+        raise ValueError("solver 'sde2m' needs a gamma grid that increases strictly along the path (some step of "
+                         "lambda = log(alpha / sigma) is <= 0)")
+    lin = linear_coefficients(gs, gt, 1.0)
+    alpha_s, alpha_t = torch.sqrt(torch.sigmoid(-gs)), torch.sqrt(torch.sigmoid(-gt))
+    c2 = torch.zeros_like(hk)
+    c2[1:] = alpha_s[1:] * (-torch.expm1(-2 * hk[1:])) / (2 * (hk[:-1] / hk[1:]))
+    if lower_order_final:
+        c2[-1] = 0.0
+    return torch.stack([lin[:, 0], lin[:, 1], lin[:, 2], c2, 1.0 / alpha_t, torch.sqrt(torch.sigmoid(gt)) / alpha_t], dim=1)
+
+
 @torch.no_grad()
 def path_tables(gamma: torch.Tensor, path: Sequence[int], eta: Optional[float] = None, solver: Optional[str] = None,
                 lower_order_final: bool = True) -> Dict[str, object]:
     """Rows of a path from the gamma grid [T+1] (fp32, `schedule_tables(...)["gamma"]`): t_idx / s_idx int32 [K], coef fp32 [K,4],
     form (0 ancestral rows, 1 linear rows) and, for eta = 1, the inpainting rows {alpha_s, sigma_s, alpha_t|s, sigma_t|s}.
     solver="dpm2m" (`eta` may also be a `Multistep`): form 2, coef fp32 [K,5] = `multistep_coefficients`, whose a and b are the
-    fp32 values of the eta = 0 rows.  eta None: 1 (ancestral), or 0 with "dpm2m"."""
+    fp32 values of the eta = 0 rows.  solver="sde2m" (a `Multistep` with `stochastic`): form 3, coef fp32 [K,6] =
+    `multistep_sde_coefficients`, whose a, b and c are the fp32 values of the eta = 1 linear rows.  eta None: 1 (ancestral, also
+    with "sde2m"), or 0 with "dpm2m"."""
     ms = eta if isinstance(eta, Multistep) else check_solver(solver, eta, lower_order_final)
     g = torch.as_tensor(gamma, dtype=torch.float32).reshape(-1, 1)
     idx = torch.as_tensor(list(path), dtype=torch.int64)
     t_idx, s_idx = idx[:-1], idx[1:]
+    if ms is not None and ms.stochastic:
+        coef = multistep_sde_coefficients(g, path, ms.lower_order_final).to(torch.float32).contiguous()
+        return {"t_idx": t_idx.to(torch.int32).contiguous(), "s_idx": s_idx.to(torch.int32).contiguous(), "coef": coef, "form": 3,
+                "coef_inpaint": None, "K": int(t_idx.numel()), "eta": 1.0, "solver": "sde2m",
+                "lower_order_final": ms.lower_order_final}
     if ms is not None:
         coef = multistep_coefficients(g, path, ms.lower_order_final).to(torch.float32).contiguous()
         return {"t_idx": t_idx.to(torch.int32).contiguous(), "s_idx": s_idx.to(torch.int32).contiguous(), "coef": coef, "form": 2,

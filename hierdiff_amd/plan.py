@@ -26,7 +26,7 @@ def given(values: dict) -> dict:
 
 class Plan(NamedTuple):
     path: Optional[List[int]]                     # grid indices T .. 0 (t_start .. 0) of the path loop; None: the plain every-step loop
-    eta: object                                   # the update on the path: eta in [0, 1], or the `paths.Multistep` of solver "dpm2m"
+    eta: object                                   # the update on the path: eta in [0, 1], or the `paths.Multistep` of solver "dpm2m" / "sde2m"
     K: int                                        # transitions
     guidance: Optional[_guidance.Guidance]
     restraints: Optional[_rs.Resolved]
@@ -60,7 +60,7 @@ def _spacing(model, spacing):
 def full_path(model, steps=None, eta=None, spacing=None, timesteps=None, inpaint: bool = False, solver=None, lower_order_final=None,
               force_path: bool = False):
     """The path keywords of a chain from T -> None for the plain loop, or (path, eta); with solver "dpm2m" (path, `paths.Multistep`)
-    - always the path loop, eta = 0 whatever `sample_eta` says.  `force_path` (or the model's `_force_path_loop`): also the identity
+    or "sde2m" - always the path loop, eta = 0 (1 with "sde2m") whatever `sample_eta` says.  `force_path` (or the model's `_force_path_loop`): also the identity
     path with ancestral steps, which IS the plain loop, comes back as a path."""
     force_path = force_path or model._force_path_loop
     if steps is None and timesteps is None:
@@ -69,8 +69,8 @@ def full_path(model, steps=None, eta=None, spacing=None, timesteps=None, inpaint
                             model.sample_lower_order_final if lower_order_final is None else lower_order_final)
     if ms is not None:
         if inpaint:
-            raise ValueError("inpainting takes ancestral steps only (eta = 1), not solver 'dpm2m': the replacement method "
-                             "re-noises the known part with the posterior's own variance")
+            raise ValueError(f"inpainting takes ancestral steps only (eta = 1), not solver '{'sde2m' if ms.stochastic else 'dpm2m'}': "
+                             "the replacement method re-noises the known part with the posterior's own variance")
         return paths.build_path(model.T, steps, _spacing(model, spacing), timesteps), ms
     eta = paths.check_eta(model.sample_eta if eta is None else eta)
     spacing = _spacing(model, spacing)

@@ -174,12 +174,15 @@ def parse_args(argv=None):
     ap.add_argument("--eta", type=float, default=_ETA_DEFAULT,
                     help="1: ancestral steps (default); 0 <= eta < 1: DDIM-family update, 0 = noise-free (not with --known)")
     ap.add_argument("--spacing", choices=["uniform", "quadratic"], default="uniform", help="how --steps spreads over the grid")
-    ap.add_argument("--solver", choices=["ddim", "dpm2m"], default=None,
+    ap.add_argument("--solver", choices=["ddim", "dpm2m", "sde2m"], default=None,
                     help="dpm2m: second-order multistep sampling (DPM-Solver++ 2M) on the --steps path, deterministic (eta = 0) at no "
                          "extra network call; combines with --steps / --spacing, --guidance and --vary, not with --known / --grow or "
-                         "--eta other than 0.  Mechanism only: which K keeps sample quality is for you to validate")
+                         "--eta other than 0.  sde2m: its stochastic counterpart (SDE-DPM-Solver++ 2M): second order with the ancestral "
+                         "noise on the path (eta = 1), so it also combines with --restraints and --particles; not with --known / "
+                         "--grow, --score, --interpolate or --eta other than 1.  Mechanism only: which K keeps sample quality is for you "
+                         "to validate")
     ap.add_argument("--no-lower-order-final", dest="lower_order_final", action="store_false",
-                    help="with --solver dpm2m: keep the second-order correction on the last transition too")
+                    help="with --solver dpm2m / sde2m: keep the second-order correction on the last transition too")
     ap.add_argument("--score", default=None, metavar="FILE",
                     help="score the molecules of FILE (a sample_results.pkl or a bare list in the sampler's output format) instead of "
                          "sampling: the variational bound with every timestep evaluated, one value per molecule, written to --out.  "
@@ -303,8 +306,16 @@ def parse_args(argv=None):
         args.out = "scores.pkl" if args.score is not None else "sample_results.pkl"
     if args.steps is not None and args.steps < 1:
         ap.error("--steps must be >= 1")
-    if not args.lower_order_final and args.solver != "dpm2m":
-        ap.error("--no-lower-order-final needs --solver dpm2m")
+    if not args.lower_order_final and args.solver not in ("dpm2m", "sde2m"):
+        ap.error("--no-lower-order-final needs --solver dpm2m or sde2m")
+    if args.solver == "sde2m":
+        if args.known is not None or args.grow is not None:
+            ap.error("--solver sde2m does not combine with --known / --grow (inpainting takes ancestral steps)")
+        if args.score is not None or args.interpolate is not None:
+            ap.error("--solver sde2m does not combine with --score / --interpolate")
+        if args.eta is not _ETA_DEFAULT and args.eta != 1.0:
+            ap.error("--solver sde2m draws the ancestral noise: --eta must be 1 (or left out)")
+        args.eta = 1.0
     if args.solver == "dpm2m":
         if args.known is not None or args.grow is not None:
             ap.error("--solver dpm2m does not combine with --known / --grow (inpainting takes ancestral steps)")
@@ -356,8 +367,8 @@ def main(argv=None) -> int:
     if args.steps is not None and args.steps > model.T:
         raise SystemExit(f"--steps {args.steps} exceeds the model's {model.T} timesteps")
     model.sample_steps, model.sample_eta, model.sample_spacing = args.steps, args.eta, args.spacing
-    if args.solver == "dpm2m":
-        model.sample_solver, model.sample_lower_order_final = "dpm2m", args.lower_order_final
+    if args.solver in ("dpm2m", "sde2m"):
+        model.sample_solver, model.sample_lower_order_final = args.solver, args.lower_order_final
     if args.guidance is not None:
         model.guidance_scale, model.guidance_rescale = args.guidance, args.guidance_rescale
         if args.null_context is not None:

@@ -65,7 +65,7 @@ def wanted(model, particles=None, steer_scale=None) -> bool:
 def resolve(model, particles, steer_scale, steer_ess, steer_schedule, eta, K: int, restrained: bool, B: Optional[int] = None,
             what: str = "steering", injected: bool = False) -> Optional[Steer]:
     """Keywords (None: the model's `particles` / `steer_scale` / `steer_ess`) -> None for the unsteered code path, untouched, or a
-    `Steer`.  `eta`: the plan's update (a float, or the `paths.Multistep` of solver "dpm2m"); `K`: its transitions; `restrained`:
+    `Steer`.  `eta`: the plan's update (a float, or the `paths.Multistep` of solver "dpm2m" - refused - or "sde2m"); `K`: its transitions; `restrained`:
     the plan holds restraints.  Pure host checks."""
     if not wanted(model, particles, steer_scale):
         return None
@@ -91,6 +91,8 @@ def resolve(model, particles, steer_scale, steer_ess, steer_schedule, eta, K: in
             raise ValueError(f"{what}: steer_schedule holds one finite multiplier >= 0 per transition ({K})")
     if not restrained:
         raise ValueError(f"{what}: steering weighs the particles by their restraint energy: restraints= is required")
+    if getattr(eta, "stochastic", False):
+        eta = 1.0                                 # solver "sde2m": second order, and the ancestral noise on the path
     if not isinstance(eta, (int, float)) or isinstance(eta, bool):
         raise ValueError(f"{what}: steering needs a stochastic update, and solver 'dpm2m' draws nothing on the path (duplicated "
                          "particles would never diverge)")

@@ -338,6 +338,34 @@ int hd_set_path_multistep(hd_handle* h, int K, const int* t_idx, const int* s_id
 int hd_multistep_step(hd_handle* h, hd_topology* topo, const float* zt, const float* eps, const float* row5, const float* x_prev,
                       float* x_out, float* zs, void* stream);
 
+/* ---- Stochastic second-order multistep sampling (ABI 12, additive; no reference counterpart): SDE-DPM-Solver++(2M), the multistep
+ * correction on the ancestral update.  With h_k and r_k as above and xi a standard normal (x part mean-removed, masked):
+ *     published   z_s = (sigma_s / sigma_t) e^{-h} z_t + alpha_s (1 - e^{-2h}) x^_k + 1/2 alpha_s (1 - e^{-2h}) (x^_k - x^_{k-1}) / r_k
+ *                       + sigma_s sqrt(1 - e^{-2h}) xi,         x^_k = (z_t - sigma_t eps) / alpha_t
+ *     as run      x^_k = p z_t - q eps,        z_s = ((a z_t - b eps) + c xi) + c2 (x^_k - x^_{k-1}),
+ *     {a, b, c} = the eta = 1 linear row of hd_set_path (form 1): sigma_s sqrt(1 - e^{-2h}) is the ancestral sigma~,
+ *     p = 1 / alpha_t,  q = sigma_t / alpha_t,  c2 = alpha_s (-expm1(-2 h_k)) / (2 r_k)       (-2 h where the 2M rows have -h),
+ * eps and xi with their x parts mean-removed, z_s re-centred, rows >= mol_shape left alone, as in the plain step.  First order of
+ * this family is ancestral sampling: a row with c2 == 0 reads no history and gives the bits of the form-1 row {a, b, c, 0} with
+ * the same draws.  Which form is which: 0 ancestral rows, 1 linear rows (eta), 2 multistep rows5 (deterministic), 3 these rows6.
+ * hd_set_path_multistep_sde: hd_set_path with host rows6 = K rows {a, b, c, c2, p, q} (form 3), validated like
+ * hd_set_path_multistep; c2 of row 0 must be 0 (HD_E_INVALID).  hd_sample_path and hd_sample_path_guided (fixed_mask == NULL) then run
+ * the path with and without use_graph; the draws (T - s of the arrival step) and injected normals (one pair per transition) are
+ * those of form 1; the history buffer, its bookkeeping and the HD_E_STATE continuity rule are those of form 2.
+ * hd_sample_path_inpaint and guided calls with a fixed_mask are HD_E_INVALID (a jump back invalidates the history).
+ * Steering (hd_steer_attach) is allowed - the update draws - and the history follows its lineage: rows that receive another
+ * row's z_t and eps^ receive its x^_{k-1} too, inside the captured transition. */
+int hd_set_path_multistep_sde(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* rows6);
+/* The single update: x_out[B,N,D] = x^_k (masked entries 0) and zs[B,N,D] = z_s from zt, eps [B,N,D] (device) and the HOST row
+ * row6 = {a, b, c, c2, p, q}.  x_prev as in hd_multistep_step (NULL allowed when c2 == 0).  Noise: raw_x [rows][mol][3] and raw_h
+ * [rows][mol][F] (device; noise_rows = 1 shares one row), or both NULL for the counter-based generator at (seed, sample_id_base + b
+ * - or sample_id_base for every row when share_rows != 0 -, draw).  mol_shape: rows >= mol_shape of a molecule are left alone (< 0
+ * or > N: N).  zs may be zt and x_out may be x_prev; any other overlap is HD_E_INVALID, as is mol * D floats beyond one workgroup's
+ * LDS (64 KiB).  Stream-ordered. */
+int hd_multistep_sde_step(hd_handle* h, hd_topology* topo, const float* zt, const float* eps, const float* row6, const float* x_prev,
+                          float* x_out, const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed,
+                          uint64_t sample_id_base, uint32_t draw, int share_rows, int mol_shape, float* zs, void* stream);
+
 /* ---- Recording a trajectory (ABI 12, additive; the reference's sample_chain, en_diffusion.py:669-710): the path loops write
  * intermediate states into a caller-owned sink chain[frames][B][N][D] (device, fp32) while they run - one more element-wise launch
  * per transition (k_chain_frame), inside the captured transition when use_graph is set.  Frames are in data units, `unnormalize`
@@ -422,7 +450,8 @@ int hd_restraint_energy(hd_handle* h, hd_topology* topo, const float* x, double*
  *     anc[j] != j receive z_t, eps^, U_prev and the lineage root of row anc[j]; the group's logw is reset to 0.  Otherwise, and in a
  *     group whose weights are all 0 (counted), nothing moves.
  * The posterior step follows with every row's own noise, so duplicates diverge: steering needs noise_rows == B and a stochastic
- * update (multistep rows are HD_E_INVALID).  u = hd_philox_uniform_host(seed, sample_id_base + g P, the transition's draw T - s,
+ * update (the deterministic multistep rows of form 2 are HD_E_INVALID; the stochastic ones of form 3 are allowed, and their history
+ * x^_{k-1} moves with z_t and eps^).  u = hd_philox_uniform_host(seed, sample_id_base + g P, the transition's draw T - s,
  * 0xfffffffe).  Four more launches per transition (k_steer_weigh, k_steer_resample, two of k_steer_gather), plain kernel nodes of
  * a captured transition.  A group's result depends on the seed, the ids of its rows, P, its masks and tables, the weights, the
  * schedule and the path only - not on other groups, graph replay or how the chain is cut into calls.
