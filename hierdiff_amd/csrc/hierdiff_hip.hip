@@ -65,13 +65,20 @@ struct ProfRec { int fam; hipEvent_t a, b; };
 // A path on the schedule's grid: K transitions t_idx[k] -> s_idx[k], the rows they read, and the generations that tie captured
 // graphs to the tables.  set_path_tables is the one writer (the every-step inpainting rows come from hd_set_inpaint_schedule).
 struct PathTables {
-    int K = 0, form = 0;             // form 0: ancestral rows, 1: linear rows {a, b, c, 0}, 2: multistep rows {a, b, c2, p, q} (5 floats)
+    int K = 0, form = 0;             // the row form of k_post_step: rows of step_row_width(form) floats
     bool up = false;                 // the path ascends (hd_set_path_up: t_idx[k] < s_idx[k], linear rows with c == 0)
     std::vector<int> t_h, s_h;
     std::vector<float> c2_h;         // forms 2 and 3: c2 of every row (which transitions read the history)
     int *d_t = nullptr, *d_s = nullptr;
-    float *d_coef = nullptr, *d_coef_ip = nullptr;   // [K][4] each; d_coef_ip null when no inpainting rows were given
+    float *d_coef = nullptr, *d_coef_ip = nullptr;   // [K][width of the form], [K][4]; d_coef_ip null when no inpainting rows were given
     unsigned long long sched_gen = 0, gen = 0;       // sched_gen the tables were set for (0: not set); bumped by every rewrite
+};
+
+// Per-transition rows that go with the caller's path (set_row_table is the one writer).
+struct RowTable {
+    float* d = nullptr;              // [K][width]
+    int K = 0;
+    unsigned long long path_gen = 0, gen = 0;   // path.gen the rows were set for (0: not set); bumped when the table moves
 };
 
 struct hd_handle {
@@ -123,14 +130,9 @@ struct hd_handle {
     float* d_chain_as;          // [K][2]; null when hd_set_chain got none
     unsigned long long chain_path_gen, chain_gen;   // path.gen the tables were set for (0: not set); bumped by every hd_set_chain
     float** d_chain_dst;        // graph replay: the sink a recording transition writes (set by k_path_state)
-    // restraints (hd_set_restraint): the rows {alpha_t, sigma_t, lambda_k, clip_k} of every transition of the current path
-    float* d_rs_rows;           // [K][4]
-    int rs_K;
-    unsigned long long rs_path_gen, rs_gen;         // path.gen the rows were set for (0: not set); bumped when the table moves
-    // steering (hd_set_steer): the rows {alpha_t, sigma_t, beta_k} of every transition of the current path
-    float* d_st_rows;           // [K][3]
-    int st_K;
-    unsigned long long st_path_gen, st_gen;         // as rs_path_gen / rs_gen
+    // restraints (hd_set_restraint): the rows {alpha_t, sigma_t, lambda_k, clip_k} of every transition of the current path; steering
+    // (hd_set_steer): the rows {alpha_t, sigma_t, beta_k}
+    RowTable rs_rows, st_rows;  // [K][4], [K][3]
     // scoring (hd_set_nll_terms / hd_nll_terms / hd_nll_finish): K terms t_idx[k] of the bound, rows {alpha_t, sigma_t, w_t, 0}
     int nll_K;
     std::vector<int> nll_t_h;
@@ -397,8 +399,6 @@ extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
     h->ip_sched_gen = 0; h->ip_gen = 0; h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
     h->chain_frames = 0; h->d_chain_frame = nullptr; h->d_chain_as = nullptr; h->chain_path_gen = 0; h->chain_gen = 0;
     h->d_chain_dst = nullptr;
-    h->d_rs_rows = nullptr; h->rs_K = 0; h->rs_path_gen = 0; h->rs_gen = 0;
-    h->d_st_rows = nullptr; h->st_K = 0; h->st_path_gen = 0; h->st_gen = 0;
     h->nll_K = 0; h->d_nll_t = nullptr; h->d_nll_coef = nullptr; h->nll_sched_gen = 0; h->nll_gen = 0;
     h->d_nanflag = nullptr; h->d_nan_events = nullptr; h->d_step = nullptr; h->d_draw = nullptr; h->d_tcur = nullptr;
     h->d_base = nullptr;
@@ -454,8 +454,8 @@ extern "C" int hd_destroy(hd_handle* h) {
         hipFree(pt->d_t); hipFree(pt->d_s); hipFree(pt->d_coef); hipFree(pt->d_coef_ip);
     }
     hipFree(h->d_chain_frame); hipFree(h->d_chain_as); hipFree(h->d_chain_dst);
-    hipFree(h->d_rs_rows);
-    hipFree(h->d_st_rows);
+    hipFree(h->rs_rows.d);
+    hipFree(h->st_rows.d);
     hipFree(h->d_nll_t); hipFree(h->d_nll_coef);
 #ifdef HD_DEBUG_KERNELS
     hipFree(h->d_trace);

@@ -39,16 +39,25 @@ struct LoopIO {
     Draw draw_of(int i, uint32_t stride) const { return captured() ? Draw{0u, draw_w + i} : Draw{stride * (uint32_t)i + draw, nullptr}; }
 };
 
-// One posterior step zt -> io.z (the loops step in place).  `ns` carries the host draw and sample base, `draw_w` the draw's device word.
-static int step_impl(hd_handle* h, hd_topology* t, const LoopIO& io, const float* zt, const float* eps, const float* coef, int coef_rows,
-                     const NoiseSrc& ns, const uint32_t* draw_w, int mol, int out_stride, int form, int raw_step0) {
+// One posterior step zt -> io.z (the loops step in place) in row form `form` (k_post_step).  `coef`: device rows, read at *io.step
+// by a captured loop, else row 0 or - coef_rows == B - the molecule's; null: the host `row` by value.  `ns` carries the host draw and
+// sample base, `draw_w` the draw's device word (form 2 draws nothing); forms 2 and 3 read the history x_prev and write x_out.
+static int step_launch(hd_handle* h, hd_topology* t, const LoopIO& io, int form, const float* zt, const float* eps, const float* coef,
+                       int coef_rows, const float* row, const float* x_prev, float* x_out, const NoiseSrc& ns, const uint32_t* draw_w,
+                       int mol, int out_stride, int raw_step0) {
     ProfScope ps(h, io.s, 2);
     StepArgs a;
-    a.zt = zt; a.eps = eps; a.coef = coef; a.nm = t->nm_bytes; a.zs = io.z; a.noise = ns; a.draw_ptr = draw_w;
-    a.step_ptr = io.step; a.base_ptr = io.base_w; a.coef_rows = coef_rows; a.B = t->B; a.N = t->N; a.D = h->D; a.F = h->F;
-    a.mol = mol; a.out_stride = out_stride; a.raw_step0 = raw_step0;
-    if (form == 0) hipLaunchKernelGGL(k_post_step<0>, dim3(t->B), dim3(256), (size_t)a.mol * a.D * sizeof(float), io.s, a);
-    else hipLaunchKernelGGL(k_post_step<1>, dim3(t->B), dim3(256), (size_t)a.mol * a.D * sizeof(float), io.s, a);
+    a.zt = zt; a.eps = eps; a.coef = coef; a.nm = t->nm_bytes; a.x_prev = x_prev; a.x_out = x_out; a.zs = io.z; a.noise = ns;
+    a.draw_ptr = draw_w; a.step_ptr = io.step; a.base_ptr = io.base_w; a.raw_step0 = raw_step0;
+    for (int k = 0; k < 6; ++k) a.row[k] = (row && k < step_row_width(form)) ? row[k] : 0.f;
+    a.coef_rows = coef_rows; a.B = t->B; a.N = t->N; a.D = h->D; a.F = h->F; a.mol = mol; a.out_stride = out_stride;
+    const size_t lds = (size_t)mol * a.D * sizeof(float);
+    switch (form) {
+    case 0: hipLaunchKernelGGL(k_post_step<0>, dim3(t->B), dim3(256), lds, io.s, a); break;
+    case 1: hipLaunchKernelGGL(k_post_step<1>, dim3(t->B), dim3(256), lds, io.s, a); break;
+    case 2: hipLaunchKernelGGL(k_post_step<2>, dim3(t->B), dim3(256), lds, io.s, a); break;
+    default: hipLaunchKernelGGL(k_post_step<3>, dim3(t->B), dim3(256), lds, io.s, a); break;
+    }
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
@@ -67,20 +76,8 @@ extern "C" int hd_posterior_step(hd_handle* h, hd_topology* topo, const float* z
     topo_use(topo, (hipStream_t)stream);
     LoopIO io{};
     io.z = zs; io.s = (hipStream_t)stream;
-    return step_impl(h, topo, io, zt, eps, coef, coef_rows, make_noise(raw_x, raw_h, noise_rows, 0, 0, 0, 0), nullptr, mol, mol, 0, 0);
-}
-
-// the multistep form of the step zt -> io.z: `coef` device rows [K][5] read at *io.step (k_solver.hpp), or the host row by value
-static int solver_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* zt, const float* eps, const float* coef,
-                         const float* row5, const float* x_prev, float* x_out, int mol) {
-    ProfScope ps(h, io.s, 2);
-    SolverArgs a;
-    a.zt = zt; a.eps = eps; a.coef = coef; a.nm = t->nm_bytes; a.x_prev = x_prev; a.x_out = x_out; a.zs = io.z; a.step_ptr = io.step;
-    for (int k = 0; k < 5; ++k) a.row[k] = row5 ? row5[k] : 0.f;
-    a.B = t->B; a.N = t->N; a.D = h->D; a.mol = mol;
-    hipLaunchKernelGGL(k_multistep_step, dim3(t->B), dim3(256), (size_t)mol * a.D * sizeof(float), io.s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
+    return step_launch(h, topo, io, 0, zt, eps, coef, coef_rows, nullptr, nullptr, nullptr, make_noise(raw_x, raw_h, noise_rows, 0, 0, 0, 0),
+                       nullptr, mol, mol, 0);
 }
 
 extern "C" int hd_multistep_step(hd_handle* h, hd_topology* topo, const float* zt, const float* eps, const float* row5,
@@ -95,23 +92,8 @@ extern "C" int hd_multistep_step(hd_handle* h, hd_topology* topo, const float* z
     topo_use(topo, (hipStream_t)stream);
     LoopIO io{};
     io.z = zs; io.s = (hipStream_t)stream;
-    return solver_launch(h, topo, io, zt, eps, nullptr, row5, x_prev, x_out, topo->N);
-}
-
-// the stochastic multistep form (k_multistep_sde_step): `coef` device rows [K][6] read at *io.step, or the host row by value; the
-// noise as in step_impl
-static int sde_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* zt, const float* eps, const float* coef,
-                      const float* row6, const float* x_prev, float* x_out, const NoiseSrc& ns, const uint32_t* draw_w, int mol,
-                      int raw_step0) {
-    ProfScope ps(h, io.s, 2);
-    SdeSolverArgs a;
-    a.zt = zt; a.eps = eps; a.coef = coef; a.nm = t->nm_bytes; a.x_prev = x_prev; a.x_out = x_out; a.zs = io.z; a.noise = ns;
-    a.draw_ptr = draw_w; a.step_ptr = io.step; a.base_ptr = io.base_w; a.raw_step0 = raw_step0;
-    for (int k = 0; k < 6; ++k) a.row[k] = row6 ? row6[k] : 0.f;
-    a.B = t->B; a.N = t->N; a.D = h->D; a.F = h->F; a.mol = mol;
-    hipLaunchKernelGGL(k_multistep_sde_step, dim3(t->B), dim3(256), (size_t)mol * a.D * sizeof(float), io.s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
+    return step_launch(h, topo, io, 2, zt, eps, nullptr, 1, row5, x_prev, x_out, make_noise(nullptr, nullptr, 1, 0, 0, 0, 0), nullptr, topo->N,
+                       topo->N, 0);
 }
 
 extern "C" int hd_multistep_sde_step(hd_handle* h, hd_topology* topo, const float* zt, const float* eps, const float* row6,
@@ -131,8 +113,9 @@ extern "C" int hd_multistep_sde_step(hd_handle* h, hd_topology* topo, const floa
     topo_use(topo, (hipStream_t)stream);
     LoopIO io{};
     io.z = zs; io.s = (hipStream_t)stream;
-    return sde_launch(h, topo, io, zt, eps, nullptr, row6, x_prev, x_out,
-                      make_noise(raw_x, raw_h, noise_rows, seed, sample_id_base, draw, (noise_rows == 1 || share_rows) ? 1 : 0), nullptr, mol, 0);
+    return step_launch(h, topo, io, 3, zt, eps, nullptr, 1, row6, x_prev, x_out,
+                       make_noise(raw_x, raw_h, noise_rows, seed, sample_id_base, draw, (noise_rows == 1 || share_rows) ? 1 : 0), nullptr, mol,
+                       topo->N, 0);
 }
 
 extern "C" int hd_final_decode(hd_handle* h, hd_topology* topo, const float* z0, const float* eps, const float* coef3,
@@ -175,9 +158,10 @@ extern "C" int hd_noise(hd_handle* h, hd_topology* topo, const float* raw_x, con
 }
 
 // The one writer of path tables - the caller's or the handle's every-step ones: K validated transitions t_idx[k] -> s_idx[k],
-// their rows of `row_width` floats and, for ancestral paths that inpaint, the inpainting rows.
-static int set_path_tables(hd_handle* h, PathTables& pt, int K, const int* t_idx, const int* s_idx, const float* rows, int row_width,
-                           const float* rows_ip, int form, bool up) {
+// their rows in the form's width and, for ancestral paths that inpaint, the inpainting rows.
+static int set_path_tables(hd_handle* h, PathTables& pt, int K, const int* t_idx, const int* s_idx, const float* rows, const float* rows_ip,
+                           int form, bool up) {
+    const size_t row_width = (size_t)step_row_width(form);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
     hipFree(pt.d_t); hipFree(pt.d_s); hipFree(pt.d_coef); hipFree(pt.d_coef_ip);
@@ -187,11 +171,11 @@ static int set_path_tables(hd_handle* h, PathTables& pt, int K, const int* t_idx
     pt.s_h.assign(s_idx, s_idx + K);
     if (form == 2 || form == 3) {
         pt.c2_h.resize((size_t)K);
-        for (int k = 0; k < K; ++k) pt.c2_h[(size_t)k] = rows[(size_t)row_width * k + (form == 3 ? 3 : 2)];
+        for (int k = 0; k < K; ++k) pt.c2_h[(size_t)k] = rows[row_width * k + step_row_c2(form)];
     }
     HD_TRY(dev_upload(&pt.d_t, pt.t_h));
     HD_TRY(dev_upload(&pt.d_s, pt.s_h));
-    HD_TRY(dev_upload(&pt.d_coef, std::vector<float>(rows, rows + (size_t)row_width * K)));
+    HD_TRY(dev_upload(&pt.d_coef, std::vector<float>(rows, rows + row_width * K)));
     if (rows_ip) HD_TRY(dev_upload(&pt.d_coef_ip, std::vector<float>(rows_ip, rows_ip + (size_t)4 * K)));
     pt.K = K; pt.form = form; pt.up = up;
     pt.sched_gen = h->sched_gen;
@@ -213,7 +197,7 @@ extern "C" int hd_set_schedule(hd_handle* h, int T, const float* tau, const floa
     // the every-step tables: the identity path T -> T - 1 -> ... -> 0 with the caller's rows (row s of coef4 is the step to s)
     std::vector<int> t_idx((size_t)T), s_idx((size_t)T);
     for (int k = 0; k < T; ++k) { t_idx[(size_t)k] = T - k; s_idx[(size_t)k] = T - 1 - k; }
-    HD_TRY(set_path_tables(h, h->every, T, t_idx.data(), s_idx.data(), rows_reversed(coef4, T).data(), 4, nullptr, 0, false));
+    HD_TRY(set_path_tables(h, h->every, T, t_idx.data(), s_idx.data(), rows_reversed(coef4, T).data(), nullptr, 0, false));
     hipFree(h->d_tau);                         // behind set_path_tables' device synchronisation
     h->d_tau = nullptr;
     h->tau_h.assign(tau, tau + T + 1);
@@ -397,19 +381,25 @@ static int inpaint_round(hd_handle* h, hd_topology* t, const LoopIO& io, int j, 
 
 // ----------------------------------------------------------------------------- few-step sampling: the loop on a path
 
+// What every setter of a descending path checks, in this order; `why` closes the range text of the multistep setters.
+static int path_down_check(const char* who, const hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* rows, const char* why) {
+    const std::string w(who);
+    if (!h || !t_idx || !s_idx || !rows || K < 1) return fail(HD_E_INVALID, w + ": bad argument");
+    if (h->T < 1) return fail(HD_E_STATE, w + ": schedule not set (hd_set_schedule)");
+    if (K > h->T) return fail(HD_E_INVALID, w + ": more transitions than the schedule has steps");
+    for (int k = 0; k < K; ++k) {
+        if (t_idx[k] > h->T || s_idx[k] < 0 || s_idx[k] >= t_idx[k]) return fail(HD_E_INVALID, w + ": need 0 <= s_idx[k] < t_idx[k] <= T" + why);
+        if (k > 0 && t_idx[k] != s_idx[k - 1]) return fail(HD_E_INVALID, w + ": transition k must start where k - 1 arrived");
+    }
+    return HD_OK;
+}
+
 extern "C" int hd_set_path(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* coef4, int form,
                            const float* coef4_inpaint) {
     if (form != 0 && form != 1) return fail(HD_E_INVALID, "hd_set_path: form must be 0 (ancestral rows) or 1 (linear rows)");
     if (form == 1 && coef4_inpaint) return fail(HD_E_INVALID, "hd_set_path: inpainting rows go with ancestral rows only (form 0)");
-    if (!h || !t_idx || !s_idx || !coef4 || K < 1) return fail(HD_E_INVALID, "hd_set_path: bad argument");
-    if (h->T < 1) return fail(HD_E_STATE, "hd_set_path: schedule not set (hd_set_schedule)");
-    if (K > h->T) return fail(HD_E_INVALID, "hd_set_path: more transitions than the schedule has steps");
-    for (int k = 0; k < K; ++k) {
-        if (t_idx[k] > h->T || s_idx[k] < 0 || s_idx[k] >= t_idx[k])
-            return fail(HD_E_INVALID, "hd_set_path: need 0 <= s_idx[k] < t_idx[k] <= T");
-        if (k > 0 && t_idx[k] != s_idx[k - 1]) return fail(HD_E_INVALID, "hd_set_path: transition k must start where k - 1 arrived");
-    }
-    return set_path_tables(h, h->path, K, t_idx, s_idx, coef4, 4, coef4_inpaint, form, false);
+    HD_TRY(path_down_check("hd_set_path", h, K, t_idx, s_idx, coef4, ""));
+    return set_path_tables(h, h->path, K, t_idx, s_idx, coef4, coef4_inpaint, form, false);
 }
 
 // An ascending path into the same tables: transition k leaves from_idx[k] (path_t: network time, as for descending paths) and
@@ -426,37 +416,22 @@ extern "C" int hd_set_path_up(hd_handle* h, int K, const int* from_idx, const in
     if (h->T < 1) return fail(HD_E_STATE, "hd_set_path_up: schedule not set (hd_set_schedule)");
     if (K > h->T) return fail(HD_E_INVALID, "hd_set_path_up: more transitions than the schedule has steps");
     if (to_idx[K - 1] > h->T) return fail(HD_E_INVALID, "hd_set_path_up: need 0 <= from_idx[k] < to_idx[k] <= T");
-    return set_path_tables(h, h->path, K, from_idx, to_idx, coef4, 4, nullptr, 1, true);
+    return set_path_tables(h, h->path, K, from_idx, to_idx, coef4, nullptr, 1, true);
 }
 
-// A descending path with multistep rows {a, b, c2, p, q} (form 2, k_solver.hpp) into the same tables.
+// Descending paths with multistep rows into the same tables: {a, b, c2, p, q} (form 2), and the stochastic {a, b, c, c2, p, q} (form 3).
+static int set_path_multistep(const char* who, hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* rows, int form) {
+    HD_TRY(path_down_check(who, h, K, t_idx, s_idx, rows, " (a multistep path descends)"));
+    if (rows[step_row_c2(form)] != 0.f) return fail(HD_E_INVALID, std::string(who) + ": c2 of row 0 must be 0 (the first transition has no history)");
+    return set_path_tables(h, h->path, K, t_idx, s_idx, rows, nullptr, form, false);
+}
+
 extern "C" int hd_set_path_multistep(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* rows5) {
-    if (!h || !t_idx || !s_idx || !rows5 || K < 1) return fail(HD_E_INVALID, "hd_set_path_multistep: bad argument");
-    if (h->T < 1) return fail(HD_E_STATE, "hd_set_path_multistep: schedule not set (hd_set_schedule)");
-    if (K > h->T) return fail(HD_E_INVALID, "hd_set_path_multistep: more transitions than the schedule has steps");
-    for (int k = 0; k < K; ++k) {
-        if (t_idx[k] > h->T || s_idx[k] < 0 || s_idx[k] >= t_idx[k])
-            return fail(HD_E_INVALID, "hd_set_path_multistep: need 0 <= s_idx[k] < t_idx[k] <= T (a multistep path descends)");
-        if (k > 0 && t_idx[k] != s_idx[k - 1])
-            return fail(HD_E_INVALID, "hd_set_path_multistep: transition k must start where k - 1 arrived");
-    }
-    if (rows5[2] != 0.f) return fail(HD_E_INVALID, "hd_set_path_multistep: c2 of row 0 must be 0 (the first transition has no history)");
-    return set_path_tables(h, h->path, K, t_idx, s_idx, rows5, 5, nullptr, 2, false);
+    return set_path_multistep("hd_set_path_multistep", h, K, t_idx, s_idx, rows5, 2);
 }
 
-// A descending path with stochastic multistep rows {a, b, c, c2, p, q} (form 3, k_solver.hpp) into the same tables.
 extern "C" int hd_set_path_multistep_sde(hd_handle* h, int K, const int* t_idx, const int* s_idx, const float* rows6) {
-    if (!h || !t_idx || !s_idx || !rows6 || K < 1) return fail(HD_E_INVALID, "hd_set_path_multistep_sde: bad argument");
-    if (h->T < 1) return fail(HD_E_STATE, "hd_set_path_multistep_sde: schedule not set (hd_set_schedule)");
-    if (K > h->T) return fail(HD_E_INVALID, "hd_set_path_multistep_sde: more transitions than the schedule has steps");
-    for (int k = 0; k < K; ++k) {
-        if (t_idx[k] > h->T || s_idx[k] < 0 || s_idx[k] >= t_idx[k])
-            return fail(HD_E_INVALID, "hd_set_path_multistep_sde: need 0 <= s_idx[k] < t_idx[k] <= T (a multistep path descends)");
-        if (k > 0 && t_idx[k] != s_idx[k - 1])
-            return fail(HD_E_INVALID, "hd_set_path_multistep_sde: transition k must start where k - 1 arrived");
-    }
-    if (rows6[3] != 0.f) return fail(HD_E_INVALID, "hd_set_path_multistep_sde: c2 of row 0 must be 0 (the first transition has no history)");
-    return set_path_tables(h, h->path, K, t_idx, s_idx, rows6, 6, nullptr, 3, false);
+    return set_path_multistep("hd_set_path_multistep_sde", h, K, t_idx, s_idx, rows6, 3);
 }
 
 extern "C" long long hd_path_graph_builds(const hd_topology* topo) { return topo ? topo->g_path.builds : -1; }
@@ -499,28 +474,41 @@ extern "C" long long hd_chain_graph_builds(const hd_topology* topo) { return top
 
 // ----------------------------------------------------------------------------- restraints on the data prediction of a path loop
 
-extern "C" int hd_set_restraint(hd_handle* h, int K, const float* rows4) {
-    if (!h || !rows4 || K < 1) return fail(HD_E_INVALID, "hd_set_restraint: bad argument");
-    if (h->path.K < 1 || h->path.sched_gen != h->sched_gen)
-        return fail(HD_E_STATE, "hd_set_restraint: path not set for the current schedule (hd_set_path)");
-    if (K != h->path.K) return fail(HD_E_INVALID, "hd_set_restraint: K differs from the path's (hd_set_path)");
-    for (int k = 0; k < K; ++k) {
-        const float *r = rows4 + (size_t)4 * k;
-        if (!(r[0] > 0.f) || !(r[1] >= 0.f) || !(r[2] - r[2] == 0.f) || !(r[3] > 0.f))
-            return fail(HD_E_INVALID, "hd_set_restraint: need alpha_t > 0, sigma_t >= 0, a finite lambda_k and clip_k > 0 (inf: no clip)");
-    }
+static bool restraint_row_ok(const float* r) { return r[0] > 0.f && r[1] >= 0.f && r[2] - r[2] == 0.f && r[3] > 0.f; }
+static bool steer_row_ok(const float* r) { return r[0] > 0.f && r[1] >= 0.f && r[2] >= 0.f && r[2] - r[2] == 0.f; }
+
+// What the setters of per-transition rows (hd_set_restraint, hd_set_steer) check, in this order; `need` is what a row must satisfy.
+static int row_table_check(const char* who, const hd_handle* h, int K, const float* rows, int width, bool (*row_ok)(const float*),
+                           const char* need) {
+    const std::string w(who);
+    if (!h || !rows || K < 1) return fail(HD_E_INVALID, w + ": bad argument");
+    if (h->path.K < 1 || h->path.sched_gen != h->sched_gen) return fail(HD_E_STATE, w + ": path not set for the current schedule (hd_set_path)");
+    if (K != h->path.K) return fail(HD_E_INVALID, w + ": K differs from the path's (hd_set_path)");
+    for (int k = 0; k < K; ++k)
+        if (!row_ok(rows + (size_t)width * k)) return fail(HD_E_INVALID, w + need);
+    return HD_OK;
+}
+
+// K checked rows of `width` floats into a table of the handle, tied to the current path.
+static int set_row_table(hd_handle* h, RowTable& tb, int K, const float* rows, int width) {
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old rows
-    if (!h->d_rs_rows || h->rs_K != K) {                // same K: the table stays where captured transitions expect it
-        hipFree(h->d_rs_rows);
-        h->d_rs_rows = nullptr; h->rs_path_gen = 0; h->rs_K = 0;
-        HD_TRY(dev_alloc(&h->d_rs_rows, (size_t)4 * K));
-        h->rs_K = K;
-        h->rs_gen++;
+    if (!tb.d || tb.K != K) {                           // same K: the table stays where captured transitions expect it
+        hipFree(tb.d);
+        tb.d = nullptr; tb.path_gen = 0; tb.K = 0;
+        HD_TRY(dev_alloc(&tb.d, (size_t)width * K));
+        tb.K = K;
+        tb.gen++;
     }
-    HIP_TRY(hipMemcpy(h->d_rs_rows, rows4, (size_t)4 * K * sizeof(float), hipMemcpyHostToDevice));
-    h->rs_path_gen = h->path.gen;
+    HIP_TRY(hipMemcpy(tb.d, rows, (size_t)width * K * sizeof(float), hipMemcpyHostToDevice));
+    tb.path_gen = h->path.gen;
     return HD_OK;
+}
+
+extern "C" int hd_set_restraint(hd_handle* h, int K, const float* rows4) {
+    HD_TRY(row_table_check("hd_set_restraint", h, K, rows4, 4, restraint_row_ok,
+                           ": need alpha_t > 0, sigma_t >= 0, a finite lambda_k and clip_k > 0 (inf: no clip)"));
+    return set_row_table(h, h->rs_rows, K, rows4, 4);
 }
 
 // one library-owned table of the topology: grown when `count` exceeds its capacity (then *moved is set), filled from `src`
@@ -604,7 +592,7 @@ extern "C" int hd_restrain_eps(hd_handle* h, hd_topology* topo, const float* z, 
     if (!h || !topo) return fail(HD_E_INVALID, "hd_restrain_eps: null handle/topology");
     if (!z || !eps || !row4 || !out) return fail(HD_E_INVALID, "hd_restrain_eps: null tensor / row");
     if (!topo->rs_on) return fail(HD_E_STATE, "hd_restrain_eps: no restraints attached to the topology (hd_restraint_attach)");
-    if (!(row4[0] > 0.f) || !(row4[1] >= 0.f) || !(row4[2] - row4[2] == 0.f) || !(row4[3] > 0.f))
+    if (!restraint_row_ok(row4))
         return fail(HD_E_INVALID, "hd_restrain_eps: need alpha_t > 0, sigma_t >= 0, a finite lambda and clip > 0 (inf: no clip)");
     const size_t per = (size_t)topo->B * topo->N * h->D;
     if (out < z + per && z < out + per) return fail(HD_E_INVALID, "hd_restrain_eps: out may not overlap z");
@@ -634,28 +622,9 @@ extern "C" int hd_restraint_energy(hd_handle* h, hd_topology* topo, const float*
 
 // ----------------------------------------------------------------------------- steering: particle resampling on the restraint energy
 
-static bool steer_row_ok(const float* r) { return r[0] > 0.f && r[1] >= 0.f && r[2] >= 0.f && r[2] - r[2] == 0.f; }
-
 extern "C" int hd_set_steer(hd_handle* h, int K, const float* rows3) {
-    if (!h || !rows3 || K < 1) return fail(HD_E_INVALID, "hd_set_steer: bad argument");
-    if (h->path.K < 1 || h->path.sched_gen != h->sched_gen)
-        return fail(HD_E_STATE, "hd_set_steer: path not set for the current schedule (hd_set_path)");
-    if (K != h->path.K) return fail(HD_E_INVALID, "hd_set_steer: K differs from the path's (hd_set_path)");
-    for (int k = 0; k < K; ++k)
-        if (!steer_row_ok(rows3 + (size_t)3 * k))
-            return fail(HD_E_INVALID, "hd_set_steer: need alpha_t > 0, sigma_t >= 0 and a finite beta_k >= 0");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old rows
-    if (!h->d_st_rows || h->st_K != K) {                // same K: the table stays where captured transitions expect it
-        hipFree(h->d_st_rows);
-        h->d_st_rows = nullptr; h->st_path_gen = 0; h->st_K = 0;
-        HD_TRY(dev_alloc(&h->d_st_rows, (size_t)3 * K));
-        h->st_K = K;
-        h->st_gen++;
-    }
-    HIP_TRY(hipMemcpy(h->d_st_rows, rows3, (size_t)3 * K * sizeof(float), hipMemcpyHostToDevice));
-    h->st_path_gen = h->path.gen;
-    return HD_OK;
+    HD_TRY(row_table_check("hd_set_steer", h, K, rows3, 3, steer_row_ok, ": need alpha_t > 0, sigma_t >= 0 and a finite beta_k >= 0"));
+    return set_row_table(h, h->st_rows, K, rows3, 3);
 }
 
 static SteerState steer_state(const hd_topology* t) {
@@ -847,7 +816,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     if (rsn) {
         if (R) return fail(HD_E_INVALID, "path loop: restraints are attached to the topology, and inpainting takes none (it re-centres "
                                          "on the known fragments: hd_restraint_detach)");
-        if (!h->d_rs_rows || h->rs_path_gen != pt.gen)
+        if (!h->rs_rows.d || h->rs_rows.path_gen != pt.gen)
             return fail(HD_E_STATE, "path loop: restraints are attached but their rows are not set for the current path (hd_set_restraint)");
         if (mol != N) return fail(HD_E_INVALID, "path loop: restraints act on whole molecules only (mol_shape < N)");
     }
@@ -855,7 +824,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     if (stn) {
         if (!rsn) return fail(HD_E_STATE, "path loop: steering is attached to the topology but no restraints are (hd_restraint_attach): "
                                           "it weighs the particles by their restraint energy");
-        if (!h->d_st_rows || h->st_path_gen != pt.gen)
+        if (!h->st_rows.d || h->st_rows.path_gen != pt.gen)
             return fail(HD_E_STATE, "path loop: steering is attached but its rows are not set for the current path (hd_set_steer)");
         if (form == 2) return fail(HD_E_INVALID, "path loop: steering needs a stochastic update, and multistep rows draw nothing "
                                                  "(duplicated particles would never diverge: hd_steer_detach)");
@@ -869,28 +838,17 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
                 HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx_u, ms, topo->eps_u, io.s));
                 HD_TRY(guide_launch(h, topo, topo->eps, topo->eps_u, io.w, gd->w_rows, gd->phi, topo->eps, io.s));
             }
-            if (rsn) HD_TRY(restrain_launch(h, topo, io, io.z, topo->eps, topo->eps, h->d_rs_rows, nullptr));
-            if (stn) HD_TRY(steer_launch(h, topo, io, io.z, topo->eps, h->d_st_rows, nullptr, io.draw_of(0, stride), c.seed,
+            if (rsn) HD_TRY(restrain_launch(h, topo, io, io.z, topo->eps, topo->eps, h->rs_rows.d, nullptr));
+            if (stn) HD_TRY(steer_launch(h, topo, io, io.z, topo->eps, h->st_rows.d, nullptr, io.draw_of(0, stride), c.seed,
                                          form == 3 ? topo->ms_hist : nullptr));
-            const bool rec_z = rec && j == rounds - 1 && topo->chain_what == 0;
             if (rec && j == rounds - 1 && topo->chain_what == 1) HD_TRY(chain_launch(h, topo, io, topo->eps));
-            if (form == 2) {
-                HD_TRY(solver_launch(h, topo, io, io.z, topo->eps, pt.d_coef + (size_t)io.row * 5, nullptr, topo->ms_hist, topo->ms_hist, mol));
-                if (rec_z) HD_TRY(chain_launch(h, topo, io, nullptr));
-                continue;
-            }
             const LoopIO::Draw d = io.draw_of(3 * j, stride);
-            NoiseSrc ns = make_noise(c.raw_x ? c.raw_x + io.ro * 3 : nullptr, c.raw_h ? c.raw_h + io.ro * h->F : nullptr, c.noise_rows,
-                                     c.seed, io.base, d.value, share);
-            if (form == 3) {
-                HD_TRY(sde_launch(h, topo, io, io.z, topo->eps, pt.d_coef + (size_t)io.row * 6, nullptr, topo->ms_hist, topo->ms_hist, ns,
-                                  d.word, mol, k_lo));
-                if (rec_z) HD_TRY(chain_launch(h, topo, io, nullptr));
-                continue;
-            }
-            HD_TRY(step_impl(h, topo, io, io.z, topo->eps, pt.d_coef + (size_t)io.row * 4, 1, ns, d.word, mol, N, form, k_lo));
+            const NoiseSrc ns = make_noise(c.raw_x ? c.raw_x + io.ro * 3 : nullptr, c.raw_h ? c.raw_h + io.ro * h->F : nullptr, c.noise_rows,
+                                           c.seed, io.base, d.value, share);
+            HD_TRY(step_launch(h, topo, io, form, io.z, topo->eps, pt.d_coef + (size_t)io.row * step_row_width(form), 1, nullptr,
+                               topo->ms_hist, topo->ms_hist, ns, d.word, mol, N, k_lo));
             if (R) HD_TRY(inpaint_round(h, topo, io, j, R, stride, c.seed, pt.d_coef_ip));
-            if (rec_z) HD_TRY(chain_launch(h, topo, io, nullptr));
+            if (rec && j == rounds - 1 && topo->chain_what == 0) HD_TRY(chain_launch(h, topo, io, nullptr));
         }
         return HD_OK;
     };
@@ -918,9 +876,9 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     key.raw_x = c.raw_x; key.raw_h = c.raw_h; key.has_ctx = c.context ? 1 : 0; key.mol_shape = ms; key.noise_rows = c.noise_rows;
     key.k_lo = c.raw_x ? k_lo : 0; key.resamplings = R; key.seed = c.seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
     key.path_gen = pt.gen; key.ip_gen = R ? h->ip_gen : 0; key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
-    key.rs_gen = rsn ? topo->rs_gen : 0; key.rs_rows_gen = rsn ? h->rs_gen : 0;
+    key.rs_gen = rsn ? topo->rs_gen : 0; key.rs_rows_gen = rsn ? h->rs_rows.gen : 0;
     key.st_P = stn ? topo->st_P : 0; key.st_ess = stn ? topo->st_ess : 0.0; key.st_gen = stn ? topo->st_gen : 0;
-    key.st_rows_gen = stn ? h->st_gen : 0;
+    key.st_rows_gen = stn ? h->st_rows.gen : 0;
     PathWords w;
     w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = R ? h->d_ipdraw : nullptr;
     w.tau = h->d_tau; w.t_idx = pt.d_t; w.s_idx = pt.d_s; w.K = K; w.T = T; w.nd = nd; w.stride = stride; w.chain = rec ? h->d_chain_dst : nullptr;

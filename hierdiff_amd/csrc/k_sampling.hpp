@@ -184,15 +184,18 @@ HD_DEVINL float raw_noise(const NoiseSrc& s, int b, int nn, int c, int mol, int 
 struct StepArgs {
     const float* zt;      // [B][N][D]
     const float* eps;     // [B][N][D]
-    const float* coef;    // [rows][4]
+    const float* coef;    // device rows of the form's width (step_row); null: `row`
+    float row[6];         // one row by value (hd_multistep_step, hd_multistep_sde_step)
     const uint8_t* nm;    // [B*N] node mask bytes
-    float* zs;            // [B][out_stride][D]
+    const float* x_prev;  // forms 2, 3: [B][N][D] x^_{k-1}; read only where the row's c2 != 0
+    float* x_out;         // forms 2, 3: [B][N][D] x^_k (masked entries 0); may be x_prev
+    float* zs;            // [B][out_stride][D]; may be zt where out_stride == N
     NoiseSrc noise;
     const uint32_t* draw_ptr;   // optional device-side draw counter (graph replay); overrides noise.draw
     const int* step_ptr;        // optional device-side step index into coef (graph replay)
     const unsigned long long* base_ptr;   // optional device-side first global sample id (graph replay); overrides noise.sample_base
     int raw_step0;              // graph replay: injected normals are indexed by *step_ptr - raw_step0 (the position the call started at)
-    int coef_rows, B, N, D, F, mol, out_stride;
+    int coef_rows, B, N, D, F, mol, out_stride;   // rows >= mol of a molecule (pocket rows) are left alone
 };
 
 // sum of `v` over the workgroup (4 wavefronts), result in every thread; `red` is 4 floats of LDS scratch
@@ -205,18 +208,8 @@ HD_DEVINL float block_sum4(float v, float* red, int tid) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// sample_p_zs_given_zt after the network call (diffusion_qm9.py:326-345) + sample_normal.
-// One workgroup (256 threads) per molecule, one thread per (node, component): every raw normal (Philox + Box-Muller
-// is ~150 instructions) is produced once and kept in LDS for the second pass; dynamic LDS = mol * D floats.
-// FORM 0: the ancestral row {alpha_t|s, sigma2_t|s, sigma_t, sigma} above.  FORM 1 (path loop with eta < 1): the linear row
-// {a, b, c, 0} of z_s = (a z_t - b eps) + c noise, eps and noise with their x parts mean-removed as in form 0; with c == 0
-// (eta = 0) no normal is generated or read at all and the LDS pass that holds them goes away.
-template <int FORM>
-__global__ __launch_bounds__(256) void k_post_step(StepArgs a) {
-    extern __shared__ float nz_s[];                // [mol * D] masked raw normals, later the un-centred z_s
-    __shared__ float red[4];
-    const int tid = threadIdx.x;
-    const int b = blockIdx.x;
+// the step's noise source: the by-value one, with the device words of a captured loop over it
+HD_DEVINL NoiseSrc step_noise(const StepArgs& a) {
     NoiseSrc ns = a.noise;
     if (a.base_ptr) ns.sample_base = *a.base_ptr;
     if (a.draw_ptr) {
@@ -227,10 +220,54 @@ __global__ __launch_bounds__(256) void k_post_step(StepArgs a) {
             ns.raw_h += k * a.F;
         }
     }
-    const float* cf = a.coef + (a.step_ptr ? (size_t)(*a.step_ptr) * 4 : (size_t)((a.coef_rows == 1) ? 0 : b) * 4);
+    return ns;
+}
+
+// the step's row of W floats: row *step_ptr of the table (captured loop), else the table's one row or molecule b's, else `row`
+template <int W>
+HD_DEVINL void step_row(const StepArgs& a, int b, float (&cf)[W]) {
+    if (a.coef) {
+        const float* r = a.coef + (a.step_ptr ? (size_t)(*a.step_ptr) * W : (size_t)((a.coef_rows == 1) ? 0 : b) * W);
+#pragma unroll
+        for (int k = 0; k < W; ++k) cf[k] = r[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < W; ++k) cf[k] = a.row[k];
+    }
+}
+
+// floats in a row of form FORM (PathTables::form), and where its second-order coefficient c2 stands (forms 2 and 3)
+constexpr int step_row_width(int form) { return form == 2 ? 5 : form == 3 ? 6 : 4; }
+constexpr int step_row_c2(int form) { return form == 3 ? 3 : 2; }
+
+// The posterior step z_t -> z_s after the network call (sample_p_zs_given_zt, diffusion_qm9.py:326-345, + sample_normal) in its
+// four row forms:
+//   0  ancestral {alpha_t|s, sigma2_t|s, sigma_t, sigma}
+//   1  linear {a, b, c, 0} (path loop with eta < 1):        z_s = (a z_t - b eps) + c xi
+//   2  DPM-Solver++(2M) {a, b, c2, p, q}, draws nothing:     z_s = (a z_t - b eps) + c2 (x^_k - x^_{k-1}),   x^_k = p z_t - q eps
+//   3  SDE-DPM-Solver++(2M) {a, b, c, c2, p, q}:             z_s = ((a z_t - b eps) + c xi) + c2 (x^_k - x^_{k-1})
+// eps and the noise xi with their x parts mean-removed, the x part of z_s re-centred.  Forms 2 and 3 (no reference counterpart) are
+// the data-prediction multistep updates folded onto the linear row; they write x^_k to x_out, and every thread reads its elements
+// of the history before it overwrites them: x_prev and x_out may be one buffer.
+// One workgroup (256 threads) per molecule, one thread per (node, component): every raw normal (Philox + Box-Muller is ~150
+// instructions) is produced once and kept in LDS for the second pass; dynamic LDS = mol * D floats.  With c == 0 (eta = 0, and
+// always in form 2) no normal is generated or read at all and the LDS pass that holds them goes away.  The sums of a molecule run
+// in one order and the first-order expression is the linear row's in forms 1 to 3, so a row with c2 == 0 gives the bits of form 1
+// on {a, b, c, 0} with the same draws.  Exact fp32, no atomics.
+template <int FORM>
+__global__ __launch_bounds__(256) void k_post_step(StepArgs a) {
+    extern __shared__ float nz_s[];                // [mol * D] masked raw normals, later the un-centred z_s
+    __shared__ float red[4];
+    constexpr int C2 = step_row_c2(FORM);          // forms 2, 3: the row is {..., c2, p, q}
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x;
+    const NoiseSrc ns = step_noise(a);
+    float cf[step_row_width(FORM)];
+    step_row(a, b, cf);
     const float alpha_ts = cf[0], sigma2_ts = cf[1], sigma_t = cf[2], sigma = cf[3];
     const float ceps = (FORM == 0) ? (sigma2_ts / alpha_ts) / sigma_t : 0.f;
-    const bool noisy = FORM == 0 || cf[2] != 0.f;  // uniform over the workgroup
+    const bool noisy = FORM == 0 || (FORM != 2 && cf[2] != 0.f);  // uniform over the workgroup
+    const bool second = FORM >= 2 && cf[C2] != 0.f;
     const int mol = a.mol, D = a.D, total = mol * D;
     // pass 1: raw normals (masked) into LDS; masked sums of eps_x and of the x-noise per component, node count
     float se[3] = {0.f, 0.f, 0.f}, sn[3] = {0.f, 0.f, 0.f}, cnt = 0.f;
@@ -255,13 +292,15 @@ __global__ __launch_bounds__(256) void k_post_step(StepArgs a) {
     cnt = block_sum4(cnt, red, tid);
 #pragma unroll
     for (int k = 0; k < 3; ++k) { em[k] /= cnt; nmn[k] /= cnt; }
-    // pass 2: z_s before the final re-centring (kept in LDS); its x sums
+    // pass 2: z_s before the final re-centring (kept in LDS), its x sums; forms 2, 3: x^_k out
     float sv[3] = {0.f, 0.f, 0.f};
     for (int e = tid; e < total; e += 256) {
         const int nn = e / D, c = e - nn * D;
-        const float m = a.nm[b * a.N + nn] ? 1.f : 0.f;
-        const float zt = a.zt[((size_t)b * a.N + nn) * D + c];
-        float ev = a.eps[((size_t)b * a.N + nn) * D + c];
+        const size_t g = ((size_t)b * a.N + nn) * D + c;
+        const bool valid = a.nm[b * a.N + nn] != 0;
+        const float m = valid ? 1.f : 0.f;
+        const float zt = a.zt[g];
+        float ev = a.eps[g];
         float z = noisy ? nz_s[e] : 0.f;
         if (c < 3) {
 #pragma unroll
@@ -270,6 +309,14 @@ __global__ __launch_bounds__(256) void k_post_step(StepArgs a) {
         float v;
         if constexpr (FORM == 0) v = (zt / alpha_ts - ceps * ev) + sigma * z;
         else v = noisy ? (cf[0] * zt - cf[1] * ev) + cf[2] * z : cf[0] * zt - cf[1] * ev;
+        if constexpr (FORM >= 2) {                 // with c2 == 0 the linear row above is the whole update
+            const float xk = cf[C2 + 1] * zt - cf[C2 + 2] * ev;
+            if (second) {
+                const float xp = a.x_prev[g];
+                if (valid) v += cf[C2] * (xk - xp);
+            }
+            a.x_out[g] = valid ? xk : 0.f;
+        }
         nz_s[e] = v;
         if (c < 3) {
 #pragma unroll

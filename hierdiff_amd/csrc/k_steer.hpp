@@ -12,7 +12,7 @@
 //                      the group is left alone and counted.
 //   k_steer_gather<0>  rows with anc[b] != b: z, eps^ and U_prev of row anc[b] into the topology's scratch
 //   k_steer_gather<1>  ... and from the scratch into row b.  Rows with anc[b] == b are not written.  With `hist` (the stochastic
-//                      multistep rows, k_solver.hpp) the data prediction x^_{k-1} of the lineage travels the same way.
+//                      multistep rows, k_post_step<3>) the data prediction x^_{k-1} of the lineage travels the same way.
 // u = philox_uniform(seed, id of the group's first row, the transition's draw T - s, ST_UNIFORM_INDEX): words 2 and 3 of the block
 // whose words 0 and 1 no normal uses (index / 2 = 2^31 - 1; a molecule has at most 16384 entries), 26 bits each, in double.
 // No atomics; every sum has a fixed order.  stats [G][3] = (resampling events, smallest ESS, transitions with every weight 0).

@@ -33,7 +33,6 @@
 #include "k_nll.hpp"
 #include "k_edit.hpp"
 #include "k_guide.hpp"
-#include "k_solver.hpp"
 #include "k_chain.hpp"
 #include "k_restrain.hpp"
 #include "k_steer.hpp"

@@ -7,7 +7,9 @@ every kernel (function symbol) and every kernel descriptor (object symbol: regis
 number of each, whether the whole code objects are byte-identical, and every symbol that is missing on one side or differs in size
 or bytes.  Exit status 0: same set of symbols, each with the same size and bytes.  (readelf lists every kernel twice, in .symtab
 and in .dynsym; this reads .symtab.  `__hip_cuid_<hash>`, one byte whose NAME is a hash of the source file's path, is left out: it
-differs between two checkouts of the same source, and is what keeps their code objects from being byte-identical.)"""
+differs between two checkouts of the same source, and is what keeps their code objects from being byte-identical.  In a kernel
+descriptor, bytes 16..23 - the distance from the descriptor to the kernel's first instruction - are left out too: they move with the
+size of every kernel placed in front, so one changed kernel would report all descriptors behind it.)"""
 import hashlib
 import struct
 import sys
@@ -58,7 +60,10 @@ def functions(co):
             continue
         sec = raw[st_shndx]
         start = sec[4] + (st_value - sec[3])
-        out[name] = (st_info & 0xF, st_size, hashlib.sha256(co[start:start + st_size]).hexdigest())
+        body = co[start:start + st_size]
+        if name.endswith(".kd") and st_size == 64:
+            body = body[:16] + body[24:]                          # kernel_code_entry_byte_offset
+        out[name] = (st_info & 0xF, st_size, hashlib.sha256(body).hexdigest())
     return out
 
 

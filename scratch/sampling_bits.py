@@ -11,6 +11,10 @@ warm call of the same row adds to the graph build counters (hd_path_graph_builds
 hd_nll_graph_builds).  Behind the matrix, the scoring loop at the same shape (`scoring_matrix`): DiffusionQM9.nll_full over all terms,
 a 4-term uniform list and an explicit subset, with and without the per-term errors and injected noise; the same in two calls of the
 term loop, the second from k_lo = 2 (`nll_split`); and `score` on the list form.
+Behind the scoring rows, the single-step ABI paths that no loop reaches (`steps_group`): hd_posterior_step at every case of
+tests/sampling_reference.py (coef_rows = B, mol_shape < N with out_stride = mol, shared noise, in place), hd_multistep_step and
+hd_multistep_sde_step with host rows at the shapes `wrap`, `F1`, `B1`, `pocket` of tests/test_gpu_sde_solver.py and the masks of
+tests/test_gpu_solver.py, injected, shared and generated noise, aliased outputs - inputs from those tests' own generators.
 A row the library refuses before it launches anything (solver "dpm2m" from k_lo > 0 without the transition before it) holds
 "HD_E_STATE"; any other library error ends the run.
 `--out` holds, per `use_graph` value and entry point, the number of rows, how they ended, the warm builds summed, and one SHA-256 over
@@ -75,6 +79,67 @@ def score_call(case, entry, opt, graph):
     return {"nll": digest(nll)} if err is None else {"nll": digest(nll), "err": digest(err)}
 
 
+def steps_group():
+    """{row name: {tensor: sha256}} of the three single-step functions, straight at the C ABI."""
+    import ctypes as C
+
+    import numpy as np
+    from oracle import egnn_oracle as orc
+    from tests import sampling_reference as smp
+    from tests import sde_solver_reference as sd
+    from tests import solver_reference as sol
+    from tests import test_gpu_sampling_kernels as tk
+    from tests import test_gpu_sde_solver as ts
+    from tests import test_gpu_solver as tm
+    from tests.test_gpu_restraint import Bare
+
+    out = {}
+    from hierdiff_amd import _lib
+    lib = _lib.load()
+    cases = smp.cases()
+    for name in smp.STEP_CASES:                                                    # hd_posterior_step
+        c = cases[name]
+        h = C.c_void_p()
+        cfg = tk.make_config(c["F"])
+        assert lib.hd_create(C.byref(cfg), 0, C.byref(h)) == 0, lib.hd_last_error()
+        with tk.topology(lib, h, c["nm"]) as topo:
+            for in_place in ((False, True) if c["mol"] == c["N"] else (False,)):
+                out[f"hd_posterior_step|{name}|in_place={int(in_place)}"] = {"zs": digest(torch.from_numpy(tk.device_step(lib, h, topo, c, in_place)))}
+        assert lib.hd_destroy(h) == 0
+    T, K = ts.T, ts.K
+    path = sd.uniform_path(T, K)
+    rows6 = sd.sde_rows(sd.analytic_grid(T), path, lower_order_final=False)
+    rows5 = sol.multistep_rows(sol.analytic_grid(T), sol.uniform_path(T, K), lower_order_final=False)
+    shapes = {name: ts.kernel_case(name) for name in ("wrap", "F1", "B1", "pocket")}
+    for name, sizes in tm.MASKS.items():
+        shapes[name] = (orc.canonical_masks(sizes)[0].bool().reshape(len(sizes), -1), 8, None)
+    for name, (nm, F, mol) in shapes.items():
+        B, N = nm.shape
+        n = N if mol is None else mol
+        zt, eps, xp = ts.kernel_inputs(nm, F, 1)
+        g = torch.Generator().manual_seed(2)
+        raw_b = (torch.randn(B, n, 3, generator=g), torch.randn(B, n, F, generator=g))
+        sources = [("injected", raw_b, B, 0), ("shared row", (raw_b[0][:1], raw_b[1][:1]), 1, 0), ("generator", None, B, 0),
+                   ("generator, shared", None, B, 1)]
+        bare = Bare(3 + F, nm)
+        topo = argparse.Namespace(ptr=bare.topo)
+        try:
+            for k in (0, 3, K - 1):
+                hist = None if k == 0 else xp
+                for in_place in (False, True):                                     # hd_multistep_step (no mol_shape: whole molecules)
+                    xk, zs = tm.step_on_device(lib, bare.h, topo, tm.f32(rows5[k]), ts.dev(zt), ts.dev(eps), ts.dev(hist), in_place)
+                    torch.cuda.synchronize()
+                    out[f"hd_multistep_step|{name}|row {k}|in_place={int(in_place)}"] = {"x": digest(xk), "zs": digest(zs)}
+                if name not in tm.MASKS:
+                    for what, raw, noise_rows, share in sources:                   # hd_multistep_sde_step
+                        for alias in ((False, True) if mol is None else (False,)):
+                            xk, zs = ts.sde_step(bare, ts.f32(rows6[k]), zt, eps, hist, raw, noise_rows, mol, share, alias=alias)
+                            out[f"hd_multistep_sde_step|{name}|row {k}|{what}|alias={int(alias)}"] = {"x": digest(xk), "zs": digest(zs)}
+        finally:
+            bare.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
@@ -113,6 +178,9 @@ def main():
             res["rows"][name] = row
         torch.cuda.synchronize()
         print(f"use_graph={graph}: {len(res['rows'])} rows", flush=True)
+    for name, sha in steps_group().items():
+        res["rows"][f"steps|{name.split('|')[0]}|{name}"] = {"sha256": sha}
+    print(f"steps: {len(res['rows'])} rows", flush=True)
     groups = {}
     for name, row in res["rows"].items():
         g = groups.setdefault("|".join(name.split("|")[:2]), {"rows": 0, "ended": {}, "warm_builds": [0] * len(COUNTERS), "sha256": hashlib.sha256()})

@@ -342,6 +342,81 @@ def test_graph_replay_equals_launches_and_reattaching_does_not_rebuild():
     assert same(model.sample_from_masks(nmd, None, None, restraints=a, **kw), "a")
 
 
+def check_row_setter_and_the_captured_graph(steer):
+    """hd_set_restraint (`steer`: hd_set_steer) between graph-replayed hd_sample_path calls at the C ABI, B = 4, N = 5, K = 3, hidden 32:
+    rows of the same K land in the table the captured transition already reads - no graph is built and the rows that were set are the
+    ones that act - and rows of another K (which takes a path of that K) cost exactly one build."""
+    lib = _lib.load()
+    model, _, _ = model_for("fp32")
+    fresh(model, graph=True)
+    _, _, nm, _, _ = batch_for((5, 4, 3, 1))
+    nmd = dev(nm)
+    B, N = nm.shape[:2]
+    hnd, tabs = model._lib_handle(), model._schedule(rows=B)
+    topo = model.dynamics.topology(nmd, None, B, N)
+    g = torch.Generator().manual_seed(11)
+    zT = dev(orc.combined_noise(torch.randn(B, N, 3, generator=g), torch.randn(B, N, 8, generator=g), nm.float()))
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    ip = lambda v: np.ascontiguousarray(v.numpy()).ctypes.data_as(C.POINTER(C.c_int))
+
+    def set_path(K):
+        pt = paths.path_tables(tabs["gamma"], paths.uniform_path(T, K), eta=0.5)
+        coef = np.ascontiguousarray(pt["coef"].numpy())
+        assert lib.hd_set_path(hnd, K, ip(pt["t_idx"]), ip(pt["s_idx"]), fp(coef), pt["form"], None) == 0, lib.hd_last_error()
+
+    def set_rows(K, strength):
+        rows4 = np.ascontiguousarray(np.tile(np.array([0.8, 0.6, 0.0 if steer else strength, 0.3], dtype=np.float32), (K, 1)))
+        assert lib.hd_set_restraint(hnd, K, fp(rows4)) == 0, lib.hd_last_error()
+        if steer:
+            rows3 = np.ascontiguousarray(np.tile(np.array([0.8, 0.6, strength], dtype=np.float32), (K, 1)))
+            assert lib.hd_set_steer(hnd, K, fp(rows3)) == 0, lib.hd_last_error()
+
+    def run(K):
+        z = zT.clone()
+        assert lib.hd_sample_path(hnd, topo.ptr, z.data_ptr(), None, -1, 0, K, None, None, B, SEED, 3, 1, stream()) == 0, lib.hd_last_error()
+        torch.cuda.synchronize()
+        return z
+
+    builds = lambda: lib.hd_path_graph_builds(topo.ptr)
+    rs, _ = rr.random_tables(B, N, 3, 2, 2, seed=4, per_molecule=False)
+    model._path_cache = None                                  # the handle's path and rows are set behind the model's back
+    try:
+        rs.attach(topo, torch.ones(1), 1.0, torch.device(DEV), stream())
+        if steer:
+            assert lib.hd_steer_attach(topo.ptr, 2, 0.5, 1, stream()) == 0, lib.hd_last_error()
+        set_path(3)
+        set_rows(3, 0.05)
+        n0 = builds()
+        first = run(3)
+        assert builds() == n0 + 1
+        set_rows(3, 0.4)
+        other = run(3)
+        assert builds() == n0 + 1, "rows of the same K rebuilt the captured transition"
+        if not steer:
+            assert not torch.equal(other, first), "the captured transition did not read the new rows"
+        if steer:
+            assert lib.hd_steer_attach(topo.ptr, 2, 0.5, 1, stream()) == 0, lib.hd_last_error()
+        set_rows(3, 0.05)
+        assert torch.equal(run(3), first) and builds() == n0 + 1
+        set_path(2)
+        set_rows(2, 0.05)
+        if steer:
+            assert lib.hd_steer_attach(topo.ptr, 2, 0.5, 1, stream()) == 0, lib.hd_last_error()
+        run(2)
+        assert builds() == n0 + 2, "rows of another K (and their path) cost exactly one build"
+        set_rows(2, 0.4)
+        run(2)
+        assert builds() == n0 + 2
+    finally:
+        lib.hd_steer_detach(topo.ptr)
+        lib.hd_restraint_detach(topo.ptr)
+        model._path_cache = model._restraint_cache = model._steer_cache = None
+
+
+def test_restraint_rows_of_the_same_K_keep_the_captured_graph_and_another_K_builds_one():
+    check_row_setter_and_the_captured_graph(steer=False)
+
+
 # ----------------------------------------------------------------------------- independence of batch and chain cuts
 
 @pytest.mark.parametrize("graph", [True, False], ids=["graph", "launches"])

@@ -47,7 +47,7 @@ def lib():
 @pytest.fixture(scope="module")
 def handles(lib):
     """One handle per feature width.  hd_noise, hd_posterior_step and hd_final_decode read the handle's D and F and the topology's
-    mask bytes only, no weights (step_impl, hd_final_decode, hd_noise in hierdiff_hip.hip): none are set."""
+    mask bytes only, no weights (step_launch, hd_final_decode, hd_noise in hierdiff_hip.hip): none are set."""
     made = {}
     for F in sorted({c["F"] for c in CASES.values()}):
         h = C.c_void_p()

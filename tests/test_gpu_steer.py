@@ -19,7 +19,7 @@ from hierdiff_amd.restraints import Restraints
 from tests import restraint_reference as rr
 from tests import steer_reference as st
 from tests.helpers import REL_L2_TOL, rel_l2
-from tests.test_gpu_restraint import Bare, batch_for, dev, model_for, stream, tables
+from tests.test_gpu_restraint import Bare, batch_for, check_row_setter_and_the_captured_graph, dev, model_for, stream, tables
 from tests.test_inpaint_cpu import SEED
 
 pytestmark = pytest.mark.gpu
@@ -184,6 +184,10 @@ def steer_batch(groups):
 
 
 SKW = dict(steps=6, eta=1.0, particles=st.CHAIN_P, steer_scale=st.CHAIN_BETA, **st.CHAIN_RKW)
+
+
+def test_steer_rows_of_the_same_K_keep_the_captured_graph_and_another_K_builds_one():
+    check_row_setter_and_the_captured_graph(steer=True)
 
 
 def test_graph_replay_equals_launches_and_a_second_call_builds_no_graph():
