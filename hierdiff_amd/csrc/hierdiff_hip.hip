@@ -171,6 +171,7 @@ struct PathKey {
     uint64_t seed;
     unsigned long long weights_gen, sched_gen, path_gen, ip_gen;
     unsigned long long rs_gen, rs_rows_gen;                  // restrained transition: the topology's tables, the handle's rows (0 / 0: plain)
+    int rs_frame;                                            // 1: its restraints act in the known fragments' frame (hd_restraint_frame)
     int st_P;                                                // steered transition: particles per group, rho, the topology's steering
     double st_ess;                                           // buffers, the handle's rows (all 0: not steered)
     unsigned long long st_gen, st_rows_gen;
@@ -178,7 +179,7 @@ struct PathKey {
         return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape && noise_rows == o.noise_rows &&
                k_lo == o.k_lo && resamplings == o.resamplings && w_rows == o.w_rows && phi == o.phi && seed == o.seed &&
                weights_gen == o.weights_gen && sched_gen == o.sched_gen && path_gen == o.path_gen && ip_gen == o.ip_gen &&
-               rs_gen == o.rs_gen && rs_rows_gen == o.rs_rows_gen && st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen &&
+               rs_gen == o.rs_gen && rs_rows_gen == o.rs_rows_gen && rs_frame == o.rs_frame && st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen &&
                st_rows_gen == o.st_rows_gen;
     }
 };
@@ -267,6 +268,7 @@ struct hd_topology {
     int rs_obs_rows, rs_P, rs_pair_rows, rs_Q, rs_anc_rows, rs_A, rs_scale_rows;
     float rs_nv0;
     unsigned long long rs_gen;
+    int rs_frame;                              // hd_restraint_frame: 0 the model's frame, 1 the known fragments' (inpainting calls)
     // hd_steer_attach: the steering state of the chain that runs on this topology (log-weights, last energies, lineage roots, the
     // ancestors of the latest transition, per-group statistics) and the scratch of k_steer_gather - one allocation each, made by the
     // first attach at addresses captured transitions keep.  It survives between the pieces of a chain; `reset` starts a new one.

@@ -555,7 +555,16 @@ extern "C" int hd_restraint_attach(hd_topology* topo, const float* obs, int obs_
         topo->rs_gen++;
     topo->rs_obs_rows = obs_rows; topo->rs_P = P; topo->rs_pair_rows = pair_rows; topo->rs_Q = Q; topo->rs_anc_rows = anc_rows;
     topo->rs_A = A; topo->rs_scale_rows = scale_rows; topo->rs_nv0 = nv0;
+    topo->rs_frame = 0;                                 // the model's frame, until hd_restraint_frame says otherwise
     topo->rs_on = true;
+    return HD_OK;
+}
+
+extern "C" int hd_restraint_frame(hd_topology* topo, int frame) {
+    if (!topo) return fail(HD_E_INVALID, "hd_restraint_frame: null topology");
+    if (frame != 0 && frame != 1) return fail(HD_E_INVALID, "hd_restraint_frame: frame is 0 (the model's) or 1 (the known fragments')");
+    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restraint_frame: no restraints attached to the topology (hd_restraint_attach)");
+    topo->rs_frame = frame;                             // part of the graph key (PathKey::rs_frame)
     return HD_OK;
 }
 
@@ -572,9 +581,9 @@ static RestraintTables restraint_tables(const hd_topology* t) {
 }
 
 // The update of one transition on eps (in place when out == eps): `rows` the device table read at position *io.step / io.row, or the
-// host row.
+// host row.  `framed`: in the frame of the known fragments io.fixed / io.known (k_restrain_eps<true>).
 static int restrain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* z, const float* eps, float* out,
-                           const float* rows, const float* row4) {
+                           const float* rows, const float* row4, bool framed = false) {
     ProfScope ps(h, io.s, 2);
     RestrainArgs a;
     a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.t = restraint_tables(t); a.scale = t->rs_scale;
@@ -582,7 +591,9 @@ static int restrain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const
     for (int i = 0; i < 4; ++i) a.row[i] = row4 ? row4[i] : 0.f;
     a.step_ptr = io.step; a.k = io.row; a.step = t->rs_step; a.nv0 = t->rs_nv0; a.scale_rows = t->rs_scale_rows;
     a.B = t->B; a.N = t->N; a.D = h->D;
-    hipLaunchKernelGGL(k_restrain_eps, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, a);
+    a.fixed = framed ? io.fixed : nullptr; a.known = framed ? io.known : nullptr;
+    if (framed) hipLaunchKernelGGL(k_restrain_eps<true>, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, a);
+    else hipLaunchKernelGGL(k_restrain_eps<false>, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, a);
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
@@ -605,6 +616,26 @@ extern "C" int hd_restrain_eps(hd_handle* h, hd_topology* topo, const float* z, 
     return restrain_launch(h, topo, io, z, eps, out, nullptr, row4);
 }
 
+extern "C" int hd_restrain_eps_framed(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4,
+                                      const uint8_t* fixed_mask, const float* xh_known, float* out, void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_restrain_eps_framed: null handle/topology");
+    if (!z || !eps || !row4 || !out || !fixed_mask || !xh_known)
+        return fail(HD_E_INVALID, "hd_restrain_eps_framed: null tensor / row / fixed_mask / xh_known");
+    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restrain_eps_framed: no restraints attached to the topology (hd_restraint_attach)");
+    if (!restraint_row_ok(row4))
+        return fail(HD_E_INVALID, "hd_restrain_eps_framed: need alpha_t > 0, sigma_t >= 0, a finite lambda and clip > 0 (inf: no clip)");
+    const size_t per = (size_t)topo->B * topo->N * h->D;
+    if (out < z + per && z < out + per) return fail(HD_E_INVALID, "hd_restrain_eps_framed: out may not overlap z");
+    if (out < xh_known + per && xh_known < out + per) return fail(HD_E_INVALID, "hd_restrain_eps_framed: out may not overlap xh_known");
+    if (out != eps && out < eps + per && eps < out + per)
+        return fail(HD_E_INVALID, "hd_restrain_eps_framed: out may be eps itself, not a shifted overlap of it");
+    HIP_TRY(hipSetDevice(h->device));
+    LoopIO io{};
+    io.s = (hipStream_t)stream; io.fixed = fixed_mask; io.known = xh_known;
+    topo_use(topo, io.s);
+    return restrain_launch(h, topo, io, z, eps, out, nullptr, row4, true);
+}
+
 extern "C" int hd_restraint_energy(hd_handle* h, hd_topology* topo, const float* x, double* out3, void* stream) {
     if (!h || !topo) return fail(HD_E_INVALID, "hd_restraint_energy: null handle/topology");
     if (!x || !out3) return fail(HD_E_INVALID, "hd_restraint_energy: null tensor");
@@ -613,9 +644,26 @@ extern "C" int hd_restraint_energy(hd_handle* h, hd_topology* topo, const float*
     hipStream_t s = (hipStream_t)stream;
     topo_use(topo, s);
     ProfScope ps(h, s, 2);
-    RestraintEnergyArgs a;
+    RestraintEnergyArgs a{};
     a.x = x; a.nm = topo->nm_bytes; a.t = restraint_tables(topo); a.out = out3; a.B = topo->B; a.N = topo->N;
-    hipLaunchKernelGGL(k_restraint_energy, dim3(topo->B), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_restraint_energy<false>, dim3(topo->B), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_restraint_energy_framed(hd_handle* h, hd_topology* topo, const float* x, const uint8_t* fixed_mask,
+                                          const float* x_known, double* out3, double* shift3, void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_restraint_energy_framed: null handle/topology");
+    if (!x || !out3 || !fixed_mask || !x_known) return fail(HD_E_INVALID, "hd_restraint_energy_framed: null tensor");
+    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restraint_energy_framed: no restraints attached to the topology (hd_restraint_attach)");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    ProfScope ps(h, s, 2);
+    RestraintEnergyArgs a{};
+    a.x = x; a.nm = topo->nm_bytes; a.t = restraint_tables(topo); a.out = out3; a.B = topo->B; a.N = topo->N;
+    a.fixed = fixed_mask; a.x_known = x_known; a.shift = shift3;
+    hipLaunchKernelGGL(k_restraint_energy<true>, dim3(topo->B), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
@@ -813,9 +861,14 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
         if (mol != N) return fail(HD_E_INVALID, "path loop: a chain sink records whole molecules only (mol_shape < N)");
     }
     const bool rsn = c.record && topo->rs_on;
+    const bool framed = rsn && topo->rs_frame == 1;
     if (rsn) {
-        if (R) return fail(HD_E_INVALID, "path loop: restraints are attached to the topology, and inpainting takes none (it re-centres "
-                                         "on the known fragments: hd_restraint_detach)");
+        if (R && !framed) return fail(HD_E_INVALID, "path loop: restraints are attached to the topology, and inpainting takes none (it re-centres "
+                                                    "on the known fragments: hd_restraint_detach)");
+        if (framed && !R) return fail(HD_E_INVALID, "path loop: the restraints are set to the known fragments' frame (hd_restraint_frame), "
+                                                    "which needs fixed fragments: an inpainting call");
+        if (framed && topo->st_on) return fail(HD_E_INVALID, "path loop: steering is attached to the topology, and restraints in the known "
+                                                             "fragments' frame take none (hd_steer_detach)");
         if (!h->rs_rows.d || h->rs_rows.path_gen != pt.gen)
             return fail(HD_E_STATE, "path loop: restraints are attached but their rows are not set for the current path (hd_set_restraint)");
         if (mol != N) return fail(HD_E_INVALID, "path loop: restraints act on whole molecules only (mol_shape < N)");
@@ -838,7 +891,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
                 HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx_u, ms, topo->eps_u, io.s));
                 HD_TRY(guide_launch(h, topo, topo->eps, topo->eps_u, io.w, gd->w_rows, gd->phi, topo->eps, io.s));
             }
-            if (rsn) HD_TRY(restrain_launch(h, topo, io, io.z, topo->eps, topo->eps, h->rs_rows.d, nullptr));
+            if (rsn) HD_TRY(restrain_launch(h, topo, io, io.z, topo->eps, topo->eps, h->rs_rows.d, nullptr, framed));
             if (stn) HD_TRY(steer_launch(h, topo, io, io.z, topo->eps, h->st_rows.d, nullptr, io.draw_of(0, stride), c.seed,
                                          form == 3 ? topo->ms_hist : nullptr));
             if (rec && j == rounds - 1 && topo->chain_what == 1) HD_TRY(chain_launch(h, topo, io, topo->eps));
@@ -876,7 +929,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     key.raw_x = c.raw_x; key.raw_h = c.raw_h; key.has_ctx = c.context ? 1 : 0; key.mol_shape = ms; key.noise_rows = c.noise_rows;
     key.k_lo = c.raw_x ? k_lo : 0; key.resamplings = R; key.seed = c.seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
     key.path_gen = pt.gen; key.ip_gen = R ? h->ip_gen : 0; key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
-    key.rs_gen = rsn ? topo->rs_gen : 0; key.rs_rows_gen = rsn ? h->rs_rows.gen : 0;
+    key.rs_gen = rsn ? topo->rs_gen : 0; key.rs_rows_gen = rsn ? h->rs_rows.gen : 0; key.rs_frame = framed ? 1 : 0;
     key.st_P = stn ? topo->st_P : 0; key.st_ess = stn ? topo->st_ess : 0.0; key.st_gen = stn ? topo->st_gen : 0;
     key.st_rows_gen = stn ? h->st_rows.gen : 0;
     PathWords w;
@@ -1016,7 +1069,7 @@ extern "C" int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z,
     const char* who = "hd_sample_path_inpaint";
     if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_sample_path_inpaint: need 0 <= k_lo <= k_hi <= K");
     HD_TRY(check_ready(h, topo, who));
-    if (topo->rs_on) return fail(HD_E_INVALID, "hd_sample_path_inpaint: restraints are attached to the topology, and inpainting takes "
+    if (topo->rs_on && !topo->rs_frame) return fail(HD_E_INVALID, "hd_sample_path_inpaint: restraints are attached to the topology, and inpainting takes "
                                                "none (it re-centres on the known fragments: hd_restraint_detach)");
     HD_TRY(path_ready(h, who, k_lo, k_hi));
     HD_TRY(inpaint_path_check(who, h, ": ancestral rows only (the path was set with form = 1)"));
@@ -1063,7 +1116,7 @@ extern "C" int hd_sample_path_guided(hd_handle* h, hd_topology* topo, float* z, 
     if (!(rescale >= 0.f && rescale <= 1.f)) return fail(HD_E_INVALID, "hd_sample_path_guided: rescale must lie in [0, 1]");
     if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_path_guided: needs a time-conditioned model");
     if (fixed_mask) {                                        // the restrictions of hd_sample_path_inpaint
-        if (topo->rs_on) return fail(HD_E_INVALID, "hd_sample_path_guided: restraints are attached to the topology, and inpainting "
+        if (topo->rs_on && !topo->rs_frame) return fail(HD_E_INVALID, "hd_sample_path_guided: restraints are attached to the topology, and inpainting "
                                                    "takes none (it re-centres on the known fragments: hd_restraint_detach)");
         HD_TRY(inpaint_path_check(who, h, ": inpainting takes ancestral rows only (the path was set with form = 1)"));
         if (!xh_known) return fail(HD_E_INVALID, "hd_sample_path_guided: fixed_mask without xh_known");

@@ -1,7 +1,7 @@
 // Restraint-guided sampling (hd_restraint_attach / hd_set_restraint / hd_restrain_eps / hd_restraint_energy; no reference
 // counterpart).  Included through kernels.hpp.
-//   k_restrain_eps       eps_x += project(clip(s_b lambda_k dU/dx)) with U evaluated on the transition's data prediction x^0
-//   k_restraint_energy   (U_obs, U_pair, U_anc) per molecule, in double, for given data-unit positions
+//   k_restrain_eps<F>    eps_x += project(clip(s_b lambda_k dU/dx)) with U evaluated on the transition's data prediction x^0
+//   k_restraint_energy<F> (U_obs, U_pair, U_anc) per molecule, in double, for given data-unit positions
 // U, in data units (x = nv0 z_x, the model's frame: the centre of mass of the valid nodes at the origin), per molecule:
 //   U_obs  = 1/2 sum_{i valid} sum_p k_p max(0, r_p - |x_i - y_p|)^2                    obs  [rows][P][5] = (y, r, k); r <= 0 or k <= 0: padding
 //   U_pair = 1/2 sum_q k_q (max(0, d - hi)^2 + max(0, lo - d)^2),  d = |x_i - x_j|      pair_idx [rows][Q][2], pair_f [rows][Q][3] = (lo, hi, k)
@@ -14,6 +14,12 @@
 // (i mod 256 / RS_GROUP) whatever B is, so the partition and the order of every sum depend on (N, P, Q, A) alone.  The mean of the
 // clipped steps is a strided double sum per thread, the butterfly of a wave, then the four wave partials in a fixed tree
 // (guide_block_sum).  Draws nothing.
+// FRAMED (hd_restraint_frame 1, hd_restrain_eps_framed, hd_restraint_energy_framed): the tables are read in the frame of the known
+// fragments of an inpainting call.  F = the molecule's valid fixed nodes, tau = mean_F(x^0) - mean_F(nv0 known) (a strided double sum
+// per thread, then guide_block_sum: the order depends on N alone); obstacle and anchor centres are y + tau (added in double, x^0 is not
+// rounded again), pairs do not see tau.  Fixed nodes gather nothing - their step is 0, the block is the frame - and receive -mean like
+// every valid node, so eps_x stays mean-free and a free node moves relative to the block by its own step.  No fixed node: tau = 0 and
+// the molecule's bits are those of the plain update.
 #pragma once
 #include "common.hpp"
 #include "k_guide.hpp"
@@ -43,6 +49,9 @@ struct RestrainArgs {
     double* step;           // [B][N][3] scratch: the clipped steps before the projection
     float nv0;
     int scale_rows, B, N, D;
+    // FRAMED only, behind everything the plain kernel reads so that its argument offsets - and with them its code - stay what they were
+    const uint8_t* fixed;   // [B*N] fixed mask bytes
+    const float* known;     // [B][N][D] normalised known values (the x columns are read)
 };
 
 struct RestraintEnergyArgs {
@@ -51,6 +60,10 @@ struct RestraintEnergyArgs {
     RestraintTables t;
     double* out;            // [B][3] (U_obs, U_pair, U_anc)
     int B, N;
+    // FRAMED only (behind the plain kernel's arguments, as in RestrainArgs)
+    const uint8_t* fixed;   // [B*N] fixed mask bytes
+    const float* x_known;   // [B][N][3] known positions, data units
+    double* shift;          // [B][3] tau (null: not wanted)
 };
 
 // One obstacle on the offset u = x_i - y at distance d: the energy, and in `c` the factor with dU/dx_i = c u.
@@ -83,15 +96,24 @@ HD_DEVINL bool rs_pair_active(const int* pi, const float* pf, const uint8_t* nm,
     return i >= 0 && j >= 0 && i < N && j < N && i != j && nm[i] && nm[j] && pf[2] > 0.f;
 }
 
-// lane `l` of the `G` lanes that gather node i: its share of dU/dx_i into g (x: the molecule's positions, data units)
+// A translation of the obstacle and anchor centres (`on` false: none), by value so that it lives in registers.
+struct RsOffset {
+    double x, y, z;
+    bool on;
+};
+#define RS_NO_OFFSET RsOffset{0.0, 0.0, 0.0, false}
+
+// lane `l` of the `G` lanes that gather node i: its share of dU/dx_i into g (x: the molecule's positions, data units).  `off`: the
+// translation of the obstacle and anchor centres.
 HD_DEVINL void rs_node_grad(const RestraintTables& t, int b, const float* x, const uint8_t* nm, int N, int i, int l, int G,
-                            double (&g)[3]) {
+                            double (&g)[3], const RsOffset off = RS_NO_OFFSET) {
     double u[3], c;
     const float* obs = t.obs + (size_t)(t.obs_rows == 1 ? 0 : b) * t.P * 5;
     for (int p = l; p < t.P; p += G) {
         const float* o = obs + (size_t)p * 5;
         if (!(o[3] > 0.f) || !(o[4] > 0.f)) continue;
-        const double d = rs_dist(x, i, (double)o[0], (double)o[1], (double)o[2], u);
+        const double d = off.on ? rs_dist(x, i, (double)o[0] + off.x, (double)o[1] + off.y, (double)o[2] + off.z, u)
+                             : rs_dist(x, i, (double)o[0], (double)o[1], (double)o[2], u);
         rs_obs_term(d, (double)o[3], (double)o[4], c);
         g[0] += c * u[0]; g[1] += c * u[1]; g[2] += c * u[2];
     }
@@ -110,16 +132,41 @@ HD_DEVINL void rs_node_grad(const RestraintTables& t, int b, const float* x, con
     for (int a = l; a < t.A; a += G) {
         const float* af = t.anc_f + (arow + a) * 5;
         if (t.anc_idx[arow + a] != i || !(af[4] > 0.f) || !(af[3] >= 0.f)) continue;
-        const double d = rs_dist(x, i, (double)af[0], (double)af[1], (double)af[2], u);
+        const double d = off.on ? rs_dist(x, i, (double)af[0] + off.x, (double)af[1] + off.y, (double)af[2] + off.z, u)
+                             : rs_dist(x, i, (double)af[0], (double)af[1], (double)af[2], u);
         rs_band_term(d, -1.0, (double)af[3], (double)af[4], c);
         g[0] += c * u[0]; g[1] += c * u[1]; g[2] += c * u[2];
     }
 }
 
+// tau of molecule b into every thread (0 and off without valid fixed nodes): pos [N][stride] positions in data units, known
+// [N][kstride] times ks.  `red`: 4 * 7 doubles of LDS.
+HD_DEVINL bool rs_frame_shift(const float* pos, int stride, const float* known, int kstride, double ks, const uint8_t* nm,
+                              const uint8_t* fixed, int N, double* red, int tid, RsOffset& tau) {
+    double f[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // nf, sum_F pos, sum_F known
+    for (int i = tid; i < N; i += 256) {
+        if (!nm[i] || !fixed[i]) continue;
+        f[0] += 1.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            f[1 + c] += (double)pos[(size_t)i * stride + c];
+            f[4 + c] += ks * (double)known[(size_t)i * kstride + c];
+        }
+    }
+    guide_block_sum<7>(f, red, tid);
+    const bool any = f[0] > 0.0;
+    tau.x = any ? f[1] / f[0] - f[4] / f[0] : 0.0;
+    tau.y = any ? f[2] / f[0] - f[5] / f[0] : 0.0;
+    tau.z = any ? f[3] / f[0] - f[6] / f[0] : 0.0;
+    tau.on = any;
+    return any;
+}
+
 // Dynamic LDS: N * 3 floats (x^0 of the molecule).
+template <bool FRAMED>
 __global__ __launch_bounds__(256) void k_restrain_eps(RestrainArgs a) {
     extern __shared__ float rs_x[];
-    __shared__ double red[4 * 4];
+    __shared__ double red[4 * (FRAMED ? 7 : 4)];
     const int tid = threadIdx.x, b = blockIdx.x;
     const int N = a.N, D = a.D, total = N * D;
     const size_t base = (size_t)b * total;
@@ -142,6 +189,12 @@ __global__ __launch_bounds__(256) void k_restrain_eps(RestrainArgs a) {
         rs_x[e] = __fmul_rn(__fmul_rn(ra, __fsub_rn(z[o], __fmul_rn(sg, eps[o]))), a.nv0);
     }
     __syncthreads();
+    RsOffset tau = RS_NO_OFFSET;
+    const uint8_t* fixed = nullptr;                    // null: every valid node is free
+    if constexpr (FRAMED) {
+        if (rs_frame_shift(rs_x, 3, a.known + base, D, (double)a.nv0, nm, a.fixed + (size_t)b * N, N, red, tid, tau))
+            fixed = a.fixed + (size_t)b * N;           // uniform over the workgroup
+    }
     double* step = a.step + (size_t)b * N * 3;
     const bool clips = clip - clip == 0.f;             // finite
     const int l = tid & (RS_GROUP - 1), grp = tid / RS_GROUP;
@@ -149,7 +202,11 @@ __global__ __launch_bounds__(256) void k_restrain_eps(RestrainArgs a) {
         const int i = i0 + grp;
         const bool on = i < N && nm[i];
         double g[3] = {0.0, 0.0, 0.0};
-        if (on) rs_node_grad(a.t, b, rs_x, nm, N, i, l, RS_GROUP, g);
+        if constexpr (FRAMED) {
+            if (on && !(fixed && fixed[i])) rs_node_grad(a.t, b, rs_x, nm, N, i, l, RS_GROUP, g, tau);
+        } else {
+            if (on) rs_node_grad(a.t, b, rs_x, nm, N, i, l, RS_GROUP, g);
+        }
 #pragma unroll
         for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -184,8 +241,9 @@ __global__ __launch_bounds__(256) void k_restrain_eps(RestrainArgs a) {
 
 // (U_obs, U_pair, U_anc) of the molecule b at positions x [N][3] (data units; global memory or LDS) into U, in every thread: a strided
 // double sum per thread, then guide_block_sum.  `red`: 4 * 3 doubles of LDS.  The one energy code of k_restraint_energy and k_steer_weigh.
+// `off`: the translation of the obstacle and anchor centres.
 HD_DEVINL void rs_energy_block(const RestraintTables& t, int b, const float* x, const uint8_t* nm, int N, double* red, int tid,
-                               double (&U)[3]) {
+                               double (&U)[3], const RsOffset off = RS_NO_OFFSET) {
     double u[3], c;
     U[0] = 0.0; U[1] = 0.0; U[2] = 0.0;
     const float* obs = t.obs + (size_t)(t.obs_rows == 1 ? 0 : b) * t.P * 5;
@@ -193,7 +251,9 @@ HD_DEVINL void rs_energy_block(const RestraintTables& t, int b, const float* x, 
         const int i = (int)(e / t.P), p = (int)(e - (long long)i * t.P);
         const float* o = obs + (size_t)p * 5;
         if (!nm[i] || !(o[3] > 0.f) || !(o[4] > 0.f)) continue;
-        U[0] += rs_obs_term(rs_dist(x, i, (double)o[0], (double)o[1], (double)o[2], u), (double)o[3], (double)o[4], c);
+        const double d = off.on ? rs_dist(x, i, (double)o[0] + off.x, (double)o[1] + off.y, (double)o[2] + off.z, u)
+                             : rs_dist(x, i, (double)o[0], (double)o[1], (double)o[2], u);
+        U[0] += rs_obs_term(d, (double)o[3], (double)o[4], c);
     }
     const size_t prow = (size_t)(t.pair_rows == 1 ? 0 : b) * t.Q;
     for (int q = tid; q < t.Q; q += 256) {
@@ -208,15 +268,28 @@ HD_DEVINL void rs_energy_block(const RestraintTables& t, int b, const float* x, 
         const float* af = t.anc_f + (arow + q) * 5;
         const int i = t.anc_idx[arow + q];
         if (i < 0 || i >= N || !nm[i] || !(af[4] > 0.f) || !(af[3] >= 0.f)) continue;
-        U[2] += rs_band_term(rs_dist(x, i, (double)af[0], (double)af[1], (double)af[2], u), -1.0, (double)af[3], (double)af[4], c);
+        const double d = off.on ? rs_dist(x, i, (double)af[0] + off.x, (double)af[1] + off.y, (double)af[2] + off.z, u)
+                             : rs_dist(x, i, (double)af[0], (double)af[1], (double)af[2], u);
+        U[2] += rs_band_term(d, -1.0, (double)af[3], (double)af[4], c);
     }
     guide_block_sum<3>(U, red, tid);
 }
 
+template <bool FRAMED>
 __global__ __launch_bounds__(256) void k_restraint_energy(RestraintEnergyArgs a) {
-    __shared__ double red[4 * 3];
+    __shared__ double red[4 * (FRAMED ? 7 : 3)];
     const int tid = threadIdx.x, b = blockIdx.x;
+    const float* x = a.x + (size_t)b * a.N * 3;
+    const uint8_t* nm = a.nm + (size_t)b * a.N;
     double U[3];
-    rs_energy_block(a.t, b, a.x + (size_t)b * a.N * 3, a.nm + (size_t)b * a.N, a.N, red, tid, U);
+    if constexpr (FRAMED) {
+        RsOffset tau;
+        rs_frame_shift(x, 3, a.x_known + (size_t)b * a.N * 3, 3, 1.0, nm, a.fixed + (size_t)b * a.N, a.N, red, tid, tau);
+        tau.on = true;                                  // (no fixed node: tau = 0)
+        rs_energy_block(a.t, b, x, nm, a.N, red, tid, U, tau);
+        if (a.shift && tid < 3) a.shift[(size_t)b * 3 + tid] = tid == 0 ? tau.x : tid == 1 ? tau.y : tau.z;
+    } else {
+        rs_energy_block(a.t, b, x, nm, a.N, red, tid, U);
+    }
     if (tid < 3) a.out[(size_t)b * 3 + tid] = U[tid];
 }

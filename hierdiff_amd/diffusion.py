@@ -204,6 +204,9 @@ class DiffusionQM9(_Base):
         self.restraint_scale = None
         self.restraint_schedule = "score"
         self.restraint_clip = None
+        # the frame the tables are read in: None / "model" (the model's, everywhere) or "known" (the known fragments' of
+        # sample_inpaint / sample_grow / inpaint_steps, which take restraints only then)
+        self.restraint_frame = None
         # steered sampling (hierdiff_amd/steering.py): defaults of the `particles` / `steer_scale` / `steer_ess` keywords.  particles of
         # None or 1, or a steer_scale of None or 0 = nothing changes.  `steer_last`: the `steering.Result` of the last steered call.
         self.particles = None
@@ -710,7 +713,7 @@ class DiffusionQM9(_Base):
         rr.rs.check_batch(B)
         import weakref
         rr.rs._model = weakref.ref(self)
-        rr.rs.attach(topo, rr.scale, float(self.norm_values[0]), dev, _stream(dev))
+        rr.rs.attach(topo, rr.scale, float(self.norm_values[0]), dev, _stream(dev), rr.frame)
 
     def _steer_open(self, handle, topo, tabs, st, reset: bool, dev):
         """Attach the steering of a resolved call (`steering.Steer`) to `topo` behind the rows of the path that `_path_tables` has
@@ -994,7 +997,7 @@ class DiffusionQM9(_Base):
                           solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                           keep_frames: Optional[int] = None, record: Optional[str] = None,
                           restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-                          particles=None, steer_scale=None, steer_ess=None, steer_schedule=None):
+                          particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None):
         """z_T -> (x, h) for given masks: draw z_T, T posterior steps, final decode.
 
         restraints / restraint_scale / restraint_schedule / restraint_clip (keyword-only; None: the model's attributes of the same
@@ -1140,7 +1143,7 @@ class DiffusionQM9(_Base):
                    guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                    solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                    restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-                   particles=None, steer_scale=None, steer_ess=None, steer_schedule=None):
+                   particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None):
         """Transitions k_lo .. k_hi-1 of `sample_from_masks`'s few-step loop on a given z [B,N,D] (normalised units, the state at
         path position k_lo); returns the state at position k_hi (default: the end of the path, z_0 before the decode).  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.
@@ -1454,7 +1457,7 @@ class DiffusionQM9(_Base):
                      raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                      solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                      restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-                     particles=None, steer_scale=None, steer_ess=None, steer_schedule=None):
+                     particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None):
         """Transitions k_lo .. k_hi-1 of `sample_from_latent`'s partial chain on a given z [B,N,D] (the state at path position k_lo);
         returns the state at position k_hi (default: the end, z_0 before the decode), as `path_steps` does for a full path.  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.  `raw_noises`: k_hi - k_lo injected
@@ -1475,7 +1478,7 @@ class DiffusionQM9(_Base):
                            solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                            keep_frames: Optional[int] = None, record: Optional[str] = None,
                            restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-                           particles=None, steer_scale=None, steer_ess=None, steer_schedule=None):
+                           particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None):
         """(x, h) from a state z [B,N,D] at the grid index `t_start` (default T; normalised units - what `diffuse` and `encode`
         return): the partial reverse chain on `paths.partial_path(T, t_start, steps, spacing, timesteps)` (default: every grid point
         below t_start) inside the library's loop (hd_sample_path), then the final decode of `sample_from_masks`.  `eta` defaults to
@@ -1707,10 +1710,18 @@ class DiffusionQM9(_Base):
 
     @torch.no_grad()
     def inpaint_steps(self, z, s_hi: int, s_lo: int, node_mask, fixed_mask, x_known, h_known, context=None, resamplings: int = 1,
-                      sample_id_base: int = 0, edge_mask=None):
+                      sample_id_base: int = 0, edge_mask=None, *, restraints=None, restraint_scale=None, restraint_schedule=None,
+                      restraint_clip=None, restraint_frame: Optional[str] = None):
         """The steps s = s_hi-1 ... s_lo of `sample_inpaint`'s loop on a given z_{s_hi} [B,N,D] (normalised units); returns z_{s_lo}.
-        Draws are keyed by the step, so a chain cut into pieces gives the bits of the whole."""
-        st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask)
+        Draws are keyed by the step, so a chain cut into pieces gives the bits of the whole.  restraint_frame="known" (or the
+        model's `restraint_frame`): the restraints of `sample_inpaint`, on the path loop; without it the restraint keywords and the
+        model's restraint attributes are ignored, as they always were."""
+        from . import restraints as _rs
+        pl = None
+        if _rs.check_frame(self, restraint_frame):
+            B, N = self._batch_of(node_mask)
+            pl = self._plan("inpaint_steps", "inpaint", B=B, N=N, guided=False, **given(locals()))
+        st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, pl)
         if tuple(z.shape) != (st.B, st.N, self.n_dims + self.in_node_nf) or not (0 <= s_lo <= s_hi <= self.T):
             raise ValueError("z must be [B, N, 3 + F] and 0 <= s_lo <= s_hi <= timesteps")
         z = z.detach().to(st.dev, torch.float32).clone().contiguous()
@@ -1724,7 +1735,8 @@ class DiffusionQM9(_Base):
                        steps: Optional[int] = None, eta: Optional[float] = None, spacing: Optional[str] = None,
                        timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                        solver: Optional[str] = None, keep_frames: Optional[int] = None, record: Optional[str] = None,
-                       restraints=None):
+                       restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
+                       restraint_frame: Optional[str] = None):
         """(x, h) on the device for molecules whose `fixed_mask` [B,N,1] nodes are known: `x_known` [B,N,3] / `h_known` [B,N,F] in
         data units (what `sample` returns; rows outside `fixed_mask` are ignored, the frame of the positions is free).  The free
         nodes are sampled around them by the replacement method, `resamplings` network calls per step (RePaint for > 1), inside
@@ -1736,9 +1748,18 @@ class DiffusionQM9(_Base):
         guidance_rescale: classifier-free guidance as in `sample_from_masks` (every round's network call is guided).
         solver="dpm2m" or "sde2m" (or the model's `sample_solver`) raises ValueError like eta < 1.  keep_frames / record: as in
         `sample_from_masks` - a third tensor chain [keep_frames, B, N, D]; a frame is the state behind its transition's last round
-        (known rows replaced), or that round's data prediction, and frame 0 the returned (x, h)."""
+        (known rows replaced), or that round's data prediction, and frame 0 the returned (x, h).
+        restraint_frame="known" (or the model's `restraint_frame`): restraints / restraint_scale / restraint_schedule / restraint_clip
+        as in `sample_from_masks`, with the tables read in the frame of `x_known` as given (hierdiff_amd/restraints.py, THE FRAME):
+        "grow this fragment without clashing with these protein atoms" in the pocket's own coordinates.  Free nodes only are pushed;
+        the update runs in every resampling round, behind guidance, on the path loop (the identity path where the keywords ask
+        for the plain loop).  The call then returns one more element, a dict with 'restraint_energy' [B,3] float64 (evaluated in
+        the known frame), 'frame_shift' [B,3] float64 (the translation tau of the returned x) and 'x_known_frame' [B,N,3] = x - tau,
+        the molecule in the coordinates of the input (known rows equal `x_known` up to fp32 rounding).  Without it restraints are
+        refused, as before: the model's frame moves with the known fragments."""
         from . import restraints as _rs
-        _rs.refuse(self, "sample_inpaint", restraints, ": inpainting re-centres on the known fragments, so its frame moves")
+        if not _rs.check_frame(self, restraint_frame):
+            _rs.refuse(self, "sample_inpaint", restraints, ": inpainting re-centres on the known fragments, so its frame moves")
         from . import steering as _st
         _st.refuse(self, "sample_inpaint")
         B, N = self._batch_of(node_mask)
@@ -1754,26 +1775,40 @@ class DiffusionQM9(_Base):
                 self._check_mean_zero(z[:, :, :self.n_dims], node_mask)
         else:
             z, chain = self._run(st, pl, z, 0, pl.K, noise, inp)
-        return self._decode(st, z, node_mask, edge_mask, False, int(sample_id_base), chain, (st.fm_u8, st.xk, st.hk))
+        got = self._decode(st, z, node_mask, edge_mask, False, int(sample_id_base), chain, (st.fm_u8, st.xk, st.hk))
+        rr = pl.restraints
+        if rr is None or not rr.frame:
+            return got
+        en, tau = rr.rs.energy(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0])),
+                               fixed_mask=st.fm_u8, x_known=st.xk, return_shift=True)
+        xkf = ((got[0].double() - tau[:, None, :]) * node_mask.to(st.dev, torch.float64)).to(torch.float32)
+        return tuple(got) + ({'restraint_energy': en, 'frame_shift': tau, 'x_known_frame': xkf},)
 
     @torch.no_grad()
     def sample_grow(self, known: Sequence[Dict[str, torch.Tensor]], sizes, device, context=None, resamplings: int = 1,
                     sample_id_base: int = 0, *, steps: Optional[int] = None, eta: Optional[float] = None,
                     spacing: Optional[str] = None, timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                     solver: Optional[str] = None, keep_frames: Optional[int] = None, record: Optional[str] = None,
-                    restraints=None):
+                    restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
+                    restraint_frame: Optional[str] = None):
         """List-level form of `sample_inpaint` in `sample`'s result format: `known[i]` = {'x': [k_i,3], 'h': [k_i,F]} are the fragments
         molecule i keeps (its first k_i rows in the result; k_i = 0 allowed), `sizes[i]` >= k_i its total number of fragments (one
         integer: that many for every molecule).  `context`: as in `sample`.  Returns [{'x': [n_i,3], 'h': [n_i,F] (, 'context')}] on
         the CPU.  steps / eta / spacing / timesteps: as in `sample_inpaint`.  keep_frames / record: every dict also holds 'chain_x'
-        [keep, n_i, 3], 'chain_h' [keep, n_i, F] and 'chain_t' [keep], as in `sample`."""
+        [keep, n_i, 3], 'chain_h' [keep, n_i, F] and 'chain_t' [keep], as in `sample`.  restraint_frame="known" with restraints /
+        restraint_scale (a float or a [len(known)] tensor) / restraint_schedule / restraint_clip: as in `sample_inpaint`, the tables
+        in the coordinates of the given fragments; every dict then also holds 'restraint_energy' [3] float64, 'frame_shift' [3]
+        float64 and 'x_known_frame' [n_i, 3]."""
         device = torch.device(device)
         from . import restraints as _rs
-        _rs.refuse(self, "sample_grow", restraints, ": inpainting re-centres on the known fragments, so its frame moves")
+        if not _rs.check_frame(self, restraint_frame):
+            _rs.refuse(self, "sample_grow", restraints, ": inpainting re-centres on the known fragments, so its frame moves")
         from . import steering as _st
         _st.refuse(self, "sample_grow")
         few = given(locals())
-        chain_t = self._plan("sample_grow", "inpaint", **few).chain_t                    # argument errors first
+        framed = _rs.check_frame(self, restraint_frame)
+        pl0 = self._plan("sample_grow", "inpaint", **(dict(B=len(known) or None) if framed else {}), **few)     # argument errors first
+        chain_t = pl0.chain_t
         num = len(known)
         if isinstance(sizes, (int, np.integer)):
             sizes = [int(sizes)] * num
@@ -1812,6 +1847,12 @@ class DiffusionQM9(_Base):
                 out[i]['context'] = ctx[i, :sizes[i]].clone()
         if chain_t is not None:
             self._chain_into(out, got[2], sizes, chain_t)
+        if pl0.restraints is not None:
+            info = {k: v.cpu() for k, v in got[-1].items()}
+            for i in range(num):
+                out[i]['restraint_energy'] = info['restraint_energy'][i].clone()
+                out[i]['frame_shift'] = info['frame_shift'][i].clone()
+                out[i]['x_known_frame'] = info['x_known_frame'][i, :sizes[i]].clone()
         return out
 
     @torch.no_grad()
@@ -1821,7 +1862,7 @@ class DiffusionQM9(_Base):
                solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                keep_frames: Optional[int] = None, record: Optional[str] = None,
                restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-               particles=None, steer_scale=None, steer_ess=None, steer_schedule=None):
+               particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None):
         """diffusion_qm9.py:347-395: list of {'x': [n_i,3], 'h': [n_i,8], ('context': [n_i,1])} on the CPU.
         steps / eta / spacing / timesteps: few-step sampling, see `sample_from_masks`; guidance_scale (a float or a
         [num_samples] tensor) / guidance_context ([num_samples, n_max, C]) / guidance_rescale: classifier-free guidance, ibid.;

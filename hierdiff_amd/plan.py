@@ -16,7 +16,7 @@ from . import guidance as _guidance, paths, restraints as _rs, steering as _stee
 #: the sampling keywords of the entry points; the list forms (`sample`, `sample_batches`, `vary`, the EDM signature) forward those given
 KEYWORDS = ("steps", "eta", "spacing", "timesteps", "guidance_scale", "guidance_context", "guidance_rescale", "solver",
             "lower_order_final", "keep_frames", "record", "restraints", "restraint_scale", "restraint_schedule", "restraint_clip",
-            "particles", "steer_scale", "steer_ess", "steer_schedule")
+            "particles", "steer_scale", "steer_ess", "steer_schedule", "restraint_frame")
 
 
 def given(values: dict) -> dict:
@@ -101,9 +101,10 @@ def plan(model, what: str, kind: str = "full", *, t_start=None, pocket=None, inj
          N: Optional[int] = None, force_path: bool = False, guided: bool = True, steps=None, eta=None, spacing=None, timesteps=None, guidance_scale=None,
          guidance_context=None, guidance_rescale=None, solver=None, lower_order_final=None, keep_frames=None, record=None,
          restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-         particles=None, steer_scale=None, steer_ess=None, steer_schedule=None) -> Plan:
+         particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None) -> Plan:
     """The `Plan` of the call `what`.  `kind`: "full" (the chain from T), "latent" (from `t_start`) or "inpaint" (from T, ancestral
-    steps only; it takes no restraints - its callers refuse them).  `pocket`: the fixed residues of the call, if any; `injected`: the
+    steps only; it takes restraints only with restraint_frame="known" - its callers refuse them otherwise - and then always runs on
+    a path; "known" with restraints in any other kind is a ValueError).  `pocket`: the fixed residues of the call, if any; `injected`: the
     caller brings its own noise; `B` / `N`: the batch, where the caller knows it (shapes of per-molecule scales are checked);
     `force_path`: never the plain loop; `guided=False`: the call takes no guidance (`inpaint_steps`).
 
@@ -123,9 +124,17 @@ def plan(model, what: str, kind: str = "full", *, t_start=None, pocket=None, inj
     gd = _guidance.resolve(model, guidance_scale, guidance_context, guidance_rescale, B, N, what, pocket, needs_noise) if guided else None
     rr = None
     steered = _steering.wanted(model, particles, steer_scale)
+    frame = _rs.check_frame(model, restraint_frame)
     if kind != "inpaint":
         rr = _rs.resolve(model, restraints, restraint_scale, restraint_schedule, restraint_clip, B, what, pocket, needs_noise,
                          steered=steered)
+        if rr is not None and frame:
+            raise ValueError(f"{what}: restraint_frame='known' reads the tables in the frame of an inpainting call's known fragments; "
+                             "it acts in sample_inpaint / sample_grow / inpaint_steps only")
+    elif frame:
+        rr = _rs.resolve(model, restraints, restraint_scale, restraint_schedule, restraint_clip, B, what, pocket, needs_noise)
+        if rr is not None:
+            rr.frame = frame
     code = None
     if keep_frames is None:
         if record is not None:

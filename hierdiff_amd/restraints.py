@@ -7,9 +7,23 @@ prediction (hd_restraint_attach / hd_set_restraint / k_restrain_eps, include/hie
     U_pair = 1/2 sum_q k_q (max(0, d - hi)^2 + max(0, lo - d)^2),  d = |x_i - x_j|     keep two nodes lo .. hi apart
     U_anc  = 1/2 sum_a k_a max(0, |x_i - a| - r)^2                                     put a node within r of a point
 
-THE FRAME.  Coordinates are x = norm_values[0] * z_x in the MODEL'S frame, which has the centre of mass of the molecule's valid nodes
-at the origin - during the whole chain and in the result.  Obstacles and anchors are given in that frame: place the pocket relative
-to where the ligand's centre should sit.  Nothing here translates them.
+THE FRAME.  Coordinates are x = norm_values[0] * z_x.  There are two frames the tables can be read in (`restraint_frame`):
+
+  "model" (the default, everywhere)   the MODEL'S frame, which has the centre of mass of the molecule's valid nodes at the origin -
+      during the whole chain and in the result.  Obstacles and anchors are given in that frame: place the pocket relative to where
+      the ligand's centre should sit.  Nothing translates them.
+  "known" (sample_inpaint / sample_grow / inpaint_steps only)   the frame of the call's `x_known`, as given - the coordinates the
+      scaffold was cut out in, a pocket's for instance.  Inpainting returns the known fragments as a pure translation of the input,
+      so it is the one mode with an absolute frame.  At every transition, with F the molecule's valid fixed nodes,
+          tau = mean_F(x^0) - mean_F(x_known)         the position of node i in the user's coordinates is x^0_i - tau
+      and the obstacle and anchor terms are evaluated on x^0_i - (y + tau) (pairs do not see tau).  The gradient is taken with tau
+      held constant and for FREE nodes only: a fixed node's step is 0 by definition - the block is the frame, and its own clashes
+      are the user's input; a pair between a free and a fixed node acts on the free one.  The mean of the clipped steps over ALL valid
+      nodes is then removed from every valid node (fixed nodes receive -mean), so eps^_x stays mean-free as the chain requires; behind
+      the posterior step and the replacement - which puts the block where the generated fixed rows' centre went - a free node has
+      moved relative to the block by exactly its own step times the update's coefficient.  A molecule without fixed nodes has
+      tau = 0: today's update.  Results carry 'frame_shift' (tau of the returned x) and 'x_known_frame' = x - tau, the molecule in
+      the coordinates of the input.
 
 A pair or anchor row whose node index is -1 (padding), >= the molecule's size or masked is inactive - documented behaviour, not an
 error, because `sample` draws the sizes.  A term at distance exactly 0 contributes no gradient.
@@ -25,6 +39,26 @@ import numpy as np
 import torch
 
 SCHEDULES = ("score", "sigma")
+FRAMES = ("model", "known")
+
+
+def check_frame(model, frame) -> int:
+    """`restraint_frame` (None: the model's attribute; None there: "model") -> the library's code, 0 "model" or 1 "known"."""
+    frame = getattr(model, "restraint_frame", None) if frame is None else frame
+    if frame is None:
+        return 0
+    if not isinstance(frame, str) or frame not in FRAMES:
+        raise ValueError(f"restraint_frame must be one of {FRAMES} (or None: the model's), got {frame!r}")
+    return FRAMES.index(frame)
+
+
+def frame_shift(x: torch.Tensor, node_mask: torch.Tensor, fixed_mask: torch.Tensor, x_known: torch.Tensor) -> torch.Tensor:
+    """[B, 3] float64 tau = mean_F(x) - mean_F(x_known) over the valid fixed nodes F of every molecule (0 where there is none)."""
+    B, N = int(x.shape[0]), int(x.shape[1])
+    f = (fixed_mask.reshape(B, N).bool() & node_mask.reshape(B, N).bool()).to(x.device).to(torch.float64).unsqueeze(-1)
+    nf = f.sum(1)
+    tau = ((x.detach().double() * f).sum(1) - (x_known.detach().to(x.device).double() * f).sum(1)) / nf.clamp(min=1.0)
+    return torch.where(nf > 0, tau, torch.zeros_like(tau))
 
 
 def _table(v, width: int, name: str) -> Optional[torch.Tensor]:
@@ -118,8 +152,9 @@ class Restraints:
         return cls(d.get("obstacles"), d.get("pairs"), d.get("anchors"))
 
     # ------------------------------------------------------------------ device side
-    def attach(self, topo, scale: torch.Tensor, nv0: float, dev, stream) -> None:
-        """hd_restraint_attach: the tables and the scales [1] or [B] into the topology's buffers (stream-ordered copies)."""
+    def attach(self, topo, scale: torch.Tensor, nv0: float, dev, stream, frame: int = 0) -> None:
+        """hd_restraint_attach: the tables and the scales [1] or [B] into the topology's buffers (stream-ordered copies).  `frame` 1:
+        then hd_restraint_frame - the tables are in the frame of an inpainting call's known fragments (attaching resets to 0)."""
         from . import _lib
         P, Q, A = self.sizes
         t = [x.to(dev).contiguous() for x in (self.obs, self.pair_idx, self.pair_f, self.anc_idx, self.anc_f, scale.to(torch.float32))]
@@ -128,22 +163,38 @@ class Restraints:
             topo.ptr, t[0].data_ptr() if P else None, ro, P, t[1].data_ptr() if Q else None, t[2].data_ptr() if Q else None, rp, Q,
             t[3].data_ptr() if A else None, t[4].data_ptr() if A else None, ra, A, t[5].data_ptr(), int(t[5].numel()), float(nv0),
             stream), "hd_restraint_attach")
+        if frame:
+            _lib.check(_lib.load().hd_restraint_frame(topo.ptr, int(frame)), "hd_restraint_frame")
 
     @staticmethod
     def detach(topo) -> None:
         from . import _lib
         _lib.check(_lib.load().hd_restraint_detach(topo.ptr), "hd_restraint_detach")
 
-    def energy(self, x: torch.Tensor, node_mask: torch.Tensor, model=None, _attach=None) -> torch.Tensor:
+    def energy(self, x: torch.Tensor, node_mask: torch.Tensor, model=None, _attach=None, fixed_mask=None, x_known=None,
+               return_shift: bool = False):
         """[B, 3] float64 (U_obs, U_pair, U_anc) of positions x [B, N, 3] in data units under node_mask [B, N, 1].  On a device the HIP
         kernel evaluates it (k_restraint_energy; `model`: the DiffusionQM9 whose handle and topology cache are used); on the CPU the
-        same formulas in torch float64."""
+        same formulas in torch float64.  fixed_mask [B, N, 1] and x_known [B, N, 3] (together): the tables are in the frame of
+        `x_known` - the energy of x - tau, tau = mean_F(x) - mean_F(x_known) over the valid fixed nodes (k_restraint_energy<true>);
+        `return_shift`: (U, tau [B, 3] float64)."""
         B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
         if tuple(x.shape) != (B, N, 3):
             raise ValueError(f"x must be [{B}, {N}, 3], got {tuple(x.shape)}")
+        if (fixed_mask is None) != (x_known is None):
+            raise ValueError("energy: fixed_mask and x_known go together")
+        framed = fixed_mask is not None
+        if return_shift and not framed:
+            raise ValueError("energy: return_shift needs fixed_mask and x_known")
+        if framed and (fixed_mask.numel() != B * N or tuple(x_known.shape) != (B, N, 3)):
+            raise ValueError(f"energy: fixed_mask must hold {B} x {N} entries and x_known be [{B}, {N}, 3]")
         self.check_batch(B, "energy")
         if x.device.type != "cuda":
-            return energy_terms(self, x.detach().double(), node_mask)
+            if not framed:
+                return energy_terms(self, x.detach().double(), node_mask)
+            tau = frame_shift(x, node_mask, fixed_mask, x_known)
+            U = energy_terms(self, x.detach().double() - tau[:, None, :], node_mask)
+            return (U, tau) if return_shift else U
         model = model if model is not None else (self._model() if getattr(self, "_model", None) is not None else None)
         if model is None:
             raise ValueError("energy on a device needs model= (the DiffusionQM9 that owns the library handle) unless these "
@@ -161,10 +212,18 @@ class Restraints:
         scale, nv0 = (torch.ones(1), 1.0) if _attach is None else _attach
         self.attach(topo, scale, nv0, dev, _stream(dev))
         try:
-            _lib.check(_lib.load().hd_restraint_energy(h, topo.ptr, xs.data_ptr(), out.data_ptr(), _stream(dev)), "hd_restraint_energy")
+            if framed:
+                tau = torch.empty((B, 3), device=dev, dtype=torch.float64)
+                fm = (fixed_mask.to(dev).reshape(B * N) != 0).to(torch.uint8).contiguous()
+                xk = x_known.detach().to(dev, torch.float32).contiguous()
+                _lib.check(_lib.load().hd_restraint_energy_framed(h, topo.ptr, xs.data_ptr(), fm.data_ptr(), xk.data_ptr(),
+                                                                  out.data_ptr(), tau.data_ptr(), _stream(dev)),
+                           "hd_restraint_energy_framed")
+            else:
+                _lib.check(_lib.load().hd_restraint_energy(h, topo.ptr, xs.data_ptr(), out.data_ptr(), _stream(dev)), "hd_restraint_energy")
         finally:
             self.detach(topo)
-        return out
+        return (out, tau) if return_shift else out
 
 
 def energy_terms(rs: Restraints, x: torch.Tensor, node_mask: torch.Tensor) -> torch.Tensor:
@@ -257,8 +316,9 @@ def lambda_rows(gamma, path: Sequence[int], schedule="score", clip=None, nv0: fl
 class Resolved:
     """A restrained call: the tables, the scales float32 [1] or [B] (CPU), the schedule and the clip."""
 
-    def __init__(self, rs: Restraints, scale: torch.Tensor, schedule, clip: float):
+    def __init__(self, rs: Restraints, scale: torch.Tensor, schedule, clip: float, frame: int = 0):
         self.rs, self.scale, self.schedule, self.clip = rs, scale, schedule, clip
+        self.frame = frame                       # 0: the model's frame; 1: the known fragments' (inpainting plans only)
 
     def key(self):
         s = self.schedule

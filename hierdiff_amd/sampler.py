@@ -222,6 +222,10 @@ def parse_args(argv=None):
                          "into every transition.  Combines with everything --steps combines with (--eta / --spacing / --solver, "
                          "--guidance, --chain, --vary) except --known / --grow.  Mechanism only: which scale, schedule and clip help "
                          "is for you to validate")
+    ap.add_argument("--restraint-frame", choices=["model", "known"], default=None,
+                    help="with --restraints: the frame the tables are in - the model's (default: the molecule's centre of mass at the "
+                         "origin) or, with --known / --grow only, the coordinates of the known fragments as given in FILE (a pocket's, "
+                         "for instance: grow without clashing with protein atoms); known makes --restraints legal with --known / --grow")
     ap.add_argument("--restraint-scale", type=float, default=None, metavar="S", help="with --restraints: the scale (default 1)")
     ap.add_argument("--restraint-schedule", choices=["score", "sigma"], default=None,
                     help="with --restraints: the weight of transition k, nv0 sigma_t / alpha_t (score, default) or sigma_t")
@@ -254,11 +258,17 @@ def parse_args(argv=None):
         if args.batch_size % args.particles or (args.vary is not None and args.variants % args.particles):
             ap.error("--batch-size (and with --vary, --variants) must be a multiple of --particles")
     if args.restraints is None and (args.restraint_scale is not None or args.restraint_schedule is not None
-                                    or args.restraint_clip is not None):
-        ap.error("--restraint-scale / --restraint-schedule / --restraint-clip need --restraints")
+                                    or args.restraint_clip is not None or args.restraint_frame is not None):
+        ap.error("--restraint-scale / --restraint-schedule / --restraint-clip / --restraint-frame need --restraints")
     if args.restraints is not None:
-        if args.known is not None or args.grow is not None:
-            ap.error("--restraints does not combine with --known / --grow (inpainting re-centres on the known fragments)")
+        if args.restraint_frame == "known":
+            if args.known is None or args.grow is None:
+                ap.error("--restraint-frame known needs --known / --grow (the frame of the known fragments)")
+            if args.particles is not None:
+                ap.error("--restraint-frame known does not combine with --particles (inpainting is not steered)")
+        elif args.known is not None or args.grow is not None:
+            ap.error("--restraints does not combine with --known / --grow (inpainting re-centres on the known fragments; "
+                     "--restraint-frame known reads the tables in the fragments' own coordinates)")
         if args.score is not None or args.interpolate is not None:
             ap.error("--restraints does not combine with --score / --interpolate")
         if args.restraint_clip is not None and not args.restraint_clip > 0.0:
@@ -380,6 +390,8 @@ def main(argv=None) -> int:
         from .restraints import Restraints
         chain.update(restraints=Restraints.from_json(args.restraints), restraint_scale=args.restraint_scale,
                      restraint_schedule=args.restraint_schedule, restraint_clip=args.restraint_clip)
+        if args.restraint_frame is not None:
+            chain.update(restraint_frame=args.restraint_frame)
     if args.particles is not None:
         chain.update(particles=args.particles, steer_scale=args.steer_scale, steer_ess=args.steer_ess)
 

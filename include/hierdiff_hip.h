@@ -421,7 +421,7 @@ long long hd_chain_graph_builds(const hd_topology* topo);
  * hd_restraint_attach: copies the tables and scale[scale_rows] (stream-ordered) into buffers the topology owns; from now on
  *   hd_sample_path and hd_sample_path_guided (fixed_mask == NULL) on this topology are restrained; hd_sample_path_inpaint and
  *   guided calls with a fixed_mask are HD_E_INVALID while attached (inpainting re-centres on the known fragments: its frame
- *   moves), as is mol_shape < N.  hd_sample_loop* ignore attached restraints, as they ignore chain sinks.
+ *   moves; hd_restraint_frame below is the way to restrain them), as is mol_shape < N.  hd_sample_loop* ignore attached restraints, as they ignore chain sinks.
  *   HD_E_INVALID: a row count other than 1 or B, negative P / Q / A, nv0 not positive, N * 3 floats beyond one workgroup's LDS.
  * hd_restraint_detach: the launches, graphs and keys are again exactly those of a topology that never had restraints.
  *   use_graph    the restrained transition lives in the slot of its unrestrained kind (plain, guided, recording) under a key that
@@ -431,7 +431,26 @@ long long hd_chain_graph_builds(const hd_topology* topo);
  *                outgrows its buffer, another row count or nv0 rebuild it once.
  * hd_restrain_eps: the single update above on given tensors with a host row4; out may be eps itself, nothing else may overlap.
  * hd_restraint_energy: out3[B][3] = (U_obs, U_pair, U_anc) in double for positions x[B][N][3] (fp32, data units) under the
- *   attached tables and the topology's mask.  Both are stream-ordered and need attached restraints (HD_E_STATE otherwise). */
+ *   attached tables and the topology's mask.  Both are stream-ordered and need attached restraints (HD_E_STATE otherwise).
+ * THE KNOWN FRAGMENTS' FRAME (additive): hd_restraint_frame(topo, 1) reads the attached tables in the coordinates of the xh_known of
+ *   an inpainting call, the one mode whose known rows come back as a pure translation of the input.  With F the valid fixed nodes
+ *   of a molecule and xk = nv0 xh_known_x (as uploaded, not centred):
+ *     tau     = mean_F(x^0) - mean_F(xk)                         double; no fixed node: tau = 0 and every node is free (the plain update)
+ *     U       = the three energies with the obstacle and anchor centres at y + tau; pairs do not see tau
+ *     Delta_i = clip(s_b lambda_k dU/dx_i), tau held constant    free valid nodes only; a fixed node's Delta is 0 (the block is the
+ *                                                                frame, its own clashes are the caller's input); a pair between a free
+ *                                                                and a fixed node acts on the free one
+ *     eps_x,i += Delta_i - mean over ALL valid nodes of Delta    fixed nodes receive -mean: eps_x stays mean-free, and behind the
+ *                                                                posterior step and the replacement a free node has moved relative
+ *                                                                to the block by its own Delta_i times the step's coefficient
+ *   Frame 0 is the model's frame; hd_restraint_attach resets to it.  HD_E_STATE: no restraints attached.  While frame 1 is set,
+ *   hd_sample_path_inpaint and guided calls with a fixed_mask run the framed update (k_restrain_eps<true>) in every resampling round,
+ *   behind guidance; calls without fixed fragments and topologies with steering attached are HD_E_INVALID.  The frame is part of the
+ *   graph key: switching it rebuilds the captured transition once, re-attaching tables of the same sizes does not.
+ * hd_restrain_eps_framed: the single framed update on given tensors (fixed_mask u8 [B*N], xh_known [B][N][D] normalised); the
+ *   aliasing rules of hd_restrain_eps, and out may not overlap xh_known.  Independent of hd_restraint_frame.
+ * hd_restraint_energy_framed: out3 as hd_restraint_energy with tau = mean_F(x) - mean_F(x_known) of the given data-unit
+ *   x / x_known [B][N][3]; shift3 [B][3] double receives tau (NULL: not wanted). */
 int hd_set_restraint(hd_handle* h, int K, const float* rows4);
 int hd_restraint_attach(hd_topology* topo, const float* obs, int obs_rows, int P, const int* pair_idx, const float* pair_f,
                         int pair_rows, int Q, const int* anc_idx, const float* anc_f, int anc_rows, int A, const float* scale,
@@ -439,6 +458,11 @@ int hd_restraint_attach(hd_topology* topo, const float* obs, int obs_rows, int P
 int hd_restraint_detach(hd_topology* topo);
 int hd_restrain_eps(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4, float* out, void* stream);
 int hd_restraint_energy(hd_handle* h, hd_topology* topo, const float* x, double* out3, void* stream);
+int hd_restraint_frame(hd_topology* topo, int frame);
+int hd_restrain_eps_framed(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4,
+                           const uint8_t* fixed_mask, const float* xh_known, float* out, void* stream);
+int hd_restraint_energy_framed(hd_handle* h, hd_topology* topo, const float* x, const uint8_t* fixed_mask, const float* x_known,
+                               double* out3, double* shift3, void* stream);
 
 /* ---- Steered sampling (ABI 12, additive; no reference counterpart): sequential Monte-Carlo steering of a restrained path loop.
  * The batch is G groups of P rows (particles); group g owns rows g P .. g P + P - 1, which the CALLER guarantees to have equal

@@ -1,0 +1,455 @@
+"""GPU tier (-m gpu) of restraints in the known fragments' frame: hd_restrain_eps_framed and hd_restraint_energy_framed against the
+float64 restatement of tests/restraint_frame_reference.py, restrained inpainting chains (`sample_inpaint(..., restraint_frame=
+"known")`) against the inpainting chain with the generator's host twin and the framed update on eps^, and the contracts of the
+device path: graph replay, re-attaching, a zero scale, batch independence, chain cuts, refusals.
+
+Bars.  hd_restrain_eps_framed: the element-wise bar of tests/sampling_reference.py - every element within 8 * 2^-23 of the sum of
+the absolute values of its terms, the obstacle and anchor terms counting |mean_F x^0| + |mean_F xk| too.  hd_restraint_energy_framed:
+1e-12 of the sum of the absolute values of its terms, as hd_restraint_energy; tau: 1e-12 of mean_F|x| + mean_F|x_known|.  Chains:
+rel-L2 < 1e-4 per state (tests/helpers.py REL_L2_TOL).  Measured figures are printed.
+Shapes: B = 5 molecules of N in {5, 33} nodes at D in {4, 11}; chains at T = 8 on the models of tests/test_gpu_restraint.py."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from hierdiff_amd import _lib, paths
+from hierdiff_amd.restraints import Restraints
+from oracle import egnn_oracle as orc
+from tests import edit_reference as er
+from tests import guidance_reference as gr
+from tests import restraint_frame_reference as fr
+from tests import restraint_reference as rr
+from tests import sampling_reference as sref
+from tests.helpers import REL_L2_TOL, rel_l2
+from tests.test_gpu_restraint import BOTH, DEV, T, Bare, batch_for, dev, fresh, model_for, stream
+from tests.test_inpaint_cpu import SEED, gamma_grid_fp64
+
+pytestmark = pytest.mark.gpu
+
+
+# ----------------------------------------------------------------------------- the kernels, on a bare handle (any D)
+
+def u8(mask):
+    return dev(mask.reshape(-1).to(torch.uint8)).contiguous()
+
+
+def run_framed(bare, rs, c, row, alias):
+    rs.attach(bare, c.scale, c.nv0, torch.device(DEV), stream())
+    zd, ed, kd, fd = dev(c.z).contiguous(), dev(c.eps).contiguous(), dev(c.known).contiguous(), u8(c.fm)
+    out = ed if alias else torch.full_like(ed, 7.0)
+    rc = bare.lib.hd_restrain_eps_framed(bare.h, bare.topo, zd.data_ptr(), ed.data_ptr(), (C.c_float * 4)(*row), fd.data_ptr(),
+                                         kd.data_ptr(), out.data_ptr(), stream())
+    assert rc == 0, bare.lib.hd_last_error()
+    return out.cpu()
+
+
+def run_plain(bare, rs, c, row):
+    rs.attach(bare, c.scale, c.nv0, torch.device(DEV), stream())
+    zd, ed = dev(c.z).contiguous(), dev(c.eps).contiguous()
+    out = torch.full_like(ed, 7.0)
+    assert bare.lib.hd_restrain_eps(bare.h, bare.topo, zd.data_ptr(), ed.data_ptr(), (C.c_float * 4)(*row), out.data_ptr(), stream()) == 0
+    return out.cpu()
+
+
+@pytest.mark.parametrize("N,D", [(5, 4), (5, 11), (33, 4), (33, 11)])
+def test_restrain_eps_framed_against_float64(N, D):
+    c = fr.kernel_case(N, D)
+    bare = Bare(D, c.nm)
+    valid, fixed = c.nm.numpy(), (c.fm & c.nm).numpy()
+    e = c.eps.numpy()
+    worst_all, moved, cases = 0.0, 0, 0
+    try:
+        for (P, Q, A) in fr.PQA:
+            for per in (False, True):
+                rs = fr.framed_tables(c.B, N, P, Q, A, seed=P + 10 * Q + 100 * A + int(per), per_molecule=per)
+                grad = fr.framed_grad(rs, c.z, c.eps, c.nm, c.fm, c.known, 0.8, 0.6, c.nv0)
+                for clip in (math.inf, 0.2):
+                    row = (0.8, 0.6, 0.75, clip)
+                    ref, mag, _ = fr.restrain_framed_ref(rs, c.z, c.eps, c.nm, c.fm, c.known, c.scale, row, c.nv0, grad=grad)
+                    got = run_framed(bare, rs, c, row, alias=False)
+                    ali = run_framed(bare, rs, c, row, alias=True)
+                    assert torch.equal(got, ali)
+                    bound = sref.BOUND * sref.U * mag
+                    err = np.abs(got.double().numpy() - ref)
+                    ratio = float((err / np.maximum(bound, 1e-300)).max())
+                    worst_all = max(worst_all, ratio)
+                    print(f"hd_restrain_eps_framed N={N} D={D} P={P} Q={Q} A={A} {'rows' if per else 'shared'} clip={clip}: "
+                          f"worst err / bound {ratio:.3f}")
+                    assert (err <= bound).all(), (P, Q, A, per, clip, ratio)
+                    g_ = got.numpy()
+                    assert (g_[:, :, 3:] == e[:, :, 3:]).all() and (g_[~valid] == e[~valid]).all()
+                    assert (g_[2] == e[2]).all()              # every valid node fixed: eps^ unchanged, bit for bit
+                    assert (g_[4] == e[4]).all()              # one valid node: the projection removes its whole step
+                    plain = run_plain(bare, rs, c, row).numpy()
+                    assert (g_[1].view(np.uint32) == plain[1].view(np.uint32)).all()      # no fixed node: the plain update's bits
+                    for b in (0, 3):                          # the block moves as one
+                        dl = (got.double().numpy() - c.eps.double().numpy())[b][fixed[b]][:, :3]
+                        bb = bound[b][fixed[b]][:, :3]
+                        assert (np.abs(dl - dl[0]) <= bb + bb[0]).all(), (b, P, Q, A)
+                    cases += 1
+                    moved += int(not (g_[[0, 3], :, :3] == e[[0, 3], :, :3]).all())
+        # lambda = 0 and s_b = 0: bit-identical, aliased or not; satisfied restraints leave eps^'s bits (-0.0 included)
+        rs = fr.framed_tables(c.B, N, 7, 3, 2, seed=5, per_molecule=True)
+        keep = c.scale
+        for sc, row in ((keep, (0.8, 0.6, 0.0, math.inf)), (torch.zeros(5), (0.8, 0.6, 0.75, 0.2)), (torch.zeros(1), (0.8, 0.6, 0.75, 0.2))):
+            c.scale = sc
+            for alias in (False, True):
+                assert torch.equal(run_framed(bare, rs, c, row, alias), c.eps)
+        c.scale = keep
+        sat = Restraints(obstacles=[[500.0, 0, 0, 1.0, 5.0]], pairs=[[0, 1, 0.0, 1e6, 5.0]], anchors=[[0, 0, 0, 0, 1e6, 5.0]])
+        e0 = c.eps.clone()
+        e0[0, 0, 0] = -0.0
+        c.eps = e0
+        out = run_framed(bare, sat, c, (0.8, 0.6, 0.75, math.inf), False)
+        assert (out.numpy().view(np.uint32) == e0.numpy().view(np.uint32)).all()
+        # argument errors
+        lib, r4 = bare.lib, (C.c_float * 4)(0.8, 0.6, 0.75, 0.2)
+        zd, ed, kd, fd = dev(c.z).contiguous(), dev(c.eps).contiguous(), dev(c.known).contiguous(), u8(c.fm)
+        args = lambda out, row=r4, f=fd, k=kd: (bare.h, bare.topo, zd.data_ptr(), ed.data_ptr(), row, None if f is None else f.data_ptr(),
+                                                None if k is None else k.data_ptr(), out.data_ptr(), stream())
+        assert lib.hd_restrain_eps_framed(*args(zd)) == -1 and b"overlap z" in lib.hd_last_error()
+        assert lib.hd_restrain_eps_framed(*args(kd)) == -1 and b"overlap xh_known" in lib.hd_last_error()
+        assert lib.hd_restrain_eps_framed(*args(ed, f=None)) == -1
+        assert lib.hd_restrain_eps_framed(*args(ed, k=None)) == -1
+        assert lib.hd_restrain_eps_framed(*args(ed, row=(C.c_float * 4)(0.0, 0.6, 1, 1))) == -1
+        assert lib.hd_restraint_detach(bare.topo) == 0
+        assert lib.hd_restrain_eps_framed(*args(ed)) == -4
+        assert lib.hd_restraint_frame(bare.topo, 1) == -4      # no restraints attached
+        print(f"hd_restrain_eps_framed N={N} D={D}: worst err / bound over all cases {worst_all:.3f}; eps moved in {moved} of {cases}")
+        assert 2 * moved >= cases                              # the cases are not no-ops
+    finally:
+        bare.close()
+
+
+@pytest.mark.parametrize("N", [5, 33])
+def test_restraint_energy_framed_against_float64(N):
+    c = fr.kernel_case(N, 11)
+    bare = Bare(11, c.nm)
+    g = torch.Generator().manual_seed(N)
+    x = (torch.randn(c.B, N, 3, generator=g) * 1.5).contiguous()
+    xd, kd, fd = dev(x), dev(c.x_known).contiguous(), u8(c.fm)
+    try:
+        for (P, Q, A) in fr.PQA:
+            for per in (False, True):
+                rs = fr.framed_tables(c.B, N, P, Q, A, seed=P + 10 * Q + 100 * A + int(per), per_molecule=per)
+                rs.attach(bare, torch.ones(1), 1.0, torch.device(DEV), stream())
+                out = torch.full((c.B, 3), -1.0, device=DEV, dtype=torch.float64)
+                sh = torch.full((c.B, 3), -1.0, device=DEV, dtype=torch.float64)
+                rc = bare.lib.hd_restraint_energy_framed(bare.h, bare.topo, xd.data_ptr(), fd.data_ptr(), kd.data_ptr(), out.data_ptr(),
+                                                         sh.data_ptr(), stream())
+                assert rc == 0, bare.lib.hd_last_error()
+                U, mag, _, _, tau = fr.framed_energy_grad(rs, x.numpy(), c.x_known.numpy(), c.nm, c.fm)
+                _, tmag = fr.frame_shift_ref(x.numpy(), c.x_known.numpy(), c.nm, c.fm)
+                err, terr = np.abs(out.cpu().numpy() - U), np.abs(sh.cpu().numpy() - tau)
+                print(f"hd_restraint_energy_framed N={N} P={P} Q={Q} A={A} {'rows' if per else 'shared'}: worst err / (1e-12 sum|terms|) "
+                      f"{float((err / np.maximum(1e-12 * mag, 1e-300)).max()):.3g}, tau {float((terr / np.maximum(1e-12 * tmag, 1e-300)).max()):.3g}")
+                assert (terr <= 1e-12 * tmag).all()
+                assert (err <= 1e-12 * mag).all()
+                assert (sh.cpu().numpy()[[1, 4]] == 0).all()   # no fixed node: no shift
+                # shift3 may be NULL
+                out2 = torch.full_like(out, -1.0)
+                assert bare.lib.hd_restraint_energy_framed(bare.h, bare.topo, xd.data_ptr(), fd.data_ptr(), kd.data_ptr(), out2.data_ptr(),
+                                                           None, stream()) == 0
+                assert torch.equal(out, out2)
+        assert bare.lib.hd_restraint_detach(bare.topo) == 0
+        assert bare.lib.hd_restraint_energy_framed(bare.h, bare.topo, xd.data_ptr(), fd.data_ptr(), kd.data_ptr(), out.data_ptr(), None,
+                                                   stream()) == -4
+    finally:
+        bare.close()
+
+
+# ----------------------------------------------------------------------------- chains
+
+def chain_case(mols=(7, 4, 1), C_=0, seed=3):
+    """The molecules of tests/test_gpu_restraint.py with their first rows fixed (3, 2, none), known positions around fr.CENTRE."""
+    _, _, nm, em, ctx = batch_for(tuple(mols), C_)
+    B, N = nm.shape[:2]
+    fm = torch.zeros(B, N, 1, dtype=torch.bool)
+    for b, k in enumerate((3, 2, 0, 2)[:B]):
+        fm[b, :k] = True
+    fm &= nm
+    g = torch.Generator().manual_seed(seed)
+    xk = (torch.tensor(fr.CENTRE) + torch.randn(B, N, 3, generator=g)) * fm
+    hk = torch.randn(B, N, 8, generator=g) * fm
+    return nm, em, ctx, fm, xk.contiguous(), hk.contiguous()
+
+
+def chain_tables(N, xk, fm, shift=0.0, P=2, rows=False):
+    """Around the known fragments, in THEIR coordinates: a wide obstacle on the centre of molecule 0's block (free nodes grow out of
+    it), a small one beside it, a pair between a fixed and a free node, one between free nodes, one out of range, an anchor."""
+    c0 = (xk[0] * fm[0]).sum(0) / fm[0].sum()
+    obs = [[float(c0[0]) + shift, float(c0[1]), float(c0[2]), 3.0, 2.0], [float(c0[0]) - 1.0, float(c0[1]) + 1.0 + shift, float(c0[2]), 1.0, 1.0]]
+    obs += [[float(c0[0]) + 3.0 + p, shift, 0.0, 1.0, 1.0] for p in range(P - 2)]
+    pairs = [[0, 3, 2.0 + shift, 2.5 + shift, 1.0], [2, 3, 0.0, 0.5, 1.0], [1, N + 3, 0.0, 1.0, 1.0]]
+    anc = [[3, float(c0[0]) + 1.0, float(c0[1]) + 1.0 + shift, float(c0[2]) + 1.0, 0.25, 1.5]]
+    if rows:
+        B = xk.shape[0]
+        return Restraints(obstacles=torch.tensor(obs).expand(B, -1, -1) + torch.arange(B).view(B, 1, 1) * torch.tensor([0.1, 0, 0, 0, 0]),
+                          pairs=pairs, anchors=anc)
+    return Restraints(obstacles=obs, pairs=pairs, anchors=anc)
+
+
+RKW = dict(restraint_scale=0.05, restraint_clip=0.3, restraint_frame="known")
+
+CHAINS = {"R1": dict(), "R2": dict(resamplings=2), "K4": dict(steps=4), "K4R2guided": dict(steps=4, resamplings=2, guidance_scale=2.0),
+          "x0": dict(record="x0")}
+
+
+@pytest.mark.parametrize("precision", BOTH)
+@pytest.mark.parametrize("case", list(CHAINS))
+def test_framed_inpainting_chain_against_the_restatement(case, precision):
+    """Per state: rel-L2 < 1e-4 against the inpainting chain (host twin of the generator) with the framed update on eps^; the states
+    are the frames of keep_frames = K, record = "z" (frame 0: the returned x, h), or the data predictions of record = "x0"."""
+    lib = _lib.load()
+    kw = dict(CHAINS[case])
+    guided = "guidance_scale" in kw
+    C_ = 1 if guided else 0
+    model, sd_np, cfg = model_for(precision, C_)
+    fresh(model)
+    nm, em, ctx, fm, xk, hk = chain_case(C_=C_)
+    B, N = nm.shape[:2]
+    R, record = kw.get("resamplings", 1), kw.pop("record", "z")
+    gg = gamma_grid_fp64(model, T)
+    path = paths.build_path(T, kw.get("steps"))
+    K = len(path) - 1
+    ids = [9 + b for b in range(B)]
+    rs = chain_tables(N, xk, fm)
+    scale = torch.tensor([0.05, 0.02, 0.05])
+    net = er.RefNet(sd_np, cfg, T, nm, em, ctx)
+    inner = gr.GuidedNet(net, er.RefNet(sd_np, cfg, T, nm, em, gr.null_ctx(nm)), 2.0, 0.0) if guided else net
+    xh_known = torch.cat([xk, hk], dim=2) * fm.float()
+    fnet = fr.FramedNet(inner, rs, scale, fr.rows_from_grid(gg, path, "score", 0.3), nm, fm, xh_known)
+    z = orc.combined_noise(*fr.philox_raw(lib, SEED, ids, 0, N), nm.float())
+    frames = []
+    ref = fr.inpaint_path_ref(lib, fnet, gg, path, T, z, nm, fm, xh_known, R, SEED, ids, x0_frames=frames)
+    pnet = fr.FramedNet(inner, rs, torch.zeros(B), {}, nm, fm, xh_known)
+    plain = fr.inpaint_path_ref(lib, pnet, gg, path, T, z, nm, fm, xh_known, R, SEED, ids)
+    got = model.sample_inpaint(dev(nm), dev(fm), dev(xk), dev(hk), context=dev(ctx), sample_id_base=9, keep_frames=K, record=record,
+                               restraints=rs, **dict(RKW, restraint_scale=scale), **kw)
+    x, h, chain, info = got
+    assert torch.isfinite(chain).all()
+    worst = 0.0
+    for k in range(K - 1):                                    # transition k arrives at position K - 1 - k, its frame at keep = K
+        f = chain[K - 1 - k].cpu()
+        if record == "z":
+            r = rel_l2(f.numpy(), ref[k].numpy())
+        else:                                                 # the data prediction of transition k's last round, x part
+            zk, ek = frames[k]
+            row = fnet.rows[int(path[k])]
+            r = rel_l2(f[:, :, :3].numpy(), (rr.x0_f32(zk, ek, row[0], row[1], 1.0) * nm.float()).numpy())
+        worst = max(worst, r)
+        print(f"framed inpainting {case} [{precision}] {'state' if record == 'z' else 'x0 frame'} {k + 1}/{K}: rel_l2 {r:.2e} "
+              f"(bar {REL_L2_TOL:.0e})")
+        assert r < REL_L2_TOL, (case, precision, k, r)
+    # the returned molecule: the decode of z_0 (the network's own eps^ at t = 0), known rows put back
+    xr, hr = gr.decode_on_eps(net, ref[-1], inner.net(ref[-1], 0), fr.philox_raw(lib, SEED, ids, T + 1, N), gg)
+    fmf = fm.float()
+    den = fmf.sum(1, keepdim=True).clamp(min=1.0)
+    xr = torch.where(fm, xk + ((xr * fmf).sum(1, keepdim=True) / den - (xk * fmf).sum(1, keepdim=True) / den), xr.float())
+    hr = torch.where(fm, hk, hr.float())
+    rx, rh = rel_l2(x.cpu().numpy(), xr.numpy()), rel_l2(h.cpu().numpy(), hr.numpy())
+    d = rel_l2(ref[-1].numpy(), plain[-1].numpy())
+    print(f"framed inpainting {case} [{precision}]: worst state {worst:.2e}, x {rx:.2e}, h {rh:.2e}; restraints active in "
+          f"{fnet.active} of {fnet.calls} network calls; distance of the restrained z_0 from the unrestrained one {d:.2e}")
+    assert rx < REL_L2_TOL and rh < REL_L2_TOL
+    assert torch.equal(chain[0], torch.cat([x, h], dim=2))
+    assert 2 * fnet.active >= fnet.calls and fnet.calls == K * R
+    assert d > 10 * REL_L2_TOL                                # not a no-op: the unrestrained chain lies far outside the bar
+    # the result in the coordinates of the input
+    tau, xkf, en = info["frame_shift"].cpu(), info["x_known_frame"].cpu(), info["restraint_energy"].cpu()
+    assert tau.dtype == torch.float64 and tau.shape == (B, 3) and en.shape == (B, 3) and xkf.shape == (B, N, 3)
+    want_tau, tmag = fr.frame_shift_ref(x.cpu().numpy(), xk.numpy(), nm, fm)
+    assert (np.abs(tau.numpy() - want_tau) <= 1e-12 * tmag).all() and (tau[2] == 0).all()
+    # x_i = fl(xk_i + s) on the fixed rows and tau = s + the mean of those roundings: |x_i - tau - xk_i| <= 2^-23 max_F |x|, and one
+    # more rounding to fp32
+    tol = 2.0 ** -23 * (x.cpu().abs().max() + xk.abs().max())
+    assert ((xkf - xk).abs() * fmf).max() <= tol, ((xkf - xk).abs() * fmf).max()
+    assert torch.equal(xkf, ((x.cpu().double() - tau[:, None, :]) * nm.double()).float())
+    want_en = rs.energy(x.cpu(), nm, fixed_mask=fm, x_known=xk)
+    assert torch.allclose(en, want_en, rtol=1e-9, atol=1e-12)
+
+
+def test_sample_grow_results_are_in_the_frame_of_the_input():
+    model, _, _ = model_for("fp32")
+    fresh(model)
+    g = torch.Generator().manual_seed(4)
+    known = [{"x": torch.tensor(fr.CENTRE) + torch.randn(k, 3, generator=g), "h": torch.randn(k, 8, generator=g)} for k in (3, 2, 0)]
+    c0 = known[0]["x"].mean(0)
+    # (an anchor acts at any distance: with synthetic weights the free nodes end far from the block, outside every obstacle)
+    rs = Restraints(obstacles=[[float(c0[0]), float(c0[1]), float(c0[2]), 3.0, 2.0]],
+                    anchors=[[3, float(c0[0]) + 1.0, float(c0[1]), float(c0[2]), 0.5, 1.5]])
+    out = model.sample_grow(known, [7, 4, 2], DEV, sample_id_base=2, steps=4, restraints=rs, **RKW)
+    plain = model.sample_grow(known, [7, 4, 2], DEV, sample_id_base=2, steps=4)
+    for i, (r, p) in enumerate(zip(out, plain)):
+        k = known[i]["x"].shape[0]
+        assert r["restraint_energy"].shape == (3,) and r["frame_shift"].shape == (3,) and r["frame_shift"].dtype == torch.float64
+        assert r["x_known_frame"].shape == r["x"].shape and "frame_shift" not in p
+        assert torch.equal(r["h"][:k], known[i]["h"])
+        if k:
+            tol = 2.0 ** -23 * (r["x"].abs().max() + known[i]["x"].abs().max())
+            assert (r["x_known_frame"][:k] - known[i]["x"]).abs().max() <= tol
+            n = r["x"].shape[0]
+            fmk = (torch.arange(n) < k).view(1, n, 1)
+            want = rs.energy(r["x"].unsqueeze(0), torch.ones(1, n, 1), fixed_mask=fmk, x_known=torch.cat([known[i]["x"], torch.zeros(n - k, 3)]).unsqueeze(0))
+            assert torch.allclose(r["restraint_energy"], want[0], rtol=1e-9, atol=1e-12)
+    assert not torch.equal(out[0]["x"], plain[0]["x"])
+
+
+# ----------------------------------------------------------------------------- contracts
+
+def test_graph_replay_equals_launches_reattaching_does_not_rebuild_and_the_frame_does():
+    lib = _lib.load()
+    model, _, _ = model_for("fp32")
+    nm, em, ctx, fm, xk, hk = chain_case()
+    nmd, N = dev(nm), nm.shape[1]
+    a, b, big = chain_tables(N, xk, fm), chain_tables(N, xk, fm, shift=0.25), chain_tables(N, xk, fm, P=9)
+    kw = dict(sample_id_base=3, steps=4, resamplings=2, **RKW)
+    call = lambda **k: model.sample_inpaint(nmd, dev(fm), dev(xk), dev(hk), **k)[:2]
+    fresh(model, graph=False)
+    want = {k: call(restraints=r, **kw) for k, r in (("a", a), ("b", b), ("big", big))}
+    want["plain"] = call(sample_id_base=3, steps=4, resamplings=2)
+    want["model"] = model.sample_from_masks(nmd, None, None, sample_id_base=3, steps=4, restraints=a, restraint_scale=0.05, restraint_clip=0.3)
+    assert not torch.equal(want["a"][0], want["b"][0]) and not torch.equal(want["a"][0], want["plain"][0])
+    fresh(model, graph=True)
+    topo = model.dynamics.topology(nmd, None, 3, N)
+    same = lambda got, k: torch.equal(got[0], want[k][0]) and torch.equal(got[1], want[k][1])
+    builds = lambda: lib.hd_path_graph_builds(topo.ptr)
+    n0 = builds()
+    assert same(call(restraints=a, **kw), "a")
+    assert builds() == n0 + 1
+    assert same(call(restraints=b, **kw), "b")                # equal sizes: a copy, no rebuild - although attaching resets the frame
+    assert same(call(restraints=a, **kw), "a")
+    assert builds() == n0 + 1
+    assert same(call(restraints=big, **kw), "big")            # a grown P rebuilds once
+    assert builds() == n0 + 2
+    assert same(call(sample_id_base=3, steps=4, resamplings=2), "plain")      # unrestrained afterwards: its own bits
+    n1 = builds()
+    assert same(call(restraints=big, **kw), "big")
+    n2 = builds()
+    assert n2 == n1 + 1
+    # the other frame (which takes a call without fixed fragments) is another graph, and coming back is one more
+    got = model.sample_from_masks(nmd, None, None, sample_id_base=3, steps=4, restraints=a, restraint_scale=0.05, restraint_clip=0.3)
+    assert same(got, "model") and builds() == n2 + 1
+    assert same(call(restraints=a, **kw), "a") and builds() == n2 + 2
+
+
+@pytest.mark.parametrize("precision", BOTH)
+@pytest.mark.parametrize("graph", [True, False], ids=["graph", "launches"])
+def test_scale_zero_is_the_unrestrained_inpainting_call_bit_for_bit(graph, precision):
+    model, _, _ = model_for(precision)
+    fresh(model, graph)
+    nm, em, ctx, fm, xk, hk = chain_case()
+    rs = chain_tables(nm.shape[1], xk, fm)
+    for few in (dict(), dict(steps=4, resamplings=2)):
+        plain = model.sample_inpaint(dev(nm), dev(fm), dev(xk), dev(hk), sample_id_base=5, **few)
+        for sc in (0, 0.0, torch.zeros(3), None):
+            got = model.sample_inpaint(dev(nm), dev(fm), dev(xk), dev(hk), sample_id_base=5, restraints=rs, restraint_frame="known",
+                                       restraint_scale=sc, restraint_clip=0.3, **few)
+            assert len(got) == 2 and torch.equal(got[0], plain[0]) and torch.equal(got[1], plain[1])
+        # inside the kernel: molecules with s_b = 0 keep their bits while the others move
+        part = model.sample_inpaint(dev(nm), dev(fm), dev(xk), dev(hk), sample_id_base=5, restraints=rs, restraint_frame="known",
+                                    restraint_scale=torch.tensor([0.0, 0.05, 0.0]), restraint_clip=0.3, **few)
+        assert torch.equal(part[0][0], plain[0][0]) and torch.equal(part[0][2], plain[0][2]) and torch.equal(part[1][0], plain[1][0])
+        assert not torch.equal(part[0][1], plain[0][1])
+        assert (part[-1]["frame_shift"][2] == 0).all()
+
+
+@pytest.mark.parametrize("graph", [True, False], ids=["graph", "launches"])
+def test_a_molecule_depends_on_its_id_masks_known_values_and_own_rows_only(graph):
+    model, _, _ = model_for("fp32")
+    fresh(model, graph)
+    nm, em, ctx, fm, xk, hk = chain_case((7, 4, 1, 6))
+    B, N = nm.shape[:2]
+    rs = chain_tables(N, xk, fm, rows=True)
+    scale = torch.tensor([0.05, 0.03, 0.05, 0.08])
+    kw = dict(steps=4, resamplings=2, restraint_clip=0.3, restraint_frame="known")
+    whole = model.sample_inpaint(dev(nm), dev(fm), dev(xk), dev(hk), sample_id_base=11, restraints=rs, restraint_scale=scale, **kw)
+    for b in range(B):
+        s = slice(b, b + 1)
+        one = model.sample_inpaint(dev(nm[s]), dev(fm[s]), dev(xk[s]), dev(hk[s]), sample_id_base=11 + b, restraints=rs.slice(b, b + 1),
+                                   restraint_scale=scale[s], **kw)
+        assert torch.equal(one[0][0], whole[0][b]) and torch.equal(one[1][0], whole[1][b]), b
+        assert torch.equal(one[2]["frame_shift"][0], whole[2]["frame_shift"][b])
+    # reordered: the last two molecules first (ids follow them one by one above; here the pair keeps consecutive ids)
+    o = [2, 3]
+    two = model.sample_inpaint(dev(nm[o]), dev(fm[o]), dev(xk[o]), dev(hk[o]), sample_id_base=13, restraints=rs.slice(2, 4),
+                               restraint_scale=scale[o], **kw)
+    assert torch.equal(two[0], whole[0][2:]) and torch.equal(two[1], whole[1][2:])
+
+
+def test_a_cut_chain_through_inpaint_steps_equals_the_whole():
+    model, _, _ = model_for("fp32")
+    fresh(model)
+    nm, em, ctx, fm, xk, hk = chain_case()
+    B, N = nm.shape[:2]
+    raw = er.raw_draws(1, B, N, seed=2)[0]
+    z = dev(orc.combined_noise(raw[0], raw[1], nm.float()))
+    rs = chain_tables(N, xk, fm)
+    kw = dict(resamplings=2, sample_id_base=4, restraints=rs, **RKW)
+    args = (dev(nm), dev(fm), dev(xk), dev(hk))
+    model.sample_steps = 4
+    try:
+        whole = model.inpaint_steps(z, 4, 0, *args, **kw)
+        cut = model.inpaint_steps(model.inpaint_steps(z, 4, 3, *args, **kw), 3, 0, *args, **kw)
+        assert torch.equal(cut, whole)
+        assert not torch.equal(whole, model.inpaint_steps(z, 4, 0, *args, resamplings=2, sample_id_base=4))
+    finally:
+        model.sample_steps = None
+    # the identity path, where the unrestrained call runs the every-step loop
+    whole = model.inpaint_steps(z, T, 0, *args, **kw)
+    cut = model.inpaint_steps(model.inpaint_steps(z, T, 5, *args, **kw), 5, 0, *args, **kw)
+    assert torch.equal(cut, whole)
+
+
+# ----------------------------------------------------------------------------- refusals on the device path
+
+def test_device_path_refusals():
+    lib = _lib.load()
+    model, _, _ = model_for("fp32")
+    fresh(model)
+    nm, em, ctx, fm, xk, hk = chain_case((5, 4, 3, 1))
+    B, N = nm.shape[:2]
+    nmd = dev(nm)
+    want = model.sample_inpaint(nmd, dev(fm), dev(xk), dev(hk), sample_id_base=1, steps=4)      # sets the path, ancestral rows
+    hnd, topo = model._lib_handle(), model.dynamics.topology(nmd, None, B, N)
+    rs = chain_tables(N, xk, fm)
+    z = torch.zeros(B, N, 11, device=DEV)
+    fmu, known = u8(fm), dev(torch.cat([xk, hk], dim=2) * fm.float()).contiguous()
+    inpaint = lambda zz: lib.hd_sample_path_inpaint(hnd, topo.ptr, zz.data_ptr(), None, -1, 0, 4, None, None, B, SEED, 1, 1,
+                                                    fmu.data_ptr(), known.data_ptr(), 1, stream())
+    assert lib.hd_restraint_frame(topo.ptr, 1) == -4 and b"no restraints attached" in lib.hd_last_error()
+    rs.attach(topo, torch.ones(1), 1.0, torch.device(DEV), stream())
+    model._restraint_cache = None
+    try:
+        rows = (C.c_float * 16)(*([0.8, 0.6, 0.5, 0.3] * 4))
+        assert lib.hd_set_restraint(hnd, 4, rows) == 0, lib.hd_last_error()
+        assert lib.hd_restraint_frame(topo.ptr, 2) == -1
+        # frame 0, the default: the old refusal, the old text
+        assert inpaint(z.clone()) == -1 and b"inpainting takes none (it re-centres on the known fragments: hd_restraint_detach)" in lib.hd_last_error()
+        # frame 1 without fixed fragments
+        assert lib.hd_restraint_frame(topo.ptr, 1) == 0
+        zz = z.clone()
+        assert lib.hd_sample_path(hnd, topo.ptr, zz.data_ptr(), None, -1, 0, 4, None, None, B, SEED, 1, 1, stream()) == -1
+        assert b"needs fixed fragments" in lib.hd_last_error()
+        # frame 1 with steering attached
+        assert lib.hd_steer_attach(topo.ptr, 2, 0.5, 1, stream()) == 0, lib.hd_last_error()
+        assert inpaint(z.clone()) == -1 and b"steering is attached" in lib.hd_last_error() and b"known" in lib.hd_last_error()
+        assert lib.hd_steer_detach(topo.ptr) == 0
+        # frame 1 alone runs; attaching again resets to frame 0
+        assert inpaint(z.clone()) == 0, lib.hd_last_error()
+        rs.attach(topo, torch.ones(1), 1.0, torch.device(DEV), stream())
+        assert inpaint(z.clone()) == -1 and b"inpainting takes none" in lib.hd_last_error()
+    finally:
+        lib.hd_steer_detach(topo.ptr)
+        Restraints.detach(topo)
+        model._restraint_cache = model._steer_cache = None
+    torch.cuda.synchronize()
+    got = model.sample_inpaint(nmd, dev(fm), dev(xk), dev(hk), sample_id_base=1, steps=4)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    with pytest.raises(NotImplementedError, match="restraints"):
+        model.sample_inpaint(nmd, dev(fm), dev(xk), dev(hk), restraints=rs, restraint_scale=1.0)
+    with pytest.raises(ValueError, match="restraint_frame='known'"):
+        model.sample_from_masks(nmd, None, None, restraints=rs, restraint_scale=1.0, restraint_frame="known")
