@@ -81,6 +81,10 @@ SIGNATURES = {
     "hd_restraint_frame": (C.c_int, [_VP, C.c_int]),
     "hd_restrain_eps_framed": (C.c_int, [_VP, _VP, _FP, _FP, C.POINTER(C.c_float), _U8P, _FP, _FP, _VP]),
     "hd_restraint_energy_framed": (C.c_int, [_VP, _VP, _FP, _U8P, _FP, _VP, _VP, _VP]),
+    "hd_restraint_fields": (C.c_int, [_VP, C.c_int, _FP, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_float), _FP, C.c_int,
+                                      _VP]),
+    "hd_restraint_field_energy": (C.c_int, [_VP, _VP, _FP, _VP, _VP]),
+    "hd_restraint_field_energy_framed": (C.c_int, [_VP, _VP, _FP, _U8P, _FP, _VP, _VP, _VP]),
     "hd_set_steer": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_float)]),
     "hd_steer_attach": (C.c_int, [_VP, C.c_int, C.c_double, C.c_int, _VP]),
     "hd_steer_detach": (C.c_int, [_VP]),

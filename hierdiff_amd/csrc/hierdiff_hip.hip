@@ -172,6 +172,7 @@ struct PathKey {
     unsigned long long weights_gen, sched_gen, path_gen, ip_gen;
     unsigned long long rs_gen, rs_rows_gen;                  // restrained transition: the topology's tables, the handle's rows (0 / 0: plain)
     int rs_frame;                                            // 1: its restraints act in the known fragments' frame (hd_restraint_frame)
+    unsigned long long rs_fld_gen;                           // its restraints hold fields (hd_restraint_fields): their buffers, NF, rows (0: none)
     int st_P;                                                // steered transition: particles per group, rho, the topology's steering
     double st_ess;                                           // buffers, the handle's rows (all 0: not steered)
     unsigned long long st_gen, st_rows_gen;
@@ -179,7 +180,7 @@ struct PathKey {
         return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape && noise_rows == o.noise_rows &&
                k_lo == o.k_lo && resamplings == o.resamplings && w_rows == o.w_rows && phi == o.phi && seed == o.seed &&
                weights_gen == o.weights_gen && sched_gen == o.sched_gen && path_gen == o.path_gen && ip_gen == o.ip_gen &&
-               rs_gen == o.rs_gen && rs_rows_gen == o.rs_rows_gen && rs_frame == o.rs_frame && st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen &&
+               rs_gen == o.rs_gen && rs_rows_gen == o.rs_rows_gen && rs_frame == o.rs_frame && rs_fld_gen == o.rs_fld_gen && st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen &&
                st_rows_gen == o.st_rows_gen;
     }
 };
@@ -269,6 +270,15 @@ struct hd_topology {
     float rs_nv0;
     unsigned long long rs_gen;
     int rs_frame;                              // hd_restraint_frame: 0 the model's frame, 1 the known fragments' (inpainting calls)
+    // hd_restraint_fields: the value pool and the weights (grown by the rule above), the offsets / dims / geometry of up to
+    // HD_MAX_FIELDS fields at fixed addresses (one allocation each, made by the first call).  rs_NF is what is attached now (0 after
+    // hd_restraint_attach); rs_fld_NF / rs_fld_w_rows are what the last fielded call baked in, and rs_fld_gen moves when that changes.
+    float *rs_fld_v, *rs_fld_w, *rs_fld_geom;
+    long long* rs_fld_off;
+    int* rs_fld_dims;
+    size_t rs_fld_cap[2];
+    int rs_NF, rs_fld_NF, rs_fld_w_rows;
+    unsigned long long rs_fld_gen;
     // hd_steer_attach: the steering state of the chain that runs on this topology (log-weights, last energies, lineage roots, the
     // ancestors of the latest transition, per-group statistics) and the scratch of k_steer_gather - one allocation each, made by the
     // first attach at addresses captured transitions keep.  It survives between the pieces of a chain; `reset` starts a new one.
@@ -853,7 +863,8 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     if (t->guide_mem) (void)hipFree(t->guide_mem);
     if (t->ms_hist) (void)hipFree(t->ms_hist);
     for (void* p : {(void*)t->rs_obs, (void*)t->rs_pair_idx, (void*)t->rs_pair_f, (void*)t->rs_anc_idx, (void*)t->rs_anc_f,
-                    (void*)t->rs_scale, (void*)t->rs_step, (void*)t->st_f64, (void*)t->st_i32, (void*)t->st_scratch})
+                    (void*)t->rs_scale, (void*)t->rs_step, (void*)t->rs_fld_v, (void*)t->rs_fld_w, (void*)t->rs_fld_geom,
+                    (void*)t->rs_fld_off, (void*)t->rs_fld_dims, (void*)t->st_f64, (void*)t->st_i32, (void*)t->st_scratch})
         if (p) (void)hipFree(p);
     if (t->ip_fixed) (void)hipFree(t->ip_fixed);
     if (t->ip_known) (void)hipFree(t->ip_known);

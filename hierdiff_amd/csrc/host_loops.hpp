@@ -556,7 +556,57 @@ extern "C" int hd_restraint_attach(hd_topology* topo, const float* obs, int obs_
     topo->rs_obs_rows = obs_rows; topo->rs_P = P; topo->rs_pair_rows = pair_rows; topo->rs_Q = Q; topo->rs_anc_rows = anc_rows;
     topo->rs_A = A; topo->rs_scale_rows = scale_rows; topo->rs_nv0 = nv0;
     topo->rs_frame = 0;                                 // the model's frame, until hd_restraint_frame says otherwise
+    topo->rs_NF = 0;                                    // no fields, until hd_restraint_fields says otherwise
     topo->rs_on = true;
+    return HD_OK;
+}
+
+extern "C" int hd_restraint_fields(hd_topology* topo, int NF, const float* values, const long long* offsets, const int* dims,
+                                   const float* geom, const float* weights, int w_rows, void* stream) {
+    if (!topo) return fail(HD_E_INVALID, "hd_restraint_fields: null topology");
+    if (NF < 0 || NF > HD_MAX_FIELDS) return fail(HD_E_INVALID, "hd_restraint_fields: NF must be 0 .. 8");
+    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restraint_fields: no restraints attached to the topology (hd_restraint_attach)");
+    if (NF == 0) { topo->rs_NF = 0; return HD_OK; }
+    if (!values || !offsets || !dims || !geom || !weights) return fail(HD_E_INVALID, "hd_restraint_fields: null table");
+    if (w_rows != 1 && w_rows != topo->B) return fail(HD_E_INVALID, "hd_restraint_fields: the weights have 1 row (shared) or B rows");
+    if (offsets[0] != 0) return fail(HD_E_INVALID, "hd_restraint_fields: offsets[0] must be 0");
+    for (int f = 0; f < NF; ++f) {
+        long long n = 1;
+        for (int c = 0; c < 3; ++c) {
+            const int d = dims[f * 3 + c];
+            if (d < 2) return fail(HD_E_INVALID, "hd_restraint_fields: every lattice dimension must be >= 2");
+            n *= d;
+            if (n >= (1LL << 31)) return fail(HD_E_INVALID, "hd_restraint_fields: a lattice holds fewer than 2^31 values");
+            const float hc = geom[f * 8 + 3 + c], oc = geom[f * 8 + c];
+            if (!(hc > 0.f) || !(hc - hc == 0.f)) return fail(HD_E_INVALID, "hd_restraint_fields: every spacing must be positive and finite");
+            if (!(oc - oc == 0.f)) return fail(HD_E_INVALID, "hd_restraint_fields: the origin must be finite");
+        }
+        for (int c = 6; c < 8; ++c) {
+            const float v = geom[f * 8 + c];
+            if (!(v >= 0.f) || !(v - v == 0.f)) return fail(HD_E_INVALID, "hd_restraint_fields: k and wall must be >= 0 and finite");
+        }
+        if (offsets[f + 1] - offsets[f] != n) return fail(HD_E_INVALID, "hd_restraint_fields: offsets[f + 1] - offsets[f] must be n0 n1 n2 of field f");
+    }
+    HIP_TRY(hipSetDevice(topo->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    topo->rs_NF = 0;
+    bool moved = false;
+    if (!topo->rs_fld_geom) {
+        if (!topo->rs_fld_off) HD_TRY(dev_alloc(&topo->rs_fld_off, (size_t)HD_MAX_FIELDS + 1));
+        if (!topo->rs_fld_dims) HD_TRY(dev_alloc(&topo->rs_fld_dims, (size_t)HD_MAX_FIELDS * 3));
+        HD_TRY(dev_alloc(&topo->rs_fld_geom, (size_t)HD_MAX_FIELDS * 8));    // last: its presence says all three are there
+        moved = true;
+    }
+    HD_TRY(rs_table(&topo->rs_fld_v, &topo->rs_fld_cap[0], values, (size_t)offsets[NF], &moved, s));
+    HD_TRY(rs_table(&topo->rs_fld_w, &topo->rs_fld_cap[1], weights, (size_t)w_rows * NF * topo->N, &moved, s));
+    // (host arrays: pageable sources are staged before the call returns)
+    HIP_TRY(hipMemcpyAsync(topo->rs_fld_off, offsets, ((size_t)NF + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(topo->rs_fld_dims, dims, (size_t)NF * 3 * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(topo->rs_fld_geom, geom, (size_t)NF * 8 * sizeof(float), hipMemcpyHostToDevice, s));
+    if (moved || NF != topo->rs_fld_NF || w_rows != topo->rs_fld_w_rows) topo->rs_fld_gen++;
+    topo->rs_fld_NF = NF; topo->rs_fld_w_rows = w_rows;
+    topo->rs_NF = NF;
     return HD_OK;
 }
 
@@ -577,6 +627,8 @@ static RestraintTables restraint_tables(const hd_topology* t) {
     RestraintTables r;
     r.obs = t->rs_obs; r.pair_idx = t->rs_pair_idx; r.pair_f = t->rs_pair_f; r.anc_idx = t->rs_anc_idx; r.anc_f = t->rs_anc_f;
     r.obs_rows = t->rs_obs_rows; r.P = t->rs_P; r.pair_rows = t->rs_pair_rows; r.Q = t->rs_Q; r.anc_rows = t->rs_anc_rows; r.A = t->rs_A;
+    r.fld_v = t->rs_fld_v; r.fld_off = t->rs_fld_off; r.fld_dims = t->rs_fld_dims; r.fld_geom = t->rs_fld_geom; r.fld_w = t->rs_fld_w;
+    r.fld_w_rows = t->rs_fld_w_rows; r.NF = t->rs_NF;
     return r;
 }
 
@@ -666,6 +718,34 @@ extern "C" int hd_restraint_energy_framed(hd_handle* h, hd_topology* topo, const
     hipLaunchKernelGGL(k_restraint_energy<true>, dim3(topo->B), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
     return HD_OK;
+}
+
+static int field_energy_launch(const char* who, hd_handle* h, hd_topology* topo, const float* x, const uint8_t* fixed_mask,
+                               const float* x_known, double* out, double* shift3, void* stream, bool framed) {
+    const std::string w(who);
+    if (!h || !topo) return fail(HD_E_INVALID, w + ": null handle/topology");
+    if (!x || !out || (framed && (!fixed_mask || !x_known))) return fail(HD_E_INVALID, w + ": null tensor");
+    if (!topo->rs_on) return fail(HD_E_STATE, w + ": no restraints attached to the topology (hd_restraint_attach)");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    ProfScope ps(h, s, 2);
+    RestraintEnergyArgs a{};
+    a.x = x; a.nm = topo->nm_bytes; a.t = restraint_tables(topo); a.out = out; a.B = topo->B; a.N = topo->N;
+    a.fixed = fixed_mask; a.x_known = x_known; a.shift = shift3;
+    if (framed) hipLaunchKernelGGL(k_restraint_field_energy<true>, dim3(topo->B), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_restraint_field_energy<false>, dim3(topo->B), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_restraint_field_energy(hd_handle* h, hd_topology* topo, const float* x, double* out, void* stream) {
+    return field_energy_launch("hd_restraint_field_energy", h, topo, x, nullptr, nullptr, out, nullptr, stream, false);
+}
+
+extern "C" int hd_restraint_field_energy_framed(hd_handle* h, hd_topology* topo, const float* x, const uint8_t* fixed_mask,
+                                                const float* x_known, double* out, double* shift3, void* stream) {
+    return field_energy_launch("hd_restraint_field_energy_framed", h, topo, x, fixed_mask, x_known, out, shift3, stream, true);
 }
 
 // ----------------------------------------------------------------------------- steering: particle resampling on the restraint energy
@@ -930,6 +1010,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     key.k_lo = c.raw_x ? k_lo : 0; key.resamplings = R; key.seed = c.seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
     key.path_gen = pt.gen; key.ip_gen = R ? h->ip_gen : 0; key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
     key.rs_gen = rsn ? topo->rs_gen : 0; key.rs_rows_gen = rsn ? h->rs_rows.gen : 0; key.rs_frame = framed ? 1 : 0;
+    key.rs_fld_gen = rsn && topo->rs_NF ? topo->rs_fld_gen : 0;
     key.st_P = stn ? topo->st_P : 0; key.st_ess = stn ? topo->st_ess : 0.0; key.st_gen = stn ? topo->st_gen : 0;
     key.st_rows_gen = stn ? h->st_rows.gen : 0;
     PathWords w;

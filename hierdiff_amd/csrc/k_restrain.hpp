@@ -20,11 +20,25 @@
 // rounded again), pairs do not see tau.  Fixed nodes gather nothing - their step is 0, the block is the frame - and receive -mean like
 // every valid node, so eps_x stays mean-free and a free node moves relative to the block by its own step.  No fixed node: tau = 0 and
 // the molecule's bits are those of the plain update.
+// FIELDS (hd_restraint_fields, hd_restraint_field_energy[_framed]): up to HD_MAX_FIELDS scalar potentials on regular lattices, read by
+// trilinear interpolation.  Field f: values v [n0][n1][n2] fp32 (last axis fastest), geom = (o[3], h[3], k, wall), weights w [rows][NF][N].
+// For a valid node at p = x - tau (tau = 0 in the model's frame), per axis c, in double:
+//   u = (p - o) / h,  ub = min(max(u, 0), n - 1),  cell = min((int)floor(ub), n - 2),  t = ub - cell,  out = (u - ub) h
+//   E = k w_i (V + 1/2 wall sum_c out_c^2),  V the trilinear interpolant of the cell's 8 corners at t
+//   dE/dx_c = k w_i ([0 <= u_c <= n_c - 1] dV/dt_c / h_c + wall out_c)
+// On an interior lattice plane the gradient is the right-hand cell's, at u = n - 1 the last cell's with t = 1; outside the box an axis
+// contributes only the wall.  A node with a non-finite coordinate contributes nothing (only a clamped, finite value becomes an int).
+// k w_i <= 0: the term is skipped.  The 8 corners are plain global loads; lane l of a node's group takes the fields l, l + G, ...
+// behind the anchors; the energy U_fld is a strided double sum over N * NF, then guide_block_sum.  In the known frame the field sees
+// tau, only free nodes gather a gradient, and the energy sums over all valid nodes.
 #pragma once
 #include "common.hpp"
 #include "k_guide.hpp"
 
 #define RS_GROUP 16
+#ifndef HD_MAX_FIELDS
+#define HD_MAX_FIELDS 8
+#endif
 
 struct RestraintTables {
     const float* obs;       // [obs_rows][P][5]
@@ -33,6 +47,13 @@ struct RestraintTables {
     const int* anc_idx;     // [anc_rows][A]
     const float* anc_f;     // [anc_rows][A][5]
     int obs_rows, P, pair_rows, Q, anc_rows, A;
+    // fields (behind the three tables; NF == 0: none, nothing below is read)
+    const float* fld_v;         // the value pool; field f is fld_v + fld_off[f], [n0][n1][n2]
+    const long long* fld_off;   // [NF + 1]
+    const int* fld_dims;        // [NF][3]
+    const float* fld_geom;      // [NF][8] = (o, h, k, wall)
+    const float* fld_w;         // [fld_w_rows][NF][N]
+    int fld_w_rows, NF;
 };
 
 struct RestrainArgs {
@@ -103,6 +124,54 @@ struct RsOffset {
 };
 #define RS_NO_OFFSET RsOffset{0.0, 0.0, 0.0, false}
 
+// One field at p (data units, the field's frame): false for a non-finite coordinate; else V + 1/2 wall |out|^2 into e and its gradient
+// into dg (both without the factor k w_i).  v: the lattice [n0][n1][n2], ge = (o, h, k, wall).
+HD_DEVINL bool rs_field_term(const float* v, const int* n, const float* ge, const double (&p)[3], double& e, double (&dg)[3]) {
+    double t[3], out[3], h[3];
+    int cell[3];
+    bool in[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        h[c] = (double)ge[3 + c];
+        const double u = (p[c] - (double)ge[c]) / h[c];
+        if (!(fabs(u) < HUGE_VAL)) return false;       // inf or NaN: never converted to int
+        const double top = (double)(n[c] - 1);
+        const double ub = fmin(fmax(u, 0.0), top);
+        const int ce = (int)floor(ub);
+        cell[c] = ce < n[c] - 2 ? ce : n[c] - 2;
+        t[c] = ub - (double)cell[c];
+        out[c] = (u - ub) * h[c];
+        in[c] = u >= 0.0 && u <= top;
+    }
+    const size_t s1 = (size_t)n[2], s0 = (size_t)n[1] * s1;
+    const float* q = v + (size_t)cell[0] * s0 + (size_t)cell[1] * s1 + (size_t)cell[2];
+    const double w0[2] = {1.0 - t[0], t[0]}, w1[2] = {1.0 - t[1], t[1]}, w2[2] = {1.0 - t[2], t[2]};
+    double V = 0.0, d0 = 0.0, d1 = 0.0, d2 = 0.0;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const double val = (double)q[a * s0 + b * s1 + c];
+                V += val * w0[a] * w1[b] * w2[c];
+                d0 += (a ? val : -val) * w1[b] * w2[c];
+                d1 += (b ? val : -val) * w0[a] * w2[c];
+                d2 += (c ? val : -val) * w0[a] * w1[b];
+            }
+    const double wall = (double)ge[7];
+    e = V + 0.5 * wall * (out[0] * out[0] + out[1] * out[1] + out[2] * out[2]);
+    dg[0] = (in[0] ? d0 / h[0] : 0.0) + wall * out[0];
+    dg[1] = (in[1] ? d1 / h[1] : 0.0) + wall * out[1];
+    dg[2] = (in[2] ? d2 / h[2] : 0.0) + wall * out[2];
+    return true;
+}
+
+// k w_i of field f on node i of molecule b
+HD_DEVINL double rs_field_kw(const RestraintTables& t, int b, int N, int f, int i) {
+    return (double)t.fld_geom[f * 8 + 6] * (double)t.fld_w[((size_t)(t.fld_w_rows == 1 ? 0 : b) * t.NF + f) * N + i];
+}
+
 // lane `l` of the `G` lanes that gather node i: its share of dU/dx_i into g (x: the molecule's positions, data units).  `off`: the
 // translation of the obstacle and anchor centres.
 HD_DEVINL void rs_node_grad(const RestraintTables& t, int b, const float* x, const uint8_t* nm, int N, int i, int l, int G,
@@ -136,6 +205,15 @@ HD_DEVINL void rs_node_grad(const RestraintTables& t, int b, const float* x, con
                              : rs_dist(x, i, (double)af[0], (double)af[1], (double)af[2], u);
         rs_band_term(d, -1.0, (double)af[3], (double)af[4], c);
         g[0] += c * u[0]; g[1] += c * u[1]; g[2] += c * u[2];
+    }
+    for (int f = l; f < t.NF; f += G) {
+        const double kw = rs_field_kw(t, b, N, f, i);
+        if (!(kw > 0.0)) continue;
+        const double p[3] = {off.on ? (double)x[3 * i] - off.x : (double)x[3 * i], off.on ? (double)x[3 * i + 1] - off.y : (double)x[3 * i + 1],
+                             off.on ? (double)x[3 * i + 2] - off.z : (double)x[3 * i + 2]};
+        double e, dg[3];
+        if (!rs_field_term(t.fld_v + t.fld_off[f], t.fld_dims + f * 3, t.fld_geom + f * 8, p, e, dg)) continue;
+        g[0] += kw * dg[0]; g[1] += kw * dg[1]; g[2] += kw * dg[2];
     }
 }
 
@@ -239,12 +317,35 @@ __global__ __launch_bounds__(256) void k_restrain_eps(RestrainArgs a) {
     }
 }
 
+// U_fld of the molecule b at positions x [N][3] into every thread: a strided double sum over N * NF per thread, then guide_block_sum.
+// `red`: 4 doubles of LDS.  NF == 0 (uniform): 0 without a barrier.
+HD_DEVINL double rs_field_block(const RestraintTables& t, int b, const float* x, const uint8_t* nm, int N, double* red, int tid,
+                                const RsOffset off = RS_NO_OFFSET) {
+    if (t.NF == 0) return 0.0;
+    double U[1] = {0.0};
+    for (int e = tid; e < N * t.NF; e += 256) {
+        const int i = e / t.NF, f = e - i * t.NF;
+        if (!nm[i]) continue;
+        const double kw = rs_field_kw(t, b, N, f, i);
+        if (!(kw > 0.0)) continue;
+        const double p[3] = {off.on ? (double)x[3 * i] - off.x : (double)x[3 * i], off.on ? (double)x[3 * i + 1] - off.y : (double)x[3 * i + 1],
+                             off.on ? (double)x[3 * i + 2] - off.z : (double)x[3 * i + 2]};
+        double en, dg[3];
+        if (!rs_field_term(t.fld_v + t.fld_off[f], t.fld_dims + f * 3, t.fld_geom + f * 8, p, en, dg)) continue;
+        U[0] += kw * en;
+    }
+    guide_block_sum<1>(U, red, tid);
+    return U[0];
+}
+
 // (U_obs, U_pair, U_anc) of the molecule b at positions x [N][3] (data units; global memory or LDS) into U, in every thread: a strided
 // double sum per thread, then guide_block_sum.  `red`: 4 * 3 doubles of LDS.  The one energy code of k_restraint_energy and k_steer_weigh.
-// `off`: the translation of the obstacle and anchor centres.
+// `off`: the translation of the obstacle and anchor centres (and of the fields' frame).  U[3] = U_fld (rs_field_block) when `fields`, else 0:
+// the first three components, their loops and their reduction do not see it.
 HD_DEVINL void rs_energy_block(const RestraintTables& t, int b, const float* x, const uint8_t* nm, int N, double* red, int tid,
-                               double (&U)[3], const RsOffset off = RS_NO_OFFSET) {
+                               double (&U4)[4], const RsOffset off = RS_NO_OFFSET, bool fields = true) {
     double u[3], c;
+    double U[3];
     U[0] = 0.0; U[1] = 0.0; U[2] = 0.0;
     const float* obs = t.obs + (size_t)(t.obs_rows == 1 ? 0 : b) * t.P * 5;
     for (long long e = tid; e < (long long)N * t.P; e += 256) {
@@ -273,6 +374,8 @@ HD_DEVINL void rs_energy_block(const RestraintTables& t, int b, const float* x, 
         U[2] += rs_band_term(d, -1.0, (double)af[3], (double)af[4], c);
     }
     guide_block_sum<3>(U, red, tid);
+    U4[0] = U[0]; U4[1] = U[1]; U4[2] = U[2];
+    U4[3] = fields ? rs_field_block(t, b, x, nm, N, red, tid, off) : 0.0;
 }
 
 template <bool FRAMED>
@@ -281,15 +384,35 @@ __global__ __launch_bounds__(256) void k_restraint_energy(RestraintEnergyArgs a)
     const int tid = threadIdx.x, b = blockIdx.x;
     const float* x = a.x + (size_t)b * a.N * 3;
     const uint8_t* nm = a.nm + (size_t)b * a.N;
-    double U[3];
+    double U[4];
     if constexpr (FRAMED) {
         RsOffset tau;
         rs_frame_shift(x, 3, a.x_known + (size_t)b * a.N * 3, 3, 1.0, nm, a.fixed + (size_t)b * a.N, a.N, red, tid, tau);
         tau.on = true;                                  // (no fixed node: tau = 0)
-        rs_energy_block(a.t, b, x, nm, a.N, red, tid, U, tau);
+        rs_energy_block(a.t, b, x, nm, a.N, red, tid, U, tau, false);
         if (a.shift && tid < 3) a.shift[(size_t)b * 3 + tid] = tid == 0 ? tau.x : tid == 1 ? tau.y : tau.z;
     } else {
-        rs_energy_block(a.t, b, x, nm, a.N, red, tid, U);
+        rs_energy_block(a.t, b, x, nm, a.N, red, tid, U, RS_NO_OFFSET, false);
     }
     if (tid < 3) a.out[(size_t)b * 3 + tid] = U[tid];
+}
+
+// U_fld per molecule (RestraintEnergyArgs with out [B]).
+template <bool FRAMED>
+__global__ __launch_bounds__(256) void k_restraint_field_energy(RestraintEnergyArgs a) {
+    __shared__ double red[4 * (FRAMED ? 7 : 1)];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const float* x = a.x + (size_t)b * a.N * 3;
+    const uint8_t* nm = a.nm + (size_t)b * a.N;
+    double U;
+    if constexpr (FRAMED) {
+        RsOffset tau;
+        rs_frame_shift(x, 3, a.x_known + (size_t)b * a.N * 3, 3, 1.0, nm, a.fixed + (size_t)b * a.N, a.N, red, tid, tau);
+        tau.on = true;
+        U = rs_field_block(a.t, b, x, nm, a.N, red, tid, tau);
+        if (a.shift && tid < 3) a.shift[(size_t)b * 3 + tid] = tid == 0 ? tau.x : tid == 1 ? tau.y : tau.z;
+    } else {
+        U = rs_field_block(a.t, b, x, nm, a.N, red, tid);
+    }
+    if (tid == 0) a.out[b] = U;
 }

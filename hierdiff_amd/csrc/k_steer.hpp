@@ -2,7 +2,7 @@
 // hd_steer_step / hd_steer_read; no reference counterpart).  Included through kernels.hpp.
 // The batch is G groups of P rows; group g owns rows g P .. g P + P - 1 (equal masks, contexts and restraint rows: the caller's
 // business).  Per transition, behind the network call, guidance and k_restrain_eps:
-//   k_steer_weigh      U(b) = U_obs + U_pair + U_anc of the transition's data prediction x^0 (the fp32 operations of k_restrain_eps,
+//   k_steer_weigh      U(b) = ((U_obs + U_pair) + U_anc) + U_fld of the transition's data prediction x^0 (the fp32 operations of k_restrain_eps,
 //                      the energy code of k_restraint_energy), logw[b] += -beta_k (U - U_prev[b]), U_prev[b] = U.  A non-finite U
 //                      (or update) is weight 0: logw = -inf.
 //   k_steer_resample   per group: m = max logw, w_i = exp(logw_i - m), S = sum w, S2 = sum w^2 in index order (a serial scan by one
@@ -70,10 +70,11 @@ __global__ __launch_bounds__(256) void k_steer_weigh(SteerWeighArgs a) {
         st_x[e] = __fmul_rn(__fmul_rn(ra, __fsub_rn(z[o], __fmul_rn(sg, eps[o]))), a.nv0);
     }
     __syncthreads();
-    double U[3];
+    double U[4];
     rs_energy_block(a.t, b, st_x, nm, N, red, tid, U);
     if (tid == 0) {
-        const double u = (U[0] + U[1]) + U[2];
+        const double u3 = (U[0] + U[1]) + U[2];
+        const double u = a.t.NF ? u3 + U[3] : u3;       // no fields: the old sum's bits
         const double dl = -(double)beta * (u - a.uprev[b]);
         // (finite: |v| < inf, false for a NaN.  Not v - v == 0: with v a product the compiler contracts that into the product's rounding error)
         a.logw[b] = (fabs(u) < HUGE_VAL && fabs(dl) < HUGE_VAL) ? a.logw[b] + dl : -HUGE_VAL;

@@ -1591,6 +1591,10 @@ class DiffusionQM9(_Base):
             got = self.sample_from_latent(z, nmd, None, ctxd, t_start=t_start, sample_id_base=base, guidance_scale=gs, **few, **rk)
             en = None if rr_all is None else rk["restraints"].energy(
                 got[0], nmd, model=self, _attach=(torch.as_tensor(rk["restraint_scale"]), float(self.norm_values[0]))).cpu()
+            fen = None
+            if en is not None and rk["restraints"].n_fields:
+                fen = rk["restraints"].field_energy(
+                    got[0], nmd, model=self, _attach=(torch.as_tensor(rk["restraint_scale"]), float(self.norm_values[0]))).cpu()
             xv, hv = got[0].cpu(), got[1].cpu()
             part = []
             for i in range(nm.shape[0]):
@@ -1600,6 +1604,8 @@ class DiffusionQM9(_Base):
                     res['context'] = ctx[i, :n].clone()
                 if en is not None:
                     res['restraint_energy'] = en[i].clone()
+                if fen is not None:
+                    res['restraint_field_energy'] = fen[i].clone()
                 part.append(res)
             if chain_t is not None:
                 self._chain_into(part, got[2], [int(nm[i].sum()) for i in range(nm.shape[0])], chain_t)
@@ -1782,7 +1788,11 @@ class DiffusionQM9(_Base):
         en, tau = rr.rs.energy(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0])),
                                fixed_mask=st.fm_u8, x_known=st.xk, return_shift=True)
         xkf = ((got[0].double() - tau[:, None, :]) * node_mask.to(st.dev, torch.float64)).to(torch.float32)
-        return tuple(got) + ({'restraint_energy': en, 'frame_shift': tau, 'x_known_frame': xkf},)
+        info = {'restraint_energy': en, 'frame_shift': tau, 'x_known_frame': xkf}
+        if rr.rs.n_fields:
+            info['restraint_field_energy'] = rr.rs.field_energy(got[0], node_mask, model=self, fixed_mask=st.fm_u8, x_known=st.xk,
+                                                                _attach=(rr.scale, float(self.norm_values[0])))
+        return tuple(got) + (info,)
 
     @torch.no_grad()
     def sample_grow(self, known: Sequence[Dict[str, torch.Tensor]], sizes, device, context=None, resamplings: int = 1,
@@ -1851,6 +1861,8 @@ class DiffusionQM9(_Base):
             info = {k: v.cpu() for k, v in got[-1].items()}
             for i in range(num):
                 out[i]['restraint_energy'] = info['restraint_energy'][i].clone()
+                if 'restraint_field_energy' in info:
+                    out[i]['restraint_field_energy'] = info['restraint_field_energy'][i].clone()
                 out[i]['frame_shift'] = info['frame_shift'][i].clone()
                 out[i]['x_known_frame'] = info['x_known_frame'][i, :sizes[i]].clone()
         return out
@@ -1937,6 +1949,10 @@ class DiffusionQM9(_Base):
             en = rr.rs.energy(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0]))).cpu()
             for i in range(num_samples):
                 out[i]['restraint_energy'] = en[i].clone()
+            if rr.rs.n_fields:
+                fen = rr.rs.field_energy(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0]))).cpu()
+                for i in range(num_samples):
+                    out[i]['restraint_field_energy'] = fen[i].clone()
         if pl.steer is not None:
             from . import steering
             steering.into(out, self.steer_last)

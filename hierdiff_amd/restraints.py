@@ -25,6 +25,23 @@ THE FRAME.  Coordinates are x = norm_values[0] * z_x.  There are two frames the 
       tau = 0: today's update.  Results carry 'frame_shift' (tau of the returned x) and 'x_known_frame' = x - tau, the molecule in
       the coordinates of the input.
 
+FIELDS.  `Field` is a scalar potential on a regular 3-D lattice - an AutoDock-style affinity map, or any field the user rasterises
+(`Field.from_obstacles` turns the sphere energy above into one) - read by trilinear interpolation: 8 loads per node whatever the
+potential was made from, any shape, negative (attractive) values included.  For a valid node at x, with p = x - tau (tau = 0 in the
+model's frame, the tau above in the known frame), origin o, spacing h, lattice v [n0, n1, n2], per axis c in double:
+
+    u_c = (p_c - o_c) / h_c,  ub_c = min(max(u_c, 0), n_c - 1),  cell_c = min(floor(ub_c), n_c - 2),  t_c = ub_c - cell_c
+    V   = sum_{a,b,c in {0,1}} v[cell_0 + a, cell_1 + b, cell_2 + c] W_a(t_0) W_b(t_1) W_c(t_2),   W_0(t) = 1 - t, W_1(t) = t
+    out_c = (u_c - ub_c) h_c                                  how far outside the box, data units; 0 inside
+    E   = k w_i (V + 1/2 wall sum_c out_c^2),    U_fld = sum over the fields and the valid nodes
+
+    dE/dx_c = k w_i ([0 <= u_c <= n_c - 1] dV/dt_c / h_c + wall out_c): on an interior lattice plane the gradient is the right-hand
+cell's, at u_c = n_c - 1 the last cell's with t = 1; outside the box an axis contributes only the wall.  A node with a non-finite
+coordinate contributes neither energy nor gradient.  U_fld may be negative.  In every other respect the term follows the obstacles:
+the gradient joins the same per-node step ahead of the clip and the mean; in the known frame only free nodes gather it and the
+energy sums over all valid nodes.  Values are shared by the molecules of a call, weights may differ per molecule; a call carries at
+most MAX_FIELDS fields.
+
 A pair or anchor row whose node index is -1 (padding), >= the molecule's size or masked is inactive - documented behaviour, not an
 error, because `sample` draws the sizes.  A term at distance exactly 0 contributes no gradient.
 
@@ -40,6 +57,7 @@ import torch
 
 SCHEDULES = ("score", "sigma")
 FRAMES = ("model", "known")
+MAX_FIELDS = 8                                   # HD_MAX_FIELDS
 
 
 def check_frame(model, frame) -> int:
@@ -80,16 +98,162 @@ def _table(v, width: int, name: str) -> Optional[torch.Tensor]:
     return t.to(torch.float64)
 
 
+def _number(v, name: str, positive: bool = False) -> float:
+    """A finite number >= 0 (> 0 with `positive`), rounded to fp32 - what the library reads."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{name} must be a number, got {v!r}")
+    f = float(np.float32(v))
+    if not math.isfinite(f) or f < 0 or (positive and not f > 0):
+        raise ValueError(f"{name} must be finite and {'> 0' if positive else '>= 0'}, got {v!r}")
+    return f
+
+
+class Field:
+    """One scalar potential on a regular lattice (module docstring: FIELDS).
+
+    values   [n0, n1, n2] array or tensor, stored as float32; every n_c >= 2, finite, fewer than 2^31 entries
+    origin   3 numbers: the position of values[0, 0, 0], data units
+    spacing  a number or 3 numbers > 0 (the lattice may be anisotropic)
+    k        stiffness >= 0 (the factor in front of the interpolated value), wall: stiffness >= 0 of the harmonic wall outside the box
+    weights  None: every valid node weighs 1; [W] (shared) or [B, W] (per molecule), >= 0: node i takes weights[i], nodes i >= W take 0
+             (documented behaviour, like an anchor on a node the molecule does not have: `sample` draws the sizes)
+    ValueError for every malformed argument, before a device is looked at.  origin, spacing, k and wall are rounded to fp32 once,
+    here.  A device copy of the values is kept per device, so a large lattice is uploaded once."""
+
+    def __init__(self, values, origin, spacing, k=1.0, wall=0.0, weights=None):
+        try:
+            v = torch.as_tensor(np.asarray(values.detach().cpu()) if isinstance(values, torch.Tensor) else np.asarray(values))
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError("Field: values must be a 3-D array [n0, n1, n2]") from None
+        if v.dim() != 3 or v.dtype == torch.bool or v.is_complex():
+            raise ValueError(f"Field: values must be a real 3-D array [n0, n1, n2], got shape {tuple(v.shape)}")
+        if min(v.shape) < 2:
+            raise ValueError(f"Field: every lattice dimension must be >= 2, got {tuple(v.shape)}")
+        if v.numel() >= 2 ** 31:
+            raise ValueError("Field: a lattice holds fewer than 2^31 values")
+        v = v.to(torch.float32).contiguous()
+        if not bool(torch.isfinite(v).all()):
+            raise ValueError("Field: values must be finite (in float32)")
+        self.values = v
+        self.origin = self._three(origin, "origin", False)
+        self.spacing = self._three(spacing, "spacing", True)
+        self.k, self.wall = _number(k, "Field: k"), _number(wall, "Field: wall")
+        self.weights = None
+        if weights is not None:
+            try:
+                w = torch.as_tensor(weights).detach().cpu().to(torch.float32)
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError("Field: weights must be None, [W] or [B, W]") from None
+            if w.dim() not in (1, 2) or w.numel() == 0:
+                raise ValueError(f"Field: weights must be None, [W] or [B, W], got {tuple(w.shape)}")
+            if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+                raise ValueError("Field: weights must be finite and >= 0")
+            self.weights = (w.unsqueeze(0) if w.dim() == 1 else w).contiguous()
+        self._dev = {}
+
+    @staticmethod
+    def _three(v, name: str, scalar_ok: bool) -> torch.Tensor:
+        try:
+            t = torch.as_tensor(v, dtype=torch.float64).detach().cpu().reshape(-1)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"Field: {name} must be {'a number or ' if scalar_ok else ''}3 numbers, got {v!r}") from None
+        if scalar_ok and t.numel() == 1 and torch.as_tensor(v).dim() == 0:
+            t = t.repeat(3)
+        if t.numel() != 3 or isinstance(v, bool):
+            raise ValueError(f"Field: {name} must be {'a number or ' if scalar_ok else ''}3 numbers, got {v!r}")
+        t = t.to(torch.float32)
+        if not bool(torch.isfinite(t).all()) or (scalar_ok and not bool((t > 0).all())):
+            raise ValueError(f"Field: {name} must be finite{' and > 0' if scalar_ok else ''}, got {v!r}")
+        return t
+
+    @property
+    def rows(self) -> int:
+        return 1 if self.weights is None else int(self.weights.shape[0])
+
+    def geom(self) -> torch.Tensor:
+        """[8] float32 (o, h, k, wall): the library's row."""
+        return torch.cat([self.origin, self.spacing, torch.tensor([self.k, self.wall], dtype=torch.float32)])
+
+    def node_weights(self, N: int) -> torch.Tensor:
+        """[rows, N] float32: the weights cut or zero-padded to N nodes (None: ones)."""
+        if self.weights is None:
+            return torch.ones(1, N, dtype=torch.float32)
+        w = torch.zeros(self.weights.shape[0], N, dtype=torch.float32)
+        n = min(N, int(self.weights.shape[1]))
+        w[:, :n] = self.weights[:, :n]
+        return w
+
+    def device_values(self, dev) -> torch.Tensor:
+        dev = torch.device(dev)
+        hit = self._dev.get(dev)
+        if hit is None:
+            hit = self._dev[dev] = self.values.to(dev).contiguous()
+        return hit
+
+    def _slice(self, lo: int, hi: int) -> "Field":
+        if self.weights is None or self.weights.shape[0] == 1:
+            return self
+        out = object.__new__(Field)
+        out.__dict__.update(self.__dict__)               # the values and their device copies are shared
+        out.weights = self.weights[lo:hi].contiguous()
+        return out
+
+    @classmethod
+    def from_obstacles(cls, obstacles, origin, shape, spacing, k=1.0, wall=0.0) -> "Field":
+        """The sphere energy 1/2 sum_p k_p max(0, r_p - |y - y_p|)^2 of `obstacles` ([P, 5] rows (y, r, k), shared) rasterised at the
+        lattice points y = origin + index * spacing of a lattice of `shape` = (n0, n1, n2): float64 on the CPU in chunks, rounded to
+        fp32 once.  Between the lattice points the field is the trilinear interpolant, not the sphere energy."""
+        obs = _table(obstacles, 5, "obstacles")
+        if obs is None or obs.shape[0] != 1:
+            raise ValueError("Field.from_obstacles: obstacles must be a non-empty shared table [P, 5]")
+        if bool((obs[..., 3:] < 0).any()):
+            raise ValueError("obstacles: r and k must be >= 0 (a row with r = 0 or k = 0 is padding)")
+        try:
+            shape = tuple(int(n) for n in shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"Field.from_obstacles: shape must be 3 integers >= 2, got {shape!r}") from None
+        if len(shape) != 3 or min(shape) < 2 or shape[0] * shape[1] * shape[2] >= 2 ** 31:
+            raise ValueError(f"Field.from_obstacles: shape must be 3 integers >= 2 (fewer than 2^31 points), got {shape!r}")
+        o = cls._three(origin, "origin", False).double()
+        h = cls._three(spacing, "spacing", True).double()
+        ob = obs[0].to(torch.float32).double()           # the fp32 rows `Restraints` keeps
+        ob = ob[(ob[:, 3] > 0) & (ob[:, 4] > 0)]
+        ax = [o[c] + torch.arange(shape[c], dtype=torch.float64) * h[c] for c in range(3)]
+        pts = torch.stack(torch.meshgrid(*ax, indexing="ij"), -1).reshape(-1, 3)
+        vals = torch.zeros(pts.shape[0], dtype=torch.float64)
+        chunk = max(1, (1 << 22) // max(1, int(ob.shape[0])))
+        for lo in range(0, pts.shape[0], chunk):
+            d = _norm(pts[lo:lo + chunk, None, :] - ob[None, :, :3])
+            vals[lo:lo + chunk] = 0.5 * (ob[None, :, 4] * torch.clamp(ob[None, :, 3] - d, min=0) ** 2).sum(1)
+        return cls(vals.reshape(shape).to(torch.float32), origin, spacing, k, wall)
+
+
+def _fields(fields) -> list:
+    if fields is None:
+        return []
+    fl = [fields] if isinstance(fields, Field) else fields
+    if not isinstance(fl, (list, tuple)) or not all(isinstance(f, Field) for f in fl):
+        raise ValueError("fields must be a restraints.Field or a list of them")
+    if len(fl) > MAX_FIELDS:
+        raise ValueError(f"fields: a call carries at most {MAX_FIELDS} fields, got {len(fl)}")
+    rows = {f.rows for f in fl} - {1}
+    if len(rows) > 1:
+        raise ValueError(f"fields: per-molecule weights hold rows for {sorted(rows)} molecules; they must agree")
+    return list(fl)
+
+
 class Restraints:
     """The three tables of one call, validated and kept on the CPU.
 
     obstacles  [P, 5] or [B, P, 5]   rows (y_x, y_y, y_z, r, k); a row with r <= 0 or k <= 0 is padding
     pairs      [Q, 5] or [B, Q, 5]   rows (i, j, lo, hi, k); i = j = -1 is padding
     anchors    [A, 6] or [B, A, 6]   rows (i, a_x, a_y, a_z, r, k); i = -1 is padding
+    fields     a `Field` or a list of at most MAX_FIELDS of them (lattice potentials; `field_energy`, not a column of `energy`)
     Tensors or nested lists; a table with a leading batch axis holds one set of rows per molecule.  ValueError: lo > hi, a negative
     r, k, lo or hi, non-finite values, i == j, fractional indices, negative indices other than -1."""
 
-    def __init__(self, obstacles=None, pairs=None, anchors=None):
+    def __init__(self, obstacles=None, pairs=None, anchors=None, fields=None):
+        self.fields = _fields(fields)
         obs, pr, an = _table(obstacles, 5, "obstacles"), _table(pairs, 5, "pairs"), _table(anchors, 6, "anchors")
         if obs is not None and bool((obs[..., 3:] < 0).any()):
             raise ValueError("obstacles: r and k must be >= 0 (a row with r = 0 or k = 0 is padding)")
@@ -127,8 +291,21 @@ class Restraints:
     def rows(self):
         return int(self.obs.shape[0]), int(self.pair_idx.shape[0]), int(self.anc_idx.shape[0])
 
+    @property
+    def n_fields(self) -> int:
+        return len(getattr(self, "fields", ()))
+
+    def field_rows(self) -> int:
+        """Rows of the field weights: 1 (shared) or the B of the per-molecule ones."""
+        return max([f.rows for f in getattr(self, "fields", ())] + [1])
+
+    def field_weights(self, N: int) -> torch.Tensor:
+        """[w_rows, NF, N] float32, always materialised: the library's weights."""
+        r = self.field_rows()
+        return torch.stack([f.node_weights(N).expand(r, N) for f in self.fields], 1).contiguous()
+
     def check_batch(self, B: int, what: str = "restraints") -> None:
-        for name, r in zip(("obstacles", "pairs", "anchors"), self.rows()):
+        for name, r in zip(("obstacles", "pairs", "anchors", "field weights"), self.rows() + (self.field_rows(),)):
             if r != 1 and r != int(B):
                 raise ValueError(f"{what}: {name} hold rows for {r} molecules, the call has {B} (give [n, w] to share one set)")
 
@@ -138,23 +315,43 @@ class Restraints:
         for k in ("obs", "pair_idx", "pair_f", "anc_idx", "anc_f"):
             t = getattr(self, k)
             setattr(out, k, t if t.shape[0] == 1 else t[lo:hi].contiguous())
+        out.fields = [f._slice(lo, hi) for f in getattr(self, "fields", ())]
         out._model = getattr(self, "_model", None)
         return out
 
     @classmethod
     def from_json(cls, path: str) -> "Restraints":
-        """A JSON file with the keys `obstacles`, `pairs`, `anchors` (each optional; the row formats above)."""
+        """A JSON file with the keys `obstacles`, `pairs`, `anchors` (each optional; the row formats above) and `fields` (optional):
+        a list of {"file": "pocket.npy", "origin": [...], "spacing": s | [...], "k": ..., "wall": ..., "weights": [...]} - `file`
+        relative to the JSON file, read with numpy.load(allow_pickle=False); k, wall and weights optional."""
         import json
+        import os
         with open(path) as f:
             d = json.load(f)
-        if not isinstance(d, dict) or set(d) - {"obstacles", "pairs", "anchors"}:
-            raise ValueError(f"{path}: expected an object with the keys obstacles / pairs / anchors")
-        return cls(d.get("obstacles"), d.get("pairs"), d.get("anchors"))
+        if not isinstance(d, dict) or set(d) - {"obstacles", "pairs", "anchors", "fields"}:
+            raise ValueError(f"{path}: expected an object with the keys obstacles / pairs / anchors / fields")
+        fields = None
+        if d.get("fields") is not None:
+            if not isinstance(d["fields"], list):
+                raise ValueError(f"{path}: fields must be a list of objects")
+            fields = []
+            for e in d["fields"]:
+                if not isinstance(e, dict) or set(e) - {"file", "origin", "spacing", "k", "wall", "weights"} or \
+                        not {"file", "origin", "spacing"} <= set(e) or not isinstance(e["file"], str):
+                    raise ValueError(f"{path}: a field is an object with the keys file, origin, spacing (and k, wall, weights)")
+                fn = os.path.join(os.path.dirname(os.path.abspath(path)), e["file"])
+                try:
+                    vals = np.load(fn, allow_pickle=False)
+                except (OSError, ValueError) as err:
+                    raise ValueError(f"{path}: cannot read the field file {e['file']!r}: {err}") from None
+                fields.append(Field(vals, e["origin"], e["spacing"], e.get("k", 1.0), e.get("wall", 0.0), e.get("weights")))
+        return cls(d.get("obstacles"), d.get("pairs"), d.get("anchors"), fields)
 
     # ------------------------------------------------------------------ device side
     def attach(self, topo, scale: torch.Tensor, nv0: float, dev, stream, frame: int = 0) -> None:
         """hd_restraint_attach: the tables and the scales [1] or [B] into the topology's buffers (stream-ordered copies).  `frame` 1:
-        then hd_restraint_frame - the tables are in the frame of an inpainting call's known fragments (attaching resets to 0)."""
+        then hd_restraint_frame - the tables are in the frame of an inpainting call's known fragments (attaching resets to 0).  With
+        fields, hd_restraint_fields goes between the two (attaching resets to no fields); `topo` then also needs its `.N`."""
         from . import _lib
         P, Q, A = self.sizes
         t = [x.to(dev).contiguous() for x in (self.obs, self.pair_idx, self.pair_f, self.anc_idx, self.anc_f, scale.to(torch.float32))]
@@ -163,8 +360,74 @@ class Restraints:
             topo.ptr, t[0].data_ptr() if P else None, ro, P, t[1].data_ptr() if Q else None, t[2].data_ptr() if Q else None, rp, Q,
             t[3].data_ptr() if A else None, t[4].data_ptr() if A else None, ra, A, t[5].data_ptr(), int(t[5].numel()), float(nv0),
             stream), "hd_restraint_attach")
+        if self.n_fields:                                # (attaching resets to no fields: the order is attach -> fields -> frame)
+            self._attach_fields(topo, dev, stream)
         if frame:
             _lib.check(_lib.load().hd_restraint_frame(topo.ptr, int(frame)), "hd_restraint_frame")
+
+    def _attach_fields(self, topo, dev, stream) -> None:
+        """hd_restraint_fields: the lattices (each field's device copy; several are concatenated on the device), their geometry and
+        the weights [w_rows, NF, N] into the topology's buffers."""
+        import ctypes as C
+        from . import _lib
+        fl = self.fields
+        NF = len(fl)
+        vals = [f.device_values(dev) for f in fl]
+        pool = vals[0].reshape(-1) if NF == 1 else torch.cat([v.reshape(-1) for v in vals])
+        off = np.zeros(NF + 1, dtype=np.int64)
+        off[1:] = np.cumsum([int(f.values.numel()) for f in fl])
+        dims = np.ascontiguousarray([list(f.values.shape) for f in fl], dtype=np.int32)
+        geom = np.ascontiguousarray(torch.stack([f.geom() for f in fl]).numpy(), dtype=np.float32)
+        w = self.field_weights(int(topo.N)).to(dev).contiguous()
+        _lib.check(_lib.load().hd_restraint_fields(
+            topo.ptr, NF, pool.data_ptr(), off.ctypes.data_as(C.POINTER(C.c_longlong)), dims.ctypes.data_as(C.POINTER(C.c_int)),
+            geom.ctypes.data_as(C.POINTER(C.c_float)), w.data_ptr(), int(w.shape[0]), stream), "hd_restraint_fields")
+
+    def field_energy(self, x: torch.Tensor, node_mask: torch.Tensor, model=None, fixed_mask=None, x_known=None, _attach=None):
+        """[B] float64 U_fld of positions x [B, N, 3] in data units under node_mask [B, N, 1] (0 without fields).  On a device the HIP
+        kernel evaluates it (k_restraint_field_energy; `model` as in `energy`); on the CPU the same formulas in torch float64.
+        fixed_mask and x_known (together): in the frame of `x_known`, as `energy`."""
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        if tuple(x.shape) != (B, N, 3):
+            raise ValueError(f"x must be [{B}, {N}, 3], got {tuple(x.shape)}")
+        if (fixed_mask is None) != (x_known is None):
+            raise ValueError("field_energy: fixed_mask and x_known go together")
+        framed = fixed_mask is not None
+        if framed and (fixed_mask.numel() != B * N or tuple(x_known.shape) != (B, N, 3)):
+            raise ValueError(f"field_energy: fixed_mask must hold {B} x {N} entries and x_known be [{B}, {N}, 3]")
+        self.check_batch(B, "field_energy")
+        if x.device.type != "cuda":
+            xd = x.detach().double()
+            if framed:
+                xd = xd - frame_shift(x, node_mask, fixed_mask, x_known)[:, None, :]
+            return field_energy_terms(self, xd, node_mask)
+        model = model if model is not None else (self._model() if getattr(self, "_model", None) is not None else None)
+        if model is None:
+            raise ValueError("field_energy on a device needs model= (the DiffusionQM9 that owns the library handle) unless these "
+                             "restraints have already run in one of its sampling calls")
+        from . import _lib
+        from .dynamics import _stream
+        dev = x.device
+        nm = node_mask.to(dev)
+        h = model._lib_handle()
+        topo = model.dynamics.topology(nm, None, B, N)
+        out = torch.empty((B,), device=dev, dtype=torch.float64)
+        xs = x.detach().to(torch.float32).contiguous()
+        scale, nv0 = (torch.ones(1), 1.0) if _attach is None else _attach
+        self.attach(topo, scale, nv0, dev, _stream(dev))
+        try:
+            if framed:
+                fm = (fixed_mask.to(dev).reshape(B * N) != 0).to(torch.uint8).contiguous()
+                xk = x_known.detach().to(dev, torch.float32).contiguous()
+                _lib.check(_lib.load().hd_restraint_field_energy_framed(h, topo.ptr, xs.data_ptr(), fm.data_ptr(), xk.data_ptr(),
+                                                                        out.data_ptr(), None, _stream(dev)),
+                           "hd_restraint_field_energy_framed")
+            else:
+                _lib.check(_lib.load().hd_restraint_field_energy(h, topo.ptr, xs.data_ptr(), out.data_ptr(), _stream(dev)),
+                           "hd_restraint_field_energy")
+        finally:
+            self.detach(topo)
+        return out
 
     @staticmethod
     def detach(topo) -> None:
@@ -260,6 +523,38 @@ def energy_terms(rs: Restraints, x: torch.Tensor, node_mask: torch.Tensor) -> to
             u_anc = 0.5 * (af[:, 4] * torch.clamp(d - af[:, 3], min=0) ** 2).sum()
         out.append(torch.stack([u_obs, u_pair, u_anc]))
     return torch.stack(out)
+
+
+def field_energy_terms(rs: Restraints, x: torch.Tensor, node_mask: torch.Tensor) -> torch.Tensor:
+    """[B] U_fld in x's dtype, differentiable in x: the field formulas of the module docstring in torch (x already in the fields'
+    frame).  A node with a non-finite coordinate contributes nothing."""
+    B, N = int(x.shape[0]), int(x.shape[1])
+    nm = node_mask.reshape(B, N).bool().to(x.device)
+    total = torch.zeros(B, dtype=x.dtype, device=x.device)
+    for f in getattr(rs, "fields", ()):
+        w = f.node_weights(N).to(x)
+        w = w.expand(B, N) if w.shape[0] == 1 else w
+        ok = nm & torch.isfinite(x).all(-1)
+        xs = torch.where(ok[..., None], x, torch.zeros_like(x))
+        o, h = f.origin.to(x), f.spacing.to(x)
+        n = torch.tensor(list(f.values.shape), device=x.device)
+        u = (xs - o) / h
+        ub = torch.minimum(torch.clamp(u, min=0), (n - 1).to(x))
+        cell = torch.minimum(torch.floor(ub.detach()).long(), n - 2)
+        t = ub - cell.to(x)
+        v = f.values.to(x)
+        V = 0
+        for a in (0, 1):
+            for b in (0, 1):
+                for c in (0, 1):
+                    wa = t[..., 0] if a else 1 - t[..., 0]
+                    wb = t[..., 1] if b else 1 - t[..., 1]
+                    wc = t[..., 2] if c else 1 - t[..., 2]
+                    V = V + v[cell[..., 0] + a, cell[..., 1] + b, cell[..., 2] + c] * wa * wb * wc
+        out = (u - ub) * h
+        e = f.k * w * (V + 0.5 * f.wall * (out * out).sum(-1))
+        total = total + torch.where(ok, e, torch.zeros_like(e)).sum(1)
+    return total
 
 
 def _norm(v):

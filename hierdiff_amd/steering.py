@@ -120,7 +120,7 @@ def _rows_equal(t: torch.Tensor, P: int) -> bool:
 
 def check_groups(st: Steer, node_mask, context=None, rs=None, scale=None, what: str = "steering") -> None:
     """All rows of a group must have equal node masks, context rows and per-molecule restraint rows (shared tables are trivially
-    equal) and restraint scales.  Compared on the host."""
+    equal; so are field values, only their weights can differ) and restraint scales.  Compared on the host."""
     P = st.P
     nm = torch.as_tensor(node_mask).detach().cpu()
     B = int(nm.shape[0])
@@ -137,6 +137,12 @@ def check_groups(st: Steer, node_mask, context=None, rs=None, scale=None, what: 
             if t.shape[0] == B and B > 1 and t.numel() and not _rows_equal(t.reshape(B, -1), P):
                 bad = f"restraint rows ({name})"
                 break
+        if bad is None:
+            for f in getattr(rs, "fields", ()):
+                w = f.weights
+                if w is not None and w.shape[0] == B and B > 1 and not _rows_equal(w.reshape(B, -1), P):
+                    bad = "restraint rows (field weights)"
+                    break
     if bad is None and scale is not None and torch.as_tensor(scale).numel() == B and not _rows_equal(torch.as_tensor(scale).cpu().reshape(B, 1), P):
         bad = "restraint scales"
     if bad is not None:

@@ -464,6 +464,45 @@ int hd_restrain_eps_framed(hd_handle* h, hd_topology* topo, const float* z, cons
 int hd_restraint_energy_framed(hd_handle* h, hd_topology* topo, const float* x, const uint8_t* fixed_mask, const float* x_known,
                                double* out3, double* shift3, void* stream);
 
+/* ---- Field restraints (ABI 12, additive; no reference counterpart): scalar potentials on regular 3-D lattices as a fourth term of
+ * the restraint energy, read by trilinear interpolation - 8 loads per node and field, whatever the potential was rasterised from.
+ * A topology with attached restraints carries up to HD_MAX_FIELDS fields.  Field f:
+ *   values   v_f [n0][n1][n2] fp32, the last axis fastest, every n_c >= 2, n0 n1 n2 < 2^31; the pool `values` holds field f at
+ *            offsets[f] .. offsets[f + 1] (offsets[0] = 0; device or host pointer)
+ *   dims     [NF][3] = (n0, n1, n2)                                  host
+ *   geom     [NF][8] = (o_x, o_y, o_z, h_x, h_y, h_z, k, wall)       host; origin, spacing > 0 per axis, stiffness k >= 0, wall >= 0
+ *   weights  [w_rows][NF][N] fp32 >= 0, w_rows = 1 (shared) or B     device or host pointer
+ * For a valid node i at x (the fp32 x^0 of the restraint update, or the given x of the energy calls), per axis c, in double:
+ *   p_c   = x_c - tau_c                              tau = 0 in the model's frame; the known fragments' tau in frame 1
+ *   u_c   = (p_c - o_c) / h_c,  ub_c = min(max(u_c, 0), n_c - 1),  cell_c = min((int)floor(ub_c), n_c - 2),  t_c = ub_c - cell_c
+ *   V     = sum_{a,b,c in {0,1}} v[cell_0 + a][cell_1 + b][cell_2 + c] W_a(t_0) W_b(t_1) W_c(t_2),  W_0(t) = 1 - t, W_1(t) = t
+ *   out_c = (u_c - ub_c) h_c                         how far outside the box, data units
+ *   E     = k w_i (V + 1/2 wall sum_c out_c^2)
+ *   dE/dx_c = k w_i ([0 <= u_c <= n_c - 1] (1 / h_c) dV/dt_c + wall out_c)
+ *   U_fld = sum_f sum_{i valid} E                    may be negative: the values may be
+ * On an interior lattice plane the gradient is the right-hand cell's; at u_c = n_c - 1 it is the last cell's with t = 1.  Outside the
+ * box an axis contributes only the wall.  A node with a non-finite coordinate contributes neither energy nor gradient.  A term with
+ * k w_i = 0 is skipped.  The gradient joins dU/dx_i of the update above, ahead of the clip and the mean; in frame 1 it sees tau, only
+ * free nodes gather it, and the energy sums over all valid nodes.  hd_steer_step and the steered loops weigh on
+ * ((U_obs + U_pair) + U_anc) + U_fld.  No atomics; every sum has a fixed order that depends on (N, NF) alone.
+ * hd_restraint_fields: stream-ordered copies into buffers the topology owns (grown as the tables of hd_restraint_attach are).  Needs
+ *   attached restraints (HD_E_STATE).  hd_restraint_attach resets the topology to NO fields, as it resets the frame: the order is
+ *   attach -> fields -> frame.  NF = 0 clears the fields.  HD_E_INVALID: NF outside 0 .. 8, a dim < 2, a lattice of 2^31 values or
+ *   more, a non-finite or non-positive spacing, a non-finite origin, a negative or non-finite k / wall, offsets that are not the
+ *   running sums of n0 n1 n2, w_rows other than 1 or B, a null pointer with NF > 0.
+ *   use_graph    re-attaching fields of the same sizes is a copy: the cached transition replays.  Another NF, a pool or weights that
+ *                outgrow their buffer, or another w_rows rebuild once; a fielded call followed by an unfielded one on the same
+ *                topology rebuilds and gives the bits of a topology that never had fields.
+ * hd_restraint_field_energy: out[B] = U_fld in double for positions x[B][N][3] (fp32, data units) under the topology's mask.
+ * hd_restraint_field_energy_framed: the same with tau = mean_F(x) - mean_F(x_known); shift3 [B][3] double receives tau (NULL: not
+ *   wanted).  Both are stream-ordered and need attached restraints (HD_E_STATE otherwise); without fields they write 0. */
+#define HD_MAX_FIELDS 8
+int hd_restraint_fields(hd_topology* topo, int NF, const float* values, const long long* offsets, const int* dims, const float* geom,
+                        const float* weights, int w_rows, void* stream);
+int hd_restraint_field_energy(hd_handle* h, hd_topology* topo, const float* x, double* out, void* stream);
+int hd_restraint_field_energy_framed(hd_handle* h, hd_topology* topo, const float* x, const uint8_t* fixed_mask, const float* x_known,
+                                     double* out, double* shift3, void* stream);
+
 /* ---- Steered sampling (ABI 12, additive; no reference counterpart): sequential Monte-Carlo steering of a restrained path loop.
  * The batch is G groups of P rows (particles); group g owns rows g P .. g P + P - 1, which the CALLER guarantees to have equal
  * masks, contexts and restraint rows.  At every transition k, behind the network call, guidance and the restraint update of eps^:
