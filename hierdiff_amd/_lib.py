@@ -107,6 +107,9 @@ SIGNATURES = {
     "hd_nll_finish": (C.c_int, [_VP, _VP, _FP, _FP, C.c_int, _FP, _FP, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_float),
                                 C.c_int, C.c_int, _VP, _FP, _VP]),
     "hd_inpaint_decode_fix": (C.c_int, [_VP, _VP, _U8P, _FP, _FP, _FP, _FP, _VP]),
+    "hd_inpaint_parts": (C.c_int, [_VP, _VP, _U8P, _VP]),
+    "hd_inpaint_replace": (C.c_int, [_VP, _VP, _FP, _U8P, _U8P, _FP, C.c_float, C.c_float, C.c_uint64, C.c_uint64, C.c_uint32, _VP]),
+    "hd_inpaint_decode_fix_parts": (C.c_int, [_VP, _VP, _U8P, _U8P, _FP, _FP, _FP, _FP, _VP]),
     "hd_topology_nodes": (C.c_int, [_VP, _VP]),
     "hd_topology_nodes_device": (C.c_int, [_VP, _VP, _VP]),
     "hd_edge_layer_forward": (C.c_int, [_VP, _VP, C.c_int] + [_FP] * 9 + [_VP]),

@@ -172,6 +172,7 @@ struct PathKey {
     unsigned long long weights_gen, sched_gen, path_gen, ip_gen;
     unsigned long long rs_gen, rs_rows_gen;                  // restrained transition: the topology's tables, the handle's rows (0 / 0: plain)
     int rs_frame;                                            // 1: its restraints act in the known fragments' frame (hd_restraint_frame)
+    int ip_parts;                                            // 1: an inpainting transition with per-channel masks (hd_inpaint_parts)
     unsigned long long rs_fld_gen;                           // its restraints hold fields (hd_restraint_fields): their buffers, NF, rows (0: none)
     int st_P;                                                // steered transition: particles per group, rho, the topology's steering
     double st_ess;                                           // buffers, the handle's rows (all 0: not steered)
@@ -180,7 +181,7 @@ struct PathKey {
         return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape && noise_rows == o.noise_rows &&
                k_lo == o.k_lo && resamplings == o.resamplings && w_rows == o.w_rows && phi == o.phi && seed == o.seed &&
                weights_gen == o.weights_gen && sched_gen == o.sched_gen && path_gen == o.path_gen && ip_gen == o.ip_gen &&
-               rs_gen == o.rs_gen && rs_rows_gen == o.rs_rows_gen && rs_frame == o.rs_frame && rs_fld_gen == o.rs_fld_gen && st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen &&
+               rs_gen == o.rs_gen && rs_rows_gen == o.rs_rows_gen && rs_frame == o.rs_frame && ip_parts == o.ip_parts && rs_fld_gen == o.rs_fld_gen && st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen &&
                st_rows_gen == o.st_rows_gen;
     }
 };
@@ -246,6 +247,10 @@ struct hd_topology {
     // the inpainting loops: the fixed mask / known values
     uint8_t* ip_fixed;
     float* ip_known;
+    // hd_inpaint_parts: the library-owned channel mask [B*N*F] (allocated by the first attach, at an address captured transitions
+    // keep) and whether it is attached - then ip_fixed means "position known"
+    uint8_t* ip_parts;
+    bool ip_parts_on;
     // hd_sample_path / hd_sample_path_inpaint (hd_path_graph_builds)
     GraphSlot<PathKey> g_path;
     // hd_sample_path_guided: the second network output, and for the captured guided transition - a graph of its own next to the
@@ -868,6 +873,7 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
         if (p) (void)hipFree(p);
     if (t->ip_fixed) (void)hipFree(t->ip_fixed);
     if (t->ip_known) (void)hipFree(t->ip_known);
+    if (t->ip_parts) (void)hipFree(t->ip_parts);
     if (t->nll_eps) (void)hipFree(t->nll_eps);
     if (t->nll_xh) (void)hipFree(t->nll_xh);
     if (t->nll_err) (void)hipFree(t->nll_err);

@@ -20,6 +20,7 @@ struct LoopIO {
     const float *ctx_u, *w;                    // guidance: second context, scales
     const uint8_t* fixed;                      // inpainting: mask, known values
     const float* known;
+    const uint8_t* fixed_h;                    // ... with per-channel masks (hd_inpaint_parts): `fixed` is the position mask
     const float* xh;                           // scoring: data, accumulator, e_t table
     double* acc;
     float* err;
@@ -307,17 +308,23 @@ extern "C" int hd_set_inpaint_schedule(hd_handle* h, int T, const float* coef4) 
     return HD_OK;
 }
 
-// On io.z at position io.row with draw `d`: put the known rows back (io.fixed / io.known), or - `jump` - go back to the departure level
-static int inpaint_launch(hd_handle* h, hd_topology* t, const LoopIO& io, bool jump, LoopIO::Draw d, uint64_t seed, const float* coef) {
+// On io.z at position io.row with draw `d`: put the known rows back (io.fixed / io.known; io.fixed_h: per channel), or - `jump` - go
+// back to the departure level
+// `coef`: the device rows read at the position; null: the host `row` {alpha_s, sigma_s, alpha_t|s, sigma_t|s} by value.
+static int inpaint_launch(hd_handle* h, hd_topology* t, const LoopIO& io, bool jump, LoopIO::Draw d, uint64_t seed, const float* coef,
+                          const float* row = nullptr) {
     ProfScope ps(h, io.s, 2);
     InpaintArgs a;
     a.z = io.z; a.nm = t->nm_bytes; a.fixed = jump ? nullptr : io.fixed; a.known = jump ? nullptr : io.known; a.coef = coef;
+    a.fixed_h = jump ? nullptr : io.fixed_h;
+    for (int i = 0; i < 4; ++i) a.row[i] = row ? row[i] : 0.f;
     a.seed = seed; a.sample_base = io.base;
     a.draw = d.value; a.step = io.row; a.draw_ptr = d.word; a.step_ptr = io.step; a.base_ptr = io.base_w;
     a.B = t->B; a.N = t->N; a.D = h->D;
     const size_t lds = (size_t)t->N * h->D * sizeof(float);
     if (jump) hipLaunchKernelGGL(k_inpaint_jump, dim3(t->B), dim3(256), lds, io.s, a);
-    else hipLaunchKernelGGL(k_inpaint_replace, dim3(t->B), dim3(256), lds, io.s, a);
+    else if (io.fixed_h) hipLaunchKernelGGL(k_inpaint_replace<true>, dim3(t->B), dim3(256), lds, io.s, a);
+    else hipLaunchKernelGGL(k_inpaint_replace<false>, dim3(t->B), dim3(256), lds, io.s, a);
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
@@ -963,6 +970,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
                                                  "(duplicated particles would never diverge: hd_steer_detach)");
         if (c.noise_rows != topo->B) return fail(HD_E_INVALID, "path loop: steering needs every row's own noise (noise_rows must be B)");
     }
+    const uint8_t* parts = (R && topo->ip_parts_on) ? topo->ip_parts : nullptr;      // calls that do not inpaint ignore the attachment
     const int rounds = R ? R : 1;
     auto transition = [&](const LoopIO& io) -> int {         // all rounds of one transition; io.row is the path position
         for (int j = 0; j < rounds; ++j) {
@@ -987,7 +995,8 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     };
     if (!c.use_graph) {
         LoopIO io{};
-        io.z = c.z; io.ctx = c.context; io.fixed = c.fixed_mask; io.known = c.xh_known; io.base = c.sample_id_base; io.s = c.s;
+        io.z = c.z; io.ctx = c.context; io.fixed = c.fixed_mask; io.known = c.xh_known; io.fixed_h = parts; io.base = c.sample_id_base;
+        io.s = c.s;
         if (gd) { io.ctx_u = gd->ctx_u; io.w = gd->w; }
         for (int k = k_lo; k < c.k_hi; ++k) {
             io.row = k; io.tcur = h->d_tau + pt.t_h[k];
@@ -1010,6 +1019,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     key.k_lo = c.raw_x ? k_lo : 0; key.resamplings = R; key.seed = c.seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
     key.path_gen = pt.gen; key.ip_gen = R ? h->ip_gen : 0; key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
     key.rs_gen = rsn ? topo->rs_gen : 0; key.rs_rows_gen = rsn ? h->rs_rows.gen : 0; key.rs_frame = framed ? 1 : 0;
+    key.ip_parts = parts ? 1 : 0;
     key.rs_fld_gen = rsn && topo->rs_NF ? topo->rs_fld_gen : 0;
     key.st_P = stn ? topo->st_P : 0; key.st_ess = stn ? topo->st_ess : 0.0; key.st_gen = stn ? topo->st_gen : 0;
     key.st_rows_gen = stn ? h->st_rows.gen : 0;
@@ -1019,6 +1029,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     auto body = [&]() -> int {
         LoopIO io = loop_io_captured(h, R ? h->d_ipdraw : h->d_draw, rs);
         io.z = topo->zbuf; io.ctx = c.context ? topo->ctxbuf : nullptr; io.fixed = topo->ip_fixed; io.known = topo->ip_known;
+        io.fixed_h = parts;
         if (gd) { io.ctx_u = topo->ctxu_buf; io.w = topo->wbuf; }
         HD_TRY(transition(io));
         hipLaunchKernelGGL(k_path_advance, dim3(1), dim3(64), 0, rs, w);
@@ -1432,9 +1443,60 @@ extern "C" int hd_inpaint_decode_fix(hd_handle* h, hd_topology* topo, const uint
     topo_use(topo, s);
     ProfScope ps(h, s, 2);
     InpaintFixArgs a;
-    a.nm = topo->nm_bytes; a.fixed = fixed_mask; a.x_known = x_known; a.h_known = h_known; a.x = x; a.hfeat = hfeat;
+    a.nm = topo->nm_bytes; a.fixed = fixed_mask; a.fixed_h = nullptr; a.x_known = x_known; a.h_known = h_known; a.x = x; a.hfeat = hfeat;
     a.B = topo->B; a.N = topo->N; a.F = h->F;
-    hipLaunchKernelGGL(k_inpaint_decode_fix, dim3((topo->B + 3) / 4), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_inpaint_decode_fix<false>, dim3((topo->B + 3) / 4), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+// ----------------------------------------------------------------------------- partial inpainting: positions / feature channels
+
+extern "C" int hd_inpaint_parts(hd_handle* h, hd_topology* topo, const uint8_t* fixed_h, void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_inpaint_parts: null handle/topology");
+    if (topo->h != h) return fail(HD_E_INVALID, "hd_inpaint_parts: topology belongs to another handle");
+    if (!fixed_h) { topo->ip_parts_on = false; return HD_OK; }
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    topo->ip_parts_on = false;
+    const size_t n = (size_t)topo->B * topo->N * h->F;      // a topology's shape is fixed: the buffer never moves
+    if (!topo->ip_parts) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->ip_parts), std::max<size_t>(n, 1)));
+    if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(s, h->ev_last, 0));      // a replay on another stream may still read the old bytes
+    if (n) HIP_TRY(hipMemcpyAsync(topo->ip_parts, fixed_h, n, hipMemcpyDeviceToDevice, s));
+    topo->ip_parts_on = true;
+    return HD_OK;
+}
+
+extern "C" int hd_inpaint_replace(hd_handle* h, hd_topology* topo, float* z, const uint8_t* fixed_x, const uint8_t* fixed_h,
+                                  const float* xh_known, float alpha_s, float sigma_s, uint64_t seed, uint64_t sample_id_base,
+                                  uint32_t draw, void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_inpaint_replace: null handle/topology");
+    if (topo->h != h) return fail(HD_E_INVALID, "hd_inpaint_replace: topology belongs to another handle");
+    if (!z || !fixed_x || !xh_known) return fail(HD_E_INVALID, "hd_inpaint_replace: null z / fixed_x / xh_known");
+    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "hd_inpaint_replace: N * D floats exceed one workgroup's LDS");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    LoopIO io{};
+    io.z = z; io.fixed = fixed_x; io.fixed_h = fixed_h; io.known = xh_known; io.base = sample_id_base; io.s = s;
+    const float row[4] = {alpha_s, sigma_s, 0.f, 0.f};
+    return inpaint_launch(h, topo, io, false, LoopIO::Draw{draw, nullptr}, seed, nullptr, row);
+}
+
+extern "C" int hd_inpaint_decode_fix_parts(hd_handle* h, hd_topology* topo, const uint8_t* fixed_x, const uint8_t* fixed_h,
+                                           const float* x_known, const float* h_known, float* x, float* hfeat, void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_inpaint_decode_fix_parts: null handle/topology");
+    if (topo->h != h) return fail(HD_E_INVALID, "hd_inpaint_decode_fix_parts: topology belongs to another handle");
+    if (!fixed_x || !fixed_h || !x_known || !h_known || !x || !hfeat) return fail(HD_E_INVALID, "hd_inpaint_decode_fix_parts: null tensor");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    ProfScope ps(h, s, 2);
+    InpaintFixArgs a;
+    a.nm = topo->nm_bytes; a.fixed = fixed_x; a.fixed_h = fixed_h; a.x_known = x_known; a.h_known = h_known; a.x = x; a.hfeat = hfeat;
+    a.B = topo->B; a.N = topo->N; a.F = h->F;
+    hipLaunchKernelGGL(k_inpaint_decode_fix<true>, dim3((topo->B + 3) / 4), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }

@@ -13,9 +13,11 @@
 struct InpaintArgs {
     float* z;                   // [B][N][D] in place: z_gen -> z_s (replace), z_s -> z_t (jump)
     const uint8_t* nm;          // [B*N] node mask bytes
-    const uint8_t* fixed;       // [B*N] fixed mask bytes (replace only)
+    const uint8_t* fixed;       // [B*N] fixed mask bytes (replace only); PARTS: "position known"
+    const uint8_t* fixed_h;     // PARTS only: [B*N][D - 3] "feature channel known"
     const float* known;         // [B][N][D] normalised known values (replace only)
     const float* coef;          // [K][4] {alpha_s, sigma_s, alpha_t|s, sigma_t|s}, one row per path position (arrival level s)
+    float row[4];               // the row by value when coef is null (hd_inpaint_replace)
     uint64_t seed, sample_base;
     uint32_t draw;
     int step;
@@ -28,6 +30,11 @@ struct InpaintArgs {
 // steps 2-3 of the algorithm (include/hierdiff_hip.h): z_kn = alpha_s known + sigma_s e_kn on the fixed rows, shifted so that the
 // fixed block keeps the centre of gravity the generated rows had, then the masked mean removal of the plain step.
 // A molecule without fixed nodes is left untouched.  Dynamic LDS = N * D floats.
+// PARTS (hd_inpaint_parts, hd_inpaint_replace): an element is replaced when its own mask says so - a position component by
+// `fixed`, a feature channel by `fixed_h` - and the shift and its count run over the position-fixed nodes alone.  A molecule
+// without them has no frame: its known channels are written in place and the x part keeps its bits.  Same expressions in the same
+// order as the whole-node form, so coinciding masks give its bits.
+template <bool PARTS>
 __global__ __launch_bounds__(256) void k_inpaint_replace(InpaintArgs a) {
     extern __shared__ float ip_s[];                // [N * D] blended z before the final re-centring
     __shared__ float red[4];
@@ -37,11 +44,23 @@ __global__ __launch_bounds__(256) void k_inpaint_replace(InpaintArgs a) {
     float nf = 0.f;
     for (int nn = tid; nn < N; nn += 256) nf += (a.fixed[b * N + nn] && a.nm[b * N + nn]) ? 1.f : 0.f;
     nf = block_sum4(nf, red, tid);
-    if (nf == 0.f) return;                         // uniform over the workgroup
+    if (!PARTS && nf == 0.f) return;               // uniform over the workgroup
     const uint64_t sid = (a.base_ptr ? (uint64_t)*a.base_ptr : a.sample_base) + (uint64_t)b;
     const uint32_t draw = a.draw_ptr ? *a.draw_ptr : a.draw;
-    const float* cf = a.coef + (size_t)(a.step_ptr ? *a.step_ptr : a.step) * 4;
-    const float alpha_s = cf[0], sigma_s = cf[1];
+    float alpha_s = a.row[0], sigma_s = a.row[1];
+    if (a.coef) {
+        const float* cf = a.coef + (size_t)(a.step_ptr ? *a.step_ptr : a.step) * 4;
+        alpha_s = cf[0]; sigma_s = cf[1];
+    }
+    if (PARTS && nf == 0.f) {                      // uniform too: no frame, so no shift and no re-centring
+        for (int e = tid; e < total; e += 256) {
+            const int nn = e / D, c = e - nn * D;
+            if (c < 3 || !a.nm[b * N + nn] || !a.fixed_h[((size_t)b * N + nn) * (D - 3) + (c - 3)]) continue;
+            const size_t g = ((size_t)b * N + nn) * D + c;
+            a.z[g] = alpha_s * a.known[g] + sigma_s * philox_normal(a.seed, sid, draw, (uint32_t)e);
+        }
+        return;
+    }
     float sg[3] = {0.f, 0.f, 0.f}, sk[3] = {0.f, 0.f, 0.f}, cnt = 0.f;
     for (int e = tid; e < total; e += 256) {
         const int nn = e / D, c = e - nn * D;
@@ -49,8 +68,9 @@ __global__ __launch_bounds__(256) void k_inpaint_replace(InpaintArgs a) {
         const bool fx = valid && a.fixed[b * N + nn] != 0;
         const size_t g = ((size_t)b * N + nn) * D + c;
         const float zg = a.z[g];
+        const bool rep = (!PARTS || c < 3) ? fx : (valid && a.fixed_h[((size_t)b * N + nn) * (D - 3) + (c - 3)] != 0);
         float v = zg;
-        if (fx) v = alpha_s * a.known[g] + sigma_s * philox_normal(a.seed, sid, draw, (uint32_t)e);
+        if (rep) v = alpha_s * a.known[g] + sigma_s * philox_normal(a.seed, sid, draw, (uint32_t)e);
         ip_s[e] = v;
         if (c < 3) {
             if (fx) {
@@ -139,9 +159,12 @@ __global__ __launch_bounds__(256) void k_inpaint_jump(InpaintArgs a) {
 
 // Behind the final decode, in data units: h = h_known and x = x_known + (mean_fixed(x) - mean_fixed(x_known)) on the fixed rows - the
 // returned fragments are a pure translation of the given ones.  One wavefront per molecule.
+// PARTS (hd_inpaint_decode_fix_parts): x on the nodes of `fixed`, h per channel of `fixed_h`; a molecule without position-fixed
+// nodes keeps its x.
 struct InpaintFixArgs {
     const uint8_t* nm;
     const uint8_t* fixed;
+    const uint8_t* fixed_h;     // PARTS only: [B*N][F]
     const float* x_known;       // [B][N][3]
     const float* h_known;       // [B][N][F]
     float* x;                   // [B][N][3]
@@ -149,6 +172,7 @@ struct InpaintFixArgs {
     int B, N, F;
 };
 
+template <bool PARTS>
 __global__ void k_inpaint_decode_fix(InpaintFixArgs a) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -168,6 +192,13 @@ __global__ void k_inpaint_decode_fix(InpaintFixArgs a) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) { sd[k] += __shfl_xor(sd[k], o); sk[k] += __shfl_xor(sk[k], o); }
     }
+    if (PARTS) {
+        for (int nn = lane; nn < a.N; nn += 64) {
+            const size_t r = (size_t)b * a.N + nn;
+            if (!a.nm[r]) continue;
+            for (int f = 0; f < a.F; ++f) { if (a.fixed_h[r * a.F + f]) a.hfeat[r * a.F + f] = a.h_known[r * a.F + f]; }
+        }
+    }
     if (nf == 0.f) return;
     float shift[3];
 #pragma unroll
@@ -177,6 +208,6 @@ __global__ void k_inpaint_decode_fix(InpaintFixArgs a) {
         if (!(a.nm[r] && a.fixed[r])) continue;
 #pragma unroll
         for (int k = 0; k < 3; ++k) a.x[r * 3 + k] = a.x_known[r * 3 + k] + shift[k];
-        for (int f = 0; f < a.F; ++f) a.hfeat[r * a.F + f] = a.h_known[r * a.F + f];
+        if (!PARTS) { for (int f = 0; f < a.F; ++f) a.hfeat[r * a.F + f] = a.h_known[r * a.F + f]; }
     }
 }

@@ -927,13 +927,14 @@ class DiffusionQM9(_Base):
     def _run(self, st, pl, z, k_lo, k_hi, noise, inpaint=None):
         """Transitions k_lo .. k_hi-1 of the plan `pl` (positions counted from the start of the chain) on z [B,N,D] in place; returns
         (z, chain - the sink of a recording plan, kept in `st` for the next piece - or None).  `noise` = (randn_x, randn_h, rows,
-        seed, sample id base): injected rows, or None, None and the generator's key.  `inpaint` = (fixed u8 [B*N], known xh, R).
+        seed, sample id base): injected rows, or None, None and the generator's key.  `inpaint` = (fixed u8 [B*N], known xh, R) or,
+        for partial masks, (fixed_x u8 [B*N], known xh, R, fixed_h u8 [B*N*F]): the channel bytes are attached like the restraints.
         Restraints, then the sink, are attached to the topology for the time of the loop.  The one place that picks the loop:
         guided -> hd_sample_path_guided; a path -> hd_sample_path(_inpaint); else the every-step hd_sample_loop(_inpaint), whose
         steps count down from T."""
         lib, topo = _lib.load(), st.topo_loop
         rx, rh, rows, seed, base = noise
-        fixed, known, R = inpaint if inpaint is not None else (None, None, 0)
+        fixed, known, R, parts = (tuple(inpaint) + (None,))[:4] if inpaint is not None else (None, None, 0, None)
         zz = z if st.tail is None else torch.cat([z, st.tail], dim=1).contiguous()      # a pocket's fixed rows ride along
         mol = -1 if st.tail is None else st.N
         common = (_ptr(rx), _ptr(rh), rows, seed, base, int(self.use_graph))
@@ -945,6 +946,8 @@ class DiffusionQM9(_Base):
                 self._steer_open(st.h, topo, st.tabs, steer, int(k_lo) == 0, st.dev)
             if pl.frames is not None:
                 st.chain = self._chain_open(st.h, topo, st.tabs, pl.frames, pl.record, st.B, st.N, st.dev, st.chain)
+            if parts is not None:
+                _lib.check(lib.hd_inpaint_parts(st.h, topo.ptr, parts.data_ptr(), st.stream), "hd_inpaint_parts")
             if st.g is not None:
                 _lib.check(lib.hd_sample_path_guided(st.h, topo.ptr, zz.data_ptr(), st.ctx.data_ptr(), st.g.ctx_u.data_ptr(),
                                                      st.g.w.data_ptr(), st.g.rows, st.g.phi, int(k_lo), int(k_hi), *common,
@@ -960,6 +963,8 @@ class DiffusionQM9(_Base):
                 _lib.check(fn(st.h, topo.ptr, zz.data_ptr(), _ptr(st.ctx), mol, int(lo), int(hi), *common, st.stream), name)
             ran = True
         finally:
+            if parts is not None:
+                _lib.check(lib.hd_inpaint_parts(st.h, topo.ptr, None, st.stream), "hd_inpaint_parts")
             if steer is not None:
                 self._steer_close(topo, steer, st.B, st.dev, ran)
             if pl.frames is not None:
@@ -971,7 +976,8 @@ class DiffusionQM9(_Base):
     def _decode(self, st, z, node_mask, edge_mask, fix_noise, noise, chain=None, inpaint=None, eps=None):
         """(x, h) of z_0 - and `chain` with cat(x, h) as its frame 0 - : the network call at t = 0 (guided as the loop's are; `eps`:
         the caller has made it) and the final decode.  `noise`: the sample id base (the generator's draw T + 1) or an injected
-        (randn_x, randn_h) pair, None = torch.randn.  `inpaint` = (fixed u8, x_known, h_known): the known rows are put back."""
+        (randn_x, randn_h) pair, None = torch.randn.  `inpaint` = (fixed u8, x_known, h_known): the known rows are put back; with a
+        fourth element (fixed_h u8 [B*N*F]) the first is the position mask and the known parts are."""
         if eps is None:
             eps = self._decode_eps(st.topo, z, st.ctx, st.g)
         philox = (int(noise), self.T + 1) if isinstance(noise, (int, np.integer)) else None
@@ -979,9 +985,14 @@ class DiffusionQM9(_Base):
                                   philox=philox)
         if inpaint is not None:
             x, h = x.contiguous(), h.contiguous()
-            _lib.check(_lib.load().hd_inpaint_decode_fix(st.h, st.topo.ptr, inpaint[0].data_ptr(), inpaint[1].data_ptr(),
-                                                         inpaint[2].data_ptr(), x.data_ptr(), h.data_ptr(), st.stream),
-                       "hd_inpaint_decode_fix")
+            if len(inpaint) > 3 and inpaint[3] is not None:
+                _lib.check(_lib.load().hd_inpaint_decode_fix_parts(st.h, st.topo.ptr, inpaint[0].data_ptr(), inpaint[3].data_ptr(),
+                                                                   inpaint[1].data_ptr(), inpaint[2].data_ptr(), x.data_ptr(),
+                                                                   h.data_ptr(), st.stream), "hd_inpaint_decode_fix_parts")
+            else:
+                _lib.check(_lib.load().hd_inpaint_decode_fix(st.h, st.topo.ptr, inpaint[0].data_ptr(), inpaint[1].data_ptr(),
+                                                             inpaint[2].data_ptr(), x.data_ptr(), h.data_ptr(), st.stream),
+                           "hd_inpaint_decode_fix")
         if chain is None:
             return x, h
         chain[0] = torch.cat([x, h], dim=2)
@@ -1674,16 +1685,29 @@ class DiffusionQM9(_Base):
             self._inpaint_tabs = tabs
         return tabs
 
-    def _inpaint_setup(self, node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, pl=None):
+    def _inpaint_setup(self, node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, pl=None, fixed_x_mask=None,
+                       fixed_h_mask=None):
         """Argument checks of the inpainting entry points (ValueError / NotImplementedError before anything is queued), then the
         device state with the inpainting extras on top: the fixed rows' mask bytes, their known values (normalised) and R.  `pl`: the
-        call's plan (None: the model's path defaults, unguided - `inpaint_steps`)."""
+        call's plan (None: the model's path defaults, unguided - `inpaint_steps`).  fixed_x_mask / fixed_h_mask: partial masks
+        (each defaults to `fixed_mask`); then `fm_u8` is the position mask and `fh_u8` [B*N*F] the channel mask (else None)."""
         if node_mask.dim() != 3 or node_mask.shape[2] != 1:
             raise ValueError(f"node_mask must be [B, N, 1], got {tuple(node_mask.shape)}")
         B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
         F_ = self.in_node_nf
-        if tuple(fixed_mask.shape) != (B, N, 1):
+        parts = fixed_x_mask is not None or fixed_h_mask is not None
+        if fixed_mask is None:
+            if fixed_x_mask is None or fixed_h_mask is None:
+                raise ValueError("fixed_mask may be None only when fixed_x_mask and fixed_h_mask are both given")
+        elif tuple(fixed_mask.shape) != (B, N, 1):
             raise ValueError(f"fixed_mask must be [{B}, {N}, 1], got {tuple(fixed_mask.shape)}")
+        if parts:
+            fixed_x_mask = fixed_mask if fixed_x_mask is None else fixed_x_mask
+            fixed_h_mask = fixed_mask if fixed_h_mask is None else fixed_h_mask
+            if tuple(fixed_x_mask.shape) != (B, N, 1):
+                raise ValueError(f"fixed_x_mask must be [{B}, {N}, 1], got {tuple(fixed_x_mask.shape)}")
+            if tuple(fixed_h_mask.shape) not in ((B, N, 1), (B, N, F_)):
+                raise ValueError(f"fixed_h_mask must be [{B}, {N}, 1] or [{B}, {N}, {F_}], got {tuple(fixed_h_mask.shape)}")
         if tuple(x_known.shape) != (B, N, self.n_dims):
             raise ValueError(f"x_known must be [{B}, {N}, {self.n_dims}], got {tuple(x_known.shape)}")
         if tuple(h_known.shape) != (B, N, F_):
@@ -1693,9 +1717,18 @@ class DiffusionQM9(_Base):
         if (self.T + 2) * 3 * int(resamplings) >= 2 ** 32:
             raise ValueError("(timesteps + 2) * 3 * resamplings exceeds the generator's 32-bit draw index")
         dev = node_mask.device
-        nmb, fmb = node_mask.to(torch.bool), fixed_mask.to(dev).to(torch.bool)
-        if bool((fmb & ~nmb).any()):
-            raise ValueError("fixed_mask must be a subset of node_mask")
+        nmb = node_mask.to(torch.bool)
+        if parts:
+            fmb = fixed_x_mask.to(dev).to(torch.bool)
+            fhb = fixed_h_mask.to(dev).to(torch.bool).expand(B, N, F_)
+            if bool((fmb & ~nmb).any()):
+                raise ValueError("fixed_x_mask must be a subset of node_mask")
+            if bool((fhb & ~nmb).any()):
+                raise ValueError("fixed_h_mask must be a subset of node_mask")
+        else:
+            fmb = fixed_mask.to(dev).to(torch.bool)
+            if bool((fmb & ~nmb).any()):
+                raise ValueError("fixed_mask must be a subset of node_mask")
         if edge_mask is not None and edge_mask.numel() != B * N * N:
             raise ValueError(f"edge_mask must hold {B} x {N} x {N} entries")
         if self.dynamics.context_node_nf > 0 and context is None:
@@ -1709,16 +1742,20 @@ class DiffusionQM9(_Base):
         # the model's own `normalize`, masked by the fixed rows (the library ignores the others)
         xh_known = torch.cat([xk / float(self.norm_values[0]),
                               (hk - float(self.norm_biases[1] or 0.0)) / float(self.norm_values[1])], dim=2)
-        xh_known = torch.where(fmb, xh_known, torch.zeros_like(xh_known)).contiguous()
+        keep = torch.cat([fmb.expand(B, N, self.n_dims), fhb], dim=2) if parts else fmb
+        xh_known = torch.where(keep, xh_known, torch.zeros_like(xh_known)).contiguous()
         fm_u8 = fmb.reshape(B * N).to(torch.uint8).contiguous()
-        st.update(pl=pl, xk=xk, hk=hk, xh_known=xh_known, fm_u8=fm_u8, R=int(resamplings), K=None if pl.path is None else pl.K)
+        fh_u8 = fhb.reshape(B * N * F_).to(torch.uint8).contiguous() if parts else None
+        st.update(pl=pl, xk=xk, hk=hk, xh_known=xh_known, fm_u8=fm_u8, fh_u8=fh_u8, R=int(resamplings),
+                  K=None if pl.path is None else pl.K)
         return st
 
     @torch.no_grad()
     def inpaint_steps(self, z, s_hi: int, s_lo: int, node_mask, fixed_mask, x_known, h_known, context=None, resamplings: int = 1,
                       sample_id_base: int = 0, edge_mask=None, *, restraints=None, restraint_scale=None, restraint_schedule=None,
-                      restraint_clip=None, restraint_frame: Optional[str] = None):
+                      restraint_clip=None, restraint_frame: Optional[str] = None, fixed_x_mask=None, fixed_h_mask=None):
         """The steps s = s_hi-1 ... s_lo of `sample_inpaint`'s loop on a given z_{s_hi} [B,N,D] (normalised units); returns z_{s_lo}.
+        fixed_x_mask / fixed_h_mask: partial masks, as in `sample_inpaint`.
         Draws are keyed by the step, so a chain cut into pieces gives the bits of the whole.  restraint_frame="known" (or the
         model's `restraint_frame`): the restraints of `sample_inpaint`, on the path loop; without it the restraint keywords and the
         model's restraint attributes are ignored, as they always were."""
@@ -1727,13 +1764,13 @@ class DiffusionQM9(_Base):
         if _rs.check_frame(self, restraint_frame):
             B, N = self._batch_of(node_mask)
             pl = self._plan("inpaint_steps", "inpaint", B=B, N=N, guided=False, **given(locals()))
-        st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, pl)
+        st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, pl, fixed_x_mask, fixed_h_mask)
         if tuple(z.shape) != (st.B, st.N, self.n_dims + self.in_node_nf) or not (0 <= s_lo <= s_hi <= self.T):
             raise ValueError("z must be [B, N, 3 + F] and 0 <= s_lo <= s_hi <= timesteps")
         z = z.detach().to(st.dev, torch.float32).clone().contiguous()
         n_loop = st.pl.K                                 # s counts path positions from the t = 0 end (the grid itself by default)
         return self._run(st, st.pl, z, n_loop - int(s_hi), n_loop - int(s_lo), (None, None, st.B, self.seed, sample_id_base),
-                         (st.fm_u8, st.xh_known, st.R))[0]
+                         (st.fm_u8, st.xh_known, st.R, st.fh_u8))[0]
 
     @torch.no_grad()
     def sample_inpaint(self, node_mask: torch.Tensor, fixed_mask: torch.Tensor, x_known: torch.Tensor, h_known: torch.Tensor,
@@ -1742,7 +1779,7 @@ class DiffusionQM9(_Base):
                        timesteps: Optional[Sequence[int]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                        solver: Optional[str] = None, keep_frames: Optional[int] = None, record: Optional[str] = None,
                        restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-                       restraint_frame: Optional[str] = None):
+                       restraint_frame: Optional[str] = None, fixed_x_mask=None, fixed_h_mask=None):
         """(x, h) on the device for molecules whose `fixed_mask` [B,N,1] nodes are known: `x_known` [B,N,3] / `h_known` [B,N,F] in
         data units (what `sample` returns; rows outside `fixed_mask` are ignored, the frame of the positions is free).  The free
         nodes are sampled around them by the replacement method, `resamplings` network calls per step (RePaint for > 1), inside
@@ -1762,7 +1799,16 @@ class DiffusionQM9(_Base):
         for the plain loop).  The call then returns one more element, a dict with 'restraint_energy' [B,3] float64 (evaluated in
         the known frame), 'frame_shift' [B,3] float64 (the translation tau of the returned x) and 'x_known_frame' [B,N,3] = x - tau,
         the molecule in the coordinates of the input (known rows equal `x_known` up to fp32 rounding).  Without it restraints are
-        refused, as before: the model's frame moves with the known fragments."""
+        refused, as before: the model's frame moves with the known fragments.
+        PARTIAL MASKS: fixed_x_mask [B,N,1] ("the position of this node is known") and fixed_h_mask [B,N,1] or [B,N,F] ("this
+        feature channel of this node is known") replace `fixed_mask` part by part; each defaults to `fixed_mask`, which may be None
+        when both are given.  Features known and positions free lays a given bag of fragments out in 3-D; positions known and features
+        (or some channels) free fills a given shape.  Rows / channels of x_known / h_known outside their mask are ignored.  Returned:
+        h = h_known exactly on the known channels, x = x_known translated as one block on the position-known nodes; everything else is
+        sampled.  Position components of a node are known together.  With restraint_frame="known" the frame, 'frame_shift' and
+        'x_known_frame' belong to the position-known nodes; a node with known features and a free position is free and is pushed, and
+        a molecule without position-known nodes reads the tables in the model's frame (tau = 0).  A mechanism only: how well free
+        positions fit known features, and which `resamplings` helps, depends on the checkpoint."""
         from . import restraints as _rs
         if not _rs.check_frame(self, restraint_frame):
             _rs.refuse(self, "sample_inpaint", restraints, ": inpainting re-centres on the known fragments, so its frame moves")
@@ -1770,18 +1816,18 @@ class DiffusionQM9(_Base):
         _st.refuse(self, "sample_inpaint")
         B, N = self._batch_of(node_mask)
         pl = self._plan("sample_inpaint", "inpaint", B=B, N=N, **given(locals()))            # every keyword error before any shape check
-        st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, pl)
+        st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, pl, fixed_x_mask, fixed_h_mask)
         z = torch.empty((st.B, st.N, self.n_dims + self.in_node_nf), device=st.dev, dtype=torch.float32)
         _lib.check(_lib.load().hd_noise(st.h, st.topo.ptr, None, None, st.B, self.seed, sample_id_base, 0, 0, z.data_ptr(), st.stream),
                    "hd_noise")
-        noise, inp = (None, None, st.B, self.seed, sample_id_base), (st.fm_u8, st.xh_known, st.R)
+        noise, inp = (None, None, st.B, self.seed, sample_id_base), (st.fm_u8, st.xh_known, st.R, st.fh_u8)
         if self.debug_checks:              # the loop's invariant after every step (host-synchronising, like the reference's asserts)
             for k in range(pl.K):
                 z, chain = self._run(st, pl, z, k, k + 1, noise, inp)
                 self._check_mean_zero(z[:, :, :self.n_dims], node_mask)
         else:
             z, chain = self._run(st, pl, z, 0, pl.K, noise, inp)
-        got = self._decode(st, z, node_mask, edge_mask, False, int(sample_id_base), chain, (st.fm_u8, st.xk, st.hk))
+        got = self._decode(st, z, node_mask, edge_mask, False, int(sample_id_base), chain, (st.fm_u8, st.xk, st.hk, st.fh_u8))
         rr = pl.restraints
         if rr is None or not rr.frame:
             return got
@@ -1808,7 +1854,10 @@ class DiffusionQM9(_Base):
         [keep, n_i, 3], 'chain_h' [keep, n_i, F] and 'chain_t' [keep], as in `sample`.  restraint_frame="known" with restraints /
         restraint_scale (a float or a [len(known)] tensor) / restraint_schedule / restraint_clip: as in `sample_inpaint`, the tables
         in the coordinates of the given fragments; every dict then also holds 'restraint_energy' [3] float64, 'frame_shift' [3]
-        float64 and 'x_known_frame' [n_i, 3]."""
+        float64 and 'x_known_frame' [n_i, 3].
+        PARTIAL KNOWLEDGE: known[i] may hold 'x' only (positions known, features sampled), 'h' only (features known, positions
+        sampled) or both, and optional boolean 'x_mask' [k_i] / 'h_mask' [k_i] or [k_i, F] that narrow them to some rows / channels;
+        k_i is the row count of whichever of 'x' / 'h' is there.  Entries with both and no masks make the whole-node call, as before."""
         device = torch.device(device)
         from . import restraints as _rs
         if not _rs.check_frame(self, restraint_frame):
@@ -1825,23 +1874,43 @@ class DiffusionQM9(_Base):
         sizes = [int(n) for n in sizes]
         if len(sizes) != num or num == 0:
             raise ValueError("sizes must hold one total size per known molecule (and there must be at least one)")
-        ks = []
+        ks, F_ = [], self.in_node_nf
+        parts = any(mol.get("x") is None or mol.get("h") is None or mol.get("x_mask") is not None or mol.get("h_mask") is not None
+                    for mol in known)
         for i, mol in enumerate(known):
-            kx, kh = torch.as_tensor(mol["x"]), torch.as_tensor(mol["h"])
-            if kx.dim() != 2 or kx.shape[1] != self.n_dims or kh.dim() != 2 or tuple(kh.shape) != (kx.shape[0], self.in_node_nf):
-                raise ValueError(f"known[{i}]: need 'x' [k, {self.n_dims}] and 'h' [k, {self.in_node_nf}]")
-            if sizes[i] < max(1, kx.shape[0]):
-                raise ValueError(f"known[{i}]: total size {sizes[i]} is smaller than its {kx.shape[0]} known fragments (or zero)")
-            ks.append(int(kx.shape[0]))
+            kx = None if mol.get("x") is None else torch.as_tensor(mol["x"])
+            kh = None if mol.get("h") is None else torch.as_tensor(mol["h"])
+            if kx is None and kh is None:
+                raise ValueError(f"known[{i}]: need 'x' [k, {self.n_dims}] or 'h' [k, {F_}] (or both)")
+            k = int((kx if kx is not None else kh).shape[0])
+            if (kx is not None and (kx.dim() != 2 or kx.shape[1] != self.n_dims)) or \
+                    (kh is not None and (kh.dim() != 2 or tuple(kh.shape) != (k, F_))):
+                raise ValueError(f"known[{i}]: need 'x' [k, {self.n_dims}] and 'h' [k, {F_}]")
+            if mol.get("x_mask") is not None and (kx is None or tuple(torch.as_tensor(mol["x_mask"]).shape) != (k,)):
+                raise ValueError(f"known[{i}]: 'x_mask' must be [{k}] and go with 'x'")
+            if mol.get("h_mask") is not None and (kh is None or tuple(torch.as_tensor(mol["h_mask"]).shape) not in ((k,), (k, F_))):
+                raise ValueError(f"known[{i}]: 'h_mask' must be [{k}] or [{k}, {F_}] and go with 'h'")
+            if sizes[i] < max(1, k):
+                raise ValueError(f"known[{i}]: total size {sizes[i]} is smaller than its {k} known fragments (or zero)")
+            ks.append(k)
         n_max = max(sizes)
         ar = torch.arange(n_max)
         node_mask = (ar[None, :] < torch.tensor(sizes)[:, None]).unsqueeze(-1)
         fixed_mask = (ar[None, :] < torch.tensor(ks)[:, None]).unsqueeze(-1)
         x_known = torch.zeros(num, n_max, self.n_dims)
-        h_known = torch.zeros(num, n_max, self.in_node_nf)
+        h_known = torch.zeros(num, n_max, F_)
+        fx_mask = torch.zeros(num, n_max, 1, dtype=torch.bool)
+        fh_mask = torch.zeros(num, n_max, F_, dtype=torch.bool)
         for i, mol in enumerate(known):
-            x_known[i, :ks[i]] = torch.as_tensor(mol["x"], dtype=torch.float32)
-            h_known[i, :ks[i]] = torch.as_tensor(mol["h"], dtype=torch.float32)
+            if mol.get("x") is not None:
+                x_known[i, :ks[i]] = torch.as_tensor(mol["x"], dtype=torch.float32)
+                xm = mol.get("x_mask")
+                fx_mask[i, :ks[i], 0] = True if xm is None else torch.as_tensor(xm).to(torch.bool)
+            if mol.get("h") is not None:
+                h_known[i, :ks[i]] = torch.as_tensor(mol["h"], dtype=torch.float32)
+                hm = mol.get("h_mask")
+                fh_mask[i, :ks[i]] = True if hm is None else torch.as_tensor(hm).to(torch.bool).reshape(ks[i], -1)
+        part_kw = dict(fixed_x_mask=fx_mask.to(device), fixed_h_mask=fh_mask.to(device)) if parts else {}
         ctx = None
         if context is not None:
             ctx = torch.zeros([num, n_max, 1]) + torch.as_tensor(context, dtype=torch.float32).cpu()
@@ -1849,7 +1918,7 @@ class DiffusionQM9(_Base):
                 raise ValueError(f"context of shape {tuple(torch.as_tensor(context).shape)} does not broadcast to [{num}, {n_max}, 1]")
         got = self.sample_inpaint(node_mask.to(device), fixed_mask.to(device), x_known.to(device), h_known.to(device),
                                   context=None if ctx is None else ctx.to(device), resamplings=resamplings,
-                                  sample_id_base=sample_id_base, **few)
+                                  sample_id_base=sample_id_base, **few, **part_kw)
         x, h = got[0].cpu(), got[1].cpu()
         out = [{'x': x[i, :sizes[i]].clone(), 'h': h[i, :sizes[i]].clone()} for i in range(num)]
         if ctx is not None:

@@ -12,7 +12,8 @@ molecules and write `sample_results.pkl` = `pickle((results, test_names))` with
 Fragment growing (no reference counterpart): `--known FILE --grow N [--resamplings R]` keeps the fragments of every molecule in
 FILE (this sampler's own output: a list of {'x', 'h'}, pickled alone or as the (results, test_names) tuple, or saved with torch.save
 as `.pt`) and samples N more around each (`DiffusionQM9.sample_grow`); the output format is unchanged, the known fragments come
-first.  Single process only.
+first.  Single process only.  `--known-parts x|h|both` keeps only the positions or only the features of every entry: `--known lead.pkl
+--known-parts h --grow 0` lays a lead's fragments out again, `--known-parts x --grow 0` re-assigns fragments to its positions.
 
 Editing given molecules (no reference counterpart; mechanism only - which settings are chemically useful is for you to validate):
 `--vary FILE --t-start S [--variants V]` noises every molecule of FILE to the grid index S and runs the reverse chain from there
@@ -121,7 +122,8 @@ def read_results(path: str) -> Tuple[List[dict], list]:
 
 def read_known(path: str) -> List[dict]:
     """`--known`: a list of {'x': [k,3], 'h': [k,8]} - `.pt` files through torch.load(weights_only=True), anything else as a pickle
-    of the list or of the sampler's (results, test_names) tuple."""
+    of the list or of the sampler's (results, test_names) tuple.  An entry may hold 'x' alone or 'h' alone (partial knowledge) and
+    boolean 'x_mask' [k] / 'h_mask' [k] or [k,8] (`sample_grow`)."""
     if path.endswith(".pt"):
         obj = torch.load(path, map_location="cpu", weights_only=True)
     else:
@@ -129,9 +131,24 @@ def read_known(path: str) -> List[dict]:
             obj = pickle.load(f)
     if isinstance(obj, tuple) and len(obj) == 2 and isinstance(obj[0], list):
         obj = obj[0]
-    if not isinstance(obj, list) or not all(isinstance(m, dict) and "x" in m and "h" in m for m in obj):
-        raise ValueError(f"{path}: expected a list of {{'x', 'h'}} dicts (the sampler's output format)")
+    if not isinstance(obj, list) or not all(isinstance(m, dict) and ("x" in m or "h" in m) for m in obj):
+        raise ValueError(f"{path}: expected a list of {{'x', 'h'}} dicts (the sampler's output format; 'x' or 'h' alone: that part)")
     return obj
+
+
+def known_parts(known: List[dict], parts: str) -> List[dict]:
+    """`--known-parts`: every entry narrowed to its positions ("x") or its features ("h"); "both" hands them on as they are."""
+    if parts == "both":
+        return known
+    drop = ("h", "h_mask") if parts == "x" else ("x", "x_mask")
+    out = [{k: v for k, v in m.items() if k not in drop} for m in known]
+    if not all(parts in m for m in out):
+        raise ValueError(f"--known-parts {parts}: an entry of --known holds no '{parts}'")
+    return out
+
+
+def known_rows(m: dict) -> int:
+    return int((m["x"] if m.get("x") is not None else m["h"]).shape[0])
 
 
 class _DefaultEta(float):
@@ -166,6 +183,13 @@ def parse_args(argv=None):
     ap.add_argument("--known", default=None,
                     help="fragment growing: file with the fragments to keep (the sampler's output format); needs --grow")
     ap.add_argument("--grow", type=int, default=None, help="fragments to add to each molecule of --known")
+    ap.add_argument("--known-parts", choices=["x", "h", "both"], default=None,
+                    help="keep only that part of every entry of --known (default both): h = the fragments are known and their "
+                         "positions are sampled (`--known lead.pkl --known-parts h --grow 0` lays a lead's fragments out again), x = the "
+                         "positions are known and the fragments are sampled (`--known-parts x --grow 0` re-assigns fragments to a "
+                         "lead's positions); combines with everything --known / --grow combines with.  With --restraint-frame known "
+                         "and --known-parts h there is no frame: the tables are read in the model's frame (tau = 0).  Mechanism "
+                         "only: how well the sampled part fits the known one is for you to validate")
     ap.add_argument("--resamplings", type=int, default=1,
                     help="network calls per diffusion step of --known runs (1: plain replacement; more: RePaint-style resampling)")
     ap.add_argument("--steps", type=int, default=None,
@@ -341,6 +365,8 @@ def parse_args(argv=None):
         ap.error("--eta < 1 does not combine with --known (inpainting takes ancestral steps)")
     if (args.known is None) != (args.grow is None):
         ap.error("--known and --grow go together")
+    if args.known_parts is not None and args.known is None:
+        ap.error("--known-parts needs --known")
     if args.known is not None and (args.grow < 0 or args.resamplings < 1):
         ap.error("--grow must be >= 0 and --resamplings >= 1")
     if args.sample_config:
@@ -434,12 +460,12 @@ def main(argv=None) -> int:
     if args.known is not None:
         if world > 1:
             raise SystemExit("--known runs in a single process")
-        known = read_known(args.known)
+        known = known_parts(read_known(args.known), args.known_parts or "both")
         grown: List[dict] = []
         for b, lo in enumerate(range(0, len(known), max(1, args.batch_size))):
             part = known[lo:lo + max(1, args.batch_size)]
             ctx = None if not args.context else args.context[b % len(args.context)]
-            grown.extend(model.sample_grow(part, [int(m["x"].shape[0]) + args.grow for m in part], dev, context=ctx,
+            grown.extend(model.sample_grow(part, [known_rows(m) + args.grow for m in part], dev, context=ctx,
                                            resamplings=args.resamplings, sample_id_base=lo, **chain))
         write_results(args.out, grown)
         return 0

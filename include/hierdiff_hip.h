@@ -609,6 +609,33 @@ int hd_sample_loop_inpaint(hd_handle* h, hd_topology* topo, float* z, const floa
  * x, x_known device [B,N,3]; hfeat, h_known device [B,N,F]; other rows and molecules without fixed nodes are untouched. */
 int hd_inpaint_decode_fix(hd_handle* h, hd_topology* topo, const uint8_t* fixed_mask, const float* x_known,
                           const float* h_known, float* x, float* hfeat, void* stream);
+/* PARTIAL INPAINTING (additive): positions or features alone, per feature channel.  Two masks replace the single one, both subsets
+ * of the node mask (a set byte on a masked row is ignored): fx[n] "the position of node n is known" and fh[n][c] "feature channel c
+ * of node n is known"; the whole-node call is fx[n] = fh[n][.] = fixed[n].  Steps 1 and 4 above are unchanged; 2 - 3 become
+ *   2'. element e = n D + c is REPLACED if c < 3 and fx[n], or c >= 3 and fh[n][c - 3]; a replaced element becomes
+ *       alpha_s known[e] + sigma_s normal(seed, id, draw, e) - today's draw and element index (stream k = 1 of the inpainting layout);
+ *       an element that is not replaced does not use its normal;
+ *   3'. with Fx the molecule's valid nodes with fx: |Fx| > 0 - c = mean_Fx(z_gen.x) - mean_Fx(z_kn.x) is added to the replaced
+ *       positions, then the masked mean over all valid nodes is removed, in the order of the whole-node form;  |Fx| = 0 - the
+ *       position part of z_gen keeps its BITS (no frame, and z_gen.x is mean-free already).  Nothing replaced: z_gen bit for bit.
+ * Masks that coincide give the bits of the whole-node form.  Position components of a node are known together (no per-axis mask).
+ * With the restraints in the known fragments' frame (hd_restraint_frame 1) "the valid fixed nodes F" is Fx: a node with known
+ * features and a free position is a free node and is pushed; |Fx| = 0 gives tau = 0 and the plain update.
+ * hd_inpaint_parts: attach (fixed_h: device bytes [B*N*F], copied in stream order into a buffer the topology owns) or detach (NULL).
+ *   While attached, the fixed_mask of hd_sample_loop_inpaint / hd_sample_path_inpaint / hd_sample_path_guided means "position known"
+ *   and the attached bytes "channel known"; calls that do not inpaint ignore the attachment.  Whether parts are attached is part of
+ *   the graph key: attaching or detaching rebuilds the captured transition once, other mask contents replay it, and a whole-node
+ *   call after a detach gives the bits of a topology that never had parts.  Every restriction of the inpainting loops stays.
+ * hd_inpaint_replace: steps 2' - 3' once, in place on z [B][N][D], with the host values alpha_s / sigma_s and the generator's
+ *   (seed, sample_id_base + row, draw); fixed_x u8 [B*N]; fixed_h u8 [B*N*F], or NULL for the whole-node form (fixed_x = fixed).
+ * hd_inpaint_decode_fix_parts: hd_inpaint_decode_fix with the two masks - hfeat = h_known exactly on the replaced channels,
+ *   x = x_known + (mean_Fx(x) - mean_Fx(x_known)) on Fx, everything else untouched. */
+int hd_inpaint_parts(hd_handle* h, hd_topology* topo, const uint8_t* fixed_h, void* stream);
+int hd_inpaint_replace(hd_handle* h, hd_topology* topo, float* z, const uint8_t* fixed_x, const uint8_t* fixed_h,
+                       const float* xh_known, float alpha_s, float sigma_s, uint64_t seed, uint64_t sample_id_base, uint32_t draw,
+                       void* stream);
+int hd_inpaint_decode_fix_parts(hd_handle* h, hd_topology* topo, const uint8_t* fixed_x, const uint8_t* fixed_h,
+                                const float* x_known, const float* h_known, float* x, float* hfeat, void* stream);
 
 /* ---- Training primitives (the handle's hd_config.precision must be 0; the fp16x3 contractions are chosen per call below).
  * One "edge layer" is the part of a GCL / EquivariantUpdate that works on edges (egnn_new.py:35-56 / :91-104 with the
