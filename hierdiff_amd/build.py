@@ -36,6 +36,8 @@ def needs_build() -> bool:
 
 
 RESOURCES = os.path.join(LIBDIR, "kernel_resources.json")
+# what decides the device code (tests/test_edge_kloop_schedule.py compiles single kernels to assembly with the same flags)
+KERNEL_FLAGS = ["--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17"]
 
 
 def _parse_resource_remarks(text: str) -> dict:
@@ -87,7 +89,7 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True, d
     if not force and not needs_build() and os.path.exists(RESOURCES):
         return LIB
     os.makedirs(LIBDIR, exist_ok=True)
-    cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "-fPIC", "-shared",
+    cmd = [_hipcc()] + KERNEL_FLAGS + ["-fPIC", "-shared",
            "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
            "-Rpass-analysis=kernel-resource-usage", "-o", LIB + ".tmp"] + SOURCES
     if save_temps:
@@ -117,7 +119,7 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True, d
 def _build_debug(verbose: bool = True) -> str:
     """Measurement build next to the product library: HD_ABLATE variants of the edge kernel + hd_debug_edge_trace."""
     os.makedirs(LIBDIR, exist_ok=True)
-    cmd = [_hipcc(), "-DHD_DEBUG_KERNELS", "--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "-fPIC",
+    cmd = [_hipcc(), "-DHD_DEBUG_KERNELS"] + KERNEL_FLAGS + ["-fPIC",
            "-shared", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result", "-o", LIB_DEBUG] + SOURCES
     if verbose:
         print(" ".join(cmd), flush=True)

@@ -21,6 +21,7 @@
 // builds the round-2 form.
 #ifndef HD_F32_SILU
 #define HD_F32_SILU silu_fast
+#define HD_F32_SILU_IS_FAST 1          // the epilogue runs silu_fast's five operations stage by stage
 #endif
 
 struct EdgeArgs {
@@ -111,6 +112,10 @@ HD_DEVINL void lds_read4(V (&f)[4], unsigned addr) {
                  "ds_read_b128 %3, %4 offset:%8"
                  : "=&v"(f[0]), "=&v"(f[1]), "=&v"(f[2]), "=&v"(f[3])
                  : "v"(addr), "i"(O0), "i"(O1), "i"(O2), "i"(O3));
+}
+template <typename V, unsigned O>
+HD_DEVINL void lds_read1(V& f, unsigned addr) {
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(f) : "v"(addr), "i"(O));
 }
 template <int N, typename V>
 HD_DEVINL void lds_wait4(V (&f)[4]) {
@@ -498,21 +503,48 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
             // Operands of chunk c+1 are produced IN PLACE: once the MFMAs of k-quad q have been issued their four operand
             // registers are dead, so quad q of the next chunk is built there (from rows requested one iteration ago) and
             // the rows of chunk c+2 go into the freed row registers (outstanding VMEM at that point: see rows_wait).
+            // A unit is pinned instruction by instruction (sched_barrier(0): nothing crosses).  An asm volatile is ordered
+            // against other volatile asms only, the MFMA builtins move freely: left alone hipcc hoists the unit's 16 MFMAs
+            // above the reads of the next unit (or, with one fence, sinks them below the next unit's wait), so that the wait
+            // sits directly behind its reads and every unit starts with an exposed LDS round trip.  Order of a unit:
+            //   wait for this unit's fragments; 4 x (MFMA, one fragment read of the next unit); w_r / w_d reads of the quad
+            //   produced behind the unit; 12 MFMAs; the quad's operands and the gathers of chunk c+2.
+            // Each read is issued in the shadow of a running MFMA and has the remaining 12 to land.  (Edge launch against the
+            // unpinned kernel: all four reads in front of the first MFMA +1.3 % - SLOWER; behind the fourth -0.6 %; one behind
+            // each of the first four, with the staged epilogue SiLU, -1.8 %.  Operand generation interleaved into the following
+            // unit's MFMAs with sched_group_barrier lost against generating it behind the unit in both read placements.
+            // EXPERIMENTS.md section AM.)
             static_for<0, NU>([&](auto Uc) {
                 constexpr int u = decltype(Uc)::value, q = u / UPQ, c0 = (u % UPQ) * HC;
                 f32x4(&cur)[4] = (u & 1) ? f1 : f0;
                 f32x4(&nxt)[4] = (u & 1) ? f0 : f1;
+                constexpr bool PRODUCE = KIND != CH_LAST && u % UPQ == UPQ - 1;
                 lds_wait4<0>(cur);
-                if constexpr (u + 1 < NU) read_unit(std::integral_constant<int, u + 1>{}, nxt);
+                __builtin_amdgcn_sched_barrier(0);
+                static_for<0, 4>([&](auto Ct) {
+                    constexpr int ct = decltype(Ct)::value;
+                    if constexpr (ct < HC) acc[c0 + ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(Pc[4 * q], cur[ct][0], acc[c0 + ct], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (u + 1 < NU) {          // (narrow tiles read a fragment again, as read_unit does)
+                        constexpr int qn = (u + 1) / UPQ, cn0 = ((u + 1) % UPQ) * HC;
+                        lds_read1<f32x4, frag_off_f32(qn * NCT + cn0 + (ct < HC ? ct : 0))>(nxt[ct], wb_lds);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+                f32x4 wr4, wd4;
+                if constexpr (PRODUCE) {
+                    wr4 = *reinterpret_cast<const f32x4*>(wrd_s + 32 * cn1 + 16 * hh + 4 * q);
+                    wd4 = *reinterpret_cast<const f32x4*>(wrd_s + H + 32 * cn1 + 16 * hh + 4 * q);
+                }
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
+                for (int j = 1; j < 4; ++j)
 #pragma unroll
                     for (int ct = 0; ct < HC; ++ct)
                         acc[c0 + ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(Pc[4 * q + j], cur[ct][j], acc[c0 + ct], 0, 0, 0);
-                if constexpr (KIND != CH_LAST && u % UPQ == UPQ - 1) {
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (PRODUCE) {
                     rows_wait(std::integral_constant<int, q>{});
-                    const f32x4 wr4 = *reinterpret_cast<const f32x4*>(wrd_s + 32 * cn1 + 16 * hh + 4 * q);
-                    const f32x4 wd4 = *reinterpret_cast<const f32x4*>(wrd_s + H + 32 * cn1 + 16 * hh + 4 * q);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         float pre = pa[q][j] + pb[q][j];
@@ -557,6 +589,9 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
                     lds_read4<f16x8, frag_off_f16<NCT>(u, 0), frag_off_f16<NCT>(u, 1), frag_off_f16<NCT>(u + 1, 0),
                               frag_off_f16<NCT>(u + 1, 1)>(nxt, wb_lds);
                 }
+                // The group is fenced at both ends, like the fp32 units above: unfenced, hipcc moved the group's MFMAs across
+                // the volatile reads and waits until most reads sat directly in front of their wait (fenced: +0.7 % molecules/s).
+                __builtin_amdgcn_sched_barrier(0);
                 // The next chunk's 8 operand pairs are produced in the FIRST half of the groups and the AB
                 // rows of chunk c+2 are requested as soon as a quad of chunk c+1 has been consumed: the
                 // per-chunk barrier implies vmcnt(0), so a gather issued late in the chunk would expose its
@@ -608,6 +643,7 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
                         __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
                     }
                 }
+                __builtin_amdgcn_sched_barrier(0);
             });
             if constexpr (KIND != CH_LAST) {
 #pragma unroll
@@ -698,12 +734,36 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
     for (int ct = 0; ct < NCT; ++ct) {
         const float wav = wrd_s[3 * H + 32 * ct + n];
         if constexpr (PREC == 0) {
+#ifdef HD_F32_SILU_IS_FAST
+            // silu_fast stage by stage over the 16 rows of a column tile, like the fp16x3 branch below and for its reason:
+            // the same five operations per value, hence the same bits (-0.2 % on the launch, EXPERIMENTS.md section AM)
+            float e[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) e[r] = acc[ct][r] * -1.44269502162933349609375f;
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) e[r] = __builtin_amdgcn_exp2f(e[r]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) e[r] = 1.0f + e[r];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) e[r] = __builtin_amdgcn_rcpf(e[r]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ct][r] *= e[r];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dot[r] = __builtin_fmaf(acc[ct][r], wav, dot[r]);
+            __builtin_amdgcn_sched_barrier(0);
+#else
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float mv = HD_F32_SILU(acc[ct][r]);
                 acc[ct][r] = mv;
                 dot[r] = __builtin_fmaf(mv, wav, dot[r]);
             }
+#endif
         } else {
             // stage by stage over the 16 rows of a column tile (exp x16, +1 x16, rcp x16, ...): left alone hipcc
             // runs each value's exp -> add -> rcp -> mul chain back to back through one or two registers and
