@@ -68,15 +68,24 @@ def _production(name: str) -> bool:
     return True
 
 
+def _packed_edge(name: str) -> bool:
+    """The packed-VALU instantiations of the exact-fp32 edge kernel (ABL = HD_EDGE_PACKED = 2048, k_edge.hpp): what the plain
+    fp32 launch runs, audited like the ABL = 0 forms."""
+    import re
+    return re.match(r"_Z6k_edgeILi\d+ELb[01]ELi0ELi2048EE", name) is not None
+
+
 def audit(resources: dict) -> list:
     """Kernels hide loads from the compiler (inline-asm loads released by hand-counted s_waitcnt): a register spill
     next to one of them would save a destination before its data has landed.  No production kernel may spill."""
     bad = []
     for name, r in resources.items():
-        if not name.startswith("_Z") or not _production(name):
+        if not name.startswith("_Z") or not (_production(name) or _packed_edge(name)):
             continue
         if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0):          # SGPR spills go to VGPR lanes, not to memory
             bad.append(f"{name}: scratch {r.get('ScratchSize')} B/lane, VGPR spills {r.get('VGPRs Spill')}")
+        elif _packed_edge(name) and r.get("VGPRs", 0) + r.get("AGPRs", 0) > 256:     # two wavefronts per SIMD
+            bad.append(f"{name}: {r.get('VGPRs')} VGPRs + {r.get('AGPRs')} AGPRs, more than 256")
     return bad
 
 

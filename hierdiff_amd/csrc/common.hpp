@@ -67,6 +67,9 @@ HD_DEVINL float silu_fast(float x) {
 // Deliberately NOT written with v_pk_*_f32: packed fp32 runs on the matrix pipe's datapath and cannot issue while
 // an MFMA of either co-resident wavefront is in flight (scratch/mb/coissue.hip: 4 v_pk_fma per MFMA cost
 // 52 ns/slot vs 30 ns for 4 v_fma_f32, which hide completely), so the file is built with -fno-slp-vectorize.
+// (This speaks of the 16-bit modes, whose MFMAs leave the VALU free.  The exact-fp32 edge kernel is the opposite case: its MFMA
+// occupies the VALU datapath itself, nothing co-issues with it, and a packed instruction does two values' work in 1.1 issue
+// slots - k_edge<H, *, 0, HD_EDGE_PACKED> uses v_pk_*_f32 on purpose, written out by hand: k_edge.hpp, EXPERIMENTS.md section AN.)
 HD_DEVINL float silu_scaled(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x)); }
 
 // fp16 head / tail of a pair ("fp16x3", PREC 3): 11 + 11 significant bits, |y - h - l| <= 2^-22 |y| as long as the tail stays a

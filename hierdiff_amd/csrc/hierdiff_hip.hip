@@ -1508,6 +1508,10 @@ static int launch_edge_h(hd_handle* h, bool coord, const EdgeArgs& a, hipStream_
     if (prec == 3) {
         if (coord) hipLaunchKernelGGL((k_edge<H, true, 3>), grid, block, lds, s, a);
         else hipLaunchKernelGGL((k_edge<H, false, 3>), grid, block, lds, s, a);
+    } else if constexpr (edge_packed_width(H)) {
+        // the plain exact-fp32 launch is the one family that runs the packed-VALU form (HD_EDGE_PACKED, k_edge.hpp): same bits
+        if (coord) hipLaunchKernelGGL((k_edge<H, true, 0, HD_EDGE_PACKED>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((k_edge<H, false, 0, HD_EDGE_PACKED>), grid, block, lds, s, a);
     } else {
         if (coord) hipLaunchKernelGGL((k_edge<H, true, 0>), grid, block, lds, s, a);
         else hipLaunchKernelGGL((k_edge<H, false, 0>), grid, block, lds, s, a);
@@ -1526,6 +1530,10 @@ static int prepare_edge_h() {
     HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, true, 0, HD_EDGE_SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, false, 0, HD_EDGE_SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if constexpr (edge_packed_width(H)) {
+        HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, true, 0, HD_EDGE_PACKED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, false, 0, HD_EDGE_PACKED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    }
     if constexpr (H >= 128) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, true, 3, HD_EDGE_SAVE | HD_EDGE_UNSCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, false, 3, HD_EDGE_SAVE | HD_EDGE_UNSCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));

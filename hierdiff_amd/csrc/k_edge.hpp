@@ -63,6 +63,25 @@ constexpr int HD_EDGE_SAVE = 256;
 // every exponential instead (one VALU instruction per activation).  The image scalars come from device memory (EdgeArgs.dscal).
 constexpr int HD_EDGE_UNSCALED = 512;
 constexpr float HD_NEG_LOG2E = -1.4426950408889634f;
+// Third such flag (PREC 0 only): the VALU arithmetic of the exact-fp32 kernel on pairs of values with v_pk_add_f32 / v_pk_mul_f32 /
+// v_pk_fma_f32 - the first-layer pre-activations and SiLUs of the operand generation, the mul / +1 / mul stages of the epilogue
+// SiLU and the gate dot.  The packed instructions are IEEE per element and every value sees the operations of the scalar form in
+// the same order, so the bits are the same; beside the fp32 MFMA (which occupies the same datapath either way) a packed
+// instruction costs about 1.1 x a scalar one, i.e. 0.55 x per value.  v_exp_f32 / v_rcp_f32 have no packed form.  Only the plain
+// k_edge<H, *, 0> launch of launch_edge_h selects it (H >= 256); k_edge_mixed, k_edge_split, the training forward and fp16x3
+// keep the scalar code.  EXPERIMENTS.md section AN.
+constexpr int HD_EDGE_PACKED = 2048;
+// the widths whose plain fp32 launch runs the packed form (-DHD_EDGE_NO_PACKED: none, the scalar kernel of a measurement build)
+constexpr bool edge_packed_width(int H) {
+#ifdef HD_EDGE_NO_PACKED
+    return false;
+#else
+    return H >= 256;
+#endif
+}
+HD_DEVINL f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+HD_DEVINL f32x2 pk2(float lo, float hi) { return f32x2{lo, hi}; }
+HD_DEVINL f32x2 pk_splat(float v) { return f32x2{v, v}; }
 
 
 // fp16x3: max_k |A_i[k]| and max_k |B_i[k]| of every AB row (the node-level halves of the first edge Linear) - the per-node part of
@@ -333,12 +352,38 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
         if constexpr (ABL & 8) { pa[u] = f32x4{radial, d0, radial, d0}; pb[u] = pa[u]; }
         else vm_load2(pa[u], pb[u], Arow + KC * c + 4 * u, Brow + KC * c + 4 * u);
     };
+    // fp32, HD_EDGE_PACKED: four values as two even-aligned pairs, stage by stage - silu_fast's operations per value in
+    // silu_fast's order (20 instructions a quad instead of 32; radial / d0 / the constants are broadcast operands)
+    constexpr bool PACKED = PREC == 0 && (ABL & HD_EDGE_PACKED) != 0;
+#ifndef HD_F32_SILU_IS_FAST
+    static_assert(!PACKED, "the packed form is silu_fast written out");
+#endif
+    auto make_quad_pk = [&](const f32x4 av, const f32x4 bv, const f32x4 wr4, const f32x4 wd4, float (&P)[16], const int at) {
+        f32x2 pre[2], e[2];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) pre[p] = pk2(av[2 * p], av[2 * p + 1]) + pk2(bv[2 * p], bv[2 * p + 1]);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) pre[p] = pk_fma(pk_splat(radial), pk2(wr4[2 * p], wr4[2 * p + 1]), pre[p]);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) pre[p] = pk_fma(pk_splat(d0), pk2(wd4[2 * p], wd4[2 * p + 1]), pre[p]);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) e[p] = pre[p] * pk_splat(-1.44269502162933349609375f);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) e[p] = pk2(__builtin_amdgcn_exp2f(e[p][0]), __builtin_amdgcn_exp2f(e[p][1]));
+#pragma unroll
+        for (int p = 0; p < 2; ++p) e[p] = pk_splat(1.0f) + e[p];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) e[p] = pk2(__builtin_amdgcn_rcpf(e[p][0]), __builtin_amdgcn_rcpf(e[p][1]));
+#pragma unroll
+        for (int p = 0; p < 2; ++p) { pre[p] = pre[p] * e[p]; P[at + 2 * p] = pre[p][0]; P[at + 2 * p + 1] = pre[p][1]; }
+    };
     // first-layer activations of this lane's edge row for K chunk c (k = 32c + 16*hh + 0..15)
     auto make_P = [&](int c, float (&P)[16]) {             // fp32 mode
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             f32x4 wr4 = *reinterpret_cast<const f32x4*>(wrd_s + 32 * c + 16 * hh + 4 * u);
             f32x4 wd4 = *reinterpret_cast<const f32x4*>(wrd_s + H + 32 * c + 16 * hh + 4 * u);
+            if constexpr (PACKED) { make_quad_pk(pa[u], pb[u], wr4, wd4, P, 4 * u); continue; }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float pre = pa[u][j] + pb[u][j];
@@ -420,6 +465,7 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) {
             const float b2v = PREC == 3 ? 0.0f : wrd_s[2 * H + 32 * ct + n];
+            // (8 v_pk_mov_b32 per column tile instead of these 16 v_mov_b32 measured nothing in the packed form: section AN)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[ct][r] = b2v;
         }
@@ -544,13 +590,20 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
                         acc[c0 + ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(Pc[4 * q + j], cur[ct][j], acc[c0 + ct], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (PRODUCE) {
+                    // (packed form: hipcc splits v_pk_*_f32 that follow an MFMA within its latency back into scalar
+                    // instructions, to co-issue them - which beside the fp32 MFMA they do not.  Its scan ends at the first
+                    // instruction that names the MFMA's destination: an empty asm on the unit's last accumulator.)
+                    if constexpr (PACKED) asm volatile("" :: "v"(acc[c0 + HC - 1]));
                     rows_wait(std::integral_constant<int, q>{});
+                    if constexpr (PACKED) make_quad_pk(pa[q], pb[q], wr4, wd4, Pc, 4 * q);
+                    else {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float pre = pa[q][j] + pb[q][j];
-                        pre = __builtin_fmaf(radial, wr4[j], pre);
-                        pre = __builtin_fmaf(d0, wd4[j], pre);
-                        Pc[4 * q + j] = HD_F32_SILU(pre);
+                        for (int j = 0; j < 4; ++j) {
+                            float pre = pa[q][j] + pb[q][j];
+                            pre = __builtin_fmaf(radial, wr4[j], pre);
+                            pre = __builtin_fmaf(d0, wd4[j], pre);
+                            Pc[4 * q + j] = HD_F32_SILU(pre);
+                        }
                     }
                     if constexpr (KIND == CH_MID) {
                         if constexpr (ABL & 8) { pa[q] = f32x4{radial, d0, radial, d0}; pb[q] = pa[q]; }
@@ -737,6 +790,33 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
 #ifdef HD_F32_SILU_IS_FAST
             // silu_fast stage by stage over the 16 rows of a column tile, like the fp16x3 branch below and for its reason:
             // the same five operations per value, hence the same bits (-0.2 % on the launch, EXPERIMENTS.md section AM)
+            if constexpr (PACKED) {
+                // the same stages; mul, +1, mul and the gate dot over the pairs (r, r+1) of the column tile's accumulator, which
+                // are adjacent, even-aligned registers: 8 packed instructions a stage instead of 16
+                f32x2 x2[8], e2[8];
+#pragma unroll
+                for (int p = 0; p < 8; ++p) { x2[p] = pk2(acc[ct][2 * p], acc[ct][2 * p + 1]); e2[p] = x2[p] * pk_splat(-1.44269502162933349609375f); }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int p = 0; p < 8; ++p) e2[p] = pk2(__builtin_amdgcn_exp2f(e2[p][0]), __builtin_amdgcn_exp2f(e2[p][1]));
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int p = 0; p < 8; ++p) e2[p] = pk_splat(1.0f) + e2[p];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int p = 0; p < 8; ++p) e2[p] = pk2(__builtin_amdgcn_rcpf(e2[p][0]), __builtin_amdgcn_rcpf(e2[p][1]));
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int p = 0; p < 8; ++p) { x2[p] = x2[p] * e2[p]; acc[ct][2 * p] = x2[p][0]; acc[ct][2 * p + 1] = x2[p][1]; }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int p = 0; p < 8; ++p) {
+                    const f32x2 d2 = pk_fma(x2[p], pk_splat(wav), pk2(dot[2 * p], dot[2 * p + 1]));
+                    dot[2 * p] = d2[0]; dot[2 * p + 1] = d2[1];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                continue;
+            }
             float e[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) e[r] = acc[ct][r] * -1.44269502162933349609375f;
@@ -855,27 +935,40 @@ HD_DEVINL void edge_tile_body(const EdgeArgs& a, float* smem, float* wrd_s, cons
         // row dot takes a select-based form of the same sums: identical bits for finite rows, NaN stays inside its
         // own segments.
         const bool tile_has_nan = __builtin_amdgcn_ballot_w64(rowdot != rowdot) != 0;
-        for (int s = 0; s < nseg; ++s) {
-            float ws[16];
+        // The sums of segment s run over the row quads that hold a row of s only.  Quad q = rows 8q .. 8q+7 of the tile = this
+        // lane's acc[ct][4q .. 4q+3] (either half), segment bytes = the dwords seg_s[2q], seg_s[2q+1]; whether one of those
+        // eight bytes equals s is decided on the scalar unit (the zero-byte test on dword ^ s s s s), so the branch is
+        // wave-uniform.  A skipped term is fma(0, finite, sum) with a sum that started at +0 and hence is never -0: it returns
+        // sum, so the bits are those of the full loop, in which at N = 30 two of three quad passes added nothing.  Segments
+        // need not be contiguous for this.  The order of the remaining terms of a sum is unchanged (r ascending).
+        uint32_t sq[8];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) ws[r] = (sg[r] == s) ? w[r] : 0.0f;
+        for (int k = 0; k < 8; ++k) sq[k] = __builtin_amdgcn_readfirstlane(seg_s[k]);
+        const int nseg_u = __builtin_amdgcn_readfirstlane(nseg);
+        for (int s = 0; s < nseg_u; ++s) {
             float* dst = a.part + (size_t)__builtin_amdgcn_readlane(pid_l, s) * H + n;
+            const uint32_t s4 = (uint32_t)s * 0x01010101u;
             float sums[NCT];
-            if (__builtin_expect(tile_has_nan, 0)) {
 #pragma unroll
-                for (int ct = 0; ct < NCT; ++ct) {
-                    float sum = 0.f;
+            for (int ct = 0; ct < NCT; ++ct) sums[ct] = 0.f;
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) sum = (sg[r] == s) ? __builtin_fmaf(ws[r], acc[ct][r], sum) : sum;
-                    sums[ct] = sum;
-                }
-            } else {
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t x0 = sq[2 * q] ^ s4, x1 = sq[2 * q + 1] ^ s4;
+                if (((((x0 - 0x01010101u) & ~x0) | ((x1 - 0x01010101u) & ~x1)) & 0x80808080u) == 0) continue;
+                float ws[4];
 #pragma unroll
-                for (int ct = 0; ct < NCT; ++ct) {
-                    float sum = 0.f;
+                for (int j = 0; j < 4; ++j) ws[j] = (sg[4 * q + j] == s) ? w[4 * q + j] : 0.0f;
+                if (__builtin_expect(tile_has_nan, 0)) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) sum = __builtin_fmaf(ws[r], acc[ct][r], sum);
-                    sums[ct] = sum;
+                    for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            sums[ct] = (sg[4 * q + j] == s) ? __builtin_fmaf(ws[j], acc[ct][4 * q + j], sums[ct]) : sums[ct];
+                } else {
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) sums[ct] = __builtin_fmaf(ws[j], acc[ct][4 * q + j], sums[ct]);
                 }
             }
             // add the two halves of the wavefront (lane n + 32 hh holds rows 4hh.. of column n)
