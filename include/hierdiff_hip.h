@@ -661,7 +661,7 @@ int hd_edge_layer_forward(hd_handle* h, hd_topology* topo, int coord, const floa
  * hd_edge_layer_forward_s with pre2 != NULL writes W2 P + b2 of every edge row into it (accumulator order per 32-row tile, opaque to
  * the caller; 228 MB per layer at B = 256, N = 30, H = 256 - sized for this GPU's HBM, not for a 16 GB card);
  * hd_edge_layer_backward_s with the same buffer runs stage A as an element-wise kernel over it (no weight stream, no matrix
- * instruction).  Same results to the bit as the recomputing path (tests/test_gpu_training.py).
+ * instruction).  Same results to the bit as the recomputing path (tests/test_gpu_edge_layer.py, tests/test_gpu_training.py).
  * (2) precision: 0 = exact fp32; 3 = "fp16x3" (hidden_nf >= 128; narrower layers run the fp32 kernels): the sampler's two-way FP16
  * split in the training path - the reference trains with apex O2 (endiffusion/conf/trainer/default.yaml:4-5); here the forward
  * contraction (the fp16x3 edge kernel on the unscaled parameters; images, image scale and row ranges made on the device per call),
@@ -691,7 +691,11 @@ int hd_edge_layer_backward_s(hd_handle* h, hd_topology* topo, int coord, int pre
  *     per-tile partial sums                             =>  db2 = colsum(b2part),  d(wa) = colsum(colpart),
  *                                                           d(ba) = sum(bapart),
  *                                                           d(w_r), d(w_d) = colsum(wrdpart[:, 0]), colsum(wrdpart[:, 1]);
- * G1 = dL/d(pre1) is the operand of the two CSR sums behind dAB and is left in the workspace. */
+ * G1 = dL/d(pre1) is the operand of the two CSR sums behind dAB and is left in the workspace.  escal, one 8-float record per edge
+ * row: {dL/du_x, dL/du_y, dL/du_z, dL/dphi, dL/d(radial), dL/d(d0), -, -} with u the unit direction and phi = wa.M of a coordinate
+ * layer and d(radial), d(d0) the paths through pre1; [0:4] are written (and read) in coordinate layers only, [6:8] never.  Every
+ * other row of every array is written - zeros on the padding rows of the table - so no workspace needs clearing
+ * (tests/test_gpu_edge_layer.py). */
 int hd_edge_layer_backward(hd_handle* h, hd_topology* topo, int coord, const float* AB, const float* x,
                            const float* x0, const float* wrd, const float* W2, const float* b2, const float* wa,
                            const float* ba, const float* gout, float* G2, float* P, float* G1, float* escal, float* colpart,
