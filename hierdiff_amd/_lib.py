@@ -85,6 +85,8 @@ SIGNATURES = {
                                       _VP]),
     "hd_restraint_field_energy": (C.c_int, [_VP, _VP, _FP, _VP, _VP]),
     "hd_restraint_field_energy_framed": (C.c_int, [_VP, _VP, _FP, _U8P, _FP, _VP, _VP, _VP]),
+    "hd_restraint_templates": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), _VP]),
+    "hd_restraint_template_energy": (C.c_int, [_VP, _VP, _FP, _VP, _VP, _VP]),
     "hd_set_steer": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_float)]),
     "hd_steer_attach": (C.c_int, [_VP, C.c_int, C.c_double, C.c_int, _VP]),
     "hd_steer_detach": (C.c_int, [_VP]),

@@ -174,6 +174,7 @@ struct PathKey {
     int rs_frame;                                            // 1: its restraints act in the known fragments' frame (hd_restraint_frame)
     int ip_parts;                                            // 1: an inpainting transition with per-channel masks (hd_inpaint_parts)
     unsigned long long rs_fld_gen;                           // its restraints hold fields (hd_restraint_fields): their buffers, NF, rows (0: none)
+    unsigned long long rs_tpl_gen;                           // ... templates (hd_restraint_templates): their buffers, NT, M, rows (0: none)
     int st_P;                                                // steered transition: particles per group, rho, the topology's steering
     double st_ess;                                           // buffers, the handle's rows (all 0: not steered)
     unsigned long long st_gen, st_rows_gen;
@@ -181,7 +182,7 @@ struct PathKey {
         return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape && noise_rows == o.noise_rows &&
                k_lo == o.k_lo && resamplings == o.resamplings && w_rows == o.w_rows && phi == o.phi && seed == o.seed &&
                weights_gen == o.weights_gen && sched_gen == o.sched_gen && path_gen == o.path_gen && ip_gen == o.ip_gen &&
-               rs_gen == o.rs_gen && rs_rows_gen == o.rs_rows_gen && rs_frame == o.rs_frame && ip_parts == o.ip_parts && rs_fld_gen == o.rs_fld_gen && st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen &&
+               rs_gen == o.rs_gen && rs_rows_gen == o.rs_rows_gen && rs_frame == o.rs_frame && ip_parts == o.ip_parts && rs_fld_gen == o.rs_fld_gen && rs_tpl_gen == o.rs_tpl_gen && st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen &&
                st_rows_gen == o.st_rows_gen;
     }
 };
@@ -284,6 +285,14 @@ struct hd_topology {
     size_t rs_fld_cap[2];
     int rs_NF, rs_fld_NF, rs_fld_w_rows;
     unsigned long long rs_fld_gen;
+    // hd_restraint_templates: the row tables (grown by the rule above) and the geometry of up to HD_MAX_TEMPLATES templates (one
+    // allocation, made by the first call).  rs_NT is what is attached now (0 after hd_restraint_attach); rs_tpl_NT / rs_tpl_M /
+    // rs_tpl_rows are what the last templated call baked in, and rs_tpl_gen moves when that changes.
+    int* rs_tpl_idx;
+    float *rs_tpl_f, *rs_tpl_geom;
+    size_t rs_tpl_cap[2];
+    int rs_NT, rs_tpl_NT, rs_tpl_M, rs_tpl_rows;
+    unsigned long long rs_tpl_gen;
     // hd_steer_attach: the steering state of the chain that runs on this topology (log-weights, last energies, lineage roots, the
     // ancestors of the latest transition, per-group statistics) and the scratch of k_steer_gather - one allocation each, made by the
     // first attach at addresses captured transitions keep.  It survives between the pieces of a chain; `reset` starts a new one.
@@ -868,7 +877,7 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     if (t->guide_mem) (void)hipFree(t->guide_mem);
     if (t->ms_hist) (void)hipFree(t->ms_hist);
     for (void* p : {(void*)t->rs_obs, (void*)t->rs_pair_idx, (void*)t->rs_pair_f, (void*)t->rs_anc_idx, (void*)t->rs_anc_f,
-                    (void*)t->rs_scale, (void*)t->rs_step, (void*)t->rs_fld_v, (void*)t->rs_fld_w, (void*)t->rs_fld_geom,
+                    (void*)t->rs_scale, (void*)t->rs_step, (void*)t->rs_fld_v, (void*)t->rs_fld_w, (void*)t->rs_fld_geom, (void*)t->rs_tpl_idx, (void*)t->rs_tpl_f, (void*)t->rs_tpl_geom,
                     (void*)t->rs_fld_off, (void*)t->rs_fld_dims, (void*)t->st_f64, (void*)t->st_i32, (void*)t->st_scratch})
         if (p) (void)hipFree(p);
     if (t->ip_fixed) (void)hipFree(t->ip_fixed);

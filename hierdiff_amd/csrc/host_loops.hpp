@@ -564,6 +564,7 @@ extern "C" int hd_restraint_attach(hd_topology* topo, const float* obs, int obs_
     topo->rs_A = A; topo->rs_scale_rows = scale_rows; topo->rs_nv0 = nv0;
     topo->rs_frame = 0;                                 // the model's frame, until hd_restraint_frame says otherwise
     topo->rs_NF = 0;                                    // no fields, until hd_restraint_fields says otherwise
+    topo->rs_NT = 0;                                    // no templates, until hd_restraint_templates says otherwise
     topo->rs_on = true;
     return HD_OK;
 }
@@ -617,6 +618,43 @@ extern "C" int hd_restraint_fields(hd_topology* topo, int NF, const float* value
     return HD_OK;
 }
 
+extern "C" int hd_restraint_templates(hd_topology* topo, int NT, int rows, int M, const int* idx, const float* f, const float* geom,
+                                      void* stream) {
+    if (!topo) return fail(HD_E_INVALID, "hd_restraint_templates: null topology");
+    if (NT < 0 || NT > HD_MAX_TEMPLATES) return fail(HD_E_INVALID, "hd_restraint_templates: NT must be 0 .. 4");
+    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restraint_templates: no restraints attached to the topology (hd_restraint_attach)");
+    if (NT == 0) { topo->rs_NT = 0; return HD_OK; }
+    if (M < 1) return fail(HD_E_INVALID, "hd_restraint_templates: M must be >= 1");
+    if (rows != 1 && rows != topo->B) return fail(HD_E_INVALID, "hd_restraint_templates: the tables have 1 row (shared) or B rows");
+    if (!idx || !f || !geom) return fail(HD_E_INVALID, "hd_restraint_templates: null table");
+    for (int t = 0; t < NT; ++t) {
+        const float k = geom[2 * t], fit = geom[2 * t + 1];
+        if (!(k >= 0.f) || !(k - k == 0.f)) return fail(HD_E_INVALID, "hd_restraint_templates: k must be >= 0 and finite");
+        if (fit != 0.f && fit != 1.f) return fail(HD_E_INVALID, "hd_restraint_templates: fit is 0 (rigid) or 1 (translation)");
+    }
+    const size_t cnt = (size_t)rows * NT * M;
+    for (size_t e = 0; e < cnt; ++e) {
+        const float* r = f + e * 4;
+        if (!(r[0] - r[0] == 0.f) || !(r[1] - r[1] == 0.f) || !(r[2] - r[2] == 0.f))
+            return fail(HD_E_INVALID, "hd_restraint_templates: the template positions must be finite");
+        if (!(r[3] >= 0.f) || !(r[3] - r[3] == 0.f)) return fail(HD_E_INVALID, "hd_restraint_templates: every weight must be >= 0 and finite");
+    }
+    HIP_TRY(hipSetDevice(topo->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    topo->rs_NT = 0;
+    bool moved = false;
+    if (!topo->rs_tpl_geom) { HD_TRY(dev_alloc(&topo->rs_tpl_geom, (size_t)HD_MAX_TEMPLATES * 2)); moved = true; }
+    // (host arrays: pageable sources are staged before the call returns)
+    HD_TRY(rs_table(&topo->rs_tpl_idx, &topo->rs_tpl_cap[0], idx, cnt, &moved, s));
+    HD_TRY(rs_table(&topo->rs_tpl_f, &topo->rs_tpl_cap[1], f, cnt * 4, &moved, s));
+    HIP_TRY(hipMemcpyAsync(topo->rs_tpl_geom, geom, (size_t)NT * 2 * sizeof(float), hipMemcpyHostToDevice, s));
+    if (moved || NT != topo->rs_tpl_NT || M != topo->rs_tpl_M || rows != topo->rs_tpl_rows) topo->rs_tpl_gen++;
+    topo->rs_tpl_NT = NT; topo->rs_tpl_M = M; topo->rs_tpl_rows = rows;
+    topo->rs_NT = NT;
+    return HD_OK;
+}
+
 extern "C" int hd_restraint_frame(hd_topology* topo, int frame) {
     if (!topo) return fail(HD_E_INVALID, "hd_restraint_frame: null topology");
     if (frame != 0 && frame != 1) return fail(HD_E_INVALID, "hd_restraint_frame: frame is 0 (the model's) or 1 (the known fragments')");
@@ -639,6 +677,13 @@ static RestraintTables restraint_tables(const hd_topology* t) {
     return r;
 }
 
+static TemplateTables template_tables(const hd_topology* t) {
+    TemplateTables r;
+    r.idx = t->rs_tpl_idx; r.f = t->rs_tpl_f; r.geom = t->rs_tpl_geom;
+    r.rows = t->rs_tpl_rows; r.NT = t->rs_NT; r.M = t->rs_tpl_M;
+    return r;
+}
+
 // The update of one transition on eps (in place when out == eps): `rows` the device table read at position *io.step / io.row, or the
 // host row.  `framed`: in the frame of the known fragments io.fixed / io.known (k_restrain_eps<true>).
 static int restrain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* z, const float* eps, float* out,
@@ -651,8 +696,13 @@ static int restrain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const
     a.step_ptr = io.step; a.k = io.row; a.step = t->rs_step; a.nv0 = t->rs_nv0; a.scale_rows = t->rs_scale_rows;
     a.B = t->B; a.N = t->N; a.D = h->D;
     a.fixed = framed ? io.fixed : nullptr; a.known = framed ? io.known : nullptr;
-    if (framed) hipLaunchKernelGGL(k_restrain_eps<true>, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, a);
-    else hipLaunchKernelGGL(k_restrain_eps<false>, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, a);
+    a.tp = template_tables(t);
+    const size_t lds = (size_t)t->N * 3 * sizeof(float);
+    if (t->rs_NT) {                                     // templates attached: the instantiations with the fit
+        if (framed) hipLaunchKernelGGL((k_restrain_eps<true, true>), dim3(t->B), dim3(256), lds, io.s, a);
+        else hipLaunchKernelGGL((k_restrain_eps<false, true>), dim3(t->B), dim3(256), lds, io.s, a);
+    } else if (framed) hipLaunchKernelGGL((k_restrain_eps<true, false>), dim3(t->B), dim3(256), lds, io.s, a);
+    else hipLaunchKernelGGL((k_restrain_eps<false, false>), dim3(t->B), dim3(256), lds, io.s, a);
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
@@ -746,6 +796,22 @@ static int field_energy_launch(const char* who, hd_handle* h, hd_topology* topo,
     return HD_OK;
 }
 
+extern "C" int hd_restraint_template_energy(hd_handle* h, hd_topology* topo, const float* x, double* out, double* fit16, void* stream) {
+    if (!h || !topo) return fail(HD_E_INVALID, "hd_restraint_template_energy: null handle/topology");
+    if (!x || !out) return fail(HD_E_INVALID, "hd_restraint_template_energy: null tensor");
+    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restraint_template_energy: no restraints attached to the topology (hd_restraint_attach)");
+    if (!topo->rs_NT) return fail(HD_E_STATE, "hd_restraint_template_energy: no templates attached to the topology (hd_restraint_templates)");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    ProfScope ps(h, s, 2);
+    TemplateEnergyArgs a{};
+    a.x = x; a.nm = topo->nm_bytes; a.tp = template_tables(topo); a.out = out; a.fit16 = fit16; a.B = topo->B; a.N = topo->N;
+    hipLaunchKernelGGL(k_restraint_template_energy, dim3(topo->B), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
 extern "C" int hd_restraint_field_energy(hd_handle* h, hd_topology* topo, const float* x, double* out, void* stream) {
     return field_energy_launch("hd_restraint_field_energy", h, topo, x, nullptr, nullptr, out, nullptr, stream, false);
 }
@@ -813,7 +879,9 @@ static int steer_launch(hd_handle* h, hd_topology* t, const LoopIO& io, float* z
     w.z = z; w.eps = eps; w.nm = t->nm_bytes; w.t = restraint_tables(t); w.rows = rows;
     for (int i = 0; i < 3; ++i) w.row[i] = row3 ? row3[i] : 0.f;
     w.step_ptr = io.step; w.k = io.row; w.nv0 = t->rs_nv0; w.logw = st.logw; w.uprev = st.uprev; w.B = t->B; w.N = t->N; w.D = h->D;
-    hipLaunchKernelGGL(k_steer_weigh, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, w);
+    w.tp = template_tables(t);
+    if (t->rs_NT) hipLaunchKernelGGL(k_steer_weigh<true>, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, w);
+    else hipLaunchKernelGGL(k_steer_weigh<false>, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, w);
     SteerResampleArgs r;
     r.st = st; r.ess = t->st_ess; r.seed = seed; r.base = io.base; r.draw = d.value; r.draw_ptr = d.word; r.base_ptr = io.base_w;
     r.P = t->st_P;
@@ -1021,6 +1089,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     key.rs_gen = rsn ? topo->rs_gen : 0; key.rs_rows_gen = rsn ? h->rs_rows.gen : 0; key.rs_frame = framed ? 1 : 0;
     key.ip_parts = parts ? 1 : 0;
     key.rs_fld_gen = rsn && topo->rs_NF ? topo->rs_fld_gen : 0;
+    key.rs_tpl_gen = rsn && topo->rs_NT ? topo->rs_tpl_gen : 0;
     key.st_P = stn ? topo->st_P : 0; key.st_ess = stn ? topo->st_ess : 0.0; key.st_gen = stn ? topo->st_gen : 0;
     key.st_rows_gen = stn ? h->st_rows.gen : 0;
     PathWords w;

@@ -31,14 +31,36 @@
 // k w_i <= 0: the term is skipped.  The 8 corners are plain global loads; lane l of a node's group takes the fields l, l + G, ...
 // behind the anchors; the energy U_fld is a strided double sum over N * NF, then guide_block_sum.  In the known frame the field sees
 // tau, only free nodes gather a gradient, and the energy sums over all valid nodes.
+// TEMPLATES (hd_restraint_templates, hd_restraint_template_energy; k_restrain_eps<F, true>): up to HD_MAX_TEMPLATES rigid templates.
+// Template t: rows (i_m, y_m, w_m) in idx [rows][NT][M] and f [rows][NT][M][4], geom [NT][2] = (k, fit: 0 rigid, 1 translation).  A row
+// is active when 0 <= i_m < N, node i_m is valid and w_m > 0.  Over the active rows, in double (rs_template_fit):
+//   W = sum w,  c_x = sum w x_i / W,  c_y = sum w y / W,  S = sum w (x_i - c_x)(y - c_y)^T,  R = argmax_{SO(3)} tr(R^T S) (k_kabsch.hpp;
+//   translation: I),  r_m = (x_i - c_x) - R (y_m - c_y),  U_tpl = 1/2 k sum w |r|^2,  dU/dx_i += k w r_m (exact: R maximises, sum w r = 0)
+// Two strided double sums per template (the centroids, then S from the centred values) with guide_block_sum, so every order depends
+// on (N, M) alone; thread 64 t then solves template t - the four waves solve up to four templates side by side - and leaves
+// (R, c_x, c_y, k, W) in LDS for the gather: lane l of a node's group takes the rows l, l + G, ... that name the node, behind the fields.
+// W = 0, fewer than two active rows, or a non-finite active coordinate: the template contributes nothing to the molecule.  A template
+// carries its own frame: it never sees tau; in the known frame rows on fixed nodes take part in the fit, only free nodes gather.
 #pragma once
 #include "common.hpp"
 #include "k_guide.hpp"
+#include "k_kabsch.hpp"
 
 #define RS_GROUP 16
 #ifndef HD_MAX_FIELDS
 #define HD_MAX_FIELDS 8
 #endif
+#ifndef HD_MAX_TEMPLATES
+#define HD_MAX_TEMPLATES 4
+#endif
+#define RS_FIT 19           // doubles of LDS per template: R [9], c_x [3], c_y [3], k, W (0: contributes nothing), U_tpl, sum w |r|^2
+
+struct TemplateTables {
+    const int* idx;         // [rows][NT][M]
+    const float* f;         // [rows][NT][M][4] = (y, w)
+    const float* geom;      // [NT][2] = (k, fit)
+    int rows, NT, M;        // NT == 0: none, nothing above is read
+};
 
 struct RestraintTables {
     const float* obs;       // [obs_rows][P][5]
@@ -73,6 +95,17 @@ struct RestrainArgs {
     // FRAMED only, behind everything the plain kernel reads so that its argument offsets - and with them its code - stay what they were
     const uint8_t* fixed;   // [B*N] fixed mask bytes
     const float* known;     // [B][N][D] normalised known values (the x columns are read)
+    // TPL only, behind everything the other instantiations read
+    TemplateTables tp;
+};
+
+struct TemplateEnergyArgs {
+    const float* x;         // [B][N][3] positions in data units
+    const uint8_t* nm;
+    TemplateTables tp;
+    double* out;            // [B][NT] U_tpl
+    double* fit16;          // [B][NT][16] (R row-major, c_x, c_y, rmsd); null: not wanted
+    int B, N;
 };
 
 struct RestraintEnergyArgs {
@@ -240,11 +273,132 @@ HD_DEVINL bool rs_frame_shift(const float* pos, int stride, const float* known, 
     return any;
 }
 
+HD_DEVINL bool rs_tpl_active(int i, float w, const uint8_t* nm, int N) { return i >= 0 && i < N && nm[i] && w > 0.f; }
+
+// The fits of the molecule b's templates at positions x [N][3] (data units; global memory or LDS) into fit [NT][RS_FIT] (LDS), visible
+// to every thread on return.  `red`: 4 * 9 doubles of LDS.  Every branch around a barrier is uniform over the workgroup.
+HD_DEVINL void rs_template_fit(const TemplateTables& tt, int b, const float* x, const uint8_t* nm, int N, double* red, double* fit, int tid) {
+    double Sk[9], ck[8];                               // of template t, kept by thread 64 t: S, (c_x, c_y), k, W
+#pragma unroll
+    for (int j = 0; j < 9; ++j) Sk[j] = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ck[j] = 0.0;
+    for (int t = 0; t < tt.NT; ++t) {
+        const size_t row = ((size_t)(tt.rows == 1 ? 0 : b) * tt.NT + t) * tt.M;
+        double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // W, sum w x, sum w y, active rows, non-finite active rows
+        for (int m = tid; m < tt.M; m += 256) {
+            const float* f = tt.f + (row + m) * 4;
+            const int i = tt.idx[row + m];
+            if (!rs_tpl_active(i, f[3], nm, N)) continue;
+            const double w = (double)f[3], x0 = (double)x[3 * i], x1 = (double)x[3 * i + 1], x2 = (double)x[3 * i + 2];
+            s[7] += 1.0;
+            if (!(fabs(x0) < HUGE_VAL && fabs(x1) < HUGE_VAL && fabs(x2) < HUGE_VAL)) { s[8] += 1.0; continue; }
+            s[0] += w;
+            s[1] += w * x0; s[2] += w * x1; s[3] += w * x2;
+            s[4] += w * (double)f[0]; s[5] += w * (double)f[1]; s[6] += w * (double)f[2];
+        }
+        guide_block_sum<9>(s, red, tid);
+        const bool live = s[0] > 0.0 && s[7] >= 2.0 && s[8] == 0.0;
+        double c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        double S[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (live) {
+#pragma unroll
+            for (int j = 0; j < 6; ++j) c[j] = s[1 + j] / s[0];
+            for (int m = tid; m < tt.M; m += 256) {
+                const float* f = tt.f + (row + m) * 4;
+                const int i = tt.idx[row + m];
+                if (!rs_tpl_active(i, f[3], nm, N)) continue;
+                const double w = (double)f[3];
+                const double xp[3] = {(double)x[3 * i] - c[0], (double)x[3 * i + 1] - c[1], (double)x[3 * i + 2] - c[2]};
+                const double yp[3] = {(double)f[0] - c[3], (double)f[1] - c[4], (double)f[2] - c[5]};
+#pragma unroll
+                for (int p = 0; p < 3; ++p)
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) S[3 * p + q] += w * xp[p] * yp[q];
+            }
+            guide_block_sum<9>(S, red, tid);
+        }
+        if (tid == 64 * t) {
+#pragma unroll
+            for (int j = 0; j < 9; ++j) Sk[j] = S[j];
+#pragma unroll
+            for (int j = 0; j < 6; ++j) ck[j] = c[j];
+            ck[6] = (double)tt.geom[2 * t];
+            ck[7] = live ? s[0] : 0.0;
+        }
+    }
+    const int t = tid >> 6;
+    if ((tid & 63) == 0 && t < tt.NT) {
+        double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+        if (ck[7] > 0.0 && tt.geom[2 * t + 1] == 0.f) kabsch_rotation(Sk, R);
+        double* F = fit + t * RS_FIT;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) F[j] = R[j];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) F[9 + j] = ck[j];
+        F[17] = 0.0; F[18] = 0.0;
+    }
+    __syncthreads();
+}
+
+// r_m = (x_i - c_x) - R (y_m - c_y) of one row on node i under the fit F.
+HD_DEVINL void rs_tpl_residual(const double* F, const float* x, int i, const float* f, double (&r)[3]) {
+    const double yp[3] = {(double)f[0] - F[12], (double)f[1] - F[13], (double)f[2] - F[14]};
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        r[c] = ((double)x[3 * i + c] - F[9 + c]) - ((F[3 * c] * yp[0] + F[3 * c + 1] * yp[1]) + F[3 * c + 2] * yp[2]);
+}
+
+// lane `l` of the `G` lanes that gather the valid node i: its share of dU_tpl/dx_i into g, behind rs_node_grad.
+HD_DEVINL void rs_template_grad(const TemplateTables& tt, int b, const float* x, const double* fit, int i, int l, int G, double (&g)[3]) {
+    for (int t = 0; t < tt.NT; ++t) {
+        const double* F = fit + t * RS_FIT;
+        const double k = F[15];
+        if (!(k > 0.0) || !(F[16] > 0.0)) continue;
+        const size_t row = ((size_t)(tt.rows == 1 ? 0 : b) * tt.NT + t) * tt.M;
+        for (int m = l; m < tt.M; m += G) {
+            const float* f = tt.f + (row + m) * 4;
+            if (tt.idx[row + m] != i || !(f[3] > 0.f)) continue;
+            double r[3];
+            rs_tpl_residual(F, x, i, f, r);
+            const double kw = k * (double)f[3];
+            g[0] += kw * r[0]; g[1] += kw * r[1]; g[2] += kw * r[2];
+        }
+    }
+}
+
+// U_tpl = ((U_0 + U_1) + U_2) + U_3 of the molecule b under the fits of rs_template_fit, into every thread: per template a strided
+// double sum over M, then guide_block_sum.  Thread 0 leaves U_t and sum w |r|^2 in fit[t][17], fit[t][18] (the caller's barrier makes
+// them visible).  `red`: 4 doubles of LDS.
+HD_DEVINL double rs_template_block(const TemplateTables& tt, int b, const float* x, const uint8_t* nm, int N, double* red, double* fit,
+                                   int tid) {
+    double total = 0.0;
+    for (int t = 0; t < tt.NT; ++t) {
+        double* F = fit + t * RS_FIT;
+        if (!(F[16] > 0.0)) continue;                  // uniform over the workgroup
+        const size_t row = ((size_t)(tt.rows == 1 ? 0 : b) * tt.NT + t) * tt.M;
+        double q[1] = {0.0};
+        for (int m = tid; m < tt.M; m += 256) {
+            const float* f = tt.f + (row + m) * 4;
+            const int i = tt.idx[row + m];
+            if (!rs_tpl_active(i, f[3], nm, N)) continue;
+            double r[3];
+            rs_tpl_residual(F, x, i, f, r);
+            q[0] += (double)f[3] * ((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+        }
+        guide_block_sum<1>(q, red, tid);
+        const double U = 0.5 * F[15] * q[0];
+        if (tid == 0) { F[17] = U; F[18] = q[0]; }
+        total += U;
+    }
+    return total;
+}
+
 // Dynamic LDS: N * 3 floats (x^0 of the molecule).
-template <bool FRAMED>
+template <bool FRAMED, bool TPL = false>
 __global__ __launch_bounds__(256) void k_restrain_eps(RestrainArgs a) {
     extern __shared__ float rs_x[];
-    __shared__ double red[4 * (FRAMED ? 7 : 4)];
+    __shared__ double red[4 * (TPL ? 9 : FRAMED ? 7 : 4)];
     const int tid = threadIdx.x, b = blockIdx.x;
     const int N = a.N, D = a.D, total = N * D;
     const size_t base = (size_t)b * total;
@@ -273,6 +427,12 @@ __global__ __launch_bounds__(256) void k_restrain_eps(RestrainArgs a) {
         if (rs_frame_shift(rs_x, 3, a.known + base, D, (double)a.nv0, nm, a.fixed + (size_t)b * N, N, red, tid, tau))
             fixed = a.fixed + (size_t)b * N;           // uniform over the workgroup
     }
+    double* fit = nullptr;
+    if constexpr (TPL) {
+        __shared__ double tp_fit[HD_MAX_TEMPLATES * RS_FIT];
+        fit = tp_fit;
+        rs_template_fit(a.tp, b, rs_x, nm, N, red, fit, tid);
+    }
     double* step = a.step + (size_t)b * N * 3;
     const bool clips = clip - clip == 0.f;             // finite
     const int l = tid & (RS_GROUP - 1), grp = tid / RS_GROUP;
@@ -281,9 +441,15 @@ __global__ __launch_bounds__(256) void k_restrain_eps(RestrainArgs a) {
         const bool on = i < N && nm[i];
         double g[3] = {0.0, 0.0, 0.0};
         if constexpr (FRAMED) {
-            if (on && !(fixed && fixed[i])) rs_node_grad(a.t, b, rs_x, nm, N, i, l, RS_GROUP, g, tau);
+            if (on && !(fixed && fixed[i])) {
+                rs_node_grad(a.t, b, rs_x, nm, N, i, l, RS_GROUP, g, tau);
+                if constexpr (TPL) rs_template_grad(a.tp, b, rs_x, fit, i, l, RS_GROUP, g);
+            }
         } else {
-            if (on) rs_node_grad(a.t, b, rs_x, nm, N, i, l, RS_GROUP, g);
+            if (on) {
+                rs_node_grad(a.t, b, rs_x, nm, N, i, l, RS_GROUP, g);
+                if constexpr (TPL) rs_template_grad(a.tp, b, rs_x, fit, i, l, RS_GROUP, g);
+            }
         }
 #pragma unroll
         for (int c = 0; c < 3; ++c)
@@ -415,4 +581,24 @@ __global__ __launch_bounds__(256) void k_restraint_field_energy(RestraintEnergyA
         U = rs_field_block(a.t, b, x, nm, a.N, red, tid);
     }
     if (tid == 0) a.out[b] = U;
+}
+
+// U_tpl [B][NT] and the fits (R, c_x, c_y, rmsd) [B][NT][16] of positions x.  A template that contributes nothing to a molecule (no
+// weight, one active row, a non-finite active coordinate) reports U = 0, R = I, c_x = c_y = 0, rmsd = 0.
+__global__ __launch_bounds__(256) void k_restraint_template_energy(TemplateEnergyArgs a) {
+    __shared__ double red[4 * 9];
+    __shared__ double fit[HD_MAX_TEMPLATES * RS_FIT];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const float* x = a.x + (size_t)b * a.N * 3;
+    const uint8_t* nm = a.nm + (size_t)b * a.N;
+    rs_template_fit(a.tp, b, x, nm, a.N, red, fit, tid);
+    rs_template_block(a.tp, b, x, nm, a.N, red, fit, tid);
+    __syncthreads();
+    const int NT = a.tp.NT;
+    if (tid < NT) a.out[(size_t)b * NT + tid] = fit[tid * RS_FIT + 17];
+    if (a.fit16 && tid < NT * 16) {
+        const int t = tid >> 4, j = tid & 15;
+        const double* F = fit + t * RS_FIT;
+        a.fit16[((size_t)b * NT + t) * 16 + j] = j < 15 ? F[j] : (F[16] > 0.0 ? sqrt(F[18] / F[16]) : 0.0);
+    }
 }

@@ -2,7 +2,7 @@
 // hd_steer_step / hd_steer_read; no reference counterpart).  Included through kernels.hpp.
 // The batch is G groups of P rows; group g owns rows g P .. g P + P - 1 (equal masks, contexts and restraint rows: the caller's
 // business).  Per transition, behind the network call, guidance and k_restrain_eps:
-//   k_steer_weigh      U(b) = ((U_obs + U_pair) + U_anc) + U_fld of the transition's data prediction x^0 (the fp32 operations of k_restrain_eps,
+//   k_steer_weigh      U(b) = (((U_obs + U_pair) + U_anc) + U_fld) + U_tpl of the transition's data prediction x^0 (the fp32 operations of k_restrain_eps,
 //                      the energy code of k_restraint_energy), logw[b] += -beta_k (U - U_prev[b]), U_prev[b] = U.  A non-finite U
 //                      (or update) is weight 0: logw = -inf.
 //   k_steer_resample   per group: m = max logw, w_i = exp(logw_i - m), S = sum w, S2 = sum w^2 in index order (a serial scan by one
@@ -48,12 +48,15 @@ struct SteerWeighArgs {
     float nv0;
     double *logw, *uprev;   // [B]
     int B, N, D;
+    TemplateTables tp;      // TPL only, behind everything k_steer_weigh<false> reads
 };
 
 // Dynamic LDS: N * 3 floats (x^0 of the molecule).
+// TPL: templates are attached; U gains U_tpl (rs_template_fit, rs_template_block) behind U_fld.
+template <bool TPL>
 __global__ __launch_bounds__(256) void k_steer_weigh(SteerWeighArgs a) {
     extern __shared__ float st_x[];
-    __shared__ double red[4 * 3];
+    __shared__ double red[4 * (TPL ? 9 : 3)];
     const int tid = threadIdx.x, b = blockIdx.x;
     const int N = a.N, D = a.D;
     const size_t base = (size_t)b * N * D;
@@ -72,9 +75,16 @@ __global__ __launch_bounds__(256) void k_steer_weigh(SteerWeighArgs a) {
     __syncthreads();
     double U[4];
     rs_energy_block(a.t, b, st_x, nm, N, red, tid, U);
+    double utpl = 0.0;
+    if constexpr (TPL) {
+        __shared__ double tp_fit[HD_MAX_TEMPLATES * RS_FIT];
+        rs_template_fit(a.tp, b, st_x, nm, N, red, tp_fit, tid);
+        utpl = rs_template_block(a.tp, b, st_x, nm, N, red, tp_fit, tid);
+    }
     if (tid == 0) {
         const double u3 = (U[0] + U[1]) + U[2];
-        const double u = a.t.NF ? u3 + U[3] : u3;       // no fields: the old sum's bits
+        const double u4 = a.t.NF ? u3 + U[3] : u3;      // no fields: the old sum's bits
+        const double u = TPL ? u4 + utpl : u4;
         const double dl = -(double)beta * (u - a.uprev[b]);
         // (finite: |v| < inf, false for a NaN.  Not v - v == 0: with v a product the compiler contracts that into the product's rounding error)
         a.logw[b] = (fabs(u) < HUGE_VAL && fabs(dl) < HUGE_VAL) ? a.logw[b] + dl : -HUGE_VAL;

@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import restraints as restraints_mod
 from .distributions import DistributionNodes
 from .dynamics import EGNN_dynamics_QM9, Topology, _ptr, _stream
 from .geom_stats import GEOM_FRAGMENT_HISTOGRAM
@@ -1606,6 +1607,10 @@ class DiffusionQM9(_Base):
             if en is not None and rk["restraints"].n_fields:
                 fen = rk["restraints"].field_energy(
                     got[0], nmd, model=self, _attach=(torch.as_tensor(rk["restraint_scale"]), float(self.norm_values[0]))).cpu()
+            tpl = None
+            if en is not None and rk["restraints"].n_templates:
+                tpl = rk["restraints"].template_results(
+                    got[0], nmd, model=self, _attach=(torch.as_tensor(rk["restraint_scale"]), float(self.norm_values[0])))
             xv, hv = got[0].cpu(), got[1].cpu()
             part = []
             for i in range(nm.shape[0]):
@@ -1617,6 +1622,8 @@ class DiffusionQM9(_Base):
                     res['restraint_energy'] = en[i].clone()
                 if fen is not None:
                     res['restraint_field_energy'] = fen[i].clone()
+                if tpl is not None:
+                    restraints_mod.template_into(res, tpl, i, n)
                 part.append(res)
             if chain_t is not None:
                 self._chain_into(part, got[2], [int(nm[i].sum()) for i in range(nm.shape[0])], chain_t)
@@ -1838,6 +1845,8 @@ class DiffusionQM9(_Base):
         if rr.rs.n_fields:
             info['restraint_field_energy'] = rr.rs.field_energy(got[0], node_mask, model=self, fixed_mask=st.fm_u8, x_known=st.xk,
                                                                 _attach=(rr.scale, float(self.norm_values[0])))
+        if rr.rs.n_templates:
+            info.update(rr.rs.template_results(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0]))))
         return tuple(got) + (info,)
 
     @torch.no_grad()
@@ -1932,6 +1941,8 @@ class DiffusionQM9(_Base):
                 out[i]['restraint_energy'] = info['restraint_energy'][i].clone()
                 if 'restraint_field_energy' in info:
                     out[i]['restraint_field_energy'] = info['restraint_field_energy'][i].clone()
+                if 'restraint_template_energy' in info:
+                    restraints_mod.template_into(out[i], info, i, sizes[i])
                 out[i]['frame_shift'] = info['frame_shift'][i].clone()
                 out[i]['x_known_frame'] = info['x_known_frame'][i, :sizes[i]].clone()
         return out
@@ -2022,6 +2033,10 @@ class DiffusionQM9(_Base):
                 fen = rr.rs.field_energy(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0]))).cpu()
                 for i in range(num_samples):
                     out[i]['restraint_field_energy'] = fen[i].clone()
+            if rr.rs.n_templates:
+                tpl = rr.rs.template_results(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0])))
+                for i in range(num_samples):
+                    restraints_mod.template_into(out[i], tpl, i, sample_n[i])
         if pl.steer is not None:
             from . import steering
             steering.into(out, self.steer_last)

@@ -42,6 +42,23 @@ the gradient joins the same per-node step ahead of the clip and the mean; in the
 energy sums over all valid nodes.  Values are shared by the molecules of a call, weights may differ per molecule; a call carries at
 most MAX_FIELDS fields.
 
+TEMPLATES.  `Template` asks for a 3-D arrangement of named nodes "wherever and however the molecule ends up oriented": at every
+transition the data prediction is superposed rigidly (Kabsch) on the template and the residual of the best fit is the restraint.  Rows
+(i_m, y_m, w_m); a row is active when node i_m exists and is valid in the molecule and w_m > 0.  Over the active rows, in double:
+
+    W = sum w_m,  c_x = sum w_m x_{i_m} / W,  c_y = sum w_m y_m / W,  x'_m = x_{i_m} - c_x,  y'_m = y_m - c_y
+    S = sum w_m x'_m y'_m^T,  R = argmax_{R in SO(3)} tr(R^T S)   ("translation": R = I)
+    r_m = x'_m - R y'_m,  U_tpl = 1/2 k sum w_m |r_m|^2,  rmsd = sqrt(sum w_m |r_m|^2 / W),  dU_tpl/dx_{i_m} += k w_m r_m
+
+R is a proper rotation, so - unlike O(M^2) pair rows, which see distances only - a mirror image of the template does not fit.  The
+gradient is exact: R maximises, so its dependence on x drops out.  No weight, exactly one active row or a non-finite active coordinate:
+the template contributes nothing to that molecule.  With two active rows or collinear ones R is not unique; the energy still is.  A
+template carries its own frame and never sees tau; in the known frame rows on fixed nodes take part in the fit, only free nodes gather
+a gradient.  The fit's by-product is an absolute frame: results carry 'x_template_frame' = R^T (x - c_x) + c_y of the first template -
+the molecule in the template's coordinates, a pocket's if that is where the template came from.  A call carries at most MAX_TEMPLATES.
+Out of scope: obstacles or fields read in the fitted frame (their gradient would need dR/dx), flat-bottomed templates, scaling fits,
+correspondence search (rows name their nodes), templates on h.
+
 A pair or anchor row whose node index is -1 (padding), >= the molecule's size or masked is inactive - documented behaviour, not an
 error, because `sample` draws the sizes.  A term at distance exactly 0 contributes no gradient.
 
@@ -58,6 +75,8 @@ import torch
 SCHEDULES = ("score", "sigma")
 FRAMES = ("model", "known")
 MAX_FIELDS = 8                                   # HD_MAX_FIELDS
+MAX_TEMPLATES = 4                                # HD_MAX_TEMPLATES
+FITS = ("rigid", "translation")
 
 
 def check_frame(model, frame) -> int:
@@ -242,6 +261,90 @@ def _fields(fields) -> list:
     return list(fl)
 
 
+class Template:
+    """One rigid template (module docstring: TEMPLATES).
+
+    index      [M] (shared) or [B, M] (per molecule) node indices, integers >= 0, or -1 for padding
+    positions  [M, 3] or [B, M, 3] template positions y_m, data units, finite (rounded to fp32 once, here)
+    weights    None: every row weighs 1; [M] or [B, M], finite and >= 0 (a row with w = 0 is inactive)
+    k          stiffness >= 0 (k = 0: no force, but the fit and 'x_template_frame' are still reported)
+    fit        "rigid" (rotation and translation) or "translation" (R = I)
+    If any of the three arrays has the batch axis, the others are repeated for every molecule.  ValueError for every malformed
+    argument, before a device is looked at."""
+
+    def __init__(self, index, positions, weights=None, k=1.0, fit="rigid"):
+        def arr(v, name, dtype=torch.float64):
+            if isinstance(v, bool):
+                raise ValueError(f"Template: {name} must be an array, got {v!r}")
+            try:
+                return torch.as_tensor(v).detach().cpu().to(dtype)
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError(f"Template: {name} must be a tensor or nested list of numbers") from None
+        idx, pos = arr(index, "index"), arr(positions, "positions")
+        if idx.dim() not in (1, 2) or idx.numel() == 0:
+            raise ValueError(f"Template: index must be [M] (shared) or [B, M] (per molecule) with M >= 1, got {tuple(idx.shape)}")
+        if not bool(torch.isfinite(idx).all()) or bool((idx != idx.round()).any()) or bool((idx < -1).any()):
+            raise ValueError("Template: node indices must be integers >= 0, or -1 for padding")
+        M = int(idx.shape[-1])
+        if pos.dim() not in (2, 3) or tuple(pos.shape[-2:]) != (M, 3):
+            raise ValueError(f"Template: positions must be [{M}, 3] (shared) or [B, {M}, 3] (per molecule), got {tuple(pos.shape)}")
+        pos = pos.to(torch.float32)
+        if not bool(torch.isfinite(pos).all()):
+            raise ValueError("Template: positions must be finite (in float32)")
+        if weights is None:
+            w = torch.ones(M, dtype=torch.float32)
+        else:
+            w = arr(weights, "weights").to(torch.float32)
+            if w.dim() not in (1, 2) or int(w.shape[-1]) != M:
+                raise ValueError(f"Template: weights must be None, [{M}] or [B, {M}], got {tuple(w.shape)}")
+            if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+                raise ValueError("Template: weights must be finite and >= 0")
+        idx = idx.unsqueeze(0) if idx.dim() == 1 else idx
+        pos = pos.unsqueeze(0) if pos.dim() == 2 else pos
+        w = w.unsqueeze(0) if w.dim() == 1 else w
+        rows = {int(t.shape[0]) for t in (idx, pos, w)} - {1}
+        if len(rows) > 1:
+            raise ValueError(f"Template: index, positions and weights hold rows for {sorted(rows)} molecules; they must agree")
+        r = max(rows | {1})
+        self.index = idx.to(torch.int32).expand(r, M).contiguous()
+        self.positions = pos.expand(r, M, 3).contiguous()
+        self.weights = w.expand(r, M).contiguous()
+        self.k = _number(k, "Template: k")
+        if not isinstance(fit, str) or fit not in FITS:
+            raise ValueError(f"Template: fit must be one of {FITS}, got {fit!r}")
+        self.fit = fit
+
+    @property
+    def rows(self) -> int:
+        return int(self.index.shape[0])
+
+    @property
+    def M(self) -> int:
+        return int(self.index.shape[1])
+
+    def _slice(self, lo: int, hi: int) -> "Template":
+        if self.rows == 1:
+            return self
+        out = object.__new__(Template)
+        out.__dict__.update(self.__dict__)
+        out.index, out.positions, out.weights = (t[lo:hi].contiguous() for t in (self.index, self.positions, self.weights))
+        return out
+
+
+def _templates(templates) -> list:
+    if templates is None:
+        return []
+    tl = [templates] if isinstance(templates, Template) else templates
+    if not isinstance(tl, (list, tuple)) or not all(isinstance(t, Template) for t in tl):
+        raise ValueError("templates must be a restraints.Template or a list of them")
+    if len(tl) > MAX_TEMPLATES:
+        raise ValueError(f"templates: a call carries at most {MAX_TEMPLATES} templates, got {len(tl)}")
+    rows = {t.rows for t in tl} - {1}
+    if len(rows) > 1:
+        raise ValueError(f"templates: per-molecule rows are given for {sorted(rows)} molecules; they must agree")
+    return list(tl)
+
+
 class Restraints:
     """The three tables of one call, validated and kept on the CPU.
 
@@ -249,11 +352,13 @@ class Restraints:
     pairs      [Q, 5] or [B, Q, 5]   rows (i, j, lo, hi, k); i = j = -1 is padding
     anchors    [A, 6] or [B, A, 6]   rows (i, a_x, a_y, a_z, r, k); i = -1 is padding
     fields     a `Field` or a list of at most MAX_FIELDS of them (lattice potentials; `field_energy`, not a column of `energy`)
+    templates  a `Template` or a list of at most MAX_TEMPLATES of them (rigid superposition; `template_energy`)
     Tensors or nested lists; a table with a leading batch axis holds one set of rows per molecule.  ValueError: lo > hi, a negative
     r, k, lo or hi, non-finite values, i == j, fractional indices, negative indices other than -1."""
 
-    def __init__(self, obstacles=None, pairs=None, anchors=None, fields=None):
+    def __init__(self, obstacles=None, pairs=None, anchors=None, fields=None, templates=None):
         self.fields = _fields(fields)
+        self.templates = _templates(templates)
         obs, pr, an = _table(obstacles, 5, "obstacles"), _table(pairs, 5, "pairs"), _table(anchors, 6, "anchors")
         if obs is not None and bool((obs[..., 3:] < 0).any()):
             raise ValueError("obstacles: r and k must be >= 0 (a row with r = 0 or k = 0 is padding)")
@@ -304,8 +409,31 @@ class Restraints:
         r = self.field_rows()
         return torch.stack([f.node_weights(N).expand(r, N) for f in self.fields], 1).contiguous()
 
+    @property
+    def n_templates(self) -> int:
+        return len(getattr(self, "templates", ()))
+
+    def template_rows(self) -> int:
+        """Rows of the template tables: 1 (shared) or the B of the per-molecule ones."""
+        return max([t.rows for t in getattr(self, "templates", ())] + [1])
+
+    def template_tables(self):
+        """(idx [rows, NT, M] int32, f [rows, NT, M, 4] float32 = (y, w), geom [NT, 2] float32 = (k, fit)): the library's tables, M the
+        longest template's, shorter ones padded with inactive rows (index -1, w = 0)."""
+        tl = self.templates
+        r, NT, M = self.template_rows(), len(tl), max(t.M for t in tl)
+        idx = torch.full((r, NT, M), -1, dtype=torch.int32)
+        f = torch.zeros((r, NT, M, 4), dtype=torch.float32)
+        for j, t in enumerate(tl):
+            idx[:, j, :t.M] = t.index
+            f[:, j, :t.M, :3] = t.positions
+            f[:, j, :t.M, 3] = t.weights
+        geom = torch.tensor([[t.k, float(FITS.index(t.fit))] for t in tl], dtype=torch.float32)
+        return idx.contiguous(), f.contiguous(), geom.contiguous()
+
     def check_batch(self, B: int, what: str = "restraints") -> None:
-        for name, r in zip(("obstacles", "pairs", "anchors", "field weights"), self.rows() + (self.field_rows(),)):
+        for name, r in zip(("obstacles", "pairs", "anchors", "field weights", "templates"),
+                           self.rows() + (self.field_rows(), self.template_rows())):
             if r != 1 and r != int(B):
                 raise ValueError(f"{what}: {name} hold rows for {r} molecules, the call has {B} (give [n, w] to share one set)")
 
@@ -316,6 +444,7 @@ class Restraints:
             t = getattr(self, k)
             setattr(out, k, t if t.shape[0] == 1 else t[lo:hi].contiguous())
         out.fields = [f._slice(lo, hi) for f in getattr(self, "fields", ())]
+        out.templates = [t._slice(lo, hi) for t in getattr(self, "templates", ())]
         out._model = getattr(self, "_model", None)
         return out
 
@@ -323,13 +452,24 @@ class Restraints:
     def from_json(cls, path: str) -> "Restraints":
         """A JSON file with the keys `obstacles`, `pairs`, `anchors` (each optional; the row formats above) and `fields` (optional):
         a list of {"file": "pocket.npy", "origin": [...], "spacing": s | [...], "k": ..., "wall": ..., "weights": [...]} - `file`
-        relative to the JSON file, read with numpy.load(allow_pickle=False); k, wall and weights optional."""
+        relative to the JSON file, read with numpy.load(allow_pickle=False); k, wall and weights optional - and `templates` (optional):
+        a list of {"index": [...], "positions": [[...]], "weights": [...], "k": ..., "fit": "rigid" | "translation"}; weights, k and
+        fit optional."""
         import json
         import os
         with open(path) as f:
             d = json.load(f)
-        if not isinstance(d, dict) or set(d) - {"obstacles", "pairs", "anchors", "fields"}:
-            raise ValueError(f"{path}: expected an object with the keys obstacles / pairs / anchors / fields")
+        if not isinstance(d, dict) or set(d) - {"obstacles", "pairs", "anchors", "fields", "templates"}:
+            raise ValueError(f"{path}: expected an object with the keys obstacles / pairs / anchors / fields / templates")
+        templates = None
+        if d.get("templates") is not None:
+            if not isinstance(d["templates"], list):
+                raise ValueError(f"{path}: templates must be a list of objects")
+            templates = []
+            for e in d["templates"]:
+                if not isinstance(e, dict) or set(e) - {"index", "positions", "weights", "k", "fit"} or not {"index", "positions"} <= set(e):
+                    raise ValueError(f"{path}: a template is an object with the keys index, positions (and weights, k, fit)")
+                templates.append(Template(e["index"], e["positions"], e.get("weights"), e.get("k", 1.0), e.get("fit", "rigid")))
         fields = None
         if d.get("fields") is not None:
             if not isinstance(d["fields"], list):
@@ -345,7 +485,7 @@ class Restraints:
                 except (OSError, ValueError) as err:
                     raise ValueError(f"{path}: cannot read the field file {e['file']!r}: {err}") from None
                 fields.append(Field(vals, e["origin"], e["spacing"], e.get("k", 1.0), e.get("wall", 0.0), e.get("weights")))
-        return cls(d.get("obstacles"), d.get("pairs"), d.get("anchors"), fields)
+        return cls(d.get("obstacles"), d.get("pairs"), d.get("anchors"), fields, templates)
 
     # ------------------------------------------------------------------ device side
     def attach(self, topo, scale: torch.Tensor, nv0: float, dev, stream, frame: int = 0) -> None:
@@ -362,6 +502,8 @@ class Restraints:
             stream), "hd_restraint_attach")
         if self.n_fields:                                # (attaching resets to no fields: the order is attach -> fields -> frame)
             self._attach_fields(topo, dev, stream)
+        if self.n_templates:                             # (attaching resets to no templates; fields and templates in either order)
+            self._attach_templates(topo, stream)
         if frame:
             _lib.check(_lib.load().hd_restraint_frame(topo.ptr, int(frame)), "hd_restraint_frame")
 
@@ -382,6 +524,57 @@ class Restraints:
         _lib.check(_lib.load().hd_restraint_fields(
             topo.ptr, NF, pool.data_ptr(), off.ctypes.data_as(C.POINTER(C.c_longlong)), dims.ctypes.data_as(C.POINTER(C.c_int)),
             geom.ctypes.data_as(C.POINTER(C.c_float)), w.data_ptr(), int(w.shape[0]), stream), "hd_restraint_fields")
+
+    def _attach_templates(self, topo, stream) -> None:
+        """hd_restraint_templates: the row tables [rows, NT, M] and the geometry (host arrays) into the topology's buffers."""
+        import ctypes as C
+        from . import _lib
+        idx, f, geom = (t.numpy() for t in self.template_tables())
+        _lib.check(_lib.load().hd_restraint_templates(
+            topo.ptr, int(idx.shape[1]), int(idx.shape[0]), int(idx.shape[2]), idx.ctypes.data_as(C.POINTER(C.c_int)),
+            f.ctypes.data_as(C.POINTER(C.c_float)), geom.ctypes.data_as(C.POINTER(C.c_float)), stream), "hd_restraint_templates")
+
+    def template_energy(self, x: torch.Tensor, node_mask: torch.Tensor, model=None, _attach=None):
+        """(U [B, NT], fit [B, NT, 16]) float64 of positions x [B, N, 3] in data units under node_mask [B, N, 1]: U_tpl per template and
+        its fit (R row-major [9], c_x [3], c_y [3], rmsd) - `template_frame` applies one.  On a device the HIP kernel evaluates it
+        (k_restraint_template_energy; `model` as in `energy`); on the CPU the same formulas in torch float64.  Needs templates."""
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        if tuple(x.shape) != (B, N, 3):
+            raise ValueError(f"x must be [{B}, {N}, 3], got {tuple(x.shape)}")
+        if not self.n_templates:
+            raise ValueError("template_energy: these restraints hold no templates")
+        self.check_batch(B, "template_energy")
+        if x.device.type != "cuda":
+            return template_energy_terms(self, x.detach().double(), node_mask, return_fit=True)
+        model = model if model is not None else (self._model() if getattr(self, "_model", None) is not None else None)
+        if model is None:
+            raise ValueError("template_energy on a device needs model= (the DiffusionQM9 that owns the library handle) unless these "
+                             "restraints have already run in one of its sampling calls")
+        from . import _lib
+        from .dynamics import _stream
+        dev = x.device
+        h = model._lib_handle()
+        topo = model.dynamics.topology(node_mask.to(dev), None, B, N)
+        NT = self.n_templates
+        out = torch.empty((B, NT), device=dev, dtype=torch.float64)
+        fit = torch.empty((B, NT, 16), device=dev, dtype=torch.float64)
+        xs = x.detach().to(torch.float32).contiguous()
+        scale, nv0 = (torch.ones(1), 1.0) if _attach is None else _attach
+        self.attach(topo, scale, nv0, dev, _stream(dev))
+        try:
+            _lib.check(_lib.load().hd_restraint_template_energy(h, topo.ptr, xs.data_ptr(), out.data_ptr(), fit.data_ptr(), _stream(dev)),
+                       "hd_restraint_template_energy")
+        finally:
+            self.detach(topo)
+        return out, fit
+
+    def template_results(self, x: torch.Tensor, node_mask: torch.Tensor, model=None, _attach=None) -> dict:
+        """The result entries of a templated call for its returned x: 'restraint_template_energy' [B, NT], 'template_rmsd' [B, NT] and
+        'x_template_frame' [B, N, 3] = R_0^T (x - c_x) + c_y of template 0 (masked nodes 0), all float64 on x's device."""
+        U, fit = self.template_energy(x, node_mask, model=model, _attach=_attach)
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        xt = template_frame(x, fit[:, 0]) * node_mask.reshape(B, N, 1).to(fit.device, torch.float64)
+        return {'restraint_template_energy': U, 'template_rmsd': fit[..., 15].clone(), 'x_template_frame': xt}
 
     def field_energy(self, x: torch.Tensor, node_mask: torch.Tensor, model=None, fixed_mask=None, x_known=None, _attach=None):
         """[B] float64 U_fld of positions x [B, N, 3] in data units under node_mask [B, N, 1] (0 without fields).  On a device the HIP
@@ -555,6 +748,70 @@ def field_energy_terms(rs: Restraints, x: torch.Tensor, node_mask: torch.Tensor)
         e = f.k * w * (V + 0.5 * f.wall * (out * out).sum(-1))
         total = total + torch.where(ok, e, torch.zeros_like(e)).sum(1)
     return total
+
+
+def kabsch_rotation(S: torch.Tensor) -> torch.Tensor:
+    """R [3, 3] = argmax over proper rotations of tr(R^T S) for S [3, 3] = sum w x' y'^T (x' ~ R y'): Horn's quaternion form, the
+    eigenvector of the largest eigenvalue of the symmetric 4x4 matrix by torch.linalg.eigh.  Never a reflection."""
+    xx, xy, xz, yx, yy, yz, zx, zy, zz = S.reshape(9).unbind()
+    K = torch.stack([torch.stack([xx + yy + zz, zy - yz, xz - zx, yx - xy]),
+                     torch.stack([zy - yz, xx - yy - zz, xy + yx, zx + xz]),
+                     torch.stack([xz - zx, xy + yx, -xx + yy - zz, yz + zy]),
+                     torch.stack([yx - xy, zx + xz, yz + zy, -xx - yy + zz])])
+    q = torch.linalg.eigh(K)[1][:, -1]
+    q0, q1, q2, q3 = (q / q.norm()).unbind()
+    return torch.stack([torch.stack([q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3, 2 * (q1 * q2 - q0 * q3), 2 * (q1 * q3 + q0 * q2)]),
+                        torch.stack([2 * (q1 * q2 + q0 * q3), q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3, 2 * (q2 * q3 - q0 * q1)]),
+                        torch.stack([2 * (q1 * q3 - q0 * q2), 2 * (q2 * q3 + q0 * q1), q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3])])
+
+
+def template_energy_terms(rs: Restraints, x: torch.Tensor, node_mask: torch.Tensor, return_fit: bool = False):
+    """[B, NT] U_tpl in x's dtype, differentiable in x: the template formulas of the module docstring in torch.  R is found under
+    no_grad - it maximises, so autograd through the rest gives the exact gradient k w r.  `return_fit`: (U, fit [B, NT, 16]) with
+    fit = (R row-major, c_x, c_y, rmsd), detached; a template that contributes nothing reports R = I, c_x = c_y = 0, rmsd = 0."""
+    B, N = int(x.shape[0]), int(x.shape[1])
+    nm = node_mask.reshape(B, N).bool().to(x.device)
+    tl = getattr(rs, "templates", ())
+    U, fits = [], torch.zeros(B, len(tl), 16, dtype=x.dtype, device=x.device)
+    for b in range(B):
+        row = []
+        for j, t in enumerate(tl):
+            r_ = 0 if t.rows == 1 else b
+            idx, y, w = t.index[r_].long().to(x.device), t.positions[r_].to(x), t.weights[r_].to(x)
+            act = (idx >= 0) & (idx < N) & (w > 0)
+            act = act & nm[b][idx.clamp(0, N - 1)]
+            fits[b, j, 0] = fits[b, j, 4] = fits[b, j, 8] = 1.0
+            u = x.new_zeros(())
+            if int(act.sum()) >= 2 and bool(torch.isfinite(x[b][idx[act]]).all()):
+                xi, y, w = x[b][idx[act]], y[act], w[act]
+                W = w.sum()
+                cx, cy = (w[:, None] * xi).sum(0) / W, (w[:, None] * y).sum(0) / W
+                xp, yp = xi - cx, y - cy
+                with torch.no_grad():
+                    R = kabsch_rotation((w[:, None, None] * xp[:, :, None] * yp[:, None, :]).sum(0)) if t.fit == "rigid" \
+                        else torch.eye(3, dtype=x.dtype, device=x.device)
+                res = xp - yp @ R.T
+                q = (w * (res * res).sum(-1)).sum()
+                u = 0.5 * t.k * q
+                fits[b, j] = torch.cat([R.reshape(9), cx.detach(), cy, torch.sqrt(q.detach() / W).reshape(1)])
+            row.append(u)
+        U.append(torch.stack(row) if row else x.new_zeros(0))
+    U = torch.stack(U)
+    return (U, fits) if return_fit else U
+
+
+def template_frame(x: torch.Tensor, fit: torch.Tensor) -> torch.Tensor:
+    """x [..., N, 3] in the coordinates of a template: R^T (x - c_x) + c_y for fit [..., 16] (float64)."""
+    fit = fit.to(torch.float64)
+    R = fit[..., :9].reshape(fit.shape[:-1] + (3, 3))
+    return (x.to(fit.device, torch.float64) - fit[..., None, 9:12]) @ R + fit[..., None, 12:15]
+
+
+def template_into(res: dict, tpl: dict, i: int, n: int) -> None:
+    """Molecule i (n nodes) of `Restraints.template_results` into the result dict of that molecule, on the CPU."""
+    res['restraint_template_energy'] = tpl['restraint_template_energy'][i].cpu().clone()
+    res['template_rmsd'] = tpl['template_rmsd'][i].cpu().clone()
+    res['x_template_frame'] = tpl['x_template_frame'][i, :n].cpu().clone()
 
 
 def _norm(v):

@@ -143,6 +143,11 @@ def check_groups(st: Steer, node_mask, context=None, rs=None, scale=None, what: 
                 if w is not None and w.shape[0] == B and B > 1 and not _rows_equal(w.reshape(B, -1), P):
                     bad = "restraint rows (field weights)"
                     break
+        if bad is None:
+            for t in getattr(rs, "templates", ()):
+                if t.rows == B and B > 1 and not all(_rows_equal(v.reshape(B, -1), P) for v in (t.index, t.positions, t.weights)):
+                    bad = "restraint rows (templates)"
+                    break
     if bad is None and scale is not None and torch.as_tensor(scale).numel() == B and not _rows_equal(torch.as_tensor(scale).cpu().reshape(B, 1), P):
         bad = "restraint scales"
     if bad is not None:

@@ -503,6 +503,43 @@ int hd_restraint_field_energy(hd_handle* h, hd_topology* topo, const float* x, d
 int hd_restraint_field_energy_framed(hd_handle* h, hd_topology* topo, const float* x, const uint8_t* fixed_mask, const float* x_known,
                                      double* out, double* shift3, void* stream);
 
+/* ---- Template restraints (ABI 12, additive; no reference counterpart): the optimal rigid superposition (Kabsch) of the data
+ * prediction onto a 3-D template as a fifth term of the restraint energy - "lay these nodes out like this arrangement, wherever and
+ * however the molecule ends up oriented".  A topology with attached restraints carries up to HD_MAX_TEMPLATES templates of M rows:
+ *   idx   [rows][NT][M] int32          the node i_m a row names; rows = 1 (shared) or B          host
+ *   f     [rows][NT][M][4] fp32        (y_x, y_y, y_z, w): the template position and the weight  host
+ *   geom  [NT][2] fp32                 (k >= 0, fit: 0 rigid, 1 translation only)                host
+ * A row is ACTIVE in molecule b when 0 <= i_m < N, node i_m is valid in b and w_m > 0 (a row that names a node the molecule lacks is
+ * inactive, as for anchors; pad a short template with w = 0).  Over the active rows, in double, on the fp32 x^0 of the restraint
+ * update or the given x of the energy call:
+ *   W = sum w_m,  c_x = sum w_m x_{i_m} / W,  c_y = sum w_m y_m / W,  x'_m = x_{i_m} - c_x,  y'_m = y_m - c_y
+ *   S = sum w_m x'_m y'_m^T,  R = argmax_{R in SO(3)} tr(R^T S)  (fit 1: R = I)      a proper rotation: a mirror image does not fit
+ *   r_m = x'_m - R y'_m,  U_tpl,t = 1/2 k_t sum w_m |r_m|^2,  rmsd_t = sqrt(sum w_m |r_m|^2 / W)
+ *   dU_tpl,t/dx_{i_m} += k_t w_m r_m        exact: R maximises, so its dependence on x drops out, and sum w_m r_m = 0
+ * R comes from Horn's quaternion form, the eigenvector of the largest eigenvalue of a symmetric 4x4 matrix by a cyclic Jacobi
+ * iteration of a fixed number of sweeps: deterministic, and independent of the molecule's place in the batch.  R is unique iff
+ * sigma_2 + sign(det S) sigma_3 > 0 for the singular values of S; otherwise (two active rows, collinear rows) some maximiser is used -
+ * the energy is unique, the gradient finite.  W = 0, exactly one active row, or a non-finite active coordinate: the template
+ * contributes neither energy nor gradient to that molecule.  The gradient joins dU/dx_i of the update above behind the fields, ahead
+ * of the scale, the clip and the mean.  A template does not see tau: it carries its own frame.  In frame 1 rows on fixed nodes take
+ * part in the fit and the energy, only free nodes gather a gradient, and fixed nodes receive -mean like every valid node.
+ * hd_steer_step and the steered loops weigh on (((U_obs + U_pair) + U_anc) + U_fld) + U_tpl, U_tpl = ((U_0 + U_1) + U_2) + U_3.
+ * No atomics; every sum has a fixed order that depends on (N, M) alone.
+ * hd_restraint_templates: stream-ordered copies into buffers the topology owns.  Needs attached restraints (HD_E_STATE).
+ *   hd_restraint_attach resets the topology to NO templates, as it resets the fields and the frame; the order of the fields and the
+ *   templates calls is free.  NT = 0 clears the templates.  HD_E_INVALID: NT outside 0 .. 4, M < 1, rows other than 1 or B, a negative
+ *   or non-finite k or w, a non-finite y, a fit other than 0 or 1, a null pointer with NT > 0.
+ *   use_graph    re-attaching tables of the same (NT, M, rows) is a copy: the cached transition replays.  Other sizes rebuild once; a
+ *                templated call followed by an untemplated one on the same topology rebuilds and gives the bits of a topology that
+ *                never had templates.
+ * hd_restraint_template_energy: out [B][NT] = U_tpl,t in double for positions x [B][N][3] (fp32, data units) under the topology's mask;
+ *   fit16 [B][NT][16] (NULL: not wanted) = (R row-major [9], c_x [3], c_y [3], rmsd): x_{template frame} = R^T (x - c_x) + c_y.  A
+ *   template that contributes nothing to a molecule reports U = 0, R = I, c_x = c_y = 0, rmsd = 0.  Stream-ordered.  Without attached
+ *   restraints or without templates it writes nothing and returns HD_E_STATE. */
+#define HD_MAX_TEMPLATES 4
+int hd_restraint_templates(hd_topology* topo, int NT, int rows, int M, const int* idx, const float* f, const float* geom, void* stream);
+int hd_restraint_template_energy(hd_handle* h, hd_topology* topo, const float* x, double* out, double* fit16, void* stream);
+
 /* ---- Steered sampling (ABI 12, additive; no reference counterpart): sequential Monte-Carlo steering of a restrained path loop.
  * The batch is G groups of P rows (particles); group g owns rows g P .. g P + P - 1, which the CALLER guarantees to have equal
  * masks, contexts and restraint rows.  At every transition k, behind the network call, guidance and the restraint update of eps^:
