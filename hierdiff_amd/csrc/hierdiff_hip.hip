@@ -161,6 +161,17 @@ struct hd_handle {
     size_t pool_used;
 };
 
+// The restraint part of a captured transition's key (restraint_key in host_loops.hpp builds it); all 0: not restrained.
+struct RestraintKey {
+    unsigned long long gen, rows_gen;          // the topology's tables (RestraintState::gen), the handle's rows
+    int frame;                                 // 1: the restraints act in the known fragments' frame (hd_restraint_frame)
+    unsigned long long fld_gen;                // fields attached: their buffers, NF, rows (0: none)
+    unsigned long long tpl_gen;                // templates attached: their buffers, NT, M, rows (0: none)
+    bool operator==(const RestraintKey& o) const {
+        return gen == o.gen && rows_gen == o.rows_gen && frame == o.frame && fld_gen == o.fld_gen && tpl_gen == o.tpl_gen;
+    }
+};
+
 // Everything a captured transition of the path loop has baked in (plain: resamplings = 0): a cached graph is replayed only when
 // all of it is unchanged.  path_gen is the generation (PathTables::gen) of the tables it runs on (the caller's path, or the every-step tables).
 struct PathKey {
@@ -170,20 +181,18 @@ struct PathKey {
     float phi;
     uint64_t seed;
     unsigned long long weights_gen, sched_gen, path_gen, ip_gen;
-    unsigned long long rs_gen, rs_rows_gen;                  // restrained transition: the topology's tables, the handle's rows (0 / 0: plain)
-    int rs_frame;                                            // 1: its restraints act in the known fragments' frame (hd_restraint_frame)
     int ip_parts;                                            // 1: an inpainting transition with per-channel masks (hd_inpaint_parts)
-    unsigned long long rs_fld_gen;                           // its restraints hold fields (hd_restraint_fields): their buffers, NF, rows (0: none)
-    unsigned long long rs_tpl_gen;                           // ... templates (hd_restraint_templates): their buffers, NT, M, rows (0: none)
+    RestraintKey rs;
     int st_P;                                                // steered transition: particles per group, rho, the topology's steering
     double st_ess;                                           // buffers, the handle's rows (all 0: not steered)
     unsigned long long st_gen, st_rows_gen;
     bool operator==(const PathKey& o) const {
-        return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape && noise_rows == o.noise_rows &&
-               k_lo == o.k_lo && resamplings == o.resamplings && w_rows == o.w_rows && phi == o.phi && seed == o.seed &&
-               weights_gen == o.weights_gen && sched_gen == o.sched_gen && path_gen == o.path_gen && ip_gen == o.ip_gen &&
-               rs_gen == o.rs_gen && rs_rows_gen == o.rs_rows_gen && rs_frame == o.rs_frame && ip_parts == o.ip_parts && rs_fld_gen == o.rs_fld_gen && rs_tpl_gen == o.rs_tpl_gen && st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen &&
-               st_rows_gen == o.st_rows_gen;
+        return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape &&
+               noise_rows == o.noise_rows && k_lo == o.k_lo && resamplings == o.resamplings &&
+               w_rows == o.w_rows && phi == o.phi && seed == o.seed &&
+               weights_gen == o.weights_gen && sched_gen == o.sched_gen && path_gen == o.path_gen &&
+               ip_gen == o.ip_gen && ip_parts == o.ip_parts && rs == o.rs &&
+               st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen && st_rows_gen == o.st_rows_gen;
     }
 };
 
@@ -219,6 +228,50 @@ struct GraphSlot {
     Key key;
     long long builds;
 };
+
+// One library-owned device table of a topology, at an address captured transitions keep; `fill` (host_loops.hpp) is its one writer.
+template <typename T>
+struct DevTable {
+    T* p;
+    size_t cap;
+    int fill(const T* src, size_t count, bool* moved, hipStream_t s);
+};
+
+// What restraints keep on a topology; all-zero when value-initialised (nothing attached).  A generation moves when something its
+// setter's captured launches bake in does - an address, a size, a row count, nv0; re-attaching tables of the same sizes is a copy.
+// NF / NT are what is attached NOW (0 after hd_restraint_attach); fld_NF, tpl_NT and the sizes next to them what was last baked in.
+struct RestraintState {
+    bool on;
+    int frame;                                 // hd_restraint_frame: 0 the model's frame, 1 the known fragments' (inpainting calls)
+    // hd_restraint_attach: the tables, the per-molecule scales and the scratch of k_restrain_eps (allocated once)
+    DevTable<float> obs, pair_f, anc_f, scale;
+    DevTable<int> pair_idx, anc_idx;
+    double* step;
+    int obs_rows, P, pair_rows, Q, anc_rows, A, scale_rows;
+    float nv0;
+    unsigned long long gen;
+    // hd_restraint_fields: the value pool, the weights; offsets / dims / geometry of up to HD_MAX_FIELDS fields (allocated once each)
+    DevTable<float> fld_v, fld_w;
+    long long* fld_off;
+    int* fld_dims;
+    float* fld_geom;
+    int NF, fld_NF, fld_w_rows;
+    unsigned long long fld_gen;
+    // hd_restraint_templates: the row tables; the geometry of up to HD_MAX_TEMPLATES templates (one allocation, made by the first call)
+    DevTable<int> tpl_idx;
+    DevTable<float> tpl_f;
+    float* tpl_geom;
+    int NT, tpl_NT, tpl_M, tpl_rows;
+    unsigned long long tpl_gen;
+};
+
+static void restraint_free(RestraintState& r) {
+    for (void* p : {(void*)r.obs.p, (void*)r.pair_idx.p, (void*)r.pair_f.p, (void*)r.anc_idx.p, (void*)r.anc_f.p, (void*)r.scale.p,
+                    (void*)r.step, (void*)r.fld_v.p, (void*)r.fld_w.p, (void*)r.fld_off, (void*)r.fld_dims, (void*)r.fld_geom,
+                    (void*)r.tpl_idx.p, (void*)r.tpl_f.p, (void*)r.tpl_geom})
+        if (p) (void)hipFree(p);
+    r = RestraintState{};
+}
 
 struct hd_topology {
     hd_handle* h;
@@ -264,35 +317,8 @@ struct hd_topology {
     int chain_frames, chain_what;              // what 0: the state behind the transition, 1: its data prediction
     float chain_nv0, chain_nv1, chain_nb1;
     GraphSlot<ChainKey> g_chain;
-    // hd_restraint_attach: library-owned copies of the restraint tables (addresses a captured transition keeps; they grow, never
-    // shrink), the per-molecule scales and the scratch of k_restrain_eps.  rs_gen moves when anything a captured launch bakes in does
-    // (an address, a size, a row count, nv0); re-attaching tables of the same sizes is a copy.
-    bool rs_on;
-    float *rs_obs, *rs_pair_f, *rs_anc_f, *rs_scale;
-    int *rs_pair_idx, *rs_anc_idx;
-    double* rs_step;
-    size_t rs_cap[6];
-    int rs_obs_rows, rs_P, rs_pair_rows, rs_Q, rs_anc_rows, rs_A, rs_scale_rows;
-    float rs_nv0;
-    unsigned long long rs_gen;
-    int rs_frame;                              // hd_restraint_frame: 0 the model's frame, 1 the known fragments' (inpainting calls)
-    // hd_restraint_fields: the value pool and the weights (grown by the rule above), the offsets / dims / geometry of up to
-    // HD_MAX_FIELDS fields at fixed addresses (one allocation each, made by the first call).  rs_NF is what is attached now (0 after
-    // hd_restraint_attach); rs_fld_NF / rs_fld_w_rows are what the last fielded call baked in, and rs_fld_gen moves when that changes.
-    float *rs_fld_v, *rs_fld_w, *rs_fld_geom;
-    long long* rs_fld_off;
-    int* rs_fld_dims;
-    size_t rs_fld_cap[2];
-    int rs_NF, rs_fld_NF, rs_fld_w_rows;
-    unsigned long long rs_fld_gen;
-    // hd_restraint_templates: the row tables (grown by the rule above) and the geometry of up to HD_MAX_TEMPLATES templates (one
-    // allocation, made by the first call).  rs_NT is what is attached now (0 after hd_restraint_attach); rs_tpl_NT / rs_tpl_M /
-    // rs_tpl_rows are what the last templated call baked in, and rs_tpl_gen moves when that changes.
-    int* rs_tpl_idx;
-    float *rs_tpl_f, *rs_tpl_geom;
-    size_t rs_tpl_cap[2];
-    int rs_NT, rs_tpl_NT, rs_tpl_M, rs_tpl_rows;
-    unsigned long long rs_tpl_gen;
+    // hd_restraint_attach / _fields / _templates / _frame: everything restraints keep on a topology
+    RestraintState rs;
     // hd_steer_attach: the steering state of the chain that runs on this topology (log-weights, last energies, lineage roots, the
     // ancestors of the latest transition, per-group statistics) and the scratch of k_steer_gather - one allocation each, made by the
     // first attach at addresses captured transitions keep.  It survives between the pieces of a chain; `reset` starts a new one.
@@ -876,9 +902,8 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     for (hipGraphExec_t* gx : graph_execs(t)) graph_drop(gx);
     if (t->guide_mem) (void)hipFree(t->guide_mem);
     if (t->ms_hist) (void)hipFree(t->ms_hist);
-    for (void* p : {(void*)t->rs_obs, (void*)t->rs_pair_idx, (void*)t->rs_pair_f, (void*)t->rs_anc_idx, (void*)t->rs_anc_f,
-                    (void*)t->rs_scale, (void*)t->rs_step, (void*)t->rs_fld_v, (void*)t->rs_fld_w, (void*)t->rs_fld_geom, (void*)t->rs_tpl_idx, (void*)t->rs_tpl_f, (void*)t->rs_tpl_geom,
-                    (void*)t->rs_fld_off, (void*)t->rs_fld_dims, (void*)t->st_f64, (void*)t->st_i32, (void*)t->st_scratch})
+    restraint_free(t->rs);
+    for (void* p : {(void*)t->st_f64, (void*)t->st_i32, (void*)t->st_scratch})
         if (p) (void)hipFree(p);
     if (t->ip_fixed) (void)hipFree(t->ip_fixed);
     if (t->ip_known) (void)hipFree(t->ip_known);

@@ -518,19 +518,29 @@ extern "C" int hd_set_restraint(hd_handle* h, int K, const float* rows4) {
     return set_row_table(h, h->rs_rows, K, rows4, 4);
 }
 
-// one library-owned table of the topology: grown when `count` exceeds its capacity (then *moved is set), filled from `src`
+// grown when `count` exceeds the capacity (then *moved is set), filled from `src` (device or host memory)
 template <typename T>
-static int rs_table(T** buf, size_t* cap, const T* src, size_t count, bool* moved, hipStream_t s) {
-    if (count > *cap || !*buf) {
+int DevTable<T>::fill(const T* src, size_t count, bool* moved, hipStream_t s) {
+    if (count > cap || !p) {
         HIP_TRY(hipDeviceSynchronize());                // a replay may still read the old table
-        if (*buf) (void)hipFree(*buf);
-        *buf = nullptr; *cap = 0;
-        HD_TRY(dev_alloc(buf, count));
-        *cap = std::max<size_t>(count, 1);
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+        HD_TRY(dev_alloc(&p, count));
+        cap = std::max<size_t>(count, 1);
         *moved = true;
     }
-    if (count) HIP_TRY(hipMemcpyAsync(*buf, src, count * sizeof(T), hipMemcpyDefault, s));
+    if (count) HIP_TRY(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyDefault, s));
     return HD_OK;
+}
+
+// The tail of a setter.  `sizes`: {what the last call baked into captured launches, what this call brings}, stored; the generation
+// moves when one of them differs or a buffer has `moved`.
+static void restraint_bake(std::initializer_list<std::pair<int*, int>> sizes, bool moved, unsigned long long* gen) {
+    for (const auto& sz : sizes) {
+        moved = moved || *sz.first != sz.second;
+        *sz.first = sz.second;
+    }
+    if (moved) ++*gen;
 }
 
 extern "C" int hd_restraint_attach(hd_topology* topo, const float* obs, int obs_rows, int P, const int* pair_idx, const float* pair_f,
@@ -548,24 +558,23 @@ extern "C" int hd_restraint_attach(hd_topology* topo, const float* obs, int obs_
     HIP_TRY(hipSetDevice(topo->device));
     hipStream_t s = (hipStream_t)stream;
     topo_use(topo, s);
-    topo->rs_on = false;
+    RestraintState& r = topo->rs;
+    r.on = false;
     bool moved = false;
-    HD_TRY(rs_table(&topo->rs_obs, &topo->rs_cap[0], obs, (size_t)obs_rows * P * 5, &moved, s));
-    HD_TRY(rs_table(&topo->rs_pair_idx, &topo->rs_cap[1], pair_idx, (size_t)pair_rows * Q * 2, &moved, s));
-    HD_TRY(rs_table(&topo->rs_pair_f, &topo->rs_cap[2], pair_f, (size_t)pair_rows * Q * 3, &moved, s));
-    HD_TRY(rs_table(&topo->rs_anc_idx, &topo->rs_cap[3], anc_idx, (size_t)anc_rows * A, &moved, s));
-    HD_TRY(rs_table(&topo->rs_anc_f, &topo->rs_cap[4], anc_f, (size_t)anc_rows * A * 5, &moved, s));
-    HD_TRY(rs_table(&topo->rs_scale, &topo->rs_cap[5], scale, (size_t)scale_rows, &moved, s));
-    if (!topo->rs_step) { HD_TRY(dev_alloc(&topo->rs_step, (size_t)B * topo->N * 3)); moved = true; }
-    if (moved || obs_rows != topo->rs_obs_rows || P != topo->rs_P || pair_rows != topo->rs_pair_rows || Q != topo->rs_Q ||
-        anc_rows != topo->rs_anc_rows || A != topo->rs_A || scale_rows != topo->rs_scale_rows || nv0 != topo->rs_nv0)
-        topo->rs_gen++;
-    topo->rs_obs_rows = obs_rows; topo->rs_P = P; topo->rs_pair_rows = pair_rows; topo->rs_Q = Q; topo->rs_anc_rows = anc_rows;
-    topo->rs_A = A; topo->rs_scale_rows = scale_rows; topo->rs_nv0 = nv0;
-    topo->rs_frame = 0;                                 // the model's frame, until hd_restraint_frame says otherwise
-    topo->rs_NF = 0;                                    // no fields, until hd_restraint_fields says otherwise
-    topo->rs_NT = 0;                                    // no templates, until hd_restraint_templates says otherwise
-    topo->rs_on = true;
+    HD_TRY(r.obs.fill(obs, (size_t)obs_rows * P * 5, &moved, s));
+    HD_TRY(r.pair_idx.fill(pair_idx, (size_t)pair_rows * Q * 2, &moved, s));
+    HD_TRY(r.pair_f.fill(pair_f, (size_t)pair_rows * Q * 3, &moved, s));
+    HD_TRY(r.anc_idx.fill(anc_idx, (size_t)anc_rows * A, &moved, s));
+    HD_TRY(r.anc_f.fill(anc_f, (size_t)anc_rows * A * 5, &moved, s));
+    HD_TRY(r.scale.fill(scale, (size_t)scale_rows, &moved, s));
+    if (!r.step) { HD_TRY(dev_alloc(&r.step, (size_t)B * topo->N * 3)); moved = true; }
+    restraint_bake({{&r.obs_rows, obs_rows}, {&r.P, P}, {&r.pair_rows, pair_rows}, {&r.Q, Q}, {&r.anc_rows, anc_rows}, {&r.A, A},
+                    {&r.scale_rows, scale_rows}}, moved || nv0 != r.nv0, &r.gen);
+    r.nv0 = nv0;
+    r.frame = 0;                                        // the model's frame, until hd_restraint_frame says otherwise
+    r.NF = 0;                                           // no fields, until hd_restraint_fields says otherwise
+    r.NT = 0;                                           // no templates, until hd_restraint_templates says otherwise
+    r.on = true;
     return HD_OK;
 }
 
@@ -573,8 +582,8 @@ extern "C" int hd_restraint_fields(hd_topology* topo, int NF, const float* value
                                    const float* geom, const float* weights, int w_rows, void* stream) {
     if (!topo) return fail(HD_E_INVALID, "hd_restraint_fields: null topology");
     if (NF < 0 || NF > HD_MAX_FIELDS) return fail(HD_E_INVALID, "hd_restraint_fields: NF must be 0 .. 8");
-    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restraint_fields: no restraints attached to the topology (hd_restraint_attach)");
-    if (NF == 0) { topo->rs_NF = 0; return HD_OK; }
+    if (!topo->rs.on) return fail(HD_E_STATE, "hd_restraint_fields: no restraints attached to the topology (hd_restraint_attach)");
+    if (NF == 0) { topo->rs.NF = 0; return HD_OK; }
     if (!values || !offsets || !dims || !geom || !weights) return fail(HD_E_INVALID, "hd_restraint_fields: null table");
     if (w_rows != 1 && w_rows != topo->B) return fail(HD_E_INVALID, "hd_restraint_fields: the weights have 1 row (shared) or B rows");
     if (offsets[0] != 0) return fail(HD_E_INVALID, "hd_restraint_fields: offsets[0] must be 0");
@@ -598,23 +607,23 @@ extern "C" int hd_restraint_fields(hd_topology* topo, int NF, const float* value
     HIP_TRY(hipSetDevice(topo->device));
     hipStream_t s = (hipStream_t)stream;
     topo_use(topo, s);
-    topo->rs_NF = 0;
+    RestraintState& r = topo->rs;
+    r.NF = 0;
     bool moved = false;
-    if (!topo->rs_fld_geom) {
-        if (!topo->rs_fld_off) HD_TRY(dev_alloc(&topo->rs_fld_off, (size_t)HD_MAX_FIELDS + 1));
-        if (!topo->rs_fld_dims) HD_TRY(dev_alloc(&topo->rs_fld_dims, (size_t)HD_MAX_FIELDS * 3));
-        HD_TRY(dev_alloc(&topo->rs_fld_geom, (size_t)HD_MAX_FIELDS * 8));    // last: its presence says all three are there
+    if (!r.fld_geom) {
+        if (!r.fld_off) HD_TRY(dev_alloc(&r.fld_off, (size_t)HD_MAX_FIELDS + 1));
+        if (!r.fld_dims) HD_TRY(dev_alloc(&r.fld_dims, (size_t)HD_MAX_FIELDS * 3));
+        HD_TRY(dev_alloc(&r.fld_geom, (size_t)HD_MAX_FIELDS * 8));          // last: its presence says all three are there
         moved = true;
     }
-    HD_TRY(rs_table(&topo->rs_fld_v, &topo->rs_fld_cap[0], values, (size_t)offsets[NF], &moved, s));
-    HD_TRY(rs_table(&topo->rs_fld_w, &topo->rs_fld_cap[1], weights, (size_t)w_rows * NF * topo->N, &moved, s));
+    HD_TRY(r.fld_v.fill(values, (size_t)offsets[NF], &moved, s));
+    HD_TRY(r.fld_w.fill(weights, (size_t)w_rows * NF * topo->N, &moved, s));
     // (host arrays: pageable sources are staged before the call returns)
-    HIP_TRY(hipMemcpyAsync(topo->rs_fld_off, offsets, ((size_t)NF + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(topo->rs_fld_dims, dims, (size_t)NF * 3 * sizeof(int), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(topo->rs_fld_geom, geom, (size_t)NF * 8 * sizeof(float), hipMemcpyHostToDevice, s));
-    if (moved || NF != topo->rs_fld_NF || w_rows != topo->rs_fld_w_rows) topo->rs_fld_gen++;
-    topo->rs_fld_NF = NF; topo->rs_fld_w_rows = w_rows;
-    topo->rs_NF = NF;
+    HIP_TRY(hipMemcpyAsync(r.fld_off, offsets, ((size_t)NF + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(r.fld_dims, dims, (size_t)NF * 3 * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(r.fld_geom, geom, (size_t)NF * 8 * sizeof(float), hipMemcpyHostToDevice, s));
+    restraint_bake({{&r.fld_NF, NF}, {&r.fld_w_rows, w_rows}}, moved, &r.fld_gen);
+    r.NF = NF;
     return HD_OK;
 }
 
@@ -622,8 +631,8 @@ extern "C" int hd_restraint_templates(hd_topology* topo, int NT, int rows, int M
                                       void* stream) {
     if (!topo) return fail(HD_E_INVALID, "hd_restraint_templates: null topology");
     if (NT < 0 || NT > HD_MAX_TEMPLATES) return fail(HD_E_INVALID, "hd_restraint_templates: NT must be 0 .. 4");
-    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restraint_templates: no restraints attached to the topology (hd_restraint_attach)");
-    if (NT == 0) { topo->rs_NT = 0; return HD_OK; }
+    if (!topo->rs.on) return fail(HD_E_STATE, "hd_restraint_templates: no restraints attached to the topology (hd_restraint_attach)");
+    if (NT == 0) { topo->rs.NT = 0; return HD_OK; }
     if (M < 1) return fail(HD_E_INVALID, "hd_restraint_templates: M must be >= 1");
     if (rows != 1 && rows != topo->B) return fail(HD_E_INVALID, "hd_restraint_templates: the tables have 1 row (shared) or B rows");
     if (!idx || !f || !geom) return fail(HD_E_INVALID, "hd_restraint_templates: null table");
@@ -642,46 +651,61 @@ extern "C" int hd_restraint_templates(hd_topology* topo, int NT, int rows, int M
     HIP_TRY(hipSetDevice(topo->device));
     hipStream_t s = (hipStream_t)stream;
     topo_use(topo, s);
-    topo->rs_NT = 0;
+    RestraintState& r = topo->rs;
+    r.NT = 0;
     bool moved = false;
-    if (!topo->rs_tpl_geom) { HD_TRY(dev_alloc(&topo->rs_tpl_geom, (size_t)HD_MAX_TEMPLATES * 2)); moved = true; }
+    if (!r.tpl_geom) { HD_TRY(dev_alloc(&r.tpl_geom, (size_t)HD_MAX_TEMPLATES * 2)); moved = true; }
     // (host arrays: pageable sources are staged before the call returns)
-    HD_TRY(rs_table(&topo->rs_tpl_idx, &topo->rs_tpl_cap[0], idx, cnt, &moved, s));
-    HD_TRY(rs_table(&topo->rs_tpl_f, &topo->rs_tpl_cap[1], f, cnt * 4, &moved, s));
-    HIP_TRY(hipMemcpyAsync(topo->rs_tpl_geom, geom, (size_t)NT * 2 * sizeof(float), hipMemcpyHostToDevice, s));
-    if (moved || NT != topo->rs_tpl_NT || M != topo->rs_tpl_M || rows != topo->rs_tpl_rows) topo->rs_tpl_gen++;
-    topo->rs_tpl_NT = NT; topo->rs_tpl_M = M; topo->rs_tpl_rows = rows;
-    topo->rs_NT = NT;
+    HD_TRY(r.tpl_idx.fill(idx, cnt, &moved, s));
+    HD_TRY(r.tpl_f.fill(f, cnt * 4, &moved, s));
+    HIP_TRY(hipMemcpyAsync(r.tpl_geom, geom, (size_t)NT * 2 * sizeof(float), hipMemcpyHostToDevice, s));
+    restraint_bake({{&r.tpl_NT, NT}, {&r.tpl_M, M}, {&r.tpl_rows, rows}}, moved, &r.tpl_gen);
+    r.NT = NT;
     return HD_OK;
 }
 
 extern "C" int hd_restraint_frame(hd_topology* topo, int frame) {
     if (!topo) return fail(HD_E_INVALID, "hd_restraint_frame: null topology");
     if (frame != 0 && frame != 1) return fail(HD_E_INVALID, "hd_restraint_frame: frame is 0 (the model's) or 1 (the known fragments')");
-    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restraint_frame: no restraints attached to the topology (hd_restraint_attach)");
-    topo->rs_frame = frame;                             // part of the graph key (PathKey::rs_frame)
+    if (!topo->rs.on) return fail(HD_E_STATE, "hd_restraint_frame: no restraints attached to the topology (hd_restraint_attach)");
+    topo->rs.frame = frame;                             // part of the graph key (RestraintKey::frame)
     return HD_OK;
 }
 
 extern "C" int hd_restraint_detach(hd_topology* topo) {
-    if (topo) topo->rs_on = false;
+    if (topo) topo->rs.on = false;
     return HD_OK;
 }
 
+// The kernels' views of the state (k_restrain.hpp): NF / NT are what is attached now, not what was last baked in.
 static RestraintTables restraint_tables(const hd_topology* t) {
+    const RestraintState& s = t->rs;
     RestraintTables r;
-    r.obs = t->rs_obs; r.pair_idx = t->rs_pair_idx; r.pair_f = t->rs_pair_f; r.anc_idx = t->rs_anc_idx; r.anc_f = t->rs_anc_f;
-    r.obs_rows = t->rs_obs_rows; r.P = t->rs_P; r.pair_rows = t->rs_pair_rows; r.Q = t->rs_Q; r.anc_rows = t->rs_anc_rows; r.A = t->rs_A;
-    r.fld_v = t->rs_fld_v; r.fld_off = t->rs_fld_off; r.fld_dims = t->rs_fld_dims; r.fld_geom = t->rs_fld_geom; r.fld_w = t->rs_fld_w;
-    r.fld_w_rows = t->rs_fld_w_rows; r.NF = t->rs_NF;
+    r.obs = s.obs.p; r.pair_idx = s.pair_idx.p; r.pair_f = s.pair_f.p; r.anc_idx = s.anc_idx.p; r.anc_f = s.anc_f.p;
+    r.obs_rows = s.obs_rows; r.P = s.P; r.pair_rows = s.pair_rows; r.Q = s.Q; r.anc_rows = s.anc_rows; r.A = s.A;
+    r.fld_v = s.fld_v.p; r.fld_off = s.fld_off; r.fld_dims = s.fld_dims; r.fld_geom = s.fld_geom; r.fld_w = s.fld_w.p;
+    r.fld_w_rows = s.fld_w_rows; r.NF = s.NF;
     return r;
 }
 
 static TemplateTables template_tables(const hd_topology* t) {
+    const RestraintState& s = t->rs;
     TemplateTables r;
-    r.idx = t->rs_tpl_idx; r.f = t->rs_tpl_f; r.geom = t->rs_tpl_geom;
-    r.rows = t->rs_tpl_rows; r.NT = t->rs_NT; r.M = t->rs_tpl_M;
+    r.idx = s.tpl_idx.p; r.f = s.tpl_f.p; r.geom = s.tpl_geom;
+    r.rows = s.tpl_rows; r.NT = s.NT; r.M = s.tpl_M;
     return r;
+}
+
+// The restraint part of a path graph's key: all 0 unless the transition is `restrained`; the fields' / templates' generations
+// only while some are attached.
+static RestraintKey restraint_key(const hd_handle* h, const hd_topology* topo, bool restrained, bool framed) {
+    RestraintKey k{};
+    if (!restrained) return k;
+    const RestraintState& s = topo->rs;
+    k.gen = s.gen; k.rows_gen = h->rs_rows.gen; k.frame = framed ? 1 : 0;
+    k.fld_gen = s.NF ? s.fld_gen : 0;
+    k.tpl_gen = s.NT ? s.tpl_gen : 0;
+    return k;
 }
 
 // The update of one transition on eps (in place when out == eps): `rows` the device table read at position *io.step / io.row, or the
@@ -690,15 +714,15 @@ static int restrain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const
                            const float* rows, const float* row4, bool framed = false) {
     ProfScope ps(h, io.s, 2);
     RestrainArgs a;
-    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.t = restraint_tables(t); a.scale = t->rs_scale;
+    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.t = restraint_tables(t); a.scale = t->rs.scale.p;
     a.rows = rows;
     for (int i = 0; i < 4; ++i) a.row[i] = row4 ? row4[i] : 0.f;
-    a.step_ptr = io.step; a.k = io.row; a.step = t->rs_step; a.nv0 = t->rs_nv0; a.scale_rows = t->rs_scale_rows;
+    a.step_ptr = io.step; a.k = io.row; a.step = t->rs.step; a.nv0 = t->rs.nv0; a.scale_rows = t->rs.scale_rows;
     a.B = t->B; a.N = t->N; a.D = h->D;
     a.fixed = framed ? io.fixed : nullptr; a.known = framed ? io.known : nullptr;
     a.tp = template_tables(t);
     const size_t lds = (size_t)t->N * 3 * sizeof(float);
-    if (t->rs_NT) {                                     // templates attached: the instantiations with the fit
+    if (t->rs.NT) {                                     // templates attached: the instantiations with the fit
         if (framed) hipLaunchKernelGGL((k_restrain_eps<true, true>), dim3(t->B), dim3(256), lds, io.s, a);
         else hipLaunchKernelGGL((k_restrain_eps<false, true>), dim3(t->B), dim3(256), lds, io.s, a);
     } else if (framed) hipLaunchKernelGGL((k_restrain_eps<true, false>), dim3(t->B), dim3(256), lds, io.s, a);
@@ -707,118 +731,98 @@ static int restrain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const
     return HD_OK;
 }
 
-extern "C" int hd_restrain_eps(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4, float* out,
-                               void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_restrain_eps: null handle/topology");
-    if (!z || !eps || !row4 || !out) return fail(HD_E_INVALID, "hd_restrain_eps: null tensor / row");
-    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restrain_eps: no restraints attached to the topology (hd_restraint_attach)");
-    if (!restraint_row_ok(row4))
-        return fail(HD_E_INVALID, "hd_restrain_eps: need alpha_t > 0, sigma_t >= 0, a finite lambda and clip > 0 (inf: no clip)");
-    const size_t per = (size_t)topo->B * topo->N * h->D;
-    if (out < z + per && z < out + per) return fail(HD_E_INVALID, "hd_restrain_eps: out may not overlap z");
-    if (out != eps && out < eps + per && eps < out + per)
-        return fail(HD_E_INVALID, "hd_restrain_eps: out may be eps itself, not a shifted overlap of it");
-    HIP_TRY(hipSetDevice(h->device));
-    LoopIO io{};
-    io.s = (hipStream_t)stream;
-    topo_use(topo, io.s);
-    return restrain_launch(h, topo, io, z, eps, out, nullptr, row4);
+// A refusal of the entry point `who`; its text is built here, so a call that passes allocates nothing.
+static int refuse(int code, const char* who, const std::string& msg) { return fail(code, who + msg); }
+
+// What every entry point that reads the attached restraints refuses first.  `given`: its tensors are there; `templates`: it needs some.
+static int restraint_refusals(const char* who, const hd_handle* h, const hd_topology* topo, bool given, const char* what,
+                              bool templates = false) {
+    if (!h || !topo) return refuse(HD_E_INVALID, who, ": null handle/topology");
+    if (!given) return refuse(HD_E_INVALID, who, std::string(": null ") + what);
+    if (!topo->rs.on) return refuse(HD_E_STATE, who, ": no restraints attached to the topology (hd_restraint_attach)");
+    if (templates && !topo->rs.NT) return refuse(HD_E_STATE, who, ": no templates attached to the topology (hd_restraint_templates)");
+    return HD_OK;
 }
 
-extern "C" int hd_restrain_eps_framed(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4,
-                                      const uint8_t* fixed_mask, const float* xh_known, float* out, void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_restrain_eps_framed: null handle/topology");
-    if (!z || !eps || !row4 || !out || !fixed_mask || !xh_known)
-        return fail(HD_E_INVALID, "hd_restrain_eps_framed: null tensor / row / fixed_mask / xh_known");
-    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restrain_eps_framed: no restraints attached to the topology (hd_restraint_attach)");
-    if (!restraint_row_ok(row4))
-        return fail(HD_E_INVALID, "hd_restrain_eps_framed: need alpha_t > 0, sigma_t >= 0, a finite lambda and clip > 0 (inf: no clip)");
+// ... and the rest of the preamble of the energy entry points: the device, and `stream` behind the arrival of the topology's tables.
+static int restraint_entry(const char* who, hd_handle* h, hd_topology* topo, bool given, bool templates, void* stream) {
+    HD_TRY(restraint_refusals(who, h, topo, given, "tensor", templates));
+    HIP_TRY(hipSetDevice(h->device));
+    topo_use(topo, (hipStream_t)stream);
+    return HD_OK;
+}
+
+// hd_restrain_eps / hd_restrain_eps_framed (`framed`: fixed_mask and xh_known are part of the call)
+static int restrain_eps(const char* who, hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4,
+                        const uint8_t* fixed_mask, const float* xh_known, float* out, void* stream, bool framed) {
+    HD_TRY(restraint_refusals(who, h, topo, z && eps && row4 && out && (!framed || (fixed_mask && xh_known)),
+                              framed ? "tensor / row / fixed_mask / xh_known" : "tensor / row"));
+    if (!restraint_row_ok(row4)) return refuse(HD_E_INVALID, who, ": need alpha_t > 0, sigma_t >= 0, a finite lambda and clip > 0 (inf: no clip)");
     const size_t per = (size_t)topo->B * topo->N * h->D;
-    if (out < z + per && z < out + per) return fail(HD_E_INVALID, "hd_restrain_eps_framed: out may not overlap z");
-    if (out < xh_known + per && xh_known < out + per) return fail(HD_E_INVALID, "hd_restrain_eps_framed: out may not overlap xh_known");
-    if (out != eps && out < eps + per && eps < out + per)
-        return fail(HD_E_INVALID, "hd_restrain_eps_framed: out may be eps itself, not a shifted overlap of it");
+    if (out < z + per && z < out + per) return refuse(HD_E_INVALID, who, ": out may not overlap z");
+    if (framed && out < xh_known + per && xh_known < out + per) return refuse(HD_E_INVALID, who, ": out may not overlap xh_known");
+    if (out != eps && out < eps + per && eps < out + per) return refuse(HD_E_INVALID, who, ": out may be eps itself, not a shifted overlap of it");
     HIP_TRY(hipSetDevice(h->device));
     LoopIO io{};
     io.s = (hipStream_t)stream; io.fixed = fixed_mask; io.known = xh_known;
     topo_use(topo, io.s);
-    return restrain_launch(h, topo, io, z, eps, out, nullptr, row4, true);
+    return restrain_launch(h, topo, io, z, eps, out, nullptr, row4, framed);
 }
 
-extern "C" int hd_restraint_energy(hd_handle* h, hd_topology* topo, const float* x, double* out3, void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_restraint_energy: null handle/topology");
-    if (!x || !out3) return fail(HD_E_INVALID, "hd_restraint_energy: null tensor");
-    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restraint_energy: no restraints attached to the topology (hd_restraint_attach)");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
-    ProfScope ps(h, s, 2);
-    RestraintEnergyArgs a{};
-    a.x = x; a.nm = topo->nm_bytes; a.t = restraint_tables(topo); a.out = out3; a.B = topo->B; a.N = topo->N;
-    hipLaunchKernelGGL(k_restraint_energy<false>, dim3(topo->B), dim3(256), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
+extern "C" int hd_restrain_eps(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4, float* out,
+                               void* stream) {
+    return restrain_eps("hd_restrain_eps", h, topo, z, eps, row4, nullptr, nullptr, out, stream, false);
 }
 
-extern "C" int hd_restraint_energy_framed(hd_handle* h, hd_topology* topo, const float* x, const uint8_t* fixed_mask,
-                                          const float* x_known, double* out3, double* shift3, void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_restraint_energy_framed: null handle/topology");
-    if (!x || !out3 || !fixed_mask || !x_known) return fail(HD_E_INVALID, "hd_restraint_energy_framed: null tensor");
-    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restraint_energy_framed: no restraints attached to the topology (hd_restraint_attach)");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
-    ProfScope ps(h, s, 2);
-    RestraintEnergyArgs a{};
-    a.x = x; a.nm = topo->nm_bytes; a.t = restraint_tables(topo); a.out = out3; a.B = topo->B; a.N = topo->N;
-    a.fixed = fixed_mask; a.x_known = x_known; a.shift = shift3;
-    hipLaunchKernelGGL(k_restraint_energy<true>, dim3(topo->B), dim3(256), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
+extern "C" int hd_restrain_eps_framed(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4,
+                                      const uint8_t* fixed_mask, const float* xh_known, float* out, void* stream) {
+    return restrain_eps("hd_restrain_eps_framed", h, topo, z, eps, row4, fixed_mask, xh_known, out, stream, true);
 }
 
-static int field_energy_launch(const char* who, hd_handle* h, hd_topology* topo, const float* x, const uint8_t* fixed_mask,
-                               const float* x_known, double* out, double* shift3, void* stream, bool framed) {
-    const std::string w(who);
-    if (!h || !topo) return fail(HD_E_INVALID, w + ": null handle/topology");
-    if (!x || !out || (framed && (!fixed_mask || !x_known))) return fail(HD_E_INVALID, w + ": null tensor");
-    if (!topo->rs_on) return fail(HD_E_STATE, w + ": no restraints attached to the topology (hd_restraint_attach)");
-    HIP_TRY(hipSetDevice(h->device));
+// One of the four kernels on RestraintEnergyArgs, behind restraint_entry (unframed: fixed_mask, x_known and shift are null).
+static int energy_launch(void (*kernel)(RestraintEnergyArgs), hd_handle* h, hd_topology* topo, const float* x, const uint8_t* fixed_mask,
+                         const float* x_known, double* out, double* shift3, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
     ProfScope ps(h, s, 2);
     RestraintEnergyArgs a{};
     a.x = x; a.nm = topo->nm_bytes; a.t = restraint_tables(topo); a.out = out; a.B = topo->B; a.N = topo->N;
     a.fixed = fixed_mask; a.x_known = x_known; a.shift = shift3;
-    if (framed) hipLaunchKernelGGL(k_restraint_field_energy<true>, dim3(topo->B), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_restraint_field_energy<false>, dim3(topo->B), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(kernel, dim3(topo->B), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
 
+extern "C" int hd_restraint_energy(hd_handle* h, hd_topology* topo, const float* x, double* out3, void* stream) {
+    HD_TRY(restraint_entry("hd_restraint_energy", h, topo, x && out3, false, stream));
+    return energy_launch(k_restraint_energy<false>, h, topo, x, nullptr, nullptr, out3, nullptr, stream);
+}
+
+extern "C" int hd_restraint_energy_framed(hd_handle* h, hd_topology* topo, const float* x, const uint8_t* fixed_mask,
+                                          const float* x_known, double* out3, double* shift3, void* stream) {
+    HD_TRY(restraint_entry("hd_restraint_energy_framed", h, topo, x && out3 && fixed_mask && x_known, false, stream));
+    return energy_launch(k_restraint_energy<true>, h, topo, x, fixed_mask, x_known, out3, shift3, stream);
+}
+
+extern "C" int hd_restraint_field_energy(hd_handle* h, hd_topology* topo, const float* x, double* out, void* stream) {
+    HD_TRY(restraint_entry("hd_restraint_field_energy", h, topo, x && out, false, stream));
+    return energy_launch(k_restraint_field_energy<false>, h, topo, x, nullptr, nullptr, out, nullptr, stream);
+}
+
+extern "C" int hd_restraint_field_energy_framed(hd_handle* h, hd_topology* topo, const float* x, const uint8_t* fixed_mask,
+                                                const float* x_known, double* out, double* shift3, void* stream) {
+    HD_TRY(restraint_entry("hd_restraint_field_energy_framed", h, topo, x && out && fixed_mask && x_known, false, stream));
+    return energy_launch(k_restraint_field_energy<true>, h, topo, x, fixed_mask, x_known, out, shift3, stream);
+}
+
 extern "C" int hd_restraint_template_energy(hd_handle* h, hd_topology* topo, const float* x, double* out, double* fit16, void* stream) {
-    if (!h || !topo) return fail(HD_E_INVALID, "hd_restraint_template_energy: null handle/topology");
-    if (!x || !out) return fail(HD_E_INVALID, "hd_restraint_template_energy: null tensor");
-    if (!topo->rs_on) return fail(HD_E_STATE, "hd_restraint_template_energy: no restraints attached to the topology (hd_restraint_attach)");
-    if (!topo->rs_NT) return fail(HD_E_STATE, "hd_restraint_template_energy: no templates attached to the topology (hd_restraint_templates)");
-    HIP_TRY(hipSetDevice(h->device));
+    HD_TRY(restraint_entry("hd_restraint_template_energy", h, topo, x && out, true, stream));
     hipStream_t s = (hipStream_t)stream;
-    topo_use(topo, s);
     ProfScope ps(h, s, 2);
     TemplateEnergyArgs a{};
     a.x = x; a.nm = topo->nm_bytes; a.tp = template_tables(topo); a.out = out; a.fit16 = fit16; a.B = topo->B; a.N = topo->N;
     hipLaunchKernelGGL(k_restraint_template_energy, dim3(topo->B), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
     return HD_OK;
-}
-
-extern "C" int hd_restraint_field_energy(hd_handle* h, hd_topology* topo, const float* x, double* out, void* stream) {
-    return field_energy_launch("hd_restraint_field_energy", h, topo, x, nullptr, nullptr, out, nullptr, stream, false);
-}
-
-extern "C" int hd_restraint_field_energy_framed(hd_handle* h, hd_topology* topo, const float* x, const uint8_t* fixed_mask,
-                                                const float* x_known, double* out, double* shift3, void* stream) {
-    return field_energy_launch("hd_restraint_field_energy_framed", h, topo, x, fixed_mask, x_known, out, shift3, stream, true);
 }
 
 // ----------------------------------------------------------------------------- steering: particle resampling on the restraint energy
@@ -878,9 +882,9 @@ static int steer_launch(hd_handle* h, hd_topology* t, const LoopIO& io, float* z
     SteerWeighArgs w;
     w.z = z; w.eps = eps; w.nm = t->nm_bytes; w.t = restraint_tables(t); w.rows = rows;
     for (int i = 0; i < 3; ++i) w.row[i] = row3 ? row3[i] : 0.f;
-    w.step_ptr = io.step; w.k = io.row; w.nv0 = t->rs_nv0; w.logw = st.logw; w.uprev = st.uprev; w.B = t->B; w.N = t->N; w.D = h->D;
+    w.step_ptr = io.step; w.k = io.row; w.nv0 = t->rs.nv0; w.logw = st.logw; w.uprev = st.uprev; w.B = t->B; w.N = t->N; w.D = h->D;
     w.tp = template_tables(t);
-    if (t->rs_NT) hipLaunchKernelGGL(k_steer_weigh<true>, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, w);
+    if (t->rs.NT) hipLaunchKernelGGL(k_steer_weigh<true>, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, w);
     else hipLaunchKernelGGL(k_steer_weigh<false>, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, w);
     SteerResampleArgs r;
     r.st = st; r.ess = t->st_ess; r.seed = seed; r.base = io.base; r.draw = d.value; r.draw_ptr = d.word; r.base_ptr = io.base_w;
@@ -900,7 +904,7 @@ extern "C" int hd_steer_step(hd_handle* h, hd_topology* topo, float* z, float* e
     if (!h || !topo) return fail(HD_E_INVALID, "hd_steer_step: null handle/topology");
     if (!z || !eps || !row3) return fail(HD_E_INVALID, "hd_steer_step: null tensor / row");
     if (!topo->st_on) return fail(HD_E_STATE, "hd_steer_step: no steering attached to the topology (hd_steer_attach)");
-    if (!topo->rs_on) return fail(HD_E_STATE, "hd_steer_step: no restraints attached to the topology (hd_restraint_attach)");
+    if (!topo->rs.on) return fail(HD_E_STATE, "hd_steer_step: no restraints attached to the topology (hd_restraint_attach)");
     if (!steer_row_ok(row3)) return fail(HD_E_INVALID, "hd_steer_step: need alpha_t > 0, sigma_t >= 0 and a finite beta >= 0");
     const size_t per = (size_t)topo->B * topo->N * h->D;
     if (z < eps + per && eps < z + per) return fail(HD_E_INVALID, "hd_steer_step: z and eps may not overlap");
@@ -1015,8 +1019,8 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
             return fail(HD_E_STATE, "path loop: recording the data prediction needs the {alpha_t, sigma_t} rows (hd_set_chain)");
         if (mol != N) return fail(HD_E_INVALID, "path loop: a chain sink records whole molecules only (mol_shape < N)");
     }
-    const bool rsn = c.record && topo->rs_on;
-    const bool framed = rsn && topo->rs_frame == 1;
+    const bool rsn = c.record && topo->rs.on;
+    const bool framed = rsn && topo->rs.frame == 1;
     if (rsn) {
         if (R && !framed) return fail(HD_E_INVALID, "path loop: restraints are attached to the topology, and inpainting takes none (it re-centres "
                                                     "on the known fragments: hd_restraint_detach)");
@@ -1086,10 +1090,8 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     key.raw_x = c.raw_x; key.raw_h = c.raw_h; key.has_ctx = c.context ? 1 : 0; key.mol_shape = ms; key.noise_rows = c.noise_rows;
     key.k_lo = c.raw_x ? k_lo : 0; key.resamplings = R; key.seed = c.seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
     key.path_gen = pt.gen; key.ip_gen = R ? h->ip_gen : 0; key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
-    key.rs_gen = rsn ? topo->rs_gen : 0; key.rs_rows_gen = rsn ? h->rs_rows.gen : 0; key.rs_frame = framed ? 1 : 0;
+    key.rs = restraint_key(h, topo, rsn, framed);
     key.ip_parts = parts ? 1 : 0;
-    key.rs_fld_gen = rsn && topo->rs_NF ? topo->rs_fld_gen : 0;
-    key.rs_tpl_gen = rsn && topo->rs_NT ? topo->rs_tpl_gen : 0;
     key.st_P = stn ? topo->st_P : 0; key.st_ess = stn ? topo->st_ess : 0.0; key.st_gen = stn ? topo->st_gen : 0;
     key.st_rows_gen = stn ? h->st_rows.gen : 0;
     PathWords w;
@@ -1230,7 +1232,7 @@ extern "C" int hd_sample_path_inpaint(hd_handle* h, hd_topology* topo, float* z,
     const char* who = "hd_sample_path_inpaint";
     if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_sample_path_inpaint: need 0 <= k_lo <= k_hi <= K");
     HD_TRY(check_ready(h, topo, who));
-    if (topo->rs_on && !topo->rs_frame) return fail(HD_E_INVALID, "hd_sample_path_inpaint: restraints are attached to the topology, and inpainting takes "
+    if (topo->rs.on && !topo->rs.frame) return fail(HD_E_INVALID, "hd_sample_path_inpaint: restraints are attached to the topology, and inpainting takes "
                                                "none (it re-centres on the known fragments: hd_restraint_detach)");
     HD_TRY(path_ready(h, who, k_lo, k_hi));
     HD_TRY(inpaint_path_check(who, h, ": ancestral rows only (the path was set with form = 1)"));
@@ -1277,7 +1279,7 @@ extern "C" int hd_sample_path_guided(hd_handle* h, hd_topology* topo, float* z, 
     if (!(rescale >= 0.f && rescale <= 1.f)) return fail(HD_E_INVALID, "hd_sample_path_guided: rescale must lie in [0, 1]");
     if (!h->cfg.condition_time) return fail(HD_E_INVALID, "hd_sample_path_guided: needs a time-conditioned model");
     if (fixed_mask) {                                        // the restrictions of hd_sample_path_inpaint
-        if (topo->rs_on && !topo->rs_frame) return fail(HD_E_INVALID, "hd_sample_path_guided: restraints are attached to the topology, and inpainting "
+        if (topo->rs.on && !topo->rs.frame) return fail(HD_E_INVALID, "hd_sample_path_guided: restraints are attached to the topology, and inpainting "
                                                    "takes none (it re-centres on the known fragments: hd_restraint_detach)");
         HD_TRY(inpaint_path_check(who, h, ": inpainting takes ancestral rows only (the path was set with form = 1)"));
         if (!xh_known) return fail(HD_E_INVALID, "hd_sample_path_guided: fixed_mask without xh_known");

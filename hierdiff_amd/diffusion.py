@@ -764,6 +764,12 @@ class DiffusionQM9(_Base):
             res['chain_t'] = chain_t.clone()
         return results
 
+    def _restraint_entries(self, rs, scale, x, node_mask, fixed_mask=None, x_known=None, cpu: bool = True) -> dict:
+        """`Restraints.result_entries` of a restrained call's returned x, attached as the call attached them (its scales, the model's
+        nv0); `cpu`: moved to the CPU."""
+        ent = rs.result_entries(x, node_mask, self, (torch.as_tensor(scale), float(self.norm_values[0])), fixed_mask, x_known)
+        return {k: v.cpu() for k, v in ent.items()} if cpu else ent
+
     def _check_masked(self, x, node_mask, what):
         if self.debug_checks:
             bad = (x * (~node_mask.bool())).abs().max().item()
@@ -1601,16 +1607,7 @@ class DiffusionQM9(_Base):
                 rk = dict(restraints=rr_all.rs.slice(lo, lo + nm.shape[0]),
                           restraint_scale=rr_all.scale if rr_all.scale.numel() == 1 else rr_all.scale[lo:lo + nm.shape[0]])
             got = self.sample_from_latent(z, nmd, None, ctxd, t_start=t_start, sample_id_base=base, guidance_scale=gs, **few, **rk)
-            en = None if rr_all is None else rk["restraints"].energy(
-                got[0], nmd, model=self, _attach=(torch.as_tensor(rk["restraint_scale"]), float(self.norm_values[0]))).cpu()
-            fen = None
-            if en is not None and rk["restraints"].n_fields:
-                fen = rk["restraints"].field_energy(
-                    got[0], nmd, model=self, _attach=(torch.as_tensor(rk["restraint_scale"]), float(self.norm_values[0]))).cpu()
-            tpl = None
-            if en is not None and rk["restraints"].n_templates:
-                tpl = rk["restraints"].template_results(
-                    got[0], nmd, model=self, _attach=(torch.as_tensor(rk["restraint_scale"]), float(self.norm_values[0])))
+            ent = {} if rr_all is None else self._restraint_entries(rk["restraints"], rk["restraint_scale"], got[0], nmd)
             xv, hv = got[0].cpu(), got[1].cpu()
             part = []
             for i in range(nm.shape[0]):
@@ -1618,12 +1615,7 @@ class DiffusionQM9(_Base):
                 res = {'x': xv[i, :n].clone(), 'h': hv[i, :n].clone()}
                 if ctx is not None:
                     res['context'] = ctx[i, :n].clone()
-                if en is not None:
-                    res['restraint_energy'] = en[i].clone()
-                if fen is not None:
-                    res['restraint_field_energy'] = fen[i].clone()
-                if tpl is not None:
-                    restraints_mod.template_into(res, tpl, i, n)
+                restraints_mod.entries_into(res, ent, i, n)
                 part.append(res)
             if chain_t is not None:
                 self._chain_into(part, got[2], [int(nm[i].sum()) for i in range(nm.shape[0])], chain_t)
@@ -1838,15 +1830,9 @@ class DiffusionQM9(_Base):
         rr = pl.restraints
         if rr is None or not rr.frame:
             return got
-        en, tau = rr.rs.energy(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0])),
-                               fixed_mask=st.fm_u8, x_known=st.xk, return_shift=True)
-        xkf = ((got[0].double() - tau[:, None, :]) * node_mask.to(st.dev, torch.float64)).to(torch.float32)
-        info = {'restraint_energy': en, 'frame_shift': tau, 'x_known_frame': xkf}
-        if rr.rs.n_fields:
-            info['restraint_field_energy'] = rr.rs.field_energy(got[0], node_mask, model=self, fixed_mask=st.fm_u8, x_known=st.xk,
-                                                                _attach=(rr.scale, float(self.norm_values[0])))
-        if rr.rs.n_templates:
-            info.update(rr.rs.template_results(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0]))))
+        info = self._restraint_entries(rr.rs, rr.scale, got[0], node_mask, st.fm_u8, st.xk, cpu=False)
+        tau = info['frame_shift']
+        info['x_known_frame'] = ((got[0].double() - tau[:, None, :]) * node_mask.to(st.dev, torch.float64)).to(torch.float32)
         return tuple(got) + (info,)
 
     @torch.no_grad()
@@ -1938,13 +1924,7 @@ class DiffusionQM9(_Base):
         if pl0.restraints is not None:
             info = {k: v.cpu() for k, v in got[-1].items()}
             for i in range(num):
-                out[i]['restraint_energy'] = info['restraint_energy'][i].clone()
-                if 'restraint_field_energy' in info:
-                    out[i]['restraint_field_energy'] = info['restraint_field_energy'][i].clone()
-                if 'restraint_template_energy' in info:
-                    restraints_mod.template_into(out[i], info, i, sizes[i])
-                out[i]['frame_shift'] = info['frame_shift'][i].clone()
-                out[i]['x_known_frame'] = info['x_known_frame'][i, :sizes[i]].clone()
+                restraints_mod.entries_into(out[i], info, i, sizes[i])
         return out
 
     @torch.no_grad()
@@ -2026,17 +2006,9 @@ class DiffusionQM9(_Base):
             self._chain_into(out, got[2], sample_n, pl.chain_t)
         rr = pl.restraints
         if rr is not None:
-            en = rr.rs.energy(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0]))).cpu()
+            ent = self._restraint_entries(rr.rs, rr.scale, got[0], node_mask)
             for i in range(num_samples):
-                out[i]['restraint_energy'] = en[i].clone()
-            if rr.rs.n_fields:
-                fen = rr.rs.field_energy(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0]))).cpu()
-                for i in range(num_samples):
-                    out[i]['restraint_field_energy'] = fen[i].clone()
-            if rr.rs.n_templates:
-                tpl = rr.rs.template_results(got[0], node_mask, model=self, _attach=(rr.scale, float(self.norm_values[0])))
-                for i in range(num_samples):
-                    restraints_mod.template_into(out[i], tpl, i, sample_n[i])
+                restraints_mod.entries_into(out[i], ent, i, sample_n[i])
         if pl.steer is not None:
             from . import steering
             steering.into(out, self.steer_last)

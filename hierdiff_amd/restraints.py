@@ -534,39 +534,67 @@ class Restraints:
             topo.ptr, int(idx.shape[1]), int(idx.shape[0]), int(idx.shape[2]), idx.ctypes.data_as(C.POINTER(C.c_int)),
             f.ctypes.data_as(C.POINTER(C.c_float)), geom.ctypes.data_as(C.POINTER(C.c_float)), stream), "hd_restraint_templates")
 
+    @staticmethod
+    def _framed_args(fixed_mask, x_known, B: int, N: int, dev, what: str):
+        """None for a call in the model's frame, else (fixed_mask, x_known) after their checks; with a device `dev`, as the library
+        takes them: uint8 [B * N] and float32 [B, N, 3] there."""
+        if (fixed_mask is None) != (x_known is None):
+            raise ValueError(f"{what}: fixed_mask and x_known go together")
+        if fixed_mask is None:
+            return None
+        if fixed_mask.numel() != B * N or tuple(x_known.shape) != (B, N, 3):
+            raise ValueError(f"{what}: fixed_mask must hold {B} x {N} entries and x_known be [{B}, {N}, 3]")
+        if dev is None:
+            return fixed_mask, x_known
+        return (fixed_mask.to(dev).reshape(B * N) != 0).to(torch.uint8).contiguous(), x_known.detach().to(dev, torch.float32).contiguous()
+
+    @staticmethod
+    def _batch_shape(x, node_mask):
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        if tuple(x.shape) != (B, N, 3):
+            raise ValueError(f"x must be [{B}, {N}, 3], got {tuple(x.shape)}")
+        return B, N
+
+    def _on_device(self, x, node_mask, model, _attach, what: str, call):
+        """The device path of `energy`, `field_energy` and `template_energy`, behind their checks: call(run) between attach and detach,
+        where run(name, *args) is the library's entry point `name`(handle, topology, x as contiguous float32, *args, stream).
+        (`_attach`: the scales and nv0 of the sampling call whose result this is - the energies read neither, and attaching what the
+        call attached keeps its cached graph.)"""
+        model = model if model is not None else (self._model() if getattr(self, "_model", None) is not None else None)
+        if model is None:
+            raise ValueError(f"{what} on a device needs model= (the DiffusionQM9 that owns the library handle) unless these "
+                             "restraints have already run in one of its sampling calls")
+        from . import _lib
+        from .dynamics import _stream
+        dev = x.device
+        h, stream = model._lib_handle(), _stream(dev)
+        topo = model.dynamics.topology(node_mask.to(dev), None, int(node_mask.shape[0]), int(node_mask.shape[1]))
+        xs = x.detach().to(torch.float32).contiguous()
+        scale, nv0 = (torch.ones(1), 1.0) if _attach is None else _attach
+        self.attach(topo, scale, nv0, dev, stream)
+        try:
+            return call(lambda name, *args: _lib.check(getattr(_lib.load(), name)(h, topo.ptr, xs.data_ptr(), *args, stream), name))
+        finally:
+            self.detach(topo)
+
     def template_energy(self, x: torch.Tensor, node_mask: torch.Tensor, model=None, _attach=None):
         """(U [B, NT], fit [B, NT, 16]) float64 of positions x [B, N, 3] in data units under node_mask [B, N, 1]: U_tpl per template and
         its fit (R row-major [9], c_x [3], c_y [3], rmsd) - `template_frame` applies one.  On a device the HIP kernel evaluates it
         (k_restraint_template_energy; `model` as in `energy`); on the CPU the same formulas in torch float64.  Needs templates."""
-        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
-        if tuple(x.shape) != (B, N, 3):
-            raise ValueError(f"x must be [{B}, {N}, 3], got {tuple(x.shape)}")
+        B, _ = self._batch_shape(x, node_mask)
         if not self.n_templates:
             raise ValueError("template_energy: these restraints hold no templates")
         self.check_batch(B, "template_energy")
         if x.device.type != "cuda":
             return template_energy_terms(self, x.detach().double(), node_mask, return_fit=True)
-        model = model if model is not None else (self._model() if getattr(self, "_model", None) is not None else None)
-        if model is None:
-            raise ValueError("template_energy on a device needs model= (the DiffusionQM9 that owns the library handle) unless these "
-                             "restraints have already run in one of its sampling calls")
-        from . import _lib
-        from .dynamics import _stream
-        dev = x.device
-        h = model._lib_handle()
-        topo = model.dynamics.topology(node_mask.to(dev), None, B, N)
-        NT = self.n_templates
-        out = torch.empty((B, NT), device=dev, dtype=torch.float64)
-        fit = torch.empty((B, NT, 16), device=dev, dtype=torch.float64)
-        xs = x.detach().to(torch.float32).contiguous()
-        scale, nv0 = (torch.ones(1), 1.0) if _attach is None else _attach
-        self.attach(topo, scale, nv0, dev, _stream(dev))
-        try:
-            _lib.check(_lib.load().hd_restraint_template_energy(h, topo.ptr, xs.data_ptr(), out.data_ptr(), fit.data_ptr(), _stream(dev)),
-                       "hd_restraint_template_energy")
-        finally:
-            self.detach(topo)
-        return out, fit
+
+        def call(run):
+            out = torch.empty((B, self.n_templates), device=x.device, dtype=torch.float64)
+            fit = torch.empty((B, self.n_templates, 16), device=x.device, dtype=torch.float64)
+            run("hd_restraint_template_energy", out.data_ptr(), fit.data_ptr())
+            return out, fit
+
+        return self._on_device(x, node_mask, model, _attach, "template_energy", call)
 
     def template_results(self, x: torch.Tensor, node_mask: torch.Tensor, model=None, _attach=None) -> dict:
         """The result entries of a templated call for its returned x: 'restraint_template_energy' [B, NT], 'template_rmsd' [B, NT] and
@@ -580,47 +608,25 @@ class Restraints:
         """[B] float64 U_fld of positions x [B, N, 3] in data units under node_mask [B, N, 1] (0 without fields).  On a device the HIP
         kernel evaluates it (k_restraint_field_energy; `model` as in `energy`); on the CPU the same formulas in torch float64.
         fixed_mask and x_known (together): in the frame of `x_known`, as `energy`."""
-        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
-        if tuple(x.shape) != (B, N, 3):
-            raise ValueError(f"x must be [{B}, {N}, 3], got {tuple(x.shape)}")
-        if (fixed_mask is None) != (x_known is None):
-            raise ValueError("field_energy: fixed_mask and x_known go together")
-        framed = fixed_mask is not None
-        if framed and (fixed_mask.numel() != B * N or tuple(x_known.shape) != (B, N, 3)):
-            raise ValueError(f"field_energy: fixed_mask must hold {B} x {N} entries and x_known be [{B}, {N}, 3]")
+        B, N = self._batch_shape(x, node_mask)
+        on_cpu = x.device.type != "cuda"
+        framed = self._framed_args(fixed_mask, x_known, B, N, None if on_cpu else x.device, "field_energy")
         self.check_batch(B, "field_energy")
-        if x.device.type != "cuda":
+        if on_cpu:
             xd = x.detach().double()
             if framed:
-                xd = xd - frame_shift(x, node_mask, fixed_mask, x_known)[:, None, :]
+                xd = xd - frame_shift(x, node_mask, *framed)[:, None, :]
             return field_energy_terms(self, xd, node_mask)
-        model = model if model is not None else (self._model() if getattr(self, "_model", None) is not None else None)
-        if model is None:
-            raise ValueError("field_energy on a device needs model= (the DiffusionQM9 that owns the library handle) unless these "
-                             "restraints have already run in one of its sampling calls")
-        from . import _lib
-        from .dynamics import _stream
-        dev = x.device
-        nm = node_mask.to(dev)
-        h = model._lib_handle()
-        topo = model.dynamics.topology(nm, None, B, N)
-        out = torch.empty((B,), device=dev, dtype=torch.float64)
-        xs = x.detach().to(torch.float32).contiguous()
-        scale, nv0 = (torch.ones(1), 1.0) if _attach is None else _attach
-        self.attach(topo, scale, nv0, dev, _stream(dev))
-        try:
+
+        def call(run):
+            out = torch.empty((B,), device=x.device, dtype=torch.float64)
             if framed:
-                fm = (fixed_mask.to(dev).reshape(B * N) != 0).to(torch.uint8).contiguous()
-                xk = x_known.detach().to(dev, torch.float32).contiguous()
-                _lib.check(_lib.load().hd_restraint_field_energy_framed(h, topo.ptr, xs.data_ptr(), fm.data_ptr(), xk.data_ptr(),
-                                                                        out.data_ptr(), None, _stream(dev)),
-                           "hd_restraint_field_energy_framed")
+                run("hd_restraint_field_energy_framed", framed[0].data_ptr(), framed[1].data_ptr(), out.data_ptr(), None)
             else:
-                _lib.check(_lib.load().hd_restraint_field_energy(h, topo.ptr, xs.data_ptr(), out.data_ptr(), _stream(dev)),
-                           "hd_restraint_field_energy")
-        finally:
-            self.detach(topo)
-        return out
+                run("hd_restraint_field_energy", out.data_ptr())
+            return out
+
+        return self._on_device(x, node_mask, model, _attach, "field_energy", call)
 
     @staticmethod
     def detach(topo) -> None:
@@ -634,52 +640,45 @@ class Restraints:
         same formulas in torch float64.  fixed_mask [B, N, 1] and x_known [B, N, 3] (together): the tables are in the frame of
         `x_known` - the energy of x - tau, tau = mean_F(x) - mean_F(x_known) over the valid fixed nodes (k_restraint_energy<true>);
         `return_shift`: (U, tau [B, 3] float64)."""
-        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
-        if tuple(x.shape) != (B, N, 3):
-            raise ValueError(f"x must be [{B}, {N}, 3], got {tuple(x.shape)}")
-        if (fixed_mask is None) != (x_known is None):
-            raise ValueError("energy: fixed_mask and x_known go together")
-        framed = fixed_mask is not None
+        B, N = self._batch_shape(x, node_mask)
+        on_cpu = x.device.type != "cuda"
+        framed = self._framed_args(fixed_mask, x_known, B, N, None if on_cpu else x.device, "energy")
         if return_shift and not framed:
             raise ValueError("energy: return_shift needs fixed_mask and x_known")
-        if framed and (fixed_mask.numel() != B * N or tuple(x_known.shape) != (B, N, 3)):
-            raise ValueError(f"energy: fixed_mask must hold {B} x {N} entries and x_known be [{B}, {N}, 3]")
         self.check_batch(B, "energy")
-        if x.device.type != "cuda":
+        if on_cpu:
             if not framed:
                 return energy_terms(self, x.detach().double(), node_mask)
-            tau = frame_shift(x, node_mask, fixed_mask, x_known)
+            tau = frame_shift(x, node_mask, *framed)
             U = energy_terms(self, x.detach().double() - tau[:, None, :], node_mask)
             return (U, tau) if return_shift else U
-        model = model if model is not None else (self._model() if getattr(self, "_model", None) is not None else None)
-        if model is None:
-            raise ValueError("energy on a device needs model= (the DiffusionQM9 that owns the library handle) unless these "
-                             "restraints have already run in one of its sampling calls")
-        from . import _lib
-        from .dynamics import _stream
-        dev = x.device
-        nm = node_mask.to(dev)
-        h = model._lib_handle()
-        topo = model.dynamics.topology(nm, None, B, N)
-        out = torch.empty((B, 3), device=dev, dtype=torch.float64)
-        xs = x.detach().to(torch.float32).contiguous()
-        # (`_attach`: the scales and nv0 of the sampling call whose result this is - the energy reads neither, and attaching what
-        # the call attached keeps its cached graph)
-        scale, nv0 = (torch.ones(1), 1.0) if _attach is None else _attach
-        self.attach(topo, scale, nv0, dev, _stream(dev))
-        try:
-            if framed:
-                tau = torch.empty((B, 3), device=dev, dtype=torch.float64)
-                fm = (fixed_mask.to(dev).reshape(B * N) != 0).to(torch.uint8).contiguous()
-                xk = x_known.detach().to(dev, torch.float32).contiguous()
-                _lib.check(_lib.load().hd_restraint_energy_framed(h, topo.ptr, xs.data_ptr(), fm.data_ptr(), xk.data_ptr(),
-                                                                  out.data_ptr(), tau.data_ptr(), _stream(dev)),
-                           "hd_restraint_energy_framed")
-            else:
-                _lib.check(_lib.load().hd_restraint_energy(h, topo.ptr, xs.data_ptr(), out.data_ptr(), _stream(dev)), "hd_restraint_energy")
-        finally:
-            self.detach(topo)
-        return (out, tau) if return_shift else out
+
+        def call(run):
+            out = torch.empty((B, 3), device=x.device, dtype=torch.float64)
+            if not framed:
+                run("hd_restraint_energy", out.data_ptr())
+                return out
+            tau = torch.empty_like(out)
+            run("hd_restraint_energy_framed", framed[0].data_ptr(), framed[1].data_ptr(), out.data_ptr(), tau.data_ptr())
+            return (out, tau) if return_shift else out
+
+        return self._on_device(x, node_mask, model, _attach, "energy", call)
+
+    def result_entries(self, x: torch.Tensor, node_mask: torch.Tensor, model, attach, fixed_mask=None, x_known=None) -> dict:
+        """The restraint entries of a sampling call's results for its returned x, batch tensors on x's device: 'restraint_energy'
+        [B, 3]; with fields 'restraint_field_energy' [B]; with templates the entries of `template_results`; for a call in the frame
+        of `x_known` (fixed_mask, x_known) also 'frame_shift' [B, 3].  `attach`: the (scales, nv0) the call attached."""
+        kw = dict(model=model, _attach=attach)
+        framed = dict(fixed_mask=fixed_mask, x_known=x_known)
+        if fixed_mask is None:
+            out = {'restraint_energy': self.energy(x, node_mask, **kw)}
+        else:
+            out = dict(zip(('restraint_energy', 'frame_shift'), self.energy(x, node_mask, return_shift=True, **kw, **framed)))
+        if self.n_fields:
+            out['restraint_field_energy'] = self.field_energy(x, node_mask, **kw, **framed)
+        if self.n_templates:
+            out.update(self.template_results(x, node_mask, **kw))
+        return out
 
 
 def energy_terms(rs: Restraints, x: torch.Tensor, node_mask: torch.Tensor) -> torch.Tensor:
@@ -807,11 +806,11 @@ def template_frame(x: torch.Tensor, fit: torch.Tensor) -> torch.Tensor:
     return (x.to(fit.device, torch.float64) - fit[..., None, 9:12]) @ R + fit[..., None, 12:15]
 
 
-def template_into(res: dict, tpl: dict, i: int, n: int) -> None:
-    """Molecule i (n nodes) of `Restraints.template_results` into the result dict of that molecule, on the CPU."""
-    res['restraint_template_energy'] = tpl['restraint_template_energy'][i].cpu().clone()
-    res['template_rmsd'] = tpl['template_rmsd'][i].cpu().clone()
-    res['x_template_frame'] = tpl['x_template_frame'][i, :n].cpu().clone()
+def entries_into(res: dict, entries: dict, i: int, n: int) -> None:
+    """Molecule i (n nodes) of `Restraints.result_entries`, moved to the CPU (and a site's own per-node entries), into the result dict
+    of that molecule."""
+    for k, v in entries.items():
+        res[k] = (v[i, :n] if k in ('x_template_frame', 'x_known_frame') else v[i]).clone()
 
 
 def _norm(v):
