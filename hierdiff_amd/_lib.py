@@ -87,6 +87,10 @@ SIGNATURES = {
     "hd_restraint_field_energy_framed": (C.c_int, [_VP, _VP, _FP, _U8P, _FP, _VP, _VP, _VP]),
     "hd_restraint_templates": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), _VP]),
     "hd_restraint_template_energy": (C.c_int, [_VP, _VP, _FP, _VP, _VP, _VP]),
+    "hd_restraint_features": (C.c_int, [_VP, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int,
+                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _VP]),
+    "hd_restrain_feat": (C.c_int, [_VP, _VP, _FP, _FP, C.POINTER(C.c_float), _FP, _VP]),
+    "hd_restraint_feature_energy": (C.c_int, [_VP, _VP, _FP, _VP, _VP, _VP]),
     "hd_set_steer": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_float)]),
     "hd_steer_attach": (C.c_int, [_VP, C.c_int, C.c_double, C.c_int, _VP]),
     "hd_steer_detach": (C.c_int, [_VP]),

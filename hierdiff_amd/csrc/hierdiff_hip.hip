@@ -167,8 +167,10 @@ struct RestraintKey {
     int frame;                                 // 1: the restraints act in the known fragments' frame (hd_restraint_frame)
     unsigned long long fld_gen;                // fields attached: their buffers, NF, rows (0: none)
     unsigned long long tpl_gen;                // templates attached: their buffers, NT, M, rows (0: none)
+    unsigned long long feat_gen;               // features attached: their buffers, W, S, rows, nv1, nb1, ratio (0: none)
     bool operator==(const RestraintKey& o) const {
-        return gen == o.gen && rows_gen == o.rows_gen && frame == o.frame && fld_gen == o.fld_gen && tpl_gen == o.tpl_gen;
+        return gen == o.gen && rows_gen == o.rows_gen && frame == o.frame && fld_gen == o.fld_gen && tpl_gen == o.tpl_gen &&
+               feat_gen == o.feat_gen;
     }
 };
 
@@ -263,12 +265,19 @@ struct RestraintState {
     float* tpl_geom;
     int NT, tpl_NT, tpl_M, tpl_rows;
     unsigned long long tpl_gen;
+    // hd_restraint_features: the band tables lo / hi / k [rows][W][F] and the sum rows coef [rows][S][F], f [rows][S][4]
+    DevTable<float> ft_lo, ft_hi, ft_k, ft_coef, ft_sum;
+    bool feat;                                 // attached NOW (false after hd_restraint_attach)
+    int ft_band_rows, ft_W, ft_sum_rows, ft_S;
+    float ft_nv1, ft_nb1, ft_ratio;
+    unsigned long long feat_gen;
 };
 
 static void restraint_free(RestraintState& r) {
     for (void* p : {(void*)r.obs.p, (void*)r.pair_idx.p, (void*)r.pair_f.p, (void*)r.anc_idx.p, (void*)r.anc_f.p, (void*)r.scale.p,
                     (void*)r.step, (void*)r.fld_v.p, (void*)r.fld_w.p, (void*)r.fld_off, (void*)r.fld_dims, (void*)r.fld_geom,
-                    (void*)r.tpl_idx.p, (void*)r.tpl_f.p, (void*)r.tpl_geom})
+                    (void*)r.tpl_idx.p, (void*)r.tpl_f.p, (void*)r.tpl_geom, (void*)r.ft_lo.p, (void*)r.ft_hi.p, (void*)r.ft_k.p,
+                    (void*)r.ft_coef.p, (void*)r.ft_sum.p})
         if (p) (void)hipFree(p);
     r = RestraintState{};
 }
@@ -317,7 +326,7 @@ struct hd_topology {
     int chain_frames, chain_what;              // what 0: the state behind the transition, 1: its data prediction
     float chain_nv0, chain_nv1, chain_nb1;
     GraphSlot<ChainKey> g_chain;
-    // hd_restraint_attach / _fields / _templates / _frame: everything restraints keep on a topology
+    // hd_restraint_attach / _fields / _templates / _features / _frame: everything restraints keep on a topology
     RestraintState rs;
     // hd_steer_attach: the steering state of the chain that runs on this topology (log-weights, last energies, lineage roots, the
     // ancestors of the latest transition, per-group statistics) and the scratch of k_steer_gather - one allocation each, made by the

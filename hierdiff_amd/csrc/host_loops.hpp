@@ -518,6 +518,9 @@ extern "C" int hd_set_restraint(hd_handle* h, int K, const float* rows4) {
     return set_row_table(h, h->rs_rows, K, rows4, 4);
 }
 
+// A refusal of the entry point `who`; its text is built here, so a call that passes allocates nothing.
+static int refuse(int code, const char* who, const std::string& msg) { return fail(code, who + msg); }
+
 // grown when `count` exceeds the capacity (then *moved is set), filled from `src` (device or host memory)
 template <typename T>
 int DevTable<T>::fill(const T* src, size_t count, bool* moved, hipStream_t s) {
@@ -574,6 +577,7 @@ extern "C" int hd_restraint_attach(hd_topology* topo, const float* obs, int obs_
     r.frame = 0;                                        // the model's frame, until hd_restraint_frame says otherwise
     r.NF = 0;                                           // no fields, until hd_restraint_fields says otherwise
     r.NT = 0;                                           // no templates, until hd_restraint_templates says otherwise
+    r.feat = false;                                     // no features, until hd_restraint_features says otherwise
     r.on = true;
     return HD_OK;
 }
@@ -664,6 +668,59 @@ extern "C" int hd_restraint_templates(hd_topology* topo, int NT, int rows, int M
     return HD_OK;
 }
 
+extern "C" int hd_restraint_features(hd_topology* topo, const float* lo, const float* hi, const float* k, int band_rows, int W,
+                                     const float* coef, const float* sum_f, int sum_rows, int S, float nv1, float nb1, float ratio,
+                                     void* stream) {
+    const char* who = "hd_restraint_features";
+    if (!topo) return refuse(HD_E_INVALID, who, ": null topology");
+    if (W < 0 || W > topo->N) return refuse(HD_E_INVALID, who, ": W must be 0 .. N (nodes i >= W have no band)");
+    if (S < 0 || S > HD_MAX_FEATURE_SUMS) return refuse(HD_E_INVALID, who, ": S must be 0 .. 8");
+    if (!topo->rs.on) return refuse(HD_E_STATE, who, ": no restraints attached to the topology (hd_restraint_attach)");
+    if (W == 0 && S == 0) { topo->rs.feat = false; return HD_OK; }
+    const int F = topo->h->D - 3;
+    if (F < 1) return refuse(HD_E_INVALID, who, ": the model has no feature columns");
+    if ((W > 0 && (!lo || !hi || !k)) || (S > 0 && (!coef || !sum_f))) return refuse(HD_E_INVALID, who, ": null table");
+    if ((W > 0 && band_rows != 1 && band_rows != topo->B) || (S > 0 && sum_rows != 1 && sum_rows != topo->B))
+        return refuse(HD_E_INVALID, who, ": every table has 1 row (shared) or B rows");
+    for (float v : {nv1, nb1, ratio})
+        if (!(v - v == 0.f)) return refuse(HD_E_INVALID, who, ": nv1, nb1 and ratio must be finite");
+    if (W == 0) band_rows = 1;
+    if (S == 0) sum_rows = 1;
+    const size_t nb = (size_t)band_rows * W * F, nc = (size_t)sum_rows * S * F, ns = (size_t)sum_rows * S;
+    for (size_t e = 0; e < nb; ++e) {
+        if (!(k[e] - k[e] == 0.f)) return refuse(HD_E_INVALID, who, ": every k must be finite");
+        if (lo[e] != lo[e] || hi[e] != hi[e]) return refuse(HD_E_INVALID, who, ": a bound may be infinite, not NaN");
+        if (lo[e] > hi[e]) return refuse(HD_E_INVALID, who, ": lo > hi");
+    }
+    for (size_t e = 0; e < nc; ++e)
+        if (!(coef[e] - coef[e] == 0.f)) return refuse(HD_E_INVALID, who, ": every coefficient must be finite");
+    for (size_t e = 0; e < ns; ++e) {
+        const float* r = sum_f + 4 * e;
+        if (!(r[2] - r[2] == 0.f)) return refuse(HD_E_INVALID, who, ": every k must be finite");
+        if (r[0] != r[0] || r[1] != r[1]) return refuse(HD_E_INVALID, who, ": a bound may be infinite, not NaN");
+        if (r[0] > r[1]) return refuse(HD_E_INVALID, who, ": lo > hi");
+        if (r[3] != 0.f && r[3] != 1.f) return refuse(HD_E_INVALID, who, ": reduce is 0 (sum) or 1 (mean)");
+    }
+    if ((size_t)topo->N * topo->h->D * sizeof(float) > 64 * 1024) return refuse(HD_E_INVALID, who, ": N * D floats exceed one workgroup's LDS");
+    HIP_TRY(hipSetDevice(topo->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    RestraintState& r = topo->rs;
+    r.feat = false;
+    bool moved = false;
+    // (host arrays: pageable sources are staged before the call returns)
+    HD_TRY(r.ft_lo.fill(lo, nb, &moved, s));
+    HD_TRY(r.ft_hi.fill(hi, nb, &moved, s));
+    HD_TRY(r.ft_k.fill(k, nb, &moved, s));
+    HD_TRY(r.ft_coef.fill(coef, nc, &moved, s));
+    HD_TRY(r.ft_sum.fill(sum_f, ns * 4, &moved, s));
+    restraint_bake({{&r.ft_band_rows, band_rows}, {&r.ft_W, W}, {&r.ft_sum_rows, sum_rows}, {&r.ft_S, S}},
+                   moved || nv1 != r.ft_nv1 || nb1 != r.ft_nb1 || ratio != r.ft_ratio, &r.feat_gen);
+    r.ft_nv1 = nv1; r.ft_nb1 = nb1; r.ft_ratio = ratio;
+    r.feat = true;
+    return HD_OK;
+}
+
 extern "C" int hd_restraint_frame(hd_topology* topo, int frame) {
     if (!topo) return fail(HD_E_INVALID, "hd_restraint_frame: null topology");
     if (frame != 0 && frame != 1) return fail(HD_E_INVALID, "hd_restraint_frame: frame is 0 (the model's) or 1 (the known fragments')");
@@ -696,6 +753,15 @@ static TemplateTables template_tables(const hd_topology* t) {
     return r;
 }
 
+static FeatureTables feature_tables(const hd_topology* t) {
+    const RestraintState& s = t->rs;
+    FeatureTables r;
+    r.lo = s.ft_lo.p; r.hi = s.ft_hi.p; r.k = s.ft_k.p; r.coef = s.ft_coef.p; r.sum_f = s.ft_sum.p;
+    r.band_rows = s.ft_band_rows; r.W = s.feat ? s.ft_W : 0; r.sum_rows = s.ft_sum_rows; r.S = s.feat ? s.ft_S : 0;
+    r.nv1 = s.ft_nv1; r.nb1 = s.ft_nb1;
+    return r;
+}
+
 // The restraint part of a path graph's key: all 0 unless the transition is `restrained`; the fields' / templates' generations
 // only while some are attached.
 static RestraintKey restraint_key(const hd_handle* h, const hd_topology* topo, bool restrained, bool framed) {
@@ -705,6 +771,7 @@ static RestraintKey restraint_key(const hd_handle* h, const hd_topology* topo, b
     k.gen = s.gen; k.rows_gen = h->rs_rows.gen; k.frame = framed ? 1 : 0;
     k.fld_gen = s.NF ? s.fld_gen : 0;
     k.tpl_gen = s.NT ? s.tpl_gen : 0;
+    k.feat_gen = s.feat ? s.feat_gen : 0;
     return k;
 }
 
@@ -731,8 +798,22 @@ static int restrain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const
     return HD_OK;
 }
 
-// A refusal of the entry point `who`; its text is built here, so a call that passes allocates nothing.
-static int refuse(int code, const char* who, const std::string& msg) { return fail(code, who + msg); }
+
+// The feature update of one transition on eps (in place when out == eps), behind restrain_launch: k_restrain_feat on the attached
+// features, the row read as there.
+static int restrain_feat_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* z, const float* eps, float* out,
+                                const float* rows, const float* row4) {
+    ProfScope ps(h, io.s, 2);
+    RestrainFeatArgs a;
+    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.t = feature_tables(t); a.scale = t->rs.scale.p;
+    a.rows = rows;
+    for (int i = 0; i < 4; ++i) a.row[i] = row4 ? row4[i] : 0.f;
+    a.step_ptr = io.step; a.k = io.row; a.ratio = t->rs.ft_ratio; a.scale_rows = t->rs.scale_rows;
+    a.B = t->B; a.N = t->N; a.D = h->D;
+    hipLaunchKernelGGL(k_restrain_feat, dim3(t->B), dim3(256), (size_t)t->N * (h->D - 3) * sizeof(float), io.s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
 
 // What every entry point that reads the attached restraints refuses first.  `given`: its tensors are there; `templates`: it needs some.
 static int restraint_refusals(const char* who, const hd_handle* h, const hd_topology* topo, bool given, const char* what,
@@ -772,6 +853,37 @@ static int restrain_eps(const char* who, hd_handle* h, hd_topology* topo, const 
 extern "C" int hd_restrain_eps(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4, float* out,
                                void* stream) {
     return restrain_eps("hd_restrain_eps", h, topo, z, eps, row4, nullptr, nullptr, out, stream, false);
+}
+
+extern "C" int hd_restrain_feat(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4, float* out,
+                                void* stream) {
+    const char* who = "hd_restrain_feat";
+    HD_TRY(restraint_refusals(who, h, topo, z && eps && row4 && out, "tensor / row"));
+    if (!topo->rs.feat) return refuse(HD_E_STATE, who, ": no features attached to the topology (hd_restraint_features)");
+    if (!restraint_row_ok(row4)) return refuse(HD_E_INVALID, who, ": need alpha_t > 0, sigma_t >= 0, a finite lambda and clip > 0 (inf: no clip)");
+    const size_t per = (size_t)topo->B * topo->N * h->D;
+    if (out < z + per && z < out + per) return refuse(HD_E_INVALID, who, ": out may not overlap z");
+    if (out != eps && out < eps + per && eps < out + per) return refuse(HD_E_INVALID, who, ": out may be eps itself, not a shifted overlap of it");
+    HIP_TRY(hipSetDevice(h->device));
+    LoopIO io{};
+    io.s = (hipStream_t)stream;
+    topo_use(topo, io.s);
+    return restrain_feat_launch(h, topo, io, z, eps, out, nullptr, row4);
+}
+
+extern "C" int hd_restraint_feature_energy(hd_handle* h, hd_topology* topo, const float* hf, double* out2, double* sums, void* stream) {
+    const char* who = "hd_restraint_feature_energy";
+    HD_TRY(restraint_refusals(who, h, topo, hf && out2, "tensor"));
+    if (!topo->rs.feat) return refuse(HD_E_STATE, who, ": no features attached to the topology (hd_restraint_features)");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    ProfScope ps(h, s, 2);
+    FeatureEnergyArgs a{};
+    a.h = hf; a.nm = topo->nm_bytes; a.t = feature_tables(topo); a.out = out2; a.sums = sums; a.B = topo->B; a.N = topo->N; a.F = h->D - 3;
+    hipLaunchKernelGGL(k_restraint_feature_energy, dim3(topo->B), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
 }
 
 extern "C" int hd_restrain_eps_framed(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4,
@@ -884,8 +996,13 @@ static int steer_launch(hd_handle* h, hd_topology* t, const LoopIO& io, float* z
     for (int i = 0; i < 3; ++i) w.row[i] = row3 ? row3[i] : 0.f;
     w.step_ptr = io.step; w.k = io.row; w.nv0 = t->rs.nv0; w.logw = st.logw; w.uprev = st.uprev; w.B = t->B; w.N = t->N; w.D = h->D;
     w.tp = template_tables(t);
-    if (t->rs.NT) hipLaunchKernelGGL(k_steer_weigh<true>, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, w);
-    else hipLaunchKernelGGL(k_steer_weigh<false>, dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, w);
+    w.ft = feature_tables(t);
+    if (t->rs.feat) {                                   // features attached: the instantiations with U_feat, and v behind x^0 in LDS
+        const size_t lds = (size_t)t->N * h->D * sizeof(float);
+        if (t->rs.NT) hipLaunchKernelGGL((k_steer_weigh<true, true>), dim3(t->B), dim3(256), lds, io.s, w);
+        else hipLaunchKernelGGL((k_steer_weigh<false, true>), dim3(t->B), dim3(256), lds, io.s, w);
+    } else if (t->rs.NT) hipLaunchKernelGGL((k_steer_weigh<true, false>), dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, w);
+    else hipLaunchKernelGGL((k_steer_weigh<false, false>), dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, w);
     SteerResampleArgs r;
     r.st = st; r.ess = t->st_ess; r.seed = seed; r.base = io.base; r.draw = d.value; r.draw_ptr = d.word; r.base_ptr = io.base_w;
     r.P = t->st_P;
@@ -1052,6 +1169,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
                 HD_TRY(guide_launch(h, topo, topo->eps, topo->eps_u, io.w, gd->w_rows, gd->phi, topo->eps, io.s));
             }
             if (rsn) HD_TRY(restrain_launch(h, topo, io, io.z, topo->eps, topo->eps, h->rs_rows.d, nullptr, framed));
+            if (rsn && topo->rs.feat) HD_TRY(restrain_feat_launch(h, topo, io, io.z, topo->eps, topo->eps, h->rs_rows.d, nullptr));
             if (stn) HD_TRY(steer_launch(h, topo, io, io.z, topo->eps, h->st_rows.d, nullptr, io.draw_of(0, stride), c.seed,
                                          form == 3 ? topo->ms_hist : nullptr));
             if (rec && j == rounds - 1 && topo->chain_what == 1) HD_TRY(chain_launch(h, topo, io, topo->eps));

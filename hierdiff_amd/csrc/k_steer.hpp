@@ -19,6 +19,7 @@
 #pragma once
 #include "common.hpp"
 #include "k_restrain.hpp"
+#include "k_restrain_feat.hpp"
 
 #define ST_MAX_P 256
 #define ST_UNIFORM_INDEX 0xfffffffeu
@@ -49,14 +50,16 @@ struct SteerWeighArgs {
     double *logw, *uprev;   // [B]
     int B, N, D;
     TemplateTables tp;      // TPL only, behind everything k_steer_weigh<false> reads
+    FeatureTables ft;       // FEAT only, behind everything the other instantiations read
 };
 
-// Dynamic LDS: N * 3 floats (x^0 of the molecule).
+// Dynamic LDS: N * 3 floats (x^0 of the molecule); FEAT: N * D floats (then its features v [N][F], k_restrain_feat.hpp).
 // TPL: templates are attached; U gains U_tpl (rs_template_fit, rs_template_block) behind U_fld.
-template <bool TPL>
+// FEAT: features are attached; U gains U_feat = U_band + U_sum (ft_energy_block) behind U_tpl.
+template <bool TPL, bool FEAT = false>
 __global__ __launch_bounds__(256) void k_steer_weigh(SteerWeighArgs a) {
     extern __shared__ float st_x[];
-    __shared__ double red[4 * (TPL ? 9 : 3)];
+    __shared__ double red[4 * (FEAT ? FT_RED : TPL ? 9 : 3)];
     const int tid = threadIdx.x, b = blockIdx.x;
     const int N = a.N, D = a.D;
     const size_t base = (size_t)b * N * D;
@@ -72,6 +75,7 @@ __global__ __launch_bounds__(256) void k_steer_weigh(SteerWeighArgs a) {
         const size_t o = (size_t)i * D + c;
         st_x[e] = __fmul_rn(__fmul_rn(ra, __fsub_rn(z[o], __fmul_rn(sg, eps[o]))), a.nv0);
     }
+    if constexpr (FEAT) ft_data_prediction(z, eps, al, sg, a.ft.nv1, a.ft.nb1, N, D, st_x + 3 * N, tid);
     __syncthreads();
     double U[4];
     rs_energy_block(a.t, b, st_x, nm, N, red, tid, U);
@@ -81,10 +85,18 @@ __global__ __launch_bounds__(256) void k_steer_weigh(SteerWeighArgs a) {
         rs_template_fit(a.tp, b, st_x, nm, N, red, tp_fit, tid);
         utpl = rs_template_block(a.tp, b, st_x, nm, N, red, tp_fit, tid);
     }
+    double ufeat = 0.0;
+    if constexpr (FEAT) {
+        __shared__ double ft_rowv[FT_ROW];
+        double Uf[2];
+        ft_energy_block(a.ft, b, st_x + 3 * N, nm, N, D - 3, red, ft_rowv, tid, Uf);
+        ufeat = Uf[0] + Uf[1];
+    }
     if (tid == 0) {
         const double u3 = (U[0] + U[1]) + U[2];
         const double u4 = a.t.NF ? u3 + U[3] : u3;      // no fields: the old sum's bits
-        const double u = TPL ? u4 + utpl : u4;
+        const double u5 = TPL ? u4 + utpl : u4;
+        const double u = FEAT ? u5 + ufeat : u5;
         const double dl = -(double)beta * (u - a.uprev[b]);
         // (finite: |v| < inf, false for a NaN.  Not v - v == 0: with v a product the compiler contracts that into the product's rounding error)
         a.logw[b] = (fabs(u) < HUGE_VAL && fabs(dl) < HUGE_VAL) ? a.logw[b] + dl : -HUGE_VAL;

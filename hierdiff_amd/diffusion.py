@@ -714,7 +714,9 @@ class DiffusionQM9(_Base):
         rr.rs.check_batch(B)
         import weakref
         rr.rs._model = weakref.ref(self)
-        rr.rs.attach(topo, rr.scale, float(self.norm_values[0]), dev, _stream(dev), rr.frame)
+        nv0, nv1 = float(self.norm_values[0]), float(self.norm_values[1])
+        rr.rs.attach(topo, rr.scale, nv0, dev, _stream(dev), rr.frame,
+                     feat=(nv1, float(self.norm_biases[1] or 0.0), restraints.feature_ratio(rr.schedule, nv0, nv1)))
 
     def _steer_open(self, handle, topo, tabs, st, reset: bool, dev):
         """Attach the steering of a resolved call (`steering.Steer`) to `topo` behind the rows of the path that `_path_tables` has
@@ -764,10 +766,10 @@ class DiffusionQM9(_Base):
             res['chain_t'] = chain_t.clone()
         return results
 
-    def _restraint_entries(self, rs, scale, x, node_mask, fixed_mask=None, x_known=None, cpu: bool = True) -> dict:
-        """`Restraints.result_entries` of a restrained call's returned x, attached as the call attached them (its scales, the model's
-        nv0); `cpu`: moved to the CPU."""
-        ent = rs.result_entries(x, node_mask, self, (torch.as_tensor(scale), float(self.norm_values[0])), fixed_mask, x_known)
+    def _restraint_entries(self, rs, scale, x, node_mask, fixed_mask=None, x_known=None, cpu: bool = True, h=None) -> dict:
+        """`Restraints.result_entries` of a restrained call's returned x (and h: the feature entries), attached as the call attached
+        them (its scales, the model's nv0); `cpu`: moved to the CPU."""
+        ent = rs.result_entries(x, node_mask, self, (torch.as_tensor(scale), float(self.norm_values[0])), fixed_mask, x_known, h=h)
         return {k: v.cpu() for k, v in ent.items()} if cpu else ent
 
     def _check_masked(self, x, node_mask, what):
@@ -1607,7 +1609,7 @@ class DiffusionQM9(_Base):
                 rk = dict(restraints=rr_all.rs.slice(lo, lo + nm.shape[0]),
                           restraint_scale=rr_all.scale if rr_all.scale.numel() == 1 else rr_all.scale[lo:lo + nm.shape[0]])
             got = self.sample_from_latent(z, nmd, None, ctxd, t_start=t_start, sample_id_base=base, guidance_scale=gs, **few, **rk)
-            ent = {} if rr_all is None else self._restraint_entries(rk["restraints"], rk["restraint_scale"], got[0], nmd)
+            ent = {} if rr_all is None else self._restraint_entries(rk["restraints"], rk["restraint_scale"], got[0], nmd, h=got[1])
             xv, hv = got[0].cpu(), got[1].cpu()
             part = []
             for i in range(nm.shape[0]):
@@ -1830,7 +1832,7 @@ class DiffusionQM9(_Base):
         rr = pl.restraints
         if rr is None or not rr.frame:
             return got
-        info = self._restraint_entries(rr.rs, rr.scale, got[0], node_mask, st.fm_u8, st.xk, cpu=False)
+        info = self._restraint_entries(rr.rs, rr.scale, got[0], node_mask, st.fm_u8, st.xk, cpu=False, h=got[1])
         tau = info['frame_shift']
         info['x_known_frame'] = ((got[0].double() - tau[:, None, :]) * node_mask.to(st.dev, torch.float64)).to(torch.float32)
         return tuple(got) + (info,)
@@ -2006,7 +2008,7 @@ class DiffusionQM9(_Base):
             self._chain_into(out, got[2], sample_n, pl.chain_t)
         rr = pl.restraints
         if rr is not None:
-            ent = self._restraint_entries(rr.rs, rr.scale, got[0], node_mask)
+            ent = self._restraint_entries(rr.rs, rr.scale, got[0], node_mask, h=got[1])
             for i in range(num_samples):
                 restraints_mod.entries_into(out[i], ent, i, sample_n[i])
         if pl.steer is not None:

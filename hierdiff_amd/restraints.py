@@ -59,6 +59,26 @@ the molecule in the template's coordinates, a pocket's if that is where the temp
 Out of scope: obstacles or fields read in the fitted frame (their gradient would need dR/dx), flat-bottomed templates, scaling fits,
 correspondence search (rows name their nodes), templates on h.
 
+FEATURES.  `Features` restrains the other F columns of a coarse molecule - the property and embedding channels h that the stage-2
+decoder reads - softly, where `fixed_h_mask` can only replace.  With v_ic the data prediction of channel c of the valid node i in data
+units (the value a record="x0" frame shows: v = (1 / alpha_t (z - sigma_t eps^)) nv1 + nb1, nv1 = norm_values[1], nb1 =
+norm_biases[1]), in double:
+
+    bands   lo, hi, k [W, F] (nodes i >= W have none); element (i, c) is active when k_ic > 0 and v_ic is finite
+            U_band = 1/2 sum k_ic (max(0, v - hi)^2 + max(0, lo - v)^2)      lo = -inf / hi = inf: one-sided; lo = hi: a harmonic target
+    sums    at most MAX_FEATURE_SUMS rows `FeatureSum(coef [F], lo, hi, k, reduce)`:  s_r = sum_{i valid} sum_c coef_rc v_ic,
+            m_r = s_r ("sum") or s_r / n ("mean", n the valid nodes),  U_sum = 1/2 sum_r k_r (max(0, m_r - hi_r)^2 + max(0, lo_r - m_r)^2)
+            a row with k_r = 0, or in a molecule without valid nodes, is inactive; a row that reads a non-finite v contributes nothing
+
+U_feat = U_band + U_sum, and eps^[i, 3 + c] += clip_i(s_b lambda_k ratio dU_feat/dv_ic): s_b and lambda_k as for the positions, ratio =
+nv1 / nv0 under the "score" schedule (dv/dz_h = nv1 / alpha_t) and 1 otherwise, the clip on the norm of the node's F steps (apart from
+the position step's clip), no mean removed.  Features have no frame: with restraint_frame="known" the term acts on every valid node and
+the replacement step overwrites the known elements afterwards.  Steering weighs on the total with U_feat - selection is the safe way
+to impose a window on channels that are rounded downstream.  Results carry 'restraint_feature_energy' [2] = (U_band, U_sum) and
+'feature_sums' [S] = m_r of the returned h.  Out of scope: per-feature scale or clip keywords (the per-element k does that), node
+weights inside sums, products or other nonlinear collective variables, the context column, pocket models, restraints that read the
+rounded integer channels.
+
 A pair or anchor row whose node index is -1 (padding), >= the molecule's size or masked is inactive - documented behaviour, not an
 error, because `sample` draws the sizes.  A term at distance exactly 0 contributes no gradient.
 
@@ -77,6 +97,8 @@ FRAMES = ("model", "known")
 MAX_FIELDS = 8                                   # HD_MAX_FIELDS
 MAX_TEMPLATES = 4                                # HD_MAX_TEMPLATES
 FITS = ("rigid", "translation")
+MAX_FEATURE_SUMS = 8                             # HD_MAX_FEATURE_SUMS
+REDUCES = ("sum", "mean")
 
 
 def check_frame(model, frame) -> int:
@@ -345,6 +367,225 @@ def _templates(templates) -> list:
     return list(tl)
 
 
+def _no_none(v, fill: float):
+    """Nested lists with None (JSON's null: no bound) -> the same with `fill`."""
+    if isinstance(v, (list, tuple)):
+        return [_no_none(e, fill) for e in v]
+    return fill if v is None else v
+
+
+def _bound(v, fill: float, name: str) -> torch.Tensor:
+    """A bound (None: `fill`, -inf or inf; inside nested lists too) as a float32 CPU tensor; +-inf are allowed, NaN is not."""
+    if v is None:
+        return torch.tensor(fill, dtype=torch.float32)
+    v = _no_none(v, fill)
+    if isinstance(v, bool):
+        raise ValueError(f"{name} must be a number or an array, got {v!r}")
+    try:
+        t = torch.as_tensor(np.array(v) if isinstance(v, np.ndarray) else v).detach().cpu().to(torch.float64).to(torch.float32)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{name} must be a number or an array of numbers") from None
+    if bool(torch.isnan(t).any()):
+        raise ValueError(f"{name} must not be NaN (None or +-inf: no bound)")
+    return t
+
+
+class FeatureSum:
+    """One molecule-wide sum restraint (module docstring: FEATURES).
+
+    coef    [F] finite coefficients of the feature channels
+    lo, hi  a number (shared) or [B] (per molecule); None: -inf / +inf
+    k       stiffness >= 0, finite (0: the row is inactive, its m_r is still not reported)
+    reduce  "sum" or "mean" (s_r / the molecule's valid nodes)
+    ValueError for every malformed argument, before a device is looked at.  Everything is rounded to fp32 once, here."""
+
+    def __init__(self, coef, lo=None, hi=None, k=1.0, reduce="sum"):
+        if isinstance(coef, bool):
+            raise ValueError(f"FeatureSum: coef must be [F] numbers, got {coef!r}")
+        try:
+            c = torch.as_tensor(coef).detach().cpu().to(torch.float64).to(torch.float32)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError("FeatureSum: coef must be [F] numbers") from None
+        if c.dim() != 1 or c.numel() == 0:
+            raise ValueError(f"FeatureSum: coef must be [F], got {tuple(c.shape)}")
+        if not bool(torch.isfinite(c).all()):
+            raise ValueError("FeatureSum: coef must be finite")
+        self.coef = c.contiguous()
+        lo_, hi_ = _bound(lo, -math.inf, "FeatureSum: lo"), _bound(hi, math.inf, "FeatureSum: hi")
+        if lo_.dim() > 1 or hi_.dim() > 1:
+            raise ValueError("FeatureSum: lo and hi must be a number or [B]")
+        rows = {int(t.numel()) for t in (lo_, hi_) if t.dim() == 1} - {1}
+        if len(rows) > 1:
+            raise ValueError(f"FeatureSum: lo and hi hold rows for {sorted(rows)} molecules; they must agree")
+        r = max(rows | {1})
+        self.lo, self.hi = lo_.reshape(-1).expand(r).contiguous(), hi_.reshape(-1).expand(r).contiguous()
+        if bool((self.lo > self.hi).any()):
+            raise ValueError("FeatureSum: lo > hi")
+        self.k = _number(k, "FeatureSum: k")
+        if not isinstance(reduce, str) or reduce not in REDUCES:
+            raise ValueError(f"FeatureSum: reduce must be one of {REDUCES}, got {reduce!r}")
+        self.reduce = reduce
+
+    @property
+    def rows(self) -> int:
+        return int(self.lo.shape[0])
+
+    @property
+    def F(self) -> int:
+        return int(self.coef.shape[0])
+
+    def _slice(self, lo: int, hi: int) -> "FeatureSum":
+        if self.rows == 1:
+            return self
+        out = object.__new__(FeatureSum)
+        out.__dict__.update(self.__dict__)
+        out.lo, out.hi = self.lo[lo:hi].contiguous(), self.hi[lo:hi].contiguous()
+        return out
+
+
+class Features:
+    """Bands and sums on the features h (module docstring: FEATURES).
+
+    lo, hi  [W, F] (shared) or [B, W, F] (per molecule); None: -inf / +inf (both None: no bands)
+    k       stiffness >= 0, finite: a number or anything that broadcasts to the bands' shape (k_ic = 0: the element is inactive)
+    sums    a `FeatureSum` or a sequence of at most MAX_FEATURE_SUMS of them
+    ValueError for every malformed argument, before a device is looked at.  Everything is rounded to fp32 once, here."""
+
+    def __init__(self, lo=None, hi=None, k=1.0, sums=()):
+        sl = [sums] if isinstance(sums, FeatureSum) else sums
+        if sl is None:
+            sl = []
+        if not isinstance(sl, (list, tuple)) or not all(isinstance(r, FeatureSum) for r in sl):
+            raise ValueError("Features: sums must be a restraints.FeatureSum or a sequence of them")
+        if len(sl) > MAX_FEATURE_SUMS:
+            raise ValueError(f"Features: a call carries at most {MAX_FEATURE_SUMS} sums, got {len(sl)}")
+        self.sums = list(sl)
+        self.lo = self.hi = self.k = None
+        if lo is not None or hi is not None:
+            lo_, hi_ = _bound(lo, -math.inf, "Features: lo"), _bound(hi, math.inf, "Features: hi")
+            shape = lo_.shape if lo is not None else hi_.shape
+            if len(shape) not in (2, 3) or 0 in shape or (lo is not None and hi is not None and lo_.shape != hi_.shape):
+                raise ValueError(f"Features: lo and hi must be [W, F] (shared) or [B, W, F] (per molecule) and agree, got "
+                                 f"{tuple(lo_.shape) if lo is not None else None} and {tuple(hi_.shape) if hi is not None else None}")
+            if isinstance(k, bool):
+                raise ValueError(f"Features: k must be a number or an array, got {k!r}")
+            try:
+                k_ = torch.as_tensor(k).detach().cpu().to(torch.float64).to(torch.float32)
+                k_ = k_.expand(shape)
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError(f"Features: k must be a number or broadcast to the bands' shape {tuple(shape)}") from None
+            if not bool(torch.isfinite(k_).all()) or bool((k_ < 0).any()):
+                raise ValueError("Features: k must be finite and >= 0")
+            lo_, hi_ = lo_.expand(shape), hi_.expand(shape)
+            if bool((lo_ > hi_).any()):
+                raise ValueError("Features: lo > hi")
+            three = (lambda t: (t.unsqueeze(0) if t.dim() == 2 else t).contiguous())
+            self.lo, self.hi, self.k = three(lo_), three(hi_), three(k_)
+        elif not self.sums:
+            raise ValueError("Features: give bands (lo / hi) or sums")
+        fs = {r.F for r in self.sums} | ({int(self.lo.shape[2])} if self.lo is not None else set())
+        if len(fs) > 1:
+            raise ValueError(f"Features: the bands and the sums name {sorted(fs)} feature channels; they must agree")
+        rows = {r.rows for r in self.sums} - {1}
+        if len(rows) > 1:
+            raise ValueError(f"Features: per-molecule sum bounds are given for {sorted(rows)} molecules; they must agree")
+
+    @classmethod
+    def target(cls, values, k=1.0, tol=0.0, sums=()) -> "Features":
+        """Harmonic targets: lo = values - tol, hi = values + tol (tol >= 0: a number or anything that broadcasts)."""
+        v = _bound(values, 0.0, "Features.target: values")
+        if values is None or not bool(torch.isfinite(v).all()):
+            raise ValueError("Features.target: values must be finite [W, F] or [B, W, F]")
+        t = _bound(tol, 0.0, "Features.target: tol")
+        if tol is None or not bool(torch.isfinite(t).all()) or bool((t < 0).any()):
+            raise ValueError("Features.target: tol must be finite and >= 0")
+        try:
+            t = t.expand(v.shape)
+        except RuntimeError:
+            raise ValueError("Features.target: tol must broadcast to the values' shape") from None
+        return cls(v - t, v + t, k, sums)
+
+    @property
+    def F(self) -> int:
+        return int(self.lo.shape[2]) if self.lo is not None else self.sums[0].F
+
+    @property
+    def W(self) -> int:
+        return 0 if self.lo is None else int(self.lo.shape[1])
+
+    @property
+    def S(self) -> int:
+        return len(self.sums)
+
+    def band_rows(self) -> int:
+        return 1 if self.lo is None else int(self.lo.shape[0])
+
+    def sum_rows(self) -> int:
+        return max([r.rows for r in self.sums] + [1])
+
+    def tables(self):
+        """(lo, hi, k [band_rows, W, F], coef [sum_rows, S, F], sum_f [sum_rows, S, 4] = (lo, hi, k, reduce)) float32: the library's."""
+        F, S, sr = self.F, self.S, self.sum_rows()
+        if self.lo is None:
+            lo = hi = k = torch.zeros((1, 0, F), dtype=torch.float32)
+        else:
+            lo, hi, k = self.lo, self.hi, self.k
+        coef = torch.zeros((sr, S, F), dtype=torch.float32)
+        f = torch.zeros((sr, S, 4), dtype=torch.float32)
+        for j, r in enumerate(self.sums):
+            coef[:, j] = r.coef
+            f[:, j, 0], f[:, j, 1], f[:, j, 2], f[:, j, 3] = r.lo, r.hi, r.k, float(REDUCES.index(r.reduce))
+        return lo.contiguous(), hi.contiguous(), k.contiguous(), coef.contiguous(), f.contiguous()
+
+    def _slice(self, lo: int, hi: int) -> "Features":
+        out = object.__new__(Features)
+        out.__dict__.update(self.__dict__)
+        if self.lo is not None and self.lo.shape[0] != 1:
+            out.lo, out.hi, out.k = (t[lo:hi].contiguous() for t in (self.lo, self.hi, self.k))
+        out.sums = [r._slice(lo, hi) for r in self.sums]
+        return out
+
+    @classmethod
+    def from_dict(cls, d, where: str = "features") -> "Features":
+        """{"bands": {"lo", "hi", "k"} | {"target", "tol", "k"}, "sums": [{"coef", "lo", "hi", "k", "reduce"}]} (each part optional)."""
+        if not isinstance(d, dict) or set(d) - {"bands", "sums"}:
+            raise ValueError(f"{where}: features is an object with the keys bands / sums")
+        sums = []
+        if d.get("sums") is not None:
+            if not isinstance(d["sums"], list):
+                raise ValueError(f"{where}: features.sums must be a list of objects")
+            for e in d["sums"]:
+                if not isinstance(e, dict) or set(e) - {"coef", "lo", "hi", "k", "reduce"} or "coef" not in e:
+                    raise ValueError(f"{where}: a sum is an object with the keys coef (and lo, hi, k, reduce)")
+                sums.append(FeatureSum(e["coef"], e.get("lo"), e.get("hi"), e.get("k", 1.0), e.get("reduce", "sum")))
+        b = d.get("bands")
+        if b is None:
+            return cls(sums=sums)
+        if not isinstance(b, dict) or (set(b) - {"lo", "hi", "k"} and set(b) - {"target", "tol", "k"}):
+            raise ValueError(f"{where}: features.bands holds the keys lo, hi, k or target, tol, k")
+        if "target" in b:
+            return cls.target(b["target"], b.get("k", 1.0), b.get("tol", 0.0), sums)
+        return cls(b.get("lo"), b.get("hi"), b.get("k", 1.0), sums)
+
+    def to_dict(self) -> dict:
+        """The JSON form `from_dict` reads (None for an infinite bound)."""
+        fin = lambda t: [fin(r) for r in t] if isinstance(t, list) else (t if math.isfinite(t) else None)
+        out = {}
+        if self.lo is not None:
+            sq = lambda t: (t[0] if t.shape[0] == 1 else t).tolist()
+            out["bands"] = {"lo": fin(sq(self.lo)), "hi": fin(sq(self.hi)), "k": sq(self.k)}
+        if self.sums:
+            one = lambda t: fin(t.tolist()[0] if t.numel() == 1 else t.tolist())
+            out["sums"] = [{"coef": r.coef.tolist(), "lo": one(r.lo), "hi": one(r.hi), "k": r.k, "reduce": r.reduce} for r in self.sums]
+        return out
+
+
+def feature_ratio(schedule, nv0: float, nv1: float) -> float:
+    """lambda^h_k / lambda_k: nv1 / nv0 under the "score" schedule (dv / dz_h = nv1 / alpha_t where dx / dz_x = nv0 / alpha_t), 1 for
+    "sigma" and for explicit weights."""
+    return float(nv1) / float(nv0) if isinstance(schedule, str) and schedule == "score" else 1.0
+
+
 class Restraints:
     """The three tables of one call, validated and kept on the CPU.
 
@@ -353,10 +594,14 @@ class Restraints:
     anchors    [A, 6] or [B, A, 6]   rows (i, a_x, a_y, a_z, r, k); i = -1 is padding
     fields     a `Field` or a list of at most MAX_FIELDS of them (lattice potentials; `field_energy`, not a column of `energy`)
     templates  a `Template` or a list of at most MAX_TEMPLATES of them (rigid superposition; `template_energy`)
+    features   a `Features`: bands and molecule-wide sums on the features h (`feature_energy`)
     Tensors or nested lists; a table with a leading batch axis holds one set of rows per molecule.  ValueError: lo > hi, a negative
     r, k, lo or hi, non-finite values, i == j, fractional indices, negative indices other than -1."""
 
-    def __init__(self, obstacles=None, pairs=None, anchors=None, fields=None, templates=None):
+    def __init__(self, obstacles=None, pairs=None, anchors=None, fields=None, templates=None, features=None):
+        if features is not None and not isinstance(features, Features):
+            raise ValueError(f"features must be a restraints.Features, got {type(features).__name__}")
+        self.features = features
         self.fields = _fields(fields)
         self.templates = _templates(templates)
         obs, pr, an = _table(obstacles, 5, "obstacles"), _table(pairs, 5, "pairs"), _table(anchors, 6, "anchors")
@@ -431,9 +676,20 @@ class Restraints:
         geom = torch.tensor([[t.k, float(FITS.index(t.fit))] for t in tl], dtype=torch.float32)
         return idx.contiguous(), f.contiguous(), geom.contiguous()
 
+    @property
+    def feature_sizes(self):
+        """(W, S) of the attached features, (0, 0) without."""
+        ft = getattr(self, "features", None)
+        return (0, 0) if ft is None else (ft.W, ft.S)
+
+    def feature_rows(self):
+        """(rows of the bands, rows of the sums): 1 (shared) or the B of the per-molecule ones."""
+        ft = getattr(self, "features", None)
+        return (1, 1) if ft is None else (ft.band_rows(), ft.sum_rows())
+
     def check_batch(self, B: int, what: str = "restraints") -> None:
-        for name, r in zip(("obstacles", "pairs", "anchors", "field weights", "templates"),
-                           self.rows() + (self.field_rows(), self.template_rows())):
+        for name, r in zip(("obstacles", "pairs", "anchors", "field weights", "templates", "feature bands", "feature sums"),
+                           self.rows() + (self.field_rows(), self.template_rows()) + self.feature_rows()):
             if r != 1 and r != int(B):
                 raise ValueError(f"{what}: {name} hold rows for {r} molecules, the call has {B} (give [n, w] to share one set)")
 
@@ -445,6 +701,9 @@ class Restraints:
             setattr(out, k, t if t.shape[0] == 1 else t[lo:hi].contiguous())
         out.fields = [f._slice(lo, hi) for f in getattr(self, "fields", ())]
         out.templates = [t._slice(lo, hi) for t in getattr(self, "templates", ())]
+        ft = getattr(self, "features", None)
+        out.features = None if ft is None else ft._slice(lo, hi)
+        out._feat = getattr(self, "_feat", None)
         out._model = getattr(self, "_model", None)
         return out
 
@@ -454,13 +713,15 @@ class Restraints:
         a list of {"file": "pocket.npy", "origin": [...], "spacing": s | [...], "k": ..., "wall": ..., "weights": [...]} - `file`
         relative to the JSON file, read with numpy.load(allow_pickle=False); k, wall and weights optional - and `templates` (optional):
         a list of {"index": [...], "positions": [[...]], "weights": [...], "k": ..., "fit": "rigid" | "translation"}; weights, k and
-        fit optional."""
+        fit optional - and `features` (optional): {"bands": {"lo": ..., "hi": ..., "k": ...} | {"target": ..., "tol": ..., "k": ...},
+        "sums": [{"coef": [...], "lo": ..., "hi": ..., "k": ..., "reduce": "sum" | "mean"}]}; null for an infinite bound."""
         import json
         import os
         with open(path) as f:
             d = json.load(f)
-        if not isinstance(d, dict) or set(d) - {"obstacles", "pairs", "anchors", "fields", "templates"}:
-            raise ValueError(f"{path}: expected an object with the keys obstacles / pairs / anchors / fields / templates")
+        if not isinstance(d, dict) or set(d) - {"obstacles", "pairs", "anchors", "fields", "templates", "features"}:
+            raise ValueError(f"{path}: expected an object with the keys obstacles / pairs / anchors / fields / templates / features")
+        features = None if d.get("features") is None else Features.from_dict(d["features"], path)
         templates = None
         if d.get("templates") is not None:
             if not isinstance(d["templates"], list):
@@ -485,13 +746,15 @@ class Restraints:
                 except (OSError, ValueError) as err:
                     raise ValueError(f"{path}: cannot read the field file {e['file']!r}: {err}") from None
                 fields.append(Field(vals, e["origin"], e["spacing"], e.get("k", 1.0), e.get("wall", 0.0), e.get("weights")))
-        return cls(d.get("obstacles"), d.get("pairs"), d.get("anchors"), fields, templates)
+        return cls(d.get("obstacles"), d.get("pairs"), d.get("anchors"), fields, templates, features)
 
     # ------------------------------------------------------------------ device side
-    def attach(self, topo, scale: torch.Tensor, nv0: float, dev, stream, frame: int = 0) -> None:
+    def attach(self, topo, scale: torch.Tensor, nv0: float, dev, stream, frame: int = 0, feat=None) -> None:
         """hd_restraint_attach: the tables and the scales [1] or [B] into the topology's buffers (stream-ordered copies).  `frame` 1:
         then hd_restraint_frame - the tables are in the frame of an inpainting call's known fragments (attaching resets to 0).  With
-        fields, hd_restraint_fields goes between the two (attaching resets to no fields); `topo` then also needs its `.N`."""
+        fields, hd_restraint_fields goes between the two (attaching resets to no fields); `topo` then also needs its `.N`.  `feat`:
+        (nv1, nb1, ratio) of the model and the resolved schedule - with it the features, if any, are attached too
+        (hd_restraint_features; attaching resets to no features); without it the call sees none."""
         from . import _lib
         P, Q, A = self.sizes
         t = [x.to(dev).contiguous() for x in (self.obs, self.pair_idx, self.pair_f, self.anc_idx, self.anc_f, scale.to(torch.float32))]
@@ -504,8 +767,24 @@ class Restraints:
             self._attach_fields(topo, dev, stream)
         if self.n_templates:                             # (attaching resets to no templates; fields and templates in either order)
             self._attach_templates(topo, stream)
+        if feat is not None and getattr(self, "features", None) is not None:
+            self._attach_features(topo, feat, stream)
         if frame:
             _lib.check(_lib.load().hd_restraint_frame(topo.ptr, int(frame)), "hd_restraint_frame")
+
+    def _attach_features(self, topo, feat, stream) -> None:
+        """hd_restraint_features: the band tables and the sum rows (host arrays) into the topology's buffers; `feat` is remembered so
+        that `feature_energy` on the call's result attaches the same and the cached graph stays."""
+        import ctypes as C
+        from . import _lib
+        lo, hi, k, coef, f = (t.numpy() for t in self.features.tables())
+        W, S = self.features.W, self.features.S
+        fp = lambda a, n: a.ctypes.data_as(C.POINTER(C.c_float)) if n else None
+        nv1, nb1, ratio = (float(v) for v in feat)
+        _lib.check(_lib.load().hd_restraint_features(
+            topo.ptr, fp(lo, W), fp(hi, W), fp(k, W), int(lo.shape[0]), W, fp(coef, S), fp(f, S), int(coef.shape[0]), S,
+            nv1, nb1, ratio, stream), "hd_restraint_features")
+        self._feat = (nv1, nb1, ratio)
 
     def _attach_fields(self, topo, dev, stream) -> None:
         """hd_restraint_fields: the lattices (each field's device copy; several are concatenated on the device), their geometry and
@@ -555,11 +834,12 @@ class Restraints:
             raise ValueError(f"x must be [{B}, {N}, 3], got {tuple(x.shape)}")
         return B, N
 
-    def _on_device(self, x, node_mask, model, _attach, what: str, call):
+    def _on_device(self, x, node_mask, model, _attach, what: str, call, features: bool = False):
         """The device path of `energy`, `field_energy` and `template_energy`, behind their checks: call(run) between attach and detach,
         where run(name, *args) is the library's entry point `name`(handle, topology, x as contiguous float32, *args, stream).
         (`_attach`: the scales and nv0 of the sampling call whose result this is - the energies read neither, and attaching what the
-        call attached keeps its cached graph.)"""
+        call attached keeps its cached graph.)  `features`: the entry point reads the features - they are attached with what the last
+        sampling call attached them with, or (1, 0, 1): the energies read h in data units, so neither enters."""
         model = model if model is not None else (self._model() if getattr(self, "_model", None) is not None else None)
         if model is None:
             raise ValueError(f"{what} on a device needs model= (the DiffusionQM9 that owns the library handle) unless these "
@@ -571,7 +851,7 @@ class Restraints:
         topo = model.dynamics.topology(node_mask.to(dev), None, int(node_mask.shape[0]), int(node_mask.shape[1]))
         xs = x.detach().to(torch.float32).contiguous()
         scale, nv0 = (torch.ones(1), 1.0) if _attach is None else _attach
-        self.attach(topo, scale, nv0, dev, stream)
+        self.attach(topo, scale, nv0, dev, stream, feat=(getattr(self, "_feat", None) or (1.0, 0.0, 1.0)) if features else None)
         try:
             return call(lambda name, *args: _lib.check(getattr(_lib.load(), name)(h, topo.ptr, xs.data_ptr(), *args, stream), name))
         finally:
@@ -628,6 +908,31 @@ class Restraints:
 
         return self._on_device(x, node_mask, model, _attach, "field_energy", call)
 
+    def feature_energy(self, h: torch.Tensor, node_mask: torch.Tensor, model=None, _attach=None, return_sums: bool = False):
+        """[B, 2] float64 (U_band, U_sum) of features h [B, N, F] in data units under node_mask [B, N, 1]; `return_sums`: (U, m [B, S]),
+        m_r = 0 for a row that is inactive or contributes nothing.  On a device the HIP kernel evaluates it
+        (k_restraint_feature_energy; `model` as in `energy`); on the CPU the same formulas in torch float64.  Needs features."""
+        ft = getattr(self, "features", None)
+        if ft is None:
+            raise ValueError("feature_energy: these restraints hold no features")
+        B, N = int(node_mask.shape[0]), int(node_mask.shape[1])
+        if tuple(h.shape) != (B, N, ft.F):
+            raise ValueError(f"h must be [{B}, {N}, {ft.F}], got {tuple(h.shape)}")
+        if ft.W > N:
+            raise ValueError(f"feature_energy: the bands name {ft.W} nodes, the molecules have {N}")
+        self.check_batch(B, "feature_energy")
+        if h.device.type != "cuda":
+            U, m = feature_energy_terms(self, h.detach().double(), node_mask)
+            return (U, m) if return_sums else U
+
+        def call(run):
+            out = torch.empty((B, 2), device=h.device, dtype=torch.float64)
+            m = torch.zeros((B, ft.S), device=h.device, dtype=torch.float64)
+            run("hd_restraint_feature_energy", out.data_ptr(), m.data_ptr() if ft.S else None)
+            return (out, m) if return_sums else out
+
+        return self._on_device(h, node_mask, model, _attach, "feature_energy", call, features=True)
+
     @staticmethod
     def detach(topo) -> None:
         from . import _lib
@@ -664,10 +969,11 @@ class Restraints:
 
         return self._on_device(x, node_mask, model, _attach, "energy", call)
 
-    def result_entries(self, x: torch.Tensor, node_mask: torch.Tensor, model, attach, fixed_mask=None, x_known=None) -> dict:
+    def result_entries(self, x: torch.Tensor, node_mask: torch.Tensor, model, attach, fixed_mask=None, x_known=None, h=None) -> dict:
         """The restraint entries of a sampling call's results for its returned x, batch tensors on x's device: 'restraint_energy'
         [B, 3]; with fields 'restraint_field_energy' [B]; with templates the entries of `template_results`; for a call in the frame
-        of `x_known` (fixed_mask, x_known) also 'frame_shift' [B, 3].  `attach`: the (scales, nv0) the call attached."""
+        of `x_known` (fixed_mask, x_known) also 'frame_shift' [B, 3]; with features and the returned `h` [B, N, F] (data units)
+        'restraint_feature_energy' [B, 2] and 'feature_sums' [B, S].  `attach`: the (scales, nv0) the call attached."""
         kw = dict(model=model, _attach=attach)
         framed = dict(fixed_mask=fixed_mask, x_known=x_known)
         if fixed_mask is None:
@@ -678,6 +984,9 @@ class Restraints:
             out['restraint_field_energy'] = self.field_energy(x, node_mask, **kw, **framed)
         if self.n_templates:
             out.update(self.template_results(x, node_mask, **kw))
+        if getattr(self, "features", None) is not None and h is not None:
+            U, m = self.feature_energy(h.to(x.device), node_mask, return_sums=True, **kw)
+            out['restraint_feature_energy'], out['feature_sums'] = U, m
         return out
 
 
@@ -747,6 +1056,38 @@ def field_energy_terms(rs: Restraints, x: torch.Tensor, node_mask: torch.Tensor)
         e = f.k * w * (V + 0.5 * f.wall * (out * out).sum(-1))
         total = total + torch.where(ok, e, torch.zeros_like(e)).sum(1)
     return total
+
+
+def feature_energy_terms(rs: Restraints, h: torch.Tensor, node_mask: torch.Tensor):
+    """([B, 2] (U_band, U_sum), m [B, S]) in h's dtype, differentiable in h: the feature formulas of the module docstring in torch.
+    A non-finite element has no band term; a sum row that reads one contributes nothing (m_r = 0)."""
+    ft = rs.features
+    B, N, F = int(h.shape[0]), int(h.shape[1]), int(h.shape[2])
+    nm = node_mask.reshape(B, N).bool().to(h.device)
+    fin = torch.isfinite(h)
+    hs = torch.where(fin, h, torch.zeros_like(h))
+    n = nm.sum(1).to(h)
+    ub = h.new_zeros(B)
+    if ft.W:
+        W = min(ft.W, N)
+        lo, hi, k = (t[:, :W].to(h).expand(B, W, F) for t in (ft.lo, ft.hi, ft.k))
+        v = hs[:, :W]
+        d = torch.clamp(v - hi, min=0) - torch.clamp(lo - v, min=0)
+        act = nm[:, :W, None] & fin[:, :W] & (k > 0)
+        ub = (0.5 * torch.where(act, k * d * d, torch.zeros_like(d))).sum((1, 2))
+    us, ms = h.new_zeros(B), []
+    for r in ft.sums:
+        c = r.coef.to(h)
+        read = nm[:, :, None] & (c != 0)[None, None, :]
+        ok = ~(read & ~fin).any(2).any(1) & (n > 0) & (r.k > 0)
+        s = torch.where(read, c * hs, torch.zeros_like(hs)).sum((1, 2))
+        m = s / n.clamp(min=1.0) if r.reduce == "mean" else s
+        m = torch.where(ok, m, torch.zeros_like(m))
+        lo, hi = r.lo.to(h).expand(B), r.hi.to(h).expand(B)
+        d = torch.clamp(m - hi, min=0) - torch.clamp(lo - m, min=0)
+        us = us + torch.where(ok, 0.5 * r.k * d * d, torch.zeros_like(d))
+        ms.append(m)
+    return torch.stack([ub, us], 1), (torch.stack(ms, 1) if ms else h.new_zeros(B, 0))
 
 
 def kabsch_rotation(S: torch.Tensor) -> torch.Tensor:
@@ -916,6 +1257,9 @@ def resolve(model, restraints, scale, schedule, clip, B: Optional[int] = None, w
     c = check_clip(clip)
     if not bool((s != 0).any()) and not steered:
         return None
+    ft = getattr(restraints, "features", None)
+    if ft is not None and ft.F != int(model.in_node_nf):
+        raise ValueError(f"{what}: the features name {ft.F} channels, the model's h has {int(model.in_node_nf)}")
     from .plan import unsupported
     unsupported(model, f"{what}: restraints", pocket, needs_noise)         # (the model's frame is the ligand's alone)
     if B is not None:

@@ -243,7 +243,9 @@ def parse_args(argv=None):
                     help="restraint-guided sampling: a JSON object with the keys obstacles [[y_x, y_y, y_z, r, k]], pairs [[i, j, lo, "
                          "hi, k]], anchors [[i, a_x, a_y, a_z, r, k]] shared by all molecules, in data units in the MODEL'S frame (the "
                          "molecule's centre of mass is the origin); the gradient of the energy on the network's data prediction goes "
-                         "into every transition.  Combines with everything --steps combines with (--eta / --spacing / --solver, "
+                         "into every transition.  The key features {bands: {lo, hi, k} | {target, tol, k}, sums: [{coef, lo, hi, k, "
+                         "reduce}]} restrains the feature channels h: bands on single elements, windows on molecule-wide sums or "
+                         "means.  Combines with everything --steps combines with (--eta / --spacing / --solver, "
                          "--guidance, --chain, --vary) except --known / --grow.  Mechanism only: which scale, schedule and clip help "
                          "is for you to validate")
     ap.add_argument("--restraint-frame", choices=["model", "known"], default=None,

@@ -148,6 +148,12 @@ def check_groups(st: Steer, node_mask, context=None, rs=None, scale=None, what: 
                 if t.rows == B and B > 1 and not all(_rows_equal(v.reshape(B, -1), P) for v in (t.index, t.positions, t.weights)):
                     bad = "restraint rows (templates)"
                     break
+        ft = getattr(rs, "features", None)
+        if bad is None and ft is not None and B > 1:
+            per = [t for t in (ft.lo, ft.hi, ft.k) if t is not None and t.shape[0] == B] + \
+                  [t for r in ft.sums for t in (r.lo, r.hi) if t.shape[0] == B]
+            if not all(_rows_equal(t.reshape(B, -1), P) for t in per):
+                bad = "restraint rows (features)"
     if bad is None and scale is not None and torch.as_tensor(scale).numel() == B and not _rows_equal(torch.as_tensor(scale).cpu().reshape(B, 1), P):
         bad = "restraint scales"
     if bad is not None:

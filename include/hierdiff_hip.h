@@ -540,6 +540,43 @@ int hd_restraint_field_energy_framed(hd_handle* h, hd_topology* topo, const floa
 int hd_restraint_templates(hd_topology* topo, int NT, int rows, int M, const int* idx, const float* f, const float* geom, void* stream);
 int hd_restraint_template_energy(hd_handle* h, hd_topology* topo, const float* x, double* out, double* fit16, void* stream);
 
+/* ---- Feature restraints (additive, ABI number unchanged; no reference counterpart): bands and molecule-wide sums on the features h
+ * of the data prediction, k_restrain_feat.hpp.  For a valid node i and channel c in [0, F), F = D - 3, in data units, with the fp32
+ * operations and the order of a record="x0" frame:
+ *   v_ic = fadd(fmul(fmul(1 / alpha_t, fsub(z[i,3+c], fmul(sigma_t, eps^[i,3+c]))), nv1), nb1)
+ * eps^ behind guidance and the position update (which does not touch the feature columns).  Everything below in double.
+ *   bands   lo, hi, k [band_rows][W][F], W <= N (nodes i >= W have none).  Element (i, c) is active when node i is valid, k_ic > 0 and
+ *           v_ic is finite:  U_band = 1/2 sum k_ic (max(0, v - hi)^2 + max(0, lo - v)^2),  dU/dv_ic = k_ic (max(0, v - hi) - max(0, lo - v)).
+ *           lo = -inf / hi = +inf: one-sided; lo = hi: a harmonic target; v on a bound: energy 0, gradient 0.
+ *   sums    at most HD_MAX_FEATURE_SUMS rows: coef [sum_rows][S][F], sum_f [sum_rows][S][4] = (lo, hi, k, reduce: 0 sum, 1 mean).
+ *           s_r = sum_{i valid} sum_c coef_rc v_ic,  n = valid nodes,  m_r = s_r or s_r / n,
+ *           U_sum = 1/2 sum_r k_r (max(0, m_r - hi_r)^2 + max(0, lo_r - m_r)^2),  dU/dv_ic += k_r (...) coef_rc (1 or 1 / n).
+ *           A row is inactive when k_r <= 0 or n = 0; it contributes nothing when a valid v it reads with a non-zero coefficient is
+ *           not finite.
+ *   update  eps^[i,3+c] += clip_i(s_b lambda_k ratio dU_feat/dv_ic) for valid nodes, U_feat = U_band + U_sum: s_b the molecule's scale
+ *           (hd_restraint_attach), lambda_k and clip_k the handle's restraint rows (hd_set_restraint), the clip on the Euclidean norm
+ *           over the node's F steps (apart from the position step's); no mean is removed.  An element whose step is exactly 0 keeps its
+ *           bits; position columns and masked rows are never written; s_b lambda_k ratio = 0 writes nothing.
+ * hd_restraint_features: HOST arrays, copied into library-owned buffers; call it behind hd_restraint_attach, which resets to "no
+ *   features" (in any order with hd_restraint_fields / _templates).  rows = 1 (shared) or B.  W = 0: no bands, S = 0: no sums, both 0:
+ *   no features.  ratio: 1, or nv1 / nv0 when lambda_k is the score weight nv0 sigma_t / alpha_t (dv / dz_h = nv1 / alpha_t).
+ *   HD_E_INVALID: null pointers, S > 8, W > N, rows not in {1, B}, non-finite k / coef / nv1 / nb1 / ratio, lo > hi, NaN bounds, reduce
+ *   not in {0, 1}; HD_E_STATE: no restraints attached.  A path loop then launches k_restrain_feat behind the position update in every
+ *   transition (in the known fragments' frame too: features have no frame, it acts on all valid nodes and the replacement step
+ *   overwrites known elements afterwards), and steering weighs on ((((U_obs + U_pair) + U_anc) + U_fld) + U_tpl) + U_feat.
+ *   use_graph    re-attaching tables of the same (W, S, rows, nv1, nb1, ratio) is a copy: the cached transition replays.  Anything else
+ *                rebuilds once; a featured call followed by an unfeatured one rebuilds once and gives the bits of a topology that never
+ *                had features.
+ * hd_restrain_feat: the single update on (z, eps) with the row {alpha_t, sigma_t, lambda, clip}, out of place or in place (out == eps).
+ * hd_restraint_feature_energy: out2 [B][2] = (U_band, U_sum) in double for features h [B][N][F] (fp32, data units) under the
+ *   topology's mask; sums [B][S] (NULL: not wanted) = m_r, 0 for a row that is inactive or contributes nothing.  Stream-ordered.
+ *   Both return HD_E_STATE without attached restraints or features and then write nothing. */
+#define HD_MAX_FEATURE_SUMS 8
+int hd_restraint_features(hd_topology* topo, const float* lo, const float* hi, const float* k, int band_rows, int W, const float* coef,
+                          const float* sum_f, int sum_rows, int S, float nv1, float nb1, float ratio, void* stream);
+int hd_restrain_feat(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4, float* out, void* stream);
+int hd_restraint_feature_energy(hd_handle* h, hd_topology* topo, const float* hf, double* out2, double* sums, void* stream);
+
 /* ---- Steered sampling (ABI 12, additive; no reference counterpart): sequential Monte-Carlo steering of a restrained path loop.
  * The batch is G groups of P rows (particles); group g owns rows g P .. g P + P - 1, which the CALLER guarantees to have equal
  * masks, contexts and restraint rows.  At every transition k, behind the network call, guidance and the restraint update of eps^:
