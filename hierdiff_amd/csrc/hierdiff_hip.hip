@@ -48,7 +48,7 @@ static int fail(int code, const std::string& msg) {
 // over its four wavefronts) instead of k_edge (one tile per wavefront); bit-identical, see k_edge_split.hpp
 #define HD_SPLIT_MAX_TILES 512
 // topologies above one whole-tile workgroup per CU and below this many tiles may run k_edge_mixed: a multiple of the CU count
-// of whole-tile workgroups plus column-split single-tile workgroups that back-fill (k_edge_split.hpp; rule in launch_edge_h)
+// of whole-tile workgroups plus column-split single-tile workgroups that back-fill (k_edge_split.hpp; rule in edge_family, launch.hpp)
 #define HD_MIX_MAX_TILES 16384
 
 struct LayerW {                 // float offsets into hd_handle::dw
@@ -406,8 +406,7 @@ static int dev_upload(T** p, const std::vector<T>& v) {
 
 // ----------------------------------------------------------------------------- create / destroy
 
-static int prepare_kernels(hd_handle* h);
-template <int H> static int prepare_edge_bwd_h();
+static int prepare_kernels(hd_handle* h);      // launch.hpp
 
 extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
     if (!cfg || !out) return fail(HD_E_INVALID, "hd_create: null argument");
@@ -1246,156 +1245,9 @@ extern "C" int hd_profile_read(hd_handle* h, double* ms3, long long* launches3) 
     return HD_OK;
 }
 
-// ----------------------------------------------------------------------------- forward
+// ----------------------------------------------------------------------------- kernel selection and launches
 
-template <int WM, int WN, int CN>
-static void launch_gemm(int epi, bool cat, const GemmArgs& g, hipStream_t s) {
-    const int nrt = (g.M + 32 * WM - 1) / (32 * WM), nct = g.Nc / (32 * WN * CN);
-    dim3 grid(8 * ((nrt + 7) / 8) * nct);
-    dim3 block(WM * WN * 64);
-    if (cat && epi == EPI_RANK1_SILU) hipLaunchKernelGGL((k_gemm<WM, WN, CN, EPI_RANK1_SILU, true>), grid, block, 0, s, g);
-    else if (epi == EPI_BIAS_MASK) hipLaunchKernelGGL((k_gemm<WM, WN, CN, EPI_BIAS_MASK, false>), grid, block, 0, s, g);
-    else if (cat && epi == EPI_BIAS) hipLaunchKernelGGL((k_gemm<WM, WN, CN, EPI_BIAS, true>), grid, block, 0, s, g);
-    else if (cat) hipLaunchKernelGGL((k_gemm<WM, WN, CN, EPI_BIAS_SILU, true>), grid, block, 0, s, g);
-    else if (epi == EPI_BIAS_SILU) hipLaunchKernelGGL((k_gemm<WM, WN, CN, EPI_BIAS_SILU, false>), grid, block, 0, s, g);
-    else if (epi == EPI_BIAS) hipLaunchKernelGGL((k_gemm<WM, WN, CN, EPI_BIAS, false>), grid, block, 0, s, g);
-    else if (epi == EPI_EGCL_PRE) hipLaunchKernelGGL((k_gemm<WM, WN, CN, EPI_EGCL_PRE, false>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((k_gemm<WM, WN, CN, EPI_RESID_MASK, false>), grid, block, 0, s, g);
-}
-
-template <int RT>
-static void launch_r16(int epi, bool agg, const R16Args& g, hipStream_t s) {
-    const int wpt = g.Nc >= 128 ? 8 : (g.Nc >> 4);
-    const dim3 grid(((g.M + 16 * RT - 1) / (16 * RT)) * (g.Nc / (16 * wpt)) * g.n_img), block(512);
-    const int lds = 16 * RT * (g.K + 4) * 4;
-    if (agg) hipLaunchKernelGGL((k_gemm_r16<EPI_BIAS_SILU, true, RT>), grid, block, lds, s, g);
-    else if (epi == EPI_BIAS) hipLaunchKernelGGL((k_gemm_r16<EPI_BIAS, false, RT>), grid, block, lds, s, g);
-    else if (epi == EPI_BIAS_SILU) hipLaunchKernelGGL((k_gemm_r16<EPI_BIAS_SILU, false, RT>), grid, block, lds, s, g);
-    else hipLaunchKernelGGL((k_gemm_r16<EPI_RESID_MASK, false, RT>), grid, block, lds, s, g);
-}
-
-static void gemm_r16(hd_handle* h, int epi, bool agg, const R16Args& g, hipStream_t s) {
-    ProfScope ps(h, s, 1);
-    launch_r16<1>(epi, agg, g, s);      // 32-row workgroups (RT = 2) were measured: slower up to B = 64, equal above (profiles/r03_r16_sweep2.log)
-}
-
-// Fused node update in two-piece FP16 arithmetic (k_node), 32-row workgroups.
-template <int H>
-static int node_lds_bytes(bool upd) {                    // region 0: the two fp16 pieces of X; region 1: those of T / the fp32 staging tile
-    const int r1 = std::max(32 * (H + 8) * 2 * 2, 32 * (H + 4) * 4);
-    return 32 * ((upd ? 2 * H : H) + 8) * 2 * 2 + r1;
-}
-
-template <int H>
-static int node_f32_lds_bytes(bool upd) { return 32 * ((upd ? 2 * H : H) + 4) * 4 + 32 * (H + 4) * 4; }
-
-template <int H, int NW>
-static void launch_node_hw(bool upd, int nab, int mode, const NodeArgs& a, hipStream_t s) {      // mode: 0 fp32, 3 fp16 two-piece
-    const int nrt = (a.M + 31) / 32;
-    const dim3 grid(8 * ((nrt + 7) / 8)), block(64 * NW);
-    if (mode == 0) {
-        const int ldsf = node_f32_lds_bytes<H>(upd);
-        if (!upd) hipLaunchKernelGGL((k_node_f32<H, NW, false, 1>), grid, block, ldsf, s, a);
-        else if (nab == 1) hipLaunchKernelGGL((k_node_f32<H, NW, true, 1>), grid, block, ldsf, s, a);
-        else hipLaunchKernelGGL((k_node_f32<H, NW, true, 2>), grid, block, ldsf, s, a);
-        return;
-    }
-    if constexpr (H >= 128) {                              // two-piece FP16 (fp16x3 mode; narrower widths run the fp32 node kernels)
-        const int lds = node_lds_bytes<H>(upd);
-        if (!upd) hipLaunchKernelGGL((k_node<H, NW, false, 1>), grid, block, lds, s, a);
-        else if (nab == 1) hipLaunchKernelGGL((k_node<H, NW, true, 1>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((k_node<H, NW, true, 2>), grid, block, lds, s, a);
-    }
-}
-
-template <int H, int NW>
-static int prepare_node_hw() {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_node_f32<H, NW, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, node_f32_lds_bytes<H>(false)));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_node_f32<H, NW, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, node_f32_lds_bytes<H>(true)));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_node_f32<H, NW, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, node_f32_lds_bytes<H>(true)));
-    if constexpr (H >= 128) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_node<H, NW, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, node_lds_bytes<H>(false)));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_node<H, NW, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, node_lds_bytes<H>(true)));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_node<H, NW, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, node_lds_bytes<H>(true)));
-    }
-    return HD_OK;
-}
-
-// wavefronts per 32-row workgroup: one 32-column tile of an H-wide output each, at most 8 (two per SIMD)
-template <int H>
-static void launch_node_h(bool upd, int nab, int mode, const NodeArgs& a, hipStream_t s) {
-    launch_node_hw<H, (H / 32 < 8 ? H / 32 : 8)>(upd, nab, mode, a, s);
-}
-
-template <int H>
-static int prepare_node_h() { return prepare_node_hw<H, (H / 32 < 8 ? H / 32 : 8)>(); }
-
-static void node_update(hd_handle* h, bool upd, int nab, const NodeArgs& a, hipStream_t s) {
-    ProfScope ps(h, s, 1);
-    const int mode = h->node_mode;
-    switch (h->H) {
-        case 32: launch_node_h<32>(upd, nab, mode, a, s); break;
-        case 64: launch_node_h<64>(upd, nab, mode, a, s); break;
-        case 128: launch_node_h<128>(upd, nab, mode, a, s); break;
-        default: launch_node_h<256>(upd, nab, mode, a, s); break;
-    }
-}
-
-// fp16x3, few rows: the node update as three launches of 32 x 32 output tiles (k_node_split.hpp), bit-identical to the fused kernel
-template <int H, int PH, int CTW>
-static void launch_node_split_hc(const NodeSplitArgs& a, hipStream_t s) {
-    const int nrt = (a.M + 31) / 32;
-    const int per = (PH == 3 ? 2 * H / 32 * a.n_img : H / 32) / CTW;
-    const int lds = node_split_lds_bytes<H, PH, CTW>();
-    hipLaunchKernelGGL((k_node_split<H, PH, CTW>), dim3(8 * ((nrt + 7) / 8) * per), dim3(256), lds, s, a);
-}
-// one 32-column tile per workgroup: two (half the workgroups, half the redundant operand loads; same bits) were measured slower
-// at every size from 24 to 64 molecules (profiles/r05_node_split_sweep.log: 0.85 / 0.86 / 0.94 / 0.96 of the fused kernel's forward
-// time with one tile, 0.90 / 0.91 / 0.95 / 0.97 with two)
-template <int H, int PH>
-static void launch_node_split_h(const NodeSplitArgs& a, hipStream_t s) { launch_node_split_hc<H, PH, 1>(a, s); }
-template <int PH>
-static void launch_node_split(hd_handle* h, const NodeSplitArgs& a, hipStream_t s) {
-    ProfScope ps(h, s, 1);
-    if (h->H == 128) launch_node_split_h<128, PH>(a, s); else launch_node_split_h<256, PH>(a, s);
-}
-template <int H, int PH, int CTW>
-static int prepare_node_split_one() {
-    const int lds = node_split_lds_bytes<H, PH, CTW>();
-    HIP_TRY(hipFuncSetAttribute((const void*)k_node_split<H, PH, CTW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    return HD_OK;
-}
-// exact fp32, widths >= 128, below HD_FUSE_MIN_ROWS rows: the same three launches on k_node_f32's arithmetic (k_node_split_f32)
-template <int H, int PH>
-static void launch_node_split_f32_h(const NodeSplitArgs& a, hipStream_t s) {
-    const int nrt = (a.M + 31) / 32;
-    const int per = (PH == 3 ? 2 * H / 32 * a.n_img : H / 32);
-    const int lds = node_split_f32_lds_bytes<H, PH>();
-    hipLaunchKernelGGL((k_node_split_f32<H, PH>), dim3(8 * ((nrt + 7) / 8) * per), dim3(256), lds, s, a);
-}
-template <int PH>
-static void launch_node_split_f32(hd_handle* h, const NodeSplitArgs& a, hipStream_t s) {
-    ProfScope ps(h, s, 1);
-    if (h->H == 128) launch_node_split_f32_h<128, PH>(a, s); else launch_node_split_f32_h<256, PH>(a, s);
-}
-template <int H, int PH>
-static int prepare_node_split_f32_one() {
-    const int lds = node_split_f32_lds_bytes<H, PH>();
-    HIP_TRY(hipFuncSetAttribute((const void*)k_node_split_f32<H, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    return HD_OK;
-}
-
-template <int H>
-static int prepare_node_split_h() {
-    HD_TRY((prepare_node_split_f32_one<H, 1>())); HD_TRY((prepare_node_split_f32_one<H, 2>())); HD_TRY((prepare_node_split_f32_one<H, 3>()));
-    HD_TRY((prepare_node_split_one<H, 1, 1>())); HD_TRY((prepare_node_split_one<H, 2, 1>())); HD_TRY((prepare_node_split_one<H, 3, 1>()));
-    return HD_OK;
-}
-
-template <int H>
-static int edge_lds_bytes() {       // dynamic part: W2 double buffer + wave scratch (w_r/w_d/b2/wa are static)
-    return (2 * 32 * H + 2 * H + 4 * 136) * 4;
-}
+#include "launch.hpp"
 
 #ifdef HD_DEBUG_KERNELS
 // Measurement build only (python -m hierdiff_amd.build --debug-kernels): HD_ABLATE=<bits> selects an ablated
@@ -1419,7 +1271,7 @@ extern "C" int hd_debug_node_trace(long long* out, int max_ll) {
 
 template <int PREC>
 static bool launch_edge_ablated(hd_handle* h, const EdgeArgs& a, hipStream_t s) {
-    const int lds = edge_lds_bytes<256>();
+    const int lds = edge_lds_bytes(256);
     const dim3 grid(a.n_wg), block(256);
     auto run = [&](auto Abl) {
         constexpr int ABL = decltype(Abl)::value;
@@ -1458,158 +1310,7 @@ static bool launch_edge_ablated(hd_handle* h, const EdgeArgs& a, hipStream_t s) 
 extern "C" int hd_debug_edge_trace(hd_handle*, long long*, int) { return 0; }      // product build: nothing is traced
 #endif
 
-// Which kernel family runs a list of n_tiles edge tiles at width >= 128 in arithmetic `mode` (launch_edge_h below and
-// hd_edge_layer_save_rows ask the same question): the column-split kernel, the mix of whole and column-split tiles, or k_edge.
-static bool edge_runs_split(const hd_handle* h, int n_tiles, int mode) {
-    return n_tiles > 0 && n_tiles <= (mode == 0 ? h->split_max_tiles + h->split_max_tiles / 3 : h->split_max_tiles);
-}
-static bool edge_runs_mixed(const hd_handle* h, int n_tiles, int mode) {
-    const int per_round = 4 * h->n_cu;
-    const int left = n_tiles - (n_tiles / per_round) * per_round;
-    const bool pays = left > 0 && left * 10 <= (mode == 0 ? 29 : 10) * h->n_cu;
-    return n_tiles > per_round && n_tiles < h->mix_max_tiles && (pays || h->mix_rounds >= 0);
-}
-
-// `mode_override` >= 0 selects the arithmetic of THIS launch (0 fp32, 3 fp16x3) instead of the handle's: the opt-in fp16x3
-// forward of the training path (hd_edge_layer_forward_s) on a handle whose other kernels stay exact fp32
-template <int H>
-static int launch_edge_h(hd_handle* h, bool coord, const EdgeArgs& a, hipStream_t s, int mode_override = -1) {
-    const int lds = edge_lds_bytes<H>();
-    // kernel family of this launch: 0 fp32, 3 fp16x3
-    const int prec = mode_override >= 0 ? mode_override : h->edge_mode;
-    const dim3 grid(a.n_wg), block(256);
-    if constexpr (H >= 128) {
-        if (a.dscal) {
-            // training forward in fp16x3 arithmetic: the whole-tile kernel on the unscaled parameters (HD_EDGE_UNSCALED), keeping pre2 or not
-            if (a.pre2) {
-                if (coord) hipLaunchKernelGGL((k_edge<H, true, 3, HD_EDGE_SAVE | HD_EDGE_UNSCALED>), grid, block, lds, s, a);
-                else hipLaunchKernelGGL((k_edge<H, false, 3, HD_EDGE_SAVE | HD_EDGE_UNSCALED>), grid, block, lds, s, a);
-            } else {
-                if (coord) hipLaunchKernelGGL((k_edge<H, true, 3, HD_EDGE_UNSCALED>), grid, block, lds, s, a);
-                else hipLaunchKernelGGL((k_edge<H, false, 3, HD_EDGE_UNSCALED>), grid, block, lds, s, a);
-            }
-            return HD_OK;
-        }
-    }
-    if (a.pre2) {
-        // training forward that keeps pre2 for the backward pass (HD_EDGE_SAVE): always the whole-tile kernel, whose accumulator
-        // layout is the saved layout (the caller offers the buffer only where this kernel would run anyway: edge_layer_saves)
-        if (coord) hipLaunchKernelGGL((k_edge<H, true, 0, HD_EDGE_SAVE>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((k_edge<H, false, 0, HD_EDGE_SAVE>), grid, block, lds, s, a);
-        return HD_OK;
-    }
-#ifdef HD_DEBUG_KERNELS
-    if constexpr (H == 256) {
-        if (h->ablate && !coord && (prec == 3 ? launch_edge_ablated<3>(h, a, s) : launch_edge_ablated<0>(h, a, s))) return HD_OK;
-    }
-#endif
-    if constexpr (H >= 128) {
-        // at most 512 tiles: one tile per workgroup, columns split over its four wavefronts (k_edge_split.hpp; bit-identical
-        // to k_edge in both precision modes, a quarter of the serial MFMA chain per wavefront)
-        const int mode = prec;
-        // measured break-even (profiles/history/r02_split_sweep.log): between 490 and 654 tiles in the 16-bit split modes, between 654 and 870
-        // in fp32 (the longer MFMA chain has more to gain from the split)
-        if (edge_runs_split(h, a.n_tiles, mode)) {
-            const dim3 sgrid(a.n_tiles);
-            if (mode == 0) {
-                if (coord) hipLaunchKernelGGL((k_edge_split<H, true, 0>), sgrid, block, 0, s, a);
-                else hipLaunchKernelGGL((k_edge_split<H, false, 0>), sgrid, block, 0, s, a);
-            } else {
-                if (coord) hipLaunchKernelGGL((k_edge_split<H, true, 3>), sgrid, block, 0, s, a);
-                else hipLaunchKernelGGL((k_edge_split<H, false, 3>), sgrid, block, 0, s, a);
-            }
-            return HD_OK;
-        }
-    }
-    if constexpr (H >= 128) {
-        // between one whole-tile workgroup per CU and HD_MIX_MAX_TILES: R * n_cu whole-tile workgroups (every CU the same
-        // number) + the remaining tiles as column-split workgroups that back-fill (k_edge_mixed; bit-identical per tile)
-        const int mode = prec;
-        const int per_round = 4 * h->n_cu;
-        // Measured (profiles/r03_mix_sweep*.log, ms per forward, plain -> mixed): fp32 B = 40 1.89 -> 1.45, 64 1.93 -> 1.88,
-        // 96 2.66 -> 2.60, 128 3.29 -> 3.17, 160 4.15 -> 3.89, 192 4.79 -> 4.40, 256 5.41 -> 5.51; the 16-bit split modes gain only
-        // while few tiles are left over (B = 40: -14 %; B = 64 ... 256: +2 ... +8 %).  A column-split tile costs about 1.5 x a
-        // whole one in SIMD time, so the mix pays when it replaces a badly filled last round: at most 2.9 left-over tiles per
-        // CU in fp32, 1.0 in fp16x3.
-        int R = a.n_tiles / per_round;
-        if (edge_runs_mixed(h, a.n_tiles, mode)) {
-            if (h->mix_rounds >= 0) R = std::min(R, h->mix_rounds);
-            EdgeArgs m = a;
-            m.n_wg = R * h->n_cu;
-            const dim3 mgrid(m.n_wg + (a.n_tiles - 4 * m.n_wg));
-            const int ldsm = std::max(edge_lds_bytes<H>(), edge_split_lds_bytes<H>());
-            if (mode == 0) {
-                if (coord) hipLaunchKernelGGL((k_edge_mixed<H, true, 0>), mgrid, block, ldsm, s, m);
-                else hipLaunchKernelGGL((k_edge_mixed<H, false, 0>), mgrid, block, ldsm, s, m);
-            } else {
-                if (coord) hipLaunchKernelGGL((k_edge_mixed<H, true, 3>), mgrid, block, ldsm, s, m);
-                else hipLaunchKernelGGL((k_edge_mixed<H, false, 3>), mgrid, block, ldsm, s, m);
-            }
-            return HD_OK;
-        }
-    }
-    if (prec == 3) {
-        if (coord) hipLaunchKernelGGL((k_edge<H, true, 3>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((k_edge<H, false, 3>), grid, block, lds, s, a);
-    } else if constexpr (edge_packed_width(H)) {
-        // the plain exact-fp32 launch is the one family that runs the packed-VALU form (HD_EDGE_PACKED, k_edge.hpp): same bits
-        if (coord) hipLaunchKernelGGL((k_edge<H, true, 0, HD_EDGE_PACKED>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((k_edge<H, false, 0, HD_EDGE_PACKED>), grid, block, lds, s, a);
-    } else {
-        if (coord) hipLaunchKernelGGL((k_edge<H, true, 0>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((k_edge<H, false, 0>), grid, block, lds, s, a);
-    }
-    return HD_OK;
-}
-
-// Raise the dynamic-LDS limit of the edge kernels for this device (done once, at hd_create: it is
-// not allowed while a stream is capturing).
-template <int H>
-static int prepare_edge_h() {
-    const int lds = edge_lds_bytes<H>();
-    HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, true, 0, HD_EDGE_SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, false, 0, HD_EDGE_SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if constexpr (edge_packed_width(H)) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, true, 0, HD_EDGE_PACKED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, false, 0, HD_EDGE_PACKED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    if constexpr (H >= 128) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, true, 3, HD_EDGE_SAVE | HD_EDGE_UNSCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, false, 3, HD_EDGE_SAVE | HD_EDGE_UNSCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, true, 3, HD_EDGE_UNSCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_edge<H, false, 3, HD_EDGE_UNSCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        const int m0 = std::max(edge_lds_bytes<H>(), edge_split_lds_bytes<H>());
-        HIP_TRY(hipFuncSetAttribute((const void*)k_edge_mixed<H, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, m0));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_edge_mixed<H, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, m0));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_edge_mixed<H, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, m0));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_edge_mixed<H, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, m0));
-    }
-    return HD_OK;
-}
-
-static int prepare_kernels(hd_handle* h) {
-    switch (h->H) {
-        case 32: HD_TRY(prepare_node_h<32>()); HD_TRY(prepare_edge_bwd_h<32>()); return prepare_edge_h<32>();
-        case 64: HD_TRY(prepare_node_h<64>()); HD_TRY(prepare_edge_bwd_h<64>()); return prepare_edge_h<64>();
-        case 128: HD_TRY(prepare_node_h<128>()); HD_TRY(prepare_node_split_h<128>()); HD_TRY(prepare_edge_bwd_h<128>()); return prepare_edge_h<128>();
-        default: HD_TRY(prepare_node_h<256>()); HD_TRY(prepare_node_split_h<256>()); HD_TRY(prepare_edge_bwd_h<256>()); return prepare_edge_h<256>();
-    }
-}
-
-static int edge(hd_handle* h, bool coord, const EdgeArgs& a, hipStream_t s, int mode_override = -1) {
-    if (a.n_wg == 0) return HD_OK;
-    ProfScope ps(h, s, 0);
-    switch (h->H) {
-        case 32: return launch_edge_h<32>(h, coord, a, s, mode_override);
-        case 64: return launch_edge_h<64>(h, coord, a, s, mode_override);
-        case 128: return launch_edge_h<128>(h, coord, a, s, mode_override);
-        default: return launch_edge_h<256>(h, coord, a, s, mode_override);
-    }
-}
+// ----------------------------------------------------------------------------- forward
 
 static int forward_impl(hd_handle* h, hd_topology* t, const float* xh, const float* tt, int t_numel,
                         const float* context, int mol_shape, float* out, hipStream_t s) {
@@ -1617,6 +1318,7 @@ static int forward_impl(hd_handle* h, hd_topology* t, const float* xh, const flo
     const int H = h->H, M = t->M;
     const float* W = h->dw;
     h->prof_now = h->prof != 0 && (h->prof_fwd++ % h->prof_stride) == 0;
+    const NodePath path = node_path(h, M);
     if (M == 0) HIP_TRY(hipMemsetAsync(h->d_nanflag, 0, sizeof(int), s));      // otherwise k_node_init resets it
     if (M > 0) {
         {
@@ -1626,7 +1328,7 @@ static int forward_impl(hd_handle* h, hd_topology* t, const float* xh, const flo
             a.embT = W + h->embT; a.emb_b = W + h->emb_b; a.h = t->hbuf; a.x0 = t->x0; a.xcur = t->xcur;
             a.nanflag = h->d_nanflag;
             // fp16x3, few rows: the AB-only launch of k_node_split accumulates the row maxima of AB with an atomic max
-            a.zero_max = (h->node_mode == 3 && M < h->node_split_max_rows && h->edge_mode == 3) ? t->abmax : nullptr;
+            a.zero_max = (path == NodePath::Split && h->edge_mode == 3) ? t->abmax : nullptr;
             a.M = M; a.N = t->N; a.D = h->D; a.F = h->F; a.C = c.context_node_nf; a.H = H;
             a.t_stride = (t_numel == 1) ? 0 : 1; a.cond_time = c.condition_time;
             const long long total = (long long)M * (H / 4);
@@ -1650,28 +1352,12 @@ static int forward_impl(hd_handle* h, hd_topology* t, const float* xh, const flo
             // fp16x3 at widths >= 128: the fused node kernel leaves the row maxima of what it writes (narrower widths: k_ab_rowmax)
             a.ABmax[q] = (h->edge_mode == 3 && h->node_mode != 0) ? (dst == t->AB ? t->abmax : t->abmax2) : nullptr;
         };
-        // fp32 mode, few rows: the fused kernel's serial chain per 32-row workgroup (~50 us) is not hidden by other workgroups
-        // (60 of them at B = 64), the k_agg + 3 x k_gemm chain spreads the same work over 64 x 64 tiles.  Both paths are
-        // bit-identical (same MFMA order per output element, bias added after the contraction), so a sample's bits do
-        // not depend on which one its batch size selects (test_fp32_node_paths_agree_bitwise).
-        const bool fused = h->node_mode != 0 || M >= h->fuse_min_rows;
         auto r16_args = [&]() {
             R16Args g;
             std::memset(&g, 0, sizeof(g));
             g.A = t->hbuf; g.lda = H; g.K1 = H; g.K = H; g.M = M; g.n_img = 1; g.nmask = t->nmask; g.norm = agg_norm(c, t);
             return g;
         };
-        auto ab_r16 = [&](int nab, const LayerW* const* nxt, float* const* dst) {       // AB_q = h [W1a | W1b]_q^T + [b1 | 0]
-            R16Args g = r16_args();
-            g.Nc = 2 * H; g.ldc = 2 * H; g.n_img = nab;
-            for (int q = 0; q < nab; ++q) { g.Bimg[q] = W + nxt[q]->ab_gimg; g.bias[q] = W + nxt[q]->ab_bias; g.C[q] = dst[q]; }
-            gemm_r16(h, EPI_BIAS, false, g, s);
-        };
-        // fp16x3, few rows: the fused kernel's chain per 32-row workgroup (20 - 27 us, a weight stream through one CU) is not hidden
-        // when only a few workgroups exist; k_node_split spreads every phase's columns over workgroups (bit-identical)
-        const bool nsplit = h->node_mode == 3 && M < h->node_split_max_rows;
-        // exact fp32, widths >= 128, below HD_FUSE_MIN_ROWS: k_node_split_f32 (bit-identical to k_node_f32) instead of k_gemm_r16
-        const bool fsplit = h->node_mode == 0 && M < h->fuse_min_rows && H >= 128 && h->f32_split;
         auto split_args = [&]() {
             NodeSplitArgs a;
             std::memset(&a, 0, sizeof(a));
@@ -1683,25 +1369,67 @@ static int forward_impl(hd_handle* h, hd_topology* t, const float* xh, const flo
             a.Wimg[q] = W + nw.ab_img; a.bias[q] = W + nw.ab_bias; a.winv[q] = 1.0f / nw.abs_; a.ABout[q] = dst;
             a.ABmax[q] = h->edge_mode == 3 ? (dst == t->AB ? t->abmax : t->abmax2) : nullptr;
         };
+        // The node side on the forward's path: the node update of layer `w` + the first edge Linear of the nab layers `nxt` that
+        // follow, their AB into dst; w == nullptr: AB only (the very first layer)
+        auto node_step = [&](const LayerW* w, int nab, const LayerW* const* nxt, float* const* dst) -> int {
+            if (path == NodePath::Split) {
+                NodeSplitArgs a = split_args();
+                if (w) { a.w3l1 = w->w3l1; a.w4l1 = w->w4l1; a.b3max = w->b3max; a.b4max = w->b4max; }
+                NodeSplitArgs p3 = a;
+                p3.n_img = nab; p3.upd = w ? 1 : 0;         // (AB only: the row maxima start from the zeros k_node_init left)
+                for (int q = 0; q < nab; ++q) split_ab(p3, q, *nxt[q], dst[q]);
+                if (w) {
+                    NodeSplitArgs p1 = a, p2 = a;
+                    p1.Wimg[0] = W + w->w3_img; p1.bias[0] = W + w->b3; p1.winv[0] = 1.0f / w->w3s;
+                    HD_TRY(node_split(h, false, 1, p1, s));
+                    p2.Wimg[0] = W + w->w4_img; p2.bias[0] = W + w->b4; p2.winv[0] = 1.0f / w->w4s;
+                    for (int q = 0; q < nab; ++q) p2.zero_max[q] = p3.ABmax[q];
+                    HD_TRY(node_split(h, false, 2, p2, s));
+                }
+                return node_split(h, false, 3, p3, s);
+            }
+            if (path == NodePath::SplitF32) {
+                if (w) {
+                    NodeSplitArgs p1 = split_args(), p2 = split_args();
+                    p1.Wimg[0] = W + w->w3_img; p1.bias[0] = W + w->b3;
+                    HD_TRY(node_split(h, true, 1, p1, s));
+                    p2.Wimg[0] = W + w->w4_img; p2.bias[0] = W + w->b4;
+                    HD_TRY(node_split(h, true, 2, p2, s));
+                }
+                NodeSplitArgs p3 = split_args();
+                p3.n_img = nab; p3.upd = w ? 1 : 0;
+                for (int q = 0; q < nab; ++q) { p3.Wimg[q] = W + nxt[q]->ab_img; p3.bias[q] = W + nxt[q]->ab_bias; p3.ABout[q] = dst[q]; }
+                return node_split(h, true, 3, p3, s);
+            }
+            if (path == NodePath::Fused) {
+                NodeArgs a = node_args();
+                if (w) {
+                    a.W3img = W + w->w3_img; a.b3 = W + w->b3; a.W4img = W + w->w4_img; a.b4 = W + w->b4;
+                    if (h->node_mode == 3) {
+                        a.w3inv = 1.0f / w->w3s; a.w4inv = 1.0f / w->w4s; a.w3l1 = w->w3l1; a.w4l1 = w->w4l1; a.b3max = w->b3max; a.b4max = w->b4max;
+                    }
+                }
+                for (int q = 0; q < nab; ++q) set_ab(a, q, *nxt[q], dst[q]);
+                return node_update(h, w != nullptr, nab, a, s);
+            }
+            if (w) {
+                R16Args g = r16_args();
+                g.part = t->part; g.pstart = t->pstart; g.K1 = H; g.K = 2 * H; g.Nc = H;
+                g.Bimg[0] = W + w->w3_gimg; g.bias[0] = W + w->b3; g.C[0] = t->Tb; g.ldc = H;
+                HD_TRY(gemm_r16(h, EPI_BIAS_SILU, true, g, s));              // T = silu([h | agg] W3^T + b3)
+                g = r16_args();
+                g.A = t->Tb; g.Bimg[0] = W + w->w4_gimg; g.bias[0] = W + w->b4; g.C[0] = t->hbuf; g.ldc = H; g.Nc = H;
+                HD_TRY(gemm_r16(h, EPI_RESID_MASK, false, g, s));            // h = (h + T W4^T + b4) mask
+            }
+            R16Args g = r16_args();                                          // AB_q = h [W1a | W1b]_q^T + [b1 | 0]
+            g.Nc = 2 * H; g.ldc = 2 * H; g.n_img = nab;
+            for (int q = 0; q < nab; ++q) { g.Bimg[q] = W + nxt[q]->ab_gimg; g.bias[q] = W + nxt[q]->ab_bias; g.C[q] = dst[q]; }
+            return gemm_r16(h, EPI_BIAS, false, g, s);
+        };
         {
             const LayerW* first[2] = {&h->gcl[0], nullptr};
             float* dst[2] = {t->AB, nullptr};
-            if (nsplit) {
-                NodeSplitArgs a = split_args();
-                split_ab(a, 0, h->gcl[0], t->AB);
-                a.upd = 0;                   // (the row maxima start from the zeros k_node_init left)
-                launch_node_split<3>(h, a, s);
-            } else if (fsplit) {
-                NodeSplitArgs a = split_args();
-                a.Wimg[0] = W + h->gcl[0].ab_img; a.bias[0] = W + h->gcl[0].ab_bias; a.ABout[0] = t->AB; a.upd = 0;
-                launch_node_split_f32<3>(h, a, s);
-            } else if (fused) {
-                NodeArgs a = node_args();
-                set_ab(a, 0, h->gcl[0], t->AB);
-                node_update(h, false, 1, a, s);
-            } else {
-                ab_r16(1, first, dst);
-            }
+            HD_TRY(node_step(nullptr, 1, first, dst));
         }
         for (int i = 0; i < c.n_layers; ++i) {
             for (int j = 0; j <= c.inv_sublayers; ++j) {
@@ -1722,7 +1450,7 @@ static int forward_impl(hd_handle* h, hd_topology* t, const float* xh, const flo
                 e.xcur = t->xcur; e.x0 = t->x0; e.part = coord ? t->xpart : t->part; e.ba = w.ba;
                 e.norm_constant = c.norm_constant; e.coords_range = range; e.attention = c.attention;
                 e.use_tanh = c.tanh; e.n_tiles = t->n_tiles; e.n_wg = t->n_wg;
-                HD_TRY(edge(h, coord, e, s));
+                HD_TRY(edge(h, coord, e, s, h->edge_mode));
                 if (!coord) {
                     // node update + the first edge Linear of the layer(s) that follow: AB of the next sub-layer, or (after the
                     // block's last GCL) of the coordinate layer and of the next block's first GCL
@@ -1735,44 +1463,7 @@ static int forward_impl(hd_handle* h, hd_topology* t, const float* xh, const flo
                         nxt[0] = &h->coord[i];
                         if (i + 1 < c.n_layers) { nxt[1] = &h->gcl[(size_t)(i + 1) * S]; nab = 2; }
                     }
-                    if (nsplit) {
-                        NodeSplitArgs a = split_args();
-                        a.w3l1 = w.w3l1; a.w4l1 = w.w4l1; a.b3max = w.b3max; a.b4max = w.b4max;
-                        NodeSplitArgs p1 = a, p2 = a, p3 = a;
-                        p1.Wimg[0] = W + w.w3_img; p1.bias[0] = W + w.b3; p1.winv[0] = 1.0f / w.w3s;
-                        launch_node_split<1>(h, p1, s);
-                        p2.Wimg[0] = W + w.w4_img; p2.bias[0] = W + w.b4; p2.winv[0] = 1.0f / w.w4s;
-                        p3.n_img = nab; p3.upd = 1;
-                        for (int q = 0; q < nab; ++q) { split_ab(p3, q, *nxt[q], dst[q]); p2.zero_max[q] = p3.ABmax[q]; }
-                        launch_node_split<2>(h, p2, s);
-                        launch_node_split<3>(h, p3, s);
-                    } else if (fsplit) {
-                        NodeSplitArgs p1 = split_args(), p2 = split_args(), p3 = split_args();
-                        p1.Wimg[0] = W + w.w3_img; p1.bias[0] = W + w.b3;
-                        launch_node_split_f32<1>(h, p1, s);
-                        p2.Wimg[0] = W + w.w4_img; p2.bias[0] = W + w.b4;
-                        launch_node_split_f32<2>(h, p2, s);
-                        p3.n_img = nab; p3.upd = 1;
-                        for (int q = 0; q < nab; ++q) { p3.Wimg[q] = W + nxt[q]->ab_img; p3.bias[q] = W + nxt[q]->ab_bias; p3.ABout[q] = dst[q]; }
-                        launch_node_split_f32<3>(h, p3, s);
-                    } else if (fused) {
-                        NodeArgs a = node_args();
-                        a.W3img = W + w.w3_img; a.b3 = W + w.b3; a.W4img = W + w.w4_img; a.b4 = W + w.b4;
-                        if (h->node_mode == 3) {
-                            a.w3inv = 1.0f / w.w3s; a.w4inv = 1.0f / w.w4s; a.w3l1 = w.w3l1; a.w4l1 = w.w4l1; a.b3max = w.b3max; a.b4max = w.b4max;
-                        }
-                        for (int q = 0; q < nab; ++q) set_ab(a, q, *nxt[q], dst[q]);
-                        node_update(h, true, nab, a, s);
-                    } else {
-                        R16Args g = r16_args();
-                        g.part = t->part; g.pstart = t->pstart; g.K1 = H; g.K = 2 * H; g.Nc = H;
-                        g.Bimg[0] = W + w.w3_gimg; g.bias[0] = W + w.b3; g.C[0] = t->Tb; g.ldc = H;
-                        gemm_r16(h, EPI_BIAS_SILU, true, g, s);                      // T = silu([h | agg] W3^T + b3)
-                        g = r16_args();
-                        g.A = t->Tb; g.Bimg[0] = W + w.w4_gimg; g.bias[0] = W + w.b4; g.C[0] = t->hbuf; g.ldc = H; g.Nc = H;
-                        gemm_r16(h, EPI_RESID_MASK, false, g, s);                    // h = (h + T W4^T + b4) mask
-                        ab_r16(nab, nxt, dst);
-                    }
+                    HD_TRY(node_step(&w, nab, nxt, dst));
                     ab_cur = t->AB;
                 } else {
                     ProfScope ps(h, s, 2);
@@ -1839,56 +1530,6 @@ extern "C" int hd_topology_nodes(const hd_topology* t, int* node_of) {
     return HD_OK;
 }
 
-template <int H>
-static int edge_bwd_lds_bytes() { return (2 * 32 * H + 4 * 288) * 4; }      // two weight chunks + per-wave scratch
-
-template <int H>
-static int prepare_edge_bwd_h() {
-    const int lds = edge_bwd_lds_bytes<H>();
-    HIP_TRY(hipFuncSetAttribute((const void*)k_edge_bwd<H, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_edge_bwd<H, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_edge_bwd<H, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_edge_bwd<H, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if constexpr (H >= 128) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_edge_bwd<H, false, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_edge_bwd<H, true, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    return HD_OK;
-}
-
-template <int H>
-static void launch_edge_bwd_h(bool coord, int stage, int prec, const EdgeBwdArgs& a, int n_wg, hipStream_t s) {
-    const dim3 grid(n_wg), block(256);
-    if (stage == 0 && a.pre2) {                     // pre2 kept by the forward pass: stage A loads it (one kernel for both arithmetics)
-        const int ldss = 4 * 288 * 4;
-        if (coord) hipLaunchKernelGGL((k_edge_bwd<H, true, 0, 0, true>), grid, block, ldss, s, a);
-        else hipLaunchKernelGGL((k_edge_bwd<H, false, 0, 0, true>), grid, block, ldss, s, a);
-        return;
-    }
-    if constexpr (H >= 128) {
-        if (prec == 3 && stage == 1) {              // fp16x3 contraction of stage B (16-wide chunks of 16 H floats)
-            const int lds = (2 * 16 * H + 4 * 288) * 4;
-            if (coord) hipLaunchKernelGGL((k_edge_bwd<H, true, 1, 3>), grid, block, lds, s, a);
-            else hipLaunchKernelGGL((k_edge_bwd<H, false, 1, 3>), grid, block, lds, s, a);
-            return;
-        }
-    }
-    const int lds = edge_bwd_lds_bytes<H>();
-    if (!coord && stage == 0) hipLaunchKernelGGL((k_edge_bwd<H, false, 0>), grid, block, lds, s, a);
-    else if (!coord) hipLaunchKernelGGL((k_edge_bwd<H, false, 1>), grid, block, lds, s, a);
-    else if (stage == 0) hipLaunchKernelGGL((k_edge_bwd<H, true, 0>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((k_edge_bwd<H, true, 1>), grid, block, lds, s, a);
-}
-
-static void launch_edge_bwd(hd_handle* h, bool coord, int stage, int prec, const EdgeBwdArgs& a, int n_wg, hipStream_t s) {
-    switch (h->H) {
-        case 32: launch_edge_bwd_h<32>(coord, stage, 0, a, n_wg, s); break;
-        case 64: launch_edge_bwd_h<64>(coord, stage, 0, a, n_wg, s); break;
-        case 128: launch_edge_bwd_h<128>(coord, stage, prec, a, n_wg, s); break;
-        default: launch_edge_bwd_h<256>(coord, stage, prec, a, n_wg, s); break;
-    }
-}
-
 static int check_train(hd_handle* h, hd_topology* t, const char* who) {
     if (!h || !t) return fail(HD_E_INVALID, std::string(who) + ": null handle/topology");
     if (t->h != h) return fail(HD_E_INVALID, std::string(who) + ": topology belongs to another handle");
@@ -1912,7 +1553,7 @@ extern "C" long long hd_edge_layer_save_rows(hd_handle* h, hd_topology* t, int p
     const int mode = h->H >= 128 ? precision : 0;
     // (the mix of whole and column-split tiles gains 2-5 % on a forward; the kept pre-activations save the backward a whole contraction:
     // only the pure column-split regime - B <= 18 at N = 30, where that forward is 2 x faster - keeps recomputing)
-    if (h->H >= 128 && edge_runs_split(h, t->n_tiles, mode)) return 0;
+    if (edge_family(h, t->n_tiles, mode) == EdgeFam::Split) return 0;
     return (long long)t->n_wg * 4 * 32 + 32;        // one tile more than the table has: the fp16x3 forward parks its image scalars there
 }
 
@@ -1955,7 +1596,8 @@ extern "C" int hd_edge_layer_forward_s(hd_handle* h, hd_topology* t, int coord, 
     e.norm_constant = c.norm_constant; e.coords_range = c.coords_range / (float)c.n_layers; e.attention = c.attention;
     e.use_tanh = c.tanh; e.n_tiles = t->n_tiles; e.n_wg = t->n_wg;
     e.pre2 = pre2;
-    HD_TRY(edge(h, coord != 0, e, s, f16 ? 3 : 0));
+    // the whole-tile forms of a training forward: on the unscaled parameters in fp16x3 arithmetic, keeping pre2 for the backward pass
+    HD_TRY(edge(h, coord != 0, e, s, f16 ? 3 : 0, (f16 ? HD_EDGE_UNSCALED : 0) | (pre2 ? HD_EDGE_SAVE : 0)));
     AggArgs ag;
     ag.part = coord ? t->xpart : t->part; ag.pstart = t->pstart; ag.agg = out; ag.norm = agg_norm(c, t);
     ag.M = M; ag.H = ow;
@@ -2030,9 +1672,9 @@ extern "C" int hd_edge_layer_backward_s(hd_handle* h, hd_topology* t, int coord,
     }
     const int prec = f16 ? 3 : 0;
     a.Wimg = t->w2img;
-    launch_edge_bwd(h, coord != 0, 0, prec, a, t->n_wg, s);
+    HD_TRY(launch(edge_bwd_kern(H, coord != 0, 0, prec, pre2 != nullptr), dim3(t->n_wg), dim3(256), a, s));
     a.Wimg = t->w2timg;
-    launch_edge_bwd(h, coord != 0, 1, prec, a, t->n_wg, s);
+    HD_TRY(launch(edge_bwd_kern(H, coord != 0, 1, prec, false), dim3(t->n_wg), dim3(256), a, s));
     CsrSumArgs cs;
     std::memset(&cs, 0, sizeof(cs));
     cs.G = G1; cs.out = dAB; cs.M = M; cs.H = H; cs.ldo = 2 * H;
@@ -2114,8 +1756,7 @@ extern "C" int hd_egcl_create(const hd_egcl_config* cfg, int device, hd_egcl** o
     g->NS = (H == 32) ? 1 : 2;
     g->n_weights = egcl_weight_count(*cfg);
     // k_node_split_f32 (the layer's node side at widths 128 / 256) needs more than 64 KB of dynamic LDS: raise the limit on this device
-    if (H == 128) { const int r = prepare_node_split_h<128>(); if (r != HD_OK) { delete g; return r; } }
-    if (H == 256) { const int r = prepare_node_split_h<256>(); if (r != HD_OK) { delete g; return r; } }
+    if (H >= 128) { const int r = prepare_node_split(H); if (r != HD_OK) { delete g; return r; } }
     *out = g;
     return HD_OK;
 }
@@ -2277,11 +1918,6 @@ extern "C" int hd_egcl_graph_create(hd_egcl* g, const int* row, const int* col, 
     return HD_OK;
 }
 
-static void egcl_gemm(hd_egcl* g, int epi, bool cat, const GemmArgs& a, hipStream_t s) {
-    if (g->NS == 1) launch_gemm<4, 1, 1>(epi, cat, a, s);
-    else launch_gemm<2, 2, 1>(epi, cat, a, s);
-}
-
 // What hd_egcl_forward_train keeps for the backward, in the caller's buffer (float offsets; row counts padded like the graph's
 // workspaces, so that every kernel that reads them sees the same extents as in the inference call).  The edge rows' pre-activations
 // come out of the forward GEMMs' epilogues on the way (the SiLU' of the backward needs them and SiLU cannot be inverted); the node
@@ -2370,18 +2006,18 @@ static int egcl_forward_impl(hd_egcl* g, hd_egcl_graph* t, const float* h, const
     if (nsplit) {
         NodeSplitArgs a = nsargs();
         a.Wimg[0] = W + g->ab_nimg; a.bias[0] = W + g->ab_bias; a.ABout[0] = t->AB; a.upd = 0;
-        if (H == 128) launch_node_split_f32_h<128, 3>(a, s); else launch_node_split_f32_h<256, 3>(a, s);
+        HD_TRY(launch_node_split(H, true, 3, a, s));
     } else {
-        egcl_gemm(g, EPI_BIAS, false, gemm_args(hsrc, H, H, H, nullptr, g->ab_img, g->ab_bias, t->AB, 2 * H, M, 2 * H, nullptr), s);
+        HD_TRY(launch_gemm(g->NS, EPI_BIAS, false, gemm_args(hsrc, H, H, H, nullptr, g->ab_img, g->ab_bias, t->AB, 2 * H, M, 2 * H, nullptr), s));
     }
     if (E > 0) {
         if (wide && direct) {
             GemmArgs p = gemm_args(edge_attr, H, H, H, nullptr, g->w1e_img, g->zero_bias, Pb, H, E, H, nullptr);
             p.erow = t->row; p.ecol = t->col; p.ABn = t->AB; p.xn = xsrc; p.xs = xs; p.geo = geob; p.geo_mode = c.geo; p.colv = W + g->w_r;
             p.pre = sv(SL.pre1);
-            egcl_gemm(g, EPI_EGCL_PRE, false, p, s);
+            HD_TRY(launch_gemm(g->NS, EPI_EGCL_PRE, false, p, s));
         } else if (wide) {
-            egcl_gemm(g, EPI_BIAS, false, gemm_args(edge_attr, H, H, H, nullptr, g->w1e_img, g->zero_bias, t->T1, H, E, H, nullptr), s);
+            HD_TRY(launch_gemm(g->NS, EPI_BIAS, false, gemm_args(edge_attr, H, H, H, nullptr, g->w1e_img, g->zero_bias, t->T1, H, E, H, nullptr), s));
         }
         if (!(wide && direct)) {
             EgclPreArgs a;
@@ -2393,7 +2029,7 @@ static int egcl_forward_impl(hd_egcl* g, hd_egcl_graph* t, const float* h, const
         {
             GemmArgs m2 = gemm_args(Pb, H, H, H, nullptr, g->w2_img, g->b2, M1b, H, E, H, nullptr);
             m2.pre = sv(SL.pre2);
-            egcl_gemm(g, EPI_BIAS_SILU, false, m2, s);
+            HD_TRY(launch_gemm(g->NS, EPI_BIAS_SILU, false, m2, s));
         }
         {   // edge_feat = M (* att) * edge_mask, in place
             EgclRowArgs a;
@@ -2404,7 +2040,7 @@ static int egcl_forward_impl(hd_egcl* g, hd_egcl_graph* t, const float* h, const
         if (c.coord_update) {
             GemmArgs c1 = gemm_args(M1b, H, H, H, nullptr, g->wc1_img, g->bc1, C1b, H, E, H, nullptr);
             c1.pre = sv(SL.pc);
-            egcl_gemm(g, EPI_BIAS_SILU, false, c1, s);
+            HD_TRY(launch_gemm(g->NS, EPI_BIAS_SILU, false, c1, s));
             EgclRowArgs a;
             std::memset(&a, 0, sizeof(a));
             a.X = C1b; a.w = W + g->wc2; a.emask = edge_mask; a.geo = geob; a.trans = t->trans; a.range = c.coords_range;
@@ -2427,17 +2063,17 @@ static int egcl_forward_impl(hd_egcl* g, hd_egcl_graph* t, const float* h, const
         NodeSplitArgs p1 = nsargs(), p2 = nsargs();
         p1.Wimg[0] = W + g->wn1_nimg; p1.bias[0] = W + g->bn1; p1.agg_dense = aggb;
         p2.Wimg[0] = W + g->wn2_nimg; p2.bias[0] = W + g->bn2; p2.resid_none = c.recurrent ? 0 : 1;
-        if (H == 128) { launch_node_split_f32_h<128, 1>(p1, s); launch_node_split_f32_h<128, 2>(p2, s); }
-        else { launch_node_split_f32_h<256, 1>(p1, s); launch_node_split_f32_h<256, 2>(p2, s); }
+        HD_TRY(launch_node_split(H, true, 1, p1, s));
+        HD_TRY(launch_node_split(H, true, 2, p2, s));
     } else {
-    egcl_gemm(g, EPI_BIAS_SILU, true, gemm_args(hsrc, H, H, 2 * H, aggb, g->wn1_img, g->bn1, t->Tn, H, M, H, nullptr), s);
+    HD_TRY(launch_gemm(g->NS, EPI_BIAS_SILU, true, gemm_args(hsrc, H, H, 2 * H, aggb, g->wn1_img, g->bn1, t->Tn, H, M, H, nullptr), s));
     if (direct) {
         GemmArgs n2 = gemm_args(t->Tn, H, H, H, nullptr, g->wn2_img, g->bn2, h_out, H, M, H, nm);
         n2.resid = h; n2.ldr = H; n2.resid_none = c.recurrent ? 0 : 1;
-        egcl_gemm(g, EPI_RESID_MASK, false, n2, s);
+        HD_TRY(launch_gemm(g->NS, EPI_RESID_MASK, false, n2, s));
     } else {
         if (!c.recurrent) HIP_TRY(hipMemsetAsync(t->hres, 0, (size_t)t->Mp * H * sizeof(float), s));
-        egcl_gemm(g, EPI_RESID_MASK, false, gemm_args(t->Tn, H, H, H, nullptr, g->wn2_img, g->bn2, t->hres, H, M, H, nm), s);
+        HD_TRY(launch_gemm(g->NS, EPI_RESID_MASK, false, gemm_args(t->Tn, H, H, H, nullptr, g->wn2_img, g->bn2, t->hres, H, M, H, nm), s));
     }
     }
     if (c.edge_update && E > 0) {
@@ -2446,9 +2082,9 @@ static int egcl_forward_impl(hd_egcl* g, hd_egcl_graph* t, const float* h, const
         // tensor - rows >= E are never stored: four stream operations less per layer, same expressions element by element)
         GemmArgs e1 = gemm_args(M1b, H, H, 2 * H, edge_attr, g->we1_img, g->be1, E1b, H, E, H, nullptr);
         e1.rowv = geob + 3; e1.rowv_stride = 4; e1.colv = W + g->w_er; e1.pre = sv(SL.pe);
-        egcl_gemm(g, EPI_RANK1_SILU, true, e1, s);
-        egcl_gemm(g, edge_mask ? EPI_BIAS_MASK : EPI_BIAS, false,
-                  gemm_args(E1b, H, H, H, nullptr, g->we2_img, g->be2, edge_attr_out, H, E, H, edge_mask), s);
+        HD_TRY(launch_gemm(g->NS, EPI_RANK1_SILU, true, e1, s));
+        HD_TRY(launch_gemm(g->NS, edge_mask ? EPI_BIAS_MASK : EPI_BIAS, false,
+                  gemm_args(E1b, H, H, H, nullptr, g->we2_img, g->be2, edge_attr_out, H, E, H, edge_mask), s));
     }
     if (!direct) {
         EgclNodeOutArgs a;
@@ -2539,10 +2175,7 @@ extern "C" int hd_gemm_f32(int device, int M, int N, int K, const float* A, long
     if (!splitting && (long long)grid.x * grid.y < 128 && K >= 32 && K <= 1024) {
         g.colsum = colsum;
         const dim3 sg((M + 31) / 32, (N + 31) / 32);
-        if (a_kc && b_kc) hipLaunchKernelGGL((k_tgemm_small<true, true>), sg, block, 0, s, g);
-        else if (a_kc) hipLaunchKernelGGL((k_tgemm_small<true, false>), sg, block, 0, s, g);
-        else if (b_kc) hipLaunchKernelGGL((k_tgemm_small<false, true>), sg, block, 0, s, g);
-        else hipLaunchKernelGGL((k_tgemm_small<false, false>), sg, block, 0, s, g);
+        HD_TRY(launch(tgemm_small_kern(a_kc, b_kc), sg, block, g, s));
         HIP_TRY(hipGetLastError());
         return HD_OK;
     }
@@ -2552,14 +2185,7 @@ extern "C" int hd_gemm_f32(int device, int M, int N, int K, const float* A, long
     }
     // FAST: full tiles, whole K chunks per slab, 16-byte aligned rows - no bounds checks, no branches around the loads
     const bool fast = g.avec && g.bvec && M % TG_BM == 0 && N % TG_BN == 0 && K % TG_BK == 0 && K > 0;
-    auto launch = [&](auto Fast) {
-        constexpr bool F = decltype(Fast)::value;
-        if (a_kc && b_kc) hipLaunchKernelGGL((k_tgemm<true, true, F>), grid, block, 0, s, g);
-        else if (a_kc) hipLaunchKernelGGL((k_tgemm<true, false, F>), grid, block, 0, s, g);
-        else if (b_kc) hipLaunchKernelGGL((k_tgemm<false, true, F>), grid, block, 0, s, g);
-        else hipLaunchKernelGGL((k_tgemm<false, false, F>), grid, block, 0, s, g);
-    };
-    if (fast) launch(std::true_type{}); else launch(std::false_type{});
+    HD_TRY(launch(tgemm_kern(a_kc, b_kc, fast), grid, block, g, s));
     if (splitting) {
         TGemmReduceArgs r;
         r.ws = ws; r.colsum_ws = g.colsum_ws; r.bias = bias; r.C = C; r.colsum = colsum; r.M = M; r.N = N; r.ldc = ldc; r.nz = split_k;
@@ -2593,13 +2219,11 @@ extern "C" int hd_dw2_f16(int device, int rows, int H, const float* G2, const fl
         std::lock_guard<std::mutex> lk(mu);
         const unsigned long long bit = 1ull << (device & 63);
         if (!(prepared_mask & bit)) {
-            HIP_TRY(hipFuncSetAttribute((const void*)k_dw2_f16<256>, hipFuncAttributeMaxDynamicSharedMemorySize, dw2_f16_lds_bytes<256>()));
-            HIP_TRY(hipFuncSetAttribute((const void*)k_dw2_f16<128>, hipFuncAttributeMaxDynamicSharedMemorySize, dw2_f16_lds_bytes<128>()));
+            for (const int width : {256, 128}) HD_TRY(prepare(dw2_f16_kern(width)));
             prepared_mask |= bit;
         }
     }
-    if (H == 256) hipLaunchKernelGGL((k_dw2_f16<256>), dim3(slabs), dim3(512), dw2_f16_lds_bytes<256>(), s, a);
-    else hipLaunchKernelGGL((k_dw2_f16<128>), dim3(slabs), dim3(512), dw2_f16_lds_bytes<128>(), s, a);
+    HD_TRY(launch(dw2_f16_kern(H), dim3(slabs), dim3(512), a, s));
     hipLaunchKernelGGL(k_dw2_reduce, dim3((H * H + 255) / 256), dim3(256), 0, s, ws, dW2, H * H, H, ldc, slabs);
     HIP_TRY(hipGetLastError());
     return HD_OK;

@@ -68,7 +68,7 @@ constexpr float HD_NEG_LOG2E = -1.4426950408889634f;
 // SiLU and the gate dot.  The packed instructions are IEEE per element and every value sees the operations of the scalar form in
 // the same order, so the bits are the same; beside the fp32 MFMA (which occupies the same datapath either way) a packed
 // instruction costs about 1.1 x a scalar one, i.e. 0.55 x per value.  v_exp_f32 / v_rcp_f32 have no packed form.  Only the plain
-// k_edge<H, *, 0> launch of launch_edge_h selects it (H >= 256); k_edge_mixed, k_edge_split, the training forward and fp16x3
+// k_edge<H, *, 0> launch selects it (edge_plain_form, launch.hpp: H >= 256); k_edge_mixed, k_edge_split, the training forward and fp16x3
 // keep the scalar code.  EXPERIMENTS.md section AN.
 constexpr int HD_EDGE_PACKED = 2048;
 // the widths whose plain fp32 launch runs the packed form (-DHD_EDGE_NO_PACKED: none, the scalar kernel of a measurement build)

@@ -8,7 +8,7 @@
 // The 32-row k_node_f32 amortises the same stream over twice the rows, the GEMM chain spreads it over 120-480 workgroups.
 // What the kernel would need is the weight stream staged through LDS by LDS-DMA (k_edge's scheme) or shared by a cluster
 // of workgroups.  Kept for its verified 16 x 16 x 4 operand mapping (Mma16).
-// To try it again: append to csrc/k_node.hpp, launch from launch_node_hw for mode 0 / upd / small M with
+// To try it again: append to csrc/k_node.hpp, launch from node_kern (launch.hpp) for mode 0 / upd / small M with
 // grid (M + 15) / 16, block 64 * (H / 32), and produce the first layer's AB with the plain GEMM.
 #pragma once
 

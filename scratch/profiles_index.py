@@ -24,7 +24,7 @@ RULES = [
     (r"r\d+_gamma_spread_.*\.txt", "spread of the learned schedule evaluated in fp32 across hosts / thread counts", "DESIGN 2 'schedule is not reproducible in fp32'"),
     (r"r\d+_small_batch.*\.log", "per-kernel averages of the forward at B = 64 / 16 / 2 in every mode", "DESIGN 4 small-batch paragraphs; r05: 12b"),
     (r"r\d+_r16_sweep.*\.log|r02_gemm16_experiment\.log|r02_direct_sweep\.log", "fp32 node chain at small batches: k_gemm_r16 vs the older chain, ms per forward by batch", "DESIGN 4 k_gemm_r16"),
-    (r"r\d+_mix_sweep.*\.log|r02_split_sweep\.log", "k_edge_mixed / k_edge_split break-even sweeps", "DESIGN 4 k_edge_mixed, launch_edge_h rule"),
+    (r"r\d+_mix_sweep.*\.log|r02_split_sweep\.log", "k_edge_mixed / k_edge_split break-even sweeps", "DESIGN 4 k_edge_mixed, edge_family rule (launch.hpp)"),
     (r"r03_edge_valu_variants\.log", "packed-fp32 / LDS-handover variants of the fp32 edge kernel (rejected)", "DESIGN 4"),
     (r"r03_node_phase_trace\.log|r04_node_first_loads_reorder_ab\.log", "phase stamps of k_node_f32 / a reorder A-B (null)", "DESIGN 4 k_node_f32, 12a"),
     (r"r03_power_clock\.log", "rocm-smi clock / power during sustained forwards", "DESIGN 4 (power-limited clock)"),
@@ -77,6 +77,8 @@ RULES = [
     (r"r06_ab_gemm_rows\.log", "same-box A/B of the node-level training GEMMs: k_tgemm vs the row-resident k_tgemm_rows (slower; removed)", "EXPERIMENTS V"),
     (r"r06_ab_dw2_two_chunks\.log", "same-box A/B of k_dw2_f16 with one vs two chunks in flight (slower; reverted)", "EXPERIMENTS V"),
     (r"sampling_bits_(parent|result)\.json", "`scratch/sampling_bits.py`: SHA-256 of what every Python sampling entry point returns over the option matrix of tests/make_golden_dispatch.py, before / after the plan / state / run / decode split; the two files are identical", "DESIGN 5a, EXPERIMENTS AE"),
+    (r"launch_selectors_trace_diff\.txt", "`scratch/launch_trace_driver.py` under `rocprofv3 --kernel-trace` with the parent's (c749001) and the result's library, one MI355X, one call, compared per dispatch by `scratch/launch_trace_diff.py` (kernel name, grid, workgroup size, LDS size, in dispatch order): the driver's result checksums, the statement that the diff is empty, dispatches and distinct launch shapes per kernel name", "DESIGN 4 (which instantiation a launch runs), EXPERIMENTS AS"),
+    (r"launch_selectors_bench\.json", "`bench.py --gpus 1 --steps 2 --warmup 1 --full --no-cpu-baseline`, eager and `--graph`, the parent's (c749001) and the result's library alternating on one MI355X in one call, reduced by `scratch/bench_ab_compare.py`: every figure of the JSON lines per run and whether the result's values lie within the range of the parent's own repeats", "EXPERIMENTS AS"),
     (r"r06_.*", "round-6 measurement", "DESIGN 0a"),
 ]
 def commit(path):
