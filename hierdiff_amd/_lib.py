@@ -96,6 +96,11 @@ SIGNATURES = {
     "hd_steer_detach": (C.c_int, [_VP]),
     "hd_steer_step": (C.c_int, [_VP, _VP, _FP, _FP, C.POINTER(C.c_float), C.c_uint32, C.c_uint64, C.c_uint64, _VP]),
     "hd_steer_read": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "hd_set_diversity": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_float)]),
+    "hd_diversity_attach": (C.c_int, [_VP, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_float), C.c_int, C.c_float, _VP]),
+    "hd_diversity_detach": (C.c_int, [_VP]),
+    "hd_diverse_eps": (C.c_int, [_VP, _VP, _FP, _FP, C.POINTER(C.c_float), _FP, _VP]),
+    "hd_diversity_energy": (C.c_int, [_VP, _VP, _FP, _VP, _VP, _VP]),
     "hd_philox_uniform_host": (C.c_double, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]),
     "hd_diffuse": (C.c_int, [_VP, _VP, _FP, C.c_float, C.c_float, _FP, _FP, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int,
                              _FP, _VP]),

@@ -69,6 +69,7 @@ struct PathTables {
     bool up = false;                 // the path ascends (hd_set_path_up: t_idx[k] < s_idx[k], linear rows with c == 0)
     std::vector<int> t_h, s_h;
     std::vector<float> c2_h;         // forms 2 and 3: c2 of every row (which transitions read the history)
+    std::vector<unsigned char> noisy_h;   // 1: the row draws noise (form 0 always, forms 1 and 3 with c != 0, form 2 never)
     int *d_t = nullptr, *d_s = nullptr;
     float *d_coef = nullptr, *d_coef_ip = nullptr;   // [K][width of the form], [K][4]; d_coef_ip null when no inpainting rows were given
     unsigned long long sched_gen = 0, gen = 0;       // sched_gen the tables were set for (0: not set); bumped by every rewrite
@@ -133,6 +134,7 @@ struct hd_handle {
     // restraints (hd_set_restraint): the rows {alpha_t, sigma_t, lambda_k, clip_k} of every transition of the current path; steering
     // (hd_set_steer): the rows {alpha_t, sigma_t, beta_k}
     RowTable rs_rows, st_rows;  // [K][4], [K][3]
+    RowTable dv_rows;           // diversity (hd_set_diversity): [K][4], the row format of rs_rows
     // scoring (hd_set_nll_terms / hd_nll_terms / hd_nll_finish): K terms t_idx[k] of the bound, rows {alpha_t, sigma_t, w_t, 0}
     int nll_K;
     std::vector<int> nll_t_h;
@@ -188,13 +190,16 @@ struct PathKey {
     int st_P;                                                // steered transition: particles per group, rho, the topology's steering
     double st_ess;                                           // buffers, the handle's rows (all 0: not steered)
     unsigned long long st_gen, st_rows_gen;
+    int dv_P;                                                // diverse transition: rows per group, the topology's diversity state,
+    unsigned long long dv_gen, dv_rows_gen;                  // the handle's rows (all 0: none attached)
     bool operator==(const PathKey& o) const {
         return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape &&
                noise_rows == o.noise_rows && k_lo == o.k_lo && resamplings == o.resamplings &&
                w_rows == o.w_rows && phi == o.phi && seed == o.seed &&
                weights_gen == o.weights_gen && sched_gen == o.sched_gen && path_gen == o.path_gen &&
                ip_gen == o.ip_gen && ip_parts == o.ip_parts && rs == o.rs &&
-               st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen && st_rows_gen == o.st_rows_gen;
+               st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen && st_rows_gen == o.st_rows_gen &&
+               dv_P == o.dv_P && dv_gen == o.dv_gen && dv_rows_gen == o.dv_rows_gen;
     }
 };
 
@@ -338,6 +343,16 @@ struct hd_topology {
     int* st_i32;                               // root [B], anc [B]
     float* st_scratch;                         // [3][B][N][D]
     unsigned long long st_gen;
+    // hd_diversity_attach: the rows of a group repel by aligned RMSD (k_diverse.hpp).  The per-group scales and the scratch of
+    // k_diverse_eps are allocated by the first attach at addresses captured transitions keep; dv_gen moves when something a captured
+    // launch bakes in does (P, scale_rows, kappa, length, nv0, an address).  No state crosses transitions.
+    bool dv_on;
+    int dv_P, dv_scale_rows;
+    double dv_kappa, dv_length;
+    float dv_nv0;
+    DevTable<float> dv_scale;
+    double* dv_step;                           // [B][N][3]
+    unsigned long long dv_gen;
     // multistep paths (hd_set_path_multistep): the previous transition's data prediction x^ [B][N][D], allocated by the first
     // form-2 call at an address the captured transitions keep; host-side, which path generation and position it belongs to
     float* ms_hist;
@@ -516,6 +531,7 @@ extern "C" int hd_destroy(hd_handle* h) {
     hipFree(h->d_chain_frame); hipFree(h->d_chain_as); hipFree(h->d_chain_dst);
     hipFree(h->rs_rows.d);
     hipFree(h->st_rows.d);
+    hipFree(h->dv_rows.d);
     hipFree(h->d_nll_t); hipFree(h->d_nll_coef);
 #ifdef HD_DEBUG_KERNELS
     hipFree(h->d_trace);
@@ -911,7 +927,7 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     if (t->guide_mem) (void)hipFree(t->guide_mem);
     if (t->ms_hist) (void)hipFree(t->ms_hist);
     restraint_free(t->rs);
-    for (void* p : {(void*)t->st_f64, (void*)t->st_i32, (void*)t->st_scratch})
+    for (void* p : {(void*)t->st_f64, (void*)t->st_i32, (void*)t->st_scratch, (void*)t->dv_scale.p, (void*)t->dv_step})
         if (p) (void)hipFree(p);
     if (t->ip_fixed) (void)hipFree(t->ip_fixed);
     if (t->ip_known) (void)hipFree(t->ip_known);

@@ -174,6 +174,8 @@ static int set_path_tables(hd_handle* h, PathTables& pt, int K, const int* t_idx
         pt.c2_h.resize((size_t)K);
         for (int k = 0; k < K; ++k) pt.c2_h[(size_t)k] = rows[row_width * k + step_row_c2(form)];
     }
+    pt.noisy_h.resize((size_t)K);
+    for (int k = 0; k < K; ++k) pt.noisy_h[(size_t)k] = form == 0 || (form != 2 && rows[row_width * k + 2] != 0.f);   // k_post_step's `noisy`
     HD_TRY(dev_upload(&pt.d_t, pt.t_h));
     HD_TRY(dev_upload(&pt.d_s, pt.s_h));
     HD_TRY(dev_upload(&pt.d_coef, std::vector<float>(rows, rows + row_width * K)));
@@ -1048,6 +1050,103 @@ extern "C" int hd_steer_read(hd_topology* topo, double* logw, double* uprev, int
     return HD_OK;
 }
 
+// ----------------------------------------------------------------------------- diversity: rows of a group repel by aligned RMSD
+
+extern "C" int hd_set_diversity(hd_handle* h, int K, const float* rows4) {
+    HD_TRY(row_table_check("hd_set_diversity", h, K, rows4, 4, restraint_row_ok,
+                           ": need alpha_t > 0, sigma_t >= 0, a finite lambda_k and clip_k > 0 (inf: no clip)"));
+    return set_row_table(h, h->dv_rows, K, rows4, 4);
+}
+
+// dynamic LDS of k_diverse_eps: x^0 of a group's rows, then - 8-byte aligned - the pair records
+static size_t diverse_lds(int P, int N) {
+    return (((size_t)P * N * 3 + 1) / 2 + (size_t)P * (P - 1) / 2 * DV_REC) * sizeof(double);
+}
+
+extern "C" int hd_diversity_attach(hd_topology* topo, int P, double kappa, double length, const float* scale, int scale_rows, float nv0,
+                                   void* stream) {
+    const char* who = "hd_diversity_attach";
+    if (!topo) return refuse(HD_E_INVALID, who, ": null topology");
+    if (P < 2 || P > DV_MAX_P) return refuse(HD_E_INVALID, who, ": need 2 <= P <= 32 rows per group");
+    if (topo->B % P != 0) return refuse(HD_E_INVALID, who, ": the topology's B is not a multiple of P");
+    if (!scale) return refuse(HD_E_INVALID, who, ": null scale");
+    if (scale_rows != 1 && scale_rows != topo->B / P) return refuse(HD_E_INVALID, who, ": scale has 1 row (shared) or B / P rows");
+    if (!(kappa >= 0.0) || !(kappa - kappa == 0.0)) return refuse(HD_E_INVALID, who, ": kappa must be >= 0 and finite");
+    if (!(length > 0.0) || !(length - length == 0.0)) return refuse(HD_E_INVALID, who, ": length must be positive and finite");
+    if (!(nv0 > 0.f) || !(nv0 - nv0 == 0.f)) return refuse(HD_E_INVALID, who, ": nv0 must be positive and finite");
+    for (int r = 0; r < scale_rows; ++r)
+        if (!(scale[r] - scale[r] == 0.f)) return refuse(HD_E_INVALID, who, ": every scale must be finite");
+    // the static LDS of k_diverse_eps is DV_MAX_P * 3 doubles
+    if (diverse_lds(P, topo->N) + (size_t)DV_MAX_P * 3 * sizeof(double) > 64 * 1024)
+        return refuse(HD_E_INVALID, who, ": P * N * 3 floats and P (P - 1) / 2 pair records exceed one workgroup's LDS");
+    HIP_TRY(hipSetDevice(topo->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    topo->dv_on = false;
+    bool moved = false;
+    if (!topo->dv_step) { HD_TRY(dev_alloc(&topo->dv_step, (size_t)topo->B * topo->N * 3)); moved = true; }
+    // (a host array: a pageable source is staged before the call returns)
+    HD_TRY(topo->dv_scale.fill(scale, (size_t)scale_rows, &moved, s));
+    restraint_bake({{&topo->dv_P, P}, {&topo->dv_scale_rows, scale_rows}},
+                   moved || kappa != topo->dv_kappa || length != topo->dv_length || nv0 != topo->dv_nv0, &topo->dv_gen);
+    topo->dv_kappa = kappa; topo->dv_length = length; topo->dv_nv0 = nv0;
+    topo->dv_on = true;
+    return HD_OK;
+}
+
+extern "C" int hd_diversity_detach(hd_topology* topo) {
+    if (topo) topo->dv_on = false;
+    return HD_OK;
+}
+
+// The diversity update of one transition on eps (in place when out == eps): the row read as restrain_launch reads it.
+static int diverse_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* z, const float* eps, float* out,
+                          const float* rows, const float* row4) {
+    ProfScope ps(h, io.s, 2);
+    DiverseArgs a;
+    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.scale = t->dv_scale.p; a.rows = rows;
+    for (int i = 0; i < 4; ++i) a.row[i] = row4 ? row4[i] : 0.f;
+    a.step_ptr = io.step; a.k = io.row; a.step = t->dv_step; a.kappa = t->dv_kappa; a.inv_l2 = 1.0 / (t->dv_length * t->dv_length);
+    a.nv0 = t->dv_nv0; a.scale_rows = t->dv_scale_rows; a.P = t->dv_P; a.B = t->B; a.N = t->N; a.D = h->D;
+    hipLaunchKernelGGL(k_diverse_eps, dim3(t->B / t->dv_P), dim3(256), diverse_lds(t->dv_P, t->N), io.s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_diverse_eps(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4, float* out,
+                              void* stream) {
+    const char* who = "hd_diverse_eps";
+    if (!h || !topo) return refuse(HD_E_INVALID, who, ": null handle/topology");
+    if (!z || !eps || !row4 || !out) return refuse(HD_E_INVALID, who, ": null tensor / row");
+    if (!topo->dv_on) return refuse(HD_E_STATE, who, ": no diversity attached to the topology (hd_diversity_attach)");
+    if (!restraint_row_ok(row4)) return refuse(HD_E_INVALID, who, ": need alpha_t > 0, sigma_t >= 0, a finite lambda and clip > 0 (inf: no clip)");
+    const size_t per = (size_t)topo->B * topo->N * h->D;
+    if (out < z + per && z < out + per) return refuse(HD_E_INVALID, who, ": out may not overlap z");
+    if (out != eps && out < eps + per && eps < out + per) return refuse(HD_E_INVALID, who, ": out may be eps itself, not a shifted overlap of it");
+    HIP_TRY(hipSetDevice(h->device));
+    LoopIO io{};
+    io.s = (hipStream_t)stream;
+    topo_use(topo, io.s);
+    return diverse_launch(h, topo, io, z, eps, out, nullptr, row4);
+}
+
+extern "C" int hd_diversity_energy(hd_handle* h, hd_topology* topo, const float* x, double* phi, double* rmsd, void* stream) {
+    const char* who = "hd_diversity_energy";
+    if (!h || !topo) return refuse(HD_E_INVALID, who, ": null handle/topology");
+    if (!x || !phi) return refuse(HD_E_INVALID, who, ": null tensor");
+    if (!topo->dv_on) return refuse(HD_E_STATE, who, ": no diversity attached to the topology (hd_diversity_attach)");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    ProfScope ps(h, s, 2);
+    DiverseEnergyArgs a;
+    a.x = x; a.nm = topo->nm_bytes; a.phi = phi; a.rmsd = rmsd; a.kappa = topo->dv_kappa;
+    a.inv_l2 = 1.0 / (topo->dv_length * topo->dv_length); a.P = topo->dv_P; a.B = topo->B; a.N = topo->N;
+    hipLaunchKernelGGL(k_diverse_energy, dim3(topo->B / topo->dv_P), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
 // Classifier-free guidance of a path loop: every network call becomes two (context, then ctx_u) and k_guide_combine in place.
 struct GuideSrc {
     const float* ctx_u;   // [B,N,C] the null (or any second) context
@@ -1159,6 +1258,20 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
                                                  "(duplicated particles would never diverge: hd_steer_detach)");
         if (c.noise_rows != topo->B) return fail(HD_E_INVALID, "path loop: steering needs every row's own noise (noise_rows must be B)");
     }
+    const bool dvn = c.record && topo->dv_on;
+    if (dvn) {
+        if (R) return fail(HD_E_INVALID, "path loop: diversity is attached to the topology, and inpainting takes none (hd_diversity_detach)");
+        if (mol != N) return fail(HD_E_INVALID, "path loop: diversity acts on whole molecules only (mol_shape < N)");
+        if (topo->st_on) return fail(HD_E_INVALID, "path loop: diversity and steering are both attached to the topology: a call takes one "
+                                                   "of them (hd_steer_detach / hd_diversity_detach)");
+        if (!h->dv_rows.d || h->dv_rows.path_gen != pt.gen)
+            return fail(HD_E_STATE, "path loop: diversity is attached but its rows are not set for the current path (hd_set_diversity)");
+        if (c.noise_rows == 1)
+            for (int k = k_lo; k < c.k_hi; ++k)
+                if (pt.noisy_h[(size_t)k])
+                    return fail(HD_E_INVALID, "path loop: diversity with one shared row of noise is allowed only on rows that draw nothing "
+                                              "(noise_rows must be B on a stochastic path)");
+    }
     const uint8_t* parts = (R && topo->ip_parts_on) ? topo->ip_parts : nullptr;      // calls that do not inpaint ignore the attachment
     const int rounds = R ? R : 1;
     auto transition = [&](const LoopIO& io) -> int {         // all rounds of one transition; io.row is the path position
@@ -1170,6 +1283,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
             }
             if (rsn) HD_TRY(restrain_launch(h, topo, io, io.z, topo->eps, topo->eps, h->rs_rows.d, nullptr, framed));
             if (rsn && topo->rs.feat) HD_TRY(restrain_feat_launch(h, topo, io, io.z, topo->eps, topo->eps, h->rs_rows.d, nullptr));
+            if (dvn) HD_TRY(diverse_launch(h, topo, io, io.z, topo->eps, topo->eps, h->dv_rows.d, nullptr));
             if (stn) HD_TRY(steer_launch(h, topo, io, io.z, topo->eps, h->st_rows.d, nullptr, io.draw_of(0, stride), c.seed,
                                          form == 3 ? topo->ms_hist : nullptr));
             if (rec && j == rounds - 1 && topo->chain_what == 1) HD_TRY(chain_launch(h, topo, io, topo->eps));
@@ -1212,6 +1326,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     key.ip_parts = parts ? 1 : 0;
     key.st_P = stn ? topo->st_P : 0; key.st_ess = stn ? topo->st_ess : 0.0; key.st_gen = stn ? topo->st_gen : 0;
     key.st_rows_gen = stn ? h->st_rows.gen : 0;
+    key.dv_P = dvn ? topo->dv_P : 0; key.dv_gen = dvn ? topo->dv_gen : 0; key.dv_rows_gen = dvn ? h->dv_rows.gen : 0;
     PathWords w;
     w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = R ? h->d_ipdraw : nullptr;
     w.tau = h->d_tau; w.t_idx = pt.d_t; w.s_idx = pt.d_s; w.K = K; w.T = T; w.nd = nd; w.stride = stride; w.chain = rec ? h->d_chain_dst : nullptr;

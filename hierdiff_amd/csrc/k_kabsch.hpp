@@ -44,8 +44,8 @@ HD_DEVINL void kb_rotate(double (&A)[4][4], double (&V)[4][4]) {
     }
 }
 
-// S row-major [3][3] (S[3 a + b] = sum w x'_a y'_b) -> R row-major [3][3].
-HD_DEVINL void kabsch_rotation(const double (&S)[9], double (&R)[9]) {
+// S row-major [3][3] (S[3 a + b] = sum w x'_a y'_b) -> the unit quaternion q of R (k_diverse.hpp keeps q per pair and rebuilds R).
+HD_DEVINL void kabsch_quaternion(const double (&S)[9], double (&q)[4]) {
     const double xx = S[0], xy = S[1], xz = S[2], yx = S[3], yy = S[4], yz = S[5], zx = S[6], zy = S[7], zz = S[8];
     double A[4][4], V[4][4];
     A[0][0] = xx + yy + zz; A[0][1] = zy - yz;      A[0][2] = xz - zx;       A[0][3] = yx - xy;
@@ -74,8 +74,20 @@ HD_DEVINL void kabsch_rotation(const double (&S)[9], double (&R)[9]) {
     double q2 = ((m0 * V[2][0] + m1 * V[2][1]) + m2 * V[2][2]) + m3 * V[2][3];
     double q3 = ((m0 * V[3][0] + m1 * V[3][1]) + m2 * V[3][2]) + m3 * V[3][3];
     const double n = 1.0 / sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
-    q0 *= n; q1 *= n; q2 *= n; q3 *= n;
+    q[0] = q0 * n; q[1] = q1 * n; q[2] = q2 * n; q[3] = q3 * n;
+}
+
+// The rotation matrix (row-major) of the unit quaternion q.
+HD_DEVINL void kb_quat_matrix(const double (&q)[4], double (&R)[9]) {
+    const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
     R[0] = q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3; R[1] = 2.0 * (q1 * q2 - q0 * q3); R[2] = 2.0 * (q1 * q3 + q0 * q2);
     R[3] = 2.0 * (q1 * q2 + q0 * q3); R[4] = q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3; R[5] = 2.0 * (q2 * q3 - q0 * q1);
     R[6] = 2.0 * (q1 * q3 - q0 * q2); R[7] = 2.0 * (q2 * q3 + q0 * q1); R[8] = q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3;
+}
+
+// S row-major [3][3] (S[3 a + b] = sum w x'_a y'_b) -> R row-major [3][3].
+HD_DEVINL void kabsch_rotation(const double (&S)[9], double (&R)[9]) {
+    double q[4];
+    kabsch_quaternion(S, q);
+    kb_quat_matrix(q, R);
 }

@@ -214,6 +214,10 @@ class DiffusionQM9(_Base):
         self.steer_scale = None
         self.steer_ess = None
         self.steer_last = None
+        # diverse sampling (hierdiff_amd/diversity.py): the default of the `diversity` keyword (a `diversity.Diversity`; None, particles
+        # = 1, or a strength or scale of 0 = nothing changes).  `diversity_last`: the `diversity.Result` of the last diverse call.
+        self.diversity = None
+        self.diversity_last = None
 
     def check_issues_norm_values(self, num_stdevs=8):
         """diffusion_qm9.py:117-131 (predefined schedules only)."""
@@ -633,6 +637,11 @@ class DiffusionQM9(_Base):
         if pl.steer is not None and fix_noise:
             raise ValueError(f"{what}: steering needs every row's own noise (fix_noise shares one row: duplicated particles would "
                              "never diverge)")
+        if pl.diversity is not None and fix_noise:
+            from . import diversity
+            if diversity.stochastic(pl.eta):
+                raise ValueError(f"{what}: diversity with fix_noise is allowed only on a path that draws nothing (eta = 0, solver "
+                                 "'dpm2m'): shared noise would pull the rows of a group together again")
         return pl
 
     def _resolve_path(self, steps=None, eta=None, spacing=None, timesteps=None, inpaint: bool = False, solver=None,
@@ -750,6 +759,35 @@ class DiffusionQM9(_Base):
         stats = stats.cpu()
         self.steer_last = steering.Result(steering.normalise(logw.cpu(), st.P), root.cpu().long(), torch.arange(B) // st.P,
                                           stats[:, 0].long(), stats[:, 1].clone(), stats[:, 2].long())
+
+    def _diversity_open(self, handle, topo, tabs, dv, dev):
+        """Attach the diversity of a resolved call (`diversity.Diversity`) to `topo` behind the rows of the path that `_path_tables` has
+        just set (hd_set_diversity, once per (path tables, schedule, clip)).  The caller detaches (hd_diversity_detach)."""
+        from . import diversity
+        pt = self._path_cache[2]
+        key = dv.key()
+        hit = self.__dict__.get("_diversity_cache")
+        if hit is None or hit[0] is not pt or hit[1] != key:
+            path = [int(t) for t in pt["t_idx"]] + [int(pt["s_idx"][-1])]
+            rows = np.ascontiguousarray(diversity.rows(tabs["gamma"], path, dv, float(self.norm_values[0])))
+            self._diversity_cache = None
+            _lib.check(_lib.load().hd_set_diversity(handle, int(rows.shape[0]), rows.ctypes.data_as(C.POINTER(C.c_float))),
+                       "hd_set_diversity")
+            self._diversity_cache = (pt, key)
+        sc = np.ascontiguousarray(dv.scale.numpy(), dtype=np.float32)
+        _lib.check(_lib.load().hd_diversity_attach(topo.ptr, dv.P, dv.strength, dv.length, sc.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   int(sc.shape[0]), float(self.norm_values[0]), _stream(dev)), "hd_diversity_attach")
+
+    def _diversity_result(self, pl, x, node_mask):
+        """`diversity_last` of a diverse call's returned x: Phi and the aligned RMSD matrix per group (hd_diversity_energy), attached as
+        the call attached it, so its cached graph stays."""
+        dv = getattr(pl, "diversity", None)
+        if dv is None:
+            return
+        from . import diversity
+        phi, rmsd = diversity._device_energy(x, node_mask, dv.P, dv.length, dv.strength, self, "diversity",
+                                             _attach=(dv.scale, float(self.norm_values[0])))
+        self.diversity_last = diversity.result(phi, rmsd)
 
     def _chain_times(self, keep_frames, t_start=None, inpaint: bool = False, **few):
         """[keep] the grid index every frame of a recording call has arrived at (`Plan.chain_t`): host arithmetic only."""
@@ -915,6 +953,9 @@ class DiffusionQM9(_Base):
         if pl is not None and pl.steer is not None:   # rows of a group interact: equal masks, contexts and tables, checked on the host
             from . import steering
             steering.check_groups(pl.steer, node_mask, context, pl.restraints.rs, pl.restraints.scale, what)
+        if pl is not None and pl.diversity is not None:
+            from . import diversity
+            diversity.check_groups(pl.diversity, node_mask, context, what)
         if dev.type != "cuda":
             raise _lib.HierDiffHipError(f"{what} runs only on an MI355X (no CPU fallback)")
         h = self._lib_handle()
@@ -948,11 +989,14 @@ class DiffusionQM9(_Base):
         mol = -1 if st.tail is None else st.N
         common = (_ptr(rx), _ptr(rh), rows, seed, base, int(self.use_graph))
         steer, ran = getattr(pl, "steer", None), False
+        dvs = getattr(pl, "diversity", None)
         try:
             if pl.restraints is not None:
                 self._restrain_open(st.h, topo, st.tabs, pl.restraints, st.B, st.dev)
             if steer is not None:
                 self._steer_open(st.h, topo, st.tabs, steer, int(k_lo) == 0, st.dev)
+            if dvs is not None:
+                self._diversity_open(st.h, topo, st.tabs, dvs, st.dev)
             if pl.frames is not None:
                 st.chain = self._chain_open(st.h, topo, st.tabs, pl.frames, pl.record, st.B, st.N, st.dev, st.chain)
             if parts is not None:
@@ -976,6 +1020,8 @@ class DiffusionQM9(_Base):
                 _lib.check(lib.hd_inpaint_parts(st.h, topo.ptr, None, st.stream), "hd_inpaint_parts")
             if steer is not None:
                 self._steer_close(topo, steer, st.B, st.dev, ran)
+            if dvs is not None:
+                _lib.check(lib.hd_diversity_detach(topo.ptr), "hd_diversity_detach")
             if pl.frames is not None:
                 _lib.check(lib.hd_chain_detach(topo.ptr), "hd_chain_detach")
             if pl.restraints is not None:
@@ -1017,7 +1063,7 @@ class DiffusionQM9(_Base):
                           solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                           keep_frames: Optional[int] = None, record: Optional[str] = None,
                           restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-                          particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None):
+                          particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None):
         """z_T -> (x, h) for given masks: draw z_T, T posterior steps, final decode.
 
         restraints / restraint_scale / restraint_schedule / restraint_clip (keyword-only; None: the model's attributes of the same
@@ -1042,6 +1088,15 @@ class DiffusionQM9(_Base):
         ids of its rows, P and its own masks and tables only.  particles of None or 1, or a steer_scale of None or 0, is the unsteered
         code path, untouched.  Not with eta = 0, solver "dpm2m" (solver "sde2m" is the second-order update that steers), fix_noise, raw_noises, pocket models, mode 'gnn_dynamics' or
         noise_mode 'torch'.  Mechanism only.
+
+        diversity (keyword-only; None: the model's `diversity`): a `diversity.Diversity(particles=P, length=l, strength=kappa, scale,
+        schedule, clip)` - diverse sampling (hierdiff_amd/diversity.py).  The batch is G groups of P rows with equal masks and contexts;
+        at every transition, behind guidance and the restraint updates, the rows of a group repel each other through
+        Phi = kappa sum_{p<q} exp(-d2_pq / (2 l^2)) of the aligned RMSD d_pq of their data predictions, fed into eps^ like a restraint
+        gradient (hd_diversity_attach, k_diverse_eps).  A gradient, not a selection: it also acts with eta = 0 and solver "dpm2m", and
+        needs no restraints.  `self.diversity_last` (`diversity.Result`) holds Phi and the pairwise RMSD of the returned x.  None,
+        particles = 1, or a strength or scale of 0 is the code path without it, untouched.  Not together with particles= (steering),
+        fix_noise on a path that draws, pocket models, mode 'gnn_dynamics' or noise_mode 'torch'.  Mechanism only.
 
         keep_frames / record (keyword-only; None: nothing is recorded and the call is today's): the reference's `sample_chain`
         (en_diffusion.py:669-710) - the chain runs in the path loop (the identity path when no few-step path is asked for) with a
@@ -1155,7 +1210,9 @@ class DiffusionQM9(_Base):
             final = int(sample_id_base)                  # decode noise: draw T+1 of the same counter stream
         self._check_mean_zero(z[:, :, :self.n_dims], node_mask)
         eps = self.phi(z, torch.zeros((B, 1), device=dev), node_mask, edge_mask, context) if gnn else None
-        return self._decode(st, z, node_mask, edge_mask, fix_noise, final, chain, eps=eps)
+        out = self._decode(st, z, node_mask, edge_mask, fix_noise, final, chain, eps=eps)
+        self._diversity_result(pl, out[0], node_mask)
+        return out
 
     @torch.no_grad()
     def path_steps(self, z, node_mask, edge_mask=None, context=None, *, steps=None, eta=None, spacing=None, timesteps=None,
@@ -1163,7 +1220,7 @@ class DiffusionQM9(_Base):
                    guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                    solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                    restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-                   particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None):
+                   particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None):
         """Transitions k_lo .. k_hi-1 of `sample_from_masks`'s few-step loop on a given z [B,N,D] (normalised units, the state at
         path position k_lo); returns the state at position k_hi (default: the end of the path, z_0 before the decode).  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.
@@ -1427,6 +1484,8 @@ class DiffusionQM9(_Base):
         _rs.refuse(self, "encode", restraints, ": the inversion follows the network's own flow")
         from . import steering as _st
         _st.refuse(self, "encode")
+        from . import diversity as _dv
+        _dv.refuse(self, "encode", None, ": the inversion follows the network's own flow")
         if paths.check_solver(solver) is not None:
             raise ValueError(f"encode: the inversion is first order (eta = 0 upwards); solver {solver!r} is not supported")
         t_end = self._grid_index(self.T if t_end is None else t_end, 1, "t_end")
@@ -1477,7 +1536,7 @@ class DiffusionQM9(_Base):
                      raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                      solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                      restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-                     particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None):
+                     particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None):
         """Transitions k_lo .. k_hi-1 of `sample_from_latent`'s partial chain on a given z [B,N,D] (the state at path position k_lo);
         returns the state at position k_hi (default: the end, z_0 before the decode), as `path_steps` does for a full path.  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.  `raw_noises`: k_hi - k_lo injected
@@ -1498,7 +1557,7 @@ class DiffusionQM9(_Base):
                            solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                            keep_frames: Optional[int] = None, record: Optional[str] = None,
                            restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-                           particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None):
+                           particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None):
         """(x, h) from a state z [B,N,D] at the grid index `t_start` (default T; normalised units - what `diffuse` and `encode`
         return): the partial reverse chain on `paths.partial_path(T, t_start, steps, spacing, timesteps)` (default: every grid point
         below t_start) inside the library's loop (hd_sample_path), then the final decode of `sample_from_masks`.  `eta` defaults to
@@ -1519,7 +1578,9 @@ class DiffusionQM9(_Base):
                                          None if raw_noises is None else raw_noises[:K])
         node_mask = node_mask.to(st.dev)
         self._check_mean_zero(z0[:, :, :self.n_dims], node_mask)
-        return self._decode(st, z0, node_mask, edge_mask, fix_noise, int(sample_id_base) if raw_noises is None else raw_noises[K], chain)
+        out = self._decode(st, z0, node_mask, edge_mask, fix_noise, int(sample_id_base) if raw_noises is None else raw_noises[K], chain)
+        self._diversity_result(pl, out[0], node_mask)
+        return out
 
     @torch.no_grad()
     def slerp(self, z_a, z_b, lambdas, node_mask):
@@ -1588,6 +1649,15 @@ class DiffusionQM9(_Base):
         if pl.steer is not None and (int(n_variants) % pl.steer.P or int(batch_size) % pl.steer.P):
             raise ValueError(f"vary: n_variants ({n_variants}) and batch_size ({batch_size}) must be multiples of particles "
                              f"({pl.steer.P}): the variants of one input form its groups")
+        dv_all = pl.diversity
+        if dv_all is not None:
+            if int(n_variants) % dv_all.P or int(batch_size) % dv_all.P:
+                raise ValueError(f"vary: n_variants ({n_variants}) and batch_size ({batch_size}) must be multiples of the diversity's "
+                                 f"particles ({dv_all.P}): the variants of one input form its groups")
+            if dv_all.scale.numel() not in (1, len(jobs) // dv_all.P):
+                raise ValueError(f"vary: the diversity scale must hold one value per group ([{len(jobs) // dv_all.P}], input-major), got "
+                                 f"{dv_all.scale.numel()}")
+            few.pop("diversity", None)                                                  # per batch below: a slice of its scales
         if gd_all is not None and gd_all.rows != 1 and gd_all.rows != len(jobs):
             raise ValueError(f"vary: guidance_scale must hold one scale per result ([{len(jobs)}], input-major), got {gd_all.rows}")
         if rr_all is not None:
@@ -1608,6 +1678,8 @@ class DiffusionQM9(_Base):
             if rr_all is not None:
                 rk = dict(restraints=rr_all.rs.slice(lo, lo + nm.shape[0]),
                           restraint_scale=rr_all.scale if rr_all.scale.numel() == 1 else rr_all.scale[lo:lo + nm.shape[0]])
+            if dv_all is not None:
+                rk["diversity"] = dv_all.slice(lo // dv_all.P, (lo + nm.shape[0]) // dv_all.P)
             got = self.sample_from_latent(z, nmd, None, ctxd, t_start=t_start, sample_id_base=base, guidance_scale=gs, **few, **rk)
             ent = {} if rr_all is None else self._restraint_entries(rk["restraints"], rk["restraint_scale"], got[0], nmd, h=got[1])
             xv, hv = got[0].cpu(), got[1].cpu()
@@ -1624,6 +1696,9 @@ class DiffusionQM9(_Base):
             if pl.steer is not None:
                 from . import steering
                 steering.into(part, self.steer_last, group0=lo // pl.steer.P)
+            if dv_all is not None:
+                from . import diversity
+                diversity.into(part, self.diversity_last, group0=lo // dv_all.P)
             out.extend(part)
         return out
 
@@ -1639,6 +1714,8 @@ class DiffusionQM9(_Base):
         _rs.refuse(self, "interpolate", restraints, ": its frames are reconstructions of the interpolated latents")
         from . import steering as _st
         _st.refuse(self, "interpolate")
+        from . import diversity as _dv
+        _dv.refuse(self, "interpolate", None, ": its frames are reconstructions of the interpolated latents")
         device = torch.device(device)
         if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or int(frames) < 2:
             raise ValueError(f"frames must be an integer >= 2, got {frames!r}")
@@ -1936,7 +2013,7 @@ class DiffusionQM9(_Base):
                solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                keep_frames: Optional[int] = None, record: Optional[str] = None,
                restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-               particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None):
+               particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None):
         """diffusion_qm9.py:347-395: list of {'x': [n_i,3], 'h': [n_i,8], ('context': [n_i,1])} on the CPU.
         steps / eta / spacing / timesteps: few-step sampling, see `sample_from_masks`; guidance_scale (a float or a
         [num_samples] tensor) / guidance_context ([num_samples, n_max, C]) / guidance_rescale: classifier-free guidance, ibid.;
@@ -1955,6 +2032,8 @@ class DiffusionQM9(_Base):
             raise ValueError("context required")
         if pl.steer is not None:                         # one size per group, P times: the particles of a group share their mask
             sample_n = [n for n in self.nodes_dist.sample(int(num_samples) // pl.steer.P) for _ in range(pl.steer.P)]
+        elif pl.diversity is not None:                   # ... and so do the rows of a diverse group
+            sample_n = [n for n in self.nodes_dist.sample(int(num_samples) // pl.diversity.P) for _ in range(pl.diversity.P)]
         else:
             sample_n = self.nodes_dist.sample(num_samples)
         pocket = None
@@ -2014,6 +2093,9 @@ class DiffusionQM9(_Base):
         if pl.steer is not None:
             from . import steering
             steering.into(out, self.steer_last)
+        if pl.diversity is not None:
+            from . import diversity
+            diversity.into(out, self.diversity_last)
         return out
 
     def sample_batches(self, batch_size, num_batches, device, context_range=None, protein_data_all=None,
@@ -2037,6 +2119,8 @@ class DiffusionQM9(_Base):
         _rs.refuse(self, "sample_batches", restraints, ": the batches' padded widths and molecule counts differ (use sample)")
         from . import steering as _st
         _st.refuse(self, "sample_batches")
+        from . import diversity as _dv
+        _dv.refuse(self, "sample_batches", None, ": the batches' molecule counts differ (use sample)")
         # classifier-free guidance (`sample_from_masks`): guidance_scale may also be a list / tuple of scales cycled per batch the way
         # context_range is; inside a merged device batch it becomes one scale per molecule
         from . import guidance

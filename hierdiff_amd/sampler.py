@@ -267,7 +267,43 @@ def parse_args(argv=None):
     ap.add_argument("--steer-scale", type=float, default=None, metavar="S", help="with --particles: beta, the weight of the energy "
                     "change in the log-weights")
     ap.add_argument("--steer-ess", type=float, default=None, metavar="R", help="with --particles: resample below R * P (default 0.5)")
+    ap.add_argument("--diverse", type=int, default=None, metavar="P",
+                    help="with --diverse-length: diverse sampling - every P consecutive molecules of a batch (with --vary: the variants "
+                         "of one input) form a group (one drawn size, equal context) whose members repel each other at every "
+                         "transition by the aligned RMSD of their data predictions, inside the device loop; --batch-size (and "
+                         "--variants) must be multiples of P (at most 32).  A gradient, not a selection: it combines with everything "
+                         "--steps combines with, --eta 0 and --solver dpm2m included, except --known / --grow and --particles.  "
+                         "Results also hold diversity_group / diversity_rmsd.  Mechanism only: which length and strength help is "
+                         "for you to validate")
+    ap.add_argument("--diverse-length", type=float, default=None, metavar="L", help="with --diverse: the width of the Gaussian in the "
+                    "units of the aligned RMSD")
+    ap.add_argument("--diverse-strength", type=float, default=None, metavar="S", help="with --diverse: kappa (default 1)")
+    ap.add_argument("--diverse-clip", type=float, default=None, metavar="C",
+                    help="with --diverse: the largest step per node in noise-prediction units (default: none)")
+    ap.add_argument("--diverse-schedule", choices=["score", "sigma"], default=None,
+                    help="with --diverse: the weight of transition k, nv0 sigma_t / alpha_t (score, default) or sigma_t")
     args = ap.parse_args(argv)
+    if (args.diverse is None) != (args.diverse_length is None):
+        ap.error("--diverse and --diverse-length go together")
+    if args.diverse is None and (args.diverse_strength is not None or args.diverse_clip is not None or args.diverse_schedule is not None):
+        ap.error("--diverse-strength / --diverse-clip / --diverse-schedule need --diverse and --diverse-length")
+    if args.diverse is not None:
+        if not 1 <= args.diverse <= 32:
+            ap.error("--diverse must lie in 1 .. 32")
+        if not (math.isfinite(args.diverse_length) and args.diverse_length > 0.0):
+            ap.error("--diverse-length must be finite and > 0")
+        if args.diverse_strength is not None and not (math.isfinite(args.diverse_strength) and args.diverse_strength >= 0.0):
+            ap.error("--diverse-strength must be finite and >= 0")
+        if args.diverse_clip is not None and not args.diverse_clip > 0.0:
+            ap.error("--diverse-clip must be > 0")
+        if args.particles is not None:
+            ap.error("--diverse does not combine with --particles (both lay groups over the batch)")
+        if args.known is not None or args.grow is not None:
+            ap.error("--diverse does not combine with --known / --grow (inpainting re-centres on the known fragments)")
+        if args.score is not None or args.interpolate is not None:
+            ap.error("--diverse does not combine with --score / --interpolate")
+        if args.batch_size % args.diverse or (args.vary is not None and args.variants % args.diverse):
+            ap.error("--batch-size (and with --vary, --variants) must be a multiple of --diverse")
     if (args.particles is None) != (args.steer_scale is None):
         ap.error("--particles and --steer-scale go together")
     if args.steer_ess is not None and args.particles is None:
@@ -422,6 +458,10 @@ def main(argv=None) -> int:
             chain.update(restraint_frame=args.restraint_frame)
     if args.particles is not None:
         chain.update(particles=args.particles, steer_scale=args.steer_scale, steer_ess=args.steer_ess)
+    if args.diverse is not None:
+        from .diversity import Diversity
+        chain.update(diversity=Diversity(args.diverse, args.diverse_length, 1.0 if args.diverse_strength is None else args.diverse_strength,
+                                         schedule=args.diverse_schedule or "score", clip=args.diverse_clip))
 
     if args.score is not None:
         if world > 1:
@@ -473,6 +513,7 @@ def main(argv=None) -> int:
         return 0
 
     steered = args.particles is not None and args.particles > 1 and args.steer_scale != 0.0
+    group = args.particles if steered else chain["diversity"].P if "diversity" in chain and chain["diversity"].active else 1
     torch.manual_seed(args.seed)           # the node-count draw uses torch's CPU generator (distributions.py)
     results: List[dict] = []
     first, count = shard_sample_ids(0, args.num_batches, rank, world)      # whole batches per rank
@@ -480,7 +521,7 @@ def main(argv=None) -> int:
         if not (first <= b < first + count):
             # advance the node-count generator over batches owned by other ranks, so the global sequence of
             # molecule sizes (and, with the counter-based noise, every sample) is independent of the world size
-            model.nodes_dist.sample(args.batch_size // (args.particles if steered else 1))    # (a steered batch draws one size per group)
+            model.nodes_dist.sample(args.batch_size // group)    # (a steered or diverse batch draws one size per group)
             continue
         ctx = None if not args.context else args.context[b % len(args.context)]
         results.extend(model.sample(args.batch_size, dev, context=ctx, sample_id_base=b * args.batch_size, **chain))

@@ -612,6 +612,41 @@ int hd_steer_step(hd_handle* h, hd_topology* topo, float* z, float* eps, const f
                   uint64_t sample_id_base, void* stream);
 int hd_steer_read(hd_topology* topo, double* logw, double* uprev, int* root, int* anc, double* stats, void* stream);
 
+/* ---- Diverse sampling (ABI 12, additive; no reference counterpart): the rows of a group repel each other by their aligned RMSD
+ * (particle guidance).  The batch is G groups of P rows; group g owns rows g P .. g P + P - 1 (the layout of steering), and groups
+ * never interact.  At every transition k, behind the network call, guidance and the restraint updates of eps^, per group, in double on
+ * the fp32 data predictions x^0 of its rows (those of the restraint update, nv0 included):
+ *   pair p < q:  A = the nodes valid in both rows, n = |A|;  c_p, c_q = the centroids over A;  S = sum_A (x_p - c_p)(x_q - c_q)^T;
+ *                R = argmax_{R in SO(3)} tr(R^T S) (a proper rotation: mirror images stay apart);  r_i = (x_p,i - c_p) - R (x_q,i - c_q);
+ *                d2 = sum_A |r_i|^2 / n;  e = exp(-d2 / (2 length^2))
+ *   Phi = kappa sum_{p<q} e;   dPhi/dx_p,i = -(kappa / (length^2 n)) sum_{q != p} e r_i  (on the q side r_i = (x_q,i - c_q) - R^T (x_p,i - c_p));
+ *   exact without dR/dx because R maximises and sum_A r = 0.  The partners q are added in ascending order.
+ *   step_{p,i} = s_g lambda_k dPhi/dx_p,i, clipped per node to clip_k, the mean over the row's valid nodes removed;
+ *   eps^_x[p,i] = fp32(double(eps^_x) + step) on valid nodes; an element whose step is exactly 0 keeps its bits; feature columns and
+ *   masked rows are never written; s_g lambda_k == 0 writes nothing.
+ * A pair with n <= 1, or with a non-finite coordinate on a node of A, contributes nothing to either side.  With n = 2 or collinear
+ * nodes R is not unique; d2 is, and the gradient is finite.  One launch (k_diverse_eps), one workgroup per group, no atomics, nothing
+ * is drawn; every sum runs in an order that depends on (N, P) alone.  A group's result depends on the seed, the ids of its rows, P, its
+ * masks, contexts and tables, the weights, the schedule and the path only - not on other groups, graph replay or how the chain is cut
+ * into calls.  No state crosses transitions.
+ * hd_set_diversity: the rows4[K][4] = {alpha_t, sigma_t, lambda_k, clip_k} (host) of the CURRENT path, checked as hd_set_restraint's.
+ * hd_diversity_attach: from now on hd_sample_path / hd_sample_path_guided on this topology carry the update, behind the restraint
+ *   updates, ahead of a recorded data prediction.  scale: host [scale_rows] s_g, scale_rows = 1 (shared) or B / P; nv0 as in
+ *   hd_restraint_attach.  HD_E_INVALID: P outside 2 .. 32, B not a multiple of P, kappa negative, length or nv0 not positive, anything
+ *   non-finite, or P * N * 3 floats plus P (P - 1) / 2 pair records of 96 bytes beyond one workgroup's LDS (64 KB).  Re-attaching with
+ *   the same sizes and numbers replays the cached graph; another P, scale_rows, kappa, length or nv0 rebuilds it once.
+ *   The path loop then refuses, behind every older refusal: an inpainting call, mol_shape < N, steering attached at the same time
+ *   (HD_E_INVALID), rows not set for the current path (HD_E_STATE), noise_rows == 1 on a range with a row that draws (HD_E_INVALID).
+ * hd_diversity_detach: the launches, graphs and keys are again those of a topology that never had it.
+ * hd_diverse_eps: the update once on given tensors with a host row4; the aliasing rules of hd_restrain_eps.
+ * hd_diversity_energy: for positions x [B][N][3] in data units Phi per group into phi [G] and, unless NULL, the aligned RMSD matrix
+ *   into rmsd [G][P][P] (device doubles): symmetric, zero diagonal, NaN for a pair that contributes nothing. */
+int hd_set_diversity(hd_handle* h, int K, const float* rows4);
+int hd_diversity_attach(hd_topology* topo, int P, double kappa, double length, const float* scale, int scale_rows, float nv0, void* stream);
+int hd_diversity_detach(hd_topology* topo);
+int hd_diverse_eps(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4, float* out, void* stream);
+int hd_diversity_energy(hd_handle* h, hd_topology* topo, const float* x, double* phi, double* rmsd, void* stream);
+
 /* ---- Scoring (ABI 12, additive; no reference counterpart beyond the one-timestep estimator, compute_loss with t0_always = True,
  * diffusion_qm9.py:530-699): the variational bound of GIVEN molecules with every term of a list evaluated, in the device loop.
  * For normalised data xh [B,N,D] and a term t in 1 .. T (s = t - 1):
