@@ -131,10 +131,9 @@ struct hd_handle {
     float* d_chain_as;          // [K][2]; null when hd_set_chain got none
     unsigned long long chain_path_gen, chain_gen;   // path.gen the tables were set for (0: not set); bumped by every hd_set_chain
     float** d_chain_dst;        // graph replay: the sink a recording transition writes (set by k_path_state)
-    // restraints (hd_set_restraint): the rows {alpha_t, sigma_t, lambda_k, clip_k} of every transition of the current path; steering
-    // (hd_set_steer): the rows {alpha_t, sigma_t, beta_k}
-    RowTable rs_rows, st_rows;  // [K][4], [K][3]
-    RowTable dv_rows;           // diversity (hd_set_diversity): [K][4], the row format of rs_rows
+    // the loop terms' rows of every transition of the current path: restraints (hd_set_restraint) and diversity (hd_set_diversity)
+    // {alpha_t, sigma_t, lambda_k, clip_k}, steering (hd_set_steer) {alpha_t, sigma_t, beta_k}
+    RowTable rs_rows, dv_rows, st_rows;   // [K][4], [K][4], [K][3]
     // scoring (hd_set_nll_terms / hd_nll_terms / hd_nll_finish): K terms t_idx[k] of the bound, rows {alpha_t, sigma_t, w_t, 0}
     int nll_K;
     std::vector<int> nll_t_h;
@@ -176,6 +175,21 @@ struct RestraintKey {
     }
 };
 
+// The steering part (steer_key): particles per group, rho, the topology's steering buffers, the handle's rows; all 0: not steered.
+struct SteerKey {
+    int P;
+    double ess;
+    unsigned long long gen, rows_gen;
+    bool operator==(const SteerKey& o) const { return P == o.P && ess == o.ess && gen == o.gen && rows_gen == o.rows_gen; }
+};
+
+// The diversity part (diverse_key builds it): rows per group, the topology's diversity state, the handle's rows; all 0: none attached.
+struct DiverseKey {
+    int P;
+    unsigned long long gen, rows_gen;
+    bool operator==(const DiverseKey& o) const { return P == o.P && gen == o.gen && rows_gen == o.rows_gen; }
+};
+
 // Everything a captured transition of the path loop has baked in (plain: resamplings = 0): a cached graph is replayed only when
 // all of it is unchanged.  path_gen is the generation (PathTables::gen) of the tables it runs on (the caller's path, or the every-step tables).
 struct PathKey {
@@ -186,20 +200,13 @@ struct PathKey {
     uint64_t seed;
     unsigned long long weights_gen, sched_gen, path_gen, ip_gen;
     int ip_parts;                                            // 1: an inpainting transition with per-channel masks (hd_inpaint_parts)
-    RestraintKey rs;
-    int st_P;                                                // steered transition: particles per group, rho, the topology's steering
-    double st_ess;                                           // buffers, the handle's rows (all 0: not steered)
-    unsigned long long st_gen, st_rows_gen;
-    int dv_P;                                                // diverse transition: rows per group, the topology's diversity state,
-    unsigned long long dv_gen, dv_rows_gen;                  // the handle's rows (all 0: none attached)
+    RestraintKey rs; SteerKey st; DiverseKey dv;             // one part per loop term
     bool operator==(const PathKey& o) const {
         return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape &&
                noise_rows == o.noise_rows && k_lo == o.k_lo && resamplings == o.resamplings &&
                w_rows == o.w_rows && phi == o.phi && seed == o.seed &&
                weights_gen == o.weights_gen && sched_gen == o.sched_gen && path_gen == o.path_gen &&
-               ip_gen == o.ip_gen && ip_parts == o.ip_parts && rs == o.rs &&
-               st_P == o.st_P && st_ess == o.st_ess && st_gen == o.st_gen && st_rows_gen == o.st_rows_gen &&
-               dv_P == o.dv_P && dv_gen == o.dv_gen && dv_rows_gen == o.dv_rows_gen;
+               ip_gen == o.ip_gen && ip_parts == o.ip_parts && rs == o.rs && st == o.st && dv == o.dv;
     }
 };
 
@@ -278,14 +285,48 @@ struct RestraintState {
     unsigned long long feat_gen;
 };
 
-static void restraint_free(RestraintState& r) {
-    for (void* p : {(void*)r.obs.p, (void*)r.pair_idx.p, (void*)r.pair_f.p, (void*)r.anc_idx.p, (void*)r.anc_f.p, (void*)r.scale.p,
-                    (void*)r.step, (void*)r.fld_v.p, (void*)r.fld_w.p, (void*)r.fld_off, (void*)r.fld_dims, (void*)r.fld_geom,
-                    (void*)r.tpl_idx.p, (void*)r.tpl_f.p, (void*)r.tpl_geom, (void*)r.ft_lo.p, (void*)r.ft_hi.p, (void*)r.ft_k.p,
-                    (void*)r.ft_coef.p, (void*)r.ft_sum.p})
+static void dev_free(std::initializer_list<void*> ps) {
+    for (void* p : ps)
         if (p) (void)hipFree(p);
+}
+
+static void restraint_free(RestraintState& r) {
+    dev_free({r.obs.p, r.pair_idx.p, r.pair_f.p, r.anc_idx.p, r.anc_f.p, r.scale.p, r.step, r.fld_v.p, r.fld_w.p, r.fld_off, r.fld_dims,
+              r.fld_geom, r.tpl_idx.p, r.tpl_f.p, r.tpl_geom, r.ft_lo.p, r.ft_hi.p, r.ft_k.p, r.ft_coef.p, r.ft_sum.p});
     r = RestraintState{};
 }
+
+// hd_steer_attach: the steered chain's state and scratch, allocated once; it survives between the pieces of a chain (`reset`: a new one).
+struct SteerAttach {
+    bool on;
+    int P;
+    double ess;
+    double* f64;                               // logw [B], U_prev [B], its scratch [B], stats [B / P][3] (room for [B][3])
+    int* i32;                                  // root [B], anc [B]
+    float* scratch;                            // [3][B][N][D]
+    unsigned long long gen;
+};
+
+// hd_diversity_attach: scales and scratch of k_diverse_eps; gen moves with P, scale_rows, kappa, length, nv0 or an address.
+struct DiverseAttach {
+    bool on;
+    int P, scale_rows;
+    double kappa, length;
+    float nv0;
+    DevTable<float> scale;
+    double* step;                              // [B][N][3]
+    unsigned long long gen;
+};
+
+// hd_chain_attach: the caller's sink every path loop on a topology records into (null: none; the caller's memory: nothing to free).
+struct ChainSink {
+    float* dst;
+    int frames, what;                          // what 0: the state behind the transition, 1: its data prediction
+    float nv0, nv1, nb1;
+};
+
+static void steer_free(SteerAttach& s) { dev_free({s.f64, s.i32, s.scratch}); s = SteerAttach{}; }
+static void diverse_free(DiverseAttach& d) { dev_free({d.scale.p, d.step}); d = DiverseAttach{}; }
 
 struct hd_topology {
     hd_handle* h;
@@ -325,34 +366,13 @@ struct hd_topology {
     // unguided one - the null context and the scales (one allocation, made by the first guided call; hd_guided_graph_builds)
     GraphSlot<PathKey> g_guided;
     float *guide_mem, *eps_u, *ctxu_buf, *wbuf;
-    // hd_chain_attach: the sink every path loop on this topology records into (null: none), and the recording transition - guided
-    // or not - in a graph of its own next to the two above (hd_chain_graph_builds)
-    float* chain_dst;
-    int chain_frames, chain_what;              // what 0: the state behind the transition, 1: its data prediction
-    float chain_nv0, chain_nv1, chain_nb1;
+    // the recording transition (a sink attached) - guided or not - in a graph of its own next to the two above (hd_chain_graph_builds)
     GraphSlot<ChainKey> g_chain;
-    // hd_restraint_attach / _fields / _templates / _features / _frame: everything restraints keep on a topology
+    // what a caller attaches for the time of a call, one struct per loop term: restraints, steering, diversity, the sink
     RestraintState rs;
-    // hd_steer_attach: the steering state of the chain that runs on this topology (log-weights, last energies, lineage roots, the
-    // ancestors of the latest transition, per-group statistics) and the scratch of k_steer_gather - one allocation each, made by the
-    // first attach at addresses captured transitions keep.  It survives between the pieces of a chain; `reset` starts a new one.
-    bool st_on;
-    int st_P;
-    double st_ess;
-    double *st_f64;                            // logw [B], U_prev [B], its scratch [B], stats [B / P][3] (room for [B][3])
-    int* st_i32;                               // root [B], anc [B]
-    float* st_scratch;                         // [3][B][N][D]
-    unsigned long long st_gen;
-    // hd_diversity_attach: the rows of a group repel by aligned RMSD (k_diverse.hpp).  The per-group scales and the scratch of
-    // k_diverse_eps are allocated by the first attach at addresses captured transitions keep; dv_gen moves when something a captured
-    // launch bakes in does (P, scale_rows, kappa, length, nv0, an address).  No state crosses transitions.
-    bool dv_on;
-    int dv_P, dv_scale_rows;
-    double dv_kappa, dv_length;
-    float dv_nv0;
-    DevTable<float> dv_scale;
-    double* dv_step;                           // [B][N][3]
-    unsigned long long dv_gen;
+    SteerAttach st;
+    DiverseAttach dv;
+    ChainSink chain;
     // multistep paths (hd_set_path_multistep): the previous transition's data prediction x^ [B][N][D], allocated by the first
     // form-2 call at an address the captured transitions keep; host-side, which path generation and position it belongs to
     float* ms_hist;
@@ -529,9 +549,7 @@ extern "C" int hd_destroy(hd_handle* h) {
         hipFree(pt->d_t); hipFree(pt->d_s); hipFree(pt->d_coef); hipFree(pt->d_coef_ip);
     }
     hipFree(h->d_chain_frame); hipFree(h->d_chain_as); hipFree(h->d_chain_dst);
-    hipFree(h->rs_rows.d);
-    hipFree(h->st_rows.d);
-    hipFree(h->dv_rows.d);
+    for (RowTable* tb : {&h->rs_rows, &h->st_rows, &h->dv_rows}) hipFree(tb->d);
     hipFree(h->d_nll_t); hipFree(h->d_nll_coef);
 #ifdef HD_DEBUG_KERNELS
     hipFree(h->d_trace);
@@ -924,18 +942,10 @@ extern "C" int hd_topology_destroy(hd_topology* t) {
     }
     if (!pooled) (void)hipDeviceSynchronize();
     for (hipGraphExec_t* gx : graph_execs(t)) graph_drop(gx);
-    if (t->guide_mem) (void)hipFree(t->guide_mem);
-    if (t->ms_hist) (void)hipFree(t->ms_hist);
     restraint_free(t->rs);
-    for (void* p : {(void*)t->st_f64, (void*)t->st_i32, (void*)t->st_scratch, (void*)t->dv_scale.p, (void*)t->dv_step})
-        if (p) (void)hipFree(p);
-    if (t->ip_fixed) (void)hipFree(t->ip_fixed);
-    if (t->ip_known) (void)hipFree(t->ip_known);
-    if (t->ip_parts) (void)hipFree(t->ip_parts);
-    if (t->nll_eps) (void)hipFree(t->nll_eps);
-    if (t->nll_xh) (void)hipFree(t->nll_xh);
-    if (t->nll_err) (void)hipFree(t->nll_err);
-    if (t->nll_acc) (void)hipFree(t->nll_acc);
+    steer_free(t->st);
+    diverse_free(t->dv);
+    dev_free({t->guide_mem, t->ms_hist, t->ip_fixed, t->ip_known, t->ip_parts, t->nll_eps, t->nll_xh, t->nll_err, t->nll_acc});
     if (t->ready) (void)hipEventDestroy(t->ready);
     if (t->arena) arena_release(sl);                    // tables and workspace live in one allocation
     delete t->node_of_host;

@@ -469,15 +469,11 @@ extern "C" int hd_set_chain(hd_handle* h, int K, const int* frame_of, const floa
 extern "C" int hd_chain_attach(hd_topology* topo, float* chain, int frames, int what, float nv0, float nv1, float nb1) {
     if (!topo || !chain || frames < 1) return fail(HD_E_INVALID, "hd_chain_attach: null topology / sink, or frames < 1");
     if (what != 0 && what != 1) return fail(HD_E_INVALID, "hd_chain_attach: what must be 0 (the state) or 1 (the data prediction)");
-    topo->chain_dst = chain; topo->chain_frames = frames; topo->chain_what = what;
-    topo->chain_nv0 = nv0; topo->chain_nv1 = nv1; topo->chain_nb1 = nb1;
+    topo->chain = ChainSink{chain, frames, what, nv0, nv1, nb1};
     return HD_OK;
 }
 
-extern "C" int hd_chain_detach(hd_topology* topo) {
-    if (topo) topo->chain_dst = nullptr;
-    return HD_OK;
-}
+extern "C" int hd_chain_detach(hd_topology* topo) { if (topo) topo->chain.dst = nullptr; return HD_OK; }
 
 extern "C" long long hd_chain_graph_builds(const hd_topology* topo) { return topo ? topo->g_chain.builds : -1; }
 
@@ -731,10 +727,7 @@ extern "C" int hd_restraint_frame(hd_topology* topo, int frame) {
     return HD_OK;
 }
 
-extern "C" int hd_restraint_detach(hd_topology* topo) {
-    if (topo) topo->rs.on = false;
-    return HD_OK;
-}
+extern "C" int hd_restraint_detach(hd_topology* topo) { if (topo) topo->rs.on = false; return HD_OK; }
 
 // The kernels' views of the state (k_restrain.hpp): NF / NT are what is attached now, not what was last baked in.
 static RestraintTables restraint_tables(const hd_topology* t) {
@@ -777,16 +770,30 @@ static RestraintKey restraint_key(const hd_handle* h, const hd_topology* topo, b
     return k;
 }
 
-// The update of one transition on eps (in place when out == eps): `rows` the device table read at position *io.step / io.row, or the
-// host row.  `framed`: in the frame of the known fragments io.fixed / io.known (k_restrain_eps<true>).
+// ... and its steering and diversity parts: all 0 unless the term takes part (`on`).
+static SteerKey steer_key(const hd_handle* h, const hd_topology* t, bool on) {
+    return on ? SteerKey{t->st.P, t->st.ess, t->st.gen, h->st_rows.gen} : SteerKey{};
+}
+static DiverseKey diverse_key(const hd_handle* h, const hd_topology* t, bool on) {
+    return on ? DiverseKey{t->dv.P, t->dv.gen, h->dv_rows.gen} : DiverseKey{};
+}
+
+// A transition's row of W floats in the argument struct of any term: the device table `rows` at *io.step / io.row, or the host `row`.
+template <typename Args>
+static void set_row(Args& a, const LoopIO& io, const float* rows, const float* row, int W) {
+    a.rows = rows; a.step_ptr = io.step; a.k = io.row;
+    for (int i = 0; i < W; ++i) a.row[i] = row ? row[i] : 0.f;
+}
+
+// The update of one transition on eps (in place when out == eps): the row as set_row finds it.  `framed`: in the frame of the known
+// fragments io.fixed / io.known (k_restrain_eps<true>).
 static int restrain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* z, const float* eps, float* out,
                            const float* rows, const float* row4, bool framed = false) {
     ProfScope ps(h, io.s, 2);
     RestrainArgs a;
     a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.t = restraint_tables(t); a.scale = t->rs.scale.p;
-    a.rows = rows;
-    for (int i = 0; i < 4; ++i) a.row[i] = row4 ? row4[i] : 0.f;
-    a.step_ptr = io.step; a.k = io.row; a.step = t->rs.step; a.nv0 = t->rs.nv0; a.scale_rows = t->rs.scale_rows;
+    set_row(a, io, rows, row4, 4);
+    a.step = t->rs.step; a.nv0 = t->rs.nv0; a.scale_rows = t->rs.scale_rows;
     a.B = t->B; a.N = t->N; a.D = h->D;
     a.fixed = framed ? io.fixed : nullptr; a.known = framed ? io.known : nullptr;
     a.tp = template_tables(t);
@@ -800,7 +807,6 @@ static int restrain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const
     return HD_OK;
 }
 
-
 // The feature update of one transition on eps (in place when out == eps), behind restrain_launch: k_restrain_feat on the attached
 // features, the row read as there.
 static int restrain_feat_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* z, const float* eps, float* out,
@@ -808,9 +814,8 @@ static int restrain_feat_launch(hd_handle* h, hd_topology* t, const LoopIO& io, 
     ProfScope ps(h, io.s, 2);
     RestrainFeatArgs a;
     a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.t = feature_tables(t); a.scale = t->rs.scale.p;
-    a.rows = rows;
-    for (int i = 0; i < 4; ++i) a.row[i] = row4 ? row4[i] : 0.f;
-    a.step_ptr = io.step; a.k = io.row; a.ratio = t->rs.ft_ratio; a.scale_rows = t->rs.scale_rows;
+    set_row(a, io, rows, row4, 4);
+    a.ratio = t->rs.ft_ratio; a.scale_rows = t->rs.scale_rows;
     a.B = t->B; a.N = t->N; a.D = h->D;
     hipLaunchKernelGGL(k_restrain_feat, dim3(t->B), dim3(256), (size_t)t->N * (h->D - 3) * sizeof(float), io.s, a);
     HIP_TRY(hipGetLastError());
@@ -835,20 +840,28 @@ static int restraint_entry(const char* who, hd_handle* h, hd_topology* topo, boo
     return HD_OK;
 }
 
-// hd_restrain_eps / hd_restrain_eps_framed (`framed`: fixed_mask and xh_known are part of the call)
+// What the single-transition entry points of the eps terms share behind their own state checks; xh_known: framed calls only.
+static int eps_entry(const char* who, hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4,
+                     const float* xh_known, const float* out, void* stream, LoopIO* io) {
+    if (!restraint_row_ok(row4)) return refuse(HD_E_INVALID, who, ": need alpha_t > 0, sigma_t >= 0, a finite lambda and clip > 0 (inf: no clip)");
+    const size_t per = (size_t)topo->B * topo->N * h->D;
+    if (out < z + per && z < out + per) return refuse(HD_E_INVALID, who, ": out may not overlap z");
+    if (xh_known && out < xh_known + per && xh_known < out + per) return refuse(HD_E_INVALID, who, ": out may not overlap xh_known");
+    if (out != eps && out < eps + per && eps < out + per) return refuse(HD_E_INVALID, who, ": out may be eps itself, not a shifted overlap of it");
+    HIP_TRY(hipSetDevice(h->device));
+    *io = LoopIO{}; io->s = (hipStream_t)stream;
+    topo_use(topo, io->s);
+    return HD_OK;
+}
+
+// hd_restrain_eps / hd_restrain_eps_framed (`framed`: fixed_mask and xh_known are part of the call, else null)
 static int restrain_eps(const char* who, hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4,
                         const uint8_t* fixed_mask, const float* xh_known, float* out, void* stream, bool framed) {
     HD_TRY(restraint_refusals(who, h, topo, z && eps && row4 && out && (!framed || (fixed_mask && xh_known)),
                               framed ? "tensor / row / fixed_mask / xh_known" : "tensor / row"));
-    if (!restraint_row_ok(row4)) return refuse(HD_E_INVALID, who, ": need alpha_t > 0, sigma_t >= 0, a finite lambda and clip > 0 (inf: no clip)");
-    const size_t per = (size_t)topo->B * topo->N * h->D;
-    if (out < z + per && z < out + per) return refuse(HD_E_INVALID, who, ": out may not overlap z");
-    if (framed && out < xh_known + per && xh_known < out + per) return refuse(HD_E_INVALID, who, ": out may not overlap xh_known");
-    if (out != eps && out < eps + per && eps < out + per) return refuse(HD_E_INVALID, who, ": out may be eps itself, not a shifted overlap of it");
-    HIP_TRY(hipSetDevice(h->device));
-    LoopIO io{};
-    io.s = (hipStream_t)stream; io.fixed = fixed_mask; io.known = xh_known;
-    topo_use(topo, io.s);
+    LoopIO io;
+    HD_TRY(eps_entry(who, h, topo, z, eps, row4, xh_known, out, stream, &io));
+    io.fixed = fixed_mask; io.known = xh_known;
     return restrain_launch(h, topo, io, z, eps, out, nullptr, row4, framed);
 }
 
@@ -862,14 +875,8 @@ extern "C" int hd_restrain_feat(hd_handle* h, hd_topology* topo, const float* z,
     const char* who = "hd_restrain_feat";
     HD_TRY(restraint_refusals(who, h, topo, z && eps && row4 && out, "tensor / row"));
     if (!topo->rs.feat) return refuse(HD_E_STATE, who, ": no features attached to the topology (hd_restraint_features)");
-    if (!restraint_row_ok(row4)) return refuse(HD_E_INVALID, who, ": need alpha_t > 0, sigma_t >= 0, a finite lambda and clip > 0 (inf: no clip)");
-    const size_t per = (size_t)topo->B * topo->N * h->D;
-    if (out < z + per && z < out + per) return refuse(HD_E_INVALID, who, ": out may not overlap z");
-    if (out != eps && out < eps + per && eps < out + per) return refuse(HD_E_INVALID, who, ": out may be eps itself, not a shifted overlap of it");
-    HIP_TRY(hipSetDevice(h->device));
-    LoopIO io{};
-    io.s = (hipStream_t)stream;
-    topo_use(topo, io.s);
+    LoopIO io;
+    HD_TRY(eps_entry(who, h, topo, z, eps, row4, nullptr, out, stream, &io));
     return restrain_feat_launch(h, topo, io, z, eps, out, nullptr, row4);
 }
 
@@ -949,7 +956,7 @@ extern "C" int hd_set_steer(hd_handle* h, int K, const float* rows3) {
 static SteerState steer_state(const hd_topology* t) {
     SteerState s;
     const size_t B = (size_t)t->B;
-    s.logw = t->st_f64; s.uprev = t->st_f64 + B; s.stats = t->st_f64 + 3 * B; s.root = t->st_i32; s.anc = t->st_i32 + B;
+    s.logw = t->st.f64; s.uprev = t->st.f64 + B; s.stats = t->st.f64 + 3 * B; s.root = t->st.i32; s.anc = t->st.i32 + B;
     return s;
 }
 
@@ -961,30 +968,27 @@ extern "C" int hd_steer_attach(hd_topology* topo, int P, double ess, int reset, 
     HIP_TRY(hipSetDevice(topo->device));
     hipStream_t s = (hipStream_t)stream;
     topo_use(topo, s);
-    topo->st_on = false;
+    topo->st.on = false;
     const size_t B = (size_t)topo->B;
-    const bool fresh = !topo->st_f64;
-    if (!reset && (fresh || P != topo->st_P))
+    const bool fresh = !topo->st.f64;
+    if (!reset && (fresh || P != topo->st.P))
         return fail(HD_E_STATE, "hd_steer_attach: reset = 0 continues a chain, and this topology holds no steering state for this P");
     if (fresh) {
-        if (!topo->st_i32) HD_TRY(dev_alloc(&topo->st_i32, 2 * B));
-        if (!topo->st_scratch) HD_TRY(dev_alloc(&topo->st_scratch, 3 * B * topo->N * topo->h->D));
-        HD_TRY(dev_alloc(&topo->st_f64, 6 * B));            // last: its presence says all three are there
+        if (!topo->st.i32) HD_TRY(dev_alloc(&topo->st.i32, 2 * B));
+        if (!topo->st.scratch) HD_TRY(dev_alloc(&topo->st.scratch, 3 * B * topo->N * topo->h->D));
+        HD_TRY(dev_alloc(&topo->st.f64, 6 * B));            // last: its presence says all three are there
     }
-    if (fresh || P != topo->st_P || ess != topo->st_ess) topo->st_gen++;
-    topo->st_P = P; topo->st_ess = ess;
+    if (fresh || P != topo->st.P || ess != topo->st.ess) topo->st.gen++;
+    topo->st.P = P; topo->st.ess = ess;
     if (reset) {
         hipLaunchKernelGGL(k_steer_init, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, steer_state(topo), topo->B, P);
         HIP_TRY(hipGetLastError());
     }
-    topo->st_on = true;
+    topo->st.on = true;
     return HD_OK;
 }
 
-extern "C" int hd_steer_detach(hd_topology* topo) {
-    if (topo) topo->st_on = false;
-    return HD_OK;
-}
+extern "C" int hd_steer_detach(hd_topology* topo) { if (topo) topo->st.on = false; return HD_OK; }
 
 // The three stages of one transition on z / eps (both may be rewritten): `rows` the device table read at *io.step / io.row, or the
 // host row; the draw and the first sample id by value or from the loop's device words.
@@ -994,9 +998,9 @@ static int steer_launch(hd_handle* h, hd_topology* t, const LoopIO& io, float* z
     ProfScope ps(h, io.s, 2);
     const SteerState st = steer_state(t);
     SteerWeighArgs w;
-    w.z = z; w.eps = eps; w.nm = t->nm_bytes; w.t = restraint_tables(t); w.rows = rows;
-    for (int i = 0; i < 3; ++i) w.row[i] = row3 ? row3[i] : 0.f;
-    w.step_ptr = io.step; w.k = io.row; w.nv0 = t->rs.nv0; w.logw = st.logw; w.uprev = st.uprev; w.B = t->B; w.N = t->N; w.D = h->D;
+    w.z = z; w.eps = eps; w.nm = t->nm_bytes; w.t = restraint_tables(t);
+    set_row(w, io, rows, row3, 3);
+    w.nv0 = t->rs.nv0; w.logw = st.logw; w.uprev = st.uprev; w.B = t->B; w.N = t->N; w.D = h->D;
     w.tp = template_tables(t);
     w.ft = feature_tables(t);
     if (t->rs.feat) {                                   // features attached: the instantiations with U_feat, and v behind x^0 in LDS
@@ -1006,11 +1010,11 @@ static int steer_launch(hd_handle* h, hd_topology* t, const LoopIO& io, float* z
     } else if (t->rs.NT) hipLaunchKernelGGL((k_steer_weigh<true, false>), dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, w);
     else hipLaunchKernelGGL((k_steer_weigh<false, false>), dim3(t->B), dim3(256), (size_t)t->N * 3 * sizeof(float), io.s, w);
     SteerResampleArgs r;
-    r.st = st; r.ess = t->st_ess; r.seed = seed; r.base = io.base; r.draw = d.value; r.draw_ptr = d.word; r.base_ptr = io.base_w;
-    r.P = t->st_P;
-    hipLaunchKernelGGL(k_steer_resample, dim3(t->B / t->st_P), dim3(256), 0, io.s, r);
+    r.st = st; r.ess = t->st.ess; r.seed = seed; r.base = io.base; r.draw = d.value; r.draw_ptr = d.word; r.base_ptr = io.base_w;
+    r.P = t->st.P;
+    hipLaunchKernelGGL(k_steer_resample, dim3(t->B / t->st.P), dim3(256), 0, io.s, r);
     SteerGatherArgs g;
-    g.z = z; g.eps = eps; g.hist = hist; g.scratch = t->st_scratch; g.uprev = st.uprev; g.us = t->st_f64 + 2 * (size_t)t->B; g.anc = st.anc;
+    g.z = z; g.eps = eps; g.hist = hist; g.scratch = t->st.scratch; g.uprev = st.uprev; g.us = t->st.f64 + 2 * (size_t)t->B; g.anc = st.anc;
     g.B = t->B; g.total = t->N * h->D;
     hipLaunchKernelGGL(k_steer_gather<0>, dim3(t->B), dim3(256), 0, io.s, g);
     hipLaunchKernelGGL(k_steer_gather<1>, dim3(t->B), dim3(256), 0, io.s, g);
@@ -1022,7 +1026,7 @@ extern "C" int hd_steer_step(hd_handle* h, hd_topology* topo, float* z, float* e
                              uint64_t sample_id_base, void* stream) {
     if (!h || !topo) return fail(HD_E_INVALID, "hd_steer_step: null handle/topology");
     if (!z || !eps || !row3) return fail(HD_E_INVALID, "hd_steer_step: null tensor / row");
-    if (!topo->st_on) return fail(HD_E_STATE, "hd_steer_step: no steering attached to the topology (hd_steer_attach)");
+    if (!topo->st.on) return fail(HD_E_STATE, "hd_steer_step: no steering attached to the topology (hd_steer_attach)");
     if (!topo->rs.on) return fail(HD_E_STATE, "hd_steer_step: no restraints attached to the topology (hd_restraint_attach)");
     if (!steer_row_ok(row3)) return fail(HD_E_INVALID, "hd_steer_step: need alpha_t > 0, sigma_t >= 0 and a finite beta >= 0");
     const size_t per = (size_t)topo->B * topo->N * h->D;
@@ -1036,7 +1040,7 @@ extern "C" int hd_steer_step(hd_handle* h, hd_topology* topo, float* z, float* e
 
 extern "C" int hd_steer_read(hd_topology* topo, double* logw, double* uprev, int* root, int* anc, double* stats, void* stream) {
     if (!topo) return fail(HD_E_INVALID, "hd_steer_read: null topology");
-    if (!topo->st_f64) return fail(HD_E_STATE, "hd_steer_read: the topology holds no steering state (hd_steer_attach)");
+    if (!topo->st.f64) return fail(HD_E_STATE, "hd_steer_read: the topology holds no steering state (hd_steer_attach)");
     HIP_TRY(hipSetDevice(topo->device));
     hipStream_t s = (hipStream_t)stream;
     topo_use(topo, s);
@@ -1046,7 +1050,7 @@ extern "C" int hd_steer_read(hd_topology* topo, double* logw, double* uprev, int
     if (uprev) HIP_TRY(hipMemcpyAsync(uprev, st.uprev, B * sizeof(double), hipMemcpyDefault, s));
     if (root) HIP_TRY(hipMemcpyAsync(root, st.root, B * sizeof(int), hipMemcpyDefault, s));
     if (anc) HIP_TRY(hipMemcpyAsync(anc, st.anc, B * sizeof(int), hipMemcpyDefault, s));
-    if (stats) HIP_TRY(hipMemcpyAsync(stats, st.stats, B / topo->st_P * 3 * sizeof(double), hipMemcpyDefault, s));
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, st.stats, B / topo->st.P * 3 * sizeof(double), hipMemcpyDefault, s));
     return HD_OK;
 }
 
@@ -1082,33 +1086,30 @@ extern "C" int hd_diversity_attach(hd_topology* topo, int P, double kappa, doubl
     HIP_TRY(hipSetDevice(topo->device));
     hipStream_t s = (hipStream_t)stream;
     topo_use(topo, s);
-    topo->dv_on = false;
+    topo->dv.on = false;
     bool moved = false;
-    if (!topo->dv_step) { HD_TRY(dev_alloc(&topo->dv_step, (size_t)topo->B * topo->N * 3)); moved = true; }
+    if (!topo->dv.step) { HD_TRY(dev_alloc(&topo->dv.step, (size_t)topo->B * topo->N * 3)); moved = true; }
     // (a host array: a pageable source is staged before the call returns)
-    HD_TRY(topo->dv_scale.fill(scale, (size_t)scale_rows, &moved, s));
-    restraint_bake({{&topo->dv_P, P}, {&topo->dv_scale_rows, scale_rows}},
-                   moved || kappa != topo->dv_kappa || length != topo->dv_length || nv0 != topo->dv_nv0, &topo->dv_gen);
-    topo->dv_kappa = kappa; topo->dv_length = length; topo->dv_nv0 = nv0;
-    topo->dv_on = true;
+    HD_TRY(topo->dv.scale.fill(scale, (size_t)scale_rows, &moved, s));
+    restraint_bake({{&topo->dv.P, P}, {&topo->dv.scale_rows, scale_rows}},
+                   moved || kappa != topo->dv.kappa || length != topo->dv.length || nv0 != topo->dv.nv0, &topo->dv.gen);
+    topo->dv.kappa = kappa; topo->dv.length = length; topo->dv.nv0 = nv0;
+    topo->dv.on = true;
     return HD_OK;
 }
 
-extern "C" int hd_diversity_detach(hd_topology* topo) {
-    if (topo) topo->dv_on = false;
-    return HD_OK;
-}
+extern "C" int hd_diversity_detach(hd_topology* topo) { if (topo) topo->dv.on = false; return HD_OK; }
 
 // The diversity update of one transition on eps (in place when out == eps): the row read as restrain_launch reads it.
 static int diverse_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* z, const float* eps, float* out,
                           const float* rows, const float* row4) {
     ProfScope ps(h, io.s, 2);
     DiverseArgs a;
-    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.scale = t->dv_scale.p; a.rows = rows;
-    for (int i = 0; i < 4; ++i) a.row[i] = row4 ? row4[i] : 0.f;
-    a.step_ptr = io.step; a.k = io.row; a.step = t->dv_step; a.kappa = t->dv_kappa; a.inv_l2 = 1.0 / (t->dv_length * t->dv_length);
-    a.nv0 = t->dv_nv0; a.scale_rows = t->dv_scale_rows; a.P = t->dv_P; a.B = t->B; a.N = t->N; a.D = h->D;
-    hipLaunchKernelGGL(k_diverse_eps, dim3(t->B / t->dv_P), dim3(256), diverse_lds(t->dv_P, t->N), io.s, a);
+    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.scale = t->dv.scale.p;
+    set_row(a, io, rows, row4, 4);
+    a.step = t->dv.step; a.kappa = t->dv.kappa; a.inv_l2 = 1.0 / (t->dv.length * t->dv.length);
+    a.nv0 = t->dv.nv0; a.scale_rows = t->dv.scale_rows; a.P = t->dv.P; a.B = t->B; a.N = t->N; a.D = h->D;
+    hipLaunchKernelGGL(k_diverse_eps, dim3(t->B / t->dv.P), dim3(256), diverse_lds(t->dv.P, t->N), io.s, a);
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
@@ -1118,15 +1119,9 @@ extern "C" int hd_diverse_eps(hd_handle* h, hd_topology* topo, const float* z, c
     const char* who = "hd_diverse_eps";
     if (!h || !topo) return refuse(HD_E_INVALID, who, ": null handle/topology");
     if (!z || !eps || !row4 || !out) return refuse(HD_E_INVALID, who, ": null tensor / row");
-    if (!topo->dv_on) return refuse(HD_E_STATE, who, ": no diversity attached to the topology (hd_diversity_attach)");
-    if (!restraint_row_ok(row4)) return refuse(HD_E_INVALID, who, ": need alpha_t > 0, sigma_t >= 0, a finite lambda and clip > 0 (inf: no clip)");
-    const size_t per = (size_t)topo->B * topo->N * h->D;
-    if (out < z + per && z < out + per) return refuse(HD_E_INVALID, who, ": out may not overlap z");
-    if (out != eps && out < eps + per && eps < out + per) return refuse(HD_E_INVALID, who, ": out may be eps itself, not a shifted overlap of it");
-    HIP_TRY(hipSetDevice(h->device));
-    LoopIO io{};
-    io.s = (hipStream_t)stream;
-    topo_use(topo, io.s);
+    if (!topo->dv.on) return refuse(HD_E_STATE, who, ": no diversity attached to the topology (hd_diversity_attach)");
+    LoopIO io;
+    HD_TRY(eps_entry(who, h, topo, z, eps, row4, nullptr, out, stream, &io));
     return diverse_launch(h, topo, io, z, eps, out, nullptr, row4);
 }
 
@@ -1134,15 +1129,15 @@ extern "C" int hd_diversity_energy(hd_handle* h, hd_topology* topo, const float*
     const char* who = "hd_diversity_energy";
     if (!h || !topo) return refuse(HD_E_INVALID, who, ": null handle/topology");
     if (!x || !phi) return refuse(HD_E_INVALID, who, ": null tensor");
-    if (!topo->dv_on) return refuse(HD_E_STATE, who, ": no diversity attached to the topology (hd_diversity_attach)");
+    if (!topo->dv.on) return refuse(HD_E_STATE, who, ": no diversity attached to the topology (hd_diversity_attach)");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     topo_use(topo, s);
     ProfScope ps(h, s, 2);
     DiverseEnergyArgs a;
-    a.x = x; a.nm = topo->nm_bytes; a.phi = phi; a.rmsd = rmsd; a.kappa = topo->dv_kappa;
-    a.inv_l2 = 1.0 / (topo->dv_length * topo->dv_length); a.P = topo->dv_P; a.B = topo->B; a.N = topo->N;
-    hipLaunchKernelGGL(k_diverse_energy, dim3(topo->B / topo->dv_P), dim3(256), 0, s, a);
+    a.x = x; a.nm = topo->nm_bytes; a.phi = phi; a.rmsd = rmsd; a.kappa = topo->dv.kappa;
+    a.inv_l2 = 1.0 / (topo->dv.length * topo->dv.length); a.P = topo->dv.P; a.B = topo->B; a.N = topo->N;
+    hipLaunchKernelGGL(k_diverse_energy, dim3(topo->B / topo->dv.P), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
@@ -1182,8 +1177,8 @@ static int chain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const fl
     ProfScope ps(h, io.s, 2);
     ChainArgs a;
     a.z = io.z; a.eps = eps; a.nm = t->nm_bytes; a.frame_of = h->d_chain_frame; a.alsig = h->d_chain_as;
-    a.dst_w = io.captured() ? h->d_chain_dst : nullptr; a.dst = io.captured() ? nullptr : t->chain_dst; a.step_ptr = io.step; a.k = io.row;
-    a.nv0 = t->chain_nv0; a.nv1 = t->chain_nv1; a.nb1 = t->chain_nb1; a.B = t->B; a.N = t->N; a.D = h->D;
+    a.dst_w = io.captured() ? h->d_chain_dst : nullptr; a.dst = io.captured() ? nullptr : t->chain.dst; a.step_ptr = io.step; a.k = io.row;
+    a.nv0 = t->chain.nv0; a.nv1 = t->chain.nv1; a.nb1 = t->chain.nb1; a.B = t->B; a.N = t->N; a.D = h->D;
     if (eps) hipLaunchKernelGGL(k_chain_frame<1>, dim3(t->B), dim3(256), 0, io.s, a);
     else hipLaunchKernelGGL(k_chain_frame<0>, dim3(t->B), dim3(256), 0, io.s, a);
     HIP_TRY(hipGetLastError());
@@ -1211,6 +1206,70 @@ struct PathCall {
     const GuideSrc* gd;
 };
 
+// The ready checks of the loop terms, asked by path_loop_run in this order: what an attachment asks of the call `c` on the tables `pt`
+// (`mol`: the rows that are stepped).  `on`: the term takes part - it is attached and the call records; a call it does not fit is refused.
+static int loop_fail(int code, const std::string& msg) { return fail(code, "path loop: " + msg); }
+static int chain_ready(const hd_handle* h, const hd_topology* topo, const PathCall& c, const PathTables& pt, int mol, bool* on) {
+    if (!(*on = c.record && topo->chain.dst != nullptr)) return HD_OK;
+    if (!h->d_chain_frame || h->chain_path_gen != pt.gen)
+        return loop_fail(HD_E_STATE, "a chain sink is attached but the chain tables are not set for the current path (hd_set_chain)");
+    if (h->chain_frames != topo->chain.frames)
+        return loop_fail(HD_E_INVALID, "the attached sink holds " + std::to_string(topo->chain.frames) + " frames, the chain tables were set for " +
+                                       std::to_string(h->chain_frames));
+    if (topo->chain.what == 1 && !h->d_chain_as)
+        return loop_fail(HD_E_STATE, "recording the data prediction needs the {alpha_t, sigma_t} rows (hd_set_chain)");
+    if (mol != topo->N) return loop_fail(HD_E_INVALID, "a chain sink records whole molecules only (mol_shape < N)");
+    return HD_OK;
+}
+
+static int restraint_ready(const hd_handle* h, const hd_topology* topo, const PathCall& c, const PathTables& pt, int mol, bool* on) {
+    if (!(*on = c.record && topo->rs.on)) return HD_OK;
+    const bool framed = topo->rs.frame == 1;
+    if (c.R && !framed)
+        return loop_fail(HD_E_INVALID, "restraints are attached to the topology, and inpainting takes none (it re-centres on the known fragments: "
+                                       "hd_restraint_detach)");
+    if (framed && !c.R)
+        return loop_fail(HD_E_INVALID, "the restraints are set to the known fragments' frame (hd_restraint_frame), which needs fixed fragments: an "
+                                       "inpainting call");
+    if (framed && topo->st.on)
+        return loop_fail(HD_E_INVALID, "steering is attached to the topology, and restraints in the known fragments' frame take none (hd_steer_detach)");
+    if (!h->rs_rows.d || h->rs_rows.path_gen != pt.gen)
+        return loop_fail(HD_E_STATE, "restraints are attached but their rows are not set for the current path (hd_set_restraint)");
+    if (mol != topo->N) return loop_fail(HD_E_INVALID, "restraints act on whole molecules only (mol_shape < N)");
+    return HD_OK;
+}
+
+static int steer_ready(const hd_handle* h, const hd_topology* topo, const PathCall& c, const PathTables& pt, int mol, bool* on) {
+    if (!(*on = c.record && topo->st.on)) return HD_OK;
+    if (!topo->rs.on)
+        return loop_fail(HD_E_STATE, "steering is attached to the topology but no restraints are (hd_restraint_attach): it weighs the particles by "
+                                     "their restraint energy");
+    if (!h->st_rows.d || h->st_rows.path_gen != pt.gen)
+        return loop_fail(HD_E_STATE, "steering is attached but its rows are not set for the current path (hd_set_steer)");
+    if (pt.form == 2)
+        return loop_fail(HD_E_INVALID, "steering needs a stochastic update, and multistep rows draw nothing (duplicated particles would never "
+                                       "diverge: hd_steer_detach)");
+    if (c.noise_rows != topo->B) return loop_fail(HD_E_INVALID, "steering needs every row's own noise (noise_rows must be B)");
+    return HD_OK;
+}
+
+static int diverse_ready(const hd_handle* h, const hd_topology* topo, const PathCall& c, const PathTables& pt, int mol, bool* on) {
+    if (!(*on = c.record && topo->dv.on)) return HD_OK;
+    if (c.R) return loop_fail(HD_E_INVALID, "diversity is attached to the topology, and inpainting takes none (hd_diversity_detach)");
+    if (mol != topo->N) return loop_fail(HD_E_INVALID, "diversity acts on whole molecules only (mol_shape < N)");
+    if (topo->st.on)
+        return loop_fail(HD_E_INVALID, "diversity and steering are both attached to the topology: a call takes one of them (hd_steer_detach / "
+                                       "hd_diversity_detach)");
+    if (!h->dv_rows.d || h->dv_rows.path_gen != pt.gen)
+        return loop_fail(HD_E_STATE, "diversity is attached but its rows are not set for the current path (hd_set_diversity)");
+    if (c.noise_rows == 1)
+        for (int k = c.k_lo; k < c.k_hi; ++k)
+            if (pt.noisy_h[(size_t)k])
+                return loop_fail(HD_E_INVALID, "diversity with one shared row of noise is allowed only on rows that draw nothing (noise_rows must be "
+                                               "B on a stochastic path)");
+    return HD_OK;
+}
+
 static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     const PathTables& pt = *c.pt;
     const GuideSrc* gd = c.gd;
@@ -1224,54 +1283,12 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     topo_use(topo, c.s);
     if (ntr == 0) return HD_OK;
     if (gd) HD_TRY(guide_buffers(h, topo));
-    const bool rec = c.record && topo->chain_dst != nullptr;
-    if (rec) {
-        if (!h->d_chain_frame || h->chain_path_gen != pt.gen)
-            return fail(HD_E_STATE, "path loop: a chain sink is attached but the chain tables are not set for the current path (hd_set_chain)");
-        if (h->chain_frames != topo->chain_frames)
-            return fail(HD_E_INVALID, "path loop: the attached sink holds " + std::to_string(topo->chain_frames) + " frames, the chain "
-                        "tables were set for " + std::to_string(h->chain_frames));
-        if (topo->chain_what == 1 && !h->d_chain_as)
-            return fail(HD_E_STATE, "path loop: recording the data prediction needs the {alpha_t, sigma_t} rows (hd_set_chain)");
-        if (mol != N) return fail(HD_E_INVALID, "path loop: a chain sink records whole molecules only (mol_shape < N)");
-    }
-    const bool rsn = c.record && topo->rs.on;
+    bool rec, rsn, stn, dvn;                                 // which terms take part: one ready check each, in this order
+    HD_TRY(chain_ready(h, topo, c, pt, mol, &rec));
+    HD_TRY(restraint_ready(h, topo, c, pt, mol, &rsn));
+    HD_TRY(steer_ready(h, topo, c, pt, mol, &stn));
+    HD_TRY(diverse_ready(h, topo, c, pt, mol, &dvn));
     const bool framed = rsn && topo->rs.frame == 1;
-    if (rsn) {
-        if (R && !framed) return fail(HD_E_INVALID, "path loop: restraints are attached to the topology, and inpainting takes none (it re-centres "
-                                                    "on the known fragments: hd_restraint_detach)");
-        if (framed && !R) return fail(HD_E_INVALID, "path loop: the restraints are set to the known fragments' frame (hd_restraint_frame), "
-                                                    "which needs fixed fragments: an inpainting call");
-        if (framed && topo->st_on) return fail(HD_E_INVALID, "path loop: steering is attached to the topology, and restraints in the known "
-                                                             "fragments' frame take none (hd_steer_detach)");
-        if (!h->rs_rows.d || h->rs_rows.path_gen != pt.gen)
-            return fail(HD_E_STATE, "path loop: restraints are attached but their rows are not set for the current path (hd_set_restraint)");
-        if (mol != N) return fail(HD_E_INVALID, "path loop: restraints act on whole molecules only (mol_shape < N)");
-    }
-    const bool stn = c.record && topo->st_on;
-    if (stn) {
-        if (!rsn) return fail(HD_E_STATE, "path loop: steering is attached to the topology but no restraints are (hd_restraint_attach): "
-                                          "it weighs the particles by their restraint energy");
-        if (!h->st_rows.d || h->st_rows.path_gen != pt.gen)
-            return fail(HD_E_STATE, "path loop: steering is attached but its rows are not set for the current path (hd_set_steer)");
-        if (form == 2) return fail(HD_E_INVALID, "path loop: steering needs a stochastic update, and multistep rows draw nothing "
-                                                 "(duplicated particles would never diverge: hd_steer_detach)");
-        if (c.noise_rows != topo->B) return fail(HD_E_INVALID, "path loop: steering needs every row's own noise (noise_rows must be B)");
-    }
-    const bool dvn = c.record && topo->dv_on;
-    if (dvn) {
-        if (R) return fail(HD_E_INVALID, "path loop: diversity is attached to the topology, and inpainting takes none (hd_diversity_detach)");
-        if (mol != N) return fail(HD_E_INVALID, "path loop: diversity acts on whole molecules only (mol_shape < N)");
-        if (topo->st_on) return fail(HD_E_INVALID, "path loop: diversity and steering are both attached to the topology: a call takes one "
-                                                   "of them (hd_steer_detach / hd_diversity_detach)");
-        if (!h->dv_rows.d || h->dv_rows.path_gen != pt.gen)
-            return fail(HD_E_STATE, "path loop: diversity is attached but its rows are not set for the current path (hd_set_diversity)");
-        if (c.noise_rows == 1)
-            for (int k = k_lo; k < c.k_hi; ++k)
-                if (pt.noisy_h[(size_t)k])
-                    return fail(HD_E_INVALID, "path loop: diversity with one shared row of noise is allowed only on rows that draw nothing "
-                                              "(noise_rows must be B on a stochastic path)");
-    }
     const uint8_t* parts = (R && topo->ip_parts_on) ? topo->ip_parts : nullptr;      // calls that do not inpaint ignore the attachment
     const int rounds = R ? R : 1;
     auto transition = [&](const LoopIO& io) -> int {         // all rounds of one transition; io.row is the path position
@@ -1286,14 +1303,14 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
             if (dvn) HD_TRY(diverse_launch(h, topo, io, io.z, topo->eps, topo->eps, h->dv_rows.d, nullptr));
             if (stn) HD_TRY(steer_launch(h, topo, io, io.z, topo->eps, h->st_rows.d, nullptr, io.draw_of(0, stride), c.seed,
                                          form == 3 ? topo->ms_hist : nullptr));
-            if (rec && j == rounds - 1 && topo->chain_what == 1) HD_TRY(chain_launch(h, topo, io, topo->eps));
+            if (rec && j == rounds - 1 && topo->chain.what == 1) HD_TRY(chain_launch(h, topo, io, topo->eps));
             const LoopIO::Draw d = io.draw_of(3 * j, stride);
             const NoiseSrc ns = make_noise(c.raw_x ? c.raw_x + io.ro * 3 : nullptr, c.raw_h ? c.raw_h + io.ro * h->F : nullptr, c.noise_rows,
                                            c.seed, io.base, d.value, share);
             HD_TRY(step_launch(h, topo, io, form, io.z, topo->eps, pt.d_coef + (size_t)io.row * step_row_width(form), 1, nullptr,
                                topo->ms_hist, topo->ms_hist, ns, d.word, mol, N, k_lo));
             if (R) HD_TRY(inpaint_round(h, topo, io, j, R, stride, c.seed, pt.d_coef_ip));
-            if (rec && j == rounds - 1 && topo->chain_what == 0) HD_TRY(chain_launch(h, topo, io, nullptr));
+            if (rec && j == rounds - 1 && topo->chain.what == 0) HD_TRY(chain_launch(h, topo, io, nullptr));
         }
         return HD_OK;
     };
@@ -1318,15 +1335,12 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     HD_TRY(replay_enter(h, c.s, &rs));
     HD_TRY(grow_ipdraw(h, rs, nd));
     if (R) HD_TRY(inpaint_buffers(h, topo));
-    PathKey key;
+    PathKey key{};
     key.raw_x = c.raw_x; key.raw_h = c.raw_h; key.has_ctx = c.context ? 1 : 0; key.mol_shape = ms; key.noise_rows = c.noise_rows;
     key.k_lo = c.raw_x ? k_lo : 0; key.resamplings = R; key.seed = c.seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
     key.path_gen = pt.gen; key.ip_gen = R ? h->ip_gen : 0; key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
-    key.rs = restraint_key(h, topo, rsn, framed);
     key.ip_parts = parts ? 1 : 0;
-    key.st_P = stn ? topo->st_P : 0; key.st_ess = stn ? topo->st_ess : 0.0; key.st_gen = stn ? topo->st_gen : 0;
-    key.st_rows_gen = stn ? h->st_rows.gen : 0;
-    key.dv_P = dvn ? topo->dv_P : 0; key.dv_gen = dvn ? topo->dv_gen : 0; key.dv_rows_gen = dvn ? h->dv_rows.gen : 0;
+    key.rs = restraint_key(h, topo, rsn, framed); key.st = steer_key(h, topo, stn); key.dv = diverse_key(h, topo, dvn);
     PathWords w;
     w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = R ? h->d_ipdraw : nullptr;
     w.tau = h->d_tau; w.t_idx = pt.d_t; w.s_idx = pt.d_s; w.K = K; w.T = T; w.nd = nd; w.stride = stride; w.chain = rec ? h->d_chain_dst : nullptr;
@@ -1344,8 +1358,8 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     const hipGraphExec_t* gx = &c.slot->exec;
     if (rec) {
         gx = &topo->g_chain.exec;
-        HD_TRY(replay_slot(h, rs, topo->g_chain, ChainKey{key, topo->chain_what, topo->chain_nv0, topo->chain_nv1, topo->chain_nb1, h->chain_gen},
-                           body));
+        const ChainSink& sk = topo->chain;
+        HD_TRY(replay_slot(h, rs, topo->g_chain, ChainKey{key, sk.what, sk.nv0, sk.nv1, sk.nb1, h->chain_gen}, body));
     } else {
         HD_TRY(replay_slot(h, rs, *c.slot, key, body));
     }
@@ -1359,7 +1373,7 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
         HIP_TRY(hipMemcpyAsync(topo->ip_fixed, c.fixed_mask, BN, hipMemcpyDeviceToDevice, rs));
         HIP_TRY(hipMemcpyAsync(topo->ip_known, c.xh_known, zbytes, hipMemcpyDeviceToDevice, rs));
     }
-    hipLaunchKernelGGL(k_path_state, dim3(1), dim3(64), 0, rs, w, k_lo, (unsigned long long)c.sample_id_base, topo->chain_dst);
+    hipLaunchKernelGGL(k_path_state, dim3(1), dim3(64), 0, rs, w, k_lo, (unsigned long long)c.sample_id_base, topo->chain.dst);
     HD_TRY(replay_run(*gx, ntr, rs));
     HIP_TRY(hipMemcpyAsync(c.z, topo->zbuf, zbytes, hipMemcpyDeviceToDevice, rs));
     return replay_leave(h, c.s, rs);

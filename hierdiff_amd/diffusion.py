@@ -18,6 +18,7 @@ nll, forward).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -27,7 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from . import restraints as restraints_mod
+from . import diversity as diversity_mod, restraints as restraints_mod, steering as steering_mod
 from .distributions import DistributionNodes
 from .dynamics import EGNN_dynamics_QM9, Topology, _ptr, _stream
 from .geom_stats import GEOM_FRAGMENT_HISTOGRAM
@@ -638,8 +639,7 @@ class DiffusionQM9(_Base):
             raise ValueError(f"{what}: steering needs every row's own noise (fix_noise shares one row: duplicated particles would "
                              "never diverge)")
         if pl.diversity is not None and fix_noise:
-            from . import diversity
-            if diversity.stochastic(pl.eta):
+            if diversity_mod.stochastic(pl.eta):
                 raise ValueError(f"{what}: diversity with fix_noise is allowed only on a path that draws nothing (eta = 0, solver "
                                  "'dpm2m'): shared noise would pull the rows of a group together again")
         return pl
@@ -653,7 +653,7 @@ class DiffusionQM9(_Base):
     def _upload_path(self, tabs, key, build, upload):
         """The path tables on the handle, cached per (schedule table, key): `build()` computes them, `upload(tables)` sets them.  One
         cache for both directions (hd_set_path / hd_set_path_multistep and hd_set_path_up fill the same tables): whichever was set
-        last is the one that is cached.  `_chain_open` and `_restrain_open` key their uploads on the identity of the cached tables."""
+        last is the one that is cached.  `_rows_open` keys the uploads of the loop terms on the identity of the cached tables."""
         hit = self.__dict__.get("_path_cache")
         if hit is None or hit[0] is not tabs or hit[1] != key:
             pt = build()
@@ -684,22 +684,36 @@ class DiffusionQM9(_Base):
         return self._upload_path(tabs, (tuple(path), ("sde2m" if eta.stochastic else "dpm2m", bool(eta.lower_order_final)) if ms else float(eta)),
                                  lambda: paths.path_tables(tabs["gamma"], path, eta), upload)
 
-    # ------------------------------------------------------------------ recording a trajectory (the reference's sample_chain)
+    # ------------------------------------------------------------------ what a call attaches to its topology (the loop terms)
+    def _rows_open(self, name: str, key, build, setter: str):
+        """The per-transition rows of the loop term `name`, behind the path tables `_path_tables` has just set: `build(pt)` gives the
+        arguments of the library's `setter`.  Once per (path tables, key): `_row_caches[name]` holds what was uploaded last."""
+        pt = self._path_cache[2]
+        caches = self.__dict__.get("_row_caches") or {}
+        hit = caches.get(name)
+        if hit is None or hit[0] is not pt or hit[1] != key:
+            args = build(pt)
+            caches.pop(name, None)
+            _lib.check(getattr(_lib.load(), setter)(*args), setter)
+            caches[name] = (pt, key)
+        self._row_caches = caches
+
+    @staticmethod
+    def _row_args(handle, tabs, pt, rows_of):
+        """(handle, K, rows [K, w] float32) for a row setter: `rows_of(gamma, path)` on the grid indices of the path tables `pt`."""
+        rows = np.ascontiguousarray(rows_of(tabs["gamma"], [int(t) for t in pt["t_idx"]] + [int(pt["s_idx"][-1])]))
+        return handle, int(rows.shape[0]), rows.ctypes.data_as(C.POINTER(C.c_float))
+
     def _chain_open(self, handle, topo, tabs, cf, what: int, B: int, N: int, dev, chain=None):
         """The sink [keep, B, N, D] of a recording call (`chain`: the one an earlier piece of the same chain wrote to), attached to
-        `topo` (hd_chain_attach) behind the tables of the path that `_path_tables` has just set (hd_set_chain, once per (path
-        tables, frame table)).  The caller detaches (hd_chain_detach)."""
-        pt = self._path_cache[2]
+        `topo` (hd_chain_attach) behind the path's frame table (hd_set_chain, once per (path tables, frame table)).  The caller detaches."""
         keep = len(cf.frame_t)
-        key = (tuple(cf.frame_of), keep)
-        hit = self.__dict__.get("_chain_cache")
-        if hit is None or hit[0] is not pt or hit[1] != key:
+
+        def build(pt):
             als = np.ascontiguousarray([self._alpha_sigma(tabs, int(t)) for t in pt["t_idx"]], dtype=np.float32)
             fo = np.ascontiguousarray(cf.frame_of, dtype=np.int32)
-            self._chain_cache = None
-            _lib.check(_lib.load().hd_set_chain(handle, int(fo.shape[0]), fo.ctypes.data_as(C.POINTER(C.c_int)),
-                                                als.ctypes.data_as(C.POINTER(C.c_float)), keep), "hd_set_chain")
-            self._chain_cache = (pt, key)
+            return handle, int(fo.shape[0]), fo.ctypes.data_as(C.POINTER(C.c_int)), als.ctypes.data_as(C.POINTER(C.c_float)), keep
+        self._rows_open("chain", (tuple(cf.frame_of), keep), build, "hd_set_chain")
         if chain is None:
             chain = torch.zeros((keep, B, N, self.n_dims + self.in_node_nf), device=dev, dtype=torch.float32)
         _lib.check(_lib.load().hd_chain_attach(topo.ptr, chain.data_ptr(), keep, int(what), float(self.norm_values[0]),
@@ -707,76 +721,31 @@ class DiffusionQM9(_Base):
         return chain
 
     def _restrain_open(self, handle, topo, tabs, rr, B: int, dev):
-        """Attach the restraints of a resolved call (`restraints.Resolved`) to `topo` behind the rows of the path that `_path_tables`
-        has just set (hd_set_restraint, once per (path tables, schedule, clip)).  The caller detaches (hd_restraint_detach)."""
-        from . import restraints
-        pt = self._path_cache[2]
-        key = rr.key()
-        hit = self.__dict__.get("_restraint_cache")
-        if hit is None or hit[0] is not pt or hit[1] != key:
-            path = [int(t) for t in pt["t_idx"]] + [int(pt["s_idx"][-1])]
-            rows = np.ascontiguousarray(restraints.lambda_rows(tabs["gamma"], path, rr.schedule, rr.clip, float(self.norm_values[0])))
-            self._restraint_cache = None
-            _lib.check(_lib.load().hd_set_restraint(handle, int(rows.shape[0]), rows.ctypes.data_as(C.POINTER(C.c_float))),
-                       "hd_set_restraint")
-            self._restraint_cache = (pt, key)
+        """Attach the restraints of a resolved call (`restraints.Resolved`) to `topo` behind their rows (hd_set_restraint, once per
+        (path tables, schedule, clip)).  The caller detaches (`Restraints.detach`)."""
+        nv0, nv1 = float(self.norm_values[0]), float(self.norm_values[1])
+        self._rows_open("restraint", rr.key(), lambda pt: self._row_args(
+            handle, tabs, pt, lambda g, path: restraints_mod.lambda_rows(g, path, rr.schedule, rr.clip, nv0)), "hd_set_restraint")
         rr.rs.check_batch(B)
         import weakref
         rr.rs._model = weakref.ref(self)
-        nv0, nv1 = float(self.norm_values[0]), float(self.norm_values[1])
         rr.rs.attach(topo, rr.scale, nv0, dev, _stream(dev), rr.frame,
-                     feat=(nv1, float(self.norm_biases[1] or 0.0), restraints.feature_ratio(rr.schedule, nv0, nv1)))
+                     feat=(nv1, float(self.norm_biases[1] or 0.0), restraints_mod.feature_ratio(rr.schedule, nv0, nv1)))
 
     def _steer_open(self, handle, topo, tabs, st, reset: bool, dev):
-        """Attach the steering of a resolved call (`steering.Steer`) to `topo` behind the rows of the path that `_path_tables` has
-        just set (hd_set_steer, once per (path tables, beta, schedule)).  `reset`: the call starts a chain (k_lo = 0); a later
-        piece continues on the state the topology holds.  The caller closes (`_steer_close`)."""
-        from . import steering
-        pt = self._path_cache[2]
-        key = st.key()
-        hit = self.__dict__.get("_steer_cache")
-        if hit is None or hit[0] is not pt or hit[1] != key:
-            path = [int(t) for t in pt["t_idx"]] + [int(pt["s_idx"][-1])]
-            rows = np.ascontiguousarray(steering.beta_rows(tabs["gamma"], path, st))
-            self._steer_cache = None
-            _lib.check(_lib.load().hd_set_steer(handle, int(rows.shape[0]), rows.ctypes.data_as(C.POINTER(C.c_float))), "hd_set_steer")
-            self._steer_cache = (pt, key)
-        _lib.check(_lib.load().hd_steer_attach(topo.ptr, st.P, st.ess, int(bool(reset)), _stream(dev)), "hd_steer_attach")
-
-    def _steer_close(self, topo, st, B: int, dev, ok: bool):
-        """Detach (hd_steer_detach) and, behind a call that ran, keep the state it left as `steer_last` (hd_steer_read)."""
-        from . import steering
-        lib = _lib.load()
-        _lib.check(lib.hd_steer_detach(topo.ptr), "hd_steer_detach")
-        if not ok:
-            return
-        G = B // st.P
-        logw = torch.empty(B, device=dev, dtype=torch.float64)
-        root = torch.empty(B, device=dev, dtype=torch.int32)
-        stats = torch.empty((G, 3), device=dev, dtype=torch.float64)
-        _lib.check(lib.hd_steer_read(topo.ptr, logw.data_ptr(), None, root.data_ptr(), None, stats.data_ptr(), _stream(dev)),
-                   "hd_steer_read")
-        stats = stats.cpu()
-        self.steer_last = steering.Result(steering.normalise(logw.cpu(), st.P), root.cpu().long(), torch.arange(B) // st.P,
-                                          stats[:, 0].long(), stats[:, 1].clone(), stats[:, 2].long())
+        """Attach the steering of a resolved call (`steering.Steer`) to `topo` behind its rows (hd_set_steer, once per (path tables,
+        beta, schedule)).  `reset`: the call starts a chain (k_lo = 0), else it continues.  The caller closes (`steering.close`)."""
+        self._rows_open("steer", st.key(), lambda pt: self._row_args(handle, tabs, pt, lambda g, path: steering_mod.beta_rows(g, path, st)),
+                        "hd_set_steer")
+        steering_mod.attach(topo, st, reset, _stream(dev))
 
     def _diversity_open(self, handle, topo, tabs, dv, dev):
-        """Attach the diversity of a resolved call (`diversity.Diversity`) to `topo` behind the rows of the path that `_path_tables` has
-        just set (hd_set_diversity, once per (path tables, schedule, clip)).  The caller detaches (hd_diversity_detach)."""
-        from . import diversity
-        pt = self._path_cache[2]
-        key = dv.key()
-        hit = self.__dict__.get("_diversity_cache")
-        if hit is None or hit[0] is not pt or hit[1] != key:
-            path = [int(t) for t in pt["t_idx"]] + [int(pt["s_idx"][-1])]
-            rows = np.ascontiguousarray(diversity.rows(tabs["gamma"], path, dv, float(self.norm_values[0])))
-            self._diversity_cache = None
-            _lib.check(_lib.load().hd_set_diversity(handle, int(rows.shape[0]), rows.ctypes.data_as(C.POINTER(C.c_float))),
-                       "hd_set_diversity")
-            self._diversity_cache = (pt, key)
-        sc = np.ascontiguousarray(dv.scale.numpy(), dtype=np.float32)
-        _lib.check(_lib.load().hd_diversity_attach(topo.ptr, dv.P, dv.strength, dv.length, sc.ctypes.data_as(C.POINTER(C.c_float)),
-                                                   int(sc.shape[0]), float(self.norm_values[0]), _stream(dev)), "hd_diversity_attach")
+        """Attach the diversity of a resolved call (`diversity.Diversity`) to `topo` behind its rows (hd_set_diversity, once per (path
+        tables, schedule, clip)).  The caller detaches (hd_diversity_detach)."""
+        nv0 = float(self.norm_values[0])
+        self._rows_open("diversity", dv.key(), lambda pt: self._row_args(handle, tabs, pt, lambda g, path: diversity_mod.rows(g, path, dv, nv0)),
+                        "hd_set_diversity")
+        diversity_mod.attach(topo, dv.P, dv.strength, dv.length, dv.scale, nv0, _stream(dev))
 
     def _diversity_result(self, pl, x, node_mask):
         """`diversity_last` of a diverse call's returned x: Phi and the aligned RMSD matrix per group (hd_diversity_energy), attached as
@@ -784,10 +753,9 @@ class DiffusionQM9(_Base):
         dv = getattr(pl, "diversity", None)
         if dv is None:
             return
-        from . import diversity
-        phi, rmsd = diversity._device_energy(x, node_mask, dv.P, dv.length, dv.strength, self, "diversity",
+        phi, rmsd = diversity_mod._device_energy(x, node_mask, dv.P, dv.length, dv.strength, self, "diversity",
                                              _attach=(dv.scale, float(self.norm_values[0])))
-        self.diversity_last = diversity.result(phi, rmsd)
+        self.diversity_last = diversity_mod.result(phi, rmsd)
 
     def _chain_times(self, keep_frames, t_start=None, inpaint: bool = False, **few):
         """[keep] the grid index every frame of a recording call has arrived at (`Plan.chain_t`): host arithmetic only."""
@@ -951,11 +919,9 @@ class DiffusionQM9(_Base):
         `tail`, `topo_loop`; inpainting: `_inpaint_setup`) on top of it."""
         dev = node_mask.device
         if pl is not None and pl.steer is not None:   # rows of a group interact: equal masks, contexts and tables, checked on the host
-            from . import steering
-            steering.check_groups(pl.steer, node_mask, context, pl.restraints.rs, pl.restraints.scale, what)
+            steering_mod.check_groups(pl.steer, node_mask, context, pl.restraints.rs, pl.restraints.scale, what)
         if pl is not None and pl.diversity is not None:
-            from . import diversity
-            diversity.check_groups(pl.diversity, node_mask, context, what)
+            diversity_mod.check_groups(pl.diversity, node_mask, context, what)
         if dev.type != "cuda":
             raise _lib.HierDiffHipError(f"{what} runs only on an MI355X (no CPU fallback)")
         h = self._lib_handle()
@@ -979,7 +945,7 @@ class DiffusionQM9(_Base):
         (z, chain - the sink of a recording plan, kept in `st` for the next piece - or None).  `noise` = (randn_x, randn_h, rows,
         seed, sample id base): injected rows, or None, None and the generator's key.  `inpaint` = (fixed u8 [B*N], known xh, R) or,
         for partial masks, (fixed_x u8 [B*N], known xh, R, fixed_h u8 [B*N*F]): the channel bytes are attached like the restraints.
-        Restraints, then the sink, are attached to the topology for the time of the loop.  The one place that picks the loop:
+        The plan's loop terms are attached to the topology for the time of the loop.  The one place that picks the loop:
         guided -> hd_sample_path_guided; a path -> hd_sample_path(_inpaint); else the every-step hd_sample_loop(_inpaint), whose
         steps count down from T."""
         lib, topo = _lib.load(), st.topo_loop
@@ -988,18 +954,23 @@ class DiffusionQM9(_Base):
         zz = z if st.tail is None else torch.cat([z, st.tail], dim=1).contiguous()      # a pocket's fixed rows ride along
         mol = -1 if st.tail is None else st.N
         common = (_ptr(rx), _ptr(rh), rows, seed, base, int(self.use_graph))
-        steer, ran = getattr(pl, "steer", None), False
-        dvs = getattr(pl, "diversity", None)
-        try:
+        steer, dvs, ran = getattr(pl, "steer", None), getattr(pl, "diversity", None), False
+        # every term the plan asks for is closed behind the loop - also when its opening, the loop or another close raises
+        with contextlib.ExitStack() as closes:
             if pl.restraints is not None:
+                closes.callback(pl.restraints.rs.detach, topo)
                 self._restrain_open(st.h, topo, st.tabs, pl.restraints, st.B, st.dev)
             if steer is not None:
+                closes.callback(lambda: steering_mod.close(self, topo, steer, st.B, st.dev, st.stream, ran))
                 self._steer_open(st.h, topo, st.tabs, steer, int(k_lo) == 0, st.dev)
             if dvs is not None:
+                closes.callback(lambda: _lib.check(lib.hd_diversity_detach(topo.ptr), "hd_diversity_detach"))
                 self._diversity_open(st.h, topo, st.tabs, dvs, st.dev)
             if pl.frames is not None:
+                closes.callback(lambda: _lib.check(lib.hd_chain_detach(topo.ptr), "hd_chain_detach"))
                 st.chain = self._chain_open(st.h, topo, st.tabs, pl.frames, pl.record, st.B, st.N, st.dev, st.chain)
             if parts is not None:
+                closes.callback(lambda: _lib.check(lib.hd_inpaint_parts(st.h, topo.ptr, None, st.stream), "hd_inpaint_parts"))
                 _lib.check(lib.hd_inpaint_parts(st.h, topo.ptr, parts.data_ptr(), st.stream), "hd_inpaint_parts")
             if st.g is not None:
                 _lib.check(lib.hd_sample_path_guided(st.h, topo.ptr, zz.data_ptr(), st.ctx.data_ptr(), st.g.ctx_u.data_ptr(),
@@ -1015,17 +986,6 @@ class DiffusionQM9(_Base):
                     (lib.hd_sample_loop, "hd_sample_loop", pl.K - k_lo, pl.K - k_hi)
                 _lib.check(fn(st.h, topo.ptr, zz.data_ptr(), _ptr(st.ctx), mol, int(lo), int(hi), *common, st.stream), name)
             ran = True
-        finally:
-            if parts is not None:
-                _lib.check(lib.hd_inpaint_parts(st.h, topo.ptr, None, st.stream), "hd_inpaint_parts")
-            if steer is not None:
-                self._steer_close(topo, steer, st.B, st.dev, ran)
-            if dvs is not None:
-                _lib.check(lib.hd_diversity_detach(topo.ptr), "hd_diversity_detach")
-            if pl.frames is not None:
-                _lib.check(lib.hd_chain_detach(topo.ptr), "hd_chain_detach")
-            if pl.restraints is not None:
-                pl.restraints.rs.detach(topo)
         return (zz if st.tail is None else zz[:, :st.N].contiguous()), st.chain
 
     def _decode(self, st, z, node_mask, edge_mask, fix_noise, noise, chain=None, inpaint=None, eps=None):
@@ -1482,10 +1442,8 @@ class DiffusionQM9(_Base):
         The inversion stays first order: solver="dpm2m" or "sde2m" raises ValueError (the model's `sample_solver` is not consulted)."""
         from . import paths, restraints as _rs
         _rs.refuse(self, "encode", restraints, ": the inversion follows the network's own flow")
-        from . import steering as _st
-        _st.refuse(self, "encode")
-        from . import diversity as _dv
-        _dv.refuse(self, "encode", None, ": the inversion follows the network's own flow")
+        steering_mod.refuse(self, "encode")
+        diversity_mod.refuse(self, "encode", None, ": the inversion follows the network's own flow")
         if paths.check_solver(solver) is not None:
             raise ValueError(f"encode: the inversion is first order (eta = 0 upwards); solver {solver!r} is not supported")
         t_end = self._grid_index(self.T if t_end is None else t_end, 1, "t_end")
@@ -1694,11 +1652,9 @@ class DiffusionQM9(_Base):
             if chain_t is not None:
                 self._chain_into(part, got[2], [int(nm[i].sum()) for i in range(nm.shape[0])], chain_t)
             if pl.steer is not None:
-                from . import steering
-                steering.into(part, self.steer_last, group0=lo // pl.steer.P)
+                steering_mod.into(part, self.steer_last, group0=lo // pl.steer.P)
             if dv_all is not None:
-                from . import diversity
-                diversity.into(part, self.diversity_last, group0=lo // dv_all.P)
+                diversity_mod.into(part, self.diversity_last, group0=lo // dv_all.P)
             out.extend(part)
         return out
 
@@ -1712,10 +1668,8 @@ class DiffusionQM9(_Base):
         Returns a list of `frames` results.  Mechanism only: what lies between two molecules is a property of the weights."""
         from . import scoring, restraints as _rs
         _rs.refuse(self, "interpolate", restraints, ": its frames are reconstructions of the interpolated latents")
-        from . import steering as _st
-        _st.refuse(self, "interpolate")
-        from . import diversity as _dv
-        _dv.refuse(self, "interpolate", None, ": its frames are reconstructions of the interpolated latents")
+        steering_mod.refuse(self, "interpolate")
+        diversity_mod.refuse(self, "interpolate", None, ": its frames are reconstructions of the interpolated latents")
         device = torch.device(device)
         if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or int(frames) < 2:
             raise ValueError(f"frames must be an integer >= 2, got {frames!r}")
@@ -1890,8 +1844,7 @@ class DiffusionQM9(_Base):
         from . import restraints as _rs
         if not _rs.check_frame(self, restraint_frame):
             _rs.refuse(self, "sample_inpaint", restraints, ": inpainting re-centres on the known fragments, so its frame moves")
-        from . import steering as _st
-        _st.refuse(self, "sample_inpaint")
+        steering_mod.refuse(self, "sample_inpaint")
         B, N = self._batch_of(node_mask)
         pl = self._plan("sample_inpaint", "inpaint", B=B, N=N, **given(locals()))            # every keyword error before any shape check
         st = self._inpaint_setup(node_mask, fixed_mask, x_known, h_known, context, resamplings, edge_mask, pl, fixed_x_mask, fixed_h_mask)
@@ -1936,8 +1889,7 @@ class DiffusionQM9(_Base):
         from . import restraints as _rs
         if not _rs.check_frame(self, restraint_frame):
             _rs.refuse(self, "sample_grow", restraints, ": inpainting re-centres on the known fragments, so its frame moves")
-        from . import steering as _st
-        _st.refuse(self, "sample_grow")
+        steering_mod.refuse(self, "sample_grow")
         few = given(locals())
         framed = _rs.check_frame(self, restraint_frame)
         pl0 = self._plan("sample_grow", "inpaint", **(dict(B=len(known) or None) if framed else {}), **few)     # argument errors first
@@ -2091,11 +2043,9 @@ class DiffusionQM9(_Base):
             for i in range(num_samples):
                 restraints_mod.entries_into(out[i], ent, i, sample_n[i])
         if pl.steer is not None:
-            from . import steering
-            steering.into(out, self.steer_last)
+            steering_mod.into(out, self.steer_last)
         if pl.diversity is not None:
-            from . import diversity
-            diversity.into(out, self.diversity_last)
+            diversity_mod.into(out, self.diversity_last)
         return out
 
     def sample_batches(self, batch_size, num_batches, device, context_range=None, protein_data_all=None,
@@ -2117,10 +2067,8 @@ class DiffusionQM9(_Base):
         device = torch.device(device)
         from . import restraints as _rs
         _rs.refuse(self, "sample_batches", restraints, ": the batches' padded widths and molecule counts differ (use sample)")
-        from . import steering as _st
-        _st.refuse(self, "sample_batches")
-        from . import diversity as _dv
-        _dv.refuse(self, "sample_batches", None, ": the batches' molecule counts differ (use sample)")
+        steering_mod.refuse(self, "sample_batches")
+        diversity_mod.refuse(self, "sample_batches", None, ": the batches' molecule counts differ (use sample)")
         # classifier-free guidance (`sample_from_masks`): guidance_scale may also be a list / tuple of scales cycled per batch the way
         # context_range is; inside a merged device batch it becomes one scale per molecule
         from . import guidance

@@ -133,7 +133,6 @@ def _device_energy(x, node_mask, P: int, length: float, strength: float, model, 
     call attached keeps its cached graph.)"""
     if model is None:
         raise ValueError(f"{what} on a device needs model= (the DiffusionQM9 that owns the library handle)")
-    import ctypes as C
     from . import _lib
     from .dynamics import _stream
     dev = x.device
@@ -142,10 +141,8 @@ def _device_energy(x, node_mask, P: int, length: float, strength: float, model, 
     topo = model.dynamics.topology(node_mask.to(dev), None, B, N)
     xs = x.detach().to(torch.float32).contiguous()
     scale, nv0 = (torch.ones(1), 1.0) if _attach is None else _attach
-    sc = np.ascontiguousarray(torch.as_tensor(scale, dtype=torch.float32).reshape(-1).numpy())
     lib = _lib.load()
-    _lib.check(lib.hd_diversity_attach(topo.ptr, P, float(strength), float(length), sc.ctypes.data_as(C.POINTER(C.c_float)),
-                                       int(sc.shape[0]), float(nv0), stream), "hd_diversity_attach")
+    attach(topo, P, strength, length, scale, nv0, stream)
     try:
         phi = torch.empty(B // P, device=dev, dtype=torch.float64)
         rmsd = torch.empty((B // P, P, P), device=dev, dtype=torch.float64)
@@ -153,6 +150,15 @@ def _device_energy(x, node_mask, P: int, length: float, strength: float, model, 
         return phi, rmsd
     finally:
         _lib.check(lib.hd_diversity_detach(topo.ptr), "hd_diversity_detach")
+
+
+def attach(topo, P: int, strength: float, length: float, scale, nv0: float, stream) -> None:
+    """Attach diversity to `topo` (hd_diversity_attach): P rows per group, kappa, l, the per-group scales (host values) and nv0."""
+    import ctypes as C
+    from . import _lib
+    sc = np.ascontiguousarray(torch.as_tensor(scale, dtype=torch.float32).reshape(-1).numpy())
+    _lib.check(_lib.load().hd_diversity_attach(topo.ptr, int(P), float(strength), float(length), sc.ctypes.data_as(C.POINTER(C.c_float)),
+                                               int(sc.shape[0]), float(nv0), stream), "hd_diversity_attach")
 
 
 def kabsch_rotation(S: torch.Tensor) -> torch.Tensor:

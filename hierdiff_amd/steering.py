@@ -195,6 +195,28 @@ def normalise(logw: torch.Tensor, P: int) -> torch.Tensor:
     return out.reshape(-1)
 
 
+def attach(topo, st: Steer, reset: bool, stream) -> None:
+    """Attach the steering `st` to `topo` (hd_steer_attach).  `reset`: start a chain; else continue on the state the topology holds."""
+    from . import _lib
+    _lib.check(_lib.load().hd_steer_attach(topo.ptr, st.P, st.ess, int(bool(reset)), stream), "hd_steer_attach")
+
+
+def close(model, topo, st: Steer, B: int, dev, stream, ran: bool) -> None:
+    """Detach (hd_steer_detach) and, behind a call that `ran`, keep the state it left as `model.steer_last` (hd_steer_read)."""
+    from . import _lib
+    lib = _lib.load()
+    _lib.check(lib.hd_steer_detach(topo.ptr), "hd_steer_detach")
+    if not ran:
+        return
+    logw = torch.empty(B, device=dev, dtype=torch.float64)
+    root = torch.empty(B, device=dev, dtype=torch.int32)
+    stats = torch.empty((B // st.P, 3), device=dev, dtype=torch.float64)
+    _lib.check(lib.hd_steer_read(topo.ptr, logw.data_ptr(), None, root.data_ptr(), None, stats.data_ptr(), stream), "hd_steer_read")
+    stats = stats.cpu()
+    model.steer_last = Result(normalise(logw.cpu(), st.P), root.cpu().long(), torch.arange(B) // st.P, stats[:, 0].long(),
+                              stats[:, 1].clone(), stats[:, 2].long())
+
+
 def into(results, res: Result, lo: int = 0, group0: int = 0) -> None:
     """'steer_logw', 'steer_root', 'steer_group' into the dicts of rows lo .. lo + len(results) - 1 of `res`."""
     for i, r in enumerate(results):

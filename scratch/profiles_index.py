@@ -76,6 +76,9 @@ RULES = [
     (r"r06_ablate_fp16x3_no_mfma\.log", "fp16x3 edge kernel of the measurement build: shipped / no MFMA (vector side alone, bit 1024) / matrix side alone / no epilogue, same box", "DESIGN 12 item 2, EXPERIMENTS W: wave specialisation cannot clear 6 %"),
     (r"r06_ab_gemm_rows\.log", "same-box A/B of the node-level training GEMMs: k_tgemm vs the row-resident k_tgemm_rows (slower; removed)", "EXPERIMENTS V"),
     (r"r06_ab_dw2_two_chunks\.log", "same-box A/B of k_dw2_f16 with one vs two chunks in flight (slower; reverted)", "EXPERIMENTS V"),
+    (r"attach_state_bits_(parent|result)\.json", "`scratch/sampling_bits.py` with its `terms` group (steered + restrained, diverse, diverse + restrained + features, recorded diverse at B = 4 as two groups of 2, steps = 4, `use_graph` on and off): 3733 rows on the parent commit's package and library (`parent`) and on this commit's (`result`), MI355X; the two files are identical", "EXPERIMENTS AU"),
+    (r"attach_state_(restraint_state|diversity|chain)_timing_(parent1|parent2|result)\.json", "`scratch/restraint_state_timing.py` / `diversity_timing.py` / `chain_timing.py` (the latter two fp32 and fp16x3, 3 repeats, no Python loop) on the parent commit (`parent1`, `parent2`) and on this commit (`result`): fresh processes on one MI355X per script, in the order parent1, result, parent2; `scratch/ab_verdict.py` gives the verdict per kind", "EXPERIMENTS AU"),
+    (r"attach_state_bench\.json", "`scratch/bench_ab_compare.py` over three `bench.py --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline --no-configs` lines, the parent commit twice and the refactored host code once (before its last compaction; device code byte-identical to this commit's), one MI355X: every headline figure of the result inside the range of the parent's two", "EXPERIMENTS AU"),
     (r"sampling_bits_(parent|result)\.json", "`scratch/sampling_bits.py`: SHA-256 of what every Python sampling entry point returns over the option matrix of tests/make_golden_dispatch.py, before / after the plan / state / run / decode split; the two files are identical", "DESIGN 5a, EXPERIMENTS AE"),
     (r"launch_selectors_trace_diff\.txt", "`scratch/launch_trace_driver.py` under `rocprofv3 --kernel-trace` with the parent's (c749001) and the result's library, one MI355X, one call, compared per dispatch by `scratch/launch_trace_diff.py` (kernel name, grid, workgroup size, LDS size, in dispatch order): the driver's result checksums, the statement that the diff is empty, dispatches and distinct launch shapes per kernel name", "DESIGN 4 (which instantiation a launch runs), EXPERIMENTS AS"),
     (r"launch_selectors_bench\.json", "`bench.py --gpus 1 --steps 2 --warmup 1 --full --no-cpu-baseline`, eager and `--graph`, the parent's (c749001) and the result's library alternating on one MI355X in one call, reduced by `scratch/bench_ab_compare.py`: every figure of the JSON lines per run and whether the result's values lie within the range of the parent's own repeats", "EXPERIMENTS AS"),

@@ -15,6 +15,8 @@ Behind the scoring rows, the single-step ABI paths that no loop reaches (`steps_
 tests/sampling_reference.py (coef_rows = B, mol_shape < N with out_stride = mol, shared noise, in place), hd_multistep_step and
 hd_multistep_sde_step with host rows at the shapes `wrap`, `F1`, `B1`, `pocket` of tests/test_gpu_sde_solver.py and the masks of
 tests/test_gpu_solver.py, injected, shared and generated noise, aliased outputs - inputs from those tests' own generators.
+Behind them, the loop terms the matrix does not attach (`terms_group`): B = 4, sizes [5, 5, 5, 5] as two groups of 2, steps = 4 on the same
+model - steered + restrained, diverse, diverse + restrained + features, recorded diverse - with `use_graph` on and off, hashed as the rows above.
 A row the library refuses before it launches anything (solver "dpm2m" from k_lo > 0 without the transition before it) holds
 "HD_E_STATE"; any other library error ends the run.
 `--out` holds, per `use_graph` value and entry point, the number of rows, how they ended, the warm builds summed, and one SHA-256 over
@@ -140,6 +142,34 @@ def steps_group():
     return out
 
 
+def terms_group(case):
+    """{row name: {tensor: sha256}} of the steered and diverse calls, `use_graph` on and off."""
+    from hierdiff_amd.diversity import Diversity
+    from hierdiff_amd.restraints import Features, FeatureSum, Restraints
+    m = case.model
+    B, N, F = 4, 5, int(m.in_node_nf)
+    nm = torch.ones(B, N, 1, dtype=torch.bool, device=case.device)
+    ctx = torch.tensor([0.25, 0.25, -0.5, -0.5], device=case.device).reshape(B, 1, 1).expand(B, N, 1).contiguous()
+    rs = lambda **kw: Restraints(obstacles=[[0.0, 0.0, 0.0, 1.0, 1.0]], pairs=[[0, 1, 0.5, 1.5, 1.0]], anchors=[[0, 0.0, 0.0, 0.0, 0.5, 1.0]], **kw)
+    feat = Features(lo=[[-0.5] * F] * 2, hi=[[0.5] * F] * 2, k=1.0, sums=[FeatureSum([1.0] * F, lo=-1.0, hi=1.0, reduce="mean")])
+    dv = lambda: Diversity(particles=2, length=1.0, strength=4.0, scale=[1.0, 0.5], clip=0.3)
+    kinds = {
+        "steered+restrained": lambda: dict(restraints=rs(), restraint_scale=0.5, restraint_clip=0.3, particles=2, steer_scale=1.0, eta=1.0),
+        "diverse": lambda: dict(diversity=dv()),
+        "diverse+restrained+features": lambda: dict(diversity=dv(), restraints=rs(features=feat), restraint_scale=0.5, restraint_clip=0.3),
+        "recorded diverse": lambda: dict(diversity=dv(), keep_frames=2),
+    }
+    out = {}
+    for graph in (True, False):
+        m.use_graph = graph
+        for kind, kw in kinds.items():
+            for call in ("first", "second"):
+                got = m.sample_from_masks(nm, None, ctx, sample_id_base=3, steps=4, **kw())
+                torch.cuda.synchronize()
+                out[f"graph={int(graph)}|{kind}|{call}"] = digests(got)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
@@ -181,6 +211,9 @@ def main():
     for name, sha in steps_group().items():
         res["rows"][f"steps|{name.split('|')[0]}|{name}"] = {"sha256": sha}
     print(f"steps: {len(res['rows'])} rows", flush=True)
+    for name, sha in terms_group(case).items():
+        res["rows"][f"terms|sample_from_masks|{name}"] = {"sha256": sha}
+    print(f"terms: {len(res['rows'])} rows", flush=True)
     groups = {}
     for name, row in res["rows"].items():
         g = groups.setdefault("|".join(name.split("|")[:2]), {"rows": 0, "ended": {}, "warm_builds": [0] * len(COUNTERS), "sha256": hashlib.sha256()})

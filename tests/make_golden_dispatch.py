@@ -34,7 +34,7 @@ LOOPS = {
     "hd_sample_path_guided": "h topo z ctx ctx_u w w_rows phi k_lo k_hi rx rh rows seed base use_graph fixed known R stream".split(),
 }
 POINTERS = {"z", "ctx", "ctx_u", "w", "rx", "rh", "fixed", "known"}
-CACHES = ("_path_cache", "_chain_cache", "_restraint_cache", "_inpaint_tabs")
+CACHES = ("_path_cache", "_row_caches", "_inpaint_tabs")
 
 
 class Reached(Exception):

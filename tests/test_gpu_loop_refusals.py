@@ -1,7 +1,9 @@
 """GPU tier (-m gpu): what the five sampling entry points and hd_nll_terms answer to calls they refuse - return code and
 hd_last_error text, record for record against tests/golden/loop_refusals.json.  tests/make_golden_loop_refusals.py walks one handle
 and one topology through every state and makes the calls (one thing wrong each, and a dozen with two things wrong where entry points
-order their checks differently); none of them gets as far as a launch."""
+order their checks differently); none of them gets as far as a launch.  The same for what a caller attaches to the topology -
+steering, diversity, framed restraints, a sink - and for the argument refusals of those terms' setters, attach calls and
+single-transition entry points."""
 import json
 
 import pytest

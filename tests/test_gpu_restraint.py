@@ -410,7 +410,7 @@ def check_row_setter_and_the_captured_graph(steer):
     finally:
         lib.hd_steer_detach(topo.ptr)
         lib.hd_restraint_detach(topo.ptr)
-        model._path_cache = model._restraint_cache = model._steer_cache = None
+        model._path_cache = model._row_caches = None
 
 
 def test_restraint_rows_of_the_same_K_keep_the_captured_graph_and_another_K_builds_one():
@@ -548,7 +548,7 @@ def test_device_path_refusals():
         args = (hnd, topo.ptr, zz.data_ptr(), None, -1, 0, 4, None, None, B, SEED, 1, 1)
         assert lib.hd_sample_path_inpaint(*args, fm.data_ptr(), zz.data_ptr(), 1, stream()) == -1
         assert b"restraints are attached" in lib.hd_last_error()
-        model._restraint_cache = None
+        model._row_caches = None
         rows = (C.c_float * 16)(*([0.8, 0.6, 0.5, 0.3] * 4))
         assert lib.hd_set_restraint(hnd, 3, rows) == -1 and b"K differs" in lib.hd_last_error()
         assert lib.hd_set_restraint(hnd, 4, (C.c_float * 16)(*([0.8, 0.6, 0.5, 0.0] * 4))) == -1
@@ -570,7 +570,7 @@ def test_device_path_refusals():
         Restraints.detach(topo)
     assert lib.hd_sample_loop(hnd, topo.ptr, zb.data_ptr(), None, -1, T, T - 2, None, None, B, SEED, 1, 1, stream()) == 0
     assert torch.equal(za, zb)
-    model._restraint_cache = None
+    model._row_caches = None
     assert torch.equal(model.path_steps(z, nmd, steps=4, sample_id_base=1), want)
     with pytest.raises(NotImplementedError, match="restraints"):
         model.sample_inpaint(nmd, nmd, z[:, :, :3], z[:, :, 3:], restraints=rs)

@@ -422,7 +422,7 @@ def test_device_path_refusals():
                                                     fmu.data_ptr(), known.data_ptr(), 1, stream())
     assert lib.hd_restraint_frame(topo.ptr, 1) == -4 and b"no restraints attached" in lib.hd_last_error()
     rs.attach(topo, torch.ones(1), 1.0, torch.device(DEV), stream())
-    model._restraint_cache = None
+    model._row_caches = None
     try:
         rows = (C.c_float * 16)(*([0.8, 0.6, 0.5, 0.3] * 4))
         assert lib.hd_set_restraint(hnd, 4, rows) == 0, lib.hd_last_error()
@@ -445,7 +445,7 @@ def test_device_path_refusals():
     finally:
         lib.hd_steer_detach(topo.ptr)
         Restraints.detach(topo)
-        model._restraint_cache = model._steer_cache = None
+        model._row_caches = None
     torch.cuda.synchronize()
     got = model.sample_inpaint(nmd, dev(fm), dev(xk), dev(hk), sample_id_base=1, steps=4)
     assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
