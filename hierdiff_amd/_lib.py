@@ -44,6 +44,7 @@ SIGNATURES = {
     "hd_topology_create_s": (C.c_int, [_VP, _U8P, _U8P, C.c_int, C.c_int, _VP, C.POINTER(_VP)]),
     "hd_topology_destroy": (C.c_int, [_VP]),
     "hd_arena_pool_trim": (C.c_int, []),
+    "hd_live_allocations": (C.c_longlong, [C.POINTER(C.c_longlong)]),
     "hd_topology_layout": (C.c_int, [_U8P, _U8P, C.c_int, C.c_int, C.POINTER(C.c_longlong), _VP, _VP, _VP, _VP, _VP, _VP]),
     "hd_topology_info": (C.c_int, [_VP, C.POINTER(C.c_longlong)]),
     "hd_egnn_forward": (C.c_int, [_VP, _VP, _FP, _FP, C.c_int, _FP, C.c_int, _FP, _VP]),

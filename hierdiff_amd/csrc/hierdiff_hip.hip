@@ -35,6 +35,37 @@ static int fail(int code, const std::string& msg) {
         if (_r != HD_OK) return _r;  \
     } while (0)
 
+// ----------------------------------------------------------------------------- memory
+//
+// The two raw functions of mem.hpp: every device allocation of the library passes through them, and hd_live_allocations reads
+// what they count.
+
+#include <atomic>
+
+static std::atomic<long long> g_live_allocs{0}, g_live_bytes{0};
+
+int hd_raw_alloc(void** p, size_t bytes) {
+    *p = nullptr;
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) { *p = nullptr; return fail(HD_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+    g_live_allocs.fetch_add(1, std::memory_order_relaxed);
+    g_live_bytes.fetch_add((long long)bytes, std::memory_order_relaxed);
+    return HD_OK;
+}
+
+void hd_raw_free(void* p, size_t bytes) {
+    (void)hipFree(p);
+    g_live_allocs.fetch_sub(1, std::memory_order_relaxed);
+    g_live_bytes.fetch_sub((long long)bytes, std::memory_order_relaxed);
+}
+
+extern "C" long long hd_live_allocations(long long* bytes) {
+    if (bytes) *bytes = g_live_bytes.load(std::memory_order_relaxed);
+    return g_live_allocs.load(std::memory_order_relaxed);
+}
+
+#include "mem.hpp"
+
 // ----------------------------------------------------------------------------- objects
 
 // fp32 mode: batches with fewer active rows than this run the node side as three launches (widths >= 128: k_node_split_f32,
@@ -70,96 +101,109 @@ struct PathTables {
     std::vector<int> t_h, s_h;
     std::vector<float> c2_h;         // forms 2 and 3: c2 of every row (which transitions read the history)
     std::vector<unsigned char> noisy_h;   // 1: the row draws noise (form 0 always, forms 1 and 3 with c != 0, form 2 never)
-    int *d_t = nullptr, *d_s = nullptr;
-    float *d_coef = nullptr, *d_coef_ip = nullptr;   // [K][width of the form], [K][4]; d_coef_ip null when no inpainting rows were given
+    DevBuf<int> d_t, d_s;
+    DevBuf<float> d_coef, d_coef_ip;                 // [K][width of the form], [K][4]; d_coef_ip empty when no inpainting rows were given
     unsigned long long sched_gen = 0, gen = 0;       // sched_gen the tables were set for (0: not set); bumped by every rewrite
 };
 
 // Per-transition rows that go with the caller's path (set_row_table is the one writer).
 struct RowTable {
-    float* d = nullptr;              // [K][width]
+    DevBuf<float> d;                 // [K][width]
     int K = 0;
     unsigned long long path_gen = 0, gen = 0;   // path.gen the rows were set for (0: not set); bumped when the table moves
 };
 
+// Recording (hd_set_chain): which frame of an attached sink every transition of the current path writes, and for the data
+// prediction {alpha_t, sigma_t} of its departure level.
+struct ChainTables {
+    int frames = 0;
+    DevBuf<int> d_frame;             // [K], -1: none
+    DevBuf<float> d_as;              // [K][2]; empty when hd_set_chain got none
+    unsigned long long path_gen = 0, gen = 0;   // path.gen the tables were set for (0: not set); bumped by every hd_set_chain
+};
+
+// Scoring (hd_set_nll_terms / hd_nll_terms / hd_nll_finish): K terms t_idx[k] of the bound, rows {alpha_t, sigma_t, w_t, 0}.
+struct NllTerms {
+    int K = 0;
+    std::vector<int> t_h;
+    DevBuf<int> d_t;
+    DevBuf<float> d_coef;
+    unsigned long long sched_gen = 0, gen = 0;  // sched_gen the terms were set for (0: not set); bumped by every hd_set_nll_terms
+};
+
+// Inpainting on the every-step tables: the generations of their inpainting rows (every.d_coef_ip) and, for graph replay, the draw
+// words of a transition's 3 * resamplings noise streams (grow_ipdraw).
+struct InpaintDraws {
+    DevBuf<uint32_t> d_draw;
+    unsigned long long sched_gen = 0, gen = 0;  // sched_gen every's inpainting rows were set for (0: not set); bumped when they / d_draw move
+};
+
 struct hd_handle {
-    hd_config cfg;
-    int device;
-    int H, fin, F, D, NS;       // NS: 32-column sub-tiles per k_gemm workgroup tile
+    hd_config cfg{};
+    int device = 0;
+    int H = 0, fin = 0, F = 0, D = 0, NS = 0;   // NS: 32-column sub-tiles per k_gemm workgroup tile
     // arithmetic of the two kernel families, derived from cfg.precision and the width (hd_create):
     //   edge_mode 0 fp32 | 3 fp16x3      node_mode 0 fp32 (k_node_f32 / k_node_split_f32 / k_gemm_r16) | 3 fp16 two-piece
     //   precision 0: 0 / 0;  3: 3 / 3 (H >= 128), else 3 / 0        (codes 1 and 2 were retired in ABI 12)
     // `scaled`: the edge model runs in the domain scaled by -log2(e) (fp16x3, silu_scaled in common.hpp)
-    int edge_mode, node_mode;
-    bool scaled;
-    long long n_weights;
-    bool weights_set;
-    float* dw;                  // packed weights
-    size_t dw_floats;
-    size_t embT, emb_b, outW, out_b;
+    int edge_mode = 0, node_mode = 0;
+    bool scaled = false;
+    long long n_weights = 0;
+    bool weights_set = false;
+    DevBuf<float> dw;           // packed weights
+    size_t dw_floats = 0;
+    size_t embT = 0, emb_b = 0, outW = 0, out_b = 0;
     std::vector<LayerW> gcl;    // [n_layers * inv_sublayers]
     std::vector<LayerW> coord;  // [n_layers]
     // device scalars
-    int* d_nanflag;
-    long long* d_nan_events;
+    DevBuf<int> d_nanflag;
+    DevBuf<long long> d_nan_events;
     // schedule
-    int T;
+    int T = 0;
     std::vector<float> tau_h;
-    float* d_tau;
+    DevBuf<float> d_tau;
     // graph-replay state (device words the captured transition reads and k_path_advance moves on)
-    int* d_step;
-    uint32_t* d_draw;
-    float* d_tcur;
-    unsigned long long* d_base; // global id of the batch's first sample (Philox stream selector)
-    hipStream_t own_stream;     // capture / replay stream used when the caller passes the legacy NULL stream
-    hipEvent_t ev_in, ev_out;   // order own_stream against the caller's stream without host syncs
-    hipEvent_t ev_last;         // recorded behind the handle's latest graph replay (any stream): the step / draw / time words
-    bool ev_last_set;           // above are shared by every topology of the handle, so replays are serialised on it
-    unsigned long long weights_gen, sched_gen;   // bumped when the packed weights / schedule tables are re-allocated
+    DevBuf<int> d_step;
+    DevBuf<uint32_t> d_draw;
+    DevBuf<float> d_tcur;
+    DevBuf<unsigned long long> d_base;   // global id of the batch's first sample (Philox stream selector)
+    DevBuf<float*> d_chain_dst; // the sink a recording transition writes (set by k_path_state)
+    Stream own_stream;          // capture / replay stream used when the caller passes the legacy NULL stream
+    Event ev_in, ev_out;        // order own_stream against the caller's stream without host syncs
+    Event ev_last;              // recorded behind the handle's latest graph replay (any stream): the step / draw / time words
+    bool ev_last_set = false;   // above are shared by every topology of the handle, so replays are serialised on it
+    unsigned long long weights_gen = 0, sched_gen = 0;   // bumped when the packed weights / schedule tables are re-allocated
     // The path loop's tables.  `path`: the caller's (hd_set_path / hd_set_path_up / hd_set_path_multistep; hd_sample_path*).
     // `every`: the identity path of the current schedule, T transitions s + 1 -> s from s = T - 1 down to 0, built by hd_set_schedule
     // from its rows in reverse order (form 0; its gen moves with sched_gen); hd_set_inpaint_schedule adds the inpainting rows
     // {alpha_s, sigma_s, alpha_t|s, sigma_t|s}, reversed too.  hd_sample_loop / hd_sample_loop_inpaint run on it.
     PathTables path, every;
-    unsigned long long ip_sched_gen, ip_gen;     // sched_gen every's inpainting rows were set for (0: not set); bumped when they / d_ipdraw move
-    uint32_t* d_ipdraw;         // graph replay: the draw words of a transition's 3 * resamplings noise streams
-    int ipdraw_cap;
-    // recording (hd_set_chain): which frame of an attached sink every transition of the current path writes, and for the data
-    // prediction {alpha_t, sigma_t} of its departure level
-    int chain_frames;
-    int* d_chain_frame;         // [K], -1: none
-    float* d_chain_as;          // [K][2]; null when hd_set_chain got none
-    unsigned long long chain_path_gen, chain_gen;   // path.gen the tables were set for (0: not set); bumped by every hd_set_chain
-    float** d_chain_dst;        // graph replay: the sink a recording transition writes (set by k_path_state)
+    InpaintDraws ip;
+    ChainTables chain;
     // the loop terms' rows of every transition of the current path: restraints (hd_set_restraint) and diversity (hd_set_diversity)
     // {alpha_t, sigma_t, lambda_k, clip_k}, steering (hd_set_steer) {alpha_t, sigma_t, beta_k}
     RowTable rs_rows, dv_rows, st_rows;   // [K][4], [K][4], [K][3]
-    // scoring (hd_set_nll_terms / hd_nll_terms / hd_nll_finish): K terms t_idx[k] of the bound, rows {alpha_t, sigma_t, w_t, 0}
-    int nll_K;
-    std::vector<int> nll_t_h;
-    int* d_nll_t;
-    float* d_nll_coef;
-    unsigned long long nll_sched_gen, nll_gen;   // sched_gen the terms were set for (0: not set); bumped by every hd_set_nll_terms
-    int split_max_tiles;        // HD_SPLIT_MAX_TILES (a measurement build may override it from the environment)
-    int fuse_min_rows;          // HD_FUSE_MIN_ROWS
-    int node_split_max_rows;    // HD_NODE_SPLIT_MAX_ROWS
-    int f32_split;              // 1: the fp32 small-row node chain of widths >= 128 is k_node_split_f32 (0, measurement build: k_gemm_r16)
-    int mix_max_tiles;          // HD_MIX_MAX_TILES
-    int mix_rounds;             // measurement build: force the number of whole-tile rounds of k_edge_mixed (-1 = rule)
-    int n_cu;                   // compute units of the device
+    NllTerms nll;
+    int split_max_tiles = HD_SPLIT_MAX_TILES;   // (a measurement build may override these from the environment)
+    int fuse_min_rows = HD_FUSE_MIN_ROWS;
+    int node_split_max_rows = HD_NODE_SPLIT_MAX_ROWS;
+    int f32_split = 1;          // 1: the fp32 small-row node chain of widths >= 128 is k_node_split_f32 (0, measurement build: k_gemm_r16)
+    int mix_max_tiles = HD_MIX_MAX_TILES;
+    int mix_rounds = -1;        // measurement build: force the number of whole-tile rounds of k_edge_mixed (-1 = rule)
+    int n_cu = 0;               // compute units of the device
 #ifdef HD_DEBUG_KERNELS
-    long long* d_trace;         // HD_ABLATE bit 16: cycle stamps of the last traced edge launch
-    int trace_wg;
-    int ablate;                 // HD_ABLATE value read at hd_create
+    DevBuf<long long> d_trace;  // HD_ABLATE bit 16: cycle stamps of the last traced edge launch
+    int trace_wg = 0;
+    int ablate = 0;             // HD_ABLATE value read at hd_create
 #endif
     // profiling
-    int prof;                   // bitmask of kernel families bracketed with events
-    int prof_stride;            // bracket every prof_stride-th forward
-    long long prof_fwd;
-    bool prof_now;
+    int prof = 0;               // bitmask of kernel families bracketed with events
+    int prof_stride = 1;        // bracket every prof_stride-th forward
+    long long prof_fwd = 0;
+    bool prof_now = false;
     std::vector<ProfRec> recs;
-    std::vector<hipEvent_t> pool;
-    size_t pool_used;
+    std::vector<Event> pool;
+    size_t pool_used = 0;
 };
 
 // The restraint part of a captured transition's key (restraint_key in host_loops.hpp builds it); all 0: not restrained.
@@ -238,136 +282,126 @@ struct NllKey {
 // built (replay_slot is the one writer; the hd_*_graph_builds getters report the count where the ABI has one).
 template <typename Key>
 struct GraphSlot {
-    hipGraphExec_t exec;
-    Key key;
-    long long builds;
+    GraphExec exec;
+    Key key{};
+    long long builds = 0;
 };
 
 // One library-owned device table of a topology, at an address captured transitions keep; `fill` (host_loops.hpp) is its one writer.
 template <typename T>
-struct DevTable {
-    T* p;
-    size_t cap;
+struct DevTable : DevBuf<T> {
     int fill(const T* src, size_t count, bool* moved, hipStream_t s);
 };
 
-// What restraints keep on a topology; all-zero when value-initialised (nothing attached).  A generation moves when something its
+// What restraints keep on a topology; a default-constructed one has nothing attached.  A generation moves when something its
 // setter's captured launches bake in does - an address, a size, a row count, nv0; re-attaching tables of the same sizes is a copy.
 // NF / NT are what is attached NOW (0 after hd_restraint_attach); fld_NF, tpl_NT and the sizes next to them what was last baked in.
 struct RestraintState {
-    bool on;
-    int frame;                                 // hd_restraint_frame: 0 the model's frame, 1 the known fragments' (inpainting calls)
+    bool on = false;
+    int frame = 0;                             // hd_restraint_frame: 0 the model's frame, 1 the known fragments' (inpainting calls)
     // hd_restraint_attach: the tables, the per-molecule scales and the scratch of k_restrain_eps (allocated once)
     DevTable<float> obs, pair_f, anc_f, scale;
     DevTable<int> pair_idx, anc_idx;
-    double* step;
-    int obs_rows, P, pair_rows, Q, anc_rows, A, scale_rows;
-    float nv0;
-    unsigned long long gen;
-    // hd_restraint_fields: the value pool, the weights; offsets / dims / geometry of up to HD_MAX_FIELDS fields (allocated once each)
+    DevBuf<double> step;
+    int obs_rows = 0, P = 0, pair_rows = 0, Q = 0, anc_rows = 0, A = 0, scale_rows = 0;
+    float nv0 = 0.f;
+    unsigned long long gen = 0;
+    // hd_restraint_fields: the value pool, the weights; offsets / dims / geometry of up to HD_MAX_FIELDS fields (allocated together)
     DevTable<float> fld_v, fld_w;
-    long long* fld_off;
-    int* fld_dims;
-    float* fld_geom;
-    int NF, fld_NF, fld_w_rows;
-    unsigned long long fld_gen;
+    DevBuf<long long> fld_off;
+    DevBuf<int> fld_dims;
+    DevBuf<float> fld_geom;
+    int NF = 0, fld_NF = 0, fld_w_rows = 0;
+    unsigned long long fld_gen = 0;
     // hd_restraint_templates: the row tables; the geometry of up to HD_MAX_TEMPLATES templates (one allocation, made by the first call)
     DevTable<int> tpl_idx;
     DevTable<float> tpl_f;
-    float* tpl_geom;
-    int NT, tpl_NT, tpl_M, tpl_rows;
-    unsigned long long tpl_gen;
+    DevBuf<float> tpl_geom;
+    int NT = 0, tpl_NT = 0, tpl_M = 0, tpl_rows = 0;
+    unsigned long long tpl_gen = 0;
     // hd_restraint_features: the band tables lo / hi / k [rows][W][F] and the sum rows coef [rows][S][F], f [rows][S][4]
     DevTable<float> ft_lo, ft_hi, ft_k, ft_coef, ft_sum;
-    bool feat;                                 // attached NOW (false after hd_restraint_attach)
-    int ft_band_rows, ft_W, ft_sum_rows, ft_S;
-    float ft_nv1, ft_nb1, ft_ratio;
-    unsigned long long feat_gen;
+    bool feat = false;                         // attached NOW (false after hd_restraint_attach)
+    int ft_band_rows = 0, ft_W = 0, ft_sum_rows = 0, ft_S = 0;
+    float ft_nv1 = 0.f, ft_nb1 = 0.f, ft_ratio = 0.f;
+    unsigned long long feat_gen = 0;
 };
-
-static void dev_free(std::initializer_list<void*> ps) {
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
-}
-
-static void restraint_free(RestraintState& r) {
-    dev_free({r.obs.p, r.pair_idx.p, r.pair_f.p, r.anc_idx.p, r.anc_f.p, r.scale.p, r.step, r.fld_v.p, r.fld_w.p, r.fld_off, r.fld_dims,
-              r.fld_geom, r.tpl_idx.p, r.tpl_f.p, r.tpl_geom, r.ft_lo.p, r.ft_hi.p, r.ft_k.p, r.ft_coef.p, r.ft_sum.p});
-    r = RestraintState{};
-}
 
 // hd_steer_attach: the steered chain's state and scratch, allocated once; it survives between the pieces of a chain (`reset`: a new one).
 struct SteerAttach {
-    bool on;
-    int P;
-    double ess;
-    double* f64;                               // logw [B], U_prev [B], its scratch [B], stats [B / P][3] (room for [B][3])
-    int* i32;                                  // root [B], anc [B]
-    float* scratch;                            // [3][B][N][D]
-    unsigned long long gen;
+    bool on = false;
+    int P = 0;
+    double ess = 0.0;
+    DevBuf<double> f64;                        // logw [B], U_prev [B], its scratch [B], stats [B / P][3] (room for [B][3])
+    DevBuf<int> i32;                           // root [B], anc [B]
+    DevBuf<float> scratch;                     // [3][B][N][D]
+    unsigned long long gen = 0;
 };
 
 // hd_diversity_attach: scales and scratch of k_diverse_eps; gen moves with P, scale_rows, kappa, length, nv0 or an address.
 struct DiverseAttach {
-    bool on;
-    int P, scale_rows;
-    double kappa, length;
-    float nv0;
+    bool on = false;
+    int P = 0, scale_rows = 0;
+    double kappa = 0.0, length = 0.0;
+    float nv0 = 0.f;
     DevTable<float> scale;
-    double* step;                              // [B][N][3]
-    unsigned long long gen;
+    DevBuf<double> step;                       // [B][N][3]
+    unsigned long long gen = 0;
 };
 
 // hd_chain_attach: the caller's sink every path loop on a topology records into (null: none; the caller's memory: nothing to free).
 struct ChainSink {
-    float* dst;
-    int frames, what;                          // what 0: the state behind the transition, 1: its data prediction
-    float nv0, nv1, nb1;
+    float* dst = nullptr;
+    int frames = 0, what = 0;                  // what 0: the state behind the transition, 1: its data prediction
+    float nv0 = 0.f, nv1 = 0.f, nb1 = 0.f;
 };
 
-static void steer_free(SteerAttach& s) { dev_free({s.f64, s.i32, s.scratch}); s = SteerAttach{}; }
-static void diverse_free(DiverseAttach& d) { dev_free({d.scale.p, d.step}); d = DiverseAttach{}; }
+// A topology's one device allocation (tables + workspace) and its pinned staging twin; between topologies it waits in the arena
+// pool (below) with the event recorded behind the last work of its previous owner.
+struct ArenaSlot {
+    int device = 0;
+    DevBuf<char> dev;
+    PinnedBuf pinned;
+    size_t pinned_bytes = 0;
+    Event done;                                // empty: nothing pending
+    bool holds(size_t d, size_t p) const { return dev && pinned && dev.bytes() >= d && pinned_bytes >= p; }
+};
 
 struct hd_topology {
-    hd_handle* h;
-    int device;
-    char* arena;                               // the one device allocation everything below points into
-    int B, N, M, M_pad, E, E_pad, n_tiles, n_wg, n_parts;
+    hd_handle* h = nullptr;
+    int device = 0;
+    ArenaSlot arena;                           // the one device allocation the tables and the workspace point into
+    int B = 0, N = 0, M = 0, M_pad = 0, E = 0, E_pad = 0, n_tiles = 0, n_wg = 0, n_parts = 0;
     // device tables
-    int *node_of, *slot_of, *ei, *ej, *seg_part, *tile_nseg, *pstart, *nvalid;
-    int *rptr, *rrows, *sptr, *srows;          // edge rows by receiving / sending node (training kernels)
-    std::vector<int>* node_of_host;            // kept for hd_topology_nodes
-    float *w2img, *w2timg;                     // training: device-packed images of the current layer's W2 and W2^T
-    uint8_t *eseg, *nm_bytes;
-    float* nmask;
+    int *node_of = nullptr, *slot_of = nullptr, *ei = nullptr, *ej = nullptr, *seg_part = nullptr, *tile_nseg = nullptr,
+        *pstart = nullptr, *nvalid = nullptr;
+    int *rptr = nullptr, *rrows = nullptr, *sptr = nullptr, *srows = nullptr;   // edge rows by receiving / sending node (training kernels)
+    std::vector<int> node_of_host;             // kept for hd_topology_nodes
+    float *w2img = nullptr, *w2timg = nullptr; // training: device-packed images of the current layer's W2 and W2^T
+    uint8_t *eseg = nullptr, *nm_bytes = nullptr;
+    float* nmask = nullptr;
     // workspace
-    float *hbuf, *AB, *AB2, *Tb, *agg, *x0, *xcur, *part, *xpart, *eps;
-    float *abmax, *abmax2;                     // fp16x3: [M_pad][2] row maxima of the AB / AB2 buffers
-    float *rowinfo;                            // fp16x3, split node chain: [M_pad][2] {max |h_r|, max |[h | agg]_r|} (k_node_split.hpp)
-    // use_graph: every device loop keeps ONE captured transition / term here in a GraphSlot and replays it once per step through
-    // the replay scaffold (host_loops.hpp; graph_execs lists the slots).  The captured body works on library-owned copies of the
-    // caller's tensors so that the instantiated graph survives across calls (the caller's tensors move); each loop allocates its
-    // copies on first use.
+    float *hbuf = nullptr, *AB = nullptr, *AB2 = nullptr, *Tb = nullptr, *agg = nullptr, *x0 = nullptr, *xcur = nullptr,
+          *part = nullptr, *xpart = nullptr, *eps = nullptr;
+    float *abmax = nullptr, *abmax2 = nullptr; // fp16x3: [M_pad][2] row maxima of the AB / AB2 buffers
+    float* rowinfo = nullptr;                  // fp16x3, split node chain: [M_pad][2] {max |h_r|, max |[h | agg]_r|} (k_node_split.hpp)
+    // use_graph: every device loop keeps ONE captured transition / term in a GraphSlot (at the end of this struct) and replays it
+    // once per step through the replay scaffold (host_loops.hpp).  The captured body works on library-owned copies of the caller's
+    // tensors so that the instantiated graph survives across calls (the caller's tensors move); each loop allocates its copies on
+    // first use.
     // all loops: z / context
-    float *zbuf, *ctxbuf;
-    // hd_sample_loop, hd_sample_loop_inpaint: the path loop on the handle's every-step tables, in slots of its own so that it and
-    // the loops on the caller's path do not evict each other (their build counts are not reported)
-    GraphSlot<PathKey> g_every, g_every_ip;
+    float *zbuf = nullptr, *ctxbuf = nullptr;
     // the inpainting loops: the fixed mask / known values
-    uint8_t* ip_fixed;
-    float* ip_known;
+    DevBuf<uint8_t> ip_fixed;
+    DevBuf<float> ip_known;
     // hd_inpaint_parts: the library-owned channel mask [B*N*F] (allocated by the first attach, at an address captured transitions
     // keep) and whether it is attached - then ip_fixed means "position known"
-    uint8_t* ip_parts;
-    bool ip_parts_on;
-    // hd_sample_path / hd_sample_path_inpaint (hd_path_graph_builds)
-    GraphSlot<PathKey> g_path;
-    // hd_sample_path_guided: the second network output, and for the captured guided transition - a graph of its own next to the
-    // unguided one - the null context and the scales (one allocation, made by the first guided call; hd_guided_graph_builds)
-    GraphSlot<PathKey> g_guided;
-    float *guide_mem, *eps_u, *ctxu_buf, *wbuf;
-    // the recording transition (a sink attached) - guided or not - in a graph of its own next to the two above (hd_chain_graph_builds)
-    GraphSlot<ChainKey> g_chain;
+    DevBuf<uint8_t> ip_parts;
+    bool ip_parts_on = false;
+    // hd_sample_path_guided: the second network output, and for the captured guided transition the null context and the scales
+    // (one allocation, made by the first guided call)
+    DevBuf<float> guide_mem;
+    float *eps_u = nullptr, *ctxu_buf = nullptr, *wbuf = nullptr;
     // what a caller attaches for the time of a call, one struct per loop term: restraints, steering, diversity, the sink
     RestraintState rs;
     SteerAttach st;
@@ -375,24 +409,29 @@ struct hd_topology {
     ChainSink chain;
     // multistep paths (hd_set_path_multistep): the previous transition's data prediction x^ [B][N][D], allocated by the first
     // form-2 call at an address the captured transitions keep; host-side, which path generation and position it belongs to
-    float* ms_hist;
-    unsigned long long ms_gen;                 // 0: no history
-    int ms_k;
-    // hd_nll_terms / hd_nll_finish: eps_t and, for the captured term, xh / the accumulator / the e_t table (z_t lives in zbuf;
-    // hd_nll_graph_builds)
-    GraphSlot<NllKey> g_nll;
-    float *nll_eps, *nll_xh, *nll_err;
-    double* nll_acc;
-    int nll_err_rows;
+    DevBuf<float> ms_hist;
+    unsigned long long ms_gen = 0;             // 0: no history
+    int ms_k = 0;
+    // hd_nll_terms / hd_nll_finish: eps_t and, for the captured term, xh / the accumulator / the e_t table (z_t lives in zbuf)
+    DevBuf<float> nll_eps, nll_xh, nll_err;
+    DevBuf<double> nll_acc;
+    int nll_err_rows = 0;
     // lifetime: the tables arrive in stream order of `stream0` (hd_topology_create_s); `ready` marks their arrival for
     // any other stream a caller launches on.  A topology used on one stream only hands its arena back to the pool
     // (arena_release) with an event instead of a device-wide synchronisation.
-    size_t arena_bytes;
-    char* staging;                             // pinned host twin of the table region (source of the async upload)
-    size_t staging_bytes;
-    hipStream_t stream0, last_stream;
-    hipEvent_t ready;
-    bool multi_stream;
+    hipStream_t stream0 = nullptr, last_stream = nullptr;
+    Event ready;
+    bool multi_stream = false;
+    // The captured graphs, one slot per loop.  They stand BEHIND every buffer above on purpose: members go in reverse order of
+    // declaration, so `delete t` destroys the graphs before the buffers their kernel nodes refer to.
+    // hd_sample_loop, hd_sample_loop_inpaint: the path loop on the handle's every-step tables, in slots of its own so that it and
+    // the loops on the caller's path do not evict each other (their build counts are not reported)
+    GraphSlot<PathKey> g_every, g_every_ip;
+    GraphSlot<PathKey> g_path;                 // hd_sample_path / hd_sample_path_inpaint (hd_path_graph_builds)
+    GraphSlot<PathKey> g_guided;               // the guided transition, next to the unguided one (hd_guided_graph_builds)
+    GraphSlot<ChainKey> g_chain;               // the recording transition (a sink attached), guided or not (hd_chain_graph_builds)
+    GraphSlot<NllKey> g_nll;                   // hd_nll_terms (hd_nll_graph_builds)
+    bool captured() const { return g_every.exec || g_every_ip.exec || g_path.exec || g_guided.exec || g_chain.exec || g_nll.exec; }
 };
 
 // ----------------------------------------------------------------------------- small helpers
@@ -422,22 +461,6 @@ static long long weight_count(const hd_config& c) {
 }
 
 extern "C" long long hd_weight_count(const hd_handle* h) { return h ? h->n_weights : 0; }
-
-template <typename T>
-static int dev_alloc(T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-    if (e != hipSuccess) return fail(HD_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    return HD_OK;
-}
-
-template <typename T>
-static int dev_upload(T** p, const std::vector<T>& v) {
-    HD_TRY(dev_alloc(p, v.size()));
-    if (!v.empty()) HIP_TRY(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return HD_OK;
-}
 
 // ----------------------------------------------------------------------------- create / destroy
 
@@ -477,38 +500,11 @@ extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
     }
     h->NS = (cfg->hidden_nf == 32) ? 1 : 2;
     h->n_weights = weight_count(*cfg);
-    h->weights_set = false;
-    h->dw = nullptr;
-    h->dw_floats = 0;
-    h->T = 0;
-    h->d_tau = nullptr;
-    h->prof = 0;
-    h->prof_stride = 1;
-    h->prof_fwd = 0;
-    h->prof_now = false;
-    h->pool_used = 0;
-    h->own_stream = nullptr;
-    h->ev_in = h->ev_out = nullptr;
-    h->ev_last = nullptr; h->ev_last_set = false;
-    h->weights_gen = h->sched_gen = 0;
-    h->ip_sched_gen = 0; h->ip_gen = 0; h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
-    h->chain_frames = 0; h->d_chain_frame = nullptr; h->d_chain_as = nullptr; h->chain_path_gen = 0; h->chain_gen = 0;
-    h->d_chain_dst = nullptr;
-    h->nll_K = 0; h->d_nll_t = nullptr; h->d_nll_coef = nullptr; h->nll_sched_gen = 0; h->nll_gen = 0;
-    h->d_nanflag = nullptr; h->d_nan_events = nullptr; h->d_step = nullptr; h->d_draw = nullptr; h->d_tcur = nullptr;
-    h->d_base = nullptr;
-    h->split_max_tiles = HD_SPLIT_MAX_TILES;
-    h->mix_max_tiles = HD_MIX_MAX_TILES;
-    h->fuse_min_rows = HD_FUSE_MIN_ROWS;
-    h->node_split_max_rows = HD_NODE_SPLIT_MAX_ROWS;
-    h->f32_split = 1;
-    h->mix_rounds = -1;
     {
         hipDeviceProp_t prop;
         h->n_cu = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
     }
 #ifdef HD_DEBUG_KERNELS
-    h->d_trace = nullptr; h->trace_wg = 0;
     { const char* e = getenv("HD_ABLATE"); h->ablate = e ? atoi(e) : 0; }
     { const char* e = getenv("HD_SPLIT_MAX_TILES"); if (e) h->split_max_tiles = atoi(e); }
     { const char* e = getenv("HD_MIX_MAX_TILES"); if (e) h->mix_max_tiles = atoi(e); }
@@ -517,19 +513,19 @@ extern "C" int hd_create(const hd_config* cfg, int device, hd_handle** out) {
     { const char* e = getenv("HD_F32_SPLIT"); if (e) h->f32_split = atoi(e); }
     { const char* e = getenv("HD_MIX_ROUNDS"); if (e) h->mix_rounds = atoi(e); }
 #endif
-    auto create_rest = [&]() -> int {        // every failure below leaves through hd_destroy (frees what exists)
-        HD_TRY(dev_alloc(&h->d_nanflag, 1));
-        HD_TRY(dev_alloc(&h->d_nan_events, 1));
-        HD_TRY(dev_alloc(&h->d_step, 1));
-        HD_TRY(dev_alloc(&h->d_draw, 1));
-        HD_TRY(dev_alloc(&h->d_tcur, 1));
-        HD_TRY(dev_alloc(&h->d_base, 1));
-        HD_TRY(dev_alloc(&h->d_chain_dst, 1));
+    auto create_rest = [&]() -> int {        // every failure below leaves through hd_destroy
+        HD_TRY(h->d_nanflag.alloc(1));
+        HD_TRY(h->d_nan_events.alloc(1));
+        HD_TRY(h->d_step.alloc(1));
+        HD_TRY(h->d_draw.alloc(1));
+        HD_TRY(h->d_tcur.alloc(1));
+        HD_TRY(h->d_base.alloc(1));
+        HD_TRY(h->d_chain_dst.alloc(1));
         HIP_TRY(hipMemset(h->d_nanflag, 0, sizeof(int)));
         HIP_TRY(hipMemset(h->d_nan_events, 0, sizeof(long long)));
-        HIP_TRY(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&h->ev_last, hipEventDisableTiming));
+        HIP_TRY(event_create(h->ev_in, hipEventDisableTiming));
+        HIP_TRY(event_create(h->ev_out, hipEventDisableTiming));
+        HIP_TRY(event_create(h->ev_last, hipEventDisableTiming));
         return prepare_kernels(h);
     };
     const int r = create_rest();
@@ -542,23 +538,6 @@ extern "C" int hd_destroy(hd_handle* h) {
     if (!h) return HD_OK;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    hipFree(h->dw); hipFree(h->d_nanflag); hipFree(h->d_nan_events);
-    hipFree(h->d_tau); hipFree(h->d_step); hipFree(h->d_draw); hipFree(h->d_tcur); hipFree(h->d_base);
-    hipFree(h->d_ipdraw);
-    for (PathTables* pt : {&h->path, &h->every}) {
-        hipFree(pt->d_t); hipFree(pt->d_s); hipFree(pt->d_coef); hipFree(pt->d_coef_ip);
-    }
-    hipFree(h->d_chain_frame); hipFree(h->d_chain_as); hipFree(h->d_chain_dst);
-    for (RowTable* tb : {&h->rs_rows, &h->st_rows, &h->dv_rows}) hipFree(tb->d);
-    hipFree(h->d_nll_t); hipFree(h->d_nll_coef);
-#ifdef HD_DEBUG_KERNELS
-    hipFree(h->d_trace);
-#endif
-    for (auto e : h->pool) hipEventDestroy(e);
-    if (h->ev_in) hipEventDestroy(h->ev_in);
-    if (h->ev_out) hipEventDestroy(h->ev_out);
-    if (h->ev_last) hipEventDestroy(h->ev_last);
-    if (h->own_stream) hipStreamDestroy(h->own_stream);
     delete h;
     return HD_OK;
 }
@@ -819,9 +798,8 @@ extern "C" int hd_set_weights(hd_handle* h, const float* blob, long long n, int 
     }
     if (p - src != n) return fail(HD_E_INVALID, "hd_set_weights: internal layout mismatch");
     if (h->dw_floats != pk.size()) {
-        hipFree(h->dw);
-        h->dw = nullptr;
-        HD_TRY(dev_alloc(&h->dw, pk.size()));
+        h->dw_floats = 0;
+        HD_TRY(h->dw.alloc(pk.size()));
         h->dw_floats = pk.size();
         h->weights_gen++;                      // captured graphs hold the old address
     }
@@ -838,21 +816,16 @@ extern "C" int hd_set_weights(hd_handle* h, const float* blob, long long n, int 
 // list instead of hipMalloc / hipFree (which synchronise the device).  A slot carries the event recorded behind the last
 // work of its previous owner; the next owner waits for it on the host before overwriting the staging buffer (in a
 // steady loop that work finished steps ago).
-struct ArenaSlot {
-    int device;
-    char* dev; size_t dev_bytes;
-    char* pinned; size_t pinned_bytes;
-    hipEvent_t done;                           // nullptr: nothing pending
-};
 static std::mutex g_pool_mu;
-static std::vector<ArenaSlot> g_pool;
+// never destroyed: at process exit the HIP runtime may be gone before a static's destructor would run
+static std::vector<ArenaSlot>& g_pool = *new std::vector<ArenaSlot>();
 static constexpr size_t kPoolSlots = 12;
 
-static void slot_free(ArenaSlot& sl) {
-    if (sl.done) { (void)hipEventSynchronize(sl.done); (void)hipEventDestroy(sl.done); }
-    if (sl.dev) (void)hipFree(sl.dev);
-    if (sl.pinned) (void)hipHostFree(sl.pinned);
-    sl = ArenaSlot{};
+// slots that leave the pool: wait for their pending work, then let them go
+static void slots_drop(std::vector<ArenaSlot>& v) {
+    for (auto& sl : v)
+        if (sl.done) (void)hipEventSynchronize(sl.done);
+    v.clear();
 }
 
 // smallest pooled slot of this device that holds both sizes, or a new allocation (10 % head room: the next batch's masks
@@ -862,33 +835,33 @@ static int arena_acquire(int device, size_t dev_bytes, size_t pinned_bytes, Aren
         std::lock_guard<std::mutex> lk(g_pool_mu);
         int best = -1;
         for (int i = 0; i < (int)g_pool.size(); ++i)
-            if (g_pool[i].device == device && g_pool[i].dev_bytes >= dev_bytes && g_pool[i].pinned_bytes >= pinned_bytes &&
-                (best < 0 || g_pool[i].dev_bytes < g_pool[best].dev_bytes)) best = i;
+            if (g_pool[i].device == device && g_pool[i].holds(dev_bytes, pinned_bytes) &&
+                (best < 0 || g_pool[i].dev.bytes() < g_pool[best].dev.bytes())) best = i;
         if (best >= 0) {
-            sl = g_pool[best];
+            sl = std::move(g_pool[best]);
             g_pool.erase(g_pool.begin() + best);
         } else {
             sl = ArenaSlot{};
         }
     }
     if (sl.dev) {
-        if (sl.done) { HIP_TRY(hipEventSynchronize(sl.done)); (void)hipEventDestroy(sl.done); sl.done = nullptr; }
+        if (sl.done) { HIP_TRY(hipEventSynchronize(sl.done)); sl.done.reset(); }
         return HD_OK;
     }
     sl.device = device;
-    sl.dev_bytes = (dev_bytes + dev_bytes / 10 + 4095) & ~size_t(4095);
-    sl.pinned_bytes = (pinned_bytes + pinned_bytes / 10 + 4095) & ~size_t(4095);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&sl.dev), sl.dev_bytes);
-    if (e != hipSuccess) {                     // make room: drop the pool and try once more
+    const size_t nd = (dev_bytes + dev_bytes / 10 + 4095) & ~size_t(4095);
+    const std::string err_before = g_err;
+    if (sl.dev.alloc(nd) != HD_OK) {           // make room: drop the pool and try once more (a success leaves no error text)
         (void)hipGetLastError();
+        g_err = err_before;
         std::vector<ArenaSlot> drop;
         { std::lock_guard<std::mutex> lk(g_pool_mu); drop.swap(g_pool); }
-        for (auto& d : drop) slot_free(d);
-        e = hipMalloc(reinterpret_cast<void**>(&sl.dev), sl.dev_bytes);
+        slots_drop(drop);
+        HD_TRY(sl.dev.alloc(nd));
     }
-    if (e != hipSuccess) { sl.dev = nullptr; return fail(HD_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-    e = hipHostMalloc(reinterpret_cast<void**>(&sl.pinned), sl.pinned_bytes, hipHostMallocDefault);
-    if (e != hipSuccess) { (void)hipFree(sl.dev); sl = ArenaSlot{}; return fail(HD_E_NOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e)); }
+    sl.pinned_bytes = (pinned_bytes + pinned_bytes / 10 + 4095) & ~size_t(4095);
+    const hipError_t e = pinned_alloc(sl.pinned, sl.pinned_bytes);
+    if (e != hipSuccess) { sl = ArenaSlot{}; return fail(HD_E_NOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e)); }
     return HD_OK;
 }
 
@@ -899,57 +872,40 @@ static void arena_release(ArenaSlot sl) {
     std::vector<ArenaSlot> evict;
     {
         std::lock_guard<std::mutex> lk(g_pool_mu);
-        g_pool.push_back(sl);
+        g_pool.push_back(std::move(sl));
         size_t total = 0;
-        for (const auto& p : g_pool) total += p.dev_bytes;
+        for (const auto& p : g_pool) total += p.dev.bytes();
         while (!g_pool.empty() && (g_pool.size() > kPoolSlots || total > kPoolBytes)) {
-            total -= g_pool.front().dev_bytes;
-            evict.push_back(g_pool.front());
+            total -= g_pool.front().dev.bytes();
+            evict.push_back(std::move(g_pool.front()));
             g_pool.erase(g_pool.begin());
         }
     }
-    for (auto& e : evict) slot_free(e);
+    slots_drop(evict);
 }
 
 extern "C" int hd_arena_pool_trim(void) {
     std::vector<ArenaSlot> drop;
     { std::lock_guard<std::mutex> lk(g_pool_mu); drop.swap(g_pool); }
-    for (auto& d : drop) slot_free(d);
+    slots_drop(drop);
     return HD_OK;
-}
-
-// the graphs of a topology's slots, one per captured loop, and the one way a slot's graph goes (replay scaffold, host_loops.hpp)
-static std::array<hipGraphExec_t*, 6> graph_execs(hd_topology* t) {
-    return {&t->g_every.exec, &t->g_every_ip.exec, &t->g_path.exec, &t->g_guided.exec, &t->g_chain.exec, &t->g_nll.exec};
-}
-static void graph_drop(hipGraphExec_t* gx) {
-    if (*gx) hipGraphExecDestroy(*gx);
-    *gx = nullptr;
 }
 
 extern "C" int hd_topology_destroy(hd_topology* t) {
     if (!t) return HD_OK;
     (void)hipSetDevice(t->device);
-    ArenaSlot sl{t->device, t->arena, t->arena_bytes, t->staging, t->staging_bytes, nullptr};
+    ArenaSlot sl = std::move(t->arena);
     // a captured graph, or launches on several streams: wait for the device (the rare case - a sampling topology lives as
     // long as its model); otherwise an event behind the topology's last work guards the arena's next owner
-    bool pooled = t->arena && !t->multi_stream;
-    for (hipGraphExec_t* gx : graph_execs(t)) pooled = pooled && !*gx;
-    if (pooled && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) == hipSuccess) {
-        if (hipEventRecord(sl.done, t->last_stream) != hipSuccess) { (void)hipEventDestroy(sl.done); sl.done = nullptr; pooled = false; }
+    bool pooled = sl.dev && !t->multi_stream && !t->captured();
+    if (pooled && event_create(sl.done, hipEventDisableTiming) == hipSuccess) {
+        if (hipEventRecord(sl.done, t->last_stream) != hipSuccess) { sl.done.reset(); pooled = false; }
     } else {
         pooled = false;
     }
     if (!pooled) (void)hipDeviceSynchronize();
-    for (hipGraphExec_t* gx : graph_execs(t)) graph_drop(gx);
-    restraint_free(t->rs);
-    steer_free(t->st);
-    diverse_free(t->dv);
-    dev_free({t->guide_mem, t->ms_hist, t->ip_fixed, t->ip_known, t->ip_parts, t->nll_eps, t->nll_xh, t->nll_err, t->nll_acc});
-    if (t->ready) (void)hipEventDestroy(t->ready);
-    if (t->arena) arena_release(sl);                    // tables and workspace live in one allocation
-    delete t->node_of_host;
-    delete t;
+    delete t;                                           // the graphs first, then what the loops allocated (member order)
+    if (sl.dev) arena_release(std::move(sl));           // tables and workspace live in one allocation
     return HD_OK;
 }
 
@@ -1130,7 +1086,6 @@ extern "C" int hd_topology_create_s(hd_handle* h, const uint8_t* node_mask, cons
     for (size_t f = 0; f < BN; ++f) nm_bytes[f] = node_mask[f] ? 1 : 0;
 
     hd_topology* t = new hd_topology();
-    std::memset(t, 0, sizeof(*t));
     t->h = h; t->device = h->device; t->B = B; t->N = N; t->M = M; t->M_pad = M_pad; t->E = (int)E; t->E_pad = E_pad;
     t->n_tiles = n_tiles; t->n_wg = n_wg; t->n_parts = n_parts;
     const int H = h->H;
@@ -1160,17 +1115,16 @@ extern "C" int hd_topology_create_s(hd_handle* h, const uint8_t* node_mask, cons
     const size_t f_eps = carve(BN * h->D), f_z = carve(BN * h->D), f_ctx = carve(BN * (size_t)std::max(1, h->cfg.context_node_nf));
     const size_t f_w2 = carve((size_t)H * H * 3 / 2), f_w2t = carve((size_t)H * H * 3 / 2);      // fp32 / fp16 images (H^2 floats) + room behind them: the fp16x3 training forward parks its image scalars there
     auto build = [&]() -> int {
-        ArenaSlot sl;
-        HD_TRY(arena_acquire(h->device, table_bytes + ws_floats * sizeof(float), table_bytes, sl));
-        t->arena = sl.dev; t->arena_bytes = sl.dev_bytes; t->staging = sl.pinned; t->staging_bytes = sl.pinned_bytes;
+        HD_TRY(arena_acquire(h->device, table_bytes + ws_floats * sizeof(float), table_bytes, t->arena));
         t->stream0 = t->last_stream = s0;
-        char* base = t->arena;
+        char* base = t->arena.dev;
+        char* staging = t->arena.pinned;                // pinned host twin of the table region (source of the async upload)
         // no host wait from here on: tables pinned staging -> device and the workspace fill in stream order of s0
-        std::memcpy(t->staging, blob.data(), blob.size());
-        HIP_TRY(hipMemcpyAsync(base, t->staging, blob.size(), hipMemcpyHostToDevice, s0));
+        std::memcpy(staging, blob.data(), blob.size());
+        HIP_TRY(hipMemcpyAsync(base, staging, blob.size(), hipMemcpyHostToDevice, s0));
         // zero-filled workspace: pad rows stay zero for the lifetime of the topology (kernels never write them)
         HIP_TRY(hipMemsetAsync(base + table_bytes, 0, ws_floats * sizeof(float), s0));
-        HIP_TRY(hipEventCreateWithFlags(&t->ready, hipEventDisableTiming));
+        HIP_TRY(event_create(t->ready, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(t->ready, s0));
         auto I = [&](size_t off) { return reinterpret_cast<int*>(base + off); };
         t->node_of = I(o_node_of); t->slot_of = I(o_slot_of); t->ei = I(o_ei); t->ej = I(o_ej); t->seg_part = I(o_seg_part);
@@ -1183,7 +1137,7 @@ extern "C" int hd_topology_create_s(hd_handle* h, const uint8_t* node_mask, cons
         t->xcur = ws + f_xcur; t->part = ws + f_part; t->xpart = ws + f_xpart; t->eps = ws + f_eps; t->zbuf = ws + f_z;
         t->abmax = ws + f_abmax; t->abmax2 = ws + f_abmax2; t->rowinfo = ws + f_rowinfo;
         t->ctxbuf = ws + f_ctx; t->w2img = ws + f_w2; t->w2timg = ws + f_w2t;
-        t->node_of_host = new std::vector<int>(node_of);
+        t->node_of_host = node_of;
         return HD_OK;
     };
     const int r = build();
@@ -1197,9 +1151,7 @@ extern "C" int hd_topology_create(hd_handle* h, const uint8_t* node_mask, const 
                                   hd_topology** out) {
     HD_TRY(hd_topology_create_s(h, node_mask, edge_mask, B, N, nullptr, out));
     HIP_TRY(hipStreamSynchronize(nullptr));
-    hipEvent_t ev = (*out)->ready;              // arrived: no stream has anything to wait for
-    (*out)->ready = nullptr;
-    if (ev) (void)hipEventDestroy(ev);
+    (*out)->ready.reset();                      // arrived: no stream has anything to wait for
     return HD_OK;
 }
 
@@ -1239,9 +1191,8 @@ extern "C" int hd_profile_enable(hd_handle* h, int on) {
 
 static hipEvent_t prof_event(hd_handle* h) {
     if (h->pool_used == h->pool.size()) {
-        hipEvent_t e;
-        hipEventCreate(&e);
-        h->pool.push_back(e);
+        h->pool.emplace_back();
+        (void)event_create(h->pool.back(), hipEventDefault);
     }
     return h->pool[h->pool_used++];
 }
@@ -1304,7 +1255,7 @@ static bool launch_edge_ablated(hd_handle* h, const EdgeArgs& a, hipStream_t s) 
         hipFuncSetAttribute((const void*)k_edge<256, false, PREC, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         EdgeArgs b = a;
         if constexpr (ABL & 16) {
-            if (!h->d_trace) hipMalloc(reinterpret_cast<void**>(&h->d_trace), sizeof(long long) * 32 * 4096);
+            (void)h->d_trace.alloc_once((size_t)32 * 4096);
             if (a.n_wg > 4096) return;
             b.trace = h->d_trace; h->trace_wg = a.n_wg;
         }
@@ -1552,7 +1503,7 @@ extern "C" int hd_nan_events(hd_handle* h, void* stream, long long* count) {
 
 extern "C" int hd_topology_nodes(const hd_topology* t, int* node_of) {
     if (!t || !node_of) return fail(HD_E_INVALID, "hd_topology_nodes: null argument");
-    std::copy(t->node_of_host->begin(), t->node_of_host->end(), node_of);
+    std::copy(t->node_of_host.begin(), t->node_of_host.end(), node_of);
     return HD_OK;
 }
 
@@ -1728,29 +1679,30 @@ extern "C" int hd_edge_layer_backward(hd_handle* h, hd_topology* t, int coord, c
 // ----------------------------------------------------------------------------- stage-2 layer E_GCL (forward)
 
 struct hd_egcl {
-    hd_egcl_config cfg;
-    int device, H, De, ctx, NS;
-    long long n_weights;
-    bool weights_set;
-    float* dw;
-    size_t dw_floats;
+    hd_egcl_config cfg{};
+    int device = 0, H = 0, De = 0, ctx = 0, NS = 0;
+    long long n_weights = 0;
+    bool weights_set = false;
+    DevBuf<float> dw;
+    size_t dw_floats = 0;
     // float offsets into dw
-    size_t ab_img, ab_bias, w_r, w_e, w_c, w1e_img, zero_bias, w2_img, b2, wa, ba, wc1_img, bc1, wc2, we1_img, be1, w_er,
-        we2_img, be2, wn1_img, bn1, wn2_img, bn2, ones;
-    size_t raw;             // the blob itself, state_dict layout (the backward's dX = dY W products read the weights unpacked)
+    size_t ab_img = 0, ab_bias = 0, w_r = 0, w_e = 0, w_c = 0, w1e_img = 0, zero_bias = 0, w2_img = 0, b2 = 0, wa = 0, ba = 0,
+           wc1_img = 0, bc1 = 0, wc2 = 0, we1_img = 0, be1 = 0, w_er = 0, we2_img = 0, be2 = 0, wn1_img = 0, bn1 = 0, wn2_img = 0,
+           bn2 = 0, ones = 0;
+    size_t raw = 0;         // the blob itself, state_dict layout (the backward's dX = dY W products read the weights unpacked)
     // widths 128 / 256 (round 5): the three node-level contractions also as k_node_f32 fragment images, for k_node_split_f32
-    size_t ab_nimg, wn1_nimg, wn2_nimg;
-    bool node_split;
+    size_t ab_nimg = 0, wn1_nimg = 0, wn2_nimg = 0;
+    bool node_split = false;
 };
 
 struct hd_egcl_graph {
-    hd_egcl* g;
-    int device, M, E, Mp, Ep;
-    int *row, *col, *cptr, *crows;
-    float *hin, *hres, *x4, *AB, *agg, *xagg, *Tn, *ea, *T1, *P, *M1, *C1, *geo, *trans, *ones;
-    int *rptr, *rrows;      // CSR over the sending index `row` (the backward's dA and dx sums)
-    float* bw;              // backward workspace (hd_egcl_backward, allocated by its first call)
-    size_t bw_floats;
+    hd_egcl* g = nullptr;
+    int device = 0, M = 0, E = 0, Mp = 0, Ep = 0;
+    DevBuf<int> row, col, cptr, crows;
+    DevBuf<float> hin, hres, x4, AB, agg, xagg, Tn, T1, P, M1, C1, geo, trans, ones;   // (the caller's edge_attr is read in place)
+    DevBuf<int> rptr, rrows;   // CSR over the sending index `row` (the backward's dA and dx sums)
+    DevBuf<float> bw;       // backward workspace (hd_egcl_backward, allocated by its first call)
+    size_t bw_floats = 0;
 };
 
 static long long egcl_weight_count(const hd_egcl_config& c) {
@@ -1777,7 +1729,6 @@ extern "C" int hd_egcl_create(const hd_egcl_config* cfg, int device, hd_egcl** o
     if (hd_device_count() <= device || device < 0) return fail(HD_E_HIP, "hd_egcl_create: no such HIP device (is a GPU visible?)");
     HIP_TRY(hipSetDevice(device));
     hd_egcl* g = new hd_egcl();
-    std::memset(g, 0, sizeof(*g));
     g->cfg = *cfg; g->device = device; g->H = H; g->De = cfg->edges_in_d; g->ctx = cfg->context_nf;
     g->NS = (H == 32) ? 1 : 2;
     g->n_weights = egcl_weight_count(*cfg);
@@ -1791,7 +1742,6 @@ extern "C" int hd_egcl_destroy(hd_egcl* g) {
     if (!g) return HD_OK;
     (void)hipSetDevice(g->device);
     (void)hipDeviceSynchronize();
-    hipFree(g->dw);
     delete g;
     return HD_OK;
 }
@@ -1878,8 +1828,8 @@ extern "C" int hd_egcl_set_weights(hd_egcl* g, const float* blob, long long n, i
     }
     if (p - src != n) return fail(HD_E_INVALID, "hd_egcl_set_weights: internal layout mismatch");
     if (g->dw_floats != pk.size()) {
-        hipFree(g->dw); g->dw = nullptr;
-        HD_TRY(dev_alloc(&g->dw, pk.size()));
+        g->dw_floats = 0;
+        HD_TRY(g->dw.alloc(pk.size()));
         g->dw_floats = pk.size();
     }
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -1892,10 +1842,6 @@ extern "C" int hd_egcl_graph_destroy(hd_egcl_graph* t) {
     if (!t) return HD_OK;
     (void)hipSetDevice(t->device);
     (void)hipDeviceSynchronize();
-    hipFree(t->row); hipFree(t->col); hipFree(t->cptr); hipFree(t->crows);
-    hipFree(t->hin); hipFree(t->hres); hipFree(t->x4); hipFree(t->AB); hipFree(t->agg); hipFree(t->xagg); hipFree(t->Tn);
-    hipFree(t->ea); hipFree(t->T1); hipFree(t->P); hipFree(t->M1); hipFree(t->C1); hipFree(t->geo); hipFree(t->trans); hipFree(t->ones);
-    hipFree(t->rptr); hipFree(t->rrows); hipFree(t->bw);
     delete t;
     return HD_OK;
 }
@@ -1916,26 +1862,25 @@ extern "C" int hd_egcl_graph_create(hd_egcl* g, const int* row, const int* col, 
     for (int i = 0; i < M; ++i) rptr[i + 1] += rptr[i];
     { std::vector<int> cur(rptr.begin(), rptr.end() - 1); for (int e = 0; e < E; ++e) rrows[cur[vr[e]]++] = e; }
     hd_egcl_graph* t = new hd_egcl_graph();
-    std::memset(t, 0, sizeof(*t));
     t->g = g; t->device = g->device; t->M = M; t->E = E;
     t->Mp = (M + 127) / 128 * 128; t->Ep = std::max(128, (E + 127) / 128 * 128);
     const int H = g->H;
     auto build = [&]() -> int {
-        HD_TRY(dev_upload(&t->row, vr)); HD_TRY(dev_upload(&t->col, vc)); HD_TRY(dev_upload(&t->cptr, cptr)); HD_TRY(dev_upload(&t->crows, crows));
-        HD_TRY(dev_upload(&t->rptr, rptr)); HD_TRY(dev_upload(&t->rrows, rrows));
-        auto zalloc = [&](float** p, size_t count) -> int {
-            HD_TRY(dev_alloc(p, count));
-            HIP_TRY(hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(float)));
+        HD_TRY(dev_upload(t->row, vr)); HD_TRY(dev_upload(t->col, vc)); HD_TRY(dev_upload(t->cptr, cptr)); HD_TRY(dev_upload(t->crows, crows));
+        HD_TRY(dev_upload(t->rptr, rptr)); HD_TRY(dev_upload(t->rrows, rrows));
+        auto zalloc = [&](DevBuf<float>& p, size_t count) -> int {
+            HD_TRY(p.alloc(count));
+            HIP_TRY(hipMemset(p, 0, p.bytes()));
             return HD_OK;
         };
         const size_t Mp = t->Mp, Ep = t->Ep;
-        HD_TRY(zalloc(&t->hin, Mp * H)); HD_TRY(zalloc(&t->hres, Mp * H)); HD_TRY(zalloc(&t->x4, Mp * 4)); HD_TRY(zalloc(&t->AB, Mp * 2 * H));
-        HD_TRY(zalloc(&t->agg, Mp * H)); HD_TRY(zalloc(&t->xagg, Mp * 4)); HD_TRY(zalloc(&t->Tn, Mp * H));
-        HD_TRY(zalloc(&t->T1, Ep * H));         // (t->ea: the caller's edge_attr is read in place since round 3)
-        HD_TRY(zalloc(&t->P, Ep * H)); HD_TRY(zalloc(&t->M1, Ep * H));
-        HD_TRY(zalloc(&t->C1, Ep * H)); HD_TRY(zalloc(&t->geo, Ep * 4)); HD_TRY(zalloc(&t->trans, Ep * 4));
+        HD_TRY(zalloc(t->hin, Mp * H)); HD_TRY(zalloc(t->hres, Mp * H)); HD_TRY(zalloc(t->x4, Mp * 4)); HD_TRY(zalloc(t->AB, Mp * 2 * H));
+        HD_TRY(zalloc(t->agg, Mp * H)); HD_TRY(zalloc(t->xagg, Mp * 4)); HD_TRY(zalloc(t->Tn, Mp * H));
+        HD_TRY(zalloc(t->T1, Ep * H));
+        HD_TRY(zalloc(t->P, Ep * H)); HD_TRY(zalloc(t->M1, Ep * H));
+        HD_TRY(zalloc(t->C1, Ep * H)); HD_TRY(zalloc(t->geo, Ep * 4)); HD_TRY(zalloc(t->trans, Ep * 4));
         std::vector<float> ones(Mp, 1.0f);
-        HD_TRY(dev_upload(&t->ones, ones));
+        HD_TRY(dev_upload(t->ones, ones));
         return HD_OK;
     };
     const int r = build();
@@ -2344,7 +2289,8 @@ extern "C" int hd_colsum_f32(int device, int rows, int n, const float* const* sr
 // one pinned, device-visible result word per device (hipHostMalloc is mapped by default); calls are serialised by the lock, which is
 // held for the few microseconds a call lasts
 static std::mutex g_digest_mu;
-static unsigned long long* g_digest_host[64] = {nullptr};
+// (never destroyed, like the arena pool)
+static PinnedBuf* const g_digest_host = new PinnedBuf[64];
 
 extern "C" int hd_params_digest(int device, const void* const* ptrs_dev, const long long* prefix_dev, int n, long long total,
                                 unsigned long long* state_dev, unsigned long long* digest_host, void* stream) {
@@ -2355,16 +2301,16 @@ extern "C" int hd_params_digest(int device, const void* const* ptrs_dev, const l
     hipStream_t s = (hipStream_t)stream;
     if (total == 0) { *digest_host = 0; return HD_OK; }
     std::lock_guard<std::mutex> lk(g_digest_mu);
-    if (!g_digest_host[device]) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&g_digest_host[device]), 64, hipHostMallocDefault));
+    if (!g_digest_host[device]) HIP_TRY(pinned_alloc(g_digest_host[device], 64));
     DigestArgs a;
     a.ptrs = reinterpret_cast<const uint32_t* const*>(ptrs_dev); a.prefix = prefix_dev; a.n = n; a.total = total;
-    a.state = state_dev; a.host_out = g_digest_host[device];
+    a.state = state_dev; a.host_out = reinterpret_cast<unsigned long long*>((char*)g_digest_host[device]);
     const long long groups = (total + DIGEST_CHUNK - 1) / DIGEST_CHUNK;
     hipLaunchKernelGGL(k_params_digest, dim3((unsigned)groups), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
     // the one host wait of the check, in stream order behind the writes the digest must see
     HIP_TRY(hipStreamSynchronize(s));
-    *digest_host = *reinterpret_cast<volatile unsigned long long*>(g_digest_host[device]);
+    *digest_host = *reinterpret_cast<volatile unsigned long long*>((char*)g_digest_host[device]);
     return HD_OK;
 }
 
@@ -2386,11 +2332,11 @@ extern "C" int hd_mfma_probe(int device, int kind, const float* in1024, float* s
         if (kind == 0) hipLaunchKernelGGL((k_mfma_probe<0>), grid, block, 0, s, in1024, scratch, n);
         else hipLaunchKernelGGL((k_mfma_probe<1>), grid, block, 0, s, in1024, scratch, n);
     };
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
+    Event e0, e1;
+    HIP_TRY(event_create(e0, hipEventDefault));
     {
-        const hipError_t ce = hipEventCreate(&e1);
-        if (ce != hipSuccess) { (void)hipEventDestroy(e0); return fail(HD_E_HIP, std::string("hd_mfma_probe: ") + hipGetErrorString(ce)); }
+        const hipError_t ce = event_create(e1, hipEventDefault);
+        if (ce != hipSuccess) return fail(HD_E_HIP, std::string("hd_mfma_probe: ") + hipGetErrorString(ce));
     }
     launch(iters);                                          // warm-up (clocks, code)
     (void)hipEventRecord(e0, s);
@@ -2399,7 +2345,6 @@ extern "C" int hd_mfma_probe(int device, int kind, const float* in1024, float* s
     const hipError_t se = hipEventSynchronize(e1);
     float ms = 0.f;
     if (se == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (se != hipSuccess) return fail(HD_E_HIP, std::string("hd_mfma_probe: ") + hipGetErrorString(se));
     HIP_TRY(hipGetLastError());
     *ns_per_mfma_per_simd = (double)ms * 1e6 / ((double)iters * 8 * 2);     // 8 MFMAs per iteration and wavefront, 2 wavefronts per SIMD
@@ -2452,8 +2397,8 @@ extern "C" int hd_egcl_backward(hd_egcl* g, hd_egcl_graph* t, const float* h, co
     const size_t wsf = (size_t)EGCL_MAX_SPLIT * (2 * (size_t)H * H + 2 * H);
     const size_t need = 7 * EH + 8 * Ep + 9 * MH + 4 * MH + 4 * Mp + wsf;
     if (t->bw_floats < need) {
-        hipFree(t->bw); t->bw = nullptr; t->bw_floats = 0;
-        HD_TRY(dev_alloc(&t->bw, need));
+        t->bw_floats = 0;
+        HD_TRY(t->bw.alloc(need));
         t->bw_floats = need;
     }
     float* p = t->bw;

@@ -165,8 +165,7 @@ static int set_path_tables(hd_handle* h, PathTables& pt, int K, const int* t_idx
     const size_t row_width = (size_t)step_row_width(form);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
-    hipFree(pt.d_t); hipFree(pt.d_s); hipFree(pt.d_coef); hipFree(pt.d_coef_ip);
-    pt.d_t = pt.d_s = nullptr; pt.d_coef = pt.d_coef_ip = nullptr;
+    pt.d_coef_ip.release();                             // stays empty when no inpainting rows are given
     pt.sched_gen = 0; pt.K = 0;
     pt.t_h.assign(t_idx, t_idx + K);
     pt.s_h.assign(s_idx, s_idx + K);
@@ -176,10 +175,10 @@ static int set_path_tables(hd_handle* h, PathTables& pt, int K, const int* t_idx
     }
     pt.noisy_h.resize((size_t)K);
     for (int k = 0; k < K; ++k) pt.noisy_h[(size_t)k] = form == 0 || (form != 2 && rows[row_width * k + 2] != 0.f);   // k_post_step's `noisy`
-    HD_TRY(dev_upload(&pt.d_t, pt.t_h));
-    HD_TRY(dev_upload(&pt.d_s, pt.s_h));
-    HD_TRY(dev_upload(&pt.d_coef, std::vector<float>(rows, rows + row_width * K)));
-    if (rows_ip) HD_TRY(dev_upload(&pt.d_coef_ip, std::vector<float>(rows_ip, rows_ip + (size_t)4 * K)));
+    HD_TRY(dev_upload(pt.d_t, pt.t_h));
+    HD_TRY(dev_upload(pt.d_s, pt.s_h));
+    HD_TRY(dev_upload(pt.d_coef, std::vector<float>(rows, rows + row_width * K)));
+    if (rows_ip) HD_TRY(dev_upload(pt.d_coef_ip, std::vector<float>(rows_ip, rows_ip + (size_t)4 * K)));
     pt.K = K; pt.form = form; pt.up = up;
     pt.sched_gen = h->sched_gen;
     pt.gen++;                             // captured graphs hold the old table addresses
@@ -201,10 +200,8 @@ extern "C" int hd_set_schedule(hd_handle* h, int T, const float* tau, const floa
     std::vector<int> t_idx((size_t)T), s_idx((size_t)T);
     for (int k = 0; k < T; ++k) { t_idx[(size_t)k] = T - k; s_idx[(size_t)k] = T - 1 - k; }
     HD_TRY(set_path_tables(h, h->every, T, t_idx.data(), s_idx.data(), rows_reversed(coef4, T).data(), nullptr, 0, false));
-    hipFree(h->d_tau);                         // behind set_path_tables' device synchronisation
-    h->d_tau = nullptr;
     h->tau_h.assign(tau, tau + T + 1);
-    HD_TRY(dev_upload(&h->d_tau, h->tau_h));
+    HD_TRY(dev_upload(h->d_tau, h->tau_h));    // behind set_path_tables' device synchronisation
     h->T = T;
     return HD_OK;
 }
@@ -229,13 +226,13 @@ static LoopIO loop_io_captured(const hd_handle* h, const uint32_t* draw_w, hipSt
 }
 
 // The replay stream (the legacy NULL stream cannot be captured: the handle's own stream stands in, ordered behind it), made to
-// wait for the handle's latest replay.  The replay state (d_step, d_draw, d_tcur, d_base, d_ipdraw) belongs to the handle: a replay
+// wait for the handle's latest replay.  The replay state (d_step, d_draw, d_tcur, d_base, ip.d_draw) belongs to the handle: a replay
 // issued on another stream - another topology of this handle, or the same one from another caller stream - must have finished
 // before this one touches it.
 static int replay_enter(hd_handle* h, hipStream_t s, hipStream_t* rs) {
     *rs = s;
     if (s == nullptr) {
-        if (!h->own_stream) HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+        if (!h->own_stream) HIP_TRY(stream_create(h->own_stream, hipStreamNonBlocking));
         *rs = h->own_stream;
         HIP_TRY(hipEventRecord(h->ev_in, s));
         HIP_TRY(hipStreamWaitEvent(*rs, h->ev_in, 0));
@@ -256,7 +253,7 @@ static int replay_quiesce(hd_handle* h, hipStream_t rs) {
 template <typename Key, typename Body>
 static int replay_slot(hd_handle* h, hipStream_t rs, GraphSlot<Key>& slot, const Key& want, Body body) {
     if (slot.exec && slot.key == want) return HD_OK;
-    if (slot.exec) { HD_TRY(replay_quiesce(h, rs)); graph_drop(&slot.exec); }
+    if (slot.exec) { HD_TRY(replay_quiesce(h, rs)); slot.exec.reset(); }
     hipGraph_t graph = nullptr;
     HIP_TRY(hipStreamBeginCapture(rs, hipStreamCaptureModeThreadLocal));
     const int was_prof = h->prof;
@@ -266,9 +263,11 @@ static int replay_slot(hd_handle* h, hipStream_t rs, GraphSlot<Key>& slot, const
     h->prof = was_prof;
     if (rc != HD_OK) { if (graph) hipGraphDestroy(graph); return rc; }
     if (ce != hipSuccess) return fail(HD_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-    const hipError_t ie = hipGraphInstantiate(&slot.exec, graph, nullptr, nullptr, 0);
+    hipGraphExec_t gx = nullptr;
+    const hipError_t ie = hipGraphInstantiate(&gx, graph, nullptr, nullptr, 0);
     hipGraphDestroy(graph);
-    if (ie != hipSuccess) { slot.exec = nullptr; return fail(HD_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+    if (ie != hipSuccess) return fail(HD_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
+    slot.exec.adopt(gx);
     slot.key = want;
     ++slot.builds;
     return HD_OK;
@@ -301,12 +300,10 @@ extern "C" int hd_set_inpaint_schedule(hd_handle* h, int T, const float* coef4) 
     if (T != h->T) return fail(HD_E_INVALID, "hd_set_inpaint_schedule: T differs from the schedule's (hd_set_schedule)");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());
-    hipFree(h->every.d_coef_ip);
-    h->every.d_coef_ip = nullptr;
-    h->ip_sched_gen = 0;
-    HD_TRY(dev_upload(&h->every.d_coef_ip, rows_reversed(coef4, T)));
-    h->ip_sched_gen = h->sched_gen;
-    h->ip_gen++;                               // captured graphs hold the old table address
+    h->ip.sched_gen = 0;
+    HD_TRY(dev_upload(h->every.d_coef_ip, rows_reversed(coef4, T)));
+    h->ip.sched_gen = h->sched_gen;
+    h->ip.gen++;                               // captured graphs hold the old table address
     return HD_OK;
 }
 
@@ -362,21 +359,17 @@ static int inpaint_path_check(const char* who, const hd_handle* h, const char* f
 
 // graph replay: room for the draw words of a step's nd = 3 * resamplings noise streams, and the library-owned mask / known values
 static int grow_ipdraw(hd_handle* h, hipStream_t rs, int nd) {
-    if (nd <= h->ipdraw_cap) return HD_OK;
+    if ((size_t)nd <= h->ip.d_draw.capacity()) return HD_OK;         // (a call that does not inpaint asks for 0 words)
     HD_TRY(replay_quiesce(h, rs));                           // graphs that hold the old address go stale (ip_gen)
-    hipFree(h->d_ipdraw);
-    h->d_ipdraw = nullptr; h->ipdraw_cap = 0;
-    HD_TRY(dev_alloc(&h->d_ipdraw, (size_t)nd));
-    h->ipdraw_cap = nd;
-    h->ip_gen++;
+    HD_TRY(h->ip.d_draw.alloc((size_t)nd));
+    h->ip.gen++;
     return HD_OK;
 }
 
 static int inpaint_buffers(const hd_handle* h, hd_topology* t) {
     const size_t BN = (size_t)t->B * t->N;
-    if (!t->ip_fixed) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->ip_fixed), BN));
-    if (!t->ip_known) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->ip_known), BN * h->D * sizeof(float)));
-    return HD_OK;
+    HD_TRY(t->ip_fixed.alloc_once(BN));
+    return t->ip_known.alloc_once(BN * h->D);
 }
 
 // Round j of R behind its posterior step: put the known rows back at the arrival level and - except in the last round - jump back
@@ -455,14 +448,13 @@ extern "C" int hd_set_chain(hd_handle* h, int K, const int* frame_of, const floa
         if (frame_of[k] < -1 || frame_of[k] >= frames) return fail(HD_E_INVALID, "hd_set_chain: need -1 <= frame_of[k] < frames");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
-    hipFree(h->d_chain_frame); hipFree(h->d_chain_as);
-    h->d_chain_frame = nullptr; h->d_chain_as = nullptr;
-    h->chain_path_gen = 0;
-    HD_TRY(dev_upload(&h->d_chain_frame, std::vector<int>(frame_of, frame_of + K)));
-    if (alpha_sigma) HD_TRY(dev_upload(&h->d_chain_as, std::vector<float>(alpha_sigma, alpha_sigma + (size_t)2 * K)));
-    h->chain_frames = frames;
-    h->chain_path_gen = h->path.gen;
-    h->chain_gen++;                            // captured graphs hold the old table addresses
+    h->chain.d_as.release();                            // stays empty when no {alpha_t, sigma_t} are given
+    h->chain.path_gen = 0;
+    HD_TRY(dev_upload(h->chain.d_frame, std::vector<int>(frame_of, frame_of + K)));
+    if (alpha_sigma) HD_TRY(dev_upload(h->chain.d_as, std::vector<float>(alpha_sigma, alpha_sigma + (size_t)2 * K)));
+    h->chain.frames = frames;
+    h->chain.path_gen = h->path.gen;
+    h->chain.gen++;                            // captured graphs hold the old table addresses
     return HD_OK;
 }
 
@@ -499,9 +491,8 @@ static int set_row_table(hd_handle* h, RowTable& tb, int K, const float* rows, i
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old rows
     if (!tb.d || tb.K != K) {                           // same K: the table stays where captured transitions expect it
-        hipFree(tb.d);
-        tb.d = nullptr; tb.path_gen = 0; tb.K = 0;
-        HD_TRY(dev_alloc(&tb.d, (size_t)width * K));
+        tb.path_gen = 0; tb.K = 0;
+        HD_TRY(tb.d.alloc((size_t)width * K));
         tb.K = K;
         tb.gen++;
     }
@@ -522,15 +513,11 @@ static int refuse(int code, const char* who, const std::string& msg) { return fa
 // grown when `count` exceeds the capacity (then *moved is set), filled from `src` (device or host memory)
 template <typename T>
 int DevTable<T>::fill(const T* src, size_t count, bool* moved, hipStream_t s) {
-    if (count > cap || !p) {
+    if (count > this->capacity() || !*this) {
         HIP_TRY(hipDeviceSynchronize());                // a replay may still read the old table
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        HD_TRY(dev_alloc(&p, count));
-        cap = std::max<size_t>(count, 1);
-        *moved = true;
+        HD_TRY(this->grow(count, moved));
     }
-    if (count) HIP_TRY(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyDefault, s));
+    if (count) HIP_TRY(hipMemcpyAsync(*this, src, count * sizeof(T), hipMemcpyDefault, s));
     return HD_OK;
 }
 
@@ -568,7 +555,7 @@ extern "C" int hd_restraint_attach(hd_topology* topo, const float* obs, int obs_
     HD_TRY(r.anc_idx.fill(anc_idx, (size_t)anc_rows * A, &moved, s));
     HD_TRY(r.anc_f.fill(anc_f, (size_t)anc_rows * A * 5, &moved, s));
     HD_TRY(r.scale.fill(scale, (size_t)scale_rows, &moved, s));
-    if (!r.step) { HD_TRY(dev_alloc(&r.step, (size_t)B * topo->N * 3)); moved = true; }
+    if (!r.step) { HD_TRY(r.step.alloc((size_t)B * topo->N * 3)); moved = true; }
     restraint_bake({{&r.obs_rows, obs_rows}, {&r.P, P}, {&r.pair_rows, pair_rows}, {&r.Q, Q}, {&r.anc_rows, anc_rows}, {&r.A, A},
                     {&r.scale_rows, scale_rows}}, moved || nv0 != r.nv0, &r.gen);
     r.nv0 = nv0;
@@ -612,10 +599,14 @@ extern "C" int hd_restraint_fields(hd_topology* topo, int NF, const float* value
     RestraintState& r = topo->rs;
     r.NF = 0;
     bool moved = false;
-    if (!r.fld_geom) {
-        if (!r.fld_off) HD_TRY(dev_alloc(&r.fld_off, (size_t)HD_MAX_FIELDS + 1));
-        if (!r.fld_dims) HD_TRY(dev_alloc(&r.fld_dims, (size_t)HD_MAX_FIELDS * 3));
-        HD_TRY(dev_alloc(&r.fld_geom, (size_t)HD_MAX_FIELDS * 8));          // last: its presence says all three are there
+    if (!r.fld_geom) {                                  // all three or none: moved in once every allocation succeeded
+        DevBuf<long long> off;
+        DevBuf<int> fdims;
+        DevBuf<float> fgeom;
+        HD_TRY(off.alloc((size_t)HD_MAX_FIELDS + 1));
+        HD_TRY(fdims.alloc((size_t)HD_MAX_FIELDS * 3));
+        HD_TRY(fgeom.alloc((size_t)HD_MAX_FIELDS * 8));
+        r.fld_off = std::move(off); r.fld_dims = std::move(fdims); r.fld_geom = std::move(fgeom);
         moved = true;
     }
     HD_TRY(r.fld_v.fill(values, (size_t)offsets[NF], &moved, s));
@@ -656,7 +647,7 @@ extern "C" int hd_restraint_templates(hd_topology* topo, int NT, int rows, int M
     RestraintState& r = topo->rs;
     r.NT = 0;
     bool moved = false;
-    if (!r.tpl_geom) { HD_TRY(dev_alloc(&r.tpl_geom, (size_t)HD_MAX_TEMPLATES * 2)); moved = true; }
+    if (!r.tpl_geom) { HD_TRY(r.tpl_geom.alloc((size_t)HD_MAX_TEMPLATES * 2)); moved = true; }
     // (host arrays: pageable sources are staged before the call returns)
     HD_TRY(r.tpl_idx.fill(idx, cnt, &moved, s));
     HD_TRY(r.tpl_f.fill(f, cnt * 4, &moved, s));
@@ -733,9 +724,9 @@ extern "C" int hd_restraint_detach(hd_topology* topo) { if (topo) topo->rs.on = 
 static RestraintTables restraint_tables(const hd_topology* t) {
     const RestraintState& s = t->rs;
     RestraintTables r;
-    r.obs = s.obs.p; r.pair_idx = s.pair_idx.p; r.pair_f = s.pair_f.p; r.anc_idx = s.anc_idx.p; r.anc_f = s.anc_f.p;
+    r.obs = s.obs; r.pair_idx = s.pair_idx; r.pair_f = s.pair_f; r.anc_idx = s.anc_idx; r.anc_f = s.anc_f;
     r.obs_rows = s.obs_rows; r.P = s.P; r.pair_rows = s.pair_rows; r.Q = s.Q; r.anc_rows = s.anc_rows; r.A = s.A;
-    r.fld_v = s.fld_v.p; r.fld_off = s.fld_off; r.fld_dims = s.fld_dims; r.fld_geom = s.fld_geom; r.fld_w = s.fld_w.p;
+    r.fld_v = s.fld_v; r.fld_off = s.fld_off; r.fld_dims = s.fld_dims; r.fld_geom = s.fld_geom; r.fld_w = s.fld_w;
     r.fld_w_rows = s.fld_w_rows; r.NF = s.NF;
     return r;
 }
@@ -743,7 +734,7 @@ static RestraintTables restraint_tables(const hd_topology* t) {
 static TemplateTables template_tables(const hd_topology* t) {
     const RestraintState& s = t->rs;
     TemplateTables r;
-    r.idx = s.tpl_idx.p; r.f = s.tpl_f.p; r.geom = s.tpl_geom;
+    r.idx = s.tpl_idx; r.f = s.tpl_f; r.geom = s.tpl_geom;
     r.rows = s.tpl_rows; r.NT = s.NT; r.M = s.tpl_M;
     return r;
 }
@@ -751,7 +742,7 @@ static TemplateTables template_tables(const hd_topology* t) {
 static FeatureTables feature_tables(const hd_topology* t) {
     const RestraintState& s = t->rs;
     FeatureTables r;
-    r.lo = s.ft_lo.p; r.hi = s.ft_hi.p; r.k = s.ft_k.p; r.coef = s.ft_coef.p; r.sum_f = s.ft_sum.p;
+    r.lo = s.ft_lo; r.hi = s.ft_hi; r.k = s.ft_k; r.coef = s.ft_coef; r.sum_f = s.ft_sum;
     r.band_rows = s.ft_band_rows; r.W = s.feat ? s.ft_W : 0; r.sum_rows = s.ft_sum_rows; r.S = s.feat ? s.ft_S : 0;
     r.nv1 = s.ft_nv1; r.nb1 = s.ft_nb1;
     return r;
@@ -791,7 +782,7 @@ static int restrain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const
                            const float* rows, const float* row4, bool framed = false) {
     ProfScope ps(h, io.s, 2);
     RestrainArgs a;
-    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.t = restraint_tables(t); a.scale = t->rs.scale.p;
+    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.t = restraint_tables(t); a.scale = t->rs.scale;
     set_row(a, io, rows, row4, 4);
     a.step = t->rs.step; a.nv0 = t->rs.nv0; a.scale_rows = t->rs.scale_rows;
     a.B = t->B; a.N = t->N; a.D = h->D;
@@ -813,7 +804,7 @@ static int restrain_feat_launch(hd_handle* h, hd_topology* t, const LoopIO& io, 
                                 const float* rows, const float* row4) {
     ProfScope ps(h, io.s, 2);
     RestrainFeatArgs a;
-    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.t = feature_tables(t); a.scale = t->rs.scale.p;
+    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.t = feature_tables(t); a.scale = t->rs.scale;
     set_row(a, io, rows, row4, 4);
     a.ratio = t->rs.ft_ratio; a.scale_rows = t->rs.scale_rows;
     a.B = t->B; a.N = t->N; a.D = h->D;
@@ -973,10 +964,14 @@ extern "C" int hd_steer_attach(hd_topology* topo, int P, double ess, int reset, 
     const bool fresh = !topo->st.f64;
     if (!reset && (fresh || P != topo->st.P))
         return fail(HD_E_STATE, "hd_steer_attach: reset = 0 continues a chain, and this topology holds no steering state for this P");
-    if (fresh) {
-        if (!topo->st.i32) HD_TRY(dev_alloc(&topo->st.i32, 2 * B));
-        if (!topo->st.scratch) HD_TRY(dev_alloc(&topo->st.scratch, 3 * B * topo->N * topo->h->D));
-        HD_TRY(dev_alloc(&topo->st.f64, 6 * B));            // last: its presence says all three are there
+    if (fresh) {                                            // all three or none: moved in once every allocation succeeded
+        DevBuf<int> i32;
+        DevBuf<float> scratch;
+        DevBuf<double> f64;
+        HD_TRY(i32.alloc(2 * B));
+        HD_TRY(scratch.alloc(3 * B * topo->N * topo->h->D));
+        HD_TRY(f64.alloc(6 * B));
+        topo->st.i32 = std::move(i32); topo->st.scratch = std::move(scratch); topo->st.f64 = std::move(f64);
     }
     if (fresh || P != topo->st.P || ess != topo->st.ess) topo->st.gen++;
     topo->st.P = P; topo->st.ess = ess;
@@ -1088,7 +1083,7 @@ extern "C" int hd_diversity_attach(hd_topology* topo, int P, double kappa, doubl
     topo_use(topo, s);
     topo->dv.on = false;
     bool moved = false;
-    if (!topo->dv.step) { HD_TRY(dev_alloc(&topo->dv.step, (size_t)topo->B * topo->N * 3)); moved = true; }
+    if (!topo->dv.step) { HD_TRY(topo->dv.step.alloc((size_t)topo->B * topo->N * 3)); moved = true; }
     // (a host array: a pageable source is staged before the call returns)
     HD_TRY(topo->dv.scale.fill(scale, (size_t)scale_rows, &moved, s));
     restraint_bake({{&topo->dv.P, P}, {&topo->dv.scale_rows, scale_rows}},
@@ -1105,7 +1100,7 @@ static int diverse_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const 
                           const float* rows, const float* row4) {
     ProfScope ps(h, io.s, 2);
     DiverseArgs a;
-    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.scale = t->dv.scale.p;
+    a.z = z; a.eps = eps; a.out = out; a.nm = t->nm_bytes; a.scale = t->dv.scale;
     set_row(a, io, rows, row4, 4);
     a.step = t->dv.step; a.kappa = t->dv.kappa; a.inv_l2 = 1.0 / (t->dv.length * t->dv.length);
     a.nv0 = t->dv.nv0; a.scale_rows = t->dv.scale_rows; a.P = t->dv.P; a.B = t->B; a.N = t->N; a.D = h->D;
@@ -1167,7 +1162,7 @@ static int guide_buffers(hd_handle* h, hd_topology* t) {
     auto pad = [](size_t n) { return (std::max<size_t>(n, 1) + 63) & ~size_t(63); };
     const size_t BN = (size_t)t->B * t->N;
     const size_t n_eps = pad(BN * h->D), n_ctx = pad(BN * (size_t)std::max(1, h->cfg.context_node_nf)), n_w = pad((size_t)t->B);
-    HD_TRY(dev_alloc(&t->guide_mem, n_eps + n_ctx + n_w));
+    HD_TRY(t->guide_mem.alloc(n_eps + n_ctx + n_w));
     t->eps_u = t->guide_mem; t->ctxu_buf = t->eps_u + n_eps; t->wbuf = t->ctxu_buf + n_ctx;
     return HD_OK;
 }
@@ -1176,7 +1171,7 @@ static int guide_buffers(hd_handle* h, hd_topology* t) {
 static int chain_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* eps) {
     ProfScope ps(h, io.s, 2);
     ChainArgs a;
-    a.z = io.z; a.eps = eps; a.nm = t->nm_bytes; a.frame_of = h->d_chain_frame; a.alsig = h->d_chain_as;
+    a.z = io.z; a.eps = eps; a.nm = t->nm_bytes; a.frame_of = h->chain.d_frame; a.alsig = h->chain.d_as;
     a.dst_w = io.captured() ? h->d_chain_dst : nullptr; a.dst = io.captured() ? nullptr : t->chain.dst; a.step_ptr = io.step; a.k = io.row;
     a.nv0 = t->chain.nv0; a.nv1 = t->chain.nv1; a.nb1 = t->chain.nb1; a.B = t->B; a.N = t->N; a.D = h->D;
     if (eps) hipLaunchKernelGGL(k_chain_frame<1>, dim3(t->B), dim3(256), 0, io.s, a);
@@ -1211,12 +1206,12 @@ struct PathCall {
 static int loop_fail(int code, const std::string& msg) { return fail(code, "path loop: " + msg); }
 static int chain_ready(const hd_handle* h, const hd_topology* topo, const PathCall& c, const PathTables& pt, int mol, bool* on) {
     if (!(*on = c.record && topo->chain.dst != nullptr)) return HD_OK;
-    if (!h->d_chain_frame || h->chain_path_gen != pt.gen)
+    if (!h->chain.d_frame || h->chain.path_gen != pt.gen)
         return loop_fail(HD_E_STATE, "a chain sink is attached but the chain tables are not set for the current path (hd_set_chain)");
-    if (h->chain_frames != topo->chain.frames)
+    if (h->chain.frames != topo->chain.frames)
         return loop_fail(HD_E_INVALID, "the attached sink holds " + std::to_string(topo->chain.frames) + " frames, the chain tables were set for " +
-                                       std::to_string(h->chain_frames));
-    if (topo->chain.what == 1 && !h->d_chain_as)
+                                       std::to_string(h->chain.frames));
+    if (topo->chain.what == 1 && !h->chain.d_as)
         return loop_fail(HD_E_STATE, "recording the data prediction needs the {alpha_t, sigma_t} rows (hd_set_chain)");
     if (mol != topo->N) return loop_fail(HD_E_INVALID, "a chain sink records whole molecules only (mol_shape < N)");
     return HD_OK;
@@ -1338,14 +1333,14 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     PathKey key{};
     key.raw_x = c.raw_x; key.raw_h = c.raw_h; key.has_ctx = c.context ? 1 : 0; key.mol_shape = ms; key.noise_rows = c.noise_rows;
     key.k_lo = c.raw_x ? k_lo : 0; key.resamplings = R; key.seed = c.seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
-    key.path_gen = pt.gen; key.ip_gen = R ? h->ip_gen : 0; key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
+    key.path_gen = pt.gen; key.ip_gen = R ? h->ip.gen : 0; key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
     key.ip_parts = parts ? 1 : 0;
     key.rs = restraint_key(h, topo, rsn, framed); key.st = steer_key(h, topo, stn); key.dv = diverse_key(h, topo, dvn);
     PathWords w;
-    w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = R ? h->d_ipdraw : nullptr;
+    w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = R ? h->ip.d_draw : nullptr;
     w.tau = h->d_tau; w.t_idx = pt.d_t; w.s_idx = pt.d_s; w.K = K; w.T = T; w.nd = nd; w.stride = stride; w.chain = rec ? h->d_chain_dst : nullptr;
     auto body = [&]() -> int {
-        LoopIO io = loop_io_captured(h, R ? h->d_ipdraw : h->d_draw, rs);
+        LoopIO io = loop_io_captured(h, R ? h->ip.d_draw : h->d_draw, rs);
         io.z = topo->zbuf; io.ctx = c.context ? topo->ctxbuf : nullptr; io.fixed = topo->ip_fixed; io.known = topo->ip_known;
         io.fixed_h = parts;
         if (gd) { io.ctx_u = topo->ctxu_buf; io.w = topo->wbuf; }
@@ -1355,11 +1350,11 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     };
     // the caller's slot (the every-step, the guided and the unguided transition are graphs of their own: such calls on one topology
     // do not evict each other); so is the recording one (either kind), keyed on everything it bakes in but the sink's address
-    const hipGraphExec_t* gx = &c.slot->exec;
+    const GraphExec* gx = &c.slot->exec;
     if (rec) {
         gx = &topo->g_chain.exec;
         const ChainSink& sk = topo->chain;
-        HD_TRY(replay_slot(h, rs, topo->g_chain, ChainKey{key, sk.what, sk.nv0, sk.nv1, sk.nb1, h->chain_gen}, body));
+        HD_TRY(replay_slot(h, rs, topo->g_chain, ChainKey{key, sk.what, sk.nv0, sk.nv1, sk.nb1, h->chain.gen}, body));
     } else {
         HD_TRY(replay_slot(h, rs, *c.slot, key, body));
     }
@@ -1393,7 +1388,7 @@ static int path_loop(hd_handle* h, hd_topology* topo, const PathCall& c) {
                     "k_lo - 1, which the last call on this topology did not leave (start at a row with c2 = 0, such as k_lo = 0, or "
                     "continue where the last call on the same path ended)");
     if ((size_t)mol * h->D * sizeof(float) > 64 * 1024) return fail(HD_E_INVALID, "multistep path: N * D floats exceed one workgroup's LDS");
-    if (!topo->ms_hist) HD_TRY(dev_alloc(&topo->ms_hist, (size_t)topo->B * topo->N * h->D));
+    HD_TRY(topo->ms_hist.alloc_once((size_t)topo->B * topo->N * h->D));
     topo->ms_gen = 0;                                        // no history unless the whole range ran
     HD_TRY(path_loop_run(h, topo, c));
     topo->ms_gen = pt.gen; topo->ms_k = c.k_hi;              // stream-ordered behind this call, like z
@@ -1445,7 +1440,7 @@ extern "C" int hd_sample_loop_inpaint(hd_handle* h, hd_topology* topo, float* z,
     const char* who = "hd_sample_loop_inpaint";
     HD_TRY(check_ready(h, topo, who));
     if (h->T < 1) return fail(HD_E_STATE, "hd_sample_loop_inpaint: schedule not set (hd_set_schedule)");
-    if (!h->every.d_coef_ip || h->ip_sched_gen != h->sched_gen)
+    if (!h->every.d_coef_ip || h->ip.sched_gen != h->sched_gen)
         return fail(HD_E_STATE, "hd_sample_loop_inpaint: inpainting schedule not set for the current schedule (hd_set_inpaint_schedule)");
     if (!z || !fixed_mask || !xh_known) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: null z / fixed_mask / xh_known");
     if (s_hi > h->T || s_lo < 0 || s_lo > s_hi) return fail(HD_E_INVALID, "hd_sample_loop_inpaint: need 0 <= s_lo <= s_hi <= T");
@@ -1602,15 +1597,13 @@ extern "C" int hd_set_nll_terms(hd_handle* h, int K, const int* t_idx, const flo
         if (t_idx[k] < 1 || t_idx[k] > h->T) return fail(HD_E_INVALID, "hd_set_nll_terms: need 1 <= t_idx[k] <= T");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());                    // a replay may still read the old tables
-    hipFree(h->d_nll_t); hipFree(h->d_nll_coef);
-    h->d_nll_t = nullptr; h->d_nll_coef = nullptr;
-    h->nll_sched_gen = 0; h->nll_K = 0;
-    h->nll_t_h.assign(t_idx, t_idx + K);
-    HD_TRY(dev_upload(&h->d_nll_t, h->nll_t_h));
-    HD_TRY(dev_upload(&h->d_nll_coef, std::vector<float>(coef4, coef4 + (size_t)4 * K)));
-    h->nll_K = K;
-    h->nll_sched_gen = h->sched_gen;
-    h->nll_gen++;                              // captured graphs hold the old table addresses
+    h->nll.sched_gen = 0; h->nll.K = 0;
+    h->nll.t_h.assign(t_idx, t_idx + K);
+    HD_TRY(dev_upload(h->nll.d_t, h->nll.t_h));
+    HD_TRY(dev_upload(h->nll.d_coef, std::vector<float>(coef4, coef4 + (size_t)4 * K)));
+    h->nll.K = K;
+    h->nll.sched_gen = h->sched_gen;
+    h->nll.gen++;                              // captured graphs hold the old table addresses
     return HD_OK;
 }
 
@@ -1621,7 +1614,7 @@ static int nll_ready(hd_handle* h, hd_topology* topo, const char* who, const flo
                      int mol_shape, const float* context) {
     const std::string w(who);
     if (h->T < 1) return fail(HD_E_STATE, w + ": schedule not set (hd_set_schedule)");
-    if (h->nll_K < 1 || h->nll_sched_gen != h->sched_gen)
+    if (h->nll.K < 1 || h->nll.sched_gen != h->sched_gen)
         return fail(HD_E_STATE, w + ": terms not set for the current schedule (hd_set_nll_terms)");
     if ((raw_x == nullptr) != (raw_h == nullptr)) return fail(HD_E_INVALID, w + ": raw_x and raw_h go together");
     if (noise_rows != topo->B) return fail(HD_E_INVALID, w + ": noise_rows must be B");
@@ -1649,7 +1642,7 @@ static int nll_launch_zt(hd_handle* h, hd_topology* t, const LoopIO& io, const f
 static int nll_launch_err(hd_handle* h, hd_topology* t, const LoopIO& io) {
     ProfScope ps(h, io.s, 2);
     NllErrArgs a;
-    a.eps = t->nll_eps; a.net = t->eps; a.coef = h->d_nll_coef; a.acc = io.acc; a.err = io.err; a.step_ptr = io.step; a.k = io.row;
+    a.eps = t->nll_eps; a.net = t->eps; a.coef = h->nll.d_coef; a.acc = io.acc; a.err = io.err; a.step_ptr = io.step; a.k = io.row;
     a.B = t->B; a.ND = t->N * h->D;
     hipLaunchKernelGGL(k_nll_err, dim3(t->B), dim3(256), 0, io.s, a);
     HIP_TRY(hipGetLastError());
@@ -1662,19 +1655,19 @@ extern "C" int hd_nll_terms(hd_handle* h, hd_topology* topo, const float* xh, co
     if (k_lo < 0 || k_lo > k_hi) return fail(HD_E_INVALID, "hd_nll_terms: need 0 <= k_lo <= k_hi <= K");
     HD_TRY(check_ready(h, topo, "hd_nll_terms"));
     HD_TRY(nll_ready(h, topo, "hd_nll_terms", raw_x, raw_h, noise_rows, mol_shape, context));
-    if (k_hi > h->nll_K) return fail(HD_E_INVALID, "hd_nll_terms: need 0 <= k_lo <= k_hi <= K");
+    if (k_hi > h->nll.K) return fail(HD_E_INVALID, "hd_nll_terms: need 0 <= k_lo <= k_hi <= K");
     if (!xh || !acc) return fail(HD_E_INVALID, "hd_nll_terms: null xh / acc");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    const int B = topo->B, N = topo->N, K = h->nll_K, nterms = k_hi - k_lo;
+    const int B = topo->B, N = topo->N, K = h->nll.K, nterms = k_hi - k_lo;
     const size_t BN = (size_t)B * N;
     const size_t zbytes = BN * h->D * sizeof(float);
     const size_t cbytes = BN * h->cfg.context_node_nf * sizeof(float);
     topo_use(topo, s);
     if (nterms == 0) return HD_OK;
-    if (!topo->nll_eps) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_eps), zbytes));
+    HD_TRY(topo->nll_eps.alloc_once(BN * h->D));
     auto term = [&](const LoopIO& io) -> int {               // io.row is the term's position in the list, io.draw its timestep
-        HD_TRY(nll_launch_zt(h, topo, io, h->d_nll_coef, 0.f, 0.f, make_noise(raw_x, raw_h, B, seed, io.base, io.draw, 0), k_lo));
+        HD_TRY(nll_launch_zt(h, topo, io, h->nll.d_coef, 0.f, 0.f, make_noise(raw_x, raw_h, B, seed, io.base, io.draw, 0), k_lo));
         HD_TRY(forward_impl(h, topo, topo->zbuf, io.tcur, 1, io.ctx, -1, topo->eps, io.s));
         return nll_launch_err(h, topo, io);
     };
@@ -1682,7 +1675,7 @@ extern "C" int hd_nll_terms(hd_handle* h, hd_topology* topo, const float* xh, co
         LoopIO io{};
         io.xh = xh; io.ctx = context; io.acc = acc; io.err = err_terms; io.base = sample_id_base; io.s = s;
         for (int k = k_lo; k < k_hi; ++k) {
-            io.row = k; io.draw = (uint32_t)h->nll_t_h[k]; io.tcur = h->d_tau + h->nll_t_h[k];
+            io.row = k; io.draw = (uint32_t)h->nll.t_h[k]; io.tcur = h->d_tau + h->nll.t_h[k];
             HD_TRY(term(io));
         }
         return HD_OK;
@@ -1690,20 +1683,19 @@ extern "C" int hd_nll_terms(hd_handle* h, hd_topology* topo, const float* xh, co
     // The term position lives in d_step; k_nll_advance derives the network time and the draw from the uploaded list.
     hipStream_t rs;
     HD_TRY(replay_enter(h, s, &rs));
-    if (!topo->nll_xh) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_xh), zbytes));
-    if (!topo->nll_acc) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_acc), (size_t)B * sizeof(double)));
+    HD_TRY(topo->nll_xh.alloc_once(BN * h->D));
+    HD_TRY(topo->nll_acc.alloc_once((size_t)B));
     if (err_terms && topo->nll_err_rows < K) {               // grow the e_t table: a graph that holds the old address goes stale (key)
         HD_TRY(replay_quiesce(h, rs));
-        if (topo->nll_err) (void)hipFree(topo->nll_err);
-        topo->nll_err = nullptr; topo->nll_err_rows = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_err), (size_t)K * B * sizeof(float)));
+        topo->nll_err_rows = 0;
+        HD_TRY(topo->nll_err.alloc((size_t)K * B));
         topo->nll_err_rows = K;
     }
     NllKey key;
     key.raw_x = raw_x; key.raw_h = raw_h; key.err = err_terms ? topo->nll_err : nullptr; key.has_ctx = context ? 1 : 0;
-    key.k_lo = raw_x ? k_lo : 0; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen; key.nll_gen = h->nll_gen;
+    key.k_lo = raw_x ? k_lo : 0; key.seed = seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen; key.nll_gen = h->nll.gen;
     NllWords w;
-    w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.tau = h->d_tau; w.t_idx = h->d_nll_t; w.K = K;
+    w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.tau = h->d_tau; w.t_idx = h->nll.d_t; w.K = K;
     HD_TRY(replay_slot(h, rs, topo->g_nll, key, [&]() -> int {
         LoopIO io = loop_io_captured(h, h->d_draw, rs);
         io.xh = topo->nll_xh; io.ctx = context ? topo->ctxbuf : nullptr; io.acc = topo->nll_acc; io.err = err_terms ? topo->nll_err : nullptr;
@@ -1736,7 +1728,7 @@ extern "C" int hd_nll_finish(hd_handle* h, hd_topology* topo, const float* xh, c
     hipStream_t s = (hipStream_t)stream;
     topo_use(topo, s);
     if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(s, h->ev_last, 0));      // zbuf / eps are the replayed term's workspaces too
-    if (!topo->nll_eps) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->nll_eps), (size_t)topo->B * topo->N * h->D * sizeof(float)));
+    HD_TRY(topo->nll_eps.alloc_once((size_t)topo->B * topo->N * h->D));
     LoopIO io{};
     io.xh = xh; io.s = s;
     HD_TRY(nll_launch_zt(h, topo, io, nullptr, consts7[0], consts7[1], make_noise(raw_x, raw_h, topo->B, seed, sample_id_base, 0, 0), 0));
@@ -1779,7 +1771,7 @@ extern "C" int hd_inpaint_parts(hd_handle* h, hd_topology* topo, const uint8_t* 
     topo_use(topo, s);
     topo->ip_parts_on = false;
     const size_t n = (size_t)topo->B * topo->N * h->F;      // a topology's shape is fixed: the buffer never moves
-    if (!topo->ip_parts) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&topo->ip_parts), std::max<size_t>(n, 1)));
+    HD_TRY(topo->ip_parts.alloc_once(n));
     if (h->ev_last_set) HIP_TRY(hipStreamWaitEvent(s, h->ev_last, 0));      // a replay on another stream may still read the old bytes
     if (n) HIP_TRY(hipMemcpyAsync(topo->ip_parts, fixed_h, n, hipMemcpyDeviceToDevice, s));
     topo->ip_parts_on = true;

@@ -129,6 +129,10 @@ int hd_topology_create_s(hd_handle* h, const uint8_t* node_mask, const uint8_t* 
 int hd_topology_destroy(hd_topology* t);
 /* Frees every pooled arena (after their pending work). */
 int hd_arena_pool_trim(void);
+/* The device allocations the library holds in this process, on all devices: what handles, topologies and stage-2 objects own,
+ * and the pooled arenas (memory torch's allocator cannot see; memory torch allocated does not count).  `bytes`, if not null,
+ * receives their size.  After every object is destroyed and the pool is trimmed both are 0.  Needs no GPU (then: 0). */
+long long hd_live_allocations(long long* bytes);
 /* Host-only view of the edge-tile tables hd_topology_create builds for the same masks (no device needed): edges are
  * packed in 32-row tiles per molecule - cuts at molecule-relative multiples of 32, remainders of neighbouring
  * molecules share a tile at 4-row-aligned offsets - so the rows summed into one partial sum ("part") of a node

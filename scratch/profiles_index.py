@@ -76,6 +76,10 @@ RULES = [
     (r"r06_ablate_fp16x3_no_mfma\.log", "fp16x3 edge kernel of the measurement build: shipped / no MFMA (vector side alone, bit 1024) / matrix side alone / no epilogue, same box", "DESIGN 12 item 2, EXPERIMENTS W: wave specialisation cannot clear 6 %"),
     (r"r06_ab_gemm_rows\.log", "same-box A/B of the node-level training GEMMs: k_tgemm vs the row-resident k_tgemm_rows (slower; removed)", "EXPERIMENTS V"),
     (r"r06_ab_dw2_two_chunks\.log", "same-box A/B of k_dw2_f16 with one vs two chunks in flight (slower; reverted)", "EXPERIMENTS V"),
+    (r"owners_bits_(parent|result)\.json", "`scratch/sampling_bits.py` (3733 rows, `use_graph` on and off) on the parent commit's package and library (`parent`, `--root`) and on this commit's (`result`), a fresh process each on one MI355X; the two files are identical", "EXPERIMENTS AV"),
+    (r"owners_restraint_state_timing_(parent1|parent2|result)\.json", "`scratch/restraint_state_timing.py` at its defaults on the parent commit (`parent1`, `parent2`) and on this commit (`result`): fresh processes on one MI355X in the order parent1, result, parent2; `scratch/ab_verdict.py` gives the verdict per kind (all five within)", "EXPERIMENTS AV"),
+    (r"owners_(topology|fresh_masks)_time\.json", "`scratch/topology_time.py` / `scratch/fresh_masks_time.py` at their defaults, parent1, result, parent2 in fresh processes on one MI355X: the figures each script prints (minimum of 5 / best of 3) and the verdict by the rule of `scratch/ab_verdict.py` (all within)", "EXPERIMENTS AV"),
+    (r"owners_bench\.json", "`scratch/bench_ab_compare.py` over `bench.py --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline --no-configs` lines of the parent commit and of this commit (`branch`), alternating on one MI355X", "EXPERIMENTS AV"),
     (r"attach_state_bits_(parent|result)\.json", "`scratch/sampling_bits.py` with its `terms` group (steered + restrained, diverse, diverse + restrained + features, recorded diverse at B = 4 as two groups of 2, steps = 4, `use_graph` on and off): 3733 rows on the parent commit's package and library (`parent`) and on this commit's (`result`), MI355X; the two files are identical", "EXPERIMENTS AU"),
     (r"attach_state_(restraint_state|diversity|chain)_timing_(parent1|parent2|result)\.json", "`scratch/restraint_state_timing.py` / `diversity_timing.py` / `chain_timing.py` (the latter two fp32 and fp16x3, 3 repeats, no Python loop) on the parent commit (`parent1`, `parent2`) and on this commit (`result`): fresh processes on one MI355X per script, in the order parent1, result, parent2; `scratch/ab_verdict.py` gives the verdict per kind", "EXPERIMENTS AU"),
     (r"attach_state_bench\.json", "`scratch/bench_ab_compare.py` over three `bench.py --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline --no-configs` lines, the parent commit twice and the refactored host code once (before its last compaction; device code byte-identical to this commit's), one MI355X: every headline figure of the result inside the range of the parent's two", "EXPERIMENTS AU"),
@@ -83,10 +87,22 @@ RULES = [
     (r"launch_selectors_trace_diff\.txt", "`scratch/launch_trace_driver.py` under `rocprofv3 --kernel-trace` with the parent's (c749001) and the result's library, one MI355X, one call, compared per dispatch by `scratch/launch_trace_diff.py` (kernel name, grid, workgroup size, LDS size, in dispatch order): the driver's result checksums, the statement that the diff is empty, dispatches and distinct launch shapes per kernel name", "DESIGN 4 (which instantiation a launch runs), EXPERIMENTS AS"),
     (r"launch_selectors_bench\.json", "`bench.py --gpus 1 --steps 2 --warmup 1 --full --no-cpu-baseline`, eager and `--graph`, the parent's (c749001) and the result's library alternating on one MI355X in one call, reduced by `scratch/bench_ab_compare.py`: every figure of the JSON lines per run and whether the result's values lie within the range of the parent's own repeats", "EXPERIMENTS AS"),
     (r"r06_.*", "round-6 measurement", "DESIGN 0a"),
+    (r'feature_timing\.json', '`scratch/feature_timing.py`: whole-call seconds of `sample_from_masks` through the path loop unrestrained, with the 200 obstacles of `scratch/restraint_timing.py`, with feature restraints only (dense bands on 30 nodes x 8 channels plus 8 sums) and with both, at B=256, N=30, H=256, L=6, T=1000, graph replay, medians of 3 with their spread, fp32 and fp16x3, one MI355X (EXPERIMENTS.md section AR)', '-'),
+    (r'fuzz_egcl_grads_gpu\.log', '`tests/fuzz_egcl_grads.py` on an MI355X: the `E_GCL` backward on generated graphs (default tier 40 cases seed 17, `big` tier 12 cases seed 23) against float64 autograd through the oracle, worst rel-L2 per tier', 'README parity row; tests/test_gpu_stage2_training.py::test_randomised_layer_gradient_sweep'),
+    (r'fuzz_egcl_grads_oracle_only\.log', 'the same cases with `--oracle-only` on a CPU: the float32 oracle against the float64 oracle at one tenth of the bars, 0 failures, 0 skipped', "the sweep's inputs leave the tolerance to the kernels"),
+    (r'inpaint_parity\.json', 'HIP inpainting chains (T = 20, H = 32 / 64, r = 1 / 3, with / without context, both precisions) vs the CPU restatement: rel-L2 and max-abs per case', 'DESIGN 5 (fragment-constrained sampling); tests/test_gpu_inpaint.py'),
+    (r'inpaint_parts_guard\.json', 'the whole-node call of `scratch/inpaint_timing.py` on the parent commit and on this one, alternating in one session, one process each', 'README row (partial inpainting), EXPERIMENTS AL'),
+    (r'inpaint_parts_timing\.json', '`scratch/inpaint_parts_timing.py`: whole-call seconds of `sample_inpaint` with 10 of 30 nodes known as whole nodes, positions only, features only, at B=256, N=30, H=256, L=6, T=1000, graph replay, medians of 3 with spreads', 'README row (partial inpainting), EXPERIMENTS AL'),
+    (r'inpaint_timing\.json', '`scratch/inpaint_timing.py`: whole-call seconds of plain sampling, `sample_inpaint` r = 1 / 3 and the step-by-step Python loop at B=256, N=30, H=256, L=6, T=1000', 'DESIGN 5, README row (cost of fragment-constrained sampling)'),
+    (r'restraint_state_timing\.json', "host-side cost of gathering the restraint state into `RestraintState`, parent 775496d against the result on one MI355X: `per_call_microseconds` - `scratch/restraint_state_timing.py` (attach, the three energy read-backs, a 4-transition restrained call; 8 processes of each side, alternating, two sessions), medians, the parent's run-to-run spread, all five kinds within it; `seconds` - `scratch/template_timing.py`, `field_timing.py`, `restraint_inpaint_timing.py` (fp32, 2 repeats; parent twice, result once), 4 of 11 kinds outside the two parent runs by 4 - 6 ms of 5.2 s, the unrestrained `path` among them; `bench` - one `bench.py --gpus 1 --steps 3 --warmup 1` line of each", 'DESIGN 5 (restraints: graphs and state), EXPERIMENTS AQ'),
+    (r'sde_solver_timing\.json', '`scratch/sde_solver_timing.py`: whole-call seconds (median / min / max of 3 runs, every run kept) of `path_steps` with `solver="sde2m"` and with `eta=1` on the same uniform path, K = 50, alternating in one process, both precisions, the ratio of the medians and the run-to-run spread of the eta = 1 runs (MI355X: 1.0004x / 1.0005x, spread 0.07 % / 0.33 %)', '-'),
+    (r'step_kernel_bits_parent\.json', "`scratch/sampling_bits.py` with its `steps` group: the matrix of `sampling_bits_*.json` (3576 rows over `use_graph` on / off) plus 141 rows of `hd_posterior_step`, `hd_multistep_step` and `hd_multistep_sde_step` at the C ABI, on the parent commit's library and on the library with the one `k_post_step<FORM>` template, same machine, one session, one fresh process each; the files (and the two `--detail` files) are identical", 'EXPERIMENTS AI'),
+    (r'step_kernel_bits_result\.json', "`scratch/sampling_bits.py` with its `steps` group: the matrix of `sampling_bits_*.json` (3576 rows over `use_graph` on / off) plus 141 rows of `hd_posterior_step`, `hd_multistep_step` and `hd_multistep_sde_step` at the C ABI, on the parent commit's library and on the library with the one `k_post_step<FORM>` template, same machine, one session, one fresh process each; the files (and the two `--detail` files) are identical", 'EXPERIMENTS AI'),
+    (r'step_kernel_timing\.json', 'ms per transition (medians) of `scratch/fewstep_timing.py --rows 20:1 20:0 50:1 50:0 100:1 100:0`, `scratch/solver_timing.py` and `scratch/sde_solver_timing.py`, fresh processes on one MI355X: parent, result, parent in one session and result, parent, result in a second; B=256, N=30, H=256, L=6, T=1000, fp32 and fp16x3', 'EXPERIMENTS AI'),
 ]
 def commit(path):
     out = subprocess.run(["git", "log", "-1", "--format=%h", "--", path], cwd=ROOT, capture_output=True, text=True).stdout.strip()
-    return out or "(uncommitted)"
+    return out or "this commit"
 def describe(name):
     for pat, what, claim in RULES:
         if re.fullmatch(pat, name):

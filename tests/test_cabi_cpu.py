@@ -31,6 +31,45 @@ def test_header_symbols_all_exported(lib):
     assert lib.hd_version() == _lib.ABI_VERSION == 12
 
 
+def test_live_allocations_zero_in_a_fresh_process(lib):
+    """A process that loaded the library and never touched a GPU holds nothing (the counters work without one)."""
+    import subprocess
+    import sys
+    from hierdiff_amd import build
+    code = ("import ctypes as C, sys; lib = C.CDLL(sys.argv[1]); lib.hd_live_allocations.restype = C.c_longlong; "
+            "b = C.c_longlong(-1); n = lib.hd_live_allocations(C.byref(b)); print(n, b.value, lib.hd_live_allocations(None))")
+    out = subprocess.run([sys.executable, "-c", code, build.LIB], check=True, capture_output=True, text=True).stdout.split()
+    assert out == ["0", "0", "0"], out
+
+
+def _csrc_files():
+    d = os.path.join(REPO, "hierdiff_amd", "csrc")
+    return {f: open(os.path.join(d, f)).read() for f in sorted(os.listdir(d)) if f.endswith((".hip", ".hpp", ".h"))}
+
+
+def test_only_mem_hpp_allocates_and_frees():
+    """csrc/mem.hpp owns every allocate / free / create / destroy call; outside it only the two raw functions of hierdiff_hip.hip
+    (hd_raw_alloc / hd_raw_free) name hipMalloc / hipFree.  No object is memset."""
+    banned = ["hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree(", "hipEventCreate", "hipEventDestroy(", "hipStreamCreate",
+              "hipStreamDestroy(", "hipGraphExecDestroy("]
+    files = _csrc_files()
+    assert "mem.hpp" in files and "hierdiff_hip.hip" in files
+    main = files["hierdiff_hip.hip"]
+    raw = re.findall(r"^(?:int|void) hd_raw_(?:alloc|free)\(.*?^}\n", main, flags=re.S | re.M)
+    assert len(raw) == 2, "the two raw functions were not found"
+    assert "hipMalloc(" in raw[0] and "hipFree(" in raw[1]
+    for body in raw:
+        main = main.replace(body, "")
+    files["hierdiff_hip.hip"] = main
+    for name, text in files.items():
+        if name == "mem.hpp":
+            continue
+        for word in banned:
+            assert word not in text, f"{name} contains {word}"
+    for word in ("memset(t,", "memset(g,", "memset(h,"):
+        assert word not in main, word
+
+
 def test_no_gpu_fails_loudly(lib):
     if lib.hd_device_count() > 0:
         pytest.skip("a GPU is visible")
