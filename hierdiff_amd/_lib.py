@@ -102,6 +102,12 @@ SIGNATURES = {
     "hd_diversity_detach": (C.c_int, [_VP]),
     "hd_diverse_eps": (C.c_int, [_VP, _VP, _FP, _FP, C.POINTER(C.c_float), _FP, _VP]),
     "hd_diversity_energy": (C.c_int, [_VP, _VP, _FP, _VP, _VP, _VP]),
+    "hd_set_corrector": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_float)]),
+    "hd_corrector_attach": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
+    "hd_corrector_detach": (C.c_int, [_VP]),
+    "hd_corrector_read": (C.c_int, [_VP, _VP, _VP]),
+    "hd_langevin_step": (C.c_int, [_VP, _VP, _FP, _FP, C.POINTER(C.c_float), C.c_int, _FP, _FP, C.c_int, C.c_uint64, C.c_uint64,
+                                   C.c_uint32, _FP, _VP, _VP]),
     "hd_philox_uniform_host": (C.c_double, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]),
     "hd_diffuse": (C.c_int, [_VP, _VP, _FP, C.c_float, C.c_float, _FP, _FP, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int,
                              _FP, _VP]),

@@ -181,8 +181,9 @@ struct hd_handle {
     InpaintDraws ip;
     ChainTables chain;
     // the loop terms' rows of every transition of the current path: restraints (hd_set_restraint) and diversity (hd_set_diversity)
-    // {alpha_t, sigma_t, lambda_k, clip_k}, steering (hd_set_steer) {alpha_t, sigma_t, beta_k}
-    RowTable rs_rows, dv_rows, st_rows;   // [K][4], [K][4], [K][3]
+    // {alpha_t, sigma_t, lambda_k, clip_k}, steering (hd_set_steer) {alpha_t, sigma_t, beta_k}, correctors (hd_set_corrector)
+    // {sigma_t, q_k, g_max_k}
+    RowTable rs_rows, dv_rows, st_rows, cr_rows;   // [K][4], [K][4], [K][3], [K][3]
     NllTerms nll;
     int split_max_tiles = HD_SPLIT_MAX_TILES;   // (a measurement build may override these from the environment)
     int fuse_min_rows = HD_FUSE_MIN_ROWS;
@@ -234,6 +235,13 @@ struct DiverseKey {
     bool operator==(const DiverseKey& o) const { return P == o.P && gen == o.gen && rows_gen == o.rows_gen; }
 };
 
+// The corrector part (corrector_key): Langevin steps per transition, the mode, the handle's rows; all 0: none attached.
+struct CorrectorKey {
+    int C, adaptive;
+    unsigned long long rows_gen;
+    bool operator==(const CorrectorKey& o) const { return C == o.C && adaptive == o.adaptive && rows_gen == o.rows_gen; }
+};
+
 // Everything a captured transition of the path loop has baked in (plain: resamplings = 0): a cached graph is replayed only when
 // all of it is unchanged.  path_gen is the generation (PathTables::gen) of the tables it runs on (the caller's path, or the every-step tables).
 struct PathKey {
@@ -244,13 +252,13 @@ struct PathKey {
     uint64_t seed;
     unsigned long long weights_gen, sched_gen, path_gen, ip_gen;
     int ip_parts;                                            // 1: an inpainting transition with per-channel masks (hd_inpaint_parts)
-    RestraintKey rs; SteerKey st; DiverseKey dv;             // one part per loop term
+    RestraintKey rs; SteerKey st; DiverseKey dv; CorrectorKey cr;   // one part per loop term
     bool operator==(const PathKey& o) const {
         return raw_x == o.raw_x && raw_h == o.raw_h && has_ctx == o.has_ctx && mol_shape == o.mol_shape &&
                noise_rows == o.noise_rows && k_lo == o.k_lo && resamplings == o.resamplings &&
                w_rows == o.w_rows && phi == o.phi && seed == o.seed &&
                weights_gen == o.weights_gen && sched_gen == o.sched_gen && path_gen == o.path_gen &&
-               ip_gen == o.ip_gen && ip_parts == o.ip_parts && rs == o.rs && st == o.st && dv == o.dv;
+               ip_gen == o.ip_gen && ip_parts == o.ip_parts && rs == o.rs && st == o.st && dv == o.dv && cr == o.cr;
     }
 };
 
@@ -349,6 +357,14 @@ struct DiverseAttach {
     unsigned long long gen = 0;
 };
 
+// hd_corrector_attach: Langevin steps per transition, the mode, and the gains of the last transition that ran (allocated once for
+// the largest C, at an address captured transitions keep).
+struct CorrectorAttach {
+    bool on = false;
+    int C = 0, adaptive = 0;
+    DevBuf<double> gain;                       // [HD_MAX_CORRECTORS][B]
+};
+
 // hd_chain_attach: the caller's sink every path loop on a topology records into (null: none; the caller's memory: nothing to free).
 struct ChainSink {
     float* dst = nullptr;
@@ -402,10 +418,11 @@ struct hd_topology {
     // (one allocation, made by the first guided call)
     DevBuf<float> guide_mem;
     float *eps_u = nullptr, *ctxu_buf = nullptr, *wbuf = nullptr;
-    // what a caller attaches for the time of a call, one struct per loop term: restraints, steering, diversity, the sink
+    // what a caller attaches for the time of a call, one struct per loop term: restraints, steering, diversity, correctors, the sink
     RestraintState rs;
     SteerAttach st;
     DiverseAttach dv;
+    CorrectorAttach cr;
     ChainSink chain;
     // multistep paths (hd_set_path_multistep): the previous transition's data prediction x^ [B][N][D], allocated by the first
     // form-2 call at an address the captured transitions keep; host-side, which path generation and position it belongs to

@@ -1137,6 +1137,83 @@ extern "C" int hd_diversity_energy(hd_handle* h, hd_topology* topo, const float*
     return HD_OK;
 }
 
+// ----------------------------------------------------------------------------- correctors: Langevin steps at the departure level
+
+static bool corrector_row_ok(const float* r) { return r[0] >= 0.f && r[0] - r[0] == 0.f && r[1] >= 0.f && r[1] - r[1] == 0.f && r[2] > 0.f; }
+static const char* const kCorrectorRowMsg = ": need sigma_t >= 0, a finite q_k >= 0 and g_max_k > 0 (inf: no cap)";
+
+extern "C" int hd_set_corrector(hd_handle* h, int K, const float* rows3) {
+    HD_TRY(row_table_check("hd_set_corrector", h, K, rows3, 3, corrector_row_ok, kCorrectorRowMsg));
+    return set_row_table(h, h->cr_rows, K, rows3, 3);
+}
+
+extern "C" int hd_corrector_attach(hd_topology* topo, int C, int adaptive, void* stream) {
+    const char* who = "hd_corrector_attach";
+    if (!topo) return refuse(HD_E_INVALID, who, ": null topology");
+    if (C < 1 || C > HD_MAX_CORRECTORS) return refuse(HD_E_INVALID, who, ": need 1 <= C <= 8 corrector steps per transition");
+    if (adaptive != 0 && adaptive != 1) return refuse(HD_E_INVALID, who, ": adaptive is 0 (mode \"fixed\") or 1 (mode \"snr\")");
+    HIP_TRY(hipSetDevice(topo->device));
+    topo_use(topo, (hipStream_t)stream);
+    topo->cr.on = false;
+    HD_TRY(topo->cr.gain.alloc_once((size_t)HD_MAX_CORRECTORS * topo->B));
+    topo->cr.C = C; topo->cr.adaptive = adaptive;
+    topo->cr.on = true;
+    return HD_OK;
+}
+
+extern "C" int hd_corrector_detach(hd_topology* topo) { if (topo) topo->cr.on = false; return HD_OK; }
+
+extern "C" int hd_corrector_read(hd_topology* topo, double* gains, void* stream) {
+    if (!topo || !gains) return fail(HD_E_INVALID, "hd_corrector_read: null topology / gains");
+    if (!topo->cr.gain || topo->cr.C < 1) return fail(HD_E_STATE, "hd_corrector_read: the topology holds no corrector state (hd_corrector_attach)");
+    HIP_TRY(hipSetDevice(topo->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(topo, s);
+    HIP_TRY(hipMemcpyAsync(gains, topo->cr.gain, (size_t)topo->cr.C * topo->B * sizeof(double), hipMemcpyDefault, s));
+    return HD_OK;
+}
+
+static CorrectorKey corrector_key(const hd_handle* h, const hd_topology* t, bool on) {
+    return on ? CorrectorKey{t->cr.C, t->cr.adaptive, h->cr_rows.gen} : CorrectorKey{};
+}
+
+// One Langevin step z -> out (in place when out == z) on eps: the row as set_row finds it, the draw and the first sample id by value
+// (`ns`) or from the loop's device words.
+static int langevin_launch(hd_handle* h, hd_topology* t, const LoopIO& io, const float* z, const float* eps, float* out, double* gain,
+                           const float* rows, const float* row3, int adaptive, const NoiseSrc& ns, const uint32_t* draw_w) {
+    ProfScope ps(h, io.s, 2);
+    LangevinArgs a;
+    a.z = z; a.eps = eps; a.nm = t->nm_bytes; a.out = out; a.gain = gain;
+    set_row(a, io, rows, row3, 3);
+    a.noise = ns; a.draw_ptr = draw_w; a.base_ptr = io.base_w; a.adaptive = adaptive;
+    a.B = t->B; a.N = t->N; a.D = h->D; a.F = h->F;
+    hipLaunchKernelGGL(k_langevin_step, dim3(t->B), dim3(256), (size_t)t->N * h->D * sizeof(float), io.s, a);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
+extern "C" int hd_langevin_step(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row3, int adaptive,
+                                const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base,
+                                uint32_t draw, float* out, double* gain_out, void* stream) {
+    const char* who = "hd_langevin_step";
+    if (!h || !topo) return refuse(HD_E_INVALID, who, ": null handle/topology");
+    if (!z || !eps || !row3 || !out) return refuse(HD_E_INVALID, who, ": null tensor / row");
+    if (!corrector_row_ok(row3)) return refuse(HD_E_INVALID, who, kCorrectorRowMsg);
+    if (adaptive != 0 && adaptive != 1) return refuse(HD_E_INVALID, who, ": adaptive is 0 (mode \"fixed\") or 1 (mode \"snr\")");
+    if ((raw_x == nullptr) != (raw_h == nullptr)) return refuse(HD_E_INVALID, who, ": raw_x and raw_h go together");
+    if (noise_rows != 1 && noise_rows != topo->B) return refuse(HD_E_INVALID, who, ": noise_rows must be 1 or B");
+    const size_t per = (size_t)topo->B * topo->N * h->D;
+    if (out < eps + per && eps < out + per) return refuse(HD_E_INVALID, who, ": out may not overlap eps");
+    if (out != z && out < z + per && z < out + per) return refuse(HD_E_INVALID, who, ": out may be z itself, not a shifted overlap of it");
+    if ((size_t)topo->N * h->D * sizeof(float) > 64 * 1024) return refuse(HD_E_INVALID, who, ": N * D floats exceed one workgroup's LDS");
+    HIP_TRY(hipSetDevice(h->device));
+    LoopIO io{};
+    io.s = (hipStream_t)stream;
+    topo_use(topo, io.s);
+    return langevin_launch(h, topo, io, z, eps, out, gain_out, nullptr, row3, adaptive,
+                           make_noise(raw_x, raw_h, noise_rows, seed, sample_id_base, draw, noise_rows == 1 ? 1 : 0), nullptr);
+}
+
 // Classifier-free guidance of a path loop: every network call becomes two (context, then ctx_u) and k_guide_combine in place.
 struct GuideSrc {
     const float* ctx_u;   // [B,N,C] the null (or any second) context
@@ -1265,37 +1342,63 @@ static int diverse_ready(const hd_handle* h, const hd_topology* topo, const Path
     return HD_OK;
 }
 
+static int corrector_ready(const hd_handle* h, const hd_topology* topo, const PathCall& c, const PathTables& pt, int mol, bool* on) {
+    if (!(*on = c.record && topo->cr.on)) return HD_OK;
+    if (c.R) return loop_fail(HD_E_INVALID, "correctors are attached to the topology, and inpainting takes none (the replacement would have to be "
+                                            "redone behind every corrector step: hd_corrector_detach)");
+    if (topo->st.on)
+        return loop_fail(HD_E_INVALID, "correctors and steering are both attached to the topology: a call takes one of them (hd_steer_detach / "
+                                       "hd_corrector_detach)");
+    if (mol != topo->N) return loop_fail(HD_E_INVALID, "correctors act on whole molecules only (mol_shape < N)");
+    if (c.raw_x) return loop_fail(HD_E_INVALID, "correctors take no injected noise: its K + 2 rows hold none for them (counter-based generator only)");
+    if (!h->cr_rows.d || h->cr_rows.path_gen != pt.gen)
+        return loop_fail(HD_E_STATE, "correctors are attached but their rows are not set for the current path (hd_set_corrector)");
+    return HD_OK;
+}
+
 static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     const PathTables& pt = *c.pt;
     const GuideSrc* gd = c.gd;
     const int T = h->T, K = pt.K, N = topo->N, form = pt.form, R = c.R, k_lo = c.k_lo;
     const int mol = (c.mol_shape < 0 || c.mol_shape > N) ? N : c.mol_shape;
     const int ms = c.mol_shape < 0 ? -1 : mol;
-    const int nd = 3 * R;
     const uint32_t stride = (uint32_t)T + 2u;
     const int share = (c.noise_rows == 1) ? 1 : 0;
     const int ntr = c.k_hi - k_lo;
     topo_use(topo, c.s);
     if (ntr == 0) return HD_OK;
     if (gd) HD_TRY(guide_buffers(h, topo));
-    bool rec, rsn, stn, dvn;                                 // which terms take part: one ready check each, in this order
+    bool rec, rsn, stn, dvn, crn;                            // which terms take part: one ready check each, in this order
     HD_TRY(chain_ready(h, topo, c, pt, mol, &rec));
     HD_TRY(restraint_ready(h, topo, c, pt, mol, &rsn));
     HD_TRY(steer_ready(h, topo, c, pt, mol, &stn));
     HD_TRY(diverse_ready(h, topo, c, pt, mol, &dvn));
+    HD_TRY(corrector_ready(h, topo, c, pt, mol, &crn));
+    const int nc = crn ? topo->cr.C : 0;                     // corrector steps per transition, on noise streams 1 .. nc
+    const int nd = crn ? 1 + nc : 3 * R;                     // draw words of a captured transition (a corrected call never inpaints)
     const bool framed = rsn && topo->rs.frame == 1;
     const uint8_t* parts = (R && topo->ip_parts_on) ? topo->ip_parts : nullptr;      // calls that do not inpaint ignore the attachment
     const int rounds = R ? R : 1;
+    auto score = [&](const LoopIO& io) -> int {              // eps^ of io.z at the departure level, with every eps term in it
+        HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx, ms, topo->eps, io.s));
+        if (gd) {
+            HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx_u, ms, topo->eps_u, io.s));
+            HD_TRY(guide_launch(h, topo, topo->eps, topo->eps_u, io.w, gd->w_rows, gd->phi, topo->eps, io.s));
+        }
+        if (rsn) HD_TRY(restrain_launch(h, topo, io, io.z, topo->eps, topo->eps, h->rs_rows.d, nullptr, framed));
+        if (rsn && topo->rs.feat) HD_TRY(restrain_feat_launch(h, topo, io, io.z, topo->eps, topo->eps, h->rs_rows.d, nullptr));
+        if (dvn) HD_TRY(diverse_launch(h, topo, io, io.z, topo->eps, topo->eps, h->dv_rows.d, nullptr));
+        return HD_OK;
+    };
     auto transition = [&](const LoopIO& io) -> int {         // all rounds of one transition; io.row is the path position
+        for (int ci = 0; ci < nc; ++ci) {                    // the correctors: Langevin steps on z at the departure level
+            HD_TRY(score(io));
+            const LoopIO::Draw d = io.draw_of(1 + ci, stride);
+            HD_TRY(langevin_launch(h, topo, io, io.z, topo->eps, io.z, topo->cr.gain + (size_t)ci * topo->B, h->cr_rows.d, nullptr,
+                                   topo->cr.adaptive, make_noise(nullptr, nullptr, c.noise_rows, c.seed, io.base, d.value, share), d.word));
+        }
         for (int j = 0; j < rounds; ++j) {
-            HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx, ms, topo->eps, io.s));
-            if (gd) {
-                HD_TRY(forward_impl(h, topo, io.z, io.tcur, 1, io.ctx_u, ms, topo->eps_u, io.s));
-                HD_TRY(guide_launch(h, topo, topo->eps, topo->eps_u, io.w, gd->w_rows, gd->phi, topo->eps, io.s));
-            }
-            if (rsn) HD_TRY(restrain_launch(h, topo, io, io.z, topo->eps, topo->eps, h->rs_rows.d, nullptr, framed));
-            if (rsn && topo->rs.feat) HD_TRY(restrain_feat_launch(h, topo, io, io.z, topo->eps, topo->eps, h->rs_rows.d, nullptr));
-            if (dvn) HD_TRY(diverse_launch(h, topo, io, io.z, topo->eps, topo->eps, h->dv_rows.d, nullptr));
+            HD_TRY(score(io));
             if (stn) HD_TRY(steer_launch(h, topo, io, io.z, topo->eps, h->st_rows.d, nullptr, io.draw_of(0, stride), c.seed,
                                          form == 3 ? topo->ms_hist : nullptr));
             if (rec && j == rounds - 1 && topo->chain.what == 1) HD_TRY(chain_launch(h, topo, io, topo->eps));
@@ -1333,14 +1436,15 @@ static int path_loop_run(hd_handle* h, hd_topology* topo, const PathCall& c) {
     PathKey key{};
     key.raw_x = c.raw_x; key.raw_h = c.raw_h; key.has_ctx = c.context ? 1 : 0; key.mol_shape = ms; key.noise_rows = c.noise_rows;
     key.k_lo = c.raw_x ? k_lo : 0; key.resamplings = R; key.seed = c.seed; key.weights_gen = h->weights_gen; key.sched_gen = h->sched_gen;
-    key.path_gen = pt.gen; key.ip_gen = R ? h->ip.gen : 0; key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
+    key.path_gen = pt.gen; key.ip_gen = nd ? h->ip.gen : 0; key.w_rows = gd ? gd->w_rows : 0; key.phi = gd ? gd->phi : 0.f;
     key.ip_parts = parts ? 1 : 0;
     key.rs = restraint_key(h, topo, rsn, framed); key.st = steer_key(h, topo, stn); key.dv = diverse_key(h, topo, dvn);
+    key.cr = corrector_key(h, topo, crn);
     PathWords w;
-    w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = R ? h->ip.d_draw : nullptr;
+    w.step = h->d_step; w.draw = h->d_draw; w.t_cur = h->d_tcur; w.base = h->d_base; w.ipdraw = nd ? h->ip.d_draw : nullptr;
     w.tau = h->d_tau; w.t_idx = pt.d_t; w.s_idx = pt.d_s; w.K = K; w.T = T; w.nd = nd; w.stride = stride; w.chain = rec ? h->d_chain_dst : nullptr;
     auto body = [&]() -> int {
-        LoopIO io = loop_io_captured(h, R ? h->ip.d_draw : h->d_draw, rs);
+        LoopIO io = loop_io_captured(h, nd ? h->ip.d_draw : h->d_draw, rs);
         io.z = topo->zbuf; io.ctx = c.context ? topo->ctxbuf : nullptr; io.fixed = topo->ip_fixed; io.known = topo->ip_known;
         io.fixed_h = parts;
         if (gd) { io.ctx_u = topo->ctxu_buf; io.w = topo->wbuf; }

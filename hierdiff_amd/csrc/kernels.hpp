@@ -14,7 +14,7 @@
 //     one launch in either mode (k_node for the fp16 split, k_node_f32).
 // Files: k_gemm_r16.hpp (fp32 node GEMMs of small / medium batches), common.hpp (types, helpers, RNG), k_node.hpp, k_edge.hpp, k_edge_split.hpp (fp32 edge kernel of very small batches), k_edge_bwd.hpp (training: backward of an edge layer),
 // k_sampling.hpp (output stage, posterior step, decode, noise), k_inpaint.hpp (fragment-constrained sampling: replacement step, jump back, decode fix-up), k_egcl.hpp (stage-2 layer E_GCL, forward), k_tgemm.hpp (training: general fp32 GEMM of the node-level Linears, forward / dX / dW split-K), k_loss.hpp (training: the variational loss around the network call, one kernel per direction), k_nll.hpp (scoring: every term of the variational bound in the device loop), k_edit.hpp (editing given molecules: noised start state, spherical interpolation of latents), k_guide.hpp (classifier-free guidance: the combination of the two network outputs), k_chain.hpp (recording a sampling trajectory: one frame of the chain per kept transition), k_digest.hpp (content digest of the parameter tensors: guards the packed weight images against silent staleness), k_refine.hpp (refine model: embedding gather, squared-distance edge attribute, size-restricted softmax head).  (The one-wave-per-SIMD edge-kernel experiments live in scratch/experiments/.)
-// k_restrain.hpp (restraint-guided sampling: the gradient of an obstacle / distance / anchor energy on the data prediction into eps^, the energy itself), k_restrain_feat.hpp (feature restraints: bands and molecule-wide sums on the data prediction's h into eps^_h, their energy), k_diverse.hpp (diverse sampling: the rows of a group repel by their aligned RMSD on the data prediction, into eps^; the energy and the RMSD matrix).
+// k_restrain.hpp (restraint-guided sampling: the gradient of an obstacle / distance / anchor energy on the data prediction into eps^, the energy itself), k_restrain_feat.hpp (feature restraints: bands and molecule-wide sums on the data prediction's h into eps^_h, their energy), k_diverse.hpp (diverse sampling: the rows of a group repel by their aligned RMSD on the data prediction, into eps^; the energy and the RMSD matrix), k_langevin.hpp (predictor-corrector sampling: one Langevin step on z at a fixed noise level).
 #pragma once
 #include "common.hpp"
 #include "k_node.hpp"
@@ -38,5 +38,6 @@
 #include "k_restrain_feat.hpp"
 #include "k_steer.hpp"
 #include "k_diverse.hpp"
+#include "k_langevin.hpp"
 #include "k_digest.hpp"
 #include "k_refine.hpp"

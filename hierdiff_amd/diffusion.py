@@ -28,7 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from . import diversity as diversity_mod, restraints as restraints_mod, steering as steering_mod
+from . import corrector as corrector_mod, diversity as diversity_mod, restraints as restraints_mod, steering as steering_mod
 from .distributions import DistributionNodes
 from .dynamics import EGNN_dynamics_QM9, Topology, _ptr, _stream
 from .geom_stats import GEOM_FRAGMENT_HISTOGRAM
@@ -219,6 +219,11 @@ class DiffusionQM9(_Base):
         # = 1, or a strength or scale of 0 = nothing changes).  `diversity_last`: the `diversity.Result` of the last diverse call.
         self.diversity = None
         self.diversity_last = None
+        # predictor-corrector sampling (hierdiff_amd/corrector.py): the default of the `corrector` keyword (a `corrector.Corrector`; None,
+        # steps = 0 or a strength of 0 = nothing changes).  `corrector_last`: [C, B] float64, the gains of the last transition of the last
+        # corrected call (0 where a molecule kept its bits).
+        self.corrector = None
+        self.corrector_last = None
 
     def check_issues_norm_values(self, num_stdevs=8):
         """diffusion_qm9.py:117-131 (predefined schedules only)."""
@@ -642,6 +647,9 @@ class DiffusionQM9(_Base):
             if diversity_mod.stochastic(pl.eta):
                 raise ValueError(f"{what}: diversity with fix_noise is allowed only on a path that draws nothing (eta = 0, solver "
                                  "'dpm2m'): shared noise would pull the rows of a group together again")
+        if pl.corrector is not None and pl.diversity is not None and fix_noise:
+            raise ValueError(f"{what}: diversity with fix_noise is allowed only on a call that draws nothing, and corrector steps draw: "
+                             "shared noise would pull the rows of a group together again")
         return pl
 
     def _resolve_path(self, steps=None, eta=None, spacing=None, timesteps=None, inpaint: bool = False, solver=None,
@@ -746,6 +754,13 @@ class DiffusionQM9(_Base):
         self._rows_open("diversity", dv.key(), lambda pt: self._row_args(handle, tabs, pt, lambda g, path: diversity_mod.rows(g, path, dv, nv0)),
                         "hd_set_diversity")
         diversity_mod.attach(topo, dv.P, dv.strength, dv.length, dv.scale, nv0, _stream(dev))
+
+    def _corrector_open(self, handle, topo, tabs, cr, dev):
+        """Attach the corrector of a resolved call (`corrector.Corrector`) to `topo` behind its rows (hd_set_corrector, once per (path
+        tables, mode, strength, cap)).  The caller detaches (hd_corrector_detach)."""
+        self._rows_open("corrector", cr.key(), lambda pt: self._row_args(handle, tabs, pt, lambda g, path: corrector_mod.rows(g, path, cr)),
+                        "hd_set_corrector")
+        corrector_mod.attach(topo, cr, _stream(dev))
 
     def _diversity_result(self, pl, x, node_mask):
         """`diversity_last` of a diverse call's returned x: Phi and the aligned RMSD matrix per group (hd_diversity_energy), attached as
@@ -954,7 +969,7 @@ class DiffusionQM9(_Base):
         zz = z if st.tail is None else torch.cat([z, st.tail], dim=1).contiguous()      # a pocket's fixed rows ride along
         mol = -1 if st.tail is None else st.N
         common = (_ptr(rx), _ptr(rh), rows, seed, base, int(self.use_graph))
-        steer, dvs, ran = getattr(pl, "steer", None), getattr(pl, "diversity", None), False
+        steer, dvs, crs, ran = getattr(pl, "steer", None), getattr(pl, "diversity", None), getattr(pl, "corrector", None), False
         # every term the plan asks for is closed behind the loop - also when its opening, the loop or another close raises
         with contextlib.ExitStack() as closes:
             if pl.restraints is not None:
@@ -966,6 +981,9 @@ class DiffusionQM9(_Base):
             if dvs is not None:
                 closes.callback(lambda: _lib.check(lib.hd_diversity_detach(topo.ptr), "hd_diversity_detach"))
                 self._diversity_open(st.h, topo, st.tabs, dvs, st.dev)
+            if crs is not None:
+                closes.callback(lambda: _lib.check(lib.hd_corrector_detach(topo.ptr), "hd_corrector_detach"))
+                self._corrector_open(st.h, topo, st.tabs, crs, st.dev)
             if pl.frames is not None:
                 closes.callback(lambda: _lib.check(lib.hd_chain_detach(topo.ptr), "hd_chain_detach"))
                 st.chain = self._chain_open(st.h, topo, st.tabs, pl.frames, pl.record, st.B, st.N, st.dev, st.chain)
@@ -986,6 +1004,8 @@ class DiffusionQM9(_Base):
                     (lib.hd_sample_loop, "hd_sample_loop", pl.K - k_lo, pl.K - k_hi)
                 _lib.check(fn(st.h, topo.ptr, zz.data_ptr(), _ptr(st.ctx), mol, int(lo), int(hi), *common, st.stream), name)
             ran = True
+            if crs is not None and int(k_hi) > int(k_lo):
+                self.corrector_last = corrector_mod.read_gains(topo, crs, st.B, st.dev, st.stream)
         return (zz if st.tail is None else zz[:, :st.N].contiguous()), st.chain
 
     def _decode(self, st, z, node_mask, edge_mask, fix_noise, noise, chain=None, inpaint=None, eps=None):
@@ -1023,7 +1043,7 @@ class DiffusionQM9(_Base):
                           solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                           keep_frames: Optional[int] = None, record: Optional[str] = None,
                           restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-                          particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None):
+                          particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None, corrector=None):
         """z_T -> (x, h) for given masks: draw z_T, T posterior steps, final decode.
 
         restraints / restraint_scale / restraint_schedule / restraint_clip (keyword-only; None: the model's attributes of the same
@@ -1180,7 +1200,7 @@ class DiffusionQM9(_Base):
                    guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                    solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                    restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-                   particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None):
+                   particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None, corrector=None):
         """Transitions k_lo .. k_hi-1 of `sample_from_masks`'s few-step loop on a given z [B,N,D] (normalised units, the state at
         path position k_lo); returns the state at position k_hi (default: the end of the path, z_0 before the decode).  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.
@@ -1330,6 +1350,7 @@ class DiffusionQM9(_Base):
         of `nll_full`."""
         from . import scoring
         device = torch.device(device)
+        corrector_mod.refuse(self, "score", kw.get("corrector"), ": it evaluates the bound of given molecules and samples nothing")
         extra = set(kw) - {"terms", "timesteps", "seed", "sample_id_base", "use_graph"}
         if extra:
             raise ValueError(f"score: unsupported keyword(s) {sorted(extra)} (terms, timesteps, seed, sample_id_base, use_graph)")
@@ -1444,6 +1465,7 @@ class DiffusionQM9(_Base):
         _rs.refuse(self, "encode", restraints, ": the inversion follows the network's own flow")
         steering_mod.refuse(self, "encode")
         diversity_mod.refuse(self, "encode", None, ": the inversion follows the network's own flow")
+        corrector_mod.refuse(self, "encode", None, ": the inversion follows the network's own flow")
         if paths.check_solver(solver) is not None:
             raise ValueError(f"encode: the inversion is first order (eta = 0 upwards); solver {solver!r} is not supported")
         t_end = self._grid_index(self.T if t_end is None else t_end, 1, "t_end")
@@ -1494,7 +1516,7 @@ class DiffusionQM9(_Base):
                      raw_noises: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, guidance_scale=None, guidance_context=None, guidance_rescale: Optional[float] = None,
                      solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                      restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-                     particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None):
+                     particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None, corrector=None):
         """Transitions k_lo .. k_hi-1 of `sample_from_latent`'s partial chain on a given z [B,N,D] (the state at path position k_lo);
         returns the state at position k_hi (default: the end, z_0 before the decode), as `path_steps` does for a full path.  Draws are
         keyed by the arrival step, so a chain cut into pieces gives the bits of the whole.  `raw_noises`: k_hi - k_lo injected
@@ -1515,7 +1537,7 @@ class DiffusionQM9(_Base):
                            solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                            keep_frames: Optional[int] = None, record: Optional[str] = None,
                            restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-                           particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None):
+                           particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None, corrector=None):
         """(x, h) from a state z [B,N,D] at the grid index `t_start` (default T; normalised units - what `diffuse` and `encode`
         return): the partial reverse chain on `paths.partial_path(T, t_start, steps, spacing, timesteps)` (default: every grid point
         below t_start) inside the library's loop (hd_sample_path), then the final decode of `sample_from_masks`.  `eta` defaults to
@@ -1670,6 +1692,7 @@ class DiffusionQM9(_Base):
         _rs.refuse(self, "interpolate", restraints, ": its frames are reconstructions of the interpolated latents")
         steering_mod.refuse(self, "interpolate")
         diversity_mod.refuse(self, "interpolate", None, ": its frames are reconstructions of the interpolated latents")
+        corrector_mod.refuse(self, "interpolate", None, ": its frames are reconstructions of the interpolated latents")
         device = torch.device(device)
         if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or int(frames) < 2:
             raise ValueError(f"frames must be an integer >= 2, got {frames!r}")
@@ -1965,7 +1988,7 @@ class DiffusionQM9(_Base):
                solver: Optional[str] = None, lower_order_final: Optional[bool] = None,
                keep_frames: Optional[int] = None, record: Optional[str] = None,
                restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-               particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None):
+               particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None, corrector=None):
         """diffusion_qm9.py:347-395: list of {'x': [n_i,3], 'h': [n_i,8], ('context': [n_i,1])} on the CPU.
         steps / eta / spacing / timesteps: few-step sampling, see `sample_from_masks`; guidance_scale (a float or a
         [num_samples] tensor) / guidance_context ([num_samples, n_max, C]) / guidance_rescale: classifier-free guidance, ibid.;
@@ -2069,6 +2092,7 @@ class DiffusionQM9(_Base):
         _rs.refuse(self, "sample_batches", restraints, ": the batches' padded widths and molecule counts differ (use sample)")
         steering_mod.refuse(self, "sample_batches")
         diversity_mod.refuse(self, "sample_batches", None, ": the batches' molecule counts differ (use sample)")
+        corrector_mod.refuse(self, "sample_batches", None, " (use sample)")
         # classifier-free guidance (`sample_from_masks`): guidance_scale may also be a list / tuple of scales cycled per batch the way
         # context_range is; inside a merged device batch it becomes one scale per molecule
         from . import guidance
@@ -2142,7 +2166,7 @@ class EnVariationalDiffusion(DiffusionQM9):
     @torch.no_grad()
     def sample(self, n_samples, n_nodes, node_mask, edge_mask, context, fix_noise=False, *,  # type: ignore[override]
                steps=None, eta=None, spacing=None, timesteps=None, guidance_scale=None, guidance_context=None, guidance_rescale=None,
-               solver=None, lower_order_final=None):
+               solver=None, lower_order_final=None, corrector=None):
         assert node_mask.shape[0] == n_samples and node_mask.shape[1] == n_nodes
         x, h = self.sample_from_masks(node_mask, edge_mask, context, fix_noise=fix_noise, **given(locals()))
         if self.debug_checks:
@@ -2157,7 +2181,7 @@ class EnVariationalDiffusion(DiffusionQM9):
     @torch.no_grad()
     def sample_chain(self, n_samples, n_nodes, node_mask, edge_mask, context, keep_frames=None, *,
                      steps=None, eta=None, spacing=None, timesteps=None, guidance_scale=None, guidance_context=None,
-                     guidance_rescale=None, solver=None, lower_order_final=None, record=None):
+                     guidance_rescale=None, solver=None, lower_order_final=None, record=None, corrector=None):
         """en_diffusion.py:669-710: the reverse chain of `sample` with `keep_frames` of its states kept (None: all of them - T on
         the full chain, the number of transitions of a few-step one).  Returns [n_samples * keep_frames, N, D], frame-major, in data
         units: frame (s * keep_frames) // T holds z_s (the last state that falls into a frame stays) and frame 0 cat(x, h) of the

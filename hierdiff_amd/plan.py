@@ -11,12 +11,12 @@ from typing import List, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import diversity as _diversity, guidance as _guidance, paths, restraints as _rs, steering as _steering
+from . import corrector as _corrector, diversity as _diversity, guidance as _guidance, paths, restraints as _rs, steering as _steering
 
 #: the sampling keywords of the entry points; the list forms (`sample`, `sample_batches`, `vary`, the EDM signature) forward those given
 KEYWORDS = ("steps", "eta", "spacing", "timesteps", "guidance_scale", "guidance_context", "guidance_rescale", "solver",
             "lower_order_final", "keep_frames", "record", "restraints", "restraint_scale", "restraint_schedule", "restraint_clip",
-            "particles", "steer_scale", "steer_ess", "steer_schedule", "restraint_frame", "diversity")
+            "particles", "steer_scale", "steer_ess", "steer_schedule", "restraint_frame", "diversity", "corrector")
 
 
 def given(values: dict) -> dict:
@@ -35,6 +35,7 @@ class Plan(NamedTuple):
     chain_t: Optional[torch.Tensor]               # [keep] int64, the grid index every frame has arrived at
     steer: Optional[_steering.Steer] = None       # a steered call: particles per group, beta, rho; None: the unsteered code path
     diversity: Optional[_diversity.Diversity] = None   # a diverse call: rows of a group repel by aligned RMSD; None: the code path without
+    corrector: Optional[_corrector.Corrector] = None   # a corrected call: Langevin steps ahead of every predictor step; None: the code path without
 
 
 def unsupported(model, what: str, pocket=None, needs_noise: bool = True, pocket_error=NotImplementedError) -> None:
@@ -102,7 +103,7 @@ def plan(model, what: str, kind: str = "full", *, t_start=None, pocket=None, inj
          N: Optional[int] = None, force_path: bool = False, guided: bool = True, steps=None, eta=None, spacing=None, timesteps=None, guidance_scale=None,
          guidance_context=None, guidance_rescale=None, solver=None, lower_order_final=None, keep_frames=None, record=None,
          restraints=None, restraint_scale=None, restraint_schedule=None, restraint_clip=None,
-         particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None) -> Plan:
+         particles=None, steer_scale=None, steer_ess=None, steer_schedule=None, restraint_frame=None, diversity=None, corrector=None) -> Plan:
     """The `Plan` of the call `what`.  `kind`: "full" (the chain from T), "latent" (from `t_start`) or "inpaint" (from T, ancestral
     steps only; it takes restraints only with restraint_frame="known" - its callers refuse them otherwise - and then always runs on
     a path; "known" with restraints in any other kind is a ValueError).  `pocket`: the fixed residues of the call, if any; `injected`: the
@@ -116,8 +117,12 @@ def plan(model, what: str, kind: str = "full", *, t_start=None, pocket=None, inj
     diversity: diverse sampling (hierdiff_amd/diversity.py) -> `Plan.diversity`; None, particles = 1, or a strength or scale of 0 is the
     plan without it, field for field.  Its errors come behind steering's; an inpainting plan and a steered plan refuse it.
 
-    Errors are raised in this order: path and solver, guidance, restraints, chain (keep_frames / record), steering, diversity; the shapes of
-    a call's tensors are its entry point's business and come after the plan.  A guided, restrained, recorded or diverse call always runs on a path:
+    corrector: predictor-corrector sampling (hierdiff_amd/corrector.py) -> `Plan.corrector`; None, steps = 0, or a strength of 0 in every
+    row is the plan without it, field for field.  Its errors come last, behind diversity's; an inpainting plan, a steered plan and a call
+    with injected noise refuse it.
+
+    Errors are raised in this order: path and solver, guidance, restraints, chain (keep_frames / record), steering, diversity, corrector; the
+    shapes of a call's tensors are its entry point's business and come after the plan.  A guided, restrained, recorded, diverse or corrected call always runs on a path:
     where the keywords ask for the plain loop it gets the identity path with ancestral steps - here, and nowhere else."""
     if kind == "latent":
         _, path, eta = latent_path(model, t_start, steps, eta, spacing, timesteps, solver, lower_order_final)
@@ -151,7 +156,8 @@ def plan(model, what: str, kind: str = "full", *, t_start=None, pocket=None, inj
         unsupported(model, f"{what}: recording a chain", pocket, needs_noise)
         code = 1 if record == "x0" else 0
     diverse = _diversity.wanted(model, diversity)
-    if path is None and (gd is not None or rr is not None or code is not None or (diverse and kind != "inpaint")):
+    corrected = _corrector.wanted(model, corrector)
+    if path is None and (gd is not None or rr is not None or code is not None or ((diverse or corrected) and kind != "inpaint")):
         path, eta = paths.build_path(model.T), 1.0
     frames = chain_t = None
     if code is not None:
@@ -173,4 +179,14 @@ def plan(model, what: str, kind: str = "full", *, t_start=None, pocket=None, inj
                                       f"(it acts in {_diversity.WHERE})")
         unsupported(model, f"{what}: diversity", pocket, needs_noise)
         dv = _diversity.resolve(model, diversity, eta, K, B, what, injected=injected, steered=st is not None)
-    return Plan(path, eta, K, gd, rr, frames, code, chain_t, st, dv)
+    cr = None
+    if corrected:
+        if kind == "inpaint":
+            raise NotImplementedError(f"{what}: predictor-corrector sampling is not supported here: the replacement of the known fragments "
+                                      f"would have to be redone behind every corrector step (it acts in {_corrector.WHERE})")
+        if injected:
+            raise NotImplementedError(f"{what}: predictor-corrector sampling takes no injected noise (raw_noises): its K + 2 rows hold none "
+                                      "for the corrector steps (counter-based generator only)")
+        unsupported(model, f"{what}: predictor-corrector sampling", pocket, True)
+        cr = _corrector.resolve(model, corrector, K, what, steered=st is not None)
+    return Plan(path, eta, K, gd, rr, frames, code, chain_t, st, dv, cr)

@@ -282,7 +282,36 @@ def parse_args(argv=None):
                     help="with --diverse: the largest step per node in noise-prediction units (default: none)")
     ap.add_argument("--diverse-schedule", choices=["score", "sigma"], default=None,
                     help="with --diverse: the weight of transition k, nv0 sigma_t / alpha_t (score, default) or sigma_t")
+    ap.add_argument("--correctors", type=int, default=None, metavar="C",
+                    help="predictor-corrector sampling: C (1 .. 8) Langevin steps at the departure level of every transition, on the "
+                         "score the network and the call's terms define (k_langevin_step); each costs one more network call.  Combines "
+                         "with everything --steps combines with except --known / --grow and --particles.  Mechanism only: r = 0.16 is "
+                         "Song et al.'s image value; which C and r help is for a trained checkpoint to show.")
+    ap.add_argument("--corrector-snr", type=float, default=None, metavar="R", help="with --correctors: Song's signal-to-noise ratio r of "
+                    "mode snr (default 0.16)")
+    ap.add_argument("--corrector-mode", choices=["snr", "fixed"], default=None,
+                    help="with --correctors: the gain follows the norms of noise and score per molecule (snr, default), or is "
+                         "--corrector-gain (fixed)")
+    ap.add_argument("--corrector-gain", type=float, default=None, metavar="G", help="with --correctors --corrector-mode fixed: the gain g")
     args = ap.parse_args(argv)
+    if args.correctors is None and (args.corrector_snr is not None or args.corrector_mode is not None or args.corrector_gain is not None):
+        ap.error("--corrector-snr / --corrector-mode / --corrector-gain need --correctors")
+    if args.correctors is not None:
+        if not 1 <= args.correctors <= 8:
+            ap.error("--correctors must lie in 1 .. 8")
+        if (args.corrector_mode == "fixed") != (args.corrector_gain is not None):
+            ap.error("--corrector-gain and --corrector-mode fixed go together")
+        if args.corrector_mode == "fixed" and args.corrector_snr is not None:
+            ap.error("--corrector-snr goes with --corrector-mode snr")
+        for name, v in (("--corrector-snr", args.corrector_snr), ("--corrector-gain", args.corrector_gain)):
+            if v is not None and not (math.isfinite(v) and v >= 0.0):
+                ap.error(f"{name} must be finite and >= 0")
+        if args.particles is not None:
+            ap.error("--correctors does not combine with --particles (the particles' weights follow the predictor's moves alone)")
+        if args.known is not None or args.grow is not None:
+            ap.error("--correctors does not combine with --known / --grow (the replacement would have to be redone behind every corrector step)")
+        if args.score is not None or args.interpolate is not None:
+            ap.error("--correctors does not combine with --score / --interpolate")
     if (args.diverse is None) != (args.diverse_length is None):
         ap.error("--diverse and --diverse-length go together")
     if args.diverse is None and (args.diverse_strength is not None or args.diverse_clip is not None or args.diverse_schedule is not None):
@@ -462,6 +491,12 @@ def main(argv=None) -> int:
         from .diversity import Diversity
         chain.update(diversity=Diversity(args.diverse, args.diverse_length, 1.0 if args.diverse_strength is None else args.diverse_strength,
                                          schedule=args.diverse_schedule or "score", clip=args.diverse_clip))
+    if args.correctors is not None:
+        from .corrector import Corrector
+        if args.corrector_mode == "fixed":
+            chain.update(corrector=Corrector(args.correctors, mode="fixed", gain=args.corrector_gain))
+        else:
+            chain.update(corrector=Corrector(args.correctors, snr=0.16 if args.corrector_snr is None else args.corrector_snr))
 
     if args.score is not None:
         if world > 1:

@@ -651,6 +651,49 @@ int hd_diversity_detach(hd_topology* topo);
 int hd_diverse_eps(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row4, float* out, void* stream);
 int hd_diversity_energy(hd_handle* h, hd_topology* topo, const float* x, double* phi, double* rmsd, void* stream);
 
+/* ---- Predictor-corrector sampling (ABI 12, additive; no reference counterpart): Langevin correctors in the path loop (Song et al.
+ * 2021; Du et al. 2023).  A corrector acts at the DEPARTURE level t_k of transition k, ahead of that transition's predictor call: it
+ * reads the same network-time word and row k of every term's table as the predictor does.  Level 0 never gets one (the decode follows
+ * it); level T (or t_start) does.  Transition k becomes
+ *     C times:  the network call with the launches the predictor's call gets (guidance, restraints, feature restraints, diversity),
+ *               then one Langevin step on z at level t_k (k_langevin_step);
+ *     then:     the predictor's own network call (+ the same terms, + a recorded data prediction) and the unchanged posterior step.
+ * The Langevin step, per molecule b on row k = {sigma_t, q_k, g_max_k}:
+ *     eps~ = eps^ with its x part freed of the mean over the valid nodes;  xi~ = normals, masked, the x part freed of its mean (both
+ *     as the posterior step forms them; the two means are double sums, rounded once);  n_xi^2 = sum xi~^2,  n_eps^2 = sum eps~^2
+ *     over the valid nodes and all D columns, of the deviations from the double means, summed in double in an order that depends on
+ *     (N, D) alone;
+ *     g_b = q_k (mode "fixed", adaptive = 0)   or   g_b = min(g_max_k, q_k n_xi^2 / n_eps^2) (mode "snr", adaptive = 1);
+ *     z' = (z - (g_b sigma_t) eps~) + (sigma_t sqrt(2 g_b)) xi~: both coefficients formed in double and rounded once to fp32, the
+ *     expression in fp32 in this order, the x part re-centred over the valid nodes
+ * - that is z + delta score + sqrt(2 delta) xi with score = -eps^ / sigma_t and delta = g_b sigma_t^2.  Masked rows are never written.
+ * A molecule keeps its bits (gain 0) when g_b == 0, when n_eps^2 is not greater than 0, when a norm or the gain is not finite, or when
+ * it has no valid node.  A row with q_k == 0 draws nothing and writes nothing.
+ * Noise: corrector step c of transition k draws on stream 1 + c of the loop's layout, draw = (T + 2) (1 + c) + (T - s_k), element
+ * index and sample id as in the posterior step: the predictor's draws do not move, a sample depends on its global id, mask, weights,
+ * schedule, path and C only, and chains cut into calls give the bits of the whole.  noise_rows == 1 shares one row.  Multistep rows
+ * keep their history: only the predictor reads and writes it.
+ * hd_set_corrector: rows3[K][3] = {sigma_t, q_k, g_max_k} (host) of the CURRENT path.  HD_E_INVALID unless sigma_t >= 0, q_k >= 0 and
+ *   finite, g_max_k > 0 (inf: no cap).
+ * hd_corrector_attach: from now on hd_sample_path / hd_sample_path_guided on this topology run C (1 .. HD_MAX_CORRECTORS) corrector
+ *   steps per transition.  Re-attaching the same C and mode with rows of the same size replays the cached graph; another C or mode
+ *   rebuilds it once.  The path loop then refuses, behind every older refusal: an inpainting call, steering attached at the same time,
+ *   mol_shape < N, injected noise - its K + 2 rows hold none for correctors - (HD_E_INVALID); rows not set for the current path
+ *   (HD_E_STATE).
+ * hd_corrector_detach: the launches, graphs and keys are again those of a topology that never had it.
+ * hd_corrector_read: the gains g_b of the last transition that ran into gains [C][B] doubles (host or device), stream-ordered.
+ * hd_langevin_step: the step once on given tensors with a host row3.  out may be z itself (in place), not a shifted overlap of it,
+ *   and may not overlap eps.  raw_x / raw_h [noise_rows][N][3] / [N][F]: injected normals, or both NULL for the generator at (seed,
+ *   sample_id_base + b, draw); noise_rows 1 (one shared row) or B.  gain_out: device [B] doubles or NULL. */
+#define HD_MAX_CORRECTORS 8
+int hd_set_corrector(hd_handle* h, int K, const float* rows3);
+int hd_corrector_attach(hd_topology* topo, int C, int adaptive, void* stream);
+int hd_corrector_detach(hd_topology* topo);
+int hd_corrector_read(hd_topology* topo, double* gains, void* stream);
+int hd_langevin_step(hd_handle* h, hd_topology* topo, const float* z, const float* eps, const float* row3, int adaptive,
+                     const float* raw_x, const float* raw_h, int noise_rows, uint64_t seed, uint64_t sample_id_base, uint32_t draw,
+                     float* out, double* gain_out, void* stream);
+
 /* ---- Scoring (ABI 12, additive; no reference counterpart beyond the one-timestep estimator, compute_loss with t0_always = True,
  * diffusion_qm9.py:530-699): the variational bound of GIVEN molecules with every term of a list evaluated, in the device loop.
  * For normalised data xh [B,N,D] and a term t in 1 .. T (s = t - 1):
