@@ -132,6 +132,7 @@ SIGNATURES = {
     "hd_topology_nodes_device": (C.c_int, [_VP, _VP, _VP]),
     "hd_edge_layer_forward": (C.c_int, [_VP, _VP, C.c_int] + [_FP] * 9 + [_VP]),
     "hd_edge_layer_backward": (C.c_int, [_VP, _VP, C.c_int] + [_FP] * 20 + [_VP]),
+    "hd_node_step": (C.c_int, [_VP, _VP, C.c_int] + [_FP] * 7 + [C.POINTER(C.c_int), _VP]),
     "hd_vlb_loss_forward": (C.c_int, [C.c_int] * 7 + [C.c_float] * 4 + [_FP] * 9 + [_VP]),
     "hd_vlb_loss_backward": (C.c_int, [C.c_int] * 7 + [C.c_float] * 4 + [_FP] * 11 + [_VP]),
     "hd_edge_prep": (C.c_int, [C.c_int, C.c_int, C.c_int] + [_FP] * 5 + [_VP]),

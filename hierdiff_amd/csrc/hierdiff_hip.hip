@@ -1304,6 +1304,122 @@ static bool launch_edge_ablated(hd_handle* h, const EdgeArgs& a, hipStream_t s) 
 extern "C" int hd_debug_edge_trace(hd_handle*, long long*, int) { return 0; }      // product build: nothing is traced
 #endif
 
+// ----------------------------------------------------------------------------- node side of a forward
+
+// fp16x3 where no node kernel leaves them: the row maxima {max |A_r|, max |B_r|} of the AB rows the next edge kernel reads, into
+// t->abmax (the forward below width 128, the training forward, hd_node_step)
+static void launch_ab_rowmax(const hd_handle* h, hd_topology* t, const float* ab, hipStream_t s) {
+    AbMaxArgs am{ab, t->abmax, t->M, h->H};
+    hipLaunchKernelGGL(k_ab_rowmax, dim3((t->M + 3) / 4), dim3(256), 0, s, am);
+}
+
+// The node side of ONE step on the forward's path, on the topology's own buffers (hbuf, part -> hbuf, dst): forward_impl runs it
+// after every GCL's edge kernel, hd_node_step runs it on a caller's rows.  The argument builders of the four paths:
+static NodeArgs node_args(const hd_handle* h, const hd_topology* t) {
+    NodeArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.h_in = t->hbuf; a.h_out = t->hbuf; a.part = t->part; a.pstart = t->pstart; a.nmask = t->nmask;
+    a.norm = agg_norm(h->cfg, t); a.M = t->M;
+    return a;
+}
+static void node_set_ab(const hd_handle* h, const hd_topology* t, NodeArgs& a, int q, const LayerW& nw, float* dst) {
+    const float* W = h->dw;
+    a.ABimg[q] = W + nw.ab_img; a.ABbias[q] = W + nw.ab_bias; a.ABout[q] = dst;
+    a.abinv[q] = h->node_mode == 3 ? 1.0f / nw.abs_ : 1.0f;
+    // fp16x3 at widths >= 128: the fused node kernel leaves the row maxima of what it writes (narrower widths: k_ab_rowmax)
+    a.ABmax[q] = (h->edge_mode == 3 && h->node_mode != 0) ? (dst == t->AB ? t->abmax : t->abmax2) : nullptr;
+}
+static R16Args node_r16_args(const hd_handle* h, const hd_topology* t) {
+    R16Args g;
+    std::memset(&g, 0, sizeof(g));
+    g.A = t->hbuf; g.lda = h->H; g.K1 = h->H; g.K = h->H; g.M = t->M; g.n_img = 1; g.nmask = t->nmask; g.norm = agg_norm(h->cfg, t);
+    return g;
+}
+static NodeSplitArgs node_split_args(const hd_handle* h, const hd_topology* t) {
+    NodeSplitArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.h_in = t->hbuf; a.h_out = t->hbuf; a.part = t->part; a.pstart = t->pstart; a.nmask = t->nmask; a.norm = agg_norm(h->cfg, t);
+    a.T = t->Tb; a.rowinfo = t->rowinfo; a.M = t->M; a.n_img = 1;
+    return a;
+}
+static void node_split_ab(const hd_handle* h, const hd_topology* t, NodeSplitArgs& a, int q, const LayerW& nw, float* dst) {
+    const float* W = h->dw;
+    a.Wimg[q] = W + nw.ab_img; a.bias[q] = W + nw.ab_bias; a.winv[q] = 1.0f / nw.abs_; a.ABout[q] = dst;
+    a.ABmax[q] = h->edge_mode == 3 ? (dst == t->AB ? t->abmax : t->abmax2) : nullptr;
+}
+
+// The layers whose first edge Linear follows the node update of GCL j of block i: the next sub-layer, or (after the block's last
+// GCL) the coordinate layer and the next block's first GCL.  Returns their number.
+static int node_step_next(const hd_handle* h, int i, int j, const LayerW* (&nxt)[2]) {
+    const int S = h->cfg.inv_sublayers;
+    nxt[0] = nxt[1] = nullptr;
+    if (j + 1 < S) { nxt[0] = &h->gcl[(size_t)i * S + j + 1]; return 1; }
+    nxt[0] = &h->coord[i];
+    if (i + 1 < h->cfg.n_layers) { nxt[1] = &h->gcl[(size_t)(i + 1) * S]; return 2; }
+    return 1;
+}
+
+// The node update of layer `w` + the first edge Linear of the nab layers `nxt` that follow, their AB into dst; w == nullptr: AB
+// only (the very first layer).  `path` is node_path(h, t->M).
+static int node_step(hd_handle* h, hd_topology* t, NodePath path, const LayerW* w, int nab, const LayerW* const* nxt,
+                     float* const* dst, hipStream_t s) {
+    const float* W = h->dw;
+    const int H = h->H;
+    if (path == NodePath::Split) {
+        NodeSplitArgs a = node_split_args(h, t);
+        if (w) { a.w3l1 = w->w3l1; a.w4l1 = w->w4l1; a.b3max = w->b3max; a.b4max = w->b4max; }
+        NodeSplitArgs p3 = a;
+        p3.n_img = nab; p3.upd = w ? 1 : 0;         // (AB only: the row maxima start from the zeros k_node_init left)
+        for (int q = 0; q < nab; ++q) node_split_ab(h, t, p3, q, *nxt[q], dst[q]);
+        if (w) {
+            NodeSplitArgs p1 = a, p2 = a;
+            p1.Wimg[0] = W + w->w3_img; p1.bias[0] = W + w->b3; p1.winv[0] = 1.0f / w->w3s;
+            HD_TRY(node_split(h, false, 1, p1, s));
+            p2.Wimg[0] = W + w->w4_img; p2.bias[0] = W + w->b4; p2.winv[0] = 1.0f / w->w4s;
+            for (int q = 0; q < nab; ++q) p2.zero_max[q] = p3.ABmax[q];
+            HD_TRY(node_split(h, false, 2, p2, s));
+        }
+        return node_split(h, false, 3, p3, s);
+    }
+    if (path == NodePath::SplitF32) {
+        if (w) {
+            NodeSplitArgs p1 = node_split_args(h, t), p2 = node_split_args(h, t);
+            p1.Wimg[0] = W + w->w3_img; p1.bias[0] = W + w->b3;
+            HD_TRY(node_split(h, true, 1, p1, s));
+            p2.Wimg[0] = W + w->w4_img; p2.bias[0] = W + w->b4;
+            HD_TRY(node_split(h, true, 2, p2, s));
+        }
+        NodeSplitArgs p3 = node_split_args(h, t);
+        p3.n_img = nab; p3.upd = w ? 1 : 0;
+        for (int q = 0; q < nab; ++q) { p3.Wimg[q] = W + nxt[q]->ab_img; p3.bias[q] = W + nxt[q]->ab_bias; p3.ABout[q] = dst[q]; }
+        return node_split(h, true, 3, p3, s);
+    }
+    if (path == NodePath::Fused) {
+        NodeArgs a = node_args(h, t);
+        if (w) {
+            a.W3img = W + w->w3_img; a.b3 = W + w->b3; a.W4img = W + w->w4_img; a.b4 = W + w->b4;
+            if (h->node_mode == 3) {
+                a.w3inv = 1.0f / w->w3s; a.w4inv = 1.0f / w->w4s; a.w3l1 = w->w3l1; a.w4l1 = w->w4l1; a.b3max = w->b3max; a.b4max = w->b4max;
+            }
+        }
+        for (int q = 0; q < nab; ++q) node_set_ab(h, t, a, q, *nxt[q], dst[q]);
+        return node_update(h, w != nullptr, nab, a, s);
+    }
+    if (w) {
+        R16Args g = node_r16_args(h, t);
+        g.part = t->part; g.pstart = t->pstart; g.K1 = H; g.K = 2 * H; g.Nc = H;
+        g.Bimg[0] = W + w->w3_gimg; g.bias[0] = W + w->b3; g.C[0] = t->Tb; g.ldc = H;
+        HD_TRY(gemm_r16(h, EPI_BIAS_SILU, true, g, s));              // T = silu([h | agg] W3^T + b3)
+        g = node_r16_args(h, t);
+        g.A = t->Tb; g.Bimg[0] = W + w->w4_gimg; g.bias[0] = W + w->b4; g.C[0] = t->hbuf; g.ldc = H; g.Nc = H;
+        HD_TRY(gemm_r16(h, EPI_RESID_MASK, false, g, s));            // h = (h + T W4^T + b4) mask
+    }
+    R16Args g = node_r16_args(h, t);                                 // AB_q = h [W1a | W1b]_q^T + [b1 | 0]
+    g.Nc = 2 * H; g.ldc = 2 * H; g.n_img = nab;
+    for (int q = 0; q < nab; ++q) { g.Bimg[q] = W + nxt[q]->ab_gimg; g.bias[q] = W + nxt[q]->ab_bias; g.C[q] = dst[q]; }
+    return gemm_r16(h, EPI_BIAS, false, g, s);
+}
+
 // ----------------------------------------------------------------------------- forward
 
 static int forward_impl(hd_handle* h, hd_topology* t, const float* xh, const float* tt, int t_numel,
@@ -1329,101 +1445,13 @@ static int forward_impl(hd_handle* h, hd_topology* t, const float* xh, const flo
             hipLaunchKernelGGL(k_node_init, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
         }
         const float range = c.coords_range / (float)c.n_layers;
-        const int S = c.inv_sublayers;
         // AB of the layer about to run is produced by the previous node update (or, for the very first layer, by an
         // AB-only launch); `ab_cur` is the buffer the next edge kernel reads
         const float* ab_cur = t->AB;
-        auto node_args = [&]() {
-            NodeArgs a;
-            std::memset(&a, 0, sizeof(a));
-            a.h_in = t->hbuf; a.h_out = t->hbuf; a.part = t->part; a.pstart = t->pstart; a.nmask = t->nmask;
-            a.norm = agg_norm(c, t); a.M = M;
-            return a;
-        };
-        auto set_ab = [&](NodeArgs& a, int q, const LayerW& nw, float* dst) {
-            a.ABimg[q] = W + nw.ab_img; a.ABbias[q] = W + nw.ab_bias; a.ABout[q] = dst;
-            a.abinv[q] = h->node_mode == 3 ? 1.0f / nw.abs_ : 1.0f;
-            // fp16x3 at widths >= 128: the fused node kernel leaves the row maxima of what it writes (narrower widths: k_ab_rowmax)
-            a.ABmax[q] = (h->edge_mode == 3 && h->node_mode != 0) ? (dst == t->AB ? t->abmax : t->abmax2) : nullptr;
-        };
-        auto r16_args = [&]() {
-            R16Args g;
-            std::memset(&g, 0, sizeof(g));
-            g.A = t->hbuf; g.lda = H; g.K1 = H; g.K = H; g.M = M; g.n_img = 1; g.nmask = t->nmask; g.norm = agg_norm(c, t);
-            return g;
-        };
-        auto split_args = [&]() {
-            NodeSplitArgs a;
-            std::memset(&a, 0, sizeof(a));
-            a.h_in = t->hbuf; a.h_out = t->hbuf; a.part = t->part; a.pstart = t->pstart; a.nmask = t->nmask; a.norm = agg_norm(c, t);
-            a.T = t->Tb; a.rowinfo = t->rowinfo; a.M = M; a.n_img = 1;
-            return a;
-        };
-        auto split_ab = [&](NodeSplitArgs& a, int q, const LayerW& nw, float* dst) {
-            a.Wimg[q] = W + nw.ab_img; a.bias[q] = W + nw.ab_bias; a.winv[q] = 1.0f / nw.abs_; a.ABout[q] = dst;
-            a.ABmax[q] = h->edge_mode == 3 ? (dst == t->AB ? t->abmax : t->abmax2) : nullptr;
-        };
-        // The node side on the forward's path: the node update of layer `w` + the first edge Linear of the nab layers `nxt` that
-        // follow, their AB into dst; w == nullptr: AB only (the very first layer)
-        auto node_step = [&](const LayerW* w, int nab, const LayerW* const* nxt, float* const* dst) -> int {
-            if (path == NodePath::Split) {
-                NodeSplitArgs a = split_args();
-                if (w) { a.w3l1 = w->w3l1; a.w4l1 = w->w4l1; a.b3max = w->b3max; a.b4max = w->b4max; }
-                NodeSplitArgs p3 = a;
-                p3.n_img = nab; p3.upd = w ? 1 : 0;         // (AB only: the row maxima start from the zeros k_node_init left)
-                for (int q = 0; q < nab; ++q) split_ab(p3, q, *nxt[q], dst[q]);
-                if (w) {
-                    NodeSplitArgs p1 = a, p2 = a;
-                    p1.Wimg[0] = W + w->w3_img; p1.bias[0] = W + w->b3; p1.winv[0] = 1.0f / w->w3s;
-                    HD_TRY(node_split(h, false, 1, p1, s));
-                    p2.Wimg[0] = W + w->w4_img; p2.bias[0] = W + w->b4; p2.winv[0] = 1.0f / w->w4s;
-                    for (int q = 0; q < nab; ++q) p2.zero_max[q] = p3.ABmax[q];
-                    HD_TRY(node_split(h, false, 2, p2, s));
-                }
-                return node_split(h, false, 3, p3, s);
-            }
-            if (path == NodePath::SplitF32) {
-                if (w) {
-                    NodeSplitArgs p1 = split_args(), p2 = split_args();
-                    p1.Wimg[0] = W + w->w3_img; p1.bias[0] = W + w->b3;
-                    HD_TRY(node_split(h, true, 1, p1, s));
-                    p2.Wimg[0] = W + w->w4_img; p2.bias[0] = W + w->b4;
-                    HD_TRY(node_split(h, true, 2, p2, s));
-                }
-                NodeSplitArgs p3 = split_args();
-                p3.n_img = nab; p3.upd = w ? 1 : 0;
-                for (int q = 0; q < nab; ++q) { p3.Wimg[q] = W + nxt[q]->ab_img; p3.bias[q] = W + nxt[q]->ab_bias; p3.ABout[q] = dst[q]; }
-                return node_split(h, true, 3, p3, s);
-            }
-            if (path == NodePath::Fused) {
-                NodeArgs a = node_args();
-                if (w) {
-                    a.W3img = W + w->w3_img; a.b3 = W + w->b3; a.W4img = W + w->w4_img; a.b4 = W + w->b4;
-                    if (h->node_mode == 3) {
-                        a.w3inv = 1.0f / w->w3s; a.w4inv = 1.0f / w->w4s; a.w3l1 = w->w3l1; a.w4l1 = w->w4l1; a.b3max = w->b3max; a.b4max = w->b4max;
-                    }
-                }
-                for (int q = 0; q < nab; ++q) set_ab(a, q, *nxt[q], dst[q]);
-                return node_update(h, w != nullptr, nab, a, s);
-            }
-            if (w) {
-                R16Args g = r16_args();
-                g.part = t->part; g.pstart = t->pstart; g.K1 = H; g.K = 2 * H; g.Nc = H;
-                g.Bimg[0] = W + w->w3_gimg; g.bias[0] = W + w->b3; g.C[0] = t->Tb; g.ldc = H;
-                HD_TRY(gemm_r16(h, EPI_BIAS_SILU, true, g, s));              // T = silu([h | agg] W3^T + b3)
-                g = r16_args();
-                g.A = t->Tb; g.Bimg[0] = W + w->w4_gimg; g.bias[0] = W + w->b4; g.C[0] = t->hbuf; g.ldc = H; g.Nc = H;
-                HD_TRY(gemm_r16(h, EPI_RESID_MASK, false, g, s));            // h = (h + T W4^T + b4) mask
-            }
-            R16Args g = r16_args();                                          // AB_q = h [W1a | W1b]_q^T + [b1 | 0]
-            g.Nc = 2 * H; g.ldc = 2 * H; g.n_img = nab;
-            for (int q = 0; q < nab; ++q) { g.Bimg[q] = W + nxt[q]->ab_gimg; g.bias[q] = W + nxt[q]->ab_bias; g.C[q] = dst[q]; }
-            return gemm_r16(h, EPI_BIAS, false, g, s);
-        };
         {
             const LayerW* first[2] = {&h->gcl[0], nullptr};
             float* dst[2] = {t->AB, nullptr};
-            HD_TRY(node_step(nullptr, 1, first, dst));
+            HD_TRY(node_step(h, t, path, nullptr, 1, first, dst, s));
         }
         for (int i = 0; i < c.n_layers; ++i) {
             for (int j = 0; j <= c.inv_sublayers; ++j) {
@@ -1437,8 +1465,7 @@ static int forward_impl(hd_handle* h, hd_topology* t, const float* xh, const flo
                 e.abmax = (fused_max && ab_cur == t->AB2) ? t->abmax2 : t->abmax;
                 if (h->edge_mode == 3 && !fused_max) {  // fp16x3: the per-node part of the activation bound (k_edge.hpp)
                     ProfScope ps(h, s, 2);
-                    AbMaxArgs am{ab_cur, t->abmax, M, H};
-                    hipLaunchKernelGGL(k_ab_rowmax, dim3((M + 3) / 4), dim3(256), 0, s, am);
+                    launch_ab_rowmax(h, t, ab_cur, s);
                 }
                 e.ei = t->ei; e.ej = t->ej; e.eseg = t->eseg; e.seg_part = t->seg_part; e.tile_nseg = t->tile_nseg;
                 e.xcur = t->xcur; e.x0 = t->x0; e.part = coord ? t->xpart : t->part; e.ba = w.ba;
@@ -1448,16 +1475,10 @@ static int forward_impl(hd_handle* h, hd_topology* t, const float* xh, const flo
                 if (!coord) {
                     // node update + the first edge Linear of the layer(s) that follow: AB of the next sub-layer, or (after the
                     // block's last GCL) of the coordinate layer and of the next block's first GCL
-                    const LayerW* nxt[2] = {nullptr, nullptr};
+                    const LayerW* nxt[2];
                     float* dst[2] = {t->AB, t->AB2};
-                    int nab = 1;
-                    if (j + 1 < S) {
-                        nxt[0] = &h->gcl[(size_t)i * S + j + 1];
-                    } else {
-                        nxt[0] = &h->coord[i];
-                        if (i + 1 < c.n_layers) { nxt[1] = &h->gcl[(size_t)(i + 1) * S]; nab = 2; }
-                    }
-                    HD_TRY(node_step(&w, nab, nxt, dst));
+                    const int nab = node_step_next(h, i, j, nxt);
+                    HD_TRY(node_step(h, t, path, &w, nab, nxt, dst, s));
                     ab_cur = t->AB;
                 } else {
                     ProfScope ps(h, s, 2);
@@ -1507,6 +1528,52 @@ extern "C" int hd_egnn_forward(hd_handle* h, hd_topology* topo, const float* xh,
     HIP_TRY(hipSetDevice(h->device));
     topo_use(topo, (hipStream_t)stream);
     return forward_impl(h, topo, xh, t, t_numel, context, mol_shape, out, (hipStream_t)stream);
+}
+
+// One node step of the forward on a caller's rows (test and diagnosis primitive, include/hierdiff_hip.h): the inputs go into the
+// topology's own buffers, node_step - the function forward_impl calls - runs on them, the results are copied out.
+extern "C" int hd_node_step(hd_handle* h, hd_topology* topo, int layer, const float* h_in, const float* part,
+                            float* h_out, float* ab0, float* ab1, float* abmax0, float* abmax1, int* path, void* stream) {
+    HD_TRY(check_ready(h, topo, "hd_node_step"));
+    const hd_config& c = h->cfg;
+    const int S = c.inv_sublayers;
+    if (layer < -1 || layer >= c.n_layers * S) return fail(HD_E_INVALID, "hd_node_step: layer out of range (-1: AB only, else a GCL i * inv_sublayers + j)");
+    if (!h_in || !h_out || !ab0 || !path) return fail(HD_E_INVALID, "hd_node_step: null tensor");
+    hd_topology* t = topo;
+    if (layer >= 0 && !part && t->n_parts > 0) return fail(HD_E_INVALID, "hd_node_step: null tensor (part is required with layer >= 0)");
+    const LayerW* nxt[2] = {&h->gcl[0], nullptr};
+    const int nab = layer < 0 ? 1 : node_step_next(h, layer / S, layer % S, nxt);
+    if (nab == 2 && !ab1) return fail(HD_E_INVALID, "hd_node_step: ab1 missing (this step writes two AB images)");
+    if (h->edge_mode == 0 && (abmax0 || abmax1))
+        return fail(HD_E_INVALID, "hd_node_step: abmax given in precision 0 (exact fp32 keeps no row maxima)");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    topo_use(t, s);
+    const int H = h->H, M = t->M;
+    const NodePath np = node_path(h, M);
+    *path = (int)np;
+    if (M == 0) return HD_OK;
+    const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
+    HIP_TRY(hipMemcpyAsync(t->hbuf, h_in, (size_t)M * H * sizeof(float), dd, s));
+    if (layer >= 0 && t->n_parts > 0) HIP_TRY(hipMemcpyAsync(t->part, part, (size_t)t->n_parts * H * sizeof(float), dd, s));
+    // what the AB-only launch of the split chain expects of k_node_init: row maxima that start from zero (forward_impl; k_node_init
+    // itself cannot run here - it writes hbuf from the network input - so the same M rows of t->abmax are cleared by a memset)
+    if (layer < 0 && np == NodePath::Split && h->edge_mode == 3) HIP_TRY(hipMemsetAsync(t->abmax, 0, (size_t)M * 2 * sizeof(float), s));
+    float* dst[2] = {t->AB, nab == 2 ? t->AB2 : nullptr};
+    HD_TRY(node_step(h, t, np, layer < 0 ? nullptr : &h->gcl[layer], nab, nxt, dst, s));
+    float* ab[2] = {ab0, ab1};
+    float* abmax[2] = {abmax0, abmax1};
+    const bool fused_max = h->edge_mode == 3 && h->node_mode != 0;
+    for (int q = 0; q < nab; ++q) {
+        HIP_TRY(hipMemcpyAsync(ab[q], dst[q], (size_t)M * 2 * H * sizeof(float), dd, s));
+        if (!abmax[q]) continue;
+        // fp16x3 below width 128: the launch the forward puts in front of the edge kernel that reads dst[q]
+        if (!fused_max) launch_ab_rowmax(h, t, dst[q], s);
+        HIP_TRY(hipMemcpyAsync(abmax[q], (fused_max && q == 1) ? t->abmax2 : t->abmax, (size_t)M * 2 * sizeof(float), dd, s));
+    }
+    HIP_TRY(hipMemcpyAsync(h_out, t->hbuf, (size_t)M * H * sizeof(float), dd, s));
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
 }
 
 extern "C" int hd_nan_events(hd_handle* h, void* stream, long long* count) {
@@ -1579,8 +1646,7 @@ extern "C" int hd_edge_layer_forward_s(hd_handle* h, hd_topology* t, int coord, 
         hipLaunchKernelGGL(k_f16_prep, dim3(1), dim3(1024), 0, s, W2, wrd, scal, H);
         hipLaunchKernelGGL((k_pack_w2_f16<false>), dim3((H * H / 8 + 255) / 256), dim3(256), 0, s, W2, (const float*)scal,
                            reinterpret_cast<f16x8*>(t->w2img), H);
-        AbMaxArgs am{AB, t->abmax, M, H};
-        hipLaunchKernelGGL(k_ab_rowmax, dim3((M + 3) / 4), dim3(256), 0, s, am);
+        launch_ab_rowmax(h, t, AB, s);
         e.dscal = scal; e.abmax = t->abmax;
     } else hipLaunchKernelGGL((k_pack_w2<false>), dim3((H * H + 255) / 256), dim3(256), 0, s, W2, t->w2img, H);
     e.AB = AB; e.wrd = wrd; e.W2img = t->w2img; e.b2 = b2; e.wa = wa;

@@ -857,6 +857,30 @@ int hd_edge_layer_backward(hd_handle* h, hd_topology* topo, int coord, const flo
                            const float* ba, const float* gout, float* G2, float* P, float* G1, float* escal, float* colpart,
                            float* bapart, float* b2part, float* wrdpart, float* dAB, float* dx, float* dx0, void* stream);
 
+/* ---- One node step of the forward on its own (ABI 12, additive): a test and diagnosis primitive, nothing on the hot path calls it.
+ * The node side of hd_egnn_forward between two edge kernels, run by the function the forward itself calls, in the handle's precision
+ * mode and on the path the forward takes at this topology's size:
+ *     agg_i = (sum of the node's rows of `part`, pstart[i] ... pstart[i + 1] - 1) / normalization_factor   (N with 'mean')
+ *     T = SiLU([h | agg] W3^T + b3),   h' = (h + T W4^T + b4) * node_mask,   AB_q = h' [W1a_q | W1b_q]^T + [b1_q | 0]
+ * layer == -1: the AB-only step after the embedding (h' = h; AB of GCL 0; `part` may be NULL).  0 <= layer < n_layers *
+ * inv_sublayers: the update with the node model of GCL layer = i * inv_sublayers + j, and the AB of what follows it in the forward:
+ * the next sub-layer (j + 1 < inv_sublayers), else the block's coordinate layer (ab0) and - for i + 1 < n_layers - the next block's
+ * first GCL (ab1): ab1 is required exactly when the step writes two images.
+ * All pointers are DEVICE pointers, rows in the topology's compact node order (hd_topology_nodes), M = active nodes:
+ * h_in, h_out [M][H] (may be the same pointer), part [parts][H] (parts = info6[5] of hd_topology_info, a node's range from the pstart
+ * of hd_topology_layout), ab0, ab1 [M][2H], abmax0, abmax1 [M][2] or NULL: {max_k |A_r[k]|, max_k |B_r[k]|}, the row maxima the
+ * next edge kernel of this handle would read - the node kernels' own where they write them, k_ab_rowmax's where the forward
+ * launches that (precision 3 below width 128); a handle of precision 0 keeps none and refuses the pointer.
+ * A handle of precision 3 runs its edge model in the domain scaled by c = -log2(e) (hd_set_weights folds c into the packed weights,
+ * one rounding per weight): there `part` is what its edge kernels leave, c x the neighbour sums, and ab* / abmax* are c x the AB above,
+ * what its edge kernels read; h_in and h_out are unscaled in every precision.
+ * The call copies h_in and part into the topology's buffers in stream order, runs the step and copies the results out; *path
+ * (host) receives the path taken: 0 three-launch fp16x3 chain, 1 three-launch fp32 chain, 2 fused kernel, 3 the 16-row GEMM chain.
+ * HD_E_INVALID (and no launch): null handle, topology or tensor, layer out of range, a topology of another handle, ab1 missing,
+ * abmax given in precision 0; HD_E_STATE: weights not set (tests/test_gpu_node_step.py). */
+int hd_node_step(hd_handle* h, hd_topology* topo, int layer, const float* h_in, const float* part, float* h_out,
+                 float* ab0, float* ab1, float* abmax0, float* abmax1, int* path, void* stream);
+
 /* ---- Stage-2 layer: E_GCL forward (/root/reference/models/egnn/gcl.py:9-205), exact fp32.
  * The layer of the edge-denoise / refine models: messages from [h_row; h_col; radial; edge_attr; context], optional
  * attention gate, coordinate update and node update aggregated over the RECEIVING index `col`, optional update of the

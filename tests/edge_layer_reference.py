@@ -61,8 +61,9 @@ def err(got, ref) -> float:
     return float((d[~zero] / s[~zero]).max()) if (~zero).any() else 0.0
 
 
-def bar(family: str, err32: float) -> float:
-    return MARGINS[family] * max(err32, YARDSTICK_FLOOR)
+def bar(family: str, err32: float, margins: Optional[Dict[str, float]] = None) -> float:
+    """margins: another harness's table of families (tests/node_step_reference.py); default: MARGINS above."""
+    return (MARGINS if margins is None else margins)[family] * max(err32, YARDSTICK_FLOOR)
 
 
 # ----------------------------------------------------------------------------- the topology's tables (host only)
